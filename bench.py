@@ -14,18 +14,23 @@ scene-windows per GPU, fp32; synthetic trajectories per SURVEY 8d (random-walk r
 complete_nuscenes_setup.py:264-286), random-init weights (torch.manual_seed(0)).  `--dataset eth-train --batch 512` is
 BASELINE configs[1] on the real (ragged) eth/train windows that travel with the repo as a test fixture.
 
-Timing: W warm-up steps, then R blocks of EXACTLY K steps, each block bracketed by barrier + torch.cuda.synchronize()
-on both sides (MAX over ranks); `ms_per_step` / `value` are the MEDIAN block, p10 / p90 ride along (R is chosen so the
-timed region lasts >= 1 s).  Two different input batches alternate from step to step.
+Timing: W warm-up steps, then R blocks (--repeats, default 1) of EXACTLY K steps, each block bracketed by barrier +
+torch.cuda.synchronize() on both sides (MAX over ranks); `ms_per_step` / `value` are the MEDIAN block.  Two different
+input batches alternate from step to step.  `--dump-outputs DIR` then writes what the last timed step returned (see
+dump_outputs); the inputs and the initial weights are seeded, so two builds run with the same arguments compare output for
+output.
 
-Rank 0 prints ONE JSON line; besides the contract fields it carries
+A plain run stops there and rank 0 prints ONE JSON line.  With `--full` the run goes on, and the line also carries
+  timing       p10 / p90 / median over further blocks of K steps, until there are >= 30 blocks lasting >= 1 s
+               (unless --repeats sets the number of blocks),
   roofline     the DOMINANT SINGLE KERNEL of the step: algorithmic FLOP per launch / its mean duration, measured live
                with HIP events the library records between its kernels on the launch stream (`composite` = the whole
                backward entry point as last round),
   pipeline     the same step with the adjacency build (utils.seq_to_graph as a HIP kernel) inside the graph,
   kernels      stand-alone HBM kernels on a working set beyond the 256 MiB Infinity Cache,
   cpu_baseline the CPU oracle run the way the reference runs (one scene per forward, N = 1) on a bounded sample of the
-               same workload: 1 thread, plus `cpu_baseline_all_cores` (one single-threaded worker per core).
+               same workload: 1 thread, plus `cpu_baseline_all_cores` (one single-threaded worker per core),
+  epoch        (--dataset eth-train / all-train) reference-style epochs from the device-resident dataset.
 """
 import argparse
 import json
@@ -48,7 +53,14 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--repeats", type=int, default=0, help="timed blocks of --steps steps (0: >= 30 and >= 1 s)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed blocks of --steps steps (default 1; ms_per_step: the median block)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also the spread over >= 30 blocks (without --repeats) and the roofline / "
+                         "pipeline / epoch / HBM-kernel / CPU-baseline legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (loss, per-scene losses, V_pred, updated model state) "
+                         "as DIR/<name>.npy")
     ap.add_argument("--batch", type=int, default=2048, help="scene-windows per GPU")
     ap.add_argument("--peds", type=int, default=32, help="pedestrians per scene-window (V)")
     ap.add_argument("--ragged", choices=("shuffled", "sorted"), default=None,
@@ -75,7 +87,10 @@ def parse_args(argv=None):
                     help="seconds the self-launched ranks of --gpus N may take before the parent stops them")
     ap.add_argument("--cpu-worker", type=int, default=-1, help=argparse.SUPPRESS)
     ap.add_argument("--probe-fds", action="store_true", help=argparse.SUPPRESS)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or (args.repeats is not None and args.repeats < 1) or args.warmup < 0:
+        ap.error("--steps and --repeats must be >= 1, --warmup >= 0")
+    return args
 
 
 # ------------------------------------------------------------------------------------------
@@ -263,6 +278,35 @@ def time_kernel(torch, fn, iters=10, warm=2):
     b.record()
     torch.cuda.synchronize()
     return a.elapsed_time(b) / iters
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(path, step_out, model):
+    """What the last timed step handed its caller, as DIR/<name>.npy: `loss` (the reported weighted loss),
+    `scene_losses` (N,), `v_pred` (N,5,P,V) and `state.<key>` for every entry of the updated state_dict -- float32,
+    integer buffers as float64.  When everything would exceed 64 MB, `v_pred` holds a fixed seeded sample of the scenes
+    and `v_pred_scenes` their indices."""
+    import numpy as np
+    total, losses, y = step_out
+
+    def host(t):
+        t = t.detach()
+        return (t.float() if t.is_floating_point() else t.double()).cpu().numpy()
+    arrays = {"loss": host(total), "scene_losses": host(losses)}
+    arrays.update(("state." + k, host(t)) for k, t in model.state_dict().items())
+    v_pred = host(y)
+    room = DUMP_LIMIT_BYTES - (64 << 10) - sum(a.nbytes for a in arrays.values())     # (64 KB for the .npy headers)
+    if v_pred.nbytes > room:
+        keep = max(1, room // (v_pred[0].nbytes + 8))
+        idx = np.sort(np.random.default_rng(0).choice(v_pred.shape[0], keep, replace=False))
+        v_pred = v_pred[idx]
+        arrays["v_pred_scenes"] = idx.astype(np.float64)
+    arrays["v_pred"] = v_pred
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
 
 
 # ------------------------------------------------------------------------------------------
@@ -478,8 +522,9 @@ def main():
         if world > 1:
             dist.barrier()
         t0 = time.perf_counter()
+        last = None
         for i in range(k):
-            fns[i % len(fns)]()
+            last = fns[i % len(fns)]()
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -488,19 +533,27 @@ def main():
             tt = torch.tensor([dt], device=dev, dtype=torch.float64)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
-        return dt
+        return dt, last
 
     for i in range(args.warmup):
         steps[i % len(steps)]()
-    first = run_block(steps, args.steps)
-    repeats = args.repeats if args.repeats > 0 else max(30, int(1.0 / max(first, 1e-6)) + 1)
-    if world > 1:                                   # every rank must run the same number of blocks
-        rr = torch.tensor([repeats], device=dev, dtype=torch.int64)
-        dist.all_reduce(rr, op=dist.ReduceOp.MAX)
-        repeats = int(rr.item())
-    blocks = [first] + [run_block(steps, args.steps) for _ in range(repeats - 1)]
+    blocks = []
+    for _ in range(args.repeats or 1):
+        dt, last_out = run_block(steps, args.steps)
+        blocks.append(dt)
+    ms_step = float(np.median(blocks)) / args.steps * 1e3
+    first = blocks[0]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_out, model)
+    if args.full and args.repeats is None:
+        # the spread: further blocks of --steps steps until there are >= 30 and they last >= 1 s
+        repeats = max(30, int(1.0 / max(first, 1e-6)) + 1)
+        if world > 1:                               # every rank must run the same number of blocks
+            rr = torch.tensor([repeats], device=dev, dtype=torch.int64)
+            dist.all_reduce(rr, op=dist.ReduceOp.MAX)
+            repeats = int(rr.item())
+        blocks += [run_block(steps, args.steps)[0] for _ in range(repeats - len(blocks))]
     per_step = np.sort(np.asarray(blocks) / args.steps * 1e3)
-    ms_step = float(np.median(per_step))
     p10, p90 = float(np.percentile(per_step, 10)), float(np.percentile(per_step, 90))
 
     out = None
@@ -531,7 +584,8 @@ def main():
             "vs_baseline": None, "dtype": "f32" if args.dtype == "f32" else "bf16-storage (fp32 accumulate, fp32 parameters)",
             "data": ("real (%s)" % args.dataset) if real else "synthetic",
             "launch": "eager" if args.no_graph else "hipGraph replay",
-            "timing": {"blocks": len(blocks), "steps_per_block": args.steps, "ms_per_step_median": ms_step,
+            "timing": {"blocks": len(blocks), "steps_per_block": args.steps,
+                       "ms_per_step_median": float(np.median(per_step)),
                        "ms_per_step_p10": p10, "ms_per_step_p90": p90, "ms_per_step_first_block": first / args.steps * 1e3,
                        "timed_region_s": float(np.sum(blocks)), "input_batches_rotated": len(steps)},
             "config": {"workload": workload, "global_batch": n * world,
@@ -542,7 +596,7 @@ def main():
         }
 
     # ---- per-kernel device time (HIP events the library records between its kernels) -> roofline ----------------
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         model.timer = ops.KernelTimer()
         for i in range(max(4, min(args.steps, 20))):
             eager(dsets[i % len(dsets)])()
@@ -612,7 +666,7 @@ def main():
                       for d in dsets]
             for i in range(4):
                 psteps[i % len(psteps)]()
-            pb = np.sort([run_block(psteps, args.steps) for _ in range(max(5, repeats // 4))]) / args.steps * 1e3
+            pb = np.sort([run_block(psteps, args.steps)[0] for _ in range(max(5, len(blocks) // 4))]) / args.steps * 1e3
             if rank == 0:
                 out["pipeline"] = {"what": "the same step with utils.seq_to_graph (adj_build kernel) inside the captured "
                                            "graph: relative trajectories in, updated weights out",
@@ -620,7 +674,7 @@ def main():
                                    "unit": "scene-windows/s"}
 
     # ---- real-data epochs from the device-resident dataset (N1): gather by device index inside the captured step ----
-    if real and not args.no_extras and not args.kernels_only and not args.no_graph and world == 1:
+    if real and args.full and not args.no_extras and not args.kernels_only and not args.no_graph and world == 1:
         from social_stgcnn_amd.dataset import DeviceWindows, EpochRunner
         win = real_windows(args.dataset)
         ds = DeviceWindows(win, dev)
@@ -648,7 +702,7 @@ def main():
                         "last_epoch_loss": float(last)}
 
     # ---- stand-alone HBM kernels on a working set beyond the Infinity Cache (rank 0) --------------------------------
-    if rank == 0 and not args.no_extras and not args.kernels_only:
+    if rank == 0 and args.full and not args.no_extras and not args.kernels_only:
         vb = 32
         nb = 16384                                            # adjacency: 16384 x 8 x 32 x 32 x 4 B = 537 MB > 256 MiB
         rel_b, _ = synth_scenes(256, vb, 7)
@@ -675,7 +729,7 @@ def main():
         torch.cuda.empty_cache()
 
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             counts0 = sets[0][2]
             one, many = cpu_baselines(dsets[0]["v"] if counts0 is None else int(np.mean(counts0) + 0.5), args.cpu_seconds)
             out["cpu_baseline"] = one

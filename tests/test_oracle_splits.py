@@ -99,7 +99,7 @@ def test_oracle_reproduces_the_reference_eth_train_epoch():
 
 
 # windows / pedestrians / largest crowd of all 15 split directories, measured with the reference's TrajectoryDataset
-# (SURVEY 8d): the known answers of the ingest.  The full dataset only exists next to the reference (build container).
+# (SURVEY 8d): the known answers of the ingest.
 ALL_COUNTS = {"eth": ((2785, 29809, 57), (660, 5349, 42), (70, 181, 5)),
               "hotel": ((2594, 29152, 57), (621, 5136, 42), (301, 1053, 8)),
               "univ": ((2076, 9231, 14), (530, 2708, 13), (947, 24334, 57)),
@@ -107,11 +107,53 @@ ALL_COUNTS = {"eth": ((2785, 29809, 57), (660, 5349, 42), (70, 181, 5)),
               "zara2": ((2112, 25507, 57), (501, 4173, 42), (921, 5833, 14))}
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/datasets"), reason="full ETH/UCY tree only in the build container")
+def _val_recordings(out):
+    """The eight *_val.txt recordings, written to `out`.  Each is the rest of its recording after the *_train.txt part,
+    row for row.  Six recordings are committed whole as test scenes (data/<split>_test); the val parts of the other two
+    (crowds_zara03, uni_examples) are the rows stored in val_parts.npz."""
+    gd = os.path.join(GOLDEN, "data")
+    stored = load_golden("val_parts.npz")
+    out.mkdir()
+    for rec in data.TRAIN_RECORDINGS:
+        base = rec[:-len("_train.txt")]
+        if base in stored.files:
+            rows = stored[base]
+        else:
+            whole = data.read_file(os.path.join(gd, next(d for d in os.listdir(gd) if os.path.exists(
+                os.path.join(gd, d, base + ".txt"))), base + ".txt"))
+            train = data.read_file(os.path.join(gd, "train_extra" if base == "biwi_eth" else "eth_train", rec))
+            assert np.array_equal(whole[:len(train)], train), base
+            rows = whole[len(train):]
+        (out / (base + "_val.txt")).write_text("".join("\t".join(repr(float(x)) for x in r) + "\n" for r in rows))
+    return {f: str(out / f) for f in os.listdir(out)}
+
+
+def _split_directory(tmp_path, name, part):
+    """datasets/<name>/<part> rebuilt from the recordings committed under tests/golden: the leave-one-out train and val
+    directories hold the *_train.txt / *_val.txt parts of the recordings that are not the split's test scene
+    (data/eth_train + data/train_extra, _val_recordings), the test directory is data/<name>_test."""
+    gd = os.path.join(GOLDEN, "data")
+    if part == "test":
+        return os.path.join(gd, name + "_test")
+    if part == "train":
+        where = {}
+        for d in (os.path.join(gd, "eth_train"), os.path.join(gd, "train_extra")):
+            where.update((f, os.path.join(d, f)) for f in os.listdir(d))
+    else:
+        where = _val_recordings(tmp_path / name / "val_recordings")
+    out = tmp_path / name / part
+    out.mkdir(parents=True)
+    for rec in data.TRAIN_RECORDINGS:
+        if rec not in data.TRAIN_LEFT_OUT[name]:
+            f = rec.replace("_train.txt", "_%s.txt" % part)
+            os.symlink(where[f], out / f)
+    return str(out)
+
+
 @pytest.mark.parametrize("name", sorted(ALL_COUNTS))
-def test_ingest_counts_of_all_fifteen_split_directories(name):
+def test_ingest_counts_of_all_fifteen_split_directories(name, tmp_path):
     for part, want in zip(("train", "val", "test"), ALL_COUNTS[name]):
-        w = data.load_windows(os.path.join("/root/reference/datasets", name, part), 8, 12, 1, with_non_linear=False)
+        w = data.load_windows(_split_directory(tmp_path, name, part), 8, 12, 1, with_non_linear=False)
         assert (len(w), int(w.num_peds.sum()), int(w.num_peds.max())) == want, (name, part)
 
 
