@@ -42,8 +42,89 @@ struct ModelLayout {
     int32_t flags, wg_waves;        // stg_model_desc.flags / .wg_waves
 };
 
+// The shape fields of a model descriptor: everything the offsets of a ModelLayout follow from.
+struct ModelShape {
+    int32_t n_blocks, n_txp, c_in, residual0, use_mdn;
+};
+
+// Every offset and size of the layout from the shape alone (validated by make_layout); eps, momentum, bn_mode, flags
+// and wg_waves stay zero -- they are the caller's runtime values.  constexpr: the canonical model's layout below is
+// compiled into its kernels from this same code.
+constexpr ModelLayout layout_of(const ModelShape &d) {
+    constexpr int C = Cfg::C, T = Cfg::T, P = Cfg::P, KT = Cfg::KT;
+    ModelLayout l{};
+    l.n_blocks = d.n_blocks;
+    l.n_txp = d.n_txp;
+    l.L = d.n_txp == 0 ? 0 : (d.n_txp - 1 > 1 ? d.n_txp - 1 : 1);
+    l.use_mdn = d.use_mdn;
+    int p = 0, b = 0, s = 0, hdr = 0, u = 0;
+    for (int j = 0; j < l.n_blocks; ++j) {
+        BlockLayout &k = l.blk[j];
+        k.cin = j == 0 ? d.c_in : C;
+        // social_stgcnn builds every block with residual=True (model.py:164-166): conv+BN when the
+        // channel count changes, identity otherwise (model.py:127-141).
+        k.residual = j == 0 ? d.residual0 : 1;
+        k.gcn_w = p; p += C * k.cin;
+        k.gcn_b = p; p += C;
+        k.bn1_g = p; p += C;
+        k.bn1_b = p; p += C;
+        k.prelu1 = p; p += 1;
+        k.tcn_w = p; p += C * C * KT;
+        k.tcn_b = p; p += C;
+        k.bn2_g = p; p += C;
+        k.bn2_b = p; p += C;
+        if (k.residual == 2) {
+            k.res_w = p; p += C * k.cin;
+            k.res_b = p; p += C;
+            k.bnr_g = p; p += C;
+            k.bnr_b = p; p += C;
+        } else {
+            k.res_w = k.res_b = k.bnr_g = k.bnr_b = -1;
+        }
+        k.prelu_o = p; p += 1;
+        k.n_bn = k.residual == 2 ? 3 : 2;
+        k.buf = b; b += 2 * C * k.n_bn;
+        k.stat = s; s += 2 * C * k.n_bn;
+        k.ws_hdr = hdr; hdr += kWsHdrPerBlock;
+        k.ws_ax = u; u += k.cin * T;
+        k.ws_cs = u; u += T;
+        k.ws_g = u; u += C * T;
+        k.ws_h2 = u; u += C * T;
+        k.ws_s = u; u += C * T;
+    }
+    for (int q = 0; q < l.n_txp; ++q) {
+        const int cin = q == 0 ? T : P;
+        l.txp_w[q] = p; p += P * cin * 9;
+        l.txp_b[q] = p; p += P;
+    }
+    if (l.n_txp > 0) {
+        l.out_w = p; p += P * P * 9;
+        l.out_b = p; p += P;
+        l.prelus = p; p += l.n_txp;
+        for (int q = 0; q < l.L; ++q) { l.ws_z[q] = u; u += P * C; }
+        l.n_planes = l.L + 1;                        // a_0 (the last block's output, model.py:187) .. a_L
+    }
+    l.n_blk_params = l.n_txp > 0 ? l.txp_w[0] : p;
+    l.n_params = p;
+    l.n_buffers = b;
+    l.stat_floats = s;
+    l.ws_hdr_floats = hdr;
+    l.ws_units = u;
+    return l;
+}
+
+// The model the reference trains (train.py defaults): one st_gcn block on input_feat 2 with a conv+BN residual, five
+// TXP-CNN layers, no MDN head.  Its scene kernels are compiled with this layout as constants (txp_x6.hip).
+constexpr ModelLayout kCanonLayout = layout_of(ModelShape{1, 5, Cfg::CIN0, 2, 0});
+static_assert(kCanonLayout.n_params == 7563, "canonical model: 7563 parameters");
+static_assert(kCanonLayout.L == 4 && kCanonLayout.n_planes == 5, "canonical model: four hidden TXP layers");
+static_assert(kCanonLayout.n_blk_params == 142 && kCanonLayout.n_buffers == 30, "canonical st_gcn block");
+static_assert(kCanonLayout.ws_hdr_floats == 64 && kCanonLayout.ws_units == 144 + 4 * 60, "canonical per-scene workspace");
+
 // Fills `lay` from the public descriptor; returns STG_OK or an error code (message in last_error).
 int make_layout(const stg_model_desc *d, ModelLayout *lay);
+// true when `L` is kCanonLayout in every field but the runtime ones (eps, momentum, bn_mode, flags, wg_waves)
+bool is_canonical(const ModelLayout &L);
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -92,14 +173,14 @@ __device__ __forceinline__ f32x4 finish_vec4(const f32x4 &raw, bool bf16) {
 // LDS geometry of one padded TXP plane set: rows = C + 2, row stride SW = vi + 2, channel stride SC
 // chosen == 16 (mod 32) so the four K-lanes groups of a 16x16x4 B-operand read hit disjoint banks.
 __host__ __device__ inline int txp_sw(int vi) { return vi + 2; }
-__host__ __device__ inline int txp_sc(int vi) {
+__host__ __device__ constexpr int txp_sc(int vi) {
     const int raw = (Cfg::C + 2) * (vi + 2);
     return raw + ((16 - (raw & 31)) & 31);
 }
 // floats of one saved plane slot (sized for the padded batch V).  Planes are SAVED position-major,
 // [(C+2)*(vi+2) padded positions][P channels] (what the weight-gradient GEMM reads conflict-free); the
 // slot is sized by the channel-major LDS form P*txp_sc(V) >= P*(C+2)*(V+2).
-__host__ __device__ inline int plane_slot(int V) { return Cfg::P * txp_sc(V); }
+__host__ __device__ constexpr int plane_slot(int V) { return Cfg::P * txp_sc(V); }
 // The wave-per-scene TXP FORWARD keeps ONE plane per scene and updates it in place: C + 4 row slots; a layer reads
 // its input at slot offset 2 (even layers) or 0 (odd layers) and writes row r of its output two slots away from
 // where it read row r -- towards the rows it has already consumed (even layers walk the positions upwards, odd
@@ -109,14 +190,14 @@ __host__ __device__ inline int txp_sci(int vi) {
     return raw + ((16 - (raw & 31)) & 31);
 }
 // floats of one dz_l hand-off slot: position-major [C*V positions][P channels] (padded batch V)
-__host__ __device__ inline int dz_slot(int V) { return Cfg::P * Cfg::C * V; }
+__host__ __device__ constexpr int dz_slot(int V) { return Cfg::P * Cfg::C * V; }
 
 // offset (floats, from the scene's workspace base, 16-byte aligned) of saved plane a_l
-__host__ __device__ inline int64_t ws_plane_off(const ModelLayout &l, int V, int idx) {
+__host__ __device__ constexpr int64_t ws_plane_off(const ModelLayout &l, int V, int idx) {
     const int64_t arrays = ((int64_t)l.ws_hdr_floats + (int64_t)l.ws_units * V + 3) & ~(int64_t)3;
     return arrays + (int64_t)idx * plane_slot(V);
 }
-__host__ __device__ inline int64_t ws_floats_per_scene(const ModelLayout &l, int V) {
+__host__ __device__ constexpr int64_t ws_floats_per_scene(const ModelLayout &l, int V) {
     return ws_plane_off(l, V, l.n_planes);
 }
 

@@ -16,6 +16,55 @@ namespace {
 
 constexpr int C = Cfg::C, P = Cfg::P, T = Cfg::T;
 
+// What the solo kernels are compiled for.  Generic: the layout and the crowd are kernel arguments (every model the x6
+// kernels fit).  Canon: the layout is kCanonLayout (model_common.hpp) -- every parameter and workspace offset a
+// constant, none of them held in SGPRs -- the crowd still a runtime value (ragged batches).  Canon32: kCanonLayout and
+// uniform scenes of exactly kCanonV pedestrians, no num_peds: the workspace stride, the aggregation offsets, the saved
+// row strides, the tile count and the lane geometry are constants as well.  The host picks a folded shape only when the
+// runtime values it passes equal the folded ones (canon_shape below).
+enum class Shape { Generic, Canon, Canon32 };
+constexpr int kCanonV = 32;
+constexpr int64_t kCanonWs32 = ws_floats_per_scene(kCanonLayout, kCanonV);
+// the aggregation launch's outputs of a Canon32 batch: in the workspace (training) or the scratch buffer (inference)
+constexpr int64_t kCanonAggStride32[2] = {(int64_t)(Cfg::CIN0 + 1) * Cfg::T * kCanonV, kCanonWs32};
+constexpr int64_t kCanonAggAx32[2] = {0, kCanonLayout.ws_hdr_floats + (int64_t)kCanonLayout.blk[0].ws_ax * kCanonV};
+constexpr int64_t kCanonAggCs32[2] = {(int64_t)Cfg::CIN0 * Cfg::T * kCanonV,
+                                      kCanonLayout.ws_hdr_floats + (int64_t)kCanonLayout.blk[0].ws_cs * kCanonV};
+
+// The kernel entry's copy of its arguments with the folded fields replaced by constants (eps, momentum, bn_mode, flags
+// and wg_waves stay the caller's).  Everything below the entry reads the copy, so the constants reach every offset.
+template <Shape S, typename Args>
+__device__ __forceinline__ void fold_shape(Args &a) {
+    if constexpr (S != Shape::Generic) {
+        ModelLayout k = kCanonLayout;
+        k.eps = a.lay.eps;
+        k.momentum = a.lay.momentum;
+        k.bn_mode = a.lay.bn_mode;
+        k.flags = a.lay.flags;
+        k.wg_waves = a.lay.wg_waves;
+        a.lay = k;
+    }
+    if constexpr (S == Shape::Canon32) {
+        a.V = a.Vl = kCanonV;
+        a.num_peds = nullptr;
+        a.tier.order = nullptr;
+        a.tier.key_start = nullptr;
+        a.ws_stride = kCanonWs32;
+    }
+}
+// Layout arrays indexed by the (runtime) layer: from the constant layout of a folded shape, so that the entry's copy of
+// the arguments is never addressed with a runtime index (that would keep it in scratch memory)
+template <Shape S>
+__device__ __forceinline__ int lay_txp_b(const ModelLayout &L, int l) {
+    if constexpr (S == Shape::Generic) return L.txp_b[l];
+    else return kCanonLayout.txp_b[l];
+}
+template <Shape S>
+__device__ __forceinline__ int lay_ws_z(const ModelLayout &L, int l) {
+    if constexpr (S == Shape::Generic) return L.ws_z[l];
+    else return kCanonLayout.ws_z[l];
+}
+
 // ------------------------------------------------------------------------------------------
 // forward, exact-bf16 variant (x6 = six bf16 products per fp32 product): the convs on v_mfma_f32_16x16x32_bf16
 // ------------------------------------------------------------------------------------------
@@ -30,7 +79,7 @@ __host__ __device__ inline int fwd6_region_floats(int v) { return (cv::image_byt
 // CK (scene_team.hpp): SoloScene -- this wave owns the scene, `region` / `ptab` are its own -- or TeamScene: the wave owns
 // the column chunk [ck.w0(), ck.w0() + ck.wc()) of a scene that ck.nch() waves share (`region` = the team's image, `ptab` =
 // this wave's table of its chunk's positions); `vi` = pedestrians of the scene.
-template <bool BF, typename CK>    // BF: bf16 storage of the saved planes / pre-activations (STG_OPT_BF16_STORE)
+template <bool BF, typename CK, Shape SH = Shape::Generic>    // BF: bf16 storage of the saved planes / pre-activations
 __device__ __forceinline__ void txp_fwd_scene_x6(const TxpFwdArgs &a, const float *__restrict__ params,
                                                  const float *blk_params, const float *blk_buffers, int n, int vi,
                                                  float *region, ptab_t *ptab, const CK &ck) {
@@ -95,12 +144,12 @@ __device__ __forceinline__ void txp_fwd_scene_x6(const TxpFwdArgs &a, const floa
         const bool is_out = l == L.L;
         cv::u32x4 w[cv::kWpVecs];
         cv::load_wp(a.wpf + (int64_t)l * cv::kWpDwords, w);
-        const float *bias = Pm + (is_out ? L.out_b : L.txp_b[l]);
+        const float *bias = Pm + (is_out ? L.out_b : lay_txp_b<SH>(L, l));
         f32x4 binit;
 #pragma unroll
         for (int r = 0; r < 4; ++r) binit[r] = kq < 3 ? bias[4 * kq + r] : 0.f;
         const float alpha = is_out ? 0.f : Pm[L.prelus + l];
-        float *zs = (wsn && !is_out) ? wsn + L.ws_hdr_floats + (int64_t)L.ws_z[l] * V : nullptr;
+        float *zs = (wsn && !is_out) ? wsn + L.ws_hdr_floats + (int64_t)lay_ws_z<SH>(L, l) * V : nullptr;
         float *ps = (wsn && !is_out) ? wsn + ws_plane_off(L, V, l + 1) : nullptr;
         // the layer's operands and bias have landed before the first guarded tile: no vmcnt wait inside the tile loop
         asm volatile("" ::"v"(w[0]), "v"(w[cv::kWpVecs - 1]), "v"(binit), "v"(alpha) : "memory");
@@ -158,10 +207,18 @@ __device__ __forceinline__ void txp_fwd_scene_x6(const TxpFwdArgs &a, const floa
     }
 }
 
-template <int WPB, bool BF>
+template <int WPB, bool BF, Shape S>
 __global__ __launch_bounds__(WPB * 64, WPB == 8 ? 1 : 2) __attribute__((amdgpu_waves_per_eu(2, 2))) void txp_fwd_x6_kernel(
-    const TxpFwdArgs a, const float *__restrict__ params, const float *__restrict__ buffers) {
+    const TxpFwdArgs a0, const float *__restrict__ params, const float *__restrict__ buffers) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
+    TxpFwdArgs a = a0;
+    fold_shape<S>(a);
+    if constexpr (S == Shape::Canon32) {
+        const int w = a.ws != nullptr;
+        a.agg_stride = kCanonAggStride32[w];
+        a.agg_ax = kCanonAggAx32[w];
+        a.agg_cs = kCanonAggCs32[w];
+    }
     const int Vl = a.Vl, wave = threadIdx.x >> 6;
     const int per_wave = fwd6_region_floats(Vl) + ptab_floats(Vl);
     float *region = sm + wave * per_wave;
@@ -180,7 +237,7 @@ __global__ __launch_bounds__(WPB * 64, WPB == 8 ? 1 : 2) __attribute__((amdgpu_w
         const int n = __builtin_amdgcn_readfirstlane(a.tier.order ? scene_index(a.tier.order[begin + it], a.N) : it);
         int vi = a.num_peds ? a.num_peds[n] : a.V;
         vi = __builtin_amdgcn_readfirstlane(vi < 0 ? 0 : (vi > a.V ? a.V : vi));
-        txp_fwd_scene_x6<BF>(a, params, blk_p, blk_b, n, vi, region, ptab, SoloScene{vi});
+        txp_fwd_scene_x6<BF, SoloScene, S>(a, params, blk_p, blk_b, n, vi, region, ptab, SoloScene{vi});
         __builtin_amdgcn_wave_barrier();
     }
 }
@@ -205,7 +262,7 @@ __host__ __device__ inline int bwd6_region_floats(int v) {
 // ck.w0() + ck.wc()) of a scene shared by ck.nch() waves (`region` = the team's image, `ptab` = this wave's table of its
 // chunk's positions); `vi` = pedestrians of the scene.  Per-scene sums are exchanged through LDS (ck.sum), the team's
 // leading wave writes the scene's loss and its row of small-parameter gradients.
-template <bool BF, typename CK>    // BF: bf16 storage of z_l (read) and dz_l (written)
+template <bool BF, typename CK, Shape SH = Shape::Generic>    // BF: bf16 storage of z_l (read) and dz_l (written)
 __device__ __forceinline__ void txp_bwd_scene_x6(const TxpBwdArgs &a, const float *blk_params, int n, int vi, float *region,
                                                  ptab_t *ptab, const CK &ck) {
     const ModelLayout &L = a.lay;
@@ -272,6 +329,9 @@ __device__ __forceinline__ void txp_bwd_scene_x6(const TxpBwdArgs &a, const floa
                 const float inv_cnt = 1.0f / (float)(P * vi);
                 const float gs = inv_cnt * (a.nll_weights ? a.nll_weights[n] : 1.f);
                 float lacc = 0.f;
+                // (one round at a time: with the crowd a constant (Canon32) the rounds would be unrolled and their loads
+                // hoisted -- 200 VGPRs spilled to scratch)
+#pragma unroll 1
                 for (int p0 = 0; p0 < P; p0 += rpi) {
                     const int p = p0 + sub;
                     if (okw && p < P) {
@@ -298,6 +358,7 @@ __device__ __forceinline__ void txp_bwd_scene_x6(const TxpBwdArgs &a, const floa
                 }
             } else {
                 constexpr int U = 4;
+#pragma unroll 1
                 for (int r0 = 0; r0 < C * P; r0 += rpi * U) {
                     float dv[U];
 #pragma unroll
@@ -346,7 +407,7 @@ __device__ __forceinline__ void txp_bwd_scene_x6(const TxpBwdArgs &a, const floa
         } else {
             // dz_l = d(a_{l+1}) * prelu'(z_l): z_l and dz_l are position-major [pos][12] in HBM, the lane's quad of tile t
             // is vector (16 t + n) * 3 + kq
-            const float *zl = wsn + L.ws_hdr_floats + (int64_t)L.ws_z[l] * V;
+            const float *zl = wsn + L.ws_hdr_floats + (int64_t)lay_ws_z<SH>(L, l) * V;
             const float alpha = Pm[L.prelus + l];
             float slope_acc = 0.f;
             // all ten quads of z_l in flight at once (the weight registers are dead here): one HBM latency per layer.
@@ -455,10 +516,12 @@ __device__ __forceinline__ void txp_bwd_scene_x6(const TxpBwdArgs &a, const floa
     }
 }
 
-template <int WPB, bool BF>
+template <int WPB, bool BF, Shape S>
 __global__ __launch_bounds__(WPB * 64, WPB == 8 ? 1 : 2) __attribute__((amdgpu_waves_per_eu(2, 2))) void txp_bwd_x6_kernel(
-    const TxpBwdArgs a) {
+    const TxpBwdArgs a0) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
+    TxpBwdArgs a = a0;
+    fold_shape<S>(a);
     const int Vl = a.Vl, wave = threadIdx.x >> 6;
     const int per_wave = bwd6_region_floats(Vl) + bwd_ptab_floats(Vl);
     float *region = sm + wave * per_wave;
@@ -477,7 +540,7 @@ __global__ __launch_bounds__(WPB * 64, WPB == 8 ? 1 : 2) __attribute__((amdgpu_w
         const int n = __builtin_amdgcn_readfirstlane(a.tier.order ? scene_index(a.tier.order[begin + it], a.N) : it);
         int vi = a.num_peds ? a.num_peds[n] : a.V;
         vi = __builtin_amdgcn_readfirstlane(vi < 0 ? 0 : (vi > a.V ? a.V : vi));
-        txp_bwd_scene_x6<BF>(a, blk_p, n, vi, region, ptab, SoloScene{vi});
+        txp_bwd_scene_x6<BF, SoloScene, S>(a, blk_p, n, vi, region, ptab, SoloScene{vi});
         __builtin_amdgcn_wave_barrier();
     }
 }
@@ -663,6 +726,22 @@ static int team_grid(size_t lds_bytes, int N) {
     return g < N ? g : N;                              // (at most one unit per scene)
 }
 
+// Shape of a solo launch: Canon32 for a uniform batch of kCanonV pedestrians per scene on the canonical model, Canon for
+// any other batch of that model, Generic for every other model.  `*ok` is false when a Canon32 batch arrives with
+// runtime values that differ from the ones the kernels fold in (an inconsistency of the entry points, never a caller's).
+template <typename Args>
+static Shape canon_shape(const Args &a, bool *ok) {
+    *ok = true;
+    if (!is_canonical(a.lay)) return Shape::Generic;
+    if (a.num_peds || a.V != kCanonV) return Shape::Canon;
+    *ok = a.Vl == kCanonV && !a.tier.order && !a.tier.key_start && a.ws_stride == kCanonWs32;
+    return Shape::Canon32;
+}
+static bool canon32_agg_matches(const TxpFwdArgs &a) {
+    const int w = a.ws != nullptr;
+    return a.agg_stride == kCanonAggStride32[w] && a.agg_ax == kCanonAggAx32[w] && a.agg_cs == kCanonAggCs32[w];
+}
+
 int launch_txp_fwd_x6(const TxpFwdArgs &a0, hipStream_t st) {
     TxpFwdArgs a = a0;
     if (a.wpf && txp_fwd_x6_fits(a.lay, a.V) && team_wanted(a.N, a.V, a.num_peds == nullptr, &a.team)) {
@@ -685,15 +764,27 @@ int launch_txp_fwd_x6(const TxpFwdArgs &a0, hipStream_t st) {
         const size_t lds = per_wave * wpb + wave_param_floats(a.lay) * sizeof(float);
         const dim3 grid(wave_grid(lds, wpb, a.N));
         const bool bf = (a.lay.flags & STG_OPT_BF16_STORE) != 0;
-#define STG_LX(W, B)                                                                                          \
+        bool ok;
+        const Shape sh = canon_shape(a, &ok);
+        STG_REQUIRE(ok && (sh != Shape::Canon32 || canon32_agg_matches(a)), STG_EINVAL,
+                    "txp_fwd_x6: the canonical V=%d batch does not match its compiled layout", a.V);
+#define STG_LX(W, B, S)                                                                                       \
     do {                                                                                                      \
-        hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(&txp_fwd_x6_kernel<W, B>),         \
+        hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(&txp_fwd_x6_kernel<W, B, S>),      \
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);            \
         if (e_ != hipSuccess) return hip_fail(e_, "txp_fwd_x6: hipFuncSetAttribute");                         \
-        hipLaunchKernelGGL((txp_fwd_x6_kernel<W, B>), grid, dim3(W * 64), lds, st, a, a.params, a.buffers);   \
+        hipLaunchKernelGGL((txp_fwd_x6_kernel<W, B, S>), grid, dim3(W * 64), lds, st, a, a.params, a.buffers);\
     } while (0)
-        if (wpb == 8) { if (bf) STG_LX(8, true); else STG_LX(8, false); }
-        else { if (bf) STG_LX(4, true); else STG_LX(4, false); }
+        // (a ragged batch with bf16 storage stays Generic: its Canon build spills two more VGPRs than the Generic one)
+#define STG_LXS(W, B)                                                                                         \
+    do {                                                                                                      \
+        if (sh == Shape::Canon32) STG_LX(W, B, Shape::Canon32);                                               \
+        else if (sh == Shape::Canon) STG_LX(W, B, (B ? Shape::Generic : Shape::Canon));                       \
+        else STG_LX(W, B, Shape::Generic);                                                                    \
+    } while (0)
+        if (wpb == 8) { if (bf) STG_LXS(8, true); else STG_LXS(8, false); }
+        else { if (bf) STG_LXS(4, true); else STG_LXS(4, false); }
+#undef STG_LXS
 #undef STG_LX
         STG_LAUNCH_CHECK("txp_fwd_x6");
         return STG_OK;
@@ -728,15 +819,25 @@ int launch_txp_bwd_x6(const TxpBwdArgs &a0, hipStream_t st) {
         const size_t lds = per_wave * wpb + wave_param_floats(a.lay) * sizeof(float);
         const dim3 grid(wave_grid(lds, wpb, a.N));
         const bool bf = (a.lay.flags & STG_OPT_BF16_STORE) != 0;
-#define STG_LX(W, B)                                                                                          \
+        bool ok;
+        const Shape sh = canon_shape(a, &ok);
+        STG_REQUIRE(ok, STG_EINVAL, "txp_bwd_x6: the canonical V=%d batch does not match its compiled layout", a.V);
+#define STG_LX(W, B, S)                                                                                       \
     do {                                                                                                      \
-        hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(&txp_bwd_x6_kernel<W, B>),         \
+        hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(&txp_bwd_x6_kernel<W, B, S>),      \
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);            \
         if (e_ != hipSuccess) return hip_fail(e_, "txp_bwd_x6: hipFuncSetAttribute");                         \
-        hipLaunchKernelGGL((txp_bwd_x6_kernel<W, B>), grid, dim3(W * 64), lds, st, a);                        \
+        hipLaunchKernelGGL((txp_bwd_x6_kernel<W, B, S>), grid, dim3(W * 64), lds, st, a);                     \
     } while (0)
-        if (wpb == 8) { if (bf) STG_LX(8, true); else STG_LX(8, false); }
-        else { if (bf) STG_LX(4, true); else STG_LX(4, false); }
+#define STG_LXS(W, B)                                                                                         \
+    do {                                                                                                      \
+        if (sh == Shape::Canon32) STG_LX(W, B, Shape::Canon32);                                               \
+        else if (sh == Shape::Canon) STG_LX(W, B, Shape::Canon);                                              \
+        else STG_LX(W, B, Shape::Generic);                                                                    \
+    } while (0)
+        if (wpb == 8) { if (bf) STG_LXS(8, true); else STG_LXS(8, false); }
+        else { if (bf) STG_LXS(4, true); else STG_LXS(4, false); }
+#undef STG_LXS
 #undef STG_LX
         STG_LAUNCH_CHECK("txp_bwd_x6");
         return STG_OK;
