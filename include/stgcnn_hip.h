@@ -36,7 +36,7 @@ extern "C" {
 #define STG_EUNSUPPORTED (-2) /* configuration outside what the kernels are built for      */
 #define STG_ELDS (-3)        /* scene too large for the 160 KiB LDS of one CU             */
 
-#define STG_ABI_VERSION 7
+#define STG_ABI_VERSION 8
 #define STG_MAX_BLOCKS 4     /* st_gcn blocks in one fused model                          */
 
 int stg_abi_version(void);
@@ -297,6 +297,23 @@ int stg_train_tail(const stg_model_desc *d, const float *stats, const int32_t *n
 int stg_bestofk_eval(const float *pred, int64_t p_sn, int64_t p_sf, int64_t p_sp, int64_t p_sv,
                      const float *target_rel, const float *obs_last, const int32_t *num_peds, const float *noise,
                      uint64_t seed, int N, int P, int V, int K, float *ade, float *fde, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * N5  the sampled trajectories of test.test (test.py:59-91, raw_data_dict[step]['pred']) for a whole batch: the K
+ *     draws of stg_bestofk_eval written out instead of reduced.  pred, obs_last, num_peds and noise as there (obs_last
+ *     NULL: trajectories relative to the origin; noise NULL: the in-kernel Philox stream, counter
+ *     (scene*V + ped, k*P + t) under the padded width V, keyed by `seed`, or by the device uint64 *seed_dev read at
+ *     execution time when seed_dev is not NULL -- a captured graph then draws afresh after the caller updates it).
+ *     samples (K,N,P,V,2) contiguous (the noise layout): obs_last + cumsum_t(mean_t + chol(cov_t) eps_{k,t}); may be
+ *     NULL only when K == 0.  mean (N,P,V,2) or NULL: obs_last + cumsum_t(mean_t), the zero-noise trajectory.  Same
+ *     draws and Cholesky arithmetic as stg_bestofk_eval: best-of-K over samples is its ade / fde for the same seed.
+ *     Padded slots are zeros in both outputs; N == 0 is a no-op.  samples, mean, noise and obs_last must be 8-byte
+ *     aligned (16-byte alignment and an even V select the two-pedestrians-per-lane float4 stores).
+ */
+int stg_sample_trajectories(const float *pred, int64_t p_sn, int64_t p_sf, int64_t p_sp, int64_t p_sv,
+                            const float *obs_last, const int32_t *num_peds, const float *noise, uint64_t seed,
+                            const uint64_t *seed_dev, int N, int P, int V, int K, float *samples, float *mean,
+                            void *stream);
 
 /* Self-test helper: C(16x16) = A(16xK) * B(Kx16) through v_mfma_f32_16x16x4_f32 with the operand
  * maps the TXP-CNN kernels rely on (K multiple of 4).                                           */

@@ -16,7 +16,7 @@ CSRC = os.path.join(_HERE, "csrc")
 # library reads no environment variable itself
 DIAG = os.environ.get("STG_USE_DIAG_LIB", "0") not in ("", "0")
 LIB_PATH = os.path.join(CSRC, "libstgcnn_hip_diag.so" if DIAG else "libstgcnn_hip.so")
-ABI_VERSION = 7
+ABI_VERSION = 8
 OPT_WG_PATH, OPT_SPLIT_BF16, OPT_WAVE_PATH, OPT_BF16_STORE, OPT_F32_MFMA = 1, 2, 4, 8, 16
 EUNSUPPORTED = -2            # STG_EUNSUPPORTED
 
@@ -67,6 +67,8 @@ _SIGNATURES = {
     "stg_optim_step": (c_i, [c_f, c_f, c_l, c_f, ctypes.c_float, ctypes.c_float, c_f, c_f]),
     "stg_bestofk_eval": (c_i, [c_f, c_l, c_l, c_l, c_l, c_f, c_f, c_f, c_f, ctypes.c_uint64, c_i, c_i, c_i, c_i,
                                c_f, c_f, c_f]),
+    "stg_sample_trajectories": (c_i, [c_f, c_l, c_l, c_l, c_l, c_f, c_f, c_f, ctypes.c_uint64, c_f, c_i, c_i, c_i, c_i,
+                                      c_f, c_f, c_f]),
     "stg_gather_windows": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f]),
     "stg_dp_pack": (c_i, [c_f, c_f, c_f, c_f, c_i, ctypes.c_float, c_i, c_i, c_i, c_i, c_f, c_f]),
     "stg_dp_fold": (c_i, [c_f, c_f, ctypes.c_float, c_i, c_i, c_i, c_i, c_f, ctypes.POINTER(ctypes.c_void_p), c_i, c_f]),

@@ -590,6 +590,47 @@ def best_of_k(y, target_rel, obs_last=None, num_peds=None, k=20, noise=None, see
     return ade, fde
 
 
+def sample_trajectories(y, obs_last=None, num_peds=None, k=20, noise=None, seed=0, seed_dev=None, samples=None,
+                        mean=None):
+    """The sampled trajectories of test.py:59-91 on the device (`stg_sample_trajectories`): y (N,5,P,V) model output
+    (any strides), obs_last (N,V,2) or None (trajectories from the origin), noise (K,N,P,V,2) standard normals or None
+    (in-kernel Philox stream keyed by `seed`, or by the one-element int64 device tensor `seed_dev`, read when the kernel
+    runs).  The draws are `best_of_k`'s for the same seed / noise.  samples / mean: preallocated outputs (graph
+    capture), contiguous float32.  Returns (samples (K,N,P,V,2), mean (N,P,V,2)), zeros in padded slots."""
+    require_gpu(y, seed_dev, samples, mean)
+    n, f, p, v = y.shape
+    k = int(k)
+    if f != 5:
+        raise ValueError("sample_trajectories: y (N,5,P,V) expected")
+    if k < 0:
+        raise ValueError("sample_trajectories: k must be >= 0")
+    y = y.to(torch.float32)
+    if obs_last is not None:
+        if tuple(obs_last.shape) != (n, v, 2):
+            raise ValueError("sample_trajectories: obs_last (N,V,2) expected")
+        obs_last = obs_last.to(device=y.device, dtype=torch.float32).contiguous()
+    if noise is not None:
+        if tuple(noise.shape) != (k, n, p, v, 2):
+            raise ValueError("sample_trajectories: noise (K,N,P,V,2) expected")
+        noise = noise.to(device=y.device, dtype=torch.float32).contiguous()
+    if seed_dev is not None and (seed_dev.numel() != 1 or seed_dev.dtype != torch.int64):
+        raise ValueError("sample_trajectories: seed_dev must be a one-element int64 device tensor")
+    for name, out, shape in (("samples", samples, (k, n, p, v, 2)), ("mean", mean, (n, p, v, 2))):
+        if out is not None and (tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous()):
+            raise ValueError("sample_trajectories: %s must be a contiguous float32 %s tensor" % (name, shape))
+    peds = peds_arg(num_peds, n, y.device)
+    if samples is None:
+        samples = torch.empty((k, n, p, v, 2), device=y.device, dtype=torch.float32)
+    if mean is None:
+        mean = torch.empty((n, p, v, 2), device=y.device, dtype=torch.float32)
+    sn, sf, sp, sv = y.stride()
+    check(lib().stg_sample_trajectories(ptr(y), sn, sf, sp, sv, ptr(obs_last), ptr(peds), ptr(noise),
+                                        int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(seed_dev), n, p, v, k,
+                                        ptr(samples) if k > 0 else None, ptr(mean), stream_ptr()),
+          "stg_sample_trajectories")
+    return samples, mean
+
+
 def scene_order(num_peds, v):
     """Scene indices sorted by pedestrian count (clamped to [0, v]) descending, stable: the schedule the fused
     kernels use for ragged batches (`stg_scene_order`).  num_peds: int32 device tensor (N,).

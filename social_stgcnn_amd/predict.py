@@ -1,0 +1,184 @@
+"""Prediction from what a user holds -- observed absolute tracks -- to K sampled future trajectories per pedestrian,
+batched on the device: the counterpart of the reference's test() (test.py:18-127) and of the `raw_data_dict` that
+test_v.py / visualize.py read.
+
+    observed_inputs   obs_abs (N,T_obs,V,2) -> model input x, adjacency, last observed position
+    Predictor         relative coordinates -> adj_build -> fused forward -> stg_sample_trajectories; eager
+                      (`predict`) or as ONE captured graph (`capture`)
+    sample_test       test() over data.SceneWindows: (ade, fde, raw_data_dict)
+"""
+import collections
+
+import numpy as np
+import torch
+
+from . import data, ops
+from ._lib import peds_arg, require_gpu
+
+Prediction = collections.namedtuple("Prediction", "samples mean v_pred")
+Prediction.__doc__ = """samples (K,N,P,V,2) absolute sampled trajectories, mean (N,P,V,2) the zero-noise trajectory,
+v_pred (N,5,P,V) the model output (the reference's V_pred before its permute).  Padded slots are zeros."""
+
+
+def _seed_i64(seed):
+    """A uint64 seed as the int64 a device tensor holds (same 64 bits)."""
+    s = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return s - (1 << 64) if s >= 1 << 63 else s
+
+
+def observed_inputs(obs_abs, num_peds=None, out=None):
+    """obs_abs (N,T_obs,V,2) absolute positions (the data.pad_batch layout, any strides; float32 or float64) ->
+    (x (N,2,T_obs,V), adj (N,T_obs,V,V), obs_last (N,V,2)), float32.  Relative coordinates as the reference dataset
+    builds them (utils.py:153-158): rel[:,0] = 0, rel[:,t] = obs[:,t] - obs[:,t-1], taken in the input's precision and
+    then rounded to float32; the graphs from the adj_build kernel.
+
+    The graph weights are 1 / |rel_h - rel_k| and 0 where two displacements are equal, so they are not continuous in
+    rel: pedestrians walking in step have equal displacements when they are taken from the dataset's float64 positions
+    and rounded, while float32 differences of float32 positions differ by an ulp of the position -- a weight of ~1e6
+    instead of 0.  Pass float64 positions, as the reference dataset holds them, to get the reference's graphs
+    (sample_test does).
+    `out` = (rel (N,T,V,2) float32, nodes (N,T,V,2), adj (N,T,V,V)) contiguous buffers to fill (graph capture)."""
+    require_gpu(obs_abs)
+    if obs_abs.dim() != 4 or obs_abs.shape[3] != 2:
+        raise ValueError("observed_inputs: obs_abs (N,T_obs,V,2) expected, got %s" % (tuple(obs_abs.shape),))
+    if obs_abs.dtype not in (torch.float32, torch.float64):
+        obs_abs = obs_abs.to(torch.float32)
+    n, t, v, _ = obs_abs.shape
+    if out is None:
+        rel = torch.empty((n, t, v, 2), device=obs_abs.device, dtype=torch.float32)
+        nodes_adj = None
+    else:
+        rel, nodes, adj = out
+        nodes_adj = (nodes, adj)
+    rel[:, 0].zero_()
+    if obs_abs.dtype == torch.float32:
+        torch.sub(obs_abs[:, 1:], obs_abs[:, :-1], out=rel[:, 1:])
+    else:
+        rel[:, 1:].copy_(obs_abs[:, 1:] - obs_abs[:, :-1])
+    nodes, adj = ops.adj_build(rel.permute(0, 2, 3, 1), num_peds, out=nodes_adj)      # (N,V,2,T) view
+    return nodes.permute(0, 3, 1, 2), adj, obs_abs[:, -1].to(torch.float32)
+
+
+class Predictor:
+    """K sampled trajectories per pedestrian from observed absolute tracks, for a whole batch of scenes."""
+
+    def __init__(self, model, k=20):
+        self.model = model
+        self.k = int(k)
+
+    def _forward(self, obs_abs, peds, seed, noise, seed_dev=None, bufs=None, outs=(None, None)):
+        x, adj, obs_last = observed_inputs(obs_abs, peds, bufs)
+        y, _ = self.model(x, adj, peds)
+        samples, mean = ops.sample_trajectories(y, obs_last, peds, self.k, noise, seed, seed_dev, *outs)
+        return Prediction(samples, mean, y)
+
+    @torch.no_grad()
+    def predict(self, obs_abs, num_peds=None, seed=0, noise=None):
+        """obs_abs (N,T_obs,V,2) device tensor, num_peds (N,) or None, noise (K,N,P,V,2) standard normals or None
+        (the kernel's Philox stream keyed by `seed`).  Runs the model in eval mode and restores its mode."""
+        require_gpu(obs_abs)
+        peds = peds_arg(num_peds, obs_abs.shape[0], obs_abs.device)
+        was = self.model.training
+        self.model.eval()
+        try:
+            return self._forward(obs_abs, peds, seed, noise)
+        finally:
+            self.model.train(was)
+
+    @torch.no_grad()
+    def capture(self, n, v, num_peds, dtype=torch.float32, warmup=2):
+        """Capture ONE graph on static buffers for batches of n scenes padded to v pedestrians, positions of `dtype`
+        (see observed_inputs): relative coordinates -> adj_build -> fused forward -> stg_sample_trajectories, the seed
+        read from a device tensor.  num_peds: (n,)
+        device tensor (no host->device copy inside a graph); its values are copied into the graph's own buffer.
+        Returns replay(obs_abs, num_peds=None, seed=None) -> Prediction on the static outputs (overwritten by the
+        next replay); the arguments are copied into the static buffers outside the graph, None keeps the last one."""
+        if not (torch.is_tensor(num_peds) and num_peds.is_cuda):
+            raise ValueError("capture() needs num_peds as a device tensor (no host->device copies in a graph)")
+        model = self.model
+        dev = num_peds.device
+        t_obs, p = model.seq_len, model.pred_seq_len
+        peds = peds_arg(num_peds, n, dev).clone()
+        obs = torch.zeros((n, t_obs, v, 2), device=dev, dtype=dtype)
+        seed_dev = torch.zeros(1, device=dev, dtype=torch.int64)
+        bufs = (torch.empty((n, t_obs, v, 2), device=dev, dtype=torch.float32),
+                torch.empty((n, t_obs, v, 2), device=dev, dtype=torch.float32),
+                torch.empty((n, t_obs, v, v), device=dev, dtype=torch.float32))
+        outs = (torch.empty((self.k, n, p, v, 2), device=dev, dtype=torch.float32),
+                torch.empty((n, p, v, 2), device=dev, dtype=torch.float32))
+        was = model.training
+        model.eval()
+        try:
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                for _ in range(max(1, warmup)):
+                    self._forward(obs, peds, 0, None, seed_dev, bufs, outs)
+            torch.cuda.current_stream().wait_stream(side)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                res = self._forward(obs, peds, 0, None, seed_dev, bufs, outs)
+        finally:
+            model.train(was)
+        self._graph = graph
+        # every buffer the graph reads or writes lives as long as replay(): a freed one would go back to the caching
+        # allocator while the graph still writes it
+        static = (obs, peds, seed_dev, bufs, outs)
+
+        def replay(obs_abs, num_peds=None, seed=None):
+            obs_s, peds_s, seed_s = static[:3]
+            obs_s.copy_(obs_abs)
+            if num_peds is not None:
+                peds_s.copy_(torch.as_tensor(num_peds).reshape(-1))
+            if seed is not None:
+                seed_s.fill_(_seed_i64(seed))
+            graph.replay()
+            return res
+        return replay
+
+
+def _displacement_errors(pred, trgt):
+    """metrics.ade / fde arithmetic (metrics.py:21-53) for every sample and pedestrian: float32 differences and
+    squares, float64 square root and sums.  pred (K,P,V,2), trgt (P,V,2) -> (ade (K,V), fde (K,V))."""
+    d = pred - trgt[None]
+    err = np.sqrt((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]).astype(np.float64))       # (K,P,V)
+    return err.sum(axis=1) / err.shape[1], err[:, -1]
+
+
+@torch.no_grad()
+def sample_test(model, windows, k=20, batch_size=64, seed=0, noise_fn=None):
+    """test.test() (test.py:18-127) over data.SceneWindows, batch_size windows per launch chain.  Returns (ade, fde,
+    raw): raw[step] (1-based, one per window) = {'obs': (T_obs,V_i,2), 'trgt': (P,V_i,2), 'pred': [K x (P,V_i,2)]}
+    float32 numpy arrays as test.py:87-105 builds them; ade / fde the best-of-k means over all pedestrians.  The draws
+    come from the kernel's Philox stream keyed by seed + batch index, or from noise_fn(batch_index, (k,N,P,V,2)) ->
+    standard normals (as in trainer.evaluate_ade_fde_device)."""
+    pred = Predictor(model, k)
+    dev = next(model.parameters()).device
+    t_obs = model.seq_len
+    raw, ades, fdes, step = {}, [], [], 0
+    for b, lo in enumerate(range(0, len(windows), batch_size)):
+        idx = np.arange(lo, min(len(windows), lo + batch_size))
+        obs_rel, pred_rel, obs_abs, _, counts = data.pad_batch(windows, idx, obs_len=t_obs)
+        n, _, v, _ = obs_abs.shape
+        obs64 = np.zeros(obs_abs.shape)                    # the dataset's float64 positions (see observed_inputs)
+        for j, i in enumerate(idx):
+            s0, e0 = windows.seq_start_end[i]
+            obs64[j, :, :e0 - s0] = np.transpose(windows.seq[s0:e0, :, :t_obs], (2, 0, 1))
+        noise = noise_fn(b, (k, n, pred_rel.shape[1], v, 2)) if noise_fn is not None else None
+        r = pred.predict(torch.from_numpy(obs64).to(dev), torch.from_numpy(counts).to(dev), seed + b, noise)
+        samples = r.samples.cpu().numpy()
+        # nodes_rel_to_nodes_abs (metrics.py:66-75) of the observed / target displacements from the first / last
+        # observed position, as test.py:73-79 calls it
+        x0, xl = obs_abs[:, 0].astype(np.float64), obs_abs[:, -1].astype(np.float64)
+        obs = (np.cumsum(obs_rel, axis=1, dtype=np.float32) + x0[:, None]).astype(np.float32)
+        trgt = (np.cumsum(pred_rel, axis=1, dtype=np.float32) + xl[:, None]).astype(np.float32)
+        for j in range(n):
+            c = int(counts[j])
+            step += 1
+            s = np.ascontiguousarray(samples[:, j, :, :c])
+            raw[step] = {"obs": np.ascontiguousarray(obs[j, :, :c]), "trgt": np.ascontiguousarray(trgt[j, :, :c]),
+                         "pred": [s[kk] for kk in range(k)]}
+            a, f = _displacement_errors(s, raw[step]["trgt"])
+            ades += a.min(axis=0).tolist()
+            fdes += f.min(axis=0).tolist()
+    return sum(ades) / len(ades), sum(fdes) / len(fdes), raw

@@ -1,0 +1,113 @@
+#!/usr/bin/env python3
+"""Device time of the captured Predictor (observed absolute tracks -> K sampled trajectories, ONE graph) and of the
+sampling kernel alone, from device events around graph replays.  One JSON line per case.
+
+    python tools/predict_bench.py [--iters 200] [--cases bench,eth,kernel]
+
+  bench   Predictor replay at N = 2048, V = 32 (every slot a pedestrian), K = 20, eth weights
+  eth     Predictor replay on eth/test: its 70 windows as one ragged batch, K = 20
+  kernel  stg_sample_trajectories alone at K = 20 x N = 2048 x V = 32, P = 12 (63 MB written), captured
+
+For the kernel's own time run this under `rocprofv3 --kernel-trace --stats -- python tools/predict_bench.py`.
+With the diagnostic library (STG_USE_DIAG_LIB=1, `make -C social_stgcnn_amd/csrc DIAG=1`) STG_SAMPLE_PEDS=1 forces
+one pedestrian per lane (float2 stores) instead of a pair (float4): the A/B of the store width.
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np
+import torch
+
+CFG = dict(n_stgcnn=1, n_txpcnn=5, output_feat=5, seq_len=8, kernel_size=3, pred_seq_len=12)
+
+
+def eth_model(dev):
+    from social_stgcnn_amd.model import social_stgcnn
+    w = np.load(os.path.join(ROOT, "tests", "golden", "weights_eth.npz"))
+    m = social_stgcnn(**CFG)
+    m.load_state_dict({k: torch.from_numpy(np.array(w[k])) for k in w.files})
+    return m.to(dev).eval()
+
+
+def time_replays(fn, iters, warmup=10):
+    """ms per call of fn() (graph replays), from device events around `iters` back-to-back calls."""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    for _ in range(iters):
+        fn()
+    t1.record()
+    t1.synchronize()
+    return t0.elapsed_time(t1) / iters
+
+
+def predictor_case(name, m, obs, peds, k, iters):
+    from social_stgcnn_amd.predict import Predictor
+    n, _, v, _ = obs.shape
+    pr = Predictor(m, k=k)
+    replay = pr.capture(n, v, peds)
+    replay(obs, seed=1)
+    ms = time_replays(pr._graph.replay, iters)
+    return {"case": name, "n": n, "v": v, "k": k, "ms_per_replay": round(ms, 5),
+            "scenes_per_s": round(n / ms * 1e3, 1), "peds": int(peds.sum())}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--cases", default="bench,eth,kernel")
+    args = ap.parse_args()
+    cases = args.cases.split(",")
+    from social_stgcnn_amd import data, ops
+    from social_stgcnn_amd import _lib
+    dev = torch.device("cuda", 0)
+    ops.OPTIONS["wave_path"] = True          # the wave-per-scene kernels for every batch size here
+    m = eth_model(dev)
+    k, n, v, p = 20, 2048, 32, 12
+    info = {"lib": os.path.basename(_lib.LIB_PATH), "sample_peds_env": os.environ.get("STG_SAMPLE_PEDS")}
+    if "bench" in cases:
+        gen = torch.Generator().manual_seed(0)
+        start = torch.rand((n, 1, v, 2), generator=gen) * 20 - 10
+        obs = torch.cat([start, start + torch.cumsum(torch.randn((n, 7, v, 2), generator=gen) * 0.3, 1)], 1).to(dev)
+        peds = torch.full((n,), v, dtype=torch.int32, device=dev)
+        print(json.dumps(dict(predictor_case("predictor_bench", m, obs, peds, k, args.iters), **info)), flush=True)
+    if "eth" in cases:
+        win = data.load_windows(os.path.join(ROOT, "tests", "golden", "data", "eth_test"), 8, 12, 1,
+                                with_non_linear=False)
+        _, _, obs_abs, _, counts = data.pad_batch(win, np.arange(len(win)))
+        obs, peds = torch.from_numpy(obs_abs).to(dev), torch.from_numpy(counts).to(dev)
+        print(json.dumps(dict(predictor_case("predictor_eth_test", m, obs, peds, k, args.iters), **info)), flush=True)
+    if "kernel" in cases:
+        gen = torch.Generator().manual_seed(1)
+        y = (torch.randn((n, p, v, 5), generator=gen) * 0.5).to(dev).permute(0, 3, 1, 2)    # the model's layout
+        obs_last = torch.randn((n, v, 2), generator=gen).to(dev)
+        seed_dev = torch.ones(1, dtype=torch.int64, device=dev)
+        samples = torch.empty((k, n, p, v, 2), device=dev)
+        mean = torch.empty((n, p, v, 2), device=dev)
+
+        def run():
+            ops.sample_trajectories(y, obs_last, None, k, None, 0, seed_dev, samples, mean)
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            run()
+        torch.cuda.current_stream().wait_stream(s)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            run()
+        ms = time_replays(g.replay, args.iters)
+        written = (samples.numel() + mean.numel()) * 4
+        print(json.dumps(dict({"case": "sample_kernel", "k": k, "n": n, "v": v, "p": p, "ms_per_replay": round(ms, 5),
+                               "mb_written": round(written / 1e6, 2), "read_mb": round(n * 5 * p * v * 4 / 1e6, 2),
+                               "store_tb_per_s": round(written / (ms * 1e-3) / 1e12, 3)}, **info)), flush=True)
+
+
+if __name__ == "__main__":
+    main()
