@@ -7,7 +7,8 @@
     batch = ds.gather(order[lo:hi])              # obs_rel / target / num_peds padded to ds.v_max, on the device
 
 `EpochRunner` captures gather -> adj_build -> forward -> loss -> backward -> update as one hipGraph on static buffers
-and replays it per group with the index buffer refreshed in place: a training epoch moves nothing over PCIe.
+and replays it per group with the index buffer refreshed in place: a training epoch moves nothing over PCIe.  Its
+validation epoch does the same with gather -> adj_build -> eval forward -> per-scene NLL -> weighted group total.
 """
 import numpy as np
 import torch
@@ -77,6 +78,8 @@ class EpochRunner:
         self.nodes = torch.empty((self.bs, dataset.t_obs, v, 2), device=dev)
         self.adj = torch.empty((self.bs, dataset.t_obs, v, v), device=dev)
         self._replays = {}                 # group size -> (replay, index slice, loss weights)
+        self._val_replays = {}             # group size -> (graph, group total, index slice, loss weights)
+        self._dataset_order = None
 
     def _group(self, cnt):
         """the captured step of a group of `cnt` scenes (cnt <= batch_size): leading slices of the static buffers"""
@@ -111,5 +114,61 @@ class EpochRunner:
             replay, index, _ = self._group(cnt)
             index.copy_(order[lo:b + 1])                        # device -> device
             total = total + replay()[0]
+            lo = b + 1
+        return total / n_scenes
+
+    @torch.no_grad()
+    def _val_group(self, cnt):
+        """the captured validation pass of a group of `cnt` scenes: gather -> adj_build -> eval forward -> per-scene NLL
+        -> sum_n w_n loss_n (stg_weighted_sum: one fixed summation order), on leading slices of the static buffers"""
+        g = self._val_replays.get(cnt)
+        if g is None:
+            from .trainer import group_weights
+            model = self.trainer.model
+            index = self.index[:cnt]
+            obs_rel, target, peds = self.obs_rel[:cnt], self.target[:cnt], self.peds[:cnt]
+            nodes, adj = self.nodes[:cnt], self.adj[:cnt]
+            weights = group_weights(cnt, self.bs, self.ds.device)
+
+            def group_total():
+                self.ds.gather(index, out=(obs_rel, target, peds))
+                ops.adj_build(obs_rel, peds, out=(nodes, adj))
+                y, _ = model(nodes.permute(0, 3, 1, 2), adj, peds)
+                losses = ops.bivariate_nll(y.permute(0, 2, 3, 1), target, peds)
+                return ops.weighted_sum(losses, weights)
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                group_total()                                   # (warm-up: an eval pass changes nothing)
+            torch.cuda.current_stream().wait_stream(side)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                total = group_total()
+            # (the graph reads `weights` and the index slice at every replay: they live as long as the graph)
+            g = self._val_replays[cnt] = (graph, total, index, weights)
+        return g
+
+    def val_epoch(self, order=None):
+        """vald() (train.py:81-122) over the dataset: the model in eval mode, windows in dataset order (or `order`, an int32
+        device tensor of window indices), groups of `batch_size` scenes whose closing scene is forwarded but not in the
+        loss, every group ONE replay of a captured graph (one per group size).  Returns the epoch loss as vald() reports
+        it (sum of group losses / scenes seen) as a 0-d device tensor; nothing in the epoch waits for the host."""
+        from .trainer import group_bounds
+        self.trainer.model.eval()
+        if order is None:
+            if self._dataset_order is None:
+                self._dataset_order = torch.arange(self.ds.n_windows, device=self.ds.device, dtype=torch.int32)
+            order = self._dataset_order
+        n_scenes = order.numel()
+        total = torch.zeros((), device=self.ds.device)
+        lo = 0
+        for b in group_bounds(n_scenes, self.bs):
+            cnt = b + 1 - lo
+            if cnt not in self._val_replays:
+                self.index[:cnt].copy_(order[lo:b + 1])         # (valid window indices while the group is captured)
+            graph, group_total, index, _ = self._val_group(cnt)
+            index.copy_(order[lo:b + 1])                        # device -> device
+            graph.replay()
+            total = total + group_total
             lo = b + 1
         return total / n_scenes

@@ -14,8 +14,10 @@ all-reduce (RCCL over xGMI; a latency-bound 30 KB message) per optimizer step, a
 running statistics are folded across ranks in rank order so that R ranks x B scenes equal one rank
 processing the concatenated R*B scenes.
 """
+import argparse
 import math
 import os
+import pickle
 
 import numpy as np
 import torch
@@ -490,3 +492,21 @@ def load_checkpoint(model, path, map_location="cpu"):
     state = torch.load(path, map_location=map_location, weights_only=True)
     model.load_state_dict(state)
     return model
+
+
+class _NamespaceUnpickler(pickle.Unpickler):
+    """resolves argparse.Namespace and no other global (see load_pickle)"""
+
+    def find_class(self, module, name):
+        if (module, name) == ("argparse", "Namespace"):
+            return argparse.Namespace
+        raise pickle.UnpicklingError("global %s.%s is not allowed in a checkpoint pickle" % (module, name))
+
+
+def load_pickle(path):
+    """pickle.load of a checkpoint's side file -- args.pkl (an argparse.Namespace), metrics.pkl, constant_metrics.pkl
+    (test.py:153-158) -- with the rule load_checkpoint applies to val_best.pth: the file comes from outside the program, so
+    it may build argparse.Namespace and plain values (dicts, lists, numbers, strings, None, bools) and nothing else.  Any
+    other global it names raises pickle.UnpicklingError before anything of it runs."""
+    with open(path, "rb") as fp:
+        return _NamespaceUnpickler(fp).load()
