@@ -315,6 +315,45 @@ int stg_sample_trajectories(const float *pred, int64_t p_sn, int64_t p_sf, int64
                             const uint64_t *seed_dev, int N, int P, int V, int K, float *samples, float *mean,
                             void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * N6  per-frame prediction scenes from raw tracks: the reference's windowing (utils.py:123-165) without the future.
+ *     At frame index f >= T_obs - 1 (frames = the recording's distinct frame numbers in ascending order, utils.py:123)
+ *     the scene is every pedestrian id with a row in each of the frames f-T_obs+1 .. f, in ascending id order; the
+ *     positions are rounded as np.around(x, d) (utils.py:145): rint(x * scale) / scale in float64, scale = 10^d
+ *     (scale <= 0: no rounding).  Outputs are float64 obs_abs (., T_obs, V, 2) oldest frame first, int64 ids (., V)
+ *     (-1 in padded slots) and int32 num_peds; padded slots are zeros.
+ *
+ *   Recording: rows sorted by (frame index, id) and uploaded once -- ids int64[M], xy float64 (M,2) -- with
+ *   frame_start int32[F+1] (rows of frame f are frame_start[f] .. frame_start[f+1]-1; no duplicate id in a frame).
+ *   stg_frame_scene_counts: count int32[F] = the scene size at every frame (0 for f < T_obs - 1).
+ *   stg_frame_scenes: the scenes of the N frame indices frames int32[N] into obs_abs (N,T_obs,V,2), ids (N,V),
+ *   num_peds (N); a scene larger than V keeps its V smallest ids (size V to the largest count).
+ *
+ *   Live stream: stg_track_push turns one frame of detections into that frame's scene (N = 1) with the track state on
+ *   the device: slot_id int64[S] (-1 = free), mask uint32[S] (bit t = seen t frames ago), ring float64 (T_obs,S,2) of
+ *   rounded positions, head_flags int32[2] = {ring row of the last frame, STG_TRACK_* flags of the last push}.  Zero
+ *   mask / head_flags and slot_id = -1 start a new stream.  Inputs: det_id int64[M_max], det_xy float64 (M_max,2) and
+ *   the detection count det_count int32[1], all DEVICE memory (a captured graph replays with another count).  A
+ *   repeated id within a push: the first detection wins.  A new id takes a free slot -- one not seen in the last
+ *   T_obs - 1 frames --, the i-th new detection (detection order) the i-th free slot (slot order); without a free slot
+ *   it is dropped for this frame.  The scene keeps the V smallest ids.  M_max <= STG_TRACK_MAX_DETECTIONS,
+ *   S <= STG_TRACK_MAX_SLOTS, T_obs <= 32.  One workgroup; no host synchronisation.
+ */
+#define STG_TRACK_MAX_DETECTIONS 2048
+#define STG_TRACK_MAX_SLOTS 2048
+#define STG_TRACK_DUPLICATE 1 /* a repeated id in the push (later detections dropped)                 */
+#define STG_TRACK_OVERFLOW 2  /* no free slot for a new id (dropped for this frame)                   */
+#define STG_TRACK_TRUNCATED 4 /* det_count > M_max (the first M_max detections used)                  */
+#define STG_TRACK_TOO_MANY 8  /* more than V fully observed pedestrians (the V smallest ids kept)      */
+int stg_frame_scene_counts(const int32_t *frame_start, const int64_t *ids, int F, int T_obs, int32_t *count,
+                           void *stream);
+int stg_frame_scenes(const int32_t *frame_start, const int64_t *ids, const double *xy, const int32_t *frames, int N,
+                     int V, int T_obs, double scale, double *obs_abs, int64_t *out_ids, int32_t *num_peds,
+                     void *stream);
+int stg_track_push(const int64_t *det_id, const double *det_xy, const int32_t *det_count, int M_max, int64_t *slot_id,
+                   uint32_t *mask, double *ring, int32_t *head_flags, int S, int T_obs, double scale, int V,
+                   double *obs_abs, int64_t *out_ids, int32_t *num_peds, void *stream);
+
 /* Self-test helper: C(16x16) = A(16xK) * B(Kx16) through v_mfma_f32_16x16x4_f32 with the operand
  * maps the TXP-CNN kernels rely on (K multiple of 4).                                           */
 int stg_selftest_mfma(const float *a, const float *b, int K, float *c, void *stream);

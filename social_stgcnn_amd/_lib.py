@@ -75,6 +75,10 @@ _SIGNATURES = {
     "stg_weighted_sum": (c_i, [c_f, c_f, c_i, c_f, c_f]),
     "stg_train_tail": (c_i, [ctypes.POINTER(ModelDesc), c_f, c_f, c_i, c_f, ctypes.POINTER(ctypes.c_void_p), c_i, c_f, c_f,
                              c_f, c_f, c_f, c_l, c_f, ctypes.c_float, ctypes.c_float, c_f, c_f]),
+    "stg_frame_scene_counts": (c_i, [c_f, c_f, c_i, c_i, c_f, c_f]),
+    "stg_frame_scenes": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, ctypes.c_double, c_f, c_f, c_f, c_f]),
+    "stg_track_push": (c_i, [c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_i, c_i, ctypes.c_double, c_i, c_f, c_f, c_f,
+                             c_f]),
     "stg_selftest_mfma": (c_i, [c_f, c_f, c_i, c_f, c_f]),
 }
 EXPORTS = tuple(_SIGNATURES)

@@ -1,0 +1,330 @@
+// frames: per-frame prediction scenes from raw tracks, the reference's windowing (utils.py:123-165) with the future
+// dropped -- at frame index f the scene is every pedestrian id with a row in each of the frames f-T_obs+1 .. f, in
+// ascending id order, positions rounded as np.around(x, 4) (utils.py:145: rint(x * 1e4) / 1e4 in float64).
+//
+//   stg_frame_scene_counts  recording: one wave per frame; every row of frame f looks its id up (binary search) in the
+//                           id-sorted rows of each of the T_obs - 1 frames before -> count[f].  Memory stays linear in
+//                           the rows (no ids x frames table: long recordings hold tens of thousands of ids).
+//   stg_frame_scenes        recording: one wave per selected frame; the fully observed rows of the frame are compacted
+//                           in id order (ballot + popcount under the lane mask) into obs_abs / ids / num_peds.
+//   stg_track_push          live stream: ONE workgroup keeps the track state on the device (slot ids, presence masks,
+//                           a position ring) and turns one frame of detections into that frame's scene.  The detection
+//                           count is read from device memory, so a captured graph replays with a different count.
+//
+// Pure data movement and integer work: a few KB per frame.  No host synchronisation in the launch functions (the push
+// is captured into the per-frame graph of FramePredictor.capture) and plain C++ stores only.
+#include "common.hpp"
+
+namespace stg {
+
+constexpr int kPushThreads = 1024;
+constexpr int kPushWaves = kPushThreads / kWave;
+constexpr int kFlagDuplicate = STG_TRACK_DUPLICATE, kFlagOverflow = STG_TRACK_OVERFLOW,
+              kFlagTruncated = STG_TRACK_TRUNCATED, kFlagTooMany = STG_TRACK_TOO_MANY;
+
+// np.around(x, decimals) for decimals >= 0: x * 10^d, round half to even, / 10^d (scale <= 0: no rounding)
+__device__ __forceinline__ double round_pos(double x, double scale) { return scale > 0.0 ? rint(x * scale) / scale : x; }
+
+// row index of `id` in frame g (frame_start offsets, ids sorted by id inside each frame), or -1
+__device__ __forceinline__ int row_of(const int32_t *__restrict__ fs, const int64_t *__restrict__ ids, int g, int64_t id) {
+    int lo = fs[g], hi = fs[g + 1];
+    const int end = hi;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (ids[mid] < id) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < end && ids[lo] == id ? lo : -1;
+}
+
+// lanes below this one whose bit is set in a wave ballot
+__device__ __forceinline__ int lanes_below(uint64_t m) {
+    const int lane = threadIdx.x & (kWave - 1);
+    return __popcll(m & ((1ull << lane) - 1ull));
+}
+
+// ---- recording ---------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void frame_scene_counts_kernel(const int32_t *__restrict__ fs,
+                                                                const int64_t *__restrict__ ids, int T_obs,
+                                                                int32_t *__restrict__ count) {
+    const int f = blockIdx.x;
+    int c = 0;
+    if (f >= T_obs - 1) {
+        for (int r = fs[f] + (int)threadIdx.x; r < fs[f + 1]; r += kWave) {
+            const int64_t id = ids[r];
+            bool full = true;
+            for (int g = f - 1; g > f - T_obs && full; --g) full = row_of(fs, ids, g, id) >= 0;
+            c += full ? 1 : 0;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, kWave);
+    if (threadIdx.x == 0) count[f] = c;
+}
+
+__global__ __launch_bounds__(64) void frame_scenes_kernel(const int32_t *__restrict__ fs, const int64_t *__restrict__ ids,
+                                                          const double *__restrict__ xy,
+                                                          const int32_t *__restrict__ frames, int V, int T_obs,
+                                                          double scale, double *__restrict__ obs_abs,
+                                                          int64_t *__restrict__ out_ids, int32_t *__restrict__ num_peds) {
+    const int n = blockIdx.x, lane = threadIdx.x;
+    const int f = frames[n];
+    double *obs = obs_abs + (int64_t)n * T_obs * V * 2;          // (T_obs, V, 2)
+    int64_t *oid = out_ids + (int64_t)n * V;
+    int base = 0;
+    // rows of frame f in id order, 64 at a time: every lane of the wave runs the loop (uniform trip count)
+    for (int r0 = fs[f]; r0 < fs[f + 1]; r0 += kWave) {
+        const int r = r0 + lane;
+        const bool real = r < fs[f + 1];
+        const int64_t id = real ? ids[r] : 0;
+        bool full = real && f >= T_obs - 1;
+        for (int g = f - 1; g > f - T_obs && full; --g) full = row_of(fs, ids, g, id) >= 0;
+        const uint64_t m = __ballot(full);
+        const int slot = base + lanes_below(m);
+        if (full && slot < V) {
+            oid[slot] = id;
+            for (int t = 0; t < T_obs; ++t) {
+                const int g = f - T_obs + 1 + t;
+                const int q = t == T_obs - 1 ? r : row_of(fs, ids, g, id);
+                obs[((int64_t)t * V + slot) * 2] = round_pos(xy[(int64_t)q * 2], scale);
+                obs[((int64_t)t * V + slot) * 2 + 1] = round_pos(xy[(int64_t)q * 2 + 1], scale);
+            }
+        }
+        base += __popcll(m);
+    }
+    const int c = base < V ? base : V;
+    for (int s = c + lane; s < V; s += kWave) {
+        oid[s] = -1;
+        for (int t = 0; t < T_obs; ++t) {
+            obs[((int64_t)t * V + s) * 2] = 0.0;
+            obs[((int64_t)t * V + s) * 2 + 1] = 0.0;
+        }
+    }
+    if (lane == 0) num_peds[n] = c;
+}
+
+// ---- live stream -------------------------------------------------------------------------------------------------
+// Block-wide exclusive rank of `flag` over the threads (thread order), added to `base`; every thread gets the block
+// total in *total.  Called by all threads of the block (it holds two barriers).
+__device__ __forceinline__ int block_rank(bool flag, int base, int *total, int *wave_cnt) {
+    const int wave = threadIdx.x / kWave;
+    const uint64_t m = __ballot(flag);
+    if ((threadIdx.x & (kWave - 1)) == 0) wave_cnt[wave] = __popcll(m);
+    __syncthreads();
+    int before = 0, all = 0;
+    for (int w = 0; w < kPushWaves; ++w) {
+        const int c = wave_cnt[w];
+        before += w < wave ? c : 0;
+        all += c;
+    }
+    __syncthreads();                    // wave_cnt is reused by the next call
+    *total = all;
+    return base + before + lanes_below(m);
+}
+
+// LDS layout (dynamic): sort keys (M2 x int64), sort indices (M2 x int32), det_slot (M_max x int32),
+// slot masks (S x uint32), free slots (S x int32)
+__global__ __launch_bounds__(kPushThreads) void track_push_kernel(
+    const int64_t *__restrict__ det_id, const double *__restrict__ det_xy, const int32_t *__restrict__ det_count,
+    int M_max, int M2, int64_t *__restrict__ slot_id, uint32_t *__restrict__ mask, double *__restrict__ ring,
+    int32_t *__restrict__ head_flags, int S, int T_obs, double scale, int V, double *__restrict__ obs_abs,
+    int64_t *__restrict__ out_ids, int32_t *__restrict__ num_peds) {
+    extern __shared__ __align__(16) unsigned char lds[];
+    int64_t *key = reinterpret_cast<int64_t *>(lds);
+    int32_t *kidx = reinterpret_cast<int32_t *>(key + M2);
+    int32_t *det_slot = kidx + M2;
+    uint32_t *smask = reinterpret_cast<uint32_t *>(det_slot + M_max);
+    int32_t *free_list = reinterpret_cast<int32_t *>(smask + S);
+    __shared__ int wave_cnt[kPushWaves];
+    __shared__ int flags;
+
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const uint32_t full = T_obs >= 32 ? 0xffffffffu : (1u << T_obs) - 1u;
+    int m = det_count[0];
+    const bool truncated = m > M_max;
+    m = m < 0 ? 0 : (m > M_max ? M_max : m);
+    const int head = (head_flags[0] + 1) % T_obs;          // ring row of this frame
+    if (tid == 0) flags = truncated ? kFlagTruncated : 0;
+
+    // 1. age the presence masks (bit t = seen t frames ago); a slot with no presence in the last T_obs - 1 frames
+    //    is free.  Load the detections into the sort buffer (padding keys sort last).
+    for (int s = tid; s < S; s += nt) {
+        const uint32_t mk = (mask[s] << 1) & full;
+        smask[s] = mk;
+        if (mk == 0) slot_id[s] = -1;
+    }
+    int n2 = 1;                                             // sort size: next power of two >= m (<= M2)
+    while (n2 < m) n2 <<= 1;
+    for (int p = tid; p < n2; p += nt) {
+        key[p] = p < m ? det_id[p] : INT64_MAX;
+        kidx[p] = p;
+    }
+    for (int j = tid; j < m; j += nt) det_slot[j] = -1;
+    __syncthreads();
+
+    // 2. sort the detections by (id, detection index): bitonic network over n2 entries (all keys are distinct)
+    for (int k = 2; k <= n2; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < n2; i += nt) {
+                const int l = i ^ j;
+                if (l > i) {
+                    const int64_t a = key[i], b = key[l];
+                    const int ia = kidx[i], ib = kidx[l];
+                    const bool gt = a > b || (a == b && ia > ib);
+                    if (gt == ((i & k) == 0)) {
+                        key[i] = b;
+                        key[l] = a;
+                        kidx[i] = ib;
+                        kidx[l] = ia;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+
+    // 3. a repeated id: the first detection wins, the others are dropped.  Every live slot finds its id among the
+    //    detections (lower bound in the sorted keys = the winner).
+    for (int p = tid; p < m; p += nt)
+        if (p > 0 && key[p] == key[p - 1]) {
+            det_slot[kidx[p]] = -2;
+            atomicOr(&flags, kFlagDuplicate);
+        }
+    for (int s = tid; s < S; s += nt) {
+        if (smask[s] == 0) continue;
+        const int64_t id = slot_id[s];
+        int lo = 0, hi = m;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (key[mid] < id) lo = mid + 1;
+            else hi = mid;
+        }
+        if (lo < m && key[lo] == id) det_slot[kidx[lo]] = s;
+    }
+    __syncthreads();
+
+    // 4. new ids take free slots: the i-th new detection (detection order) gets the i-th free slot (slot order)
+    int n_free = 0, tot = 0;
+    for (int s0 = 0; s0 < S; s0 += nt) {
+        const int s = s0 + tid;
+        const bool fr = s < S && smask[s] == 0;
+        const int r = block_rank(fr, n_free, &tot, wave_cnt);
+        if (fr) free_list[r] = s;
+        n_free += tot;
+    }
+    __syncthreads();
+    int n_new = 0;
+    for (int j0 = 0; j0 < m; j0 += nt) {
+        const int j = j0 + tid;
+        const bool nw = j < m && det_slot[j] == -1;
+        const int r = block_rank(nw, n_new, &tot, wave_cnt);
+        if (nw) {
+            if (r < n_free) det_slot[j] = free_list[r];
+            else {
+                det_slot[j] = -3;
+                atomicOr(&flags, kFlagOverflow);
+            }
+        }
+        n_new += tot;
+    }
+    __syncthreads();
+
+    // 5. record this frame: id, presence bit 0, rounded position in the ring row `head`
+    for (int j = tid; j < m; j += nt) {
+        const int s = det_slot[j];
+        if (s < 0) continue;
+        slot_id[s] = det_id[j];
+        smask[s] |= 1u;
+        ring[((int64_t)head * S + s) * 2] = round_pos(det_xy[(int64_t)j * 2], scale);
+        ring[((int64_t)head * S + s) * 2 + 1] = round_pos(det_xy[(int64_t)j * 2 + 1], scale);
+    }
+    __syncthreads();
+
+    // 6. the scene: slots seen in each of the last T_obs frames, in ascending id order (the sorted detections), the
+    //    first V of them; gather their T_obs positions, oldest first
+    int c = 0;
+    for (int p0 = 0; p0 < m; p0 += nt) {
+        const int p = p0 + tid;
+        const int j = p < m ? kidx[p] : 0;
+        const int s = p < m ? det_slot[j] : -1;
+        const bool in = s >= 0 && (smask[s] & full) == full;
+        const int r = block_rank(in, c, &tot, wave_cnt);
+        if (in && r < V) {
+            out_ids[r] = key[p];
+            for (int t = 0; t < T_obs - 1; ++t) {
+                const int row = (head + 1 + t) % T_obs;           // head - (T_obs - 1 - t) mod T_obs
+                obs_abs[((int64_t)t * V + r) * 2] = ring[((int64_t)row * S + s) * 2];
+                obs_abs[((int64_t)t * V + r) * 2 + 1] = ring[((int64_t)row * S + s) * 2 + 1];
+            }
+            // this frame's position from the input (the ring row written above is another thread's store)
+            obs_abs[((int64_t)(T_obs - 1) * V + r) * 2] = round_pos(det_xy[(int64_t)j * 2], scale);
+            obs_abs[((int64_t)(T_obs - 1) * V + r) * 2 + 1] = round_pos(det_xy[(int64_t)j * 2 + 1], scale);
+        }
+        c += tot;
+    }
+    if (c > V && tid == 0) atomicOr(&flags, kFlagTooMany);
+    const int np = c < V ? c : V;
+    for (int e = np + tid; e < V; e += nt) out_ids[e] = -1;
+    for (int e = tid; e < T_obs * (V - np); e += nt) {
+        const int t = e / (V - np), r = np + e % (V - np);
+        obs_abs[((int64_t)t * V + r) * 2] = 0.0;
+        obs_abs[((int64_t)t * V + r) * 2 + 1] = 0.0;
+    }
+    for (int s = tid; s < S; s += nt) mask[s] = smask[s];
+    __syncthreads();
+    if (tid == 0) {
+        num_peds[0] = np;
+        head_flags[0] = head;
+        head_flags[1] = flags;
+    }
+}
+
+}  // namespace stg
+
+extern "C" {
+
+int stg_frame_scene_counts(const int32_t *frame_start, const int64_t *ids, int F, int T_obs, int32_t *count,
+                           void *stream) {
+    STG_REQUIRE(F >= 0 && T_obs >= 1, STG_EINVAL, "stg_frame_scene_counts: bad sizes F=%d T_obs=%d", F, T_obs);
+    if (F == 0) return STG_OK;
+    STG_REQUIRE(frame_start && ids && count, STG_EINVAL, "stg_frame_scene_counts: null pointer");
+    hipLaunchKernelGGL(stg::frame_scene_counts_kernel, dim3(F), dim3(stg::kWave), 0, stg::as_stream(stream),
+                       frame_start, ids, T_obs, count);
+    STG_LAUNCH_CHECK("stg_frame_scene_counts");
+    return STG_OK;
+}
+
+int stg_frame_scenes(const int32_t *frame_start, const int64_t *ids, const double *xy, const int32_t *frames, int N,
+                     int V, int T_obs, double scale, double *obs_abs, int64_t *out_ids, int32_t *num_peds,
+                     void *stream) {
+    STG_REQUIRE(N >= 0 && V > 0 && T_obs >= 1, STG_EINVAL, "stg_frame_scenes: bad sizes N=%d V=%d T_obs=%d", N, V,
+                T_obs);
+    if (N == 0) return STG_OK;
+    STG_REQUIRE(frame_start && ids && xy && frames && obs_abs && out_ids && num_peds, STG_EINVAL,
+                "stg_frame_scenes: null pointer");
+    hipLaunchKernelGGL(stg::frame_scenes_kernel, dim3(N), dim3(stg::kWave), 0, stg::as_stream(stream), frame_start,
+                       ids, xy, frames, V, T_obs, scale, obs_abs, out_ids, num_peds);
+    STG_LAUNCH_CHECK("stg_frame_scenes");
+    return STG_OK;
+}
+
+int stg_track_push(const int64_t *det_id, const double *det_xy, const int32_t *det_count, int M_max, int64_t *slot_id,
+                   uint32_t *mask, double *ring, int32_t *head_flags, int S, int T_obs, double scale, int V,
+                   double *obs_abs, int64_t *out_ids, int32_t *num_peds, void *stream) {
+    STG_REQUIRE(M_max >= 1 && M_max <= STG_TRACK_MAX_DETECTIONS && S >= 1 && S <= STG_TRACK_MAX_SLOTS && V >= 1 &&
+                    T_obs >= 1 && T_obs <= 32,
+                STG_EINVAL, "stg_track_push: bad sizes M_max=%d S=%d V=%d T_obs=%d", M_max, S, V, T_obs);
+    STG_REQUIRE(det_id && det_xy && det_count && slot_id && mask && ring && head_flags && obs_abs && out_ids &&
+                    num_peds,
+                STG_EINVAL, "stg_track_push: null pointer");
+    int m2 = 1;
+    while (m2 < M_max) m2 <<= 1;
+    const size_t lds = (size_t)m2 * (sizeof(int64_t) + sizeof(int32_t)) + (size_t)M_max * sizeof(int32_t) +
+                       (size_t)S * (sizeof(uint32_t) + sizeof(int32_t));
+    hipLaunchKernelGGL(stg::track_push_kernel, dim3(1), dim3(stg::kPushThreads), lds, stg::as_stream(stream), det_id,
+                       det_xy, det_count, M_max, m2, slot_id, mask, ring, head_flags, S, T_obs, scale, V, obs_abs,
+                       out_ids, num_peds);
+    STG_LAUNCH_CHECK("stg_track_push");
+    return STG_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,57 @@
+"""Frame-by-frame prediction over a whole recording (frames.predict_recording): at every frame, K sampled future
+trajectories for every pedestrian tracked over the last obs_seq_len frames.
+
+    python -m social_stgcnn_amd.predict_frames --checkpoint DIR --recording FILE [--ksteps 20] [--seed 0]
+                                               [--min_peds 1] [--delim tab] --out preds.npz
+
+DIR is a checkpoint directory in the reference's layout (args.pkl and val_best.pth, as social_stgcnn_amd.test reads
+it); FILE a recording in the ETH/UCY text format (<frame> <ped> <x> <y>).  The .npz holds, one entry per frame scene:
+frame (N,) frame numbers, ids (N,V) int64 (-1 in padded slots), num_peds (N,), mean (N,P,V,2) the zero-noise
+trajectories and samples (K,N,P,V,2), float32, zeros in padded slots.
+"""
+import argparse
+import os
+
+import numpy as np
+import torch
+
+from . import data
+from .frames import predict_recording
+from .model import social_stgcnn
+from .trainer import load_checkpoint, load_pickle
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description="Per-frame trajectory prediction over a recording (on the device).")
+    p.add_argument("--checkpoint", required=True, help="checkpoint directory (args.pkl, val_best.pth)")
+    p.add_argument("--recording", required=True, help="recording: <frame> <ped> <x> <y> rows")
+    p.add_argument("--ksteps", type=int, default=20, help="samples per pedestrian")
+    p.add_argument("--seed", type=int, default=0, help="seed of the device sampler")
+    p.add_argument("--min_peds", type=int, default=1, help="skip frames with fewer pedestrians")
+    p.add_argument("--delim", default="tab", help="column delimiter of the recording (tab, space or a character)")
+    p.add_argument("--out", required=True, help="output .npz")
+    return p
+
+
+def load_model(exp_path, device):
+    args = load_pickle(os.path.join(exp_path, "args.pkl"))
+    model = social_stgcnn(n_stgcnn=args.n_stgcnn, n_txpcnn=args.n_txpcnn, output_feat=args.output_size,
+                          seq_len=args.obs_seq_len, kernel_size=args.kernel_size, pred_seq_len=args.pred_seq_len)
+    load_checkpoint(model, os.path.join(exp_path, "val_best.pth"))
+    return model.to(device).eval()
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
+    if not torch.cuda.is_available():
+        raise RuntimeError("social_stgcnn_amd.predict_frames needs a GPU (MI355X)")
+    model = load_model(a.checkpoint, torch.device("cuda", torch.cuda.current_device()))
+    rows = data.read_file(a.recording, a.delim)
+    scenes, pred = predict_recording(model, rows, k=a.ksteps, seed=a.seed, min_peds=a.min_peds)
+    np.savez(a.out, frame=scenes.frame, ids=scenes.ids.cpu().numpy(), num_peds=scenes.num_peds.cpu().numpy(),
+             mean=pred.mean.cpu().numpy(), samples=pred.samples.cpu().numpy())
+    print("%d frame scenes, up to %d pedestrians -> %s" % (len(scenes.frame), scenes.ids.shape[1], a.out))
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,111 @@
+#!/usr/bin/env python3
+"""Per-frame prediction timings (social_stgcnn_amd.frames).  One JSON line per case.
+
+    python tools/frames_bench.py [--pushes 2000] [--cases latency,recording] [--k 20]
+
+  latency    the captured FramePredictor (ONE graph: stg_track_push -> observed_inputs -> forward -> sampler) pushed
+             every frame of a recording in a loop, --pushes timed pushes after a warm-up.  Host clock around staging +
+             replay + synchronise: what a caller with host detections waits per frame.  p50 / p90 / mean in ms, at
+             max_peds 32 and 128 (biwi_eth, up to 20 pedestrians) and 128 (students001, up to 73).
+  recording  predict_recording (batches of 64 frame scenes) on each test recording: frames/s, host clock around the
+             call and a synchronise, after one warm-up call.
+
+Kernel times come from a separate run under the profiler (tracing slows the host):
+    rocprofv3 --kernel-trace --stats -d OUT -o frames -- python tools/frames_bench.py --cases latency --pushes 500
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np
+import torch
+
+CFG = dict(n_stgcnn=1, n_txpcnn=5, output_feat=5, seq_len=8, kernel_size=3, pred_seq_len=12)
+DATA = os.path.join(ROOT, "tests", "golden", "data")
+TEST_RECORDINGS = (("eth", "eth_test/biwi_eth.txt"), ("hotel", "hotel_test/biwi_hotel.txt"),
+                   ("univ", "univ_test/students001.txt"), ("univ", "univ_test/students003.txt"),
+                   ("zara1", "zara1_test/crowds_zara01.txt"), ("zara2", "zara2_test/crowds_zara02.txt"))
+
+
+def model_for(split, dev):
+    from social_stgcnn_amd.model import social_stgcnn
+    w = np.load(os.path.join(ROOT, "tests", "golden", "weights_%s.npz" % split))
+    m = social_stgcnn(**CFG)
+    m.load_state_dict({k: torch.from_numpy(np.array(w[k])) for k in w.files})
+    return m.to(dev).eval()
+
+
+def pushes_of(rows):
+    frames = np.unique(rows[:, 0])
+    f_idx = np.searchsorted(frames, rows[:, 0])
+    order = np.argsort(f_idx, kind="stable")
+    bounds = np.searchsorted(f_idx[order], np.arange(len(frames) + 1))
+    return [(rows[order[a:b], 1].astype(np.int64), np.ascontiguousarray(rows[order[a:b], 2:4]))
+            for a, b in zip(bounds[:-1], bounds[1:])]
+
+
+def latency_case(split, rec, max_peds, k, n_push, dev, warmup=50):
+    from social_stgcnn_amd import data, frames
+    pushes = pushes_of(data.read_file(os.path.join(DATA, rec)))
+    fp = frames.FramePredictor(model_for(split, dev), k=k, max_peds=max_peds)
+    push = fp.capture()
+    times, peds = [], []
+    for i in range(warmup + n_push):
+        ids, xy = pushes[i % len(pushes)]
+        if i % len(pushes) == 0:
+            fp.reset()
+        t0 = time.perf_counter()
+        out = push(ids, xy)
+        torch.cuda.synchronize()
+        if i >= warmup:
+            times.append(time.perf_counter() - t0)
+            peds.append(out.num_peds.clone())
+    ms = np.array(times) * 1e3
+    peds = torch.cat(peds).cpu().numpy()
+    return {"case": "latency", "recording": os.path.basename(rec), "max_peds": max_peds, "k": k, "pushes": n_push,
+            "p50_ms": round(float(np.percentile(ms, 50)), 4), "p90_ms": round(float(np.percentile(ms, 90)), 4),
+            "mean_ms": round(float(ms.mean()), 4), "frames_per_s_p50": round(1e3 / float(np.percentile(ms, 50)), 1),
+            "mean_peds": round(float(peds.mean()), 2), "max_peds_seen": int(peds.max())}
+
+
+def recording_case(split, rec, k, dev):
+    from social_stgcnn_amd import data, frames
+    rows = data.read_file(os.path.join(DATA, rec))
+    model = model_for(split, dev)
+    frames.predict_recording(model, rows, k=k)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    sc, _ = frames.predict_recording(model, rows, k=k)
+    torch.cuda.synchronize()
+    secs = time.perf_counter() - t0
+    n = len(sc.frame)
+    return {"case": "recording", "recording": os.path.basename(rec), "k": k, "frame_scenes": n,
+            "v": int(sc.ids.shape[1]), "seconds": round(secs, 4), "frames_per_s": round(n / secs, 1)}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--pushes", type=int, default=2000)
+    ap.add_argument("--cases", default="latency,recording")
+    ap.add_argument("--k", type=int, default=20)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("frames_bench needs a GPU (MI355X)")
+    dev = torch.device("cuda", 0)
+    cases = a.cases.split(",")
+    if "latency" in cases:
+        for split, rec, v in (("eth", "eth_test/biwi_eth.txt", 32), ("eth", "eth_test/biwi_eth.txt", 128),
+                              ("univ", "univ_test/students001.txt", 128)):
+            print(json.dumps(latency_case(split, rec, v, a.k, a.pushes, dev)), flush=True)
+    if "recording" in cases:
+        for split, rec in TEST_RECORDINGS:
+            print(json.dumps(recording_case(split, rec, a.k, dev)), flush=True)
+
+
+if __name__ == "__main__":
+    main()
