@@ -367,13 +367,9 @@ extern "C" int stg_adj_build(const float *rel, int64_t rel_sn, int64_t rel_sv, i
                 hipLaunchKernelGGL(stg::adj_build_rows32_kernel<128>, grid, block, lds32, stg::as_stream(stream), rel, rel_sn,
                                    rel_sv, rel_sc, rel_st, num_peds, T, normalize, nodes, adj);
             } else {
-                if (lds32 > 48 * 1024) {
-                    hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(&stg::adj_build_rows32_kernel<256>),
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds32);
-                    if (e_ != hipSuccess) return stg::hip_fail(e_, "stg_adj_build: hipFuncSetAttribute");
-                }
-                hipLaunchKernelGGL(stg::adj_build_rows32_kernel<256>, grid, block, lds32, stg::as_stream(stream), rel, rel_sn,
-                                   rel_sv, rel_sc, rel_st, num_peds, T, normalize, nodes, adj);
+                const stg::Launch lc{"stg_adj_build", grid, block, lds32, stg::as_stream(stream), 48 * 1024};
+                return stg::launch(lc, stg::adj_build_rows32_kernel<256>, rel, rel_sn, rel_sv, rel_sc, rel_st, num_peds, T,
+                                   normalize, nodes, adj);
             }
             STG_LAUNCH_CHECK("stg_adj_build");
             return STG_OK;

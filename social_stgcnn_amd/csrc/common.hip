@@ -29,6 +29,13 @@ int hip_fail(hipError_t e, const char *what) {
     return static_cast<int>(e);
 }
 
+int raise_lds_limit(const void *kernel, size_t lds, const char *what) {
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess) return STG_OK;
+    snprintf(g_err, sizeof(g_err), "%s: hipFuncSetAttribute: %s", what, hipGetErrorString(e));
+    return static_cast<int>(e);
+}
+
 // p -= lr * g  (train.py:197 SGD without momentum / weight decay)
 __global__ void sgd_kernel(float *__restrict__ p, const float *__restrict__ g, int64_t n, float lr) {
     int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;

@@ -27,6 +27,28 @@ int hip_fail(hipError_t e, const char *what);
 
 static inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
+// One kernel launch with dynamic LDS: raise the kernel's hipFuncAttributeMaxDynamicSharedMemorySize to `lds` (only
+// when lds > raise_above: 0 = always; a site that stays under the runtime's own limit on most batches names that limit
+// and makes no runtime call for them), launch, check.  Returns STG_OK or the HIP error, recorded under `what`.
+struct Launch {
+    const char *what;
+    dim3 grid, block;
+    size_t lds;
+    hipStream_t st;
+    size_t raise_above = 0;
+};
+int raise_lds_limit(const void *kernel, size_t lds, const char *what);      // common.hip
+template <typename... Params, typename... Args>
+inline int launch(const Launch &l, void (*kernel)(Params...), const Args &...args) {
+    if (l.lds > l.raise_above) {
+        const int rc = raise_lds_limit(reinterpret_cast<const void *>(kernel), l.lds, l.what);
+        if (rc != STG_OK) return rc;
+    }
+    hipLaunchKernelGGL(kernel, l.grid, l.block, l.lds, l.st, args...);
+    STG_LAUNCH_CHECK(l.what);
+    return STG_OK;
+}
+
 // The product library reads NO environment variable.  A diagnostic build (make DIAG=1 -> -DSTG_DIAG,
 // libstgcnn_hip_diag.so, used by tools/ only) can override tuning constants and skip kernel phases for timing.
 #ifdef STG_DIAG
@@ -72,20 +94,28 @@ constexpr int kLdsBytes = 160 * 1024;
 constexpr int kNumCU = 256;
 
 // ---- device helpers --------------------------------------------------------------------
+// v += the value of the lane that the DPP control CTRL names (rows outside ROW_MASK add 0): one DPP-modified v_add
+template <int CTRL, int ROW_MASK = 0xf>
+__device__ __forceinline__ void dpp_add(float &v) {
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xf, false));
+}
 // Sum over the 64 lanes of the wave, result in every lane.  Six DPP-modified v_add (quad swaps, row
 // mirrors, row broadcasts -- pure VALU, no LDS crossbar, no s_waitcnt) leave the total in lane 63;
 // v_readlane broadcasts it.  Needs all 64 lanes active (call from wave-uniform control flow).
 __device__ __forceinline__ float wave_sum(float v) {
-#define STG_DPP_ADD(ctrl, row_mask)                                                                              \
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), (ctrl), (row_mask), 0xf, false))
-    STG_DPP_ADD(0xB1, 0xf);    // quad_perm [1,0,3,2]
-    STG_DPP_ADD(0x4E, 0xf);    // quad_perm [2,3,0,1]
-    STG_DPP_ADD(0x141, 0xf);   // row_half_mirror
-    STG_DPP_ADD(0x140, 0xf);   // row_mirror            -> every lane holds its 16-lane row sum
-    STG_DPP_ADD(0x142, 0xa);   // row_bcast15 into rows 1, 3
-    STG_DPP_ADD(0x143, 0xc);   // row_bcast31 into rows 2, 3 -> lane 63 holds the wave sum
-#undef STG_DPP_ADD
+    dpp_add<0xB1>(v);          // quad_perm [1,0,3,2]
+    dpp_add<0x4E>(v);          // quad_perm [2,3,0,1]
+    dpp_add<0x141>(v);         // row_half_mirror
+    dpp_add<0x140>(v);         // row_mirror            -> every lane holds its 16-lane row sum
+    dpp_add<0x142, 0xa>(v);    // row_bcast15 into rows 1, 3
+    dpp_add<0x143, 0xc>(v);    // row_bcast31 into rows 2, 3 -> lane 63 holds the wave sum
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+}
+// one DPP stage applied to K values
+template <int CTRL, int ROW_MASK = 0xf, int K>
+__device__ __forceinline__ void dpp_stage(float (&v)[K]) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) dpp_add<CTRL, ROW_MASK>(v[k]);
 }
 // K independent wave sums at once: every DPP stage is applied to all K values before the next stage, so the
 // dependent-DPP wait states of one chain are filled by the other chains (a lone wave_sum costs ~350 cycles of
@@ -93,16 +123,12 @@ __device__ __forceinline__ float wave_sum(float v) {
 // the DPP stages alone: lane 63 ends up with the K wave totals (the other lanes hold partial sums)
 template <int K>
 __device__ __forceinline__ void wave_sum_to_last(float (&v)[K]) {
-#define STG_DPP_STAGE(ctrl, row_mask)                                                                                \
-    _Pragma("unroll") for (int k = 0; k < K; ++k)                                                                    \
-        v[k] += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v[k]), (ctrl), (row_mask), 0xf, false))
-    STG_DPP_STAGE(0xB1, 0xf);
-    STG_DPP_STAGE(0x4E, 0xf);
-    STG_DPP_STAGE(0x141, 0xf);
-    STG_DPP_STAGE(0x140, 0xf);
-    STG_DPP_STAGE(0x142, 0xa);
-    STG_DPP_STAGE(0x143, 0xc);
-#undef STG_DPP_STAGE
+    dpp_stage<0xB1>(v);
+    dpp_stage<0x4E>(v);
+    dpp_stage<0x141>(v);
+    dpp_stage<0x140>(v);
+    dpp_stage<0x142, 0xa>(v);
+    dpp_stage<0x143, 0xc>(v);
 }
 template <int K>
 __device__ __forceinline__ void wave_sum_n(float (&v)[K]) {

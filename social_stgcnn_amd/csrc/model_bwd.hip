@@ -26,7 +26,8 @@
 // denser K1 launch.
 #include "model_common.hpp"
 #include "stgcn_block.hpp"
-#include "txp_wave.hpp"
+#include "txp_scene_common.hpp"
+#include "step_plan.hpp"
 #include "txp_wgrad.hpp"
 #include "tail_parts.hpp"
 #include "nll_elem.hpp"
@@ -418,10 +419,8 @@ static size_t bwd_lds_bytes(const ModelLayout &L, int V, int waves) {
 
 // measured (profiles/): the st_gcn backward is fastest with ONE wave per scene up to V ~ 40 (no cross-wave
 // barriers in its ~15 block reductions), more waves only when a scene's rows no longer fit one wave's registers
-static int bwd_waves(const ModelLayout &L, int N, int V) {
-    int w = 0;
-    use_wave_path(L, N, V, &w);          // (small batches: more waves per scene, see use_wave_path)
-    return w ? w : (V <= 40 ? 1 : (V <= 80 ? 4 : 8));
+static int bwd_waves(const StepPath &path, int V) {      // (small batches: more waves per scene, see choose_path)
+    return path.wg_waves ? path.wg_waves : (V <= 40 ? 1 : (V <= 80 ? 4 : 8));
 }
 
 static int bwd_grid_w(const ModelLayout &L, int N, int V, int waves) {
@@ -435,7 +434,7 @@ static int bwd_grid_w(const ModelLayout &L, int N, int V, int waves) {
     if (const int g = diag_env("STG_BWD_GRID", 0)) grid = g > 0 ? g : grid;
     return grid < N ? grid : N;
 }
-static int bwd_grid(const ModelLayout &L, int N, int V) { return bwd_grid_w(L, N, V, bwd_waves(L, N, V)); }
+static int bwd_grid(const ModelLayout &L, const StepPath &path, int N, int V) { return bwd_grid_w(L, N, V, bwd_waves(path, V)); }
 // ragged batches padded beyond kBwdTierV: the scenes up to kBwdTierV pedestrians (most of a real batch) run in a
 // second launch with ONE wave per scene and the LDS image of V = kBwdTierV; slab rows of both launches are stacked
 constexpr int kBwdTierV = 32;
@@ -451,13 +450,13 @@ static int bwd_grid_small(const ModelLayout &L, int N, int V) {
 struct BwdCarve {
     int64_t rows, slab2, dzg, order, total;
 };
-static bool bwd_carve(const ModelLayout &L, int N, int V, BwdCarve *c, WgradGeom *wg) {
-    const int g1 = bwd_grid(L, N, V);
+static bool bwd_carve(const ModelLayout &L, const StepPath &path, int N, int V, BwdCarve *c, WgradGeom *wg) {
+    const int g1 = bwd_grid(L, path, N, V);
     if (g1 < 0) return false;
     int gs = bwd_grid_small(L, N, V);
     if (gs < 0) gs = 0;
     int64_t n_rows = g1 + gs;
-    if (use_wave_path(L, N, V, nullptr) && N > n_rows) n_rows = N;
+    if (path.scene() && N > n_rows) n_rows = N;
     c->rows = 0;
     int64_t fl = (n_rows * (L.n_blk_params + L.n_txp) + 3) & ~(int64_t)3;
     c->slab2 = fl;
@@ -484,7 +483,7 @@ int64_t stg_model_bwd_scratch_floats(const stg_model_desc *d, int N, int V) {
     if (N <= 0 || V <= 0) return stg::fail(STG_EINVAL, "stg_model_bwd_scratch_floats: N=%d V=%d", N, V);
     stg::BwdCarve c;
     stg::WgradGeom wg{};
-    if (!stg::bwd_carve(l, N, V, &c, &wg)) return stg::fail(STG_ELDS, "stg_model_bwd: V=%d does not fit the LDS of one CU", V);
+    if (!stg::bwd_carve(l, stg::choose_path(l, N, V), N, V, &c, &wg)) return stg::fail(STG_ELDS, "stg_model_bwd: V=%d does not fit the LDS of one CU", V);
     return c.total;
 }
 
@@ -516,23 +515,21 @@ static int model_bwd_impl(const stg_model_desc *d, const float *params, const fl
     }
     BwdCarve cv;
     WgradGeom wg{};
-    STG_REQUIRE(bwd_carve(L, N, V, &cv, &wg), STG_ELDS, "stg_model_bwd: V=%d does not fit the LDS of one CU", V);
+    const StepPath path = choose_path(L, N, V);
+    STG_REQUIRE(bwd_carve(L, path, N, V, &cv, &wg), STG_ELDS, "stg_model_bwd: V=%d does not fit the LDS of one CU", V);
     const int n_small = L.n_blk_params + L.n_txp;
     float *rows = scratch + cv.rows, *slab2 = scratch + cv.slab2;
     float *dzg = L.n_txp > 0 ? scratch + cv.dzg : nullptr;
     // the wave-per-scene kernels compute no input gradient (the reference never needs one: x is data), and their
     // saved pre-activations are laid out for themselves: a caller that wants dx runs BOTH passes on the workgroup
     // kernels (STG_OPT_WG_PATH in the descriptor)
-    int auto_waves = 0;
-    const bool wave_path = use_wave_path(L, N, V, &auto_waves);
-    (void)auto_waves;
-    STG_REQUIRE(wave_path || !(L.flags & STG_OPT_BF16_STORE), STG_EUNSUPPORTED,
+    STG_REQUIRE(path.scene() || !(L.flags & STG_OPT_BF16_STORE), STG_EUNSUPPORTED,
                 "stg_model_bwd: bf16 storage (STG_OPT_BF16_STORE) is built for the wave-per-scene kernels only");
     STG_REQUIRE(!((L.flags & STG_OPT_BF16_STORE) && (L.flags & STG_OPT_SPLIT_BF16)), STG_EUNSUPPORTED,
                 "stg_model_bwd: STG_OPT_BF16_STORE and STG_OPT_SPLIT_BF16 cannot be combined");
     if (nll_target && ((L.flags & STG_OPT_SPLIT_BF16) || L.n_txp == 0))
         return STG_EUNSUPPORTED;        // (no message: the caller falls back to stg_nll_fwd + stg_model_bwd)
-    STG_REQUIRE(!(wave_path && dx), STG_EUNSUPPORTED,
+    STG_REQUIRE(!(path.scene() && dx), STG_EUNSUPPORTED,
                 "stg_model_bwd: dx is only computed by the workgroup-per-scene kernels: set STG_OPT_WG_PATH in the "
                 "descriptor of the forward and the backward call");
     a.params = params; a.buffers = buffers; a.x = x;
@@ -543,10 +540,11 @@ static int model_bwd_impl(const stg_model_desc *d, const float *params, const fl
     // ragged batch: sorted scene list at the tail of the scratch buffer
     int32_t *order = reinterpret_cast<int32_t *>(scratch + cv.order);
     bool sorted;
-    if (wave_path && scene_order_applies(num_peds, N, V)) {
-        // the wave-per-scene forward left its order in the workspace's batch tail (stg_model_ws_tail_floats)
-        order = reinterpret_cast<int32_t *>(const_cast<float *>(ws) + (int64_t)N * ws_floats_per_scene(L, V) +
-                                            ws_tail_wp_floats(L, V));
+    const WsTail wt = ws_tail(L, path, N, V);
+    const float *ws_end = ws + wt.base;       // (the batch tail of the workspace)
+    if (tail_has_order(path, num_peds, N, V)) {
+        // the forward left its order in the workspace's batch tail
+        order = reinterpret_cast<int32_t *>(const_cast<float *>(ws_end) + wt.order);
         sorted = true;
     } else {
         sorted = launch_scene_order(num_peds, N, V, order, order + N, st, order + N + V + 2);
@@ -556,7 +554,7 @@ static int model_bwd_impl(const stg_model_desc *d, const float *params, const fl
     a.tier = SceneTier{sorted ? order : nullptr, sorted ? order + N : nullptr, -1, V, serp};
     a.debug_skip = diag_env("STG_DEBUG_SKIP", 0);
     int slab_rows;
-    if (wave_path) {
+    if (path.scene()) {
         // K1 (wave per scene): TXP input-gradient chain + st_gcn block backward; one small-gradient row per scene
         TxpBwdArgs t{};
         t.lay = L; t.params = params; t.num_peds = num_peds; t.N = N; t.V = V; t.dy = dy; t.ws = ws;
@@ -568,60 +566,41 @@ static int model_bwd_impl(const stg_model_desc *d, const float *params, const fl
         t.debug_skip = a.debug_skip;
         t.split_bf16 = (L.flags & STG_OPT_SPLIT_BF16) ? 1 : 0;
         t.stagger = diag_env("STG_STAGGER_B", 0);
-        // the prepared A operands of the exact-bf16 chain sit in the batch tail of the workspace (written by the forward)
-        if (txp_bwd_x6_fits(L, V))
-            t.wp = reinterpret_cast<const unsigned *>(ws + (int64_t)N * a.ws_stride);
-        const int rcw = launch_txp_bwd_wave(t, st);
+        if (wt.wp >= 0) t.wp = reinterpret_cast<const unsigned *>(ws_end + wt.wp);
+        const int rcw = launch_scene_bwd(path, t, st);
         if (rcw != STG_OK) return rcw;
         slab_rows = N;
     } else {
-        const int waves = bwd_waves(L, N, V);
+        const int waves = bwd_waves(path, V);
         const size_t lds = bwd_lds_bytes(L, V, waves);
         STG_REQUIRE(lds <= (size_t)kLdsBytes, STG_ELDS, "stg_model_bwd: V=%d needs %zu bytes of LDS (> %d)", V, lds,
                     kLdsBytes);
-        const int grid = bwd_grid(L, N, V);
-#define STG_LAUNCH_BWD(W)                                                                                    \
-    do {                                                                                                     \
-        hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(&model_bwd_kernel<W>),            \
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);           \
-        if (e_ != hipSuccess) return hip_fail(e_, "stg_model_bwd: hipFuncSetAttribute");                     \
-        hipLaunchKernelGGL(model_bwd_kernel<W>, dim3(grid), dim3(W * 64), lds, st, a, params);               \
-    } while (0)
+        const int grid = bwd_grid(L, path, N, V);
+        void (*k1)(BwdArgs, const float *);
+        switch (waves) {
+            case 1: k1 = model_bwd_kernel<1>; break;
+            case 2: k1 = model_bwd_kernel<2>; break;
+            case 4: k1 = model_bwd_kernel<4>; break;
+            default: k1 = model_bwd_kernel<8>; break;
+        }
         slab_rows = grid;
-        if (a.tier.order && bwd_grid_small(L, N, V) > 0) {
-            // large scenes: `waves` per scene, slab rows [0, grid); small scenes: one wave per scene with the LDS image
-            // (and so the residency) of V = kBwdTierV, slab rows behind them
-            a.tier.v_lo = kBwdTierV;
-            switch (waves) {
-                case 1: STG_LAUNCH_BWD(1); break;
-                case 2: STG_LAUNCH_BWD(2); break;
-                case 4: STG_LAUNCH_BWD(4); break;
-                default: STG_LAUNCH_BWD(8); break;
-            }
-            STG_LAUNCH_CHECK("stg_model_bwd: K1 (large scenes)");
-            const int grid_hi = grid;
-            {
-                const int grid = bwd_grid_small(L, N, V);
-                const size_t lds = bwd_lds_bytes(L, kBwdTierV, 1);
-                a.Vl = kBwdTierV;
-                a.tier.v_lo = -1; a.tier.v_hi = kBwdTierV;
-                a.slab1 = rows + (int64_t)grid_hi * n_small;
-                STG_LAUNCH_BWD(1);
-                slab_rows = grid_hi + grid;
-            }
+        const int grid_small = a.tier.order ? bwd_grid_small(L, N, V) : 0;
+        if (grid_small > 0) a.tier.v_lo = kBwdTierV;        // large scenes only: `waves` per scene, slab rows [0, grid)
+        int rck = launch(Launch{"stg_model_bwd: K1", dim3(grid), dim3(waves * 64), lds, st}, k1, a, params);
+        if (rck != STG_OK) return rck;
+        if (grid_small > 0) {
+            // small scenes: one wave per scene with the LDS image (and so the residency) of V = kBwdTierV, slab rows behind
+            a.Vl = kBwdTierV;
+            a.tier.v_lo = -1; a.tier.v_hi = kBwdTierV;
+            a.slab1 = rows + (int64_t)grid * n_small;
+            rck = launch(Launch{"stg_model_bwd: K1 (small scenes)", dim3(grid_small), dim3(64), bwd_lds_bytes(L, kBwdTierV, 1), st},
+                         model_bwd_kernel<1>, a, params);
+            if (rck != STG_OK) return rck;
+            slab_rows = grid + grid_small;
             a.slab1 = rows;
             a.Vl = 0;
-            a.tier.v_lo = -1; a.tier.v_hi = V;
-        } else {
-            switch (waves) {
-                case 1: STG_LAUNCH_BWD(1); break;
-                case 2: STG_LAUNCH_BWD(2); break;
-                case 4: STG_LAUNCH_BWD(4); break;
-                default: STG_LAUNCH_BWD(8); break;
-            }
+            a.tier.v_hi = V;
         }
-#undef STG_LAUNCH_BWD
-        STG_LAUNCH_CHECK("stg_model_bwd: K1");
     }
     evl.mark();
 

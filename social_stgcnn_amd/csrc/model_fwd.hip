@@ -17,7 +17,8 @@
 // wave-per-scene TXP kernel of txp_wave.hip (F2) in that kernel's in-place plane layout.
 #include "model_common.hpp"
 #include "stgcn_block.hpp"
-#include "txp_wave.hpp"
+#include "txp_scene_common.hpp"
+#include "step_plan.hpp"
 
 namespace stg {
 
@@ -223,38 +224,7 @@ static size_t fwd_lds_bytes(int V, int waves) {
     return (size_t)(plane + reg + waves * 16 + 16) * sizeof(float);
 }
 
-// scratch carve of stg_model_fwd: [aggregated input of block 0: N x (cin + 1) T V | scene order | (diag) stamps]
-static int64_t fwd_agg_floats(const ModelLayout &l, int N, int V) {
-    return (((int64_t)N * (l.blk[0].cin + 1) * Cfg::T * V + 3) & ~(int64_t)3) + 4;
-}
-
-// ... | prepared forward operands of the exact-bf16 convs (16-byte vectors)]
-static int64_t fwd_wp_off(const ModelLayout &l, int N, int V, bool stamps) {
-    return (fwd_agg_floats(l, N, V) + order_floats(N, V) + (stamps ? (int64_t)N * 32 : 0) + 3) & ~(int64_t)3;
-}
-
 }  // namespace stg
-
-// batch tail of the training workspace: [prepared operands of the exact-bf16 input-gradient chain | scene order]
-namespace stg {
-int64_t ws_tail_wp_floats(const ModelLayout &l, int V) { return txp_bwd_x6_fits(l, V) ? txp_bwd_x6_wp_floats(l) : 0; }
-}
-extern "C" int64_t stg_model_ws_tail_floats(const stg_model_desc *d, int N, int V) {
-    stg::ModelLayout l;
-    const int rc = stg::make_layout(d, &l);
-    if (rc != STG_OK) return rc;
-    if (N < 0 || V <= 0) return stg::fail(STG_EINVAL, "stg_model_ws_tail_floats: N=%d V=%d", N, V);
-    return stg::ws_tail_wp_floats(l, V) + stg::order_floats(N, V);
-}
-
-extern "C" int64_t stg_model_fwd_scratch_floats(const stg_model_desc *d, int N, int V) {
-    stg::ModelLayout l;
-    const int rc = stg::make_layout(d, &l);
-    if (rc != STG_OK) return rc;
-    if (N < 0 || V <= 0) return stg::fail(STG_EINVAL, "stg_model_fwd_scratch_floats: N=%d V=%d", N, V);
-    const bool stamps = stg::diag_env("STG_STAMPS", 0) != 0;
-    return stg::fwd_wp_off(l, N, V, stamps) + (stg::txp_fwd_x6_fits(l, V) ? stg::txp_bwd_x6_wp_floats(l) : 0);
-}
 
 extern "C" int stg_model_fwd(const stg_model_desc *d, const float *params, const float *buffers, const float *x,
                              int64_t x_sn, int64_t x_sc, int64_t x_st, int64_t x_sv, const float *adj,
@@ -275,9 +245,11 @@ extern "C" int stg_model_fwd(const stg_model_desc *d, const float *params, const
     a.x_sn = x_sn; a.x_sc = x_sc; a.x_st = x_st; a.x_sv = x_sv;
     a.adj = adj; a.a_sn = a_sn; a.num_peds = num_peds; a.N = N; a.V = V;
     a.y = y; a.ws = ws; a.ws_stride = ws_floats_per_scene(L, V); a.stats = stats;
-    int auto_waves = 0;
-    const bool wave_path = use_wave_path(L, N, V, &auto_waves);
-    STG_REQUIRE(wave_path || !(L.flags & STG_OPT_BF16_STORE), STG_EUNSUPPORTED,
+    const StepPath path = choose_path(L, N, V);
+    const FwdCarve fc = fwd_carve(L, path, N, V);
+    const WsTail wt = ws_tail(L, path, N, V);
+    float *ws_end = ws ? ws + wt.base : nullptr;       // (the batch tail of the workspace)
+    STG_REQUIRE(path.scene() || !(L.flags & STG_OPT_BF16_STORE), STG_EUNSUPPORTED,
                 "stg_model_fwd: bf16 storage (STG_OPT_BF16_STORE) is built for the wave-per-scene kernels only "
                 "(one st_gcn block, input_feat 2, V <= 68, no STG_OPT_WG_PATH)");
     hipStream_t st = as_stream(stream);
@@ -291,11 +263,14 @@ extern "C" int stg_model_fwd(const stg_model_desc *d, const float *params, const
         a.agg_ax = L.ws_hdr_floats + (int64_t)b0.ws_ax * V;
         a.agg_cs = L.ws_hdr_floats + (int64_t)b0.ws_cs * V;
     } else {
-        a.agg = scratch; a.agg_stride = (int64_t)(b0.cin + 1) * Cfg::T * V;
+        a.agg = scratch + fc.agg; a.agg_stride = (int64_t)(b0.cin + 1) * Cfg::T * V;
         a.agg_ax = 0;
         a.agg_cs = (int64_t)b0.cin * Cfg::T * V;
     }
     a.debug_skip = diag_env("STG_DEBUG_SKIP", 0);
+    // the scene order of a ragged batch: training on a scene path leaves it in the workspace's batch tail, where the
+    // backward finds it (tail_has_order) -- no second sort
+    int32_t *order = reinterpret_cast<int32_t *>(ws_end && path.scene() ? ws_end + wt.order : scratch + fc.order);
     bool sorted_in_agg = false;
     {
         // training on the wave-per-scene path: the launch also prepares the backward's exact-bf16 A operands into the
@@ -304,28 +279,21 @@ extern "C" int stg_model_fwd(const stg_model_desc *d, const float *params, const
         prep.params = params;
         prep.n_layers = L.L + 1;
         for (int l = 0; l <= L.L; ++l) prep.w_off[l] = l < L.L ? L.txp_w[l] : L.out_w;
-        if (ws && wave_path && txp_bwd_x6_fits(L, V)) prep.wp = reinterpret_cast<unsigned *>(ws + (int64_t)N * a.ws_stride);
+        if (ws_end && wt.wp >= 0) prep.wp = reinterpret_cast<unsigned *>(ws_end + wt.wp);
         // ... and the forward's own (this launch's successor reads them from the scratch buffer)
-        if (wave_path && txp_fwd_x6_fits(L, V))
-            prep.wp_fwd = reinterpret_cast<unsigned *>(scratch + fwd_wp_off(L, N, V, diag_env("STG_STAMPS", 0) != 0));
+        if (fc.wp_fwd >= 0) prep.wp_fwd = reinterpret_cast<unsigned *>(scratch + fc.wp_fwd);
         // ... and, for a ragged batch on the wave-per-scene path, the scene order: one more workgroup of this launch
-        // (training: into the workspace's batch tail, where the backward finds it -- no second sort)
-        int32_t *order0 = reinterpret_cast<int32_t *>(scratch + fwd_agg_floats(L, N, V));
-        if (ws && wave_path) order0 = reinterpret_cast<int32_t *>(ws + (int64_t)N * a.ws_stride + ws_tail_wp_floats(L, V));
-        sorted_in_agg = wave_path && agg_sorts(num_peds, N, V);
-        if (sorted_in_agg) { prep.order = order0; prep.key_start = order0 + N; prep.order_peds = order0 + N + V + 2; }
+        sorted_in_agg = path.scene() && agg_sorts(num_peds, N, V);
+        if (sorted_in_agg) { prep.order = order; prep.key_start = order + N; prep.order_peds = order + N + V + 2; }
         const int rca = launch_stgcn_agg(b0.cin, x, x_sn, x_sc, x_st, x_sv, adj, a_sn, num_peds, N, V,
                                          const_cast<float *>(a.agg), a.agg_stride, a.agg_ax, a.agg_cs, st,
                                          (prep.wp || prep.wp_fwd || prep.order) ? &prep : nullptr);
         if (rca != STG_OK) return rca;
     }
     evl.mark();
-    int32_t *order = reinterpret_cast<int32_t *>(scratch + fwd_agg_floats(L, N, V));
-    if (wave_path) {
+    if (path.scene()) {
         // K1: ONE wave-per-scene kernel for the whole model: st_gcn block (VALU) + TXP-CNN (MFMA), the a_0 plane never
-        // leaves LDS.  Ragged batch: sorted scene list, walked boustrophedon.  Training: the order (with its tier offsets
-        // and the sorted counts) goes to the workspace's batch tail, where the backward finds it -- no second sort.
-        if (ws) order = reinterpret_cast<int32_t *>(ws + (int64_t)N * a.ws_stride + ws_tail_wp_floats(L, V));
+        // leaves LDS.  Ragged batch: sorted scene list, walked boustrophedon.
         bool sorted = sorted_in_agg;                   // (sorted by a workgroup of the aggregation launch above ...)
         if (!sorted) {                                  // (... or, for a large batch, by the 16-wave kernel)
             sorted = launch_scene_order(num_peds, N, V, order, order + N, st, order + N + V + 2);
@@ -337,9 +305,8 @@ extern "C" int stg_model_fwd(const stg_model_desc *d, const float *params, const
         t.adj = adj; t.a_sn = a_sn;
         t.agg = a.agg; t.agg_stride = a.agg_stride; t.agg_ax = a.agg_ax; t.agg_cs = a.agg_cs;
         t.y = y; t.ws = ws; t.ws_stride = a.ws_stride; t.stats = stats;
-        if (txp_fwd_x6_fits(L, V))
-            t.wpf = reinterpret_cast<const unsigned *>(scratch + fwd_wp_off(L, N, V, diag_env("STG_STAMPS", 0) != 0));
-        t.stamps = diag_env("STG_STAMPS", 0) ? reinterpret_cast<unsigned long long *>(scratch + fwd_agg_floats(L, N, V) + order_floats(N, V)) : nullptr;
+        if (fc.wp_fwd >= 0) t.wpf = reinterpret_cast<const unsigned *>(scratch + fc.wp_fwd);
+        if (fc.stamps >= 0) t.stamps = reinterpret_cast<unsigned long long *>(scratch + fc.stamps);
         const int serp = diag_env("STG_WALK", 1);
         // one launch for the whole (sorted) batch: V-tiers in separate launches were measured slower -- the few
         // large scenes of a real batch take one wave tens of microseconds each and need the small ones to overlap
@@ -347,32 +314,25 @@ extern "C" int stg_model_fwd(const stg_model_desc *d, const float *params, const
         t.Vl = V;
         t.debug_skip = a.debug_skip;
         t.stagger = diag_env("STG_STAGGER_F", 0);
-        const int rcw = launch_txp_fwd_wave(t, st);
+        const int rcw = launch_scene_fwd(path, t, st);
         evl.mark();
         evl.finish();
         return rcw;
     }
     int waves = V <= 12 ? 1 : (V <= 40 ? 2 : (V <= 80 ? 4 : 8));
-    if (auto_waves) waves = auto_waves;
+    if (path.wg_waves) waves = path.wg_waves;
     const size_t lds = fwd_lds_bytes(V, waves);
     STG_REQUIRE(lds <= (size_t)kLdsBytes, STG_ELDS, "stg_model_fwd: V=%d needs %zu bytes of LDS (> %d)", V, lds,
                 kLdsBytes);
-    const dim3 grid((unsigned)N);
-#define STG_LAUNCH_FWD(W)                                                                                    \
-    do {                                                                                                     \
-        hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(&model_fwd_kernel<W>),            \
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);           \
-        if (e_ != hipSuccess) return hip_fail(e_, "stg_model_fwd: hipFuncSetAttribute");                     \
-        hipLaunchKernelGGL(model_fwd_kernel<W>, grid, dim3(W * 64), lds, st, a, params, buffers);                             \
-    } while (0)
+    const Launch lc{"stg_model_fwd", dim3((unsigned)N), dim3(waves * 64), lds, st};
+    int rck;
     switch (waves) {
-        case 1: STG_LAUNCH_FWD(1); break;
-        case 2: STG_LAUNCH_FWD(2); break;
-        case 4: STG_LAUNCH_FWD(4); break;
-        default: STG_LAUNCH_FWD(8); break;
+        case 1: rck = launch(lc, model_fwd_kernel<1>, a, params, buffers); break;
+        case 2: rck = launch(lc, model_fwd_kernel<2>, a, params, buffers); break;
+        case 4: rck = launch(lc, model_fwd_kernel<4>, a, params, buffers); break;
+        default: rck = launch(lc, model_fwd_kernel<8>, a, params, buffers); break;
     }
-#undef STG_LAUNCH_FWD
-    STG_LAUNCH_CHECK("stg_model_fwd");
+    if (rck != STG_OK) return rck;
     evl.mark();
     evl.finish();
     return STG_OK;

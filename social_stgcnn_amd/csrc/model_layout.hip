@@ -3,6 +3,8 @@
 #include <type_traits>
 #include "model_common.hpp"
 #include "scene_order.hpp"
+#include "step_plan.hpp"
+#include "txp_wave.hpp"
 
 namespace stg {
 
@@ -47,6 +49,56 @@ bool is_canonical(const ModelLayout &L) {
     return std::memcmp(&c, &kCanonLayout, sizeof c) == 0;
 }
 
+// ---- the plan of a model step (step_plan.hpp) ------------------------------------------------------------------
+// A small batch of small scenes (fewer scenes than resident wave slots: every scene's latency chain is the step) runs
+// the workgroup-per-scene kernels with several waves per scene instead of the fp32-MFMA wave kernels (measured: N = 512
+// x 4 waves 2.9 vs 2.5 M scene-windows/s, N = 128 x 8 waves 0.95 vs 0.70).  The exact-bf16 kernels cut the scenes of a
+// small batch into finer teams themselves (team_geom) and keep every batch they fit.
+constexpr int kSmallBatch = 288;      // measured: 256 scenes 1.89 (workgroup kernels) vs 1.79 M/s (a wave per scene), 320 scenes 2.10 vs 2.19
+
+StepPath choose_path(const ModelLayout &L, int N, int V) {
+    StepPath p{StepPath::Workgroup, L.wg_waves, txp_fwd_x6_fits(L, V), txp_bwd_x6_fits(L, V)};
+    // a wave (or a team of waves) per scene: the whole model with one st_gcn block on the two input features
+    if (L.n_txp < 1 || L.n_blocks != 1 || L.blk[0].cin != Cfg::CIN0 || (L.flags & STG_OPT_WG_PATH)) return p;
+    if (p.fwd_x6 && p.bwd_x6) {
+        p.kind = StepPath::SceneX6;
+    } else if (txp_wave_f32_fits(V)) {
+        if (N >= kSmallBatch || L.wg_waves != 0 || V > 40 || (L.flags & (STG_OPT_WAVE_PATH | STG_OPT_BF16_STORE)))
+            p.kind = StepPath::WaveF32;
+        else
+            p.wg_waves = N <= 192 ? 8 : 4;     // 2048 resident wave slots / N scenes, at most the 8 waves a scene's tiles can use
+    }
+    return p;
+}
+
+FwdCarve fwd_carve(const ModelLayout &L, const StepPath &path, int N, int V) {
+    const bool stamps = diag_env("STG_STAMPS", 0) != 0;
+    FwdCarve c;
+    c.agg = 0;
+    c.order = (((int64_t)N * (L.blk[0].cin + 1) * Cfg::T * V + 3) & ~(int64_t)3) + 4;
+    c.stamps = stamps ? c.order + order_floats(N, V) : -1;
+    const int64_t wp = (c.order + order_floats(N, V) + (stamps ? (int64_t)N * 32 : 0) + 3) & ~(int64_t)3;   // (16-byte vectors)
+    c.wp_fwd = path.scene() && path.fwd_x6 ? wp : -1;
+    c.total = wp + (path.fwd_x6 ? txp_bwd_x6_wp_floats(L) : 0);
+    return c;
+}
+
+WsTail ws_tail(const ModelLayout &L, const StepPath &path, int N, int V) {
+    WsTail t;
+    t.base = (int64_t)N * ws_floats_per_scene(L, V);
+    t.wp = path.scene() && path.bwd_x6 ? 0 : -1;
+    t.order = path.bwd_x6 ? txp_bwd_x6_wp_floats(L) : 0;
+    t.total = t.order + order_floats(N, V);
+    return t;
+}
+
+int launch_scene_fwd(const StepPath &path, const TxpFwdArgs &a, hipStream_t st) {
+    return path.fwd_x6 ? launch_txp_fwd_x6(a, st) : launch_txp_fwd_wave(a, st);
+}
+int launch_scene_bwd(const StepPath &path, const TxpBwdArgs &a, hipStream_t st) {
+    return path.bwd_x6 ? launch_txp_bwd_x6(a, st) : launch_txp_bwd_wave(a, st);
+}
+
 __global__ __launch_bounds__(1024) void scene_order_kernel(const int32_t *__restrict__ num_peds, int N, int V,
                                                            int32_t *__restrict__ order,
                                                            int32_t *__restrict__ key_start,
@@ -88,6 +140,20 @@ int64_t stg_model_ws_floats(const stg_model_desc *d, int V) {
     if (rc != STG_OK) return rc;
     if (V <= 0) return stg::fail(STG_EINVAL, "stg_model_ws_floats: V=%d", V);
     return stg::ws_floats_per_scene(l, V);
+}
+int64_t stg_model_ws_tail_floats(const stg_model_desc *d, int N, int V) {
+    stg::ModelLayout l;
+    const int rc = stg::make_layout(d, &l);
+    if (rc != STG_OK) return rc;
+    if (N < 0 || V <= 0) return stg::fail(STG_EINVAL, "stg_model_ws_tail_floats: N=%d V=%d", N, V);
+    return stg::ws_tail(l, stg::choose_path(l, N, V), N, V).total;
+}
+int64_t stg_model_fwd_scratch_floats(const stg_model_desc *d, int N, int V) {
+    stg::ModelLayout l;
+    const int rc = stg::make_layout(d, &l);
+    if (rc != STG_OK) return rc;
+    if (N < 0 || V <= 0) return stg::fail(STG_EINVAL, "stg_model_fwd_scratch_floats: N=%d V=%d", N, V);
+    return stg::fwd_carve(l, stg::choose_path(l, N, V), N, V).total;
 }
 int stg_scene_order(const int32_t *num_peds, int N, int V, int32_t *order, int32_t *key_start, void *stream) {
     STG_REQUIRE(N >= 0 && V > 0, STG_EINVAL, "stg_scene_order: bad sizes N=%d V=%d", N, V);

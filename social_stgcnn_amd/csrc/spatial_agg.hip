@@ -137,13 +137,12 @@ __global__ __launch_bounds__(256) void spatial_agg_fwd_quarters_kernel(
                     }
                 }
             }
-#define STG_ROR_ADD(v_, ctrl) v_ += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v_), (ctrl), 0xf, 0xf, false))
 #pragma unroll
             for (int c = 0; c < kAggMaxC; ++c) {
                 if (c < cn) {
                     // the four quarters: lanes l, l + 4, l + 8, l + 12 of the 16-lane row (row_ror:4, then row_ror:8)
-                    STG_ROR_ADD(acc[c].x, 0x124); STG_ROR_ADD(acc[c].y, 0x124); STG_ROR_ADD(acc[c].z, 0x124); STG_ROR_ADD(acc[c].w, 0x124);
-                    STG_ROR_ADD(acc[c].x, 0x128); STG_ROR_ADD(acc[c].y, 0x128); STG_ROR_ADD(acc[c].z, 0x128); STG_ROR_ADD(acc[c].w, 0x128);
+                    dpp_add<0x124>(acc[c].x); dpp_add<0x124>(acc[c].y); dpp_add<0x124>(acc[c].z); dpp_add<0x124>(acc[c].w);
+                    dpp_add<0x128>(acc[c].x); dpp_add<0x128>(acc[c].y); dpp_add<0x128>(acc[c].z); dpp_add<0x128>(acc[c].w);
                     if (live && q == 0) {
                         float4 r;
                         r.x = (w0 + 0 < vi) ? acc[c].x : 0.f;
@@ -154,7 +153,6 @@ __global__ __launch_bounds__(256) void spatial_agg_fwd_quarters_kernel(
                     }
                 }
             }
-#undef STG_ROR_ADD
         }
     }
 }
@@ -251,12 +249,10 @@ __global__ __launch_bounds__(256) void spatial_agg_bwd_kernel(
 // time step reads the same 128 bytes).
 template <int LPR>
 __device__ __forceinline__ float row_group_sum(float v) {
-#define STG_DPP_ADD(ctrl) v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), (ctrl), 0xf, 0xf, false))
-    if (LPR >= 2) STG_DPP_ADD(0xB1);       // quad_perm [1,0,3,2]
-    if (LPR >= 4) STG_DPP_ADD(0x4E);       // quad_perm [2,3,0,1]
-    if (LPR >= 8) STG_DPP_ADD(0x141);      // row_half_mirror: every lane holds the sum of its 8 lanes
-    if (LPR >= 16) STG_DPP_ADD(0x140);     // row_mirror: ... of its 16 lanes
-#undef STG_DPP_ADD
+    if (LPR >= 2) dpp_add<0xB1>(v);       // quad_perm [1,0,3,2]
+    if (LPR >= 4) dpp_add<0x4E>(v);       // quad_perm [2,3,0,1]
+    if (LPR >= 8) dpp_add<0x141>(v);      // row_half_mirror: every lane holds the sum of its 8 lanes
+    if (LPR >= 16) dpp_add<0x140>(v);     // row_mirror: ... of its 16 lanes
     return v;
 }
 
@@ -371,22 +367,10 @@ int stg_spatial_agg_bwd(const float *dy, const float *adj, int64_t a_sn, const i
             case 32: hipLaunchKernelGGL(stg::spatial_agg_bwd_rows_kernel<8>, dim3((unsigned)N), dim3(256), lds, stg::as_stream(stream), dy, adj, a_sn, num_peds, C, T, dx); break;
             default: hipLaunchKernelGGL(stg::spatial_agg_bwd_rows_kernel<16>, dim3((unsigned)N), dim3(256), lds, stg::as_stream(stream), dy, adj, a_sn, num_peds, C, T, dx); break;
         }
-    } else if (vec4) {
-        if (lds > 64 * 1024) {
-            hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(&stg::spatial_agg_bwd_kernel<4>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e_ != hipSuccess) return stg::hip_fail(e_, "stg_spatial_agg_bwd: hipFuncSetAttribute");
-        }
-        hipLaunchKernelGGL(stg::spatial_agg_bwd_kernel<4>, dim3((unsigned)N), dim3(256), lds, stg::as_stream(stream), dy, adj,
-                           a_sn, num_peds, C, T, V, dx);
     } else {
-        if (lds > 64 * 1024) {
-            hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(&stg::spatial_agg_bwd_kernel<1>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e_ != hipSuccess) return stg::hip_fail(e_, "stg_spatial_agg_bwd: hipFuncSetAttribute");
-        }
-        hipLaunchKernelGGL(stg::spatial_agg_bwd_kernel<1>, dim3((unsigned)N), dim3(256), lds, stg::as_stream(stream), dy, adj,
-                           a_sn, num_peds, C, T, V, dx);
+        const stg::Launch lc{"stg_spatial_agg_bwd", dim3((unsigned)N), dim3(256), lds, stg::as_stream(stream), 64 * 1024};
+        return stg::launch(lc, vec4 ? stg::spatial_agg_bwd_kernel<4> : stg::spatial_agg_bwd_kernel<1>, dy, adj, a_sn, num_peds, C, T,
+                           V, dx);
     }
     STG_LAUNCH_CHECK("stg_spatial_agg_bwd");
     return STG_OK;

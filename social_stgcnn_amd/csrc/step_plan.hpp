@@ -1,0 +1,57 @@
+// The host-side plan of one model step (model_layout.hip): which kernels serve a batch, and where the buffers that the
+// forward and the backward share keep their parts.  Entry points and size queries compute it once per call from
+// (layout, N, V); nothing else decides a path or adds up an offset.
+#pragma once
+#include "model_common.hpp"
+
+namespace stg {
+
+struct TxpFwdArgs;
+struct TxpBwdArgs;
+
+// SceneX6: the exact-bf16 scene kernels in both passes (txp_x6.hip; one wave per scene or the team launch: team_wanted).
+// WaveF32: a wave per scene with the round-1 fp32-MFMA kernels (txp_wave.hip) in at least one pass -- STG_OPT_F32_MFMA,
+//   STG_OPT_SPLIT_BF16 (forward x6, backward two-piece bf16), the diagnostic STG_FWD_F32 / STG_BWD_F32.
+// Workgroup: the workgroup-per-scene kernels of model_fwd.hip / model_bwd.hip, `wg_waves` waves per scene (0: by V).
+struct StepPath {
+    enum Kind { SceneX6, WaveF32, Workgroup } kind;
+    int wg_waves;
+    bool fwd_x6, bwd_x6;   // the exact-bf16 kernels fit this pass at (layout, V): they run it unless kind == Workgroup,
+                           // and their prepared operands have room in the buffers whatever the kind
+    bool scene() const { return kind != Workgroup; }
+};
+StepPath choose_path(const ModelLayout &L, int N, int V);
+
+// Scratch of stg_model_fwd (offsets in floats; -1: not in use on this path):
+//   agg     aggregated input of block 0, N x (cin + 1) T V -- inference only (training: straight into the workspace)
+//   order   sorted scene list + tier offsets + sorted counts -- inference, and training on the Workgroup path
+//   stamps  [N][16] 64-bit cycle stamps of the scene kernels (diagnostic build with STG_STAMPS=1)
+//   wp_fwd  prepared forward operands of the exact-bf16 convs: written by the aggregation launch, read by the scene
+//           launch behind it, when path.scene() && path.fwd_x6
+struct FwdCarve {
+    int64_t agg, order, stamps, wp_fwd, total;
+};
+FwdCarve fwd_carve(const ModelLayout &L, const StepPath &path, int N, int V);
+
+// Batch tail of the training workspace, `base` floats behind its start: the N per-scene blocks (offsets in floats from
+// ws + base; -1: not in use):
+//   wp      prepared input-gradient operands of the exact-bf16 convs: written by the forward's aggregation launch, read
+//           by the backward's scene launch, when path.scene() && path.bwd_x6
+//   order   sorted scene list + tier offsets + sorted counts: written by the forward (aggregation launch or
+//           scene_order_kernel), read by the backward, when tail_has_order() -- the backward takes it on trust, so both
+//           passes must be given the same descriptor, N, V and num_peds
+// `total` (stg_model_ws_tail_floats, ABI) reserves the operands wherever path.bwd_x6 holds, also on the Workgroup path
+// that does not use them: the reservation is wider than the use.
+struct WsTail {
+    int64_t base, wp, order, total;
+};
+WsTail ws_tail(const ModelLayout &L, const StepPath &path, int N, int V);
+inline bool tail_has_order(const StepPath &path, const int32_t *num_peds, int N, int V) {
+    return path.scene() && scene_order_applies(num_peds, N, V);
+}
+
+// the scene launch of a pass on a path with scene(): exact-bf16 or fp32-MFMA kernels as the path says
+int launch_scene_fwd(const StepPath &path, const TxpFwdArgs &a, hipStream_t st);
+int launch_scene_bwd(const StepPath &path, const TxpBwdArgs &a, hipStream_t st);
+
+}  // namespace stg

@@ -196,7 +196,6 @@ __global__ __launch_bounds__(256) void stgcn_agg_q32_kernel(const float *__restr
     }
     __syncthreads();
     float *axo = out + n * out_stride + ax_off, *cso = out + n * out_stride + cs_off;
-#define STG_ROR_ADD(v_, ctrl) v_ += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v_), (ctrl), 0xf, 0xf, false))
 #pragma unroll
     for (int pass = 0; pass < T / (4 * TL); ++pass) {
         const int t = pass * 4 * TL + wave * TL + tl;
@@ -219,8 +218,8 @@ __global__ __launch_bounds__(256) void stgcn_agg_q32_kernel(const float *__restr
         }
 #pragma unroll
         for (int c = 0; c <= CIN; ++c) {
-            STG_ROR_ADD(acc[c].x, 0x124); STG_ROR_ADD(acc[c].y, 0x124); STG_ROR_ADD(acc[c].z, 0x124); STG_ROR_ADD(acc[c].w, 0x124);
-            STG_ROR_ADD(acc[c].x, 0x128); STG_ROR_ADD(acc[c].y, 0x128); STG_ROR_ADD(acc[c].z, 0x128); STG_ROR_ADD(acc[c].w, 0x128);
+            dpp_add<0x124>(acc[c].x); dpp_add<0x124>(acc[c].y); dpp_add<0x124>(acc[c].z); dpp_add<0x124>(acc[c].w);
+            dpp_add<0x128>(acc[c].x); dpp_add<0x128>(acc[c].y); dpp_add<0x128>(acc[c].z); dpp_add<0x128>(acc[c].w);
         }
         if (q == 0) {
             // outputs are compact ([.][T][vi]): 16-byte stores when the scene fills its 32 slots, scalar ones otherwise
@@ -238,7 +237,6 @@ __global__ __launch_bounds__(256) void stgcn_agg_q32_kernel(const float *__restr
             }
         }
     }
-#undef STG_ROR_ADD
 }
 
 }  // namespace
@@ -261,37 +259,18 @@ int launch_stgcn_agg(int cin, const float *x, int64_t x_sn, int64_t x_sc, int64_
     const bool can_q32 = ((reinterpret_cast<uintptr_t>(adj) & 15) == 0) && (a_sn % 4 == 0) &&
                          ((reinterpret_cast<uintptr_t>(out) & 15) == 0) && (out_stride % 4 == 0) && (ax_off % 4 == 0) &&
                          (cs_off % 4 == 0);
-#define STG_AGG(CI, VE)                                                                                          \
-    do {                                                                                                         \
-        if (lds > 64 * 1024) {                                                                                   \
-            hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(&stgcn_agg_kernel<CI, VE>),       \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);           \
-            if (e_ != hipSuccess) return hip_fail(e_, "stgcn_agg: hipFuncSetAttribute");                        \
-        }                                                                                                        \
-        hipLaunchKernelGGL((stgcn_agg_kernel<CI, VE>), grid, block, lds, st, x, x_sn, x_sc, x_st, x_sv, adj, a_sn, \
-                           num_peds, N, V, out, out_stride, ax_off, cs_off, prep);                               \
-    } while (0)
     // V = 32 with 16-byte aligned rows and outputs: the quarters form
     const bool q32 = V == 32 && can_q32 && !diag_env("STG_AGG_COLS", 0);
     if (q32) {
         const size_t lds32 = lds > (size_t)cin * T * 32 * sizeof(float) ? lds : (size_t)cin * T * 32 * sizeof(float);
-        if (cin == Cfg::CIN0)
-            hipLaunchKernelGGL((stgcn_agg_q32_kernel<Cfg::CIN0>), grid, block, lds32, st, x, x_sn, x_sc, x_st, x_sv, adj, a_sn,
-                               num_peds, N, out, out_stride, ax_off, cs_off, prep);
-        else
-            hipLaunchKernelGGL((stgcn_agg_q32_kernel<Cfg::C>), grid, block, lds32, st, x, x_sn, x_sc, x_st, x_sv, adj, a_sn,
-                               num_peds, N, out, out_stride, ax_off, cs_off, prep);
-        STG_LAUNCH_CHECK("stgcn_agg");
-        return STG_OK;
+        const Launch lc{"stgcn_agg", grid, block, lds32, st, (size_t)kLdsBytes};     // (24 KB at most: the limit is never raised)
+        return launch(lc, cin == Cfg::CIN0 ? stgcn_agg_q32_kernel<Cfg::CIN0> : stgcn_agg_q32_kernel<Cfg::C>, x, x_sn, x_sc, x_st,
+                      x_sv, adj, a_sn, num_peds, N, out, out_stride, ax_off, cs_off, prep);
     }
-    if (cin == Cfg::CIN0) {
-        if (vec) STG_AGG(Cfg::CIN0, 4); else STG_AGG(Cfg::CIN0, 1);
-    } else {
-        if (vec) STG_AGG(Cfg::C, 4); else STG_AGG(Cfg::C, 1);
-    }
-#undef STG_AGG
-    STG_LAUNCH_CHECK("stgcn_agg");
-    return STG_OK;
+    const Launch lc{"stgcn_agg", grid, block, lds, st, 64 * 1024};
+    const auto k = cin == Cfg::CIN0 ? (vec ? stgcn_agg_kernel<Cfg::CIN0, 4> : stgcn_agg_kernel<Cfg::CIN0, 1>)
+                                    : (vec ? stgcn_agg_kernel<Cfg::C, 4> : stgcn_agg_kernel<Cfg::C, 1>);
+    return launch(lc, k, x, x_sn, x_sc, x_st, x_sv, adj, a_sn, num_peds, N, V, out, out_stride, ax_off, cs_off, prep);
 }
 
 }  // namespace stg

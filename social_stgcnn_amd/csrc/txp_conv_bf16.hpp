@@ -247,10 +247,10 @@ __device__ __forceinline__ void read16(unsigned addr, u32x2 &lo, u32x2 &hi) {
 }
 
 // issue the 32 reads of a tile (LDS returns in order: wait_groups<N>() below makes the first N groups usable)
-__device__ __forceinline__ void load_b(unsigned lds_base, const Tile &t, BRegs &b) {
 #define STG_CV_G(g, bi, imm)                                       \
     read16<imm>(lds_base + t.r1[bi], b.s1[g][0], b.s1[g][1]);     \
     read16<imm>(lds_base + t.r2[bi], b.s2[g][0], b.s2[g][1]);
+__device__ __forceinline__ void load_b(unsigned lds_base, const Tile &t, BRegs &b) {
     STG_CV_G(0, 0, 0)
     STG_CV_G(1, 0, 32)
     STG_CV_G(2, 3, 0)
@@ -259,8 +259,8 @@ __device__ __forceinline__ void load_b(unsigned lds_base, const Tile &t, BRegs &
     STG_CV_G(5, 2, 0)
     STG_CV_G(6, 2, 32)
     STG_CV_G(7, 2, 64)
-#undef STG_CV_G
 }
+#undef STG_CV_G
 // the record quad (channels 4q..4q+3, three pieces) of one position: the residual input of the tile's epilogue, fetched
 // with the tile's operand reads
 struct Quad {
@@ -355,11 +355,12 @@ __device__ __forceinline__ void mma_half(const u32x4 (&w)[kWpVecs], const BHalf 
 // work covers the LDS latency), then tile i's MFMAs.  The in-place forward tolerates the late writes: a tile's output
 // rows are rows no later tile reads.  RES: fetch the tile's own records of the INPUT image (slot offset IN0) for the
 // epilogue's residual.  REV walks the tiles from the last position down (the in-place forward's low -> high layers).
+// (diagnostic: cycle stamps of tile i of conv_tiles<DBG & 32>)
+#define STG_CV_STAMP(k) do { if ((DBG & 32) && stamps && threadIdx.x == 0) stamps[i * 8 + (k)] = __builtin_readcyclecounter(); } while (0)
 template <int IN0, bool REV, bool RES, int DBG = 0, typename Epi>
 __device__ __forceinline__ void conv_tiles(const u32x4 (&w)[kWpVecs], const f32x4 binit, const unsigned char *lds,
                                            const ptab_t *ptab, int npos, int vi, const LaneGeom &lg, Epi epi,
                                            long long *stamps = nullptr) {
-#define STG_CV_STAMP(k) do { if ((DBG & 32) && stamps && threadIdx.x == 0) stamps[i * 8 + (k)] = __builtin_readcyclecounter(); } while (0)
     const int ntiles = (npos + 15) >> 4;
     const unsigned lds_base = (unsigned)(uintptr_t)lds;      // (LDS addresses are 32-bit: the low half of the generic one)
     const int kq = (threadIdx.x & 63) >> 4;
@@ -404,8 +405,8 @@ __device__ __forceinline__ void conv_tiles(const u32x4 (&w)[kWpVecs], const f32x
     }
     if (ntiles > 0) epi(tp, cp, qp);
     if ((DBG & 16) && !late) __builtin_amdgcn_s_barrier();
-#undef STG_CV_STAMP
 }
+#undef STG_CV_STAMP
 __device__ __forceinline__ f32x4 unsplit4(const Quad &q) {
     return unsplit4(make_uint2(q.h.x, q.h.y), make_uint2(q.m.x, q.m.y), make_uint2(q.l.x, q.l.y));
 }

@@ -13,7 +13,7 @@
 // stride is == 16 (mod 32) dwords; weights sit in VGPRs for the whole layer (the next layer's are
 // prefetched while the current layer computes).  Epilogues write position-major [pos][12] images with
 // 16-byte stores: the layout the weight-gradient GEMM (model_bwd.hip, K2) stages back with LDS-DMA.
-#include "txp_scene_common.hpp"
+#include "txp_wave.hpp"
 #include "nll_elem.hpp"
 
 namespace stg {
@@ -942,24 +942,9 @@ __global__ __launch_bounds__(256, 2) void txp_bwd_wave_mixed_kernel(const TxpBwd
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
-bool txp_wave_fits(const ModelLayout &L, int V) {
-    if (L.n_txp < 1 || L.n_blocks != 1 || L.blk[0].cin != Cfg::CIN0) return false;
-    if (L.flags & STG_OPT_WG_PATH) return false;
-    if (txp_fwd_x6_fits(L, V) && txp_bwd_x6_fits(L, V)) return true;      // the exact-bf16 kernels (teams of waves beyond 32)
+bool txp_wave_f32_fits(int V) {
     const size_t fwd = (size_t)2 * plane_slot(V) * sizeof(float);
-    return fwd <= 48 * 1024;        // the fp32-MFMA wave kernels: at least three waves per CU
-}
-
-constexpr int kSmallBatch = 288;      // measured: 256 scenes 1.89 (workgroup kernels) vs 1.79 M/s (a wave per scene), 320 scenes 2.10 vs 2.19
-
-bool use_wave_path(const ModelLayout &L, int N, int V, int *wg_waves) {
-    if (wg_waves) *wg_waves = L.wg_waves;
-    if (!txp_wave_fits(L, V)) return false;
-    if (txp_fwd_x6_fits(L, V) && txp_bwd_x6_fits(L, V)) return true;     // (small batches: finer teams, see team_geom)
-    if (N >= kSmallBatch || L.wg_waves != 0 || V > 40 || (L.flags & (STG_OPT_WAVE_PATH | STG_OPT_BF16_STORE))) return true;
-    // small batch of small scenes: 2048 resident wave slots / N scenes, at most the 8 waves a scene's tiles can use
-    if (wg_waves) *wg_waves = N <= 192 ? 8 : 4;
-    return false;
+    return fwd <= 48 * 1024;        // at least three waves per CU
 }
 
 static size_t fwd_per_wave_floats(int v) { return (size_t)P * txp_sci(v) + ptab_floats(v); }
@@ -991,69 +976,44 @@ static int mix_grid(size_t lds_bytes, int N) {
 
 int launch_txp_fwd_wave(const TxpFwdArgs &a0, hipStream_t st) {
     TxpFwdArgs a = a0;
-    if (a.wpf && txp_fwd_x6_fits(a.lay, a.V)) return launch_txp_fwd_x6(a, st);     // txp_x6.hip: one wave per scene, or teams
     if (mix_geom(fwd_per_wave_floats, a.V, a.tier.order && a.tier.key_start, &a.mix)) {
         const size_t lds = ((size_t)a.mix.block_floats + wave_param_floats(a.lay)) * sizeof(float);
-        hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(&txp_fwd_wave_mixed_kernel),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e_ != hipSuccess) return hip_fail(e_, "txp_fwd_wave_mixed: hipFuncSetAttribute");
-        hipLaunchKernelGGL(txp_fwd_wave_mixed_kernel, dim3(mix_grid(lds, a.N)), dim3(256), lds, st, a, a.params, a.buffers);
-        STG_LAUNCH_CHECK("txp_fwd_wave_mixed");
-        return STG_OK;
+        return launch(Launch{"txp_fwd_wave_mixed", dim3(mix_grid(lds, a.N)), dim3(256), lds, st}, txp_fwd_wave_mixed_kernel, a,
+                      a.params, a.buffers);
     }
     const size_t per_wave = fwd_per_wave_floats(a.Vl) * sizeof(float);
     const int wpb = wave_wpb(per_wave);
     const size_t lds = per_wave * wpb + wave_param_floats(a.lay) * sizeof(float);
-    const dim3 grid(wave_grid(lds, wpb, a.N));
-#define STG_L(W)                                                                                              \
-    do {                                                                                                      \
-        hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(&txp_fwd_wave_kernel<W>),          \
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);            \
-        if (e_ != hipSuccess) return hip_fail(e_, "txp_fwd_wave: hipFuncSetAttribute");                       \
-        hipLaunchKernelGGL(txp_fwd_wave_kernel<W>, grid, dim3(W * 64), lds, st, a, a.params, a.buffers);       \
-    } while (0)
-    if (wpb == 8) STG_L(8); else if (wpb == 4) STG_L(4); else if (wpb == 2) STG_L(2); else STG_L(1);
-#undef STG_L
-    STG_LAUNCH_CHECK("txp_fwd_wave");
-    return STG_OK;
+    const Launch lc{"txp_fwd_wave", dim3(wave_grid(lds, wpb, a.N)), dim3(wpb * 64), lds, st};
+    switch (wpb) {
+        case 8: return launch(lc, txp_fwd_wave_kernel<8>, a, a.params, a.buffers);
+        case 4: return launch(lc, txp_fwd_wave_kernel<4>, a, a.params, a.buffers);
+        case 2: return launch(lc, txp_fwd_wave_kernel<2>, a, a.params, a.buffers);
+        default: return launch(lc, txp_fwd_wave_kernel<1>, a, a.params, a.buffers);
+    }
 }
+
+template <int W>
+static auto bwd_wave_kernel(bool split_bf16) { return split_bf16 ? txp_bwd_wave_kernel<W, true> : txp_bwd_wave_kernel<W, false>; }
 
 int launch_txp_bwd_wave(const TxpBwdArgs &a0, hipStream_t st) {
     TxpBwdArgs a = a0;
-    if (a.wp && txp_bwd_x6_fits(a.lay, a.V)) return launch_txp_bwd_x6(a, st);      // txp_x6.hip
     if (mix_geom(bwd_per_wave_floats, a.V, a.tier.order && a.tier.key_start, &a.mix)) {
         const size_t lds = ((size_t)a.mix.block_floats + wave_param_floats(a.lay)) * sizeof(float);
-        const void *fn = a.split_bf16 ? reinterpret_cast<const void *>(&txp_bwd_wave_mixed_kernel<true>)
-                                      : reinterpret_cast<const void *>(&txp_bwd_wave_mixed_kernel<false>);
-        hipError_t e_ = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e_ != hipSuccess) return hip_fail(e_, "txp_bwd_wave_mixed: hipFuncSetAttribute");
-        if (a.split_bf16)
-            hipLaunchKernelGGL(txp_bwd_wave_mixed_kernel<true>, dim3(mix_grid(lds, a.N)), dim3(256), lds, st, a);
-        else
-            hipLaunchKernelGGL(txp_bwd_wave_mixed_kernel<false>, dim3(mix_grid(lds, a.N)), dim3(256), lds, st, a);
-        STG_LAUNCH_CHECK("txp_bwd_wave_mixed");
-        return STG_OK;
+        return launch(Launch{"txp_bwd_wave_mixed", dim3(mix_grid(lds, a.N)), dim3(256), lds, st},
+                      a.split_bf16 ? txp_bwd_wave_mixed_kernel<true> : txp_bwd_wave_mixed_kernel<false>, a);
     }
     const size_t per_wave = bwd_per_wave_floats(a.Vl) * sizeof(float);
     const int wpb = wave_wpb(per_wave);
     const size_t lds = per_wave * wpb + wave_param_floats(a.lay) * sizeof(float);
-    const dim3 grid(wave_grid(lds, wpb, a.N));
-#define STG_L2(W, B)                                                                                          \
-    do {                                                                                                      \
-        hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(&txp_bwd_wave_kernel<W, B>),       \
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);            \
-        if (e_ != hipSuccess) return hip_fail(e_, "txp_bwd_wave: hipFuncSetAttribute");                       \
-        hipLaunchKernelGGL((txp_bwd_wave_kernel<W, B>), grid, dim3(W * 64), lds, st, a);                      \
-    } while (0)
-#define STG_L(W)                                                                                              \
-    do {                                                                                                      \
-        if (a.split_bf16) STG_L2(W, true); else STG_L2(W, false);                                             \
-    } while (0)
-    if (wpb == 8) STG_L(8); else if (wpb == 4) STG_L(4); else if (wpb == 2) STG_L(2); else STG_L(1);
-#undef STG_L
-#undef STG_L2
-    STG_LAUNCH_CHECK("txp_bwd_wave");
-    return STG_OK;
+    const Launch lc{"txp_bwd_wave", dim3(wave_grid(lds, wpb, a.N)), dim3(wpb * 64), lds, st};
+    const bool sp = a.split_bf16 != 0;
+    switch (wpb) {
+        case 8: return launch(lc, bwd_wave_kernel<8>(sp), a);
+        case 4: return launch(lc, bwd_wave_kernel<4>(sp), a);
+        case 2: return launch(lc, bwd_wave_kernel<2>(sp), a);
+        default: return launch(lc, bwd_wave_kernel<1>(sp), a);
+    }
 }
 
 }  // namespace stg

@@ -332,23 +332,11 @@ bool wgrad_geom(const ModelLayout &L, int N, int V, WgradGeom *g) {
 
 int launch_txp_wgrad(const WgradArgs &w, const WgradGeom &g, hipStream_t st) {
     if (g.bf16mma) return launch_txp_wgrad_bf16(w, g, st);
-    const dim3 grid(g.grid), block(kWaves * 64);
-#define STG_LAUNCH_WG(NB, BF)                                                                                \
-    do {                                                                                                     \
-        hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(&txp_wgrad_kernel<NB, BF>),       \
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds);         \
-        if (e_ != hipSuccess) return hip_fail(e_, "txp_wgrad: hipFuncSetAttribute");                         \
-        hipLaunchKernelGGL((txp_wgrad_kernel<NB, BF>), grid, block, g.lds, st, w, w.order, w.order_peds, w.num_peds); \
-    } while (0)
+    const Launch lc{"txp_wgrad", dim3(g.grid), dim3(kWaves * 64), g.lds, st};
     const bool bf16 = (w.lay.flags & STG_OPT_BF16_STORE) != 0;
-    if (g.nbuf == 3) {
-        if (bf16) STG_LAUNCH_WG(3, true); else STG_LAUNCH_WG(3, false);
-    } else {
-        if (bf16) STG_LAUNCH_WG(4, true); else STG_LAUNCH_WG(4, false);
-    }
-#undef STG_LAUNCH_WG
-    STG_LAUNCH_CHECK("txp_wgrad");
-    return STG_OK;
+    if (g.nbuf == 3)
+        return launch(lc, bf16 ? txp_wgrad_kernel<3, true> : txp_wgrad_kernel<3, false>, w, w.order, w.order_peds, w.num_peds);
+    return launch(lc, bf16 ? txp_wgrad_kernel<4, true> : txp_wgrad_kernel<4, false>, w, w.order, w.order_peds, w.num_peds);
 }
 
 }  // namespace stg

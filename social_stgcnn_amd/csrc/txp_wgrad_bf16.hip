@@ -421,35 +421,26 @@ void wgrad_bf16_geom(WgradGeom *g, const ModelLayout &L, int V) {
     g->lds = lds;
 }
 
+// the kernel for a storage mode (B), chunked scenes (ch) and a workgroup shape of NW waves and NI images
+template <bool B, int NW, int NI>
+static auto wgrad_bf16_kernel(bool ch) { return ch ? txp_wgrad_bf16_kernel<B, true, NW, NI> : txp_wgrad_bf16_kernel<B, false, NW, NI>; }
+
 int launch_txp_wgrad_bf16(const WgradArgs &w, const WgradGeom &g, hipStream_t st) {
-    const dim3 grid(g.grid), block(g.waves * 64);
+    const Launch lc{"txp_wgrad_bf16", dim3(g.grid), dim3(g.waves * 64), g.lds, st};
     const bool bf = (w.lay.flags & STG_OPT_BF16_STORE) != 0, ch = w.V > kWgradChunkV;
-#define STG_LW3(B, H, NW, NI)                                                                                         \
-    do {                                                                                                              \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&txp_wgrad_bf16_kernel<B, H, NW, NI>),                 \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds);                   \
-        if (e != hipSuccess) return hip_fail(e, "txp_wgrad_bf16: hipFuncSetAttribute");                                \
-        hipLaunchKernelGGL((txp_wgrad_bf16_kernel<B, H, NW, NI>), grid, block, g.lds, st, w, w.order, w.order_peds, w.num_peds,  \
-                           w.key_start);                                                                              \
-    } while (0)
-#define STG_LW3V(NW, NI)                                                                                              \
-    do {                                                                                                              \
-        if (bf) { if (ch) STG_LW3(true, true, NW, NI); else STG_LW3(true, false, NW, NI); }                           \
-        else { if (ch) STG_LW3(false, true, NW, NI); else STG_LW3(false, false, NW, NI); }                            \
-    } while (0)
+    const bool five = g.waves == 5 && g.nbuf == 1, ten = g.waves == 10 && g.nbuf == 2;
 #ifdef STG_K2_ALL_SHAPES                               // (tools/micro/k2_bench.hip: every storage mode in both workgroup shapes)
-    if (g.waves == 5 && g.nbuf == 1) STG_LW3V(5, 1);
-    else if (g.waves == 10 && g.nbuf == 2) STG_LW3V(10, 2);
-    else return fail(STG_EINVAL, "txp_wgrad_bf16: no kernel for %d waves / %d images", g.waves, g.nbuf);
+    if (five || ten) {
+        const auto k = five ? (bf ? wgrad_bf16_kernel<true, 5, 1>(ch) : wgrad_bf16_kernel<false, 5, 1>(ch))
+                            : (bf ? wgrad_bf16_kernel<true, 10, 2>(ch) : wgrad_bf16_kernel<false, 10, 2>(ch));
+        return launch(lc, k, w, w.order, w.order_peds, w.num_peds, w.key_start);
+    }
 #else
-    if (bf && g.waves == 5 && g.nbuf == 1) { if (ch) STG_LW3(true, true, 5, 1); else STG_LW3(true, false, 5, 1); }
-    else if (!bf && g.waves == 10 && g.nbuf == 2) { if (ch) STG_LW3(false, true, 10, 2); else STG_LW3(false, false, 10, 2); }
-    else return fail(STG_EINVAL, "txp_wgrad_bf16: no kernel for %d waves / %d images", g.waves, g.nbuf);
+    if (bf ? five : ten)
+        return launch(lc, bf ? wgrad_bf16_kernel<true, 5, 1>(ch) : wgrad_bf16_kernel<false, 10, 2>(ch), w, w.order, w.order_peds,
+                      w.num_peds, w.key_start);
 #endif
-#undef STG_LW3V
-#undef STG_LW3
-    STG_LAUNCH_CHECK("txp_wgrad_bf16");
-    return STG_OK;
+    return fail(STG_EINVAL, "txp_wgrad_bf16: no kernel for %d waves / %d images", g.waves, g.nbuf);
 }
 
 }  // namespace stg

@@ -742,54 +742,44 @@ static bool canon32_agg_matches(const TxpFwdArgs &a) {
     return a.agg_stride == kCanonAggStride32[w] && a.agg_ax == kCanonAggAx32[w] && a.agg_cs == kCanonAggCs32[w];
 }
 
+// the kernel of a solo launch: `wpb` waves per workgroup, fp32 or bf16 storage, the compiled-in shape
+// (a ragged batch with bf16 storage stays Generic: its Canon build spills two more VGPRs than the Generic one)
+template <int W>
+static auto fwd_x6_kernel(bool bf, Shape sh) {
+    if (bf) return sh == Shape::Canon32 ? txp_fwd_x6_kernel<W, true, Shape::Canon32> : txp_fwd_x6_kernel<W, true, Shape::Generic>;
+    if (sh == Shape::Canon32) return txp_fwd_x6_kernel<W, false, Shape::Canon32>;
+    return sh == Shape::Canon ? txp_fwd_x6_kernel<W, false, Shape::Canon> : txp_fwd_x6_kernel<W, false, Shape::Generic>;
+}
+template <int W>
+static auto bwd_x6_kernel(bool bf, Shape sh) {
+    if (bf) {
+        if (sh == Shape::Canon32) return txp_bwd_x6_kernel<W, true, Shape::Canon32>;
+        return sh == Shape::Canon ? txp_bwd_x6_kernel<W, true, Shape::Canon> : txp_bwd_x6_kernel<W, true, Shape::Generic>;
+    }
+    if (sh == Shape::Canon32) return txp_bwd_x6_kernel<W, false, Shape::Canon32>;
+    return sh == Shape::Canon ? txp_bwd_x6_kernel<W, false, Shape::Canon> : txp_bwd_x6_kernel<W, false, Shape::Generic>;
+}
+
 int launch_txp_fwd_x6(const TxpFwdArgs &a0, hipStream_t st) {
     TxpFwdArgs a = a0;
-    if (a.wpf && txp_fwd_x6_fits(a.lay, a.V) && team_wanted(a.N, a.V, a.num_peds == nullptr, &a.team)) {
+    STG_REQUIRE(a.wpf, STG_EINVAL, "txp_fwd_x6: the prepared operands are missing");
+    const bool bf = (a.lay.flags & STG_OPT_BF16_STORE) != 0;
+    if (team_wanted(a.N, a.V, a.num_peds == nullptr, &a.team)) {
         const size_t lds = ((size_t)a.team.region_floats + 4 * team_ptab_floats() + 2 * kXrFwd + wave_param_floats(a.lay)) * sizeof(float);
         STG_REQUIRE(lds <= (size_t)kLdsBytes, STG_ELDS, "txp_fwd_team: V=%d needs %zu bytes of LDS", a.V, lds);
-        const bool bf = (a.lay.flags & STG_OPT_BF16_STORE) != 0;
-        const void *fn = bf ? reinterpret_cast<const void *>(&txp_fwd_team_kernel<true>)
-                            : reinterpret_cast<const void *>(&txp_fwd_team_kernel<false>);
-        hipError_t e_ = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e_ != hipSuccess) return hip_fail(e_, "txp_fwd_team: hipFuncSetAttribute");
-        const dim3 grid(team_grid(lds, a.N));
-        if (bf) hipLaunchKernelGGL(txp_fwd_team_kernel<true>, grid, dim3(256), lds, st, a, a.params, a.buffers);
-        else hipLaunchKernelGGL(txp_fwd_team_kernel<false>, grid, dim3(256), lds, st, a, a.params, a.buffers);
-        STG_LAUNCH_CHECK("txp_fwd_team");
-        return STG_OK;
+        return launch(Launch{"txp_fwd_team", dim3(team_grid(lds, a.N)), dim3(256), lds, st},
+                      bf ? txp_fwd_team_kernel<true> : txp_fwd_team_kernel<false>, a, a.params, a.buffers);
     }
-    if (a.wpf && txp_fwd_x6_fits(a.lay, a.V) && a.V <= 16 * kF6Tiles / C) {
-        const size_t per_wave = (size_t)(fwd6_region_floats(a.Vl) + ptab_floats(a.Vl)) * sizeof(float);
-        const int wpb = wave_wpb(per_wave) == 8 ? 8 : 4;     // (the 18 KB images of V <= 32 always fit four waves)
-        const size_t lds = per_wave * wpb + wave_param_floats(a.lay) * sizeof(float);
-        const dim3 grid(wave_grid(lds, wpb, a.N));
-        const bool bf = (a.lay.flags & STG_OPT_BF16_STORE) != 0;
-        bool ok;
-        const Shape sh = canon_shape(a, &ok);
-        STG_REQUIRE(ok && (sh != Shape::Canon32 || canon32_agg_matches(a)), STG_EINVAL,
-                    "txp_fwd_x6: the canonical V=%d batch does not match its compiled layout", a.V);
-#define STG_LX(W, B, S)                                                                                       \
-    do {                                                                                                      \
-        hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(&txp_fwd_x6_kernel<W, B, S>),      \
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);            \
-        if (e_ != hipSuccess) return hip_fail(e_, "txp_fwd_x6: hipFuncSetAttribute");                         \
-        hipLaunchKernelGGL((txp_fwd_x6_kernel<W, B, S>), grid, dim3(W * 64), lds, st, a, a.params, a.buffers);\
-    } while (0)
-        // (a ragged batch with bf16 storage stays Generic: its Canon build spills two more VGPRs than the Generic one)
-#define STG_LXS(W, B)                                                                                         \
-    do {                                                                                                      \
-        if (sh == Shape::Canon32) STG_LX(W, B, Shape::Canon32);                                               \
-        else if (sh == Shape::Canon) STG_LX(W, B, (B ? Shape::Generic : Shape::Canon));                       \
-        else STG_LX(W, B, Shape::Generic);                                                                    \
-    } while (0)
-        if (wpb == 8) { if (bf) STG_LXS(8, true); else STG_LXS(8, false); }
-        else { if (bf) STG_LXS(4, true); else STG_LXS(4, false); }
-#undef STG_LXS
-#undef STG_LX
-        STG_LAUNCH_CHECK("txp_fwd_x6");
-        return STG_OK;
-    }
-    return fail(STG_EUNSUPPORTED, "txp_fwd_x6: V=%d outside the exact-bf16 kernels", a.V);
+    STG_REQUIRE(a.V <= 16 * kF6Tiles / C, STG_EUNSUPPORTED, "txp_fwd_x6: V=%d outside the exact-bf16 kernels", a.V);
+    const size_t per_wave = (size_t)(fwd6_region_floats(a.Vl) + ptab_floats(a.Vl)) * sizeof(float);
+    const int wpb = wave_wpb(per_wave) == 8 ? 8 : 4;     // (the 18 KB images of V <= 32 always fit four waves)
+    const size_t lds = per_wave * wpb + wave_param_floats(a.lay) * sizeof(float);
+    bool ok;
+    const Shape sh = canon_shape(a, &ok);
+    STG_REQUIRE(ok && (sh != Shape::Canon32 || canon32_agg_matches(a)), STG_EINVAL,
+                "txp_fwd_x6: the canonical V=%d batch does not match its compiled layout", a.V);
+    return launch(Launch{"txp_fwd_x6", dim3(wave_grid(lds, wpb, a.N)), dim3(wpb * 64), lds, st},
+                  wpb == 8 ? fwd_x6_kernel<8>(bf, sh) : fwd_x6_kernel<4>(bf, sh), a, a.params, a.buffers);
 }
 
 bool txp_bwd_x6_fits(const ModelLayout &L, int V) {
@@ -799,50 +789,23 @@ bool txp_bwd_x6_fits(const ModelLayout &L, int V) {
 int64_t txp_bwd_x6_wp_floats(const ModelLayout &L) { return (int64_t)(L.L + 1) * cv::kWpDwords; }
 int launch_txp_bwd_x6(const TxpBwdArgs &a0, hipStream_t st) {
     TxpBwdArgs a = a0;
-    if (a.wp && txp_bwd_x6_fits(a.lay, a.V) && team_wanted(a.N, a.V, a.num_peds == nullptr, &a.team)) {
+    STG_REQUIRE(a.wp, STG_EINVAL, "txp_bwd_x6: the prepared operands are missing");
+    const bool bf = (a.lay.flags & STG_OPT_BF16_STORE) != 0;
+    if (team_wanted(a.N, a.V, a.num_peds == nullptr, &a.team)) {
         const size_t lds = ((size_t)a.team.region_floats + 4 * team_ptab_floats() + kXrBwdWg + wave_param_floats(a.lay)) * sizeof(float);
         STG_REQUIRE(lds <= (size_t)kLdsBytes, STG_ELDS, "txp_bwd_team: V=%d needs %zu bytes of LDS", a.V, lds);
-        const bool bf = (a.lay.flags & STG_OPT_BF16_STORE) != 0;
-        const void *fn = bf ? reinterpret_cast<const void *>(&txp_bwd_team_kernel<true>)
-                            : reinterpret_cast<const void *>(&txp_bwd_team_kernel<false>);
-        hipError_t e_ = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e_ != hipSuccess) return hip_fail(e_, "txp_bwd_team: hipFuncSetAttribute");
-        const dim3 grid(team_grid(lds, a.N));
-        if (bf) hipLaunchKernelGGL(txp_bwd_team_kernel<true>, grid, dim3(256), lds, st, a);
-        else hipLaunchKernelGGL(txp_bwd_team_kernel<false>, grid, dim3(256), lds, st, a);
-        STG_LAUNCH_CHECK("txp_bwd_team");
-        return STG_OK;
+        return launch(Launch{"txp_bwd_team", dim3(team_grid(lds, a.N)), dim3(256), lds, st},
+                      bf ? txp_bwd_team_kernel<true> : txp_bwd_team_kernel<false>, a);
     }
-    if (a.wp && txp_bwd_x6_fits(a.lay, a.V) && a.V <= 16 * kX6Tiles / C) {
-        const size_t per_wave = (size_t)(bwd6_region_floats(a.Vl) + bwd_ptab_floats(a.Vl)) * sizeof(float);
-        const int wpb = wave_wpb(per_wave) == 8 ? 8 : 4;
-        const size_t lds = per_wave * wpb + wave_param_floats(a.lay) * sizeof(float);
-        const dim3 grid(wave_grid(lds, wpb, a.N));
-        const bool bf = (a.lay.flags & STG_OPT_BF16_STORE) != 0;
-        bool ok;
-        const Shape sh = canon_shape(a, &ok);
-        STG_REQUIRE(ok, STG_EINVAL, "txp_bwd_x6: the canonical V=%d batch does not match its compiled layout", a.V);
-#define STG_LX(W, B, S)                                                                                       \
-    do {                                                                                                      \
-        hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(&txp_bwd_x6_kernel<W, B, S>),      \
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);            \
-        if (e_ != hipSuccess) return hip_fail(e_, "txp_bwd_x6: hipFuncSetAttribute");                         \
-        hipLaunchKernelGGL((txp_bwd_x6_kernel<W, B, S>), grid, dim3(W * 64), lds, st, a);                     \
-    } while (0)
-#define STG_LXS(W, B)                                                                                         \
-    do {                                                                                                      \
-        if (sh == Shape::Canon32) STG_LX(W, B, Shape::Canon32);                                               \
-        else if (sh == Shape::Canon) STG_LX(W, B, Shape::Canon);                                              \
-        else STG_LX(W, B, Shape::Generic);                                                                    \
-    } while (0)
-        if (wpb == 8) { if (bf) STG_LXS(8, true); else STG_LXS(8, false); }
-        else { if (bf) STG_LXS(4, true); else STG_LXS(4, false); }
-#undef STG_LXS
-#undef STG_LX
-        STG_LAUNCH_CHECK("txp_bwd_x6");
-        return STG_OK;
-    }
-    return fail(STG_EUNSUPPORTED, "txp_bwd_x6: V=%d outside the exact-bf16 kernels", a.V);
+    STG_REQUIRE(a.V <= 16 * kX6Tiles / C, STG_EUNSUPPORTED, "txp_bwd_x6: V=%d outside the exact-bf16 kernels", a.V);
+    const size_t per_wave = (size_t)(bwd6_region_floats(a.Vl) + bwd_ptab_floats(a.Vl)) * sizeof(float);
+    const int wpb = wave_wpb(per_wave) == 8 ? 8 : 4;
+    const size_t lds = per_wave * wpb + wave_param_floats(a.lay) * sizeof(float);
+    bool ok;
+    const Shape sh = canon_shape(a, &ok);
+    STG_REQUIRE(ok, STG_EINVAL, "txp_bwd_x6: the canonical V=%d batch does not match its compiled layout", a.V);
+    return launch(Launch{"txp_bwd_x6", dim3(wave_grid(lds, wpb, a.N)), dim3(wpb * 64), lds, st},
+                  wpb == 8 ? bwd_x6_kernel<8>(bf, sh) : bwd_x6_kernel<4>(bf, sh), a);
 }
 
 }  // namespace stg

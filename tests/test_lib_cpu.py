@@ -59,6 +59,27 @@ def test_layout_queries_match_reference_counts(L):
     assert L.stg_model_param_count(ctypes.byref(d3)) == blk1
 
 
+def test_size_queries_match_the_recorded_table(L):
+    """stg_model_ws_tail_floats / stg_model_fwd_scratch_floats / stg_model_bwd_scratch_floats (error codes included) over
+    path flags x batch sizes x padded crowd sizes, against tests/size_queries.json: the answers of the library built
+    from commit 28a5f63, the last one before the host-side step plan (csrc/step_plan.hpp).  Buffer sizes are ABI
+    behaviour: callers allocate by them."""
+    import json
+    from social_stgcnn_amd import _lib, ops
+    table = json.load(open(os.path.join(ROOT, "tests", "size_queries.json")))["rows"]
+    flags = [0, _lib.OPT_WAVE_PATH, _lib.OPT_WG_PATH, _lib.OPT_F32_MFMA, _lib.OPT_SPLIT_BF16,
+             _lib.OPT_BF16_STORE | _lib.OPT_WAVE_PATH]
+    cases = [(f, n, v) for f in flags for n in (1, 7, 100, 287, 288, 2048) for v in (3, 32, 33, 40, 41, 64, 128, 129, 400)]
+    assert [tuple(r[:3]) for r in table] == cases
+    for f, n, v, tail, fwd, bwd in table:
+        d = ops.make_desc(1, 5, 2, 5, 8, 12, 3, 2, False, True)
+        d.flags = f
+        got = (L.stg_model_ws_tail_floats(ctypes.byref(d), n, v), L.stg_model_fwd_scratch_floats(ctypes.byref(d), n, v),
+               L.stg_model_bwd_scratch_floats(ctypes.byref(d), n, v))
+        assert got == (tail, fwd, bwd), (f, n, v)
+    assert sum(1 for r in table if r[5] == -3) == 36 and all(r[2] == 400 for r in table if r[5] == -3)
+
+
 def test_invalid_arguments_return_status_not_abort(L):
     from social_stgcnn_amd import ops
     assert L.stg_adj_build(None, 0, 0, 0, 0, None, 1, 4, 8, 1, None, None, None) == -1
