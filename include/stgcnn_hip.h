@@ -354,6 +354,31 @@ int stg_track_push(const int64_t *det_id, const double *det_xy, const int32_t *d
                    uint32_t *mask, double *ring, int32_t *head_flags, int S, int T_obs, double scale, int V,
                    double *obs_abs, int64_t *out_ids, int32_t *num_peds, void *stream);
 
+/* NS independent live streams in ONE launch, one workgroup per stream: stream b runs exactly stg_track_push on its own
+ * state slices -- slot_id (NS,S), mask (NS,S), ring (NS,T_obs,S,2), head_flags (NS,2) -- and its own range of one
+ * packed tick of detections, writing obs_abs (NS,T_obs,V,2), out_ids (NS,V), num_peds (NS) and out_flags (NS) (the
+ * STG_TRACK_* flags of the push; may be NULL).  All DEVICE memory, read when the kernel runs, so one captured graph
+ * serves every tick whatever its counts:
+ *   det_id int64 and det_xy float64 hold M_total detections; detection j of the tick is det_id[j*id_stride],
+ *   (det_xy[j*xy_stride], det_xy[j*xy_stride+1]) -- id_stride 1, xy_stride 2 is the contiguous (M_total), (M_total,2)
+ *   layout; packed (id, x, y) records are id_stride = xy_stride = 3 (det_xy = the record's second element).
+ *   det_start int32[NS+1]: stream b owns detections det_start[b] .. det_start[b+1]-1, clamped to [0, M_total); more than
+ *   M_max of them: the first M_max, flag STG_TRACK_TRUNCATED.  pushed int32[NS]: 0 = stream b is not pushed this
+ *   tick -- its state is left bit for bit as it was and its scene is empty (num_peds 0, ids -1, zero positions,
+ *   out_flags 0).  A push with no detections is a push (it ages the tracks).
+ * block_threads: 0 (the measured default), 64, 256 or 1024 -- the same results at every size.
+ * Limits: NS <= STG_TRACK_MAX_STREAMS: 4096 streams are 8 rounds of the chip's concurrent push workgroups at the
+ * largest block (512 on 256 CUs), their state at the 2048-slot limit stays inside int64 offsets and every per-stream
+ * index in int32; more streams are better served by a second launch.  M_total <= STG_TRACK_MAX_TOTAL_DETECTIONS =
+ * STG_TRACK_MAX_STREAMS * STG_TRACK_MAX_DETECTIONS (every stream at its own limit); det_start stays in int32.         */
+#define STG_TRACK_MAX_STREAMS 4096
+#define STG_TRACK_MAX_TOTAL_DETECTIONS (STG_TRACK_MAX_STREAMS * STG_TRACK_MAX_DETECTIONS)
+int stg_track_push_streams(const int64_t *det_id, int64_t id_stride, const double *det_xy, int64_t xy_stride,
+                           int M_total, const int32_t *det_start, const int32_t *pushed, int NS, int M_max,
+                           int64_t *slot_id, uint32_t *mask, double *ring, int32_t *head_flags, int S, int T_obs,
+                           double scale, int V, double *obs_abs, int64_t *out_ids, int32_t *num_peds,
+                           int32_t *out_flags, int block_threads, void *stream);
+
 /* Self-test helper: C(16x16) = A(16xK) * B(Kx16) through v_mfma_f32_16x16x4_f32 with the operand
  * maps the TXP-CNN kernels rely on (K multiple of 4).                                           */
 int stg_selftest_mfma(const float *a, const float *b, int K, float *c, void *stream);

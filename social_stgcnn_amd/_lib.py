@@ -79,6 +79,8 @@ _SIGNATURES = {
     "stg_frame_scenes": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, ctypes.c_double, c_f, c_f, c_f, c_f]),
     "stg_track_push": (c_i, [c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_i, c_i, ctypes.c_double, c_i, c_f, c_f, c_f,
                              c_f]),
+    "stg_track_push_streams": (c_i, [c_f, c_l, c_f, c_l, c_i, c_f, c_f, c_i, c_i, c_f, c_f, c_f, c_f, c_i, c_i,
+                                     ctypes.c_double, c_i, c_f, c_f, c_f, c_f, c_i, c_f]),
     "stg_selftest_mfma": (c_i, [c_f, c_f, c_i, c_f, c_f]),
 }
 EXPORTS = tuple(_SIGNATURES)

@@ -10,6 +10,9 @@
 //   stg_track_push          live stream: ONE workgroup keeps the track state on the device (slot ids, presence masks,
 //                           a position ring) and turns one frame of detections into that frame's scene.  The detection
 //                           count is read from device memory, so a captured graph replays with a different count.
+//   stg_track_push_streams  NS live streams: one workgroup per stream runs the same push (track_push_body) on the
+//                           stream's slice of the state and its range of one packed tick of detections; the counts,
+//                           offsets and pushed flags are read from device memory, so one captured graph serves a tick.
 //
 // Pure data movement and integer work: a few KB per frame.  No host synchronisation in the launch functions (the push
 // is captured into the per-frame graph of FramePredictor.capture) and plain C++ stores only.
@@ -19,6 +22,8 @@ namespace stg {
 
 constexpr int kPushThreads = 1024;
 constexpr int kPushWaves = kPushThreads / kWave;
+// workgroup of stg_track_push_streams when the caller passes block_threads = 0 (measured)
+constexpr int kStreamThreads = 256;
 constexpr int kFlagDuplicate = STG_TRACK_DUPLICATE, kFlagOverflow = STG_TRACK_OVERFLOW,
               kFlagTruncated = STG_TRACK_TRUNCATED, kFlagTooMany = STG_TRACK_TOO_MANY;
 
@@ -102,16 +107,18 @@ __global__ __launch_bounds__(64) void frame_scenes_kernel(const int32_t *__restr
     if (lane == 0) num_peds[n] = c;
 }
 
-// ---- live stream -------------------------------------------------------------------------------------------------
+// ---- live streams ------------------------------------------------------------------------------------------------
 // Block-wide exclusive rank of `flag` over the threads (thread order), added to `base`; every thread gets the block
-// total in *total.  Called by all threads of the block (it holds two barriers).
+// total in *total.  Called by all kThreads threads of the block (it holds two barriers).
+template <int kThreads>
 __device__ __forceinline__ int block_rank(bool flag, int base, int *total, int *wave_cnt) {
+    constexpr int kWaves = kThreads / kWave;
     const int wave = threadIdx.x / kWave;
     const uint64_t m = __ballot(flag);
     if ((threadIdx.x & (kWave - 1)) == 0) wave_cnt[wave] = __popcll(m);
     __syncthreads();
     int before = 0, all = 0;
-    for (int w = 0; w < kPushWaves; ++w) {
+    for (int w = 0; w < kWaves; ++w) {
         const int c = wave_cnt[w];
         before += w < wave ? c : 0;
         all += c;
@@ -121,25 +128,32 @@ __device__ __forceinline__ int block_rank(bool flag, int base, int *total, int *
     return base + before + lanes_below(m);
 }
 
+// One push of one stream by one workgroup of kThreads threads: `count` detections (more than M_max: the first M_max,
+// flag TRUNCATED), detection j = (det_id[j * id_stride], det_xy[j * xy_stride], det_xy[j * xy_stride + 1]) -- strides
+// 1 and 2 for the single stream's (M), (M,2) arrays --; the stream's state slot_id (S), mask (S), ring (T_obs,S,2),
+// head_flags (2); its scene obs_abs (T_obs,V,2), out_ids (V), *num_peds.  Returns (in every thread) the flags.
 // LDS layout (dynamic): sort keys (M2 x int64), sort indices (M2 x int32), det_slot (M_max x int32),
 // slot masks (S x uint32), free slots (S x int32)
-__global__ __launch_bounds__(kPushThreads) void track_push_kernel(
-    const int64_t *__restrict__ det_id, const double *__restrict__ det_xy, const int32_t *__restrict__ det_count,
-    int M_max, int M2, int64_t *__restrict__ slot_id, uint32_t *__restrict__ mask, double *__restrict__ ring,
-    int32_t *__restrict__ head_flags, int S, int T_obs, double scale, int V, double *__restrict__ obs_abs,
-    int64_t *__restrict__ out_ids, int32_t *__restrict__ num_peds) {
+template <int kThreads>
+__device__ __forceinline__ int track_push_body(const int64_t *__restrict__ det_id, int64_t id_stride,
+                                               const double *__restrict__ det_xy, int64_t xy_stride, int count,
+                                               int M_max, int M2, int64_t *__restrict__ slot_id,
+                                               uint32_t *__restrict__ mask, double *__restrict__ ring,
+                                               int32_t *__restrict__ head_flags, int S, int T_obs, double scale, int V,
+                                               double *__restrict__ obs_abs, int64_t *__restrict__ out_ids,
+                                               int32_t *__restrict__ num_peds) {
     extern __shared__ __align__(16) unsigned char lds[];
     int64_t *key = reinterpret_cast<int64_t *>(lds);
     int32_t *kidx = reinterpret_cast<int32_t *>(key + M2);
     int32_t *det_slot = kidx + M2;
     uint32_t *smask = reinterpret_cast<uint32_t *>(det_slot + M_max);
     int32_t *free_list = reinterpret_cast<int32_t *>(smask + S);
-    __shared__ int wave_cnt[kPushWaves];
+    __shared__ int wave_cnt[kThreads / kWave];
     __shared__ int flags;
 
     const int tid = threadIdx.x, nt = blockDim.x;
     const uint32_t full = T_obs >= 32 ? 0xffffffffu : (1u << T_obs) - 1u;
-    int m = det_count[0];
+    int m = count;
     const bool truncated = m > M_max;
     m = m < 0 ? 0 : (m > M_max ? M_max : m);
     const int head = (head_flags[0] + 1) % T_obs;          // ring row of this frame
@@ -155,7 +169,7 @@ __global__ __launch_bounds__(kPushThreads) void track_push_kernel(
     int n2 = 1;                                             // sort size: next power of two >= m (<= M2)
     while (n2 < m) n2 <<= 1;
     for (int p = tid; p < n2; p += nt) {
-        key[p] = p < m ? det_id[p] : INT64_MAX;
+        key[p] = p < m ? det_id[p * id_stride] : INT64_MAX;
         kidx[p] = p;
     }
     for (int j = tid; j < m; j += nt) det_slot[j] = -1;
@@ -207,7 +221,7 @@ __global__ __launch_bounds__(kPushThreads) void track_push_kernel(
     for (int s0 = 0; s0 < S; s0 += nt) {
         const int s = s0 + tid;
         const bool fr = s < S && smask[s] == 0;
-        const int r = block_rank(fr, n_free, &tot, wave_cnt);
+        const int r = block_rank<kThreads>(fr, n_free, &tot, wave_cnt);
         if (fr) free_list[r] = s;
         n_free += tot;
     }
@@ -216,7 +230,7 @@ __global__ __launch_bounds__(kPushThreads) void track_push_kernel(
     for (int j0 = 0; j0 < m; j0 += nt) {
         const int j = j0 + tid;
         const bool nw = j < m && det_slot[j] == -1;
-        const int r = block_rank(nw, n_new, &tot, wave_cnt);
+        const int r = block_rank<kThreads>(nw, n_new, &tot, wave_cnt);
         if (nw) {
             if (r < n_free) det_slot[j] = free_list[r];
             else {
@@ -232,10 +246,10 @@ __global__ __launch_bounds__(kPushThreads) void track_push_kernel(
     for (int j = tid; j < m; j += nt) {
         const int s = det_slot[j];
         if (s < 0) continue;
-        slot_id[s] = det_id[j];
+        slot_id[s] = det_id[j * id_stride];
         smask[s] |= 1u;
-        ring[((int64_t)head * S + s) * 2] = round_pos(det_xy[(int64_t)j * 2], scale);
-        ring[((int64_t)head * S + s) * 2 + 1] = round_pos(det_xy[(int64_t)j * 2 + 1], scale);
+        ring[((int64_t)head * S + s) * 2] = round_pos(det_xy[j * xy_stride], scale);
+        ring[((int64_t)head * S + s) * 2 + 1] = round_pos(det_xy[j * xy_stride + 1], scale);
     }
     __syncthreads();
 
@@ -247,7 +261,7 @@ __global__ __launch_bounds__(kPushThreads) void track_push_kernel(
         const int j = p < m ? kidx[p] : 0;
         const int s = p < m ? det_slot[j] : -1;
         const bool in = s >= 0 && (smask[s] & full) == full;
-        const int r = block_rank(in, c, &tot, wave_cnt);
+        const int r = block_rank<kThreads>(in, c, &tot, wave_cnt);
         if (in && r < V) {
             out_ids[r] = key[p];
             for (int t = 0; t < T_obs - 1; ++t) {
@@ -256,8 +270,8 @@ __global__ __launch_bounds__(kPushThreads) void track_push_kernel(
                 obs_abs[((int64_t)t * V + r) * 2 + 1] = ring[((int64_t)row * S + s) * 2 + 1];
             }
             // this frame's position from the input (the ring row written above is another thread's store)
-            obs_abs[((int64_t)(T_obs - 1) * V + r) * 2] = round_pos(det_xy[(int64_t)j * 2], scale);
-            obs_abs[((int64_t)(T_obs - 1) * V + r) * 2 + 1] = round_pos(det_xy[(int64_t)j * 2 + 1], scale);
+            obs_abs[((int64_t)(T_obs - 1) * V + r) * 2] = round_pos(det_xy[j * xy_stride], scale);
+            obs_abs[((int64_t)(T_obs - 1) * V + r) * 2 + 1] = round_pos(det_xy[j * xy_stride + 1], scale);
         }
         c += tot;
     }
@@ -276,6 +290,48 @@ __global__ __launch_bounds__(kPushThreads) void track_push_kernel(
         head_flags[0] = head;
         head_flags[1] = flags;
     }
+    return flags;
+}
+
+__global__ __launch_bounds__(kPushThreads) void track_push_kernel(
+    const int64_t *__restrict__ det_id, const double *__restrict__ det_xy, const int32_t *__restrict__ det_count,
+    int M_max, int M2, int64_t *__restrict__ slot_id, uint32_t *__restrict__ mask, double *__restrict__ ring,
+    int32_t *__restrict__ head_flags, int S, int T_obs, double scale, int V, double *__restrict__ obs_abs,
+    int64_t *__restrict__ out_ids, int32_t *__restrict__ num_peds) {
+    track_push_body<kPushThreads>(det_id, 1, det_xy, 2, det_count[0], M_max, M2, slot_id, mask, ring, head_flags, S,
+                                  T_obs, scale, V, obs_abs, out_ids, num_peds);
+}
+
+// One workgroup per stream: stream b pushes detections det_start[b] .. det_start[b+1]-1 (clamped to [0, M_total))
+// when pushed[b] != 0; otherwise its state is not touched and its scene is the empty one.  Every stream's pointers
+// are its own slices of the (NS, ...) state and output arrays.
+template <int kThreads>
+__global__ __launch_bounds__(kThreads) void track_push_streams_kernel(
+    const int64_t *__restrict__ det_id, int64_t id_stride, const double *__restrict__ det_xy, int64_t xy_stride,
+    int M_total, const int32_t *__restrict__ det_start, const int32_t *__restrict__ pushed, int M_max, int M2,
+    int64_t *__restrict__ slot_id, uint32_t *__restrict__ mask, double *__restrict__ ring,
+    int32_t *__restrict__ head_flags, int S, int T_obs, double scale, int V, double *__restrict__ obs_abs,
+    int64_t *__restrict__ out_ids, int32_t *__restrict__ num_peds, int32_t *__restrict__ out_flags) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    double *obs = obs_abs + (int64_t)b * T_obs * V * 2;
+    int64_t *oid = out_ids + (int64_t)b * V;
+    if (pushed[b] == 0) {                                   // uniform over the block: no barrier is skipped halfway
+        for (int e = tid; e < V; e += kThreads) oid[e] = -1;
+        for (int e = tid; e < T_obs * V * 2; e += kThreads) obs[e] = 0.0;
+        if (tid == 0) {
+            num_peds[b] = 0;
+            if (out_flags) out_flags[b] = 0;
+        }
+        return;
+    }
+    int lo = det_start[b], hi = det_start[b + 1];
+    lo = lo < 0 ? 0 : (lo > M_total ? M_total : lo);
+    hi = hi < lo ? lo : (hi > M_total ? M_total : hi);
+    const int flags = track_push_body<kThreads>(det_id + lo * id_stride, id_stride, det_xy + lo * xy_stride, xy_stride,
+                                                hi - lo, M_max, M2, slot_id + (int64_t)b * S, mask + (int64_t)b * S,
+                                                ring + (int64_t)b * T_obs * S * 2, head_flags + 2 * b, S, T_obs, scale,
+                                                V, obs, oid, num_peds + b);
+    if (out_flags && tid == 0) out_flags[b] = flags;
 }
 
 }  // namespace stg
@@ -324,6 +380,39 @@ int stg_track_push(const int64_t *det_id, const double *det_xy, const int32_t *d
                        det_xy, det_count, M_max, m2, slot_id, mask, ring, head_flags, S, T_obs, scale, V, obs_abs,
                        out_ids, num_peds);
     STG_LAUNCH_CHECK("stg_track_push");
+    return STG_OK;
+}
+
+int stg_track_push_streams(const int64_t *det_id, int64_t id_stride, const double *det_xy, int64_t xy_stride,
+                           int M_total, const int32_t *det_start, const int32_t *pushed, int NS, int M_max,
+                           int64_t *slot_id, uint32_t *mask, double *ring, int32_t *head_flags, int S, int T_obs,
+                           double scale, int V, double *obs_abs, int64_t *out_ids, int32_t *num_peds,
+                           int32_t *out_flags, int block_threads, void *stream) {
+    STG_REQUIRE(NS >= 1 && NS <= STG_TRACK_MAX_STREAMS && M_total >= 0 && M_total <= STG_TRACK_MAX_TOTAL_DETECTIONS &&
+                    M_max >= 1 && M_max <= STG_TRACK_MAX_DETECTIONS && S >= 1 && S <= STG_TRACK_MAX_SLOTS && V >= 1 &&
+                    T_obs >= 1 && T_obs <= 32 && id_stride >= 1 && xy_stride >= 2,
+                STG_EINVAL,
+                "stg_track_push_streams: bad sizes NS=%d M_total=%d M_max=%d S=%d V=%d T_obs=%d strides %lld/%lld", NS,
+                M_total, M_max, S, V, T_obs, (long long)id_stride, (long long)xy_stride);
+    if (block_threads == 0) block_threads = stg::kStreamThreads;
+    STG_REQUIRE(block_threads == 64 || block_threads == 256 || block_threads == 1024, STG_EINVAL,
+                "stg_track_push_streams: block_threads=%d (0, 64, 256 or 1024)", block_threads);
+    STG_REQUIRE(det_id && det_xy && det_start && pushed && slot_id && mask && ring && head_flags && obs_abs &&
+                    out_ids && num_peds,
+                STG_EINVAL, "stg_track_push_streams: null pointer");
+    int m2 = 1;
+    while (m2 < M_max) m2 <<= 1;
+    const size_t lds = (size_t)m2 * (sizeof(int64_t) + sizeof(int32_t)) + (size_t)M_max * sizeof(int32_t) +
+                       (size_t)S * (sizeof(uint32_t) + sizeof(int32_t));
+    auto go = [&](auto kernel, int threads) {
+        hipLaunchKernelGGL(kernel, dim3(NS), dim3(threads), lds, stg::as_stream(stream), det_id, id_stride, det_xy,
+                           xy_stride, M_total, det_start, pushed, M_max, m2, slot_id, mask, ring, head_flags, S, T_obs,
+                           scale, V, obs_abs, out_ids, num_peds, out_flags);
+    };
+    if (block_threads == 64) go(stg::track_push_streams_kernel<64>, 64);
+    else if (block_threads == 256) go(stg::track_push_streams_kernel<256>, 256);
+    else go(stg::track_push_streams_kernel<1024>, 1024);
+    STG_LAUNCH_CHECK("stg_track_push_streams");
     return STG_OK;
 }
 

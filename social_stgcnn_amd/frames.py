@@ -15,8 +15,11 @@ stg_frame_scenes over a recording uploaded once, stg_track_push with the track s
     recording_scenes   (M,4) rows of data.read_file -> FrameScenes on the device
     predict_recording  Predictor over the frame scenes in batches
     FramePredictor     push(ids, xy) per frame, eager or as ONE captured graph (capture())
+    StreamsPredictor   NS independent live streams: push(tick) per tick, one host->device copy of the packed
+                       detections and ONE launch chain (stg_track_push_streams -> the batched forward -> sampler)
 """
 import collections
+import collections.abc
 import ctypes
 
 import numpy as np
@@ -28,6 +31,9 @@ from .predict import Prediction, Predictor, _seed_i64
 MAX_OBS_LEN = 32                       # presence masks are 32-bit
 MAX_DETECTIONS = 2048                  # STG_TRACK_MAX_DETECTIONS
 MAX_SLOTS = 2048                       # STG_TRACK_MAX_SLOTS
+MAX_STREAMS = 4096                     # STG_TRACK_MAX_STREAMS
+MAX_TOTAL_DETECTIONS = MAX_STREAMS * MAX_DETECTIONS      # STG_TRACK_MAX_TOTAL_DETECTIONS
+STREAM_THREADS = 256                   # stg_track_push_streams' default workgroup (kStreamThreads, csrc/frames.hip)
 # FramePrediction.flags bits (STG_TRACK_* in include/stgcnn_hip.h)
 DUPLICATE, OVERFLOW, TRUNCATED, TOO_MANY = 1, 2, 4, 8
 
@@ -307,6 +313,329 @@ class FramePredictor:
 
         def replay(ids, xy, seed=None):
             self._stage(ids, xy, seed)
+            static[3].replay()
+            return res
+        return replay
+
+
+StreamsPrediction = collections.namedtuple("StreamsPrediction", "ids num_peds obs_abs samples mean v_pred flags pushed")
+StreamsPrediction.__doc__ = """One tick of NS streams, on the device: ids (NS,V) int64 (-1 in padded slots),
+num_peds (NS,) int32, obs_abs (NS,T_obs,V,2) float64, samples (K,NS,P,V,2), mean (NS,P,V,2), v_pred (NS,5,P,V) float32,
+flags (NS,) int32 (the STG_TRACK_* flags of each stream's push, 0 where not pushed), pushed (NS,) bool.  A stream not
+pushed this tick has the empty scene.  From a captured tick the tensors are the graph's static buffers, overwritten by
+the next."""
+
+PackedTick = collections.namedtuple("PackedTick", "det_start pushed ids xy")
+PackedTick.__doc__ = """One tick packed for stg_track_push_streams: det_start (NS+1,) int32 (stream s owns detections
+det_start[s] .. det_start[s+1]-1), pushed (NS,) int32 (1 = pushed this tick, an empty push included), ids (M,) int64 and
+xy (M,2) float64: the pushed streams' detections concatenated in stream order."""
+
+DeviceTick = collections.namedtuple("DeviceTick", "ids xy counts")
+DeviceTick.__doc__ = """A tick whose detections are already device tensors, packed: ids (M,) int64 and xy (M,2)
+float64, the streams' detections concatenated in stream order; counts (NS,) int32 (a device tensor, or host values):
+stream s owns counts[s] detections, -1 = not pushed this tick (0 is an empty push).  Ranges past M are clamped; a count
+above max_detections uses the first max_detections (flag TRUNCATED); a repeated id within a stream: the first detection
+wins (flag DUPLICATE)."""
+
+
+def pack_tick(tick, streams, max_detections, max_total_detections):
+    """One tick of host detections -> PackedTick, validated as host_detections validates one push: in every stream at
+    most max_detections of them, integral ids >= 0, no id twice; stream indices in [0, streams); at most
+    max_total_detections in all.  tick: a mapping {stream index: (ids, xy)} or a length-`streams` sequence of (ids, xy)
+    or None (None: the stream is not pushed this tick; (ids, xy) with no detections is an empty push)."""
+    if isinstance(tick, collections.abc.Mapping):
+        entries = []
+        for key, det in tick.items():
+            if isinstance(key, (bool, np.bool_)) or not isinstance(key, (int, np.integer)) or not 0 <= key < streams:
+                raise ValueError("tick: stream index %r not in [0, %d)" % (key, streams))
+            if det is not None:
+                entries.append((int(key), det))
+        entries.sort(key=lambda e: e[0])
+    else:
+        tick = list(tick)
+        if len(tick) != streams:
+            raise ValueError("tick: %d entries for %d streams" % (len(tick), streams))
+        entries = [(s, det) for s, det in enumerate(tick) if det is not None]
+    counts = np.zeros(streams, np.int64)
+    pushed = np.zeros(streams, np.int32)
+    ids_l, xy_l = [], []
+    for s, det in entries:
+        if len(det) != 2:
+            raise ValueError("tick: stream %d: (ids, xy) expected" % s)
+        ids_np, xy_np = det
+        # numpy arrays already in shape are taken as they are (a tick of many streams is packed on the host clock)
+        if type(ids_np) is not np.ndarray or ids_np.ndim != 1:
+            ids_np = np.asarray(ids_np.cpu() if torch.is_tensor(ids_np) else ids_np).reshape(-1)
+        if type(xy_np) is not np.ndarray or xy_np.dtype != np.float64 or xy_np.ndim != 2 or xy_np.shape[1] != 2:
+            xy_np = np.asarray(xy_np.cpu() if torch.is_tensor(xy_np) else xy_np, dtype=np.float64).reshape(-1, 2)
+        m = len(ids_np)
+        if m > max_detections:
+            raise ValueError("tick: stream %d: %d detections > max_detections=%d" % (s, m, max_detections))
+        if xy_np.shape[0] != m:
+            raise ValueError("tick: stream %d: %d ids but %d positions" % (s, m, xy_np.shape[0]))
+        counts[s] = m
+        pushed[s] = 1
+        ids_l.append(ids_np)
+        xy_l.append(xy_np)
+    total = int(counts.sum())
+    if total > max_total_detections:
+        raise ValueError("tick: %d detections > max_total_detections=%d" % (total, max_total_detections))
+    ids = _integral_ids(np.concatenate(ids_l) if ids_l else np.zeros(0, np.int64), "tick")
+    xy = np.concatenate(xy_l) if xy_l else np.zeros((0, 2))
+    det_start = np.zeros(streams + 1, np.int32)
+    det_start[1:] = np.cumsum(counts)
+    if total > 1:
+        # a repeated (stream, id): one sort of stream << b | id where the ids fit in b bits, else a two-key sort
+        owner = np.repeat(np.arange(streams, dtype=np.int64), counts)
+        b = 63 - int(streams - 1).bit_length()
+        if int(ids.max()) < 1 << b:
+            key = np.sort((owner << b) | ids)
+            dup = np.nonzero(key[1:] == key[:-1])[0]
+            if len(dup):
+                raise ValueError("tick: stream %d: duplicate pedestrian id %d in one frame"
+                                 % (key[dup[0]] >> b, key[dup[0]] & ((1 << b) - 1)))
+        else:
+            order = np.lexsort((ids, owner))
+            same = (owner[order[1:]] == owner[order[:-1]]) & (ids[order[1:]] == ids[order[:-1]])
+            if same.any():
+                at = order[1:][same][0]
+                raise ValueError("tick: stream %d: duplicate pedestrian id %d in one frame" % (owner[at], ids[at]))
+    return PackedTick(det_start, pushed, ids, np.ascontiguousarray(xy))
+
+
+class StreamsPredictor:
+    """Live prediction for NS independent streams (cameras, tracker feeds) at once.  Each stream is what a
+    FramePredictor with the same capacity, max_detections, max_peds and decimals would be, fed only that stream's
+    pushes: its own slots, presence masks and ring on the device, so the same pedestrian id in two streams is two
+    tracks and a flag of one stream never shows in another.  One push(tick) stages the whole tick with ONE
+    host->device copy (packed in a pinned buffer) and runs stg_track_push_streams (one workgroup per stream) ->
+    observed_inputs -> forward -> sampler on the NS scenes as one batch padded to max_peds; capture() makes that ONE
+    graph.  The sampler's Philox draws are keyed by the scene's index in the tick: stream s draws what Predictor.predict
+    draws for scene s of the tick's batch, not what a lone FramePredictor with the same seed draws.
+    max_total_detections (default streams * max_detections) sizes the staging buffers."""
+
+    def __init__(self, model, streams, k=20, obs_len=8, capacity=1024, max_peds=128, max_detections=1024, decimals=4,
+                 max_total_detections=None, block_threads=0):
+        self.model = model
+        self.k = int(k)
+        self.t_obs = _obs_len(obs_len)
+        if self.t_obs != model.seq_len:
+            raise ValueError("obs_len=%d but the model observes %d frames" % (self.t_obs, model.seq_len))
+        self.scale = _scale(decimals)
+        self.s, self.v, self.m_max = int(capacity), int(max_peds), int(max_detections)
+        if not 1 <= self.s <= MAX_SLOTS:
+            raise ValueError("capacity must be in [1, %d], got %r" % (MAX_SLOTS, capacity))
+        if not 1 <= self.m_max <= MAX_DETECTIONS:
+            raise ValueError("max_detections must be in [1, %d], got %r" % (MAX_DETECTIONS, max_detections))
+        if self.v < 1:
+            raise ValueError("max_peds must be >= 1, got %r" % (max_peds,))
+        if isinstance(streams, bool) or int(streams) != streams or not 1 <= int(streams) <= MAX_STREAMS:
+            raise ValueError("streams must be an integer in [1, %d], got %r" % (MAX_STREAMS, streams))
+        self.ns = int(streams)
+        if max_total_detections is None:
+            cap = min(self.ns * self.m_max, MAX_TOTAL_DETECTIONS)
+        else:
+            cap = max_total_detections
+            if isinstance(cap, bool) or int(cap) != cap or not 1 <= int(cap) <= MAX_TOTAL_DETECTIONS:
+                raise ValueError("max_total_detections must be an integer in [1, %d], got %r"
+                                 % (MAX_TOTAL_DETECTIONS, max_total_detections))
+        self.cap = int(cap)
+        if block_threads not in (0, 64, 256, 1024):
+            raise ValueError("block_threads must be 0 (default), 64, 256 or 1024, got %r" % (block_threads,))
+        self.block_threads = int(block_threads)
+        dev = next(model.parameters()).device
+        require_gpu(next(model.parameters()))
+        self.device = dev
+        ns, t, s = self.ns, self.t_obs, self.s
+        self.slot_id = torch.empty((ns, s), device=dev, dtype=torch.int64)
+        self.mask = torch.empty((ns, s), device=dev, dtype=torch.int32)
+        self.ring = torch.zeros((ns, t, s, 2), device=dev, dtype=torch.float64)
+        self.head_flags = torch.empty((ns, 2), device=dev, dtype=torch.int32)
+        # staging, the same byte layout on the host (pinned) and on the device: det_start (NS+1) int32 | pushed (NS)
+        # int32 | seed int64 | cap records (id int64, x, y float64).  A tick copies the header and its M records.
+        o_pushed = 4 * (ns + 1)
+        o_seed = (4 * (2 * ns + 1) + 7) // 8 * 8
+        self._hdr = o_seed + 8
+        nbytes = self._hdr + 24 * self.cap
+        self._host = torch.zeros(nbytes, dtype=torch.uint8, pin_memory=True)
+        self._dev = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        hb = self._host.numpy()
+        self._h_start = hb[:o_pushed].view(np.int32)
+        self._h_pushed = hb[o_pushed:o_pushed + 4 * ns].view(np.int32)
+        self._h_seed = hb[o_seed:self._hdr].view(np.int64)
+        self._h_rec_i = hb[self._hdr:].view(np.int64).reshape(self.cap, 3)
+        self._h_rec_f = hb[self._hdr:].view(np.float64).reshape(self.cap, 3)
+        self.det_start = self._dev[:o_pushed].view(torch.int32)
+        self.pushed_dev = self._dev[o_pushed:o_pushed + 4 * ns].view(torch.int32)
+        self.seed_dev = self._dev[o_seed:self._hdr].view(torch.int64)
+        self._rec_i = self._dev[self._hdr:].view(torch.int64).view(self.cap, 3)
+        self._rec_f = self._dev[self._hdr:].view(torch.float64).view(self.cap, 3)
+        self._copied = torch.cuda.Event()
+        self._in_flight = False
+        self._pred = Predictor(model, self.k)
+        self.reset()
+
+    def reset(self, streams=None):
+        """Forget every track of all streams, or of the listed stream indices only (their next obs_len - 1 pushes
+        return empty scenes; the other streams go on)."""
+        if streams is None:
+            self.slot_id.fill_(-1)
+            self.mask.zero_()
+            self.ring.zero_()
+            self.head_flags.zero_()
+            return
+        idx = [int(x) for x in (streams if isinstance(streams, (list, tuple, np.ndarray, range)) else [streams])]
+        for x in idx:
+            if not 0 <= x < self.ns:
+                raise ValueError("reset: stream index %d not in [0, %d)" % (x, self.ns))
+        if not idx:
+            return
+        at = torch.tensor(idx, dtype=torch.int64).to(self.device)
+        self.slot_id.index_fill_(0, at, -1)
+        self.mask.index_fill_(0, at, 0)
+        self.ring.index_fill_(0, at, 0.0)
+        self.head_flags.index_fill_(0, at, 0)
+
+    def _wait_host(self):
+        """The pinned buffer is rewritten only after the previous tick's copy has left it."""
+        if self._in_flight:
+            self._copied.synchronize()
+            self._in_flight = False
+
+    def _copy(self, nbytes):
+        self._dev[:nbytes].copy_(self._host[:nbytes], non_blocking=True)
+        self._copied.record()
+        self._in_flight = True
+
+    def _stage(self, tick, seed):
+        """One tick into the device staging buffer: host detections with ONE copy, device detections by device ops."""
+        if isinstance(tick, DeviceTick):
+            return self._stage_device(tick, seed)
+        pk = pack_tick(tick, self.ns, self.m_max, self.cap)           # refuses before anything is written or copied
+        m = len(pk.ids)
+        self._wait_host()
+        self._h_start[:] = pk.det_start
+        self._h_pushed[:] = pk.pushed
+        if seed is not None:
+            self._h_seed[0] = _seed_i64(seed)
+        if m:
+            self._h_rec_i[:m, 0] = pk.ids
+            self._h_rec_f[:m, 1:] = pk.xy
+        self._copy(self._hdr + 24 * m)
+
+    def _stage_device(self, tick, seed):
+        ids, xy, counts = tick
+        if not (torch.is_tensor(ids) and ids.is_cuda and torch.is_tensor(xy) and xy.is_cuda):
+            raise ValueError("DeviceTick: ids and xy must be device tensors")
+        m = ids.numel()
+        if m > self.cap:
+            raise ValueError("tick: %d detections > max_total_detections=%d" % (m, self.cap))
+        if tuple(xy.shape) != (m, 2):
+            raise ValueError("DeviceTick: xy (%d,2) expected" % m)
+        dev_counts = torch.is_tensor(counts) and counts.is_cuda
+        if not dev_counts:
+            counts = np.asarray(counts.cpu() if torch.is_tensor(counts) else counts).reshape(-1)
+            if counts.dtype.kind not in "iu":
+                raise ValueError("DeviceTick: counts must be integers")
+        n_counts = counts.numel() if dev_counts else counts.size
+        if n_counts != self.ns:
+            raise ValueError("DeviceTick: %d counts for %d streams" % (n_counts, self.ns))
+        self._wait_host()
+        if seed is not None:
+            self._h_seed[0] = _seed_i64(seed)
+        if dev_counts:
+            c = counts.reshape(-1).to(torch.int32)
+            self.pushed_dev.copy_(c >= 0)
+            self.det_start[:1].zero_()
+            torch.cumsum(c.clamp(min=0), 0, dtype=torch.int32, out=self.det_start[1:])
+            self.det_start.clamp_(max=m)
+            if seed is not None:
+                self.seed_dev.fill_(_seed_i64(seed))
+        else:
+            self._h_pushed[:] = counts >= 0
+            self._h_start[0] = 0
+            self._h_start[1:] = np.minimum(np.cumsum(np.maximum(counts.astype(np.int64), 0)), m)
+            self._copy(self._hdr)
+        if m:
+            self._rec_i[:m, 0].copy_(ids.reshape(-1))
+            self._rec_f[:m, 1:].copy_(xy)
+
+    def _outs(self):
+        dev, ns, t, v = self.device, self.ns, self.t_obs, self.v
+        return (torch.empty((ns, t, v, 2), device=dev, dtype=torch.float64),
+                torch.empty((ns, v), device=dev, dtype=torch.int64), torch.empty(ns, device=dev, dtype=torch.int32),
+                torch.empty(ns, device=dev, dtype=torch.int32), torch.empty(ns, device=dev, dtype=torch.bool))
+
+    def _push(self, outs):
+        obs, ids, peds, flags, pushed = outs
+        check(lib().stg_track_push_streams(ptr(self._rec_i), 3, ctypes.c_void_p(self._rec_f.data_ptr() + 8), 3,
+                                           self.cap, ptr(self.det_start), ptr(self.pushed_dev), self.ns, self.m_max,
+                                           ptr(self.slot_id), ptr(self.mask), ptr(self.ring), ptr(self.head_flags),
+                                           self.s, self.t_obs, ctypes.c_double(self.scale), self.v, ptr(obs), ptr(ids),
+                                           ptr(peds), ptr(flags), self.block_threads, stream_ptr()),
+              "stg_track_push_streams")
+        torch.ne(self.pushed_dev, 0, out=pushed)
+
+    @staticmethod
+    def _tick(outs, r):
+        obs, ids, peds, flags, pushed = outs
+        return StreamsPrediction(ids, peds, obs, r.samples, r.mean, r.v_pred, flags, pushed)
+
+    @torch.no_grad()
+    def push(self, tick, seed=None, noise=None):
+        """One tick: a mapping {stream index: (ids, xy)}, a length-NS sequence of (ids, xy) or None (host arrays; see
+        pack_tick), or a DeviceTick.  seed: the sampler's Philox seed from now on (None keeps the last one); noise
+        (K,NS,P,V,2) standard normals instead of the Philox stream.  Runs eagerly."""
+        self._stage(tick, seed)
+        outs = self._outs()
+        self._push(outs)
+        was = self.model.training
+        self.model.eval()
+        try:
+            r = self._pred._forward(outs[0], outs[2], 0, noise, self.seed_dev)
+        finally:
+            self.model.train(was)
+        return self._tick(outs, r)
+
+    @torch.no_grad()
+    def capture(self, warmup=2):
+        """Capture ONE linear graph: stg_track_push_streams -> observed_inputs -> forward -> stg_sample_trajectories on
+        static buffers, the seed read from the device staging buffer.  Returns replay(tick, seed=None) ->
+        StreamsPrediction on the static outputs; the tick is staged (one host->device copy) outside the graph.  Warm-up
+        and capture run with no stream pushed, so every stream's state stays as it was."""
+        model, dev, ns, t, v, p = self.model, self.device, self.ns, self.t_obs, self.v, self.model.pred_seq_len
+        outs = self._outs()
+        bufs = (torch.empty((ns, t, v, 2), device=dev, dtype=torch.float32),
+                torch.empty((ns, t, v, 2), device=dev, dtype=torch.float32),
+                torch.empty((ns, t, v, v), device=dev, dtype=torch.float32))
+        samp = (torch.empty((self.k, ns, p, v, 2), device=dev, dtype=torch.float32),
+                torch.empty((ns, p, v, 2), device=dev, dtype=torch.float32))
+
+        def step():
+            self._push(outs)
+            return self._pred._forward(outs[0], outs[2], 0, None, self.seed_dev, bufs, samp)
+        was = model.training
+        model.eval()
+        try:
+            self.det_start.zero_()
+            self.pushed_dev.zero_()                    # the warm-up touches no stream's state
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                for _ in range(max(1, warmup)):
+                    step()
+            torch.cuda.current_stream().wait_stream(side)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                r = step()
+        finally:
+            model.train(was)
+        res = self._tick(outs, r)
+        # every buffer the graph reads or writes lives as long as the returned replay
+        static = (outs, bufs, samp, graph)
+
+        def replay(tick, seed=None):
+            self._stage(tick, seed)
             static[3].replay()
             return res
         return replay

@@ -2,6 +2,7 @@
 """Per-frame prediction timings (social_stgcnn_amd.frames).  One JSON line per case.
 
     python tools/frames_bench.py [--pushes 2000] [--cases latency,recording] [--k 20]
+    python tools/frames_bench.py --cases streams [--streams 1,8,64,256,600] [--ticks 200] [--block 0] [--no-lone]
 
   latency    the captured FramePredictor (ONE graph: stg_track_push -> observed_inputs -> forward -> sampler) pushed
              every frame of a recording in a loop, --pushes timed pushes after a warm-up.  Host clock around staging +
@@ -9,6 +10,12 @@
              max_peds 32 and 128 (biwi_eth, up to 20 pedestrians) and 128 (students001, up to 73).
   recording  predict_recording (batches of 64 frame scenes) on each test recording: frames/s, host clock around the
              call and a synchronise, after one warm-up call.
+  streams    NS streams in ONE captured StreamsPredictor graph (stg_track_push_streams -> forward -> sampler), the six
+             test recordings cycled with staggered starts, every stream pushed every tick, max_peds 128: tick p50 / p90
+             (host clock around staging + replay + synchronise) and aggregate frames/s.  Beside it the yardstick: the
+             same per-stream sequences through NS lone captured FramePredictors one after another (each push timed as
+             the latency case times it; a tick is the sum of its NS pushes).  --block picks the push workgroup size
+             (0: the default); --no-lone skips the yardstick.
 
 Kernel times come from a separate run under the profiler (tracing slows the host):
     rocprofv3 --kernel-trace --stats -d OUT -o frames -- python tools/frames_bench.py --cases latency --pushes 500
@@ -88,11 +95,74 @@ def recording_case(split, rec, k, dev):
             "v": int(sc.ids.shape[1]), "seconds": round(secs, 4), "frames_per_s": round(n / secs, 1)}
 
 
+def _stream_sequences(ns, n):
+    """Per stream the first n pushes of a test recording (cycled over the streams), from a staggered start."""
+    from social_stgcnn_amd import data
+    recs = [pushes_of(data.read_file(os.path.join(DATA, rec))) for _, rec in TEST_RECORDINGS]
+    out = []
+    for s in range(ns):
+        p = recs[s % len(recs)]
+        off = (s // len(recs)) * 7
+        out.append([p[(off + t) % len(p)] for t in range(n)])
+    return out
+
+
+def streams_case(ns, k, n_ticks, dev, block=0, lone=True, max_peds=128, warmup=20):
+    from social_stgcnn_amd import frames
+    model = model_for("univ", dev)
+    seq = _stream_sequences(ns, warmup + n_ticks)
+    sp = frames.StreamsPredictor(model, ns, k=k, max_peds=max_peds, block_threads=block)
+    replay = sp.capture()
+    times, peds = [], []
+    for t in range(warmup + n_ticks):
+        tick = [q[t] for q in seq]
+        t0 = time.perf_counter()
+        out = replay(tick)
+        torch.cuda.synchronize()
+        if t >= warmup:
+            times.append(time.perf_counter() - t0)
+            peds.append(out.num_peds.clone())
+    ms = np.array(times) * 1e3
+    peds = torch.stack(peds).cpu().numpy()
+    p50 = float(np.percentile(ms, 50))
+    res = {"case": "streams", "streams": ns, "k": k, "max_peds": max_peds, "block": block or frames.STREAM_THREADS,
+           "ticks": n_ticks, "tick_p50_ms": round(p50, 4), "tick_p90_ms": round(float(np.percentile(ms, 90)), 4),
+           "frames_per_s_p50": round(ns * 1e3 / p50, 1), "mean_peds": round(float(peds.mean()), 2),
+           "max_peds_seen": int(peds.max())}
+    if lone:
+        # the yardstick: NS lone captured FramePredictors, one after another; fewer ticks at large NS
+        n_seq = max(10, min(n_ticks, 4000 // ns))
+        fps = [frames.FramePredictor(model, k=k, max_peds=max_peds) for _ in range(ns)]
+        pushes = [fp.capture() for fp in fps]
+        times = []
+        for t in range(warmup + n_seq):
+            tot = 0.0
+            for s in range(ns):
+                ids, xy = seq[s][t]
+                t0 = time.perf_counter()
+                pushes[s](ids, xy)
+                torch.cuda.synchronize()
+                tot += time.perf_counter() - t0
+            if t >= warmup:
+                times.append(tot)
+        ms = np.array(times) * 1e3
+        seq_p50 = float(np.percentile(ms, 50))
+        res.update({"lone_ticks": n_seq, "lone_tick_p50_ms": round(seq_p50, 4),
+                    "lone_tick_p90_ms": round(float(np.percentile(ms, 90)), 4),
+                    "lone_frames_per_s_p50": round(ns * 1e3 / seq_p50, 1), "speedup_p50": round(seq_p50 / p50, 2)})
+        del pushes, fps
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--pushes", type=int, default=2000)
     ap.add_argument("--cases", default="latency,recording")
     ap.add_argument("--k", type=int, default=20)
+    ap.add_argument("--streams", default="1,8,64,256,600")
+    ap.add_argument("--ticks", type=int, default=200)
+    ap.add_argument("--block", default="0", help="push workgroup size(s) of the streams case, comma separated")
+    ap.add_argument("--no-lone", action="store_true")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("frames_bench needs a GPU (MI355X)")
@@ -105,6 +175,10 @@ def main():
     if "recording" in cases:
         for split, rec in TEST_RECORDINGS:
             print(json.dumps(recording_case(split, rec, a.k, dev)), flush=True)
+    if "streams" in cases:
+        for block in (int(b) for b in a.block.split(",")):
+            for ns in (int(n) for n in a.streams.split(",")):
+                print(json.dumps(streams_case(ns, a.k, a.ticks, dev, block, not a.no_lone)), flush=True)
 
 
 if __name__ == "__main__":
