@@ -13,7 +13,7 @@ validation epoch does the same with gather -> adj_build -> eval forward -> per-s
 import numpy as np
 import torch
 
-from . import ops
+from . import graphs, ops
 from ._lib import check, lib, ptr, require_gpu, stream_ptr
 
 
@@ -136,14 +136,7 @@ class EpochRunner:
                 y, _ = model(nodes.permute(0, 3, 1, 2), adj, peds)
                 losses = ops.bivariate_nll(y.permute(0, 2, 3, 1), target, peds)
                 return ops.weighted_sum(losses, weights)
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                group_total()                                   # (warm-up: an eval pass changes nothing)
-            torch.cuda.current_stream().wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                total = group_total()
+            graph, total = graphs.warm_capture(group_total, 1)  # (warm-up: an eval pass changes nothing)
             # (the graph reads `weights` and the index slice at every replay: they live as long as the graph)
             g = self._val_replays[cnt] = (graph, total, index, weights)
         return g

@@ -17,6 +17,11 @@ stg_frame_scenes over a recording uploaded once, stg_track_push with the track s
     FramePredictor     push(ids, xy) per frame, eager or as ONE captured graph (capture())
     StreamsPredictor   NS independent live streams: push(tick) per tick, one host->device copy of the packed
                        detections and ONE launch chain (stg_track_push_streams -> the batched forward -> sampler)
+
+The two live predictors are one core, _LivePredictor: the argument checks, the track state, the eager push and its
+capture (the push kernel ahead of predict.Predictor.capture_chain; the capture recipe itself is graphs.py).  Each class
+keeps what is its own: how a push is staged, its push kernel, its result tuple, its reset, and how the warm-up is kept
+from moving the tracks.
 """
 import collections
 import collections.abc
@@ -26,7 +31,7 @@ import numpy as np
 import torch
 
 from ._lib import check, lib, ptr, require_gpu, stream_ptr
-from .predict import Prediction, Predictor, _seed_i64
+from .predict import Prediction, Predictor, _seed_i64, eval_mode
 
 MAX_OBS_LEN = 32                       # presence masks are 32-bit
 MAX_DETECTIONS = 2048                  # STG_TRACK_MAX_DETECTIONS
@@ -48,8 +53,13 @@ OVERFLOW | TRUNCATED | TOO_MANY of this push).  From a captured push the tensors
 overwritten by the next push."""
 
 
+def _is_int(x, lo, hi=None):
+    """x is an integer (a bool is not) with lo <= x (<= hi)."""
+    return not isinstance(x, bool) and int(x) == x and lo <= int(x) and (hi is None or int(x) <= hi)
+
+
 def _obs_len(obs_len):
-    if isinstance(obs_len, bool) or int(obs_len) != obs_len or not 1 <= int(obs_len) <= MAX_OBS_LEN:
+    if not _is_int(obs_len, 1, MAX_OBS_LEN):
         raise ValueError("obs_len must be an integer in [1, %d], got %r" % (MAX_OBS_LEN, obs_len))
     return int(obs_len)
 
@@ -58,7 +68,7 @@ def _scale(decimals):
     """np.around's 10^decimals (0.0: no rounding)."""
     if decimals is None:
         return 0.0
-    if isinstance(decimals, bool) or int(decimals) != decimals or not 0 <= int(decimals) <= 15:
+    if not _is_int(decimals, 0, 15):
         raise ValueError("decimals must be None or an integer in [0, 15], got %r" % (decimals,))
     return float(10 ** int(decimals))
 
@@ -104,7 +114,7 @@ def recording_scenes(rows, device, obs_len=8, min_peds=1, decimals=4, v_pad=None
     (stg_frame_scene_counts, then stg_frame_scenes) and one read-back of the per-frame counts."""
     obs_len = _obs_len(obs_len)
     scale = _scale(decimals)
-    if isinstance(min_peds, bool) or int(min_peds) != min_peds or min_peds < 0:
+    if not _is_int(min_peds, 0):
         raise ValueError("min_peds must be an integer >= 0, got %r" % (min_peds,))
     frames, fs, ids, xy = sorted_rows(rows)
     device = torch.device(device)
@@ -178,13 +188,19 @@ def host_detections(ids, xy, max_detections):
     return ids_np, np.ascontiguousarray(xy_np)
 
 
-class FramePredictor:
-    """Live prediction: push(ids, xy) with one frame of detections returns that frame's scene (the pedestrians seen
-    in each of the last obs_len pushes, ascending ids, at most max_peds: the smallest) and K sampled trajectories per
-    pedestrian.  The tracks live on the device (stg_track_push): `capacity` slots, a slot freed once its pedestrian has
-    been missing for obs_len - 1 frames.  Ids come from the caller's tracker (association is not done here)."""
+class _LivePredictor:
+    """What FramePredictor and StreamsPredictor share: the argument checks, the track state on the device (with the
+    subclass's leading axis), the eager push and its capture as ONE graph.  A subclass supplies
 
-    def __init__(self, model, k=20, obs_len=8, capacity=1024, max_peds=128, max_detections=1024, decimals=4):
+        _stage(*det, seed)       copy one push's detections (and the seed, unless None) into its device staging buffers
+        _outs()                  fresh per-push outputs (obs_abs, ids, num_peds, ...)
+        _push(outs)              launch its push kernel: staging buffers + track state -> outs
+        _wrap(outs, r, static)   the result tuple of outs and the chain's Prediction r (static: a captured push)
+        _still()                 make warm-up pushes harmless; returns the (tensor, saved copy) pairs to put back after
+
+    and `seed_dev`, the (1,) int64 device tensor the sampler reads its seed from."""
+
+    def __init__(self, model, k, obs_len, capacity, max_peds, max_detections, decimals):
         self.model = model
         self.k = int(k)
         self.t_obs = _obs_len(obs_len)
@@ -198,19 +214,72 @@ class FramePredictor:
             raise ValueError("max_detections must be in [1, %d], got %r" % (MAX_DETECTIONS, max_detections))
         if self.v < 1:
             raise ValueError("max_peds must be >= 1, got %r" % (max_peds,))
-        dev = next(model.parameters()).device
-        require_gpu(next(model.parameters()))
+
+    def _track_state(self, lead=()):
+        """Look the model's device up (every argument has been checked by now) and allocate the track state, one set
+        per index of `lead`: slot ids, presence masks, the position ring and {head, flags}."""
+        dev = next(self.model.parameters()).device
+        require_gpu(next(self.model.parameters()))
         self.device = dev
-        t, s, v, m = self.t_obs, self.s, self.v, self.m_max
-        self.slot_id = torch.empty(s, device=dev, dtype=torch.int64)
-        self.mask = torch.empty(s, device=dev, dtype=torch.int32)
-        self.ring = torch.zeros((t, s, 2), device=dev, dtype=torch.float64)
-        self.head_flags = torch.empty(2, device=dev, dtype=torch.int32)
+        self.slot_id = torch.empty(lead + (self.s,), device=dev, dtype=torch.int64)
+        self.mask = torch.empty(lead + (self.s,), device=dev, dtype=torch.int32)
+        self.ring = torch.zeros(lead + (self.t_obs, self.s, 2), device=dev, dtype=torch.float64)
+        self.head_flags = torch.empty(lead + (2,), device=dev, dtype=torch.int32)
+        self._pred = Predictor(self.model, self.k)
+        return dev
+
+    @torch.no_grad()
+    def push(self, *det, seed=None, noise=None):
+        """One push, run eagerly: `det` as the class describes it.  seed (by keyword): the sampler's Philox seed from
+        now on (None keeps the last one); noise (K,N,P,V,2) standard normals instead of the Philox stream, N = 1 or
+        the number of streams.  The outputs are fresh tensors: earlier results stay."""
+        self._stage(*det, seed)
+        outs = self._outs()
+        self._push(outs)
+        with eval_mode(self.model):
+            r = self._pred._forward(outs[0], outs[2], 0, noise, self.seed_dev)
+        return self._wrap(outs, r, False)
+
+    @torch.no_grad()
+    def capture(self, warmup=2):
+        """Capture ONE linear graph: the push kernel -> observed_inputs -> forward -> stg_sample_trajectories on static
+        buffers, the seed read from `seed_dev` (Predictor.capture_chain).  Returns replay(*det, seed=None) -> the
+        result on the static outputs, overwritten by the next replay; the detections are staged outside the graph.
+        Warm-up and capture leave the track state as it was."""
+        outs = self._outs()
+        saved = self._still()
+        try:
+            graph, r, chain = self._pred.capture_chain(outs[0], outs[2], self.seed_dev, warmup,
+                                                       pre=lambda: self._push(outs))
+        finally:
+            for x, x0 in saved:
+                x.copy_(x0)
+        res = self._wrap(outs, r, True)
+        # every buffer the graph reads or writes lives as long as the returned replay
+        static = (outs, chain, graph)
+
+        def replay(*det, seed=None):
+            self._stage(*det, seed)
+            static[2].replay()
+            return res
+        return replay
+
+
+class FramePredictor(_LivePredictor):
+    """Live prediction: push(ids, xy) with one frame of detections returns that frame's scene (the pedestrians seen
+    in each of the last obs_len pushes, ascending ids, at most max_peds: the smallest) and K sampled trajectories per
+    pedestrian, as a FramePrediction.  ids (M,) integral, xy (M,2) positions: host arrays (a repeated id is refused)
+    or device tensors (a repeated id: the first detection wins, flag DUPLICATE).  The tracks live on the device
+    (stg_track_push): `capacity` slots, a slot freed once its pedestrian has been missing for obs_len - 1 frames.  Ids
+    come from the caller's tracker (association is not done here)."""
+
+    def __init__(self, model, k=20, obs_len=8, capacity=1024, max_peds=128, max_detections=1024, decimals=4):
+        super().__init__(model, k, obs_len, capacity, max_peds, max_detections, decimals)
+        dev, m = self._track_state(), self.m_max
         self.det_id = torch.zeros(m, device=dev, dtype=torch.int64)
         self.det_xy = torch.zeros((m, 2), device=dev, dtype=torch.float64)
         self.det_count = torch.zeros(1, device=dev, dtype=torch.int32)
         self.seed_dev = torch.zeros(1, device=dev, dtype=torch.int64)
-        self._pred = Predictor(model, self.k)
         self.reset()
 
     def reset(self):
@@ -251,71 +320,17 @@ class FramePredictor:
                                    self.t_obs, ctypes.c_double(self.scale), self.v, ptr(obs), ptr(ids), ptr(peds),
                                    stream_ptr()), "stg_track_push")
 
-    @staticmethod
-    def _frame(outs, r, flags):
+    def _wrap(self, outs, r, static):
         obs, ids, peds = outs
-        return FramePrediction(ids, peds, obs, r.samples[:, 0], r.mean[0], r.v_pred[0], flags)
+        flags = self.head_flags[1:]          # (a captured push returns the state's own flags word)
+        return FramePrediction(ids, peds, obs, r.samples[:, 0], r.mean[0], r.v_pred[0],
+                               flags if static else flags.clone())
 
-    @torch.no_grad()
-    def push(self, ids, xy, seed=None, noise=None):
-        """One frame: ids (M,) integral, xy (M,2) positions, host arrays (a repeated id is refused) or device tensors
-        (a repeated id: the first detection wins, flag DUPLICATE).  seed: the sampler's Philox seed from now on (None
-        keeps the last one); noise (K,1,P,V,2) standard normals instead of the Philox stream.  Runs eagerly."""
-        self._stage(ids, xy, seed)
-        outs = self._outs()
-        self._push(outs)
-        was = self.model.training
-        self.model.eval()
-        try:
-            r = self._pred._forward(outs[0], outs[2], 0, noise, self.seed_dev)
-        finally:
-            self.model.train(was)
-        return self._frame(outs, r, self.head_flags[1:].clone())
-
-    @torch.no_grad()
-    def capture(self, warmup=2):
-        """Capture ONE graph: stg_track_push -> observed_inputs -> forward -> stg_sample_trajectories, on static
-        buffers, the seed read from a device tensor (as Predictor.capture).  Returns push(ids, xy, seed=None) ->
-        FramePrediction on the static outputs; the detections are copied into the static buffers outside the graph.
-        Warm-up and capture leave the track state as it was."""
-        model, dev, t, v, p = self.model, self.device, self.t_obs, self.v, self.model.pred_seq_len
-        outs = self._outs()
-        bufs = (torch.empty((1, t, v, 2), device=dev, dtype=torch.float32),
-                torch.empty((1, t, v, 2), device=dev, dtype=torch.float32),
-                torch.empty((1, t, v, v), device=dev, dtype=torch.float32))
-        samp = (torch.empty((self.k, 1, p, v, 2), device=dev, dtype=torch.float32),
-                torch.empty((1, p, v, 2), device=dev, dtype=torch.float32))
-        saved = [x.clone() for x in (self.slot_id, self.mask, self.ring, self.head_flags, self.det_count)]
-
-        def step():
-            self._push(outs)
-            return self._pred._forward(outs[0], outs[2], 0, None, self.seed_dev, bufs, samp)
-        was = model.training
-        model.eval()
-        try:
-            self.det_count.zero_()
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(max(1, warmup)):
-                    step()
-            torch.cuda.current_stream().wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                r = step()
-        finally:
-            model.train(was)
-            for x, y in zip((self.slot_id, self.mask, self.ring, self.head_flags, self.det_count), saved):
-                x.copy_(y)
-        res = self._frame(outs, r, self.head_flags[1:])
-        # every buffer the graph reads or writes lives as long as the returned push
-        static = (outs, bufs, samp, graph)
-
-        def replay(ids, xy, seed=None):
-            self._stage(ids, xy, seed)
-            static[3].replay()
-            return res
-        return replay
+    def _still(self):
+        """The warm-up pushes frames without detections, which age the tracks: the state goes back after it."""
+        saved = [(x, x.clone()) for x in (self.slot_id, self.mask, self.ring, self.head_flags, self.det_count)]
+        self.det_count.zero_()
+        return saved
 
 
 StreamsPrediction = collections.namedtuple("StreamsPrediction", "ids num_peds obs_abs samples mean v_pred flags pushed")
@@ -403,54 +418,38 @@ def pack_tick(tick, streams, max_detections, max_total_detections):
     return PackedTick(det_start, pushed, ids, np.ascontiguousarray(xy))
 
 
-class StreamsPredictor:
+class StreamsPredictor(_LivePredictor):
     """Live prediction for NS independent streams (cameras, tracker feeds) at once.  Each stream is what a
     FramePredictor with the same capacity, max_detections, max_peds and decimals would be, fed only that stream's
     pushes: its own slots, presence masks and ring on the device, so the same pedestrian id in two streams is two
-    tracks and a flag of one stream never shows in another.  One push(tick) stages the whole tick with ONE
-    host->device copy (packed in a pinned buffer) and runs stg_track_push_streams (one workgroup per stream) ->
+    tracks and a flag of one stream never shows in another.  One push(tick) -> StreamsPrediction stages the whole tick
+    with ONE host->device copy (packed in a pinned buffer) and runs stg_track_push_streams (one workgroup per stream) ->
     observed_inputs -> forward -> sampler on the NS scenes as one batch padded to max_peds; capture() makes that ONE
-    graph.  The sampler's Philox draws are keyed by the scene's index in the tick: stream s draws what Predictor.predict
-    draws for scene s of the tick's batch, not what a lone FramePredictor with the same seed draws.
+    graph, warmed up and captured with no stream pushed.  tick: a mapping {stream index: (ids, xy)}, a length-NS
+    sequence of (ids, xy) or None (host arrays; see pack_tick), or a DeviceTick.  The sampler's Philox draws are keyed
+    by the scene's index in the tick: stream s draws what Predictor.predict draws for scene s of the tick's batch, not
+    what a lone FramePredictor with the same seed draws.  The seed lives in the staging block.
     max_total_detections (default streams * max_detections) sizes the staging buffers."""
 
     def __init__(self, model, streams, k=20, obs_len=8, capacity=1024, max_peds=128, max_detections=1024, decimals=4,
                  max_total_detections=None, block_threads=0):
-        self.model = model
-        self.k = int(k)
-        self.t_obs = _obs_len(obs_len)
-        if self.t_obs != model.seq_len:
-            raise ValueError("obs_len=%d but the model observes %d frames" % (self.t_obs, model.seq_len))
-        self.scale = _scale(decimals)
-        self.s, self.v, self.m_max = int(capacity), int(max_peds), int(max_detections)
-        if not 1 <= self.s <= MAX_SLOTS:
-            raise ValueError("capacity must be in [1, %d], got %r" % (MAX_SLOTS, capacity))
-        if not 1 <= self.m_max <= MAX_DETECTIONS:
-            raise ValueError("max_detections must be in [1, %d], got %r" % (MAX_DETECTIONS, max_detections))
-        if self.v < 1:
-            raise ValueError("max_peds must be >= 1, got %r" % (max_peds,))
-        if isinstance(streams, bool) or int(streams) != streams or not 1 <= int(streams) <= MAX_STREAMS:
+        super().__init__(model, k, obs_len, capacity, max_peds, max_detections, decimals)
+        if not _is_int(streams, 1, MAX_STREAMS):
             raise ValueError("streams must be an integer in [1, %d], got %r" % (MAX_STREAMS, streams))
         self.ns = int(streams)
         if max_total_detections is None:
             cap = min(self.ns * self.m_max, MAX_TOTAL_DETECTIONS)
         else:
             cap = max_total_detections
-            if isinstance(cap, bool) or int(cap) != cap or not 1 <= int(cap) <= MAX_TOTAL_DETECTIONS:
+            if not _is_int(cap, 1, MAX_TOTAL_DETECTIONS):
                 raise ValueError("max_total_detections must be an integer in [1, %d], got %r"
                                  % (MAX_TOTAL_DETECTIONS, max_total_detections))
         self.cap = int(cap)
         if block_threads not in (0, 64, 256, 1024):
             raise ValueError("block_threads must be 0 (default), 64, 256 or 1024, got %r" % (block_threads,))
         self.block_threads = int(block_threads)
-        dev = next(model.parameters()).device
-        require_gpu(next(model.parameters()))
-        self.device = dev
-        ns, t, s = self.ns, self.t_obs, self.s
-        self.slot_id = torch.empty((ns, s), device=dev, dtype=torch.int64)
-        self.mask = torch.empty((ns, s), device=dev, dtype=torch.int32)
-        self.ring = torch.zeros((ns, t, s, 2), device=dev, dtype=torch.float64)
-        self.head_flags = torch.empty((ns, 2), device=dev, dtype=torch.int32)
+        ns = self.ns
+        dev = self._track_state((ns,))
         # staging, the same byte layout on the host (pinned) and on the device: det_start (NS+1) int32 | pushed (NS)
         # int32 | seed int64 | cap records (id int64, x, y float64).  A tick copies the header and its M records.
         o_pushed = 4 * (ns + 1)
@@ -472,7 +471,6 @@ class StreamsPredictor:
         self._rec_f = self._dev[self._hdr:].view(torch.float64).view(self.cap, 3)
         self._copied = torch.cuda.Event()
         self._in_flight = False
-        self._pred = Predictor(model, self.k)
         self.reset()
 
     def reset(self, streams=None):
@@ -576,66 +574,12 @@ class StreamsPredictor:
               "stg_track_push_streams")
         torch.ne(self.pushed_dev, 0, out=pushed)
 
-    @staticmethod
-    def _tick(outs, r):
+    def _wrap(self, outs, r, static):
         obs, ids, peds, flags, pushed = outs
         return StreamsPrediction(ids, peds, obs, r.samples, r.mean, r.v_pred, flags, pushed)
 
-    @torch.no_grad()
-    def push(self, tick, seed=None, noise=None):
-        """One tick: a mapping {stream index: (ids, xy)}, a length-NS sequence of (ids, xy) or None (host arrays; see
-        pack_tick), or a DeviceTick.  seed: the sampler's Philox seed from now on (None keeps the last one); noise
-        (K,NS,P,V,2) standard normals instead of the Philox stream.  Runs eagerly."""
-        self._stage(tick, seed)
-        outs = self._outs()
-        self._push(outs)
-        was = self.model.training
-        self.model.eval()
-        try:
-            r = self._pred._forward(outs[0], outs[2], 0, noise, self.seed_dev)
-        finally:
-            self.model.train(was)
-        return self._tick(outs, r)
-
-    @torch.no_grad()
-    def capture(self, warmup=2):
-        """Capture ONE linear graph: stg_track_push_streams -> observed_inputs -> forward -> stg_sample_trajectories on
-        static buffers, the seed read from the device staging buffer.  Returns replay(tick, seed=None) ->
-        StreamsPrediction on the static outputs; the tick is staged (one host->device copy) outside the graph.  Warm-up
-        and capture run with no stream pushed, so every stream's state stays as it was."""
-        model, dev, ns, t, v, p = self.model, self.device, self.ns, self.t_obs, self.v, self.model.pred_seq_len
-        outs = self._outs()
-        bufs = (torch.empty((ns, t, v, 2), device=dev, dtype=torch.float32),
-                torch.empty((ns, t, v, 2), device=dev, dtype=torch.float32),
-                torch.empty((ns, t, v, v), device=dev, dtype=torch.float32))
-        samp = (torch.empty((self.k, ns, p, v, 2), device=dev, dtype=torch.float32),
-                torch.empty((ns, p, v, 2), device=dev, dtype=torch.float32))
-
-        def step():
-            self._push(outs)
-            return self._pred._forward(outs[0], outs[2], 0, None, self.seed_dev, bufs, samp)
-        was = model.training
-        model.eval()
-        try:
-            self.det_start.zero_()
-            self.pushed_dev.zero_()                    # the warm-up touches no stream's state
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(max(1, warmup)):
-                    step()
-            torch.cuda.current_stream().wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                r = step()
-        finally:
-            model.train(was)
-        res = self._tick(outs, r)
-        # every buffer the graph reads or writes lives as long as the returned replay
-        static = (outs, bufs, samp, graph)
-
-        def replay(tick, seed=None):
-            self._stage(tick, seed)
-            static[3].replay()
-            return res
-        return replay
+    def _still(self):
+        """Warm-up and capture run with no stream pushed, so no stream's state moves and nothing is put back."""
+        self.det_start.zero_()
+        self.pushed_dev.zero_()
+        return ()

@@ -4,15 +4,17 @@ test_v.py / visualize.py read.
 
     observed_inputs   obs_abs (N,T_obs,V,2) -> model input x, adjacency, last observed position
     Predictor         relative coordinates -> adj_build -> fused forward -> stg_sample_trajectories; eager
-                      (`predict`) or as ONE captured graph (`capture`)
+                      (`predict`) or as ONE captured graph (`capture`; `capture_chain` is the same chain on the
+                      caller's static inputs, which frames.py puts behind its push kernels)
     sample_test       test() over data.SceneWindows: (ade, fde, raw_data_dict)
 """
 import collections
+import contextlib
 
 import numpy as np
 import torch
 
-from . import data, ops
+from . import data, graphs, ops
 from ._lib import peds_arg, require_gpu
 
 Prediction = collections.namedtuple("Prediction", "samples mean v_pred")
@@ -59,6 +61,17 @@ def observed_inputs(obs_abs, num_peds=None, out=None):
     return nodes.permute(0, 3, 1, 2), adj, obs_abs[:, -1].to(torch.float32)
 
 
+@contextlib.contextmanager
+def eval_mode(model):
+    """The model in eval mode inside the block, its own mode again after it (after an exception too)."""
+    was = model.training
+    model.eval()
+    try:
+        yield
+    finally:
+        model.train(was)
+
+
 class Predictor:
     """K sampled trajectories per pedestrian from observed absolute tracks, for a whole batch of scenes."""
 
@@ -78,14 +91,37 @@ class Predictor:
         (the kernel's Philox stream keyed by `seed`).  Runs the model in eval mode and restores its mode."""
         require_gpu(obs_abs)
         peds = peds_arg(num_peds, obs_abs.shape[0], obs_abs.device)
-        was = self.model.training
-        self.model.eval()
-        try:
+        with eval_mode(self.model):
             return self._forward(obs_abs, peds, seed, noise)
-        finally:
-            self.model.train(was)
+
+    def _chain_buffers(self, n, v, dev):
+        """The chain's static buffers for n scenes padded to v pedestrians: (rel, nodes, adj) that observed_inputs
+        fills and (samples, mean) that the sampler fills."""
+        t_obs, p = self.model.seq_len, self.model.pred_seq_len
+        f32 = dict(device=dev, dtype=torch.float32)
+        return ((torch.empty((n, t_obs, v, 2), **f32), torch.empty((n, t_obs, v, 2), **f32),
+                 torch.empty((n, t_obs, v, v), **f32)),
+                (torch.empty((self.k, n, p, v, 2), **f32), torch.empty((n, p, v, 2), **f32)))
 
     @torch.no_grad()
+    def capture_chain(self, obs, peds, seed_dev, warmup=2, pre=None):
+        """Capture ONE graph on the static obs (N,T_obs,V,2), peds (N,) int32 and seed_dev (1,) int64: [pre() ->]
+        observed_inputs -> fused forward -> stg_sample_trajectories, the model in eval mode, the seed read from
+        seed_dev.  `pre` (optional callable) runs inside the graph ahead of the chain -- the live predictors' push
+        launch, which fills obs and peds; it runs in the warm-up too.  Returns (graph, the static Prediction, the
+        chain's own buffers): every buffer the graph reads or writes has to live as long as the graph is replayed -- a
+        freed one would go back to the caching allocator while the graph still writes it."""
+        n, _, v, _ = obs.shape
+        bufs, outs = self._chain_buffers(n, v, obs.device)
+
+        def step():
+            if pre is not None:
+                pre()
+            return self._forward(obs, peds, 0, None, seed_dev, bufs, outs)
+        with eval_mode(self.model):
+            graph, res = graphs.warm_capture(step, warmup)
+        return graph, res, (bufs, outs)
+
     def capture(self, n, v, num_peds, dtype=torch.float32, warmup=2):
         """Capture ONE graph on static buffers for batches of n scenes padded to v pedestrians, positions of `dtype`
         (see observed_inputs): relative coordinates -> adj_build -> fused forward -> stg_sample_trajectories, the seed
@@ -95,35 +131,13 @@ class Predictor:
         next replay); the arguments are copied into the static buffers outside the graph, None keeps the last one."""
         if not (torch.is_tensor(num_peds) and num_peds.is_cuda):
             raise ValueError("capture() needs num_peds as a device tensor (no host->device copies in a graph)")
-        model = self.model
         dev = num_peds.device
-        t_obs, p = model.seq_len, model.pred_seq_len
         peds = peds_arg(num_peds, n, dev).clone()
-        obs = torch.zeros((n, t_obs, v, 2), device=dev, dtype=dtype)
+        obs = torch.zeros((n, self.model.seq_len, v, 2), device=dev, dtype=dtype)
         seed_dev = torch.zeros(1, device=dev, dtype=torch.int64)
-        bufs = (torch.empty((n, t_obs, v, 2), device=dev, dtype=torch.float32),
-                torch.empty((n, t_obs, v, 2), device=dev, dtype=torch.float32),
-                torch.empty((n, t_obs, v, v), device=dev, dtype=torch.float32))
-        outs = (torch.empty((self.k, n, p, v, 2), device=dev, dtype=torch.float32),
-                torch.empty((n, p, v, 2), device=dev, dtype=torch.float32))
-        was = model.training
-        model.eval()
-        try:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(max(1, warmup)):
-                    self._forward(obs, peds, 0, None, seed_dev, bufs, outs)
-            torch.cuda.current_stream().wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                res = self._forward(obs, peds, 0, None, seed_dev, bufs, outs)
-        finally:
-            model.train(was)
+        graph, res, chain = self.capture_chain(obs, peds, seed_dev, warmup)
         self._graph = graph
-        # every buffer the graph reads or writes lives as long as replay(): a freed one would go back to the caching
-        # allocator while the graph still writes it
-        static = (obs, peds, seed_dev, bufs, outs)
+        static = (obs, peds, seed_dev, chain)          # (alive as long as replay())
 
         def replay(obs_abs, num_peds=None, seed=None):
             obs_s, peds_s, seed_s = static[:3]

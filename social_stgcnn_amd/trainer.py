@@ -23,7 +23,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import ops
+from . import graphs, ops
 from .metrics import bivariate_loss, rel_to_abs
 
 
@@ -283,28 +283,21 @@ class Trainer:
         nbt = model._tensors()[2]
         self._lr_tensor(flat_p.device)       # allocate outside the capture
         saved = (flat_p.clone(), flat_b.clone(), [t.clone() for t in nbt])
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(max(1, warmup)):
-                if pre is not None:
-                    pre()
-                if single:
-                    self.step(x, adj, target, num_peds, weights)
-                else:
-                    self.forward_backward(x, adj, target, num_peds, weights)
-        torch.cuda.current_stream().wait_stream(side)
+
+        def run():                           # one rank: the whole step; several: what comes ahead of the all-reduce
+            if pre is not None:
+                pre()
+            if single:
+                return self.step(x, adj, target, num_peds, weights)
+            return self.forward_backward(x, adj, target, num_peds, weights)
+        graphs.warm_up(run, warmup)
         with torch.no_grad():
             flat_p.copy_(saved[0])
             flat_b.copy_(saved[1])
             for t, t0 in zip(nbt, saved[2]):
                 t.copy_(t0)
         if single:
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                if pre is not None:
-                    pre()
-                out = self.step(x, adj, target, num_peds, weights)
+            graph, out = graphs.capture(run)
             self._graph = graph
 
             def replay():
@@ -316,16 +309,20 @@ class Trainer:
         rank = dist.get_rank(self.group)
         mom = model.st_gcns[0].tcn[0].momentum
         pack, before = self._dp_buffers(flat_p, flat_b)
-        g_a, g_b = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g_a):
+
+        def part_a():
             if pre is not None:
                 pre()
             before.copy_(flat_b)
             out = self.forward_backward(x, adj, target, num_peds, weights)
             ops.dp_pack(self._flat_grad(), before, flat_b, num_peds, int(x.shape[0]), mom, rank, self.world, pack)
-        with torch.cuda.graph(g_b, pool=g_a.pool()):
+            return out
+
+        def part_b():
             ops.dp_fold(pack, before, mom, rank, self.world, n_p, flat_b, nbt)
             self._update(flat_p, pack[:n_p])
+        g_a, out = graphs.capture(part_a)
+        g_b, _ = graphs.capture(part_b, pool=g_a.pool())
         self._graph = (g_a, g_b)
 
         def replay():

@@ -65,7 +65,7 @@ def main():
     ap.add_argument("--cases", default="bench,eth,kernel")
     args = ap.parse_args()
     cases = args.cases.split(",")
-    from social_stgcnn_amd import data, ops
+    from social_stgcnn_amd import data, graphs, ops
     from social_stgcnn_amd import _lib
     dev = torch.device("cuda", 0)
     ops.OPTIONS["wave_path"] = True          # the wave-per-scene kernels for every batch size here
@@ -94,14 +94,7 @@ def main():
 
         def run():
             ops.sample_trajectories(y, obs_last, None, k, None, 0, seed_dev, samples, mean)
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            run()
-        torch.cuda.current_stream().wait_stream(s)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            run()
+        g, _ = graphs.warm_capture(run, 1)
         ms = time_replays(g.replay, args.iters)
         written = (samples.numel() + mean.numel()) * 4
         print(json.dumps(dict({"case": "sample_kernel", "k": k, "n": n, "v": v, "p": p, "ms_per_replay": round(ms, 5),
