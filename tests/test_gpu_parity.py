@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from conftest import load_golden
+from layout_cases import ZERO_GRAD_BIASES, grad_errors
 
 pytestmark = pytest.mark.gpu
 
@@ -44,34 +45,8 @@ def _maxdiff(a, b):
     return float(np.max(np.abs(np.asarray(a, dtype=np.float64) - np.asarray(b, dtype=np.float64))))
 
 
-# Conv biases that feed a train-mode BatchNorm (gcn.conv.bias, tcn.2.bias, residual.0.bias) have an
-# exactly-zero true gradient: the normalisation removes any per-channel shift.  Both the reference and the
-# kernels hold fp32 rounding noise of the same sum there (order eps * |weight gradient|), so they are
-# compared on the scale of the sibling weight gradient instead of their own ~1e-8 magnitude.
-_ZERO_GRAD_BIASES = ("gcn.conv.bias", "tcn.2.bias", "residual.0.bias")
-
-
-def _grad_errors(named_got, ref_of):
-    """named_got: iterable of (name, grad tensor or None); ref_of(name) -> numpy array or None (dead).
-    Returns {name: relative error} for live parameters; asserts dead ones are None on both sides."""
-    named_got = list(named_got)
-    refs = {name: ref_of(name) for name, _ in named_got}
-    out = {}
-    for name, got in named_got:
-        ref = refs[name]
-        if ref is None:
-            assert got is None, name
-            continue
-        assert got is not None, name
-        scale = max(1e-3, float(np.abs(ref).max()))
-        if name.endswith(_ZERO_GRAD_BIASES):
-            sib = refs.get(name[:-4] + "weight")
-            if sib is not None:
-                scale = max(scale, float(np.abs(sib).max()))
-        err = _maxdiff(got.cpu().numpy(), ref) / scale
-        # pure-noise entries get a 10x looser bar (they scale with depth / batch, not with the kernels)
-        out[name] = err / 10.0 if name.endswith(_ZERO_GRAD_BIASES) else err
-    return out
+# The gradient comparison (scaling, the zero-gradient-bias rule) is stated once, in tests/layout_cases.py
+_grad_errors, _ZERO_GRAD_BIASES = grad_errors, ZERO_GRAD_BIASES
 
 
 # ------------------------------------------------------------------------------------------
