@@ -193,6 +193,11 @@ class social_stgcnn(nn.Module):
         return self._pp.ensure(params)
 
     def forward(self, v, a, num_peds=None):
+        return self._forward(v, a, num_peds)
+
+    def _forward(self, v, a, num_peds=None, defer_bn_fold=False):
+        """forward(); defer_bn_fold (the trainer's request): a training forward leaves the running-statistics fold to
+        the step's tail launch, the statistics travel in `self._fwd_state`."""
         assert a.size(-3) == self.st_gcns[0].gcn.kernel_size
         if self.n_txpcnn < 1:
             raise NotImplementedError("social_stgcnn needs n_txpcnn >= 1 (model.py:168 always builds tpcnns[0])")
@@ -205,5 +210,5 @@ class social_stgcnn(nn.Module):
         desc = ops.make_desc(self.n_stgcnn, self.n_txpcnn, self.input_feat, self.output_feat, self.seq_len,
                              self.pred_seq_len, self.kt, self.st_gcns[0].residual_kind, False, self.training,
                              bn.eps, bn.momentum, options=getattr(self, "options", None))
-        y = ops.fused_model(v, a, num_peds, desc, flat_p, flat_b, nbt, dead, params, self)
+        y = ops.fused_model(v, a, num_peds, desc, flat_p, flat_b, nbt, dead, params, self, defer_bn_fold)
         return y, a

@@ -4,6 +4,8 @@ Every function here launches hand-written HIP kernels on the current torch strea
 raises if the library or a GPU tensor is missing -- there is no eager fallback.
 """
 import ctypes
+import dataclasses
+import math
 
 import torch
 
@@ -140,6 +142,15 @@ def conv_t(x, weight, bias, pad=0, num_peds=None):
 # --------------------------------------------------------------------------------------------
 # R4/R5 fused st_gcn / social_stgcnn
 # --------------------------------------------------------------------------------------------
+def flat_walk(items):
+    """(index, offset, count) of every entry of `items` (tensors or shapes) laid end to end in one flat buffer."""
+    off = 0
+    for i, it in enumerate(items):
+        cnt = it.numel() if torch.is_tensor(it) else math.prod(it)
+        yield i, off, cnt
+        off += cnt
+
+
 class FlatPack:
     """Keeps a list of tensors as views of ONE flat fp32 device buffer (the layout the fused
     kernels read).  `ensure()` is cheap when nothing moved; it re-packs after .to(), a
@@ -152,26 +163,18 @@ class FlatPack:
         total = sum(t.numel() for t in tensors)
         dev = tensors[0].device
         flat = self.flat
-        ok = flat is not None and flat.device == dev and flat.numel() == total
-        if ok:
-            base = flat.data_ptr()
-            off = 0
-            for t in tensors:
-                if t.data_ptr() != base + 4 * off or not t.is_contiguous():
-                    ok = False
-                    break
-                off += t.numel()
-        if not ok:
-            flat = torch.empty(total, device=dev, dtype=torch.float32)
-            off = 0
-            with torch.no_grad():
-                for t in tensors:
-                    n = t.numel()
-                    flat[off:off + n].copy_(t.detach().reshape(-1))
-                    t.data = flat[off:off + n].view(t.shape)
-                    off += n
-            self.flat = flat
-        return self.flat
+        if (flat is not None and flat.device == dev and flat.numel() == total
+                and all(tensors[i].data_ptr() == flat.data_ptr() + 4 * off and tensors[i].is_contiguous()
+                        for i, off, _ in flat_walk(tensors))):
+            return flat
+        flat = torch.empty(total, device=dev, dtype=torch.float32)
+        with torch.no_grad():
+            for i, off, n in flat_walk(tensors):
+                t = tensors[i]
+                flat[off:off + n].copy_(t.detach().reshape(-1))
+                t.data = flat[off:off + n].view(t.shape)
+        self.flat = flat
+        return flat
 
 
 # Launch options of the fused model entry points (stg_model_desc.flags / .wg_waves).  Host-side switches: the
@@ -255,11 +258,44 @@ def _timer_of(holder):
     return getattr(holder, "timer", None) if holder is not None else None
 
 
+def _size(n, what):
+    """the value of a size query of the C ABI; a negative one is a status"""
+    if n < 0:
+        check(int(n), what)
+    return int(n)
+
+
+def _ptr_array(tensors):
+    """one device pointer per tensor, as the `void* const*` arguments of the C ABI take them (None for no tensors)"""
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors]) if len(tensors) else None
+
+
+@dataclasses.dataclass(eq=False)
+class FwdRecord:
+    """What ONE fused forward leaves behind for the backward and the step tail that follow it: `ctx` of the autograd
+    node holds it, and so does `holder._fwd_state`, from a forward that saved activations until a backward ran."""
+    desc: ModelDesc                 # the descriptor actually used (the workgroup flag may have been added)
+    a_sn: int
+    dead: frozenset                 # indices of the parameters forward() never touches (grad stays None)
+    shapes: list                    # parameter shapes in kernel order
+    flat_params: torch.Tensor
+    flat_buffers: torch.Tensor
+    x: torch.Tensor
+    adj_c: torch.Tensor
+    peds: torch.Tensor
+    ws: torch.Tensor                # saved activations; None = nothing to run a backward from
+    # the BatchNorm fold this forward left to the step's tail (train_tail / stg_model_bwd_step); None = folded or eval
+    stats: torch.Tensor = None
+    nbt: list = None
+    n: int = 0
+
+
 class _FusedModel(torch.autograd.Function):
     """x (N,Cin,T,V), adj -> y.  Extra (non-differentiable) arguments carry the packed buffers."""
 
     @staticmethod
-    def forward(ctx, x, adj, num_peds, desc, flat_params, flat_buffers, nbt, dead, holder, grad_on, *params):
+    def forward(ctx, x, adj, num_peds, desc, flat_params, flat_buffers, nbt, dead, holder, grad_on, defer_bn_fold,
+                *params):
         require_gpu(x, adj, flat_params, flat_buffers)
         _lib.as_f32(x, "x")
         _lib.as_f32(adj, "adj")
@@ -281,29 +317,21 @@ class _FusedModel(torch.autograd.Function):
             desc = ModelDesc(**fields)
         out_t = desc.t_pred if desc.n_txpcnn > 0 else desc.t_obs
         y = torch.empty((n, desc.c_out, out_t, v), device=x.device, dtype=torch.float32)
-        ws_floats = 0                  # (diagnostics: activation workspace this forward allocated; 0 = inference)
-        ws = None
+        ws = None                      # (its size is a diagnostic: last_ws_floats, 0 = inference)
         if need_grad:
-            wsf = L.stg_model_ws_floats(ctypes.byref(desc), v)
-            if wsf < 0:
-                check(int(wsf), "stg_model_ws_floats")
-            tail = L.stg_model_ws_tail_floats(ctypes.byref(desc), n, v)
-            if tail < 0:
-                check(int(tail), "stg_model_ws_tail_floats")
+            wsf = _size(L.stg_model_ws_floats(ctypes.byref(desc), v), "stg_model_ws_floats")
+            tail = _size(L.stg_model_ws_tail_floats(ctypes.byref(desc), n, v), "stg_model_ws_tail_floats")
             ws = torch.empty(n * wsf + tail, device=x.device, dtype=torch.float32)
-            ws_floats = ws.numel()
         stats = None
         if training:
             sf = L.stg_model_stat_floats(ctypes.byref(desc))
             stats = torch.empty((n, max(int(sf), 1)), device=x.device, dtype=torch.float32)
         scr = None
-        nscr = L.stg_model_fwd_scratch_floats(ctypes.byref(desc), n, v)
-        if nscr < 0:
-            check(int(nscr), "stg_model_fwd_scratch_floats")
+        nscr = _size(L.stg_model_fwd_scratch_floats(ctypes.byref(desc), n, v), "stg_model_fwd_scratch_floats")
         if nscr > 0:
-            scr = torch.empty(int(nscr), device=x.device, dtype=torch.float32)
+            scr = torch.empty(nscr, device=x.device, dtype=torch.float32)
         if holder is not None:
-            holder.last_ws_floats = ws_floats
+            holder.last_ws_floats = ws.numel() if need_grad else 0
             holder._last_fwd_scratch = scr  # diagnostics only (STG_STAMPS=1 reads the stamp tail)
         sn, sc, st, sv = x.stride()
         timer = _timer_of(holder)
@@ -312,63 +340,80 @@ class _FusedModel(torch.autograd.Function):
                               ptr(adj_c), a_sn, ptr(peds), n, v, ptr(y), ptr(ws), ptr(stats), ptr(scr),
                               ev.arr if ev else None, ev.n if ev else 0, stream_ptr()),
               "stg_model_fwd")
-        if training and holder is not None and getattr(holder, "_defer_bn_fold", False):
-            # the trainer folds the running statistics in the step's tail launch (ops.train_tail)
-            holder._pending_bn = (desc, stats, peds, n, flat_buffers, nbt)
+        rec = FwdRecord(desc, a_sn, dead, [tuple(p.shape) for p in params], flat_params, flat_buffers, x, adj_c, peds,
+                        ws)
+        if training and defer_bn_fold:
+            # the trainer folds the running statistics in the step's tail launch (train_tail / stg_model_bwd_step)
+            rec.stats, rec.nbt, rec.n = stats, nbt, n
         elif training:
-            arr = (ctypes.c_void_p * len(nbt))(*[b.data_ptr() for b in nbt])
             # nbt[k] counts forwards of BatchNorm k; buffers are interleaved (mean, var) per BatchNorm, the
             # kernel bumps counter i for statistic row i < len(nbt): pass one pointer per BatchNorm.
-            check(L.stg_bn_fold(ctypes.byref(desc), ptr(stats), ptr(peds), n, ptr(flat_buffers), arr, len(nbt),
-                                stream_ptr()), "stg_bn_fold")
+            check(L.stg_bn_fold(ctypes.byref(desc), ptr(stats), ptr(peds), n, ptr(flat_buffers), _ptr_array(nbt),
+                                len(nbt), stream_ptr()), "stg_bn_fold")
         if holder is not None:
-            # what a backward needs, for the trainer's fused loss + backward (backward_from_target)
-            holder._fwd_state = (desc, a_sn, dead, [tuple(p.shape) for p in params], flat_params, flat_buffers,
-                                 (x, adj_c, peds, ws)) if need_grad else None
-        ctx.desc = desc
-        ctx.a_sn = a_sn
-        ctx.dead = dead
+            holder._fwd_state = rec if need_grad else None
+        ctx.rec = rec
         ctx.holder = holder
-        ctx.shapes = [tuple(p.shape) for p in params]
-        ctx.flat_params = flat_params
-        ctx.flat_buffers = flat_buffers
-        ctx.tensors = (x, adj_c, peds, ws)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        L = lib()
-        desc = ctx.desc
-        x, adj_c, peds, ws = ctx.tensors
-        if ws is None:
+        if ctx.rec.ws is None:
             raise RuntimeError("backward through a forward that saved no activations")
-        dy = dy.contiguous()
-        n, cin, t, v = x.shape
-        np_ = int(L.stg_model_param_count(ctypes.byref(desc)))
-        n_scratch = L.stg_model_bwd_scratch_floats(ctypes.byref(desc), n, v)
-        if n_scratch < 0:
-            check(int(n_scratch), "stg_model_bwd_scratch_floats")
-        slabs = torch.empty(int(n_scratch), device=x.device, dtype=torch.float32)
-        grad = torch.empty(np_, device=x.device, dtype=torch.float32)
-        dx = torch.empty((n, cin, t, v), device=x.device, dtype=torch.float32) if ctx.needs_input_grad[0] else None
-        sn, sc, st, sv = x.stride()
-        timer = _timer_of(ctx.holder)
-        ev = timer.events("model_bwd") if timer is not None else None
-        check(L.stg_model_bwd(ctypes.byref(desc), ptr(ctx.flat_params), ptr(ctx.flat_buffers), ptr(x), sn, sc, st,
-                              sv, ptr(adj_c), ctx.a_sn, ptr(peds), n, v, ptr(dy), ptr(ws), ptr(slabs), ptr(grad),
-                              ptr(dx), ev.arr if ev else None, ev.n if ev else 0, stream_ptr()), "stg_model_bwd")
-        grads = []
-        off = 0
-        for i, shp in enumerate(ctx.shapes):
-            cnt = 1
-            for s in shp:
-                cnt *= s
-            grads.append(None if i in ctx.dead else grad[off:off + cnt].view(shp))
-            off += cnt
-        if ctx.holder is not None:
-            ctx.holder._flat_grad = grad       # the trainer all-reduces / applies this buffer directly
-            ctx.holder._fwd_state = None
-        return (dx, None, None, None, None, None, None, None, None, None, *grads)
+        grads, dx = _launch_backward(ctx.rec, ctx.holder, dy=dy.contiguous(), need_dx=ctx.needs_input_grad[0])
+        return (dx, None, None, None, None, None, None, None, None, None, None, *grads)
+
+
+def _launch_backward(rec, holder, dy=None, need_dx=False, y=None, target=None, weights=None, step=None):
+    """The ONE launcher of the fused backward of the forward `rec` records.  It starts from `dy` (stg_model_bwd; also
+    the input gradient when `need_dx`), or from the model output `y`, `target` and the per-scene `weights`
+    (stg_model_bwd_nll), with step = (lr, lr_dev) also running the tail of a single-rank step (stg_model_bwd_step).
+    Returns (per-parameter gradient views, None for the dead ones; dx | losses | (losses, total)), with the flat
+    gradient left in `holder._flat_grad` -- or None, nothing launched, where the library has no form that starts from
+    the target."""
+    L = lib()
+    desc, x = rec.desc, rec.x
+    n, cin, t, v = x.shape
+    np_ = int(L.stg_model_param_count(ctypes.byref(desc)))
+    n_scratch = _size(L.stg_model_bwd_scratch_floats(ctypes.byref(desc), n, v), "stg_model_bwd_scratch_floats")
+    slabs = torch.empty(n_scratch, device=x.device, dtype=torch.float32)
+    grad = torch.empty(np_, device=x.device, dtype=torch.float32)
+    sn, sc, st, sv = x.stride()
+    timer = _timer_of(holder)
+    ev = timer.events("model_bwd") if timer is not None else None
+    head = (ctypes.byref(desc), ptr(rec.flat_params), ptr(rec.flat_buffers), ptr(x), sn, sc, st, sv, ptr(rec.adj_c),
+            rec.a_sn, ptr(rec.peds), n, v)
+    end = (ev.arr if ev else None, ev.n if ev else 0, stream_ptr())
+    if dy is not None:
+        out = torch.empty((n, cin, t, v), device=x.device, dtype=torch.float32) if need_dx else None
+        name, rc = "stg_model_bwd", L.stg_model_bwd(*head, ptr(dy), ptr(rec.ws), ptr(slabs), ptr(grad), ptr(out), *end)
+    else:
+        out = losses = torch.empty(n, device=x.device, dtype=torch.float32)
+        mid = (ptr(y), ptr(target), ptr(weights), ptr(losses), ptr(rec.ws), ptr(slabs), ptr(grad))
+        if step is None:
+            name, rc = "stg_model_bwd_nll", L.stg_model_bwd_nll(*head, *mid, *end)
+        else:
+            lr, lr_dev = step
+            total = torch.empty(1, device=x.device, dtype=torch.float32)
+            tail = _lib.StepTail()
+            tail.params, tail.lr_dev, tail.lr = ptr(rec.flat_params), ptr(lr_dev), float(lr)
+            tail.total = ptr(total)
+            if rec.stats is not None:
+                arr = _ptr_array(rec.nbt)
+                tail.stats, tail.buffers, tail.nbt, tail.n_bn = ptr(rec.stats), ptr(rec.flat_buffers), arr, len(rec.nbt)
+            name, rc = "stg_model_bwd_step", L.stg_model_bwd_step(*head, *mid, ctypes.addressof(tail), *end)
+            out = (losses, total[0])
+        if rc == _lib.EUNSUPPORTED:
+            if ev is not None:
+                timer.calls["model_bwd"].pop()
+            return None
+    check(rc, name)
+    grads = [None if i in rec.dead else grad[off:off + cnt].view(rec.shapes[i])
+             for i, off, cnt in flat_walk(rec.shapes)]
+    if holder is not None:
+        holder._flat_grad = grad           # the trainer all-reduces / applies this buffer directly
+        holder._fwd_state = None
+    return grads, out
 
 
 def backward_from_target(holder, y, target, weights=None, step=None):
@@ -378,68 +423,33 @@ def backward_from_target(holder, y, target, weights=None, step=None):
     Returns None -- nothing launched -- where the library has no fused form (STG_OPT_SPLIT_BF16, a model without a
     TXP-CNN): the caller then takes the separate loss kernel + autograd backward.
 
-    step = (pending_bn, lr, lr_dev): the rest of a single-rank training step rides in the same launches
-    (stg_model_bwd_step: SGD without clipping on the flat parameters, the BatchNorm fold of `pending_bn` -- what a
-    forward with a deferred fold left behind -- and the reported loss); returns (losses, total) then."""
-    st = getattr(holder, "_fwd_state", None)
-    if st is None:
+    step = (lr, lr_dev): the rest of a single-rank training step rides in the same launches (stg_model_bwd_step: SGD
+    without clipping on the flat parameters, the BatchNorm fold a forward with a deferred fold left in its record, and
+    the reported loss); returns (losses, total) then."""
+    rec = getattr(holder, "_fwd_state", None)
+    if rec is None:
         raise RuntimeError("backward_from_target: no fused forward with saved activations to start from")
-    desc, a_sn, dead, shapes, flat_params, flat_buffers, (x, adj_c, peds, ws) = st
-    L = lib()
-    n, cin, t, v = x.shape
-    if tuple(y.shape) != (n, 5, desc.t_pred, v) or not y.is_contiguous():
+    n, _, _, v = rec.x.shape
+    if tuple(y.shape) != (n, 5, rec.desc.t_pred, v) or not y.is_contiguous():
         return None
     target = target.to(torch.float32).contiguous()
-    if tuple(target.shape) != (n, desc.t_pred, v, 2):
+    if tuple(target.shape) != (n, rec.desc.t_pred, v, 2):
         raise ValueError("backward_from_target: target (N,P,V,2) expected, got %s" % (tuple(target.shape),))
     w = weights.to(torch.float32).contiguous() if weights is not None else None
-    np_ = int(L.stg_model_param_count(ctypes.byref(desc)))
-    n_scratch = L.stg_model_bwd_scratch_floats(ctypes.byref(desc), n, v)
-    if n_scratch < 0:
-        check(int(n_scratch), "stg_model_bwd_scratch_floats")
-    slabs = torch.empty(int(n_scratch), device=x.device, dtype=torch.float32)
-    grad = torch.empty(np_, device=x.device, dtype=torch.float32)
-    losses = torch.empty(n, device=x.device, dtype=torch.float32)
-    sn, sc, st_, sv = x.stride()
-    timer = _timer_of(holder)
-    ev = timer.events("model_bwd") if timer is not None else None
-    total = None
-    if step is None:
-        rc = L.stg_model_bwd_nll(ctypes.byref(desc), ptr(flat_params), ptr(flat_buffers), ptr(x), sn, sc, st_, sv,
-                                 ptr(adj_c), a_sn, ptr(peds), n, v, ptr(y), ptr(target), ptr(w), ptr(losses), ptr(ws),
-                                 ptr(slabs), ptr(grad), ev.arr if ev else None, ev.n if ev else 0, stream_ptr())
-    else:
-        pending_bn, lr, lr_dev = step
-        total = torch.empty(1, device=x.device, dtype=torch.float32)
-        tail = _lib.StepTail()
-        tail.params, tail.lr_dev, tail.lr = ptr(flat_params), ptr(lr_dev), float(lr)
-        tail.total = ptr(total)
-        if pending_bn is not None:
-            _, stats, _, _, bn_buffers, nbt = pending_bn
-            arr = (ctypes.c_void_p * len(nbt))(*[b.data_ptr() for b in nbt])
-            tail.stats, tail.buffers, tail.nbt, tail.n_bn = ptr(stats), ptr(bn_buffers), arr, len(nbt)
-        rc = L.stg_model_bwd_step(ctypes.byref(desc), ptr(flat_params), ptr(flat_buffers), ptr(x), sn, sc, st_, sv,
-                                  ptr(adj_c), a_sn, ptr(peds), n, v, ptr(y), ptr(target), ptr(w), ptr(losses), ptr(ws),
-                                  ptr(slabs), ptr(grad), ctypes.addressof(tail), ev.arr if ev else None,
-                                  ev.n if ev else 0, stream_ptr())
-    if rc == _lib.EUNSUPPORTED:
-        if ev is not None:
-            timer.calls["model_bwd"].pop()
+    res = _launch_backward(rec, holder, y=y, target=target, weights=w, step=step)
+    if res is None:
         return None
-    check(rc, "stg_model_bwd_nll" if step is None else "stg_model_bwd_step")
-    off = 0
-    for i, (p, shp) in enumerate(zip(holder._tensors()[0], shapes)):
-        cnt = p.numel()
-        p.grad = None if i in dead else grad[off:off + cnt].view(shp)
-        off += cnt
-    holder._flat_grad = grad
-    holder._fwd_state = None
-    return losses if step is None else (losses, total[0])
+    for p, g in zip(holder._tensors()[0], res[0]):
+        p.grad = g
+    return res[1]
 
 
-def fused_model(x, adj, num_peds, desc, flat_params, flat_buffers, nbt, dead, params, holder=None):
+def fused_model(x, adj, num_peds, desc, flat_params, flat_buffers, nbt, dead, params, holder=None,
+                defer_bn_fold=False):
+    """defer_bn_fold: leave the running-statistics fold of a training forward to the step's tail launch (the trainer's
+    request); the statistics then travel in the forward's record (`holder._fwd_state`)."""
     return _FusedModel.apply(x, adj, num_peds, desc, flat_params, flat_buffers, nbt, dead, holder,
-                             torch.is_grad_enabled(), *params)
+                             torch.is_grad_enabled(), defer_bn_fold, *params)
 
 
 # --------------------------------------------------------------------------------------------
@@ -517,19 +527,16 @@ def optim_step(flat_params, flat_grads, lr, max_norm=None, lr_dev=None, grad_nor
           "stg_optim_step")
 
 
-def train_tail(pending_bn, losses, weights, flat_params, flat_grads, lr, max_norm=None, lr_dev=None):
-    """The tail of a single-rank step in one launch (stg_train_tail): BatchNorm fold of `pending_bn` (what a fused
-    forward with a deferred fold left behind), the reported loss sum_n w_n loss_n, clip + SGD.  Returns the loss as a
-    0-d device tensor."""
+def train_tail(rec, losses, weights, flat_params, flat_grads, lr, max_norm=None, lr_dev=None):
+    """The tail of a single-rank step in one launch (stg_train_tail): the BatchNorm fold that the forward of record
+    `rec` deferred, the reported loss sum_n w_n loss_n, clip + SGD.  Returns the loss as a 0-d device tensor."""
     require_gpu(losses, flat_params, flat_grads)
-    desc, stats, peds, n, flat_buffers, nbt = pending_bn
-    arr = (ctypes.c_void_p * len(nbt))(*[b.data_ptr() for b in nbt])
     w = weights.to(torch.float32).contiguous() if weights is not None else None
     out = torch.empty(1, device=losses.device, dtype=torch.float32)
-    check(lib().stg_train_tail(ctypes.byref(desc), ptr(stats), ptr(peds), n, ptr(flat_buffers), arr, len(nbt),
-                               ptr(losses), ptr(w), ptr(out), ptr(flat_params), ptr(flat_grads), flat_params.numel(),
-                               ptr(lr_dev), float(lr), float(max_norm) if max_norm is not None else 0.0, None,
-                               stream_ptr()), "stg_train_tail")
+    check(lib().stg_train_tail(ctypes.byref(rec.desc), ptr(rec.stats), ptr(rec.peds), rec.n, ptr(rec.flat_buffers),
+                               _ptr_array(rec.nbt), len(rec.nbt), ptr(losses), ptr(w), ptr(out), ptr(flat_params),
+                               ptr(flat_grads), flat_params.numel(), ptr(lr_dev), float(lr),
+                               float(max_norm) if max_norm is not None else 0.0, None, stream_ptr()), "stg_train_tail")
     return out[0]
 
 
@@ -547,9 +554,8 @@ def dp_fold(pack, bn_before, momentum, rank, world, n_params, buffers, nbt=()):
     """the exact sequential fold of the running statistics over the ranks from the all-reduced pack (stg_dp_fold);
     `nbt` (the num_batches_tracked tensors) also receive the other ranks' scene counts from the pack."""
     require_gpu(pack, bn_before, buffers)
-    arr = (ctypes.c_void_p * len(nbt))(*[b.data_ptr() for b in nbt]) if len(nbt) else None
     check(lib().stg_dp_fold(ptr(pack), ptr(bn_before), float(momentum), int(rank), int(world), int(n_params),
-                            bn_before.numel(), ptr(buffers), arr, len(nbt), stream_ptr()), "stg_dp_fold")
+                            bn_before.numel(), ptr(buffers), _ptr_array(nbt), len(nbt), stream_ptr()), "stg_dp_fold")
 
 
 def weighted_sum(values, weights=None):

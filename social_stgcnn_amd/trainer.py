@@ -152,9 +152,6 @@ class Trainer:
         self._lr_dev = None                  # device copy of lr read by the update kernel (graph-safe)
         self.world = dist.get_world_size(group) if (dist.is_available() and dist.is_initialized()) else 1
 
-    def _bn_buffers(self):
-        return self.model._tensors()[1]
-
     def _lr_tensor(self, device):
         if self._lr_dev is None or self._lr_dev.device != device:
             self._lr_dev = torch.full((1,), self.lr, device=device, dtype=torch.float32)
@@ -174,93 +171,95 @@ class Trainer:
         """clip_grad_norm_ + SGD update over the flat buffers: one launch (train.py:71-74)."""
         ops.optim_step(flat_p, flat_g, self.lr, self.clip_grad, self._lr_tensor(flat_p.device))
 
-    def forward_backward(self, x, adj, target, num_peds=None, weights=None, defer_tail=False):
-        """One fused forward + loss + backward.  x (N,2,T,V) (any strides), adj (N,T,V,V) or (T,V,V),
-        target (N,P,V,2).  Returns (weighted loss, per-scene losses, V_pred (N,5,P,V)).  defer_tail: leave the loss
-        total to the caller's tail launch (returned as None)."""
+    def _forward(self, x, adj, num_peds, defer_bn_fold=False):
+        """clear the gradients and run the model; returns (V_pred with its autograd node, the forward's record -- what
+        `ops.train_tail` folds from when the fold was deferred)"""
         model = self.model
         for p in model.parameters():
             p.grad = None
-        y, _ = model(x, adj, num_peds)
-        # loss and backward in the backward's own launches (the input stage of the wave-per-scene kernel computes
-        # dV_pred from V_pred and the target: stg_model_bwd_nll); on the workgroup path: loss + its gradient w.r.t.
-        # V_pred in ONE kernel (per-scene weights folded in), then backward straight from dV_pred -- either way no
-        # autograd graph through the loss, no separate scale / sum / expand kernels
-        losses = ops.backward_from_target(model, y.detach(), target, weights) if y.requires_grad else None
-        if losses is None:
-            losses, dy = ops.bivariate_nll_with_grad(y.detach(), target, num_peds, weights)
-            y.backward(dy)
-        if defer_tail:
-            return None, losses, y.detach()
-        total = ops.weighted_sum(losses, weights)
+        y, _ = model._forward(x, adj, num_peds, defer_bn_fold)
+        return y, model._fwd_state
+
+    def _backward(self, y, target, num_peds, weights, step=None):
+        """Loss and backward in the backward's own launches (the input stage of the wave-per-scene kernel computes
+        dV_pred from V_pred and the target: stg_model_bwd_nll; with step = (lr, lr_dev) the step's tail rides along:
+        stg_model_bwd_step).  Where the library has no such form (the workgroup path): loss + its gradient w.r.t.
+        V_pred in ONE kernel (per-scene weights folded in), then backward straight from dV_pred -- either way no
+        autograd graph through the loss, no separate scale / sum / expand kernels.
+        Returns (per-scene losses, the step's reported loss or None when no tail has run yet)."""
+        res = ops.backward_from_target(self.model, y.detach(), target, weights, step) if y.requires_grad else None
+        if res is not None:
+            return res if step is not None else (res, None)
+        losses, dy = ops.bivariate_nll_with_grad(y.detach(), target, num_peds, weights)
+        y.backward(dy)
+        return losses, None
+
+    def forward_backward(self, x, adj, target, num_peds=None, weights=None):
+        """One fused forward + loss + backward.  x (N,2,T,V) (any strides), adj (N,T,V,V) or (T,V,V),
+        target (N,P,V,2).  Returns (weighted loss, per-scene losses, V_pred (N,5,P,V))."""
+        y, _ = self._forward(x, adj, num_peds)
+        losses, _ = self._backward(y, target, num_peds, weights)
+        return ops.weighted_sum(losses, weights), losses, y.detach()
+
+    def step(self, x, adj, target, num_peds=None, weights=None):
+        """Forward + loss + backward + [ONE all-reduce: gradient and BatchNorm fold across ranks] + SGD update.  No host
+        synchronisation anywhere: the scene counts the fold needs travel inside the collective.
+        Returns (weighted loss, per-scene losses, V_pred (N,5,P,V))."""
+        if self.world > 1:
+            out = self._before_allreduce(x, adj, target, num_peds, weights)
+            self._allreduce()
+            self._after_allreduce()
+            return out
+        model = self.model
+        training = model.training
+        y, rec = self._forward(x, adj, num_peds, defer_bn_fold=training)
+        flat_p = model.flat_parameters()
+        lr_dev = self._lr_tensor(flat_p.device)
+        # no clipping: the whole tail (SGD, running-statistics fold, reported loss) rides in the backward's last launch
+        # (stg_model_bwd_step) -- when the batch runs the wave-per-scene kernels
+        ride = training and self.clip_grad is None
+        losses, total = self._backward(y, target, num_peds, weights, (self.lr, lr_dev) if ride else None)
+        if total is None and training:
+            # ONE tail launch: running-statistics fold, reported loss, clip + SGD
+            total = ops.train_tail(rec, losses, weights, flat_p, self._flat_grad(), self.lr, self.clip_grad, lr_dev)
+        elif total is None:                                     # (eval-mode model: nothing to fold)
+            # (the eval-mode step has always launched this sum twice, the first result unused: DESIGN 5.14 keeps the
+            # launch list as it was and names this one as redundant)
+            ops.weighted_sum(losses, weights)
+            total = ops.weighted_sum(losses, weights)
+            self._update(flat_p, self._flat_grad())
         return total, losses, y.detach()
 
-    def _dp_buffers(self, flat_p, flat_b):
-        """the step's ONE collective buffer [gradient | world x (BatchNorm contribution, scene count)] + a snapshot
-        slot for the running statistics (allocated once: the captured step replays on them)."""
+    # ---- several ranks: what runs ahead of the step's ONE collective, the collective, what runs behind it ----------
+    def _dp_state(self):
+        """(flat parameters, flat running statistics, the collective buffer [gradient | world x (BatchNorm
+        contribution, scene count)], a snapshot slot for the running statistics, BatchNorm momentum, rank).  The two
+        buffers are allocated once: the captured step replays on them."""
+        model = self.model
+        flat_p = model.flat_parameters()
+        flat_b = model._pb.ensure(model._tensors()[1])
         n = flat_p.numel() + self.world * (flat_b.numel() + 1)
         if getattr(self, "_pack", None) is None or self._pack.numel() != n or self._pack.device != flat_p.device:
             self._pack = torch.zeros(n, device=flat_p.device, dtype=torch.float32)
             self._bn_before = torch.empty_like(flat_b)
-        return self._pack, self._bn_before
+        return (flat_p, flat_b, self._pack, self._bn_before, model.st_gcns[0].tcn[0].momentum,
+                dist.get_rank(self.group))
 
-    def step(self, x, adj, target, num_peds=None, weights=None):
-        """forward_backward + [ONE all-reduce: gradient and BatchNorm fold across ranks] + SGD update.  No host
-        synchronisation anywhere: the scene counts the fold needs travel inside the collective."""
-        model = self.model
-        if self.world == 1 and self.clip_grad is None and model.training:
-            # no clipping: the whole tail (SGD, running-statistics fold, reported loss) rides in the backward's last
-            # launch (stg_model_bwd_step) -- when the batch runs the wave-per-scene kernels
-            for p in model.parameters():
-                p.grad = None
-            model._defer_bn_fold, model._pending_bn = True, None
-            try:
-                y, _ = model(x, adj, num_peds)
-            finally:
-                model._defer_bn_fold = False
-            flat_p = model.flat_parameters()
-            res = None
-            if y.requires_grad and model._pending_bn is not None:
-                res = ops.backward_from_target(model, y.detach(), target, weights,
-                                               step=(model._pending_bn, self.lr, self._lr_tensor(flat_p.device)))
-            if res is not None:
-                model._pending_bn = None
-                return res[1], res[0], y.detach()
-            # workgroup path: loss kernel + autograd backward + the tail launch
-            losses, dy = ops.bivariate_nll_with_grad(y.detach(), target, num_peds, weights)
-            y.backward(dy)
-            total = ops.train_tail(model._pending_bn, losses, weights, flat_p, self._flat_grad(), self.lr, None,
-                                   self._lr_tensor(flat_p.device))
-            model._pending_bn = None
-            return total, losses, y.detach()
-        if self.world == 1:
-            # forward + loss + backward, then ONE tail launch: running-statistics fold, reported loss, clip + SGD
-            model._defer_bn_fold, model._pending_bn = model.training, None
-            try:
-                _, losses, y = self.forward_backward(x, adj, target, num_peds, weights, defer_tail=model.training)
-            finally:
-                model._defer_bn_fold = False
-            flat_p = model.flat_parameters()
-            if model._pending_bn is None:                       # (eval-mode model: nothing to fold)
-                total = ops.weighted_sum(losses, weights)
-                self._update(flat_p, self._flat_grad())
-                return total, losses, y
-            total = ops.train_tail(model._pending_bn, losses, weights, flat_p, self._flat_grad(), self.lr,
-                                   self.clip_grad, self._lr_tensor(flat_p.device))
-            model._pending_bn = None
-            return total, losses, y
-        flat_p = model.flat_parameters()
-        flat_b = model._pb.ensure(self._bn_buffers())
-        pack, before = self._dp_buffers(flat_p, flat_b)
+    def _before_allreduce(self, x, adj, target, num_peds, weights):
+        _, flat_b, pack, before, mom, rank = self._dp_state()
         before.copy_(flat_b)
-        total, losses, y = self.forward_backward(x, adj, target, num_peds, weights)
-        mom = model.st_gcns[0].tcn[0].momentum
-        rank = dist.get_rank(self.group)
+        out = self.forward_backward(x, adj, target, num_peds, weights)
         ops.dp_pack(self._flat_grad(), before, flat_b, num_peds, int(x.shape[0]), mom, rank, self.world, pack)
-        dist.all_reduce(pack, op=dist.ReduceOp.SUM, group=self.group)          # the step's ONE collective
-        ops.dp_fold(pack, before, mom, rank, self.world, flat_p.numel(), flat_b, model._tensors()[2])
-        self._update(flat_p, pack[:flat_p.numel()])
-        return total, losses, y
+        return out
+
+    def _allreduce(self):
+        dist.all_reduce(self._pack, op=dist.ReduceOp.SUM, group=self.group)
+
+    def _after_allreduce(self):
+        flat_p, flat_b, pack, before, mom, rank = self._dp_state()
+        n_p = flat_p.numel()
+        ops.dp_fold(pack, before, mom, rank, self.world, n_p, flat_b, self.model._tensors()[2])
+        self._update(flat_p, pack[:n_p])
 
     # ---- hipGraph capture of the step (launch-bound at these sizes: ~15 kernels of 10-150 us) ----------
     def capture(self, x, adj, target, num_peds=None, weights=None, warmup=3, pre=None):
@@ -279,25 +278,26 @@ class Trainer:
         model = self.model
         # warm-up launches (outside the capture) must not change the model: snapshot / restore its state
         flat_p = model.flat_parameters()
-        flat_b = model._pb.ensure(self._bn_buffers())
+        flat_b = model._pb.ensure(model._tensors()[1])
         nbt = model._tensors()[2]
         self._lr_tensor(flat_p.device)       # allocate outside the capture
         saved = (flat_p.clone(), flat_b.clone(), [t.clone() for t in nbt])
 
-        def run():                           # one rank: the whole step; several: what comes ahead of the all-reduce
-            if pre is not None:
-                pre()
-            if single:
-                return self.step(x, adj, target, num_peds, weights)
-            return self.forward_backward(x, adj, target, num_peds, weights)
-        graphs.warm_up(run, warmup)
+        def ahead(fn):                       # `fn` behind the caller's `pre`
+            def run():
+                if pre is not None:
+                    pre()
+                return fn(x, adj, target, num_peds, weights)
+            return run
+        # one rank: the whole step; several: the forward and backward, as they come ahead of the all-reduce
+        graphs.warm_up(ahead(self.step if single else self.forward_backward), warmup)
         with torch.no_grad():
             flat_p.copy_(saved[0])
             flat_b.copy_(saved[1])
             for t, t0 in zip(nbt, saved[2]):
                 t.copy_(t0)
         if single:
-            graph, out = graphs.capture(run)
+            graph, out = graphs.capture(ahead(self.step))
             self._graph = graph
 
             def replay():
@@ -305,29 +305,14 @@ class Trainer:
                 return out
             return replay
 
-        n_p = flat_p.numel()
-        rank = dist.get_rank(self.group)
-        mom = model.st_gcns[0].tcn[0].momentum
-        pack, before = self._dp_buffers(flat_p, flat_b)
-
-        def part_a():
-            if pre is not None:
-                pre()
-            before.copy_(flat_b)
-            out = self.forward_backward(x, adj, target, num_peds, weights)
-            ops.dp_pack(self._flat_grad(), before, flat_b, num_peds, int(x.shape[0]), mom, rank, self.world, pack)
-            return out
-
-        def part_b():
-            ops.dp_fold(pack, before, mom, rank, self.world, n_p, flat_b, nbt)
-            self._update(flat_p, pack[:n_p])
-        g_a, out = graphs.capture(part_a)
-        g_b, _ = graphs.capture(part_b, pool=g_a.pool())
+        self._dp_state()                     # allocate outside the capture
+        g_a, out = graphs.capture(ahead(self._before_allreduce))
+        g_b, _ = graphs.capture(self._after_allreduce, pool=g_a.pool())
         self._graph = (g_a, g_b)
 
         def replay():
             g_a.replay()
-            dist.all_reduce(pack, op=dist.ReduceOp.SUM, group=self.group)      # the step's ONE collective
+            self._allreduce()                # the step's ONE collective
             g_b.replay()
             return out
         return replay
@@ -336,17 +321,10 @@ class Trainer:
         """Gradients as one flat buffer in parameter order (dead parameters contribute zeros)."""
         flat = getattr(self.model, "_flat_grad", None)
         params = list(self.model._tensors()[0])
-        if flat is not None:
-            off, ok = 0, True
-            for p in params:
-                if p.grad is not None and p.grad.data_ptr() != flat.data_ptr() + 4 * off:
-                    ok = False
-                    break
-                off += p.numel()
-            if ok:
-                return flat
-        flat = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in params])
-        return flat
+        if flat is not None and all(params[i].grad is None or params[i].grad.data_ptr() == flat.data_ptr() + 4 * off
+                                    for i, off, _ in ops.flat_walk(params)):
+            return flat
+        return torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in params])
 
     # ---- reference-style epoch (train.py:28-79) -------------------------------------------------
     def train_epoch(self, batcher, n_scenes, batch_size):
@@ -457,7 +435,6 @@ class Checkpoint:
     when the validation loss improves and rewrites the two metric files."""
 
     def __init__(self, directory, args=None):
-        import pickle
         self.dir = directory
         os.makedirs(directory, exist_ok=True)
         self.metrics = {"train_loss": [], "val_loss": []}
@@ -467,7 +444,6 @@ class Checkpoint:
                 pickle.dump(args, fp)
 
     def record(self, epoch, model, train_loss, val_loss):
-        import pickle
         self.metrics["train_loss"].append(train_loss)
         self.metrics["val_loss"].append(val_loss)
         improved = val_loss < self.constant_metrics["min_val_loss"]
