@@ -363,16 +363,9 @@ extern "C" int stg_adj_build(const float *rel, int64_t rel_sn, int64_t rel_sv, i
         const int rows = N > 2048 ? 128 : 256;              // (rows of the LDS tile: see the kernel)
         const size_t lds32 = ((size_t)3 * T * V + (size_t)rows * V) * sizeof(float);
         if (lds32 <= (size_t)stg::kLdsBytes) {
-            if (rows == 128) {
-                hipLaunchKernelGGL(stg::adj_build_rows32_kernel<128>, grid, block, lds32, stg::as_stream(stream), rel, rel_sn,
-                                   rel_sv, rel_sc, rel_st, num_peds, T, normalize, nodes, adj);
-            } else {
-                const stg::Launch lc{"stg_adj_build", grid, block, lds32, stg::as_stream(stream), 48 * 1024};
-                return stg::launch(lc, stg::adj_build_rows32_kernel<256>, rel, rel_sn, rel_sv, rel_sc, rel_st, num_peds, T,
-                                   normalize, nodes, adj);
-            }
-            STG_LAUNCH_CHECK("stg_adj_build");
-            return STG_OK;
+            const stg::Launch lc{"stg_adj_build", grid, block, lds32, stg::as_stream(stream), 48 * 1024};
+            return stg::launch(lc, rows == 128 ? stg::adj_build_rows32_kernel<128> : stg::adj_build_rows32_kernel<256>, rel,
+                               rel_sn, rel_sv, rel_sc, rel_st, num_peds, T, normalize, nodes, adj);
         }
     }
     // small batches: a workgroup per (scene, time step) -- T times the workgroups -- while the per-scene form would leave most of
@@ -380,21 +373,11 @@ extern "C" int stg_adj_build(const float *rel, int64_t rel_sn, int64_t rel_sv, i
     if (N < 1024 || stg::diag_env("STG_ADJ_TILE", 0)) {
         const dim3 tgrid((unsigned)(N * T));
         const size_t tlds = (size_t)4 * V * sizeof(float);
-        if (vec4)
-            hipLaunchKernelGGL(stg::adj_build_tile_kernel<true>, tgrid, block, tlds, stg::as_stream(stream), rel, rel_sn,
-                               rel_sv, rel_sc, rel_st, num_peds, V, T, normalize, nodes, adj);
-        else
-            hipLaunchKernelGGL(stg::adj_build_tile_kernel<false>, tgrid, block, tlds, stg::as_stream(stream), rel, rel_sn,
-                               rel_sv, rel_sc, rel_st, num_peds, V, T, normalize, nodes, adj);
-        STG_LAUNCH_CHECK("stg_adj_build");
-        return STG_OK;
+        const stg::Launch lc{"stg_adj_build", tgrid, block, tlds, stg::as_stream(stream), 64 * 1024};
+        return stg::launch(lc, vec4 ? stg::adj_build_tile_kernel<true> : stg::adj_build_tile_kernel<false>, rel, rel_sn, rel_sv,
+                           rel_sc, rel_st, num_peds, V, T, normalize, nodes, adj);
     }
-    if (vec4)
-        hipLaunchKernelGGL(stg::adj_build_kernel<true>, grid, block, lds, stg::as_stream(stream), rel, rel_sn,
-                           rel_sv, rel_sc, rel_st, num_peds, V, T, normalize, nodes, adj);
-    else
-        hipLaunchKernelGGL(stg::adj_build_kernel<false>, grid, block, lds, stg::as_stream(stream), rel, rel_sn,
-                           rel_sv, rel_sc, rel_st, num_peds, V, T, normalize, nodes, adj);
-    STG_LAUNCH_CHECK("stg_adj_build");
-    return STG_OK;
+    const stg::Launch lc{"stg_adj_build", grid, block, lds, stg::as_stream(stream), 64 * 1024};
+    return stg::launch(lc, vec4 ? stg::adj_build_kernel<true> : stg::adj_build_kernel<false>, rel, rel_sn, rel_sv, rel_sc, rel_st,
+                       num_peds, V, T, normalize, nodes, adj);
 }

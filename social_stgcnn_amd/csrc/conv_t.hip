@@ -137,10 +137,8 @@ int stg_conv_t_fwd(const float *x, int64_t x_sn, int64_t x_sc, int64_t x_st, int
     const size_t lds = ((size_t)Cout * Cin * kt + (size_t)Cin * T * V) * sizeof(float);
     STG_REQUIRE(lds <= stg::kLdsBytes, STG_ELDS, "stg_conv_t_fwd: scene does not fit LDS (%zu bytes)", lds);
     const int grid = N < 2048 ? N : 2048;
-    hipLaunchKernelGGL(stg::conv_t_fwd_kernel, dim3(grid), dim3(256), lds, stg::as_stream(stream), x, x_sn, x_sc,
-                       x_st, x_sv, w, b, num_peds, N, Cin, Cout, T, V, kt, pad, y);
-    STG_LAUNCH_CHECK("stg_conv_t_fwd");
-    return STG_OK;
+    const stg::Launch lc{"stg_conv_t_fwd", dim3(grid), dim3(256), lds, stg::as_stream(stream), 64 * 1024};
+    return stg::launch(lc, stg::conv_t_fwd_kernel, x, x_sn, x_sc, x_st, x_sv, w, b, num_peds, N, Cin, Cout, T, V, kt, pad, y);
 }
 
 int stg_conv_t_bwd(const float *x, int64_t x_sn, int64_t x_sc, int64_t x_st, int64_t x_sv, const float *w,
@@ -157,10 +155,9 @@ int stg_conv_t_bwd(const float *x, int64_t x_sn, int64_t x_sc, int64_t x_st, int
     const size_t lds = ((size_t)Cout * Cin * kt + (size_t)Cin * T * V + (size_t)Cout * To * V) * sizeof(float);
     STG_REQUIRE(lds <= stg::kLdsBytes, STG_ELDS, "stg_conv_t_bwd: scene does not fit LDS (%zu bytes)", lds);
     const int grid = N < 512 ? N : 512;
-    hipLaunchKernelGGL(stg::conv_t_bwd_kernel, dim3(grid), dim3(256), lds, stg::as_stream(stream), x, x_sn, x_sc,
-                       x_st, x_sv, w, dy, num_peds, N, Cin, Cout, T, V, kt, pad, dx, dw, db);
-    STG_LAUNCH_CHECK("stg_conv_t_bwd");
-    return STG_OK;
+    const stg::Launch lc{"stg_conv_t_bwd", dim3(grid), dim3(256), lds, stg::as_stream(stream), 64 * 1024};
+    return stg::launch(lc, stg::conv_t_bwd_kernel, x, x_sn, x_sc, x_st, x_sv, w, dy, num_peds, N, Cin, Cout, T, V, kt, pad, dx,
+                       dw, db);
 }
 
 }  // extern "C"

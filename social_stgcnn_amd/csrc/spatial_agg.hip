@@ -334,19 +334,15 @@ int stg_spatial_agg_fwd(const float *x, int64_t x_sn, int64_t x_sc, int64_t x_st
     STG_REQUIRE(lds <= stg::kLdsBytes, STG_ELDS, "stg_spatial_agg_fwd: C*T*V=%d floats exceed LDS", C * T * V);
     const bool vec4 = (V % 4 == 0) && ((reinterpret_cast<uintptr_t>(adj) & 15) == 0) &&
                       ((reinterpret_cast<uintptr_t>(y) & 15) == 0) && (a_sn % 4 == 0);
+    // (above 64 KiB, the runtime's own limit, `launch` raises the kernel's dynamic-LDS limit first)
+    const stg::Launch lc{"stg_spatial_agg_fwd", dim3((unsigned)N), dim3(256), lds, stg::as_stream(stream), 64 * 1024};
     if (vec4 && V == 32 && lds <= 64 * 1024) {
         // (same box, 537 MB working set: 4.07 -> 4.82 TB/s; at V = 64 the quarters form -- 16 loads in flight per lane -- loses to
         // the strip form, 3.85 against 4.15, at V = 16 they are equal: only instantiated for 32)
-        hipLaunchKernelGGL(stg::spatial_agg_fwd_quarters_kernel<8>, dim3(N), dim3(256), lds, stg::as_stream(stream), x, x_sn,
-                           x_sc, x_st, x_sv, adj, a_sn, num_peds, C, T, y);
-    } else if (vec4)
-        hipLaunchKernelGGL(stg::spatial_agg_fwd_kernel<4>, dim3(N), dim3(256), lds, stg::as_stream(stream), x,
-                           x_sn, x_sc, x_st, x_sv, adj, a_sn, num_peds, C, T, V, y);
-    else
-        hipLaunchKernelGGL(stg::spatial_agg_fwd_kernel<1>, dim3(N), dim3(256), lds, stg::as_stream(stream), x,
-                           x_sn, x_sc, x_st, x_sv, adj, a_sn, num_peds, C, T, V, y);
-    STG_LAUNCH_CHECK("stg_spatial_agg_fwd");
-    return STG_OK;
+        return stg::launch(lc, stg::spatial_agg_fwd_quarters_kernel<8>, x, x_sn, x_sc, x_st, x_sv, adj, a_sn, num_peds, C, T, y);
+    }
+    return stg::launch(lc, vec4 ? stg::spatial_agg_fwd_kernel<4> : stg::spatial_agg_fwd_kernel<1>, x, x_sn, x_sc, x_st, x_sv, adj,
+                       a_sn, num_peds, C, T, V, y);
 }
 
 int stg_spatial_agg_bwd(const float *dy, const float *adj, int64_t a_sn, const int32_t *num_peds, int N,
@@ -359,21 +355,15 @@ int stg_spatial_agg_bwd(const float *dy, const float *adj, int64_t a_sn, const i
     STG_REQUIRE(lds <= stg::kLdsBytes, STG_ELDS, "stg_spatial_agg_bwd: C*T*V=%d floats exceed LDS", C * T * V);
     const bool vec4 = (V % 4 == 0) && ((reinterpret_cast<uintptr_t>(adj) & 15) == 0) && (a_sn % 4 == 0);
     const bool aligned = vec4 && ((reinterpret_cast<uintptr_t>(dy) & 15) == 0);
+    const stg::Launch lc{"stg_spatial_agg_bwd", dim3((unsigned)N), dim3(256), lds, stg::as_stream(stream), 64 * 1024};
     if (aligned && (V == 8 || V == 16 || V == 32 || V == 64) && lds <= 64 * 1024) {
         // the coalesced form: rows shared by V / 4 lanes (measured at V = 32 on a 537 MB working set: see DESIGN 5)
-        switch (V) {
-            case 8: hipLaunchKernelGGL(stg::spatial_agg_bwd_rows_kernel<2>, dim3((unsigned)N), dim3(256), lds, stg::as_stream(stream), dy, adj, a_sn, num_peds, C, T, dx); break;
-            case 16: hipLaunchKernelGGL(stg::spatial_agg_bwd_rows_kernel<4>, dim3((unsigned)N), dim3(256), lds, stg::as_stream(stream), dy, adj, a_sn, num_peds, C, T, dx); break;
-            case 32: hipLaunchKernelGGL(stg::spatial_agg_bwd_rows_kernel<8>, dim3((unsigned)N), dim3(256), lds, stg::as_stream(stream), dy, adj, a_sn, num_peds, C, T, dx); break;
-            default: hipLaunchKernelGGL(stg::spatial_agg_bwd_rows_kernel<16>, dim3((unsigned)N), dim3(256), lds, stg::as_stream(stream), dy, adj, a_sn, num_peds, C, T, dx); break;
-        }
-    } else {
-        const stg::Launch lc{"stg_spatial_agg_bwd", dim3((unsigned)N), dim3(256), lds, stg::as_stream(stream), 64 * 1024};
-        return stg::launch(lc, vec4 ? stg::spatial_agg_bwd_kernel<4> : stg::spatial_agg_bwd_kernel<1>, dy, adj, a_sn, num_peds, C, T,
-                           V, dx);
+        auto *rows = V == 8 ? stg::spatial_agg_bwd_rows_kernel<2> : V == 16 ? stg::spatial_agg_bwd_rows_kernel<4>
+                   : V == 32 ? stg::spatial_agg_bwd_rows_kernel<8> : stg::spatial_agg_bwd_rows_kernel<16>;
+        return stg::launch(lc, rows, dy, adj, a_sn, num_peds, C, T, dx);
     }
-    STG_LAUNCH_CHECK("stg_spatial_agg_bwd");
-    return STG_OK;
+    return stg::launch(lc, vec4 ? stg::spatial_agg_bwd_kernel<4> : stg::spatial_agg_bwd_kernel<1>, dy, adj, a_sn, num_peds, C, T, V,
+                       dx);
 }
 
 }  // extern "C"
