@@ -465,7 +465,8 @@ __device__ __forceinline__ void stgcn_block_fwd(const Args &a, const float *__re
 // [ck.w0(), ck.w0() + ck.wc()) of a scene shared by ck.nch() waves (HALF only; the scene-wide BatchNorm sums are
 // exchanged through LDS, `plane_base` is the team's shared image and is zeroed by all of them, `qtab` is the wave's own
 // table of its chunk's positions).
-template <bool HALF, typename Args, typename CK>
+// QTAB = false: the caller needs no table (a crowd it knows at compile time), `qtab` is left untouched.
+template <bool HALF, bool QTAB = true, typename Args, typename CK>
 __device__ __forceinline__ void stgcn_block_fwd_cols(const Args &a, const float *P_, const float *B_, const BlockLayout &b,
                                                      int n, int vi, float *wsn, float *statn, const float *pre_ax,
                                                      const float *pre_cs, float *plane, int plane_sc, float *plane_base,
@@ -505,10 +506,12 @@ __device__ __forceinline__ void stgcn_block_fwd_cols(const Args &a, const float 
         {
             float4 *z4 = reinterpret_cast<float4 *>(plane_base);
             for (int e = lane + 64 * ck.ci(); e < plane_zero_f4; e += 64 * ck.nch()) z4[e] = make_float4(0.f, 0.f, 0.f, 0.f);
-            const int wcw = ck.wc();
-            for (int p = lane; p < T * wcw; p += 64) {
-                const int h = p / wcw;
-                qtab[p] = (ptab_t)((h << 8) | (ck.w0() + p - h * wcw));
+            if constexpr (QTAB) {
+                const int wcw = ck.wc();
+                for (int p = lane; p < T * wcw; p += 64) {
+                    const int h = p / wcw;
+                    qtab[p] = (ptab_t)((h << 8) | (ck.w0() + p - h * wcw));
+                }
             }
         }
         // ---- gcn 1x1 conv on the aggregated input (model.py:66-67) --------------------------------------

@@ -31,6 +31,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
+#include <utility>
 
 namespace stg {
 namespace cv {
@@ -339,6 +341,74 @@ __device__ __forceinline__ void load_b_half(unsigned lds_base, const Tile &t, BH
             : "memory");
     }
 }
+
+// ---- table-free tiles: a scene whose crowd VI is a compile-time constant (a multiple of 16) and that one wave owns ------------
+// Position 16 t + n of tile t is row t / (VI / 16), column 16 (t % (VI / 16)) + n: every read base of tile t is tile 0's
+// plus ONE constant, and r1[1] / r1[2] are r1[0] plus one / two rows.  So a scene needs four address registers -- tile 0's
+// r1[0], r1[3], r2[0], r2[3] with the image's LDS address added -- and every tile's reads are those registers with the
+// tile's byte offset in the instruction's offset field (largest: tile 9 of VI = 32, 3552 + 2 * 792 + 72 = 5208 of 65535).
+// Nothing per tile is ever a register, so nothing can be hoisted out of the layer loop and spilled.
+// (IN0 == 1 images only: the ring wrap of tile_from<3>'s kernel row 2 is not a constant distance.)
+__host__ __device__ constexpr int tile_row(int vi, int t) { return t / (vi / 16); }
+__host__ __device__ constexpr int tile_col0(int vi, int t) { return 16 * (t % (vi / 16)); }
+__host__ __device__ constexpr int tile_byte_delta(int vi, int t) { return (tile_row(vi, t) * (vi + 1) + tile_col0(vi, t)) * kPosBytes; }
+struct LaneBases {
+    unsigned a0, a3, c0, c3;     // lds_base + r1[0], r1[3], r2[0], r2[3] of tile 0
+};
+__device__ __forceinline__ LaneBases lane_bases(unsigned lds_base, const LaneGeom &lg, int vi) {
+    const Tile t0 = tile_from<1>(0, threadIdx.x & 15, 16, lg, vi);     // (tile 0: row 0, column = lane & 15)
+    LaneBases lb = {lds_base + t0.r1[0], lds_base + t0.r1[3], lds_base + t0.r2[0], lds_base + t0.r2[3]};
+    // four plain values from here on: never re-derived from the lane id in front of a tile
+    asm volatile("" : "+v"(lb.a0), "+v"(lb.a3), "+v"(lb.c0), "+v"(lb.c3));
+    return lb;
+}
+// load_b_half of tile T: the same sixteen reads in the same order, (base, immediate) =
+//     H == 0: (a0, D) (a0, D + 32) (a3, D) (a0, D + RB + 16)   H == 1: (a0, D + RB + 48) (a0, D + 2 RB + {0, 32, 64})
+// with D = tile_byte_delta(VI, T), RB = row_bytes(VI); read set 2 from c0 / c3
+template <int H, int VI, int T>
+__device__ __forceinline__ void load_b_half_imm(const LaneBases &lb, BHalf &b) {
+    static_assert(VI % 16 == 0 && T >= 0, "whole tiles per row");
+    constexpr int D = tile_byte_delta(VI, T), RB = (VI + 1) * kPosBytes;
+    static_assert(D + 2 * RB + 72 < 65536, "the DS offset field is 16 bits");
+    if (H == 0) {
+        asm volatile(
+            "ds_read_b64 %0, %16 offset:%20\n\tds_read_b64 %1, %16 offset:%21\n\tds_read_b64 %2, %18 offset:%20\n\tds_read_b64 %3, %18 offset:%21\n\t"
+            "ds_read_b64 %4, %16 offset:%22\n\tds_read_b64 %5, %16 offset:%23\n\tds_read_b64 %6, %18 offset:%22\n\tds_read_b64 %7, %18 offset:%23\n\t"
+            "ds_read_b64 %8, %17 offset:%20\n\tds_read_b64 %9, %17 offset:%21\n\tds_read_b64 %10, %19 offset:%20\n\tds_read_b64 %11, %19 offset:%21\n\t"
+            "ds_read_b64 %12, %16 offset:%24\n\tds_read_b64 %13, %16 offset:%25\n\tds_read_b64 %14, %18 offset:%24\n\tds_read_b64 %15, %18 offset:%25\n\t"
+            "s_waitcnt lgkmcnt(0)"
+            : "=&v"(b.s1[0][0]), "=&v"(b.s1[0][1]), "=&v"(b.s2[0][0]), "=&v"(b.s2[0][1]), "=&v"(b.s1[1][0]), "=&v"(b.s1[1][1]),
+              "=&v"(b.s2[1][0]), "=&v"(b.s2[1][1]), "=&v"(b.s1[2][0]), "=&v"(b.s1[2][1]), "=&v"(b.s2[2][0]), "=&v"(b.s2[2][1]),
+              "=&v"(b.s1[3][0]), "=&v"(b.s1[3][1]), "=&v"(b.s2[3][0]), "=&v"(b.s2[3][1])
+            : "v"(lb.a0), "v"(lb.a3), "v"(lb.c0), "v"(lb.c3), "n"(D), "n"(D + 8), "n"(D + 32), "n"(D + 40), "n"(D + RB + 16),
+              "n"(D + RB + 24)
+            : "memory");
+    } else {
+        asm volatile(
+            "ds_read_b64 %0, %16 offset:%18\n\tds_read_b64 %1, %16 offset:%19\n\tds_read_b64 %2, %17 offset:%18\n\tds_read_b64 %3, %17 offset:%19\n\t"
+            "ds_read_b64 %4, %16 offset:%20\n\tds_read_b64 %5, %16 offset:%21\n\tds_read_b64 %6, %17 offset:%20\n\tds_read_b64 %7, %17 offset:%21\n\t"
+            "ds_read_b64 %8, %16 offset:%22\n\tds_read_b64 %9, %16 offset:%23\n\tds_read_b64 %10, %17 offset:%22\n\tds_read_b64 %11, %17 offset:%23\n\t"
+            "ds_read_b64 %12, %16 offset:%24\n\tds_read_b64 %13, %16 offset:%25\n\tds_read_b64 %14, %17 offset:%24\n\tds_read_b64 %15, %17 offset:%25\n\t"
+            "s_waitcnt lgkmcnt(0)"
+            : "=&v"(b.s1[0][0]), "=&v"(b.s1[0][1]), "=&v"(b.s2[0][0]), "=&v"(b.s2[0][1]), "=&v"(b.s1[1][0]), "=&v"(b.s1[1][1]),
+              "=&v"(b.s2[1][0]), "=&v"(b.s2[1][1]), "=&v"(b.s1[2][0]), "=&v"(b.s1[2][1]), "=&v"(b.s2[2][0]), "=&v"(b.s2[2][1]),
+              "=&v"(b.s1[3][0]), "=&v"(b.s1[3][1]), "=&v"(b.s2[3][0]), "=&v"(b.s2[3][1])
+            : "v"(lb.a0), "v"(lb.c0), "n"(D + RB + 48), "n"(D + RB + 56), "n"(D + 2 * RB), "n"(D + 2 * RB + 8), "n"(D + 2 * RB + 32),
+              "n"(D + 2 * RB + 40), "n"(D + 2 * RB + 64), "n"(D + 2 * RB + 72)
+            : "memory");
+    }
+}
+// f(std::integral_constant<int, t>) for t = 0 .. N-1: a tile loop whose index can be an asm immediate (the variable of a
+// `#pragma unroll` loop cannot)
+template <typename F, int... I>
+__device__ __forceinline__ void for_tiles_seq(F &&f, std::integer_sequence<int, I...>) {
+    (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, typename F>
+__device__ __forceinline__ void for_tiles(F &&f) {
+    for_tiles_seq(f, std::make_integer_sequence<int, N>{});
+}
+
 template <int H>
 __device__ __forceinline__ void mma_half(const u32x4 (&w)[kWpVecs], const BHalf &b, f32x4 &acc) {
 #pragma unroll

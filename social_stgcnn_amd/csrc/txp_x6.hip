@@ -52,6 +52,12 @@ __device__ __forceinline__ void fold_shape(Args &a) {
         a.ws_stride = kCanonWs32;
     }
 }
+// Canon32 needs no position table: the wave owns a scene of kCanonV columns, so position 16 t + nq of (unrolled) tile t is
+// row cv::tile_row -- a constant of the tile -- and column cv::tile_col0 + nq -- a lane constant plus 0 or 16.  The
+// (row << 8 | column) code the table would return:
+__device__ __forceinline__ unsigned canon32_code(int t, int nq) {
+    return (unsigned)(cv::tile_row(kCanonV, t) << 8 | (cv::tile_col0(kCanonV, t) + nq));
+}
 // Layout arrays indexed by the (runtime) layer: from the constant layout of a folded shape, so that the entry's copy of
 // the arguments is never addressed with a runtime index (that would keep it in scratch memory)
 template <Shape S>
@@ -102,12 +108,14 @@ __device__ __forceinline__ void txp_fwd_scene_x6(const TxpFwdArgs &a, const floa
     const int SWs = save_sw(vi, bf16), VWs = save_vw(vi, bf16);   // row strides (positions) of the saved arrays
 
     // ---- st_gcn block (model.py:145-155), column mode: lane = pedestrian; zeroes the image, builds the position table
+    // (no table for Canon32)
     {
         // lane = (pedestrian, time half); a lane receives plane channels 4*half .. 4*half+3 of its pedestrian's C rows
         float sv[C * T / 2];
         const float *agn = a.agg + n * a.agg_stride;
-        stgcn_block_fwd_cols<true>(a, blk_params, blk_buffers, L.blk[0], n, vi, wsn, statn, agn + a.agg_ax, agn + a.agg_cs,
-                                   nullptr, 0, region, cv::image_bytes(vi, kF6Slots) >> 4, ptab, sv, ck);
+        stgcn_block_fwd_cols<true, SH != Shape::Canon32>(a, blk_params, blk_buffers, L.blk[0], n, vi, wsn, statn,
+                                                         agn + a.agg_ax, agn + a.agg_cs, nullptr, 0, region,
+                                                         cv::image_bytes(vi, kF6Slots) >> 4, ptab, sv, ck);
         // (a team: the block's own ck.sync() has made the whole image zero before anyone writes its interior)
         // v.view(N, T, C, V) (model.py:187): flat f = c*T+t of the block output is plane channel f / C, row f % C.  Per
         // row a pedestrian's eight channels are two record quads (one per lane of the pair); the third quad (channels
@@ -137,6 +145,11 @@ __device__ __forceinline__ void txp_fwd_scene_x6(const TxpFwdArgs &a, const floa
     // ---- TXP-CNN (model.py:187-195) -------------------------------------------------------------------
     if (STG_SKIP(a, 16)) return;                       // (diagnostic build: time the block alone)
     const unsigned lds_base = (unsigned)(uintptr_t)img;
+    [[maybe_unused]] cv::LaneBases lb;                 // Canon32: the scene's four read bases, every tile an immediate
+    if constexpr (SH == Shape::Canon32) {
+        static_assert(!CK::kTeam && 16 * kF6Tiles == C * kCanonV, "Canon32: one wave, ten full tiles");
+        lb = cv::lane_bases(lds_base, lg, vi);
+    }
     f32x4 av[kF6Tiles];
 #pragma unroll
     for (int t = 0; t < kF6Tiles; ++t) av[t] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -158,33 +171,50 @@ __device__ __forceinline__ void txp_fwd_scene_x6(const TxpFwdArgs &a, const floa
         // (same-box A/B, three rounds: teams gain -- F 147.9 -> 144.8 us at V = 64, 532 -> 517 at V = 128 x 4096; the solo kernel
         // at V = 32 and the backward's tile loops: no difference)
         __builtin_amdgcn_s_setprio(1);
-        unsigned code = cv::tile_code(0, ptab, npos);
+        // tile t's conv output z at the lane's position (row h, column wc): the layer's epilogue
+        auto finish = [&](int t, int h, int wc, bool ok, const f32x4 &z) __attribute__((always_inline)) {
+            if (ok && kq < 3) {
+                if (is_out) {
+                    // v.view(N, C, P, V) (model.py:195): the (P, C, V) conv output IS the (C, P, V) tensor
 #pragma unroll
-        for (int t = 0; t < kF6Tiles; ++t) {
-            if (t < ntiles) {
-                const cv::Tile tl = cv::tile_from<1>(t, code, npos, lg, vi);
-                if (t + 1 < kF6Tiles) code = cv::tile_code(t + 1, ptab, npos);      // (in flight behind this tile's reads)
+                    for (int r = 0; r < 4; ++r) yn[(int64_t)((4 * kq + r) * C + h) * V + wc] = z[r];
+                } else {
+                    f32x4 v4;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v4[r] = (z[r] > 0.f ? z[r] : alpha * z[r]) + av[t][r];   // (av = 0 at l = 0)
+                    av[t] = v4;
+                    if (zs) {
+                        store_vec4(zs, (h * VWs + wc) * 3 + kq, z, bf16);
+                        store_vec4(ps, (h * SWs + wc + 1) * 3 + kq, v4, bf16);
+                    }
+                }
+            }
+        };
+        if constexpr (SH == Shape::Canon32) {
+            cv::for_tiles<kF6Tiles>([&](auto tc) __attribute__((always_inline)) {
+                constexpr int t = decltype(tc)::value;
                 cv::BHalf b;
                 f32x4 z = binit;
-                cv::load_b_half<0>(lds_base, tl, b);
+                cv::load_b_half_imm<0, kCanonV, t>(lb, b);
                 cv::mma_half<0>(w, b, z);
-                cv::load_b_half<1>(lds_base, tl, b);
+                cv::load_b_half_imm<1, kCanonV, t>(lb, b);
                 cv::mma_half<1>(w, b, z);
-                if (tl.ok && kq < 3) {
-                    if (is_out) {
-                        // v.view(N, C, P, V) (model.py:195): the (P, C, V) conv output IS the (C, P, V) tensor
+                finish(t, cv::tile_row(kCanonV, t), cv::tile_col0(kCanonV, t) + nq, true, z);
+            });
+        } else {
+            unsigned code = cv::tile_code(0, ptab, npos);
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) yn[(int64_t)((4 * kq + r) * C + tl.h) * V + tl.w] = z[r];
-                    } else {
-                        f32x4 v4;
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) v4[r] = (z[r] > 0.f ? z[r] : alpha * z[r]) + av[t][r];   // (av = 0 at l = 0)
-                        av[t] = v4;
-                        if (zs) {
-                            store_vec4(zs, (tl.h * VWs + tl.w) * 3 + kq, z, bf16);
-                            store_vec4(ps, (tl.h * SWs + tl.w + 1) * 3 + kq, v4, bf16);
-                        }
-                    }
+            for (int t = 0; t < kF6Tiles; ++t) {
+                if (t < ntiles) {
+                    const cv::Tile tl = cv::tile_from<1>(t, code, npos, lg, vi);
+                    if (t + 1 < kF6Tiles) code = cv::tile_code(t + 1, ptab, npos);      // (in flight behind this tile's reads)
+                    cv::BHalf b;
+                    f32x4 z = binit;
+                    cv::load_b_half<0>(lds_base, tl, b);
+                    cv::mma_half<0>(w, b, z);
+                    cv::load_b_half<1>(lds_base, tl, b);
+                    cv::mma_half<1>(w, b, z);
+                    finish(t, tl.h, tl.w, tl.ok, z);
                 }
             }
         }
@@ -194,7 +224,7 @@ __device__ __forceinline__ void txp_fwd_scene_x6(const TxpFwdArgs &a, const floa
         ck.sync();
         unsigned codes[kF6Tiles];                      // (all ten table reads in flight: the weight registers are dead here)
 #pragma unroll
-        for (int t = 0; t < kF6Tiles; ++t) codes[t] = cv::tile_code(t, ptab, npos);
+        for (int t = 0; t < kF6Tiles; ++t) codes[t] = SH == Shape::Canon32 ? canon32_code(t, nq) : cv::tile_code(t, ptab, npos);
 #pragma unroll
         for (int t = 0; t < kF6Tiles; ++t) {
             const int p = 16 * t + nq;
@@ -289,19 +319,33 @@ __device__ __forceinline__ void txp_bwd_scene_x6(const TxpBwdArgs &a, const floa
     const int VWs = save_vw(vi, bf16);                             // row stride (positions) of the saved z_l / dz_l
     // From ONE read of the position table: the vector index of the lane's quad of tile t in those arrays (fp32: rows of vi
     // positions, i.e. (16 t + n) * 3 + kq) and the byte offset of its record quad in the image (interior row 0 = slot 1;
-    // -1 past the scene's last position)
+    // -1 past the scene's last position).  Canon32: no table -- both are ONE lane value plus a constant of the tile, which
+    // the loads and stores below take in their offset fields, and whether a lane has a quad is the same for every tile.
     auto tile_slots = [&](int t, int &rec, int &quad) {
-        const int p = 16 * t + nq;
-        const unsigned hw = ptab[p < npos ? p : 0];
-        const int h = (int)(hw >> 8), w = (int)(hw & 0xffu);
-        quad = (h * VWs + w) * 3 + kq;
-        rec = (p < npos && kq < 3) ? cv::pos_off(vi, 1 + h, w) + 8 * kq : -1;
+        if constexpr (SH == Shape::Canon32) {
+            const int h = cv::tile_row(kCanonV, t), w = cv::tile_col0(kCanonV, t) + nq;
+            quad = (h * VWs + w) * 3 + kq;
+            rec = cv::pos_off(vi, 1 + h, w) + 8 * kq;
+        } else {
+            const int p = 16 * t + nq;
+            const unsigned hw = ptab[p < npos ? p : 0];
+            const int h = (int)(hw >> 8), w = (int)(hw & 0xffu);
+            quad = (h * VWs + w) * 3 + kq;
+            rec = (p < npos && kq < 3) ? cv::pos_off(vi, 1 + h, w) + 8 * kq : -1;
+        }
     };
+    auto has_quad = [&](int rec) { return SH == Shape::Canon32 ? kq < 3 : rec >= 0; };
     {
         uint4 *z4 = reinterpret_cast<uint4 *>(img);
         for (int e = lane + 64 * ck.ci(); e < cv::image_bytes(vi, kX6Slots) >> 4; e += 64 * ck.nch()) z4[e] = make_uint4(0u, 0u, 0u, 0u);
     }
-    build_ptab(ptab, ck.w0(), ck.wc());
+    [[maybe_unused]] cv::LaneBases lb;                 // Canon32: the scene's four read bases, every tile an immediate
+    if constexpr (SH == Shape::Canon32) {
+        static_assert(!CK::kTeam && 16 * kX6Tiles == C * kCanonV, "Canon32: one wave, ten full tiles");
+        lb = cv::lane_bases((unsigned)(uintptr_t)img, lg, vi);
+    } else {
+        build_ptab(ptab, ck.w0(), ck.wc());
+    }
     ck.sync();
     f32x4 dcur[kX6Tiles];
 #pragma unroll
@@ -384,7 +428,7 @@ __device__ __forceinline__ void txp_bwd_scene_x6(const TxpBwdArgs &a, const floa
 #pragma unroll
             for (int t = 0; t < kX6Tiles; ++t) {
                 const int p = 16 * t + nq;
-                const unsigned hw = ptab[p < npos ? p : 0];
+                const unsigned hw = SH == Shape::Canon32 ? canon32_code(t, nq) : ptab[p < npos ? p : 0];
                 const float *sq = S + ((4 * (kq < 3 ? kq : 0)) * C + (int)(hw >> 8)) * vi + (int)(hw & 0xffu);
                 qd[t] = f32x4{sq[0], sq[C * vi], sq[2 * C * vi], sq[3 * C * vi]};
             }
@@ -399,7 +443,7 @@ __device__ __forceinline__ void txp_bwd_scene_x6(const TxpBwdArgs &a, const floa
             for (int t = 0; t < kX6Tiles; ++t) tile_slots(t, rec[t], qv[t]);
 #pragma unroll
             for (int t = 0; t < kX6Tiles; ++t) {
-                if (rec[t] >= 0) {
+                if (has_quad(rec[t])) {
                     cv::put4(img, (unsigned)rec[t], lg.PL, qd[t]);
                     store_vec4(dzo, qv[t], qd[t], bf16);
                 }
@@ -420,7 +464,7 @@ __device__ __forceinline__ void txp_bwd_scene_x6(const TxpBwdArgs &a, const floa
             for (int t = 0; t < kX6Tiles; ++t) tile_slots(t, rec[t], qv[t]);
 #pragma unroll
             for (int t = 0; t < kX6Tiles; ++t)
-                zv[t] = rec[t] >= 0 ? load_vec4_raw(zl, qv[t], bf16) : f32x4{1.f, 1.f, 1.f, 1.f};
+                zv[t] = has_quad(rec[t]) ? load_vec4_raw(zl, qv[t], bf16) : f32x4{1.f, 1.f, 1.f, 1.f};
             // all ten have landed before the first guarded tile: the tiles' dz stores are not waited for (vm_drain)
             asm volatile("" ::"v"(zv[0]), "v"(zv[1]), "v"(zv[2]), "v"(zv[3]), "v"(zv[4]), "v"(zv[5]), "v"(zv[6]), "v"(zv[7]),
                          "v"(zv[8]), "v"(zv[9]), "v"(alpha)
@@ -428,7 +472,7 @@ __device__ __forceinline__ void txp_bwd_scene_x6(const TxpBwdArgs &a, const floa
             vm_drain();
 #pragma unroll
             for (int t = 0; t < kX6Tiles; ++t) {
-                if (rec[t] >= 0) {
+                if (has_quad(rec[t])) {
                     f32x4 dzv;
                     const f32x4 zq = finish_vec4(zv[t], bf16);
 #pragma unroll
@@ -459,21 +503,34 @@ __device__ __forceinline__ void txp_bwd_scene_x6(const TxpBwdArgs &a, const floa
             const unsigned lds_base = (unsigned)(uintptr_t)img;
             const bool keep = l != L.L && l != 0;       // d(a_l) += d(a_{l+1}) (a_{l+1} = prelu(z_l) + a_l for 1 <= l < L)
             const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-            unsigned code = cv::tile_code(0, ptab, npos);
-#pragma unroll
-            for (int t = 0; t < kX6Tiles; ++t) {
-                if (t < ntiles) {
-                    const cv::Tile tl = cv::tile_from<1>(t, code, npos, lg, vi);
-                    if (t + 1 < kX6Tiles) code = cv::tile_code(t + 1, ptab, npos);  // (in flight behind this tile's reads)
-                    // two half-tiles through ONE 32-register operand set (96 weight + 40 gradient registers are live);
-                    // each half's reads and their wait are one asm statement, the SIMD's other wave covers the latency
+            // two half-tiles through ONE 32-register operand set (96 weight + 40 gradient registers are live);
+            // each half's reads and their wait are one asm statement, the SIMD's other wave covers the latency
+            if constexpr (SH == Shape::Canon32) {
+                cv::for_tiles<kX6Tiles>([&](auto tc) __attribute__((always_inline)) {
+                    constexpr int t = decltype(tc)::value;
                     cv::BHalf b;
                     f32x4 acc = keep ? dcur[t] : zero;
-                    cv::load_b_half<0>(lds_base, tl, b);
+                    cv::load_b_half_imm<0, kCanonV, t>(lb, b);
                     cv::mma_half<0>(w, b, acc);
-                    cv::load_b_half<1>(lds_base, tl, b);
+                    cv::load_b_half_imm<1, kCanonV, t>(lb, b);
                     cv::mma_half<1>(w, b, acc);
                     dcur[t] = acc;
+                });
+            } else {
+                unsigned code = cv::tile_code(0, ptab, npos);
+#pragma unroll
+                for (int t = 0; t < kX6Tiles; ++t) {
+                    if (t < ntiles) {
+                        const cv::Tile tl = cv::tile_from<1>(t, code, npos, lg, vi);
+                        if (t + 1 < kX6Tiles) code = cv::tile_code(t + 1, ptab, npos);  // (in flight behind this tile's reads)
+                        cv::BHalf b;
+                        f32x4 acc = keep ? dcur[t] : zero;
+                        cv::load_b_half<0>(lds_base, tl, b);
+                        cv::mma_half<0>(w, b, acc);
+                        cv::load_b_half<1>(lds_base, tl, b);
+                        cv::mma_half<1>(w, b, acc);
+                        dcur[t] = acc;
+                    }
                 }
             }
         }
@@ -486,7 +543,7 @@ __device__ __forceinline__ void txp_bwd_scene_x6(const TxpBwdArgs &a, const floa
     for (int t = 0; t < kX6Tiles; ++t) {
         const int p = 16 * t + nq;
         if (p < npos && kq < T / 4) {
-            const unsigned hw = ptab[p];
+            const unsigned hw = SH == Shape::Canon32 ? canon32_code(t, nq) : ptab[p];
             const int h = (int)(hw >> 8), ww = (int)(hw & 0xffu);
 #pragma unroll
             for (int r = 0; r < 4; ++r) D[((4 * kq + r) * C + h) * vi + ww] = dcur[t][r];
