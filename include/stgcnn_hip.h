@@ -379,6 +379,38 @@ int stg_track_push_streams(const int64_t *det_id, int64_t id_stride, const doubl
                            double scale, int V, double *obs_abs, int64_t *out_ids, int32_t *num_peds,
                            int32_t *out_flags, int block_threads, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * N7  what a caller acts on, reduced from the K samples of N5 without writing them out: conflict and zone-occupancy
+ *     counts.  pred, strides, obs_last, num_peds (clamped to [0, V]), noise, seed and seed_dev exactly as in
+ *     stg_sample_trajectories; with s[k,n,t,v] the position it would write for the same arguments and vi the scene's
+ *     clamped count, every output is an int32 count over the K samples (integers only: bitwise repeatable).
+ *
+ *   Conflicts (radius > 0): hit[k,n,t,i,j] = i != j, both below vi, dx*dx + dy*dy < radius*radius in float32 (strict).
+ *     conflict (N,P,V)   #k with any_j hit[k,n,t,i,j]
+ *     conflict_any (N,V) #k with any_{t,j} hit
+ *     pair (N,V,V)       #k with any_t hit[k,n,t,i,j]: symmetric, zero diagonal; may be NULL
+ *     partner (N,V)      argmax_j pair[n,i,j], the smallest j on ties, -1 when the row is all zero (computed whether or
+ *                        not pair is written)
+ *   Zones (Z > 0): zones (N,Z,4) float32 [x0,y0,x1,y1] with scene stride z_sn floats (0: one set shared by every
+ *   scene); a sample is inside when x0 <= x < x1 && y0 <= y < y1, by comparison only (an inverted rectangle is empty).
+ *     zone_any (N,P,Z)   #k with some pedestrian below vi inside at step t
+ *     zone_count (N,P,Z) sum over k of the number inside
+ *     ped_zone (N,V,Z)   #k in which pedestrian v is inside at any step
+ *   Padded slots are 0 (-1 in partner).  radius <= 0 skips the conflict outputs, Z == 0 the zone outputs (their
+ *   pointers may then be NULL); both at once is STG_EINVAL, as are a NULL pred or required output, P, V or K below 1 and
+ *   noise / obs_last that are not 8-byte aligned.  N == 0 is a no-op.  One workgroup per scene with the samples of a
+ *   few k at a time in LDS; sizes above the STG_RISK_MAX_* limits are refused with STG_EUNSUPPORTED before any launch
+ *   (every size inside them fits the 160 KiB of LDS).                                                                */
+#define STG_RISK_MAX_V 256
+#define STG_RISK_MAX_K 64
+#define STG_RISK_MAX_Z 16
+#define STG_RISK_MAX_P 32
+int stg_sample_risk(const float *pred, int64_t p_sn, int64_t p_sf, int64_t p_sp, int64_t p_sv, const float *obs_last,
+                    const int32_t *num_peds, const float *noise, uint64_t seed, const uint64_t *seed_dev, int N, int P,
+                    int V, int K, float radius, const float *zones, int64_t z_sn, int Z, int32_t *conflict,
+                    int32_t *conflict_any, int32_t *partner, int32_t *pair, int32_t *zone_any, int32_t *zone_count,
+                    int32_t *ped_zone, void *stream);
+
 /* Self-test helper: C(16x16) = A(16xK) * B(Kx16) through v_mfma_f32_16x16x4_f32 with the operand
  * maps the TXP-CNN kernels rely on (K multiple of 4).                                           */
 int stg_selftest_mfma(const float *a, const float *b, int K, float *c, void *stream);

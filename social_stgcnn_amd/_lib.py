@@ -69,6 +69,8 @@ _SIGNATURES = {
                                c_f, c_f, c_f]),
     "stg_sample_trajectories": (c_i, [c_f, c_l, c_l, c_l, c_l, c_f, c_f, c_f, ctypes.c_uint64, c_f, c_i, c_i, c_i, c_i,
                                       c_f, c_f, c_f]),
+    "stg_sample_risk": (c_i, [c_f, c_l, c_l, c_l, c_l, c_f, c_f, c_f, ctypes.c_uint64, c_f, c_i, c_i, c_i, c_i,
+                              ctypes.c_float, c_f, c_l, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
     "stg_gather_windows": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f]),
     "stg_dp_pack": (c_i, [c_f, c_f, c_f, c_f, c_i, ctypes.c_float, c_i, c_i, c_i, c_i, c_f, c_f]),
     "stg_dp_fold": (c_i, [c_f, c_f, ctypes.c_float, c_i, c_i, c_i, c_i, c_f, ctypes.POINTER(ctypes.c_void_p), c_i, c_f]),

@@ -30,6 +30,7 @@ import ctypes
 import numpy as np
 import torch
 
+from . import ops
 from ._lib import check, lib, ptr, require_gpu, stream_ptr
 from .predict import Prediction, Predictor, _seed_i64, eval_mode
 
@@ -148,28 +149,42 @@ def recording_scenes(rows, device, obs_len=8, min_peds=1, decimals=4, v_pad=None
 
 
 @torch.no_grad()
-def predict_recording(model, rows, k=20, seed=0, batch_size=64, noise_fn=None, min_peds=1, decimals=4, v_pad=None):
+def predict_recording(model, rows, k=20, seed=0, batch_size=64, noise_fn=None, min_peds=1, decimals=4, v_pad=None,
+                      risk=None):
     """Predictions at every frame scene of a recording (recording_scenes with obs_len = model.seq_len): the Predictor
     over batch_size scenes per launch chain, the draws from the Philox stream keyed by seed + batch index, or from
     noise_fn(batch_index, (k,N,P,V,2)) -> standard normals (as predict.sample_test).  Returns (FrameScenes,
-    Prediction) with the per-frame predictions concatenated: samples (K,N,P,V,2), mean (N,P,V,2), v_pred (N,5,P,V)."""
+    Prediction) with the per-frame predictions concatenated: samples (K,N,P,V,2), mean (N,P,V,2), v_pred (N,5,P,V).
+    risk: a predict.RiskSpec (zones (Z,4), the same for every frame) -- the result is then (FrameScenes, Prediction,
+    ops.Risk), the counts of ops.sample_risk over each frame's K samples, concatenated like the predictions."""
     if int(batch_size) < 1:
         raise ValueError("batch_size must be >= 1")
     dev = next(model.parameters()).device
     scenes = recording_scenes(rows, dev, model.seq_len, min_peds, decimals, v_pad)
-    pred = Predictor(model, k)
+    pred = Predictor(model, k, risk)
+    if risk is not None and pred.spec.zones is not None and np.ndim(pred.spec.zones) != 2:
+        raise ValueError("predict_recording: risk zones (Z,4) expected")
     n, _, v, _ = scenes.obs_abs.shape
     p = model.pred_seq_len
-    parts = []
+    parts, risks = [], []
     for b, lo in enumerate(range(0, n, int(batch_size))):
         hi = min(n, lo + int(batch_size))
         noise = noise_fn(b, (pred.k, hi - lo, p, v, 2)) if noise_fn is not None else None
         parts.append(pred.predict(scenes.obs_abs[lo:hi], scenes.num_peds[lo:hi], seed + b, noise))
+        risks.append(pred.risk)
     if not parts:
         z = lambda *s: torch.zeros(s, device=dev, dtype=torch.float32)      # noqa: E731
-        return scenes, Prediction(z(pred.k, 0, p, v, 2), z(0, p, v, 2), z(0, 5, p, v))
-    return scenes, Prediction(torch.cat([r.samples for r in parts], 1), torch.cat([r.mean for r in parts], 0),
-                              torch.cat([r.v_pred for r in parts], 0))
+        res = Prediction(z(pred.k, 0, p, v, 2), z(0, p, v, 2), z(0, 5, p, v))
+        if risk is None:
+            return scenes, res
+        zones = pred._zones(0, dev)
+        return scenes, res, ops.risk_buffers(0, p, v, pred.k, pred.spec.radius, 0 if zones is None else zones.shape[0],
+                                             pred.spec.pairs, dev)
+    res = Prediction(torch.cat([r.samples for r in parts], 1), torch.cat([r.mean for r in parts], 0),
+                     torch.cat([r.v_pred for r in parts], 0))
+    if risk is None:
+        return scenes, res
+    return scenes, res, ops.Risk(pred.k, *(None if f[0] is None else torch.cat(f, 0) for f in list(zip(*risks))[1:]))
 
 
 def host_detections(ids, xy, max_detections):
@@ -200,9 +215,10 @@ class _LivePredictor:
 
     and `seed_dev`, the (1,) int64 device tensor the sampler reads its seed from."""
 
-    def __init__(self, model, k, obs_len, capacity, max_peds, max_detections, decimals):
+    def __init__(self, model, k, obs_len, capacity, max_peds, max_detections, decimals, risk=None, keep_samples=True):
         self.model = model
         self.k = int(k)
+        self._risk_args = (risk, keep_samples)
         self.t_obs = _obs_len(obs_len)
         if self.t_obs != model.seq_len:
             raise ValueError("obs_len=%d but the model observes %d frames" % (self.t_obs, model.seq_len))
@@ -225,8 +241,20 @@ class _LivePredictor:
         self.mask = torch.empty(lead + (self.s,), device=dev, dtype=torch.int32)
         self.ring = torch.zeros(lead + (self.t_obs, self.s, 2), device=dev, dtype=torch.float64)
         self.head_flags = torch.empty(lead + (2,), device=dev, dtype=torch.int32)
-        self._pred = Predictor(self.model, self.k)
+        self._pred = Predictor(self.model, self.k, *self._risk_args)
         return dev
+
+    @property
+    def risk(self):
+        """The ops.Risk of the last push (predict.RiskSpec given as `risk`): counts over the K samples, one scene per
+        stream; from a captured push the graph's static tensors.  None without a RiskSpec or before the first push."""
+        return self._pred.risk
+
+    @property
+    def zones(self):
+        """The device tensor of rectangles the reducer reads ((Z,4), or per stream (NS,Z,4)); a caller may overwrite
+        it between pushes."""
+        return self._pred.zones
 
     @torch.no_grad()
     def push(self, *det, seed=None, noise=None):
@@ -273,8 +301,9 @@ class FramePredictor(_LivePredictor):
     (stg_track_push): `capacity` slots, a slot freed once its pedestrian has been missing for obs_len - 1 frames.  Ids
     come from the caller's tracker (association is not done here)."""
 
-    def __init__(self, model, k=20, obs_len=8, capacity=1024, max_peds=128, max_detections=1024, decimals=4):
-        super().__init__(model, k, obs_len, capacity, max_peds, max_detections, decimals)
+    def __init__(self, model, k=20, obs_len=8, capacity=1024, max_peds=128, max_detections=1024, decimals=4,
+                 risk=None, keep_samples=True):
+        super().__init__(model, k, obs_len, capacity, max_peds, max_detections, decimals, risk, keep_samples)
         dev, m = self._track_state(), self.m_max
         self.det_id = torch.zeros(m, device=dev, dtype=torch.int64)
         self.det_xy = torch.zeros((m, 2), device=dev, dtype=torch.float64)
@@ -429,11 +458,13 @@ class StreamsPredictor(_LivePredictor):
     sequence of (ids, xy) or None (host arrays; see pack_tick), or a DeviceTick.  The sampler's Philox draws are keyed
     by the scene's index in the tick: stream s draws what Predictor.predict draws for scene s of the tick's batch, not
     what a lone FramePredictor with the same seed draws.  The seed lives in the staging block.
-    max_total_detections (default streams * max_detections) sizes the staging buffers."""
+    max_total_detections (default streams * max_detections) sizes the staging buffers.  risk (a predict.RiskSpec, its
+    zones (Z,4) for every stream or (NS,Z,4) per stream) and keep_samples as in predict.Predictor: the tick's counts are
+    at `.risk`, 5.4 MB of int32 counts at 600 streams padded to 128 pedestrians, where the samples are 147 MB."""
 
     def __init__(self, model, streams, k=20, obs_len=8, capacity=1024, max_peds=128, max_detections=1024, decimals=4,
-                 max_total_detections=None, block_threads=0):
-        super().__init__(model, k, obs_len, capacity, max_peds, max_detections, decimals)
+                 max_total_detections=None, block_threads=0, risk=None, keep_samples=True):
+        super().__init__(model, k, obs_len, capacity, max_peds, max_detections, decimals, risk, keep_samples)
         if not _is_int(streams, 1, MAX_STREAMS):
             raise ValueError("streams must be an integer in [1, %d], got %r" % (MAX_STREAMS, streams))
         self.ns = int(streams)

@@ -3,6 +3,7 @@
 Every function here launches hand-written HIP kernels on the current torch stream and
 raises if the library or a GPU tensor is missing -- there is no eager fallback.
 """
+import collections
 import ctypes
 import dataclasses
 import math
@@ -635,6 +636,94 @@ def sample_trajectories(y, obs_last=None, num_peds=None, k=20, noise=None, seed=
                                         ptr(samples) if k > 0 else None, ptr(mean), stream_ptr()),
           "stg_sample_trajectories")
     return samples, mean
+
+
+Risk = collections.namedtuple("Risk", "k conflict conflict_any partner pair zone_any zone_count ped_zone")
+Risk.__doc__ = """int32 counts over the k samples (`stg_sample_risk`): conflict (N,P,V), conflict_any (N,V), partner (N,V)
+(-1: nobody), pair (N,V,V), zone_any (N,P,Z), zone_count (N,P,Z), ped_zone (N,V,Z); a count / k is the estimated
+probability.  Fields that were not asked for are None.  Padded slots are 0 (-1 in partner)."""
+RISK_MAX_V, RISK_MAX_K, RISK_MAX_Z, RISK_MAX_P = 256, 64, 16, 32          # STG_RISK_MAX_*
+
+
+def risk_buffers(n, p, v, k, radius, z, pairs, device):
+    """An empty Risk for n scenes: the outputs sample_risk fills for this radius (None / <= 0: no conflict outputs),
+    z rectangles (0: no zone outputs) and pairs (the (N,V,V) pair counts)."""
+    def i32(*shape):
+        return torch.empty(shape, device=device, dtype=torch.int32)
+    conf = radius is not None and radius > 0
+    return Risk(int(k), i32(n, p, v) if conf else None, i32(n, v) if conf else None, i32(n, v) if conf else None,
+                i32(n, v, v) if conf and pairs else None, i32(n, p, z) if z else None, i32(n, p, z) if z else None,
+                i32(n, v, z) if z else None)
+
+
+def sample_risk(y, obs_last=None, num_peds=None, k=20, radius=None, zones=None, noise=None, seed=0, seed_dev=None,
+                pairs=False, out=None):
+    """Conflict and zone-occupancy counts over the k samples `sample_trajectories` would write for the same arguments,
+    reduced on the device without writing the samples (`stg_sample_risk`).  y, obs_last, num_peds, noise, seed and
+    seed_dev as there.  radius: two pedestrians of a sample conflict at a step when they are closer than this (strictly;
+    None: no conflict outputs); zones: (Z,4) rectangles [x0,y0,x1,y1] shared by the scenes or (N,Z,4) per scene
+    (x0 <= x < x1 and y0 <= y < y1 is inside; None: no zone outputs); pairs: also the (N,V,V) pair counts.
+    out: an earlier Risk of the same call to fill (graph capture).  Returns a Risk."""
+    require_gpu(y, seed_dev)
+    n, f, p, v = y.shape
+    k = int(k)
+    if f != 5:
+        raise ValueError("sample_risk: y (N,5,P,V) expected")
+    if k < 1:
+        raise ValueError("sample_risk: k must be >= 1")
+    radius = None if radius is None else float(radius)
+    if radius is not None and not radius > 0:
+        raise ValueError("sample_risk: radius must be > 0 (None: no conflict outputs), got %r" % (radius,))
+    if radius is None and zones is None:
+        raise ValueError("sample_risk: nothing to compute (neither a radius nor zones)")
+    if pairs and radius is None:
+        raise ValueError("sample_risk: pairs=True needs a radius")
+    y = y.to(torch.float32)
+    if obs_last is not None:
+        if tuple(obs_last.shape) != (n, v, 2):
+            raise ValueError("sample_risk: obs_last (N,V,2) expected")
+        obs_last = obs_last.to(device=y.device, dtype=torch.float32).contiguous()
+    if noise is not None:
+        if tuple(noise.shape) != (k, n, p, v, 2):
+            raise ValueError("sample_risk: noise (K,N,P,V,2) expected")
+        noise = noise.to(device=y.device, dtype=torch.float32).contiguous()
+    if seed_dev is not None and (seed_dev.numel() != 1 or seed_dev.dtype != torch.int64):
+        raise ValueError("sample_risk: seed_dev must be a one-element int64 device tensor")
+    z, z_sn = 0, 0
+    if zones is not None:
+        zones = torch.as_tensor(zones, dtype=torch.float32).to(device=y.device).contiguous()
+        if zones.dim() == 2 and zones.shape[1] == 4:
+            z, z_sn = zones.shape[0], 0
+        elif zones.dim() == 3 and zones.shape[0] == n and zones.shape[2] == 4:
+            z, z_sn = zones.shape[1], zones.shape[1] * 4
+        else:
+            raise ValueError("sample_risk: zones (Z,4) or (N,Z,4) expected, got %s" % (tuple(zones.shape),))
+        if z < 1:
+            raise ValueError("sample_risk: zones holds no rectangle (pass None)")
+    for what, got, most in (("V", v, RISK_MAX_V), ("k", k, RISK_MAX_K), ("Z", z, RISK_MAX_Z), ("P", p, RISK_MAX_P)):
+        if got > most:
+            raise ValueError("sample_risk: %s=%d above the kernel's limit of %d" % (what, got, most))
+    want = risk_buffers(n, p, v, k, radius, z, pairs, "meta")
+    if out is None:
+        out = risk_buffers(n, p, v, k, radius, z, pairs, y.device)
+    else:
+        if out.k != k:
+            raise ValueError("sample_risk: out was made for k=%d, not %d" % (out.k, k))
+        for name, o, w in zip(Risk._fields[1:], out[1:], want[1:]):
+            if (o is None) != (w is None) or (o is not None and (
+                    tuple(o.shape) != tuple(w.shape) or o.dtype != torch.int32 or not o.is_contiguous()
+                    or not o.is_cuda)):
+                raise ValueError("sample_risk: out.%s does not fit this call (%s)"
+                                 % (name, "None" if w is None else "contiguous int32 %s" % (tuple(w.shape),)))
+    peds = peds_arg(num_peds, n, y.device)
+    sn, sf, sp, sv = y.stride()
+    check(lib().stg_sample_risk(ptr(y), sn, sf, sp, sv, ptr(obs_last), ptr(peds), ptr(noise),
+                                int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(seed_dev), n, p, v, k,
+                                ctypes.c_float(radius if radius is not None else 0.0), ptr(zones), z_sn, z,
+                                ptr(out.conflict), ptr(out.conflict_any), ptr(out.partner), ptr(out.pair),
+                                ptr(out.zone_any), ptr(out.zone_count), ptr(out.ped_zone), stream_ptr()),
+          "stg_sample_risk")
+    return out
 
 
 def scene_order(num_peds, v):

@@ -5,7 +5,8 @@ test_v.py / visualize.py read.
     observed_inputs   obs_abs (N,T_obs,V,2) -> model input x, adjacency, last observed position
     Predictor         relative coordinates -> adj_build -> fused forward -> stg_sample_trajectories; eager
                       (`predict`) or as ONE captured graph (`capture`; `capture_chain` is the same chain on the
-                      caller's static inputs, which frames.py puts behind its push kernels)
+                      caller's static inputs, which frames.py puts behind its push kernels).  With `risk=RiskSpec(...)`
+                      the chain ends in stg_sample_risk: conflict and zone-occupancy counts over the K samples
     sample_test       test() over data.SceneWindows: (ade, fde, raw_data_dict)
 """
 import collections
@@ -20,6 +21,12 @@ from ._lib import peds_arg, require_gpu
 Prediction = collections.namedtuple("Prediction", "samples mean v_pred")
 Prediction.__doc__ = """samples (K,N,P,V,2) absolute sampled trajectories, mean (N,P,V,2) the zero-noise trajectory,
 v_pred (N,5,P,V) the model output (the reference's V_pred before its permute).  Padded slots are zeros."""
+
+
+RiskSpec = collections.namedtuple("RiskSpec", "radius zones pairs", defaults=(None, None, False))
+RiskSpec.__doc__ = """What a Predictor reduces its K samples to (ops.sample_risk): radius (two pedestrians closer than
+this conflict; None: no conflict counts), zones ((Z,4) rectangles [x0,y0,x1,y1] for every scene or (N,Z,4) per scene;
+None: no zone counts), pairs (also the (N,V,V) pair counts)."""
 
 
 def _seed_i64(seed):
@@ -75,14 +82,43 @@ def eval_mode(model):
 class Predictor:
     """K sampled trajectories per pedestrian from observed absolute tracks, for a whole batch of scenes."""
 
-    def __init__(self, model, k=20):
+    def __init__(self, model, k=20, risk=None, keep_samples=True):
+        """risk: a RiskSpec -- every prediction also reduces its K samples to conflict / zone counts on the device
+        (ops.sample_risk, same draws), left at `self.risk` (an ops.Risk) by predict() and by every replay; `self.zones`
+        is the device tensor of rectangles the reducer reads, which a caller may overwrite between replays.
+        keep_samples=False (with risk only): the samples themselves are not written, Prediction.samples is
+        (0,N,P,V,2)."""
         self.model = model
         self.k = int(k)
+        if risk is not None:
+            risk = RiskSpec(*risk)
+            if risk.radius is None and risk.zones is None:
+                raise ValueError("Predictor: risk needs a radius or zones")
+        elif not keep_samples:
+            raise ValueError("Predictor: keep_samples=False without risk leaves nothing to return")
+        self.spec = risk
+        self.keep_samples = bool(keep_samples)
+        self.risk = None
+        self.zones = None
 
-    def _forward(self, obs_abs, peds, seed, noise, seed_dev=None, bufs=None, outs=(None, None)):
+    def _zones(self, n, dev):
+        """The static device tensor of the spec's rectangles, (Z,4) or (n,Z,4)."""
+        if self.zones is None and self.spec.zones is not None:
+            z = torch.as_tensor(self.spec.zones, dtype=torch.float32).to(dev).contiguous()
+            if not ((z.dim() == 2 or (z.dim() == 3 and z.shape[0] == n)) and z.shape[-1] == 4 and z.shape[-2] >= 1):
+                raise ValueError("risk zones (Z,4) or (%d,Z,4) expected, got %s" % (n, tuple(z.shape)))
+            self.zones = z
+        return self.zones
+
+    def _forward(self, obs_abs, peds, seed, noise, seed_dev=None, bufs=None, outs=(None, None), risk_out=None):
         x, adj, obs_last = observed_inputs(obs_abs, peds, bufs)
         y, _ = self.model(x, adj, peds)
-        samples, mean = ops.sample_trajectories(y, obs_last, peds, self.k, noise, seed, seed_dev, *outs)
+        keep = self.keep_samples
+        samples, mean = ops.sample_trajectories(y, obs_last, peds, self.k if keep else 0, noise if keep else None,
+                                                seed, seed_dev, *outs)
+        if self.spec is not None:
+            self.risk = ops.sample_risk(y, obs_last, peds, self.k, self.spec.radius, self._zones(y.shape[0], y.device),
+                                        noise, seed, seed_dev, self.spec.pairs, risk_out)
         return Prediction(samples, mean, y)
 
     @torch.no_grad()
@@ -96,31 +132,38 @@ class Predictor:
 
     def _chain_buffers(self, n, v, dev):
         """The chain's static buffers for n scenes padded to v pedestrians: (rel, nodes, adj) that observed_inputs
-        fills and (samples, mean) that the sampler fills."""
+        fills, (samples, mean) that the sampler fills and, with a RiskSpec, the Risk that the reducer fills."""
         t_obs, p = self.model.seq_len, self.model.pred_seq_len
         f32 = dict(device=dev, dtype=torch.float32)
+        risk = None
+        if self.spec is not None:
+            zones = self._zones(n, dev)
+            risk = ops.risk_buffers(n, p, v, self.k, self.spec.radius, 0 if zones is None else zones.shape[-2],
+                                    self.spec.pairs, dev)
         return ((torch.empty((n, t_obs, v, 2), **f32), torch.empty((n, t_obs, v, 2), **f32),
                  torch.empty((n, t_obs, v, v), **f32)),
-                (torch.empty((self.k, n, p, v, 2), **f32), torch.empty((n, p, v, 2), **f32)))
+                (torch.empty((self.k if self.keep_samples else 0, n, p, v, 2), **f32),
+                 torch.empty((n, p, v, 2), **f32)), risk)
 
     @torch.no_grad()
     def capture_chain(self, obs, peds, seed_dev, warmup=2, pre=None):
         """Capture ONE graph on the static obs (N,T_obs,V,2), peds (N,) int32 and seed_dev (1,) int64: [pre() ->]
         observed_inputs -> fused forward -> stg_sample_trajectories, the model in eval mode, the seed read from
-        seed_dev.  `pre` (optional callable) runs inside the graph ahead of the chain -- the live predictors' push
-        launch, which fills obs and peds; it runs in the warm-up too.  Returns (graph, the static Prediction, the
+        seed_dev (and stg_sample_risk into the static `self.risk` with a RiskSpec).  `pre` (optional callable) runs
+        inside the graph ahead of the chain -- the live predictors' push launch, which fills obs and peds; it runs in
+        the warm-up too.  Returns (graph, the static Prediction, the
         chain's own buffers): every buffer the graph reads or writes has to live as long as the graph is replayed -- a
         freed one would go back to the caching allocator while the graph still writes it."""
         n, _, v, _ = obs.shape
-        bufs, outs = self._chain_buffers(n, v, obs.device)
+        bufs, outs, risk = self._chain_buffers(n, v, obs.device)
 
         def step():
             if pre is not None:
                 pre()
-            return self._forward(obs, peds, 0, None, seed_dev, bufs, outs)
+            return self._forward(obs, peds, 0, None, seed_dev, bufs, outs, risk)
         with eval_mode(self.model):
             graph, res = graphs.warm_capture(step, warmup)
-        return graph, res, (bufs, outs)
+        return graph, res, (bufs, outs, risk, self.zones)
 
     def capture(self, n, v, num_peds, dtype=torch.float32, warmup=2):
         """Capture ONE graph on static buffers for batches of n scenes padded to v pedestrians, positions of `dtype`

@@ -2,15 +2,20 @@
 trajectories for every pedestrian tracked over the last obs_seq_len frames.
 
     python -m social_stgcnn_amd.predict_frames --checkpoint DIR --recording FILE [--ksteps 20] [--seed 0]
-                                               [--min_peds 1] [--delim tab] --out preds.npz
+                                               [--min_peds 1] [--delim tab] [--radius R]
+                                               [--zones x0,y0,x1,y1 ...] --out preds.npz
 
 DIR is a checkpoint directory in the reference's layout (args.pkl and val_best.pth, as social_stgcnn_amd.test reads
 it); FILE a recording in the ETH/UCY text format (<frame> <ped> <x> <y>).  The .npz holds, one entry per frame scene:
 frame (N,) frame numbers, ids (N,V) int64 (-1 in padded slots), num_peds (N,), mean (N,P,V,2) the zero-noise
-trajectories and samples (K,N,P,V,2), float32, zeros in padded slots.
+trajectories and samples (K,N,P,V,2), float32, zeros in padded slots.  With --radius and / or --zones it also holds
+the counts of ops.sample_risk over each frame's K samples, aligned with the frames: risk_k, and risk_conflict (N,P,V),
+risk_conflict_any (N,V), risk_partner (N,V), risk_pair (N,V,V) for a radius, risk_zones (Z,4), risk_zone_any (N,P,Z),
+risk_zone_count (N,P,Z), risk_ped_zone (N,V,Z) for zones.
 """
 import argparse
 import os
+import re
 
 import numpy as np
 import torch
@@ -18,6 +23,7 @@ import torch
 from . import data
 from .frames import predict_recording
 from .model import social_stgcnn
+from .predict import RiskSpec
 from .trainer import load_checkpoint, load_pickle
 
 
@@ -29,8 +35,25 @@ def build_parser():
     p.add_argument("--seed", type=int, default=0, help="seed of the device sampler")
     p.add_argument("--min_peds", type=int, default=1, help="skip frames with fewer pedestrians")
     p.add_argument("--delim", default="tab", help="column delimiter of the recording (tab, space or a character)")
+    p.add_argument("--radius", type=float, default=None,
+                   help="also count the samples in which two pedestrians come closer than this (risk_* arrays)")
+    p.add_argument("--zones", nargs="+", default=None, metavar="x0,y0,x1,y1",
+                   help="also count the samples in which each rectangle is occupied (risk_* arrays)")
     p.add_argument("--out", required=True, help="output .npz")
+    # a rectangle may begin with a negative coordinate: "-1,-1,1,1" is a value, not an option
+    p._negative_number_matcher = re.compile(r"^-[0-9.][0-9.,eE+-]*$")
     return p
+
+
+def parse_zones(specs):
+    """['x0,y0,x1,y1', ...] -> (Z,4) float32."""
+    out = []
+    for s in specs:
+        parts = s.split(",")
+        if len(parts) != 4:
+            raise ValueError("--zones: x0,y0,x1,y1 expected, got %r" % s)
+        out.append([float(x) for x in parts])
+    return np.asarray(out, dtype=np.float32)
 
 
 def load_model(exp_path, device):
@@ -47,9 +70,19 @@ def main(argv=None):
         raise RuntimeError("social_stgcnn_amd.predict_frames needs a GPU (MI355X)")
     model = load_model(a.checkpoint, torch.device("cuda", torch.cuda.current_device()))
     rows = data.read_file(a.recording, a.delim)
-    scenes, pred = predict_recording(model, rows, k=a.ksteps, seed=a.seed, min_peds=a.min_peds)
+    extra = {}
+    if a.radius is None and a.zones is None:
+        scenes, pred = predict_recording(model, rows, k=a.ksteps, seed=a.seed, min_peds=a.min_peds)
+    else:
+        zones = parse_zones(a.zones) if a.zones is not None else None
+        scenes, pred, risk = predict_recording(model, rows, k=a.ksteps, seed=a.seed, min_peds=a.min_peds,
+                                               risk=RiskSpec(a.radius, zones, a.radius is not None))
+        extra = {"risk_" + f: x.cpu().numpy() for f, x in zip(risk._fields[1:], risk[1:]) if x is not None}
+        extra["risk_k"] = np.int32(risk.k)
+        if zones is not None:
+            extra["risk_zones"] = zones
     np.savez(a.out, frame=scenes.frame, ids=scenes.ids.cpu().numpy(), num_peds=scenes.num_peds.cpu().numpy(),
-             mean=pred.mean.cpu().numpy(), samples=pred.samples.cpu().numpy())
+             mean=pred.mean.cpu().numpy(), samples=pred.samples.cpu().numpy(), **extra)
     print("%d frame scenes, up to %d pedestrians -> %s" % (len(scenes.frame), scenes.ids.shape[1], a.out))
 
 

@@ -3,6 +3,7 @@
 
     python tools/frames_bench.py [--pushes 2000] [--cases latency,recording] [--k 20]
     python tools/frames_bench.py --cases streams [--streams 1,8,64,256,600] [--ticks 200] [--block 0] [--no-lone]
+                                 [--risk none,samples,lean]
 
   latency    the captured FramePredictor (ONE graph: stg_track_push -> observed_inputs -> forward -> sampler) pushed
              every frame of a recording in a loop, --pushes timed pushes after a warm-up.  Host clock around staging +
@@ -15,7 +16,9 @@
              (host clock around staging + replay + synchronise) and aggregate frames/s.  Beside it the yardstick: the
              same per-stream sequences through NS lone captured FramePredictors one after another (each push timed as
              the latency case times it; a tick is the sum of its NS pushes).  --block picks the push workgroup size
-             (0: the default); --no-lone skips the yardstick.
+             (0: the default); --no-lone skips the yardstick.  --risk: the modes to time -- none (the default: no
+             reducer), samples (RiskSpec(0.5, three rectangles): stg_sample_risk after the sampler) and lean (the same
+             with keep_samples=False); result_mb is what a tick leaves for the caller (samples + mean + counts).
 
 Kernel times come from a separate run under the profiler (tracing slows the host):
     rocprofv3 --kernel-trace --stats -d OUT -o frames -- python tools/frames_bench.py --cases latency --pushes 500
@@ -107,11 +110,16 @@ def _stream_sequences(ns, n):
     return out
 
 
-def streams_case(ns, k, n_ticks, dev, block=0, lone=True, max_peds=128, warmup=20):
+def streams_case(ns, k, n_ticks, dev, block=0, lone=True, max_peds=128, warmup=20, risk="none"):
     from social_stgcnn_amd import frames
     model = model_for("univ", dev)
     seq = _stream_sequences(ns, warmup + n_ticks)
-    sp = frames.StreamsPredictor(model, ns, k=k, max_peds=max_peds, block_threads=block)
+    kw = {}
+    if risk != "none":
+        from social_stgcnn_amd.predict import RiskSpec
+        kw = dict(risk=RiskSpec(0.5, np.array([[-1, -1, 1, 1], [0, 0, 4, 3], [-50, -50, 50, 50]], np.float32)),
+                  keep_samples=risk == "samples")
+    sp = frames.StreamsPredictor(model, ns, k=k, max_peds=max_peds, block_threads=block, **kw)
     replay = sp.capture()
     times, peds = [], []
     for t in range(warmup + n_ticks):
@@ -129,6 +137,11 @@ def streams_case(ns, k, n_ticks, dev, block=0, lone=True, max_peds=128, warmup=2
            "ticks": n_ticks, "tick_p50_ms": round(p50, 4), "tick_p90_ms": round(float(np.percentile(ms, 90)), 4),
            "frames_per_s_p50": round(ns * 1e3 / p50, 1), "mean_peds": round(float(peds.mean()), 2),
            "max_peds_seen": int(peds.max())}
+    if risk != "none":
+        res["risk"] = risk
+        res["conflict_any_mean"] = round(float(sp.risk.conflict_any.float().mean()), 3)
+    counts = 0 if risk == "none" else sum(x.numel() for x in sp.risk[1:] if x is not None)
+    res["result_mb"] = round((out.samples.numel() + out.mean.numel() + counts) * 4 / 1e6, 3)
     if lone:
         # the yardstick: NS lone captured FramePredictors, one after another; fewer ticks at large NS
         n_seq = max(10, min(n_ticks, 4000 // ns))
@@ -163,6 +176,7 @@ def main():
     ap.add_argument("--ticks", type=int, default=200)
     ap.add_argument("--block", default="0", help="push workgroup size(s) of the streams case, comma separated")
     ap.add_argument("--no-lone", action="store_true")
+    ap.add_argument("--risk", default="none", help="modes of the streams case, comma separated: none, samples, lean")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("frames_bench needs a GPU (MI355X)")
@@ -178,7 +192,9 @@ def main():
     if "streams" in cases:
         for block in (int(b) for b in a.block.split(",")):
             for ns in (int(n) for n in a.streams.split(",")):
-                print(json.dumps(streams_case(ns, a.k, a.ticks, dev, block, not a.no_lone)), flush=True)
+                for mode in a.risk.split(","):
+                    print(json.dumps(streams_case(ns, a.k, a.ticks, dev, block, not a.no_lone, risk=mode)),
+                          flush=True)
 
 
 if __name__ == "__main__":

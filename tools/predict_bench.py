@@ -2,11 +2,14 @@
 """Device time of the captured Predictor (observed absolute tracks -> K sampled trajectories, ONE graph) and of the
 sampling kernel alone, from device events around graph replays.  One JSON line per case.
 
-    python tools/predict_bench.py [--iters 200] [--cases bench,eth,kernel]
+    python tools/predict_bench.py [--iters 200] [--cases bench,eth,kernel,risk]
 
   bench   Predictor replay at N = 2048, V = 32 (every slot a pedestrian), K = 20, eth weights
   eth     Predictor replay on eth/test: its 70 windows as one ragged batch, K = 20
   kernel  stg_sample_trajectories alone at K = 20 x N = 2048 x V = 32, P = 12 (63 MB written), captured
+  risk    stg_sample_risk (radius 0.5, three rectangles, pair counts) against stg_sample_trajectories on the same
+          arguments, both captured: K = 20 at N = 2048 x V = 32 with every slot full, and at N = 600 x V = 128 with the
+          ragged scene sizes of the six test recordings (frame scenes taken at a fixed stride)
 
 For the kernel's own time run this under `rocprofv3 --kernel-trace --stats -- python tools/predict_bench.py`.
 With the diagnostic library (STG_USE_DIAG_LIB=1, `make -C social_stgcnn_amd/csrc DIAG=1`) STG_SAMPLE_PEDS=1 forces
@@ -100,6 +103,39 @@ def main():
         print(json.dumps(dict({"case": "sample_kernel", "k": k, "n": n, "v": v, "p": p, "ms_per_replay": round(ms, 5),
                                "mb_written": round(written / 1e6, 2), "read_mb": round(n * 5 * p * v * 4 / 1e6, 2),
                                "store_tb_per_s": round(written / (ms * 1e-3) / 1e12, 3)}, **info)), flush=True)
+    if "risk" in cases:
+        from social_stgcnn_amd import frames
+        counts = torch.cat([frames.recording_scenes(data.read_file(os.path.join(ROOT, "tests", "golden", "data", d, f)),
+                                                    dev).num_peds
+                            for d, f in (("eth_test", "biwi_eth.txt"), ("hotel_test", "biwi_hotel.txt"),
+                                         ("univ_test", "students001.txt"), ("univ_test", "students003.txt"),
+                                         ("zara1_test", "crowds_zara01.txt"), ("zara2_test", "crowds_zara02.txt"))])
+        ragged = counts[torch.arange(600, device=dev) * (len(counts) // 600)].clamp(max=128).contiguous()
+        zones = torch.tensor([[-1, -1, 1, 1], [0, 0, 4, 3], [-50, -50, 50, 50]], dtype=torch.float32, device=dev)
+        for rn, rv, peds in ((2048, 32, None), (600, 128, ragged)):
+            gen = torch.Generator().manual_seed(2)
+            y = (torch.randn((rn, p, rv, 5), generator=gen) * 0.5).to(dev).permute(0, 3, 1, 2)
+            obs_last = ((torch.rand((rn, rv, 2), generator=gen) * 2 - 1) * (rv ** 0.5)).to(dev)
+            seed_dev = torch.ones(1, dtype=torch.int64, device=dev)
+            samples = torch.empty((k, rn, p, rv, 2), device=dev)
+            mean = torch.empty((rn, p, rv, 2), device=dev)
+            risk = ops.sample_risk(y, obs_last, peds, k, 0.5, zones, seed_dev=seed_dev, pairs=True)
+
+            def run_samples():
+                ops.sample_trajectories(y, obs_last, peds, k, None, 0, seed_dev, samples, mean)
+
+            def run_risk():
+                ops.sample_risk(y, obs_last, peds, k, 0.5, zones, seed_dev=seed_dev, pairs=True, out=risk)
+            ms_s = time_replays(graphs.warm_capture(run_samples, 1)[0].replay, args.iters)
+            ms_r = time_replays(graphs.warm_capture(run_risk, 1)[0].replay, args.iters)
+            vi = torch.full((rn,), rv, device=dev) if peds is None else peds
+            print(json.dumps(dict({"case": "risk_kernel", "k": k, "n": rn, "v": rv, "p": p,
+                                   "peds": int(vi.sum()), "pair_tests_m": round(float((vi.double() * (vi - 1) / 2).sum())
+                                                                                * k * p / 1e6, 1),
+                                   "sample_ms": round(ms_s, 5), "risk_ms": round(ms_r, 5),
+                                   "ratio": round(ms_r / ms_s, 3),
+                                   "risk_mb": round(sum(x.numel() for x in risk[1:]) * 4 / 1e6, 3),
+                                   "samples_mb": round(samples.numel() * 4 / 1e6, 2)}, **info)), flush=True)
 
 
 if __name__ == "__main__":
