@@ -379,6 +379,43 @@ int stg_track_push_streams(const int64_t *det_id, int64_t id_stride, const doubl
                            double scale, int V, double *obs_abs, int64_t *out_ids, int32_t *num_peds,
                            int32_t *out_flags, int block_threads, void *stream);
 
+/* Partially observed tracks: the N6 scenes for pedestrians with a short history or tracker gaps (added entry points).
+ * A rule is (min_seen in [2, T_obs], max_gap in [0, T_obs - 2]).  The window of a frame has steps t = 0 .. T_obs-1,
+ * oldest first, the last one the frame itself; frames before the first one count as missed.  An id is in the scene iff
+ * it is seen at step T_obs-1, seen in at least min_seen steps, and every run of missed steps between two seen steps is
+ * at most max_gap long (missed steps ahead of the first seen one are no gap).  min_seen = T_obs, max_gap = 0 is the
+ * strict rule of N6.  Order, the V smallest ids, STG_TRACK_TOO_MANY and the lifetime of a slot are those of N6.
+ *   Fill, in float64 with IEEE operations as written (no fused multiply-add), round = the rounding of N6:
+ *     interior step t between the nearest seen steps a < t < b:  p[t] = round(p[a] + (p[b]-p[a]) * ((double)(t-a) / (double)(b-a)))
+ *     leading step t < a0 (the first seen step), q = the window after the interior fill:
+ *                                                              p[t] = round(q[a0] - (double)(a0-t) * (q[a0+1] - q[a0]))
+ *   seen: int32 per scene slot, bit t set = observed t frames ago (bit 0 = this frame, the orientation of the state's
+ *   masks), 0 in padded slots.
+ * The fill on a batch in place: obs_abs (N,T_obs,V,2) float64, seen (N,V), num_peds int32[N] or NULL (all V columns); one
+ * lane per (scene, pedestrian).  A column's seen steps are rounded and its missed steps filled; a column at or past
+ * num_peds, with bit 0 clear or with fewer than two bits set is left untouched.  2 <= T_obs <= 32.
+ * The two recording kernels and the two pushes of N6 under a rule take (min_seen, max_gap) after their sizes and write
+ * seen (N,V) / (V) / (NS,V) beside their other outputs; every other argument is as in the strict entry point, which
+ * keeps its own code.  The recording scenes start at frame index min_seen - 1.  The pushes read only the ring rows of
+ * seen frames.                                                                                                        */
+int stg_fill_tracks(double *obs_abs, const int32_t *seen, const int32_t *num_peds, int N, int T_obs, int V,
+                    double scale, void *stream);
+int stg_frame_scene_counts_rule(const int32_t *frame_start, const int64_t *ids, int F, int T_obs, int min_seen,
+                                int max_gap, int32_t *count, void *stream);
+int stg_frame_scenes_rule(const int32_t *frame_start, const int64_t *ids, const double *xy, const int32_t *frames,
+                          int N, int V, int T_obs, double scale, int min_seen, int max_gap, double *obs_abs,
+                          int64_t *out_ids, int32_t *num_peds, int32_t *seen, void *stream);
+int stg_track_push_rule(const int64_t *det_id, const double *det_xy, const int32_t *det_count, int M_max,
+                        int64_t *slot_id, uint32_t *mask, double *ring, int32_t *head_flags, int S, int T_obs,
+                        double scale, int V, int min_seen, int max_gap, double *obs_abs, int64_t *out_ids,
+                        int32_t *num_peds, int32_t *seen, void *stream);
+int stg_track_push_streams_rule(const int64_t *det_id, int64_t id_stride, const double *det_xy, int64_t xy_stride,
+                                int M_total, const int32_t *det_start, const int32_t *pushed, int NS, int M_max,
+                                int64_t *slot_id, uint32_t *mask, double *ring, int32_t *head_flags, int S, int T_obs,
+                                double scale, int V, int min_seen, int max_gap, double *obs_abs, int64_t *out_ids,
+                                int32_t *num_peds, int32_t *out_flags, int32_t *seen, int block_threads,
+                                void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * N7  what a caller acts on, reduced from the K samples of N5 without writing them out: conflict and zone-occupancy
  *     counts.  pred, strides, obs_last, num_peds (clamped to [0, V]), noise, seed and seed_dev exactly as in

@@ -83,6 +83,14 @@ _SIGNATURES = {
                              c_f]),
     "stg_track_push_streams": (c_i, [c_f, c_l, c_f, c_l, c_i, c_f, c_f, c_i, c_i, c_f, c_f, c_f, c_f, c_i, c_i,
                                      ctypes.c_double, c_i, c_f, c_f, c_f, c_f, c_i, c_f]),
+    "stg_fill_tracks": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, ctypes.c_double, c_f]),
+    "stg_frame_scene_counts_rule": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_f, c_f]),
+    "stg_frame_scenes_rule": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, ctypes.c_double, c_i, c_i, c_f, c_f, c_f, c_f,
+                                    c_f]),
+    "stg_track_push_rule": (c_i, [c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_i, c_i, ctypes.c_double, c_i, c_i, c_i,
+                                  c_f, c_f, c_f, c_f, c_f]),
+    "stg_track_push_streams_rule": (c_i, [c_f, c_l, c_f, c_l, c_i, c_f, c_f, c_i, c_i, c_f, c_f, c_f, c_f, c_i, c_i,
+                                          ctypes.c_double, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_i, c_f]),
     "stg_selftest_mfma": (c_i, [c_f, c_f, c_i, c_f, c_f]),
 }
 EXPORTS = tuple(_SIGNATURES)

@@ -14,6 +14,12 @@
 //                           stream's slice of the state and its range of one packed tick of detections; the counts,
 //                           offsets and pushed flags are read from device memory, so one captured graph serves a tick.
 //
+//
+// Partially observed tracks: TrackRule below admits a pedestrian with a short history or tracker gaps
+// and fills the frames it missed.  stg_fill_tracks applies the fill to a batch in place; the *_rule entry points are
+// the two recording kernels and the two pushes with the rule in the place of "seen in each of the T_obs frames", plus
+// a `seen` output (the presence bits of every scene slot).  The strict entry points launch the strict code.
+//
 // Pure data movement and integer work: a few KB per frame.  No host synchronisation in the launch functions (the push
 // is captured into the per-frame graph of FramePredictor.capture) and plain C++ stores only.
 #include "common.hpp"
@@ -46,6 +52,96 @@ __device__ __forceinline__ int row_of(const int32_t *__restrict__ fs, const int6
 __device__ __forceinline__ int lanes_below(uint64_t m) {
     const int lane = threadIdx.x & (kWave - 1);
     return __popcll(m & ((1ull << lane) - 1ull));
+}
+
+// ---- the rule for partially observed tracks ------------------------------------------------------------------------
+// Presence bits m of one pedestrian over the T_obs-frame window: bit t = seen t frames ago (bit 0 = this frame), the
+// orientation of the state's masks; window step t (oldest first) is bit T_obs - 1 - t.
+//   member  seen now, in at least min_seen frames of the window, and no run of missed frames between two seen ones
+//           longer than max_gap (missed frames ahead of the first seen one are no gap)
+//   fill    the window with every missed step filled, in float64 with IEEE operations as written (no fused
+//           multiply-add): an interior step t between the nearest seen steps a < t < b is
+//           round_pos(p[a] + (p[b] - p[a]) * ((double)(t - a) / (double)(b - a))); a leading step t < a0 (the first seen
+//           step) is round_pos(q[a0] - (double)(a0 - t) * (q[a0+1] - q[a0])) with q the window after the interior fill
+// min_seen = T_obs, max_gap = 0 is the strict rule.
+struct TrackRule {
+    int min_seen, max_gap;
+
+    __device__ __forceinline__ bool member(uint32_t m) const {
+        if ((m & 1u) == 0 || __popc(m) < min_seen) return false;
+        // the missed frames below the oldest seen one; a run of max_gap + 1 of them survives max_gap shifted ANDs
+        const uint32_t z = ~m & ((1u << (31 - __clz(m))) - 1u);
+        uint32_t run = z;
+        for (int k = 1; k <= max_gap; ++k) run &= z >> k;
+        return run == 0;
+    }
+
+    // m: a member's bits (bit 0 and at least one more set, nothing at or above bit T_obs).  read(t, x, y) yields the
+    // rounded position of a SEEN step t -- a missed step is never read --, write(t, x, y) takes every step's once.
+    // A seen step is read before it is written and a filled one is only written, so the two may be the same memory.
+    template <class Read, class Write>
+    static __device__ __forceinline__ void fill(uint32_t m, int T_obs, double scale, Read read, Write write) {
+#pragma clang fp contract(off)
+        const int a0 = T_obs - 1 - (31 - __clz(m));          // the first seen step
+        double ax, ay;
+        read(a0, ax, ay);
+        write(a0, ax, ay);
+        const double q0x = ax, q0y = ay;
+        double q1x = 0.0, q1y = 0.0;                          // q[a0 + 1]
+        int a = a0;
+        for (int b = a0 + 1; b < T_obs; ++b) {
+            if (((m >> (T_obs - 1 - b)) & 1u) == 0) continue;
+            double bx, by;
+            read(b, bx, by);
+            for (int t = a + 1; t < b; ++t) {
+                const double w = (double)(t - a) / (double)(b - a);
+                const double x = round_pos(ax + (bx - ax) * w, scale), y = round_pos(ay + (by - ay) * w, scale);
+                write(t, x, y);
+                if (t == a0 + 1) {
+                    q1x = x;
+                    q1y = y;
+                }
+            }
+            write(b, bx, by);
+            if (b == a0 + 1) {
+                q1x = bx;
+                q1y = by;
+            }
+            a = b;
+            ax = bx;
+            ay = by;
+        }
+        const double dx = q1x - q0x, dy = q1y - q0y;
+        for (int t = 0; t < a0; ++t) {
+            const double k = (double)(a0 - t);
+            write(t, round_pos(q0x - k * dx, scale), round_pos(q0y - k * dy, scale));
+        }
+    }
+};
+
+// One lane per (scene, pedestrian): the column's missed steps filled in place, its seen steps rounded.  A column past
+// the scene's count, not seen now or seen only once is left as it is.
+__global__ __launch_bounds__(256) void fill_tracks_kernel(double *__restrict__ obs_abs, const int32_t *__restrict__ seen,
+                                                          const int32_t *__restrict__ num_peds, int N, int T_obs, int V,
+                                                          double scale) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)N * V) return;
+    const int n = (int)(i / V), v = (int)(i % V);
+    if (num_peds && v >= num_peds[n]) return;
+    const uint32_t full = T_obs >= 32 ? 0xffffffffu : (1u << T_obs) - 1u;
+    const uint32_t m = (uint32_t)seen[i] & full;
+    if (!TrackRule{2, T_obs - 2}.member(m)) return;
+    double *col = obs_abs + ((int64_t)n * T_obs * V + v) * 2;           // step stride V * 2
+    TrackRule::fill(
+        m, T_obs, scale,
+        [&](int t, double &x, double &y) {
+            x = round_pos(col[(int64_t)t * V * 2], scale);
+            y = round_pos(col[(int64_t)t * V * 2 + 1], scale);
+        },
+        [&](int t, double x, double y) {
+            col[(int64_t)t * V * 2] = x;
+            col[(int64_t)t * V * 2 + 1] = y;
+        });
 }
 
 // ---- recording ---------------------------------------------------------------------------------------------------
@@ -107,6 +203,74 @@ __global__ __launch_bounds__(64) void frame_scenes_kernel(const int32_t *__restr
     if (lane == 0) num_peds[n] = c;
 }
 
+// The recording kernels under a TrackRule.  presence bits of `id`, a row of frame f: bit k = a row in frame f - k
+// (frames before the recording's first count as missed).
+__device__ __forceinline__ uint32_t presence_bits(const int32_t *__restrict__ fs, const int64_t *__restrict__ ids, int f,
+                                                  int T_obs, int64_t id) {
+    uint32_t m = 1u;
+    for (int k = 1; k < T_obs && k <= f; ++k) m |= row_of(fs, ids, f - k, id) >= 0 ? 1u << k : 0u;
+    return m;
+}
+
+__global__ __launch_bounds__(64) void frame_scene_counts_rule_kernel(const int32_t *__restrict__ fs,
+                                                                     const int64_t *__restrict__ ids, int T_obs,
+                                                                     TrackRule rule, int32_t *__restrict__ count) {
+    const int f = blockIdx.x;
+    int c = 0;
+    if (f >= rule.min_seen - 1)
+        for (int r = fs[f] + (int)threadIdx.x; r < fs[f + 1]; r += kWave)
+            c += rule.member(presence_bits(fs, ids, f, T_obs, ids[r])) ? 1 : 0;
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, kWave);
+    if (threadIdx.x == 0) count[f] = c;
+}
+
+__global__ __launch_bounds__(64) void frame_scenes_rule_kernel(
+    const int32_t *__restrict__ fs, const int64_t *__restrict__ ids, const double *__restrict__ xy,
+    const int32_t *__restrict__ frames, int V, int T_obs, double scale, TrackRule rule, double *__restrict__ obs_abs,
+    int64_t *__restrict__ out_ids, int32_t *__restrict__ num_peds, int32_t *__restrict__ seen) {
+    const int n = blockIdx.x, lane = threadIdx.x;
+    const int f = frames[n];
+    double *obs = obs_abs + (int64_t)n * T_obs * V * 2;          // (T_obs, V, 2)
+    int64_t *oid = out_ids + (int64_t)n * V;
+    int32_t *osn = seen + (int64_t)n * V;
+    int base = 0;
+    for (int r0 = fs[f]; r0 < fs[f + 1]; r0 += kWave) {
+        const int r = r0 + lane;
+        const bool real = r < fs[f + 1];
+        const int64_t id = real ? ids[r] : 0;
+        const uint32_t pm = real ? presence_bits(fs, ids, f, T_obs, id) : 0u;
+        const bool in = real && f >= rule.min_seen - 1 && rule.member(pm);
+        const uint64_t m = __ballot(in);
+        const int slot = base + lanes_below(m);
+        if (in && slot < V) {
+            oid[slot] = id;
+            osn[slot] = (int32_t)pm;
+            TrackRule::fill(
+                pm, T_obs, scale,
+                [&](int t, double &x, double &y) {
+                    const int q = t == T_obs - 1 ? r : row_of(fs, ids, f - T_obs + 1 + t, id);
+                    x = round_pos(xy[(int64_t)q * 2], scale);
+                    y = round_pos(xy[(int64_t)q * 2 + 1], scale);
+                },
+                [&](int t, double x, double y) {
+                    obs[((int64_t)t * V + slot) * 2] = x;
+                    obs[((int64_t)t * V + slot) * 2 + 1] = y;
+                });
+        }
+        base += __popcll(m);
+    }
+    const int c = base < V ? base : V;
+    for (int s = c + lane; s < V; s += kWave) {
+        oid[s] = -1;
+        osn[s] = 0;
+        for (int t = 0; t < T_obs; ++t) {
+            obs[((int64_t)t * V + s) * 2] = 0.0;
+            obs[((int64_t)t * V + s) * 2 + 1] = 0.0;
+        }
+    }
+    if (lane == 0) num_peds[n] = c;
+}
+
 // ---- live streams ------------------------------------------------------------------------------------------------
 // Block-wide exclusive rank of `flag` over the threads (thread order), added to `base`; every thread gets the block
 // total in *total.  Called by all kThreads threads of the block (it holds two barriers).
@@ -134,14 +298,17 @@ __device__ __forceinline__ int block_rank(bool flag, int base, int *total, int *
 // head_flags (2); its scene obs_abs (T_obs,V,2), out_ids (V), *num_peds.  Returns (in every thread) the flags.
 // LDS layout (dynamic): sort keys (M2 x int64), sort indices (M2 x int32), det_slot (M_max x int32),
 // slot masks (S x uint32), free slots (S x int32)
-template <int kThreads>
+// kRule: the scene phase admits and fills by `rule` and writes the presence bits of every scene slot to seen (V);
+// without it (the strict entry points) neither is looked at.
+template <int kThreads, bool kRule>
 __device__ __forceinline__ int track_push_body(const int64_t *__restrict__ det_id, int64_t id_stride,
                                                const double *__restrict__ det_xy, int64_t xy_stride, int count,
                                                int M_max, int M2, int64_t *__restrict__ slot_id,
                                                uint32_t *__restrict__ mask, double *__restrict__ ring,
                                                int32_t *__restrict__ head_flags, int S, int T_obs, double scale, int V,
                                                double *__restrict__ obs_abs, int64_t *__restrict__ out_ids,
-                                               int32_t *__restrict__ num_peds) {
+                                               int32_t *__restrict__ num_peds, TrackRule rule = {},
+                                               int32_t *__restrict__ seen = nullptr) {
     extern __shared__ __align__(16) unsigned char lds[];
     int64_t *key = reinterpret_cast<int64_t *>(lds);
     int32_t *kidx = reinterpret_cast<int32_t *>(key + M2);
@@ -260,9 +427,35 @@ __device__ __forceinline__ int track_push_body(const int64_t *__restrict__ det_i
         const int p = p0 + tid;
         const int j = p < m ? kidx[p] : 0;
         const int s = p < m ? det_slot[j] : -1;
-        const bool in = s >= 0 && (smask[s] & full) == full;
+        bool in;
+        if constexpr (kRule) in = s >= 0 && rule.member(smask[s]);
+        else in = s >= 0 && (smask[s] & full) == full;
         const int r = block_rank<kThreads>(in, c, &tot, wave_cnt);
-        if (in && r < V) {
+        if constexpr (kRule) {
+            // the rule's scene: the ring rows of the seen frames only (a missed frame's row is stale), this frame's
+            // position from the input as below
+            if (in && r < V) {
+                const uint32_t pm = smask[s];
+                out_ids[r] = key[p];
+                seen[r] = (int32_t)pm;
+                TrackRule::fill(
+                    pm, T_obs, scale,
+                    [&](int t, double &x, double &y) {
+                        if (t == T_obs - 1) {
+                            x = round_pos(det_xy[j * xy_stride], scale);
+                            y = round_pos(det_xy[j * xy_stride + 1], scale);
+                        } else {
+                            const int row = (head + 1 + t) % T_obs;
+                            x = ring[((int64_t)row * S + s) * 2];
+                            y = ring[((int64_t)row * S + s) * 2 + 1];
+                        }
+                    },
+                    [&](int t, double x, double y) {
+                        obs_abs[((int64_t)t * V + r) * 2] = x;
+                        obs_abs[((int64_t)t * V + r) * 2 + 1] = y;
+                    });
+            }
+        } else if (in && r < V) {
             out_ids[r] = key[p];
             for (int t = 0; t < T_obs - 1; ++t) {
                 const int row = (head + 1 + t) % T_obs;           // head - (T_obs - 1 - t) mod T_obs
@@ -278,6 +471,8 @@ __device__ __forceinline__ int track_push_body(const int64_t *__restrict__ det_i
     if (c > V && tid == 0) atomicOr(&flags, kFlagTooMany);
     const int np = c < V ? c : V;
     for (int e = np + tid; e < V; e += nt) out_ids[e] = -1;
+    if constexpr (kRule)
+        for (int e = np + tid; e < V; e += nt) seen[e] = 0;
     for (int e = tid; e < T_obs * (V - np); e += nt) {
         const int t = e / (V - np), r = np + e % (V - np);
         obs_abs[((int64_t)t * V + r) * 2] = 0.0;
@@ -298,25 +493,39 @@ __global__ __launch_bounds__(kPushThreads) void track_push_kernel(
     int M_max, int M2, int64_t *__restrict__ slot_id, uint32_t *__restrict__ mask, double *__restrict__ ring,
     int32_t *__restrict__ head_flags, int S, int T_obs, double scale, int V, double *__restrict__ obs_abs,
     int64_t *__restrict__ out_ids, int32_t *__restrict__ num_peds) {
-    track_push_body<kPushThreads>(det_id, 1, det_xy, 2, det_count[0], M_max, M2, slot_id, mask, ring, head_flags, S,
-                                  T_obs, scale, V, obs_abs, out_ids, num_peds);
+    track_push_body<kPushThreads, false>(det_id, 1, det_xy, 2, det_count[0], M_max, M2, slot_id, mask, ring,
+                                         head_flags, S, T_obs, scale, V, obs_abs, out_ids, num_peds);
+}
+
+__global__ __launch_bounds__(kPushThreads) void track_push_rule_kernel(
+    const int64_t *__restrict__ det_id, const double *__restrict__ det_xy, const int32_t *__restrict__ det_count,
+    int M_max, int M2, int64_t *__restrict__ slot_id, uint32_t *__restrict__ mask, double *__restrict__ ring,
+    int32_t *__restrict__ head_flags, int S, int T_obs, double scale, int V, TrackRule rule,
+    double *__restrict__ obs_abs, int64_t *__restrict__ out_ids, int32_t *__restrict__ num_peds,
+    int32_t *__restrict__ seen) {
+    track_push_body<kPushThreads, true>(det_id, 1, det_xy, 2, det_count[0], M_max, M2, slot_id, mask, ring,
+                                        head_flags, S, T_obs, scale, V, obs_abs, out_ids, num_peds, rule, seen);
 }
 
 // One workgroup per stream: stream b pushes detections det_start[b] .. det_start[b+1]-1 (clamped to [0, M_total))
 // when pushed[b] != 0; otherwise its state is not touched and its scene is the empty one.  Every stream's pointers
 // are its own slices of the (NS, ...) state and output arrays.
-template <int kThreads>
-__global__ __launch_bounds__(kThreads) void track_push_streams_kernel(
+template <int kThreads, bool kRule>
+__device__ __forceinline__ void track_push_stream(
     const int64_t *__restrict__ det_id, int64_t id_stride, const double *__restrict__ det_xy, int64_t xy_stride,
     int M_total, const int32_t *__restrict__ det_start, const int32_t *__restrict__ pushed, int M_max, int M2,
     int64_t *__restrict__ slot_id, uint32_t *__restrict__ mask, double *__restrict__ ring,
     int32_t *__restrict__ head_flags, int S, int T_obs, double scale, int V, double *__restrict__ obs_abs,
-    int64_t *__restrict__ out_ids, int32_t *__restrict__ num_peds, int32_t *__restrict__ out_flags) {
+    int64_t *__restrict__ out_ids, int32_t *__restrict__ num_peds, int32_t *__restrict__ out_flags,
+    TrackRule rule = {}, int32_t *__restrict__ seen = nullptr) {
     const int b = blockIdx.x, tid = threadIdx.x;
     double *obs = obs_abs + (int64_t)b * T_obs * V * 2;
     int64_t *oid = out_ids + (int64_t)b * V;
+    int32_t *osn = kRule ? seen + (int64_t)b * V : nullptr;
     if (pushed[b] == 0) {                                   // uniform over the block: no barrier is skipped halfway
         for (int e = tid; e < V; e += kThreads) oid[e] = -1;
+        if constexpr (kRule)
+            for (int e = tid; e < V; e += kThreads) osn[e] = 0;
         for (int e = tid; e < T_obs * V * 2; e += kThreads) obs[e] = 0.0;
         if (tid == 0) {
             num_peds[b] = 0;
@@ -327,11 +536,44 @@ __global__ __launch_bounds__(kThreads) void track_push_streams_kernel(
     int lo = det_start[b], hi = det_start[b + 1];
     lo = lo < 0 ? 0 : (lo > M_total ? M_total : lo);
     hi = hi < lo ? lo : (hi > M_total ? M_total : hi);
-    const int flags = track_push_body<kThreads>(det_id + lo * id_stride, id_stride, det_xy + lo * xy_stride, xy_stride,
-                                                hi - lo, M_max, M2, slot_id + (int64_t)b * S, mask + (int64_t)b * S,
-                                                ring + (int64_t)b * T_obs * S * 2, head_flags + 2 * b, S, T_obs, scale,
-                                                V, obs, oid, num_peds + b);
+    const int flags = track_push_body<kThreads, kRule>(
+        det_id + lo * id_stride, id_stride, det_xy + lo * xy_stride, xy_stride, hi - lo, M_max, M2,
+        slot_id + (int64_t)b * S, mask + (int64_t)b * S, ring + (int64_t)b * T_obs * S * 2, head_flags + 2 * b, S, T_obs,
+        scale, V, obs, oid, num_peds + b, rule, osn);
     if (out_flags && tid == 0) out_flags[b] = flags;
+}
+
+template <int kThreads>
+__global__ __launch_bounds__(kThreads) void track_push_streams_kernel(
+    const int64_t *__restrict__ det_id, int64_t id_stride, const double *__restrict__ det_xy, int64_t xy_stride,
+    int M_total, const int32_t *__restrict__ det_start, const int32_t *__restrict__ pushed, int M_max, int M2,
+    int64_t *__restrict__ slot_id, uint32_t *__restrict__ mask, double *__restrict__ ring,
+    int32_t *__restrict__ head_flags, int S, int T_obs, double scale, int V, double *__restrict__ obs_abs,
+    int64_t *__restrict__ out_ids, int32_t *__restrict__ num_peds, int32_t *__restrict__ out_flags) {
+    track_push_stream<kThreads, false>(det_id, id_stride, det_xy, xy_stride, M_total, det_start, pushed, M_max, M2,
+                                       slot_id, mask, ring, head_flags, S, T_obs, scale, V, obs_abs, out_ids, num_peds,
+                                       out_flags);
+}
+
+template <int kThreads>
+__global__ __launch_bounds__(kThreads) void track_push_streams_rule_kernel(
+    const int64_t *__restrict__ det_id, int64_t id_stride, const double *__restrict__ det_xy, int64_t xy_stride,
+    int M_total, const int32_t *__restrict__ det_start, const int32_t *__restrict__ pushed, int M_max, int M2,
+    int64_t *__restrict__ slot_id, uint32_t *__restrict__ mask, double *__restrict__ ring,
+    int32_t *__restrict__ head_flags, int S, int T_obs, double scale, int V, TrackRule rule,
+    double *__restrict__ obs_abs, int64_t *__restrict__ out_ids, int32_t *__restrict__ num_peds,
+    int32_t *__restrict__ out_flags, int32_t *__restrict__ seen) {
+    track_push_stream<kThreads, true>(det_id, id_stride, det_xy, xy_stride, M_total, det_start, pushed, M_max, M2,
+                                      slot_id, mask, ring, head_flags, S, T_obs, scale, V, obs_abs, out_ids, num_peds,
+                                      out_flags, rule, seen);
+}
+
+// the launch geometry the strict and the rule pushes share: sort size and dynamic LDS bytes
+static inline size_t push_lds(int M_max, int S, int *m2) {
+    *m2 = 1;
+    while (*m2 < M_max) *m2 <<= 1;
+    return (size_t)*m2 * (sizeof(int64_t) + sizeof(int32_t)) + (size_t)M_max * sizeof(int32_t) +
+           (size_t)S * (sizeof(uint32_t) + sizeof(int32_t));
 }
 
 }  // namespace stg
@@ -372,10 +614,8 @@ int stg_track_push(const int64_t *det_id, const double *det_xy, const int32_t *d
     STG_REQUIRE(det_id && det_xy && det_count && slot_id && mask && ring && head_flags && obs_abs && out_ids &&
                     num_peds,
                 STG_EINVAL, "stg_track_push: null pointer");
-    int m2 = 1;
-    while (m2 < M_max) m2 <<= 1;
-    const size_t lds = (size_t)m2 * (sizeof(int64_t) + sizeof(int32_t)) + (size_t)M_max * sizeof(int32_t) +
-                       (size_t)S * (sizeof(uint32_t) + sizeof(int32_t));
+    int m2;
+    const size_t lds = stg::push_lds(M_max, S, &m2);
     hipLaunchKernelGGL(stg::track_push_kernel, dim3(1), dim3(stg::kPushThreads), lds, stg::as_stream(stream), det_id,
                        det_xy, det_count, M_max, m2, slot_id, mask, ring, head_flags, S, T_obs, scale, V, obs_abs,
                        out_ids, num_peds);
@@ -400,10 +640,8 @@ int stg_track_push_streams(const int64_t *det_id, int64_t id_stride, const doubl
     STG_REQUIRE(det_id && det_xy && det_start && pushed && slot_id && mask && ring && head_flags && obs_abs &&
                     out_ids && num_peds,
                 STG_EINVAL, "stg_track_push_streams: null pointer");
-    int m2 = 1;
-    while (m2 < M_max) m2 <<= 1;
-    const size_t lds = (size_t)m2 * (sizeof(int64_t) + sizeof(int32_t)) + (size_t)M_max * sizeof(int32_t) +
-                       (size_t)S * (sizeof(uint32_t) + sizeof(int32_t));
+    int m2;
+    const size_t lds = stg::push_lds(M_max, S, &m2);
     auto go = [&](auto kernel, int threads) {
         hipLaunchKernelGGL(kernel, dim3(NS), dim3(threads), lds, stg::as_stream(stream), det_id, id_stride, det_xy,
                            xy_stride, M_total, det_start, pushed, M_max, m2, slot_id, mask, ring, head_flags, S, T_obs,
@@ -413,6 +651,104 @@ int stg_track_push_streams(const int64_t *det_id, int64_t id_stride, const doubl
     else if (block_threads == 256) go(stg::track_push_streams_kernel<256>, 256);
     else go(stg::track_push_streams_kernel<1024>, 1024);
     STG_LAUNCH_CHECK("stg_track_push_streams");
+    return STG_OK;
+}
+
+// ---- partially observed tracks: the rule's entry points -------------------------------------------------------------
+#define STG_REQUIRE_RULE(what)                                                                                       \
+    STG_REQUIRE(T_obs >= 2 && T_obs <= 32 && min_seen >= 2 && min_seen <= T_obs && max_gap >= 0 &&                   \
+                    max_gap <= T_obs - 2,                                                                            \
+                STG_EINVAL, what ": min_seen=%d not in [2, T_obs=%d] or max_gap=%d not in [0, T_obs - 2]", min_seen, \
+                T_obs, max_gap)
+
+int stg_fill_tracks(double *obs_abs, const int32_t *seen, const int32_t *num_peds, int N, int T_obs, int V,
+                    double scale, void *stream) {
+    STG_REQUIRE(N >= 0 && V >= 1 && T_obs >= 2 && T_obs <= 32 && (int64_t)N * V < ((int64_t)1 << 31) * 256, STG_EINVAL,
+                "stg_fill_tracks: bad sizes N=%d T_obs=%d V=%d", N, T_obs, V);
+    if (N == 0) return STG_OK;
+    STG_REQUIRE(obs_abs && seen, STG_EINVAL, "stg_fill_tracks: null pointer");
+    const int64_t blocks = ((int64_t)N * V + 255) / 256;
+    hipLaunchKernelGGL(stg::fill_tracks_kernel, dim3((unsigned)blocks), dim3(256), 0, stg::as_stream(stream), obs_abs,
+                       seen, num_peds, N, T_obs, V, scale);
+    STG_LAUNCH_CHECK("stg_fill_tracks");
+    return STG_OK;
+}
+
+int stg_frame_scene_counts_rule(const int32_t *frame_start, const int64_t *ids, int F, int T_obs, int min_seen,
+                                int max_gap, int32_t *count, void *stream) {
+    STG_REQUIRE(F >= 0, STG_EINVAL, "stg_frame_scene_counts_rule: bad size F=%d", F);
+    STG_REQUIRE_RULE("stg_frame_scene_counts_rule");
+    if (F == 0) return STG_OK;
+    STG_REQUIRE(frame_start && ids && count, STG_EINVAL, "stg_frame_scene_counts_rule: null pointer");
+    hipLaunchKernelGGL(stg::frame_scene_counts_rule_kernel, dim3(F), dim3(stg::kWave), 0, stg::as_stream(stream),
+                       frame_start, ids, T_obs, stg::TrackRule{min_seen, max_gap}, count);
+    STG_LAUNCH_CHECK("stg_frame_scene_counts_rule");
+    return STG_OK;
+}
+
+int stg_frame_scenes_rule(const int32_t *frame_start, const int64_t *ids, const double *xy, const int32_t *frames,
+                          int N, int V, int T_obs, double scale, int min_seen, int max_gap, double *obs_abs,
+                          int64_t *out_ids, int32_t *num_peds, int32_t *seen, void *stream) {
+    STG_REQUIRE(N >= 0 && V > 0, STG_EINVAL, "stg_frame_scenes_rule: bad sizes N=%d V=%d", N, V);
+    STG_REQUIRE_RULE("stg_frame_scenes_rule");
+    if (N == 0) return STG_OK;
+    STG_REQUIRE(frame_start && ids && xy && frames && obs_abs && out_ids && num_peds && seen, STG_EINVAL,
+                "stg_frame_scenes_rule: null pointer");
+    hipLaunchKernelGGL(stg::frame_scenes_rule_kernel, dim3(N), dim3(stg::kWave), 0, stg::as_stream(stream), frame_start,
+                       ids, xy, frames, V, T_obs, scale, stg::TrackRule{min_seen, max_gap}, obs_abs, out_ids, num_peds,
+                       seen);
+    STG_LAUNCH_CHECK("stg_frame_scenes_rule");
+    return STG_OK;
+}
+
+int stg_track_push_rule(const int64_t *det_id, const double *det_xy, const int32_t *det_count, int M_max,
+                        int64_t *slot_id, uint32_t *mask, double *ring, int32_t *head_flags, int S, int T_obs,
+                        double scale, int V, int min_seen, int max_gap, double *obs_abs, int64_t *out_ids,
+                        int32_t *num_peds, int32_t *seen, void *stream) {
+    STG_REQUIRE(M_max >= 1 && M_max <= STG_TRACK_MAX_DETECTIONS && S >= 1 && S <= STG_TRACK_MAX_SLOTS && V >= 1,
+                STG_EINVAL, "stg_track_push_rule: bad sizes M_max=%d S=%d V=%d", M_max, S, V);
+    STG_REQUIRE_RULE("stg_track_push_rule");
+    STG_REQUIRE(det_id && det_xy && det_count && slot_id && mask && ring && head_flags && obs_abs && out_ids &&
+                    num_peds && seen,
+                STG_EINVAL, "stg_track_push_rule: null pointer");
+    int m2;
+    const size_t lds = stg::push_lds(M_max, S, &m2);
+    hipLaunchKernelGGL(stg::track_push_rule_kernel, dim3(1), dim3(stg::kPushThreads), lds, stg::as_stream(stream),
+                       det_id, det_xy, det_count, M_max, m2, slot_id, mask, ring, head_flags, S, T_obs, scale, V,
+                       stg::TrackRule{min_seen, max_gap}, obs_abs, out_ids, num_peds, seen);
+    STG_LAUNCH_CHECK("stg_track_push_rule");
+    return STG_OK;
+}
+
+int stg_track_push_streams_rule(const int64_t *det_id, int64_t id_stride, const double *det_xy, int64_t xy_stride,
+                                int M_total, const int32_t *det_start, const int32_t *pushed, int NS, int M_max,
+                                int64_t *slot_id, uint32_t *mask, double *ring, int32_t *head_flags, int S, int T_obs,
+                                double scale, int V, int min_seen, int max_gap, double *obs_abs, int64_t *out_ids,
+                                int32_t *num_peds, int32_t *out_flags, int32_t *seen, int block_threads,
+                                void *stream) {
+    STG_REQUIRE(NS >= 1 && NS <= STG_TRACK_MAX_STREAMS && M_total >= 0 && M_total <= STG_TRACK_MAX_TOTAL_DETECTIONS &&
+                    M_max >= 1 && M_max <= STG_TRACK_MAX_DETECTIONS && S >= 1 && S <= STG_TRACK_MAX_SLOTS && V >= 1 &&
+                    id_stride >= 1 && xy_stride >= 2,
+                STG_EINVAL, "stg_track_push_streams_rule: bad sizes NS=%d M_total=%d M_max=%d S=%d V=%d strides %lld/%lld",
+                NS, M_total, M_max, S, V, (long long)id_stride, (long long)xy_stride);
+    STG_REQUIRE_RULE("stg_track_push_streams_rule");
+    if (block_threads == 0) block_threads = stg::kStreamThreads;
+    STG_REQUIRE(block_threads == 64 || block_threads == 256 || block_threads == 1024, STG_EINVAL,
+                "stg_track_push_streams_rule: block_threads=%d (0, 64, 256 or 1024)", block_threads);
+    STG_REQUIRE(det_id && det_xy && det_start && pushed && slot_id && mask && ring && head_flags && obs_abs &&
+                    out_ids && num_peds && seen,
+                STG_EINVAL, "stg_track_push_streams_rule: null pointer");
+    int m2;
+    const size_t lds = stg::push_lds(M_max, S, &m2);
+    auto go = [&](auto kernel, int threads) {
+        hipLaunchKernelGGL(kernel, dim3(NS), dim3(threads), lds, stg::as_stream(stream), det_id, id_stride, det_xy,
+                           xy_stride, M_total, det_start, pushed, M_max, m2, slot_id, mask, ring, head_flags, S, T_obs,
+                           scale, V, stg::TrackRule{min_seen, max_gap}, obs_abs, out_ids, num_peds, out_flags, seen);
+    };
+    if (block_threads == 64) go(stg::track_push_streams_rule_kernel<64>, 64);
+    else if (block_threads == 256) go(stg::track_push_streams_rule_kernel<256>, 256);
+    else go(stg::track_push_streams_rule_kernel<1024>, 1024);
+    STG_LAUNCH_CHECK("stg_track_push_streams_rule");
     return STG_OK;
 }
 

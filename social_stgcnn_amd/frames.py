@@ -17,6 +17,9 @@ stg_frame_scenes over a recording uploaded once, stg_track_push with the track s
     FramePredictor     push(ids, xy) per frame, eager or as ONE captured graph (capture())
     StreamsPredictor   NS independent live streams: push(tick) per tick, one host->device copy of the packed
                        detections and ONE launch chain (stg_track_push_streams -> the batched forward -> sampler)
+    TrackRule          tracks=TrackRule(min_seen, max_gap) on any of the four: pedestrians with a short history or
+                       tracker gaps are predicted too, their missed frames filled by the kernels
+    fill_tracks        the fill alone, on a batch of scenes in place (stg_fill_tracks)
 
 The two live predictors are one core, _LivePredictor: the argument checks, the track state, the eager push and its
 capture (the push kernel ahead of predict.Predictor.capture_chain; the capture recipe itself is graphs.py).  Each class
@@ -31,7 +34,7 @@ import numpy as np
 import torch
 
 from . import ops
-from ._lib import check, lib, ptr, require_gpu, stream_ptr
+from ._lib import check, lib, peds_arg, ptr, require_gpu, stream_ptr
 from .predict import Prediction, Predictor, _seed_i64, eval_mode
 
 MAX_OBS_LEN = 32                       # presence masks are 32-bit
@@ -46,6 +49,47 @@ DUPLICATE, OVERFLOW, TRUNCATED, TOO_MANY = 1, 2, 4, 8
 FrameScenes = collections.namedtuple("FrameScenes", "frame obs_abs ids num_peds")
 FrameScenes.__doc__ = """frame (N,) float64 numpy: the frame numbers of the scenes; on the device: obs_abs (N,T_obs,V,2)
 float64, ids (N,V) int64 (-1 in padded slots), num_peds (N,) int32.  Padded slots are zeros."""
+
+PartialScenes = collections.namedtuple("PartialScenes", "frame obs_abs ids num_peds seen")
+PartialScenes.__doc__ = """FrameScenes under a TrackRule, and seen (N,V) int32 on the device: bit t set = the pedestrian
+was observed t frames ago (bit 0: this frame), 0 in padded slots.  The steps whose bit is clear are filled."""
+
+
+class TrackRule(collections.namedtuple("TrackRule", "min_seen max_gap")):
+    """Whom a frame scene holds when tracks are partial.  The window of a frame is its last obs_len frames (frames
+    before the first count as missed).  A pedestrian is in the scene iff seen in this frame, seen in at least min_seen
+    frames of the window (2 <= min_seen <= obs_len), and no run of missed frames between two seen ones is longer than
+    max_gap (0 <= max_gap <= obs_len - 2; missed frames ahead of the first seen one are no gap).  Missed frames are
+    filled in float64: between two seen frames by linear interpolation, ahead of the first seen one at the constant
+    velocity of the first two frames of the interpolated window; every filled position is rounded like an observed one.
+    TrackRule(obs_len, 0) is the strict rule.  Scenes start at frame index min_seen - 1."""
+    __slots__ = ()
+
+    def __new__(cls, min_seen, max_gap=0):
+        if not _is_int(min_seen, 2, MAX_OBS_LEN):
+            raise ValueError("TrackRule: min_seen must be an integer in [2, obs_len <= %d], got %r"
+                             % (MAX_OBS_LEN, min_seen))
+        if not _is_int(max_gap, 0, MAX_OBS_LEN - 2):
+            raise ValueError("TrackRule: max_gap must be an integer in [0, obs_len - 2 <= %d], got %r"
+                             % (MAX_OBS_LEN - 2, max_gap))
+        return super().__new__(cls, int(min_seen), int(max_gap))
+
+    def checked(self, obs_len):
+        """The rule, once it fits a window of obs_len frames."""
+        if self.min_seen > obs_len:
+            raise ValueError("TrackRule: min_seen=%d > obs_len=%d" % (self.min_seen, obs_len))
+        if self.max_gap > obs_len - 2:
+            raise ValueError("TrackRule: max_gap=%d > obs_len - 2 = %d (a slot is freed after obs_len - 1 missed "
+                             "frames)" % (self.max_gap, obs_len - 2))
+        return self
+
+
+def _rule(tracks, obs_len):
+    """tracks (None, a TrackRule or a (min_seen, max_gap) pair) -> None or the TrackRule checked against obs_len."""
+    if tracks is None:
+        return None
+    return (tracks if isinstance(tracks, TrackRule) else TrackRule(*tracks)).checked(obs_len)
+
 
 FramePrediction = collections.namedtuple("FramePrediction", "ids num_peds obs_abs samples mean v_pred flags")
 FramePrediction.__doc__ = """One push, on the device: ids (V,) int64 (-1 in padded slots), num_peds (1,) int32,
@@ -109,12 +153,14 @@ def sorted_rows(rows):
     return frames, frame_start, id_s, np.ascontiguousarray(rows[order, 2:4])
 
 
-def recording_scenes(rows, device, obs_len=8, min_peds=1, decimals=4, v_pad=None):
+def recording_scenes(rows, device, obs_len=8, min_peds=1, decimals=4, v_pad=None, tracks=None):
     """The frame scenes of a recording (rows as data.read_file returns them) with at least min_peds pedestrians,
     padded to V = the largest scene (or v_pad, which must hold it).  The rows are uploaded once; two launches
-    (stg_frame_scene_counts, then stg_frame_scenes) and one read-back of the per-frame counts."""
+    (stg_frame_scene_counts, then stg_frame_scenes) and one read-back of the per-frame counts.  tracks: a TrackRule --
+    the scenes under that rule, from frame index min_seen - 1, as PartialScenes (the *_rule kernels)."""
     obs_len = _obs_len(obs_len)
     scale = _scale(decimals)
+    rule = _rule(tracks, obs_len)
     if not _is_int(min_peds, 0):
         raise ValueError("min_peds must be an integer >= 0, got %r" % (min_peds,))
     frames, fs, ids, xy = sorted_rows(rows)
@@ -126,10 +172,15 @@ def recording_scenes(rows, device, obs_len=8, min_peds=1, decimals=4, v_pad=None
     ids_d = torch.from_numpy(ids).to(device)
     xy_d = torch.from_numpy(xy).to(device)
     count = torch.zeros(nf, device=device, dtype=torch.int32)
-    check(lib().stg_frame_scene_counts(ptr(fs_d), ptr(ids_d), nf, obs_len, ptr(count), stream_ptr()),
-          "stg_frame_scene_counts")
+    if rule is None:
+        check(lib().stg_frame_scene_counts(ptr(fs_d), ptr(ids_d), nf, obs_len, ptr(count), stream_ptr()),
+              "stg_frame_scene_counts")
+    else:
+        check(lib().stg_frame_scene_counts_rule(ptr(fs_d), ptr(ids_d), nf, obs_len, rule.min_seen, rule.max_gap,
+                                                ptr(count), stream_ptr()), "stg_frame_scene_counts_rule")
     cnt = count.cpu().numpy()
-    sel = np.nonzero((cnt >= int(min_peds)) & (np.arange(nf) >= obs_len - 1))[0]
+    first = obs_len - 1 if rule is None else rule.min_seen - 1
+    sel = np.nonzero((cnt >= int(min_peds)) & (np.arange(nf) >= first))[0]
     vmax = int(cnt[sel].max()) if len(sel) else 0
     if v_pad is None:
         v = max(1, vmax)
@@ -141,6 +192,14 @@ def recording_scenes(rows, device, obs_len=8, min_peds=1, decimals=4, v_pad=None
     obs = torch.empty((n, obs_len, v, 2), device=device, dtype=torch.float64)
     out_ids = torch.empty((n, v), device=device, dtype=torch.int64)
     peds = torch.empty(n, device=device, dtype=torch.int32)
+    if rule is not None:
+        seen = torch.empty((n, v), device=device, dtype=torch.int32)
+        if n:
+            sel_d = torch.from_numpy(sel.astype(np.int32)).to(device)
+            check(lib().stg_frame_scenes_rule(ptr(fs_d), ptr(ids_d), ptr(xy_d), ptr(sel_d), n, v, obs_len, scale,
+                                              rule.min_seen, rule.max_gap, ptr(obs), ptr(out_ids), ptr(peds),
+                                              ptr(seen), stream_ptr()), "stg_frame_scenes_rule")
+        return PartialScenes(frames[sel], obs, out_ids, peds, seen)
     if n:
         sel_d = torch.from_numpy(sel.astype(np.int32)).to(device)
         check(lib().stg_frame_scenes(ptr(fs_d), ptr(ids_d), ptr(xy_d), ptr(sel_d), n, v, obs_len, scale, ptr(obs),
@@ -148,19 +207,44 @@ def recording_scenes(rows, device, obs_len=8, min_peds=1, decimals=4, v_pad=None
     return FrameScenes(frames[sel], obs, out_ids, peds)
 
 
+def fill_tracks(obs_abs, seen, num_peds=None, decimals=4):
+    """Fill the missed frames of a batch of scenes in place (stg_fill_tracks, one lane per scene and pedestrian) and
+    return it: obs_abs (N,T_obs,V,2) float64 contiguous device tensor, seen (N,V) integers with bit t set = observed t
+    frames ago (bit 0: the last frame), num_peds (N,) or None (every column).  A column's seen frames are rounded to
+    `decimals` and its missed frames filled as under a TrackRule; a column at or past num_peds, not seen in the last
+    frame or seen only once is left untouched."""
+    require_gpu(obs_abs)
+    if obs_abs.dim() != 4 or obs_abs.shape[3] != 2 or obs_abs.dtype != torch.float64 or not obs_abs.is_contiguous():
+        raise ValueError("fill_tracks: obs_abs (N,T_obs,V,2) float64, contiguous, expected, got %s %s"
+                         % (tuple(obs_abs.shape), obs_abs.dtype))
+    n, t, v, _ = obs_abs.shape
+    if not 2 <= t <= MAX_OBS_LEN:
+        raise ValueError("fill_tracks: T_obs must be in [2, %d], got %d" % (MAX_OBS_LEN, t))
+    scale = _scale(decimals)
+    seen = torch.as_tensor(seen).to(device=obs_abs.device, dtype=torch.int32).contiguous()
+    if tuple(seen.shape) != (n, v):
+        raise ValueError("fill_tracks: seen (%d,%d) expected, got %s" % (n, v, tuple(seen.shape)))
+    peds = peds_arg(num_peds, n, obs_abs.device)
+    if n and v:
+        check(lib().stg_fill_tracks(ptr(obs_abs), ptr(seen), ptr(peds), n, t, v, scale, stream_ptr()),
+              "stg_fill_tracks")
+    return obs_abs
+
+
 @torch.no_grad()
 def predict_recording(model, rows, k=20, seed=0, batch_size=64, noise_fn=None, min_peds=1, decimals=4, v_pad=None,
-                      risk=None):
+                      risk=None, tracks=None):
     """Predictions at every frame scene of a recording (recording_scenes with obs_len = model.seq_len): the Predictor
     over batch_size scenes per launch chain, the draws from the Philox stream keyed by seed + batch index, or from
     noise_fn(batch_index, (k,N,P,V,2)) -> standard normals (as predict.sample_test).  Returns (FrameScenes,
     Prediction) with the per-frame predictions concatenated: samples (K,N,P,V,2), mean (N,P,V,2), v_pred (N,5,P,V).
     risk: a predict.RiskSpec (zones (Z,4), the same for every frame) -- the result is then (FrameScenes, Prediction,
-    ops.Risk), the counts of ops.sample_risk over each frame's K samples, concatenated like the predictions."""
+    ops.Risk), the counts of ops.sample_risk over each frame's K samples, concatenated like the predictions.
+    tracks: a TrackRule -- the scenes of recording_scenes(tracks=...), a PartialScenes in the place of FrameScenes."""
     if int(batch_size) < 1:
         raise ValueError("batch_size must be >= 1")
     dev = next(model.parameters()).device
-    scenes = recording_scenes(rows, dev, model.seq_len, min_peds, decimals, v_pad)
+    scenes = recording_scenes(rows, dev, model.seq_len, min_peds, decimals, v_pad, tracks)
     pred = Predictor(model, k, risk)
     if risk is not None and pred.spec.zones is not None and np.ndim(pred.spec.zones) != 2:
         raise ValueError("predict_recording: risk zones (Z,4) expected")
@@ -208,14 +292,15 @@ class _LivePredictor:
     subclass's leading axis), the eager push and its capture as ONE graph.  A subclass supplies
 
         _stage(*det, seed)       copy one push's detections (and the seed, unless None) into its device staging buffers
-        _outs()                  fresh per-push outputs (obs_abs, ids, num_peds, ...)
+        _outs()                  fresh per-push outputs (obs_abs, ids, num_peds, ...; under a TrackRule `seen` last)
         _push(outs)              launch its push kernel: staging buffers + track state -> outs
         _wrap(outs, r, static)   the result tuple of outs and the chain's Prediction r (static: a captured push)
         _still()                 make warm-up pushes harmless; returns the (tensor, saved copy) pairs to put back after
 
     and `seed_dev`, the (1,) int64 device tensor the sampler reads its seed from."""
 
-    def __init__(self, model, k, obs_len, capacity, max_peds, max_detections, decimals, risk=None, keep_samples=True):
+    def __init__(self, model, k, obs_len, capacity, max_peds, max_detections, decimals, risk=None, keep_samples=True,
+                 tracks=None):
         self.model = model
         self.k = int(k)
         self._risk_args = (risk, keep_samples)
@@ -223,6 +308,8 @@ class _LivePredictor:
         if self.t_obs != model.seq_len:
             raise ValueError("obs_len=%d but the model observes %d frames" % (self.t_obs, model.seq_len))
         self.scale = _scale(decimals)
+        self.rule = _rule(tracks, self.t_obs)
+        self.seen = None
         self.s, self.v, self.m_max = int(capacity), int(max_peds), int(max_detections)
         if not 1 <= self.s <= MAX_SLOTS:
             raise ValueError("capacity must be in [1, %d], got %r" % (MAX_SLOTS, capacity))
@@ -250,6 +337,10 @@ class _LivePredictor:
         stream; from a captured push the graph's static tensors.  None without a RiskSpec or before the first push."""
         return self._pred.risk
 
+    def _seen_out(self, *shape):
+        """Under a TrackRule, the push's extra output: the presence bits of every scene slot (kept at `.seen`)."""
+        return () if self.rule is None else (torch.empty(shape, device=self.device, dtype=torch.int32),)
+
     @property
     def zones(self):
         """The device tensor of rectangles the reducer reads ((Z,4), or per stream (NS,Z,4)); a caller may overwrite
@@ -264,6 +355,8 @@ class _LivePredictor:
         self._stage(*det, seed)
         outs = self._outs()
         self._push(outs)
+        if self.rule is not None:
+            self.seen = outs[-1]
         with eval_mode(self.model):
             r = self._pred._forward(outs[0], outs[2], 0, noise, self.seed_dev)
         return self._wrap(outs, r, False)
@@ -289,6 +382,8 @@ class _LivePredictor:
         def replay(*det, seed=None):
             self._stage(*det, seed)
             static[2].replay()
+            if self.rule is not None:
+                self.seen = static[0][-1]
             return res
         return replay
 
@@ -299,11 +394,13 @@ class FramePredictor(_LivePredictor):
     pedestrian, as a FramePrediction.  ids (M,) integral, xy (M,2) positions: host arrays (a repeated id is refused)
     or device tensors (a repeated id: the first detection wins, flag DUPLICATE).  The tracks live on the device
     (stg_track_push): `capacity` slots, a slot freed once its pedestrian has been missing for obs_len - 1 frames.  Ids
-    come from the caller's tracker (association is not done here)."""
+    come from the caller's tracker (association is not done here).  tracks: a TrackRule -- the scene holds the
+    pedestrians that rule admits, their missed frames filled (stg_track_push_rule); `.seen` (V,) int32 then holds the
+    presence bits of the last push's scene slots (from a captured push the graph's static buffer, like `.risk`)."""
 
     def __init__(self, model, k=20, obs_len=8, capacity=1024, max_peds=128, max_detections=1024, decimals=4,
-                 risk=None, keep_samples=True):
-        super().__init__(model, k, obs_len, capacity, max_peds, max_detections, decimals, risk, keep_samples)
+                 risk=None, keep_samples=True, tracks=None):
+        super().__init__(model, k, obs_len, capacity, max_peds, max_detections, decimals, risk, keep_samples, tracks)
         dev, m = self._track_state(), self.m_max
         self.det_id = torch.zeros(m, device=dev, dtype=torch.int64)
         self.det_xy = torch.zeros((m, 2), device=dev, dtype=torch.float64)
@@ -340,17 +437,25 @@ class FramePredictor(_LivePredictor):
     def _outs(self):
         dev, t, v = self.device, self.t_obs, self.v
         return (torch.empty((1, t, v, 2), device=dev, dtype=torch.float64),
-                torch.empty(v, device=dev, dtype=torch.int64), torch.empty(1, device=dev, dtype=torch.int32))
+                torch.empty(v, device=dev, dtype=torch.int64),
+                torch.empty(1, device=dev, dtype=torch.int32)) + self._seen_out(v)
 
     def _push(self, outs):
-        obs, ids, peds = outs
+        obs, ids, peds = outs[:3]
+        if self.rule is not None:
+            check(lib().stg_track_push_rule(ptr(self.det_id), ptr(self.det_xy), ptr(self.det_count), self.m_max,
+                                            ptr(self.slot_id), ptr(self.mask), ptr(self.ring), ptr(self.head_flags),
+                                            self.s, self.t_obs, ctypes.c_double(self.scale), self.v, self.rule.min_seen,
+                                            self.rule.max_gap, ptr(obs), ptr(ids), ptr(peds), ptr(outs[3]),
+                                            stream_ptr()), "stg_track_push_rule")
+            return
         check(lib().stg_track_push(ptr(self.det_id), ptr(self.det_xy), ptr(self.det_count), self.m_max,
                                    ptr(self.slot_id), ptr(self.mask), ptr(self.ring), ptr(self.head_flags), self.s,
                                    self.t_obs, ctypes.c_double(self.scale), self.v, ptr(obs), ptr(ids), ptr(peds),
                                    stream_ptr()), "stg_track_push")
 
     def _wrap(self, outs, r, static):
-        obs, ids, peds = outs
+        obs, ids, peds = outs[:3]
         flags = self.head_flags[1:]          # (a captured push returns the state's own flags word)
         return FramePrediction(ids, peds, obs, r.samples[:, 0], r.mean[0], r.v_pred[0],
                                flags if static else flags.clone())
@@ -460,11 +565,13 @@ class StreamsPredictor(_LivePredictor):
     what a lone FramePredictor with the same seed draws.  The seed lives in the staging block.
     max_total_detections (default streams * max_detections) sizes the staging buffers.  risk (a predict.RiskSpec, its
     zones (Z,4) for every stream or (NS,Z,4) per stream) and keep_samples as in predict.Predictor: the tick's counts are
-    at `.risk`, 5.4 MB of int32 counts at 600 streams padded to 128 pedestrians, where the samples are 147 MB."""
+    at `.risk`, 5.4 MB of int32 counts at 600 streams padded to 128 pedestrians, where the samples are 147 MB.
+    tracks: a TrackRule for every stream, as in FramePredictor (stg_track_push_streams_rule); `.seen` is (NS,V), zero
+    for a stream not pushed."""
 
     def __init__(self, model, streams, k=20, obs_len=8, capacity=1024, max_peds=128, max_detections=1024, decimals=4,
-                 max_total_detections=None, block_threads=0, risk=None, keep_samples=True):
-        super().__init__(model, k, obs_len, capacity, max_peds, max_detections, decimals, risk, keep_samples)
+                 max_total_detections=None, block_threads=0, risk=None, keep_samples=True, tracks=None):
+        super().__init__(model, k, obs_len, capacity, max_peds, max_detections, decimals, risk, keep_samples, tracks)
         if not _is_int(streams, 1, MAX_STREAMS):
             raise ValueError("streams must be an integer in [1, %d], got %r" % (MAX_STREAMS, streams))
         self.ns = int(streams)
@@ -593,20 +700,29 @@ class StreamsPredictor(_LivePredictor):
         dev, ns, t, v = self.device, self.ns, self.t_obs, self.v
         return (torch.empty((ns, t, v, 2), device=dev, dtype=torch.float64),
                 torch.empty((ns, v), device=dev, dtype=torch.int64), torch.empty(ns, device=dev, dtype=torch.int32),
-                torch.empty(ns, device=dev, dtype=torch.int32), torch.empty(ns, device=dev, dtype=torch.bool))
+                torch.empty(ns, device=dev, dtype=torch.int32),
+                torch.empty(ns, device=dev, dtype=torch.bool)) + self._seen_out(ns, v)
 
     def _push(self, outs):
-        obs, ids, peds, flags, pushed = outs
-        check(lib().stg_track_push_streams(ptr(self._rec_i), 3, ctypes.c_void_p(self._rec_f.data_ptr() + 8), 3,
-                                           self.cap, ptr(self.det_start), ptr(self.pushed_dev), self.ns, self.m_max,
-                                           ptr(self.slot_id), ptr(self.mask), ptr(self.ring), ptr(self.head_flags),
-                                           self.s, self.t_obs, ctypes.c_double(self.scale), self.v, ptr(obs), ptr(ids),
-                                           ptr(peds), ptr(flags), self.block_threads, stream_ptr()),
-              "stg_track_push_streams")
+        obs, ids, peds, flags, pushed = outs[:5]
+        if self.rule is None:
+            check(lib().stg_track_push_streams(ptr(self._rec_i), 3, ctypes.c_void_p(self._rec_f.data_ptr() + 8), 3,
+                                               self.cap, ptr(self.det_start), ptr(self.pushed_dev), self.ns, self.m_max,
+                                               ptr(self.slot_id), ptr(self.mask), ptr(self.ring), ptr(self.head_flags),
+                                               self.s, self.t_obs, ctypes.c_double(self.scale), self.v, ptr(obs), ptr(ids),
+                                               ptr(peds), ptr(flags), self.block_threads, stream_ptr()),
+                  "stg_track_push_streams")
+        else:
+            check(lib().stg_track_push_streams_rule(
+                ptr(self._rec_i), 3, ctypes.c_void_p(self._rec_f.data_ptr() + 8), 3, self.cap, ptr(self.det_start),
+                ptr(self.pushed_dev), self.ns, self.m_max, ptr(self.slot_id), ptr(self.mask), ptr(self.ring),
+                ptr(self.head_flags), self.s, self.t_obs, ctypes.c_double(self.scale), self.v, self.rule.min_seen,
+                self.rule.max_gap, ptr(obs), ptr(ids), ptr(peds), ptr(flags), ptr(outs[5]), self.block_threads,
+                stream_ptr()), "stg_track_push_streams_rule")
         torch.ne(self.pushed_dev, 0, out=pushed)
 
     def _wrap(self, outs, r, static):
-        obs, ids, peds, flags, pushed = outs
+        obs, ids, peds, flags, pushed = outs[:5]
         return StreamsPrediction(ids, peds, obs, r.samples, r.mean, r.v_pred, flags, pushed)
 
     def _still(self):

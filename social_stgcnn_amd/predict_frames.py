@@ -3,7 +3,8 @@ trajectories for every pedestrian tracked over the last obs_seq_len frames.
 
     python -m social_stgcnn_amd.predict_frames --checkpoint DIR --recording FILE [--ksteps 20] [--seed 0]
                                                [--min_peds 1] [--delim tab] [--radius R]
-                                               [--zones x0,y0,x1,y1 ...] --out preds.npz
+                                               [--zones x0,y0,x1,y1 ...] [--min_seen M] [--max_gap G]
+                                               --out preds.npz
 
 DIR is a checkpoint directory in the reference's layout (args.pkl and val_best.pth, as social_stgcnn_amd.test reads
 it); FILE a recording in the ETH/UCY text format (<frame> <ped> <x> <y>).  The .npz holds, one entry per frame scene:
@@ -12,6 +13,11 @@ trajectories and samples (K,N,P,V,2), float32, zeros in padded slots.  With --ra
 the counts of ops.sample_risk over each frame's K samples, aligned with the frames: risk_k, and risk_conflict (N,P,V),
 risk_conflict_any (N,V), risk_partner (N,V), risk_pair (N,V,V) for a radius, risk_zones (Z,4), risk_zone_any (N,P,Z),
 risk_zone_count (N,P,Z), risk_ped_zone (N,V,Z) for zones.
+
+--min_seen M and / or --max_gap G predict partially observed tracks too (frames.TrackRule; the other one defaults to
+obs_seq_len / 0): a pedestrian seen now, in at least M of the last obs_seq_len frames and with no run of more than G
+missed frames between two seen ones; the missed frames are filled.  The .npz then also holds seen (N,V) int32: bit t set
+= observed t frames ago, so a caller can tell a filled history from an observed one.
 """
 import argparse
 import os
@@ -21,7 +27,7 @@ import numpy as np
 import torch
 
 from . import data
-from .frames import predict_recording
+from .frames import TrackRule, predict_recording
 from .model import social_stgcnn
 from .predict import RiskSpec
 from .trainer import load_checkpoint, load_pickle
@@ -39,6 +45,10 @@ def build_parser():
                    help="also count the samples in which two pedestrians come closer than this (risk_* arrays)")
     p.add_argument("--zones", nargs="+", default=None, metavar="x0,y0,x1,y1",
                    help="also count the samples in which each rectangle is occupied (risk_* arrays)")
+    p.add_argument("--min_seen", type=int, default=None,
+                   help="predict a pedestrian seen in at least this many of the last obs_seq_len frames (seen array)")
+    p.add_argument("--max_gap", type=int, default=None,
+                   help="... with at most this many missed frames in a row between two seen ones (seen array)")
     p.add_argument("--out", required=True, help="output .npz")
     # a rectangle may begin with a negative coordinate: "-1,-1,1,1" is a value, not an option
     p._negative_number_matcher = re.compile(r"^-[0-9.][0-9.,eE+-]*$")
@@ -71,16 +81,21 @@ def main(argv=None):
     model = load_model(a.checkpoint, torch.device("cuda", torch.cuda.current_device()))
     rows = data.read_file(a.recording, a.delim)
     extra = {}
+    tracks = None
+    if a.min_seen is not None or a.max_gap is not None:
+        tracks = TrackRule(model.seq_len if a.min_seen is None else a.min_seen, 0 if a.max_gap is None else a.max_gap)
     if a.radius is None and a.zones is None:
-        scenes, pred = predict_recording(model, rows, k=a.ksteps, seed=a.seed, min_peds=a.min_peds)
+        scenes, pred = predict_recording(model, rows, k=a.ksteps, seed=a.seed, min_peds=a.min_peds, tracks=tracks)
     else:
         zones = parse_zones(a.zones) if a.zones is not None else None
         scenes, pred, risk = predict_recording(model, rows, k=a.ksteps, seed=a.seed, min_peds=a.min_peds,
-                                               risk=RiskSpec(a.radius, zones, a.radius is not None))
+                                               risk=RiskSpec(a.radius, zones, a.radius is not None), tracks=tracks)
         extra = {"risk_" + f: x.cpu().numpy() for f, x in zip(risk._fields[1:], risk[1:]) if x is not None}
         extra["risk_k"] = np.int32(risk.k)
         if zones is not None:
             extra["risk_zones"] = zones
+    if tracks is not None:
+        extra["seen"] = scenes.seen.cpu().numpy()
     np.savez(a.out, frame=scenes.frame, ids=scenes.ids.cpu().numpy(), num_peds=scenes.num_peds.cpu().numpy(),
              mean=pred.mean.cpu().numpy(), samples=pred.samples.cpu().numpy(), **extra)
     print("%d frame scenes, up to %d pedestrians -> %s" % (len(scenes.frame), scenes.ids.shape[1], a.out))

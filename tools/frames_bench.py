@@ -4,6 +4,7 @@
     python tools/frames_bench.py [--pushes 2000] [--cases latency,recording] [--k 20]
     python tools/frames_bench.py --cases streams [--streams 1,8,64,256,600] [--ticks 200] [--block 0] [--no-lone]
                                  [--risk none,samples,lean]
+    python tools/frames_bench.py --tracks 2,2 ...       every case under frames.TrackRule(2, 2) (the *_rule kernels)
 
   latency    the captured FramePredictor (ONE graph: stg_track_push -> observed_inputs -> forward -> sampler) pushed
              every frame of a recording in a loop, --pushes timed pushes after a warm-up.  Host clock around staging +
@@ -59,10 +60,16 @@ def pushes_of(rows):
             for a, b in zip(bounds[:-1], bounds[1:])]
 
 
-def latency_case(split, rec, max_peds, k, n_push, dev, warmup=50):
+def tracks_kw(tracks):
+    """--tracks M,G -> the keyword of the predictors (nothing without the flag: the strict calls)."""
+    from social_stgcnn_amd import frames
+    return {} if tracks is None else {"tracks": frames.TrackRule(*tracks)}
+
+
+def latency_case(split, rec, max_peds, k, n_push, dev, warmup=50, tracks=None):
     from social_stgcnn_amd import data, frames
     pushes = pushes_of(data.read_file(os.path.join(DATA, rec)))
-    fp = frames.FramePredictor(model_for(split, dev), k=k, max_peds=max_peds)
+    fp = frames.FramePredictor(model_for(split, dev), k=k, max_peds=max_peds, **tracks_kw(tracks))
     push = fp.capture()
     times, peds = [], []
     for i in range(warmup + n_push):
@@ -80,22 +87,25 @@ def latency_case(split, rec, max_peds, k, n_push, dev, warmup=50):
     return {"case": "latency", "recording": os.path.basename(rec), "max_peds": max_peds, "k": k, "pushes": n_push,
             "p50_ms": round(float(np.percentile(ms, 50)), 4), "p90_ms": round(float(np.percentile(ms, 90)), 4),
             "mean_ms": round(float(ms.mean()), 4), "frames_per_s_p50": round(1e3 / float(np.percentile(ms, 50)), 1),
-            "mean_peds": round(float(peds.mean()), 2), "max_peds_seen": int(peds.max())}
+            "mean_peds": round(float(peds.mean()), 2), "max_peds_seen": int(peds.max()),
+            **({} if tracks is None else {"tracks": list(tracks)})}
 
 
-def recording_case(split, rec, k, dev):
+def recording_case(split, rec, k, dev, tracks=None):
     from social_stgcnn_amd import data, frames
     rows = data.read_file(os.path.join(DATA, rec))
     model = model_for(split, dev)
-    frames.predict_recording(model, rows, k=k)
+    frames.predict_recording(model, rows, k=k, **tracks_kw(tracks))
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    sc, _ = frames.predict_recording(model, rows, k=k)
+    sc, _ = frames.predict_recording(model, rows, k=k, **tracks_kw(tracks))
     torch.cuda.synchronize()
     secs = time.perf_counter() - t0
     n = len(sc.frame)
     return {"case": "recording", "recording": os.path.basename(rec), "k": k, "frame_scenes": n,
-            "v": int(sc.ids.shape[1]), "seconds": round(secs, 4), "frames_per_s": round(n / secs, 1)}
+            "v": int(sc.ids.shape[1]), "seconds": round(secs, 4), "frames_per_s": round(n / secs, 1),
+            "mean_peds": round(float(sc.num_peds.float().mean()), 2),
+            **({} if tracks is None else {"tracks": list(tracks)})}
 
 
 def _stream_sequences(ns, n):
@@ -110,7 +120,7 @@ def _stream_sequences(ns, n):
     return out
 
 
-def streams_case(ns, k, n_ticks, dev, block=0, lone=True, max_peds=128, warmup=20, risk="none"):
+def streams_case(ns, k, n_ticks, dev, block=0, lone=True, max_peds=128, warmup=20, risk="none", tracks=None):
     from social_stgcnn_amd import frames
     model = model_for("univ", dev)
     seq = _stream_sequences(ns, warmup + n_ticks)
@@ -119,6 +129,7 @@ def streams_case(ns, k, n_ticks, dev, block=0, lone=True, max_peds=128, warmup=2
         from social_stgcnn_amd.predict import RiskSpec
         kw = dict(risk=RiskSpec(0.5, np.array([[-1, -1, 1, 1], [0, 0, 4, 3], [-50, -50, 50, 50]], np.float32)),
                   keep_samples=risk == "samples")
+    kw.update(tracks_kw(tracks))
     sp = frames.StreamsPredictor(model, ns, k=k, max_peds=max_peds, block_threads=block, **kw)
     replay = sp.capture()
     times, peds = [], []
@@ -137,6 +148,8 @@ def streams_case(ns, k, n_ticks, dev, block=0, lone=True, max_peds=128, warmup=2
            "ticks": n_ticks, "tick_p50_ms": round(p50, 4), "tick_p90_ms": round(float(np.percentile(ms, 90)), 4),
            "frames_per_s_p50": round(ns * 1e3 / p50, 1), "mean_peds": round(float(peds.mean()), 2),
            "max_peds_seen": int(peds.max())}
+    if tracks is not None:
+        res["tracks"] = list(tracks)
     if risk != "none":
         res["risk"] = risk
         res["conflict_any_mean"] = round(float(sp.risk.conflict_any.float().mean()), 3)
@@ -145,7 +158,7 @@ def streams_case(ns, k, n_ticks, dev, block=0, lone=True, max_peds=128, warmup=2
     if lone:
         # the yardstick: NS lone captured FramePredictors, one after another; fewer ticks at large NS
         n_seq = max(10, min(n_ticks, 4000 // ns))
-        fps = [frames.FramePredictor(model, k=k, max_peds=max_peds) for _ in range(ns)]
+        fps = [frames.FramePredictor(model, k=k, max_peds=max_peds, **tracks_kw(tracks)) for _ in range(ns)]
         pushes = [fp.capture() for fp in fps]
         times = []
         for t in range(warmup + n_seq):
@@ -177,7 +190,10 @@ def main():
     ap.add_argument("--block", default="0", help="push workgroup size(s) of the streams case, comma separated")
     ap.add_argument("--no-lone", action="store_true")
     ap.add_argument("--risk", default="none", help="modes of the streams case, comma separated: none, samples, lean")
+    ap.add_argument("--tracks", default=None, metavar="M,G",
+                    help="run every case under frames.TrackRule(min_seen=M, max_gap=G); default: the strict rule")
     a = ap.parse_args()
+    tracks = None if a.tracks is None else tuple(int(x) for x in a.tracks.split(","))
     if not torch.cuda.is_available():
         raise SystemExit("frames_bench needs a GPU (MI355X)")
     dev = torch.device("cuda", 0)
@@ -185,15 +201,16 @@ def main():
     if "latency" in cases:
         for split, rec, v in (("eth", "eth_test/biwi_eth.txt", 32), ("eth", "eth_test/biwi_eth.txt", 128),
                               ("univ", "univ_test/students001.txt", 128)):
-            print(json.dumps(latency_case(split, rec, v, a.k, a.pushes, dev)), flush=True)
+            print(json.dumps(latency_case(split, rec, v, a.k, a.pushes, dev, tracks=tracks)), flush=True)
     if "recording" in cases:
         for split, rec in TEST_RECORDINGS:
-            print(json.dumps(recording_case(split, rec, a.k, dev)), flush=True)
+            print(json.dumps(recording_case(split, rec, a.k, dev, tracks)), flush=True)
     if "streams" in cases:
         for block in (int(b) for b in a.block.split(",")):
             for ns in (int(n) for n in a.streams.split(",")):
                 for mode in a.risk.split(","):
-                    print(json.dumps(streams_case(ns, a.k, a.ticks, dev, block, not a.no_lone, risk=mode)),
+                    print(json.dumps(streams_case(ns, a.k, a.ticks, dev, block, not a.no_lone, risk=mode,
+                                                  tracks=tracks)),
                           flush=True)
 
 
