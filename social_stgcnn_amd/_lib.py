@@ -206,6 +206,17 @@ def require_gpu(*tensors):
                                % t.device.type)
 
 
+def seed_u64(seed):
+    """A Python integer seed as the uint64 the C ABI takes (its low 64 bits)."""
+    return int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
+def seed_i64(seed):
+    """The same 64 bits as the int64 a `seed_dev` device tensor holds."""
+    s = seed_u64(seed)
+    return s - (1 << 64) if s >= 1 << 63 else s
+
+
 def as_f32(t, what):
     if t.dtype != torch.float32:
         raise TypeError("%s must be float32 (got %s)" % (what, t.dtype))

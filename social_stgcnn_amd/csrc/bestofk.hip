@@ -9,7 +9,7 @@
 // re-reads) + the optional noise tensor.  Noise: either caller-provided standard normals (exact parity with a
 // CPU sampler fed the same numbers) or an in-kernel Philox4x32-10 stream keyed by (seed; scene, ped, k, t).
 #include "common.hpp"
-#include "philox.hpp"
+#include "sample_draw.hpp"
 
 namespace stg {
 
@@ -42,19 +42,15 @@ __global__ __launch_bounds__(256) void bestofk_kernel(
         for (int t = 0; t < P; ++t) {
             const float *q = pn + t * p_sp;
             const float mx = q[0], my = q[p_sf];
-            const float sx = expf(q[2 * p_sf]), sy = expf(q[3 * p_sf]), rho = tanhf(q[4 * p_sf]);
-            // chol([[sx^2, rho sx sy], [rho sx sy, sy^2]]) in the order torch.linalg.cholesky evaluates it
-            const float c01 = rho * sx * sy;
-            const float l00 = sqrtf(sx * sx);
-            const float l10 = c01 / l00;
-            const float l11 = sqrtf(sy * sy - l10 * l10);
+            // (draw_chol(q, p_sf) with its arguments evaluated here: inside the helper the compiler moves the two expf
+            // behind tanhf's branch and away from their loads, measured +1.2 % on this kernel's time)
+            const Chol2 l = draw_chol(expf(q[2 * p_sf]), expf(q[3 * p_sf]), tanhf(q[4 * p_sf]));
             float2 e;
             if (noise)
                 e = *reinterpret_cast<const float2 *>(noise + ((((int64_t)k * N + n) * P + t) * V + v) * 2);
             else
-                e = philox_normal2(seed, (uint64_t)idx, (uint32_t)(k * P + t));
-            cx += mx + l00 * e.x;                       // cumulative sum of sampled displacements (metrics.py:70-73)
-            cy += my + (l10 * e.x + l11 * e.y);
+                e = draw_normal2(seed, idx, k, P, t);   // idx = n * V + v
+            draw_step(cx, cy, mx, my, l, e);            // cumulative sum of sampled displacements (metrics.py:70-73)
             const float2 tg = *reinterpret_cast<const float2 *>(tn + (int64_t)t * V * 2);
             gx += tg.x;
             gy += tg.y;

@@ -26,6 +26,8 @@ int hip_fail(hipError_t e, const char *what);
     } while (0)
 
 static inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
+// p is a multiple of `bytes` (a power of two); NULL is
+static inline bool aligned(const void *p, uintptr_t bytes) { return ((uintptr_t)p & (bytes - 1)) == 0; }
 
 // One kernel launch with dynamic LDS: raise the kernel's hipFuncAttributeMaxDynamicSharedMemorySize to `lds` (only
 // when lds > raise_above: 0 = always; a site that stays under the runtime's own limit on most batches names that limit

@@ -1,7 +1,6 @@
-// The in-kernel standard-normal stream shared by stg_bestofk_eval and stg_sample_trajectories: Philox4x32-10 keyed by
-// the 64-bit seed, counter (lane, draw, 0, 'STGN'), two uniforms -> Box-Muller.  Both kernels use lane = scene * V + ped
-// (V = the padded width) and draw = k * P + t, so a sample of one is the sample of the other.  tests/philox_np.py is
-// the host replay of this stream.
+// The in-kernel standard-normal stream of the sampling kernels: Philox4x32-10 keyed by the 64-bit seed, counter
+// (lane, draw, 0, 'STGN'), two uniforms -> Box-Muller.  Which lane and draw a sample takes is sample_draw.hpp's
+// business.  tests/philox_np.py is the host replay of this stream.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

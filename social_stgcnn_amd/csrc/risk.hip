@@ -5,10 +5,10 @@
 //
 // The work is not a stream: K * P * vi^2 / 2 distance tests per scene (1.95 M at vi = 128) on top of the sampler's
 // draws.  One workgroup per scene, the K samples in passes of kb:
-//   draw    lane = (kk, pedestrian): all P steps of one sample into the LDS image img[kk][t][v] (sample_traj_kernel's
-//           draw, term for term: same Philox counter, same Cholesky expression order).  The image is carved for kb
-//           samples of V pedestrians and laid out with the scene's own width vi, so a scene of few pedestrians takes
-//           more samples per pass (kb * V / vi, up to K): the draw is the long serial part, and it needs lanes
+//   draw    lane = (kk, pedestrian): all P steps of one sample into the LDS image img[kk][t][v] (sample_draw.hpp's
+//           draw, as in sample_traj_kernel).  The image is carved for kb samples of V pedestrians and laid out with
+//           the scene's own width vi, so a scene of few pedestrians takes more samples per pass (kb * V / vi, up to
+//           K): the draw is the long serial part, and it needs lanes
 //   pairs   lane = unordered pair, enumerated by offset: item -> (d, i), j = (i + d) mod vi, d = 1 .. (vi-1)/2 for
 //           every i, and d = vi/2 for i < vi/2 when vi is even -- every pair once, no idle half, and the lanes of a wave
 //           read consecutive i and consecutive j (conflict-free 8-byte LDS reads).  A lane owns the same items in every
@@ -17,7 +17,7 @@
 //   zones   lane = (kk, t, z) over the pedestrians and lane = (kk, v, z) over the steps, LDS integer atomics
 // and at the end the accumulators go out with plain vector stores; partner is a row scan of the pair counts.
 #include "common.hpp"
-#include "philox.hpp"
+#include "sample_draw.hpp"
 
 namespace stg {
 
@@ -157,19 +157,13 @@ __global__ __launch_bounds__(1024) void sample_risk_kernel(const RiskArgs a) {
             for (int t = 0; t < P; ++t) {
                 const float *q = a.pred + n * a.p_sn + v * a.p_sv + t * a.p_sp;
                 const float mx = q[0], my = q[a.p_sf];
-                const float sx = expf(q[2 * a.p_sf]), sy = expf(q[3 * a.p_sf]), rho = tanhf(q[4 * a.p_sf]);
-                // sample_traj_kernel's arithmetic, term for term
-                const float c01 = rho * sx * sy;
-                const float l00 = sqrtf(sx * sx);
-                const float l10 = c01 / l00;
-                const float l11 = sqrtf(sy * sy - l10 * l10);
+                const Chol2 l = draw_chol(q, a.p_sf);
                 float2 e;
                 if (nrow)
                     e = *reinterpret_cast<const float2 *>(nrow + (int64_t)t * V * 2);
                 else
-                    e = philox_normal2(seed, (uint64_t)((int64_t)n * V + v), (uint32_t)(k * P + t));
-                cx += mx + l00 * e.x;
-                cy += my + (l10 * e.x + l11 * e.y);
+                    e = draw_normal2(seed, n, V, v, k, P, t);
+                draw_step(cx, cy, mx, my, l, e);
                 img[(kk * P + t) * vs + v] = make_float2(cx + ox, cy + oy);
             }
         }
@@ -303,8 +297,7 @@ int stg_sample_risk(const float *pred, int64_t p_sn, int64_t p_sf, int64_t p_sp,
                 "stg_sample_risk: null pointer (conflict / conflict_any / partner with radius > 0)");
     STG_REQUIRE(Z == 0 || (zones && zone_any && zone_count && ped_zone), STG_EINVAL,
                 "stg_sample_risk: null pointer (zones / zone_any / zone_count / ped_zone with Z=%d)", Z);
-    auto al = [](const void *p, uintptr_t x) { return ((uintptr_t)p & (x - 1)) == 0; };
-    STG_REQUIRE(al(noise, 8) && al(obs_last, 8), STG_EINVAL,
+    STG_REQUIRE(stg::aligned(noise, 8) && stg::aligned(obs_last, 8), STG_EINVAL,
                 "stg_sample_risk: noise / obs_last must be 8-byte aligned");
     STG_REQUIRE(V <= STG_RISK_MAX_V, STG_EUNSUPPORTED, "stg_sample_risk: V=%d above STG_RISK_MAX_V=%d", V,
                 STG_RISK_MAX_V);

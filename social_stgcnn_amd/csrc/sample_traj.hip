@@ -6,11 +6,10 @@
 // A write-bound stream (K x N x P x V x 2 floats out against N x 5 x P x V in, re-read K times from L2 / MALL), so the
 // mapping is chosen for stores and parallelism: one lane per (k, scene, pedestrian group of PEDS), pedestrians
 // fastest, k slowest.  Each time step a lane stores its PEDS x 2 floats of the row samples[k, n, t, :, :] (one float4
-// for a pair), so a wave's store covers whole 128-byte lines of consecutive rows.  The draws and the Cholesky
-// arithmetic are bestofk_kernel's: same Philox counter (scene * V + ped, k * P + t), same expression order, so
-// best-of-K over `samples` is what stg_bestofk_eval reports for the same seed.
+// for a pair), so a wave's store covers whole 128-byte lines of consecutive rows.  The draw is sample_draw.hpp's, as
+// in bestofk_kernel, so best-of-K over `samples` is what stg_bestofk_eval reports for the same seed.
 #include "common.hpp"
-#include "philox.hpp"
+#include "sample_draw.hpp"
 
 #include <type_traits>
 
@@ -61,20 +60,13 @@ __global__ __launch_bounds__(256) void sample_traj_kernel(
             const float *q = pred + n * p_sn + v * p_sv + t * p_sp;
             const float mx = q[0], my = q[p_sf];
             if (do_samp) {
-                const float sx = expf(q[2 * p_sf]), sy = expf(q[3 * p_sf]), rho = tanhf(q[4 * p_sf]);
-                // chol([[sx^2, rho sx sy], [rho sx sy, sy^2]]) in the order torch.linalg.cholesky evaluates it
-                // (bestofk_kernel's arithmetic, term for term)
-                const float c01 = rho * sx * sy;
-                const float l00 = sqrtf(sx * sx);
-                const float l10 = c01 / l00;
-                const float l11 = sqrtf(sy * sy - l10 * l10);
+                const Chol2 l = draw_chol(q, p_sf);
                 float2 e;
                 if (noise)
                     e = make_float2(e_in[2 * j], e_in[2 * j + 1]);
                 else
-                    e = philox_normal2(seed, (uint64_t)((int64_t)n * V + v), (uint32_t)(k * P + t));
-                cx[j] += mx + l00 * e.x;
-                cy[j] += my + (l10 * e.x + l11 * e.y);
+                    e = draw_normal2(seed, n, V, v, k, P, t);
+                draw_step(cx[j], cy[j], mx, my, l, e);
                 s_out[2 * j] = cx[j] + ox[j];
                 s_out[2 * j + 1] = cy[j] + oy[j];
             }
@@ -104,11 +96,11 @@ int stg_sample_trajectories(const float *pred, int64_t p_sn, int64_t p_sf, int64
     STG_REQUIRE(pred, STG_EINVAL, "stg_sample_trajectories: null pointer (pred)");
     STG_REQUIRE(samples || K == 0, STG_EINVAL, "stg_sample_trajectories: null pointer (samples with K=%d)", K);
     STG_REQUIRE(samples || mean, STG_EINVAL, "stg_sample_trajectories: null pointer (no output)");
-    auto al = [](const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; };
-    STG_REQUIRE(al(samples, 8) && al(mean, 8) && al(noise, 8) && al(obs_last, 8), STG_EINVAL,
+    using stg::aligned;
+    STG_REQUIRE(aligned(samples, 8) && aligned(mean, 8) && aligned(noise, 8) && aligned(obs_last, 8), STG_EINVAL,
                 "stg_sample_trajectories: samples / mean / noise / obs_last must be 8-byte aligned");
     // a pair of pedestrians per lane (float4 stores) when the rows split into aligned pairs, else one (float2)
-    int peds = (V % 2 == 0 && al(samples, 16) && al(mean, 16) && al(noise, 16)) ? 2 : 1;
+    int peds = (V % 2 == 0 && aligned(samples, 16) && aligned(mean, 16) && aligned(noise, 16)) ? 2 : 1;
     if (stg::diag_env("STG_SAMPLE_PEDS", 2) == 1) peds = 1;            // A/B switch of the diagnostic build only
     const int64_t total = (int64_t)(K > 0 ? K : 1) * N * (V / peds);
     STG_REQUIRE(total < (1ll << 31) * 256, STG_EINVAL, "stg_sample_trajectories: K*N*V too large");

@@ -34,8 +34,8 @@ import numpy as np
 import torch
 
 from . import ops
-from ._lib import check, lib, peds_arg, ptr, require_gpu, stream_ptr
-from .predict import Prediction, Predictor, _seed_i64, eval_mode
+from ._lib import check, lib, peds_arg, ptr, require_gpu, seed_i64, stream_ptr
+from .predict import Prediction, Predictor, eval_mode
 
 MAX_OBS_LEN = 32                       # presence masks are 32-bit
 MAX_DETECTIONS = 2048                  # STG_TRACK_MAX_DETECTIONS
@@ -432,7 +432,7 @@ class FramePredictor(_LivePredictor):
                 self.det_xy[:m].copy_(torch.from_numpy(xy_np))
         self.det_count.fill_(m)
         if seed is not None:
-            self.seed_dev.fill_(_seed_i64(seed))
+            self.seed_dev.fill_(seed_i64(seed))
 
     def _outs(self):
         dev, t, v = self.device, self.t_obs, self.v
@@ -653,7 +653,7 @@ class StreamsPredictor(_LivePredictor):
         self._h_start[:] = pk.det_start
         self._h_pushed[:] = pk.pushed
         if seed is not None:
-            self._h_seed[0] = _seed_i64(seed)
+            self._h_seed[0] = seed_i64(seed)
         if m:
             self._h_rec_i[:m, 0] = pk.ids
             self._h_rec_f[:m, 1:] = pk.xy
@@ -678,7 +678,7 @@ class StreamsPredictor(_LivePredictor):
             raise ValueError("DeviceTick: %d counts for %d streams" % (n_counts, self.ns))
         self._wait_host()
         if seed is not None:
-            self._h_seed[0] = _seed_i64(seed)
+            self._h_seed[0] = seed_i64(seed)
         if dev_counts:
             c = counts.reshape(-1).to(torch.int32)
             self.pushed_dev.copy_(c >= 0)
@@ -686,7 +686,7 @@ class StreamsPredictor(_LivePredictor):
             torch.cumsum(c.clamp(min=0), 0, dtype=torch.int32, out=self.det_start[1:])
             self.det_start.clamp_(max=m)
             if seed is not None:
-                self.seed_dev.fill_(_seed_i64(seed))
+                self.seed_dev.fill_(seed_i64(seed))
         else:
             self._h_pushed[:] = counts >= 0
             self._h_start[0] = 0

@@ -11,7 +11,7 @@ import math
 import torch
 
 from . import _lib
-from ._lib import ModelDesc, check, lib, peds_arg, ptr, require_gpu, stream_ptr
+from ._lib import ModelDesc, check, lib, peds_arg, ptr, require_gpu, seed_u64, stream_ptr
 
 
 def _adj_layout(adj, n, t, v):
@@ -569,30 +569,43 @@ def weighted_sum(values, weights=None):
     return out[0]
 
 
+def sample_args(what, y, k, obs_last, noise, seed_dev=None):
+    """The argument rule of the sampling family (best_of_k, sample_trajectories, sample_risk; `what` names the caller
+    in the messages): y (N,5,P,V), obs_last (N,V,2) or None, noise (k,N,P,V,2) or None, seed_dev a one-element int64
+    device tensor or None.  Returns (y as float32, obs_last and noise as contiguous float32 on y's device, N, P, V)."""
+    if y.dim() != 4 or y.shape[1] != 5:
+        raise ValueError("%s: y (N,5,P,V) expected" % what)
+    n, _, p, v = y.shape
+    y = y.to(torch.float32)
+    if obs_last is not None:
+        if tuple(obs_last.shape) != (n, v, 2):
+            raise ValueError("%s: obs_last (N,V,2) expected" % what)
+        obs_last = obs_last.to(device=y.device, dtype=torch.float32).contiguous()
+    if noise is not None:
+        if tuple(noise.shape) != (k, n, p, v, 2):
+            raise ValueError("%s: noise (K,N,P,V,2) expected" % what)
+        noise = noise.to(device=y.device, dtype=torch.float32).contiguous()
+    if seed_dev is not None and (seed_dev.numel() != 1 or seed_dev.dtype != torch.int64):
+        raise ValueError("%s: seed_dev must be a one-element int64 device tensor" % what)
+    return y, obs_last, noise, n, p, v
+
+
 def best_of_k(y, target_rel, obs_last=None, num_peds=None, k=20, noise=None, seed=0):
     """Evaluation tail of test.py:59-123 on the device: y (N,5,P,V) model output (any strides), target_rel
     (N,P,V,2), obs_last (N,V,2) or None, noise (K,N,P,V,2) standard normals or None (in-kernel Philox stream keyed
     by `seed`).  Returns per-pedestrian (min ADE, min FDE), each (N,V) with zeros in padded slots."""
     require_gpu(y, target_rel)
-    n, f, p, v = y.shape
-    if f != 5 or tuple(target_rel.shape) != (n, p, v, 2):
-        raise ValueError("best_of_k: y (N,5,P,V) / target_rel (N,P,V,2) expected")
-    y = y.to(torch.float32)
+    k = int(k)
+    y, obs_last, noise, n, p, v = sample_args("best_of_k", y, k, obs_last, noise)
+    if tuple(target_rel.shape) != (n, p, v, 2):
+        raise ValueError("best_of_k: target_rel (N,P,V,2) expected")
     target_rel = target_rel.to(torch.float32).contiguous()
-    if obs_last is not None:
-        if tuple(obs_last.shape) != (n, v, 2):
-            raise ValueError("best_of_k: obs_last (N,V,2) expected")
-        obs_last = obs_last.to(device=y.device, dtype=torch.float32).contiguous()
-    if noise is not None:
-        if tuple(noise.shape) != (k, n, p, v, 2):
-            raise ValueError("best_of_k: noise (K,N,P,V,2) expected")
-        noise = noise.to(device=y.device, dtype=torch.float32).contiguous()
     peds = peds_arg(num_peds, n, y.device)
     ade = torch.empty((n, v), device=y.device, dtype=torch.float32)
     fde = torch.empty((n, v), device=y.device, dtype=torch.float32)
     sn, sf, sp, sv = y.stride()
     check(lib().stg_bestofk_eval(ptr(y), sn, sf, sp, sv, ptr(target_rel), ptr(obs_last), ptr(peds), ptr(noise),
-                                 int(seed) & 0xFFFFFFFFFFFFFFFF, n, p, v, int(k), ptr(ade), ptr(fde), stream_ptr()),
+                                 seed_u64(seed), n, p, v, k, ptr(ade), ptr(fde), stream_ptr()),
           "stg_bestofk_eval")
     return ade, fde
 
@@ -605,23 +618,10 @@ def sample_trajectories(y, obs_last=None, num_peds=None, k=20, noise=None, seed=
     runs).  The draws are `best_of_k`'s for the same seed / noise.  samples / mean: preallocated outputs (graph
     capture), contiguous float32.  Returns (samples (K,N,P,V,2), mean (N,P,V,2)), zeros in padded slots."""
     require_gpu(y, seed_dev, samples, mean)
-    n, f, p, v = y.shape
     k = int(k)
-    if f != 5:
-        raise ValueError("sample_trajectories: y (N,5,P,V) expected")
     if k < 0:
         raise ValueError("sample_trajectories: k must be >= 0")
-    y = y.to(torch.float32)
-    if obs_last is not None:
-        if tuple(obs_last.shape) != (n, v, 2):
-            raise ValueError("sample_trajectories: obs_last (N,V,2) expected")
-        obs_last = obs_last.to(device=y.device, dtype=torch.float32).contiguous()
-    if noise is not None:
-        if tuple(noise.shape) != (k, n, p, v, 2):
-            raise ValueError("sample_trajectories: noise (K,N,P,V,2) expected")
-        noise = noise.to(device=y.device, dtype=torch.float32).contiguous()
-    if seed_dev is not None and (seed_dev.numel() != 1 or seed_dev.dtype != torch.int64):
-        raise ValueError("sample_trajectories: seed_dev must be a one-element int64 device tensor")
+    y, obs_last, noise, n, p, v = sample_args("sample_trajectories", y, k, obs_last, noise, seed_dev)
     for name, out, shape in (("samples", samples, (k, n, p, v, 2)), ("mean", mean, (n, p, v, 2))):
         if out is not None and (tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous()):
             raise ValueError("sample_trajectories: %s must be a contiguous float32 %s tensor" % (name, shape))
@@ -632,7 +632,7 @@ def sample_trajectories(y, obs_last=None, num_peds=None, k=20, noise=None, seed=
         mean = torch.empty((n, p, v, 2), device=y.device, dtype=torch.float32)
     sn, sf, sp, sv = y.stride()
     check(lib().stg_sample_trajectories(ptr(y), sn, sf, sp, sv, ptr(obs_last), ptr(peds), ptr(noise),
-                                        int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(seed_dev), n, p, v, k,
+                                        seed_u64(seed), ptr(seed_dev), n, p, v, k,
                                         ptr(samples) if k > 0 else None, ptr(mean), stream_ptr()),
           "stg_sample_trajectories")
     return samples, mean
@@ -656,6 +656,23 @@ def risk_buffers(n, p, v, k, radius, z, pairs, device):
                 i32(n, v, z) if z else None)
 
 
+def risk_zones(zones, n, device):
+    """The rule for sample_risk's rectangles: (Z,4) shared by the n scenes or (n,Z,4) per scene, Z >= 1, or None.
+    Returns (contiguous float32 tensor on `device` or None, Z, the scene stride z_sn the kernel takes: 0 = shared)."""
+    if zones is None:
+        return None, 0, 0
+    zones = torch.as_tensor(zones, dtype=torch.float32).to(device=device).contiguous()
+    if zones.dim() == 2 and zones.shape[1] == 4:
+        z, z_sn = zones.shape[0], 0
+    elif zones.dim() == 3 and zones.shape[0] == n and zones.shape[2] == 4:
+        z, z_sn = zones.shape[1], zones.shape[1] * 4
+    else:
+        raise ValueError("sample_risk: zones (Z,4) or (N,Z,4) expected, got %s" % (tuple(zones.shape),))
+    if z < 1:
+        raise ValueError("sample_risk: zones holds no rectangle (pass None)")
+    return zones, z, z_sn
+
+
 def sample_risk(y, obs_last=None, num_peds=None, k=20, radius=None, zones=None, noise=None, seed=0, seed_dev=None,
                 pairs=False, out=None):
     """Conflict and zone-occupancy counts over the k samples `sample_trajectories` would write for the same arguments,
@@ -665,10 +682,7 @@ def sample_risk(y, obs_last=None, num_peds=None, k=20, radius=None, zones=None, 
     (x0 <= x < x1 and y0 <= y < y1 is inside; None: no zone outputs); pairs: also the (N,V,V) pair counts.
     out: an earlier Risk of the same call to fill (graph capture).  Returns a Risk."""
     require_gpu(y, seed_dev)
-    n, f, p, v = y.shape
     k = int(k)
-    if f != 5:
-        raise ValueError("sample_risk: y (N,5,P,V) expected")
     if k < 1:
         raise ValueError("sample_risk: k must be >= 1")
     radius = None if radius is None else float(radius)
@@ -678,28 +692,8 @@ def sample_risk(y, obs_last=None, num_peds=None, k=20, radius=None, zones=None, 
         raise ValueError("sample_risk: nothing to compute (neither a radius nor zones)")
     if pairs and radius is None:
         raise ValueError("sample_risk: pairs=True needs a radius")
-    y = y.to(torch.float32)
-    if obs_last is not None:
-        if tuple(obs_last.shape) != (n, v, 2):
-            raise ValueError("sample_risk: obs_last (N,V,2) expected")
-        obs_last = obs_last.to(device=y.device, dtype=torch.float32).contiguous()
-    if noise is not None:
-        if tuple(noise.shape) != (k, n, p, v, 2):
-            raise ValueError("sample_risk: noise (K,N,P,V,2) expected")
-        noise = noise.to(device=y.device, dtype=torch.float32).contiguous()
-    if seed_dev is not None and (seed_dev.numel() != 1 or seed_dev.dtype != torch.int64):
-        raise ValueError("sample_risk: seed_dev must be a one-element int64 device tensor")
-    z, z_sn = 0, 0
-    if zones is not None:
-        zones = torch.as_tensor(zones, dtype=torch.float32).to(device=y.device).contiguous()
-        if zones.dim() == 2 and zones.shape[1] == 4:
-            z, z_sn = zones.shape[0], 0
-        elif zones.dim() == 3 and zones.shape[0] == n and zones.shape[2] == 4:
-            z, z_sn = zones.shape[1], zones.shape[1] * 4
-        else:
-            raise ValueError("sample_risk: zones (Z,4) or (N,Z,4) expected, got %s" % (tuple(zones.shape),))
-        if z < 1:
-            raise ValueError("sample_risk: zones holds no rectangle (pass None)")
+    y, obs_last, noise, n, p, v = sample_args("sample_risk", y, k, obs_last, noise, seed_dev)
+    zones, z, z_sn = risk_zones(zones, n, y.device)
     for what, got, most in (("V", v, RISK_MAX_V), ("k", k, RISK_MAX_K), ("Z", z, RISK_MAX_Z), ("P", p, RISK_MAX_P)):
         if got > most:
             raise ValueError("sample_risk: %s=%d above the kernel's limit of %d" % (what, got, most))
@@ -718,7 +712,7 @@ def sample_risk(y, obs_last=None, num_peds=None, k=20, radius=None, zones=None, 
     peds = peds_arg(num_peds, n, y.device)
     sn, sf, sp, sv = y.stride()
     check(lib().stg_sample_risk(ptr(y), sn, sf, sp, sv, ptr(obs_last), ptr(peds), ptr(noise),
-                                int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(seed_dev), n, p, v, k,
+                                seed_u64(seed), ptr(seed_dev), n, p, v, k,
                                 ctypes.c_float(radius if radius is not None else 0.0), ptr(zones), z_sn, z,
                                 ptr(out.conflict), ptr(out.conflict_any), ptr(out.partner), ptr(out.pair),
                                 ptr(out.zone_any), ptr(out.zone_count), ptr(out.ped_zone), stream_ptr()),

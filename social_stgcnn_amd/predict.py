@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import data, graphs, ops
-from ._lib import peds_arg, require_gpu
+from ._lib import peds_arg, require_gpu, seed_i64
 
 Prediction = collections.namedtuple("Prediction", "samples mean v_pred")
 Prediction.__doc__ = """samples (K,N,P,V,2) absolute sampled trajectories, mean (N,P,V,2) the zero-noise trajectory,
@@ -27,12 +27,6 @@ RiskSpec = collections.namedtuple("RiskSpec", "radius zones pairs", defaults=(No
 RiskSpec.__doc__ = """What a Predictor reduces its K samples to (ops.sample_risk): radius (two pedestrians closer than
 this conflict; None: no conflict counts), zones ((Z,4) rectangles [x0,y0,x1,y1] for every scene or (N,Z,4) per scene;
 None: no zone counts), pairs (also the (N,V,V) pair counts)."""
-
-
-def _seed_i64(seed):
-    """A uint64 seed as the int64 a device tensor holds (same 64 bits)."""
-    s = int(seed) & 0xFFFFFFFFFFFFFFFF
-    return s - (1 << 64) if s >= 1 << 63 else s
 
 
 def observed_inputs(obs_abs, num_peds=None, out=None):
@@ -104,10 +98,7 @@ class Predictor:
     def _zones(self, n, dev):
         """The static device tensor of the spec's rectangles, (Z,4) or (n,Z,4)."""
         if self.zones is None and self.spec.zones is not None:
-            z = torch.as_tensor(self.spec.zones, dtype=torch.float32).to(dev).contiguous()
-            if not ((z.dim() == 2 or (z.dim() == 3 and z.shape[0] == n)) and z.shape[-1] == 4 and z.shape[-2] >= 1):
-                raise ValueError("risk zones (Z,4) or (%d,Z,4) expected, got %s" % (n, tuple(z.shape)))
-            self.zones = z
+            self.zones = ops.risk_zones(self.spec.zones, n, dev)[0]
         return self.zones
 
     def _forward(self, obs_abs, peds, seed, noise, seed_dev=None, bufs=None, outs=(None, None), risk_out=None):
@@ -188,7 +179,7 @@ class Predictor:
             if num_peds is not None:
                 peds_s.copy_(torch.as_tensor(num_peds).reshape(-1))
             if seed is not None:
-                seed_s.fill_(_seed_i64(seed))
+                seed_s.fill_(seed_i64(seed))
             graph.replay()
             return res
         return replay

@@ -19,6 +19,7 @@ import torch
 
 from conftest import GOLDEN, load_golden
 import risk_np
+from sampling_inputs import random_pred as _random_pred
 
 pytestmark = pytest.mark.gpu
 CFG = dict(n_stgcnn=1, n_txpcnn=5, output_feat=5, seq_len=8, kernel_size=3, pred_seq_len=12)
@@ -144,17 +145,6 @@ def test_exact_counts_equal_the_numpy_statement(dev, v, k):
 
 
 # ---- real tier ----------------------------------------------------------------------------------------------------
-
-def _random_pred(gen, n, p, v, dev):
-    """test_gpu_sampling's recipe: (N,5,P,V) strided view of a (N,P,V,5) tensor: means, unequal log sigmas,
-    correlations."""
-    base = torch.empty((n, p, v, 5))
-    base[..., 0:2] = torch.randn((n, p, v, 2), generator=gen) * 0.5
-    base[..., 2] = torch.rand((n, p, v), generator=gen) * 1.5 - 1.0
-    base[..., 3] = torch.rand((n, p, v), generator=gen) * 1.5 - 0.5
-    base[..., 4] = torch.randn((n, p, v), generator=gen)
-    return base.to(dev).permute(0, 3, 1, 2)
-
 
 REAL_SHAPES = {8: ([8, 5, 8, 1, 3], 3.0), 33: ([33, 20, 0, 27], 6.0), 130: ([130], 12.0)}
 

@@ -13,6 +13,7 @@ import torch
 
 from conftest import GOLDEN, load_golden
 import philox_np
+from sampling_inputs import random_pred as _random_pred
 
 pytestmark = pytest.mark.gpu
 CFG = dict(n_stgcnn=1, n_txpcnn=5, output_feat=5, seq_len=8, kernel_size=3, pred_seq_len=12)
@@ -54,16 +55,6 @@ def _reference_noise_fn(win):
         at[0] += n
         return out
     return noise_fn
-
-
-def _random_pred(gen, n, p, v, dev, rho_raw=None):
-    """(N,5,P,V) strided view of a (N,P,V,5) tensor: means, unequal log sigmas, correlations."""
-    base = torch.empty((n, p, v, 5))
-    base[..., 0:2] = torch.randn((n, p, v, 2), generator=gen) * 0.5
-    base[..., 2] = torch.rand((n, p, v), generator=gen) * 1.5 - 1.0
-    base[..., 3] = torch.rand((n, p, v), generator=gen) * 1.5 - 0.5
-    base[..., 4] = torch.randn((n, p, v), generator=gen) if rho_raw is None else rho_raw
-    return base.to(dev).permute(0, 3, 1, 2)
 
 
 def _host_samples(y, obs_last, noise):

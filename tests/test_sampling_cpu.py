@@ -90,3 +90,66 @@ def test_philox_replay_is_the_standard_generator_and_draws_normals():
     assert abs(z.mean()) < 5 * se and abs(z.var() - 1.0) < 5 * math.sqrt(2.0) * se
     assert abs(np.mean(z[..., 0] * z[..., 1])) < 5 * math.sqrt(2.0) * se
     assert not np.array_equal(z, philox_np.noise_tensor(4, 16, 8, 12, 20))
+
+
+def test_sampling_argument_rules_on_cpu_tensors():
+    """ops.sample_args (the checks best_of_k, sample_trajectories and sample_risk share), _lib.seed_u64 / seed_i64 and
+    ops.risk_zones, on CPU tensors: N = 2, P = 3, V = 4, K = 2."""
+    import torch
+    from social_stgcnn_amd import _lib, ops
+    n, p, v, k = 2, 3, 4, 2
+    y = torch.zeros((n, p, v, 5), dtype=torch.float64).permute(0, 3, 1, 2)          # a strided (N,5,P,V) view
+    ol, nz = torch.ones((n, v, 2)), torch.ones((k, n, p, v, 2))
+    seed_dev = torch.zeros(1, dtype=torch.int64)
+    bad = {"y (N,5,P,V)": [dict(y=torch.zeros((n, 4, p, v))), dict(y=torch.zeros((n, 5, p))),
+                           dict(y=torch.zeros((n, p, v, 5)))],
+           "obs_last (N,V,2)": [dict(obs_last=torch.zeros((n, v + 1, 2))), dict(obs_last=torch.zeros((n, v))),
+                                dict(obs_last=torch.zeros((v, n, 2)))],
+           "noise (K,N,P,V,2)": [dict(noise=torch.zeros((k + 1, n, p, v, 2))), dict(noise=torch.zeros((n, p, v, 2))),
+                                 dict(noise=torch.zeros((k, n, v, p, 2)))],
+           "seed_dev must be a one-element int64": [dict(seed_dev=torch.zeros(2, dtype=torch.int64)),
+                                                    dict(seed_dev=torch.zeros(1, dtype=torch.int32))]}
+    for what in ("best_of_k", "sample_trajectories", "sample_risk"):
+        for msg, cases in bad.items():
+            for kw in cases:
+                args = {**dict(y=y, k=k, obs_last=ol, noise=nz, seed_dev=seed_dev), **kw}
+                with pytest.raises(ValueError, match="^" + re.escape("%s: %s" % (what, msg))):
+                    ops.sample_args(what, **args)
+    # what comes back: float32 throughout, y with its strides, obs_last and noise contiguous, the sizes
+    ol64 = torch.arange(2.0 * n * v, dtype=torch.float64).reshape(2, n, v).permute(1, 2, 0)
+    nz16 = torch.ones((2, k, n, p, v), dtype=torch.float16).permute(1, 2, 3, 4, 0)
+    assert not ol64.is_contiguous() and not nz16.is_contiguous()
+    y2, ol2, nz2, *sizes = ops.sample_args("sample_risk", y, k, ol64, nz16, seed_dev)
+    assert sizes == [n, p, v]
+    assert y2.dtype == torch.float32 and y2.shape == y.shape and y2.stride() == y.stride()
+    assert ol2.dtype == torch.float32 and ol2.is_contiguous() and torch.equal(ol2, ol64.to(torch.float32))
+    assert nz2.dtype == torch.float32 and nz2.is_contiguous() and nz2.shape == (k, n, p, v, 2)
+    yf = y.to(torch.float32)
+    assert ops.sample_args("best_of_k", yf, k, None, None)[:3] == (yf, None, None)
+    assert ops.sample_args("best_of_k", yf, k, ol, nz)[1] is ol                    # nothing to convert: no copy
+
+    # one seed, the same 64 bits as the ABI's uint64 and as the int64 of a seed_dev tensor
+    s = 2 ** 64 - 3
+    assert _lib.seed_u64(s) == s and _lib.seed_i64(s) == -3
+    assert ctypes.c_uint64(_lib.seed_i64(s)).value == _lib.seed_u64(s) == ctypes.c_uint64(s).value
+    assert torch.tensor([_lib.seed_i64(s)], dtype=torch.int64).numpy().view(np.uint64)[0] == s
+    for s in (0, 7, 2 ** 63 - 1, 2 ** 63, 2 ** 64 + 5, -1):
+        assert _lib.seed_u64(s) == s % 2 ** 64 and (_lib.seed_i64(s) - s) % 2 ** 64 == 0
+        assert -2 ** 63 <= _lib.seed_i64(s) < 2 ** 63
+
+    # rectangles: (Z,4) for every scene (stride 0) or (N,Z,4) per scene (stride 4 Z); anything else is refused
+    cpu = torch.device("cpu")
+    assert ops.risk_zones(None, n, cpu) == (None, 0, 0)
+    shared = np.arange(12, dtype=np.float64).reshape(3, 4)
+    t, z, z_sn = ops.risk_zones(shared, n, cpu)
+    assert (z, z_sn) == (3, 0) and t.dtype == torch.float32 and t.is_contiguous()
+    assert np.array_equal(t.numpy(), shared.astype(np.float32))
+    per = torch.from_numpy(np.stack([shared, shared + 1])).to(torch.float32)
+    t, z, z_sn = ops.risk_zones(per, n, cpu)
+    assert (z, z_sn) == (3, 12) and t is per                                       # a ready tensor is used as it is
+    for empty in (np.zeros((0, 4)), np.zeros((n, 0, 4))):
+        with pytest.raises(ValueError, match="holds no rectangle"):
+            ops.risk_zones(empty, n, cpu)
+    for wrong in (np.zeros((n + 1, 3, 4)), np.zeros((3, 5)), np.zeros(4), np.zeros((n, 3, 5))):
+        with pytest.raises(ValueError, match=r"zones \(Z,4\) or \(N,Z,4\) expected"):
+            ops.risk_zones(wrong, n, cpu)

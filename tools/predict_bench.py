@@ -2,7 +2,7 @@
 """Device time of the captured Predictor (observed absolute tracks -> K sampled trajectories, ONE graph) and of the
 sampling kernel alone, from device events around graph replays.  One JSON line per case.
 
-    python tools/predict_bench.py [--iters 200] [--cases bench,eth,kernel,risk]
+    python tools/predict_bench.py [--iters 200] [--cases bench,eth,kernel,risk,bestofk]
 
   bench   Predictor replay at N = 2048, V = 32 (every slot a pedestrian), K = 20, eth weights
   eth     Predictor replay on eth/test: its 70 windows as one ragged batch, K = 20
@@ -10,6 +10,7 @@ sampling kernel alone, from device events around graph replays.  One JSON line p
   risk    stg_sample_risk (radius 0.5, three rectangles, pair counts) against stg_sample_trajectories on the same
           arguments, both captured: K = 20 at N = 2048 x V = 32 with every slot full, and at N = 600 x V = 128 with the
           ragged scene sizes of the six test recordings (frame scenes taken at a fixed stride)
+  bestofk stg_bestofk_eval alone at the kernel case's shape, in-kernel normals, captured
 
 For the kernel's own time run this under `rocprofv3 --kernel-trace --stats -- python tools/predict_bench.py`.
 With the diagnostic library (STG_USE_DIAG_LIB=1, `make -C social_stgcnn_amd/csrc DIAG=1`) STG_SAMPLE_PEDS=1 forces
@@ -103,6 +104,17 @@ def main():
         print(json.dumps(dict({"case": "sample_kernel", "k": k, "n": n, "v": v, "p": p, "ms_per_replay": round(ms, 5),
                                "mb_written": round(written / 1e6, 2), "read_mb": round(n * 5 * p * v * 4 / 1e6, 2),
                                "store_tb_per_s": round(written / (ms * 1e-3) / 1e12, 3)}, **info)), flush=True)
+    if "bestofk" in cases:
+        gen = torch.Generator().manual_seed(3)
+        y = (torch.randn((n, p, v, 5), generator=gen) * 0.5).to(dev).permute(0, 3, 1, 2)
+        obs_last = torch.randn((n, v, 2), generator=gen).to(dev)
+        target_rel = (torch.randn((n, p, v, 2), generator=gen) * 0.5).to(dev)
+
+        def run_best():
+            ops.best_of_k(y, target_rel, obs_last, None, k, None, 1)
+        ms = time_replays(graphs.warm_capture(run_best, 1)[0].replay, args.iters)
+        print(json.dumps(dict({"case": "bestofk", "k": k, "n": n, "v": v, "p": p, "ms_per_replay": round(ms, 5)},
+                              **info)), flush=True)
     if "risk" in cases:
         from social_stgcnn_amd import frames
         counts = torch.cat([frames.recording_scenes(data.read_file(os.path.join(ROOT, "tests", "golden", "data", d, f)),
