@@ -448,6 +448,75 @@ int stg_sample_risk(const float *pred, int64_t p_sn, int64_t p_sf, int64_t p_sp,
                     int32_t *conflict_any, int32_t *partner, int32_t *pair, int32_t *zone_any, int32_t *zone_count,
                     int32_t *ped_zone, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * N8  live predictions scored against the tracks that follow (added entry points, the ABI version
+ *     stays).  Per stream, pushes numbered 0, 1, ... since the state was cleared.  Push m leaves a record in ring row
+ *     m mod P: the scene's ids and num_peds (clamped to [0, V]), mean (P,V,2), the K samples (K,P,V,2) and the cumulative
+ *     covariance C_h = sum_{t<=h} [sx^2, rho sx sy, sy^2]_t, sx = expf(v_pred[2]), sy = expf(v_pred[3]),
+ *     rho = tanhf(v_pred[4]), summed in float32 in ascending t.  At push m the record of push m-h (h = 1..P, as far as
+ *     pushes exist) is scored at its step h against the truth: the first detection of the pedestrian's id among the
+ *     first min(count, M_max) detections of the push, rounded as N6 rounds (scale) and converted to float32 -- taken
+ *     from the detections, whatever the track state did with them.  For a matched pedestrian v < num_peds, in float32
+ *     as written (no fused multiply-add), dx, dy = mean_h - truth, (cxx, cxy, cyy) = C_h:
+ *       err = sqrtf(dx*dx + dy*dy)          det = cxx*cyy - cxy*cxy
+ *       d2  = (cyy*(dx*dx) - 2*cxy*dx*dy + cxx*(dy*dy)) / det
+ *       nll = 0.5*d2 + 0.5*log(det) + log(2 pi)   (log(det): the correctly rounded float32 logarithm)
+ *       best = min_k |samples[k,h] - truth|;   acc[k] += |samples[k,h] - truth|, acc_mean += err, steps += 1
+ *     Order within a push: score the pending records, retire the one that turns P pushes old, then write this push's
+ *     record into the retired row and zero its accumulators.
+ *
+ *   State (stg_score_state, NS leading, all DEVICE memory; zero head and totals start a stream):
+ *     rec_ids int64 (NS,P,V), rec_peds int32 (NS,P), rec_mean (NS,P,P,V,2), rec_cov (NS,P,P,V,3),
+ *     rec_samples (NS,P,K,P,V,2), acc (NS,P,K,V), acc_mean (NS,P,V) float32, steps int32 (NS,P,V),
+ *     head int32 (NS,2) = {ring row of the next push, records that exist (<= P)},
+ *     totals float64 (NS,P,5+Q) = per horizon {matched, sum err, sum d2, sum nll, sum best, #(d2 <= thr_q) for q < Q},
+ *     traj_totals float64 (NS,5) = {trajectories with steps == P, the sums of their traj_ade, traj_fde, traj_ade_mean,
+ *     traj_fde_mean}.  Each workgroup owns its stream's totals and sums them in a fixed order (no atomics).
+ *     P*V*(8 + 20P + 8KP + 4K + 8) bytes per stream beside the totals.
+ *   Outputs (stg_score_out, NS leading): rec_ids int64 (NS,P,V) (row h-1: the id where matched, else -1), matched int32,
+ *     err, d2, nll, best float32 (NS,P,V); from the retired record traj_steps int32 (NS,V), traj_ade = min_k acc[k] /
+ *     steps, traj_fde = best at h = P (0 if unmatched there), traj_ade_mean = acc_mean / steps, traj_fde_mean = err at
+ *     h = P, float32 (NS,V).  Unmatched, padded and not yet existing entries are 0.  With traj_steps == P, traj_ade /
+ *     traj_fde are the reference's per-pedestrian best-of-K ADE / FDE (test.py:93-123).
+ *   Inputs: the prediction as the chain leaves it -- mean (NS,P,V,2), v_pred (NS,5,P,V) with its strides as in N5,
+ *     samples (K,NS,P,V,2) or NULL, ids int64 (NS,V), num_peds int32 (NS) -- and thr float32[Q].  NULL samples or K == 0
+ *     skips every sample-based value: rec_samples, acc, best, traj_ade and traj_fde may then be NULL.
+ *   stg_score_push: one stream (NS = 1), det_id / det_xy / det_count as stg_track_push reads them.
+ *   stg_score_push_streams: det_id / det_xy with strides, M_total, det_start and pushed as stg_track_push_streams reads
+ *     them (the same clamping and M_max truncation); a stream not pushed keeps its state bit for bit and gets all-zero
+ *     outputs (ids -1).  NS == 0 is a no-op.
+ *   One workgroup per stream, 12 bytes of LDS per detection slot (24 KB at the limit), plain stores, no host
+ *   synchronisation.  Sizes above STG_SCORE_MAX_* or the STG_TRACK_MAX_* limits: STG_EUNSUPPORTED; bad sizes, NULL
+ *   required pointers or mean / samples not 8-byte aligned: STG_EINVAL; both decided before any launch.             */
+#define STG_SCORE_MAX_V 256
+#define STG_SCORE_MAX_K 64
+#define STG_SCORE_MAX_P 32
+#define STG_SCORE_MAX_Q 4
+typedef struct stg_score_state {
+    int64_t *rec_ids;
+    int32_t *rec_peds;
+    float *rec_mean, *rec_cov, *rec_samples, *acc, *acc_mean;
+    int32_t *steps, *head;
+    double *totals, *traj_totals;
+} stg_score_state;
+typedef struct stg_score_out {
+    int64_t *rec_ids;
+    int32_t *matched;
+    float *err, *d2, *nll, *best;
+    int32_t *traj_steps;
+    float *traj_ade, *traj_fde, *traj_ade_mean, *traj_fde_mean;
+} stg_score_out;
+int stg_score_push(const int64_t *det_id, const double *det_xy, const int32_t *det_count, int M_max, double scale,
+                   const float *mean, const float *v_pred, int64_t p_sn, int64_t p_sf, int64_t p_sp, int64_t p_sv,
+                   const float *samples, const int64_t *ids, const int32_t *num_peds, int P, int V, int K,
+                   const stg_score_state *state, const float *thr, int Q, const stg_score_out *out, void *stream);
+int stg_score_push_streams(const int64_t *det_id, int64_t id_stride, const double *det_xy, int64_t xy_stride,
+                           int M_total, const int32_t *det_start, const int32_t *pushed, int NS, int M_max,
+                           double scale, const float *mean, const float *v_pred, int64_t p_sn, int64_t p_sf,
+                           int64_t p_sp, int64_t p_sv, const float *samples, const int64_t *ids,
+                           const int32_t *num_peds, int P, int V, int K, const stg_score_state *state,
+                           const float *thr, int Q, const stg_score_out *out, void *stream);
+
 /* Self-test helper: C(16x16) = A(16xK) * B(Kx16) through v_mfma_f32_16x16x4_f32 with the operand
  * maps the TXP-CNN kernels rely on (K multiple of 4).                                           */
 int stg_selftest_mfma(const float *a, const float *b, int K, float *c, void *stream);

@@ -34,6 +34,18 @@ class ModelDesc(ctypes.Structure):
                 ("flags", ctypes.c_int32), ("wg_waves", ctypes.c_int32)]
 
 
+class ScoreState(ctypes.Structure):
+    """stg_score_state (include/stgcnn_hip.h)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("rec_ids", "rec_peds", "rec_mean", "rec_cov", "rec_samples", "acc",
+                                               "acc_mean", "steps", "head", "totals", "traj_totals")]
+
+
+class ScoreOut(ctypes.Structure):
+    """stg_score_out (include/stgcnn_hip.h)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("rec_ids", "matched", "err", "d2", "nll", "best", "traj_steps",
+                                               "traj_ade", "traj_fde", "traj_ade_mean", "traj_fde_mean")]
+
+
 _SIGNATURES = {
     "stg_abi_version": (c_i, []),
     "stg_last_error": (ctypes.c_char_p, []),
@@ -91,6 +103,11 @@ _SIGNATURES = {
                                   c_f, c_f, c_f, c_f, c_f]),
     "stg_track_push_streams_rule": (c_i, [c_f, c_l, c_f, c_l, c_i, c_f, c_f, c_i, c_i, c_f, c_f, c_f, c_f, c_i, c_i,
                                           ctypes.c_double, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_i, c_f]),
+    "stg_score_push": (c_i, [c_f, c_f, c_f, c_i, ctypes.c_double, c_f, c_f, c_l, c_l, c_l, c_l, c_f, c_f, c_f, c_i, c_i,
+                             c_i, ctypes.POINTER(ScoreState), c_f, c_i, ctypes.POINTER(ScoreOut), c_f]),
+    "stg_score_push_streams": (c_i, [c_f, c_l, c_f, c_l, c_i, c_f, c_f, c_i, c_i, ctypes.c_double, c_f, c_f, c_l, c_l,
+                                     c_l, c_l, c_f, c_f, c_f, c_i, c_i, c_i, ctypes.POINTER(ScoreState), c_f, c_i,
+                                     ctypes.POINTER(ScoreOut), c_f]),
     "stg_selftest_mfma": (c_i, [c_f, c_f, c_i, c_f, c_f]),
 }
 EXPORTS = tuple(_SIGNATURES)

@@ -1,0 +1,451 @@
+// score: live predictions scored against the tracks that follow, on the device.
+//
+// The rule, per stream.  Pushes are numbered 0, 1, ... since the state was cleared; a push with no detections is a
+// push, a stream that is not pushed does not advance.  Push m leaves a RECORD in row m mod P of the state's ring: its
+// scene's ids (V) and num_peds, the mean trajectory (P,V,2), the K sampled trajectories (K,P,V,2) and the cumulative
+// covariance (P,V,3): C_h = sum_{t<=h} [sx^2, rho sx sy, sy^2]_t with sx = expf(v_pred[2]), sy = expf(v_pred[3]),
+// rho = tanhf(v_pred[4]) -- the terms of sample_draw.hpp -- summed in float32 in ascending t.  The per-step draws are
+// independent, so the absolute position at horizon h is N(mean_h, C_h).
+//
+//   truth    of id i at push m: its first detection among the first min(count, M_max) detections of the push, rounded
+//            as the push kernel rounds (rint(x * scale) / scale in float64) and then converted to float32.  Taken from
+//            the detections, not from the track state: it depends neither on the slots nor on a TrackRule.
+//   values   at push m the pending record of push m-h (h = 1..P, as far as pushes exist) is scored at its step h.  For
+//            each of its pedestrians v < num_peds: matched = found among the detections.  Where matched, with
+//            dx, dy = mean_h - truth in float32 and (cxx, cxy, cyy) = C_h, every operation in float32 as written (no
+//            fused multiply-add):
+//              err  = sqrtf(dx*dx + dy*dy)
+//              det  = cxx*cyy - cxy*cxy
+//              d2   = (cyy*(dx*dx) - 2*cxy*dx*dy + cxx*(dy*dy)) / det
+//              nll  = 0.5*d2 + 0.5*log(det) + log(2 pi), log(det) the correctly rounded float32 logarithm (taken in
+//                     float64 and rounded), log(2 pi) the float32 constant
+//              best = min_k |samples[k,h] - truth|
+//            and the record's accumulators advance: acc[k] += |samples[k,h] - truth|, acc_mean += err, steps += 1.
+//            Unmatched, padded and not yet existing entries are 0, and -1 in rec_ids.
+//   outputs  per horizon rec_ids (P,V) (row h-1: the scene of push m-h), matched, err, d2, nll, best (P,V); from the
+//            record that turns P pushes old: traj_steps (V), traj_ade = min_k acc[k] / steps, traj_fde = best at h = P
+//            (0 if unmatched there), traj_ade_mean = acc_mean / steps, traj_fde_mean = err at h = P.  With steps == P
+//            traj_ade / traj_fde are the reference's per-pedestrian best-of-K ADE / FDE.
+//   totals   float64 (P, 5+Q) per stream: matched count, sum err, sum d2, sum nll, sum best, and for each of the Q
+//            thresholds the number with d2 <= thr_q; traj_totals (5): the number of full trajectories (steps == P)
+//            and the sums of their four errors.
+//   order    score the pending records; retire the oldest; only then, behind a barrier, write this push's record into
+//            the retired row (m mod P) and zero its accumulators.
+//   A stream not pushed keeps its state bit for bit and gets all-zero outputs (ids -1).
+//
+// One workgroup per stream:
+//   sort     the detections by (id, index), a bitonic network in LDS (the push kernel's phase 2, copied: frames.hip
+//            keeps its own)
+//   score    a wave per horizon h (wave w takes h = w+1, w+1+waves, ...), a lane per pedestrian: lower bound of the
+//            record's id in the sorted keys, then the loop over k -- the reads of samples[k,h,:] are contiguous in v.
+//            The row of a horizon belongs to one wave, so its accumulators are plain read-modify-writes
+//   totals   a lane sums its pedestrians in ascending v in float64, the wave adds the 64 partials by a fixed butterfly
+//            and lane 0 adds the sum to the stream's totals: the workgroup owns them, no atomics, the same order
+//            every run
+//   retire   the wave of h = P writes the trajectory outputs from the accumulators it has just advanced
+//   enqueue  behind a barrier: ids, the running covariance sum, and the pedestrians' columns of mean and samples into
+//            row m mod P
+// No host synchronisation (the launch is captured into the live predictors' graph), plain C++ stores only, 24 KB of
+// dynamic LDS at the 2,048-detection limit.
+#include "common.hpp"
+
+namespace stg {
+
+constexpr int kScoreThreads = 256;
+constexpr int kScoreWaves = kScoreThreads / kWave;
+constexpr int kScoreCols = 5;                      // totals columns ahead of the coverage counts
+
+// np.around(x, decimals) as frames.hip's round_pos
+__device__ __forceinline__ double score_round_pos(double x, double scale) {
+    return scale > 0.0 ? rint(x * scale) / scale : x;
+}
+
+struct ScoreArgs {
+    // the prediction as the chain leaves it
+    const float *mean, *v_pred;
+    int64_t p_sn, p_sf, p_sp, p_sv;
+    const float *samples;
+    const int64_t *ids;
+    const int32_t *num_peds;
+    stg_score_state st;
+    const float *thr;
+    stg_score_out out;
+    int NS, P, V, K, Q, M_max, M2;
+    double scale;
+};
+
+// |p - t|, float32 as written
+__device__ __forceinline__ float score_dist(float px, float py, float tx, float ty) {
+#pragma clang fp contract(off)
+    const float dx = px - tx, dy = py - ty;
+    return sqrtf(dx * dx + dy * dy);
+}
+
+// d2 and nll of the offset (dx, dy) under the covariance (cxx, cxy, cyy), float32 as written
+__device__ __forceinline__ void score_gauss(float dx, float dy, float cxx, float cxy, float cyy, float &d2, float &nll) {
+#pragma clang fp contract(off)
+    const float det = cxx * cyy - cxy * cxy;
+    d2 = (cyy * (dx * dx) - 2.f * cxy * dx * dy + cxx * (dy * dy)) / det;
+    nll = 0.5f * d2 + 0.5f * (float)log((double)det) + 1.8378770664093453f;
+}
+
+// the outputs of a stream that has nothing to report
+__device__ __forceinline__ void score_empty(const ScoreArgs &a, int b) {
+    const int P = a.P, V = a.V, tid = threadIdx.x;
+    const int64_t o = (int64_t)b * P * V;
+    for (int e = tid; e < P * V; e += kScoreThreads) {
+        a.out.rec_ids[o + e] = -1;
+        a.out.matched[o + e] = 0;
+        a.out.err[o + e] = 0.f;
+        a.out.d2[o + e] = 0.f;
+        a.out.nll[o + e] = 0.f;
+        if (a.out.best) a.out.best[o + e] = 0.f;
+    }
+    for (int v = tid; v < V; v += kScoreThreads) {
+        const int64_t x = (int64_t)b * V + v;
+        a.out.traj_steps[x] = 0;
+        if (a.out.traj_ade) a.out.traj_ade[x] = 0.f;
+        if (a.out.traj_fde) a.out.traj_fde[x] = 0.f;
+        a.out.traj_ade_mean[x] = 0.f;
+        a.out.traj_fde_mean[x] = 0.f;
+    }
+}
+
+// One push of stream b by one workgroup of kScoreThreads threads: `count` detections, detection j =
+// (det_id[j * id_stride], det_xy[j * xy_stride], det_xy[j * xy_stride + 1]).
+// LDS (dynamic): sort keys (M2 x int64), sort indices (M2 x int32)
+__device__ __forceinline__ void score_push_body(const ScoreArgs &a, int b, const int64_t *__restrict__ det_id,
+                                                int64_t id_stride, const double *__restrict__ det_xy,
+                                                int64_t xy_stride, int count) {
+    extern __shared__ __align__(16) unsigned char lds[];
+    int64_t *key = reinterpret_cast<int64_t *>(lds);
+    int32_t *kidx = reinterpret_cast<int32_t *>(key + a.M2);
+
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+    const int P = a.P, V = a.V, K = a.K, Q = a.Q, W = kScoreCols + Q;
+    const int m = count < 0 ? 0 : (count > a.M_max ? a.M_max : count);
+
+    // the stream's slices of the state
+    int32_t *hd = a.st.head + 2 * b;
+    // the ring row of this push and the number of records that exist (clamped: a state that was never cleared must
+    // not index outside its arrays)
+    const int head = (int)((uint32_t)hd[0] % (uint32_t)P), filled = hd[1] < 0 ? 0 : (hd[1] > P ? P : hd[1]);
+    int64_t *rec_ids = a.st.rec_ids + (int64_t)b * P * V;
+    int32_t *rec_peds = a.st.rec_peds + (int64_t)b * P;
+    float *rec_mean = a.st.rec_mean + (int64_t)b * P * P * V * 2;
+    float *rec_cov = a.st.rec_cov + (int64_t)b * P * P * V * 3;
+    float *rec_samples = K > 0 ? a.st.rec_samples + (int64_t)b * P * K * P * V * 2 : nullptr;
+    float *acc = K > 0 ? a.st.acc + (int64_t)b * P * K * V : nullptr;
+    float *acc_mean = a.st.acc_mean + (int64_t)b * P * V;
+    int32_t *steps = a.st.steps + (int64_t)b * P * V;
+    double *totals = a.st.totals + (int64_t)b * P * W;
+    double *traj_totals = a.st.traj_totals + (int64_t)b * 5;
+    const int64_t ob = (int64_t)b * P * V;
+
+    // 1. the detections into the sort buffer (padding keys sort last), sorted by (id, detection index)
+    int n2 = 1;
+    while (n2 < m) n2 <<= 1;
+    for (int p = tid; p < n2; p += kScoreThreads) {
+        key[p] = p < m ? det_id[p * id_stride] : INT64_MAX;
+        kidx[p] = p;
+    }
+    __syncthreads();
+    for (int k = 2; k <= n2; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < n2; i += kScoreThreads) {
+                const int l = i ^ j;
+                if (l > i) {
+                    const int64_t ka = key[i], kb = key[l];
+                    const int ia = kidx[i], ib = kidx[l];
+                    const bool gt = ka > kb || (ka == kb && ia > ib);
+                    if (gt == ((i & k) == 0)) {
+                        key[i] = kb;
+                        key[l] = ka;
+                        kidx[i] = ib;
+                        kidx[l] = ia;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+
+    // 2. score: wave -> horizon, lane -> pedestrian
+    for (int h = 1 + wave; h <= P; h += kScoreWaves) {
+        const bool pending = h <= filled;
+        const int r = pending ? (head - h + P) % P : 0;             // the row of push m - h
+        int np = pending ? rec_peds[r] : 0;
+        np = np < 0 ? 0 : (np > V ? V : np);
+        const bool retire = pending && h == P;
+        double part[kScoreCols + STG_SCORE_MAX_Q], tpart[5];
+#pragma unroll
+        for (int i = 0; i < kScoreCols + STG_SCORE_MAX_Q; ++i) part[i] = 0.0;
+#pragma unroll
+        for (int i = 0; i < 5; ++i) tpart[i] = 0.0;
+        for (int v0 = 0; v0 < V; v0 += kWave) {
+            const int v = v0 + lane;
+            if (v >= V) continue;                                   // (the wave sums below are outside this loop)
+            int64_t oid = -1;
+            int mt = 0, st = 0;
+            float err = 0.f, d2 = 0.f, nll = 0.f, best = 0.f;
+            float t_ade = 0.f, t_fde = 0.f, t_adem = 0.f, t_fdem = 0.f;
+            if (v < np) {
+                const int64_t id = rec_ids[r * V + v];
+                int lo = 0, hi = m;
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (key[mid] < id) lo = mid + 1;
+                    else hi = mid;
+                }
+                if (lo < m && key[lo] == id) {                      // the lower bound is the first detection of the id
+                    const int j = kidx[lo];
+                    const float tx = (float)score_round_pos(det_xy[j * xy_stride], a.scale);
+                    const float ty = (float)score_round_pos(det_xy[j * xy_stride + 1], a.scale);
+                    const int64_t e = ((int64_t)r * P + (h - 1)) * V + v;
+                    const float2 mu = *reinterpret_cast<const float2 *>(rec_mean + e * 2);
+                    mt = 1;
+                    oid = id;
+                    err = score_dist(mu.x, mu.y, tx, ty);
+                    score_gauss(mu.x - tx, mu.y - ty, rec_cov[e * 3], rec_cov[e * 3 + 1], rec_cov[e * 3 + 2], d2, nll);
+                    acc_mean[r * V + v] += err;
+                    steps[r * V + v] += 1;
+                    if (K > 0) {
+                        float bmin = INFINITY;
+                        for (int k = 0; k < K; ++k) {
+                            const int64_t se = (((int64_t)r * K + k) * P + (h - 1)) * V + v;
+                            const float2 s = *reinterpret_cast<const float2 *>(rec_samples + se * 2);
+                            const float d = score_dist(s.x, s.y, tx, ty);
+                            bmin = fminf(bmin, d);
+                            acc[((int64_t)r * K + k) * V + v] += d;
+                        }
+                        best = bmin;
+                    }
+                }
+                if (retire) {
+                    st = steps[r * V + v];
+                    if (st > 0) {
+                        if (K > 0) {
+                            float amin = INFINITY;
+                            for (int k = 0; k < K; ++k) amin = fminf(amin, acc[((int64_t)r * K + k) * V + v]);
+                            t_ade = amin / (float)st;
+                        }
+                        t_adem = acc_mean[r * V + v] / (float)st;
+                    }
+                    t_fde = best;
+                    t_fdem = err;
+                    if (st == P) {
+                        tpart[0] += 1.0;
+                        tpart[1] += (double)t_ade;
+                        tpart[2] += (double)t_fde;
+                        tpart[3] += (double)t_adem;
+                        tpart[4] += (double)t_fdem;
+                    }
+                }
+            }
+            const int64_t o = ob + (int64_t)(h - 1) * V + v;
+            a.out.rec_ids[o] = oid;
+            a.out.matched[o] = mt;
+            a.out.err[o] = err;
+            a.out.d2[o] = d2;
+            a.out.nll[o] = nll;
+            if (a.out.best) a.out.best[o] = best;
+            if (h == P) {
+                const int64_t x = (int64_t)b * V + v;
+                a.out.traj_steps[x] = st;
+                if (a.out.traj_ade) a.out.traj_ade[x] = t_ade;
+                if (a.out.traj_fde) a.out.traj_fde[x] = t_fde;
+                a.out.traj_ade_mean[x] = t_adem;
+                a.out.traj_fde_mean[x] = t_fdem;
+            }
+            if (mt) {
+                part[0] += 1.0;
+                part[1] += (double)err;
+                part[2] += (double)d2;
+                part[3] += (double)nll;
+                part[4] += (double)best;
+#pragma unroll
+                for (int q = 0; q < STG_SCORE_MAX_Q; ++q)
+                    if (q < Q && d2 <= a.thr[q]) part[kScoreCols + q] += 1.0;
+            }
+        }
+        // 3. the horizon's sums: the whole wave is here (h, pending and retire are uniform over it)
+        if (pending) {
+#pragma unroll
+            for (int i = 0; i < kScoreCols + STG_SCORE_MAX_Q; ++i) {
+                if (i < W) {                                        // (W is uniform)
+                    const double s = wave_sum(part[i]);
+                    if (lane == 0) totals[(h - 1) * W + i] += s;
+                }
+            }
+        }
+        if (retire) {
+#pragma unroll
+            for (int i = 0; i < 5; ++i) {
+                const double s = wave_sum(tpart[i]);
+                if (lane == 0) traj_totals[i] += s;
+            }
+        }
+    }
+    __syncthreads();
+
+    // 4. enqueue: this push's record into the retired row, its accumulators zeroed
+    int npn = a.num_peds[b];
+    npn = npn < 0 ? 0 : (npn > V ? V : npn);
+    for (int v = tid; v < V; v += kScoreThreads) {
+        rec_ids[head * V + v] = v < npn ? a.ids[(int64_t)b * V + v] : -1;
+        acc_mean[head * V + v] = 0.f;
+        steps[head * V + v] = 0;
+        {
+#pragma clang fp contract(off)
+            float cxx = 0.f, cxy = 0.f, cyy = 0.f;
+            for (int t = 0; t < P; ++t) {
+                float *c = rec_cov + (((int64_t)head * P + t) * V + v) * 3;
+                if (v < npn) {
+                    const float *q = a.v_pred + b * a.p_sn + v * a.p_sv + t * a.p_sp;
+                    const float sx = expf(q[2 * a.p_sf]), sy = expf(q[3 * a.p_sf]), rho = tanhf(q[4 * a.p_sf]);
+                    cxx += sx * sx;
+                    cxy += rho * sx * sy;
+                    cyy += sy * sy;
+                }
+                c[0] = cxx;
+                c[1] = cxy;
+                c[2] = cyy;
+            }
+        }
+    }
+    // mean and samples: the columns of the scene's pedestrians only (nothing reads a slot at or past num_peds, and a
+    // scene of 15 in a padding of 128 would otherwise move eight times the bytes)
+    {
+        const float2 *src = reinterpret_cast<const float2 *>(a.mean + (int64_t)b * P * V * 2);
+        float2 *dst = reinterpret_cast<float2 *>(rec_mean + (int64_t)head * P * V * 2);
+        for (int e = tid; e < P * npn; e += kScoreThreads) {
+            const int t = e / npn, x = t * V + (e - t * npn);
+            dst[x] = src[x];
+        }
+    }
+    if (K > 0) {
+        const int pv = P * V;
+#pragma unroll 4
+        for (int e = tid; e < K * P * npn; e += kScoreThreads) {
+            const int row = e / npn, v = e - row * npn, k = row / P, x = (row - k * P) * V + v;      // row = k * P + t
+            const float2 *src = reinterpret_cast<const float2 *>(a.samples + ((int64_t)k * a.NS + b) * pv * 2);
+            float2 *dst = reinterpret_cast<float2 *>(rec_samples + ((int64_t)head * K + k) * pv * 2);
+            dst[x] = src[x];
+        }
+        for (int e = tid; e < K * V; e += kScoreThreads) acc[(int64_t)head * K * V + e] = 0.f;
+    }
+    if (tid == 0) {                                          // (every read of the head and of rec_peds is behind the barrier)
+        rec_peds[head] = npn;
+        hd[0] = (head + 1) % P;
+        hd[1] = filled < P ? filled + 1 : P;
+    }
+}
+
+__global__ __launch_bounds__(kScoreThreads) void score_push_kernel(const ScoreArgs a,
+                                                                   const int64_t *__restrict__ det_id,
+                                                                   const double *__restrict__ det_xy,
+                                                                   const int32_t *__restrict__ det_count) {
+    score_push_body(a, 0, det_id, 1, det_xy, 2, det_count[0]);
+}
+
+// One workgroup per stream: stream b scores against detections det_start[b] .. det_start[b+1]-1 (clamped to
+// [0, M_total)) when pushed[b] != 0, as stg_track_push_streams reads them.
+__global__ __launch_bounds__(kScoreThreads) void score_push_streams_kernel(
+    const ScoreArgs a, const int64_t *__restrict__ det_id, int64_t id_stride, const double *__restrict__ det_xy,
+    int64_t xy_stride, int M_total, const int32_t *__restrict__ det_start, const int32_t *__restrict__ pushed) {
+    const int b = blockIdx.x;
+    if (pushed[b] == 0) {                                   // uniform over the block
+        score_empty(a, b);
+        return;
+    }
+    int lo = det_start[b], hi = det_start[b + 1];
+    lo = lo < 0 ? 0 : (lo > M_total ? M_total : lo);
+    hi = hi < lo ? lo : (hi > M_total ? M_total : hi);
+    score_push_body(a, b, det_id + lo * id_stride, id_stride, det_xy + lo * xy_stride, xy_stride, hi - lo);
+}
+
+// the checks both entry points share; fills `a`
+static int score_args(const char *what, int NS, int M_max, double scale, const float *mean, const float *v_pred,
+                      int64_t p_sn, int64_t p_sf, int64_t p_sp, int64_t p_sv, const float *samples,
+                      const int64_t *ids, const int32_t *num_peds, int P, int V, int K, const stg_score_state *st,
+                      const float *thr, int Q, const stg_score_out *out, ScoreArgs *a) {
+    STG_REQUIRE(M_max >= 1 && P >= 1 && V >= 1 && K >= 0 && Q >= 0, STG_EINVAL,
+                "%s: bad sizes M_max=%d P=%d V=%d K=%d Q=%d", what, M_max, P, V, K, Q);
+    STG_REQUIRE(st && out, STG_EINVAL, "%s: null pointer (state / out)", what);
+    if (!samples) K = 0;
+    STG_REQUIRE(mean && v_pred && ids && num_peds, STG_EINVAL, "%s: null pointer (mean / v_pred / ids / num_peds)", what);
+    STG_REQUIRE(st->rec_ids && st->rec_peds && st->rec_mean && st->rec_cov && st->acc_mean && st->steps && st->head &&
+                    st->totals && st->traj_totals,
+                STG_EINVAL, "%s: null pointer in the state", what);
+    STG_REQUIRE(K == 0 || (st->rec_samples && st->acc), STG_EINVAL,
+                "%s: null pointer in the state (rec_samples / acc with K=%d)", what, K);
+    STG_REQUIRE(out->rec_ids && out->matched && out->err && out->d2 && out->nll && out->traj_steps &&
+                    out->traj_ade_mean && out->traj_fde_mean,
+                STG_EINVAL, "%s: null pointer among the outputs", what);
+    STG_REQUIRE(K == 0 || (out->best && out->traj_ade && out->traj_fde), STG_EINVAL,
+                "%s: null pointer among the outputs (best / traj_ade / traj_fde with K=%d)", what, K);
+    STG_REQUIRE(Q == 0 || thr, STG_EINVAL, "%s: null pointer (thr with Q=%d)", what, Q);
+    STG_REQUIRE(aligned(mean, 8) && aligned(samples, 8) && aligned(st->rec_mean, 8) && aligned(st->rec_samples, 8),
+                STG_EINVAL, "%s: mean / samples and their records must be 8-byte aligned", what);
+    STG_REQUIRE(M_max <= STG_TRACK_MAX_DETECTIONS, STG_EUNSUPPORTED, "%s: M_max=%d above STG_TRACK_MAX_DETECTIONS=%d",
+                what, M_max, STG_TRACK_MAX_DETECTIONS);
+    STG_REQUIRE(NS <= STG_TRACK_MAX_STREAMS, STG_EUNSUPPORTED, "%s: NS=%d above STG_TRACK_MAX_STREAMS=%d", what, NS,
+                STG_TRACK_MAX_STREAMS);
+    STG_REQUIRE(V <= STG_SCORE_MAX_V, STG_EUNSUPPORTED, "%s: V=%d above STG_SCORE_MAX_V=%d", what, V, STG_SCORE_MAX_V);
+    STG_REQUIRE(K <= STG_SCORE_MAX_K, STG_EUNSUPPORTED, "%s: K=%d above STG_SCORE_MAX_K=%d", what, K, STG_SCORE_MAX_K);
+    STG_REQUIRE(P <= STG_SCORE_MAX_P, STG_EUNSUPPORTED, "%s: P=%d above STG_SCORE_MAX_P=%d", what, P, STG_SCORE_MAX_P);
+    STG_REQUIRE(Q <= STG_SCORE_MAX_Q, STG_EUNSUPPORTED, "%s: Q=%d above STG_SCORE_MAX_Q=%d", what, Q, STG_SCORE_MAX_Q);
+    int m2 = 1;
+    while (m2 < M_max) m2 <<= 1;
+    *a = ScoreArgs{mean, v_pred, p_sn, p_sf, p_sp, p_sv, K > 0 ? samples : nullptr, ids, num_peds, *st, thr, *out,
+                   NS, P, V, K, Q, M_max, m2, scale};
+    return STG_OK;
+}
+
+static inline size_t score_lds(const ScoreArgs &a) { return (size_t)a.M2 * (sizeof(int64_t) + sizeof(int32_t)); }
+
+}  // namespace stg
+
+extern "C" {
+
+int stg_score_push(const int64_t *det_id, const double *det_xy, const int32_t *det_count, int M_max, double scale,
+                   const float *mean, const float *v_pred, int64_t p_sn, int64_t p_sf, int64_t p_sp, int64_t p_sv,
+                   const float *samples, const int64_t *ids, const int32_t *num_peds, int P, int V, int K,
+                   const stg_score_state *state, const float *thr, int Q, const stg_score_out *out, void *stream) {
+    stg::ScoreArgs a;
+    const int rc = stg::score_args("stg_score_push", 1, M_max, scale, mean, v_pred, p_sn, p_sf, p_sp, p_sv, samples, ids,
+                                   num_peds, P, V, K, state, thr, Q, out, &a);
+    if (rc != STG_OK) return rc;
+    STG_REQUIRE(det_id && det_xy && det_count, STG_EINVAL, "stg_score_push: null pointer (detections)");
+    hipLaunchKernelGGL(stg::score_push_kernel, dim3(1), dim3(stg::kScoreThreads), stg::score_lds(a),
+                       stg::as_stream(stream), a, det_id, det_xy, det_count);
+    STG_LAUNCH_CHECK("stg_score_push");
+    return STG_OK;
+}
+
+int stg_score_push_streams(const int64_t *det_id, int64_t id_stride, const double *det_xy, int64_t xy_stride,
+                           int M_total, const int32_t *det_start, const int32_t *pushed, int NS, int M_max,
+                           double scale, const float *mean, const float *v_pred, int64_t p_sn, int64_t p_sf,
+                           int64_t p_sp, int64_t p_sv, const float *samples, const int64_t *ids,
+                           const int32_t *num_peds, int P, int V, int K, const stg_score_state *state,
+                           const float *thr, int Q, const stg_score_out *out, void *stream) {
+    STG_REQUIRE(NS >= 0 && M_total >= 0 && id_stride >= 1 && xy_stride >= 2, STG_EINVAL,
+                "stg_score_push_streams: bad sizes NS=%d M_total=%d strides %lld/%lld", NS, M_total,
+                (long long)id_stride, (long long)xy_stride);
+    if (NS == 0) return STG_OK;
+    stg::ScoreArgs a;
+    const int rc = stg::score_args("stg_score_push_streams", NS, M_max, scale, mean, v_pred, p_sn, p_sf, p_sp, p_sv,
+                                   samples, ids, num_peds, P, V, K, state, thr, Q, out, &a);
+    if (rc != STG_OK) return rc;
+    STG_REQUIRE(det_id && det_xy && det_start && pushed, STG_EINVAL,
+                "stg_score_push_streams: null pointer (detections)");
+    STG_REQUIRE(M_total <= STG_TRACK_MAX_TOTAL_DETECTIONS, STG_EUNSUPPORTED,
+                "stg_score_push_streams: M_total=%d above STG_TRACK_MAX_TOTAL_DETECTIONS=%d", M_total,
+                STG_TRACK_MAX_TOTAL_DETECTIONS);
+    hipLaunchKernelGGL(stg::score_push_streams_kernel, dim3((unsigned)NS), dim3(stg::kScoreThreads), stg::score_lds(a),
+                       stg::as_stream(stream), a, det_id, id_stride, det_xy, xy_stride, M_total, det_start, pushed);
+    STG_LAUNCH_CHECK("stg_score_push_streams");
+    return STG_OK;
+}
+
+}  // extern "C"

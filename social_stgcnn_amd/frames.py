@@ -20,6 +20,9 @@ stg_frame_scenes over a recording uploaded once, stg_track_push with the track s
     TrackRule          tracks=TrackRule(min_seen, max_gap) on any of the four: pedestrians with a short history or
                        tracker gaps are predicted too, their missed frames filled by the kernels
     fill_tracks        the fill alone, on a batch of scenes in place (stg_fill_tracks)
+    ScoreSpec          score=ScoreSpec(levels, best_of_k) on the two live predictors: every push also scores the
+                       predictions of the last pred_seq_len pushes against its detections (stg_score_push, DESIGN.md
+                       5.17); `.score`, `.score_totals`, and score_summary for host numbers
 
 The two live predictors are one core, _LivePredictor: the argument checks, the track state, the eager push and its
 capture (the push kernel ahead of predict.Predictor.capture_chain; the capture recipe itself is graphs.py).  Each class
@@ -35,7 +38,7 @@ import torch
 
 from . import ops
 from ._lib import check, lib, peds_arg, ptr, require_gpu, seed_i64, stream_ptr
-from .predict import Prediction, Predictor, eval_mode
+from .predict import Prediction, Predictor, ScoreSpec, eval_mode
 
 MAX_OBS_LEN = 32                       # presence masks are 32-bit
 MAX_DETECTIONS = 2048                  # STG_TRACK_MAX_DETECTIONS
@@ -300,10 +303,26 @@ class _LivePredictor:
     and `seed_dev`, the (1,) int64 device tensor the sampler reads its seed from."""
 
     def __init__(self, model, k, obs_len, capacity, max_peds, max_detections, decimals, risk=None, keep_samples=True,
-                 tracks=None):
+                 tracks=None, score=None):
         self.model = model
         self.k = int(k)
         self._risk_args = (risk, keep_samples)
+        if score is not None:
+            score = score if isinstance(score, ScoreSpec) else ScoreSpec(*score)
+            if score.best_of_k and not keep_samples:
+                raise ValueError("score: ScoreSpec(best_of_k=True) scores the K samples, and keep_samples=False leaves "
+                                 "none (pass ScoreSpec(best_of_k=False) or keep the samples)")
+            if score.best_of_k and not 1 <= self.k <= ops.SCORE_MAX_K:
+                raise ValueError("score: best_of_k needs 1 <= k <= %d, got %d" % (ops.SCORE_MAX_K, self.k))
+            if int(max_peds) > ops.SCORE_MAX_V:
+                raise ValueError("score: max_peds=%d above the score kernel's limit of %d"
+                                 % (int(max_peds), ops.SCORE_MAX_V))
+            if model.pred_seq_len > ops.SCORE_MAX_P:
+                raise ValueError("score: pred_seq_len=%d above the score kernel's limit of %d"
+                                 % (model.pred_seq_len, ops.SCORE_MAX_P))
+        self.score_spec = score
+        self.score = None
+        self._score_state = None
         self.t_obs = _obs_len(obs_len)
         if self.t_obs != model.seq_len:
             raise ValueError("obs_len=%d but the model observes %d frames" % (self.t_obs, model.seq_len))
@@ -329,7 +348,28 @@ class _LivePredictor:
         self.ring = torch.zeros(lead + (self.t_obs, self.s, 2), device=dev, dtype=torch.float64)
         self.head_flags = torch.empty(lead + (2,), device=dev, dtype=torch.int32)
         self._pred = Predictor(self.model, self.k, *self._risk_args)
+        if self.score_spec is not None:
+            spec = self.score_spec
+            self._score_state = ops.score_state(lead[0] if lead else 1, self.model.pred_seq_len, self.v, self.k, dev,
+                                                spec.best_of_k, len(spec.levels))
+            self._thr = torch.tensor(spec.thresholds, dtype=torch.float32).to(dev) if spec.levels else None
         return dev
+
+    @property
+    def score_totals(self):
+        """With score=ScoreSpec(...): the running totals on the device since reset(), (totals (NS,P,5+Q) float64,
+        traj_totals (NS,5) float64) as ops.ScoreState describes them (NS = 1 for a FramePredictor); reading them is the
+        caller's synchronisation -- frames.score_summary turns them into host numbers.  None without a ScoreSpec."""
+        st = self._score_state
+        return None if st is None else (st.totals, st.traj_totals)
+
+    def _score_push(self, outs, r, out=None):
+        """The score launch of one push, behind the sampler (and the risk counts): the pending predictions against this
+        push's detections, then this push's prediction into the records (ops.score_push)."""
+        ns = self._score_state.head.shape[0]
+        return ops.score_push(self._score_state, self._thr, r.mean, r.v_pred,
+                              r.samples if self.score_spec.best_of_k else None, outs[1].view(ns, self.v), outs[2],
+                              out=out, **self._score_det())
 
     @property
     def risk(self):
@@ -359,6 +399,8 @@ class _LivePredictor:
             self.seen = outs[-1]
         with eval_mode(self.model):
             r = self._pred._forward(outs[0], outs[2], 0, noise, self.seed_dev)
+        if self.score_spec is not None:
+            self.score = self._score_push(outs, r)
         return self._wrap(outs, r, False)
 
     @torch.no_grad()
@@ -366,22 +408,28 @@ class _LivePredictor:
         """Capture ONE linear graph: the push kernel -> observed_inputs -> forward -> stg_sample_trajectories on static
         buffers, the seed read from `seed_dev` (Predictor.capture_chain).  Returns replay(*det, seed=None) -> the
         result on the static outputs, overwritten by the next replay; the detections are staged outside the graph.
-        Warm-up and capture leave the track state as it was."""
+        Warm-up and capture leave the track state as it was, and with it the score records and totals."""
         outs = self._outs()
         saved = self._still()
+        scored = None
+        if self.score_spec is not None:
+            scored = ops.score_buffers(self._score_state.head.shape[0], self.model.pred_seq_len, self.v, self.device,
+                                       self.score_spec.best_of_k)
         try:
-            graph, r, chain = self._pred.capture_chain(outs[0], outs[2], self.seed_dev, warmup,
-                                                       pre=lambda: self._push(outs))
+            graph, r, chain = self._pred.capture_chain(
+                outs[0], outs[2], self.seed_dev, warmup, pre=lambda: self._push(outs),
+                post=None if scored is None else lambda res: self._score_push(outs, res, scored))
         finally:
             for x, x0 in saved:
                 x.copy_(x0)
         res = self._wrap(outs, r, True)
         # every buffer the graph reads or writes lives as long as the returned replay
-        static = (outs, chain, graph)
+        static = (outs, chain, graph, scored)
 
         def replay(*det, seed=None):
             self._stage(*det, seed)
             static[2].replay()
+            self.score = static[3]
             if self.rule is not None:
                 self.seen = static[0][-1]
             return res
@@ -396,11 +444,15 @@ class FramePredictor(_LivePredictor):
     (stg_track_push): `capacity` slots, a slot freed once its pedestrian has been missing for obs_len - 1 frames.  Ids
     come from the caller's tracker (association is not done here).  tracks: a TrackRule -- the scene holds the
     pedestrians that rule admits, their missed frames filled (stg_track_push_rule); `.seen` (V,) int32 then holds the
-    presence bits of the last push's scene slots (from a captured push the graph's static buffer, like `.risk`)."""
+    presence bits of the last push's scene slots (from a captured push the graph's static buffer, like `.risk`).
+    score: a predict.ScoreSpec -- every push also scores the predictions of the last pred_seq_len pushes against its
+    detections (stg_score_push, behind the sampler): `.score` holds the push's ops.Score (leading axis 1; from a captured
+    push the graph's static tensors) and `.score_totals` the running totals on the device."""
 
     def __init__(self, model, k=20, obs_len=8, capacity=1024, max_peds=128, max_detections=1024, decimals=4,
-                 risk=None, keep_samples=True, tracks=None):
-        super().__init__(model, k, obs_len, capacity, max_peds, max_detections, decimals, risk, keep_samples, tracks)
+                 risk=None, keep_samples=True, tracks=None, score=None):
+        super().__init__(model, k, obs_len, capacity, max_peds, max_detections, decimals, risk, keep_samples, tracks,
+                         score)
         dev, m = self._track_state(), self.m_max
         self.det_id = torch.zeros(m, device=dev, dtype=torch.int64)
         self.det_xy = torch.zeros((m, 2), device=dev, dtype=torch.float64)
@@ -409,10 +461,16 @@ class FramePredictor(_LivePredictor):
         self.reset()
 
     def reset(self):
-        """Forget every track (the next obs_len - 1 pushes return empty scenes)."""
+        """Forget every track (the next obs_len - 1 pushes return empty scenes), and with score= the pending records
+        and the running totals."""
         self.slot_id.fill_(-1)
         self.mask.zero_()
         self.head_flags.zero_()
+        if self._score_state is not None:
+            ops.score_reset(self._score_state)
+
+    def _score_det(self):
+        return dict(det_id=self.det_id, det_xy=self.det_xy, det_count=self.det_count, m_max=self.m_max, scale=self.scale)
 
     def _stage(self, ids, xy, seed):
         """Copy one frame of detections (host arrays or device tensors) into the device buffers the push reads."""
@@ -462,7 +520,10 @@ class FramePredictor(_LivePredictor):
 
     def _still(self):
         """The warm-up pushes frames without detections, which age the tracks: the state goes back after it."""
-        saved = [(x, x.clone()) for x in (self.slot_id, self.mask, self.ring, self.head_flags, self.det_count)]
+        state = (self.slot_id, self.mask, self.ring, self.head_flags, self.det_count)
+        if self._score_state is not None:                    # an empty push is a push: it scores and enqueues
+            state += tuple(x for x in self._score_state if x is not None)
+        saved = [(x, x.clone()) for x in state]
         self.det_count.zero_()
         return saved
 
@@ -567,11 +628,16 @@ class StreamsPredictor(_LivePredictor):
     zones (Z,4) for every stream or (NS,Z,4) per stream) and keep_samples as in predict.Predictor: the tick's counts are
     at `.risk`, 5.4 MB of int32 counts at 600 streams padded to 128 pedestrians, where the samples are 147 MB.
     tracks: a TrackRule for every stream, as in FramePredictor (stg_track_push_streams_rule); `.seen` is (NS,V), zero
-    for a stream not pushed."""
+    for a stream not pushed.  score: a predict.ScoreSpec for every stream, as in FramePredictor
+    (stg_score_push_streams, one workgroup per stream): `.score` is the tick's ops.Score with the streams leading, all
+    zero for a stream not pushed, `.score_totals` the per-stream totals.  With best_of_k the records keep every push's
+    samples for pred_seq_len pushes: about 3.5 MB per stream at 12 steps, 128 pedestrians and k = 20, so 600 streams
+    hold about 2.1 GB (0.4 MB per stream with ScoreSpec(best_of_k=False))."""
 
     def __init__(self, model, streams, k=20, obs_len=8, capacity=1024, max_peds=128, max_detections=1024, decimals=4,
-                 max_total_detections=None, block_threads=0, risk=None, keep_samples=True, tracks=None):
-        super().__init__(model, k, obs_len, capacity, max_peds, max_detections, decimals, risk, keep_samples, tracks)
+                 max_total_detections=None, block_threads=0, risk=None, keep_samples=True, tracks=None, score=None):
+        super().__init__(model, k, obs_len, capacity, max_peds, max_detections, decimals, risk, keep_samples, tracks,
+                         score)
         if not _is_int(streams, 1, MAX_STREAMS):
             raise ValueError("streams must be an integer in [1, %d], got %r" % (MAX_STREAMS, streams))
         self.ns = int(streams)
@@ -613,12 +679,15 @@ class StreamsPredictor(_LivePredictor):
 
     def reset(self, streams=None):
         """Forget every track of all streams, or of the listed stream indices only (their next obs_len - 1 pushes
-        return empty scenes; the other streams go on)."""
+        return empty scenes; the other streams go on).  With score= their pending records and running totals are
+        cleared with them."""
         if streams is None:
             self.slot_id.fill_(-1)
             self.mask.zero_()
             self.ring.zero_()
             self.head_flags.zero_()
+            if self._score_state is not None:
+                ops.score_reset(self._score_state)
             return
         idx = [int(x) for x in (streams if isinstance(streams, (list, tuple, np.ndarray, range)) else [streams])]
         for x in idx:
@@ -631,6 +700,13 @@ class StreamsPredictor(_LivePredictor):
         self.mask.index_fill_(0, at, 0)
         self.ring.index_fill_(0, at, 0.0)
         self.head_flags.index_fill_(0, at, 0)
+        if self._score_state is not None:
+            ops.score_reset(self._score_state, at)
+
+    def _score_det(self):
+        return dict(det_id=ptr(self._rec_i), id_stride=3, det_xy=ctypes.c_void_p(self._rec_f.data_ptr() + 8),
+                    xy_stride=3, m_total=self.cap, det_start=self.det_start, pushed=self.pushed_dev, m_max=self.m_max,
+                    scale=self.scale)
 
     def _wait_host(self):
         """The pinned buffer is rewritten only after the previous tick's copy has left it."""
@@ -726,7 +802,39 @@ class StreamsPredictor(_LivePredictor):
         return StreamsPrediction(ids, peds, obs, r.samples, r.mean, r.v_pred, flags, pushed)
 
     def _still(self):
-        """Warm-up and capture run with no stream pushed, so no stream's state moves and nothing is put back."""
+        """Warm-up and capture run with no stream pushed, so no stream's state moves -- its score records and totals
+        included: a stream not pushed keeps them bit for bit -- and nothing is put back."""
         self.det_start.zero_()
         self.pushed_dev.zero_()
         return ()
+
+
+ScoreSummary = collections.namedtuple("ScoreSummary", "count err d2 nll best coverage trajectories ade fde ade_mean "
+                                                      "fde_mean levels")
+ScoreSummary.__doc__ = """Host numbers of the running score totals, numpy float64 with the totals' leading axes: per
+horizon h = 1..P (last axis) count (matched pedestrians), err (mean displacement of the zero-noise trajectory), d2 (mean
+squared Mahalanobis distance: 2 for a calibrated bivariate Gaussian), nll (mean negative log-likelihood) and best (mean
+best-of-K displacement); coverage (...,P,Q): the fraction with d2 inside the ellipse of each level (calibrated: the level
+itself); over the full trajectories (every one of the P steps matched): trajectories (their number), ade / fde (best-of-K,
+as the reference reports them) and ade_mean / fde_mean (zero-noise).  NaN where nothing was counted."""
+
+
+def score_summary(totals, traj_totals, levels=()):
+    """The totals of `.score_totals` (device tensors or arrays, (...,P,5+Q) and (...,5)) as a ScoreSummary.  Reading
+    device totals synchronises with the stream: this is the one place where scoring waits for the device, and only when
+    the caller asks."""
+    tot = np.asarray(totals.cpu() if torch.is_tensor(totals) else totals, dtype=np.float64)
+    trj = np.asarray(traj_totals.cpu() if torch.is_tensor(traj_totals) else traj_totals, dtype=np.float64)
+    levels = tuple(float(x) for x in levels)
+    if tot.ndim < 2 or tot.shape[-1] != 5 + len(levels):
+        raise ValueError("score_summary: totals (...,P,5+%d) expected for %d levels, got %s"
+                         % (len(levels), len(levels), tot.shape))
+    if trj.shape != tot.shape[:-2] + (5,):
+        raise ValueError("score_summary: traj_totals %s expected, got %s" % (tot.shape[:-2] + (5,), trj.shape))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        n = tot[..., 0]
+        per = [np.where(n > 0, tot[..., i] / n, np.nan) for i in range(1, 5)]
+        cover = np.where(n[..., None] > 0, tot[..., 5:] / n[..., None], np.nan)
+        nt = trj[..., 0]
+        full = [np.where(nt > 0, trj[..., i] / nt, np.nan) for i in range(1, 5)]
+    return ScoreSummary(n, per[0], per[1], per[2], per[3], cover, nt, full[0], full[1], full[2], full[3], levels)

@@ -720,6 +720,152 @@ def sample_risk(y, obs_last=None, num_peds=None, k=20, radius=None, zones=None, 
     return out
 
 
+ScoreState = collections.namedtuple("ScoreState", "rec_ids rec_peds rec_mean rec_cov rec_samples acc acc_mean steps head "
+                                                 "totals traj_totals")
+ScoreState.__doc__ = """The device state of `score_push` (stg_score_state), NS leading: the ring of P records per stream
+-- rec_ids (NS,P,V) int64, rec_peds (NS,P) int32, rec_mean (NS,P,P,V,2), rec_cov (NS,P,P,V,3), rec_samples
+(NS,P,K,P,V,2) and the accumulators acc (NS,P,K,V), acc_mean (NS,P,V) float32, steps (NS,P,V) int32 --, head (NS,2) int32
+{ring row of the next push, records that exist}, and the running totals: totals (NS,P,5+Q) float64 = per horizon
+{matched, sum err, sum d2, sum nll, sum best, #(d2 <= thr_q)}, traj_totals (NS,5) float64 = {full trajectories, the sums of
+their traj_ade, traj_fde, traj_ade_mean, traj_fde_mean}.  rec_samples and acc are None when samples are not scored."""
+Score = collections.namedtuple("Score", "rec_ids matched err d2 nll best traj_steps traj_ade traj_fde traj_ade_mean "
+                                        "traj_fde_mean")
+Score.__doc__ = """One push scored (`stg_score_push`), NS leading.  Row h-1 of the (NS,P,V) fields is the prediction made
+h pushes ago, scored at its step h against this push's detections: rec_ids int64 (the id where matched, else -1),
+matched int32, err (displacement of the mean trajectory), d2 (squared Mahalanobis distance under the predicted
+Gaussian), nll and best (min over the K samples) float32.  The (NS,V) fields are the record that turned P pushes old:
+traj_steps int32 (the steps at which its pedestrian was matched), traj_ade / traj_fde (best-of-K; the reference's ADE /
+FDE where traj_steps == P) and traj_ade_mean / traj_fde_mean (the zero-noise trajectory).  Unmatched and padded entries
+are 0.  best, traj_ade and traj_fde are None when samples are not scored."""
+SCORE_MAX_V, SCORE_MAX_K, SCORE_MAX_P, SCORE_MAX_Q = 256, 64, 32, 4          # STG_SCORE_MAX_*
+
+
+def score_thresholds(levels):
+    """Probability levels -> the d2 thresholds of a bivariate Gaussian: P(d2 <= thr) = p for thr = -2 ln(1 - p) (d2 is
+    chi-square with two degrees of freedom).  At most SCORE_MAX_Q levels, each in (0, 1)."""
+    levels = [float(x) for x in levels]
+    if len(levels) > SCORE_MAX_Q:
+        raise ValueError("score: at most %d levels, got %d" % (SCORE_MAX_Q, len(levels)))
+    for x in levels:
+        if not 0.0 < x < 1.0:
+            raise ValueError("score: a level must lie in (0, 1), got %r" % (x,))
+    return [-2.0 * math.log1p(-x) for x in levels]
+
+
+def score_state(ns, p, v, k, device, samples=True, q=3):
+    """A cleared ScoreState for ns streams, horizons p, scenes padded to v pedestrians, k samples and q coverage
+    thresholds.  samples=False (or k = 0): the samples are not kept and nothing sample-based is scored.
+    Size: with samples P*V*(8 + 20P + 8KP + 4K + 8) bytes per stream -- about 3.5 MB at P 12, V 128, K 20, so 600
+    streams hold about 2.1 GB --, about 0.4 MB per stream without samples; the totals add 8P(5+q) + 40 bytes."""
+    ns, p, v, k, q = int(ns), int(p), int(v), int(k) if samples else 0, int(q)
+    for what, got, most in (("V", v, SCORE_MAX_V), ("k", k, SCORE_MAX_K), ("P", p, SCORE_MAX_P), ("q", q, SCORE_MAX_Q)):
+        if got > most:
+            raise ValueError("score_state: %s=%d above the kernel's limit of %d" % (what, got, most))
+    if ns < 1 or p < 1 or v < 1 or k < 0 or q < 0:
+        raise ValueError("score_state: bad sizes ns=%d p=%d v=%d k=%d q=%d" % (ns, p, v, k, q))
+
+    def z(dtype, *shape):
+        return torch.zeros(shape, device=device, dtype=dtype)
+    f32, i32 = torch.float32, torch.int32
+    return ScoreState(torch.full((ns, p, v), -1, device=device, dtype=torch.int64), z(i32, ns, p), z(f32, ns, p, p, v, 2),
+                      z(f32, ns, p, p, v, 3), z(f32, ns, p, k, p, v, 2) if k else None, z(f32, ns, p, k, v) if k else None,
+                      z(f32, ns, p, v), z(i32, ns, p, v), z(i32, ns, 2), z(torch.float64, ns, p, 5 + q),
+                      z(torch.float64, ns, 5))
+
+
+def score_reset(state, streams=None):
+    """Clear records and totals of every stream, or of the stream indices in the int64 device tensor `streams`."""
+    for name, x in zip(ScoreState._fields, state):
+        if x is None:
+            continue
+        fill = -1 if name == "rec_ids" else 0
+        if streams is None:
+            x.fill_(fill)
+        else:
+            x.index_fill_(0, streams, fill)
+
+
+def score_buffers(ns, p, v, device, samples=True):
+    """An empty Score for ns streams (graph capture: the outputs `score_push(out=...)` fills)."""
+    def e(dtype, *shape):
+        return torch.empty(shape, device=device, dtype=dtype)
+    f32, i32 = torch.float32, torch.int32
+    return Score(e(torch.int64, ns, p, v), e(i32, ns, p, v), e(f32, ns, p, v), e(f32, ns, p, v), e(f32, ns, p, v),
+                 e(f32, ns, p, v) if samples else None, e(i32, ns, v), e(f32, ns, v) if samples else None,
+                 e(f32, ns, v) if samples else None, e(f32, ns, v), e(f32, ns, v))
+
+
+def _dev_ptr(x):
+    return x if x is None or isinstance(x, ctypes.c_void_p) else ptr(x)
+
+
+def score_push(state, thr, mean, v_pred, samples, ids, num_peds, det_id, det_xy, m_max, scale, det_count=None,
+               det_start=None, pushed=None, id_stride=1, xy_stride=2, m_total=None, out=None):
+    """Score the pending predictions of every stream against one push of detections, then enqueue this push's
+    prediction (`stg_score_push` / `stg_score_push_streams`; the rule: DESIGN.md 5.17).  state: a ScoreState; thr: (Q,)
+    float32 device tensor of d2 thresholds (score_thresholds) or None; the prediction as the chain leaves it: mean
+    (NS,P,V,2), v_pred (NS,5,P,V) (any strides), samples (K,NS,P,V,2) or None, ids (NS,V) int64, num_peds (NS,) int32;
+    scale = 10^decimals of the push's rounding (0: none).  The detections are device memory, tensors or raw pointers:
+    with det_count ((1,) int32) one stream's det_id (m_max,), det_xy (m_max,2) as stg_track_push reads them; with
+    det_start (NS+1,) and pushed (NS,) int32 the packed tick of stg_track_push_streams (id_stride, xy_stride, m_total).
+    out: an earlier Score to fill (graph capture).  No host synchronisation.  Returns a Score."""
+    require_gpu(mean, v_pred, samples, ids, num_peds, *[x for x in state if x is not None])
+    if v_pred.dim() != 4 or v_pred.shape[1] != 5:
+        raise ValueError("score_push: v_pred (NS,5,P,V) expected")
+    ns, _, p, v = v_pred.shape
+    _lib.as_f32(v_pred, "v_pred")
+    if tuple(mean.shape) != (ns, p, v, 2) or mean.dtype != torch.float32 or not mean.is_contiguous():
+        raise ValueError("score_push: mean must be a contiguous float32 (NS,P,V,2) tensor")
+    k = 0 if samples is None or state.rec_samples is None else samples.shape[0]
+    if k and (tuple(samples.shape) != (k, ns, p, v, 2) or samples.dtype != torch.float32 or not samples.is_contiguous()):
+        raise ValueError("score_push: samples must be a contiguous float32 (K,NS,P,V,2) tensor")
+    if ids.numel() != ns * v or ids.dtype != torch.int64 or not ids.is_contiguous():
+        raise ValueError("score_push: ids must be a contiguous int64 (NS,V) tensor")
+    if num_peds.numel() != ns or num_peds.dtype != torch.int32:
+        raise ValueError("score_push: num_peds must be an int32 (NS,) tensor")
+    q = state.totals.shape[2] - 5
+    want = dict(rec_ids=(ns, p, v), rec_peds=(ns, p), rec_mean=(ns, p, p, v, 2), rec_cov=(ns, p, p, v, 3),
+                rec_samples=(ns, p, k, p, v, 2), acc=(ns, p, k, v), acc_mean=(ns, p, v), steps=(ns, p, v), head=(ns, 2),
+                totals=(ns, p, 5 + q), traj_totals=(ns, 5))
+    for name, x in zip(ScoreState._fields, state):
+        if k == 0 and name in ("rec_samples", "acc"):
+            continue
+        if x is None or tuple(x.shape) != want[name] or not x.is_contiguous():
+            raise ValueError("score_push: state.%s does not fit this call (%s expected)" % (name, want[name]))
+    if q and (thr is None or thr.numel() != q or thr.dtype != torch.float32 or not thr.is_cuda):
+        raise ValueError("score_push: thr must be a float32 device tensor of %d thresholds" % q)
+    for what, got, most in (("V", v, SCORE_MAX_V), ("K", k, SCORE_MAX_K), ("P", p, SCORE_MAX_P), ("Q", q, SCORE_MAX_Q)):
+        if got > most:
+            raise ValueError("score_push: %s=%d above the kernel's limit of %d" % (what, got, most))
+    if out is None:
+        out = score_buffers(ns, p, v, mean.device, k > 0)
+    else:
+        for name, o, w in zip(Score._fields, out, score_buffers(ns, p, v, "meta", k > 0)):
+            if (o is None) != (w is None) or (o is not None and (
+                    tuple(o.shape) != tuple(w.shape) or o.dtype != w.dtype or not o.is_contiguous() or not o.is_cuda)):
+                raise ValueError("score_push: out.%s does not fit this call" % name)
+    st = _lib.ScoreState(*[None if (x is None or (k == 0 and name in ("rec_samples", "acc"))) else x.data_ptr()
+                           for name, x in zip(ScoreState._fields, state)])
+    so = _lib.ScoreOut(*[None if o is None else o.data_ptr() for o in out])
+    sn, sf, sp, sv = v_pred.stride()
+    pred = (ptr(mean), ptr(v_pred), sn, sf, sp, sv, ptr(samples) if k else None, ptr(ids), ptr(num_peds), p, v, k,
+            ctypes.byref(st), ptr(thr) if q else None, q, ctypes.byref(so), stream_ptr())
+    if (det_count is None) == (det_start is None):
+        raise ValueError("score_push: pass det_count (one stream) or det_start and pushed (a packed tick)")
+    if det_count is not None:
+        if ns != 1:
+            raise ValueError("score_push: det_count serves one stream, the prediction holds %d" % ns)
+        check(lib().stg_score_push(_dev_ptr(det_id), _dev_ptr(det_xy), _dev_ptr(det_count), int(m_max),
+                                   ctypes.c_double(scale), *pred), "stg_score_push")
+    else:
+        if pushed is None or m_total is None:
+            raise ValueError("score_push: det_start needs pushed and m_total")
+        check(lib().stg_score_push_streams(_dev_ptr(det_id), int(id_stride), _dev_ptr(det_xy), int(xy_stride),
+                                           int(m_total), _dev_ptr(det_start), _dev_ptr(pushed), ns, int(m_max),
+                                           ctypes.c_double(scale), *pred), "stg_score_push_streams")
+    return out
+
+
 def scene_order(num_peds, v):
     """Scene indices sorted by pedestrian count (clamped to [0, v]) descending, stable: the schedule the fused
     kernels use for ragged batches (`stg_scene_order`).  num_peds: int32 device tensor (N,).

@@ -7,6 +7,7 @@ test_v.py / visualize.py read.
                       (`predict`) or as ONE captured graph (`capture`; `capture_chain` is the same chain on the
                       caller's static inputs, which frames.py puts behind its push kernels).  With `risk=RiskSpec(...)`
                       the chain ends in stg_sample_risk: conflict and zone-occupancy counts over the K samples
+    ScoreSpec         what the live predictors (frames.py) score their predictions for once the truth has arrived
     sample_test       test() over data.SceneWindows: (ade, fde, raw_data_dict)
 """
 import collections
@@ -27,6 +28,27 @@ RiskSpec = collections.namedtuple("RiskSpec", "radius zones pairs", defaults=(No
 RiskSpec.__doc__ = """What a Predictor reduces its K samples to (ops.sample_risk): radius (two pedestrians closer than
 this conflict; None: no conflict counts), zones ((Z,4) rectangles [x0,y0,x1,y1] for every scene or (N,Z,4) per scene;
 None: no zone counts), pairs (also the (N,V,V) pair counts)."""
+
+
+class ScoreSpec(collections.namedtuple("ScoreSpec", "levels best_of_k")):
+    """What a live predictor scores its predictions for, once the tracker has delivered the positions they predicted
+    (ops.score_push).  levels: at most four probability levels in (0, 1) -- the running totals count how
+    often the truth fell inside the predicted Gaussian's ellipse of that level (d2 <= -2 ln(1 - p)), the calibration
+    check; best_of_k: also keep each push's K samples on the device and score best-of-K ADE / FDE as the paper defines
+    them (needs the predictor's samples: not with keep_samples=False)."""
+    __slots__ = ()
+
+    def __new__(cls, levels=(0.5, 0.9, 0.99), best_of_k=True):
+        levels = tuple(float(x) for x in levels)
+        ops.score_thresholds(levels)                       # refuses a level outside (0, 1) and more than four of them
+        if not isinstance(best_of_k, (bool, np.bool_)):
+            raise ValueError("ScoreSpec: best_of_k must be True or False, got %r" % (best_of_k,))
+        return super().__new__(cls, levels, bool(best_of_k))
+
+    @property
+    def thresholds(self):
+        """The d2 thresholds of the levels, -2 ln(1 - p)."""
+        return ops.score_thresholds(self.levels)
 
 
 def observed_inputs(obs_abs, num_peds=None, out=None):
@@ -137,12 +159,13 @@ class Predictor:
                  torch.empty((n, p, v, 2), **f32)), risk)
 
     @torch.no_grad()
-    def capture_chain(self, obs, peds, seed_dev, warmup=2, pre=None):
+    def capture_chain(self, obs, peds, seed_dev, warmup=2, pre=None, post=None):
         """Capture ONE graph on the static obs (N,T_obs,V,2), peds (N,) int32 and seed_dev (1,) int64: [pre() ->]
         observed_inputs -> fused forward -> stg_sample_trajectories, the model in eval mode, the seed read from
         seed_dev (and stg_sample_risk into the static `self.risk` with a RiskSpec).  `pre` (optional callable) runs
-        inside the graph ahead of the chain -- the live predictors' push launch, which fills obs and peds; it runs in
-        the warm-up too.  Returns (graph, the static Prediction, the
+        inside the graph ahead of the chain -- the live predictors' push launch, which fills obs and peds; `post`
+        (optional callable) is given the chain's Prediction and runs inside the graph behind it -- the live predictors'
+        score launch; both run in the warm-up too.  Returns (graph, the static Prediction, the
         chain's own buffers): every buffer the graph reads or writes has to live as long as the graph is replayed -- a
         freed one would go back to the caching allocator while the graph still writes it."""
         n, _, v, _ = obs.shape
@@ -151,7 +174,10 @@ class Predictor:
         def step():
             if pre is not None:
                 pre()
-            return self._forward(obs, peds, 0, None, seed_dev, bufs, outs, risk)
+            r = self._forward(obs, peds, 0, None, seed_dev, bufs, outs, risk)
+            if post is not None:
+                post(r)
+            return r
         with eval_mode(self.model):
             graph, res = graphs.warm_capture(step, warmup)
         return graph, res, (bufs, outs, risk, self.zones)

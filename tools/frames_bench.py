@@ -4,6 +4,7 @@
     python tools/frames_bench.py [--pushes 2000] [--cases latency,recording] [--k 20]
     python tools/frames_bench.py --cases streams [--streams 1,8,64,256,600] [--ticks 200] [--block 0] [--no-lone]
                                  [--risk none,samples,lean]
+    python tools/frames_bench.py --cases score [--streams 1,64,600] [--ticks 200]
     python tools/frames_bench.py --tracks 2,2 ...       every case under frames.TrackRule(2, 2) (the *_rule kernels)
 
   latency    the captured FramePredictor (ONE graph: stg_track_push -> observed_inputs -> forward -> sampler) pushed
@@ -20,6 +21,10 @@
              (0: the default); --no-lone skips the yardstick.  --risk: the modes to time -- none (the default: no
              reducer), samples (RiskSpec(0.5, three rectangles): stg_sample_risk after the sampler) and lean (the same
              with keep_samples=False); result_mb is what a tick leaves for the caller (samples + mean + counts).
+
+  score      the streams case with and without score=ScoreSpec() (stg_score_push_streams behind the sampler, inside the
+             graph) at NS = 1, 64 and 600 (or --streams), no yardstick: tick p50 / p90 of both, the difference, what
+             the score records hold on the device (state_mb) and the running summary at the last tick.
 
 Kernel times come from a separate run under the profiler (tracing slows the host):
     rocprofv3 --kernel-trace --stats -d OUT -o frames -- python tools/frames_bench.py --cases latency --pushes 500
@@ -120,11 +125,12 @@ def _stream_sequences(ns, n):
     return out
 
 
-def streams_case(ns, k, n_ticks, dev, block=0, lone=True, max_peds=128, warmup=20, risk="none", tracks=None):
+def streams_case(ns, k, n_ticks, dev, block=0, lone=True, max_peds=128, warmup=20, risk="none", tracks=None,
+                 score=None):
     from social_stgcnn_amd import frames
     model = model_for("univ", dev)
     seq = _stream_sequences(ns, warmup + n_ticks)
-    kw = {}
+    kw = {} if score is None else {"score": score}
     if risk != "none":
         from social_stgcnn_amd.predict import RiskSpec
         kw = dict(risk=RiskSpec(0.5, np.array([[-1, -1, 1, 1], [0, 0, 4, 3], [-50, -50, 50, 50]], np.float32)),
@@ -155,6 +161,14 @@ def streams_case(ns, k, n_ticks, dev, block=0, lone=True, max_peds=128, warmup=2
         res["conflict_any_mean"] = round(float(sp.risk.conflict_any.float().mean()), 3)
     counts = 0 if risk == "none" else sum(x.numel() for x in sp.risk[1:] if x is not None)
     res["result_mb"] = round((out.samples.numel() + out.mean.numel() + counts) * 4 / 1e6, 3)
+    if score is not None:
+        st = sp._score_state
+        s = frames.score_summary(*sp.score_totals, score.levels)
+        n = s.count.sum(axis=0)
+        res.update({"state_mb": round(sum(x.numel() * x.element_size() for x in st if x is not None) / 1e6, 1),
+                    "scored": int(n.sum()), "trajectories": int(s.trajectories.sum()),
+                    "err_h1": round(float(np.nansum(s.err[:, 0] * s.count[:, 0]) / max(1.0, n[0])), 4),
+                    "err_hP": round(float(np.nansum(s.err[:, -1] * s.count[:, -1]) / max(1.0, n[-1])), 4)})
     if lone:
         # the yardstick: NS lone captured FramePredictors, one after another; fewer ticks at large NS
         n_seq = max(10, min(n_ticks, 4000 // ns))
@@ -205,6 +219,15 @@ def main():
     if "recording" in cases:
         for split, rec in TEST_RECORDINGS:
             print(json.dumps(recording_case(split, rec, a.k, dev, tracks)), flush=True)
+    if "score" in cases:
+        from social_stgcnn_amd.predict import ScoreSpec
+        for ns in (int(n) for n in (a.streams if a.streams != "1,8,64,256,600" else "1,64,600").split(",")):
+            off = streams_case(ns, a.k, a.ticks, dev, 0, False, tracks=tracks)
+            on = streams_case(ns, a.k, a.ticks, dev, 0, False, tracks=tracks, score=ScoreSpec())
+            on.update({"case": "score", "tick_p50_ms_without": off["tick_p50_ms"],
+                       "tick_p90_ms_without": off["tick_p90_ms"],
+                       "score_cost_p50_ms": round(on["tick_p50_ms"] - off["tick_p50_ms"], 4)})
+            print(json.dumps(on), flush=True)
     if "streams" in cases:
         for block in (int(b) for b in a.block.split(",")):
             for ns in (int(n) for n in a.streams.split(",")):
