@@ -13,7 +13,7 @@
 //   stg_track_push_streams  NS live streams: one workgroup per stream runs the same push (track_push_body) on the
 //                           stream's slice of the state and its range of one packed tick of detections; the counts,
 //                           offsets and pushed flags are read from device memory, so one captured graph serves a tick.
-//
+// The pushes sort their detections and look ids up with detections.hpp, as the score kernels do.
 //
 // Partially observed tracks: TrackRule below admits a pedestrian with a short history or tracker gaps
 // and fills the frames it missed.  stg_fill_tracks applies the fill to a batch in place; the *_rule entry points are
@@ -22,7 +22,7 @@
 //
 // Pure data movement and integer work: a few KB per frame.  No host synchronisation in the launch functions (the push
 // is captured into the per-frame graph of FramePredictor.capture) and plain C++ stores only.
-#include "common.hpp"
+#include "detections.hpp"
 
 namespace stg {
 
@@ -33,19 +33,10 @@ constexpr int kStreamThreads = 256;
 constexpr int kFlagDuplicate = STG_TRACK_DUPLICATE, kFlagOverflow = STG_TRACK_OVERFLOW,
               kFlagTruncated = STG_TRACK_TRUNCATED, kFlagTooMany = STG_TRACK_TOO_MANY;
 
-// np.around(x, decimals) for decimals >= 0: x * 10^d, round half to even, / 10^d (scale <= 0: no rounding)
-__device__ __forceinline__ double round_pos(double x, double scale) { return scale > 0.0 ? rint(x * scale) / scale : x; }
-
 // row index of `id` in frame g (frame_start offsets, ids sorted by id inside each frame), or -1
 __device__ __forceinline__ int row_of(const int32_t *__restrict__ fs, const int64_t *__restrict__ ids, int g, int64_t id) {
-    int lo = fs[g], hi = fs[g + 1];
-    const int end = hi;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (ids[mid] < id) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo < end && ids[lo] == id ? lo : -1;
+    const int lo = fs[g], at = det_find(ids + lo, fs[g + 1] - lo, id);
+    return at < 0 ? -1 : lo + at;
 }
 
 // lanes below this one whose bit is set in a wave ballot
@@ -333,38 +324,16 @@ __device__ __forceinline__ int track_push_body(const int64_t *__restrict__ det_i
         smask[s] = mk;
         if (mk == 0) slot_id[s] = -1;
     }
-    int n2 = 1;                                             // sort size: next power of two >= m (<= M2)
-    while (n2 < m) n2 <<= 1;
-    for (int p = tid; p < n2; p += nt) {
-        key[p] = p < m ? det_id[p * id_stride] : INT64_MAX;
-        kidx[p] = p;
-    }
+    const int n2 = det_sort_n(m);                           // (<= M2)
+    det_load(key, kidx, det_id, id_stride, m, n2, tid, nt);
     for (int j = tid; j < m; j += nt) det_slot[j] = -1;
     __syncthreads();
 
-    // 2. sort the detections by (id, detection index): bitonic network over n2 entries (all keys are distinct)
-    for (int k = 2; k <= n2; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < n2; i += nt) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const int64_t a = key[i], b = key[l];
-                    const int ia = kidx[i], ib = kidx[l];
-                    const bool gt = a > b || (a == b && ia > ib);
-                    if (gt == ((i & k) == 0)) {
-                        key[i] = b;
-                        key[l] = a;
-                        kidx[i] = ib;
-                        kidx[l] = ia;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
+    // 2. sort the detections by (id, detection index)
+    det_sort(key, kidx, n2, tid, nt);
 
     // 3. a repeated id: the first detection wins, the others are dropped.  Every live slot finds its id among the
-    //    detections (lower bound in the sorted keys = the winner).
+    //    detections (det_find: the winner).
     for (int p = tid; p < m; p += nt)
         if (p > 0 && key[p] == key[p - 1]) {
             det_slot[kidx[p]] = -2;
@@ -372,14 +341,8 @@ __device__ __forceinline__ int track_push_body(const int64_t *__restrict__ det_i
         }
     for (int s = tid; s < S; s += nt) {
         if (smask[s] == 0) continue;
-        const int64_t id = slot_id[s];
-        int lo = 0, hi = m;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (key[mid] < id) lo = mid + 1;
-            else hi = mid;
-        }
-        if (lo < m && key[lo] == id) det_slot[kidx[lo]] = s;
+        const int at = det_find(key, m, slot_id[s]);
+        if (at >= 0) det_slot[kidx[at]] = s;
     }
     __syncthreads();
 
@@ -533,11 +496,10 @@ __device__ __forceinline__ void track_push_stream(
         }
         return;
     }
-    int lo = det_start[b], hi = det_start[b + 1];
-    lo = lo < 0 ? 0 : (lo > M_total ? M_total : lo);
-    hi = hi < lo ? lo : (hi > M_total ? M_total : hi);
+    int lo;
+    const int count = det_range(det_start, b, M_total, lo);
     const int flags = track_push_body<kThreads, kRule>(
-        det_id + lo * id_stride, id_stride, det_xy + lo * xy_stride, xy_stride, hi - lo, M_max, M2,
+        det_id + lo * id_stride, id_stride, det_xy + lo * xy_stride, xy_stride, count, M_max, M2,
         slot_id + (int64_t)b * S, mask + (int64_t)b * S, ring + (int64_t)b * T_obs * S * 2, head_flags + 2 * b, S, T_obs,
         scale, V, obs, oid, num_peds + b, rule, osn);
     if (out_flags && tid == 0) out_flags[b] = flags;
@@ -568,12 +530,82 @@ __global__ __launch_bounds__(kThreads) void track_push_streams_rule_kernel(
                                       out_flags, rule, seen);
 }
 
-// the launch geometry the strict and the rule pushes share: sort size and dynamic LDS bytes
-static inline size_t push_lds(int M_max, int S, int *m2) {
-    *m2 = 1;
-    while (*m2 < M_max) *m2 <<= 1;
-    return (size_t)*m2 * (sizeof(int64_t) + sizeof(int32_t)) + (size_t)M_max * sizeof(int32_t) +
-           (size_t)S * (sizeof(uint32_t) + sizeof(int32_t));
+// ---- the pushes' entry points ---------------------------------------------------------------------------------------
+// Each pair (strict, *_rule) shares one function for its checks and its launch, under its own name `what`.  Without
+// `ruled` (the strict entry point) T_obs starts at 1, the rule and `seen` are not looked at and the strict kernel runs.
+#define STG_REQUIRE_RULE(what)                                                                                        \
+    STG_REQUIRE(T_obs >= 2 && T_obs <= 32 && min_seen >= 2 && min_seen <= T_obs && max_gap >= 0 &&                    \
+                    max_gap <= T_obs - 2,                                                                             \
+                STG_EINVAL, "%s: min_seen=%d not in [2, T_obs=%d] or max_gap=%d not in [0, T_obs - 2]", what, min_seen, \
+                T_obs, max_gap)
+
+// dynamic LDS of a push: the sort arrays of M2 entries, det_slot, slot masks, free slots
+static inline size_t push_lds(int M_max, int M2, int S) {
+    return det_sort_lds(M2) + (size_t)M_max * sizeof(int32_t) + (size_t)S * (sizeof(uint32_t) + sizeof(int32_t));
+}
+
+static int track_push(const char *what, bool ruled, int min_seen, int max_gap, const int64_t *det_id,
+                      const double *det_xy, const int32_t *det_count, int M_max, int64_t *slot_id, uint32_t *mask,
+                      double *ring, int32_t *head_flags, int S, int T_obs, double scale, int V, double *obs_abs,
+                      int64_t *out_ids, int32_t *num_peds, int32_t *seen, void *stream) {
+    STG_REQUIRE(M_max >= 1 && M_max <= STG_TRACK_MAX_DETECTIONS && S >= 1 && S <= STG_TRACK_MAX_SLOTS && V >= 1 &&
+                    (ruled || (T_obs >= 1 && T_obs <= 32)),
+                STG_EINVAL, "%s: bad sizes M_max=%d S=%d V=%d T_obs=%d", what, M_max, S, V, T_obs);
+    if (ruled) STG_REQUIRE_RULE(what);
+    STG_REQUIRE(det_id && det_xy && det_count && slot_id && mask && ring && head_flags && obs_abs && out_ids &&
+                    num_peds && (seen || !ruled),
+                STG_EINVAL, "%s: null pointer", what);
+    const int m2 = det_sort_n(M_max);
+    const dim3 grid(1), block(kPushThreads);
+    if (ruled)
+        hipLaunchKernelGGL(track_push_rule_kernel, grid, block, push_lds(M_max, m2, S), as_stream(stream), det_id,
+                           det_xy, det_count, M_max, m2, slot_id, mask, ring, head_flags, S, T_obs, scale, V,
+                           TrackRule{min_seen, max_gap}, obs_abs, out_ids, num_peds, seen);
+    else
+        hipLaunchKernelGGL(track_push_kernel, grid, block, push_lds(M_max, m2, S), as_stream(stream), det_id, det_xy,
+                           det_count, M_max, m2, slot_id, mask, ring, head_flags, S, T_obs, scale, V, obs_abs, out_ids,
+                           num_peds);
+    STG_LAUNCH_CHECK(what);
+    return STG_OK;
+}
+
+static int track_push_streams(const char *what, bool ruled, int min_seen, int max_gap, const int64_t *det_id,
+                              int64_t id_stride, const double *det_xy, int64_t xy_stride, int M_total,
+                              const int32_t *det_start, const int32_t *pushed, int NS, int M_max, int64_t *slot_id,
+                              uint32_t *mask, double *ring, int32_t *head_flags, int S, int T_obs, double scale, int V,
+                              double *obs_abs, int64_t *out_ids, int32_t *num_peds, int32_t *out_flags, int32_t *seen,
+                              int block_threads, void *stream) {
+    STG_REQUIRE(NS >= 1 && NS <= STG_TRACK_MAX_STREAMS && M_total >= 0 && M_total <= STG_TRACK_MAX_TOTAL_DETECTIONS &&
+                    M_max >= 1 && M_max <= STG_TRACK_MAX_DETECTIONS && S >= 1 && S <= STG_TRACK_MAX_SLOTS && V >= 1 &&
+                    (ruled || (T_obs >= 1 && T_obs <= 32)) && id_stride >= 1 && xy_stride >= 2,
+                STG_EINVAL, "%s: bad sizes NS=%d M_total=%d M_max=%d S=%d V=%d T_obs=%d strides %lld/%lld", what, NS,
+                M_total, M_max, S, V, T_obs, (long long)id_stride, (long long)xy_stride);
+    if (ruled) STG_REQUIRE_RULE(what);
+    if (block_threads == 0) block_threads = kStreamThreads;
+    STG_REQUIRE(block_threads == 64 || block_threads == 256 || block_threads == 1024, STG_EINVAL,
+                "%s: block_threads=%d (0, 64, 256 or 1024)", what, block_threads);
+    STG_REQUIRE(det_id && det_xy && det_start && pushed && slot_id && mask && ring && head_flags && obs_abs &&
+                    out_ids && num_peds && (seen || !ruled),
+                STG_EINVAL, "%s: null pointer", what);
+    const int m2 = det_sort_n(M_max);
+    const size_t lds = push_lds(M_max, m2, S);
+    const dim3 grid(NS), block(block_threads);
+    // the workgroup size picks the instantiation, `ruled` the kernel of the pair
+    auto go = [&](auto strict_kernel, auto rule_kernel) {
+        if (ruled)
+            hipLaunchKernelGGL(rule_kernel, grid, block, lds, as_stream(stream), det_id, id_stride, det_xy, xy_stride,
+                               M_total, det_start, pushed, M_max, m2, slot_id, mask, ring, head_flags, S, T_obs, scale, V,
+                               TrackRule{min_seen, max_gap}, obs_abs, out_ids, num_peds, out_flags, seen);
+        else
+            hipLaunchKernelGGL(strict_kernel, grid, block, lds, as_stream(stream), det_id, id_stride, det_xy, xy_stride,
+                               M_total, det_start, pushed, M_max, m2, slot_id, mask, ring, head_flags, S, T_obs, scale, V,
+                               obs_abs, out_ids, num_peds, out_flags);
+    };
+    if (block_threads == 64) go(track_push_streams_kernel<64>, track_push_streams_rule_kernel<64>);
+    else if (block_threads == 256) go(track_push_streams_kernel<256>, track_push_streams_rule_kernel<256>);
+    else go(track_push_streams_kernel<1024>, track_push_streams_rule_kernel<1024>);
+    STG_LAUNCH_CHECK(what);
+    return STG_OK;
 }
 
 }  // namespace stg
@@ -608,19 +640,8 @@ int stg_frame_scenes(const int32_t *frame_start, const int64_t *ids, const doubl
 int stg_track_push(const int64_t *det_id, const double *det_xy, const int32_t *det_count, int M_max, int64_t *slot_id,
                    uint32_t *mask, double *ring, int32_t *head_flags, int S, int T_obs, double scale, int V,
                    double *obs_abs, int64_t *out_ids, int32_t *num_peds, void *stream) {
-    STG_REQUIRE(M_max >= 1 && M_max <= STG_TRACK_MAX_DETECTIONS && S >= 1 && S <= STG_TRACK_MAX_SLOTS && V >= 1 &&
-                    T_obs >= 1 && T_obs <= 32,
-                STG_EINVAL, "stg_track_push: bad sizes M_max=%d S=%d V=%d T_obs=%d", M_max, S, V, T_obs);
-    STG_REQUIRE(det_id && det_xy && det_count && slot_id && mask && ring && head_flags && obs_abs && out_ids &&
-                    num_peds,
-                STG_EINVAL, "stg_track_push: null pointer");
-    int m2;
-    const size_t lds = stg::push_lds(M_max, S, &m2);
-    hipLaunchKernelGGL(stg::track_push_kernel, dim3(1), dim3(stg::kPushThreads), lds, stg::as_stream(stream), det_id,
-                       det_xy, det_count, M_max, m2, slot_id, mask, ring, head_flags, S, T_obs, scale, V, obs_abs,
-                       out_ids, num_peds);
-    STG_LAUNCH_CHECK("stg_track_push");
-    return STG_OK;
+    return stg::track_push("stg_track_push", false, 0, 0, det_id, det_xy, det_count, M_max, slot_id, mask, ring,
+                           head_flags, S, T_obs, scale, V, obs_abs, out_ids, num_peds, nullptr, stream);
 }
 
 int stg_track_push_streams(const int64_t *det_id, int64_t id_stride, const double *det_xy, int64_t xy_stride,
@@ -628,39 +649,12 @@ int stg_track_push_streams(const int64_t *det_id, int64_t id_stride, const doubl
                            int64_t *slot_id, uint32_t *mask, double *ring, int32_t *head_flags, int S, int T_obs,
                            double scale, int V, double *obs_abs, int64_t *out_ids, int32_t *num_peds,
                            int32_t *out_flags, int block_threads, void *stream) {
-    STG_REQUIRE(NS >= 1 && NS <= STG_TRACK_MAX_STREAMS && M_total >= 0 && M_total <= STG_TRACK_MAX_TOTAL_DETECTIONS &&
-                    M_max >= 1 && M_max <= STG_TRACK_MAX_DETECTIONS && S >= 1 && S <= STG_TRACK_MAX_SLOTS && V >= 1 &&
-                    T_obs >= 1 && T_obs <= 32 && id_stride >= 1 && xy_stride >= 2,
-                STG_EINVAL,
-                "stg_track_push_streams: bad sizes NS=%d M_total=%d M_max=%d S=%d V=%d T_obs=%d strides %lld/%lld", NS,
-                M_total, M_max, S, V, T_obs, (long long)id_stride, (long long)xy_stride);
-    if (block_threads == 0) block_threads = stg::kStreamThreads;
-    STG_REQUIRE(block_threads == 64 || block_threads == 256 || block_threads == 1024, STG_EINVAL,
-                "stg_track_push_streams: block_threads=%d (0, 64, 256 or 1024)", block_threads);
-    STG_REQUIRE(det_id && det_xy && det_start && pushed && slot_id && mask && ring && head_flags && obs_abs &&
-                    out_ids && num_peds,
-                STG_EINVAL, "stg_track_push_streams: null pointer");
-    int m2;
-    const size_t lds = stg::push_lds(M_max, S, &m2);
-    auto go = [&](auto kernel, int threads) {
-        hipLaunchKernelGGL(kernel, dim3(NS), dim3(threads), lds, stg::as_stream(stream), det_id, id_stride, det_xy,
-                           xy_stride, M_total, det_start, pushed, M_max, m2, slot_id, mask, ring, head_flags, S, T_obs,
-                           scale, V, obs_abs, out_ids, num_peds, out_flags);
-    };
-    if (block_threads == 64) go(stg::track_push_streams_kernel<64>, 64);
-    else if (block_threads == 256) go(stg::track_push_streams_kernel<256>, 256);
-    else go(stg::track_push_streams_kernel<1024>, 1024);
-    STG_LAUNCH_CHECK("stg_track_push_streams");
-    return STG_OK;
+    return stg::track_push_streams("stg_track_push_streams", false, 0, 0, det_id, id_stride, det_xy, xy_stride,
+                                   M_total, det_start, pushed, NS, M_max, slot_id, mask, ring, head_flags, S, T_obs,
+                                   scale, V, obs_abs, out_ids, num_peds, out_flags, nullptr, block_threads, stream);
 }
 
 // ---- partially observed tracks: the rule's entry points -------------------------------------------------------------
-#define STG_REQUIRE_RULE(what)                                                                                       \
-    STG_REQUIRE(T_obs >= 2 && T_obs <= 32 && min_seen >= 2 && min_seen <= T_obs && max_gap >= 0 &&                   \
-                    max_gap <= T_obs - 2,                                                                            \
-                STG_EINVAL, what ": min_seen=%d not in [2, T_obs=%d] or max_gap=%d not in [0, T_obs - 2]", min_seen, \
-                T_obs, max_gap)
-
 int stg_fill_tracks(double *obs_abs, const int32_t *seen, const int32_t *num_peds, int N, int T_obs, int V,
                     double scale, void *stream) {
     STG_REQUIRE(N >= 0 && V >= 1 && T_obs >= 2 && T_obs <= 32 && (int64_t)N * V < ((int64_t)1 << 31) * 256, STG_EINVAL,
@@ -705,19 +699,8 @@ int stg_track_push_rule(const int64_t *det_id, const double *det_xy, const int32
                         int64_t *slot_id, uint32_t *mask, double *ring, int32_t *head_flags, int S, int T_obs,
                         double scale, int V, int min_seen, int max_gap, double *obs_abs, int64_t *out_ids,
                         int32_t *num_peds, int32_t *seen, void *stream) {
-    STG_REQUIRE(M_max >= 1 && M_max <= STG_TRACK_MAX_DETECTIONS && S >= 1 && S <= STG_TRACK_MAX_SLOTS && V >= 1,
-                STG_EINVAL, "stg_track_push_rule: bad sizes M_max=%d S=%d V=%d", M_max, S, V);
-    STG_REQUIRE_RULE("stg_track_push_rule");
-    STG_REQUIRE(det_id && det_xy && det_count && slot_id && mask && ring && head_flags && obs_abs && out_ids &&
-                    num_peds && seen,
-                STG_EINVAL, "stg_track_push_rule: null pointer");
-    int m2;
-    const size_t lds = stg::push_lds(M_max, S, &m2);
-    hipLaunchKernelGGL(stg::track_push_rule_kernel, dim3(1), dim3(stg::kPushThreads), lds, stg::as_stream(stream),
-                       det_id, det_xy, det_count, M_max, m2, slot_id, mask, ring, head_flags, S, T_obs, scale, V,
-                       stg::TrackRule{min_seen, max_gap}, obs_abs, out_ids, num_peds, seen);
-    STG_LAUNCH_CHECK("stg_track_push_rule");
-    return STG_OK;
+    return stg::track_push("stg_track_push_rule", true, min_seen, max_gap, det_id, det_xy, det_count, M_max, slot_id,
+                           mask, ring, head_flags, S, T_obs, scale, V, obs_abs, out_ids, num_peds, seen, stream);
 }
 
 int stg_track_push_streams_rule(const int64_t *det_id, int64_t id_stride, const double *det_xy, int64_t xy_stride,
@@ -726,30 +709,9 @@ int stg_track_push_streams_rule(const int64_t *det_id, int64_t id_stride, const 
                                 double scale, int V, int min_seen, int max_gap, double *obs_abs, int64_t *out_ids,
                                 int32_t *num_peds, int32_t *out_flags, int32_t *seen, int block_threads,
                                 void *stream) {
-    STG_REQUIRE(NS >= 1 && NS <= STG_TRACK_MAX_STREAMS && M_total >= 0 && M_total <= STG_TRACK_MAX_TOTAL_DETECTIONS &&
-                    M_max >= 1 && M_max <= STG_TRACK_MAX_DETECTIONS && S >= 1 && S <= STG_TRACK_MAX_SLOTS && V >= 1 &&
-                    id_stride >= 1 && xy_stride >= 2,
-                STG_EINVAL, "stg_track_push_streams_rule: bad sizes NS=%d M_total=%d M_max=%d S=%d V=%d strides %lld/%lld",
-                NS, M_total, M_max, S, V, (long long)id_stride, (long long)xy_stride);
-    STG_REQUIRE_RULE("stg_track_push_streams_rule");
-    if (block_threads == 0) block_threads = stg::kStreamThreads;
-    STG_REQUIRE(block_threads == 64 || block_threads == 256 || block_threads == 1024, STG_EINVAL,
-                "stg_track_push_streams_rule: block_threads=%d (0, 64, 256 or 1024)", block_threads);
-    STG_REQUIRE(det_id && det_xy && det_start && pushed && slot_id && mask && ring && head_flags && obs_abs &&
-                    out_ids && num_peds && seen,
-                STG_EINVAL, "stg_track_push_streams_rule: null pointer");
-    int m2;
-    const size_t lds = stg::push_lds(M_max, S, &m2);
-    auto go = [&](auto kernel, int threads) {
-        hipLaunchKernelGGL(kernel, dim3(NS), dim3(threads), lds, stg::as_stream(stream), det_id, id_stride, det_xy,
-                           xy_stride, M_total, det_start, pushed, M_max, m2, slot_id, mask, ring, head_flags, S, T_obs,
-                           scale, V, stg::TrackRule{min_seen, max_gap}, obs_abs, out_ids, num_peds, out_flags, seen);
-    };
-    if (block_threads == 64) go(stg::track_push_streams_rule_kernel<64>, 64);
-    else if (block_threads == 256) go(stg::track_push_streams_rule_kernel<256>, 256);
-    else go(stg::track_push_streams_rule_kernel<1024>, 1024);
-    STG_LAUNCH_CHECK("stg_track_push_streams_rule");
-    return STG_OK;
+    return stg::track_push_streams("stg_track_push_streams_rule", true, min_seen, max_gap, det_id, id_stride, det_xy,
+                                   xy_stride, M_total, det_start, pushed, NS, M_max, slot_id, mask, ring, head_flags, S,
+                                   T_obs, scale, V, obs_abs, out_ids, num_peds, out_flags, seen, block_threads, stream);
 }
 
 }  // extern "C"

@@ -34,8 +34,8 @@
 //   A stream not pushed keeps its state bit for bit and gets all-zero outputs (ids -1).
 //
 // One workgroup per stream:
-//   sort     the detections by (id, index), a bitonic network in LDS (the push kernel's phase 2, copied: frames.hip
-//            keeps its own)
+//   sort     the detections by (id, index), a bitonic network in LDS: the push kernel's load, sort and lookup
+//            (detections.hpp), so the truth of a repeated id is the detection the scene took
 //   score    a wave per horizon h (wave w takes h = w+1, w+1+waves, ...), a lane per pedestrian: lower bound of the
 //            record's id in the sorted keys, then the loop over k -- the reads of samples[k,h,:] are contiguous in v.
 //            The row of a horizon belongs to one wave, so its accumulators are plain read-modify-writes
@@ -47,18 +47,13 @@
 //            row m mod P
 // No host synchronisation (the launch is captured into the live predictors' graph), plain C++ stores only, 24 KB of
 // dynamic LDS at the 2,048-detection limit.
-#include "common.hpp"
+#include "detections.hpp"
 
 namespace stg {
 
 constexpr int kScoreThreads = 256;
 constexpr int kScoreWaves = kScoreThreads / kWave;
 constexpr int kScoreCols = 5;                      // totals columns ahead of the coverage counts
-
-// np.around(x, decimals) as frames.hip's round_pos
-__device__ __forceinline__ double score_round_pos(double x, double scale) {
-    return scale > 0.0 ? rint(x * scale) / scale : x;
-}
 
 struct ScoreArgs {
     // the prediction as the chain leaves it
@@ -143,32 +138,10 @@ __device__ __forceinline__ void score_push_body(const ScoreArgs &a, int b, const
     const int64_t ob = (int64_t)b * P * V;
 
     // 1. the detections into the sort buffer (padding keys sort last), sorted by (id, detection index)
-    int n2 = 1;
-    while (n2 < m) n2 <<= 1;
-    for (int p = tid; p < n2; p += kScoreThreads) {
-        key[p] = p < m ? det_id[p * id_stride] : INT64_MAX;
-        kidx[p] = p;
-    }
+    const int n2 = det_sort_n(m);
+    det_load(key, kidx, det_id, id_stride, m, n2, tid, kScoreThreads);
     __syncthreads();
-    for (int k = 2; k <= n2; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < n2; i += kScoreThreads) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const int64_t ka = key[i], kb = key[l];
-                    const int ia = kidx[i], ib = kidx[l];
-                    const bool gt = ka > kb || (ka == kb && ia > ib);
-                    if (gt == ((i & k) == 0)) {
-                        key[i] = kb;
-                        key[l] = ka;
-                        kidx[i] = ib;
-                        kidx[l] = ia;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
+    det_sort(key, kidx, n2, tid, kScoreThreads);
 
     // 2. score: wave -> horizon, lane -> pedestrian
     for (int h = 1 + wave; h <= P; h += kScoreWaves) {
@@ -191,16 +164,11 @@ __device__ __forceinline__ void score_push_body(const ScoreArgs &a, int b, const
             float t_ade = 0.f, t_fde = 0.f, t_adem = 0.f, t_fdem = 0.f;
             if (v < np) {
                 const int64_t id = rec_ids[r * V + v];
-                int lo = 0, hi = m;
-                while (lo < hi) {
-                    const int mid = (lo + hi) >> 1;
-                    if (key[mid] < id) lo = mid + 1;
-                    else hi = mid;
-                }
-                if (lo < m && key[lo] == id) {                      // the lower bound is the first detection of the id
-                    const int j = kidx[lo];
-                    const float tx = (float)score_round_pos(det_xy[j * xy_stride], a.scale);
-                    const float ty = (float)score_round_pos(det_xy[j * xy_stride + 1], a.scale);
+                const int at = det_find(key, m, id);                // the first detection of the id
+                if (at >= 0) {
+                    const int j = kidx[at];
+                    const float tx = (float)round_pos(det_xy[j * xy_stride], a.scale);
+                    const float ty = (float)round_pos(det_xy[j * xy_stride + 1], a.scale);
                     const int64_t e = ((int64_t)r * P + (h - 1)) * V + v;
                     const float2 mu = *reinterpret_cast<const float2 *>(rec_mean + e * 2);
                     mt = 1;
@@ -358,10 +326,9 @@ __global__ __launch_bounds__(kScoreThreads) void score_push_streams_kernel(
         score_empty(a, b);
         return;
     }
-    int lo = det_start[b], hi = det_start[b + 1];
-    lo = lo < 0 ? 0 : (lo > M_total ? M_total : lo);
-    hi = hi < lo ? lo : (hi > M_total ? M_total : hi);
-    score_push_body(a, b, det_id + lo * id_stride, id_stride, det_xy + lo * xy_stride, xy_stride, hi - lo);
+    int lo;
+    const int count = det_range(det_start, b, M_total, lo);
+    score_push_body(a, b, det_id + lo * id_stride, id_stride, det_xy + lo * xy_stride, xy_stride, count);
 }
 
 // the checks both entry points share; fills `a`
@@ -395,14 +362,10 @@ static int score_args(const char *what, int NS, int M_max, double scale, const f
     STG_REQUIRE(K <= STG_SCORE_MAX_K, STG_EUNSUPPORTED, "%s: K=%d above STG_SCORE_MAX_K=%d", what, K, STG_SCORE_MAX_K);
     STG_REQUIRE(P <= STG_SCORE_MAX_P, STG_EUNSUPPORTED, "%s: P=%d above STG_SCORE_MAX_P=%d", what, P, STG_SCORE_MAX_P);
     STG_REQUIRE(Q <= STG_SCORE_MAX_Q, STG_EUNSUPPORTED, "%s: Q=%d above STG_SCORE_MAX_Q=%d", what, Q, STG_SCORE_MAX_Q);
-    int m2 = 1;
-    while (m2 < M_max) m2 <<= 1;
     *a = ScoreArgs{mean, v_pred, p_sn, p_sf, p_sp, p_sv, K > 0 ? samples : nullptr, ids, num_peds, *st, thr, *out,
-                   NS, P, V, K, Q, M_max, m2, scale};
+                   NS, P, V, K, Q, M_max, det_sort_n(M_max), scale};
     return STG_OK;
 }
-
-static inline size_t score_lds(const ScoreArgs &a) { return (size_t)a.M2 * (sizeof(int64_t) + sizeof(int32_t)); }
 
 }  // namespace stg
 
@@ -417,7 +380,7 @@ int stg_score_push(const int64_t *det_id, const double *det_xy, const int32_t *d
                                    num_peds, P, V, K, state, thr, Q, out, &a);
     if (rc != STG_OK) return rc;
     STG_REQUIRE(det_id && det_xy && det_count, STG_EINVAL, "stg_score_push: null pointer (detections)");
-    hipLaunchKernelGGL(stg::score_push_kernel, dim3(1), dim3(stg::kScoreThreads), stg::score_lds(a),
+    hipLaunchKernelGGL(stg::score_push_kernel, dim3(1), dim3(stg::kScoreThreads), stg::det_sort_lds(a.M2),
                        stg::as_stream(stream), a, det_id, det_xy, det_count);
     STG_LAUNCH_CHECK("stg_score_push");
     return STG_OK;
@@ -442,7 +405,7 @@ int stg_score_push_streams(const int64_t *det_id, int64_t id_stride, const doubl
     STG_REQUIRE(M_total <= STG_TRACK_MAX_TOTAL_DETECTIONS, STG_EUNSUPPORTED,
                 "stg_score_push_streams: M_total=%d above STG_TRACK_MAX_TOTAL_DETECTIONS=%d", M_total,
                 STG_TRACK_MAX_TOTAL_DETECTIONS);
-    hipLaunchKernelGGL(stg::score_push_streams_kernel, dim3((unsigned)NS), dim3(stg::kScoreThreads), stg::score_lds(a),
+    hipLaunchKernelGGL(stg::score_push_streams_kernel, dim3((unsigned)NS), dim3(stg::kScoreThreads), stg::det_sort_lds(a.M2),
                        stg::as_stream(stream), a, det_id, id_stride, det_xy, xy_stride, M_total, det_start, pushed);
     STG_LAUNCH_CHECK("stg_score_push_streams");
     return STG_OK;

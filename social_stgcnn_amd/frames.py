@@ -175,12 +175,10 @@ def recording_scenes(rows, device, obs_len=8, min_peds=1, decimals=4, v_pad=None
     ids_d = torch.from_numpy(ids).to(device)
     xy_d = torch.from_numpy(xy).to(device)
     count = torch.zeros(nf, device=device, dtype=torch.int32)
-    if rule is None:
-        check(lib().stg_frame_scene_counts(ptr(fs_d), ptr(ids_d), nf, obs_len, ptr(count), stream_ptr()),
-              "stg_frame_scene_counts")
-    else:
-        check(lib().stg_frame_scene_counts_rule(ptr(fs_d), ptr(ids_d), nf, obs_len, rule.min_seen, rule.max_gap,
-                                                ptr(count), stream_ptr()), "stg_frame_scene_counts_rule")
+    # the strict kernels, or their *_rule twins with the rule ahead of the outputs and `seen` behind them
+    name, rule_args = ("%s", ()) if rule is None else ("%s_rule", tuple(rule))
+    check(getattr(lib(), name % "stg_frame_scene_counts")(ptr(fs_d), ptr(ids_d), nf, obs_len, *rule_args, ptr(count),
+                                                          stream_ptr()), name % "stg_frame_scene_counts")
     cnt = count.cpu().numpy()
     first = obs_len - 1 if rule is None else rule.min_seen - 1
     sel = np.nonzero((cnt >= int(min_peds)) & (np.arange(nf) >= first))[0]
@@ -195,19 +193,13 @@ def recording_scenes(rows, device, obs_len=8, min_peds=1, decimals=4, v_pad=None
     obs = torch.empty((n, obs_len, v, 2), device=device, dtype=torch.float64)
     out_ids = torch.empty((n, v), device=device, dtype=torch.int64)
     peds = torch.empty(n, device=device, dtype=torch.int32)
-    if rule is not None:
-        seen = torch.empty((n, v), device=device, dtype=torch.int32)
-        if n:
-            sel_d = torch.from_numpy(sel.astype(np.int32)).to(device)
-            check(lib().stg_frame_scenes_rule(ptr(fs_d), ptr(ids_d), ptr(xy_d), ptr(sel_d), n, v, obs_len, scale,
-                                              rule.min_seen, rule.max_gap, ptr(obs), ptr(out_ids), ptr(peds),
-                                              ptr(seen), stream_ptr()), "stg_frame_scenes_rule")
-        return PartialScenes(frames[sel], obs, out_ids, peds, seen)
+    seen = () if rule is None else (torch.empty((n, v), device=device, dtype=torch.int32),)
     if n:
         sel_d = torch.from_numpy(sel.astype(np.int32)).to(device)
-        check(lib().stg_frame_scenes(ptr(fs_d), ptr(ids_d), ptr(xy_d), ptr(sel_d), n, v, obs_len, scale, ptr(obs),
-                                     ptr(out_ids), ptr(peds), stream_ptr()), "stg_frame_scenes")
-    return FrameScenes(frames[sel], obs, out_ids, peds)
+        check(getattr(lib(), name % "stg_frame_scenes")(ptr(fs_d), ptr(ids_d), ptr(xy_d), ptr(sel_d), n, v, obs_len,
+                                                        scale, *rule_args, ptr(obs), ptr(out_ids), ptr(peds),
+                                                        *map(ptr, seen), stream_ptr()), name % "stg_frame_scenes")
+    return (FrameScenes if rule is None else PartialScenes)(frames[sel], obs, out_ids, peds, *seen)
 
 
 def fill_tracks(obs_abs, seen, num_peds=None, decimals=4):
@@ -297,6 +289,8 @@ class _LivePredictor:
         _stage(*det, seed)       copy one push's detections (and the seed, unless None) into its device staging buffers
         _outs()                  fresh per-push outputs (obs_abs, ids, num_peds, ...; under a TrackRule `seen` last)
         _push(outs)              launch its push kernel: staging buffers + track state -> outs
+        _det                     its staging buffers by the names ops.score_push takes them, in the order its push
+                                 kernel does: _push and the score launch read the same ones
         _wrap(outs, r, static)   the result tuple of outs and the chain's Prediction r (static: a captured push)
         _still()                 make warm-up pushes harmless; returns the (tensor, saved copy) pairs to put back after
 
@@ -369,7 +363,16 @@ class _LivePredictor:
         ns = self._score_state.head.shape[0]
         return ops.score_push(self._score_state, self._thr, r.mean, r.v_pred,
                               r.samples if self.score_spec.best_of_k else None, outs[1].view(ns, self.v), outs[2],
-                              out=out, **self._score_det())
+                              out=out, m_max=self.m_max, scale=self.scale, **self._det)
+
+    def _launch_push(self, name, det, outs, n_out, *tail):
+        """The push kernel `name` on the detections `det` (its leading arguments) and the track state, or under a
+        TrackRule its *_rule twin: the rule goes ahead of the kernel's n_out outputs, `seen` (the last of outs) behind."""
+        rule, seen = ((), ()) if self.rule is None else (tuple(self.rule), (ptr(outs[-1]),))
+        name += "_rule" if rule else ""
+        check(getattr(lib(), name)(*det, ptr(self.slot_id), ptr(self.mask), ptr(self.ring), ptr(self.head_flags), self.s,
+                                   self.t_obs, ctypes.c_double(self.scale), self.v, *rule, *map(ptr, outs[:n_out]),
+                                   *seen, *tail, stream_ptr()), name)
 
     @property
     def risk(self):
@@ -458,6 +461,7 @@ class FramePredictor(_LivePredictor):
         self.det_xy = torch.zeros((m, 2), device=dev, dtype=torch.float64)
         self.det_count = torch.zeros(1, device=dev, dtype=torch.int32)
         self.seed_dev = torch.zeros(1, device=dev, dtype=torch.int64)
+        self._det = dict(det_id=ptr(self.det_id), det_xy=ptr(self.det_xy), det_count=ptr(self.det_count))
         self.reset()
 
     def reset(self):
@@ -468,9 +472,6 @@ class FramePredictor(_LivePredictor):
         self.head_flags.zero_()
         if self._score_state is not None:
             ops.score_reset(self._score_state)
-
-    def _score_det(self):
-        return dict(det_id=self.det_id, det_xy=self.det_xy, det_count=self.det_count, m_max=self.m_max, scale=self.scale)
 
     def _stage(self, ids, xy, seed):
         """Copy one frame of detections (host arrays or device tensors) into the device buffers the push reads."""
@@ -499,18 +500,7 @@ class FramePredictor(_LivePredictor):
                 torch.empty(1, device=dev, dtype=torch.int32)) + self._seen_out(v)
 
     def _push(self, outs):
-        obs, ids, peds = outs[:3]
-        if self.rule is not None:
-            check(lib().stg_track_push_rule(ptr(self.det_id), ptr(self.det_xy), ptr(self.det_count), self.m_max,
-                                            ptr(self.slot_id), ptr(self.mask), ptr(self.ring), ptr(self.head_flags),
-                                            self.s, self.t_obs, ctypes.c_double(self.scale), self.v, self.rule.min_seen,
-                                            self.rule.max_gap, ptr(obs), ptr(ids), ptr(peds), ptr(outs[3]),
-                                            stream_ptr()), "stg_track_push_rule")
-            return
-        check(lib().stg_track_push(ptr(self.det_id), ptr(self.det_xy), ptr(self.det_count), self.m_max,
-                                   ptr(self.slot_id), ptr(self.mask), ptr(self.ring), ptr(self.head_flags), self.s,
-                                   self.t_obs, ctypes.c_double(self.scale), self.v, ptr(obs), ptr(ids), ptr(peds),
-                                   stream_ptr()), "stg_track_push")
+        self._launch_push("stg_track_push", (*self._det.values(), self.m_max), outs, 3)
 
     def _wrap(self, outs, r, static):
         obs, ids, peds = outs[:3]
@@ -673,6 +663,9 @@ class StreamsPredictor(_LivePredictor):
         self.seed_dev = self._dev[o_seed:self._hdr].view(torch.int64)
         self._rec_i = self._dev[self._hdr:].view(torch.int64).view(self.cap, 3)
         self._rec_f = self._dev[self._hdr:].view(torch.float64).view(self.cap, 3)
+        # a record is (id, x, y): ids at stride 3 from its start, positions at stride 3 from 8 bytes in
+        self._det = dict(det_id=ptr(self._rec_i), id_stride=3, det_xy=ctypes.c_void_p(self._rec_f.data_ptr() + 8),
+                         xy_stride=3, m_total=self.cap, det_start=ptr(self.det_start), pushed=ptr(self.pushed_dev))
         self._copied = torch.cuda.Event()
         self._in_flight = False
         self.reset()
@@ -702,11 +695,6 @@ class StreamsPredictor(_LivePredictor):
         self.head_flags.index_fill_(0, at, 0)
         if self._score_state is not None:
             ops.score_reset(self._score_state, at)
-
-    def _score_det(self):
-        return dict(det_id=ptr(self._rec_i), id_stride=3, det_xy=ctypes.c_void_p(self._rec_f.data_ptr() + 8),
-                    xy_stride=3, m_total=self.cap, det_start=self.det_start, pushed=self.pushed_dev, m_max=self.m_max,
-                    scale=self.scale)
 
     def _wait_host(self):
         """The pinned buffer is rewritten only after the previous tick's copy has left it."""
@@ -780,22 +768,9 @@ class StreamsPredictor(_LivePredictor):
                 torch.empty(ns, device=dev, dtype=torch.bool)) + self._seen_out(ns, v)
 
     def _push(self, outs):
-        obs, ids, peds, flags, pushed = outs[:5]
-        if self.rule is None:
-            check(lib().stg_track_push_streams(ptr(self._rec_i), 3, ctypes.c_void_p(self._rec_f.data_ptr() + 8), 3,
-                                               self.cap, ptr(self.det_start), ptr(self.pushed_dev), self.ns, self.m_max,
-                                               ptr(self.slot_id), ptr(self.mask), ptr(self.ring), ptr(self.head_flags),
-                                               self.s, self.t_obs, ctypes.c_double(self.scale), self.v, ptr(obs), ptr(ids),
-                                               ptr(peds), ptr(flags), self.block_threads, stream_ptr()),
-                  "stg_track_push_streams")
-        else:
-            check(lib().stg_track_push_streams_rule(
-                ptr(self._rec_i), 3, ctypes.c_void_p(self._rec_f.data_ptr() + 8), 3, self.cap, ptr(self.det_start),
-                ptr(self.pushed_dev), self.ns, self.m_max, ptr(self.slot_id), ptr(self.mask), ptr(self.ring),
-                ptr(self.head_flags), self.s, self.t_obs, ctypes.c_double(self.scale), self.v, self.rule.min_seen,
-                self.rule.max_gap, ptr(obs), ptr(ids), ptr(peds), ptr(flags), ptr(outs[5]), self.block_threads,
-                stream_ptr()), "stg_track_push_streams_rule")
-        torch.ne(self.pushed_dev, 0, out=pushed)
+        self._launch_push("stg_track_push_streams", (*self._det.values(), self.ns, self.m_max), outs, 4,
+                          self.block_threads)
+        torch.ne(self.pushed_dev, 0, out=outs[4])
 
     def _wrap(self, outs, r, static):
         obs, ids, peds, flags, pushed = outs[:5]

@@ -11,52 +11,16 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN, load_golden
+from conftest import load_golden
 import frames_np
+from live_inputs import DATA, _assert_scene, _model, _pushes, _recordings, _rows, _xy
 
 pytestmark = pytest.mark.gpu
-CFG = dict(n_stgcnn=1, n_txpcnn=5, output_feat=5, seq_len=8, kernel_size=3, pred_seq_len=12)
-DATA = os.path.join(GOLDEN, "data")
 
 
 @pytest.fixture(scope="module")
 def dev():
     return torch.device("cuda", 0)
-
-
-def _recordings():
-    return sorted((d, f) for d in os.listdir(DATA) for f in os.listdir(os.path.join(DATA, d)))
-
-
-def _rows(d, f):
-    from social_stgcnn_amd import data
-    return data.read_file(os.path.join(DATA, d, f))
-
-
-def _model(name, dev):
-    from social_stgcnn_amd.model import social_stgcnn
-    w = load_golden("weights_%s.npz" % name)
-    m = social_stgcnn(**CFG)
-    m.load_state_dict({k: torch.from_numpy(np.array(w[k])) for k in w.files})
-    return m.to(dev).eval()
-
-
-def _pushes(rows):
-    """One (ids, xy) per frame of the recording, rows in file order (the detection order)."""
-    frames = np.unique(rows[:, 0])
-    f_idx = np.searchsorted(frames, rows[:, 0])
-    order = np.argsort(f_idx, kind="stable")
-    bounds = np.searchsorted(f_idx[order], np.arange(len(frames) + 1))
-    return [(rows[order[a:b], 1].astype(np.int64), rows[order[a:b], 2:4]) for a, b in zip(bounds[:-1], bounds[1:])]
-
-
-def _assert_scene(ids, peds, obs, ref_ids, ref_obs, what):
-    """One padded scene (ids (V,), num_peds, obs (T,V,2)) equals a restated one, bit for bit, zeros / -1 padded."""
-    c = len(ref_ids)
-    assert int(peds) == c, what
-    assert np.array_equal(ids[:c], ref_ids) and np.all(ids[c:] == -1), what
-    assert np.array_equal(obs[:, :c], ref_obs), what
-    assert not np.any(obs[:, c:]), what
 
 
 def test_recording_scenes_equal_the_restatement_on_every_recording(dev):
@@ -233,10 +197,6 @@ def _run_script(push, script, model_ref):
         _assert_scene(out.ids.cpu().numpy(), out.num_peds.item(), out.obs_abs[0].cpu().numpy(), ref_ids, ref_obs, i)
         flags.append(int(out.flags.item()))
     return flags
-
-
-def _xy(gen, m):
-    return gen.uniform(-20, 20, size=(m, 2))            # more decimals than the rounding keeps
 
 
 def test_stream_edge_cases(dev):

@@ -12,13 +12,11 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN, load_golden
 import frames_fill_np
 import frames_np
+from live_inputs import DATA, _assert_scene, _model, _pushes, _rows
 
 pytestmark = pytest.mark.gpu
-CFG = dict(n_stgcnn=1, n_txpcnn=5, output_feat=5, seq_len=8, kernel_size=3, pred_seq_len=12)
-DATA = os.path.join(GOLDEN, "data")
 ETH = os.path.join(DATA, "eth_test", "biwi_eth.txt")
 RULES = ((8, 0), (2, 0), (2, 6), (3, 1), (5, 2))
 
@@ -30,16 +28,11 @@ def dev():
 
 @pytest.fixture(scope="module")
 def model(dev):
-    from social_stgcnn_amd.model import social_stgcnn
-    w = load_golden("weights_eth.npz")
-    m = social_stgcnn(**CFG)
-    m.load_state_dict({k: torch.from_numpy(np.array(w[k])) for k in w.files})
-    return m.to(dev).eval()
+    return _model("eth", dev)
 
 
 def _eth_rows():
-    from social_stgcnn_amd import data
-    return data.read_file(ETH)
+    return _rows("eth_test", "biwi_eth.txt")
 
 
 def _pattern_rows():
@@ -56,27 +49,6 @@ def _sparse_rows():
     gen = np.random.default_rng(12)
     rows = np.array([(10.0 * t, float(k)) for t in range(40) for k in range(100, 130) if gen.random() < 0.7])
     return np.concatenate([rows, gen.uniform(-20, 20, size=(len(rows), 2))], axis=1)
-
-
-def _pushes(rows):
-    """One (ids, xy) per frame of the recording, rows in file order (the detection order)."""
-    frames = np.unique(rows[:, 0])
-    f_idx = np.searchsorted(frames, rows[:, 0])
-    order = np.argsort(f_idx, kind="stable")
-    bounds = np.searchsorted(f_idx[order], np.arange(len(frames) + 1))
-    return [(rows[order[a:b], 1].astype(np.int64), np.ascontiguousarray(rows[order[a:b], 2:4]))
-            for a, b in zip(bounds[:-1], bounds[1:])]
-
-
-def _assert_scene(ids, peds, obs, seen, ref_ids, ref_obs, ref_seen, what):
-    """One padded scene (ids (V,), num_peds, obs (T,V,2), seen (V,)) equals a stated one bit for bit; padded slots are
-    -1 / zeros."""
-    c = len(ref_ids)
-    assert int(peds) == c, what
-    assert np.array_equal(ids[:c], ref_ids) and np.all(ids[c:] == -1), what
-    assert np.array_equal(seen[:c], ref_seen) and not np.any(seen[c:]), what
-    assert np.array_equal(obs[:, :c], ref_obs), (what, np.argwhere(obs[:, :c] != ref_obs)[:4])
-    assert not np.any(obs[:, c:]), what
 
 
 def _host_scenes(sc):
@@ -97,7 +69,7 @@ def test_every_presence_pattern_through_the_recording_kernels(dev, decimals):
         ids, peds, obs, seen = _host_scenes(sc)
         assert ids.shape[1] == max(len(r[2]) for r in ref), (ms, mg)
         for i, (_, _, rid, robs, rseen) in enumerate(ref):
-            _assert_scene(ids[i], peds[i], obs[i], seen[i], rid, robs, rseen, (ms, mg, decimals, i))
+            _assert_scene(ids[i], peds[i], obs[i], rid, robs, (ms, mg, decimals, i), seen[i], rseen)
         if (ms, mg) == (2, 6):
             # the last frame holds every pattern seen now and at least once more
             assert int(peds[-1]) == 127 and sorted(seen[-1].tolist()) == list(range(3, 256, 2))
@@ -199,14 +171,14 @@ def test_live_pushes_equal_the_recording_scenes(dev, model, which, rule, decimal
         s_ids, s_obs, s_seen, more = ref.push(ids, xy)
         assert not more
         c_ids, c_peds, c_obs, c_seen, c_flags = c_push.push(ids, xy)
-        _assert_scene(c_ids, c_peds, c_obs, c_seen, s_ids, s_obs, s_seen, ("c", f))
+        _assert_scene(c_ids, c_peds, c_obs, s_ids, s_obs, ("c", f), c_seen, s_seen)
         assert c_flags == 0
         e = eager.push(ids, xy, seed=f)
         c = replay(ids, xy, seed=f)
         for out, p, what in ((e, eager, "eager"), (c, cap, "captured")):
             assert p.seen.shape == (vp,) and p.seen.dtype == torch.int32
-            _assert_scene(out.ids.cpu().numpy(), out.num_peds.item(), out.obs_abs[0].cpu().numpy(),
-                          p.seen.cpu().numpy(), s_ids, s_obs, s_seen, (what, f))
+            _assert_scene(out.ids.cpu().numpy(), out.num_peds.item(), out.obs_abs[0].cpu().numpy(), s_ids, s_obs,
+                          (what, f), p.seen.cpu().numpy(), s_seen)
             assert int(out.flags.item()) == 0
         assert torch.equal(c.mean, e.mean), f          # (random jumps: the sampled positions need not be finite)
         # an eager push leaves earlier results alone; a captured one writes the graph's static buffer
@@ -219,7 +191,7 @@ def test_live_pushes_equal_the_recording_scenes(dev, model, which, rule, decimal
             assert len(s_ids) == 0 and fnums[f] not in at
             continue
         i = at[fnums[f]]
-        _assert_scene(r_ids[i], r_peds[i], r_obs[i], r_seen[i], s_ids, s_obs, s_seen, ("recording", f))
+        _assert_scene(r_ids[i], r_peds[i], r_obs[i], s_ids, s_obs, ("recording", f), r_seen[i], s_seen)
         some += len(s_ids)
     assert some > 100 and len(static) == 1
 
@@ -239,8 +211,8 @@ def test_live_edge_cases(dev, model):
             p = xy(10)
             out = push(ids, p)
             s_ids, s_obs, s_seen, more = ref.push(ids, p)
-            _assert_scene(out.ids.cpu().numpy(), out.num_peds.item(), out.obs_abs[0].cpu().numpy(),
-                          fp.seen.cpu().numpy(), s_ids, s_obs, s_seen, (mode, f))
+            _assert_scene(out.ids.cpu().numpy(), out.num_peds.item(), out.obs_abs[0].cpu().numpy(), s_ids, s_obs,
+                          (mode, f), fp.seen.cpu().numpy(), s_seen)
             assert int(out.flags.item()) == (frames.TOO_MANY if f >= 1 else 0) and more == (f >= 1), (mode, f)
         assert out.ids.tolist() == [3, 5, 7, 11]
     # gaps.  id 1 is always there.  id 2 misses frames 4-6 (max_gap + 1 frames): out while frame 3 and frame 7 share a
@@ -265,8 +237,8 @@ def test_live_edge_cases(dev, model):
         for f, (ids, p) in enumerate(script):
             out = push(ids, p)
             s_ids, s_obs, s_seen, _ = ref.push(ids, p)
-            _assert_scene(out.ids.cpu().numpy(), out.num_peds.item(), out.obs_abs[0].cpu().numpy(),
-                          fp.seen.cpu().numpy(), s_ids, s_obs, s_seen, (mode, f))
+            _assert_scene(out.ids.cpu().numpy(), out.num_peds.item(), out.obs_abs[0].cpu().numpy(), s_ids, s_obs,
+                          (mode, f), fp.seen.cpu().numpy(), s_seen)
             assert int(out.flags.item()) == 0
             got.append(dict(zip(s_ids.tolist(), s_seen.tolist())))
             slot3.append((fp.slot_id == 3).nonzero().flatten().tolist())
@@ -281,8 +253,8 @@ def test_live_edge_cases(dev, model):
         for f, (ids, p) in enumerate(script[:3]):
             out = push(ids, p)
             s_ids, s_obs, s_seen, _ = ref.push(ids, p)
-            _assert_scene(out.ids.cpu().numpy(), out.num_peds.item(), out.obs_abs[0].cpu().numpy(),
-                          fp.seen.cpu().numpy(), s_ids, s_obs, s_seen, (mode, "reset", f))
+            _assert_scene(out.ids.cpu().numpy(), out.num_peds.item(), out.obs_abs[0].cpu().numpy(), s_ids, s_obs,
+                          (mode, "reset", f), fp.seen.cpu().numpy(), s_seen)
             assert (f == 0) == (len(s_ids) == 0)
     # a repeated id within a push given as device tensors: flag, the first detection wins
     for mode in ("eager", "captured"):
@@ -294,8 +266,8 @@ def test_live_edge_cases(dev, model):
             p = xy(len(ids))
             out = push(torch.from_numpy(ids).to(dev), torch.from_numpy(p).to(dev))
             s_ids, s_obs, s_seen, _ = ref.push(ids, p)
-            _assert_scene(out.ids.cpu().numpy(), out.num_peds.item(), out.obs_abs[0].cpu().numpy(),
-                          fp.seen.cpu().numpy(), s_ids, s_obs, s_seen, (mode, f))
+            _assert_scene(out.ids.cpu().numpy(), out.num_peds.item(), out.obs_abs[0].cpu().numpy(), s_ids, s_obs,
+                          (mode, f), fp.seen.cpu().numpy(), s_seen)
             assert int(out.flags.item()) == (frames.DUPLICATE if f % 3 == 0 else 0), (mode, f)
 
 
@@ -405,7 +377,7 @@ def test_predictions_of_filled_scenes_end_to_end(dev, model, tmp_path):
     want = np.zeros((n, 8, v, 2))
     counts = np.zeros(n, np.int32)
     for i, (_, _, rid, robs, rseen) in enumerate(ref):
-        _assert_scene(ids[i], peds[i], obs[i], seen[i], rid, robs, rseen, i)
+        _assert_scene(ids[i], peds[i], obs[i], rid, robs, i, seen[i], rseen)
         want[i, :, :len(rid)] = robs
         counts[i] = len(rid)
     # Predictor.predict on the statement's filled positions: bit-equal at the same padding and batching (the bars of

@@ -5,78 +5,21 @@ captured; every stream against a lone FramePredictor -- scenes, flags, track sta
 against Predictor.predict on the same tick; isolation of the edge cases and of reset; more streams than one round of
 push workgroups, with v_pred against lone predictors and the fp64 oracle; the entry point's refusals."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN, load_golden
+from conftest import load_golden
 import frames_np
+from live_inputs import Schedule, _assert_scene, _model, _pushes, _recordings, _rows, _xy
 
 pytestmark = pytest.mark.gpu
-CFG = dict(n_stgcnn=1, n_txpcnn=5, output_feat=5, seq_len=8, kernel_size=3, pred_seq_len=12)
-DATA = os.path.join(GOLDEN, "data")
 
 
 @pytest.fixture(scope="module")
 def dev():
     return torch.device("cuda", 0)
-
-
-def _recordings():
-    return sorted((d, f) for d in os.listdir(DATA) for f in os.listdir(os.path.join(DATA, d)))
-
-
-def _rows(d, f):
-    from social_stgcnn_amd import data
-    return data.read_file(os.path.join(DATA, d, f))
-
-
-def _model(name, dev):
-    from social_stgcnn_amd.model import social_stgcnn
-    w = load_golden("weights_%s.npz" % name)
-    m = social_stgcnn(**CFG)
-    m.load_state_dict({k: torch.from_numpy(np.array(w[k])) for k in w.files})
-    return m.to(dev).eval()
-
-
-def _pushes(rows):
-    """One (ids, xy) per frame of the recording, rows in file order (the detection order)."""
-    frames = np.unique(rows[:, 0])
-    f_idx = np.searchsorted(frames, rows[:, 0])
-    order = np.argsort(f_idx, kind="stable")
-    bounds = np.searchsorted(f_idx[order], np.arange(len(frames) + 1))
-    return [(rows[order[a:b], 1].astype(np.int64), np.ascontiguousarray(rows[order[a:b], 2:4]))
-            for a, b in zip(bounds[:-1], bounds[1:])]
-
-
-class Schedule:
-    """Stream s pushes the frames of its recording in order from tick start[s] on; an odd stream skips the ticks
-    divisible by s + 3 (its next frame waits for the next tick); a finished recording is not pushed."""
-
-    def __init__(self, pushes, starts, skip=True):
-        self.pushes, self.starts, self.skip = pushes, starts, skip
-        self.cursor = [0] * len(pushes)
-
-    def tick(self, t):
-        out = []
-        for s, p in enumerate(self.pushes):
-            go = t >= self.starts[s] and self.cursor[s] < len(p) and not (self.skip and s % 2 and t % (s + 3) == 0)
-            if go:
-                out.append(p[self.cursor[s]])
-                self.cursor[s] += 1
-            else:
-                out.append(None)
-        return out
-
-
-def _assert_scene(ids, peds, obs, ref_ids, ref_obs, what):
-    c = len(ref_ids)
-    assert int(peds) == c, what
-    assert np.array_equal(ids[:c], ref_ids) and np.all(ids[c:] == -1), what
-    assert np.array_equal(obs[:, :c], ref_obs), what
-    assert not np.any(obs[:, c:]), what
 
 
 def _assert_empty(out_np, s, what):
@@ -226,10 +169,6 @@ def test_captured_draws_are_the_predictors(dev):
             assert not torch.equal(other.samples, out.samples), t
             seen += 1
     assert seen >= 5
-
-
-def _xy(gen, m):
-    return gen.uniform(-20, 20, size=(m, 2))
 
 
 def _device_tick(tick, ns, dev, host_counts=False):

@@ -11,13 +11,11 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN, load_golden
 import frames_np
+from live_inputs import DATA, Schedule, _model, _pushes, _recordings, _rows
 import score_np
 
 pytestmark = pytest.mark.gpu
-CFG = dict(n_stgcnn=1, n_txpcnn=5, output_feat=5, seq_len=8, kernel_size=3, pred_seq_len=12)
-DATA = os.path.join(GOLDEN, "data")
 U = 2.0 ** -24                                       # float32 unit roundoff
 FLOAT_FIELDS = ("err", "d2", "nll", "best", "traj_ade", "traj_fde", "traj_ade_mean", "traj_fde_mean")
 
@@ -25,29 +23,6 @@ FLOAT_FIELDS = ("err", "d2", "nll", "best", "traj_ade", "traj_fde", "traj_ade_me
 @pytest.fixture(scope="module")
 def dev():
     return torch.device("cuda", 0)
-
-
-def _model(name, dev):
-    from social_stgcnn_amd.model import social_stgcnn
-    w = load_golden("weights_%s.npz" % name)
-    m = social_stgcnn(**CFG)
-    m.load_state_dict({k: torch.from_numpy(np.array(w[k])) for k in w.files})
-    return m.to(dev).eval()
-
-
-def _rows(d, f):
-    from social_stgcnn_amd import data
-    return data.read_file(os.path.join(DATA, d, f))
-
-
-def _pushes(rows):
-    """One (ids, xy) per frame of the recording, rows in file order (the detection order)."""
-    frames = np.unique(rows[:, 0])
-    f_idx = np.searchsorted(frames, rows[:, 0])
-    order = np.argsort(f_idx, kind="stable")
-    bounds = np.searchsorted(f_idx[order], np.arange(len(frames) + 1))
-    return [(rows[order[a:b], 1].astype(np.int64), np.ascontiguousarray(rows[order[a:b], 2:4]))
-            for a, b in zip(bounds[:-1], bounds[1:])]
 
 
 # ---- through the C ABI -------------------------------------------------------------------------------------------
@@ -421,30 +396,13 @@ def test_frame_predictor_eager_captured_and_restatement(dev):
     assert (eager._score_state.rec_ids == -1).all()
 
 
-class Schedule:
-    """Stream s pushes the frames of its recording in order from tick start[s] on; an odd stream skips the ticks
-    divisible by s + 3; a finished recording is not pushed (the schedule of tests/test_gpu_frames_streams.py)."""
-
-    def __init__(self, pushes, starts):
-        self.pushes, self.starts = pushes, starts
-        self.cursor = [0] * len(pushes)
-
-    def tick(self, t):
-        out = []
-        for s, p in enumerate(self.pushes):
-            go = t >= self.starts[s] and self.cursor[s] < len(p) and not (s % 2 and t % (s + 3) == 0)
-            out.append(p[self.cursor[s]] if go else None)
-            self.cursor[s] += int(go)
-        return out
-
-
 def test_streams_equal_lone_frame_predictors(dev):
     """14 recordings, staggered starts, explicit noise: the Score and the totals of stream s are those of a lone
     FramePredictor fed that stream's pushes with noise[:, s:s+1], bit for bit, eager for 24 ticks and captured after;
     a stream not pushed has the empty Score and unchanged totals; reset([s]) clears that stream's totals alone."""
     from social_stgcnn_amd import frames
     from social_stgcnn_amd.predict import ScoreSpec
-    recs = sorted((d, f) for d in os.listdir(DATA) for f in os.listdir(os.path.join(DATA, d)))
+    recs = _recordings()
     assert len(recs) == 14
     pushes = [_pushes(_rows(*r))[:40] for r in recs]
     ns, k, v, p = 14, 3, 128, 12

@@ -48,6 +48,7 @@ TEST_RECORDINGS = (("eth", "eth_test/biwi_eth.txt"), ("hotel", "hotel_test/biwi_
                    ("zara1", "zara1_test/crowds_zara01.txt"), ("zara2", "zara2_test/crowds_zara02.txt"))
 
 
+# model_for and pushes_of restate _model and _pushes of tests/live_inputs.py: a tool does not import from tests/
 def model_for(split, dev):
     from social_stgcnn_amd.model import social_stgcnn
     w = np.load(os.path.join(ROOT, "tests", "golden", "weights_%s.npz" % split))
