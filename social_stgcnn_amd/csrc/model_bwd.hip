@@ -12,12 +12,10 @@
 //     then the st_gcn blocks: BatchNorm backward with PER-SCENE statistics, PReLU, temporal conv,
 //     1x1 convs -- VALU with wave-shuffle + LDS block reductions.  Small-parameter gradients
 //     (block parameters, PReLU slopes) accumulate in LDS for the whole launch and leave as one slab row.
-//  K2 txp_wgrad_kernel<W>   the TXP weight/bias gradients as ONE skinny GEMM per layer over ALL scenes:
+//  K2 the TXP weight/bias gradients as ONE skinny GEMM per layer over ALL scenes:
 //        dW_l[co][ci][tap] = sum_{scene,pos} dz_l[co][pos] a_l[ci][pos+tap],  db_l = sum dz_l
-//     M = 12 out-channels (16-row tile), N = 9*c_in columns + a ones column (bias), K = every position of
-//     every scene.  Each wave owns work items (scene, or <= 32-column chunk of a larger scene) round-robin with a
-//     private LDS image (plane a_l + dz_l) and keeps the N/16 accumulator tiles in VGPRs for the whole launch --
-//     no barriers, no atomics.
+//     The kernels, their work items and their LDS staging are described where they live: txp_wgrad.hip (fp32 MFMA)
+//     and txp_wgrad_bf16.hip (the default); this file only launches them.
 //  reduce_slabs_kernel      sums the slab rows of K1 and K2 into the flat gradient in a fixed order.
 //
 // On the fast path (one st_gcn block, V <= 68) the TXP input-gradient chain runs wave-per-scene in
@@ -27,6 +25,7 @@
 #include "model_common.hpp"
 #include "stgcn_block.hpp"
 #include "txp_scene_common.hpp"
+#include "txp_f32_operands.hpp"
 #include "step_plan.hpp"
 #include "txp_wgrad.hpp"
 #include "tail_parts.hpp"
@@ -59,19 +58,6 @@ struct BwdArgs {
 // ------------------------------------------------------------------------------------------
 // TXP-CNN backward pieces
 // ------------------------------------------------------------------------------------------
-// dgrad weights: A operand lane (i = ci, kq) of K-step (tap', j) holds W[co = 4j+kq][ci][8 - tap'].
-template <int CINL>
-__device__ __forceinline__ void txp_load_weights_t(const float *__restrict__ W, float (&wreg)[27]) {
-    const int lane = threadIdx.x & 63, ci = lane & 15, kq = lane >> 4;
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const int co = 4 * j + kq;
-            wreg[tap * 3 + j] = ci < CINL ? W[(co * CINL + ci) * 9 + (8 - tap)] : 0.f;
-        }
-}
-
 // d(a_l)[ci][h][w] = sum_{co,kh,kw} W[co][ci][kh][kw] dz[co][h-kh+1][w-kw+1]  (+ dcur if accumulate)
 template <int CINL, int WAVES>
 __device__ void txp_dgrad(const float *__restrict__ W, const float *dzb, float *dcur, int vi, bool accumulate) {
@@ -81,7 +67,7 @@ __device__ void txp_dgrad(const float *__restrict__ W, const float *dzb, float *
     const int SW = txp_sw(vi), SC = txp_sc(vi);
     const int npos = C * vi, ntiles = (npos + 15) >> 4;
     float wreg[27];
-    txp_load_weights_t<CINL>(W, wreg);
+    load_w_bwd<CINL>(W, wreg);
     for (int tile0 = wave * 2; tile0 < ntiles; tile0 += WAVES * 2) {
         int hh[2], ww[2], base[2];
         bool ok[2];

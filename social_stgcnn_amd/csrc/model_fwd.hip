@@ -18,6 +18,7 @@
 #include "model_common.hpp"
 #include "stgcn_block.hpp"
 #include "txp_scene_common.hpp"
+#include "txp_f32_operands.hpp"
 #include "step_plan.hpp"
 
 namespace stg {
@@ -45,18 +46,6 @@ __host__ __device__ inline int fwd_plane_floats(int V) { return Cfg::P * txp_sc(
 // ------------------------------------------------------------------------------------------
 // TXP-CNN layer on MFMA
 // ------------------------------------------------------------------------------------------
-template <int CINL>
-__device__ __forceinline__ void txp_load_weights(const float *__restrict__ W, float (&wreg)[CINL * 9 / 4]) {
-    const int lane = threadIdx.x & 63, co = lane & 15, kq = lane >> 4;
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap)
-#pragma unroll
-        for (int j = 0; j < CINL / 4; ++j) {
-            const int ci = 4 * j + kq;
-            wreg[tap * (CINL / 4) + j] = co < Cfg::P ? W[(co * CINL + ci) * 9 + tap] : 0.f;
-        }
-}
-
 // kind: 0 = hidden layer without residual (layer 0), 1 = hidden layer with residual, 2 = output conv
 template <int CINL, int WAVES>
 __device__ void txp_layer_fwd(const float *__restrict__ W, const float *__restrict__ bias, float alpha, int kind,
@@ -67,7 +56,7 @@ __device__ void txp_layer_fwd(const float *__restrict__ W, const float *__restri
     const int SW = txp_sw(vi), SC = txp_sc(vi);
     const int npos = C * vi, ntiles = (npos + 15) >> 4;
     float wreg[KS];
-    txp_load_weights<CINL>(W, wreg);
+    load_w_fwd<CINL>(W, wreg);
     f32x4 binit;
 #pragma unroll
     for (int r = 0; r < 4; ++r) binit[r] = (4 * kq + r) < P ? bias[4 * kq + r] : 0.f;

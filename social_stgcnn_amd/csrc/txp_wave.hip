@@ -12,8 +12,9 @@
 // The B operand is one ds_read_b32 per MFMA from a zero-bordered channel-major plane whose channel
 // stride is == 16 (mod 32) dwords; weights sit in VGPRs for the whole layer (the next layer's are
 // prefetched while the current layer computes).  Epilogues write position-major [pos][12] images with
-// 16-byte stores: the layout the weight-gradient GEMM (model_bwd.hip, K2) stages back with LDS-DMA.
+// 16-byte stores: the layout the weight-gradient GEMM (K2: txp_wgrad.hip, txp_wgrad_bf16.hip) stages back with LDS-DMA.
 #include "txp_wave.hpp"
+#include "txp_f32_operands.hpp"
 #include "nll_elem.hpp"
 
 namespace stg {
@@ -21,49 +22,6 @@ namespace stg {
 namespace {
 
 constexpr int C = Cfg::C, P = Cfg::P, T = Cfg::T;
-
-// A lane's weights of one (co, ci) pair are 9 consecutive floats (the taps): two 16-byte loads + one dword per pair
-// instead of nine scattered dwords (every lane reads a different cache line, so the request count is what costs)
-struct __attribute__((packed, aligned(4))) F4U {
-    float v[4];
-};
-__device__ __forceinline__ void load_taps(const float *__restrict__ p, float (&t)[9]) {
-    const F4U a = *reinterpret_cast<const F4U *>(p), b = *reinterpret_cast<const F4U *>(p + 4);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        t[i] = a.v[i];
-        t[4 + i] = b.v[i];
-    }
-    t[8] = p[8];
-}
-
-// forward A operand: lane (co = l&15, kq = l>>4) of K-step (tap, j) holds W[co][4j+kq][tap]
-template <int CINL>
-__device__ __forceinline__ void load_w_fwd(const float *__restrict__ W, float (&wreg)[CINL * 9 / 4]) {
-    const int lane = threadIdx.x & 63, co = lane & 15, kq = lane >> 4;
-    const int cc = co < P ? co : 0;                   // rows 12..15 of the tile are zero
-#pragma unroll
-    for (int j = 0; j < CINL / 4; ++j) {
-        float t[9];
-        load_taps(W + (cc * CINL + 4 * j + kq) * 9, t);
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) wreg[tap * (CINL / 4) + j] = co < P ? t[tap] : 0.f;
-    }
-}
-
-// input-gradient A operand: lane (ci = l&15, kq) of K-step (tap', j) holds W[4j+kq][ci][8 - tap']
-template <int CINL>
-__device__ __forceinline__ void load_w_bwd(const float *__restrict__ W, float (&wreg)[27]) {
-    const int lane = threadIdx.x & 63, ci = lane & 15, kq = lane >> 4;
-    const int cc = ci < CINL ? ci : 0;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        float t[9];
-        load_taps(W + ((4 * j + kq) * CINL + cc) * 9, t);
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) wreg[tap * 3 + j] = ci < CINL ? t[8 - tap] : 0.f;
-    }
-}
 
 // ---- tile loop ------------------------------------------------------------------------------------
 // A scene's positions are walked in pairs of 16-position tiles: all 18*KJ im2col reads of the pair are
@@ -614,6 +572,10 @@ __device__ __forceinline__ void txp_bwd_scene(const TxpBwdArgs &a, const float *
 // rate of the fp32 MFMA.  K = 16 is ONE tap x 12 output channels (+ 4 zero lanes).  The dz plane is position-major:
 // [padded position][12] bf16 for hi, the same for lo behind it -- exactly the bytes of the fp32 plane -- so a lane's
 // B operand (four consecutive channels at one position) is one 8-byte LDS read per part.
+// txp_bwd_scene_bf16 below is txp_bwd_scene with that image.  The differences are meant: no fused-loss stage and no bf16
+// storage forms (the host refuses both: model_bwd_impl), no STG_SKIP 512 / 1024 switches, and dz_L = dy leaves for the
+// weight-gradient GEMM value by value next to the split (hi + lo is not dy, so it cannot be gathered from the image).
+// One templated function for both measured slower in one kernel or another in every form tried.
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ unsigned short bf16_rne(float x) {

@@ -131,7 +131,7 @@ __device__ __forceinline__ void layer(const WgradArgs &a, const int32_t *__restr
     const int kg = lane >> 4, rq = (lane & 15) >> 2, cp = lane & 3;   // tr reads: K sub-chunk, position and channel quad
     const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)sm;
 
-    // ---- work items (as in txp_wgrad_bf16.hip): chunk c of a scene exists when the scene has more than 32 c pedestrians;
+    // ---- work items (as in txp_wgrad.hip): chunk c of a scene exists when the scene has more than 32 c pedestrians;
     // with the sorted scene list the items are compact [chunk 0 of all scenes | chunk 1 of those with more than 32 | ...]
     const int nch = CH ? wgrad_chunks(V) : 1;
     const bool compact = CH && order && key_start && nch > 1;

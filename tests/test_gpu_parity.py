@@ -897,3 +897,151 @@ def test_kernel_options_belong_to_a_model(dev):
     assert m1.last_ws_floats - m2.last_ws_floats == 5 * 24 * 64 * 4          # the operand tables of five layers
     assert torch.equal(y1, y1b) and _maxdiff(y1.detach().cpu().numpy(), y2.detach().cpu().numpy()) < 2e-5
     assert dict(ops.OPTIONS) == before
+
+
+# ------------------------------------------------------------------------------------------
+# The round-1 wave kernels (STG_OPT_F32_MFMA / STG_OPT_SPLIT_BF16, csrc/txp_wave.hip) at their largest shape
+# ------------------------------------------------------------------------------------------
+# 68 / 65: the wave-mode block tail and the second 64-column block of the dy stage; 64 / 33 / 32: the column-mode halves
+# and the class bound of the mixed-V launch; 2 / 1: the smallest row length of the dy stage; 0: the empty-scene row
+_WAVE_F32_PEDS = (68, 65, 64, 33, 32, 17, 2, 1, 0)
+_WAVE_F32_CASES = {}
+
+
+def _wave_f32_case(kind):
+    """Inputs and the fp64 oracle's results of the "ragged" batch (nine scenes padded to V = 68, shuffled by a fixed
+    seed) or the "uniform" one (three full scenes at V = 68, no num_peds); computed once, read-only afterwards."""
+    if kind in _WAVE_F32_CASES:
+        return _WAVE_F32_CASES[kind]
+    from social_stgcnn_amd.model import social_stgcnn
+    O = _oracle()
+    v = 68
+    assert max(_WAVE_F32_PEDS) == v
+    if kind == "ragged":
+        counts = [int(c) for c in np.random.default_rng(68).permutation(_WAVE_F32_PEDS)]
+    else:
+        counts = [v] * 3
+    rels = [_synthetic_scene(v, 6800 + i) for i in range(len(counts))]
+    for r, c in zip(rels, counts):
+        r[c:] = 0.0
+    torch.manual_seed(68)
+    state = social_stgcnn(n_stgcnn=1, n_txpcnn=5, output_feat=5, seq_len=8, kernel_size=3, pred_seq_len=12).state_dict()
+    state = {k: val.detach().clone() for k, val in state.items()}
+    state64 = {k: (val.double() if val.is_floating_point() else val.clone()) for k, val in state.items()}
+    params = {k: val.clone().requires_grad_(True) for k, val in state64.items() if "running" not in k and "num_batches" not in k}
+    work = dict(state64)
+    work.update(params)
+    ref_losses, ref_pred = [], []
+    for rel, c in zip(rels, counts):
+        if c == 0:                                              # the oracle side skips the empty scene
+            ref_losses.append(torch.zeros((), dtype=torch.float64))
+            ref_pred.append(None)
+            continue
+        nodes, lap = O.seq_to_graph_np(rel[:c, :, :8])
+        tgt, _ = O.seq_to_graph_np(rel[:c, :, 8:])
+        l, vp = O.scene_loss(work, torch.from_numpy(nodes).double().unsqueeze(0).permute(0, 3, 1, 2),
+                             torch.from_numpy(lap).double(), torch.from_numpy(tgt).double(), True)
+        ref_losses.append(l)
+        ref_pred.append(vp.detach().numpy())
+    torch.stack(ref_losses).sum().backward()
+    case = dict(counts=counts, ragged=kind == "ragged", rel=np.stack(rels), state=state, ref_pred=ref_pred,
+                ref_losses=torch.stack(ref_losses).detach().numpy(),
+                ref_grads={k: (None if p.grad is None else p.grad.numpy()) for k, p in params.items()})
+    _WAVE_F32_CASES[kind] = case
+    return case
+
+
+def _wave_f32_inputs(dev, case):
+    from social_stgcnn_amd import ops
+    rel_d = torch.from_numpy(case["rel"]).to(dev)
+    peds = torch.tensor(case["counts"], dtype=torch.int32, device=dev) if case["ragged"] else None
+    nodes_d, adj_d = ops.adj_build(rel_d[..., :8], peds)
+    return nodes_d.permute(0, 3, 1, 2), adj_d, rel_d[..., 8:].permute(0, 3, 1, 2).contiguous(), peds
+
+
+def _wave_f32_autograd(dev, case):
+    """The batch through the model and the stand-alone loss kernel under the current ops.OPTIONS -> (model, V_pred, losses)."""
+    from social_stgcnn_amd.metrics import bivariate_loss
+    m = _model(dev, state=case["state"]).train()
+    x, adj, tgt, peds = _wave_f32_inputs(dev, case)
+    y, _ = m(x, adj, peds)
+    losses = bivariate_loss(y.permute(0, 2, 3, 1), tgt, peds)
+    losses.sum().backward()
+    return m, y.detach(), losses.detach()
+
+
+def _check_wave_f32_against_oracle(dev, kind, options, monkeypatch):
+    from social_stgcnn_amd import ops
+    assert ops.OPTIONS["wave_path"]
+    monkeypatch.setitem(ops.OPTIONS, options, True)
+    case = _wave_f32_case(kind)
+    m, y, losses = _wave_f32_autograd(dev, case)
+    worst_y = 0.0
+    for i, c in enumerate(case["counts"]):
+        assert torch.all(y[i, :, :, c:] == 0), i                   # padded output slots are exactly 0
+        if c == 0:
+            assert float(losses[i]) == 0.0
+            continue
+        err = _maxdiff(y[i, :, :, :c].permute(1, 2, 0).cpu().numpy(), case["ref_pred"][i])
+        worst_y = max(worst_y, err)
+        assert err < 5e-5, (i, c, err)
+    err_l = _maxdiff(losses.cpu().numpy(), case["ref_losses"])
+    assert err_l < 5e-5, err_l
+    errs = _grad_errors(((name, p.grad) for name, p in m.named_parameters()), lambda name: case["ref_grads"][name])
+    print("%s, %s batch at V = 68: V_pred %.1e, losses %.1e, worst relative gradient error %.1e (%s) vs the fp64 oracle"
+          % (options, kind, worst_y, err_l, max(errs.values()), max(errs, key=errs.get)))
+    bad = {k: e for k, e in errs.items() if e > 1e-4}       # the bound of test_every_crowd_size_of_the_wave_path
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("options", ("f32_mfma", "split_bf16"))
+def test_wave_f32_kernels_ragged_batch_to_the_limit(dev, monkeypatch, options):
+    """The fp32-MFMA and the split-bf16 wave kernels on one shuffled ragged batch padded to V = 68, the documented limit
+    of txp_wave_f32_fits: crowds of 68, 65, 64, 33, 32, 17, 2, 1 and 0 (the mixed-V kernels; see _WAVE_F32_PEDS for what
+    each size runs) -- forward, losses and every gradient against the fp64 oracle, the empty scene with loss 0."""
+    _check_wave_f32_against_oracle(dev, "ragged", options, monkeypatch)
+
+
+@pytest.mark.parametrize("options", ("f32_mfma", "split_bf16"))
+def test_wave_f32_kernels_uniform_batch_at_the_limit(dev, monkeypatch, options):
+    """Three full scenes at V = 68 without num_peds: the uniform (non-mixed) kernels and the batch-order scene walk."""
+    _check_wave_f32_against_oracle(dev, "uniform", options, monkeypatch)
+
+
+def test_wave_f32_kernels_fused_loss_on_the_ragged_batch(dev, monkeypatch):
+    """The ragged batch above through Trainer.forward_backward under f32_mfma: the loss stage inside the backward scene
+    kernel (stg_model_bwd_nll) gives the losses and every gradient of the autograd route (bounds of
+    test_gpu_eval_optim.py: 1e-5 of the largest gradient entry).  Under split_bf16 nothing is fused and the caller is told."""
+    from social_stgcnn_amd import ops
+    from social_stgcnn_amd.trainer import Trainer
+    case = _wave_f32_case("ragged")
+    x, adj, tgt, peds = _wave_f32_inputs(dev, case)
+    monkeypatch.setitem(ops.OPTIONS, "f32_mfma", True)
+    m_ref, y_ref, l_ref = _wave_f32_autograd(dev, case)
+    fused_calls = []
+    inner = ops.backward_from_target
+    monkeypatch.setattr(ops, "backward_from_target", lambda *a, **k: fused_calls.append(inner(*a, **k)) or fused_calls[-1])
+    m = _model(dev, state=case["state"]).train()
+    _, losses, y = Trainer(m, lr=0.01).forward_backward(x, adj, tgt, peds)
+    assert len(fused_calls) == 1 and fused_calls[0] is not None          # the fused loss stage ran
+    assert torch.equal(y, y_ref)
+    assert torch.allclose(losses.cpu(), l_ref.cpu(), rtol=2e-6, atol=1e-6)
+    assert float(losses[case["counts"].index(0)]) == 0.0
+    ref = {k: p.grad for k, p in m_ref.named_parameters()}
+    gmax = max(float(g.abs().max()) for g in ref.values() if g is not None)
+    worst = 0.0
+    for k, p in m.named_parameters():
+        if ref[k] is None:
+            assert p.grad is None, k
+            continue
+        d = float((p.grad - ref[k]).abs().max())
+        worst = max(worst, d / gmax)
+        assert d <= 1e-5 * gmax, (k, d, gmax)
+    print("f32_mfma fused loss vs autograd route, ragged batch at V = 68: worst gradient difference %.1e of the largest "
+          "gradient entry" % worst)
+    monkeypatch.setattr(ops, "backward_from_target", inner)
+    monkeypatch.setitem(ops.OPTIONS, "f32_mfma", False)
+    monkeypatch.setitem(ops.OPTIONS, "split_bf16", True)
+    m2 = _model(dev, state=case["state"]).train()
+    y2, _ = m2(x, adj, peds)
+    assert ops.backward_from_target(m2, y2.detach(), tgt) is None
