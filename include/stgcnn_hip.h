@@ -416,6 +416,49 @@ int stg_track_push_streams_rule(const int64_t *det_id, int64_t id_stride, const 
                                 int32_t *num_peds, int32_t *out_flags, int32_t *seen, int block_threads,
                                 void *stream);
 
+/* Timestamped pushes at the tracker's own rate (added entry points, the ABI version stays).  Time is
+ * integer ticks (int64: a frame number, microseconds, whatever the caller's clock counts; differences must not overflow)
+ * and `step` the model's step in ticks.  A push carries its time det_time int64[1] in DEVICE memory, strictly greater
+ * than the stream's last push (the first push takes any time); a push that is not changes no state but the flags word
+ * head_flags[1] and returns the empty scene with STG_TRACK_TIME_ORDER.
+ *   State: slot_id int64[S] (-1 = free); per slot the ring of its newest R samples, t_ring int64 (S,R) and xy_ring
+ *   float64 (S,R,2) (rounded positions, ring order = time order, the oldest overwritten); slot_head int32 (S,2) = {next
+ *   write index, samples held}; clock int64[2] = {time of the last accepted push, accepted pushes so far}; head_flags
+ *   int32[2] = {unused, STG_TRACK_* flags of the last push}.  Zero slot_head / clock / head_flags and slot_id = -1 start
+ *   a stream.  2 <= R <= STG_TRACK_MAX_HISTORY (above: STG_EUNSUPPORTED).
+ *   Samples: a detection is recorded as (t_now, round(x), round(y)).  Duplicate ids, TRUNCATED, OVERFLOW, the order in
+ *   which new ids take free slots, TOO_MANY and the V smallest ids are those of stg_track_push.  A slot is live while
+ *   t_now - t_newest <= (T_obs-1) * step; it is freed, its ring emptied, at the start of the first push for which that
+ *   fails (on a feed of one push per step: the lifetime of stg_track_push).
+ *   Window: step k (oldest first) is the instant tau = t_now - (T_obs-1-k) * step.  It is observed iff the track has a
+ *   sample at exactly tau -- that position is taken, no arithmetic is done -- or samples ta < tau < tb adjacent in its
+ *   ring with tb - ta <= max_dt (1 <= max_dt <= (T_obs-1) * step): the position is then, per coordinate, in float64
+ *   with IEEE operations as written,  round(pa + (pb - pa) * ((double)(tau - ta) / (double)(tb - ta))).
+ *   step >= 1 and step * T_obs < 2^31 (above: STG_EUNSUPPORTED), so every difference is exact in a double.  The observed
+ *   steps are the presence bits (`seen`: bit j = step T_obs-1-j); membership (min_seen, max_gap) and the fill of the
+ *   missed steps, from observed steps that may themselves be interpolated, are those of the *_rule entry points.  Fed
+ *   pushes at t = f * step with max_dt = step and R >= T_obs, the scenes, seen and flags are those of
+ *   stg_track_push_rule bit for bit.
+ * stg_track_push_streams_timed: one workgroup per stream on the (NS, ...) slices of all of the above, det_time int64[NS],
+ * with det_start, pushed, out_flags and block_threads as stg_track_push_streams_rule takes them; a stream not pushed
+ * keeps its state bit for bit, its clock included.  Bad sizes, rules, R, step, max_dt or NULL pointers are refused before
+ * any launch.  No host synchronisation; everything is read when the kernel runs, so one captured graph serves every push
+ * whatever its time and count.                                                                                        */
+#define STG_TRACK_MAX_HISTORY 256
+#define STG_TRACK_TIME_ORDER 16 /* the push's time is not after the stream's last push (nothing recorded)       */
+int stg_track_push_timed(const int64_t *det_id, const double *det_xy, const int32_t *det_count,
+                         const int64_t *det_time, int M_max, int64_t *slot_id, int64_t *t_ring, double *xy_ring,
+                         int32_t *slot_head, int64_t *clock, int32_t *head_flags, int S, int R, int T_obs, double scale,
+                         int V, int64_t step, int64_t max_dt, int min_seen, int max_gap, double *obs_abs,
+                         int64_t *out_ids, int32_t *num_peds, int32_t *seen, void *stream);
+int stg_track_push_streams_timed(const int64_t *det_id, int64_t id_stride, const double *det_xy, int64_t xy_stride,
+                                 int M_total, const int32_t *det_start, const int32_t *pushed, const int64_t *det_time,
+                                 int NS, int M_max, int64_t *slot_id, int64_t *t_ring, double *xy_ring,
+                                 int32_t *slot_head, int64_t *clock, int32_t *head_flags, int S, int R, int T_obs,
+                                 double scale, int V, int64_t step, int64_t max_dt, int min_seen, int max_gap,
+                                 double *obs_abs, int64_t *out_ids, int32_t *num_peds, int32_t *out_flags,
+                                 int32_t *seen, int block_threads, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * N7  what a caller acts on, reduced from the K samples of N5 without writing them out: conflict and zone-occupancy
  *     counts.  pred, strides, obs_last, num_peds (clamped to [0, V]), noise, seed and seed_dev exactly as in

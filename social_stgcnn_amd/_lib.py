@@ -103,6 +103,11 @@ _SIGNATURES = {
                                   c_f, c_f, c_f, c_f, c_f]),
     "stg_track_push_streams_rule": (c_i, [c_f, c_l, c_f, c_l, c_i, c_f, c_f, c_i, c_i, c_f, c_f, c_f, c_f, c_i, c_i,
                                           ctypes.c_double, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_i, c_f]),
+    "stg_track_push_timed": (c_i, [c_f, c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i,
+                                   ctypes.c_double, c_i, c_l, c_l, c_i, c_i, c_f, c_f, c_f, c_f, c_f]),
+    "stg_track_push_streams_timed": (c_i, [c_f, c_l, c_f, c_l, c_i, c_f, c_f, c_f, c_i, c_i, c_f, c_f, c_f, c_f, c_f,
+                                           c_f, c_i, c_i, c_i, ctypes.c_double, c_i, c_l, c_l, c_i, c_i, c_f, c_f, c_f,
+                                           c_f, c_f, c_i, c_f]),
     "stg_score_push": (c_i, [c_f, c_f, c_f, c_i, ctypes.c_double, c_f, c_f, c_l, c_l, c_l, c_l, c_f, c_f, c_f, c_i, c_i,
                              c_i, ctypes.POINTER(ScoreState), c_f, c_i, ctypes.POINTER(ScoreOut), c_f]),
     "stg_score_push_streams": (c_i, [c_f, c_l, c_f, c_l, c_i, c_f, c_f, c_i, c_i, ctypes.c_double, c_f, c_f, c_l, c_l,

@@ -1,0 +1,414 @@
+// frames_time: the live push with TIME.  stg_track_push of frames.hip takes every push for one model
+// step; here a push carries its time in integer ticks and the scene is built "as of now": each pedestrian's position at
+// t_now - k * step, k = 0 .. T_obs-1, taken from the track's samples -- a sample at exactly that instant as it is, else
+// the linear interpolation of the two samples that bracket it when they are at most max_dt apart.  An instant with
+// neither is a missed step and goes through TrackRule (track_rule.hpp): membership by the presence bits, the fill of
+// the missed steps from the observed ones.
+//
+//   stg_track_push_timed          ONE workgroup, the state of one stream: slot ids, per slot a ring of its newest R
+//                                 samples (time, rounded position), {next write index, count} per slot, the clock
+//   stg_track_push_streams_timed  one workgroup per stream on the (NS, ...) slices, as stg_track_push_streams_rule
+//
+// The sort, the id lookup and the slot assignment are those of track_push_body (detections.hpp, the same order of new
+// ids over free slots); a slot is live by its newest sample's age instead of a presence mask.  Everything is read from
+// device memory when the kernel runs -- the time too -- so one captured graph serves every push.  Integer work, float64
+// arithmetic with IEEE operations as written, plain C++ stores, LDS atomics on integer words, no scratch, no host
+// synchronisation.
+#include "detections.hpp"
+#include "track_rule.hpp"
+
+namespace stg {
+
+constexpr int kFlagTimeOrder = STG_TRACK_TIME_ORDER;
+
+// round(pa + (pb - pa) * w): the statement's interpolation, one IEEE operation at a time
+__device__ __forceinline__ double lerp_pos(double pa, double pb, double w, double scale) {
+#pragma clang fp contract(off)
+    const double d = pb - pa;
+    const double p = d * w;
+    return round_pos(pa + p, scale);
+}
+
+// The slot's samples as a push sees them, oldest first: the newest n_old = min(count, R - 1) recorded ones (the one
+// this push overwrites is not among them) and then this push's own.  ring_at: ring index of logical sample i < n_old.
+__device__ __forceinline__ int ring_at(int head, int n_old, int i, int R) {
+    const int x = head + R - n_old + i;                     // < 2 R
+    return x >= R ? x - R : x;
+}
+
+// One timed push of one stream by one workgroup of kThreads threads; the arguments of track_push_body with the timed
+// state in the place of mask / ring: t_ring (S,R), xy_ring (S,R,2), slot_head (S,2), clock (2).  Returns the flags.
+// LDS layout (dynamic): sort keys (M2 x int64), sort indices (M2 x int32), det_slot, det_rank (M_max x int32 each),
+// slot masks, free slots, slot heads, slot counts (S x 4 bytes each), found (M_max x T_obs bytes: the logical index of
+// the sample at or below each observed instant, so the scene pass does not search again)
+template <int kThreads>
+__device__ __forceinline__ int track_push_timed_body(
+    const int64_t *__restrict__ det_id, int64_t id_stride, const double *__restrict__ det_xy, int64_t xy_stride,
+    int count, int64_t t_now, int M_max, int M2, int64_t *__restrict__ slot_id, int64_t *__restrict__ t_ring,
+    double *__restrict__ xy_ring, int32_t *__restrict__ slot_head, int64_t *__restrict__ clock,
+    int32_t *__restrict__ head_flags, int S, int R, int T_obs, double scale, int V, int64_t step, int64_t max_dt,
+    TrackRule rule, double *__restrict__ obs_abs, int64_t *__restrict__ out_ids, int32_t *__restrict__ num_peds,
+    int32_t *__restrict__ seen) {
+    extern __shared__ __align__(16) unsigned char lds[];
+    int64_t *key = reinterpret_cast<int64_t *>(lds);
+    int32_t *kidx = reinterpret_cast<int32_t *>(key + M2);
+    int32_t *det_slot = kidx + M2;
+    int32_t *det_rank = det_slot + M_max;
+    uint32_t *smask = reinterpret_cast<uint32_t *>(det_rank + M_max);
+    int32_t *free_list = reinterpret_cast<int32_t *>(smask + S);
+    int32_t *shead = free_list + S;
+    int32_t *scnt = shead + S;
+    uint8_t *found = reinterpret_cast<uint8_t *>(scnt + S);
+    __shared__ int wave_cnt[kThreads / kWave];
+    __shared__ int flags;
+
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const uint32_t full = T_obs >= 32 ? 0xffffffffu : (1u << T_obs) - 1u;
+    const int64_t last = clock[0], pushes = clock[1];
+
+    // 0. time must move forward (the first push takes any time): otherwise the empty scene and no change of state.
+    //    Uniform over the block, ahead of every barrier.
+    if (pushes > 0 && t_now <= last) {
+        for (int e = tid; e < V; e += nt) {
+            out_ids[e] = -1;
+            seen[e] = 0;
+        }
+        for (int e = tid; e < T_obs * V * 2; e += nt) obs_abs[e] = 0.0;
+        if (tid == 0) {
+            num_peds[0] = 0;
+            head_flags[1] = kFlagTimeOrder;
+        }
+        return kFlagTimeOrder;
+    }
+
+    int m = count;
+    const bool truncated = m > M_max;
+    m = m < 0 ? 0 : (m > M_max ? M_max : m);
+    if (tid == 0) flags = truncated ? kFlagTruncated : 0;
+
+    // 1. a slot whose newest sample is older than T_obs - 1 steps is free, its ring empty.  Load the detections into
+    //    the sort buffer (padding keys sort last).
+    const int64_t span = (int64_t)(T_obs - 1) * step;
+    for (int s = tid; s < S; s += nt) {
+        int h = slot_head[2 * s], c = slot_head[2 * s + 1];
+        if (c > 0 && t_now - t_ring[(int64_t)s * R + (h == 0 ? R - 1 : h - 1)] > span) {
+            h = c = 0;
+            slot_id[s] = -1;
+            slot_head[2 * s] = 0;
+            slot_head[2 * s + 1] = 0;
+        }
+        smask[s] = 0;
+        shead[s] = h;
+        scnt[s] = c;
+    }
+    const int n2 = det_sort_n(m);                           // (<= M2)
+    det_load(key, kidx, det_id, id_stride, m, n2, tid, nt);
+    for (int j = tid; j < m; j += nt) det_slot[j] = -1;
+    __syncthreads();
+
+    // 2. sort the detections by (id, detection index)
+    det_sort(key, kidx, n2, tid, nt);
+
+    // 3. a repeated id: the first detection wins.  Every live slot finds its id among the detections.
+    for (int p = tid; p < m; p += nt)
+        if (p > 0 && key[p] == key[p - 1]) {
+            det_slot[kidx[p]] = -2;
+            atomicOr(&flags, kFlagDuplicate);
+        }
+    for (int s = tid; s < S; s += nt) {
+        if (scnt[s] == 0) continue;
+        const int at = det_find(key, m, slot_id[s]);
+        if (at >= 0) det_slot[kidx[at]] = s;
+    }
+    __syncthreads();
+
+    // 4. new ids take free slots: the i-th new detection (detection order) gets the i-th free slot (slot order)
+    int n_free = 0, tot = 0;
+    for (int s0 = 0; s0 < S; s0 += nt) {
+        const int s = s0 + tid;
+        const bool fr = s < S && scnt[s] == 0;
+        const int r = block_rank<kThreads>(fr, n_free, &tot, wave_cnt);
+        if (fr) free_list[r] = s;
+        n_free += tot;
+    }
+    __syncthreads();
+    int n_new = 0;
+    for (int j0 = 0; j0 < m; j0 += nt) {
+        const int j = j0 + tid;
+        const bool nw = j < m && det_slot[j] == -1;
+        const int r = block_rank<kThreads>(nw, n_new, &tot, wave_cnt);
+        if (nw) {
+            if (r < n_free) det_slot[j] = free_list[r];
+            else {
+                det_slot[j] = -3;
+                atomicOr(&flags, kFlagOverflow);
+            }
+        }
+        n_new += tot;
+    }
+    __syncthreads();
+
+    // 5. record this push's sample (time, rounded position) at the slot's write index; the ring entry it overwrites is
+    //    outside what the search below reads (n_old <= R - 1), so the two need no barrier between them
+    for (int j = tid; j < m; j += nt) {
+        const int s = det_slot[j];
+        if (s < 0) continue;
+        const int h = shead[s], c = scnt[s];
+        const int64_t at = (int64_t)s * R + h;
+        slot_id[s] = det_id[j * id_stride];
+        atomicOr(&smask[s], 1u);
+        t_ring[at] = t_now;
+        xy_ring[at * 2] = round_pos(det_xy[j * xy_stride], scale);
+        xy_ring[at * 2 + 1] = round_pos(det_xy[j * xy_stride + 1], scale);
+        slot_head[2 * s] = h + 1 == R ? 0 : h + 1;
+        slot_head[2 * s + 1] = c < R ? c + 1 : R;
+    }
+
+    // 6. one thread per (detection with a slot, earlier window step k): binary search of the instant in the slot's
+    //    times (ring order is time order).  Observed: a sample at the instant, or its neighbours at most max_dt apart.
+    const int T1 = T_obs - 1;
+    for (int e = tid; e < m * T1; e += nt) {
+        const int j = e / T1, k = e % T1;
+        const int s = det_slot[j];
+        if (s < 0) continue;
+        const int c = scnt[s], n_old = c < R - 1 ? c : R - 1, h = shead[s];
+        const int64_t tau = t_now - (int64_t)(T1 - k) * step;
+        const int64_t *tr = t_ring + (int64_t)s * R;
+        int lo = 0, hi = n_old;                              // the first sample later than tau
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (tr[ring_at(h, n_old, mid, R)] <= tau) lo = mid + 1;
+            else hi = mid;
+        }
+        const int i = lo - 1;
+        if (i < 0) continue;
+        const int64_t ta = tr[ring_at(h, n_old, i, R)];
+        const int64_t tb = i + 1 < n_old ? tr[ring_at(h, n_old, i + 1, R)] : t_now;
+        if (ta == tau || tb - ta <= max_dt) {
+            atomicOr(&smask[s], 1u << (T1 - k));
+            found[j * T_obs + k] = (uint8_t)i;
+        }
+    }
+    __syncthreads();
+
+    // 7. the scene: the rule's members in ascending id order (the sorted detections), the first V of them
+    int c = 0;
+    for (int p0 = 0; p0 < m; p0 += nt) {
+        const int p = p0 + tid;
+        const int j = p < m ? kidx[p] : 0;
+        const int s = p < m ? det_slot[j] : -1;
+        const bool in = s >= 0 && rule.member(smask[s]);
+        const int r = block_rank<kThreads>(in, c, &tot, wave_cnt);
+        if (p < m) det_rank[j] = in && r < V ? r : -1;
+        if (in && r < V) {
+            out_ids[r] = key[p];
+            seen[r] = (int32_t)smask[s];
+        }
+        c += tot;
+    }
+    if (c > V && tid == 0) atomicOr(&flags, kFlagTooMany);
+    const int np = c < V ? c : V;
+    __syncthreads();
+
+    // 8. one thread per (member, observed step): the sample at the instant, or the interpolation of its bracket; this
+    //    push's own sample comes from the input (the ring entry written above is another thread's store)
+    for (int e = tid; e < m * T_obs; e += nt) {
+        const int j = e / T_obs, k = e % T_obs;
+        const int r = det_rank[j];
+        if (r < 0) continue;
+        const int s = det_slot[j];
+        if (((smask[s] >> (T1 - k)) & 1u) == 0) continue;
+        const double nx = round_pos(det_xy[j * xy_stride], scale), ny = round_pos(det_xy[j * xy_stride + 1], scale);
+        double x = nx, y = ny;
+        if (k < T1) {
+            const int cs = scnt[s], n_old = cs < R - 1 ? cs : R - 1, h = shead[s], i = found[j * T_obs + k];
+            const int64_t tau = t_now - (int64_t)(T1 - k) * step;
+            const int64_t a = (int64_t)s * R + ring_at(h, n_old, i, R);
+            const int64_t ta = t_ring[a];
+            x = xy_ring[a * 2];
+            y = xy_ring[a * 2 + 1];
+            if (ta != tau) {
+                int64_t tb = t_now;
+                double bx = nx, by = ny;
+                if (i + 1 < n_old) {
+                    const int64_t b = (int64_t)s * R + ring_at(h, n_old, i + 1, R);
+                    tb = t_ring[b];
+                    bx = xy_ring[b * 2];
+                    by = xy_ring[b * 2 + 1];
+                }
+                const double w = (double)(tau - ta) / (double)(tb - ta);
+                x = lerp_pos(x, bx, w, scale);
+                y = lerp_pos(y, by, w, scale);
+            }
+        }
+        obs_abs[((int64_t)k * V + r) * 2] = x;
+        obs_abs[((int64_t)k * V + r) * 2 + 1] = y;
+    }
+    __syncthreads();
+
+    // 9. a member with missed steps: TrackRule::fill in place (a seen step is read before it is written)
+    for (int j = tid; j < m; j += nt) {
+        const int r = det_rank[j];
+        if (r < 0) continue;
+        const uint32_t pm = smask[det_slot[j]];
+        if (pm == full) continue;
+        TrackRule::fill(
+            pm, T_obs, scale,
+            [&](int t, double &x, double &y) {
+                x = obs_abs[((int64_t)t * V + r) * 2];
+                y = obs_abs[((int64_t)t * V + r) * 2 + 1];
+            },
+            [&](int t, double x, double y) {
+                obs_abs[((int64_t)t * V + r) * 2] = x;
+                obs_abs[((int64_t)t * V + r) * 2 + 1] = y;
+            });
+    }
+    for (int e = np + tid; e < V; e += nt) {
+        out_ids[e] = -1;
+        seen[e] = 0;
+    }
+    for (int e = tid; e < T_obs * (V - np); e += nt) {
+        const int t = e / (V - np), r = np + e % (V - np);
+        obs_abs[((int64_t)t * V + r) * 2] = 0.0;
+        obs_abs[((int64_t)t * V + r) * 2 + 1] = 0.0;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        num_peds[0] = np;
+        head_flags[1] = flags;
+        clock[0] = t_now;
+        clock[1] = pushes + 1;
+    }
+    return flags;
+}
+
+__global__ __launch_bounds__(kPushThreads) void track_push_timed_kernel(
+    const int64_t *__restrict__ det_id, const double *__restrict__ det_xy, const int32_t *__restrict__ det_count,
+    const int64_t *__restrict__ det_time, int M_max, int M2, int64_t *__restrict__ slot_id,
+    int64_t *__restrict__ t_ring, double *__restrict__ xy_ring, int32_t *__restrict__ slot_head,
+    int64_t *__restrict__ clock, int32_t *__restrict__ head_flags, int S, int R, int T_obs, double scale, int V,
+    int64_t step, int64_t max_dt, TrackRule rule, double *__restrict__ obs_abs, int64_t *__restrict__ out_ids,
+    int32_t *__restrict__ num_peds, int32_t *__restrict__ seen) {
+    track_push_timed_body<kPushThreads>(det_id, 1, det_xy, 2, det_count[0], det_time[0], M_max, M2, slot_id, t_ring,
+                                        xy_ring, slot_head, clock, head_flags, S, R, T_obs, scale, V, step, max_dt,
+                                        rule, obs_abs, out_ids, num_peds, seen);
+}
+
+// One workgroup per stream, as track_push_stream: a stream not pushed keeps its state, its clock included
+template <int kThreads>
+__global__ __launch_bounds__(kThreads) void track_push_streams_timed_kernel(
+    const int64_t *__restrict__ det_id, int64_t id_stride, const double *__restrict__ det_xy, int64_t xy_stride,
+    int M_total, const int32_t *__restrict__ det_start, const int32_t *__restrict__ pushed,
+    const int64_t *__restrict__ det_time, int M_max, int M2, int64_t *__restrict__ slot_id,
+    int64_t *__restrict__ t_ring, double *__restrict__ xy_ring, int32_t *__restrict__ slot_head,
+    int64_t *__restrict__ clock, int32_t *__restrict__ head_flags, int S, int R, int T_obs, double scale, int V,
+    int64_t step, int64_t max_dt, TrackRule rule, double *__restrict__ obs_abs, int64_t *__restrict__ out_ids,
+    int32_t *__restrict__ num_peds, int32_t *__restrict__ out_flags, int32_t *__restrict__ seen) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    double *obs = obs_abs + (int64_t)b * T_obs * V * 2;
+    int64_t *oid = out_ids + (int64_t)b * V;
+    int32_t *osn = seen + (int64_t)b * V;
+    if (pushed[b] == 0) {                                   // uniform over the block: no barrier is skipped halfway
+        for (int e = tid; e < V; e += kThreads) {
+            oid[e] = -1;
+            osn[e] = 0;
+        }
+        for (int e = tid; e < T_obs * V * 2; e += kThreads) obs[e] = 0.0;
+        if (tid == 0) {
+            num_peds[b] = 0;
+            if (out_flags) out_flags[b] = 0;
+        }
+        return;
+    }
+    int lo;
+    const int count = det_range(det_start, b, M_total, lo);
+    const int flags = track_push_timed_body<kThreads>(
+        det_id + lo * id_stride, id_stride, det_xy + lo * xy_stride, xy_stride, count, det_time[b], M_max, M2,
+        slot_id + (int64_t)b * S, t_ring + (int64_t)b * S * R, xy_ring + (int64_t)b * S * R * 2,
+        slot_head + (int64_t)b * S * 2, clock + 2 * b, head_flags + 2 * b, S, R, T_obs, scale, V, step, max_dt, rule,
+        obs, oid, num_peds + b, osn);
+    if (out_flags && tid == 0) out_flags[b] = flags;
+}
+
+// dynamic LDS of a timed push: the sort arrays, det_slot and det_rank, four words per slot, one byte per
+// (detection, step)
+static inline size_t push_timed_lds(int M_max, int M2, int S, int T_obs) {
+    return det_sort_lds(M2) + (size_t)M_max * 2 * sizeof(int32_t) + (size_t)S * 4 * sizeof(int32_t) +
+           (size_t)M_max * T_obs;
+}
+
+// the checks the two entry points share, under the name `what`
+static int timed_args(const char *what, int M_max, int S, int R, int T_obs, int V, int64_t step, int64_t max_dt,
+                      int min_seen, int max_gap) {
+    STG_REQUIRE(M_max >= 1 && M_max <= STG_TRACK_MAX_DETECTIONS && S >= 1 && S <= STG_TRACK_MAX_SLOTS && V >= 1,
+                STG_EINVAL, "%s: bad sizes M_max=%d S=%d V=%d", what, M_max, S, V);
+    STG_REQUIRE_RULE(what);
+    STG_REQUIRE(R >= 2, STG_EINVAL, "%s: R=%d samples per track (at least 2)", what, R);
+    STG_REQUIRE(R <= STG_TRACK_MAX_HISTORY, STG_EUNSUPPORTED, "%s: R=%d above STG_TRACK_MAX_HISTORY=%d", what, R,
+                STG_TRACK_MAX_HISTORY);
+    STG_REQUIRE(step >= 1, STG_EINVAL, "%s: step=%lld ticks (at least 1)", what, (long long)step);
+    STG_REQUIRE(step < ((int64_t)1 << 31) && step * T_obs < ((int64_t)1 << 31), STG_EUNSUPPORTED,
+                "%s: step=%lld: step * T_obs must stay below 2^31", what, (long long)step);
+    STG_REQUIRE(max_dt >= 1 && max_dt <= (int64_t)(T_obs - 1) * step, STG_EINVAL,
+                "%s: max_dt=%lld not in [1, (T_obs - 1) * step = %lld]", what, (long long)max_dt,
+                (long long)((int64_t)(T_obs - 1) * step));
+    return STG_OK;
+}
+
+}  // namespace stg
+
+extern "C" {
+
+int stg_track_push_timed(const int64_t *det_id, const double *det_xy, const int32_t *det_count,
+                         const int64_t *det_time, int M_max, int64_t *slot_id, int64_t *t_ring, double *xy_ring,
+                         int32_t *slot_head, int64_t *clock, int32_t *head_flags, int S, int R, int T_obs, double scale,
+                         int V, int64_t step, int64_t max_dt, int min_seen, int max_gap, double *obs_abs,
+                         int64_t *out_ids, int32_t *num_peds, int32_t *seen, void *stream) {
+    const char *what = "stg_track_push_timed";
+    const int rc = stg::timed_args(what, M_max, S, R, T_obs, V, step, max_dt, min_seen, max_gap);
+    if (rc != STG_OK) return rc;
+    STG_REQUIRE(det_id && det_xy && det_count && det_time && slot_id && t_ring && xy_ring && slot_head && clock &&
+                    head_flags && obs_abs && out_ids && num_peds && seen,
+                STG_EINVAL, "%s: null pointer", what);
+    const int m2 = stg::det_sort_n(M_max);
+    return stg::launch({what, dim3(1), dim3(stg::kPushThreads), stg::push_timed_lds(M_max, m2, S, T_obs),
+                        stg::as_stream(stream), 64 * 1024},
+                       stg::track_push_timed_kernel, det_id, det_xy, det_count, det_time, M_max, m2, slot_id, t_ring,
+                       xy_ring, slot_head, clock, head_flags, S, R, T_obs, scale, V, step, max_dt,
+                       stg::TrackRule{min_seen, max_gap}, obs_abs, out_ids, num_peds, seen);
+}
+
+int stg_track_push_streams_timed(const int64_t *det_id, int64_t id_stride, const double *det_xy, int64_t xy_stride,
+                                 int M_total, const int32_t *det_start, const int32_t *pushed, const int64_t *det_time,
+                                 int NS, int M_max, int64_t *slot_id, int64_t *t_ring, double *xy_ring,
+                                 int32_t *slot_head, int64_t *clock, int32_t *head_flags, int S, int R, int T_obs,
+                                 double scale, int V, int64_t step, int64_t max_dt, int min_seen, int max_gap,
+                                 double *obs_abs, int64_t *out_ids, int32_t *num_peds, int32_t *out_flags,
+                                 int32_t *seen, int block_threads, void *stream) {
+    const char *what = "stg_track_push_streams_timed";
+    STG_REQUIRE(NS >= 1 && NS <= STG_TRACK_MAX_STREAMS && M_total >= 0 && M_total <= STG_TRACK_MAX_TOTAL_DETECTIONS &&
+                    id_stride >= 1 && xy_stride >= 2,
+                STG_EINVAL, "%s: bad sizes NS=%d M_total=%d strides %lld/%lld", what, NS, M_total, (long long)id_stride,
+                (long long)xy_stride);
+    const int rc = stg::timed_args(what, M_max, S, R, T_obs, V, step, max_dt, min_seen, max_gap);
+    if (rc != STG_OK) return rc;
+    if (block_threads == 0) block_threads = stg::kStreamThreads;
+    STG_REQUIRE(block_threads == 64 || block_threads == 256 || block_threads == 1024, STG_EINVAL,
+                "%s: block_threads=%d (0, 64, 256 or 1024)", what, block_threads);
+    STG_REQUIRE(det_id && det_xy && det_start && pushed && det_time && slot_id && t_ring && xy_ring && slot_head &&
+                    clock && head_flags && obs_abs && out_ids && num_peds && seen,
+                STG_EINVAL, "%s: null pointer", what);
+    const int m2 = stg::det_sort_n(M_max);
+    const stg::Launch l{what, dim3(NS), dim3(block_threads), stg::push_timed_lds(M_max, m2, S, T_obs),
+                        stg::as_stream(stream), 64 * 1024};
+    auto go = [&](auto kernel) {
+        return stg::launch(l, kernel, det_id, id_stride, det_xy, xy_stride, M_total, det_start, pushed, det_time, M_max,
+                           m2, slot_id, t_ring, xy_ring, slot_head, clock, head_flags, S, R, T_obs, scale, V, step,
+                           max_dt, stg::TrackRule{min_seen, max_gap}, obs_abs, out_ids, num_peds, out_flags, seen);
+    };
+    if (block_threads == 64) return go(stg::track_push_streams_timed_kernel<64>);
+    if (block_threads == 256) return go(stg::track_push_streams_timed_kernel<256>);
+    return go(stg::track_push_streams_timed_kernel<1024>);
+}
+
+}  // extern "C"

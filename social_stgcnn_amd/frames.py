@@ -23,6 +23,9 @@ stg_frame_scenes over a recording uploaded once, stg_track_push with the track s
     ScoreSpec          score=ScoreSpec(levels, best_of_k) on the two live predictors: every push also scores the
                        predictions of the last pred_seq_len pushes against its detections (stg_score_push, DESIGN.md
                        5.17); `.score`, `.score_totals`, and score_summary for host numbers
+    TimeRule           time=TimeRule(step, max_dt, history) on the two live predictors: pushes carry their time in
+                       integer ticks and arrive at the tracker's own rate; every push predicts from the scene "as of
+                       now", the tracks resampled at t - k * step on the device (stg_track_push_timed)
 
 The two live predictors are one core, _LivePredictor: the argument checks, the track state, the eager push and its
 capture (the push kernel ahead of predict.Predictor.capture_chain; the capture recipe itself is graphs.py).  Each class
@@ -45,9 +48,10 @@ MAX_DETECTIONS = 2048                  # STG_TRACK_MAX_DETECTIONS
 MAX_SLOTS = 2048                       # STG_TRACK_MAX_SLOTS
 MAX_STREAMS = 4096                     # STG_TRACK_MAX_STREAMS
 MAX_TOTAL_DETECTIONS = MAX_STREAMS * MAX_DETECTIONS      # STG_TRACK_MAX_TOTAL_DETECTIONS
+MAX_HISTORY = 256                      # STG_TRACK_MAX_HISTORY
 STREAM_THREADS = 256                   # stg_track_push_streams' default workgroup (kStreamThreads, csrc/frames.hip)
 # FramePrediction.flags bits (STG_TRACK_* in include/stgcnn_hip.h)
-DUPLICATE, OVERFLOW, TRUNCATED, TOO_MANY = 1, 2, 4, 8
+DUPLICATE, OVERFLOW, TRUNCATED, TOO_MANY, TIME_ORDER = 1, 2, 4, 8, 16
 
 FrameScenes = collections.namedtuple("FrameScenes", "frame obs_abs ids num_peds")
 FrameScenes.__doc__ = """frame (N,) float64 numpy: the frame numbers of the scenes; on the device: obs_abs (N,T_obs,V,2)
@@ -94,11 +98,51 @@ def _rule(tracks, obs_len):
     return (tracks if isinstance(tracks, TrackRule) else TrackRule(*tracks)).checked(obs_len)
 
 
+class TimeRule(collections.namedtuple("TimeRule", "step max_dt history")):
+    """Live pushes with time.  Time is integer ticks (the recording's frame number, microseconds, whatever the caller's
+    clock counts); `step` is the model's step in ticks (10 for the ETH/UCY recordings: frame numbers 10 apart).  A push
+    at time t predicts from the positions at t - k * step, k = 0 .. obs_len - 1: a sample recorded at exactly that
+    instant, else the linear interpolation (float64, rounded like an observed position) of the two samples next to it
+    when they are at most max_dt ticks apart (default: step; 1 <= max_dt <= (obs_len - 1) * step); an instant with
+    neither is a missed step under the predictor's TrackRule (TrackRule(obs_len, 0) without tracks=).  Every track keeps
+    its newest `history` samples (2 .. 256) and lives while its newest one is at most (obs_len - 1) * step old.  A push
+    whose time is not after the stream's last one changes nothing and returns the empty scene, flag TIME_ORDER."""
+    __slots__ = ()
+
+    def __new__(cls, step, max_dt=None, history=96):
+        if not _is_int(step, 1, (1 << 31) - 1):
+            raise ValueError("TimeRule: step must be an integer number of ticks in [1, 2^31), got %r" % (step,))
+        if max_dt is not None and not _is_int(max_dt, 1, (1 << 31) - 1):
+            raise ValueError("TimeRule: max_dt must be None or an integer in [1, (obs_len - 1) * step], got %r"
+                             % (max_dt,))
+        if not _is_int(history, 2, MAX_HISTORY):
+            raise ValueError("TimeRule: history must be an integer in [2, %d], got %r" % (MAX_HISTORY, history))
+        return super().__new__(cls, int(step), None if max_dt is None else int(max_dt), int(history))
+
+    def checked(self, obs_len):
+        """The rule with max_dt resolved, once it fits a window of obs_len steps."""
+        if obs_len < 2:
+            raise ValueError("TimeRule: obs_len=%d (a timed window has at least 2 steps)" % obs_len)
+        if self.step * obs_len >= 1 << 31:
+            raise ValueError("TimeRule: step=%d: step * obs_len must stay below 2^31" % self.step)
+        max_dt = self.step if self.max_dt is None else self.max_dt
+        if max_dt > (obs_len - 1) * self.step:
+            raise ValueError("TimeRule: max_dt=%d > (obs_len - 1) * step = %d (a track is forgotten by then)"
+                             % (max_dt, (obs_len - 1) * self.step))
+        return TimeRule(self.step, max_dt, self.history)
+
+
+def _tick_time(t, what):
+    if isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, np.integer)) or not -(1 << 62) <= int(t) < 1 << 62:
+        raise ValueError("%s: the time must be an integer number of ticks (|t| < 2^62), got %r" % (what, t))
+    return int(t)
+
+
 FramePrediction = collections.namedtuple("FramePrediction", "ids num_peds obs_abs samples mean v_pred flags")
 FramePrediction.__doc__ = """One push, on the device: ids (V,) int64 (-1 in padded slots), num_peds (1,) int32,
 obs_abs (1,T_obs,V,2) float64, samples (K,P,V,2), mean (P,V,2), v_pred (5,P,V) float32, flags (1,) int32 (DUPLICATE |
-OVERFLOW | TRUNCATED | TOO_MANY of this push).  From a captured push the tensors are the graph's static buffers,
-overwritten by the next push."""
+OVERFLOW | TRUNCATED | TOO_MANY | TIME_ORDER of this push).  From a captured push the tensors are the graph's static
+buffers, overwritten by the next push."""
 
 
 def _is_int(x, lo, hi=None):
@@ -286,7 +330,8 @@ class _LivePredictor:
     """What FramePredictor and StreamsPredictor share: the argument checks, the track state on the device (with the
     subclass's leading axis), the eager push and its capture as ONE graph.  A subclass supplies
 
-        _stage(*det, seed)       copy one push's detections (and the seed, unless None) into its device staging buffers
+        _stage(*det, seed)       copy one push's detections (and the seed, unless None) into its device staging buffers;
+                                 with time= it takes the push's time(s) by keyword and stages them with the detections
         _outs()                  fresh per-push outputs (obs_abs, ids, num_peds, ...; under a TrackRule `seen` last)
         _push(outs)              launch its push kernel: staging buffers + track state -> outs
         _det                     its staging buffers by the names ops.score_push takes them, in the order its push
@@ -297,9 +342,12 @@ class _LivePredictor:
     and `seed_dev`, the (1,) int64 device tensor the sampler reads its seed from."""
 
     def __init__(self, model, k, obs_len, capacity, max_peds, max_detections, decimals, risk=None, keep_samples=True,
-                 tracks=None, score=None):
+                 tracks=None, score=None, time=None):
         self.model = model
         self.k = int(k)
+        if time is not None and score is not None:
+            raise ValueError("time= together with score= is not supported: the score records are indexed by push, and "
+                             "re-indexing them by time is a change of its own (DESIGN.md 8)")
         self._risk_args = (risk, keep_samples)
         if score is not None:
             score = score if isinstance(score, ScoreSpec) else ScoreSpec(*score)
@@ -322,6 +370,11 @@ class _LivePredictor:
             raise ValueError("obs_len=%d but the model observes %d frames" % (self.t_obs, model.seq_len))
         self.scale = _scale(decimals)
         self.rule = _rule(tracks, self.t_obs)
+        self.time = None
+        if time is not None:
+            self.time = (time if isinstance(time, TimeRule) else TimeRule(*time)).checked(self.t_obs)
+            if self.rule is None:                            # a timed push always goes through the rule, and writes `seen`
+                self.rule = TrackRule(self.t_obs, 0)
         self.seen = None
         self.s, self.v, self.m_max = int(capacity), int(max_peds), int(max_detections)
         if not 1 <= self.s <= MAX_SLOTS:
@@ -333,14 +386,26 @@ class _LivePredictor:
 
     def _track_state(self, lead=()):
         """Look the model's device up (every argument has been checked by now) and allocate the track state, one set
-        per index of `lead`: slot ids, presence masks, the position ring and {head, flags}."""
+        per index of `lead`: slot ids, presence masks, the position ring and {head, flags}; with time= the sample
+        rings (times, positions), their {write index, count} and the clock in the place of masks and ring."""
         dev = next(self.model.parameters()).device
         require_gpu(next(self.model.parameters()))
         self.device = dev
         self.slot_id = torch.empty(lead + (self.s,), device=dev, dtype=torch.int64)
-        self.mask = torch.empty(lead + (self.s,), device=dev, dtype=torch.int32)
-        self.ring = torch.zeros(lead + (self.t_obs, self.s, 2), device=dev, dtype=torch.float64)
         self.head_flags = torch.empty(lead + (2,), device=dev, dtype=torch.int32)
+        if self.time is None:
+            self.mask = torch.empty(lead + (self.s,), device=dev, dtype=torch.int32)
+            self.ring = torch.zeros(lead + (self.t_obs, self.s, 2), device=dev, dtype=torch.float64)
+            self._state = (self.slot_id, self.mask, self.ring, self.head_flags)
+            self._forget = (self.mask, self.head_flags)      # (a ring row is read only where the mask says seen)
+        else:
+            r = self.time.history
+            self.t_ring = torch.zeros(lead + (self.s, r), device=dev, dtype=torch.int64)
+            self.xy_ring = torch.zeros(lead + (self.s, r, 2), device=dev, dtype=torch.float64)
+            self.slot_head = torch.empty(lead + (self.s, 2), device=dev, dtype=torch.int32)
+            self.clock = torch.empty(lead + (2,), device=dev, dtype=torch.int64)
+            self._state = (self.slot_id, self.t_ring, self.xy_ring, self.slot_head, self.clock, self.head_flags)
+            self._forget = (self.slot_head, self.clock, self.head_flags)     # (a ring holds what its count says)
         self._pred = Predictor(self.model, self.k, *self._risk_args)
         if self.score_spec is not None:
             spec = self.score_spec
@@ -369,6 +434,14 @@ class _LivePredictor:
         """The push kernel `name` on the detections `det` (its leading arguments) and the track state, or under a
         TrackRule its *_rule twin: the rule goes ahead of the kernel's n_out outputs, `seen` (the last of outs) behind."""
         rule, seen = ((), ()) if self.rule is None else (tuple(self.rule), (ptr(outs[-1]),))
+        if self.time is not None:
+            # the timed twin: the time(s) behind the detections, the sample rings as the state, (step, max_dt) ahead
+            # of the rule
+            name += "_timed"
+            check(getattr(lib(), name)(*det, *map(ptr, self._state), self.s, self.time.history, self.t_obs,
+                                       ctypes.c_double(self.scale), self.v, self.time.step, self.time.max_dt, *rule,
+                                       *map(ptr, outs[:n_out]), *seen, *tail, stream_ptr()), name)
+            return
         name += "_rule" if rule else ""
         check(getattr(lib(), name)(*det, ptr(self.slot_id), ptr(self.mask), ptr(self.ring), ptr(self.head_flags), self.s,
                                    self.t_obs, ctypes.c_double(self.scale), self.v, *rule, *map(ptr, outs[:n_out]),
@@ -391,11 +464,12 @@ class _LivePredictor:
         return self._pred.zones
 
     @torch.no_grad()
-    def push(self, *det, seed=None, noise=None):
+    def push(self, *det, seed=None, noise=None, **when):
         """One push, run eagerly: `det` as the class describes it.  seed (by keyword): the sampler's Philox seed from
         now on (None keeps the last one); noise (K,N,P,V,2) standard normals instead of the Philox stream, N = 1 or
-        the number of streams.  The outputs are fresh tensors: earlier results stay."""
-        self._stage(*det, seed)
+        the number of streams.  when: the push's time(s) under time=, by the class's keyword.  The outputs are fresh
+        tensors: earlier results stay."""
+        self._stage(*det, seed, **when)
         outs = self._outs()
         self._push(outs)
         if self.rule is not None:
@@ -429,8 +503,8 @@ class _LivePredictor:
         # every buffer the graph reads or writes lives as long as the returned replay
         static = (outs, chain, graph, scored)
 
-        def replay(*det, seed=None):
-            self._stage(*det, seed)
+        def replay(*det, seed=None, **when):
+            self._stage(*det, seed, **when)
             static[2].replay()
             self.score = static[3]
             if self.rule is not None:
@@ -450,16 +524,21 @@ class FramePredictor(_LivePredictor):
     presence bits of the last push's scene slots (from a captured push the graph's static buffer, like `.risk`).
     score: a predict.ScoreSpec -- every push also scores the predictions of the last pred_seq_len pushes against its
     detections (stg_score_push, behind the sampler): `.score` holds the push's ops.Score (leading axis 1; from a captured
-    push the graph's static tensors) and `.score_totals` the running totals on the device."""
+    push the graph's static tensors) and `.score_totals` the running totals on the device.
+    time: a TimeRule -- push(ids, xy, t=TICKS) and the captured replay(ids, xy, t=TICKS) at any rate: the scene is the
+    tracks resampled at t - k * step (stg_track_push_timed; the time is staged into a device int64 next to the count,
+    so one graph serves every push); `.seen` is always set; a time not after the last push's: the empty scene, flag
+    TIME_ORDER, nothing recorded.  Not together with score=."""
 
     def __init__(self, model, k=20, obs_len=8, capacity=1024, max_peds=128, max_detections=1024, decimals=4,
-                 risk=None, keep_samples=True, tracks=None, score=None):
+                 risk=None, keep_samples=True, tracks=None, score=None, time=None):
         super().__init__(model, k, obs_len, capacity, max_peds, max_detections, decimals, risk, keep_samples, tracks,
-                         score)
+                         score, time)
         dev, m = self._track_state(), self.m_max
         self.det_id = torch.zeros(m, device=dev, dtype=torch.int64)
         self.det_xy = torch.zeros((m, 2), device=dev, dtype=torch.float64)
         self.det_count = torch.zeros(1, device=dev, dtype=torch.int32)
+        self.det_time = torch.zeros(1, device=dev, dtype=torch.int64)
         self.seed_dev = torch.zeros(1, device=dev, dtype=torch.int64)
         self._det = dict(det_id=ptr(self.det_id), det_xy=ptr(self.det_xy), det_count=ptr(self.det_count))
         self.reset()
@@ -468,13 +547,21 @@ class FramePredictor(_LivePredictor):
         """Forget every track (the next obs_len - 1 pushes return empty scenes), and with score= the pending records
         and the running totals."""
         self.slot_id.fill_(-1)
-        self.mask.zero_()
-        self.head_flags.zero_()
+        for x in self._forget:
+            x.zero_()
         if self._score_state is not None:
             ops.score_reset(self._score_state)
 
-    def _stage(self, ids, xy, seed):
-        """Copy one frame of detections (host arrays or device tensors) into the device buffers the push reads."""
+    def _stage(self, ids, xy, seed, t=None):
+        """Copy one frame of detections (host arrays or device tensors) into the device buffers the push reads, and
+        with time= the push's time t."""
+        if self.time is None:
+            if t is not None:
+                raise ValueError("push: t= needs a predictor made with time=TimeRule(...)")
+        elif t is None:
+            raise ValueError("push: a predictor made with time= needs the push's time, t=TICKS")
+        else:
+            t = _tick_time(t, "push")
         if torch.is_tensor(ids) and ids.is_cuda:
             m = ids.numel()
             if m > self.m_max:
@@ -490,6 +577,8 @@ class FramePredictor(_LivePredictor):
                 self.det_id[:m].copy_(torch.from_numpy(ids_np))
                 self.det_xy[:m].copy_(torch.from_numpy(xy_np))
         self.det_count.fill_(m)
+        if t is not None:
+            self.det_time.fill_(t)
         if seed is not None:
             self.seed_dev.fill_(seed_i64(seed))
 
@@ -500,7 +589,8 @@ class FramePredictor(_LivePredictor):
                 torch.empty(1, device=dev, dtype=torch.int32)) + self._seen_out(v)
 
     def _push(self, outs):
-        self._launch_push("stg_track_push", (*self._det.values(), self.m_max), outs, 3)
+        when = () if self.time is None else (ptr(self.det_time),)
+        self._launch_push("stg_track_push", (*self._det.values(), *when, self.m_max), outs, 3)
 
     def _wrap(self, outs, r, static):
         obs, ids, peds = outs[:3]
@@ -509,8 +599,9 @@ class FramePredictor(_LivePredictor):
                                flags if static else flags.clone())
 
     def _still(self):
-        """The warm-up pushes frames without detections, which age the tracks: the state goes back after it."""
-        state = (self.slot_id, self.mask, self.ring, self.head_flags, self.det_count)
+        """The warm-up pushes frames without detections, which age the tracks (with time=: move the clock): the state
+        goes back after it."""
+        state = self._state + (self.det_count,)
         if self._score_state is not None:                    # an empty push is a push: it scores and enqueues
             state += tuple(x for x in self._score_state if x is not None)
         saved = [(x, x.clone()) for x in state]
@@ -622,12 +713,18 @@ class StreamsPredictor(_LivePredictor):
     (stg_score_push_streams, one workgroup per stream): `.score` is the tick's ops.Score with the streams leading, all
     zero for a stream not pushed, `.score_totals` the per-stream totals.  With best_of_k the records keep every push's
     samples for pred_seq_len pushes: about 3.5 MB per stream at 12 steps, 128 pedestrians and k = 20, so 600 streams
-    hold about 2.1 GB (0.4 MB per stream with ScoreSpec(best_of_k=False))."""
+    hold about 2.1 GB (0.4 MB per stream with ScoreSpec(best_of_k=False)).
+    time: a TimeRule for every stream, each with its own clock (stg_track_push_streams_timed): push(tick, times=...)
+    with times a length-NS sequence or a {stream: t} mapping that covers every pushed stream -- staged in the same ONE
+    copy, the staging header extended by NS int64 --, or with a DeviceTick a device int64 (NS) tensor.  The sample
+    rings are capacity * history * 24 bytes per stream (2.4 MB at the defaults): size capacity and history to the feed.
+    Not together with score=."""
 
     def __init__(self, model, streams, k=20, obs_len=8, capacity=1024, max_peds=128, max_detections=1024, decimals=4,
-                 max_total_detections=None, block_threads=0, risk=None, keep_samples=True, tracks=None, score=None):
+                 max_total_detections=None, block_threads=0, risk=None, keep_samples=True, tracks=None, score=None,
+                 time=None):
         super().__init__(model, k, obs_len, capacity, max_peds, max_detections, decimals, risk, keep_samples, tracks,
-                         score)
+                         score, time)
         if not _is_int(streams, 1, MAX_STREAMS):
             raise ValueError("streams must be an integer in [1, %d], got %r" % (MAX_STREAMS, streams))
         self.ns = int(streams)
@@ -646,21 +743,25 @@ class StreamsPredictor(_LivePredictor):
         dev = self._track_state((ns,))
         # staging, the same byte layout on the host (pinned) and on the device: det_start (NS+1) int32 | pushed (NS)
         # int32 | seed int64 | cap records (id int64, x, y float64).  A tick copies the header and its M records.
+        # With time= the header also holds the streams' push times, (NS) int64 behind the seed.
         o_pushed = 4 * (ns + 1)
         o_seed = (4 * (2 * ns + 1) + 7) // 8 * 8
-        self._hdr = o_seed + 8
+        self._hdr = o_seed + 8 + (0 if self.time is None else 8 * ns)
         nbytes = self._hdr + 24 * self.cap
         self._host = torch.zeros(nbytes, dtype=torch.uint8, pin_memory=True)
         self._dev = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
         hb = self._host.numpy()
         self._h_start = hb[:o_pushed].view(np.int32)
         self._h_pushed = hb[o_pushed:o_pushed + 4 * ns].view(np.int32)
-        self._h_seed = hb[o_seed:self._hdr].view(np.int64)
+        self._h_seed = hb[o_seed:o_seed + 8].view(np.int64)
         self._h_rec_i = hb[self._hdr:].view(np.int64).reshape(self.cap, 3)
         self._h_rec_f = hb[self._hdr:].view(np.float64).reshape(self.cap, 3)
         self.det_start = self._dev[:o_pushed].view(torch.int32)
         self.pushed_dev = self._dev[o_pushed:o_pushed + 4 * ns].view(torch.int32)
-        self.seed_dev = self._dev[o_seed:self._hdr].view(torch.int64)
+        self.seed_dev = self._dev[o_seed:o_seed + 8].view(torch.int64)
+        if self.time is not None:
+            self._h_times = hb[o_seed + 8:self._hdr].view(np.int64)
+            self.times_dev = self._dev[o_seed + 8:self._hdr].view(torch.int64)
         self._rec_i = self._dev[self._hdr:].view(torch.int64).view(self.cap, 3)
         self._rec_f = self._dev[self._hdr:].view(torch.float64).view(self.cap, 3)
         # a record is (id, x, y): ids at stride 3 from its start, positions at stride 3 from 8 bytes in
@@ -676,9 +777,8 @@ class StreamsPredictor(_LivePredictor):
         cleared with them."""
         if streams is None:
             self.slot_id.fill_(-1)
-            self.mask.zero_()
-            self.ring.zero_()
-            self.head_flags.zero_()
+            for x in self._state[1:]:
+                x.zero_()
             if self._score_state is not None:
                 ops.score_reset(self._score_state)
             return
@@ -690,9 +790,8 @@ class StreamsPredictor(_LivePredictor):
             return
         at = torch.tensor(idx, dtype=torch.int64).to(self.device)
         self.slot_id.index_fill_(0, at, -1)
-        self.mask.index_fill_(0, at, 0)
-        self.ring.index_fill_(0, at, 0.0)
-        self.head_flags.index_fill_(0, at, 0)
+        for x in self._state[1:]:
+            x.index_fill_(0, at, 0)
         if self._score_state is not None:
             ops.score_reset(self._score_state, at)
 
@@ -707,13 +806,47 @@ class StreamsPredictor(_LivePredictor):
         self._copied.record()
         self._in_flight = True
 
-    def _stage(self, tick, seed):
+    def _host_times(self, times, pushed):
+        """times (a length-NS sequence, None where a stream has none, or a {stream: t} mapping) -> (NS,) int64 with a
+        time for every stream of `pushed`; refuses before anything is written."""
+        if not isinstance(times, collections.abc.Mapping) and not torch.is_tensor(times):
+            # a full sequence of plain integers, the case of a tick of many streams: no Python loop over the streams
+            arr = times if type(times) is np.ndarray else np.asarray(times)
+            if arr.dtype.kind == "i" and arr.shape == (self.ns,) and bool(((arr >= -(1 << 62)) & (arr < 1 << 62)).all()):
+                return arr.astype(np.int64, copy=False)
+        out = np.zeros(self.ns, np.int64)
+        have = np.zeros(self.ns, bool)
+        if isinstance(times, collections.abc.Mapping):
+            entries = list(times.items())
+        else:
+            entries = list(enumerate(np.asarray(times.cpu()).tolist() if torch.is_tensor(times) else times))
+            if len(entries) != self.ns:
+                raise ValueError("times: %d entries for %d streams" % (len(entries), self.ns))
+        for key, t in entries:
+            if isinstance(key, (bool, np.bool_)) or not isinstance(key, (int, np.integer)) or not 0 <= key < self.ns:
+                raise ValueError("times: stream index %r not in [0, %d)" % (key, self.ns))
+            if t is not None:
+                out[key], have[key] = _tick_time(t, "times: stream %d" % key), True
+        missing = np.nonzero((np.asarray(pushed) != 0) & ~have)[0]
+        if len(missing):
+            raise ValueError("times: stream %d is pushed without a time" % missing[0])
+        return out
+
+    def _stage(self, tick, seed, times=None):
         """One tick into the device staging buffer: host detections with ONE copy, device detections by device ops."""
+        if self.time is None and times is not None:
+            raise ValueError("push: times= needs a predictor made with time=TimeRule(...)")
+        if self.time is not None and times is None:
+            raise ValueError("push: a predictor made with time= needs the streams' push times, times=...")
         if isinstance(tick, DeviceTick):
-            return self._stage_device(tick, seed)
+            return self._stage_device(tick, seed, times)
         pk = pack_tick(tick, self.ns, self.m_max, self.cap)           # refuses before anything is written or copied
         m = len(pk.ids)
+        if times is not None:
+            times = self._host_times(times, pk.pushed)
         self._wait_host()
+        if times is not None:
+            self._h_times[:] = times
         self._h_start[:] = pk.det_start
         self._h_pushed[:] = pk.pushed
         if seed is not None:
@@ -723,8 +856,11 @@ class StreamsPredictor(_LivePredictor):
             self._h_rec_f[:m, 1:] = pk.xy
         self._copy(self._hdr + 24 * m)
 
-    def _stage_device(self, tick, seed):
+    def _stage_device(self, tick, seed, times=None):
         ids, xy, counts = tick
+        if times is not None and not (torch.is_tensor(times) and times.is_cuda and times.dtype == torch.int64
+                                      and times.numel() == self.ns):
+            raise ValueError("DeviceTick: times must be a device int64 (%d) tensor" % self.ns)
         if not (torch.is_tensor(ids) and ids.is_cuda and torch.is_tensor(xy) and xy.is_cuda):
             raise ValueError("DeviceTick: ids and xy must be device tensors")
         m = ids.numel()
@@ -756,6 +892,8 @@ class StreamsPredictor(_LivePredictor):
             self._h_start[0] = 0
             self._h_start[1:] = np.minimum(np.cumsum(np.maximum(counts.astype(np.int64), 0)), m)
             self._copy(self._hdr)
+        if times is not None:                                # behind the header copy, which carries stale host times
+            self.times_dev.copy_(times.reshape(-1))
         if m:
             self._rec_i[:m, 0].copy_(ids.reshape(-1))
             self._rec_f[:m, 1:].copy_(xy)
@@ -768,7 +906,8 @@ class StreamsPredictor(_LivePredictor):
                 torch.empty(ns, device=dev, dtype=torch.bool)) + self._seen_out(ns, v)
 
     def _push(self, outs):
-        self._launch_push("stg_track_push_streams", (*self._det.values(), self.ns, self.m_max), outs, 4,
+        when = () if self.time is None else (ptr(self.times_dev),)
+        self._launch_push("stg_track_push_streams", (*self._det.values(), *when, self.ns, self.m_max), outs, 4,
                           self.block_threads)
         torch.ne(self.pushed_dev, 0, out=outs[4])
 

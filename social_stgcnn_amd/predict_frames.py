@@ -4,6 +4,7 @@ trajectories for every pedestrian tracked over the last obs_seq_len frames.
     python -m social_stgcnn_amd.predict_frames --checkpoint DIR --recording FILE [--ksteps 20] [--seed 0]
                                                [--min_peds 1] [--delim tab] [--radius R]
                                                [--zones x0,y0,x1,y1 ...] [--min_seen M] [--max_gap G]
+                                               [--step TICKS [--max_dt D] [--history R] [--max_peds V]]
                                                --out preds.npz
 
 DIR is a checkpoint directory in the reference's layout (args.pkl and val_best.pth, as social_stgcnn_amd.test reads
@@ -18,6 +19,15 @@ risk_zone_count (N,P,Z), risk_ped_zone (N,V,Z) for zones.
 obs_seq_len / 0): a pedestrian seen now, in at least M of the last obs_seq_len frames and with no run of more than G
 missed frames between two seen ones; the missed frames are filled.  The .npz then also holds seen (N,V) int32: bit t set
 = observed t frames ago, so a caller can tell a filled history from an observed one.
+
+--step TICKS takes the frame column for the TIME of a detection, in integer ticks, and TICKS for the model's step (10 for
+the ETH/UCY recordings; frames.TimeRule, with --max_dt and --history): the recording may then come at the tracker's own
+rate, with jitter and dropped frames.  Every distinct frame number is one push of a captured frames.FramePredictor, which
+predicts from the tracks resampled at t - k * TICKS; the .npz holds one entry per push with at least --min_peds
+pedestrians, padded to the largest scene (at most --max_peds, default 128: the smallest ids), and besides the arrays
+above `seen` and `time` (N,) int64, the pushes' times (`frame` holds the same numbers as float64).  The sampler's seed is
+--seed + the push's index.  Not together with --radius / --zones.  Where a recording skips a frame number the two rules
+differ: the frame-index rule makes neighbours of frames 20 ticks apart, the timed rule sees a gap.
 """
 import argparse
 import os
@@ -27,7 +37,7 @@ import numpy as np
 import torch
 
 from . import data
-from .frames import TrackRule, predict_recording
+from .frames import FramePredictor, TimeRule, TrackRule, predict_recording, sorted_rows
 from .model import social_stgcnn
 from .predict import RiskSpec
 from .trainer import load_checkpoint, load_pickle
@@ -49,6 +59,13 @@ def build_parser():
                    help="predict a pedestrian seen in at least this many of the last obs_seq_len frames (seen array)")
     p.add_argument("--max_gap", type=int, default=None,
                    help="... with at most this many missed frames in a row between two seen ones (seen array)")
+    p.add_argument("--step", type=int, default=None,
+                   help="the model's step in ticks of the frame column: predict at every frame number, from the tracks "
+                        "resampled in time (seen and time arrays)")
+    p.add_argument("--max_dt", type=int, default=None, help="with --step: interpolate between samples at most this many "
+                                                            "ticks apart (default: the step)")
+    p.add_argument("--history", type=int, default=96, help="with --step: samples kept per track")
+    p.add_argument("--max_peds", type=int, default=128, help="with --step: the widest scene (the smallest ids are kept)")
     p.add_argument("--out", required=True, help="output .npz")
     # a rectangle may begin with a negative coordinate: "-1,-1,1,1" is a value, not an option
     p._negative_number_matcher = re.compile(r"^-[0-9.][0-9.,eE+-]*$")
@@ -74,6 +91,38 @@ def load_model(exp_path, device):
     return model.to(device).eval()
 
 
+def predict_timed(model, rows, time, k=20, seed=0, min_peds=1, tracks=None, max_peds=128):
+    """Every distinct frame number of `rows`, taken as a time in ticks, pushed through ONE captured timed
+    FramePredictor -> a dict of host arrays, one entry per push whose scene holds at least min_peds pedestrians."""
+    frames, fs, ids, xy = sorted_rows(rows)
+    if np.any(frames != np.round(frames)):
+        raise ValueError("--step: the frame column must hold integer ticks")
+    ticks = frames.astype(np.int64)
+    m_max = max(1, int(np.diff(fs).max()) if len(frames) else 1)
+    fp = FramePredictor(model, k=k, obs_len=model.seq_len, max_peds=max_peds, max_detections=m_max, tracks=tracks,
+                        time=time)
+    replay = fp.capture()
+    keep = {name: [] for name in ("time", "ids", "num_peds", "mean", "samples", "seen")}
+    for f, t in enumerate(ticks.tolist()):
+        out = replay(ids[fs[f]:fs[f + 1]], xy[fs[f]:fs[f + 1]], t=t, seed=seed + f)
+        n = int(out.num_peds.item())
+        if n < min_peds:
+            continue
+        for name, x in (("time", np.int64(t)), ("ids", out.ids), ("num_peds", np.int32(n)), ("mean", out.mean),
+                        ("samples", out.samples), ("seen", fp.seen)):
+            keep[name].append(x.cpu().numpy() if torch.is_tensor(x) else x)
+    v = max(1, max(keep["num_peds"], default=0))
+    p = model.pred_seq_len
+    empty = dict(time=np.zeros(0, np.int64), ids=np.zeros((0, v), np.int64), num_peds=np.zeros(0, np.int32),
+                 mean=np.zeros((0, p, v, 2), np.float32), samples=np.zeros((0, fp.k, p, v, 2), np.float32),
+                 seen=np.zeros((0, v), np.int32))
+    res = {name: np.stack(x) if x else empty[name] for name, x in keep.items()}
+    res.update(ids=res["ids"][:, :v], seen=res["seen"][:, :v], mean=res["mean"][:, :, :v],
+               samples=np.ascontiguousarray(np.moveaxis(res["samples"], 0, 1)[:, :, :, :v]))
+    res["frame"] = res["time"].astype(np.float64)
+    return res
+
+
 def main(argv=None):
     a = build_parser().parse_args(argv)
     if not torch.cuda.is_available():
@@ -84,6 +133,14 @@ def main(argv=None):
     tracks = None
     if a.min_seen is not None or a.max_gap is not None:
         tracks = TrackRule(model.seq_len if a.min_seen is None else a.min_seen, 0 if a.max_gap is None else a.max_gap)
+    if a.step is not None:
+        if a.radius is not None or a.zones is not None:
+            raise ValueError("--step does not go together with --radius / --zones")
+        res = predict_timed(model, rows, TimeRule(a.step, a.max_dt, a.history), a.ksteps, a.seed, a.min_peds, tracks,
+                            a.max_peds)
+        np.savez(a.out, **res)
+        print("%d pushes with a scene, up to %d pedestrians -> %s" % (len(res["time"]), res["ids"].shape[1], a.out))
+        return
     if a.radius is None and a.zones is None:
         scenes, pred = predict_recording(model, rows, k=a.ksteps, seed=a.seed, min_peds=a.min_peds, tracks=tracks)
     else:

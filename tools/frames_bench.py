@@ -6,6 +6,10 @@
                                  [--risk none,samples,lean]
     python tools/frames_bench.py --cases score [--streams 1,64,600] [--ticks 200]
     python tools/frames_bench.py --tracks 2,2 ...       every case under frames.TrackRule(2, 2) (the *_rule kernels)
+    python tools/frames_bench.py --time 10,10 ...       the latency and streams cases on timestamped pushes
+                                                        (frames.TimeRule(10, history=--history), stg_track_push_timed):
+                                                        a model step is 10 ticks and the feed is upsampled 10x by linear
+                                                        interpolation, one push per tick (--time STEP: not upsampled)
 
   latency    the captured FramePredictor (ONE graph: stg_track_push -> observed_inputs -> forward -> sampler) pushed
              every frame of a recording in a loop, --pushes timed pushes after a warm-up.  Host clock around staging +
@@ -66,24 +70,49 @@ def pushes_of(rows):
             for a, b in zip(bounds[:-1], bounds[1:])]
 
 
-def tracks_kw(tracks):
-    """--tracks M,G -> the keyword of the predictors (nothing without the flag: the strict calls)."""
+def tracks_kw(tracks, timed=None):
+    """--tracks M,G and --time STEP,UP -> the keywords of the predictors (nothing without the flags: the strict calls)."""
     from social_stgcnn_amd import frames
-    return {} if tracks is None else {"tracks": frames.TrackRule(*tracks)}
+    kw = {} if tracks is None else {"tracks": frames.TrackRule(*tracks)}
+    if timed is not None:
+        kw["time"] = frames.TimeRule(timed[0], history=timed[2])
+    return kw
 
 
-def latency_case(split, rec, max_peds, k, n_push, dev, warmup=50, tracks=None):
+def timed_pushes(rows, step, up):
+    """The recording as timestamped pushes [(ids, xy, t)]: a frame number f (the recordings count 10 per model step)
+    is the time f / 10 * step ticks; between two frames 10 apart every pedestrian of both is interpolated linearly at
+    up - 1 instants, step / up ticks apart."""
+    if step % up:
+        raise SystemExit("--time STEP,UP: STEP must be a multiple of UP")
+    fnum = np.unique(rows[:, 0])
+    base = pushes_of(rows)
+    out = []
+    for f, (ids, xy) in enumerate(base):
+        t0 = int(round(fnum[f] / 10 * step))
+        out.append((ids, xy, t0))
+        if up > 1 and f + 1 < len(base) and fnum[f + 1] - fnum[f] == 10:
+            nxt = dict(zip(base[f + 1][0].tolist(), base[f + 1][1]))
+            both = [j for j, i in enumerate(ids.tolist()) if i in nxt]
+            a, b = xy[both], np.array([nxt[int(ids[j])] for j in both]).reshape(-1, 2)
+            out += [(ids[both], a + (b - a) * (j / up), t0 + j * (step // up)) for j in range(1, up)]
+    return out
+
+
+def latency_case(split, rec, max_peds, k, n_push, dev, warmup=50, tracks=None, timed=None):
     from social_stgcnn_amd import data, frames
-    pushes = pushes_of(data.read_file(os.path.join(DATA, rec)))
-    fp = frames.FramePredictor(model_for(split, dev), k=k, max_peds=max_peds, **tracks_kw(tracks))
+    rows = data.read_file(os.path.join(DATA, rec))
+    pushes = pushes_of(rows) if timed is None else timed_pushes(rows, *timed[:2])
+    fp = frames.FramePredictor(model_for(split, dev), k=k, max_peds=max_peds, **tracks_kw(tracks, timed))
     push = fp.capture()
     times, peds = [], []
     for i in range(warmup + n_push):
-        ids, xy = pushes[i % len(pushes)]
+        ids, xy = pushes[i % len(pushes)][:2]
+        when = {} if timed is None else {"t": pushes[i % len(pushes)][2]}
         if i % len(pushes) == 0:
             fp.reset()
         t0 = time.perf_counter()
-        out = push(ids, xy)
+        out = push(ids, xy, **when)
         torch.cuda.synchronize()
         if i >= warmup:
             times.append(time.perf_counter() - t0)
@@ -94,7 +123,7 @@ def latency_case(split, rec, max_peds, k, n_push, dev, warmup=50, tracks=None):
             "p50_ms": round(float(np.percentile(ms, 50)), 4), "p90_ms": round(float(np.percentile(ms, 90)), 4),
             "mean_ms": round(float(ms.mean()), 4), "frames_per_s_p50": round(1e3 / float(np.percentile(ms, 50)), 1),
             "mean_peds": round(float(peds.mean()), 2), "max_peds_seen": int(peds.max()),
-            **({} if tracks is None else {"tracks": list(tracks)})}
+            **({} if tracks is None else {"tracks": list(tracks)}), **({} if timed is None else {"time": list(timed)})}
 
 
 def recording_case(split, rec, k, dev, tracks=None):
@@ -114,10 +143,13 @@ def recording_case(split, rec, k, dev, tracks=None):
             **({} if tracks is None else {"tracks": list(tracks)})}
 
 
-def _stream_sequences(ns, n):
-    """Per stream the first n pushes of a test recording (cycled over the streams), from a staggered start."""
+def _stream_sequences(ns, n, timed=None):
+    """Per stream the first n pushes of a test recording (cycled over the streams), from a staggered start; with
+    `timed` the timestamped pushes (a stream's times wrap with its recording: its tracks then start over, as its
+    clock does with reset)."""
     from social_stgcnn_amd import data
-    recs = [pushes_of(data.read_file(os.path.join(DATA, rec))) for _, rec in TEST_RECORDINGS]
+    recs = [data.read_file(os.path.join(DATA, rec)) for _, rec in TEST_RECORDINGS]
+    recs = [pushes_of(r) if timed is None else timed_pushes(r, *timed[:2]) for r in recs]
     out = []
     for s in range(ns):
         p = recs[s % len(recs)]
@@ -127,23 +159,27 @@ def _stream_sequences(ns, n):
 
 
 def streams_case(ns, k, n_ticks, dev, block=0, lone=True, max_peds=128, warmup=20, risk="none", tracks=None,
-                 score=None):
+                 score=None, timed=None):
     from social_stgcnn_amd import frames
     model = model_for("univ", dev)
-    seq = _stream_sequences(ns, warmup + n_ticks)
+    seq = _stream_sequences(ns, warmup + n_ticks, timed)
+    # a recording that wraps inside the run would push a time that is not after the last: keep the run inside it
+    if timed is not None and any(q[t + 1][2] <= q[t][2] for q in seq for t in range(len(q) - 1)):
+        raise SystemExit("--time: %d ticks wrap a recording; use fewer --ticks" % (warmup + n_ticks))
     kw = {} if score is None else {"score": score}
     if risk != "none":
         from social_stgcnn_amd.predict import RiskSpec
         kw = dict(risk=RiskSpec(0.5, np.array([[-1, -1, 1, 1], [0, 0, 4, 3], [-50, -50, 50, 50]], np.float32)),
                   keep_samples=risk == "samples")
-    kw.update(tracks_kw(tracks))
+    kw.update(tracks_kw(tracks, timed))
     sp = frames.StreamsPredictor(model, ns, k=k, max_peds=max_peds, block_threads=block, **kw)
     replay = sp.capture()
     times, peds = [], []
     for t in range(warmup + n_ticks):
-        tick = [q[t] for q in seq]
+        tick = [q[t][:2] for q in seq]
+        when = {} if timed is None else {"times": [q[t][2] for q in seq]}
         t0 = time.perf_counter()
-        out = replay(tick)
+        out = replay(tick, **when)
         torch.cuda.synchronize()
         if t >= warmup:
             times.append(time.perf_counter() - t0)
@@ -157,6 +193,9 @@ def streams_case(ns, k, n_ticks, dev, block=0, lone=True, max_peds=128, warmup=2
            "max_peds_seen": int(peds.max())}
     if tracks is not None:
         res["tracks"] = list(tracks)
+    if timed is not None:
+        res["time"] = list(timed)
+        res["state_mb_per_stream"] = round(sum(x[0].numel() * x.element_size() for x in sp._state) / 1e6, 3)
     if risk != "none":
         res["risk"] = risk
         res["conflict_any_mean"] = round(float(sp.risk.conflict_any.float().mean()), 3)
@@ -173,15 +212,16 @@ def streams_case(ns, k, n_ticks, dev, block=0, lone=True, max_peds=128, warmup=2
     if lone:
         # the yardstick: NS lone captured FramePredictors, one after another; fewer ticks at large NS
         n_seq = max(10, min(n_ticks, 4000 // ns))
-        fps = [frames.FramePredictor(model, k=k, max_peds=max_peds, **tracks_kw(tracks)) for _ in range(ns)]
+        fps = [frames.FramePredictor(model, k=k, max_peds=max_peds, **tracks_kw(tracks, timed)) for _ in range(ns)]
         pushes = [fp.capture() for fp in fps]
         times = []
         for t in range(warmup + n_seq):
             tot = 0.0
             for s in range(ns):
-                ids, xy = seq[s][t]
+                ids, xy = seq[s][t][:2]
+                when = {} if timed is None else {"t": seq[s][t][2]}
                 t0 = time.perf_counter()
-                pushes[s](ids, xy)
+                pushes[s](ids, xy, **when)
                 torch.cuda.synchronize()
                 tot += time.perf_counter() - t0
             if t >= warmup:
@@ -207,8 +247,16 @@ def main():
     ap.add_argument("--risk", default="none", help="modes of the streams case, comma separated: none, samples, lean")
     ap.add_argument("--tracks", default=None, metavar="M,G",
                     help="run every case under frames.TrackRule(min_seen=M, max_gap=G); default: the strict rule")
+    ap.add_argument("--time", default=None, metavar="STEP[,UP]",
+                    help="timestamped pushes (frames.TimeRule(STEP)) on the feed upsampled UP x (default 1) by linear "
+                         "interpolation: the latency and streams cases")
+    ap.add_argument("--history", type=int, default=96, help="with --time: samples kept per track")
     a = ap.parse_args()
     tracks = None if a.tracks is None else tuple(int(x) for x in a.tracks.split(","))
+    timed = None
+    if a.time is not None:
+        timed = tuple(int(x) for x in a.time.split(","))
+        timed = (timed[0], timed[1] if len(timed) > 1 else 1, a.history)
     if not torch.cuda.is_available():
         raise SystemExit("frames_bench needs a GPU (MI355X)")
     dev = torch.device("cuda", 0)
@@ -216,7 +264,8 @@ def main():
     if "latency" in cases:
         for split, rec, v in (("eth", "eth_test/biwi_eth.txt", 32), ("eth", "eth_test/biwi_eth.txt", 128),
                               ("univ", "univ_test/students001.txt", 128)):
-            print(json.dumps(latency_case(split, rec, v, a.k, a.pushes, dev, tracks=tracks)), flush=True)
+            print(json.dumps(latency_case(split, rec, v, a.k, a.pushes, dev, tracks=tracks, timed=timed)),
+                  flush=True)
     if "recording" in cases:
         for split, rec in TEST_RECORDINGS:
             print(json.dumps(recording_case(split, rec, a.k, dev, tracks)), flush=True)
@@ -234,7 +283,7 @@ def main():
             for ns in (int(n) for n in a.streams.split(",")):
                 for mode in a.risk.split(","):
                     print(json.dumps(streams_case(ns, a.k, a.ticks, dev, block, not a.no_lone, risk=mode,
-                                                  tracks=tracks)),
+                                                  tracks=tracks, timed=timed)),
                           flush=True)
 
 
