@@ -560,6 +560,51 @@ int stg_score_push_streams(const int64_t *det_id, int64_t id_stride, const doubl
                            const int32_t *num_peds, int P, int V, int K, const stg_score_state *state,
                            const float *thr, int Q, const stg_score_out *out, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * N9  unlabelled detections -> track ids, the front end of the live pushes (added entry points, the ABI
+ *     version stays).  A per-stream tracker with constant-velocity prediction and gated, globally greedy
+ *     nearest-neighbour matching; exact and deterministic.
+ *   State (all DEVICE memory; zeros and trk_id = -1 start a stream): C track slots -- trk_id int64[C] (-1 = free),
+ *     trk_pos float64 (C,2) the last matched rounded position, trk_vel float64 (C,2) displacement per push, trk_miss
+ *     int32[C] pushes since the last match, trk_hits int32[C] matches so far (>= 1 for a live track) --, next_id
+ *     int64[1] and assoc_flags int32[1], the STG_ASSOC_* flags of the last push.
+ *   One push with m = min(count, M_max) detections at p_j = round(xy_j) (the rounding of N6, scale), float64 with one
+ *   IEEE operation at a time (no fused multiply-add):
+ *     1. every live slot s predicts q_s = pos_s + vel_s * (double)(miss_s + 1);
+ *     2. cost(s,j) = dx*dx + dy*dy, dx = q_s.x - p_j.x, dy = q_s.y - p_j.y; the pair is a candidate iff cost <= g2_s,
+ *        g2_s = gate2 when hits_s >= 2 (the track has a velocity), gate_new2 when hits_s == 1;
+ *     3. the candidates are taken in ascending order of (cost, s, j), each accepted when its track and its detection
+ *        are both still free;
+ *     4. a matched pair: id_j = trk_id_s, vel_s = (p_j - pos_s) / (double)(miss_s + 1), pos_s = p_j, miss_s = 0,
+ *        hits_s += 1;
+ *     5. a live slot not matched: miss_s += 1; once miss_s > max_miss the slot is freed (trk_id -1, the rest zero);
+ *     6. the detections not matched, in detection order: the i-th gets id next_id + i and the i-th free slot in slot
+ *        order (the slots freed in 5 included) with pos = p_j, vel = 0, miss = 0, hits = 1; when the free slots run
+ *        out the others still get their ids, no slot, and STG_ASSOC_FULL is set; next_id advances by their number.
+ *   The ids are written to det_id[j * id_stride], j < m: the array the push and score launches behind it read.
+ *   Detections past M_max are not touched (the push drops them, STG_TRACK_TRUNCATED).  Ids are >= 0 and distinct within
+ *   a push.  gate2 and gate_new2 are the SQUARED gates: finite, gate2 > 0, gate_new2 >= gate2; max_miss >= 0.
+ *   stg_associate: one workgroup; det_xy float64 (M_max,2), det_count int32[1], det_id int64[M_max].
+ *   stg_associate_streams: one workgroup per stream on the (NS, ...) slices of the state, det_id / det_xy with strides,
+ *     M_total, det_start and pushed as stg_track_push_streams reads them; a stream not pushed keeps its state bit for
+ *     bit and its ids are not written.
+ *   LDS: 28 bytes per track slot and 20 per detection, 98,304 bytes at both limits.  Sizes above STG_ASSOC_MAX_*:
+ *   STG_EUNSUPPORTED; bad sizes, gates, max_miss or NULL pointers: STG_EINVAL; both decided before any launch.  Every
+ *   count, range and state word is read when the kernel runs, so one captured graph serves every push.  No host
+ *   synchronisation.                                                                                                 */
+#define STG_ASSOC_MAX_SLOTS STG_TRACK_MAX_SLOTS
+#define STG_ASSOC_MAX_DETECTIONS STG_TRACK_MAX_DETECTIONS
+#define STG_ASSOC_FULL 1 /* no free slot for a new track (the detection has its fresh id, nothing is remembered) */
+int stg_associate(int64_t *det_id, const double *det_xy, const int32_t *det_count, int M_max, int64_t *trk_id,
+                  double *trk_pos, double *trk_vel, int32_t *trk_miss, int32_t *trk_hits, int64_t *next_id,
+                  int32_t *assoc_flags, int C, double scale, double gate2, double gate_new2, int max_miss,
+                  void *stream);
+int stg_associate_streams(int64_t *det_id, int64_t id_stride, const double *det_xy, int64_t xy_stride, int M_total,
+                          const int32_t *det_start, const int32_t *pushed, int NS, int M_max, int64_t *trk_id,
+                          double *trk_pos, double *trk_vel, int32_t *trk_miss, int32_t *trk_hits, int64_t *next_id,
+                          int32_t *assoc_flags, int C, double scale, double gate2, double gate_new2, int max_miss,
+                          void *stream);
+
 /* Self-test helper: C(16x16) = A(16xK) * B(Kx16) through v_mfma_f32_16x16x4_f32 with the operand
  * maps the TXP-CNN kernels rely on (K multiple of 4).                                           */
 int stg_selftest_mfma(const float *a, const float *b, int K, float *c, void *stream);

@@ -113,6 +113,10 @@ _SIGNATURES = {
     "stg_score_push_streams": (c_i, [c_f, c_l, c_f, c_l, c_i, c_f, c_f, c_i, c_i, ctypes.c_double, c_f, c_f, c_l, c_l,
                                      c_l, c_l, c_f, c_f, c_f, c_i, c_i, c_i, ctypes.POINTER(ScoreState), c_f, c_i,
                                      ctypes.POINTER(ScoreOut), c_f]),
+    "stg_associate": (c_i, [c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, ctypes.c_double,
+                            ctypes.c_double, ctypes.c_double, c_i, c_f]),
+    "stg_associate_streams": (c_i, [c_f, c_l, c_f, c_l, c_i, c_f, c_f, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f,
+                                    c_i, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_i, c_f]),
     "stg_selftest_mfma": (c_i, [c_f, c_f, c_i, c_f, c_f]),
 }
 EXPORTS = tuple(_SIGNATURES)

@@ -26,6 +26,9 @@ stg_frame_scenes over a recording uploaded once, stg_track_push with the track s
     TimeRule           time=TimeRule(step, max_dt, history) on the two live predictors: pushes carry their time in
                        integer ticks and arrive at the tracker's own rate; every push predicts from the scene "as of
                        now", the tracks resampled at t - k * step on the device (stg_track_push_timed)
+    AssociateSpec      associate=AssociateSpec(gate, gate_new, max_miss) on the two live predictors: pushes carry
+                       positions only, push(None, xy); a launch ahead of the push kernel gives every detection its track
+                       id on the device (stg_associate); `.det_ids`, `.assoc_flags`
 
 The two live predictors are one core, _LivePredictor: the argument checks, the track state, the eager push and its
 capture (the push kernel ahead of predict.Predictor.capture_chain; the capture recipe itself is graphs.py).  Each class
@@ -130,6 +133,41 @@ class TimeRule(collections.namedtuple("TimeRule", "step max_dt history")):
             raise ValueError("TimeRule: max_dt=%d > (obs_len - 1) * step = %d (a track is forgotten by then)"
                              % (max_dt, (obs_len - 1) * self.step))
         return TimeRule(self.step, max_dt, self.history)
+
+
+ASSOC_FULL = 1                         # STG_ASSOC_FULL, the one bit of `.assoc_flags`
+
+
+class AssociateSpec(collections.namedtuple("AssociateSpec", "gate gate_new max_miss capacity")):
+    """Live pushes without identities: a detector gives positions, the device gives them track ids.
+    Per stream a tracker with constant-velocity prediction and gated, globally greedy nearest-neighbour matching: a
+    track predicts pos + vel * (pushes since its last match + 1); a detection within `gate` of that (within gate_new,
+    default 2 * gate, of a track seen once, which has no velocity yet) is a candidate; the candidates are taken nearest
+    first, each track and each detection once.  A track not matched for more than max_miss pushes is forgotten; a
+    detection not matched starts a track with a fresh id (0, 1, ... per stream).  `capacity` track slots (default: the
+    predictor's capacity); past them a new detection still gets its id but is not remembered (flag ASSOC_FULL).  The
+    distances are in the units of the positions, per push."""
+    __slots__ = ()
+
+    def __new__(cls, gate, gate_new=None, max_miss=0, capacity=None):
+        def number(x, what):
+            if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not np.isfinite(x):
+                raise ValueError("AssociateSpec: %s must be a finite number, got %r" % (what, x))
+            return float(x)
+        gate = number(gate, "gate")
+        gate_new = 2.0 * gate if gate_new is None else number(gate_new, "gate_new")
+        if not gate > 0.0:
+            raise ValueError("AssociateSpec: gate must be > 0, got %r" % (gate,))
+        if not gate_new >= gate:
+            raise ValueError("AssociateSpec: gate_new=%r must be >= gate=%r" % (gate_new, gate))
+        if not np.isfinite(gate * gate) or not np.isfinite(gate_new * gate_new) or not gate * gate > 0.0:
+            raise ValueError("AssociateSpec: the squared gates must be finite and > 0, got %r, %r" % (gate, gate_new))
+        if not _is_int(max_miss, 0, (1 << 31) - 2):
+            raise ValueError("AssociateSpec: max_miss must be an integer >= 0, got %r" % (max_miss,))
+        if capacity is not None and not _is_int(capacity, 1, MAX_SLOTS):
+            raise ValueError("AssociateSpec: capacity must be None or an integer in [1, %d], got %r"
+                             % (MAX_SLOTS, capacity))
+        return super().__new__(cls, gate, gate_new, int(max_miss), None if capacity is None else int(capacity))
 
 
 def _tick_time(t, what):
@@ -312,9 +350,13 @@ def predict_recording(model, rows, k=20, seed=0, batch_size=64, noise_fn=None, m
 
 def host_detections(ids, xy, max_detections):
     """One frame of detections given as host arrays -> (ids (M,) int64, xy (M,2) float64), validated: at most
-    max_detections of them, integral ids >= 0, no id twice."""
-    ids_np = np.asarray(ids.cpu() if torch.is_tensor(ids) else ids).reshape(-1)
+    max_detections of them, integral ids >= 0, no id twice.  ids None (a predictor with associate=): (None, xy)."""
     xy_np = np.asarray(xy.cpu() if torch.is_tensor(xy) else xy, dtype=np.float64).reshape(-1, 2)
+    if ids is None:
+        if len(xy_np) > max_detections:
+            raise ValueError("push: %d detections > max_detections=%d" % (len(xy_np), max_detections))
+        return None, np.ascontiguousarray(xy_np)
+    ids_np = np.asarray(ids.cpu() if torch.is_tensor(ids) else ids).reshape(-1)
     m = len(ids_np)
     if m > max_detections:
         raise ValueError("push: %d detections > max_detections=%d" % (m, max_detections))
@@ -338,13 +380,23 @@ class _LivePredictor:
                                  kernel does: _push and the score launch read the same ones
         _wrap(outs, r, static)   the result tuple of outs and the chain's Prediction r (static: a captured push)
         _still()                 make warm-up pushes harmless; returns the (tensor, saved copy) pairs to put back after
+        _associate()             with associate=: launch its association kernel on the staging buffers, ahead of _push
 
     and `seed_dev`, the (1,) int64 device tensor the sampler reads its seed from."""
+    assoc = None                         # the AssociateSpec; None: ids come with the pushes
 
     def __init__(self, model, k, obs_len, capacity, max_peds, max_detections, decimals, risk=None, keep_samples=True,
-                 tracks=None, score=None, time=None):
+                 tracks=None, score=None, time=None, associate=None):
         self.model = model
         self.k = int(k)
+        if associate is not None and time is not None:
+            raise ValueError("associate= together with time= is not supported: a velocity per tick and a gate that "
+                             "grows with the gap are a change of their own (DESIGN.md 8)")
+        if associate is not None and not isinstance(associate, AssociateSpec):
+            associate = AssociateSpec(*associate) if isinstance(associate, (tuple, list)) else AssociateSpec(associate)
+        self.assoc = associate
+        self._assoc_state = None
+        self._n_det = 0
         if time is not None and score is not None:
             raise ValueError("time= together with score= is not supported: the score records are indexed by push, and "
                              "re-indexing them by time is a change of its own (DESIGN.md 8)")
@@ -406,6 +458,22 @@ class _LivePredictor:
             self.clock = torch.empty(lead + (2,), device=dev, dtype=torch.int64)
             self._state = (self.slot_id, self.t_ring, self.xy_ring, self.slot_head, self.clock, self.head_flags)
             self._forget = (self.slot_head, self.clock, self.head_flags)     # (a ring holds what its count says)
+        if self.assoc is not None:
+            # the association state: slot ids, positions, velocities, misses, hits; per stream next_id and the flags
+            c = self.s if self.assoc.capacity is None else self.assoc.capacity
+            one = lead or (1,)
+            self.trk_id = torch.empty(lead + (c,), device=dev, dtype=torch.int64)
+            self.trk_pos = torch.zeros(lead + (c, 2), device=dev, dtype=torch.float64)
+            self.trk_vel = torch.zeros(lead + (c, 2), device=dev, dtype=torch.float64)
+            self.trk_miss = torch.zeros(lead + (c,), device=dev, dtype=torch.int32)
+            self.trk_hits = torch.zeros(lead + (c,), device=dev, dtype=torch.int32)
+            self.next_id = torch.zeros(one, device=dev, dtype=torch.int64)
+            self.assoc_flags = torch.zeros(one, device=dev, dtype=torch.int32)
+            self._assoc_state = (self.trk_id, self.trk_pos, self.trk_vel, self.trk_miss, self.trk_hits, self.next_id,
+                                 self.assoc_flags)
+            # (the gates travel squared, in float64)
+            self._assoc_args = (c, ctypes.c_double(self.scale), ctypes.c_double(self.assoc.gate * self.assoc.gate),
+                                ctypes.c_double(self.assoc.gate_new * self.assoc.gate_new), self.assoc.max_miss)
         self._pred = Predictor(self.model, self.k, *self._risk_args)
         if self.score_spec is not None:
             spec = self.score_spec
@@ -429,6 +497,28 @@ class _LivePredictor:
         return ops.score_push(self._score_state, self._thr, r.mean, r.v_pred,
                               r.samples if self.score_spec.best_of_k else None, outs[1].view(ns, self.v), outs[2],
                               out=out, m_max=self.m_max, scale=self.scale, **self._det)
+
+    def _reset_assoc(self, at=None):
+        """Forget the association's tracks and start its ids at 0 again: everywhere, or at the stream indices `at`."""
+        if self._assoc_state is None:
+            return
+        for x in self._assoc_state:
+            fill = -1 if x is self.trk_id else 0
+            if at is None:
+                x.fill_(fill)
+            else:
+                x.index_fill_(0, at, fill)
+
+    def _launch_associate(self, name, det):
+        """The association kernel `name` on the detections `det` (its leading arguments) and the association state: it
+        writes the ids the push kernel behind it reads."""
+        check(getattr(lib(), name)(*det, *map(ptr, self._assoc_state), *self._assoc_args, stream_ptr()), name)
+
+    def _front(self, outs):
+        """The launches that turn the staged detections into the scene: with associate= the association, then the push."""
+        if self.assoc is not None:
+            self._associate()
+        self._push(outs)
 
     def _launch_push(self, name, det, outs, n_out, *tail):
         """The push kernel `name` on the detections `det` (its leading arguments) and the track state, or under a
@@ -471,7 +561,7 @@ class _LivePredictor:
         tensors: earlier results stay."""
         self._stage(*det, seed, **when)
         outs = self._outs()
-        self._push(outs)
+        self._front(outs)
         if self.rule is not None:
             self.seen = outs[-1]
         with eval_mode(self.model):
@@ -494,7 +584,7 @@ class _LivePredictor:
                                        self.score_spec.best_of_k)
         try:
             graph, r, chain = self._pred.capture_chain(
-                outs[0], outs[2], self.seed_dev, warmup, pre=lambda: self._push(outs),
+                outs[0], outs[2], self.seed_dev, warmup, pre=lambda: self._front(outs),
                 post=None if scored is None else lambda res: self._score_push(outs, res, scored))
         finally:
             for x, x0 in saved:
@@ -513,13 +603,21 @@ class _LivePredictor:
         return replay
 
 
+def _ids_or_associate(ids, assoc, what):
+    """Ids come from the caller, or from associate=: never both, never neither."""
+    if assoc is None and ids is None:
+        raise ValueError("%s: ids=None needs a predictor made with associate=AssociateSpec(...)" % what)
+    if assoc is not None and ids is not None:
+        raise ValueError("%s: a predictor made with associate= assigns the ids itself: pass ids=None" % what)
+
+
 class FramePredictor(_LivePredictor):
     """Live prediction: push(ids, xy) with one frame of detections returns that frame's scene (the pedestrians seen
     in each of the last obs_len pushes, ascending ids, at most max_peds: the smallest) and K sampled trajectories per
     pedestrian, as a FramePrediction.  ids (M,) integral, xy (M,2) positions: host arrays (a repeated id is refused)
     or device tensors (a repeated id: the first detection wins, flag DUPLICATE).  The tracks live on the device
     (stg_track_push): `capacity` slots, a slot freed once its pedestrian has been missing for obs_len - 1 frames.  Ids
-    come from the caller's tracker (association is not done here).  tracks: a TrackRule -- the scene holds the
+    come from the caller's tracker, or with associate= from the device (below).  tracks: a TrackRule -- the scene holds the
     pedestrians that rule admits, their missed frames filled (stg_track_push_rule); `.seen` (V,) int32 then holds the
     presence bits of the last push's scene slots (from a captured push the graph's static buffer, like `.risk`).
     score: a predict.ScoreSpec -- every push also scores the predictions of the last pred_seq_len pushes against its
@@ -528,12 +626,17 @@ class FramePredictor(_LivePredictor):
     time: a TimeRule -- push(ids, xy, t=TICKS) and the captured replay(ids, xy, t=TICKS) at any rate: the scene is the
     tracks resampled at t - k * step (stg_track_push_timed; the time is staged into a device int64 next to the count,
     so one graph serves every push); `.seen` is always set; a time not after the last push's: the empty scene, flag
-    TIME_ORDER, nothing recorded.  Not together with score=."""
+    TIME_ORDER, nothing recorded.  Not together with score=.
+    associate: an AssociateSpec -- pushes carry no ids, push(None, xy) and the captured replay(None, xy): stg_associate,
+    one launch ahead of the push kernel (inside the captured graph), gives every detection its track id in the staging
+    buffer the push and the score read; the returned ids are those track ids, `.det_ids` (M,) the id of every detection
+    of the last push in the caller's order, `.assoc_flags` (1,) int32 the association's flags (ASSOC_FULL).  Ids given
+    with associate=, or None without it, are refused.  Not together with time=."""
 
     def __init__(self, model, k=20, obs_len=8, capacity=1024, max_peds=128, max_detections=1024, decimals=4,
-                 risk=None, keep_samples=True, tracks=None, score=None, time=None):
+                 risk=None, keep_samples=True, tracks=None, score=None, time=None, associate=None):
         super().__init__(model, k, obs_len, capacity, max_peds, max_detections, decimals, risk, keep_samples, tracks,
-                         score, time)
+                         score, time, associate)
         dev, m = self._track_state(), self.m_max
         self.det_id = torch.zeros(m, device=dev, dtype=torch.int64)
         self.det_xy = torch.zeros((m, 2), device=dev, dtype=torch.float64)
@@ -549,8 +652,18 @@ class FramePredictor(_LivePredictor):
         self.slot_id.fill_(-1)
         for x in self._forget:
             x.zero_()
+        self._reset_assoc()
         if self._score_state is not None:
             ops.score_reset(self._score_state)
+
+    @property
+    def det_ids(self):
+        """With associate=: the track id given to every detection of the last push, (M,) int64 on the device in the
+        caller's detection order (a view of the staging buffer, overwritten by the next push)."""
+        return None if self.assoc is None else self.det_id[:self._n_det]
+
+    def _associate(self):
+        self._launch_associate("stg_associate", (ptr(self.det_id), ptr(self.det_xy), ptr(self.det_count), self.m_max))
 
     def _stage(self, ids, xy, seed, t=None):
         """Copy one frame of detections (host arrays or device tensors) into the device buffers the push reads, and
@@ -562,7 +675,16 @@ class FramePredictor(_LivePredictor):
             raise ValueError("push: a predictor made with time= needs the push's time, t=TICKS")
         else:
             t = _tick_time(t, "push")
-        if torch.is_tensor(ids) and ids.is_cuda:
+        if (ids is None) != (self.assoc is not None):
+            _ids_or_associate(ids, self.assoc, "push")
+        if ids is None and torch.is_tensor(xy) and xy.is_cuda:
+            m = xy.shape[0] if xy.dim() == 2 and xy.shape[1] == 2 else -1
+            if m < 0:
+                raise ValueError("push: xy (M,2) tensor expected, got %s" % (tuple(xy.shape),))
+            if m > self.m_max:
+                raise ValueError("push: %d detections > max_detections=%d" % (m, self.m_max))
+            self.det_xy[:m].copy_(xy)
+        elif torch.is_tensor(ids) and ids.is_cuda:
             m = ids.numel()
             if m > self.m_max:
                 raise ValueError("push: %d detections > max_detections=%d" % (m, self.m_max))
@@ -572,10 +694,12 @@ class FramePredictor(_LivePredictor):
             self.det_xy[:m].copy_(xy)
         else:
             ids_np, xy_np = host_detections(ids, xy, self.m_max)
-            m = len(ids_np)
+            m = len(xy_np)
             if m:
-                self.det_id[:m].copy_(torch.from_numpy(ids_np))
+                if ids_np is not None:
+                    self.det_id[:m].copy_(torch.from_numpy(ids_np))
                 self.det_xy[:m].copy_(torch.from_numpy(xy_np))
+        self._n_det = m
         self.det_count.fill_(m)
         if t is not None:
             self.det_time.fill_(t)
@@ -602,6 +726,8 @@ class FramePredictor(_LivePredictor):
         """The warm-up pushes frames without detections, which age the tracks (with time=: move the clock): the state
         goes back after it."""
         state = self._state + (self.det_count,)
+        if self._assoc_state is not None:                    # an empty push ages the association's tracks too
+            state += self._assoc_state
         if self._score_state is not None:                    # an empty push is a push: it scores and enqueues
             state += tuple(x for x in self._score_state if x is not None)
         saved = [(x, x.clone()) for x in state]
@@ -629,11 +755,13 @@ above max_detections uses the first max_detections (flag TRUNCATED); a repeated 
 wins (flag DUPLICATE)."""
 
 
-def pack_tick(tick, streams, max_detections, max_total_detections):
+def pack_tick(tick, streams, max_detections, max_total_detections, associate=False):
     """One tick of host detections -> PackedTick, validated as host_detections validates one push: in every stream at
     most max_detections of them, integral ids >= 0, no id twice; stream indices in [0, streams); at most
     max_total_detections in all.  tick: a mapping {stream index: (ids, xy)} or a length-`streams` sequence of (ids, xy)
-    or None (None: the stream is not pushed this tick; (ids, xy) with no detections is an empty push)."""
+    or None (None: the stream is not pushed this tick; (ids, xy) with no detections is an empty push).
+    associate: the entries are (None, xy) -- the device assigns the ids --, the PackedTick's ids are None and no id is
+    looked at; without it an entry (None, xy) is refused."""
     if isinstance(tick, collections.abc.Mapping):
         entries = []
         for key, det in tick.items():
@@ -654,12 +782,14 @@ def pack_tick(tick, streams, max_detections, max_total_detections):
         if len(det) != 2:
             raise ValueError("tick: stream %d: (ids, xy) expected" % s)
         ids_np, xy_np = det
+        if (ids_np is None) != bool(associate):
+            _ids_or_associate(ids_np, True if associate else None, "tick: stream %d" % s)
         # numpy arrays already in shape are taken as they are (a tick of many streams is packed on the host clock)
-        if type(ids_np) is not np.ndarray or ids_np.ndim != 1:
+        if not associate and (type(ids_np) is not np.ndarray or ids_np.ndim != 1):
             ids_np = np.asarray(ids_np.cpu() if torch.is_tensor(ids_np) else ids_np).reshape(-1)
         if type(xy_np) is not np.ndarray or xy_np.dtype != np.float64 or xy_np.ndim != 2 or xy_np.shape[1] != 2:
             xy_np = np.asarray(xy_np.cpu() if torch.is_tensor(xy_np) else xy_np, dtype=np.float64).reshape(-1, 2)
-        m = len(ids_np)
+        m = len(xy_np) if associate else len(ids_np)
         if m > max_detections:
             raise ValueError("tick: stream %d: %d detections > max_detections=%d" % (s, m, max_detections))
         if xy_np.shape[0] != m:
@@ -671,10 +801,12 @@ def pack_tick(tick, streams, max_detections, max_total_detections):
     total = int(counts.sum())
     if total > max_total_detections:
         raise ValueError("tick: %d detections > max_total_detections=%d" % (total, max_total_detections))
-    ids = _integral_ids(np.concatenate(ids_l) if ids_l else np.zeros(0, np.int64), "tick")
     xy = np.concatenate(xy_l) if xy_l else np.zeros((0, 2))
     det_start = np.zeros(streams + 1, np.int32)
     det_start[1:] = np.cumsum(counts)
+    if associate:
+        return PackedTick(det_start, pushed, None, np.ascontiguousarray(xy))
+    ids = _integral_ids(np.concatenate(ids_l) if ids_l else np.zeros(0, np.int64), "tick")
     if total > 1:
         # a repeated (stream, id): one sort of stream << b | id where the ids fit in b bits, else a two-key sort
         owner = np.repeat(np.arange(streams, dtype=np.int64), counts)
@@ -714,6 +846,11 @@ class StreamsPredictor(_LivePredictor):
     zero for a stream not pushed, `.score_totals` the per-stream totals.  With best_of_k the records keep every push's
     samples for pred_seq_len pushes: about 3.5 MB per stream at 12 steps, 128 pedestrians and k = 20, so 600 streams
     hold about 2.1 GB (0.4 MB per stream with ScoreSpec(best_of_k=False)).
+    associate: an AssociateSpec for every stream, each with its own tracks and its own ids from 0
+    (stg_associate_streams, one workgroup per stream ahead of the push launch): tick entries are (None, xy), a
+    DeviceTick is DeviceTick(None, xy, counts); `.det_ids` (M,) holds the ids of the tick's packed detections,
+    `.assoc_flags` (NS,) the flags of each stream's last push.  A stream not pushed keeps its association state bit for
+    bit.  Not together with time=.
     time: a TimeRule for every stream, each with its own clock (stg_track_push_streams_timed): push(tick, times=...)
     with times a length-NS sequence or a {stream: t} mapping that covers every pushed stream -- staged in the same ONE
     copy, the staging header extended by NS int64 --, or with a DeviceTick a device int64 (NS) tensor.  The sample
@@ -722,9 +859,9 @@ class StreamsPredictor(_LivePredictor):
 
     def __init__(self, model, streams, k=20, obs_len=8, capacity=1024, max_peds=128, max_detections=1024, decimals=4,
                  max_total_detections=None, block_threads=0, risk=None, keep_samples=True, tracks=None, score=None,
-                 time=None):
+                 time=None, associate=None):
         super().__init__(model, k, obs_len, capacity, max_peds, max_detections, decimals, risk, keep_samples, tracks,
-                         score, time)
+                         score, time, associate)
         if not _is_int(streams, 1, MAX_STREAMS):
             raise ValueError("streams must be an integer in [1, %d], got %r" % (MAX_STREAMS, streams))
         self.ns = int(streams)
@@ -779,6 +916,7 @@ class StreamsPredictor(_LivePredictor):
             self.slot_id.fill_(-1)
             for x in self._state[1:]:
                 x.zero_()
+            self._reset_assoc()
             if self._score_state is not None:
                 ops.score_reset(self._score_state)
             return
@@ -792,8 +930,19 @@ class StreamsPredictor(_LivePredictor):
         self.slot_id.index_fill_(0, at, -1)
         for x in self._state[1:]:
             x.index_fill_(0, at, 0)
+        self._reset_assoc(at)
         if self._score_state is not None:
             ops.score_reset(self._score_state, at)
+
+    @property
+    def det_ids(self):
+        """With associate=: the track id given to every detection of the last tick, (M,) int64 on the device, the
+        pushed streams' detections in stream order as the tick listed them (a view of the staging records, overwritten
+        by the next tick).  Ids count from 0 in every stream."""
+        return None if self.assoc is None else self._rec_i[:self._n_det, 0]
+
+    def _associate(self):
+        self._launch_associate("stg_associate_streams", (*self._det.values(), self.ns, self.m_max))
 
     def _wait_host(self):
         """The pinned buffer is rewritten only after the previous tick's copy has left it."""
@@ -840,8 +989,10 @@ class StreamsPredictor(_LivePredictor):
             raise ValueError("push: a predictor made with time= needs the streams' push times, times=...")
         if isinstance(tick, DeviceTick):
             return self._stage_device(tick, seed, times)
-        pk = pack_tick(tick, self.ns, self.m_max, self.cap)           # refuses before anything is written or copied
-        m = len(pk.ids)
+        # refuses before anything is written or copied
+        pk = pack_tick(tick, self.ns, self.m_max, self.cap, self.assoc is not None)
+        m = len(pk.xy)
+        self._n_det = m
         if times is not None:
             times = self._host_times(times, pk.pushed)
         self._wait_host()
@@ -852,7 +1003,8 @@ class StreamsPredictor(_LivePredictor):
         if seed is not None:
             self._h_seed[0] = seed_i64(seed)
         if m:
-            self._h_rec_i[:m, 0] = pk.ids
+            if pk.ids is not None:                           # (with associate= the id field is the kernel's to write)
+                self._h_rec_i[:m, 0] = pk.ids
             self._h_rec_f[:m, 1:] = pk.xy
         self._copy(self._hdr + 24 * m)
 
@@ -861,9 +1013,10 @@ class StreamsPredictor(_LivePredictor):
         if times is not None and not (torch.is_tensor(times) and times.is_cuda and times.dtype == torch.int64
                                       and times.numel() == self.ns):
             raise ValueError("DeviceTick: times must be a device int64 (%d) tensor" % self.ns)
-        if not (torch.is_tensor(ids) and ids.is_cuda and torch.is_tensor(xy) and xy.is_cuda):
+        _ids_or_associate(ids, self.assoc, "DeviceTick")
+        if not ((ids is None or (torch.is_tensor(ids) and ids.is_cuda)) and torch.is_tensor(xy) and xy.is_cuda):
             raise ValueError("DeviceTick: ids and xy must be device tensors")
-        m = ids.numel()
+        m = xy.shape[0] if ids is None else ids.numel()
         if m > self.cap:
             raise ValueError("tick: %d detections > max_total_detections=%d" % (m, self.cap))
         if tuple(xy.shape) != (m, 2):
@@ -876,6 +1029,7 @@ class StreamsPredictor(_LivePredictor):
         n_counts = counts.numel() if dev_counts else counts.size
         if n_counts != self.ns:
             raise ValueError("DeviceTick: %d counts for %d streams" % (n_counts, self.ns))
+        self._n_det = m
         self._wait_host()
         if seed is not None:
             self._h_seed[0] = seed_i64(seed)
@@ -895,7 +1049,8 @@ class StreamsPredictor(_LivePredictor):
         if times is not None:                                # behind the header copy, which carries stale host times
             self.times_dev.copy_(times.reshape(-1))
         if m:
-            self._rec_i[:m, 0].copy_(ids.reshape(-1))
+            if ids is not None:
+                self._rec_i[:m, 0].copy_(ids.reshape(-1))
             self._rec_f[:m, 1:].copy_(xy)
 
     def _outs(self):

@@ -5,6 +5,7 @@ trajectories for every pedestrian tracked over the last obs_seq_len frames.
                                                [--min_peds 1] [--delim tab] [--radius R]
                                                [--zones x0,y0,x1,y1 ...] [--min_seen M] [--max_gap G]
                                                [--step TICKS [--max_dt D] [--history R] [--max_peds V]]
+                                               [--associate GATE[,GATE_NEW[,MAX_MISS]] [--max_peds V]]
                                                --out preds.npz
 
 DIR is a checkpoint directory in the reference's layout (args.pkl and val_best.pth, as social_stgcnn_amd.test reads
@@ -28,6 +29,12 @@ pedestrians, padded to the largest scene (at most --max_peds, default 128: the s
 above `seen` and `time` (N,) int64, the pushes' times (`frame` holds the same numbers as float64).  The sampler's seed is
 --seed + the push's index.  Not together with --radius / --zones.  Where a recording skips a frame number the two rules
 differ: the frame-index rule makes neighbours of frames 20 ticks apart, the timed rule sees a gap.
+
+--associate GATE[,GATE_NEW[,MAX_MISS]] ignores the id column: every distinct frame number is one push of positions only,
+rows in file order, through a captured frames.FramePredictor(associate=frames.AssociateSpec(...)), which gives every
+detection its track id on the device.  The .npz holds one entry per push with at least --min_peds
+pedestrians, padded to the largest scene (at most --max_peds), its ids the assigned track ids, and assoc_ids (M,) int64:
+the assigned id of every row of the recording, in file order.  Not together with --step or --radius / --zones.
 """
 import argparse
 import os
@@ -37,7 +44,7 @@ import numpy as np
 import torch
 
 from . import data
-from .frames import FramePredictor, TimeRule, TrackRule, predict_recording, sorted_rows
+from .frames import AssociateSpec, FramePredictor, TimeRule, TrackRule, predict_recording, sorted_rows
 from .model import social_stgcnn
 from .predict import RiskSpec
 from .trainer import load_checkpoint, load_pickle
@@ -65,7 +72,10 @@ def build_parser():
     p.add_argument("--max_dt", type=int, default=None, help="with --step: interpolate between samples at most this many "
                                                             "ticks apart (default: the step)")
     p.add_argument("--history", type=int, default=96, help="with --step: samples kept per track")
-    p.add_argument("--max_peds", type=int, default=128, help="with --step: the widest scene (the smallest ids are kept)")
+    p.add_argument("--max_peds", type=int, default=128,
+                   help="with --step or --associate: the widest scene (the smallest ids are kept)")
+    p.add_argument("--associate", default=None, metavar="GATE[,GATE_NEW[,MAX_MISS]]",
+                   help="ignore the id column: associate the detections to tracks on the device (assoc_ids array)")
     p.add_argument("--out", required=True, help="output .npz")
     # a rectangle may begin with a negative coordinate: "-1,-1,1,1" is a value, not an option
     p._negative_number_matcher = re.compile(r"^-[0-9.][0-9.,eE+-]*$")
@@ -123,6 +133,54 @@ def predict_timed(model, rows, time, k=20, seed=0, min_peds=1, tracks=None, max_
     return res
 
 
+def parse_associate(spec):
+    """'GATE[,GATE_NEW[,MAX_MISS]]' -> frames.AssociateSpec."""
+    parts = spec.split(",")
+    if not 1 <= len(parts) <= 3:
+        raise ValueError("--associate: GATE[,GATE_NEW[,MAX_MISS]] expected, got %r" % spec)
+    return AssociateSpec(float(parts[0]), float(parts[1]) if len(parts) > 1 else None,
+                         int(parts[2]) if len(parts) > 2 else 0)
+
+
+def predict_associated(model, rows, associate, k=20, seed=0, min_peds=1, tracks=None, max_peds=128):
+    """Every distinct frame number of `rows` pushed without ids, rows in file order, through ONE captured
+    FramePredictor(associate=...) -> a dict of host arrays: one entry per push whose scene holds at least min_peds
+    pedestrians, and assoc_ids, the assigned id of every row."""
+    rows = np.asarray(rows, dtype=np.float64)
+    frames = np.unique(rows[:, 0])
+    f_idx = np.searchsorted(frames, rows[:, 0])
+    order = np.argsort(f_idx, kind="stable")
+    fs = np.searchsorted(f_idx[order], np.arange(len(frames) + 1))
+    m_max = max(1, int(np.diff(fs).max()) if len(frames) else 1)
+    fp = FramePredictor(model, k=k, obs_len=model.seq_len, max_peds=max_peds, max_detections=m_max, tracks=tracks,
+                        associate=associate)
+    replay = fp.capture()
+    assoc_ids = np.full(len(rows), -1, np.int64)
+    names = ("frame", "ids", "num_peds", "mean", "samples") + (() if tracks is None else ("seen",))
+    keep = {name: [] for name in names}
+    for f in range(len(frames)):
+        at = order[fs[f]:fs[f + 1]]
+        out = replay(None, rows[at, 2:4], seed=seed + f)
+        assoc_ids[at] = fp.det_ids.cpu().numpy()
+        n = int(out.num_peds.item())
+        if n < min_peds:
+            continue
+        for name, x in zip(names, (frames[f], out.ids, np.int32(n), out.mean, out.samples, fp.seen)):
+            keep[name].append(x.cpu().numpy() if torch.is_tensor(x) else x)
+    v = max(1, max(keep["num_peds"], default=0))
+    p = model.pred_seq_len
+    empty = dict(frame=np.zeros(0), ids=np.zeros((0, v), np.int64), num_peds=np.zeros(0, np.int32),
+                 mean=np.zeros((0, p, v, 2), np.float32), samples=np.zeros((0, fp.k, p, v, 2), np.float32),
+                 seen=np.zeros((0, v), np.int32))
+    res = {name: np.stack(x) if x else empty[name] for name, x in keep.items()}
+    res.update(ids=res["ids"][:, :v], mean=res["mean"][:, :, :v],
+               samples=np.ascontiguousarray(np.moveaxis(res["samples"], 0, 1)[:, :, :, :v]))
+    if tracks is not None:
+        res["seen"] = res["seen"][:, :v]
+    res["assoc_ids"] = assoc_ids
+    return res
+
+
 def main(argv=None):
     a = build_parser().parse_args(argv)
     if not torch.cuda.is_available():
@@ -133,6 +191,15 @@ def main(argv=None):
     tracks = None
     if a.min_seen is not None or a.max_gap is not None:
         tracks = TrackRule(model.seq_len if a.min_seen is None else a.min_seen, 0 if a.max_gap is None else a.max_gap)
+    if a.associate is not None:
+        if a.step is not None or a.radius is not None or a.zones is not None:
+            raise ValueError("--associate does not go together with --step or --radius / --zones")
+        res = predict_associated(model, rows, parse_associate(a.associate), a.ksteps, a.seed, a.min_peds, tracks,
+                                 a.max_peds)
+        np.savez(a.out, **res)
+        print("%d pushes with a scene, up to %d pedestrians, %d track ids -> %s"
+              % (len(res["frame"]), res["ids"].shape[1], int(res["assoc_ids"].max(initial=-1)) + 1, a.out))
+        return
     if a.step is not None:
         if a.radius is not None or a.zones is not None:
             raise ValueError("--step does not go together with --radius / --zones")

@@ -5,6 +5,8 @@
     python tools/frames_bench.py --cases streams [--streams 1,8,64,256,600] [--ticks 200] [--block 0] [--no-lone]
                                  [--risk none,samples,lean]
     python tools/frames_bench.py --cases score [--streams 1,64,600] [--ticks 200]
+    python tools/frames_bench.py --cases associate [--streams 1,64,600] [--ticks 200] [--associate 1.0,2.0,0]
+                                 [--no-lone]
     python tools/frames_bench.py --tracks 2,2 ...       every case under frames.TrackRule(2, 2) (the *_rule kernels)
     python tools/frames_bench.py --time 10,10 ...       the latency and streams cases on timestamped pushes
                                                         (frames.TimeRule(10, history=--history), stg_track_push_timed):
@@ -29,6 +31,13 @@
   score      the streams case with and without score=ScoreSpec() (stg_score_push_streams behind the sampler, inside the
              graph) at NS = 1, 64 and 600 (or --streams), no yardstick: tick p50 / p90 of both, the difference, what
              the score records hold on the device (state_mb) and the running summary at the last tick.
+
+  associate  the streams case with and without associate=AssociateSpec(...) (stg_associate_streams ahead of the push
+             launch, inside the graph; ticks of (None, xy)) at NS = 1, 64 and 600 (or --streams), no yardstick: tick p50 /
+             p90 of both and host_p50_ms, the host's share (staging + the replay call, before the synchronise); then, on
+             crowds_zara01 and students003, a captured FramePredictor with score=ScoreSpec() fed the recording's own ids
+             and one fed none: best-of-K ADE / FDE of both, and the share of wrong links (a detection whose recorded id
+             was in the previous push and whose assigned id is not the one that pedestrian had then).
 
 Kernel times come from a separate run under the profiler (tracing slows the host):
     rocprofv3 --kernel-trace --stats -d OUT -o frames -- python tools/frames_bench.py --cases latency --pushes 500
@@ -159,7 +168,7 @@ def _stream_sequences(ns, n, timed=None):
 
 
 def streams_case(ns, k, n_ticks, dev, block=0, lone=True, max_peds=128, warmup=20, risk="none", tracks=None,
-                 score=None, timed=None):
+                 score=None, timed=None, associate=None):
     from social_stgcnn_amd import frames
     model = model_for("univ", dev)
     seq = _stream_sequences(ns, warmup + n_ticks, timed)
@@ -172,17 +181,22 @@ def streams_case(ns, k, n_ticks, dev, block=0, lone=True, max_peds=128, warmup=2
         kw = dict(risk=RiskSpec(0.5, np.array([[-1, -1, 1, 1], [0, 0, 4, 3], [-50, -50, 50, 50]], np.float32)),
                   keep_samples=risk == "samples")
     kw.update(tracks_kw(tracks, timed))
+    if associate is not None:
+        kw["associate"] = associate
+        seq = [[(None, xy) for _, xy in q] for q in seq]
     sp = frames.StreamsPredictor(model, ns, k=k, max_peds=max_peds, block_threads=block, **kw)
     replay = sp.capture()
-    times, peds = [], []
+    times, host, peds = [], [], []
     for t in range(warmup + n_ticks):
         tick = [q[t][:2] for q in seq]
         when = {} if timed is None else {"times": [q[t][2] for q in seq]}
         t0 = time.perf_counter()
         out = replay(tick, **when)
+        t1 = time.perf_counter()
         torch.cuda.synchronize()
         if t >= warmup:
             times.append(time.perf_counter() - t0)
+            host.append(t1 - t0)
             peds.append(out.num_peds.clone())
     ms = np.array(times) * 1e3
     peds = torch.stack(peds).cpu().numpy()
@@ -190,7 +204,10 @@ def streams_case(ns, k, n_ticks, dev, block=0, lone=True, max_peds=128, warmup=2
     res = {"case": "streams", "streams": ns, "k": k, "max_peds": max_peds, "block": block or frames.STREAM_THREADS,
            "ticks": n_ticks, "tick_p50_ms": round(p50, 4), "tick_p90_ms": round(float(np.percentile(ms, 90)), 4),
            "frames_per_s_p50": round(ns * 1e3 / p50, 1), "mean_peds": round(float(peds.mean()), 2),
-           "max_peds_seen": int(peds.max())}
+           "max_peds_seen": int(peds.max()), "host_p50_ms": round(float(np.percentile(host, 50)) * 1e3, 4)}
+    if associate is not None:
+        res["associate"] = list(associate[:3])
+        res["assoc_full"] = int((sp.assoc_flags != 0).sum())
     if tracks is not None:
         res["tracks"] = list(tracks)
     if timed is not None:
@@ -235,6 +252,34 @@ def streams_case(ns, k, n_ticks, dev, block=0, lone=True, max_peds=128, warmup=2
     return res
 
 
+def associate_quality(split, rec, k, dev, spec, max_peds=128):
+    """One recording through two captured FramePredictors with score=ScoreSpec(): one fed the recording's ids, one fed
+    positions only.  What an identity switch costs in prediction quality."""
+    from social_stgcnn_amd import data, frames
+    from social_stgcnn_amd.predict import ScoreSpec
+    pushes = pushes_of(data.read_file(os.path.join(DATA, rec)))
+    model = model_for(split, dev)
+    score = ScoreSpec()
+    res = {"case": "associate_quality", "recording": os.path.basename(rec), "k": k, "associate": list(spec[:3])}
+    for name, assoc in (("ids", None), ("assoc", spec)):
+        fp = frames.FramePredictor(model, k=k, max_peds=max_peds, score=score, associate=assoc)
+        replay = fp.capture()
+        prev, wrong, links = {}, 0, 0
+        for t, (ids, xy) in enumerate(pushes):
+            replay(None if assoc else ids, xy, seed=t)
+            if assoc:
+                now = dict(zip(ids.tolist(), fp.det_ids.cpu().tolist()))
+                links += sum(1 for r in now if r in prev)
+                wrong += sum(1 for r, g in now.items() if r in prev and prev[r] != g)
+                prev = now
+        s = frames.score_summary(*fp.score_totals, score.levels)
+        res.update({name + "_trajectories": int(s.trajectories[0]), name + "_ade": round(float(s.ade[0]), 4),
+                    name + "_fde": round(float(s.fde[0]), 4), name + "_scored": int(s.count[0].sum())})
+        if assoc:
+            res.update({"links": links, "wrong_links": wrong, "assoc_full": int(fp.assoc_flags.item())})
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--pushes", type=int, default=2000)
@@ -243,7 +288,8 @@ def main():
     ap.add_argument("--streams", default="1,8,64,256,600")
     ap.add_argument("--ticks", type=int, default=200)
     ap.add_argument("--block", default="0", help="push workgroup size(s) of the streams case, comma separated")
-    ap.add_argument("--no-lone", action="store_true")
+    ap.add_argument("--no-lone", action="store_true",
+                    help="streams: skip the yardstick; associate: skip the two single-stream quality runs")
     ap.add_argument("--risk", default="none", help="modes of the streams case, comma separated: none, samples, lean")
     ap.add_argument("--tracks", default=None, metavar="M,G",
                     help="run every case under frames.TrackRule(min_seen=M, max_gap=G); default: the strict rule")
@@ -251,6 +297,8 @@ def main():
                     help="timestamped pushes (frames.TimeRule(STEP)) on the feed upsampled UP x (default 1) by linear "
                          "interpolation: the latency and streams cases")
     ap.add_argument("--history", type=int, default=96, help="with --time: samples kept per track")
+    ap.add_argument("--associate", default="1.0,2.0,0", metavar="GATE[,GATE_NEW[,MAX_MISS]]",
+                    help="the AssociateSpec of the associate case")
     a = ap.parse_args()
     tracks = None if a.tracks is None else tuple(int(x) for x in a.tracks.split(","))
     timed = None
@@ -278,6 +326,20 @@ def main():
                        "tick_p90_ms_without": off["tick_p90_ms"],
                        "score_cost_p50_ms": round(on["tick_p50_ms"] - off["tick_p50_ms"], 4)})
             print(json.dumps(on), flush=True)
+    if "associate" in cases:
+        from social_stgcnn_amd.frames import AssociateSpec
+        g = a.associate.split(",")
+        spec = AssociateSpec(float(g[0]), float(g[1]) if len(g) > 1 else None, int(g[2]) if len(g) > 2 else 0)
+        for ns in (int(n) for n in (a.streams if a.streams != "1,8,64,256,600" else "1,64,600").split(",")):
+            off = streams_case(ns, a.k, a.ticks, dev, 0, False, tracks=tracks)
+            on = streams_case(ns, a.k, a.ticks, dev, 0, False, tracks=tracks, associate=spec)
+            on.update({"case": "associate", "tick_p50_ms_without": off["tick_p50_ms"],
+                       "tick_p90_ms_without": off["tick_p90_ms"], "host_p50_ms_without": off["host_p50_ms"],
+                       "associate_cost_p50_ms": round(on["tick_p50_ms"] - off["tick_p50_ms"], 4)})
+            print(json.dumps(on), flush=True)
+        for split, rec in (() if a.no_lone else (("zara1", "zara1_test/crowds_zara01.txt"),
+                                                 ("univ", "univ_test/students003.txt"))):
+            print(json.dumps(associate_quality(split, rec, a.k, dev, spec)), flush=True)
     if "streams" in cases:
         for block in (int(b) for b in a.block.split(",")):
             for ns in (int(n) for n in a.streams.split(",")):
