@@ -13,7 +13,9 @@
 //   stg_track_push_streams  NS live streams: one workgroup per stream runs the same push (track_push_body) on the
 //                           stream's slice of the state and its range of one packed tick of detections; the counts,
 //                           offsets and pushed flags are read from device memory, so one captured graph serves a tick.
-// The pushes sort their detections and look ids up with detections.hpp, as the score kernels do.
+// The pushes sort their detections and look ids up with detections.hpp, as the score kernels do; the
+// slot assignment, the padding of a scene, the per-stream wrapper and the host's stream checks are those of every push
+// (track_rule.hpp).
 //
 // Partially observed tracks: TrackRule (track_rule.hpp) admits a pedestrian with a short history or tracker gaps
 // and fills the frames it missed.  stg_fill_tracks applies the fill to a batch in place; the *_rule entry points are
@@ -232,48 +234,9 @@ __device__ __forceinline__ int track_push_body(const int64_t *__restrict__ det_i
     for (int j = tid; j < m; j += nt) det_slot[j] = -1;
     __syncthreads();
 
-    // 2. sort the detections by (id, detection index)
-    det_sort(key, kidx, n2, tid, nt);
-
-    // 3. a repeated id: the first detection wins, the others are dropped.  Every live slot finds its id among the
-    //    detections (det_find: the winner).
-    for (int p = tid; p < m; p += nt)
-        if (p > 0 && key[p] == key[p - 1]) {
-            det_slot[kidx[p]] = -2;
-            atomicOr(&flags, kFlagDuplicate);
-        }
-    for (int s = tid; s < S; s += nt) {
-        if (smask[s] == 0) continue;
-        const int at = det_find(key, m, slot_id[s]);
-        if (at >= 0) det_slot[kidx[at]] = s;
-    }
-    __syncthreads();
-
-    // 4. new ids take free slots: the i-th new detection (detection order) gets the i-th free slot (slot order)
-    int n_free = 0, tot = 0;
-    for (int s0 = 0; s0 < S; s0 += nt) {
-        const int s = s0 + tid;
-        const bool fr = s < S && smask[s] == 0;
-        const int r = block_rank<kThreads>(fr, n_free, &tot, wave_cnt);
-        if (fr) free_list[r] = s;
-        n_free += tot;
-    }
-    __syncthreads();
-    int n_new = 0;
-    for (int j0 = 0; j0 < m; j0 += nt) {
-        const int j = j0 + tid;
-        const bool nw = j < m && det_slot[j] == -1;
-        const int r = block_rank<kThreads>(nw, n_new, &tot, wave_cnt);
-        if (nw) {
-            if (r < n_free) det_slot[j] = free_list[r];
-            else {
-                det_slot[j] = -3;
-                atomicOr(&flags, kFlagOverflow);
-            }
-        }
-        n_new += tot;
-    }
-    __syncthreads();
+    // 2-4. every detection gets its slot (assign_slots: the one rule of the pushes); a slot is live by its mask
+    assign_slots<kThreads>(key, kidx, det_slot, free_list, wave_cnt, &flags, m, n2, S, slot_id,
+                           [&](int s) { return smask[s] != 0; });
 
     // 5. record this frame: id, presence bit 0, rounded position in the ring row `head`
     for (int j = tid; j < m; j += nt) {
@@ -288,7 +251,7 @@ __device__ __forceinline__ int track_push_body(const int64_t *__restrict__ det_i
 
     // 6. the scene: slots seen in each of the last T_obs frames, in ascending id order (the sorted detections), the
     //    first V of them; gather their T_obs positions, oldest first
-    int c = 0;
+    int c = 0, tot = 0;
     for (int p0 = 0; p0 < m; p0 += nt) {
         const int p = p0 + tid;
         const int j = p < m ? kidx[p] : 0;
@@ -336,14 +299,7 @@ __device__ __forceinline__ int track_push_body(const int64_t *__restrict__ det_i
     }
     if (c > V && tid == 0) atomicOr(&flags, kFlagTooMany);
     const int np = c < V ? c : V;
-    for (int e = np + tid; e < V; e += nt) out_ids[e] = -1;
-    if constexpr (kRule)
-        for (int e = np + tid; e < V; e += nt) seen[e] = 0;
-    for (int e = tid; e < T_obs * (V - np); e += nt) {
-        const int t = e / (V - np), r = np + e % (V - np);
-        obs_abs[((int64_t)t * V + r) * 2] = 0.0;
-        obs_abs[((int64_t)t * V + r) * 2 + 1] = 0.0;
-    }
+    pad_scene(obs_abs, out_ids, kRule ? seen : nullptr, T_obs, V, np);
     for (int s = tid; s < S; s += nt) mask[s] = smask[s];
     __syncthreads();
     if (tid == 0) {
@@ -373,9 +329,8 @@ __global__ __launch_bounds__(kPushThreads) void track_push_rule_kernel(
                                         head_flags, S, T_obs, scale, V, obs_abs, out_ids, num_peds, rule, seen);
 }
 
-// One workgroup per stream: stream b pushes detections det_start[b] .. det_start[b+1]-1 (clamped to [0, M_total))
-// when pushed[b] != 0; otherwise its state is not touched and its scene is the empty one.  Every stream's pointers
-// are its own slices of the (NS, ...) state and output arrays.
+// One workgroup per stream (push_stream): every stream's pointers are its own slices of the (NS, ...) state and output
+// arrays.
 template <int kThreads, bool kRule>
 __device__ __forceinline__ void track_push_stream(
     const int64_t *__restrict__ det_id, int64_t id_stride, const double *__restrict__ det_xy, int64_t xy_stride,
@@ -384,28 +339,14 @@ __device__ __forceinline__ void track_push_stream(
     int32_t *__restrict__ head_flags, int S, int T_obs, double scale, int V, double *__restrict__ obs_abs,
     int64_t *__restrict__ out_ids, int32_t *__restrict__ num_peds, int32_t *__restrict__ out_flags,
     TrackRule rule = {}, int32_t *__restrict__ seen = nullptr) {
-    const int b = blockIdx.x, tid = threadIdx.x;
-    double *obs = obs_abs + (int64_t)b * T_obs * V * 2;
-    int64_t *oid = out_ids + (int64_t)b * V;
-    int32_t *osn = kRule ? seen + (int64_t)b * V : nullptr;
-    if (pushed[b] == 0) {                                   // uniform over the block: no barrier is skipped halfway
-        for (int e = tid; e < V; e += kThreads) oid[e] = -1;
-        if constexpr (kRule)
-            for (int e = tid; e < V; e += kThreads) osn[e] = 0;
-        for (int e = tid; e < T_obs * V * 2; e += kThreads) obs[e] = 0.0;
-        if (tid == 0) {
-            num_peds[b] = 0;
-            if (out_flags) out_flags[b] = 0;
-        }
-        return;
-    }
-    int lo;
-    const int count = det_range(det_start, b, M_total, lo);
-    const int flags = track_push_body<kThreads, kRule>(
-        det_id + lo * id_stride, id_stride, det_xy + lo * xy_stride, xy_stride, count, M_max, M2,
-        slot_id + (int64_t)b * S, mask + (int64_t)b * S, ring + (int64_t)b * T_obs * S * 2, head_flags + 2 * b, S, T_obs,
-        scale, V, obs, oid, num_peds + b, rule, osn);
-    if (out_flags && tid == 0) out_flags[b] = flags;
+    push_stream(det_start, pushed, M_total, T_obs, V, obs_abs, out_ids, kRule ? seen : nullptr, num_peds, out_flags,
+                [&](int lo, int count, double *obs, int64_t *oid, int32_t *osn, int32_t *peds) {
+                    const int64_t b = blockIdx.x;
+                    return track_push_body<kThreads, kRule>(
+                        det_id + lo * id_stride, id_stride, det_xy + lo * xy_stride, xy_stride, count, M_max, M2,
+                        slot_id + b * S, mask + b * S, ring + b * T_obs * S * 2, head_flags + 2 * b, S, T_obs, scale, V,
+                        obs, oid, peds, rule, osn);
+                });
 }
 
 template <int kThreads>
@@ -472,15 +413,12 @@ static int track_push_streams(const char *what, bool ruled, int min_seen, int ma
                               uint32_t *mask, double *ring, int32_t *head_flags, int S, int T_obs, double scale, int V,
                               double *obs_abs, int64_t *out_ids, int32_t *num_peds, int32_t *out_flags, int32_t *seen,
                               int block_threads, void *stream) {
-    STG_REQUIRE(NS >= 1 && NS <= STG_TRACK_MAX_STREAMS && M_total >= 0 && M_total <= STG_TRACK_MAX_TOTAL_DETECTIONS &&
-                    M_max >= 1 && M_max <= STG_TRACK_MAX_DETECTIONS && S >= 1 && S <= STG_TRACK_MAX_SLOTS && V >= 1 &&
-                    (ruled || (T_obs >= 1 && T_obs <= 32)) && id_stride >= 1 && xy_stride >= 2,
-                STG_EINVAL, "%s: bad sizes NS=%d M_total=%d M_max=%d S=%d V=%d T_obs=%d strides %lld/%lld", what, NS,
-                M_total, M_max, S, V, T_obs, (long long)id_stride, (long long)xy_stride);
+    const int rc = push_streams_args(what, NS, M_total, id_stride, xy_stride, block_threads);
+    if (rc != STG_OK) return rc;
+    STG_REQUIRE(M_max >= 1 && M_max <= STG_TRACK_MAX_DETECTIONS && S >= 1 && S <= STG_TRACK_MAX_SLOTS && V >= 1 &&
+                    (ruled || (T_obs >= 1 && T_obs <= 32)),
+                STG_EINVAL, "%s: bad sizes M_max=%d S=%d V=%d T_obs=%d", what, M_max, S, V, T_obs);
     if (ruled) STG_REQUIRE_RULE(what);
-    if (block_threads == 0) block_threads = kStreamThreads;
-    STG_REQUIRE(block_threads == 64 || block_threads == 256 || block_threads == 1024, STG_EINVAL,
-                "%s: block_threads=%d (0, 64, 256 or 1024)", what, block_threads);
     STG_REQUIRE(det_id && det_xy && det_start && pushed && slot_id && mask && ring && head_flags && obs_abs &&
                     out_ids && num_peds && (seen || !ruled),
                 STG_EINVAL, "%s: null pointer", what);
@@ -488,21 +426,19 @@ static int track_push_streams(const char *what, bool ruled, int min_seen, int ma
     const size_t lds = push_lds(M_max, m2, S);
     const dim3 grid(NS), block(block_threads);
     // the workgroup size picks the instantiation, `ruled` the kernel of the pair
-    auto go = [&](auto strict_kernel, auto rule_kernel) {
+    return with_stream_threads(block_threads, [&](auto kt) -> int {
         if (ruled)
-            hipLaunchKernelGGL(rule_kernel, grid, block, lds, as_stream(stream), det_id, id_stride, det_xy, xy_stride,
-                               M_total, det_start, pushed, M_max, m2, slot_id, mask, ring, head_flags, S, T_obs, scale, V,
-                               TrackRule{min_seen, max_gap}, obs_abs, out_ids, num_peds, out_flags, seen);
+            hipLaunchKernelGGL(track_push_streams_rule_kernel<kt()>, grid, block, lds, as_stream(stream), det_id,
+                               id_stride, det_xy, xy_stride, M_total, det_start, pushed, M_max, m2, slot_id, mask, ring,
+                               head_flags, S, T_obs, scale, V, TrackRule{min_seen, max_gap}, obs_abs, out_ids, num_peds,
+                               out_flags, seen);
         else
-            hipLaunchKernelGGL(strict_kernel, grid, block, lds, as_stream(stream), det_id, id_stride, det_xy, xy_stride,
-                               M_total, det_start, pushed, M_max, m2, slot_id, mask, ring, head_flags, S, T_obs, scale, V,
-                               obs_abs, out_ids, num_peds, out_flags);
-    };
-    if (block_threads == 64) go(track_push_streams_kernel<64>, track_push_streams_rule_kernel<64>);
-    else if (block_threads == 256) go(track_push_streams_kernel<256>, track_push_streams_rule_kernel<256>);
-    else go(track_push_streams_kernel<1024>, track_push_streams_rule_kernel<1024>);
-    STG_LAUNCH_CHECK(what);
-    return STG_OK;
+            hipLaunchKernelGGL(track_push_streams_kernel<kt()>, grid, block, lds, as_stream(stream), det_id, id_stride,
+                               det_xy, xy_stride, M_total, det_start, pushed, M_max, m2, slot_id, mask, ring, head_flags,
+                               S, T_obs, scale, V, obs_abs, out_ids, num_peds, out_flags);
+        STG_LAUNCH_CHECK(what);
+        return STG_OK;
+    });
 }
 
 }  // namespace stg

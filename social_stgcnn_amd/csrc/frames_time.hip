@@ -9,11 +9,11 @@
 //                                 samples (time, rounded position), {next write index, count} per slot, the clock
 //   stg_track_push_streams_timed  one workgroup per stream on the (NS, ...) slices, as stg_track_push_streams_rule
 //
-// The sort, the id lookup and the slot assignment are those of track_push_body (detections.hpp, the same order of new
-// ids over free slots); a slot is live by its newest sample's age instead of a presence mask.  Everything is read from
-// device memory when the kernel runs -- the time too -- so one captured graph serves every push.  Integer work, float64
-// arithmetic with IEEE operations as written, plain C++ stores, LDS atomics on integer words, no scratch, no host
-// synchronisation.
+// The sort and the slot assignment (assign_slots), the padding of a scene and the per-stream wrapper are those of every
+// push (track_rule.hpp); a slot is live by its newest sample's age instead of a presence mask.
+// Everything is read from device memory when the kernel runs -- the time too -- so one captured graph serves every
+// push.  Integer work, float64 arithmetic with IEEE operations as written, plain C++ stores, LDS atomics on integer
+// words, no scratch, no host synchronisation.
 #include "detections.hpp"
 #include "track_rule.hpp"
 
@@ -69,11 +69,7 @@ __device__ __forceinline__ int track_push_timed_body(
     // 0. time must move forward (the first push takes any time): otherwise the empty scene and no change of state.
     //    Uniform over the block, ahead of every barrier.
     if (pushes > 0 && t_now <= last) {
-        for (int e = tid; e < V; e += nt) {
-            out_ids[e] = -1;
-            seen[e] = 0;
-        }
-        for (int e = tid; e < T_obs * V * 2; e += nt) obs_abs[e] = 0.0;
+        pad_scene(obs_abs, out_ids, seen, T_obs, V, 0);
         if (tid == 0) {
             num_peds[0] = 0;
             head_flags[1] = kFlagTimeOrder;
@@ -106,47 +102,9 @@ __device__ __forceinline__ int track_push_timed_body(
     for (int j = tid; j < m; j += nt) det_slot[j] = -1;
     __syncthreads();
 
-    // 2. sort the detections by (id, detection index)
-    det_sort(key, kidx, n2, tid, nt);
-
-    // 3. a repeated id: the first detection wins.  Every live slot finds its id among the detections.
-    for (int p = tid; p < m; p += nt)
-        if (p > 0 && key[p] == key[p - 1]) {
-            det_slot[kidx[p]] = -2;
-            atomicOr(&flags, kFlagDuplicate);
-        }
-    for (int s = tid; s < S; s += nt) {
-        if (scnt[s] == 0) continue;
-        const int at = det_find(key, m, slot_id[s]);
-        if (at >= 0) det_slot[kidx[at]] = s;
-    }
-    __syncthreads();
-
-    // 4. new ids take free slots: the i-th new detection (detection order) gets the i-th free slot (slot order)
-    int n_free = 0, tot = 0;
-    for (int s0 = 0; s0 < S; s0 += nt) {
-        const int s = s0 + tid;
-        const bool fr = s < S && scnt[s] == 0;
-        const int r = block_rank<kThreads>(fr, n_free, &tot, wave_cnt);
-        if (fr) free_list[r] = s;
-        n_free += tot;
-    }
-    __syncthreads();
-    int n_new = 0;
-    for (int j0 = 0; j0 < m; j0 += nt) {
-        const int j = j0 + tid;
-        const bool nw = j < m && det_slot[j] == -1;
-        const int r = block_rank<kThreads>(nw, n_new, &tot, wave_cnt);
-        if (nw) {
-            if (r < n_free) det_slot[j] = free_list[r];
-            else {
-                det_slot[j] = -3;
-                atomicOr(&flags, kFlagOverflow);
-            }
-        }
-        n_new += tot;
-    }
-    __syncthreads();
+    // 2-4. every detection gets its slot (assign_slots); a slot is live while its ring holds a sample
+    assign_slots<kThreads>(key, kidx, det_slot, free_list, wave_cnt, &flags, m, n2, S, slot_id,
+                           [&](int s) { return scnt[s] != 0; });
 
     // 5. record this push's sample (time, rounded position) at the slot's write index; the ring entry it overwrites is
     //    outside what the search below reads (n_old <= R - 1), so the two need no barrier between them
@@ -192,7 +150,7 @@ __device__ __forceinline__ int track_push_timed_body(
     __syncthreads();
 
     // 7. the scene: the rule's members in ascending id order (the sorted detections), the first V of them
-    int c = 0;
+    int c = 0, tot = 0;
     for (int p0 = 0; p0 < m; p0 += nt) {
         const int p = p0 + tid;
         const int j = p < m ? kidx[p] : 0;
@@ -263,15 +221,7 @@ __device__ __forceinline__ int track_push_timed_body(
                 obs_abs[((int64_t)t * V + r) * 2 + 1] = y;
             });
     }
-    for (int e = np + tid; e < V; e += nt) {
-        out_ids[e] = -1;
-        seen[e] = 0;
-    }
-    for (int e = tid; e < T_obs * (V - np); e += nt) {
-        const int t = e / (V - np), r = np + e % (V - np);
-        obs_abs[((int64_t)t * V + r) * 2] = 0.0;
-        obs_abs[((int64_t)t * V + r) * 2 + 1] = 0.0;
-    }
+    pad_scene(obs_abs, out_ids, seen, T_obs, V, np);
     __syncthreads();
     if (tid == 0) {
         num_peds[0] = np;
@@ -294,7 +244,7 @@ __global__ __launch_bounds__(kPushThreads) void track_push_timed_kernel(
                                         rule, obs_abs, out_ids, num_peds, seen);
 }
 
-// One workgroup per stream, as track_push_stream: a stream not pushed keeps its state, its clock included
+// One workgroup per stream (push_stream): a stream not pushed keeps its state, its clock included
 template <int kThreads>
 __global__ __launch_bounds__(kThreads) void track_push_streams_timed_kernel(
     const int64_t *__restrict__ det_id, int64_t id_stride, const double *__restrict__ det_xy, int64_t xy_stride,
@@ -304,30 +254,15 @@ __global__ __launch_bounds__(kThreads) void track_push_streams_timed_kernel(
     int64_t *__restrict__ clock, int32_t *__restrict__ head_flags, int S, int R, int T_obs, double scale, int V,
     int64_t step, int64_t max_dt, TrackRule rule, double *__restrict__ obs_abs, int64_t *__restrict__ out_ids,
     int32_t *__restrict__ num_peds, int32_t *__restrict__ out_flags, int32_t *__restrict__ seen) {
-    const int b = blockIdx.x, tid = threadIdx.x;
-    double *obs = obs_abs + (int64_t)b * T_obs * V * 2;
-    int64_t *oid = out_ids + (int64_t)b * V;
-    int32_t *osn = seen + (int64_t)b * V;
-    if (pushed[b] == 0) {                                   // uniform over the block: no barrier is skipped halfway
-        for (int e = tid; e < V; e += kThreads) {
-            oid[e] = -1;
-            osn[e] = 0;
-        }
-        for (int e = tid; e < T_obs * V * 2; e += kThreads) obs[e] = 0.0;
-        if (tid == 0) {
-            num_peds[b] = 0;
-            if (out_flags) out_flags[b] = 0;
-        }
-        return;
-    }
-    int lo;
-    const int count = det_range(det_start, b, M_total, lo);
-    const int flags = track_push_timed_body<kThreads>(
-        det_id + lo * id_stride, id_stride, det_xy + lo * xy_stride, xy_stride, count, det_time[b], M_max, M2,
-        slot_id + (int64_t)b * S, t_ring + (int64_t)b * S * R, xy_ring + (int64_t)b * S * R * 2,
-        slot_head + (int64_t)b * S * 2, clock + 2 * b, head_flags + 2 * b, S, R, T_obs, scale, V, step, max_dt, rule,
-        obs, oid, num_peds + b, osn);
-    if (out_flags && tid == 0) out_flags[b] = flags;
+    push_stream(det_start, pushed, M_total, T_obs, V, obs_abs, out_ids, seen, num_peds, out_flags,
+                [&](int lo, int count, double *obs, int64_t *oid, int32_t *osn, int32_t *peds) {
+                    const int64_t b = blockIdx.x;
+                    return track_push_timed_body<kThreads>(
+                        det_id + lo * id_stride, id_stride, det_xy + lo * xy_stride, xy_stride, count, det_time[b],
+                        M_max, M2, slot_id + b * S, t_ring + b * S * R, xy_ring + b * S * R * 2, slot_head + b * S * 2,
+                        clock + 2 * b, head_flags + 2 * b, S, R, T_obs, scale, V, step, max_dt, rule, obs, oid, peds,
+                        osn);
+                });
 }
 
 // dynamic LDS of a timed push: the sort arrays, det_slot and det_rank, four words per slot, one byte per
@@ -386,29 +321,21 @@ int stg_track_push_streams_timed(const int64_t *det_id, int64_t id_stride, const
                                  double *obs_abs, int64_t *out_ids, int32_t *num_peds, int32_t *out_flags,
                                  int32_t *seen, int block_threads, void *stream) {
     const char *what = "stg_track_push_streams_timed";
-    STG_REQUIRE(NS >= 1 && NS <= STG_TRACK_MAX_STREAMS && M_total >= 0 && M_total <= STG_TRACK_MAX_TOTAL_DETECTIONS &&
-                    id_stride >= 1 && xy_stride >= 2,
-                STG_EINVAL, "%s: bad sizes NS=%d M_total=%d strides %lld/%lld", what, NS, M_total, (long long)id_stride,
-                (long long)xy_stride);
-    const int rc = stg::timed_args(what, M_max, S, R, T_obs, V, step, max_dt, min_seen, max_gap);
+    int rc = stg::push_streams_args(what, NS, M_total, id_stride, xy_stride, block_threads);
+    if (rc == STG_OK) rc = stg::timed_args(what, M_max, S, R, T_obs, V, step, max_dt, min_seen, max_gap);
     if (rc != STG_OK) return rc;
-    if (block_threads == 0) block_threads = stg::kStreamThreads;
-    STG_REQUIRE(block_threads == 64 || block_threads == 256 || block_threads == 1024, STG_EINVAL,
-                "%s: block_threads=%d (0, 64, 256 or 1024)", what, block_threads);
     STG_REQUIRE(det_id && det_xy && det_start && pushed && det_time && slot_id && t_ring && xy_ring && slot_head &&
                     clock && head_flags && obs_abs && out_ids && num_peds && seen,
                 STG_EINVAL, "%s: null pointer", what);
     const int m2 = stg::det_sort_n(M_max);
     const stg::Launch l{what, dim3(NS), dim3(block_threads), stg::push_timed_lds(M_max, m2, S, T_obs),
                         stg::as_stream(stream), 64 * 1024};
-    auto go = [&](auto kernel) {
-        return stg::launch(l, kernel, det_id, id_stride, det_xy, xy_stride, M_total, det_start, pushed, det_time, M_max,
-                           m2, slot_id, t_ring, xy_ring, slot_head, clock, head_flags, S, R, T_obs, scale, V, step,
-                           max_dt, stg::TrackRule{min_seen, max_gap}, obs_abs, out_ids, num_peds, out_flags, seen);
-    };
-    if (block_threads == 64) return go(stg::track_push_streams_timed_kernel<64>);
-    if (block_threads == 256) return go(stg::track_push_streams_timed_kernel<256>);
-    return go(stg::track_push_streams_timed_kernel<1024>);
+    return stg::with_stream_threads(block_threads, [&](auto kt) {
+        return stg::launch(l, stg::track_push_streams_timed_kernel<kt()>, det_id, id_stride, det_xy, xy_stride, M_total,
+                           det_start, pushed, det_time, M_max, m2, slot_id, t_ring, xy_ring, slot_head, clock, head_flags,
+                           S, R, T_obs, scale, V, step, max_dt, stg::TrackRule{min_seen, max_gap}, obs_abs, out_ids,
+                           num_peds, out_flags, seen);
+    });
 }
 
 }  // extern "C"

@@ -1,7 +1,12 @@
 // track_rule: what the live pushes share (frames.hip: one push = one model step; frames_time.hip: timestamped pushes,
 // DESIGN.md 5.20) beyond the detection sort of detections.hpp -- the workgroup sizes and flags of a push, the block-wide
-// rank, and TrackRule, the rule for partially observed tracks, which the recording kernels use too.
+// rank, TrackRule, the rule for partially observed tracks, which the recording kernels use too, and the
+// parts of a push that do not depend on its state: the slot assignment, the padding of a scene, the
+// per-stream wrapper and, on the host, the stream checks and the workgroup-size dispatch of the _streams entry points.
+// Device helpers without state, as in detections.hpp: the caller owns the LDS arrays and its thread geometry.
 #pragma once
+#include <type_traits>
+
 #include "common.hpp"
 #include "detections.hpp"
 
@@ -105,11 +110,124 @@ __device__ __forceinline__ int block_rank(bool flag, int base, int *total, int *
     return base + before + lanes_below(m);
 }
 
+// ---- the parts of a push that do not depend on its state ------------------------------------------------------------
+// The slot assignment: sort the m detections by (id, detection index), then give every detection j its det_slot[j]
+// (-1 on entry).  A live slot keeps its id's detection; THE i-TH NEW DETECTION IN DETECTION ORDER TAKES THE i-TH FREE
+// SLOT IN SLOT ORDER.  A repeated id: the first detection wins, the others get -2 and *flags DUPLICATE.  No free slot:
+// -3 and *flags OVERFLOW.  live(s): slot s holds a track (the caller's notion: a presence mask, a sample count); its
+// id is slot_id[s].  key / kidx (n2 entries, loaded: det_load), det_slot (m), free_list (S), wave_cnt and flags are
+// the caller's LDS.  Every thread of the kThreads calls it behind a barrier after det_load; it ends on a barrier.
+template <int kThreads, class Live>
+__device__ __forceinline__ void assign_slots(int64_t *key, int32_t *kidx, int32_t *det_slot, int32_t *free_list,
+                                             int *wave_cnt, int *flags, int m, int n2, int S, const int64_t *slot_id,
+                                             Live live) {
+    const int tid = threadIdx.x, nt = blockDim.x;
+    det_sort(key, kidx, n2, tid, nt);
+    for (int p = tid; p < m; p += nt)
+        if (p > 0 && key[p] == key[p - 1]) {
+            det_slot[kidx[p]] = -2;
+            atomicOr(flags, kFlagDuplicate);
+        }
+    for (int s = tid; s < S; s += nt) {
+        if (!live(s)) continue;
+        const int at = det_find(key, m, slot_id[s]);         // (the winner)
+        if (at >= 0) det_slot[kidx[at]] = s;
+    }
+    __syncthreads();
+    int n_free = 0, tot = 0;
+    for (int s0 = 0; s0 < S; s0 += nt) {
+        const int s = s0 + tid;
+        const bool fr = s < S && !live(s);
+        const int r = block_rank<kThreads>(fr, n_free, &tot, wave_cnt);
+        if (fr) free_list[r] = s;
+        n_free += tot;
+    }
+    __syncthreads();
+    int n_new = 0;
+    for (int j0 = 0; j0 < m; j0 += nt) {
+        const int j = j0 + tid;
+        const bool nw = j < m && det_slot[j] == -1;
+        const int r = block_rank<kThreads>(nw, n_new, &tot, wave_cnt);
+        if (nw) {
+            if (r < n_free) det_slot[j] = free_list[r];
+            else {
+                det_slot[j] = -3;
+                atomicOr(flags, kFlagOverflow);
+            }
+        }
+        n_new += tot;
+    }
+    __syncthreads();
+}
+
+// The padding of one scene obs (T_obs,V,2), oid (V), osn (V, or null): slots [from, V) get id -1, seen 0 and zero
+// positions; from = 0 is the whole empty scene.  num_peds and the flags are the caller's.  No barrier.
+__device__ __forceinline__ void pad_scene(double *obs, int64_t *oid, int32_t *osn, int T_obs, int V, int from) {
+    const int tid = threadIdx.x, nt = blockDim.x;
+    for (int e = from + tid; e < V; e += nt) {
+        oid[e] = -1;
+        if (osn) osn[e] = 0;
+    }
+    for (int e = tid; e < T_obs * (V - from); e += nt) {
+        const int t = e / (V - from), r = from + e % (V - from);
+        obs[((int64_t)t * V + r) * 2] = 0.0;
+        obs[((int64_t)t * V + r) * 2 + 1] = 0.0;
+    }
+}
+
+// One workgroup per stream: stream b = blockIdx.x pushes detections det_start[b] .. det_start[b+1]-1 (clamped to
+// [0, M_total)) when pushed[b] != 0: flags = body(first, count, obs, oid, osn, num_peds + b) on its own slices of the
+// (NS, ...) outputs (seen may be null, osn then too); the body slices its state by b.  Otherwise no state is touched
+// and the scene is the empty one.
+template <class Body>
+__device__ __forceinline__ void push_stream(const int32_t *__restrict__ det_start, const int32_t *__restrict__ pushed,
+                                            int M_total, int T_obs, int V, double *__restrict__ obs_abs,
+                                            int64_t *__restrict__ out_ids, int32_t *__restrict__ seen,
+                                            int32_t *__restrict__ num_peds, int32_t *__restrict__ out_flags, Body body) {
+    const int b = blockIdx.x;
+    double *obs = obs_abs + (int64_t)b * T_obs * V * 2;
+    int64_t *oid = out_ids + (int64_t)b * V;
+    int32_t *osn = seen ? seen + (int64_t)b * V : nullptr;
+    int flags = 0;
+    if (pushed[b] == 0) {                                   // uniform over the block: no barrier is skipped halfway
+        pad_scene(obs, oid, osn, T_obs, V, 0);
+        if (threadIdx.x == 0) num_peds[b] = 0;
+    } else {
+        int lo;
+        const int count = det_range(det_start, b, M_total, lo);
+        flags = body(lo, count, obs, oid, osn, num_peds + b);
+    }
+    if (out_flags && threadIdx.x == 0) out_flags[b] = flags;
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------
 // the range check of a rule and its window, in an entry point that names them T_obs, min_seen and max_gap
 #define STG_REQUIRE_RULE(what)                                                                                        \
     STG_REQUIRE(T_obs >= 2 && T_obs <= 32 && min_seen >= 2 && min_seen <= T_obs && max_gap >= 0 &&                    \
                     max_gap <= T_obs - 2,                                                                             \
                 STG_EINVAL, "%s: min_seen=%d not in [2, T_obs=%d] or max_gap=%d not in [0, T_obs - 2]", what, min_seen, \
                 T_obs, max_gap)
+
+// What the _streams pushes check of their streams, under the entry point's name `what`, and their workgroup size:
+// block_threads = 0 becomes kStreamThreads
+static inline int push_streams_args(const char *what, int NS, int M_total, int64_t id_stride, int64_t xy_stride,
+                                    int &block_threads) {
+    STG_REQUIRE(NS >= 1 && NS <= STG_TRACK_MAX_STREAMS && M_total >= 0 && M_total <= STG_TRACK_MAX_TOTAL_DETECTIONS &&
+                    id_stride >= 1 && xy_stride >= 2,
+                STG_EINVAL, "%s: bad sizes NS=%d M_total=%d strides %lld/%lld", what, NS, M_total, (long long)id_stride,
+                (long long)xy_stride);
+    if (block_threads == 0) block_threads = kStreamThreads;
+    STG_REQUIRE(block_threads == 64 || block_threads == 256 || block_threads == 1024, STG_EINVAL,
+                "%s: block_threads=%d (0, 64, 256 or 1024)", what, block_threads);
+    return STG_OK;
+}
+
+// ... and the instantiation that size picks: go(std::integral_constant<int, kThreads>) for the checked block_threads
+template <class Go>
+static inline int with_stream_threads(int block_threads, Go go) {
+    if (block_threads == 64) return go(std::integral_constant<int, 64>{});
+    if (block_threads == 256) return go(std::integral_constant<int, 256>{});
+    return go(std::integral_constant<int, 1024>{});
+}
 
 }  // namespace stg

@@ -1,6 +1,9 @@
 """Inputs and scene assertions for the tests of the live path (test_gpu_frames.py, test_gpu_frames_streams.py,
-test_gpu_frames_fill.py, test_gpu_score.py, test_gpu_detections.py): the committed recordings as rows and as pushes,
-the golden models, a schedule of pushes over many streams, and the bit-for-bit comparison of one padded scene."""
+test_gpu_frames_fill.py, test_gpu_frames_time.py, test_gpu_score.py, test_gpu_detections.py, test_gpu_push_slots.py):
+the committed recordings as rows and as pushes, the golden models, a schedule of pushes over many streams, a sparse
+recording, the feed of the slot-table tests, the C push driven directly, and the bit-for-bit comparison of one padded
+scene."""
+import ctypes
 import os
 
 import numpy as np
@@ -43,6 +46,29 @@ def _xy(gen, m):
     return gen.uniform(-20, 20, size=(m, 2))            # more decimals than the rounding keeps
 
 
+def _sparse_rows():
+    """40 frames, 30 ids, each present in a frame with probability 0.7."""
+    gen = np.random.default_rng(12)
+    rows = np.array([(10.0 * t, float(k)) for t in range(40) for k in range(100, 130) if gen.random() < 0.7])
+    return np.concatenate([rows, gen.uniform(-20, 20, size=(len(rows), 2))], axis=1)
+
+
+def _slot_feed():
+    """60 pushes (ids, xy) over 120 ids, half of them above 2^33, for a state of 70 slots and 80 detections a push: the
+    first n of a permutation, n in [84, 90] when f % 7 == 3 (TRUNCATED, OVERFLOW), in [0, 3] when f % 7 is 1 or 2 (the
+    slots run free), else in [4, 35]; when f % 4 == 0 the first id once more (DUPLICATE).  tests/test_push_slots_cpu.py
+    holds what the feed has to reach."""
+    gen = np.random.default_rng(7)
+    ids = np.array([(3 * i + 11) | ((i % 2) << 33) for i in range(120)], np.int64)
+    feed = []
+    for f in range(60):
+        lo, hi = (84, 90) if f % 7 == 3 else (0, 3) if f % 7 in (1, 2) else (4, 35)
+        n = int(gen.integers(lo, hi + 1))
+        p = gen.permutation(ids)[:n]
+        feed.append(np.concatenate([p, p[:1]]) if f % 4 == 0 else p)
+    return [(p, _xy(gen, len(p))) for p in feed]
+
+
 class Schedule:
     """Stream s pushes the frames of its recording in order from tick start[s] on; with skip an odd stream skips the
     ticks divisible by s + 3 (its next frame waits for the next tick); a finished recording is not pushed."""
@@ -70,3 +96,48 @@ def _assert_scene(ids, peds, obs, ref_ids, ref_obs, what, seen=None, ref_seen=No
         assert np.array_equal(seen[:c], ref_seen) and not np.any(seen[c:]), what
     assert np.array_equal(obs[:, :c], ref_obs), (what, np.argwhere(obs[:, :c] != ref_obs)[:4])
     assert not np.any(obs[:, c:]), what
+
+
+class _CPush:
+    """stg_track_push_timed (time=(step, max_dt, R)) or stg_track_push_rule driven directly: the caller's state and
+    staging tensors.  The outputs are pre-filled with 7s: the kernel writes every element."""
+
+    def __init__(self, dev, rule, v, s, m_max, t_obs=8, decimals=4, time=None):
+        from social_stgcnn_amd import frames
+        self.dev, self.rule, self.v, self.s, self.m_max, self.t, self.time = dev, rule, v, s, m_max, t_obs, time
+        self.scale = frames._scale(decimals)
+        z = lambda shape, dt: torch.zeros(shape, device=dev, dtype=dt)      # noqa: E731
+        self.slot_id = torch.full((s,), -1, device=dev, dtype=torch.int64)
+        self.head_flags = z(2, torch.int32)
+        if time is None:
+            self.state = (self.slot_id, z(s, torch.int32), z((t_obs, s, 2), torch.float64), self.head_flags)
+        else:
+            r = time[2]
+            self.state = (self.slot_id, z((s, r), torch.int64), z((s, r, 2), torch.float64), z((s, 2), torch.int32),
+                          z(2, torch.int64), self.head_flags)
+
+    def push(self, ids, xy, t=None, count=None):
+        from social_stgcnn_amd._lib import check, lib, ptr, stream_ptr
+        dev, m = self.dev, len(ids)
+        det_id = torch.zeros(max(m, self.m_max), device=dev, dtype=torch.int64)
+        det_xy = torch.zeros((max(m, self.m_max), 2), device=dev, dtype=torch.float64)
+        det_id[:m] = torch.from_numpy(np.asarray(ids, np.int64)).to(dev)
+        det_xy[:m] = torch.from_numpy(np.asarray(xy, np.float64).reshape(-1, 2)).to(dev)
+        cnt = torch.tensor([m if count is None else count], device=dev, dtype=torch.int32)
+        obs = torch.full((self.t, self.v, 2), 7.0, device=dev, dtype=torch.float64)
+        out_ids = torch.full((self.v,), 7, device=dev, dtype=torch.int64)
+        peds = torch.full((1,), 7, device=dev, dtype=torch.int32)
+        seen = torch.full((self.v,), 7, device=dev, dtype=torch.int32)
+        outs = (ptr(obs), ptr(out_ids), ptr(peds), ptr(seen), stream_ptr())
+        if self.time is None:
+            check(lib().stg_track_push_rule(ptr(det_id), ptr(det_xy), ptr(cnt), self.m_max, *map(ptr, self.state),
+                                            self.s, self.t, ctypes.c_double(self.scale), self.v, *self.rule, *outs),
+                  "stg_track_push_rule")
+        else:
+            when = torch.tensor([t], device=dev, dtype=torch.int64)
+            check(lib().stg_track_push_timed(ptr(det_id), ptr(det_xy), ptr(cnt), ptr(when), self.m_max,
+                                             *map(ptr, self.state), self.s, self.time[2], self.t,
+                                             ctypes.c_double(self.scale), self.v, self.time[0], self.time[1],
+                                             *self.rule, *outs), "stg_track_push_timed")
+        return (out_ids.cpu().numpy(), int(peds.item()), obs.cpu().numpy(), seen.cpu().numpy(),
+                int(self.head_flags[1].item()))

@@ -5,7 +5,6 @@ the recording kernels and the push-by-push statement, with its edge cases; Strea
 FramePredictors; the strict rule through the new kernels against the strict kernels; predictions, risk counts and the
 command end to end; and the accuracy of a history cut to two frames against the full one on the device."""
 import argparse
-import ctypes
 import os
 
 import numpy as np
@@ -14,7 +13,7 @@ import torch
 
 import frames_fill_np
 import frames_np
-from live_inputs import DATA, _assert_scene, _model, _pushes, _rows
+from live_inputs import DATA, _assert_scene, _CPush, _model, _pushes, _rows, _sparse_rows
 
 pytestmark = pytest.mark.gpu
 ETH = os.path.join(DATA, "eth_test", "biwi_eth.txt")
@@ -41,13 +40,6 @@ def _pattern_rows():
     gen = np.random.default_rng(11)
     rows = [(10.0 * t, float(k)) for t in range(8) for k in range(1, 256) if (k >> t) & 1]
     rows = np.array(rows)
-    return np.concatenate([rows, gen.uniform(-20, 20, size=(len(rows), 2))], axis=1)
-
-
-def _sparse_rows():
-    """40 frames, 30 ids, each present in a frame with probability 0.7."""
-    gen = np.random.default_rng(12)
-    rows = np.array([(10.0 * t, float(k)) for t in range(40) for k in range(100, 130) if gen.random() < 0.7])
     return np.concatenate([rows, gen.uniform(-20, 20, size=(len(rows), 2))], axis=1)
 
 
@@ -111,38 +103,6 @@ def test_every_presence_pattern_through_fill_tracks(dev, decimals):
 
 
 # ---- 2. live equals recording ------------------------------------------------------------------------------------------
-class _CPush:
-    """stg_track_push_rule driven directly: the caller's state and staging tensors."""
-
-    def __init__(self, dev, rule, v, s=512, m_max=256, t_obs=8, decimals=4):
-        from social_stgcnn_amd import frames
-        self.dev, self.rule, self.v, self.s, self.m_max, self.t = dev, rule, v, s, m_max, t_obs
-        self.scale = frames._scale(decimals)
-        self.slot_id = torch.full((s,), -1, device=dev, dtype=torch.int64)
-        self.mask = torch.zeros(s, device=dev, dtype=torch.int32)
-        self.ring = torch.zeros((t_obs, s, 2), device=dev, dtype=torch.float64)
-        self.head_flags = torch.zeros(2, device=dev, dtype=torch.int32)
-
-    def push(self, ids, xy):
-        from social_stgcnn_amd._lib import check, lib, ptr, stream_ptr
-        dev, m = self.dev, len(ids)
-        det_id = torch.zeros(self.m_max, device=dev, dtype=torch.int64)
-        det_xy = torch.zeros((self.m_max, 2), device=dev, dtype=torch.float64)
-        det_id[:m] = torch.from_numpy(np.asarray(ids, np.int64)).to(dev)
-        det_xy[:m] = torch.from_numpy(np.asarray(xy, np.float64).reshape(-1, 2)).to(dev)
-        count = torch.tensor([m], device=dev, dtype=torch.int32)
-        obs = torch.full((self.t, self.v, 2), 7.0, device=dev, dtype=torch.float64)
-        out_ids = torch.full((self.v,), 7, device=dev, dtype=torch.int64)
-        peds = torch.full((1,), 7, device=dev, dtype=torch.int32)
-        seen = torch.full((self.v,), 7, device=dev, dtype=torch.int32)
-        check(lib().stg_track_push_rule(ptr(det_id), ptr(det_xy), ptr(count), self.m_max, ptr(self.slot_id),
-                                        ptr(self.mask), ptr(self.ring), ptr(self.head_flags), self.s, self.t,
-                                        ctypes.c_double(self.scale), self.v, self.rule[0], self.rule[1], ptr(obs),
-                                        ptr(out_ids), ptr(peds), ptr(seen), stream_ptr()), "stg_track_push_rule")
-        return (out_ids.cpu().numpy(), int(peds.item()), obs.cpu().numpy(), seen.cpu().numpy(),
-                int(self.head_flags[1].item()))
-
-
 @pytest.mark.parametrize("which,rule,decimals", [("pattern", (2, 6), None), ("pattern", (3, 1), 4),
                                                  ("sparse", (2, 2), 4), ("sparse", (5, 2), None)])
 def test_live_pushes_equal_the_recording_scenes(dev, model, which, rule, decimals):
@@ -158,7 +118,7 @@ def test_live_pushes_equal_the_recording_scenes(dev, model, which, rule, decimal
     r_ids, r_peds, r_obs, r_seen = _host_scenes(sc)
     fnums = np.unique(rows[:, 0])
     ref = frames_fill_np.StreamModelRule(8, rule[0], rule[1], max_peds=v, decimals=decimals)
-    c_push = _CPush(dev, rule, v, decimals=decimals)
+    c_push = _CPush(dev, rule, v, 512, 256, decimals=decimals)
     vp = 128
     assert max(len(ids) for ids, _ in _pushes(rows)) <= vp
     kw = dict(k=2, capacity=512, max_peds=vp, max_detections=256, decimals=decimals, tracks=tr)

@@ -5,14 +5,13 @@ max_dt, TOO_MANY, OVERFLOW, a repeated id, TRUNCATED); a push whose time does no
 times through FramePredictor, eager and as ONE captured graph; StreamsPredictor against lone FramePredictors; risk
 counts, reset(), capture and the command end to end."""
 import argparse
-import ctypes
 
 import numpy as np
 import pytest
 import torch
 
 from frames_time_np import DUPLICATE, OVERFLOW, TIME_ORDER, TOO_MANY, TRUNCATED, StreamModelTimed
-from live_inputs import _assert_scene, _model, _pushes, _rows
+from live_inputs import _assert_scene, _CPush, _model, _pushes, _rows, _sparse_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -25,59 +24,6 @@ def dev():
 @pytest.fixture(scope="module")
 def model(dev):
     return _model("eth", dev)
-
-
-def _sparse_rows():
-    """40 frames, 30 ids, each present in a frame with probability 0.7 (the recording of tests/test_gpu_frames_fill.py:
-    the same generator and seed)."""
-    gen = np.random.default_rng(12)
-    rows = np.array([(10.0 * t, float(k)) for t in range(40) for k in range(100, 130) if gen.random() < 0.7])
-    return np.concatenate([rows, gen.uniform(-20, 20, size=(len(rows), 2))], axis=1)
-
-
-class _CPush:
-    """stg_track_push_timed (time=(step, max_dt, R)) or stg_track_push_rule driven directly: the caller's state and
-    staging tensors.  The outputs are pre-filled with 7s: the kernel writes every element."""
-
-    def __init__(self, dev, rule, v, s, m_max, t_obs=8, decimals=4, time=None):
-        from social_stgcnn_amd import frames
-        self.dev, self.rule, self.v, self.s, self.m_max, self.t, self.time = dev, rule, v, s, m_max, t_obs, time
-        self.scale = frames._scale(decimals)
-        z = lambda shape, dt: torch.zeros(shape, device=dev, dtype=dt)      # noqa: E731
-        self.slot_id = torch.full((s,), -1, device=dev, dtype=torch.int64)
-        self.head_flags = z(2, torch.int32)
-        if time is None:
-            self.state = (self.slot_id, z(s, torch.int32), z((t_obs, s, 2), torch.float64), self.head_flags)
-        else:
-            r = time[2]
-            self.state = (self.slot_id, z((s, r), torch.int64), z((s, r, 2), torch.float64), z((s, 2), torch.int32),
-                          z(2, torch.int64), self.head_flags)
-
-    def push(self, ids, xy, t=None, count=None):
-        from social_stgcnn_amd._lib import check, lib, ptr, stream_ptr
-        dev, m = self.dev, len(ids)
-        det_id = torch.zeros(max(m, self.m_max), device=dev, dtype=torch.int64)
-        det_xy = torch.zeros((max(m, self.m_max), 2), device=dev, dtype=torch.float64)
-        det_id[:m] = torch.from_numpy(np.asarray(ids, np.int64)).to(dev)
-        det_xy[:m] = torch.from_numpy(np.asarray(xy, np.float64).reshape(-1, 2)).to(dev)
-        cnt = torch.tensor([m if count is None else count], device=dev, dtype=torch.int32)
-        obs = torch.full((self.t, self.v, 2), 7.0, device=dev, dtype=torch.float64)
-        out_ids = torch.full((self.v,), 7, device=dev, dtype=torch.int64)
-        peds = torch.full((1,), 7, device=dev, dtype=torch.int32)
-        seen = torch.full((self.v,), 7, device=dev, dtype=torch.int32)
-        outs = (ptr(obs), ptr(out_ids), ptr(peds), ptr(seen), stream_ptr())
-        if self.time is None:
-            check(lib().stg_track_push_rule(ptr(det_id), ptr(det_xy), ptr(cnt), self.m_max, *map(ptr, self.state),
-                                            self.s, self.t, ctypes.c_double(self.scale), self.v, *self.rule, *outs),
-                  "stg_track_push_rule")
-        else:
-            when = torch.tensor([t], device=dev, dtype=torch.int64)
-            check(lib().stg_track_push_timed(ptr(det_id), ptr(det_xy), ptr(cnt), ptr(when), self.m_max,
-                                             *map(ptr, self.state), self.s, self.time[2], self.t,
-                                             ctypes.c_double(self.scale), self.v, self.time[0], self.time[1],
-                                             *self.rule, *outs), "stg_track_push_timed")
-        return (out_ids.cpu().numpy(), int(peds.item()), obs.cpu().numpy(), seen.cpu().numpy(),
-                int(self.head_flags[1].item()))
 
 
 # ---- 1. one push per step: the rule kernel ---------------------------------------------------------------------------
