@@ -124,6 +124,8 @@ typedef struct {
 #define STG_OPT_F32_MFMA 16   /* run the TXP convolutions and the weight-gradient GEMM on v_mfma_f32_16x16x4_f32 (the round-1 kernels)
                                * where the default uses v_mfma_f32_16x16x32_bf16 with exact three-piece operands (V <= 32, fp32
                                * storage): same accuracy class, for A/B measurements                                            */
+#define STG_OPT_SEPARATE_FB 32 /* stg_model_step: run the forward and the backward scene kernels as two launches also where
+                               * one launch serves both (same results bit for bit: A/B measurements and tests)           */
 #define STG_OPT_WAVE_PATH 4   /* keep the wave-per-scene kernels for small batches too (default: batches of fewer than  */
                               /* 288 scenes of <= 40 pedestrians run the workgroup kernels, several waves per scene)     */
 
@@ -145,6 +147,10 @@ int64_t stg_model_fwd_scratch_floats(const stg_model_desc *d, int N, int V);
 /* Scratch floats stg_model_bwd needs (partial-gradient slab rows of its kernels + the dz hand-off
  * between the input-gradient kernel and the weight-gradient kernel). */
 int64_t stg_model_bwd_scratch_floats(const stg_model_desc *d, int N, int V);
+/* Diagnostic build with STG_STAMPS=1: where in the forward's / the backward's scratch buffer (in floats) the scene
+ * kernels leave their N x 16 64-bit time stamps.  STG_EUNSUPPORTED where none are written (every other build).  */
+int64_t stg_model_fwd_stamps_offset(const stg_model_desc *d, int N, int V);
+int64_t stg_model_bwd_stamps_offset(const stg_model_desc *d, int N, int V);
 
 /* x (N,c_in,t_obs,V) strided; adj (N,t_obs,V,V), batch stride a_sn (0 = shared);
  * y: (N,c_out,t_pred,V) when n_txpcnn>0, else the block output (N,c_out,t_obs,V).
@@ -199,6 +205,22 @@ int stg_model_bwd_step(const stg_model_desc *d, const float *params, const float
                        int N, int V, const float *y, const float *target, const float *weights, float *losses,
                        const float *ws, float *scratch, float *grad_params, const stg_step_tail *tail, void **events,
                        int n_events, void *stream);
+/* One single-rank training step without clipping in ONE call: stg_model_fwd (training: ws and stats as there) followed by
+ * stg_model_bwd_step on its output, with the arguments of both -- y is written by the forward and read by the backward,
+ * fwd_scratch / bwd_scratch are the two calls' scratch buffers, fwd_events / bwd_events their event lists.  Results
+ * are those of the two calls bit for bit.  Where both passes run the scene kernels compiled for the canonical model on
+ * uniform scenes of 32 pedestrians (one st_gcn block, five TXP layers, V = 32, num_peds NULL, a batch of more than 1024
+ * scenes), the forward and the backward scene kernels are ONE launch: a wave runs the backward of its scene straight
+ * behind the forward.  The step is then four launches, not five; bwd_events[1] closes the interval of that launch and
+ * the forward scene kernel's own interval (fwd_events[1] .. fwd_events[2]) is empty.  STG_OPT_SEPARATE_FB in the
+ * descriptor keeps the two launches; every other batch runs them as the two calls do.  STG_EUNSUPPORTED, nothing
+ * launched, where stg_model_bwd_step is (STG_OPT_SPLIT_BF16, no TXP-CNN, N == 0).                                   */
+int stg_model_step(const stg_model_desc *d, const float *params, const float *buffers, const float *x, int64_t x_sn,
+                   int64_t x_sc, int64_t x_st, int64_t x_sv, const float *adj, int64_t a_sn, const int32_t *num_peds,
+                   int N, int V, float *y, float *ws, float *stats, float *fwd_scratch, const float *target,
+                   const float *weights, float *losses, float *bwd_scratch, float *grad_params,
+                   const stg_step_tail *tail, void **fwd_events, int n_fwd_events, void **bwd_events,
+                   int n_bwd_events, void *stream);
 /* Sequential-fold update of the BatchNorm running statistics with the per-scene statistics of a
  * batch, exactly as N successive reference forwards would (momentum update per scene,
  * model.py:114,123,140; SURVEY 7 'BatchNorm semantics').  Scenes with num_peds[n] == 0 are skipped.

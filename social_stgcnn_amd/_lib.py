@@ -17,7 +17,7 @@ CSRC = os.path.join(_HERE, "csrc")
 DIAG = os.environ.get("STG_USE_DIAG_LIB", "0") not in ("", "0")
 LIB_PATH = os.path.join(CSRC, "libstgcnn_hip_diag.so" if DIAG else "libstgcnn_hip.so")
 ABI_VERSION = 8
-OPT_WG_PATH, OPT_SPLIT_BF16, OPT_WAVE_PATH, OPT_BF16_STORE, OPT_F32_MFMA = 1, 2, 4, 8, 16
+OPT_WG_PATH, OPT_SPLIT_BF16, OPT_WAVE_PATH, OPT_BF16_STORE, OPT_F32_MFMA, OPT_SEPARATE_FB = 1, 2, 4, 8, 16, 32
 EUNSUPPORTED = -2            # STG_EUNSUPPORTED
 
 c_f = ctypes.c_void_p          # device pointers travel as void*
@@ -62,6 +62,8 @@ _SIGNATURES = {
     "stg_model_stat_floats": (c_l, [ctypes.POINTER(ModelDesc)]),
     "stg_model_fwd_scratch_floats": (c_l, [ctypes.POINTER(ModelDesc), c_i, c_i]),
     "stg_model_bwd_scratch_floats": (c_l, [ctypes.POINTER(ModelDesc), c_i, c_i]),
+    "stg_model_fwd_stamps_offset": (c_l, [ctypes.POINTER(ModelDesc), c_i, c_i]),
+    "stg_model_bwd_stamps_offset": (c_l, [ctypes.POINTER(ModelDesc), c_i, c_i]),
     "stg_model_fwd": (c_i, [ctypes.POINTER(ModelDesc), c_f, c_f, c_f, c_l, c_l, c_l, c_l, c_f, c_l, c_f, c_i, c_i,
                             c_f, c_f, c_f, c_f, ctypes.POINTER(ctypes.c_void_p), c_i, c_f]),
     "stg_model_bwd": (c_i, [ctypes.POINTER(ModelDesc), c_f, c_f, c_f, c_l, c_l, c_l, c_l, c_f, c_l, c_f, c_i, c_i,
@@ -71,6 +73,9 @@ _SIGNATURES = {
     "stg_model_bwd_step": (c_i, [ctypes.POINTER(ModelDesc), c_f, c_f, c_f, c_l, c_l, c_l, c_l, c_f, c_l, c_f, c_i, c_i,
                                  c_f, c_f, c_f, c_f, c_f, c_f, c_f, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), c_i,
                                  c_f]),
+    "stg_model_step": (c_i, [ctypes.POINTER(ModelDesc), c_f, c_f, c_f, c_l, c_l, c_l, c_l, c_f, c_l, c_f, c_i, c_i,
+                             c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, ctypes.c_void_p,
+                             ctypes.POINTER(ctypes.c_void_p), c_i, ctypes.POINTER(ctypes.c_void_p), c_i, c_f]),
     "stg_bn_fold": (c_i, [ctypes.POINTER(ModelDesc), c_f, c_f, c_i, c_f, ctypes.POINTER(ctypes.c_void_p), c_i, c_f]),
     "stg_nll_fwd": (c_i, [c_f, c_l, c_l, c_l, c_l, c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_f]),
     "stg_nll_bwd": (c_i, [c_f, c_f, c_i, c_i, c_i, c_f, c_f]),

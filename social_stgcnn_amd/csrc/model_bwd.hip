@@ -433,8 +433,9 @@ static int bwd_grid_small(const ModelLayout &L, int N, int V) {
 //          launches of a two-tier ragged run), or one per SCENE on the wave-per-scene path
 //   slab2  weight-gradient slab rows of K2          dzg  dz_l hand-off [N][L+1][dz_slot(V)]
 //   order  sorted scene list + tier offsets (int32)
+//   stamps [N][16] 64-bit cycle stamps of the backward scene kernel (diagnostic build with STG_STAMPS=1; else -1)
 struct BwdCarve {
-    int64_t rows, slab2, dzg, order, total;
+    int64_t rows, slab2, dzg, order, stamps, total;
 };
 static bool bwd_carve(const ModelLayout &L, const StepPath &path, int N, int V, BwdCarve *c, WgradGeom *wg) {
     const int g1 = bwd_grid(L, path, N, V);
@@ -455,6 +456,11 @@ static bool bwd_carve(const ModelLayout &L, const StepPath &path, int N, int V, 
     }
     c->order = fl;
     c->total = fl + order_floats(N, V);
+    c->stamps = -1;
+    if (diag_env("STG_STAMPS", 0) != 0) {
+        c->stamps = c->total;
+        c->total += (int64_t)N * 32;
+    }
     return true;
 }
 
@@ -472,15 +478,29 @@ int64_t stg_model_bwd_scratch_floats(const stg_model_desc *d, int N, int V) {
     if (!stg::bwd_carve(l, stg::choose_path(l, N, V), N, V, &c, &wg)) return stg::fail(STG_ELDS, "stg_model_bwd: V=%d does not fit the LDS of one CU", V);
     return c.total;
 }
+int64_t stg_model_bwd_stamps_offset(const stg_model_desc *d, int N, int V) {
+    stg::ModelLayout l;
+    const int rc = stg::make_layout(d, &l);
+    if (rc != STG_OK) return rc;
+    if (N <= 0 || V <= 0) return stg::fail(STG_EINVAL, "stg_model_bwd_stamps_offset: N=%d V=%d", N, V);
+    stg::BwdCarve c;
+    stg::WgradGeom wg{};
+    if (!stg::bwd_carve(l, stg::choose_path(l, N, V), N, V, &c, &wg)) return stg::fail(STG_ELDS, "stg_model_bwd: V=%d does not fit the LDS of one CU", V);
+    return c.stamps >= 0 ? c.stamps : STG_EUNSUPPORTED;
+}
+
+}  // extern "C"
+
+namespace stg {
 
 // dy = dV_pred, or (nll_target != null) V_pred itself: the wave-per-scene backward then computes the loss gradient in
-// its input stage and writes the per-scene losses (stg_model_bwd_nll)
-static int model_bwd_impl(const stg_model_desc *d, const float *params, const float *buffers, const float *x, int64_t x_sn,
-                          int64_t x_sc, int64_t x_st, int64_t x_sv, const float *adj, int64_t a_sn,
-                          const int32_t *num_peds, int N, int V, const float *dy, const float *nll_target,
-                          const float *nll_weights, float *nll_losses, const stg_step_tail *tail, const float *ws,
-                          float *scratch, float *grad_params, float *dx, void **events, int n_events, void *stream) {
-    using namespace stg;
+// its input stage and writes the per-scene losses (stg_model_bwd_nll).  `deferred` (stg_model_step): the scene launch
+// the forward left to this one -- both run as one launch.
+int model_bwd_impl(const stg_model_desc *d, const float *params, const float *buffers, const float *x, int64_t x_sn,
+                   int64_t x_sc, int64_t x_st, int64_t x_sv, const float *adj, int64_t a_sn, const int32_t *num_peds,
+                   int N, int V, const float *dy, const float *nll_target, const float *nll_weights, float *nll_losses,
+                   const stg_step_tail *tail, const float *ws, float *scratch, float *grad_params, float *dx,
+                   void **events, int n_events, void *stream, const TxpFwdArgs *deferred) {
     BwdArgs a{};
     const int rc = make_layout(d, &a.lay);
     if (rc != STG_OK) return rc;
@@ -553,10 +573,14 @@ static int model_bwd_impl(const stg_model_desc *d, const float *params, const fl
         t.split_bf16 = (L.flags & STG_OPT_SPLIT_BF16) ? 1 : 0;
         t.stagger = diag_env("STG_STAGGER_B", 0);
         if (wt.wp >= 0) t.wp = reinterpret_cast<const unsigned *>(ws_end + wt.wp);
-        const int rcw = launch_scene_bwd(path, t, st);
+        if (cv.stamps >= 0) t.stamps = reinterpret_cast<unsigned long long *>(scratch + cv.stamps);
+        STG_REQUIRE(!deferred || step_one_launch(L, path, num_peds, N, V), STG_EINVAL,
+                    "stg_model_bwd: a deferred scene launch outside the one-launch step");
+        const int rcw = deferred ? launch_scene_step(*deferred, t, st) : launch_scene_bwd(path, t, st);
         if (rcw != STG_OK) return rcw;
         slab_rows = N;
     } else {
+        STG_REQUIRE(!deferred, STG_EINVAL, "stg_model_bwd: a deferred scene launch outside the one-launch step");
         const int waves = bwd_waves(path, V);
         const size_t lds = bwd_lds_bytes(L, V, waves);
         STG_REQUIRE(lds <= (size_t)kLdsBytes, STG_ELDS, "stg_model_bwd: V=%d needs %zu bytes of LDS (> %d)", V, lds,
@@ -635,12 +659,18 @@ static int model_bwd_impl(const stg_model_desc *d, const float *params, const fl
     return STG_OK;
 }
 
+}  // namespace stg
+
+extern "C" {
+
+using stg::model_bwd_impl;
+
 int stg_model_bwd(const stg_model_desc *d, const float *params, const float *buffers, const float *x, int64_t x_sn,
                   int64_t x_sc, int64_t x_st, int64_t x_sv, const float *adj, int64_t a_sn, const int32_t *num_peds,
                   int N, int V, const float *dy, const float *ws, float *scratch, float *grad_params, float *dx,
                   void **events, int n_events, void *stream) {
     return model_bwd_impl(d, params, buffers, x, x_sn, x_sc, x_st, x_sv, adj, a_sn, num_peds, N, V, dy, nullptr, nullptr,
-                          nullptr, nullptr, ws, scratch, grad_params, dx, events, n_events, stream);
+                          nullptr, nullptr, ws, scratch, grad_params, dx, events, n_events, stream, nullptr);
 }
 
 int stg_model_bwd_nll(const stg_model_desc *d, const float *params, const float *buffers, const float *x, int64_t x_sn,
@@ -649,7 +679,7 @@ int stg_model_bwd_nll(const stg_model_desc *d, const float *params, const float 
                       const float *ws, float *scratch, float *grad_params, void **events, int n_events, void *stream) {
     if (!target || !losses || (N > 0 && !y)) return stg::fail(STG_EINVAL, "stg_model_bwd_nll: null pointer");
     return model_bwd_impl(d, params, buffers, x, x_sn, x_sc, x_st, x_sv, adj, a_sn, num_peds, N, V, y, target, weights,
-                          losses, nullptr, ws, scratch, grad_params, nullptr, events, n_events, stream);
+                          losses, nullptr, ws, scratch, grad_params, nullptr, events, n_events, stream, nullptr);
 }
 
 int stg_model_bwd_step(const stg_model_desc *d, const float *params, const float *buffers, const float *x, int64_t x_sn,
@@ -662,7 +692,34 @@ int stg_model_bwd_step(const stg_model_desc *d, const float *params, const float
         return stg::fail(STG_EINVAL, "stg_model_bwd_step: bad tail");
     if (N == 0) return STG_EUNSUPPORTED;               // (an empty batch has no backward launch to ride on)
     return model_bwd_impl(d, params, buffers, x, x_sn, x_sc, x_st, x_sv, adj, a_sn, num_peds, N, V, y, target, weights,
-                          losses, tail, ws, scratch, grad_params, nullptr, events, n_events, stream);
+                          losses, tail, ws, scratch, grad_params, nullptr, events, n_events, stream, nullptr);
+}
+
+int stg_model_step(const stg_model_desc *d, const float *params, const float *buffers, const float *x, int64_t x_sn,
+                   int64_t x_sc, int64_t x_st, int64_t x_sv, const float *adj, int64_t a_sn, const int32_t *num_peds,
+                   int N, int V, float *y, float *ws, float *stats, float *fwd_scratch, const float *target,
+                   const float *weights, float *losses, float *bwd_scratch, float *grad_params,
+                   const stg_step_tail *tail, void **fwd_events, int n_fwd_events, void **bwd_events,
+                   int n_bwd_events, void *stream) {
+    using namespace stg;
+    if (!target || !losses || !y || !ws) return fail(STG_EINVAL, "stg_model_step: null pointer");
+    if (!tail || !tail->params || (tail->stats && !tail->buffers) || tail->n_bn < 0 || tail->n_bn > 3 * STG_MAX_BLOCKS)
+        return fail(STG_EINVAL, "stg_model_step: bad tail");
+    ModelLayout L;
+    const int rc = make_layout(d, &L);
+    if (rc != STG_OK) return rc;
+    STG_REQUIRE(N >= 0 && V > 0, STG_EINVAL, "stg_model_step: bad sizes N=%d V=%d", N, V);
+    // (where stg_model_bwd_step has no form, decided before the forward launches anything)
+    if (N == 0 || (L.flags & STG_OPT_SPLIT_BF16) || L.n_txp == 0) return STG_EUNSUPPORTED;
+    STG_REQUIRE(grad_params && bwd_scratch, STG_EINVAL, "stg_model_step: null pointer");
+    TxpFwdArgs f{};
+    const bool one = step_one_launch(L, choose_path(L, N, V), num_peds, N, V);
+    const int rcf = model_fwd_impl(d, params, buffers, x, x_sn, x_sc, x_st, x_sv, adj, a_sn, num_peds, N, V, y, ws, stats,
+                                   fwd_scratch, fwd_events, n_fwd_events, stream, one ? &f : nullptr);
+    if (rcf != STG_OK) return rcf;
+    return model_bwd_impl(d, params, buffers, x, x_sn, x_sc, x_st, x_sv, adj, a_sn, num_peds, N, V, y, target, weights,
+                          losses, tail, ws, bwd_scratch, grad_params, nullptr, bwd_events, n_bwd_events, stream,
+                          one ? &f : nullptr);
 }
 
 }  // extern "C"

@@ -213,13 +213,12 @@ static size_t fwd_lds_bytes(int V, int waves) {
     return (size_t)(plane + reg + waves * 16 + 16) * sizeof(float);
 }
 
-}  // namespace stg
-
-extern "C" int stg_model_fwd(const stg_model_desc *d, const float *params, const float *buffers, const float *x,
-                             int64_t x_sn, int64_t x_sc, int64_t x_st, int64_t x_sv, const float *adj,
-                             int64_t a_sn, const int32_t *num_peds, int N, int V, float *y, float *ws,
-                             float *stats, float *scratch, void **events, int n_events, void *stream) {
-    using namespace stg;
+// stg_model_fwd.  `defer` (stg_model_step, step_one_launch() holds): the scene launch is left to the backward's -- its
+// arguments go to *defer, and the forward scene kernel's event interval is recorded empty.
+int model_fwd_impl(const stg_model_desc *d, const float *params, const float *buffers, const float *x, int64_t x_sn,
+                   int64_t x_sc, int64_t x_st, int64_t x_sv, const float *adj, int64_t a_sn, const int32_t *num_peds,
+                   int N, int V, float *y, float *ws, float *stats, float *scratch, void **events, int n_events,
+                   void *stream, TxpFwdArgs *defer) {
     FwdArgs a{};
     const int rc = make_layout(d, &a.lay);
     if (rc != STG_OK) return rc;
@@ -238,6 +237,8 @@ extern "C" int stg_model_fwd(const stg_model_desc *d, const float *params, const
     const FwdCarve fc = fwd_carve(L, path, N, V);
     const WsTail wt = ws_tail(L, path, N, V);
     float *ws_end = ws ? ws + wt.base : nullptr;       // (the batch tail of the workspace)
+    STG_REQUIRE(!defer || step_one_launch(L, path, num_peds, N, V), STG_EINVAL,
+                "stg_model_fwd: a scene launch deferred outside the one-launch step");
     STG_REQUIRE(path.scene() || !(L.flags & STG_OPT_BF16_STORE), STG_EUNSUPPORTED,
                 "stg_model_fwd: bf16 storage (STG_OPT_BF16_STORE) is built for the wave-per-scene kernels only "
                 "(one st_gcn block, input_feat 2, V <= 68, no STG_OPT_WG_PATH)");
@@ -303,7 +304,8 @@ extern "C" int stg_model_fwd(const stg_model_desc *d, const float *params, const
         t.Vl = V;
         t.debug_skip = a.debug_skip;
         t.stagger = diag_env("STG_STAGGER_F", 0);
-        const int rcw = launch_scene_fwd(path, t, st);
+        if (defer) *defer = t;
+        const int rcw = defer ? STG_OK : launch_scene_fwd(path, t, st);
         evl.mark();
         evl.finish();
         return rcw;
@@ -325,4 +327,14 @@ extern "C" int stg_model_fwd(const stg_model_desc *d, const float *params, const
     evl.mark();
     evl.finish();
     return STG_OK;
+}
+
+}  // namespace stg
+
+extern "C" int stg_model_fwd(const stg_model_desc *d, const float *params, const float *buffers, const float *x,
+                             int64_t x_sn, int64_t x_sc, int64_t x_st, int64_t x_sv, const float *adj,
+                             int64_t a_sn, const int32_t *num_peds, int N, int V, float *y, float *ws,
+                             float *stats, float *scratch, void **events, int n_events, void *stream) {
+    return stg::model_fwd_impl(d, params, buffers, x, x_sn, x_sc, x_st, x_sv, adj, a_sn, num_peds, N, V, y, ws, stats,
+                               scratch, events, n_events, stream, nullptr);
 }

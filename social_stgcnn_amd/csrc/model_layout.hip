@@ -24,7 +24,8 @@ int make_layout(const stg_model_desc *d, ModelLayout *lay) {
     STG_REQUIRE(d->bn_mode == 0 || d->bn_mode == 1, STG_EINVAL, "bn_mode=%d (0 eval, 1 per-scene train)", d->bn_mode);
     STG_REQUIRE(d->residual0 >= 0 && d->residual0 <= 2, STG_EINVAL, "residual0=%d", d->residual0);
     STG_REQUIRE(d->residual0 != 1 || d->c_in == d->c_out, STG_EINVAL, "identity residual needs c_in == c_out");
-    STG_REQUIRE((d->flags & ~(STG_OPT_WG_PATH | STG_OPT_SPLIT_BF16 | STG_OPT_WAVE_PATH | STG_OPT_BF16_STORE | STG_OPT_F32_MFMA)) == 0, STG_EINVAL,
+    STG_REQUIRE((d->flags & ~(STG_OPT_WG_PATH | STG_OPT_SPLIT_BF16 | STG_OPT_WAVE_PATH | STG_OPT_BF16_STORE | STG_OPT_F32_MFMA |
+                              STG_OPT_SEPARATE_FB)) == 0, STG_EINVAL,
                 "unknown flags 0x%x", d->flags);
     STG_REQUIRE(d->wg_waves == 0 || d->wg_waves == 1 || d->wg_waves == 2 || d->wg_waves == 4 || d->wg_waves == 8,
                 STG_EINVAL, "wg_waves=%d (0 auto, 1, 2, 4, 8)", d->wg_waves);
@@ -99,6 +100,12 @@ int launch_scene_bwd(const StepPath &path, const TxpBwdArgs &a, hipStream_t st) 
     return path.bwd_x6 ? launch_txp_bwd_x6(a, st) : launch_txp_bwd_wave(a, st);
 }
 
+bool step_one_launch(const ModelLayout &L, const StepPath &path, const int32_t *num_peds, int N, int V) {
+    return path.kind == StepPath::SceneX6 && path.fwd_x6 && path.bwd_x6 && !(L.flags & STG_OPT_SEPARATE_FB) &&
+           txp_step_x6_fits(L, num_peds, N, V);
+}
+int launch_scene_step(const TxpFwdArgs &f, const TxpBwdArgs &b, hipStream_t st) { return launch_txp_step_x6(f, b, st); }
+
 __global__ __launch_bounds__(1024) void scene_order_kernel(const int32_t *__restrict__ num_peds, int N, int V,
                                                            int32_t *__restrict__ order,
                                                            int32_t *__restrict__ key_start,
@@ -154,6 +161,14 @@ int64_t stg_model_fwd_scratch_floats(const stg_model_desc *d, int N, int V) {
     if (rc != STG_OK) return rc;
     if (N < 0 || V <= 0) return stg::fail(STG_EINVAL, "stg_model_fwd_scratch_floats: N=%d V=%d", N, V);
     return stg::fwd_carve(l, stg::choose_path(l, N, V), N, V).total;
+}
+int64_t stg_model_fwd_stamps_offset(const stg_model_desc *d, int N, int V) {
+    stg::ModelLayout l;
+    const int rc = stg::make_layout(d, &l);
+    if (rc != STG_OK) return rc;
+    if (N < 0 || V <= 0) return stg::fail(STG_EINVAL, "stg_model_fwd_stamps_offset: N=%d V=%d", N, V);
+    const int64_t off = stg::fwd_carve(l, stg::choose_path(l, N, V), N, V).stamps;
+    return off >= 0 ? off : STG_EUNSUPPORTED;
 }
 int stg_scene_order(const int32_t *num_peds, int N, int V, int32_t *order, int32_t *key_start, void *stream) {
     STG_REQUIRE(N >= 0 && V > 0, STG_EINVAL, "stg_scene_order: bad sizes N=%d V=%d", N, V);

@@ -54,4 +54,26 @@ inline bool tail_has_order(const StepPath &path, const int32_t *num_peds, int N,
 int launch_scene_fwd(const StepPath &path, const TxpFwdArgs &a, hipStream_t st);
 int launch_scene_bwd(const StepPath &path, const TxpBwdArgs &a, hipStream_t st);
 
+// The training step in one call (stg_model_step): whether the forward and the backward scene kernels run as ONE launch
+// (txp_x6.hip, txp_step_x6_kernel).  Exactly where both passes would run their solo kernels compiled for the canonical
+// model and uniform scenes of 32 pedestrians (Shape::Canon32): the SceneX6 path with both passes on the exact-bf16
+// kernels, a canonical layout, V = 32 without num_peds, a batch large enough that no team launch is wanted -- and the
+// caller has not asked for separate launches (STG_OPT_SEPARATE_FB), nor the diagnostic build for one of the solo
+// kernels' timing switches (txp_step_x6_fits).  Everything the launch itself requires is decided here: where this holds
+// the launch goes through, where it does not the step runs its two launches.
+bool step_one_launch(const ModelLayout &L, const StepPath &path, const int32_t *num_peds, int N, int V);
+int launch_scene_step(const TxpFwdArgs &f, const TxpBwdArgs &b, hipStream_t st);
+
+// the two passes behind the C entry points (model_fwd.hip, model_bwd.hip).  `defer` / `deferred`: the forward leaves its
+// scene launch to the backward's (step_one_launch() holds), which runs both as one.
+int model_fwd_impl(const stg_model_desc *d, const float *params, const float *buffers, const float *x, int64_t x_sn,
+                   int64_t x_sc, int64_t x_st, int64_t x_sv, const float *adj, int64_t a_sn, const int32_t *num_peds,
+                   int N, int V, float *y, float *ws, float *stats, float *scratch, void **events, int n_events,
+                   void *stream, TxpFwdArgs *defer);
+int model_bwd_impl(const stg_model_desc *d, const float *params, const float *buffers, const float *x, int64_t x_sn,
+                   int64_t x_sc, int64_t x_st, int64_t x_sv, const float *adj, int64_t a_sn, const int32_t *num_peds,
+                   int N, int V, const float *dy, const float *nll_target, const float *nll_weights, float *nll_losses,
+                   const stg_step_tail *tail, const float *ws, float *scratch, float *grad_params, float *dx,
+                   void **events, int n_events, void *stream, const TxpFwdArgs *deferred);
+
 }  // namespace stg

@@ -50,7 +50,10 @@ struct TxpFwdArgs {
     float *ws;             // per-scene workspace or null (inference)
     int64_t ws_stride;
     float *stats;          // (N, stat_floats) per-scene BatchNorm statistics (bn_mode 1) or null
-    unsigned long long *stamps;   // diagnostic build only (STG_STAMPS=1): [N][16] s_memtime stamps, else null
+    unsigned long long *stamps;   // diagnostic build only (STG_STAMPS=1), else null: [N][16] stamps per scene -- the
+                                  // exact-bf16 kernels write s_memrealtime into slots 0 and 8 (scene taken up / done,
+                                  // txp_x6.hip), the fp32-MFMA kernels and the block phases s_memtime (another counter,
+                                  // another rate: never subtract one kind from the other)
     int debug_skip;        // diagnostic builds only
     int stagger;           // start delay of the second half of every workgroup's waves (stagger_start units)
 };
@@ -81,6 +84,7 @@ struct TxpBwdArgs {
     const unsigned *wp;    // prepared input-gradient A operands (txp_conv_bf16.hpp), [L+1][cv::kWpDwords] -- the batch
                            // tail of the workspace, written by the forward's aggregation launch -- or null
     float *rows;           // [N][n_blk_params + n_txp]  per-scene small-parameter gradients: st_gcn block, PReLU slopes
+    unsigned long long *stamps;   // diagnostic build only (STG_STAMPS=1), else null: [N][16], as TxpFwdArgs::stamps
     int debug_skip;        // timing-only diagnostic (STG_DEBUG_SKIP): 512 dz build, 1024 dgrad tile loops -- wrong results
     int split_bf16;        // 1: the input-gradient GEMMs run on bf16 MFMAs with hi/lo-split operands (see txp_wave.hip)
     int stagger;           // start delay of the second half of every workgroup's waves (stagger_start units)
@@ -93,6 +97,9 @@ bool txp_bwd_x6_fits(const ModelLayout &L, int V);
 int64_t txp_bwd_x6_wp_floats(const ModelLayout &L);
 int launch_txp_fwd_x6(const TxpFwdArgs &a, hipStream_t st);
 int launch_txp_bwd_x6(const TxpBwdArgs &a, hipStream_t st);
+// both passes of a training step as one launch (txp_step_x6_kernel): where each pass would run its solo Canon32 kernel
+bool txp_step_x6_fits(const ModelLayout &L, const int32_t *num_peds, int N, int V);
+int launch_txp_step_x6(const TxpFwdArgs &f, const TxpBwdArgs &b, hipStream_t st);
 
 // LDS floats of one wave's position table (16-bit entries, Cfg::T * v of them) [+ the st_gcn tail's 32 reduction totals]
 __host__ __device__ inline int ptab_floats(int v) { return ((Cfg::T * v + 1) / 2 + 3) & ~3; }

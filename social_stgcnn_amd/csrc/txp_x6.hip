@@ -71,6 +71,17 @@ __device__ __forceinline__ int lay_ws_z(const ModelLayout &L, int l) {
     else return kCanonLayout.ws_z[l];
 }
 
+// diagnostic build with STG_STAMPS=1: when a wave takes up a scene (slot 0) and when it is done with it (slot 8), in the
+// launch's own [N][16] stamp array (tools/stamps_x6.py: start and end skew of a launch)
+#ifdef STG_DIAG
+#define STG_X6_STAMP(a, n, k)                                                                                          \
+    do {                                                                                                              \
+        if ((a).stamps && (threadIdx.x & 63) == 0) (a).stamps[(int64_t)(n) * 16 + (k)] = __builtin_amdgcn_s_memrealtime(); \
+    } while (0)
+#else
+#define STG_X6_STAMP(a, n, k) do { } while (0)
+#endif
+
 // ------------------------------------------------------------------------------------------
 // forward, exact-bf16 variant (x6 = six bf16 products per fp32 product): the convs on v_mfma_f32_16x16x32_bf16
 // ------------------------------------------------------------------------------------------
@@ -267,8 +278,10 @@ __global__ __launch_bounds__(WPB * 64, WPB == 8 ? 1 : 2) __attribute__((amdgpu_w
         const int n = __builtin_amdgcn_readfirstlane(a.tier.order ? scene_index(a.tier.order[begin + it], a.N) : it);
         int vi = a.num_peds ? a.num_peds[n] : a.V;
         vi = __builtin_amdgcn_readfirstlane(vi < 0 ? 0 : (vi > a.V ? a.V : vi));
+        STG_X6_STAMP(a, n, 0);
         txp_fwd_scene_x6<BF, SoloScene, S>(a, params, blk_p, blk_b, n, vi, region, ptab, SoloScene{vi});
         __builtin_amdgcn_wave_barrier();
+        STG_X6_STAMP(a, n, 8);
     }
 }
 
@@ -597,9 +610,64 @@ __global__ __launch_bounds__(WPB * 64, WPB == 8 ? 1 : 2) __attribute__((amdgpu_w
         const int n = __builtin_amdgcn_readfirstlane(a.tier.order ? scene_index(a.tier.order[begin + it], a.N) : it);
         int vi = a.num_peds ? a.num_peds[n] : a.V;
         vi = __builtin_amdgcn_readfirstlane(vi < 0 ? 0 : (vi > a.V ? a.V : vi));
+        STG_X6_STAMP(a, n, 0);
         txp_bwd_scene_x6<BF, SoloScene, S>(a, blk_p, n, vi, region, ptab, SoloScene{vi});
         __builtin_amdgcn_wave_barrier();
+        STG_X6_STAMP(a, n, 8);
     }
+}
+
+// ------------------------------------------------------------------------------------------
+// forward and backward of a Canon32 scene in ONE launch (the training step: stg_model_step)
+// ------------------------------------------------------------------------------------------
+// The backward of scene n needs the forward of scene n only (BatchNorm statistics, loss and gradients are per scene), so a
+// wave runs the backward of its scene straight behind the forward instead of waiting for the grid's slowest wave at a launch
+// boundary.  The two scene functions are the solo kernels' own, in the solo kernels' order: every saved array (z_l, a_l, the
+// block arrays, V_pred) is still stored to global memory -- the weight-gradient kernel and the caller read them -- and read
+// back by the backward exactly as between two launches.  A wave reads only what it wrote itself: program order within a
+// wave is all the visibility that needs (no cache action at wavefront scope), the fence keeps the compiler from moving the
+// backward's loads above the forward's stores.  The LDS region is the larger of the two stages', reused; the block
+// parameters are staged once.
+__host__ __device__ inline int step6_per_wave_floats(int v) {
+    const int f = fwd6_region_floats(v) + ptab_floats(v), b = bwd6_region_floats(v) + bwd_ptab_floats(v);
+    return f > b ? f : b;
+}
+
+// One scene per wave and no scene loop: the grid is N / WPB workgroups, the first 2048 waves fill the chip exactly as the solo
+// kernels' persistent grids do, and the dispatcher hands a freed workgroup slot to the next four scenes of a larger batch.
+// With the solo kernels' loop around both stages the compiler hoists the lane constants of BOTH stages in front of it and
+// keeps them live across the whole kernel (50 VGPRs spilled to scratch memory, 151 SGPRs); without a loop there is
+// nothing to hoist out of, and the kernel spills nothing at all.
+template <int WPB, bool BF>
+__global__ __launch_bounds__(WPB * 64, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) void txp_step_x6_kernel(
+    const TxpFwdArgs f0, const TxpBwdArgs b0) {
+    constexpr Shape S = Shape::Canon32;
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    TxpFwdArgs f = f0;
+    fold_shape<S>(f);
+    f.agg_stride = kCanonAggStride32[1];               // (a training step: the aggregation launch wrote into the workspace)
+    f.agg_ax = kCanonAggAx32[1];
+    f.agg_cs = kCanonAggCs32[1];
+    TxpBwdArgs b = b0;
+    fold_shape<S>(b);
+    const int wave = threadIdx.x >> 6;
+    const int per_wave = step6_per_wave_floats(kCanonV);
+    float *region = sm + wave * per_wave;
+    ptab_t *ptab = reinterpret_cast<ptab_t *>(region + bwd6_region_floats(kCanonV));      // (Canon32 builds no table)
+    float *blk_p = sm + WPB * per_wave, *blk_b = blk_p + ((kCanonLayout.n_blk_params + 3) & ~3);
+    stage_block_params(f.lay, f.params, f.buffers, blk_p, blk_b, WPB * 64);
+    const int n = __builtin_amdgcn_readfirstlane(blockIdx.x * WPB + wave);
+    if (n >= f.N) return;
+    STG_X6_STAMP(f, n, 0);
+    txp_fwd_scene_x6<BF, SoloScene, S>(f, f.params, blk_p, blk_b, n, kCanonV, region, ptab, SoloScene{kCanonV});
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    STG_X6_STAMP(f, n, 8);
+    STG_X6_STAMP(b, n, 0);
+    txp_bwd_scene_x6<BF, SoloScene, S>(b, blk_p, n, kCanonV, region, ptab, SoloScene{kCanonV});
+    __builtin_amdgcn_wave_barrier();
+    STG_X6_STAMP(b, n, 8);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -863,6 +931,44 @@ int launch_txp_bwd_x6(const TxpBwdArgs &a0, hipStream_t st) {
     STG_REQUIRE(ok, STG_EINVAL, "txp_bwd_x6: the canonical V=%d batch does not match its compiled layout", a.V);
     return launch(Launch{"txp_bwd_x6", dim3(wave_grid(lds, wpb, a.N)), dim3(wpb * 64), lds, st},
                   wpb == 8 ? bwd_x6_kernel<8>(bf, sh) : bwd_x6_kernel<4>(bf, sh), a);
+}
+
+// One launch serves both passes exactly where each pass on its own would run its solo Canon32 kernel with four waves per
+// workgroup on the same batch: a training forward (workspace, prepared operands of both passes) of a uniform batch of
+// kCanonV pedestrians on the canonical model, large enough that no team launch is wanted.
+// The solo kernels' switches of the diagnostic build (STG_DEBUG_SKIP, STG_STAGGER_F / _B, eight waves per workgroup with
+// STG_TXP_WPB) have no form in the one-launch kernel: with any of them set the step keeps its two launches.
+static bool step_x6_plain(int debug_skip_f, int debug_skip_b, int stagger_f, int stagger_b) {
+    const size_t pf = (size_t)(fwd6_region_floats(kCanonV) + ptab_floats(kCanonV)) * sizeof(float);
+    const size_t pb = (size_t)(bwd6_region_floats(kCanonV) + bwd_ptab_floats(kCanonV)) * sizeof(float);
+    return !debug_skip_f && !debug_skip_b && !stagger_f && !stagger_b && wave_wpb(pf) != 8 && wave_wpb(pb) != 8;
+}
+bool txp_step_x6_fits(const ModelLayout &L, const int32_t *num_peds, int N, int V) {
+    TeamGeom g;
+    const int skip = diag_env("STG_DEBUG_SKIP", 0);
+    return is_canonical(L) && V == kCanonV && !num_peds && txp_fwd_x6_fits(L, V) && txp_bwd_x6_fits(L, V) &&
+           !team_wanted(N, V, true, &g) &&
+           step_x6_plain(skip, skip, diag_env("STG_STAGGER_F", 0), diag_env("STG_STAGGER_B", 0));
+}
+// (the launch's own check of what the planner promised: the arguments the two passes built agree with each other and with
+// the folded shape)
+static bool txp_step_x6_applies(const TxpFwdArgs &f, const TxpBwdArgs &b) {
+    if (!f.wpf || !b.wp || !f.ws || f.ws != b.ws || f.N != b.N || f.V != b.V || f.params != b.params) return false;
+    if (f.lay.flags != b.lay.flags || !step_x6_plain(f.debug_skip, b.debug_skip, f.stagger, b.stagger)) return false;
+    TeamGeom g;
+    if (team_wanted(f.N, f.V, f.num_peds == nullptr, &g) || team_wanted(b.N, b.V, b.num_peds == nullptr, &g)) return false;
+    bool okf, okb;
+    if (canon_shape(f, &okf) != Shape::Canon32 || canon_shape(b, &okb) != Shape::Canon32) return false;
+    return okf && okb && canon32_agg_matches(f);
+}
+int launch_txp_step_x6(const TxpFwdArgs &f, const TxpBwdArgs &b, hipStream_t st) {
+    STG_REQUIRE(txp_step_x6_applies(f, b), STG_EINVAL, "txp_step_x6: the batch is outside the one-launch scene kernel");
+    constexpr int wpb = 4;
+    const size_t lds = ((size_t)step6_per_wave_floats(kCanonV) * wpb + wave_param_floats(f.lay)) * sizeof(float);
+    const bool bf = (f.lay.flags & STG_OPT_BF16_STORE) != 0;
+    STG_REQUIRE(2 * lds <= (size_t)kLdsBytes, STG_ELDS, "txp_step_x6: %zu bytes of LDS do not fit two workgroups per CU", lds);
+    return launch(Launch{"txp_step_x6", dim3((f.N + wpb - 1) / wpb), dim3(wpb * 64), lds, st},
+                  bf ? txp_step_x6_kernel<wpb, true> : txp_step_x6_kernel<wpb, false>, f, b);
 }
 
 }  // namespace stg

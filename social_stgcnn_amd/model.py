@@ -198,9 +198,16 @@ class social_stgcnn(nn.Module):
     def _forward(self, v, a, num_peds=None, defer_bn_fold=False):
         """forward(); defer_bn_fold (the trainer's request): a training forward leaves the running-statistics fold to
         the step's tail launch, the statistics travel in `self._fwd_state`."""
-        assert a.size(-3) == self.st_gcns[0].gcn.kernel_size
         if self.n_txpcnn < 1:
             raise NotImplementedError("social_stgcnn needs n_txpcnn >= 1 (model.py:168 always builds tpcnns[0])")
+        desc, flat_p, flat_b, nbt, dead, params = self._launch_args(a)
+        y = ops.fused_model(v, a, num_peds, desc, flat_p, flat_b, nbt, dead, params, self, defer_bn_fold)
+        return y, a
+
+    def _launch_args(self, a):
+        """what every fused launch of this model starts from: (descriptor, flat parameters, flat buffers, the
+        num_batches_tracked counters, the indices of the dead parameters, the parameters)"""
+        assert a.size(-3) == self.st_gcns[0].gcn.kernel_size
         for blk in self.st_gcns:
             _check_block(blk, self.training)
         params, bufs, nbt, dead = self._tensors()
@@ -210,5 +217,19 @@ class social_stgcnn(nn.Module):
         desc = ops.make_desc(self.n_stgcnn, self.n_txpcnn, self.input_feat, self.output_feat, self.seq_len,
                              self.pred_seq_len, self.kt, self.st_gcns[0].residual_kind, False, self.training,
                              bn.eps, bn.momentum, options=getattr(self, "options", None))
-        y = ops.fused_model(v, a, num_peds, desc, flat_p, flat_b, nbt, dead, params, self, defer_bn_fold)
-        return y, a
+        return desc, flat_p, flat_b, nbt, dead, params
+
+    def _step(self, v, a, target, num_peds, weights, lr, lr_dev):
+        """One training step without clipping in one library call (ops.fused_step): forward, loss, backward, SGD, the
+        running-statistics fold and the reported loss; the gradients land in every live parameter's .grad.  Returns
+        (V_pred, per-scene losses, reported loss) or None where the library has no such step."""
+        if self.n_txpcnn < 1 or not self.training:
+            return None
+        desc, flat_p, flat_b, nbt, dead, params = self._launch_args(a)
+        res = ops.fused_step(v, a, num_peds, desc, flat_p, flat_b, nbt, dead, params, self, target, weights, lr, lr_dev)
+        if res is None:
+            return None
+        y, losses, total, grads = res
+        for p, g in zip(params, grads):
+            p.grad = g
+        return y, losses, total

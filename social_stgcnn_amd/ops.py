@@ -188,12 +188,14 @@ class FlatPack:
 #   bf16_store  bf16 storage of the saved TXP activations and of the dz hand-off (STG_OPT_BF16_STORE): fp32 forward
 #               result, ~1e-3 relative error in the TXP weight / slope gradients; wave-per-scene path only
 #   f32_mfma    the fp32-MFMA kernels where the default runs the exact bf16-pipe ones (STG_OPT_F32_MFMA): A/B measurements
+#   separate_fb the training step (stg_model_step) keeps the forward and the backward scene kernels as two launches where
+#               one launch serves both (STG_OPT_SEPARATE_FB): same results bit for bit, A/B measurements and tests
 class KernelOptions(dict):
     """The launch options of ONE model: `model.options = ops.KernelOptions(bf16_store=True)` makes that model (and the
     Trainer / EpochRunner driving it) run with its own choices, whatever other models in the process do.  A model without
     an `options` attribute of its own uses the process-wide defaults, `ops.OPTIONS`."""
     DEFAULTS = {"wg_path": False, "split_bf16": False, "wg_waves": 0, "wave_path": False, "bf16_store": False,
-                "f32_mfma": False}
+                "f32_mfma": False, "separate_fb": False}
 
     def __init__(self, **kw):
         bad = set(kw) - set(self.DEFAULTS)
@@ -212,7 +214,8 @@ def make_desc(n_stgcnn, n_txpcnn, c_in, c_out, t_obs, t_pred, kt, residual0, use
     flags = ((_lib.OPT_WG_PATH if o["wg_path"] else 0) | (_lib.OPT_SPLIT_BF16 if o["split_bf16"] else 0)
              | (_lib.OPT_WAVE_PATH if o["wave_path"] else 0)
              | (_lib.OPT_BF16_STORE if o["bf16_store"] else 0)
-             | (_lib.OPT_F32_MFMA if o["f32_mfma"] else 0))
+             | (_lib.OPT_F32_MFMA if o["f32_mfma"] else 0)
+             | (_lib.OPT_SEPARATE_FB if o["separate_fb"] else 0))
     return ModelDesc(n_stgcnn, n_txpcnn, c_in, c_out, t_obs, t_pred, kt, residual0, 1 if use_mdn else 0,
                      1 if training else 0, eps, momentum, flags, int(o["wg_waves"]))
 
@@ -291,20 +294,85 @@ class FwdRecord:
     n: int = 0
 
 
+def _check_model_input(x, adj, desc, flat_params, flat_buffers):
+    """the checks every fused forward starts with; returns the sizes (n, c_in, t, v) of x"""
+    require_gpu(x, adj, flat_params, flat_buffers)
+    _lib.as_f32(x, "x")
+    _lib.as_f32(adj, "adj")
+    n, cin, t, v = x.shape
+    if cin != desc.c_in or t != desc.t_obs:
+        raise ValueError("input (N,%d,%d,V) does not match the model (input_feat=%d, seq_len=%d)"
+                         % (cin, t, desc.c_in, desc.t_obs))
+    return n, cin, t, v
+
+
+def _fwd_buffers(desc, n, v, dev, save, training, holder):
+    """The arrays stg_model_fwd writes, sized by the library: (y, ws, stats, scratch).  ws (the saved activations) only
+    when `save`, stats only when `training`, scratch only where the path needs one."""
+    L, d = lib(), ctypes.byref(desc)
+    out_t = desc.t_pred if desc.n_txpcnn > 0 else desc.t_obs
+    y = torch.empty((n, desc.c_out, out_t, v), device=dev, dtype=torch.float32)
+    ws = None                      # (its size is a diagnostic: last_ws_floats, 0 = inference)
+    if save:
+        wsf = _size(L.stg_model_ws_floats(d, v), "stg_model_ws_floats")
+        tail = _size(L.stg_model_ws_tail_floats(d, n, v), "stg_model_ws_tail_floats")
+        ws = torch.empty(n * wsf + tail, device=dev, dtype=torch.float32)
+    stats = None
+    if training:
+        sf = L.stg_model_stat_floats(d)
+        stats = torch.empty((n, max(int(sf), 1)), device=dev, dtype=torch.float32)
+    scr = None
+    nscr = _size(L.stg_model_fwd_scratch_floats(d, n, v), "stg_model_fwd_scratch_floats")
+    if nscr > 0:
+        scr = torch.empty(nscr, device=dev, dtype=torch.float32)
+    if holder is not None:
+        holder.last_ws_floats = ws.numel() if save else 0
+        holder._last_fwd_scratch = scr  # diagnostics only (STG_STAMPS=1 reads the stamps in it)
+    return y, ws, stats, scr
+
+
+def _bwd_buffers(desc, n, v, dev):
+    """The arrays the fused backward writes, sized by the library: (scratch, flat gradient)."""
+    L, d = lib(), ctypes.byref(desc)
+    np_ = int(L.stg_model_param_count(d))
+    n_scratch = _size(L.stg_model_bwd_scratch_floats(d, n, v), "stg_model_bwd_scratch_floats")
+    slabs = torch.empty(n_scratch, device=dev, dtype=torch.float32)
+    grad = torch.empty(np_, device=dev, dtype=torch.float32)
+    return slabs, grad
+
+
+def _step_tail(flat_params, flat_buffers, step, stats, nbt):
+    """The tail of a single-rank step (stg_step_tail) for step = (lr, lr_dev): SGD on the flat parameters, the reported
+    loss and, with `stats`, the BatchNorm fold the forward deferred.  Returns (tail, total, what must stay alive until
+    the call has been made)."""
+    lr, lr_dev = step
+    total = torch.empty(1, device=flat_params.device, dtype=torch.float32)
+    tail = _lib.StepTail()
+    tail.params, tail.lr_dev, tail.lr = ptr(flat_params), ptr(lr_dev), float(lr)
+    tail.total = ptr(total)
+    arr = None
+    if stats is not None:
+        arr = _ptr_array(nbt)
+        tail.stats, tail.buffers, tail.nbt, tail.n_bn = ptr(stats), ptr(flat_buffers), arr, len(nbt)
+    return tail, total, arr
+
+
+def _grad_views(grad, shapes, dead, holder):
+    """per-parameter views of the flat gradient (None for the dead ones); the flat gradient goes to the holder"""
+    if holder is not None:
+        holder._flat_grad = grad           # the trainer all-reduces / applies this buffer directly
+        holder._fwd_state = None
+    return [None if i in dead else grad[off:off + cnt].view(shapes[i]) for i, off, cnt in flat_walk(shapes)]
+
+
 class _FusedModel(torch.autograd.Function):
     """x (N,Cin,T,V), adj -> y.  Extra (non-differentiable) arguments carry the packed buffers."""
 
     @staticmethod
     def forward(ctx, x, adj, num_peds, desc, flat_params, flat_buffers, nbt, dead, holder, grad_on, defer_bn_fold,
                 *params):
-        require_gpu(x, adj, flat_params, flat_buffers)
-        _lib.as_f32(x, "x")
-        _lib.as_f32(adj, "adj")
+        n, cin, t, v = _check_model_input(x, adj, desc, flat_params, flat_buffers)
         L = lib()
-        n, cin, t, v = x.shape
-        if cin != desc.c_in or t != desc.t_obs:
-            raise ValueError("input (N,%d,%d,V) does not match the model (input_feat=%d, seq_len=%d)"
-                             % (cin, t, desc.c_in, desc.t_obs))
         adj_c, a_sn = _adj_layout(adj, n, t, v)
         peds = peds_arg(num_peds, n, x.device)
         training = desc.bn_mode == 1
@@ -316,24 +384,7 @@ class _FusedModel(torch.autograd.Function):
             fields = {f: getattr(desc, f) for f, _ in ModelDesc._fields_}
             fields["flags"] |= _lib.OPT_WG_PATH
             desc = ModelDesc(**fields)
-        out_t = desc.t_pred if desc.n_txpcnn > 0 else desc.t_obs
-        y = torch.empty((n, desc.c_out, out_t, v), device=x.device, dtype=torch.float32)
-        ws = None                      # (its size is a diagnostic: last_ws_floats, 0 = inference)
-        if need_grad:
-            wsf = _size(L.stg_model_ws_floats(ctypes.byref(desc), v), "stg_model_ws_floats")
-            tail = _size(L.stg_model_ws_tail_floats(ctypes.byref(desc), n, v), "stg_model_ws_tail_floats")
-            ws = torch.empty(n * wsf + tail, device=x.device, dtype=torch.float32)
-        stats = None
-        if training:
-            sf = L.stg_model_stat_floats(ctypes.byref(desc))
-            stats = torch.empty((n, max(int(sf), 1)), device=x.device, dtype=torch.float32)
-        scr = None
-        nscr = _size(L.stg_model_fwd_scratch_floats(ctypes.byref(desc), n, v), "stg_model_fwd_scratch_floats")
-        if nscr > 0:
-            scr = torch.empty(nscr, device=x.device, dtype=torch.float32)
-        if holder is not None:
-            holder.last_ws_floats = ws.numel() if need_grad else 0
-            holder._last_fwd_scratch = scr  # diagnostics only (STG_STAMPS=1 reads the stamp tail)
+        y, ws, stats, scr = _fwd_buffers(desc, n, v, x.device, need_grad, training, holder)
         sn, sc, st, sv = x.stride()
         timer = _timer_of(holder)
         ev = timer.events("model_fwd") if timer is not None else None
@@ -375,10 +426,7 @@ def _launch_backward(rec, holder, dy=None, need_dx=False, y=None, target=None, w
     L = lib()
     desc, x = rec.desc, rec.x
     n, cin, t, v = x.shape
-    np_ = int(L.stg_model_param_count(ctypes.byref(desc)))
-    n_scratch = _size(L.stg_model_bwd_scratch_floats(ctypes.byref(desc), n, v), "stg_model_bwd_scratch_floats")
-    slabs = torch.empty(n_scratch, device=x.device, dtype=torch.float32)
-    grad = torch.empty(np_, device=x.device, dtype=torch.float32)
+    slabs, grad = _bwd_buffers(desc, n, v, x.device)
     sn, sc, st, sv = x.stride()
     timer = _timer_of(holder)
     ev = timer.events("model_bwd") if timer is not None else None
@@ -394,14 +442,7 @@ def _launch_backward(rec, holder, dy=None, need_dx=False, y=None, target=None, w
         if step is None:
             name, rc = "stg_model_bwd_nll", L.stg_model_bwd_nll(*head, *mid, *end)
         else:
-            lr, lr_dev = step
-            total = torch.empty(1, device=x.device, dtype=torch.float32)
-            tail = _lib.StepTail()
-            tail.params, tail.lr_dev, tail.lr = ptr(rec.flat_params), ptr(lr_dev), float(lr)
-            tail.total = ptr(total)
-            if rec.stats is not None:
-                arr = _ptr_array(rec.nbt)
-                tail.stats, tail.buffers, tail.nbt, tail.n_bn = ptr(rec.stats), ptr(rec.flat_buffers), arr, len(rec.nbt)
+            tail, total, keep = _step_tail(rec.flat_params, rec.flat_buffers, step, rec.stats, rec.nbt)
             name, rc = "stg_model_bwd_step", L.stg_model_bwd_step(*head, *mid, ctypes.addressof(tail), *end)
             out = (losses, total[0])
         if rc == _lib.EUNSUPPORTED:
@@ -409,12 +450,7 @@ def _launch_backward(rec, holder, dy=None, need_dx=False, y=None, target=None, w
                 timer.calls["model_bwd"].pop()
             return None
     check(rc, name)
-    grads = [None if i in rec.dead else grad[off:off + cnt].view(rec.shapes[i])
-             for i, off, cnt in flat_walk(rec.shapes)]
-    if holder is not None:
-        holder._flat_grad = grad           # the trainer all-reduces / applies this buffer directly
-        holder._fwd_state = None
-    return grads, out
+    return _grad_views(grad, rec.shapes, rec.dead, holder), out
 
 
 def backward_from_target(holder, y, target, weights=None, step=None):
@@ -443,6 +479,47 @@ def backward_from_target(holder, y, target, weights=None, step=None):
     for p, g in zip(holder._tensors()[0], res[0]):
         p.grad = g
     return res[1]
+
+
+def fused_step(x, adj, num_peds, desc, flat_params, flat_buffers, nbt, dead, params, holder, target, weights, lr,
+               lr_dev):
+    """One single-rank training step without clipping in ONE library call (stg_model_step): the training forward, the
+    loss, the backward and the step's tail (SGD, running-statistics fold, reported loss) -- what `fused_model` with a
+    deferred fold followed by `backward_from_target(step=...)` runs, bit for bit, with the forward and the backward scene
+    kernels as one launch where the library has that form.  No autograd graph is built.  Returns (V_pred (N,5,P,V),
+    per-scene losses, the reported loss, per-parameter gradient views), the flat gradient left in `holder._flat_grad` --
+    or None, nothing launched, where the library has no such step (the caller then takes the two calls)."""
+    n, cin, t, v = _check_model_input(x, adj, desc, flat_params, flat_buffers)
+    if desc.bn_mode != 1 or desc.n_txpcnn < 1 or n == 0 or (desc.flags & _lib.OPT_SPLIT_BF16):
+        return None
+    target = target.to(torch.float32).contiguous()
+    if tuple(target.shape) != (n, desc.t_pred, v, 2):
+        raise ValueError("fused_step: target (N,P,V,2) expected, got %s" % (tuple(target.shape),))
+    w = weights.to(torch.float32).contiguous() if weights is not None else None
+    adj_c, a_sn = _adj_layout(adj, n, t, v)
+    peds = peds_arg(num_peds, n, x.device)
+    y, ws, stats, scr = _fwd_buffers(desc, n, v, x.device, True, True, holder)
+    slabs, grad = _bwd_buffers(desc, n, v, x.device)
+    if holder is not None:
+        holder._last_bwd_scratch = slabs  # diagnostics only (STG_STAMPS=1 reads the stamps in it)
+    losses = torch.empty(n, device=x.device, dtype=torch.float32)
+    tail, total, keep = _step_tail(flat_params, flat_buffers, (lr, lr_dev), stats, nbt)
+    timer = _timer_of(holder)
+    ev_f = timer.events("model_fwd") if timer is not None else None
+    ev_b = timer.events("model_bwd") if timer is not None else None
+    sn, sc, st, sv = x.stride()
+    rc = lib().stg_model_step(ctypes.byref(desc), ptr(flat_params), ptr(flat_buffers), ptr(x), sn, sc, st, sv, ptr(adj_c),
+                              a_sn, ptr(peds), n, v, ptr(y), ptr(ws), ptr(stats), ptr(scr), ptr(target), ptr(w),
+                              ptr(losses), ptr(slabs), ptr(grad), ctypes.addressof(tail),
+                              ev_f.arr if ev_f else None, ev_f.n if ev_f else 0,
+                              ev_b.arr if ev_b else None, ev_b.n if ev_b else 0, stream_ptr())
+    if rc == _lib.EUNSUPPORTED:
+        if timer is not None:
+            timer.calls["model_fwd"].pop()
+            timer.calls["model_bwd"].pop()
+        return None
+    check(rc, "stg_model_step")
+    return y, losses, total[0], _grad_views(grad, [tuple(p.shape) for p in params], dead, holder)
 
 
 def fused_model(x, adj, num_peds, desc, flat_params, flat_buffers, nbt, dead, params, holder=None,

@@ -212,6 +212,16 @@ class Trainer:
             return out
         model = self.model
         training = model.training
+        if (training and self.clip_grad is None and torch.is_grad_enabled() and not x.requires_grad
+                and all(p.requires_grad for p in model.parameters())):
+            # the whole step in ONE library call (stg_model_step): the forward and the backward scene kernels run as one
+            # launch where the library has that form, as the two calls below everywhere else
+            for p in model.parameters():
+                p.grad = None
+            res = model._step(x, adj, target, num_peds, weights, self.lr, self._lr_tensor(model.flat_parameters().device))
+            if res is not None:
+                y, losses, total = res
+                return total, losses, y
         y, rec = self._forward(x, adj, num_peds, defer_bn_fold=training)
         flat_p = model.flat_parameters()
         lr_dev = self._lr_tensor(flat_p.device)
