@@ -126,6 +126,9 @@ typedef struct {
                                * storage): same accuracy class, for A/B measurements                                            */
 #define STG_OPT_SEPARATE_FB 32 /* stg_model_step: run the forward and the backward scene kernels as two launches also where
                                * one launch serves both (same results bit for bit: A/B measurements and tests)           */
+#define STG_OPT_GENERIC_WGRAD 64 /* keep the generic weight-gradient kernel also where the one compiled for the canonical model
+                                 * with uniform scenes of 32 pedestrians serves the batch (same results bit for bit: A/B
+                                 * measurements and tests)                                                              */
 #define STG_OPT_WAVE_PATH 4   /* keep the wave-per-scene kernels for small batches too (default: batches of fewer than  */
                               /* 288 scenes of <= 40 pedestrians run the workgroup kernels, several waves per scene)     */
 

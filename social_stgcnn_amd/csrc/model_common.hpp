@@ -144,8 +144,8 @@ __device__ __forceinline__ f32x4 unpack_bf16x4(const uint2 &u) {
 // Row strides (in positions) of the SAVED position-major arrays.  fp32: the natural ones (vi + 2 with the border
 // columns for a plane, vi for dz).  bf16 storage: rounded up to even, so that every row of 24-byte positions starts
 // 16-byte aligned -- the weight-gradient kernel stages rows and column chunks with 16-byte LDS-DMA.
-__host__ __device__ inline int save_sw(int vi, bool bf16) { return bf16 ? (vi + 3) & ~1 : vi + 2; }
-__host__ __device__ inline int save_vw(int vi, bool bf16) { return bf16 ? (vi + 1) & ~1 : vi; }
+__host__ __device__ constexpr int save_sw(int vi, bool bf16) { return bf16 ? (vi + 3) & ~1 : vi + 2; }
+__host__ __device__ constexpr int save_vw(int vi, bool bf16) { return bf16 ? (vi + 1) & ~1 : vi; }
 
 // a 4-channel vector of a position-major [pos][12] array: 16 bytes in fp32, 8 bytes in bf16 storage
 __device__ __forceinline__ void store_vec4(float *base, int vec, const f32x4 &v, bool bf16) {
@@ -200,6 +200,16 @@ __host__ __device__ constexpr int64_t ws_plane_off(const ModelLayout &l, int V, 
 __host__ __device__ constexpr int64_t ws_floats_per_scene(const ModelLayout &l, int V) {
     return ws_plane_off(l, V, l.n_planes);
 }
+
+// What a kernel is compiled for.  Generic: the layout and the crowd are kernel arguments.  Canon: the layout is
+// kCanonLayout -- every parameter and workspace offset a constant, none of them held in SGPRs -- the crowd still a runtime
+// value (ragged batches).  Canon32: kCanonLayout and uniform scenes of exactly kCanonV pedestrians, no num_peds: the
+// workspace stride, the saved row strides, the tile counts and the lane geometry are constants as well.  The host picks a
+// folded shape only when the runtime values it passes equal the folded ones (txp_x6.hip: canon_shape; txp_wgrad_bf16.hip:
+// wgrad_canon32).
+enum class Shape { Generic, Canon, Canon32 };
+constexpr int kCanonV = 32;
+constexpr int64_t kCanonWs32 = ws_floats_per_scene(kCanonLayout, kCanonV);
 
 // ---- ragged batches: balanced static schedules ------------------------------------------------
 // The persistent kernels give worker w of G (a wave or a workgroup) the scenes of a fixed walk.  With per-scene

@@ -25,7 +25,7 @@ int make_layout(const stg_model_desc *d, ModelLayout *lay) {
     STG_REQUIRE(d->residual0 >= 0 && d->residual0 <= 2, STG_EINVAL, "residual0=%d", d->residual0);
     STG_REQUIRE(d->residual0 != 1 || d->c_in == d->c_out, STG_EINVAL, "identity residual needs c_in == c_out");
     STG_REQUIRE((d->flags & ~(STG_OPT_WG_PATH | STG_OPT_SPLIT_BF16 | STG_OPT_WAVE_PATH | STG_OPT_BF16_STORE | STG_OPT_F32_MFMA |
-                              STG_OPT_SEPARATE_FB)) == 0, STG_EINVAL,
+                              STG_OPT_SEPARATE_FB | STG_OPT_GENERIC_WGRAD)) == 0, STG_EINVAL,
                 "unknown flags 0x%x", d->flags);
     STG_REQUIRE(d->wg_waves == 0 || d->wg_waves == 1 || d->wg_waves == 2 || d->wg_waves == 4 || d->wg_waves == 8,
                 STG_EINVAL, "wg_waves=%d (0 auto, 1, 2, 4, 8)", d->wg_waves);

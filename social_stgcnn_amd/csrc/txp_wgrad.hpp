@@ -59,5 +59,8 @@ int launch_txp_wgrad(const WgradArgs &w, const WgradGeom &g, hipStream_t st);
 bool wgrad_bf16_fits(const ModelLayout &L, int V);
 void wgrad_bf16_geom(WgradGeom *g, const ModelLayout &L, int V);
 int launch_txp_wgrad_bf16(const WgradArgs &w, const WgradGeom &g, hipStream_t st);
+// txp_wgrad_bf16_canon32.hip: the same kernels compiled for the canonical model with uniform scenes of kCanonV pedestrians
+// (launch_txp_wgrad_bf16 hands it the batches that are of that shape)
+int launch_txp_wgrad_bf16_canon32(const WgradArgs &w, const WgradGeom &g, hipStream_t st);
 
 }  // namespace stg

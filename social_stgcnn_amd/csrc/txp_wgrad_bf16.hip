@@ -28,6 +28,11 @@
 //  * The six MFMAs of a tile accumulate IN PLACE (one asm statement with a read-write accumulator).  Reading tile t+1's
 //    operand in front of tile t's MFMAs (a second operand set) was measured: it spills at the 80 registers two 10-wave
 //    workgroups per CU allow (54.7 us against 47.4).
+//  * Two shapes (Shape, model_common.hpp): Generic, above, and Canon32 -- the canonical layout and uniform scenes of 32
+//    pedestrians compiled in: item pointers by a constant stride, one thread-constant staging offset, K slots and operand
+//    addresses computed once, the second half of an operand an instruction immediate.  Same walk, same sums, bitwise-equal
+//    results; 49.7 -> 41.2 us at the headline shape, bf16 storage 32.1 -> 17.6.  The second operand set
+//    was tried again there: 80 registers with 6 spilled, 47.1 us.
 #include "txp_conv_bf16.hpp"
 #include "txp_wgrad.hpp"
 #include "scene_team.hpp"
@@ -75,6 +80,25 @@ __device__ __forceinline__ void read_op(unsigned a0, unsigned a1, Op &o) {
                  : "v"(a0), "v"(a1), "n"(OFF), "n"(OFF + kPiece), "n"(OFF + 2 * kPiece)
                  : "memory");
 }
+// the same with ONE address register: the second half of the operand lies D bytes behind the first (Canon32: 16 records)
+template <int OFF, int D>
+__device__ __forceinline__ void read_op1(unsigned a0, Op &o) {
+    asm volatile("ds_read_b64_tr_b16 %0, %6 offset:%7\n\tds_read_b64_tr_b16 %1, %6 offset:%8\n\t"
+                 "ds_read_b64_tr_b16 %2, %6 offset:%9\n\tds_read_b64_tr_b16 %3, %6 offset:%10\n\t"
+                 "ds_read_b64_tr_b16 %4, %6 offset:%11\n\tds_read_b64_tr_b16 %5, %6 offset:%12\n\t"
+                 "s_waitcnt lgkmcnt(0)"
+                 : "=&v"(o.h[0]), "=&v"(o.h[1]), "=&v"(o.m[0]), "=&v"(o.m[1]), "=&v"(o.l[0]), "=&v"(o.l[1])
+                 : "v"(a0), "n"(OFF), "n"(OFF + D), "n"(OFF + kPiece), "n"(OFF + D + kPiece), "n"(OFF + 2 * kPiece),
+                   "n"(OFF + D + 2 * kPiece)
+                 : "memory");
+}
+template <int OFF, int D>
+__device__ __forceinline__ void read_op1_h(unsigned a0, Op &o) {
+    asm volatile("ds_read_b64_tr_b16 %0, %2 offset:%3\n\tds_read_b64_tr_b16 %1, %2 offset:%4\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&v"(o.h[0]), "=&v"(o.h[1])
+                 : "v"(a0), "n"(OFF), "n"(OFF + D)
+                 : "memory");
+}
 template <int OFF>
 __device__ __forceinline__ void read_op_h(unsigned a0, unsigned a1, Op &o) {
     asm volatile("ds_read_b64_tr_b16 %0, %2 offset:%4\n\tds_read_b64_tr_b16 %1, %3 offset:%4\n\ts_waitcnt lgkmcnt(0)"
@@ -113,10 +137,21 @@ template <> struct StageType<true> { typedef u32x2 type; };
 
 // NW waves per workgroup (5: a wave owns a K-step and every column tile; 10: two waves share a K-step's tiles);
 // NIMG LDS images per workgroup (1: two barriers per item; 2: one)
-template <int CINL, bool BF, bool CH, int NW, int NIMG>
+// SH (model_common.hpp): Generic, or Canon32 -- the canonical layout and uniform scenes of kCanonV = kWgradChunkV
+// pedestrians in batch order (no num_peds, no sorted list, the folded workspace stride: wgrad_canon32 below).  An item is
+// then a scene index and a full image: the saved rows have the image's own strides, so staging quad e of an item is its
+// quad e in memory (one thread-constant offset, no column predicate), the K slots and every operand address are
+// computed once in front of the item loop, and the second half of an operand lies 16 records behind the first (an
+// instruction immediate).  The item walk, the workgroup count, the slab rows and the order of every floating-point
+// operation are the Generic form's: the results are bitwise equal.
+template <int CINL, bool BF, bool CH, int NW, int NIMG, Shape SH>
 __device__ __forceinline__ void layer(const WgradArgs &a, const int32_t *__restrict__ order,
                                       const int32_t *__restrict__ order_peds, const int32_t *__restrict__ num_peds,
                                       const int32_t *__restrict__ key_start, int layer, unsigned char *sm, int wg, int nwg) {
+    constexpr bool K32 = SH == Shape::Canon32;
+    static_assert(SH != Shape::Canon && !(K32 && CH), "Generic, or Canon32 with one chunk per scene");
+    static_assert(kCanonV == kWgradChunkV && save_sw(kCanonV, BF) == SWI && save_vw(kCanonV, BF) == VWI,
+                  "Canon32: the saved rows have the image's strides");
     constexpr int NTH = NW * 64;
     constexpr int HS = NW / 5;                       // waves sharing a K-step
     constexpr int QPT = CINL / 4;                    // channel quads of a tap
@@ -125,7 +160,7 @@ __device__ __forceinline__ void layer(const WgradArgs &a, const int32_t *__restr
     constexpr int T0 = HS == 1 ? NT : (NT + 1) / 2;  // tiles of the first wave of a K-step
     constexpr int TA = (kATasks + NTH - 1) / NTH, TZ = (kZTasks + NTH - 1) / NTH;
     const ModelLayout &L = a.lay;
-    const int V = a.V, tid = threadIdx.x, lane = tid & 63;
+    const int V = K32 ? kCanonV : a.V, tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int ks = wave / HS, hf = wave - ks * HS;
     const int kg = lane >> 4, rq = (lane & 15) >> 2, cp = lane & 3;   // tr reads: K sub-chunk, position and channel quad
@@ -143,8 +178,15 @@ __device__ __forceinline__ void layer(const WgradArgs &a, const int32_t *__restr
             items += more < 0 ? 0 : (more > a.N ? a.N : more);
         }
     }
-    const int64_t plane_off = ws_plane_off(L, V, layer), dzs_floats = dz_slot(V);
+    const int64_t plane_off = K32 ? ws_plane_off(kCanonLayout, kCanonV, 0) + (int64_t)layer * plane_slot(kCanonV)
+                                  : ws_plane_off(L, V, layer);
+    const int64_t dzs_floats = dz_slot(V);
     const bool bf = BF;
+    // Canon32: the item of round r is scene r nwg + wg (walk_item without a sorted list), valid while it is below N; its
+    // plane and its dz advance by a constant stride per round
+    constexpr int64_t kDzScene = (int64_t)(kCanonLayout.L + 1) * dz_slot(kCanonV);
+    auto plane32 = [&](int n) { return a.ws + n * kCanonWs32 + plane_off; };
+    auto dz32 = [&](int n) { return a.dzg + n * kDzScene + layer * (int64_t)dz_slot(kCanonV); };
     auto fetch = [&](int r) -> Item {
         Item it{0, 0, 0, 0, false, nullptr, nullptr};
         const int at = walk_item(r, wg, nwg, items, order != nullptr && a.serpentine);
@@ -201,6 +243,22 @@ __device__ __forceinline__ void layer(const WgradArgs &a, const int32_t *__restr
         rowz[u] = row * 3 * TF;
         colz[u] = e < kZTasks ? ((col * 3 + q) * TF) | (col << 16) : -1;
     }
+    // Canon32: quad e of the image is quad e of the saved array (row strides SWI / VWI); a thread without a task reads the
+    // item's first bytes and writes nothing
+    auto load32 = [&](bool ok, const float *pl, const float *dz, Stage &s) {
+        const bool live = ok && !STG_SKIP(a, 64);
+        const float *pa = live ? pl : a.ws, *pz = live ? dz : a.ws;
+#pragma unroll
+        for (int u = 0; u < TA; ++u) {
+            const int e = tid + u * NTH;
+            s.a[u] = *reinterpret_cast<const StageV *>(pa + (e < kATasks ? e * TF : 0));
+        }
+#pragma unroll
+        for (int u = 0; u < TZ; ++u) {
+            const int e = tid + u * NTH;
+            s.z[u] = *reinterpret_cast<const StageV *>(pz + (e < kZTasks ? e * TF : 0));
+        }
+    };
     auto load = [&](const Item &it, Stage &s) {
         const bool live = it.valid && !STG_SKIP(a, 64);
         const int lima = live ? it.vc + 2 : 0, limz = live ? it.vc : 0;
@@ -238,6 +296,15 @@ __device__ __forceinline__ void layer(const WgradArgs &a, const int32_t *__restr
 #pragma unroll
         for (int u = 0; u < TZ; ++u)
             if (colz[u] >= 0 && (colz[u] >> 16) < it.vc) put(img + dstz[u], s.z[u]);
+    };
+    auto convert32 = [&](bool ok, const Stage &s, unsigned char *img) {
+        if (!ok || STG_SKIP(a, 64)) return;
+#pragma unroll
+        for (int u = 0; u < TA; ++u)
+            if (tid + u * NTH < kATasks) put(img + dsta[u], s.a[u]);
+#pragma unroll
+        for (int u = 0; u < TZ; ++u)
+            if (tid + u * NTH < kZTasks) put(img + dstz[u], s.z[u]);
     };
 
     // ---- operands ---------------------------------------------------------------------------------------------------
@@ -311,6 +378,57 @@ __device__ __forceinline__ void layer(const WgradArgs &a, const int32_t *__restr
         (void)zm; (void)zl;
         __builtin_amdgcn_s_setprio(0);
     };
+    // Canon32: every item has C * 32 = five full K-steps, so no K slot is past the end (the zero record is never
+    // addressed) and slot p = 32 ks + 16 rd + 4 kg + rq is row ks, column 16 rd + 4 kg + rq: the rd = 1 half of an operand
+    // lies 16 records behind the rd = 0 half.  za32 / ta32[k]: the lane's rd = 0 addresses in image 0; only the bias quad
+    // of the last column tile (the ones record for both halves) needs a second address, tb32.
+    constexpr int kHalf = 16 * kRec;
+    static_assert(kImageBytes + kHalf + 3 * kPiece < 65536, "the operand offsets are 16-bit immediates");
+    unsigned za32 = 0u, tb32 = 0u, ta32[T0];
+#pragma unroll
+    for (int k = 0; k < T0; ++k) ta32[k] = 0u;
+    if constexpr (K32) {
+        const int ww = 4 * kg + rq;
+        za32 = lds0 + (unsigned)((kARecs + ks * VWI + ww) * kRec + 8 * cp);
+#pragma unroll
+        for (int k = 0; k < T0; ++k) {
+            ta32[k] = lds0 + (unsigned)((ks * SWI + ww) * kRec) + (unsigned)toff[k];
+            if (hf * T0 + k == NT - 1) {
+                tb32 = ta32[k] + (unsigned)kHalf;
+                if (ones_last) ta32[k] = tb32 = lds0 + (unsigned)(kOnesRec * kRec + 8 * cp);
+            }
+        }
+    }
+    auto compute32 = [&](bool ok, unsigned ib) {
+        if (!ok || STG_SKIP(a, 128)) return;
+        __builtin_amdgcn_s_setprio(2);
+        Op z, x0;
+        u32x4 zh, zm = u32x4{0u, 0u, 0u, 0u}, zl = zm;
+        if constexpr (BF) {
+            read_op1_h<0, kHalf>(za32 + ib, z);
+            zh = cat(z.h);
+        } else {
+            read_op1<0, kHalf>(za32 + ib, z);
+            zh = cat(z.h); zm = cat(z.m); zl = cat(z.l);
+        }
+#pragma unroll
+        for (int k = 0; k < T0; ++k) {
+            if (hf * T0 + k < NT) {
+                const bool last = hf * T0 + k == NT - 1;       // (uniform over the wave)
+                if constexpr (BF) {
+                    if (last) read_op_h<0>(ta32[k] + ib, tb32 + ib, x0);
+                    else read_op1_h<0, kHalf>(ta32[k] + ib, x0);
+                    mma1(zh, cat(x0.h), acc[k]);
+                } else {
+                    if (last) read_op<0>(ta32[k] + ib, tb32 + ib, x0);
+                    else read_op1<0, kHalf>(ta32[k] + ib, x0);
+                    mma6(zh, zm, zl, x0, acc[k]);
+                }
+            }
+        }
+        (void)zm; (void)zl;
+        __builtin_amdgcn_s_setprio(0);
+    };
 
     // ---- constants of the images: everything zero (the plane's border rows stay so), the ones record --------------------
     for (int i = 0; i < NIMG; ++i) {
@@ -324,22 +442,42 @@ __device__ __forceinline__ void layer(const WgradArgs &a, const int32_t *__restr
 
     // ---- the pipeline -------------------------------------------------------------------------------------------------
     const int rounds = (items + nwg - 1) / nwg;        // (uniform over the workgroup: the barriers match)
-    Item cur = fetch(0), nxt = fetch(1);
     Stage s;
 #pragma unroll
     for (int u = 0; u < TA; ++u) s.a[u] = StageV{};
 #pragma unroll
     for (int u = 0; u < TZ; ++u) s.z[u] = StageV{};
-    load(cur, s);
-    for (int r = 0; r < rounds; ++r) {
-        const int ib = NIMG == 1 ? 0 : (r & 1) * kImageBytes;
-        if (NIMG == 1 && r > 0) team_barrier();        // every wave has read the previous item
-        convert(cur, s, sm + ib);
-        load(nxt, s);
-        team_barrier();
-        compute(cur, lds0 + (unsigned)ib);
-        cur = nxt;
-        nxt = fetch(r + 2);
+    if constexpr (K32) {
+        int n = wg;                                    // the scene of the round whose quads are being fetched
+        const float *pl = plane32(n), *dz = dz32(n);
+        bool cur = n < a.N;
+        load32(cur, pl, dz, s);
+        for (int r = 0; r < rounds; ++r) {
+            const int ib = NIMG == 1 ? 0 : (r & 1) * kImageBytes;
+            if (NIMG == 1 && r > 0) team_barrier();    // every wave has read the previous item
+            convert32(cur, s, sm + ib);
+            n += nwg;
+            pl += nwg * kCanonWs32;
+            dz += nwg * kDzScene;
+            const bool nxt = n < a.N;
+            load32(nxt, pl, dz, s);
+            team_barrier();
+            compute32(cur, (unsigned)ib);
+            cur = nxt;
+        }
+    } else {
+        Item cur = fetch(0), nxt = fetch(1);
+        load(cur, s);
+        for (int r = 0; r < rounds; ++r) {
+            const int ib = NIMG == 1 ? 0 : (r & 1) * kImageBytes;
+            if (NIMG == 1 && r > 0) team_barrier();    // every wave has read the previous item
+            convert(cur, s, sm + ib);
+            load(nxt, s);
+            team_barrier();
+            compute(cur, lds0 + (unsigned)ib);
+            cur = nxt;
+            nxt = fetch(r + 2);
+        }
     }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -382,25 +520,31 @@ __device__ __forceinline__ void layer(const WgradArgs &a, const int32_t *__restr
     }
 }
 
-template <bool BF, bool CH, int NW, int NIMG>
+template <bool BF, bool CH, int NW, int NIMG, Shape SH = Shape::Generic>
 __global__ __launch_bounds__(NW * 64, NW == 5 ? 5 : 6) void txp_wgrad_bf16_kernel(const WgradArgs a, const int32_t *__restrict__ order,
                                                                    const int32_t *__restrict__ order_peds,
                                                                    const int32_t *__restrict__ num_peds,
                                                                    const int32_t *__restrict__ key_start) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smb[];
     int l = 0;
-    while (l < a.lay.L && (int)blockIdx.x >= a.wg_begin[l + 1]) ++l;
+    const int hidden = SH == Shape::Canon32 ? kCanonLayout.L : a.lay.L;
+    while (l < hidden && (int)blockIdx.x >= a.wg_begin[l + 1]) ++l;
     const int wg = (int)blockIdx.x - a.wg_begin[l];
     const int nwg = a.wg_begin[l + 1] - a.wg_begin[l];
     if (l == 0)
-        layer<Cfg::T, BF, CH, NW, NIMG>(a, order, order_peds, num_peds, key_start, l, smb, wg, nwg);
+        layer<Cfg::T, BF, CH, NW, NIMG, SH>(a, order, order_peds, num_peds, key_start, l, smb, wg, nwg);
     else
-        layer<Cfg::P, BF, CH, NW, NIMG>(a, order, order_peds, num_peds, key_start, l, smb, wg, nwg);
+        layer<Cfg::P, BF, CH, NW, NIMG, SH>(a, order, order_peds, num_peds, key_start, l, smb, wg, nwg);
 }
 
 
 }  // namespace
 
+// This file is compiled twice (the library's build keeps the two sets of kernels apart: they compile side by side, and a
+// check of the generic kernels' code sees those alone): as txp_wgrad_bf16.o with the Generic kernels, the geometry and the
+// launcher, and through txp_wgrad_bf16_canon32.hip (STG_K2_CANON32_TU) with the Canon32 kernels and their launcher only.
+// tools/micro/k2_bench.hip (STG_K2_ALL_SHAPES) compiles both parts into one harness.
+#ifndef STG_K2_CANON32_TU
 bool wgrad_bf16_fits(const ModelLayout &L, int V) {
     (void)V;                                           // (every V: larger scenes are cut into <= 32-column chunks)
     return !(L.flags & STG_OPT_F32_MFMA);
@@ -420,12 +564,45 @@ void wgrad_bf16_geom(WgradGeom *g, const ModelLayout &L, int V) {
     if (lds < row) lds = row;
     g->lds = lds;
 }
+#endif
+
+#if defined(STG_K2_CANON32_TU) || defined(STG_K2_ALL_SHAPES)
+// the Canon32 kernel of a storage mode in its workgroup shape (what wgrad_bf16_geom picks; the harness: both shapes)
+int launch_txp_wgrad_bf16_canon32(const WgradArgs &w, const WgradGeom &g, hipStream_t st) {
+    const Launch lc{"txp_wgrad_bf16 (Canon32)", dim3(g.grid), dim3(g.waves * 64), g.lds, st};
+    const bool bf = (w.lay.flags & STG_OPT_BF16_STORE) != 0;
+    const bool five = g.waves == 5 && g.nbuf == 1, ten = g.waves == 10 && g.nbuf == 2;
+    constexpr Shape S = Shape::Canon32;
+#ifdef STG_K2_ALL_SHAPES
+    if (five || ten) {
+        const auto k = five ? (bf ? txp_wgrad_bf16_kernel<true, false, 5, 1, S> : txp_wgrad_bf16_kernel<false, false, 5, 1, S>)
+                            : (bf ? txp_wgrad_bf16_kernel<true, false, 10, 2, S> : txp_wgrad_bf16_kernel<false, false, 10, 2, S>);
+        return launch(lc, k, w, w.order, w.order_peds, w.num_peds, w.key_start);
+    }
+#else
+    if (bf ? five : ten)
+        return launch(lc, bf ? txp_wgrad_bf16_kernel<true, false, 5, 1, S> : txp_wgrad_bf16_kernel<false, false, 10, 2, S>, w,
+                      w.order, w.order_peds, w.num_peds, w.key_start);
+#endif
+    return fail(STG_EINVAL, "txp_wgrad_bf16 (Canon32): no kernel for %d waves / %d images", g.waves, g.nbuf);
+}
+#endif
+
+#ifndef STG_K2_CANON32_TU
+// Canon32 serves exactly the batches whose runtime values equal the ones it has folded: the canonical model, uniform
+// scenes of kCanonV pedestrians in batch order, the folded workspace stride -- whatever N and whichever step path.
+// STG_OPT_GENERIC_WGRAD keeps the Generic kernel (same results bit for bit).
+static bool wgrad_canon32(const WgradArgs &w) {
+    return is_canonical(w.lay) && w.V == kCanonV && !w.num_peds && !w.order && !w.key_start && w.ws_stride == kCanonWs32 &&
+           !(w.lay.flags & STG_OPT_GENERIC_WGRAD);
+}
 
 // the kernel for a storage mode (B), chunked scenes (ch) and a workgroup shape of NW waves and NI images
 template <bool B, int NW, int NI>
 static auto wgrad_bf16_kernel(bool ch) { return ch ? txp_wgrad_bf16_kernel<B, true, NW, NI> : txp_wgrad_bf16_kernel<B, false, NW, NI>; }
 
 int launch_txp_wgrad_bf16(const WgradArgs &w, const WgradGeom &g, hipStream_t st) {
+    if (wgrad_canon32(w)) return launch_txp_wgrad_bf16_canon32(w, g, st);
     const Launch lc{"txp_wgrad_bf16", dim3(g.grid), dim3(g.waves * 64), g.lds, st};
     const bool bf = (w.lay.flags & STG_OPT_BF16_STORE) != 0, ch = w.V > kWgradChunkV;
     const bool five = g.waves == 5 && g.nbuf == 1, ten = g.waves == 10 && g.nbuf == 2;
@@ -442,5 +619,6 @@ int launch_txp_wgrad_bf16(const WgradArgs &w, const WgradGeom &g, hipStream_t st
 #endif
     return fail(STG_EINVAL, "txp_wgrad_bf16: no kernel for %d waves / %d images", g.waves, g.nbuf);
 }
+#endif
 
 }  // namespace stg

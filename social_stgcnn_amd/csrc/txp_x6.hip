@@ -16,15 +16,9 @@ namespace {
 
 constexpr int C = Cfg::C, P = Cfg::P, T = Cfg::T;
 
-// What the solo kernels are compiled for.  Generic: the layout and the crowd are kernel arguments (every model the x6
-// kernels fit).  Canon: the layout is kCanonLayout (model_common.hpp) -- every parameter and workspace offset a
-// constant, none of them held in SGPRs -- the crowd still a runtime value (ragged batches).  Canon32: kCanonLayout and
-// uniform scenes of exactly kCanonV pedestrians, no num_peds: the workspace stride, the aggregation offsets, the saved
-// row strides, the tile count and the lane geometry are constants as well.  The host picks a folded shape only when the
-// runtime values it passes equal the folded ones (canon_shape below).
-enum class Shape { Generic, Canon, Canon32 };
-constexpr int kCanonV = 32;
-constexpr int64_t kCanonWs32 = ws_floats_per_scene(kCanonLayout, kCanonV);
+// What the solo kernels are compiled for: Shape (model_common.hpp).  Generic serves every model the x6 kernels fit; for
+// Canon32 the aggregation offsets are constants too.  The host picks a folded shape only when the runtime values it
+// passes equal the folded ones (canon_shape below).
 // the aggregation launch's outputs of a Canon32 batch: in the workspace (training) or the scratch buffer (inference)
 constexpr int64_t kCanonAggStride32[2] = {(int64_t)(Cfg::CIN0 + 1) * Cfg::T * kCanonV, kCanonWs32};
 constexpr int64_t kCanonAggAx32[2] = {0, kCanonLayout.ws_hdr_floats + (int64_t)kCanonLayout.blk[0].ws_ax * kCanonV};

@@ -190,12 +190,14 @@ class FlatPack:
 #   f32_mfma    the fp32-MFMA kernels where the default runs the exact bf16-pipe ones (STG_OPT_F32_MFMA): A/B measurements
 #   separate_fb the training step (stg_model_step) keeps the forward and the backward scene kernels as two launches where
 #               one launch serves both (STG_OPT_SEPARATE_FB): same results bit for bit, A/B measurements and tests
+#   generic_wgrad keeps the generic weight-gradient kernel where the one compiled for the canonical model with uniform scenes
+#               of 32 pedestrians serves the batch (STG_OPT_GENERIC_WGRAD): same results bit for bit, A/B measurements and tests
 class KernelOptions(dict):
     """The launch options of ONE model: `model.options = ops.KernelOptions(bf16_store=True)` makes that model (and the
     Trainer / EpochRunner driving it) run with its own choices, whatever other models in the process do.  A model without
     an `options` attribute of its own uses the process-wide defaults, `ops.OPTIONS`."""
     DEFAULTS = {"wg_path": False, "split_bf16": False, "wg_waves": 0, "wave_path": False, "bf16_store": False,
-                "f32_mfma": False, "separate_fb": False}
+                "f32_mfma": False, "separate_fb": False, "generic_wgrad": False}
 
     def __init__(self, **kw):
         bad = set(kw) - set(self.DEFAULTS)
@@ -215,7 +217,8 @@ def make_desc(n_stgcnn, n_txpcnn, c_in, c_out, t_obs, t_pred, kt, residual0, use
              | (_lib.OPT_WAVE_PATH if o["wave_path"] else 0)
              | (_lib.OPT_BF16_STORE if o["bf16_store"] else 0)
              | (_lib.OPT_F32_MFMA if o["f32_mfma"] else 0)
-             | (_lib.OPT_SEPARATE_FB if o["separate_fb"] else 0))
+             | (_lib.OPT_SEPARATE_FB if o["separate_fb"] else 0)
+             | (_lib.OPT_GENERIC_WGRAD if o["generic_wgrad"] else 0))
     return ModelDesc(n_stgcnn, n_txpcnn, c_in, c_out, t_obs, t_pred, kt, residual0, 1 if use_mdn else 0,
                      1 if training else 0, eps, momentum, flags, int(o["wg_waves"]))
 

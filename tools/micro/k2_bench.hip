@@ -1,6 +1,9 @@
 // k2_bench: the weight-gradient kernel (K2) alone, on synthetic saved arrays -- A/B of the shipped launcher
 // (stg::launch_txp_wgrad, from libstgcnn_hip.so) against the workgroup shapes of csrc/txp_wgrad_bf16.hip as it stands in the tree, checked against each other
 // and against an fp64 host sum (N <= 64 always; any N with K2_FP64=1 -- about 10 s of host work at 4096 x 128).
+// A uniform V = 32 batch (ragged=0 sorted=0) is served by the kernel compiled for that shape (Canon32): the harness then also
+// runs the library's launcher with STG_OPT_GENERIC_WGRAD and prints both times and the largest difference between the two
+// slabs, which must be 0 -- the two forms add the same numbers in the same order.
 //   build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I social_stgcnn_amd/csrc -I include tools/micro/k2_bench.hip \
 //          -L social_stgcnn_amd/csrc -lstgcnn_hip -Wl,-rpath,'$ORIGIN/../../social_stgcnn_amd/csrc' -o tools/micro/k2_bench
 //   run:   tools/micro/k2_bench [N=2048] [V=32] [ragged=0] [bf16=0] [sorted=0]
@@ -11,10 +14,12 @@
 #define wgrad_bf16_fits dev_wgrad_bf16_fits
 #define wgrad_bf16_geom dev_wgrad_bf16_geom
 #define launch_txp_wgrad_bf16 dev_launch_txp_wgrad_bf16
+#define launch_txp_wgrad_bf16_canon32 dev_launch_txp_wgrad_bf16_canon32
 #include "../../social_stgcnn_amd/csrc/txp_wgrad_bf16.hip"
 #undef wgrad_bf16_fits
 #undef wgrad_bf16_geom
 #undef launch_txp_wgrad_bf16
+#undef launch_txp_wgrad_bf16_canon32
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -153,11 +158,12 @@ int main(int argc, char **argv) {
     };
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
-    auto run = [&](const char *name, auto &&launch, const WgradGeom &g) -> std::vector<double> {
+    auto run = [&](const char *name, auto &&launch, const WgradGeom &g, std::vector<float> *keep = nullptr) -> std::vector<double> {
         CK(hipMemset(d_slab, 0, slab_floats * 4));
         if (launch() != STG_OK) { printf("%s: launch failed: %s\n", name, stg_last_error()); exit(1); }
         CK(hipDeviceSynchronize());
         CK(hipMemcpy(slab.data(), d_slab, slab_floats * 4, hipMemcpyDeviceToHost));
+        if (keep) *keep = slab;
         auto sums = sum_rows(slab, g, nl);
         for (int i = 0; i < 5; ++i) launch();
         CK(hipDeviceSynchronize());
@@ -174,7 +180,22 @@ int main(int argc, char **argv) {
     WgradGeom g0{};
     if (!wgrad_geom(L, N, V, &g0)) { printf("wgrad_geom failed\n"); return 1; }
     const WgradArgs w0 = args(g0);
-    const auto ref = run("shipped (launch_txp_wgrad)", [&] { return launch_txp_wgrad(w0, g0, 0); }, g0);
+    std::vector<float> slab_shipped;
+    const auto ref = run("shipped (launch_txp_wgrad)", [&] { return launch_txp_wgrad(w0, g0, 0); }, g0, &slab_shipped);
+    if (g0.bf16mma && wgrad_canon32(w0)) {               // (the launcher's own predicate, compiled into this harness)
+        WgradArgs wg = w0;
+        wg.lay.flags |= STG_OPT_GENERIC_WGRAD;
+        std::vector<float> slab_generic;
+        run("shipped, generic kernel", [&] { return launch_txp_wgrad(wg, g0, 0); }, g0, &slab_generic);
+        double worst = 0;
+        size_t differ = 0;
+        for (size_t i = 0; i < slab_floats; ++i) {
+            const double e = std::fabs((double)slab_shipped[i] - (double)slab_generic[i]);
+            differ += !(e == 0);
+            if (!(e <= worst)) worst = e;
+        }
+        printf("    canon32 against generic: max |diff| %.3e (%zu of %zu slab floats differ)\n", worst, differ, slab_floats);
+    }
     double refmax = 0;
     for (double v : ref) refmax = std::fmax(refmax, std::fabs(v));
     const int nvar = 2;
