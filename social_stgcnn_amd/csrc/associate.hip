@@ -36,12 +36,11 @@ struct AssocRule {
     int max_miss;
 };
 
-// One push of one stream by one workgroup of kThreads threads: detection j = (det_id[j * id_stride] (written),
-// det_xy[j * xy_stride], det_xy[j * xy_stride + 1]), j < min(count, M_max).
+// One push of one stream by one workgroup of kThreads threads: the positions of the detections j < min(count, M_max)
+// are read, their ids written.
 template <int kThreads>
-__device__ __forceinline__ void associate_body(int64_t *__restrict__ det_id, int64_t id_stride,
-                                               const double *__restrict__ det_xy, int64_t xy_stride, int count,
-                                               int M_max, const AssocState st, int C, const AssocRule rule) {
+__device__ __forceinline__ void associate_body(const DetectionsOut &det, int count, int M_max, const AssocState st, int C,
+                                               const AssocRule rule) {
     extern __shared__ __align__(16) unsigned char lds[];
     double *tq = reinterpret_cast<double *>(lds);               // (C,2) predicted positions
     double *dp = tq + 2 * (size_t)C;                             // (M_max,2) rounded detections
@@ -73,8 +72,8 @@ __device__ __forceinline__ void associate_body(int64_t *__restrict__ det_id, int
         tstate[s] = kUnknown;
     }
     for (int j = tid; j < m; j += kThreads) {
-        dp[2 * j] = round_pos(det_xy[j * xy_stride], rule.scale);
-        dp[2 * j + 1] = round_pos(det_xy[j * xy_stride + 1], rule.scale);
+        dp[2 * j] = round_pos(det.x(j), rule.scale);
+        dp[2 * j + 1] = round_pos(det.y(j), rule.scale);
         dstate[j] = kUnknown;
     }
     __syncthreads();
@@ -182,7 +181,7 @@ __device__ __forceinline__ void associate_body(int64_t *__restrict__ det_id, int
             st.trk_pos[2 * s + 1] = py;
             st.trk_miss[s] = 0;
             st.trk_hits[s] = hits + 1;
-            det_id[j * id_stride] = id;
+            det.id_at(j) = id;
             tgate[s] = 0;
         } else if (miss + 1 > rule.max_miss) {
             st.trk_id[s] = -1;
@@ -214,7 +213,7 @@ __device__ __forceinline__ void associate_body(int64_t *__restrict__ det_id, int
         const bool nw = j < m && !assoc_taken(dstate[j]);
         const int r = block_rank<kThreads>(nw, n_new, &tot, wave_cnt);
         if (nw) {
-            det_id[j * id_stride] = next0 + r;
+            det.id_at(j) = next0 + r;
             if (r < n_free) {
                 const int s = list[r];
                 st.trk_id[s] = next0 + r;
@@ -236,26 +235,22 @@ __device__ __forceinline__ void associate_body(int64_t *__restrict__ det_id, int
     }
 }
 
-__global__ __launch_bounds__(kAssocThreads) void associate_kernel(int64_t *__restrict__ det_id,
-                                                                  const double *__restrict__ det_xy,
-                                                                  const int32_t *__restrict__ det_count, int M_max,
-                                                                  AssocState st, int C, AssocRule rule) {
-    associate_body<kAssocThreads>(det_id, 1, det_xy, 2, det_count[0], M_max, st, C, rule);
+__global__ __launch_bounds__(kAssocThreads) void associate_kernel(
+    int64_t *__restrict__ det_id, const double *__restrict__ det_xy, const int32_t *__restrict__ det_count, int M_max,
+    AssocState st, int C, AssocRule rule) {
+    associate_body<kAssocThreads>({det_id, 1, det_xy, 2}, det_count[0], M_max, st, C, rule);
 }
 
-__global__ __launch_bounds__(kAssocStreamThreads) void associate_streams_kernel(
-    int64_t *__restrict__ det_id, int64_t id_stride, const double *__restrict__ det_xy, int64_t xy_stride, int M_total,
-    const int32_t *__restrict__ det_start, const int32_t *__restrict__ pushed, int M_max, AssocState st, int C,
-    AssocRule rule) {
+__global__ __launch_bounds__(kAssocStreamThreads) void associate_streams_kernel(DetectionsOut det, Tick tick, int M_max,
+                                                                                AssocState st, int C, AssocRule rule) {
     const int b = blockIdx.x;
-    if (pushed[b] == 0) return;                             // uniform over the block, ahead of the first barrier
+    if (tick.pushed_at(b) == 0) return;                     // uniform over the block, ahead of the first barrier
     int lo;
-    const int count = det_range(det_start, b, M_total, lo);
+    const int count = tick.range(b, lo);
     const AssocState mine = {st.trk_id + (int64_t)b * C,   st.trk_pos + (int64_t)b * C * 2, st.trk_vel + (int64_t)b * C * 2,
                              st.trk_miss + (int64_t)b * C, st.trk_hits + (int64_t)b * C,    st.next_id + b,
                              st.assoc_flags + b};
-    associate_body<kAssocStreamThreads>(det_id + lo * id_stride, id_stride, det_xy + lo * xy_stride, xy_stride, count,
-                                        M_max, mine, C, rule);
+    associate_body<kAssocStreamThreads>(det.from(lo), count, M_max, mine, C, rule);
 }
 
 // the checks the two entry points share: sizes (above the limits: STG_EUNSUPPORTED), the rule, the pointers
@@ -299,18 +294,17 @@ int stg_associate_streams(int64_t *det_id, int64_t id_stride, const double *det_
                           double *trk_pos, double *trk_vel, int32_t *trk_miss, int32_t *trk_hits, int64_t *next_id,
                           int32_t *assoc_flags, int C, double scale, double gate2, double gate_new2, int max_miss,
                           void *stream) {
-    STG_REQUIRE(NS >= 1 && NS <= STG_TRACK_MAX_STREAMS && M_total >= 0 && M_total <= STG_TRACK_MAX_TOTAL_DETECTIONS &&
-                    id_stride >= 1 && xy_stride >= 2,
-                STG_EINVAL, "stg_associate_streams: bad sizes NS=%d M_total=%d strides %lld/%lld", NS, M_total,
-                (long long)id_stride, (long long)xy_stride);
+    int rc = stg::stream_args("stg_associate_streams", NS, M_total, id_stride, xy_stride);
+    if (rc != STG_OK) return rc;
     const stg::AssocState st = {trk_id, trk_pos, trk_vel, trk_miss, trk_hits, next_id, assoc_flags};
-    const int rc = stg::assoc_args("stg_associate_streams", M_max, C, gate2, gate_new2, max_miss, det_id, det_xy, st);
+    rc = stg::assoc_args("stg_associate_streams", M_max, C, gate2, gate_new2, max_miss, det_id, det_xy, st);
     if (rc != STG_OK) return rc;
     STG_REQUIRE(det_start && pushed, STG_EINVAL, "stg_associate_streams: null pointer");
     return stg::launch({"stg_associate_streams", dim3(NS), dim3(stg::kAssocStreamThreads), stg::assoc_lds(C, M_max),
                         stg::as_stream(stream), 63 * 1024},
-                       stg::associate_streams_kernel, det_id, id_stride, det_xy, xy_stride, M_total, det_start, pushed,
-                       M_max, st, C, stg::AssocRule{scale, gate2, gate_new2, max_miss});
+                       stg::associate_streams_kernel, stg::DetectionsOut{det_id, id_stride, det_xy, xy_stride},
+                       stg::Tick{det_start, pushed, M_total}, M_max, st, C,
+                       stg::AssocRule{scale, gate2, gate_new2, max_miss});
 }
 
 }  // extern "C"

@@ -5,7 +5,7 @@
 // FIRST DETECTION WINS: the detections of a repeated id are neighbours in ascending index, and the lower bound of the
 // id (det_find) is its first detection.  The scene of a push and the truth of a score are both taken there.
 #pragma once
-#include "common.hpp"
+#include "live_args.hpp"
 
 namespace stg {
 
@@ -21,11 +21,12 @@ __host__ __device__ __forceinline__ int det_sort_n(int m) {
 }
 static inline size_t det_sort_lds(int m2) { return (size_t)m2 * (sizeof(int64_t) + sizeof(int32_t)); }
 
-// (key, kidx) <- det_id[p * id_stride].  No barrier: the caller puts its own work ahead of the one det_sort needs
-__device__ __forceinline__ void det_load(int64_t *key, int32_t *kidx, const int64_t *__restrict__ det_id,
-                                         int64_t id_stride, int m, int n2, int tid, int nt) {
+// (key, kidx) <- the first m ids.  No barrier: the caller puts its own work ahead of the one det_sort needs
+template <class Id>
+__device__ __forceinline__ void det_load(int64_t *key, int32_t *kidx, const DetectionsOf<Id> &det, int m, int n2,
+                                         int tid, int nt) {
     for (int p = tid; p < n2; p += nt) {
-        key[p] = p < m ? det_id[p * id_stride] : INT64_MAX;
+        key[p] = p < m ? det.id_at(p) : INT64_MAX;
         kidx[p] = p;
     }
 }
@@ -62,13 +63,6 @@ __device__ __forceinline__ int det_find(const int64_t *key, int n, int64_t id) {
         else hi = mid;
     }
     return lo < n && key[lo] == id ? lo : -1;
-}
-
-// stream b's detections of a packed tick, det_start[b] .. det_start[b+1]-1 clamped to [0, M_total): first, and the count
-__device__ __forceinline__ int det_range(const int32_t *__restrict__ det_start, int b, int M_total, int &first) {
-    const int lo = det_start[b], hi = det_start[b + 1];
-    first = lo < 0 ? 0 : (lo > M_total ? M_total : lo);
-    return (hi < first ? first : (hi > M_total ? M_total : hi)) - first;
 }
 
 }  // namespace stg

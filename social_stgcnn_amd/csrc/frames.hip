@@ -15,7 +15,7 @@
 //                           offsets and pushed flags are read from device memory, so one captured graph serves a tick.
 // The pushes sort their detections and look ids up with detections.hpp, as the score kernels do; the
 // slot assignment, the padding of a scene, the per-stream wrapper and the host's stream checks are those of every push
-// (track_rule.hpp).
+// (track_rule.hpp), the argument records those of the whole live path (live_args.hpp).
 //
 // Partially observed tracks: TrackRule (track_rule.hpp) admits a pedestrian with a short history or tracker gaps
 // and fills the frames it missed.  stg_fill_tracks applies the fill to a batch in place; the *_rule entry points are
@@ -188,23 +188,32 @@ __global__ __launch_bounds__(64) void frame_scenes_rule_kernel(
 }
 
 // ---- live streams ------------------------------------------------------------------------------------------------
-// One push of one stream by one workgroup of kThreads threads: `count` detections (more than M_max: the first M_max,
-// flag TRUNCATED), detection j = (det_id[j * id_stride], det_xy[j * xy_stride], det_xy[j * xy_stride + 1]) -- strides
-// 1 and 2 for the single stream's (M), (M,2) arrays --; the stream's state slot_id (S), mask (S), ring (T_obs,S,2),
-// head_flags (2); its scene obs_abs (T_obs,V,2), out_ids (V), *num_peds.  Returns (in every thread) the flags.
+// The strict scene's column `obs` (step stride V * 2) <- the T_obs - 1 earlier ring rows (stride S * 2) of a slot, oldest
+// first.  __restrict__ PARAMETERS: a record's members cannot say that scene and ring do not alias.
+__device__ __forceinline__ void gather_ring(double *__restrict__ obs, const double *__restrict__ ring, int head, int S,
+                                            int T_obs, int V) {
+    for (int t = 0; t < T_obs - 1; ++t) {
+        const int row = (head + 1 + t) % T_obs;           // head - (T_obs - 1 - t) mod T_obs
+        obs[(int64_t)t * V * 2] = ring[(int64_t)row * S * 2];
+        obs[(int64_t)t * V * 2 + 1] = ring[(int64_t)row * S * 2 + 1];
+    }
+}
+
+// One push of one stream by one workgroup of kThreads threads: `count` detections of `det` (more than M_max: the first
+// M_max, flag TRUNCATED), the stream's own state and scene (live_args.hpp).  Returns (in every thread) the flags.
 // LDS layout (dynamic): sort keys (M2 x int64), sort indices (M2 x int32), det_slot (M_max x int32),
 // slot masks (S x uint32), free slots (S x int32)
-// kRule: the scene phase admits and fills by `rule` and writes the presence bits of every scene slot to seen (V);
+// kRule: the scene phase admits and fills by `rule` and writes the presence bits of every scene slot to out.seen (V);
 // without it (the strict entry points) neither is looked at.
 template <int kThreads, bool kRule>
-__device__ __forceinline__ int track_push_body(const int64_t *__restrict__ det_id, int64_t id_stride,
-                                               const double *__restrict__ det_xy, int64_t xy_stride, int count,
-                                               int M_max, int M2, int64_t *__restrict__ slot_id,
-                                               uint32_t *__restrict__ mask, double *__restrict__ ring,
-                                               int32_t *__restrict__ head_flags, int S, int T_obs, double scale, int V,
-                                               double *__restrict__ obs_abs, int64_t *__restrict__ out_ids,
-                                               int32_t *__restrict__ num_peds, TrackRule rule = {},
-                                               int32_t *__restrict__ seen = nullptr) {
+__device__ __forceinline__ int track_push_body(const Detections &det, int count, const TrackState &st, const PushDims &d,
+                                               const TrackRule &rule, const SceneOut &out) {
+    const int M_max = d.M_max, M2 = d.M2, S = d.S, T_obs = d.T_obs, V = d.V;
+    const double scale = d.scale;
+    int64_t *slot_id = st.slot_id, *out_ids = out.out_ids;
+    uint32_t *mask = st.mask;
+    double *ring = st.ring, *obs_abs = out.obs_abs;
+    int32_t *head_flags = st.head_flags, *seen = out.seen;
     extern __shared__ __align__(16) unsigned char lds[];
     int64_t *key = reinterpret_cast<int64_t *>(lds);
     int32_t *kidx = reinterpret_cast<int32_t *>(key + M2);
@@ -230,7 +239,7 @@ __device__ __forceinline__ int track_push_body(const int64_t *__restrict__ det_i
         if (mk == 0) slot_id[s] = -1;
     }
     const int n2 = det_sort_n(m);                           // (<= M2)
-    det_load(key, kidx, det_id, id_stride, m, n2, tid, nt);
+    det_load(key, kidx, det, m, n2, tid, nt);
     for (int j = tid; j < m; j += nt) det_slot[j] = -1;
     __syncthreads();
 
@@ -242,10 +251,10 @@ __device__ __forceinline__ int track_push_body(const int64_t *__restrict__ det_i
     for (int j = tid; j < m; j += nt) {
         const int s = det_slot[j];
         if (s < 0) continue;
-        slot_id[s] = det_id[j * id_stride];
+        slot_id[s] = det.id_at(j);
         smask[s] |= 1u;
-        ring[((int64_t)head * S + s) * 2] = round_pos(det_xy[j * xy_stride], scale);
-        ring[((int64_t)head * S + s) * 2 + 1] = round_pos(det_xy[j * xy_stride + 1], scale);
+        ring[((int64_t)head * S + s) * 2] = round_pos(det.x(j), scale);
+        ring[((int64_t)head * S + s) * 2 + 1] = round_pos(det.y(j), scale);
     }
     __syncthreads();
 
@@ -271,8 +280,8 @@ __device__ __forceinline__ int track_push_body(const int64_t *__restrict__ det_i
                     pm, T_obs, scale,
                     [&](int t, double &x, double &y) {
                         if (t == T_obs - 1) {
-                            x = round_pos(det_xy[j * xy_stride], scale);
-                            y = round_pos(det_xy[j * xy_stride + 1], scale);
+                            x = round_pos(det.x(j), scale);
+                            y = round_pos(det.y(j), scale);
                         } else {
                             const int row = (head + 1 + t) % T_obs;
                             x = ring[((int64_t)row * S + s) * 2];
@@ -286,158 +295,92 @@ __device__ __forceinline__ int track_push_body(const int64_t *__restrict__ det_i
             }
         } else if (in && r < V) {
             out_ids[r] = key[p];
-            for (int t = 0; t < T_obs - 1; ++t) {
-                const int row = (head + 1 + t) % T_obs;           // head - (T_obs - 1 - t) mod T_obs
-                obs_abs[((int64_t)t * V + r) * 2] = ring[((int64_t)row * S + s) * 2];
-                obs_abs[((int64_t)t * V + r) * 2 + 1] = ring[((int64_t)row * S + s) * 2 + 1];
-            }
+            gather_ring(obs_abs + r * 2, ring + s * 2, head, S, T_obs, V);
             // this frame's position from the input (the ring row written above is another thread's store)
-            obs_abs[((int64_t)(T_obs - 1) * V + r) * 2] = round_pos(det_xy[j * xy_stride], scale);
-            obs_abs[((int64_t)(T_obs - 1) * V + r) * 2 + 1] = round_pos(det_xy[j * xy_stride + 1], scale);
+            obs_abs[((int64_t)(T_obs - 1) * V + r) * 2] = round_pos(det.x(j), scale);
+            obs_abs[((int64_t)(T_obs - 1) * V + r) * 2 + 1] = round_pos(det.y(j), scale);
         }
         c += tot;
     }
     if (c > V && tid == 0) atomicOr(&flags, kFlagTooMany);
     const int np = c < V ? c : V;
-    pad_scene(obs_abs, out_ids, kRule ? seen : nullptr, T_obs, V, np);
+    pad_scene(out, T_obs, V, np);
     for (int s = tid; s < S; s += nt) mask[s] = smask[s];
     __syncthreads();
     if (tid == 0) {
-        num_peds[0] = np;
+        out.num_peds[0] = np;
         head_flags[0] = head;
         head_flags[1] = flags;
     }
     return flags;
 }
 
+// One kernel per (single | streams) push; kRule picks the strict or the rule's scene phase of the body, and the strict
+// instantiation reads neither `rule` nor out.seen.
+template <bool kRule>
 __global__ __launch_bounds__(kPushThreads) void track_push_kernel(
     const int64_t *__restrict__ det_id, const double *__restrict__ det_xy, const int32_t *__restrict__ det_count,
-    int M_max, int M2, int64_t *__restrict__ slot_id, uint32_t *__restrict__ mask, double *__restrict__ ring,
-    int32_t *__restrict__ head_flags, int S, int T_obs, double scale, int V, double *__restrict__ obs_abs,
-    int64_t *__restrict__ out_ids, int32_t *__restrict__ num_peds) {
-    track_push_body<kPushThreads, false>(det_id, 1, det_xy, 2, det_count[0], M_max, M2, slot_id, mask, ring,
-                                         head_flags, S, T_obs, scale, V, obs_abs, out_ids, num_peds);
+    TrackState st, PushDims d, TrackRule rule, SceneOut out) {
+    if constexpr (!kRule) out.seen = nullptr;
+    track_push_body<kPushThreads, kRule>({det_id, 1, det_xy, 2}, det_count[0], st, d, rule, out);
 }
 
-__global__ __launch_bounds__(kPushThreads) void track_push_rule_kernel(
-    const int64_t *__restrict__ det_id, const double *__restrict__ det_xy, const int32_t *__restrict__ det_count,
-    int M_max, int M2, int64_t *__restrict__ slot_id, uint32_t *__restrict__ mask, double *__restrict__ ring,
-    int32_t *__restrict__ head_flags, int S, int T_obs, double scale, int V, TrackRule rule,
-    double *__restrict__ obs_abs, int64_t *__restrict__ out_ids, int32_t *__restrict__ num_peds,
-    int32_t *__restrict__ seen) {
-    track_push_body<kPushThreads, true>(det_id, 1, det_xy, 2, det_count[0], M_max, M2, slot_id, mask, ring,
-                                        head_flags, S, T_obs, scale, V, obs_abs, out_ids, num_peds, rule, seen);
-}
-
-// One workgroup per stream (push_stream): every stream's pointers are its own slices of the (NS, ...) state and output
-// arrays.
+// One workgroup per stream (push_stream): every stream's records are its own slices of the (NS, ...) arrays.
 template <int kThreads, bool kRule>
-__device__ __forceinline__ void track_push_stream(
-    const int64_t *__restrict__ det_id, int64_t id_stride, const double *__restrict__ det_xy, int64_t xy_stride,
-    int M_total, const int32_t *__restrict__ det_start, const int32_t *__restrict__ pushed, int M_max, int M2,
-    int64_t *__restrict__ slot_id, uint32_t *__restrict__ mask, double *__restrict__ ring,
-    int32_t *__restrict__ head_flags, int S, int T_obs, double scale, int V, double *__restrict__ obs_abs,
-    int64_t *__restrict__ out_ids, int32_t *__restrict__ num_peds, int32_t *__restrict__ out_flags,
-    TrackRule rule = {}, int32_t *__restrict__ seen = nullptr) {
-    push_stream(det_start, pushed, M_total, T_obs, V, obs_abs, out_ids, kRule ? seen : nullptr, num_peds, out_flags,
-                [&](int lo, int count, double *obs, int64_t *oid, int32_t *osn, int32_t *peds) {
-                    const int64_t b = blockIdx.x;
-                    return track_push_body<kThreads, kRule>(
-                        det_id + lo * id_stride, id_stride, det_xy + lo * xy_stride, xy_stride, count, M_max, M2,
-                        slot_id + b * S, mask + b * S, ring + b * T_obs * S * 2, head_flags + 2 * b, S, T_obs, scale, V,
-                        obs, oid, peds, rule, osn);
+__global__ __launch_bounds__(kThreads) void track_push_streams_kernel(Detections det, Tick tick, TrackState st, PushDims d,
+                                                                      TrackRule rule, SceneOut out,
+                                                                      int32_t *__restrict__ out_flags) {
+    if constexpr (!kRule) out.seen = nullptr;
+    push_stream(det, tick, out, d.T_obs, d.V, out_flags,
+                [&](const Detections &mine, int count, const SceneOut &scene) {
+                    return track_push_body<kThreads, kRule>(mine, count, st.of_stream(blockIdx.x, d), d, rule, scene);
                 });
-}
-
-template <int kThreads>
-__global__ __launch_bounds__(kThreads) void track_push_streams_kernel(
-    const int64_t *__restrict__ det_id, int64_t id_stride, const double *__restrict__ det_xy, int64_t xy_stride,
-    int M_total, const int32_t *__restrict__ det_start, const int32_t *__restrict__ pushed, int M_max, int M2,
-    int64_t *__restrict__ slot_id, uint32_t *__restrict__ mask, double *__restrict__ ring,
-    int32_t *__restrict__ head_flags, int S, int T_obs, double scale, int V, double *__restrict__ obs_abs,
-    int64_t *__restrict__ out_ids, int32_t *__restrict__ num_peds, int32_t *__restrict__ out_flags) {
-    track_push_stream<kThreads, false>(det_id, id_stride, det_xy, xy_stride, M_total, det_start, pushed, M_max, M2,
-                                       slot_id, mask, ring, head_flags, S, T_obs, scale, V, obs_abs, out_ids, num_peds,
-                                       out_flags);
-}
-
-template <int kThreads>
-__global__ __launch_bounds__(kThreads) void track_push_streams_rule_kernel(
-    const int64_t *__restrict__ det_id, int64_t id_stride, const double *__restrict__ det_xy, int64_t xy_stride,
-    int M_total, const int32_t *__restrict__ det_start, const int32_t *__restrict__ pushed, int M_max, int M2,
-    int64_t *__restrict__ slot_id, uint32_t *__restrict__ mask, double *__restrict__ ring,
-    int32_t *__restrict__ head_flags, int S, int T_obs, double scale, int V, TrackRule rule,
-    double *__restrict__ obs_abs, int64_t *__restrict__ out_ids, int32_t *__restrict__ num_peds,
-    int32_t *__restrict__ out_flags, int32_t *__restrict__ seen) {
-    track_push_stream<kThreads, true>(det_id, id_stride, det_xy, xy_stride, M_total, det_start, pushed, M_max, M2,
-                                      slot_id, mask, ring, head_flags, S, T_obs, scale, V, obs_abs, out_ids, num_peds,
-                                      out_flags, rule, seen);
 }
 
 // ---- the pushes' entry points ---------------------------------------------------------------------------------------
 // Each pair (strict, *_rule) shares one function for its checks and its launch, under its own name `what`.  Without
 // `ruled` (the strict entry point) T_obs starts at 1, the rule and `seen` are not looked at and the strict kernel runs.
-// dynamic LDS of a push: the sort arrays of M2 entries, det_slot, slot masks, free slots
-static inline size_t push_lds(int M_max, int M2, int S) {
-    return det_sort_lds(M2) + (size_t)M_max * sizeof(int32_t) + (size_t)S * (sizeof(uint32_t) + sizeof(int32_t));
+// dynamic LDS of a push: the sort arrays of M2 entries, det_slot, slot masks, free slots.  At most 48 KB (M_max = S =
+// 2048: 24 + 8 + 16), below the 64 KB a kernel may use without asking: the launches name that limit and never raise it
+static inline size_t push_lds(const PushDims &d) {
+    return det_sort_lds(d.M2) + (size_t)d.M_max * sizeof(int32_t) + (size_t)d.S * (sizeof(uint32_t) + sizeof(int32_t));
 }
 
-static int track_push(const char *what, bool ruled, int min_seen, int max_gap, const int64_t *det_id,
-                      const double *det_xy, const int32_t *det_count, int M_max, int64_t *slot_id, uint32_t *mask,
-                      double *ring, int32_t *head_flags, int S, int T_obs, double scale, int V, double *obs_abs,
-                      int64_t *out_ids, int32_t *num_peds, int32_t *seen, void *stream) {
-    STG_REQUIRE(M_max >= 1 && M_max <= STG_TRACK_MAX_DETECTIONS && S >= 1 && S <= STG_TRACK_MAX_SLOTS && V >= 1 &&
-                    (ruled || (T_obs >= 1 && T_obs <= 32)),
-                STG_EINVAL, "%s: bad sizes M_max=%d S=%d V=%d T_obs=%d", what, M_max, S, V, T_obs);
+// the checks the two pushes share (`counts`: the push's det_count, or the streams' det_start and pushed); fills d.M2.
+// A strict push has no `seen` (its entry points pass null, and its kernels null the member: pad_scene looks at it).
+static int push_args(const char *what, bool ruled, const TrackRule &rule, const Detections &det, bool counts,
+                     const TrackState &st, PushDims &d, const SceneOut &out) {
+    const int T_obs = d.T_obs, min_seen = rule.min_seen, max_gap = rule.max_gap;
+    STG_REQUIRE(d.M_max >= 1 && d.M_max <= STG_TRACK_MAX_DETECTIONS && d.S >= 1 && d.S <= STG_TRACK_MAX_SLOTS &&
+                    d.V >= 1 && (ruled || (T_obs >= 1 && T_obs <= 32)),
+                STG_EINVAL, "%s: bad sizes M_max=%d S=%d V=%d T_obs=%d", what, d.M_max, d.S, d.V, T_obs);
     if (ruled) STG_REQUIRE_RULE(what);
-    STG_REQUIRE(det_id && det_xy && det_count && slot_id && mask && ring && head_flags && obs_abs && out_ids &&
-                    num_peds && (seen || !ruled),
+    STG_REQUIRE(det.id && det.xy && counts && st.slot_id && st.mask && st.ring && st.head_flags && out.obs_abs &&
+                    out.out_ids && out.num_peds && (out.seen != nullptr) == ruled,
                 STG_EINVAL, "%s: null pointer", what);
-    const int m2 = det_sort_n(M_max);
-    const dim3 grid(1), block(kPushThreads);
-    if (ruled)
-        hipLaunchKernelGGL(track_push_rule_kernel, grid, block, push_lds(M_max, m2, S), as_stream(stream), det_id,
-                           det_xy, det_count, M_max, m2, slot_id, mask, ring, head_flags, S, T_obs, scale, V,
-                           TrackRule{min_seen, max_gap}, obs_abs, out_ids, num_peds, seen);
-    else
-        hipLaunchKernelGGL(track_push_kernel, grid, block, push_lds(M_max, m2, S), as_stream(stream), det_id, det_xy,
-                           det_count, M_max, m2, slot_id, mask, ring, head_flags, S, T_obs, scale, V, obs_abs, out_ids,
-                           num_peds);
-    STG_LAUNCH_CHECK(what);
+    d.M2 = det_sort_n(d.M_max);
     return STG_OK;
 }
 
-static int track_push_streams(const char *what, bool ruled, int min_seen, int max_gap, const int64_t *det_id,
-                              int64_t id_stride, const double *det_xy, int64_t xy_stride, int M_total,
-                              const int32_t *det_start, const int32_t *pushed, int NS, int M_max, int64_t *slot_id,
-                              uint32_t *mask, double *ring, int32_t *head_flags, int S, int T_obs, double scale, int V,
-                              double *obs_abs, int64_t *out_ids, int32_t *num_peds, int32_t *out_flags, int32_t *seen,
-                              int block_threads, void *stream) {
-    const int rc = push_streams_args(what, NS, M_total, id_stride, xy_stride, block_threads);
+static int track_push(const char *what, bool ruled, TrackRule rule, Detections det, const int32_t *det_count,
+                      TrackState st, PushDims d, SceneOut out, void *stream) {
+    const int rc = push_args(what, ruled, rule, det, det_count != nullptr, st, d, out);
     if (rc != STG_OK) return rc;
-    STG_REQUIRE(M_max >= 1 && M_max <= STG_TRACK_MAX_DETECTIONS && S >= 1 && S <= STG_TRACK_MAX_SLOTS && V >= 1 &&
-                    (ruled || (T_obs >= 1 && T_obs <= 32)),
-                STG_EINVAL, "%s: bad sizes M_max=%d S=%d V=%d T_obs=%d", what, M_max, S, V, T_obs);
-    if (ruled) STG_REQUIRE_RULE(what);
-    STG_REQUIRE(det_id && det_xy && det_start && pushed && slot_id && mask && ring && head_flags && obs_abs &&
-                    out_ids && num_peds && (seen || !ruled),
-                STG_EINVAL, "%s: null pointer", what);
-    const int m2 = det_sort_n(M_max);
-    const size_t lds = push_lds(M_max, m2, S);
-    const dim3 grid(NS), block(block_threads);
+    return launch({what, dim3(1), dim3(kPushThreads), push_lds(d), as_stream(stream), 64 * 1024},
+                  ruled ? track_push_kernel<true> : track_push_kernel<false>, det.id, det.xy, det_count, st, d, rule, out);
+}
+
+static int track_push_streams(const char *what, bool ruled, TrackRule rule, Detections det, Tick tick, int NS,
+                              TrackState st, PushDims d, SceneOut out, int32_t *out_flags, int block_threads,
+                              void *stream) {
+    int rc = push_streams_args(what, NS, tick.M_total, det.id_stride, det.xy_stride, block_threads);
+    if (rc == STG_OK) rc = push_args(what, ruled, rule, det, tick.det_start && tick.pushed, st, d, out);
+    if (rc != STG_OK) return rc;
+    const Launch l{what, dim3(NS), dim3(block_threads), push_lds(d), as_stream(stream), 64 * 1024};
     // the workgroup size picks the instantiation, `ruled` the kernel of the pair
-    return with_stream_threads(block_threads, [&](auto kt) -> int {
-        if (ruled)
-            hipLaunchKernelGGL(track_push_streams_rule_kernel<kt()>, grid, block, lds, as_stream(stream), det_id,
-                               id_stride, det_xy, xy_stride, M_total, det_start, pushed, M_max, m2, slot_id, mask, ring,
-                               head_flags, S, T_obs, scale, V, TrackRule{min_seen, max_gap}, obs_abs, out_ids, num_peds,
-                               out_flags, seen);
-        else
-            hipLaunchKernelGGL(track_push_streams_kernel<kt()>, grid, block, lds, as_stream(stream), det_id, id_stride,
-                               det_xy, xy_stride, M_total, det_start, pushed, M_max, m2, slot_id, mask, ring, head_flags,
-                               S, T_obs, scale, V, obs_abs, out_ids, num_peds, out_flags);
-        STG_LAUNCH_CHECK(what);
-        return STG_OK;
+    return with_stream_threads(block_threads, [&](auto kt) {
+        return launch(l, ruled ? track_push_streams_kernel<kt(), true> : track_push_streams_kernel<kt(), false>, det,
+                      tick, st, d, rule, out, out_flags);
     });
 }
 
@@ -450,10 +393,8 @@ int stg_frame_scene_counts(const int32_t *frame_start, const int64_t *ids, int F
     STG_REQUIRE(F >= 0 && T_obs >= 1, STG_EINVAL, "stg_frame_scene_counts: bad sizes F=%d T_obs=%d", F, T_obs);
     if (F == 0) return STG_OK;
     STG_REQUIRE(frame_start && ids && count, STG_EINVAL, "stg_frame_scene_counts: null pointer");
-    hipLaunchKernelGGL(stg::frame_scene_counts_kernel, dim3(F), dim3(stg::kWave), 0, stg::as_stream(stream),
-                       frame_start, ids, T_obs, count);
-    STG_LAUNCH_CHECK("stg_frame_scene_counts");
-    return STG_OK;
+    return stg::launch({"stg_frame_scene_counts", dim3(F), dim3(stg::kWave), 0, stg::as_stream(stream)},
+                       stg::frame_scene_counts_kernel, frame_start, ids, T_obs, count);
 }
 
 int stg_frame_scenes(const int32_t *frame_start, const int64_t *ids, const double *xy, const int32_t *frames, int N,
@@ -464,17 +405,17 @@ int stg_frame_scenes(const int32_t *frame_start, const int64_t *ids, const doubl
     if (N == 0) return STG_OK;
     STG_REQUIRE(frame_start && ids && xy && frames && obs_abs && out_ids && num_peds, STG_EINVAL,
                 "stg_frame_scenes: null pointer");
-    hipLaunchKernelGGL(stg::frame_scenes_kernel, dim3(N), dim3(stg::kWave), 0, stg::as_stream(stream), frame_start,
-                       ids, xy, frames, V, T_obs, scale, obs_abs, out_ids, num_peds);
-    STG_LAUNCH_CHECK("stg_frame_scenes");
-    return STG_OK;
+    return stg::launch({"stg_frame_scenes", dim3(N), dim3(stg::kWave), 0, stg::as_stream(stream)},
+                       stg::frame_scenes_kernel, frame_start, ids, xy, frames, V, T_obs, scale, obs_abs, out_ids,
+                       num_peds);
 }
 
 int stg_track_push(const int64_t *det_id, const double *det_xy, const int32_t *det_count, int M_max, int64_t *slot_id,
                    uint32_t *mask, double *ring, int32_t *head_flags, int S, int T_obs, double scale, int V,
                    double *obs_abs, int64_t *out_ids, int32_t *num_peds, void *stream) {
-    return stg::track_push("stg_track_push", false, 0, 0, det_id, det_xy, det_count, M_max, slot_id, mask, ring,
-                           head_flags, S, T_obs, scale, V, obs_abs, out_ids, num_peds, nullptr, stream);
+    return stg::track_push("stg_track_push", false, {}, {det_id, 1, det_xy, 2}, det_count,
+                           {slot_id, mask, ring, head_flags}, {M_max, 0, S, T_obs, V, scale},
+                           {obs_abs, out_ids, num_peds, nullptr}, stream);
 }
 
 int stg_track_push_streams(const int64_t *det_id, int64_t id_stride, const double *det_xy, int64_t xy_stride,
@@ -482,9 +423,10 @@ int stg_track_push_streams(const int64_t *det_id, int64_t id_stride, const doubl
                            int64_t *slot_id, uint32_t *mask, double *ring, int32_t *head_flags, int S, int T_obs,
                            double scale, int V, double *obs_abs, int64_t *out_ids, int32_t *num_peds,
                            int32_t *out_flags, int block_threads, void *stream) {
-    return stg::track_push_streams("stg_track_push_streams", false, 0, 0, det_id, id_stride, det_xy, xy_stride,
-                                   M_total, det_start, pushed, NS, M_max, slot_id, mask, ring, head_flags, S, T_obs,
-                                   scale, V, obs_abs, out_ids, num_peds, out_flags, nullptr, block_threads, stream);
+    return stg::track_push_streams("stg_track_push_streams", false, {}, {det_id, id_stride, det_xy, xy_stride},
+                                   {det_start, pushed, M_total}, NS, {slot_id, mask, ring, head_flags},
+                                   {M_max, 0, S, T_obs, V, scale}, {obs_abs, out_ids, num_peds, nullptr}, out_flags,
+                                   block_threads, stream);
 }
 
 // ---- partially observed tracks: the rule's entry points -------------------------------------------------------------
@@ -495,10 +437,8 @@ int stg_fill_tracks(double *obs_abs, const int32_t *seen, const int32_t *num_ped
     if (N == 0) return STG_OK;
     STG_REQUIRE(obs_abs && seen, STG_EINVAL, "stg_fill_tracks: null pointer");
     const int64_t blocks = ((int64_t)N * V + 255) / 256;
-    hipLaunchKernelGGL(stg::fill_tracks_kernel, dim3((unsigned)blocks), dim3(256), 0, stg::as_stream(stream), obs_abs,
-                       seen, num_peds, N, T_obs, V, scale);
-    STG_LAUNCH_CHECK("stg_fill_tracks");
-    return STG_OK;
+    return stg::launch({"stg_fill_tracks", dim3((unsigned)blocks), dim3(256), 0, stg::as_stream(stream)},
+                       stg::fill_tracks_kernel, obs_abs, seen, num_peds, N, T_obs, V, scale);
 }
 
 int stg_frame_scene_counts_rule(const int32_t *frame_start, const int64_t *ids, int F, int T_obs, int min_seen,
@@ -507,10 +447,9 @@ int stg_frame_scene_counts_rule(const int32_t *frame_start, const int64_t *ids, 
     STG_REQUIRE_RULE("stg_frame_scene_counts_rule");
     if (F == 0) return STG_OK;
     STG_REQUIRE(frame_start && ids && count, STG_EINVAL, "stg_frame_scene_counts_rule: null pointer");
-    hipLaunchKernelGGL(stg::frame_scene_counts_rule_kernel, dim3(F), dim3(stg::kWave), 0, stg::as_stream(stream),
-                       frame_start, ids, T_obs, stg::TrackRule{min_seen, max_gap}, count);
-    STG_LAUNCH_CHECK("stg_frame_scene_counts_rule");
-    return STG_OK;
+    return stg::launch({"stg_frame_scene_counts_rule", dim3(F), dim3(stg::kWave), 0, stg::as_stream(stream)},
+                       stg::frame_scene_counts_rule_kernel, frame_start, ids, T_obs, stg::TrackRule{min_seen, max_gap},
+                       count);
 }
 
 int stg_frame_scenes_rule(const int32_t *frame_start, const int64_t *ids, const double *xy, const int32_t *frames,
@@ -521,19 +460,18 @@ int stg_frame_scenes_rule(const int32_t *frame_start, const int64_t *ids, const 
     if (N == 0) return STG_OK;
     STG_REQUIRE(frame_start && ids && xy && frames && obs_abs && out_ids && num_peds && seen, STG_EINVAL,
                 "stg_frame_scenes_rule: null pointer");
-    hipLaunchKernelGGL(stg::frame_scenes_rule_kernel, dim3(N), dim3(stg::kWave), 0, stg::as_stream(stream), frame_start,
-                       ids, xy, frames, V, T_obs, scale, stg::TrackRule{min_seen, max_gap}, obs_abs, out_ids, num_peds,
-                       seen);
-    STG_LAUNCH_CHECK("stg_frame_scenes_rule");
-    return STG_OK;
+    return stg::launch({"stg_frame_scenes_rule", dim3(N), dim3(stg::kWave), 0, stg::as_stream(stream)},
+                       stg::frame_scenes_rule_kernel, frame_start, ids, xy, frames, V, T_obs, scale,
+                       stg::TrackRule{min_seen, max_gap}, obs_abs, out_ids, num_peds, seen);
 }
 
 int stg_track_push_rule(const int64_t *det_id, const double *det_xy, const int32_t *det_count, int M_max,
                         int64_t *slot_id, uint32_t *mask, double *ring, int32_t *head_flags, int S, int T_obs,
                         double scale, int V, int min_seen, int max_gap, double *obs_abs, int64_t *out_ids,
                         int32_t *num_peds, int32_t *seen, void *stream) {
-    return stg::track_push("stg_track_push_rule", true, min_seen, max_gap, det_id, det_xy, det_count, M_max, slot_id,
-                           mask, ring, head_flags, S, T_obs, scale, V, obs_abs, out_ids, num_peds, seen, stream);
+    return stg::track_push("stg_track_push_rule", true, {min_seen, max_gap}, {det_id, 1, det_xy, 2}, det_count,
+                           {slot_id, mask, ring, head_flags}, {M_max, 0, S, T_obs, V, scale},
+                           {obs_abs, out_ids, num_peds, seen}, stream);
 }
 
 int stg_track_push_streams_rule(const int64_t *det_id, int64_t id_stride, const double *det_xy, int64_t xy_stride,
@@ -542,9 +480,10 @@ int stg_track_push_streams_rule(const int64_t *det_id, int64_t id_stride, const 
                                 double scale, int V, int min_seen, int max_gap, double *obs_abs, int64_t *out_ids,
                                 int32_t *num_peds, int32_t *out_flags, int32_t *seen, int block_threads,
                                 void *stream) {
-    return stg::track_push_streams("stg_track_push_streams_rule", true, min_seen, max_gap, det_id, id_stride, det_xy,
-                                   xy_stride, M_total, det_start, pushed, NS, M_max, slot_id, mask, ring, head_flags, S,
-                                   T_obs, scale, V, obs_abs, out_ids, num_peds, out_flags, seen, block_threads, stream);
+    return stg::track_push_streams("stg_track_push_streams_rule", true, {min_seen, max_gap},
+                                   {det_id, id_stride, det_xy, xy_stride}, {det_start, pushed, M_total}, NS,
+                                   {slot_id, mask, ring, head_flags}, {M_max, 0, S, T_obs, V, scale},
+                                   {obs_abs, out_ids, num_peds, seen}, out_flags, block_threads, stream);
 }
 
 }  // extern "C"

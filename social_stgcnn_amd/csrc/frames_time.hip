@@ -36,19 +36,21 @@ __device__ __forceinline__ int ring_at(int head, int n_old, int i, int R) {
     return x >= R ? x - R : x;
 }
 
-// One timed push of one stream by one workgroup of kThreads threads; the arguments of track_push_body with the timed
-// state in the place of mask / ring: t_ring (S,R), xy_ring (S,R,2), slot_head (S,2), clock (2).  Returns the flags.
+// One timed push of one stream by one workgroup of kThreads threads at the time t_now; the arguments of
+// track_push_body with the timed state and sizes (live_args.hpp) in the place of the plain ones.  Returns the flags.
 // LDS layout (dynamic): sort keys (M2 x int64), sort indices (M2 x int32), det_slot, det_rank (M_max x int32 each),
 // slot masks, free slots, slot heads, slot counts (S x 4 bytes each), found (M_max x T_obs bytes: the logical index of
 // the sample at or below each observed instant, so the scene pass does not search again)
 template <int kThreads>
-__device__ __forceinline__ int track_push_timed_body(
-    const int64_t *__restrict__ det_id, int64_t id_stride, const double *__restrict__ det_xy, int64_t xy_stride,
-    int count, int64_t t_now, int M_max, int M2, int64_t *__restrict__ slot_id, int64_t *__restrict__ t_ring,
-    double *__restrict__ xy_ring, int32_t *__restrict__ slot_head, int64_t *__restrict__ clock,
-    int32_t *__restrict__ head_flags, int S, int R, int T_obs, double scale, int V, int64_t step, int64_t max_dt,
-    TrackRule rule, double *__restrict__ obs_abs, int64_t *__restrict__ out_ids, int32_t *__restrict__ num_peds,
-    int32_t *__restrict__ seen) {
+__device__ __forceinline__ int track_push_timed_body(const Detections &det, int count, int64_t t_now,
+                                                     const TimedState &st, const TimedDims &d, const TrackRule &rule,
+                                                     const SceneOut &out) {
+    const int M_max = d.M_max, M2 = d.M2, S = d.S, R = d.R, T_obs = d.T_obs, V = d.V;
+    const double scale = d.scale;
+    const int64_t step = d.step, max_dt = d.max_dt;
+    int64_t *slot_id = st.slot_id, *t_ring = st.t_ring, *clock = st.clock, *out_ids = out.out_ids;
+    double *xy_ring = st.xy_ring, *obs_abs = out.obs_abs;
+    int32_t *slot_head = st.slot_head, *head_flags = st.head_flags, *seen = out.seen;
     extern __shared__ __align__(16) unsigned char lds[];
     int64_t *key = reinterpret_cast<int64_t *>(lds);
     int32_t *kidx = reinterpret_cast<int32_t *>(key + M2);
@@ -69,9 +71,9 @@ __device__ __forceinline__ int track_push_timed_body(
     // 0. time must move forward (the first push takes any time): otherwise the empty scene and no change of state.
     //    Uniform over the block, ahead of every barrier.
     if (pushes > 0 && t_now <= last) {
-        pad_scene(obs_abs, out_ids, seen, T_obs, V, 0);
+        pad_scene(out, T_obs, V, 0);
         if (tid == 0) {
-            num_peds[0] = 0;
+            out.num_peds[0] = 0;
             head_flags[1] = kFlagTimeOrder;
         }
         return kFlagTimeOrder;
@@ -98,7 +100,7 @@ __device__ __forceinline__ int track_push_timed_body(
         scnt[s] = c;
     }
     const int n2 = det_sort_n(m);                           // (<= M2)
-    det_load(key, kidx, det_id, id_stride, m, n2, tid, nt);
+    det_load(key, kidx, det, m, n2, tid, nt);
     for (int j = tid; j < m; j += nt) det_slot[j] = -1;
     __syncthreads();
 
@@ -113,11 +115,11 @@ __device__ __forceinline__ int track_push_timed_body(
         if (s < 0) continue;
         const int h = shead[s], c = scnt[s];
         const int64_t at = (int64_t)s * R + h;
-        slot_id[s] = det_id[j * id_stride];
+        slot_id[s] = det.id_at(j);
         atomicOr(&smask[s], 1u);
         t_ring[at] = t_now;
-        xy_ring[at * 2] = round_pos(det_xy[j * xy_stride], scale);
-        xy_ring[at * 2 + 1] = round_pos(det_xy[j * xy_stride + 1], scale);
+        xy_ring[at * 2] = round_pos(det.x(j), scale);
+        xy_ring[at * 2 + 1] = round_pos(det.y(j), scale);
         slot_head[2 * s] = h + 1 == R ? 0 : h + 1;
         slot_head[2 * s + 1] = c < R ? c + 1 : R;
     }
@@ -176,7 +178,7 @@ __device__ __forceinline__ int track_push_timed_body(
         if (r < 0) continue;
         const int s = det_slot[j];
         if (((smask[s] >> (T1 - k)) & 1u) == 0) continue;
-        const double nx = round_pos(det_xy[j * xy_stride], scale), ny = round_pos(det_xy[j * xy_stride + 1], scale);
+        const double nx = round_pos(det.x(j), scale), ny = round_pos(det.y(j), scale);
         double x = nx, y = ny;
         if (k < T1) {
             const int cs = scnt[s], n_old = cs < R - 1 ? cs : R - 1, h = shead[s], i = found[j * T_obs + k];
@@ -221,10 +223,10 @@ __device__ __forceinline__ int track_push_timed_body(
                 obs_abs[((int64_t)t * V + r) * 2 + 1] = y;
             });
     }
-    pad_scene(obs_abs, out_ids, seen, T_obs, V, np);
+    pad_scene(out, T_obs, V, np);
     __syncthreads();
     if (tid == 0) {
-        num_peds[0] = np;
+        out.num_peds[0] = np;
         head_flags[1] = flags;
         clock[0] = t_now;
         clock[1] = pushes + 1;
@@ -234,47 +236,34 @@ __device__ __forceinline__ int track_push_timed_body(
 
 __global__ __launch_bounds__(kPushThreads) void track_push_timed_kernel(
     const int64_t *__restrict__ det_id, const double *__restrict__ det_xy, const int32_t *__restrict__ det_count,
-    const int64_t *__restrict__ det_time, int M_max, int M2, int64_t *__restrict__ slot_id,
-    int64_t *__restrict__ t_ring, double *__restrict__ xy_ring, int32_t *__restrict__ slot_head,
-    int64_t *__restrict__ clock, int32_t *__restrict__ head_flags, int S, int R, int T_obs, double scale, int V,
-    int64_t step, int64_t max_dt, TrackRule rule, double *__restrict__ obs_abs, int64_t *__restrict__ out_ids,
-    int32_t *__restrict__ num_peds, int32_t *__restrict__ seen) {
-    track_push_timed_body<kPushThreads>(det_id, 1, det_xy, 2, det_count[0], det_time[0], M_max, M2, slot_id, t_ring,
-                                        xy_ring, slot_head, clock, head_flags, S, R, T_obs, scale, V, step, max_dt,
-                                        rule, obs_abs, out_ids, num_peds, seen);
+    const int64_t *__restrict__ det_time, TimedState st, TimedDims d, TrackRule rule, SceneOut out) {
+    track_push_timed_body<kPushThreads>({det_id, 1, det_xy, 2}, det_count[0], det_time[0], st, d, rule, out);
 }
 
 // One workgroup per stream (push_stream): a stream not pushed keeps its state, its clock included
 template <int kThreads>
 __global__ __launch_bounds__(kThreads) void track_push_streams_timed_kernel(
-    const int64_t *__restrict__ det_id, int64_t id_stride, const double *__restrict__ det_xy, int64_t xy_stride,
-    int M_total, const int32_t *__restrict__ det_start, const int32_t *__restrict__ pushed,
-    const int64_t *__restrict__ det_time, int M_max, int M2, int64_t *__restrict__ slot_id,
-    int64_t *__restrict__ t_ring, double *__restrict__ xy_ring, int32_t *__restrict__ slot_head,
-    int64_t *__restrict__ clock, int32_t *__restrict__ head_flags, int S, int R, int T_obs, double scale, int V,
-    int64_t step, int64_t max_dt, TrackRule rule, double *__restrict__ obs_abs, int64_t *__restrict__ out_ids,
-    int32_t *__restrict__ num_peds, int32_t *__restrict__ out_flags, int32_t *__restrict__ seen) {
-    push_stream(det_start, pushed, M_total, T_obs, V, obs_abs, out_ids, seen, num_peds, out_flags,
-                [&](int lo, int count, double *obs, int64_t *oid, int32_t *osn, int32_t *peds) {
-                    const int64_t b = blockIdx.x;
-                    return track_push_timed_body<kThreads>(
-                        det_id + lo * id_stride, id_stride, det_xy + lo * xy_stride, xy_stride, count, det_time[b],
-                        M_max, M2, slot_id + b * S, t_ring + b * S * R, xy_ring + b * S * R * 2, slot_head + b * S * 2,
-                        clock + 2 * b, head_flags + 2 * b, S, R, T_obs, scale, V, step, max_dt, rule, obs, oid, peds,
-                        osn);
-                });
+    Detections det, Tick tick, const int64_t *__restrict__ det_time, TimedState st, TimedDims d, TrackRule rule,
+    SceneOut out, int32_t *__restrict__ out_flags) {
+    push_stream(det, tick, out, d.T_obs, d.V, out_flags, [&](const Detections &mine, int count, const SceneOut &scene) {
+        const int b = blockIdx.x;
+        return track_push_timed_body<kThreads>(mine, count, det_time[b], st.of_stream(b, d), d, rule, scene);
+    });
 }
 
 // dynamic LDS of a timed push: the sort arrays, det_slot and det_rank, four words per slot, one byte per
 // (detection, step)
-static inline size_t push_timed_lds(int M_max, int M2, int S, int T_obs) {
-    return det_sort_lds(M2) + (size_t)M_max * 2 * sizeof(int32_t) + (size_t)S * 4 * sizeof(int32_t) +
-           (size_t)M_max * T_obs;
+static inline size_t push_timed_lds(const TimedDims &d) {
+    return det_sort_lds(d.M2) + (size_t)d.M_max * 2 * sizeof(int32_t) + (size_t)d.S * 4 * sizeof(int32_t) +
+           (size_t)d.M_max * d.T_obs;
 }
 
-// the checks the two entry points share, under the name `what`
-static int timed_args(const char *what, int M_max, int S, int R, int T_obs, int V, int64_t step, int64_t max_dt,
-                      int min_seen, int max_gap) {
+// the checks the two entry points share (`counts`: the push's det_count, or the streams' det_start and pushed); fills d.M2
+static int timed_args(const char *what, const TrackRule &rule, const Detections &det, bool counts,
+                      const int64_t *det_time, const TimedState &st, TimedDims &d, const SceneOut &out) {
+    const int M_max = d.M_max, S = d.S, R = d.R, T_obs = d.T_obs, V = d.V, min_seen = rule.min_seen,
+              max_gap = rule.max_gap;
+    const int64_t step = d.step, max_dt = d.max_dt;
     STG_REQUIRE(M_max >= 1 && M_max <= STG_TRACK_MAX_DETECTIONS && S >= 1 && S <= STG_TRACK_MAX_SLOTS && V >= 1,
                 STG_EINVAL, "%s: bad sizes M_max=%d S=%d V=%d", what, M_max, S, V);
     STG_REQUIRE_RULE(what);
@@ -287,6 +276,10 @@ static int timed_args(const char *what, int M_max, int S, int R, int T_obs, int 
     STG_REQUIRE(max_dt >= 1 && max_dt <= (int64_t)(T_obs - 1) * step, STG_EINVAL,
                 "%s: max_dt=%lld not in [1, (T_obs - 1) * step = %lld]", what, (long long)max_dt,
                 (long long)((int64_t)(T_obs - 1) * step));
+    STG_REQUIRE(det.id && det.xy && counts && det_time && st.slot_id && st.t_ring && st.xy_ring && st.slot_head &&
+                    st.clock && st.head_flags && out.obs_abs && out.out_ids && out.num_peds && out.seen,
+                STG_EINVAL, "%s: null pointer", what);
+    d.M2 = det_sort_n(M_max);
     return STG_OK;
 }
 
@@ -300,17 +293,15 @@ int stg_track_push_timed(const int64_t *det_id, const double *det_xy, const int3
                          int V, int64_t step, int64_t max_dt, int min_seen, int max_gap, double *obs_abs,
                          int64_t *out_ids, int32_t *num_peds, int32_t *seen, void *stream) {
     const char *what = "stg_track_push_timed";
-    const int rc = stg::timed_args(what, M_max, S, R, T_obs, V, step, max_dt, min_seen, max_gap);
+    const stg::Detections det{det_id, 1, det_xy, 2};
+    const stg::TimedState st{slot_id, t_ring, xy_ring, slot_head, clock, head_flags};
+    const stg::TrackRule rule{min_seen, max_gap};
+    const stg::SceneOut out{obs_abs, out_ids, num_peds, seen};
+    stg::TimedDims d{{M_max, 0, S, T_obs, V, scale}, R, step, max_dt};
+    const int rc = stg::timed_args(what, rule, det, det_count != nullptr, det_time, st, d, out);
     if (rc != STG_OK) return rc;
-    STG_REQUIRE(det_id && det_xy && det_count && det_time && slot_id && t_ring && xy_ring && slot_head && clock &&
-                    head_flags && obs_abs && out_ids && num_peds && seen,
-                STG_EINVAL, "%s: null pointer", what);
-    const int m2 = stg::det_sort_n(M_max);
-    return stg::launch({what, dim3(1), dim3(stg::kPushThreads), stg::push_timed_lds(M_max, m2, S, T_obs),
-                        stg::as_stream(stream), 64 * 1024},
-                       stg::track_push_timed_kernel, det_id, det_xy, det_count, det_time, M_max, m2, slot_id, t_ring,
-                       xy_ring, slot_head, clock, head_flags, S, R, T_obs, scale, V, step, max_dt,
-                       stg::TrackRule{min_seen, max_gap}, obs_abs, out_ids, num_peds, seen);
+    return stg::launch({what, dim3(1), dim3(stg::kPushThreads), stg::push_timed_lds(d), stg::as_stream(stream), 64 * 1024},
+                       stg::track_push_timed_kernel, det_id, det_xy, det_count, det_time, st, d, rule, out);
 }
 
 int stg_track_push_streams_timed(const int64_t *det_id, int64_t id_stride, const double *det_xy, int64_t xy_stride,
@@ -321,20 +312,19 @@ int stg_track_push_streams_timed(const int64_t *det_id, int64_t id_stride, const
                                  double *obs_abs, int64_t *out_ids, int32_t *num_peds, int32_t *out_flags,
                                  int32_t *seen, int block_threads, void *stream) {
     const char *what = "stg_track_push_streams_timed";
+    const stg::Detections det{det_id, id_stride, det_xy, xy_stride};
+    const stg::Tick tick{det_start, pushed, M_total};
+    const stg::TimedState st{slot_id, t_ring, xy_ring, slot_head, clock, head_flags};
+    const stg::TrackRule rule{min_seen, max_gap};
+    const stg::SceneOut out{obs_abs, out_ids, num_peds, seen};
+    stg::TimedDims d{{M_max, 0, S, T_obs, V, scale}, R, step, max_dt};
     int rc = stg::push_streams_args(what, NS, M_total, id_stride, xy_stride, block_threads);
-    if (rc == STG_OK) rc = stg::timed_args(what, M_max, S, R, T_obs, V, step, max_dt, min_seen, max_gap);
+    if (rc == STG_OK) rc = stg::timed_args(what, rule, det, det_start && pushed, det_time, st, d, out);
     if (rc != STG_OK) return rc;
-    STG_REQUIRE(det_id && det_xy && det_start && pushed && det_time && slot_id && t_ring && xy_ring && slot_head &&
-                    clock && head_flags && obs_abs && out_ids && num_peds && seen,
-                STG_EINVAL, "%s: null pointer", what);
-    const int m2 = stg::det_sort_n(M_max);
-    const stg::Launch l{what, dim3(NS), dim3(block_threads), stg::push_timed_lds(M_max, m2, S, T_obs),
-                        stg::as_stream(stream), 64 * 1024};
+    const stg::Launch l{what, dim3(NS), dim3(block_threads), stg::push_timed_lds(d), stg::as_stream(stream), 64 * 1024};
     return stg::with_stream_threads(block_threads, [&](auto kt) {
-        return stg::launch(l, stg::track_push_streams_timed_kernel<kt()>, det_id, id_stride, det_xy, xy_stride, M_total,
-                           det_start, pushed, det_time, M_max, m2, slot_id, t_ring, xy_ring, slot_head, clock, head_flags,
-                           S, R, T_obs, scale, V, step, max_dt, stg::TrackRule{min_seen, max_gap}, obs_abs, out_ids,
-                           num_peds, out_flags, seen);
+        return stg::launch(l, stg::track_push_streams_timed_kernel<kt()>, det, tick, det_time, st, d, rule, out,
+                           out_flags);
     });
 }
 

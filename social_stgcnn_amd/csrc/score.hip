@@ -46,7 +46,7 @@
 //   enqueue  behind a barrier: ids, the running covariance sum, and the pedestrians' columns of mean and samples into
 //            row m mod P
 // No host synchronisation (the launch is captured into the live predictors' graph), plain C++ stores only, 24 KB of
-// dynamic LDS at the 2,048-detection limit.
+// dynamic LDS at the 2,048-detection limit (under the 64 KB the launches name: the kernel's limit is never raised).
 #include "detections.hpp"
 
 namespace stg {
@@ -106,12 +106,9 @@ __device__ __forceinline__ void score_empty(const ScoreArgs &a, int b) {
     }
 }
 
-// One push of stream b by one workgroup of kScoreThreads threads: `count` detections, detection j =
-// (det_id[j * id_stride], det_xy[j * xy_stride], det_xy[j * xy_stride + 1]).
+// One push of stream b by one workgroup of kScoreThreads threads: `count` detections of `det` (live_args.hpp).
 // LDS (dynamic): sort keys (M2 x int64), sort indices (M2 x int32)
-__device__ __forceinline__ void score_push_body(const ScoreArgs &a, int b, const int64_t *__restrict__ det_id,
-                                                int64_t id_stride, const double *__restrict__ det_xy,
-                                                int64_t xy_stride, int count) {
+__device__ __forceinline__ void score_push_body(const ScoreArgs &a, int b, const Detections &det, int count) {
     extern __shared__ __align__(16) unsigned char lds[];
     int64_t *key = reinterpret_cast<int64_t *>(lds);
     int32_t *kidx = reinterpret_cast<int32_t *>(key + a.M2);
@@ -139,7 +136,7 @@ __device__ __forceinline__ void score_push_body(const ScoreArgs &a, int b, const
 
     // 1. the detections into the sort buffer (padding keys sort last), sorted by (id, detection index)
     const int n2 = det_sort_n(m);
-    det_load(key, kidx, det_id, id_stride, m, n2, tid, kScoreThreads);
+    det_load(key, kidx, det, m, n2, tid, kScoreThreads);
     __syncthreads();
     det_sort(key, kidx, n2, tid, kScoreThreads);
 
@@ -167,8 +164,8 @@ __device__ __forceinline__ void score_push_body(const ScoreArgs &a, int b, const
                 const int at = det_find(key, m, id);                // the first detection of the id
                 if (at >= 0) {
                     const int j = kidx[at];
-                    const float tx = (float)round_pos(det_xy[j * xy_stride], a.scale);
-                    const float ty = (float)round_pos(det_xy[j * xy_stride + 1], a.scale);
+                    const float tx = (float)round_pos(det.x(j), a.scale);
+                    const float ty = (float)round_pos(det.y(j), a.scale);
                     const int64_t e = ((int64_t)r * P + (h - 1)) * V + v;
                     const float2 mu = *reinterpret_cast<const float2 *>(rec_mean + e * 2);
                     mt = 1;
@@ -309,38 +306,35 @@ __device__ __forceinline__ void score_push_body(const ScoreArgs &a, int b, const
     }
 }
 
-__global__ __launch_bounds__(kScoreThreads) void score_push_kernel(const ScoreArgs a,
-                                                                   const int64_t *__restrict__ det_id,
-                                                                   const double *__restrict__ det_xy,
-                                                                   const int32_t *__restrict__ det_count) {
-    score_push_body(a, 0, det_id, 1, det_xy, 2, det_count[0]);
+__global__ __launch_bounds__(kScoreThreads) void score_push_kernel(
+    const ScoreArgs a, const int64_t *__restrict__ det_id, const double *__restrict__ det_xy,
+    const int32_t *__restrict__ det_count) {
+    score_push_body(a, 0, {det_id, 1, det_xy, 2}, det_count[0]);
 }
 
-// One workgroup per stream: stream b scores against detections det_start[b] .. det_start[b+1]-1 (clamped to
-// [0, M_total)) when pushed[b] != 0, as stg_track_push_streams reads them.
-__global__ __launch_bounds__(kScoreThreads) void score_push_streams_kernel(
-    const ScoreArgs a, const int64_t *__restrict__ det_id, int64_t id_stride, const double *__restrict__ det_xy,
-    int64_t xy_stride, int M_total, const int32_t *__restrict__ det_start, const int32_t *__restrict__ pushed) {
+// One workgroup per stream: stream b scores against its range of the tick when pushed[b] != 0, as
+// stg_track_push_streams reads them.
+__global__ __launch_bounds__(kScoreThreads) void score_push_streams_kernel(const ScoreArgs a, Detections det, Tick tick) {
     const int b = blockIdx.x;
-    if (pushed[b] == 0) {                                   // uniform over the block
+    if (tick.pushed_at(b) == 0) {                           // uniform over the block
         score_empty(a, b);
         return;
     }
     int lo;
-    const int count = det_range(det_start, b, M_total, lo);
-    score_push_body(a, b, det_id + lo * id_stride, id_stride, det_xy + lo * xy_stride, xy_stride, count);
+    const int count = tick.range(b, lo);
+    score_push_body(a, b, det.from(lo), count);
 }
 
-// the checks both entry points share; fills `a`
-static int score_args(const char *what, int NS, int M_max, double scale, const float *mean, const float *v_pred,
-                      int64_t p_sn, int64_t p_sf, int64_t p_sp, int64_t p_sv, const float *samples,
-                      const int64_t *ids, const int32_t *num_peds, int P, int V, int K, const stg_score_state *st,
-                      const float *thr, int Q, const stg_score_out *out, ScoreArgs *a) {
+// the checks both entry points share, on `a` as the entry point filled it from its arguments; completes it (st, out, M2)
+static int score_args(const char *what, const stg_score_state *st, const stg_score_out *out, ScoreArgs *a) {
+    const int NS = a->NS, M_max = a->M_max, P = a->P, V = a->V, Q = a->Q;
+    int K = a->K;
+    const float *mean = a->mean, *v_pred = a->v_pred, *samples = a->samples, *thr = a->thr;
     STG_REQUIRE(M_max >= 1 && P >= 1 && V >= 1 && K >= 0 && Q >= 0, STG_EINVAL,
                 "%s: bad sizes M_max=%d P=%d V=%d K=%d Q=%d", what, M_max, P, V, K, Q);
     STG_REQUIRE(st && out, STG_EINVAL, "%s: null pointer (state / out)", what);
     if (!samples) K = 0;
-    STG_REQUIRE(mean && v_pred && ids && num_peds, STG_EINVAL, "%s: null pointer (mean / v_pred / ids / num_peds)", what);
+    STG_REQUIRE(mean && v_pred && a->ids && a->num_peds, STG_EINVAL, "%s: null pointer (mean / v_pred / ids / num_peds)", what);
     STG_REQUIRE(st->rec_ids && st->rec_peds && st->rec_mean && st->rec_cov && st->acc_mean && st->steps && st->head &&
                     st->totals && st->traj_totals,
                 STG_EINVAL, "%s: null pointer in the state", what);
@@ -362,8 +356,11 @@ static int score_args(const char *what, int NS, int M_max, double scale, const f
     STG_REQUIRE(K <= STG_SCORE_MAX_K, STG_EUNSUPPORTED, "%s: K=%d above STG_SCORE_MAX_K=%d", what, K, STG_SCORE_MAX_K);
     STG_REQUIRE(P <= STG_SCORE_MAX_P, STG_EUNSUPPORTED, "%s: P=%d above STG_SCORE_MAX_P=%d", what, P, STG_SCORE_MAX_P);
     STG_REQUIRE(Q <= STG_SCORE_MAX_Q, STG_EUNSUPPORTED, "%s: Q=%d above STG_SCORE_MAX_Q=%d", what, Q, STG_SCORE_MAX_Q);
-    *a = ScoreArgs{mean, v_pred, p_sn, p_sf, p_sp, p_sv, K > 0 ? samples : nullptr, ids, num_peds, *st, thr, *out,
-                   NS, P, V, K, Q, M_max, det_sort_n(M_max), scale};
+    a->samples = K > 0 ? samples : nullptr;
+    a->K = K;
+    a->st = *st;
+    a->out = *out;
+    a->M2 = det_sort_n(M_max);
     return STG_OK;
 }
 
@@ -375,15 +372,16 @@ int stg_score_push(const int64_t *det_id, const double *det_xy, const int32_t *d
                    const float *mean, const float *v_pred, int64_t p_sn, int64_t p_sf, int64_t p_sp, int64_t p_sv,
                    const float *samples, const int64_t *ids, const int32_t *num_peds, int P, int V, int K,
                    const stg_score_state *state, const float *thr, int Q, const stg_score_out *out, void *stream) {
-    stg::ScoreArgs a;
-    const int rc = stg::score_args("stg_score_push", 1, M_max, scale, mean, v_pred, p_sn, p_sf, p_sp, p_sv, samples, ids,
-                                   num_peds, P, V, K, state, thr, Q, out, &a);
+    stg::ScoreArgs a{};
+    a.mean = mean, a.v_pred = v_pred, a.samples = samples, a.ids = ids, a.num_peds = num_peds, a.thr = thr;
+    a.p_sn = p_sn, a.p_sf = p_sf, a.p_sp = p_sp, a.p_sv = p_sv, a.scale = scale;
+    a.NS = 1, a.P = P, a.V = V, a.K = K, a.Q = Q, a.M_max = M_max;
+    const int rc = stg::score_args("stg_score_push", state, out, &a);
     if (rc != STG_OK) return rc;
     STG_REQUIRE(det_id && det_xy && det_count, STG_EINVAL, "stg_score_push: null pointer (detections)");
-    hipLaunchKernelGGL(stg::score_push_kernel, dim3(1), dim3(stg::kScoreThreads), stg::det_sort_lds(a.M2),
-                       stg::as_stream(stream), a, det_id, det_xy, det_count);
-    STG_LAUNCH_CHECK("stg_score_push");
-    return STG_OK;
+    return stg::launch({"stg_score_push", dim3(1), dim3(stg::kScoreThreads), stg::det_sort_lds(a.M2),
+                        stg::as_stream(stream), 64 * 1024},
+                       stg::score_push_kernel, a, det_id, det_xy, det_count);
 }
 
 int stg_score_push_streams(const int64_t *det_id, int64_t id_stride, const double *det_xy, int64_t xy_stride,
@@ -392,23 +390,23 @@ int stg_score_push_streams(const int64_t *det_id, int64_t id_stride, const doubl
                            int64_t p_sp, int64_t p_sv, const float *samples, const int64_t *ids,
                            const int32_t *num_peds, int P, int V, int K, const stg_score_state *state,
                            const float *thr, int Q, const stg_score_out *out, void *stream) {
-    STG_REQUIRE(NS >= 0 && M_total >= 0 && id_stride >= 1 && xy_stride >= 2, STG_EINVAL,
-                "stg_score_push_streams: bad sizes NS=%d M_total=%d strides %lld/%lld", NS, M_total,
-                (long long)id_stride, (long long)xy_stride);
-    if (NS == 0) return STG_OK;
-    stg::ScoreArgs a;
-    const int rc = stg::score_args("stg_score_push_streams", NS, M_max, scale, mean, v_pred, p_sn, p_sf, p_sp, p_sv,
-                                   samples, ids, num_peds, P, V, K, state, thr, Q, out, &a);
+    int rc = stg::stream_args("stg_score_push_streams", NS, M_total, id_stride, xy_stride, 0, false);    // (see there)
+    if (rc != STG_OK || NS == 0) return rc;
+    stg::ScoreArgs a{};
+    a.mean = mean, a.v_pred = v_pred, a.samples = samples, a.ids = ids, a.num_peds = num_peds, a.thr = thr;
+    a.p_sn = p_sn, a.p_sf = p_sf, a.p_sp = p_sp, a.p_sv = p_sv, a.scale = scale;
+    a.NS = NS, a.P = P, a.V = V, a.K = K, a.Q = Q, a.M_max = M_max;
+    rc = stg::score_args("stg_score_push_streams", state, out, &a);
     if (rc != STG_OK) return rc;
     STG_REQUIRE(det_id && det_xy && det_start && pushed, STG_EINVAL,
                 "stg_score_push_streams: null pointer (detections)");
     STG_REQUIRE(M_total <= STG_TRACK_MAX_TOTAL_DETECTIONS, STG_EUNSUPPORTED,
                 "stg_score_push_streams: M_total=%d above STG_TRACK_MAX_TOTAL_DETECTIONS=%d", M_total,
                 STG_TRACK_MAX_TOTAL_DETECTIONS);
-    hipLaunchKernelGGL(stg::score_push_streams_kernel, dim3((unsigned)NS), dim3(stg::kScoreThreads), stg::det_sort_lds(a.M2),
-                       stg::as_stream(stream), a, det_id, id_stride, det_xy, xy_stride, M_total, det_start, pushed);
-    STG_LAUNCH_CHECK("stg_score_push_streams");
-    return STG_OK;
+    return stg::launch({"stg_score_push_streams", dim3((unsigned)NS), dim3(stg::kScoreThreads), stg::det_sort_lds(a.M2),
+                        stg::as_stream(stream), 64 * 1024},
+                       stg::score_push_streams_kernel, a, stg::Detections{det_id, id_stride, det_xy, xy_stride},
+                       stg::Tick{det_start, pushed, M_total});
 }
 
 }  // extern "C"

@@ -160,42 +160,37 @@ __device__ __forceinline__ void assign_slots(int64_t *key, int32_t *kidx, int32_
     __syncthreads();
 }
 
-// The padding of one scene obs (T_obs,V,2), oid (V), osn (V, or null): slots [from, V) get id -1, seen 0 and zero
-// positions; from = 0 is the whole empty scene.  num_peds and the flags are the caller's.  No barrier.
-__device__ __forceinline__ void pad_scene(double *obs, int64_t *oid, int32_t *osn, int T_obs, int V, int from) {
+// The padding of one scene (o.seen may be null): slots [from, V) get id -1, seen 0 and zero positions; from = 0 is the
+// whole empty scene.  num_peds and the flags are the caller's.  No barrier.
+__device__ __forceinline__ void pad_scene(const SceneOut &o, int T_obs, int V, int from) {
     const int tid = threadIdx.x, nt = blockDim.x;
     for (int e = from + tid; e < V; e += nt) {
-        oid[e] = -1;
-        if (osn) osn[e] = 0;
+        o.out_ids[e] = -1;
+        if (o.seen) o.seen[e] = 0;
     }
     for (int e = tid; e < T_obs * (V - from); e += nt) {
         const int t = e / (V - from), r = from + e % (V - from);
-        obs[((int64_t)t * V + r) * 2] = 0.0;
-        obs[((int64_t)t * V + r) * 2 + 1] = 0.0;
+        o.obs_abs[((int64_t)t * V + r) * 2] = 0.0;
+        o.obs_abs[((int64_t)t * V + r) * 2 + 1] = 0.0;
     }
 }
 
-// One workgroup per stream: stream b = blockIdx.x pushes detections det_start[b] .. det_start[b+1]-1 (clamped to
-// [0, M_total)) when pushed[b] != 0: flags = body(first, count, obs, oid, osn, num_peds + b) on its own slices of the
-// (NS, ...) outputs (seen may be null, osn then too); the body slices its state by b.  Otherwise no state is touched
-// and the scene is the empty one.
+// One workgroup per stream: stream b = blockIdx.x pushes its range of the tick when pushed[b] != 0: flags =
+// body(its detections, count, its scene), the scene being its slices of the (NS, ...) outputs; the body slices its
+// state by b (of_stream).  Otherwise no state is touched and the scene is the empty one.
 template <class Body>
-__device__ __forceinline__ void push_stream(const int32_t *__restrict__ det_start, const int32_t *__restrict__ pushed,
-                                            int M_total, int T_obs, int V, double *__restrict__ obs_abs,
-                                            int64_t *__restrict__ out_ids, int32_t *__restrict__ seen,
-                                            int32_t *__restrict__ num_peds, int32_t *__restrict__ out_flags, Body body) {
+__device__ __forceinline__ void push_stream(const Detections &det, const Tick &tick, const SceneOut &out, int T_obs, int V,
+                                            int32_t *__restrict__ out_flags, Body body) {
     const int b = blockIdx.x;
-    double *obs = obs_abs + (int64_t)b * T_obs * V * 2;
-    int64_t *oid = out_ids + (int64_t)b * V;
-    int32_t *osn = seen ? seen + (int64_t)b * V : nullptr;
+    const SceneOut mine = out.of_stream(b, T_obs, V);
     int flags = 0;
-    if (pushed[b] == 0) {                                   // uniform over the block: no barrier is skipped halfway
-        pad_scene(obs, oid, osn, T_obs, V, 0);
-        if (threadIdx.x == 0) num_peds[b] = 0;
+    if (tick.pushed_at(b) == 0) {                           // uniform over the block: no barrier is skipped halfway
+        pad_scene(mine, T_obs, V, 0);
+        if (threadIdx.x == 0) mine.num_peds[0] = 0;
     } else {
         int lo;
-        const int count = det_range(det_start, b, M_total, lo);
-        flags = body(lo, count, obs, oid, osn, num_peds + b);
+        const int count = tick.range(b, lo);
+        flags = body(det.from(lo), count, mine);
     }
     if (out_flags && threadIdx.x == 0) out_flags[b] = flags;
 }
@@ -208,14 +203,12 @@ __device__ __forceinline__ void push_stream(const int32_t *__restrict__ det_star
                 STG_EINVAL, "%s: min_seen=%d not in [2, T_obs=%d] or max_gap=%d not in [0, T_obs - 2]", what, min_seen, \
                 T_obs, max_gap)
 
-// What the _streams pushes check of their streams, under the entry point's name `what`, and their workgroup size:
-// block_threads = 0 becomes kStreamThreads
+// What the _streams pushes check of their streams (stream_args, live_args.hpp), under the entry point's name `what`, and
+// their workgroup size: block_threads = 0 becomes kStreamThreads
 static inline int push_streams_args(const char *what, int NS, int M_total, int64_t id_stride, int64_t xy_stride,
                                     int &block_threads) {
-    STG_REQUIRE(NS >= 1 && NS <= STG_TRACK_MAX_STREAMS && M_total >= 0 && M_total <= STG_TRACK_MAX_TOTAL_DETECTIONS &&
-                    id_stride >= 1 && xy_stride >= 2,
-                STG_EINVAL, "%s: bad sizes NS=%d M_total=%d strides %lld/%lld", what, NS, M_total, (long long)id_stride,
-                (long long)xy_stride);
+    const int rc = stream_args(what, NS, M_total, id_stride, xy_stride);
+    if (rc != STG_OK) return rc;
     if (block_threads == 0) block_threads = kStreamThreads;
     STG_REQUIRE(block_threads == 64 || block_threads == 256 || block_threads == 1024, STG_EINVAL,
                 "%s: block_threads=%d (0, 64, 256 or 1024)", what, block_threads);

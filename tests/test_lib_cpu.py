@@ -29,6 +29,52 @@ def test_header_symbols_are_exported(L):
     assert L.stg_abi_version() == _lib.ABI_VERSION
 
 
+def test_header_prototypes_match_the_binding():
+    """Every prototype of include/stgcnn_hip.h, its return and parameter types mapped to ctypes, equals the restype /
+    argtypes _lib binds it with: the header and _lib._SIGNATURES are two hand-written copies of the C ABI."""
+    from social_stgcnn_amd import _lib
+    hdr = open(os.path.join(ROOT, "include", "stgcnn_hip.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
+    hdr = re.sub(r"//[^\n]*", " ", hdr)
+    hdr = "\n".join(l for l in hdr.split("\n") if not l.lstrip().startswith("#"))
+    structs = {"stg_model_desc": ctypes.POINTER(_lib.ModelDesc), "stg_score_state": ctypes.POINTER(_lib.ScoreState),
+               "stg_score_out": ctypes.POINTER(_lib.ScoreOut), "stg_step_tail": ctypes.c_void_p}
+    scalars = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64,
+               "float": ctypes.c_float, "double": ctypes.c_double}
+
+    def ctype(decl, named):
+        """`decl`: a C type, followed by the parameter's name when `named`"""
+        words = decl.replace("*", " * ").split()
+        stars = words.count("*")
+        words = [w for w in words if w not in ("*", "const", "struct")]
+        base = words[0]
+        assert len(words) == (2 if named else 1), decl
+        if stars == 0:
+            return scalars[base]
+        if base in structs:
+            assert stars == 1, decl
+            return structs[base]
+        if base == "char":
+            assert stars == 1, decl
+            return ctypes.c_char_p
+        if stars == 2:                     # void **, int64_t *const *: a host array of device pointers
+            assert base not in structs, decl
+            return ctypes.POINTER(ctypes.c_void_p)
+        assert stars == 1, decl
+        return ctypes.c_void_p
+
+    protos = re.findall(r"([A-Za-z_][\w\s\*]*?)\b(stg_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", hdr)
+    assert len(protos) == 51 and len({name for _, name, _ in protos}) == 51, \
+        "%d prototypes parsed, 51 pinned: a new entry point changes this count on purpose" % len(protos)
+    assert {name for _, name, _ in protos} == set(_lib._SIGNATURES)
+    for ret, name, params in protos:
+        args = [] if params.strip() == "void" else [ctype(p, True) for p in params.split(",")]
+        res, bound = _lib._SIGNATURES[name]
+        assert ctype(ret, False) == res, (name, ret, res)
+        assert args == list(bound), (name, [i for i, (a, b) in enumerate(zip(args, bound)) if a != b],
+                                     len(args), len(bound))
+
+
 def test_layout_queries_match_reference_counts(L):
     from social_stgcnn_amd import ops
     d = ops.make_desc(1, 5, 2, 5, 8, 12, 3, 2, False, True)
