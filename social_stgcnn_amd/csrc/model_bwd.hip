@@ -54,7 +54,6 @@ struct BwdArgs {
     int debug_skip;   // timing-only diagnostic (STG_DEBUG_SKIP): 1 wgrad, 2 dgrad, 4 st_gcn -- wrong results
 };
 
-
 // ------------------------------------------------------------------------------------------
 // TXP-CNN backward pieces
 // ------------------------------------------------------------------------------------------
@@ -388,11 +387,6 @@ __global__ __launch_bounds__(256) void reduce_slabs_kernel(const ReduceArgs a, c
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
-static int env_waves(const char *name, int dflt) {     // (diagnostic builds only; the product returns dflt)
-    const int w = diag_env(name, dflt);
-    return (w == 1 || w == 2 || w == 4 || w == 8) ? w : dflt;
-}
-
 static size_t bwd_lds_bytes(const ModelLayout &L, int V, int waves) {
     const int plane = Cfg::P * txp_sc(V);
     const int st = (2 * Cfg::C * (Cfg::T + 2) + Cfg::C * Cfg::T) * V;
@@ -464,68 +458,58 @@ static bool bwd_carve(const ModelLayout &L, const StepPath &path, int N, int V, 
     return true;
 }
 
+// one item of the carve for the two size queries of the backward, which refuse an empty batch (-1: not in use)
+static int64_t bwd_query(const char *what, const stg_model_desc *d, int N, int V, int64_t BwdCarve::*item) {
+    StepPlan p;
+    const int rc = plan_sized(what, d, nullptr, N, V, 1, &p);
+    if (rc != STG_OK) return rc;
+    BwdCarve c;
+    WgradGeom wg{};
+    STG_REQUIRE(bwd_carve(p.lay, p.path, N, V, &c, &wg), STG_ELDS, "stg_model_bwd: V=%d does not fit the LDS of one CU", V);
+    return c.*item >= 0 ? c.*item : STG_EUNSUPPORTED;
+}
+
 }  // namespace stg
 
 extern "C" {
 
 int64_t stg_model_bwd_scratch_floats(const stg_model_desc *d, int N, int V) {
-    stg::ModelLayout l;
-    const int rc = stg::make_layout(d, &l);
-    if (rc != STG_OK) return rc;
-    if (N <= 0 || V <= 0) return stg::fail(STG_EINVAL, "stg_model_bwd_scratch_floats: N=%d V=%d", N, V);
-    stg::BwdCarve c;
-    stg::WgradGeom wg{};
-    if (!stg::bwd_carve(l, stg::choose_path(l, N, V), N, V, &c, &wg)) return stg::fail(STG_ELDS, "stg_model_bwd: V=%d does not fit the LDS of one CU", V);
-    return c.total;
+    return stg::bwd_query("stg_model_bwd_scratch_floats:", d, N, V, &stg::BwdCarve::total);
 }
 int64_t stg_model_bwd_stamps_offset(const stg_model_desc *d, int N, int V) {
-    stg::ModelLayout l;
-    const int rc = stg::make_layout(d, &l);
-    if (rc != STG_OK) return rc;
-    if (N <= 0 || V <= 0) return stg::fail(STG_EINVAL, "stg_model_bwd_stamps_offset: N=%d V=%d", N, V);
-    stg::BwdCarve c;
-    stg::WgradGeom wg{};
-    if (!stg::bwd_carve(l, stg::choose_path(l, N, V), N, V, &c, &wg)) return stg::fail(STG_ELDS, "stg_model_bwd: V=%d does not fit the LDS of one CU", V);
-    return c.stamps >= 0 ? c.stamps : STG_EUNSUPPORTED;
+    return stg::bwd_query("stg_model_bwd_stamps_offset:", d, N, V, &stg::BwdCarve::stamps);
 }
 
 }  // extern "C"
 
 namespace stg {
 
-// dy = dV_pred, or (nll_target != null) V_pred itself: the wave-per-scene backward then computes the loss gradient in
+// b.dy = dV_pred, or (b.nll_target != null) V_pred itself: the wave-per-scene backward then computes the loss gradient in
 // its input stage and writes the per-scene losses (stg_model_bwd_nll).  `deferred` (stg_model_step): the scene launch
 // the forward left to this one -- both run as one launch.
-int model_bwd_impl(const stg_model_desc *d, const float *params, const float *buffers, const float *x, int64_t x_sn,
-                   int64_t x_sc, int64_t x_st, int64_t x_sv, const float *adj, int64_t a_sn, const int32_t *num_peds,
-                   int N, int V, const float *dy, const float *nll_target, const float *nll_weights, float *nll_losses,
-                   const stg_step_tail *tail, const float *ws, float *scratch, float *grad_params, float *dx,
-                   void **events, int n_events, void *stream, const TxpFwdArgs *deferred) {
-    BwdArgs a{};
-    const int rc = make_layout(d, &a.lay);
-    if (rc != STG_OK) return rc;
-    const ModelLayout &L = a.lay;
-    STG_REQUIRE(N >= 0 && V > 0, STG_EINVAL, "stg_model_bwd: bad sizes N=%d V=%d", N, V);
-    STG_REQUIRE(grad_params, STG_EINVAL, "stg_model_bwd: null grad_params");
-    STG_REQUIRE(N == 0 || (params && buffers && x && adj && dy && ws && scratch), STG_EINVAL,
+int model_bwd_impl(const ModelCall &c, const BwdBuffers &b, const StepPlan &p, const TxpFwdArgs *deferred) {
+    const SceneInput &in = c.in;
+    const int N = in.N, V = in.V;
+    const ModelLayout &L = p.lay;
+    STG_REQUIRE(b.grad_params, STG_EINVAL, "stg_model_bwd: null grad_params");
+    STG_REQUIRE(N == 0 || (c.params && c.buffers && in.x && in.adj && b.dy && b.ws && b.scratch), STG_EINVAL,
                 "stg_model_bwd: null pointer");
-    STG_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0 && (reinterpret_cast<uintptr_t>(scratch) & 15) == 0,
-                STG_EINVAL, "stg_model_bwd: ws / scratch must be 16-byte aligned");
-    hipStream_t st = as_stream(stream);
-    EventList evl{events, events ? n_events : 0, 0, st};
+    STG_REQUIRE(aligned(b.ws, 16) && aligned(b.scratch, 16), STG_EINVAL, "stg_model_bwd: ws / scratch must be 16-byte aligned");
+    hipStream_t st = as_stream(c.stream);
+    EventList evl{b.events, b.events ? b.n_events : 0, 0, st};
     evl.mark();
     if (N == 0) {
-        hipError_t e = hipMemsetAsync(grad_params, 0, sizeof(float) * L.n_params, st);
+        hipError_t e = hipMemsetAsync(b.grad_params, 0, sizeof(float) * L.n_params, st);
         if (e != hipSuccess) return hip_fail(e, "stg_model_bwd: memset");
         return STG_OK;
     }
     BwdCarve cv;
     WgradGeom wg{};
-    const StepPath path = choose_path(L, N, V);
+    const StepPath &path = p.path;
     STG_REQUIRE(bwd_carve(L, path, N, V, &cv, &wg), STG_ELDS, "stg_model_bwd: V=%d does not fit the LDS of one CU", V);
     const int n_small = L.n_blk_params + L.n_txp;
-    float *rows = scratch + cv.rows, *slab2 = scratch + cv.slab2;
-    float *dzg = L.n_txp > 0 ? scratch + cv.dzg : nullptr;
+    float *rows = b.scratch + cv.rows, *slab2 = b.scratch + cv.slab2;
+    float *dzg = L.n_txp > 0 ? b.scratch + cv.dzg : nullptr;
     // the wave-per-scene kernels compute no input gradient (the reference never needs one: x is data), and their
     // saved pre-activations are laid out for themselves: a caller that wants dx runs BOTH passes on the workgroup
     // kernels (STG_OPT_WG_PATH in the descriptor)
@@ -533,54 +517,48 @@ int model_bwd_impl(const stg_model_desc *d, const float *params, const float *bu
                 "stg_model_bwd: bf16 storage (STG_OPT_BF16_STORE) is built for the wave-per-scene kernels only");
     STG_REQUIRE(!((L.flags & STG_OPT_BF16_STORE) && (L.flags & STG_OPT_SPLIT_BF16)), STG_EUNSUPPORTED,
                 "stg_model_bwd: STG_OPT_BF16_STORE and STG_OPT_SPLIT_BF16 cannot be combined");
-    if (nll_target && ((L.flags & STG_OPT_SPLIT_BF16) || L.n_txp == 0))
+    if (b.nll_target && ((L.flags & STG_OPT_SPLIT_BF16) || L.n_txp == 0))
         return STG_EUNSUPPORTED;        // (no message: the caller falls back to stg_nll_fwd + stg_model_bwd)
-    STG_REQUIRE(!(path.scene() && dx), STG_EUNSUPPORTED,
+    STG_REQUIRE(!(path.scene() && b.dx), STG_EUNSUPPORTED,
                 "stg_model_bwd: dx is only computed by the workgroup-per-scene kernels: set STG_OPT_WG_PATH in the "
                 "descriptor of the forward and the backward call");
-    a.params = params; a.buffers = buffers; a.x = x;
-    a.x_sn = x_sn; a.x_sc = x_sc; a.x_st = x_st; a.x_sv = x_sv;
-    a.adj = adj; a.a_sn = a_sn; a.num_peds = num_peds; a.N = N; a.V = V;
-    a.nll_target = nll_target; a.nll_weights = nll_weights; a.nll_losses = nll_losses;
-    a.dy = dy; a.ws = ws; a.ws_stride = ws_floats_per_scene(L, V); a.slab1 = rows; a.dzg = dzg; a.dx = dx;
-    // ragged batch: sorted scene list at the tail of the scratch buffer
-    int32_t *order = reinterpret_cast<int32_t *>(scratch + cv.order);
-    bool sorted;
-    const WsTail wt = ws_tail(L, path, N, V);
-    const float *ws_end = ws + wt.base;       // (the batch tail of the workspace)
-    if (tail_has_order(path, num_peds, N, V)) {
-        // the forward left its order in the workspace's batch tail
-        order = reinterpret_cast<int32_t *>(const_cast<float *>(ws_end) + wt.order);
-        sorted = true;
-    } else {
-        sorted = launch_scene_order(num_peds, N, V, order, order + N, st, order + N + V + 2);
-    }
-    int32_t *order_peds = order + N + V + 2;
-    const int serp = diag_env("STG_WALK", 1);
-    a.tier = SceneTier{sorted ? order : nullptr, sorted ? order + N : nullptr, -1, V, serp};
-    a.debug_skip = diag_env("STG_DEBUG_SKIP", 0);
+    // ragged batch: the order the forward left in the workspace's batch tail, or a sort into the tail of the scratch buffer
+    const float *ws_end = b.ws + p.tail.base;       // (the batch tail of the workspace)
+    const bool in_tail = tail_has_order(path, in.num_peds, N, V);
+    float *order = in_tail ? const_cast<float *>(ws_end) + p.tail.order : b.scratch + cv.order;
+    const SceneOrder so = scene_order_at(reinterpret_cast<int32_t *>(order), N, V);
+    const bool sorted = in_tail || launch_scene_order(in.num_peds, N, V, so, st);
+    const SceneTier tier{sorted ? so.order : nullptr, sorted ? so.key_start : nullptr, -1, V, diag_env("STG_WALK", 1)};
+    // what the argument structs of K1 (both kernel families) and K2 take from the call and the plan ...
+    const auto fill = [&](auto &a) {
+        set_input(a, c);
+        a.lay = L; a.ws_stride = p.ws_stride; a.ws = b.ws; a.dzg = dzg;
+        a.debug_skip = diag_env("STG_DEBUG_SKIP", 0);
+    };
+    const auto fill_k1 = [&](auto &a) {                 // ... and the two of K1 beside that
+        fill(a);
+        a.dy = b.dy; a.nll_target = b.nll_target; a.nll_weights = b.nll_weights; a.nll_losses = b.nll_losses;
+        a.tier = tier;
+    };
     int slab_rows;
     if (path.scene()) {
         // K1 (wave per scene): TXP input-gradient chain + st_gcn block backward; one small-gradient row per scene
         TxpBwdArgs t{};
-        t.lay = L; t.params = params; t.num_peds = num_peds; t.N = N; t.V = V; t.dy = dy; t.ws = ws;
-        t.nll_target = nll_target; t.nll_weights = nll_weights; t.nll_losses = nll_losses;
-        t.x = x; t.x_sn = x_sn; t.x_sc = x_sc; t.x_st = x_st; t.x_sv = x_sv; t.adj = adj; t.a_sn = a_sn;
-        t.ws_stride = a.ws_stride; t.dzg = dzg; t.rows = rows;
-        t.tier = a.tier;
-        t.Vl = V;
-        t.debug_skip = a.debug_skip;
+        fill_k1(t);
+        t.rows = rows; t.Vl = V;
         t.split_bf16 = (L.flags & STG_OPT_SPLIT_BF16) ? 1 : 0;
         t.stagger = diag_env("STG_STAGGER_B", 0);
-        if (wt.wp >= 0) t.wp = reinterpret_cast<const unsigned *>(ws_end + wt.wp);
-        if (cv.stamps >= 0) t.stamps = reinterpret_cast<unsigned long long *>(scratch + cv.stamps);
-        STG_REQUIRE(!deferred || step_one_launch(L, path, num_peds, N, V), STG_EINVAL,
-                    "stg_model_bwd: a deferred scene launch outside the one-launch step");
+        if (p.tail.wp >= 0) t.wp = reinterpret_cast<const unsigned *>(ws_end + p.tail.wp);
+        if (cv.stamps >= 0) t.stamps = reinterpret_cast<unsigned long long *>(b.scratch + cv.stamps);
+        STG_REQUIRE(!deferred || p.one_launch, STG_EINVAL, "stg_model_bwd: a deferred scene launch outside the one-launch step");
         const int rcw = deferred ? launch_scene_step(*deferred, t, st) : launch_scene_bwd(path, t, st);
         if (rcw != STG_OK) return rcw;
         slab_rows = N;
     } else {
         STG_REQUIRE(!deferred, STG_EINVAL, "stg_model_bwd: a deferred scene launch outside the one-launch step");
+        BwdArgs a{};
+        fill_k1(a);
+        a.buffers = c.buffers; a.slab1 = rows; a.dx = b.dx;
         const int waves = bwd_waves(path, V);
         const size_t lds = bwd_lds_bytes(L, V, waves);
         STG_REQUIRE(lds <= (size_t)kLdsBytes, STG_ELDS, "stg_model_bwd: V=%d needs %zu bytes of LDS (> %d)", V, lds,
@@ -596,7 +574,7 @@ int model_bwd_impl(const stg_model_desc *d, const float *params, const float *bu
         slab_rows = grid;
         const int grid_small = a.tier.order ? bwd_grid_small(L, N, V) : 0;
         if (grid_small > 0) a.tier.v_lo = kBwdTierV;        // large scenes only: `waves` per scene, slab rows [0, grid)
-        int rck = launch(Launch{"stg_model_bwd: K1", dim3(grid), dim3(waves * 64), lds, st}, k1, a, params);
+        int rck = launch(Launch{"stg_model_bwd: K1", dim3(grid), dim3(waves * 64), lds, st}, k1, a, c.params);
         if (rck != STG_OK) return rck;
         if (grid_small > 0) {
             // small scenes: one wave per scene with the LDS image (and so the residency) of V = kBwdTierV, slab rows behind
@@ -604,30 +582,27 @@ int model_bwd_impl(const stg_model_desc *d, const float *params, const float *bu
             a.tier.v_lo = -1; a.tier.v_hi = kBwdTierV;
             a.slab1 = rows + (int64_t)grid * n_small;
             rck = launch(Launch{"stg_model_bwd: K1 (small scenes)", dim3(grid_small), dim3(64), bwd_lds_bytes(L, kBwdTierV, 1), st},
-                         model_bwd_kernel<1>, a, params);
+                         model_bwd_kernel<1>, a, c.params);
             if (rck != STG_OK) return rck;
             slab_rows = grid + grid_small;
-            a.slab1 = rows;
-            a.Vl = 0;
-            a.tier.v_hi = V;
         }
     }
     evl.mark();
 
     ReduceArgs r{};
-    r.slabs = scratch;
-    r.grad = grad_params;
+    r.slabs = b.scratch;
+    r.grad = b.grad_params;
     r.n_params = L.n_params;
     r.seg[r.n_seg++] = ReduceSeg{0, L.n_blk_params, slab_rows, n_small, cv.rows};
     if (L.n_txp > 0) {
         r.seg[r.n_seg++] = ReduceSeg{L.prelus, L.n_txp, slab_rows, n_small, cv.rows + (int64_t)L.n_blk_params};
         WgradArgs w{};
-        w.lay = L; w.num_peds = num_peds; w.order = a.tier.order; w.order_peds = sorted ? order_peds : nullptr;
-        w.key_start = a.tier.key_start;
-        w.serpentine = a.tier.serpentine; w.N = N; w.V = V;
-        w.ws = ws; w.dzg = dzg; w.ws_stride = a.ws_stride; w.slab2 = slab2; w.rows = wg.rows; w.debug_skip = a.debug_skip;
+        fill(w);
+        w.order = tier.order; w.order_peds = sorted ? so.order_peds : nullptr; w.key_start = tier.key_start;
+        w.serpentine = tier.serpentine;
+        w.slab2 = slab2; w.rows = wg.rows;
         for (int l = 0; l <= L.L + 1; ++l) w.wg_begin[l] = wg.wg_begin[l];
-        if (!STG_SKIP(a, 1)) {
+        if (!STG_SKIP(w, 1)) {
             const int rck = launch_txp_wgrad(w, wg, st);
             if (rck != STG_OK) return rck;
         }
@@ -635,18 +610,18 @@ int model_bwd_impl(const stg_model_desc *d, const float *params, const float *bu
         for (int l = 0; l <= L.L; ++l) {
             const int p0 = l == L.L ? L.out_w : L.txp_w[l];
             // (only the rows the layer's workgroups wrote: no memset of the slab needed)
-            r.seg[r.n_seg++] = ReduceSeg{p0, wgrad_row_len(l), STG_SKIP(a, 1) ? 0 : wg.wg_begin[l + 1] - wg.wg_begin[l],
+            r.seg[r.n_seg++] = ReduceSeg{p0, wgrad_row_len(l), STG_SKIP(w, 1) ? 0 : wg.wg_begin[l + 1] - wg.wg_begin[l],
                                          wgrad_row_len(l), cv.slab2 + wgrad_slab_base(l, wg.rows)};
         }
     }
     TailArgs ta{};
     ta.n_reduce = (L.n_params + 7) / 8;
     int extra = 0;
-    if (tail) {
+    if (const stg_step_tail *tail = b.tail) {
         ta.params = tail->params; ta.lr_dev = tail->lr_dev; ta.lr = tail->lr;
         ta.stats = tail->stats; ta.buffers = tail->buffers; ta.total = tail->total;
-        ta.losses = nll_losses; ta.weights = nll_weights; ta.num_peds = num_peds;
-        ta.N = N; ta.stat_floats = L.stat_floats; ta.momentum = d->bn_momentum;
+        ta.losses = b.nll_losses; ta.weights = b.nll_weights; ta.num_peds = in.num_peds;
+        ta.N = N; ta.stat_floats = L.stat_floats; ta.momentum = c.d->bn_momentum;
         ta.n_buffers = (tail->stats && N > 0) ? L.n_buffers : 0;
         ta.nbt.n = tail->nbt ? tail->n_bn : 0;
         for (int k = 0; k < ta.nbt.n; ++k) ta.nbt.p[k] = tail->nbt[k];
@@ -659,27 +634,39 @@ int model_bwd_impl(const stg_model_desc *d, const float *params, const float *bu
     return STG_OK;
 }
 
+// the tail of stg_model_bwd_step / stg_model_step as the reduction launch can carry it
+static bool tail_ok(const stg_step_tail *tail) {
+    return tail && tail->params && !(tail->stats && !tail->buffers) && tail->n_bn >= 0 && tail->n_bn <= 3 * STG_MAX_BLOCKS;
+}
+
+// stg_model_bwd and its two forms with the fused loss: one plan, one pass
+static int run_bwd(const ModelCall &c, const BwdBuffers &b) {
+    StepPlan p;
+    const int rc = plan_sized("stg_model_bwd: bad sizes", c.d, c.in.num_peds, c.in.N, c.in.V, 0, &p);
+    return rc != STG_OK ? rc : model_bwd_impl(c, b, p, nullptr);
+}
+
 }  // namespace stg
 
 extern "C" {
 
-using stg::model_bwd_impl;
+using namespace stg;
 
 int stg_model_bwd(const stg_model_desc *d, const float *params, const float *buffers, const float *x, int64_t x_sn,
                   int64_t x_sc, int64_t x_st, int64_t x_sv, const float *adj, int64_t a_sn, const int32_t *num_peds,
                   int N, int V, const float *dy, const float *ws, float *scratch, float *grad_params, float *dx,
                   void **events, int n_events, void *stream) {
-    return model_bwd_impl(d, params, buffers, x, x_sn, x_sc, x_st, x_sv, adj, a_sn, num_peds, N, V, dy, nullptr, nullptr,
-                          nullptr, nullptr, ws, scratch, grad_params, dx, events, n_events, stream, nullptr);
+    const ModelCall c{d, params, buffers, {x, x_sn, x_sc, x_st, x_sv, adj, a_sn, num_peds, N, V}, stream};
+    return run_bwd(c, BwdBuffers{dy, nullptr, nullptr, nullptr, nullptr, ws, scratch, grad_params, dx, events, n_events});
 }
 
 int stg_model_bwd_nll(const stg_model_desc *d, const float *params, const float *buffers, const float *x, int64_t x_sn,
                       int64_t x_sc, int64_t x_st, int64_t x_sv, const float *adj, int64_t a_sn, const int32_t *num_peds,
                       int N, int V, const float *y, const float *target, const float *weights, float *losses,
                       const float *ws, float *scratch, float *grad_params, void **events, int n_events, void *stream) {
-    if (!target || !losses || (N > 0 && !y)) return stg::fail(STG_EINVAL, "stg_model_bwd_nll: null pointer");
-    return model_bwd_impl(d, params, buffers, x, x_sn, x_sc, x_st, x_sv, adj, a_sn, num_peds, N, V, y, target, weights,
-                          losses, nullptr, ws, scratch, grad_params, nullptr, events, n_events, stream, nullptr);
+    if (!target || !losses || (N > 0 && !y)) return fail(STG_EINVAL, "stg_model_bwd_nll: null pointer");
+    const ModelCall c{d, params, buffers, {x, x_sn, x_sc, x_st, x_sv, adj, a_sn, num_peds, N, V}, stream};
+    return run_bwd(c, BwdBuffers{y, target, weights, losses, nullptr, ws, scratch, grad_params, nullptr, events, n_events});
 }
 
 int stg_model_bwd_step(const stg_model_desc *d, const float *params, const float *buffers, const float *x, int64_t x_sn,
@@ -687,12 +674,11 @@ int stg_model_bwd_step(const stg_model_desc *d, const float *params, const float
                        int N, int V, const float *y, const float *target, const float *weights, float *losses,
                        const float *ws, float *scratch, float *grad_params, const stg_step_tail *tail, void **events,
                        int n_events, void *stream) {
-    if (!target || !losses || (N > 0 && !y)) return stg::fail(STG_EINVAL, "stg_model_bwd_step: null pointer");
-    if (!tail || !tail->params || (tail->stats && !tail->buffers) || tail->n_bn < 0 || tail->n_bn > 3 * STG_MAX_BLOCKS)
-        return stg::fail(STG_EINVAL, "stg_model_bwd_step: bad tail");
+    if (!target || !losses || (N > 0 && !y)) return fail(STG_EINVAL, "stg_model_bwd_step: null pointer");
+    if (!tail_ok(tail)) return fail(STG_EINVAL, "stg_model_bwd_step: bad tail");
     if (N == 0) return STG_EUNSUPPORTED;               // (an empty batch has no backward launch to ride on)
-    return model_bwd_impl(d, params, buffers, x, x_sn, x_sc, x_st, x_sv, adj, a_sn, num_peds, N, V, y, target, weights,
-                          losses, tail, ws, scratch, grad_params, nullptr, events, n_events, stream, nullptr);
+    const ModelCall c{d, params, buffers, {x, x_sn, x_sc, x_st, x_sv, adj, a_sn, num_peds, N, V}, stream};
+    return run_bwd(c, BwdBuffers{y, target, weights, losses, tail, ws, scratch, grad_params, nullptr, events, n_events});
 }
 
 int stg_model_step(const stg_model_desc *d, const float *params, const float *buffers, const float *x, int64_t x_sn,
@@ -701,25 +687,21 @@ int stg_model_step(const stg_model_desc *d, const float *params, const float *bu
                    const float *weights, float *losses, float *bwd_scratch, float *grad_params,
                    const stg_step_tail *tail, void **fwd_events, int n_fwd_events, void **bwd_events,
                    int n_bwd_events, void *stream) {
-    using namespace stg;
     if (!target || !losses || !y || !ws) return fail(STG_EINVAL, "stg_model_step: null pointer");
-    if (!tail || !tail->params || (tail->stats && !tail->buffers) || tail->n_bn < 0 || tail->n_bn > 3 * STG_MAX_BLOCKS)
-        return fail(STG_EINVAL, "stg_model_step: bad tail");
-    ModelLayout L;
-    const int rc = make_layout(d, &L);
+    if (!tail_ok(tail)) return fail(STG_EINVAL, "stg_model_step: bad tail");
+    StepPlan p;
+    const int rc = plan_sized("stg_model_step: bad sizes", d, num_peds, N, V, 0, &p);
     if (rc != STG_OK) return rc;
-    STG_REQUIRE(N >= 0 && V > 0, STG_EINVAL, "stg_model_step: bad sizes N=%d V=%d", N, V);
     // (where stg_model_bwd_step has no form, decided before the forward launches anything)
-    if (N == 0 || (L.flags & STG_OPT_SPLIT_BF16) || L.n_txp == 0) return STG_EUNSUPPORTED;
+    if (N == 0 || (p.lay.flags & STG_OPT_SPLIT_BF16) || p.lay.n_txp == 0) return STG_EUNSUPPORTED;
     STG_REQUIRE(grad_params && bwd_scratch, STG_EINVAL, "stg_model_step: null pointer");
+    const ModelCall c{d, params, buffers, {x, x_sn, x_sc, x_st, x_sv, adj, a_sn, num_peds, N, V}, stream};
     TxpFwdArgs f{};
-    const bool one = step_one_launch(L, choose_path(L, N, V), num_peds, N, V);
-    const int rcf = model_fwd_impl(d, params, buffers, x, x_sn, x_sc, x_st, x_sv, adj, a_sn, num_peds, N, V, y, ws, stats,
-                                   fwd_scratch, fwd_events, n_fwd_events, stream, one ? &f : nullptr);
+    TxpFwdArgs *both = p.one_launch ? &f : nullptr;     // the forward's scene launch, run with the backward's as one
+    const int rcf = model_fwd_impl(c, FwdBuffers{y, ws, stats, fwd_scratch, fwd_events, n_fwd_events}, p, both);
     if (rcf != STG_OK) return rcf;
-    return model_bwd_impl(d, params, buffers, x, x_sn, x_sc, x_st, x_sv, adj, a_sn, num_peds, N, V, y, target, weights,
-                          losses, tail, ws, bwd_scratch, grad_params, nullptr, bwd_events, n_bwd_events, stream,
-                          one ? &f : nullptr);
+    return model_bwd_impl(c, BwdBuffers{y, target, weights, losses, tail, ws, bwd_scratch, grad_params, nullptr, bwd_events,
+                                        n_bwd_events}, p, both);
 }
 
 }  // extern "C"

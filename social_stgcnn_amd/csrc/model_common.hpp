@@ -246,11 +246,15 @@ constexpr int kOrderMaxV = 1023;
 // floats reserved in the scratch buffers for the scene order: N int32 + the V+2 tier offsets key_start[]
 // (+ the sorted pedestrian counts behind them: N more)
 __host__ __device__ inline int64_t order_floats(int N, int V) { return ((int64_t)2 * N + V + 2 + 3) & ~(int64_t)3; }
-// Fills order[0..N) with the scene indices sorted by clamp(num_peds[n], 0, V) descending (stable) on `st`;
+// ... and the three parts of such a block at `base`: the only place their offsets are written
+struct SceneOrder {
+    int32_t *order, *key_start, *order_peds;
+};
+inline SceneOrder scene_order_at(int32_t *base, int N, int V) { return SceneOrder{base, base + N, base + N + V + 2}; }
+// Fills o.order[0..N) with the scene indices sorted by clamp(num_peds[n], 0, V) descending (stable) on `st`;
 // returns false (order untouched) when the batch is outside the kernel's limits or num_peds is null.
-// order_peds (optional): order_peds[i] = clamp(num_peds[order[i]], 0, V), the sorted counts themselves.
-bool launch_scene_order(const int32_t *num_peds, int N, int V, int32_t *order, int32_t *key_start, hipStream_t st,
-                        int32_t *order_peds = nullptr);
+// o.order_peds (optional): order_peds[i] = clamp(num_peds[order[i]], 0, V), the sorted counts themselves.
+bool launch_scene_order(const int32_t *num_peds, int N, int V, const SceneOrder &o, hipStream_t st);
 // whether launch_scene_order sorts such a batch at all (the training forward leaves its order in the workspace's batch
 // tail and the backward picks it up instead of sorting again: both sides decide with this)
 inline bool scene_order_applies(const int32_t *num_peds, int N, int V) {
@@ -258,7 +262,7 @@ inline bool scene_order_applies(const int32_t *num_peds, int N, int V) {
 }
 
 // stgcn_agg.hip: ax = x A ([cin][T][V_n]) and cs = colsum(A) ([T][V_n]) of every scene -- the one read of A in a
-// step -- written to out + n * out_stride + ax_off / cs_off.
+// step -- written to out.ptr + n * out.stride + out.ax_off / out.cs_off.
 // prep (optional): the launch also prepares the A operands of the backward's exact-bf16 input-gradient GEMMs
 // (txp_conv_bf16.hpp) into `wp`, [n_layers][cv::kWpDwords], from the conv weights at params + w_off[l].
 struct AggPrep {
@@ -275,8 +279,11 @@ struct AggPrep {
 // scenes the sorting workgroup outlasts the aggregation itself (measured at 2048: 30 us against 21) and the 16-wave
 // scene_order_kernel as a launch of its own is the cheaper way (5 us + a kernel boundary)
 inline bool agg_sorts(const int32_t *num_peds, int N, int V) { return scene_order_applies(num_peds, N, V) && N <= 1024; }
-int launch_stgcn_agg(int cin, const float *x, int64_t x_sn, int64_t x_sc, int64_t x_st, int64_t x_sv, const float *adj,
-                     int64_t a_sn, const int32_t *num_peds, int N, int V, float *out, int64_t out_stride, int64_t ax_off,
-                     int64_t cs_off, hipStream_t st, const AggPrep *prep = nullptr);
+struct AggOut {
+    float *ptr;
+    int64_t stride, ax_off, cs_off;
+};
+struct SceneInput;     // step_plan.hpp: the batch of a call
+int launch_stgcn_agg(int cin, const SceneInput &in, const AggOut &out, hipStream_t st, const AggPrep *prep = nullptr);
 
 }  // namespace stg

@@ -213,96 +213,75 @@ static size_t fwd_lds_bytes(int V, int waves) {
     return (size_t)(plane + reg + waves * 16 + 16) * sizeof(float);
 }
 
-// stg_model_fwd.  `defer` (stg_model_step, step_one_launch() holds): the scene launch is left to the backward's -- its
+// stg_model_fwd.  `defer` (stg_model_step, the plan's one_launch holds): the scene launch is left to the backward's -- its
 // arguments go to *defer, and the forward scene kernel's event interval is recorded empty.
-int model_fwd_impl(const stg_model_desc *d, const float *params, const float *buffers, const float *x, int64_t x_sn,
-                   int64_t x_sc, int64_t x_st, int64_t x_sv, const float *adj, int64_t a_sn, const int32_t *num_peds,
-                   int N, int V, float *y, float *ws, float *stats, float *scratch, void **events, int n_events,
-                   void *stream, TxpFwdArgs *defer) {
-    FwdArgs a{};
-    const int rc = make_layout(d, &a.lay);
-    if (rc != STG_OK) return rc;
-    STG_REQUIRE(N >= 0 && V > 0, STG_EINVAL, "stg_model_fwd: bad sizes N=%d V=%d", N, V);
+int model_fwd_impl(const ModelCall &c, const FwdBuffers &b, const StepPlan &p, TxpFwdArgs *defer) {
+    const SceneInput &in = c.in;
+    const int N = in.N, V = in.V;
     if (N == 0) return STG_OK;                        // empty batch: nothing to read or write
-    STG_REQUIRE(params && buffers && x && adj && y, STG_EINVAL, "stg_model_fwd: null pointer");
-    STG_REQUIRE(scratch && (reinterpret_cast<uintptr_t>(scratch) & 15) == 0, STG_EINVAL,
+    STG_REQUIRE(c.params && c.buffers && in.x && in.adj && b.y, STG_EINVAL, "stg_model_fwd: null pointer");
+    STG_REQUIRE(b.scratch && aligned(b.scratch, 16), STG_EINVAL,
                 "stg_model_fwd: scratch (stg_model_fwd_scratch_floats floats, 16-byte aligned) is missing");
-    STG_REQUIRE(!ws || (reinterpret_cast<uintptr_t>(ws) & 15) == 0, STG_EINVAL, "stg_model_fwd: ws must be 16-byte aligned");
-    const ModelLayout &L = a.lay;
-    a.params = params; a.buffers = buffers; a.x = x;
-    a.x_sn = x_sn; a.x_sc = x_sc; a.x_st = x_st; a.x_sv = x_sv;
-    a.adj = adj; a.a_sn = a_sn; a.num_peds = num_peds; a.N = N; a.V = V;
-    a.y = y; a.ws = ws; a.ws_stride = ws_floats_per_scene(L, V); a.stats = stats;
-    const StepPath path = choose_path(L, N, V);
-    const FwdCarve fc = fwd_carve(L, path, N, V);
-    const WsTail wt = ws_tail(L, path, N, V);
-    float *ws_end = ws ? ws + wt.base : nullptr;       // (the batch tail of the workspace)
-    STG_REQUIRE(!defer || step_one_launch(L, path, num_peds, N, V), STG_EINVAL,
-                "stg_model_fwd: a scene launch deferred outside the one-launch step");
+    STG_REQUIRE(aligned(b.ws, 16), STG_EINVAL, "stg_model_fwd: ws must be 16-byte aligned");
+    const ModelLayout &L = p.lay;
+    const StepPath &path = p.path;
+    float *ws_end = b.ws ? b.ws + p.tail.base : nullptr;       // (the batch tail of the workspace)
+    STG_REQUIRE(!defer || p.one_launch, STG_EINVAL, "stg_model_fwd: a scene launch deferred outside the one-launch step");
     STG_REQUIRE(path.scene() || !(L.flags & STG_OPT_BF16_STORE), STG_EUNSUPPORTED,
                 "stg_model_fwd: bf16 storage (STG_OPT_BF16_STORE) is built for the wave-per-scene kernels only "
                 "(one st_gcn block, input_feat 2, V <= 68, no STG_OPT_WG_PATH)");
-    hipStream_t st = as_stream(stream);
-    EventList evl{events, events ? n_events : 0, 0, st};
+    hipStream_t st = as_stream(c.stream);
+    EventList evl{b.events, b.events ? b.n_events : 0, 0, st};
     evl.mark();
     // K0: x A and colsum(A) of the first block -- the only read of A.  Training: straight into the saved arrays of
     // the workspace (the backward needs exactly these); inference: into the scratch buffer.
     const BlockLayout &b0 = L.blk[0];
-    if (ws) {
-        a.agg = ws; a.agg_stride = a.ws_stride;
-        a.agg_ax = L.ws_hdr_floats + (int64_t)b0.ws_ax * V;
-        a.agg_cs = L.ws_hdr_floats + (int64_t)b0.ws_cs * V;
-    } else {
-        a.agg = scratch + fc.agg; a.agg_stride = (int64_t)(b0.cin + 1) * Cfg::T * V;
-        a.agg_ax = 0;
-        a.agg_cs = (int64_t)b0.cin * Cfg::T * V;
-    }
-    a.debug_skip = diag_env("STG_DEBUG_SKIP", 0);
+    const AggOut agg = b.ws ? AggOut{b.ws, p.ws_stride, L.ws_hdr_floats + (int64_t)b0.ws_ax * V,
+                                     L.ws_hdr_floats + (int64_t)b0.ws_cs * V}
+                            : AggOut{b.scratch + p.fwd.agg, (int64_t)(b0.cin + 1) * Cfg::T * V, 0, (int64_t)b0.cin * Cfg::T * V};
+    // what the argument structs of both kernel families take from the call, the plan and the aggregation
+    const auto fill = [&](auto &a) {
+        set_input(a, c);
+        a.lay = L; a.buffers = c.buffers; a.ws_stride = p.ws_stride; a.y = b.y; a.ws = b.ws; a.stats = b.stats;
+        a.agg = agg.ptr; a.agg_stride = agg.stride; a.agg_ax = agg.ax_off; a.agg_cs = agg.cs_off;
+        a.debug_skip = diag_env("STG_DEBUG_SKIP", 0);
+    };
     // the scene order of a ragged batch: training on a scene path leaves it in the workspace's batch tail, where the
     // backward finds it (tail_has_order) -- no second sort
-    int32_t *order = reinterpret_cast<int32_t *>(ws_end && path.scene() ? ws_end + wt.order : scratch + fc.order);
-    bool sorted_in_agg = false;
-    {
-        // training on the wave-per-scene path: the launch also prepares the backward's exact-bf16 A operands into the
-        // batch tail of the workspace (stg_model_ws_tail_floats behind the N per-scene blocks)
-        AggPrep prep{};
-        prep.params = params;
-        prep.n_layers = L.L + 1;
-        for (int l = 0; l <= L.L; ++l) prep.w_off[l] = l < L.L ? L.txp_w[l] : L.out_w;
-        if (ws_end && wt.wp >= 0) prep.wp = reinterpret_cast<unsigned *>(ws_end + wt.wp);
-        // ... and the forward's own (this launch's successor reads them from the scratch buffer)
-        if (fc.wp_fwd >= 0) prep.wp_fwd = reinterpret_cast<unsigned *>(scratch + fc.wp_fwd);
-        // ... and, for a ragged batch on the wave-per-scene path, the scene order: one more workgroup of this launch
-        sorted_in_agg = path.scene() && agg_sorts(num_peds, N, V);
-        if (sorted_in_agg) { prep.order = order; prep.key_start = order + N; prep.order_peds = order + N + V + 2; }
-        const int rca = launch_stgcn_agg(b0.cin, x, x_sn, x_sc, x_st, x_sv, adj, a_sn, num_peds, N, V,
-                                         const_cast<float *>(a.agg), a.agg_stride, a.agg_ax, a.agg_cs, st,
-                                         (prep.wp || prep.wp_fwd || prep.order) ? &prep : nullptr);
-        if (rca != STG_OK) return rca;
-    }
+    const SceneOrder so = scene_order_at(
+        reinterpret_cast<int32_t *>(ws_end && path.scene() ? ws_end + p.tail.order : b.scratch + p.fwd.order), N, V);
+    // training on the wave-per-scene path: the launch also prepares the backward's exact-bf16 A operands into the
+    // batch tail of the workspace (stg_model_ws_tail_floats behind the N per-scene blocks)
+    AggPrep prep{};
+    prep.params = c.params;
+    prep.n_layers = L.L + 1;
+    for (int l = 0; l <= L.L; ++l) prep.w_off[l] = l < L.L ? L.txp_w[l] : L.out_w;
+    if (ws_end && p.tail.wp >= 0) prep.wp = reinterpret_cast<unsigned *>(ws_end + p.tail.wp);
+    // ... and the forward's own (this launch's successor reads them from the scratch buffer)
+    if (p.fwd.wp_fwd >= 0) prep.wp_fwd = reinterpret_cast<unsigned *>(b.scratch + p.fwd.wp_fwd);
+    // ... and, for a ragged batch on the wave-per-scene path, the scene order: one more workgroup of this launch
+    const bool sorted_in_agg = path.scene() && agg_sorts(in.num_peds, N, V);
+    if (sorted_in_agg) { prep.order = so.order; prep.key_start = so.key_start; prep.order_peds = so.order_peds; }
+    const int rca = launch_stgcn_agg(b0.cin, in, agg, st, (prep.wp || prep.wp_fwd || prep.order) ? &prep : nullptr);
+    if (rca != STG_OK) return rca;
     evl.mark();
     if (path.scene()) {
         // K1: ONE wave-per-scene kernel for the whole model: st_gcn block (VALU) + TXP-CNN (MFMA), the a_0 plane never
         // leaves LDS.  Ragged batch: sorted scene list, walked boustrophedon.
         bool sorted = sorted_in_agg;                   // (sorted by a workgroup of the aggregation launch above ...)
         if (!sorted) {                                  // (... or, for a large batch, by the 16-wave kernel)
-            sorted = launch_scene_order(num_peds, N, V, order, order + N, st, order + N + V + 2);
-            if (!sorted && scene_order_applies(num_peds, N, V)) return hip_fail(hipErrorLaunchFailure, "stg_model_fwd: scene_order launch");
+            sorted = launch_scene_order(in.num_peds, N, V, so, st);
+            if (!sorted && scene_order_applies(in.num_peds, N, V)) return hip_fail(hipErrorLaunchFailure, "stg_model_fwd: scene_order launch");
         }
         TxpFwdArgs t{};
-        t.lay = L; t.params = params; t.buffers = buffers; t.num_peds = num_peds; t.N = N; t.V = V;
-        t.x = x; t.x_sn = x_sn; t.x_sc = x_sc; t.x_st = x_st; t.x_sv = x_sv;
-        t.adj = adj; t.a_sn = a_sn;
-        t.agg = a.agg; t.agg_stride = a.agg_stride; t.agg_ax = a.agg_ax; t.agg_cs = a.agg_cs;
-        t.y = y; t.ws = ws; t.ws_stride = a.ws_stride; t.stats = stats;
-        if (fc.wp_fwd >= 0) t.wpf = reinterpret_cast<const unsigned *>(scratch + fc.wp_fwd);
-        if (fc.stamps >= 0) t.stamps = reinterpret_cast<unsigned long long *>(scratch + fc.stamps);
+        fill(t);
+        if (p.fwd.wp_fwd >= 0) t.wpf = reinterpret_cast<const unsigned *>(b.scratch + p.fwd.wp_fwd);
+        if (p.fwd.stamps >= 0) t.stamps = reinterpret_cast<unsigned long long *>(b.scratch + p.fwd.stamps);
         const int serp = diag_env("STG_WALK", 1);
         // one launch for the whole (sorted) batch: V-tiers in separate launches were measured slower -- the few
         // large scenes of a real batch take one wave tens of microseconds each and need the small ones to overlap
-        t.tier = SceneTier{sorted ? order : nullptr, sorted ? order + N : nullptr, -1, V, serp};
+        t.tier = SceneTier{sorted ? so.order : nullptr, sorted ? so.key_start : nullptr, -1, V, serp};
         t.Vl = V;
-        t.debug_skip = a.debug_skip;
         t.stagger = diag_env("STG_STAGGER_F", 0);
         if (defer) *defer = t;
         const int rcw = defer ? STG_OK : launch_scene_fwd(path, t, st);
@@ -310,6 +289,8 @@ int model_fwd_impl(const stg_model_desc *d, const float *params, const float *bu
         evl.finish();
         return rcw;
     }
+    FwdArgs a{};
+    fill(a);
     int waves = V <= 12 ? 1 : (V <= 40 ? 2 : (V <= 80 ? 4 : 8));
     if (path.wg_waves) waves = path.wg_waves;
     const size_t lds = fwd_lds_bytes(V, waves);
@@ -318,10 +299,10 @@ int model_fwd_impl(const stg_model_desc *d, const float *params, const float *bu
     const Launch lc{"stg_model_fwd", dim3((unsigned)N), dim3(waves * 64), lds, st};
     int rck;
     switch (waves) {
-        case 1: rck = launch(lc, model_fwd_kernel<1>, a, params, buffers); break;
-        case 2: rck = launch(lc, model_fwd_kernel<2>, a, params, buffers); break;
-        case 4: rck = launch(lc, model_fwd_kernel<4>, a, params, buffers); break;
-        default: rck = launch(lc, model_fwd_kernel<8>, a, params, buffers); break;
+        case 1: rck = launch(lc, model_fwd_kernel<1>, a, c.params, c.buffers); break;
+        case 2: rck = launch(lc, model_fwd_kernel<2>, a, c.params, c.buffers); break;
+        case 4: rck = launch(lc, model_fwd_kernel<4>, a, c.params, c.buffers); break;
+        default: rck = launch(lc, model_fwd_kernel<8>, a, c.params, c.buffers); break;
     }
     if (rck != STG_OK) return rck;
     evl.mark();
@@ -335,6 +316,9 @@ extern "C" int stg_model_fwd(const stg_model_desc *d, const float *params, const
                              int64_t x_sn, int64_t x_sc, int64_t x_st, int64_t x_sv, const float *adj,
                              int64_t a_sn, const int32_t *num_peds, int N, int V, float *y, float *ws,
                              float *stats, float *scratch, void **events, int n_events, void *stream) {
-    return stg::model_fwd_impl(d, params, buffers, x, x_sn, x_sc, x_st, x_sv, adj, a_sn, num_peds, N, V, y, ws, stats,
-                               scratch, events, n_events, stream, nullptr);
+    stg::StepPlan p;
+    const int rc = stg::plan_sized("stg_model_fwd: bad sizes", d, num_peds, N, V, 0, &p);
+    if (rc != STG_OK) return rc;
+    const stg::ModelCall c{d, params, buffers, {x, x_sn, x_sc, x_st, x_sv, adj, a_sn, num_peds, N, V}, stream};
+    return stg::model_fwd_impl(c, stg::FwdBuffers{y, ws, stats, scratch, events, n_events}, p, nullptr);
 }

@@ -57,7 +57,7 @@ bool is_canonical(const ModelLayout &L) {
 // small batch into finer teams themselves (team_geom) and keep every batch they fit.
 constexpr int kSmallBatch = 288;      // measured: 256 scenes 1.89 (workgroup kernels) vs 1.79 M/s (a wave per scene), 320 scenes 2.10 vs 2.19
 
-StepPath choose_path(const ModelLayout &L, int N, int V) {
+static StepPath choose_path(const ModelLayout &L, int N, int V) {
     StepPath p{StepPath::Workgroup, L.wg_waves, txp_fwd_x6_fits(L, V), txp_bwd_x6_fits(L, V)};
     // a wave (or a team of waves) per scene: the whole model with one st_gcn block on the two input features
     if (L.n_txp < 1 || L.n_blocks != 1 || L.blk[0].cin != Cfg::CIN0 || (L.flags & STG_OPT_WG_PATH)) return p;
@@ -72,7 +72,7 @@ StepPath choose_path(const ModelLayout &L, int N, int V) {
     return p;
 }
 
-FwdCarve fwd_carve(const ModelLayout &L, const StepPath &path, int N, int V) {
+static FwdCarve fwd_carve(const ModelLayout &L, const StepPath &path, int N, int V) {
     const bool stamps = diag_env("STG_STAMPS", 0) != 0;
     FwdCarve c;
     c.agg = 0;
@@ -84,7 +84,7 @@ FwdCarve fwd_carve(const ModelLayout &L, const StepPath &path, int N, int V) {
     return c;
 }
 
-WsTail ws_tail(const ModelLayout &L, const StepPath &path, int N, int V) {
+static WsTail ws_tail(const ModelLayout &L, const StepPath &path, int N, int V) {
     WsTail t;
     t.base = (int64_t)N * ws_floats_per_scene(L, V);
     t.wp = path.scene() && path.bwd_x6 ? 0 : -1;
@@ -100,11 +100,30 @@ int launch_scene_bwd(const StepPath &path, const TxpBwdArgs &a, hipStream_t st) 
     return path.bwd_x6 ? launch_txp_bwd_x6(a, st) : launch_txp_bwd_wave(a, st);
 }
 
-bool step_one_launch(const ModelLayout &L, const StepPath &path, const int32_t *num_peds, int N, int V) {
+static bool step_one_launch(const ModelLayout &L, const StepPath &path, const int32_t *num_peds, int N, int V) {
     return path.kind == StepPath::SceneX6 && path.fwd_x6 && path.bwd_x6 && !(L.flags & STG_OPT_SEPARATE_FB) &&
            txp_step_x6_fits(L, num_peds, N, V);
 }
 int launch_scene_step(const TxpFwdArgs &f, const TxpBwdArgs &b, hipStream_t st) { return launch_txp_step_x6(f, b, st); }
+
+int plan_step(const stg_model_desc *d, const int32_t *num_peds, int N, int V, StepPlan *p) {
+    const int rc = make_layout(d, &p->lay);
+    p->sized = rc == STG_OK && N >= 0 && V > 0;
+    if (!p->sized) return rc;
+    const ModelLayout &L = p->lay;
+    p->path = choose_path(L, N, V);
+    p->ws_stride = ws_floats_per_scene(L, V);
+    p->tail = ws_tail(L, p->path, N, V);
+    p->fwd = fwd_carve(L, p->path, N, V);
+    p->one_launch = step_one_launch(L, p->path, num_peds, N, V);
+    return STG_OK;
+}
+int plan_sized(const char *what, const stg_model_desc *d, const int32_t *num_peds, int N, int V, int min_N, StepPlan *p) {
+    const int rc = plan_step(d, num_peds, N, V, p);
+    if (rc != STG_OK) return rc;
+    STG_REQUIRE(p->sized && N >= min_N, STG_EINVAL, "%s N=%d V=%d", what, N, V);
+    return STG_OK;
+}
 
 __global__ __launch_bounds__(1024) void scene_order_kernel(const int32_t *__restrict__ num_peds, int N, int V,
                                                            int32_t *__restrict__ order,
@@ -115,15 +134,14 @@ __global__ __launch_bounds__(1024) void scene_order_kernel(const int32_t *__rest
     scene_order_body<16>(num_peds, N, V, order, key_start, order_peds, hist, wave_tot);
 }
 
-bool launch_scene_order(const int32_t *num_peds, int N, int V, int32_t *order, int32_t *key_start, hipStream_t st,
-                        int32_t *order_peds) {
-    if (!order || !scene_order_applies(num_peds, N, V)) return false;
+bool launch_scene_order(const int32_t *num_peds, int N, int V, const SceneOrder &o, hipStream_t st) {
+    if (!o.order || !scene_order_applies(num_peds, N, V)) return false;
     const size_t lds = (size_t)(V + 1) * 16 * sizeof(int);
     if (lds > 48 * 1024 &&
         hipFuncSetAttribute(reinterpret_cast<const void *>(&scene_order_kernel),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return false;
-    hipLaunchKernelGGL(scene_order_kernel, dim3(1), dim3(1024), lds, st, num_peds, N, V, order, key_start, order_peds);
+    hipLaunchKernelGGL(scene_order_kernel, dim3(1), dim3(1024), lds, st, num_peds, N, V, o.order, o.key_start, o.order_peds);
     return hipGetLastError() == hipSuccess;
 }
 
@@ -131,16 +149,14 @@ bool launch_scene_order(const int32_t *num_peds, int N, int V, int32_t *order, i
 
 extern "C" {
 
-int64_t stg_model_param_count(const stg_model_desc *d) {
+static int64_t layout_query(const stg_model_desc *d, int32_t stg::ModelLayout::*count) {
     stg::ModelLayout l;
     const int rc = stg::make_layout(d, &l);
-    return rc == STG_OK ? l.n_params : rc;
+    return rc == STG_OK ? l.*count : rc;
 }
-int64_t stg_model_buffer_count(const stg_model_desc *d) {
-    stg::ModelLayout l;
-    const int rc = stg::make_layout(d, &l);
-    return rc == STG_OK ? l.n_buffers : rc;
-}
+int64_t stg_model_param_count(const stg_model_desc *d) { return layout_query(d, &stg::ModelLayout::n_params); }
+int64_t stg_model_buffer_count(const stg_model_desc *d) { return layout_query(d, &stg::ModelLayout::n_buffers); }
+int64_t stg_model_stat_floats(const stg_model_desc *d) { return layout_query(d, &stg::ModelLayout::stat_floats); }
 int64_t stg_model_ws_floats(const stg_model_desc *d, int V) {
     stg::ModelLayout l;
     const int rc = stg::make_layout(d, &l);
@@ -149,26 +165,19 @@ int64_t stg_model_ws_floats(const stg_model_desc *d, int V) {
     return stg::ws_floats_per_scene(l, V);
 }
 int64_t stg_model_ws_tail_floats(const stg_model_desc *d, int N, int V) {
-    stg::ModelLayout l;
-    const int rc = stg::make_layout(d, &l);
-    if (rc != STG_OK) return rc;
-    if (N < 0 || V <= 0) return stg::fail(STG_EINVAL, "stg_model_ws_tail_floats: N=%d V=%d", N, V);
-    return stg::ws_tail(l, stg::choose_path(l, N, V), N, V).total;
+    stg::StepPlan p;
+    const int rc = stg::plan_sized("stg_model_ws_tail_floats:", d, nullptr, N, V, 0, &p);
+    return rc == STG_OK ? p.tail.total : rc;
 }
 int64_t stg_model_fwd_scratch_floats(const stg_model_desc *d, int N, int V) {
-    stg::ModelLayout l;
-    const int rc = stg::make_layout(d, &l);
-    if (rc != STG_OK) return rc;
-    if (N < 0 || V <= 0) return stg::fail(STG_EINVAL, "stg_model_fwd_scratch_floats: N=%d V=%d", N, V);
-    return stg::fwd_carve(l, stg::choose_path(l, N, V), N, V).total;
+    stg::StepPlan p;
+    const int rc = stg::plan_sized("stg_model_fwd_scratch_floats:", d, nullptr, N, V, 0, &p);
+    return rc == STG_OK ? p.fwd.total : rc;
 }
 int64_t stg_model_fwd_stamps_offset(const stg_model_desc *d, int N, int V) {
-    stg::ModelLayout l;
-    const int rc = stg::make_layout(d, &l);
-    if (rc != STG_OK) return rc;
-    if (N < 0 || V <= 0) return stg::fail(STG_EINVAL, "stg_model_fwd_stamps_offset: N=%d V=%d", N, V);
-    const int64_t off = stg::fwd_carve(l, stg::choose_path(l, N, V), N, V).stamps;
-    return off >= 0 ? off : STG_EUNSUPPORTED;
+    stg::StepPlan p;
+    const int rc = stg::plan_sized("stg_model_fwd_stamps_offset:", d, nullptr, N, V, 0, &p);
+    return rc != STG_OK ? rc : p.fwd.stamps >= 0 ? p.fwd.stamps : STG_EUNSUPPORTED;
 }
 int stg_scene_order(const int32_t *num_peds, int N, int V, int32_t *order, int32_t *key_start, void *stream) {
     STG_REQUIRE(N >= 0 && V > 0, STG_EINVAL, "stg_scene_order: bad sizes N=%d V=%d", N, V);
@@ -178,15 +187,9 @@ int stg_scene_order(const int32_t *num_peds, int N, int V, int32_t *order, int32
     STG_REQUIRE(N <= stg::kOrderMaxN && V <= stg::kOrderMaxV, STG_EUNSUPPORTED,
                 "stg_scene_order: N=%d V=%d outside the single-workgroup sort (N <= %d, V <= %d)", N, V,
                 stg::kOrderMaxN, stg::kOrderMaxV);
-    STG_REQUIRE(stg::launch_scene_order(num_peds, N, V, order, key_start, stg::as_stream(stream)), STG_EINVAL,
-                "stg_scene_order: launch failed");
+    STG_REQUIRE(stg::launch_scene_order(num_peds, N, V, stg::SceneOrder{order, key_start, nullptr}, stg::as_stream(stream)),
+                STG_EINVAL, "stg_scene_order: launch failed");
     return STG_OK;
-}
-
-int64_t stg_model_stat_floats(const stg_model_desc *d) {
-    stg::ModelLayout l;
-    const int rc = stg::make_layout(d, &l);
-    return rc == STG_OK ? l.stat_floats : rc;
 }
 
 }  // extern "C"

@@ -14,6 +14,7 @@
 #include "model_common.hpp"
 #include "txp_conv_bf16.hpp"
 #include "scene_order.hpp"
+#include "step_plan.hpp"
 
 namespace stg {
 
@@ -241,10 +242,9 @@ __global__ __launch_bounds__(256) void stgcn_agg_q32_kernel(const float *__restr
 
 }  // namespace
 
-// out + n * out_stride + ax_off : ax [cin][T][V_n];  out + n * out_stride + cs_off : cs [T][V_n]
-int launch_stgcn_agg(int cin, const float *x, int64_t x_sn, int64_t x_sc, int64_t x_st, int64_t x_sv, const float *adj,
-                     int64_t a_sn, const int32_t *num_peds, int N, int V, float *out, int64_t out_stride, int64_t ax_off,
-                     int64_t cs_off, hipStream_t st, const AggPrep *prep_in) {
+// out.ptr + n * out.stride + out.ax_off : ax [cin][T][V_n];  out.ptr + n * out.stride + out.cs_off : cs [T][V_n]
+int launch_stgcn_agg(int cin, const SceneInput &in, const AggOut &out, hipStream_t st, const AggPrep *prep_in) {
+    const int N = in.N, V = in.V;
     if (N == 0) return STG_OK;
     AggPrep prep{};
     if (prep_in) prep = *prep_in;
@@ -254,23 +254,22 @@ int launch_stgcn_agg(int cin, const float *x, int64_t x_sn, int64_t x_sc, int64_
     STG_REQUIRE(lds <= (size_t)kLdsBytes, STG_ELDS, "stgcn_agg: V=%d needs %zu bytes of LDS", V, lds);
     // 16-byte loads need 16-byte aligned rows: V a multiple of 4 and a 16-byte aligned base / batch stride
     const int min_strips = diag_env("STG_AGG_VEC_STRIPS", 256);
-    const bool vec = (V % 4 == 0) && ((reinterpret_cast<uintptr_t>(adj) & 15) == 0) && (a_sn % 4 == 0) &&
-                     T * (V / 4) >= min_strips;
-    const bool can_q32 = ((reinterpret_cast<uintptr_t>(adj) & 15) == 0) && (a_sn % 4 == 0) &&
-                         ((reinterpret_cast<uintptr_t>(out) & 15) == 0) && (out_stride % 4 == 0) && (ax_off % 4 == 0) &&
-                         (cs_off % 4 == 0);
+    const bool adj16 = aligned(in.adj, 16) && in.a_sn % 4 == 0;
+    const bool vec = V % 4 == 0 && adj16 && T * (V / 4) >= min_strips;
+    const bool can_q32 = adj16 && aligned(out.ptr, 16) && out.stride % 4 == 0 && out.ax_off % 4 == 0 && out.cs_off % 4 == 0;
     // V = 32 with 16-byte aligned rows and outputs: the quarters form
     const bool q32 = V == 32 && can_q32 && !diag_env("STG_AGG_COLS", 0);
     if (q32) {
         const size_t lds32 = lds > (size_t)cin * T * 32 * sizeof(float) ? lds : (size_t)cin * T * 32 * sizeof(float);
         const Launch lc{"stgcn_agg", grid, block, lds32, st, (size_t)kLdsBytes};     // (24 KB at most: the limit is never raised)
-        return launch(lc, cin == Cfg::CIN0 ? stgcn_agg_q32_kernel<Cfg::CIN0> : stgcn_agg_q32_kernel<Cfg::C>, x, x_sn, x_sc, x_st,
-                      x_sv, adj, a_sn, num_peds, N, out, out_stride, ax_off, cs_off, prep);
+        return launch(lc, cin == Cfg::CIN0 ? stgcn_agg_q32_kernel<Cfg::CIN0> : stgcn_agg_q32_kernel<Cfg::C>, in.x, in.x_sn, in.x_sc,
+                      in.x_st, in.x_sv, in.adj, in.a_sn, in.num_peds, N, out.ptr, out.stride, out.ax_off, out.cs_off, prep);
     }
     const Launch lc{"stgcn_agg", grid, block, lds, st, 64 * 1024};
     const auto k = cin == Cfg::CIN0 ? (vec ? stgcn_agg_kernel<Cfg::CIN0, 4> : stgcn_agg_kernel<Cfg::CIN0, 1>)
                                     : (vec ? stgcn_agg_kernel<Cfg::C, 4> : stgcn_agg_kernel<Cfg::C, 1>);
-    return launch(lc, k, x, x_sn, x_sc, x_st, x_sv, adj, a_sn, num_peds, N, V, out, out_stride, ax_off, cs_off, prep);
+    return launch(lc, k, in.x, in.x_sn, in.x_sc, in.x_st, in.x_sv, in.adj, in.a_sn, in.num_peds, N, V, out.ptr, out.stride,
+                  out.ax_off, out.cs_off, prep);
 }
 
 }  // namespace stg
