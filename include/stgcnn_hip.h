@@ -585,6 +585,9 @@ int stg_score_push_streams(const int64_t *det_id, int64_t id_stride, const doubl
                            const int32_t *num_peds, int P, int V, int K, const stg_score_state *state,
                            const float *thr, int Q, const stg_score_out *out, void *stream);
 
+/* Timed predictions scored by TIME (added entry points, the ABI version stays): the structs, limits and
+ * the two entry points are declared in stgcnn_hip_score_time.h, included at the end of this header.                  */
+
 /* ---------------------------------------------------------------------------------------------
  * N9  unlabelled detections -> track ids, the front end of the live pushes (added entry points, the ABI
  *     version stays).  A per-stream tracker with constant-velocity prediction and gated, globally greedy
@@ -633,6 +636,9 @@ int stg_associate_streams(int64_t *det_id, int64_t id_stride, const double *det_
 /* Self-test helper: C(16x16) = A(16xK) * B(Kx16) through v_mfma_f32_16x16x4_f32 with the operand
  * maps the TXP-CNN kernels rely on (K multiple of 4).                                           */
 int stg_selftest_mfma(const float *a, const float *b, int K, float *c, void *stream);
+
+/* N8 continued: the time-indexed score (inside the extern "C" block above) */
+#include "stgcnn_hip_score_time.h"
 
 #ifdef __cplusplus
 }

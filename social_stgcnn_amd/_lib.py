@@ -47,6 +47,19 @@ class ScoreOut(ctypes.Structure):
                                                "traj_ade", "traj_fde", "traj_ade_mean", "traj_fde_mean")]
 
 
+class ScoreTimedState(ctypes.Structure):
+    """stg_score_timed_state (include/stgcnn_hip_score_time.h)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("rec_t", "rec_status", "rec_peds", "rec_ids", "rec_mean", "rec_cov",
+                                               "rec_samples", "acc", "acc_mean", "steps", "matched", "err", "d2", "nll",
+                                               "best", "traj_steps", "traj_ade", "traj_fde", "traj_ade_mean",
+                                               "traj_fde_mean", "counters", "totals", "traj_totals")]
+
+
+class ScoreTimedOut(ctypes.Structure):
+    """stg_score_timed_out (include/stgcnn_hip_score_time.h)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("push_totals", "push_traj")]
+
+
 _SIGNATURES = {
     "stg_abi_version": (c_i, []),
     "stg_last_error": (ctypes.c_char_p, []),
@@ -126,6 +139,15 @@ _SIGNATURES = {
     "stg_selftest_mfma": (c_i, [c_f, c_f, c_i, c_f, c_f]),
 }
 EXPORTS = tuple(_SIGNATURES)
+# the entry points of include/stgcnn_hip_score_time.h (the header stgcnn_hip.h includes at its end), bound with the rest
+_SIGNATURES_SCORE_TIME = {
+    # (state and out: ctypes.byref of a ScoreTimedState / ScoreTimedOut, which a void* parameter takes)
+    "stg_score_push_timed": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, ctypes.c_double, c_l, c_l, c_f, c_f, c_l, c_l,
+                                   c_l, c_l, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f, c_f, c_i, c_f, c_f]),
+    "stg_score_push_streams_timed": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, ctypes.c_double, c_l, c_l,
+                                           c_f, c_f, c_l, c_l, c_l, c_l, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f, c_f, c_i,
+                                           c_f, c_f]),
+}
 
 _lib = None
 
@@ -151,7 +173,7 @@ def lib():
                 "--offload-arch=gfx950) or `python -c 'import __graft_entry__ as g; g.build()'`. "
                 "There is no CPU or eager-PyTorch fallback for this path." % (LIB_PATH, CSRC))
         h = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
+        for name, (res, args) in {**_SIGNATURES, **_SIGNATURES_SCORE_TIME}.items():
             fn = getattr(h, name)
             fn.restype = res
             fn.argtypes = args

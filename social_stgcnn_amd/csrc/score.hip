@@ -48,6 +48,7 @@
 // No host synchronisation (the launch is captured into the live predictors' graph), plain C++ stores only, 24 KB of
 // dynamic LDS at the 2,048-detection limit (under the 64 KB the launches name: the kernel's limit is never raised).
 #include "detections.hpp"
+#include "score_fn.hpp"
 
 namespace stg {
 
@@ -68,21 +69,6 @@ struct ScoreArgs {
     int NS, P, V, K, Q, M_max, M2;
     double scale;
 };
-
-// |p - t|, float32 as written
-__device__ __forceinline__ float score_dist(float px, float py, float tx, float ty) {
-#pragma clang fp contract(off)
-    const float dx = px - tx, dy = py - ty;
-    return sqrtf(dx * dx + dy * dy);
-}
-
-// d2 and nll of the offset (dx, dy) under the covariance (cxx, cxy, cyy), float32 as written
-__device__ __forceinline__ void score_gauss(float dx, float dy, float cxx, float cxy, float cyy, float &d2, float &nll) {
-#pragma clang fp contract(off)
-    const float det = cxx * cyy - cxy * cxy;
-    d2 = (cyy * (dx * dx) - 2.f * cxy * dx * dy + cxx * (dy * dy)) / det;
-    nll = 0.5f * d2 + 0.5f * (float)log((double)det) + 1.8378770664093453f;
-}
 
 // the outputs of a stream that has nothing to report
 __device__ __forceinline__ void score_empty(const ScoreArgs &a, int b) {

@@ -1,0 +1,24 @@
+// score_fn: the values of a scored prediction, what the push-indexed and the time-indexed score kernels (score.hip,
+// score_time.hip) share.  Device helpers without state, float32 as written (no fused
+// multiply-add).
+#pragma once
+#include "common.hpp"
+
+namespace stg {
+
+// |p - t|, float32 as written
+__device__ __forceinline__ float score_dist(float px, float py, float tx, float ty) {
+#pragma clang fp contract(off)
+    const float dx = px - tx, dy = py - ty;
+    return sqrtf(dx * dx + dy * dy);
+}
+
+// d2 and nll of the offset (dx, dy) under the covariance (cxx, cxy, cyy), float32 as written
+__device__ __forceinline__ void score_gauss(float dx, float dy, float cxx, float cxy, float cyy, float &d2, float &nll) {
+#pragma clang fp contract(off)
+    const float det = cxx * cyy - cxy * cxy;
+    d2 = (cyy * (dx * dx) - 2.f * cxy * dx * dy + cxx * (dy * dy)) / det;
+    nll = 0.5f * d2 + 0.5f * (float)log((double)det) + 1.8378770664093453f;
+}
+
+}  // namespace stg

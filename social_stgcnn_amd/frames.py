@@ -20,6 +20,9 @@ stg_frame_scenes over a recording uploaded once, stg_track_push with the track s
     TrackRule          tracks=TrackRule(min_seen, max_gap) on any of the four: pedestrians with a short history or
                        tracker gaps are predicted too, their missed frames filled by the kernels
     fill_tracks        the fill alone, on a batch of scenes in place (stg_fill_tracks)
+    TimedScoreSpec     score=TimedScoreSpec(levels, best_of_k, pending) on the two live predictors together with time=:
+                       records indexed by time, truth interpolated as the timed push interpolates (stg_score_push_timed,
+                       DESIGN.md 5.25); `.score`, `.score_totals`, `.score_records`, `.score_evictions`
     ScoreSpec          score=ScoreSpec(levels, best_of_k) on the two live predictors: every push also scores the
                        predictions of the last pred_seq_len pushes against its detections (stg_score_push, DESIGN.md
                        5.17); `.score`, `.score_totals`, and score_summary for host numbers
@@ -44,7 +47,7 @@ import torch
 
 from . import ops
 from ._lib import check, lib, peds_arg, ptr, require_gpu, seed_i64, stream_ptr
-from .predict import Prediction, Predictor, ScoreSpec, eval_mode
+from .predict import Prediction, Predictor, ScoreSpec, TimedScoreSpec, eval_mode
 
 MAX_OBS_LEN = 32                       # presence masks are 32-bit
 MAX_DETECTIONS = 2048                  # STG_TRACK_MAX_DETECTIONS
@@ -384,6 +387,7 @@ class _LivePredictor:
 
     and `seed_dev`, the (1,) int64 device tensor the sampler reads its seed from."""
     assoc = None                         # the AssociateSpec; None: ids come with the pushes
+    _score_pushed = None                 # the (NS,) int32 `pushed` words a timed score launch reads; None: one stream
 
     def __init__(self, model, k, obs_len, capacity, max_peds, max_detections, decimals, risk=None, keep_samples=True,
                  tracks=None, score=None, time=None, associate=None):
@@ -397,12 +401,17 @@ class _LivePredictor:
         self.assoc = associate
         self._assoc_state = None
         self._n_det = 0
-        if time is not None and score is not None:
+        timed_score = isinstance(score, TimedScoreSpec)
+        if time is not None and score is not None and not timed_score:
             raise ValueError("time= together with score= is not supported: the score records are indexed by push, and "
-                             "re-indexing them by time is a change of its own (DESIGN.md 8)")
+                             "re-indexing them by time is a change of its own (DESIGN.md 8); the records indexed by "
+                             "time are score=TimedScoreSpec(...) (DESIGN.md 5.25)")
+        if timed_score and time is None:
+            raise ValueError("score=TimedScoreSpec(...) needs time=TimeRule(...): its records are indexed by time "
+                             "(without time= the push-indexed ScoreSpec serves)")
         self._risk_args = (risk, keep_samples)
         if score is not None:
-            score = score if isinstance(score, ScoreSpec) else ScoreSpec(*score)
+            score = score if isinstance(score, (ScoreSpec, TimedScoreSpec)) else ScoreSpec(*score)
             if score.best_of_k and not keep_samples:
                 raise ValueError("score: ScoreSpec(best_of_k=True) scores the K samples, and keep_samples=False leaves "
                                  "none (pass ScoreSpec(best_of_k=False) or keep the samples)")
@@ -477,8 +486,12 @@ class _LivePredictor:
         self._pred = Predictor(self.model, self.k, *self._risk_args)
         if self.score_spec is not None:
             spec = self.score_spec
-            self._score_state = ops.score_state(lead[0] if lead else 1, self.model.pred_seq_len, self.v, self.k, dev,
-                                                spec.best_of_k, len(spec.levels))
+            if isinstance(spec, TimedScoreSpec):
+                self._score_state = ops.score_timed_state(lead[0] if lead else 1, self.model.pred_seq_len, self.v,
+                                                          self.k, spec.pending, dev, spec.best_of_k, len(spec.levels))
+            else:
+                self._score_state = ops.score_state(lead[0] if lead else 1, self.model.pred_seq_len, self.v, self.k,
+                                                    dev, spec.best_of_k, len(spec.levels))
             self._thr = torch.tensor(spec.thresholds, dtype=torch.float32).to(dev) if spec.levels else None
         return dev
 
@@ -490,10 +503,48 @@ class _LivePredictor:
         st = self._score_state
         return None if st is None else (st.totals, st.traj_totals)
 
+    @property
+    def _timed_score(self):
+        return isinstance(self.score_spec, TimedScoreSpec)
+
+    @property
+    def score_records(self):
+        """With score=TimedScoreSpec(...): the record ring on the device, the ops.ScoreTimedState itself (NS = 1 for a
+        FramePredictor) -- rec_t, rec_status, rec_peds, rec_ids, the tables matched / err / d2 / nll / best (NS,Rp,P,V)
+        and the retired rows traj_* (NS,Rp,V); reading it is the caller's synchronisation.  None otherwise."""
+        return self._score_state if self._timed_score else None
+
+    @property
+    def score_evictions(self):
+        """With score=TimedScoreSpec(...): (NS,) int64 on the device, the records overwritten while still pending since
+        reset() (size `pending` to the feed: predict.TimedScoreSpec).  None otherwise."""
+        return self._score_state.counters[:, 1] if self._timed_score else None
+
+    def _score_streams(self):
+        st = self._score_state
+        return (st.counters if self._timed_score else st.head).shape[0]
+
+    def _score_buffers(self):
+        """Fresh outputs of the score launch (graph capture)."""
+        ns, p = self._score_streams(), self.model.pred_seq_len
+        if self._timed_score:
+            return ops.score_timed_buffers(ns, p, len(self.score_spec.levels), self.device)
+        return ops.score_buffers(ns, p, self.v, self.device, self.score_spec.best_of_k)
+
+    def _score_reset(self, at=None):
+        if self._score_state is not None:
+            (ops.score_timed_reset if self._timed_score else ops.score_reset)(self._score_state, at)
+
     def _score_push(self, outs, r, out=None):
         """The score launch of one push, behind the sampler (and the risk counts): the pending predictions against this
-        push's detections, then this push's prediction into the records (ops.score_push)."""
-        ns = self._score_state.head.shape[0]
+        push's detections, then this push's prediction into the records (ops.score_push); with a TimedScoreSpec against
+        the track samples the timed push has just recorded (ops.score_timed_push)."""
+        ns = self._score_streams()
+        if self._timed_score:
+            return ops.score_timed_push(self._score_state, self._thr, r.mean, r.v_pred,
+                                        r.samples if self.score_spec.best_of_k else None, outs[1].view(ns, self.v),
+                                        outs[2], self._state, self.time.step, self.time.max_dt, self.scale,
+                                        pushed=self._score_pushed, out=out)
         return ops.score_push(self._score_state, self._thr, r.mean, r.v_pred,
                               r.samples if self.score_spec.best_of_k else None, outs[1].view(ns, self.v), outs[2],
                               out=out, m_max=self.m_max, scale=self.scale, **self._det)
@@ -580,8 +631,7 @@ class _LivePredictor:
         saved = self._still()
         scored = None
         if self.score_spec is not None:
-            scored = ops.score_buffers(self._score_state.head.shape[0], self.model.pred_seq_len, self.v, self.device,
-                                       self.score_spec.best_of_k)
+            scored = self._score_buffers()
         try:
             graph, r, chain = self._pred.capture_chain(
                 outs[0], outs[2], self.seed_dev, warmup, pre=lambda: self._front(outs),
@@ -626,7 +676,11 @@ class FramePredictor(_LivePredictor):
     time: a TimeRule -- push(ids, xy, t=TICKS) and the captured replay(ids, xy, t=TICKS) at any rate: the scene is the
     tracks resampled at t - k * step (stg_track_push_timed; the time is staged into a device int64 next to the count,
     so one graph serves every push); `.seen` is always set; a time not after the last push's: the empty scene, flag
-    TIME_ORDER, nothing recorded.  Not together with score=.
+    TIME_ORDER, nothing recorded.  Not together with score=ScoreSpec(...), whose records are indexed by push; with
+    score=predict.TimedScoreSpec(...) (only together with time=) the prediction made at t is graded at t + h * step
+    against the track's sample or interpolated position at that instant (stg_score_push_timed, behind the sampler):
+    `.score` holds what the push added (ops.ScoreTimed), `.score_totals` the running totals, `.score_records` the
+    record ring with its per-record tables and retired rows, `.score_evictions` the records lost to a full ring.
     associate: an AssociateSpec -- pushes carry no ids, push(None, xy) and the captured replay(None, xy): stg_associate,
     one launch ahead of the push kernel (inside the captured graph), gives every detection its track id in the staging
     buffer the push and the score read; the returned ids are those track ids, `.det_ids` (M,) the id of every detection
@@ -653,8 +707,7 @@ class FramePredictor(_LivePredictor):
         for x in self._forget:
             x.zero_()
         self._reset_assoc()
-        if self._score_state is not None:
-            ops.score_reset(self._score_state)
+        self._score_reset()
 
     @property
     def det_ids(self):
@@ -855,7 +908,10 @@ class StreamsPredictor(_LivePredictor):
     with times a length-NS sequence or a {stream: t} mapping that covers every pushed stream -- staged in the same ONE
     copy, the staging header extended by NS int64 --, or with a DeviceTick a device int64 (NS) tensor.  The sample
     rings are capacity * history * 24 bytes per stream (2.4 MB at the defaults): size capacity and history to the feed.
-    Not together with score=."""
+    Not together with score=ScoreSpec(...); score=predict.TimedScoreSpec(...) as in FramePredictor
+    (stg_score_push_streams_timed, one workgroup per stream, every stream on its own clock): at pending 128, 128
+    pedestrians, k = 20 and 12 steps the records hold about 41 MB per stream, 2.6 GB for 64 streams (7.5 MB per stream
+    with best_of_k=False)."""
 
     def __init__(self, model, streams, k=20, obs_len=8, capacity=1024, max_peds=128, max_detections=1024, decimals=4,
                  max_total_detections=None, block_threads=0, risk=None, keep_samples=True, tracks=None, score=None,
@@ -904,6 +960,7 @@ class StreamsPredictor(_LivePredictor):
         # a record is (id, x, y): ids at stride 3 from its start, positions at stride 3 from 8 bytes in
         self._det = dict(det_id=ptr(self._rec_i), id_stride=3, det_xy=ctypes.c_void_p(self._rec_f.data_ptr() + 8),
                          xy_stride=3, m_total=self.cap, det_start=ptr(self.det_start), pushed=ptr(self.pushed_dev))
+        self._score_pushed = self.pushed_dev
         self._copied = torch.cuda.Event()
         self._in_flight = False
         self.reset()
@@ -917,8 +974,7 @@ class StreamsPredictor(_LivePredictor):
             for x in self._state[1:]:
                 x.zero_()
             self._reset_assoc()
-            if self._score_state is not None:
-                ops.score_reset(self._score_state)
+            self._score_reset()
             return
         idx = [int(x) for x in (streams if isinstance(streams, (list, tuple, np.ndarray, range)) else [streams])]
         for x in idx:
@@ -931,8 +987,7 @@ class StreamsPredictor(_LivePredictor):
         for x in self._state[1:]:
             x.index_fill_(0, at, 0)
         self._reset_assoc(at)
-        if self._score_state is not None:
-            ops.score_reset(self._score_state, at)
+        self._score_reset(at)
 
     @property
     def det_ids(self):

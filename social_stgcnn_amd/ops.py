@@ -946,6 +946,146 @@ def score_push(state, thr, mean, v_pred, samples, ids, num_peds, det_id, det_xy,
     return out
 
 
+ScoreTimedState = collections.namedtuple(
+    "ScoreTimedState", "rec_t rec_status rec_peds rec_ids rec_mean rec_cov rec_samples acc acc_mean steps matched err d2 "
+                       "nll best traj_steps traj_ade traj_fde traj_ade_mean traj_fde_mean counters totals traj_totals")
+ScoreTimedState.__doc__ = """The device state of `score_timed_push` (stg_score_timed_state), NS leading: the ring of Rp
+records per stream, indexed by time (DESIGN.md 5.25) -- rec_t (NS,Rp) int64 the time of the push that made the record,
+rec_status (NS,Rp) int32 {0 empty, 1 pending, 2 retired}, rec_peds (NS,Rp) int32, rec_ids (NS,Rp,V) int64, rec_mean
+(NS,Rp,P,V,2), rec_cov (NS,Rp,P,V,3), rec_samples (NS,Rp,K,P,V,2), the accumulators acc (NS,Rp,K,V), acc_mean (NS,Rp,V)
+float32 and steps (NS,Rp,V) int32 --, the record's own tables matched int32, err, d2, nll, best float32 (NS,Rp,P,V)
+(row h-1: the record scored at t_r + h * step), the retired rows traj_steps int32, traj_ade, traj_fde, traj_ade_mean,
+traj_fde_mean float32 (NS,Rp,V), counters (NS,2) int64 {accepted pushes, evictions} and the running totals: totals
+(NS,P,5+Q), traj_totals (NS,5) float64 with ScoreState's columns.  Columns v >= rec_peds of a row are not part of the
+contract.  rec_samples, acc, best, traj_ade and traj_fde are None when samples are not scored."""
+ScoreTimed = collections.namedtuple("ScoreTimed", "push_totals push_traj")
+ScoreTimed.__doc__ = """What one timed push added to the running totals (`stg_score_push_timed`), NS leading: push_totals
+(NS,P,5+Q) and push_traj (NS,5) float64, all zero for a stream not pushed or refused."""
+SCORE_MAX_PENDING = 1024                                                     # STG_SCORE_MAX_PENDING
+_SCORE_TIMED_SAMPLED = ("rec_samples", "acc", "best", "traj_ade", "traj_fde")
+
+
+def _score_timed_shapes(ns, p, v, k, q, rp):
+    rpv = (ns, rp, p, v)
+    return dict(rec_t=(ns, rp), rec_status=(ns, rp), rec_peds=(ns, rp), rec_ids=(ns, rp, v), rec_mean=rpv + (2,),
+                rec_cov=rpv + (3,), rec_samples=(ns, rp, k, p, v, 2), acc=(ns, rp, k, v), acc_mean=(ns, rp, v),
+                steps=(ns, rp, v), matched=rpv, err=rpv, d2=rpv, nll=rpv, best=rpv, traj_steps=(ns, rp, v),
+                traj_ade=(ns, rp, v), traj_fde=(ns, rp, v), traj_ade_mean=(ns, rp, v), traj_fde_mean=(ns, rp, v),
+                counters=(ns, 2), totals=(ns, p, 5 + q), traj_totals=(ns, 5))
+
+
+def score_timed_state(ns, p, v, k, pending, device, samples=True, q=3):
+    """A cleared ScoreTimedState for ns streams, horizons p, scenes padded to v pedestrians, k samples, `pending` record
+    rows and q coverage thresholds.  samples=False (or k = 0): the samples are not kept, nothing sample-based is scored.
+    Size per stream: pending*V*(28 + 36P) bytes, and pending*V*(8KP + 4K + 4P + 8) more with samples -- at pending 128,
+    V 128, K 20, P 12 about 7.5 MB without and 41 MB with the samples (31.5 MB of it the samples themselves), so 64
+    streams hold 2.6 GB; the totals add 8P(5+q) + 40 bytes."""
+    ns, p, v, k, q, rp = int(ns), int(p), int(v), int(k) if samples else 0, int(q), int(pending)
+    for what, got, most in (("V", v, SCORE_MAX_V), ("k", k, SCORE_MAX_K), ("P", p, SCORE_MAX_P), ("q", q, SCORE_MAX_Q),
+                            ("pending", rp, SCORE_MAX_PENDING)):
+        if got > most:
+            raise ValueError("score_timed_state: %s=%d above the kernel's limit of %d" % (what, got, most))
+    if ns < 1 or p < 1 or v < 1 or k < 0 or q < 0 or rp < 1:
+        raise ValueError("score_timed_state: bad sizes ns=%d p=%d v=%d k=%d q=%d pending=%d" % (ns, p, v, k, q, rp))
+    dtypes = dict(rec_t=torch.int64, rec_ids=torch.int64, counters=torch.int64, totals=torch.float64,
+                  traj_totals=torch.float64)
+    dtypes.update({n: torch.int32 for n in ("rec_status", "rec_peds", "steps", "matched", "traj_steps")})
+    shapes = _score_timed_shapes(ns, p, v, k, q, rp)
+    return ScoreTimedState(*[None if (k == 0 and n in _SCORE_TIMED_SAMPLED) else
+                             torch.full(shapes[n], -1 if n == "rec_ids" else 0, device=device,
+                                        dtype=dtypes.get(n, torch.float32)) for n in ScoreTimedState._fields])
+
+
+def score_timed_reset(state, streams=None):
+    """Clear records, counters and totals of every stream, or of the stream indices in the int64 device tensor
+    `streams`."""
+    for name, x in zip(ScoreTimedState._fields, state):
+        if x is None:
+            continue
+        fill = -1 if name == "rec_ids" else 0
+        if streams is None:
+            x.fill_(fill)
+        else:
+            x.index_fill_(0, streams, fill)
+
+
+def score_timed_buffers(ns, p, q, device):
+    """An empty ScoreTimed for ns streams (graph capture: the outputs `score_timed_push(out=...)` fills)."""
+    return ScoreTimed(torch.empty((ns, p, 5 + q), device=device, dtype=torch.float64),
+                      torch.empty((ns, 5), device=device, dtype=torch.float64))
+
+
+def score_timed_push(state, thr, mean, v_pred, samples, ids, num_peds, tracks, step, max_dt, scale, pushed=None,
+                     out=None):
+    """Score the pending timed predictions of every stream against the track samples of the timed push that has just
+    run, retire those whose last instant has arrived, then enqueue this push's prediction (`stg_score_push_timed` /
+    `stg_score_push_streams_timed`; the rule: DESIGN.md 5.25).  state: a ScoreTimedState; thr: (Q,) float32 device tensor
+    of d2 thresholds or None; the prediction as the chain leaves it, as `score_push` takes it; tracks: the timed push's
+    state (slot_id (NS,S), t_ring (NS,S,R), xy_ring (NS,S,R,2), slot_head (NS,S,2), clock (NS,2), head_flags (NS,2)),
+    read only; step, max_dt and scale as that push was given them.  pushed: (NS,) int32 device tensor (the packed tick's)
+    -- None: one stream, always pushed.  out: an earlier ScoreTimed to fill (graph capture).  No host synchronisation.
+    Returns a ScoreTimed."""
+    require_gpu(mean, v_pred, samples, ids, num_peds, *tracks, *[x for x in state if x is not None])
+    if v_pred.dim() != 4 or v_pred.shape[1] != 5:
+        raise ValueError("score_timed_push: v_pred (NS,5,P,V) expected")
+    ns, _, p, v = v_pred.shape
+    _lib.as_f32(v_pred, "v_pred")
+    if tuple(mean.shape) != (ns, p, v, 2) or mean.dtype != torch.float32 or not mean.is_contiguous():
+        raise ValueError("score_timed_push: mean must be a contiguous float32 (NS,P,V,2) tensor")
+    k = 0 if samples is None or state.rec_samples is None else samples.shape[0]
+    if k and (tuple(samples.shape) != (k, ns, p, v, 2) or samples.dtype != torch.float32 or not samples.is_contiguous()):
+        raise ValueError("score_timed_push: samples must be a contiguous float32 (K,NS,P,V,2) tensor")
+    if ids.numel() != ns * v or ids.dtype != torch.int64 or not ids.is_contiguous():
+        raise ValueError("score_timed_push: ids must be a contiguous int64 (NS,V) tensor")
+    if num_peds.numel() != ns or num_peds.dtype != torch.int32:
+        raise ValueError("score_timed_push: num_peds must be an int32 (NS,) tensor")
+    slot_id, t_ring, xy_ring, slot_head, clock, head_flags = tracks
+    if t_ring.dim() < 2 or slot_id.numel() % ns:
+        raise ValueError("score_timed_push: tracks do not fit %d streams" % ns)
+    s, r = slot_id.numel() // ns, t_ring.shape[-1]
+    track_want = ((slot_id, ns * s, torch.int64), (t_ring, ns * s * r, torch.int64), (xy_ring, ns * s * r * 2, torch.float64),
+                  (slot_head, ns * s * 2, torch.int32), (clock, ns * 2, torch.int64), (head_flags, ns * 2, torch.int32))
+    for x, n, dt in track_want:
+        if x.numel() != n or x.dtype != dt or not x.is_contiguous():
+            raise ValueError("score_timed_push: the track state does not fit this call (S=%d, R=%d)" % (s, r))
+    q, rp = state.totals.shape[2] - 5, state.rec_t.shape[1]
+    want = _score_timed_shapes(ns, p, v, k, q, rp)
+    for name, x in zip(ScoreTimedState._fields, state):
+        if k == 0 and name in _SCORE_TIMED_SAMPLED:
+            continue
+        if x is None or tuple(x.shape) != want[name] or not x.is_contiguous():
+            raise ValueError("score_timed_push: state.%s does not fit this call (%s expected)" % (name, want[name]))
+    if q and (thr is None or thr.numel() != q or thr.dtype != torch.float32 or not thr.is_cuda):
+        raise ValueError("score_timed_push: thr must be a float32 device tensor of %d thresholds" % q)
+    for what, got, most in (("V", v, SCORE_MAX_V), ("K", k, SCORE_MAX_K), ("P", p, SCORE_MAX_P), ("Q", q, SCORE_MAX_Q),
+                            ("pending", rp, SCORE_MAX_PENDING)):
+        if got > most:
+            raise ValueError("score_timed_push: %s=%d above the kernel's limit of %d" % (what, got, most))
+    if out is None:
+        out = score_timed_buffers(ns, p, q, mean.device)
+    else:
+        for name, o, w in zip(ScoreTimed._fields, out, score_timed_buffers(ns, p, q, "meta")):
+            if tuple(o.shape) != tuple(w.shape) or o.dtype != w.dtype or not o.is_contiguous() or not o.is_cuda:
+                raise ValueError("score_timed_push: out.%s does not fit this call" % name)
+    st = _lib.ScoreTimedState(*[None if (x is None or (k == 0 and name in _SCORE_TIMED_SAMPLED)) else x.data_ptr()
+                                for name, x in zip(ScoreTimedState._fields, state)])
+    so = _lib.ScoreTimedOut(*[o.data_ptr() for o in out])
+    sn, sf, sp, sv = v_pred.stride()
+    sizes = (s, r, ctypes.c_double(scale), int(step), int(max_dt))
+    pred = (ptr(mean), ptr(v_pred), sn, sf, sp, sv, ptr(samples) if k else None, ptr(ids), ptr(num_peds), p, v, k, rp,
+            ctypes.byref(st), ptr(thr) if q else None, q, ctypes.byref(so), stream_ptr())
+    if pushed is None:
+        if ns != 1:
+            raise ValueError("score_timed_push: %d streams need `pushed`" % ns)
+        check(lib().stg_score_push_timed(*map(ptr, tracks), *sizes, *pred), "stg_score_push_timed")
+    else:
+        if pushed.numel() != ns or pushed.dtype != torch.int32 or not pushed.is_cuda:
+            raise ValueError("score_timed_push: pushed must be an int32 (NS,) device tensor")
+        check(lib().stg_score_push_streams_timed(*map(ptr, tracks), ptr(pushed), ns, *sizes, *pred),
+              "stg_score_push_streams_timed")
+    return out
+
+
 def scene_order(num_peds, v):
     """Scene indices sorted by pedestrian count (clamped to [0, v]) descending, stable: the schedule the fused
     kernels use for ragged batches (`stg_scene_order`).  num_peds: int32 device tensor (N,).

@@ -8,6 +8,7 @@ test_v.py / visualize.py read.
                       caller's static inputs, which frames.py puts behind its push kernels).  With `risk=RiskSpec(...)`
                       the chain ends in stg_sample_risk: conflict and zone-occupancy counts over the K samples
     ScoreSpec         what the live predictors (frames.py) score their predictions for once the truth has arrived
+    TimedScoreSpec    the same for predictors driven with time=: records indexed by time, truth interpolated
     sample_test       test() over data.SceneWindows: (ade, fde, raw_data_dict)
 """
 import collections
@@ -44,6 +45,35 @@ class ScoreSpec(collections.namedtuple("ScoreSpec", "levels best_of_k")):
         if not isinstance(best_of_k, (bool, np.bool_)):
             raise ValueError("ScoreSpec: best_of_k must be True or False, got %r" % (best_of_k,))
         return super().__new__(cls, levels, bool(best_of_k))
+
+    @property
+    def thresholds(self):
+        """The d2 thresholds of the levels, -2 ln(1 - p)."""
+        return ops.score_thresholds(self.levels)
+
+
+class TimedScoreSpec(collections.namedtuple("TimedScoreSpec", "levels best_of_k pending")):
+    """What a live predictor driven with time= scores its predictions for (ops.score_timed_push): the
+    prediction made at time t is graded at t + h * step against the track's position at that instant -- a sample at
+    exactly that time, or the interpolation of the two samples that bracket it when they are at most max_dt apart, as
+    the timed push builds its window.  levels and best_of_k as ScoreSpec; pending: the number of record rows per stream
+    (1 .. 1024).  Every accepted push leaves a record and a record lives for pred_seq_len * step ticks, so `pending`
+    should be at least (pushes per step) * pred_seq_len -- 48 for a 25 Hz feed and a 0.4 s step at pred_seq_len 12 --
+    or records are evicted before their last instant (counted in `.score_evictions`; a full trajectory is never lost
+    that way, an evicted one only never becomes full).  The records hold pending * V * (28 + 36 P) bytes per stream and
+    pending * V * (8 K P + 4 K + 4 P + 8) more with best_of_k."""
+    __slots__ = ()
+
+    def __new__(cls, levels=(0.5, 0.9, 0.99), best_of_k=True, pending=128):
+        levels = tuple(float(x) for x in levels)
+        ops.score_thresholds(levels)                       # refuses a level outside (0, 1) and more than four of them
+        if not isinstance(best_of_k, (bool, np.bool_)):
+            raise ValueError("TimedScoreSpec: best_of_k must be True or False, got %r" % (best_of_k,))
+        if isinstance(pending, (bool, np.bool_)) or not isinstance(pending, (int, np.integer)) or \
+                not 1 <= int(pending) <= ops.SCORE_MAX_PENDING:
+            raise ValueError("TimedScoreSpec: pending must be an integer in [1, %d], got %r"
+                             % (ops.SCORE_MAX_PENDING, pending))
+        return super().__new__(cls, levels, bool(best_of_k), int(pending))
 
     @property
     def thresholds(self):

@@ -4,7 +4,8 @@ trajectories for every pedestrian tracked over the last obs_seq_len frames.
     python -m social_stgcnn_amd.predict_frames --checkpoint DIR --recording FILE [--ksteps 20] [--seed 0]
                                                [--min_peds 1] [--delim tab] [--radius R]
                                                [--zones x0,y0,x1,y1 ...] [--min_seen M] [--max_gap G]
-                                               [--step TICKS [--max_dt D] [--history R] [--max_peds V]]
+                                               [--step TICKS [--max_dt D] [--history R] [--max_peds V]
+                                                [--score [--pending N]]]
                                                [--associate GATE[,GATE_NEW[,MAX_MISS]] [--max_peds V]]
                                                --out preds.npz
 
@@ -29,6 +30,12 @@ pedestrians, padded to the largest scene (at most --max_peds, default 128: the s
 above `seen` and `time` (N,) int64, the pushes' times (`frame` holds the same numbers as float64).  The sampler's seed is
 --seed + the push's index.  Not together with --radius / --zones.  Where a recording skips a frame number the two rules
 differ: the frame-index rule makes neighbours of frames 20 ticks apart, the timed rule sees a gap.
+With --score every push also grades the earlier predictions against the tracks that followed (predict.TimedScoreSpec with
+--pending record rows, DESIGN.md 5.25: the prediction made at t is graded at t + h * TICKS, the truth interpolated as the
+window is) and the .npz also holds the running summary at the end of the recording (frames.score_summary), per horizon
+score_count, score_err, score_d2, score_nll, score_best (P,) and score_coverage (P,Q) at score_levels (Q,), and
+score_trajectories, score_ade, score_fde, score_ade_mean, score_fde_mean over the fully observed trajectories, with
+score_evictions, the records that left the ring before their last instant.
 
 --associate GATE[,GATE_NEW[,MAX_MISS]] ignores the id column: every distinct frame number is one push of positions only,
 rows in file order, through a captured frames.FramePredictor(associate=frames.AssociateSpec(...)), which gives every
@@ -44,9 +51,9 @@ import numpy as np
 import torch
 
 from . import data
-from .frames import AssociateSpec, FramePredictor, TimeRule, TrackRule, predict_recording, sorted_rows
+from .frames import AssociateSpec, FramePredictor, TimeRule, TrackRule, predict_recording, score_summary, sorted_rows
 from .model import social_stgcnn
-from .predict import RiskSpec
+from .predict import RiskSpec, TimedScoreSpec
 from .trainer import load_checkpoint, load_pickle
 
 
@@ -74,6 +81,10 @@ def build_parser():
     p.add_argument("--history", type=int, default=96, help="with --step: samples kept per track")
     p.add_argument("--max_peds", type=int, default=128,
                    help="with --step or --associate: the widest scene (the smallest ids are kept)")
+    p.add_argument("--score", action="store_true",
+                   help="with --step: grade the predictions against the tracks that follow (score_* arrays)")
+    p.add_argument("--pending", type=int, default=128,
+                   help="with --score: record rows kept (at least pushes per step x pred_seq_len)")
     p.add_argument("--associate", default=None, metavar="GATE[,GATE_NEW[,MAX_MISS]]",
                    help="ignore the id column: associate the detections to tracks on the device (assoc_ids array)")
     p.add_argument("--out", required=True, help="output .npz")
@@ -101,16 +112,17 @@ def load_model(exp_path, device):
     return model.to(device).eval()
 
 
-def predict_timed(model, rows, time, k=20, seed=0, min_peds=1, tracks=None, max_peds=128):
+def predict_timed(model, rows, time, k=20, seed=0, min_peds=1, tracks=None, max_peds=128, score=None):
     """Every distinct frame number of `rows`, taken as a time in ticks, pushed through ONE captured timed
-    FramePredictor -> a dict of host arrays, one entry per push whose scene holds at least min_peds pedestrians."""
+    FramePredictor -> a dict of host arrays, one entry per push whose scene holds at least min_peds pedestrians.
+    score: a predict.TimedScoreSpec -- the dict also holds the summary of the running totals as score_* arrays."""
     frames, fs, ids, xy = sorted_rows(rows)
     if np.any(frames != np.round(frames)):
         raise ValueError("--step: the frame column must hold integer ticks")
     ticks = frames.astype(np.int64)
     m_max = max(1, int(np.diff(fs).max()) if len(frames) else 1)
     fp = FramePredictor(model, k=k, obs_len=model.seq_len, max_peds=max_peds, max_detections=m_max, tracks=tracks,
-                        time=time)
+                        time=time, score=score)
     replay = fp.capture()
     keep = {name: [] for name in ("time", "ids", "num_peds", "mean", "samples", "seen")}
     for f, t in enumerate(ticks.tolist()):
@@ -130,6 +142,11 @@ def predict_timed(model, rows, time, k=20, seed=0, min_peds=1, tracks=None, max_
     res.update(ids=res["ids"][:, :v], seen=res["seen"][:, :v], mean=res["mean"][:, :, :v],
                samples=np.ascontiguousarray(np.moveaxis(res["samples"], 0, 1)[:, :, :, :v]))
     res["frame"] = res["time"].astype(np.float64)
+    if score is not None:
+        summary = score_summary(*fp.score_totals, score.levels)
+        res.update({"score_" + name: np.asarray(x)[0] for name, x in zip(summary._fields[:-1], summary[:-1])})
+        res["score_levels"] = np.asarray(score.levels, np.float64)
+        res["score_evictions"] = fp.score_evictions.cpu().numpy()[0]
     return res
 
 
@@ -191,6 +208,9 @@ def main(argv=None):
     tracks = None
     if a.min_seen is not None or a.max_gap is not None:
         tracks = TrackRule(model.seq_len if a.min_seen is None else a.min_seen, 0 if a.max_gap is None else a.max_gap)
+    if a.score and (a.step is None or a.associate is not None):
+        raise ValueError("--score needs --step (and does not go with --associate): the records it keeps are indexed "
+                         "by time")
     if a.associate is not None:
         if a.step is not None or a.radius is not None or a.zones is not None:
             raise ValueError("--associate does not go together with --step or --radius / --zones")
@@ -204,9 +224,13 @@ def main(argv=None):
         if a.radius is not None or a.zones is not None:
             raise ValueError("--step does not go together with --radius / --zones")
         res = predict_timed(model, rows, TimeRule(a.step, a.max_dt, a.history), a.ksteps, a.seed, a.min_peds, tracks,
-                            a.max_peds)
+                            a.max_peds, TimedScoreSpec(pending=a.pending) if a.score else None)
         np.savez(a.out, **res)
         print("%d pushes with a scene, up to %d pedestrians -> %s" % (len(res["time"]), res["ids"].shape[1], a.out))
+        if a.score:
+            print("scored: %d entries, %d full trajectories, ADE %.4f FDE %.4f, %d records evicted"
+                  % (int(res["score_count"].sum()), int(res["score_trajectories"]), float(res["score_ade"]),
+                     float(res["score_fde"]), int(res["score_evictions"])))
         return
     if a.radius is None and a.zones is None:
         scenes, pred = predict_recording(model, rows, k=a.ksteps, seed=a.seed, min_peds=a.min_peds, tracks=tracks)

@@ -8,7 +8,7 @@
     python tools/frames_bench.py --cases associate [--streams 1,64,600] [--ticks 200] [--associate 1.0,2.0,0]
                                  [--no-lone]
     python tools/frames_bench.py --tracks 2,2 ...       every case under frames.TrackRule(2, 2) (the *_rule kernels)
-    python tools/frames_bench.py --time 10,10 ...       the latency and streams cases on timestamped pushes
+    python tools/frames_bench.py --time 10,10 ...       the latency, streams and score cases on timestamped pushes
                                                         (frames.TimeRule(10, history=--history), stg_track_push_timed):
                                                         a model step is 10 ticks and the feed is upsampled 10x by linear
                                                         interpolation, one push per tick (--time STEP: not upsampled)
@@ -30,7 +30,9 @@
 
   score      the streams case with and without score=ScoreSpec() (stg_score_push_streams behind the sampler, inside the
              graph) at NS = 1, 64 and 600 (or --streams), no yardstick: tick p50 / p90 of both, the difference, what
-             the score records hold on the device (state_mb) and the running summary at the last tick.
+             the score records hold on the device (state_mb) and the running summary at the last tick.  With --time
+             both sides are the timed predictors and the spec is TimedScoreSpec(pending=--pending)
+             (stg_score_push_streams_timed, records indexed by time); `evictions` counts the records lost to the ring.
 
   associate  the streams case with and without associate=AssociateSpec(...) (stg_associate_streams ahead of the push
              launch, inside the graph; ticks of (None, xy)) at NS = 1, 64 and 600 (or --streams), no yardstick: tick p50 /
@@ -224,6 +226,8 @@ def streams_case(ns, k, n_ticks, dev, block=0, lone=True, max_peds=128, warmup=2
         n = s.count.sum(axis=0)
         res.update({"state_mb": round(sum(x.numel() * x.element_size() for x in st if x is not None) / 1e6, 1),
                     "scored": int(n.sum()), "trajectories": int(s.trajectories.sum()),
+                    **({} if sp.score_evictions is None else {"pending": score.pending,
+                                                              "evictions": int(sp.score_evictions.sum())}),
                     "err_h1": round(float(np.nansum(s.err[:, 0] * s.count[:, 0]) / max(1.0, n[0])), 4),
                     "err_hP": round(float(np.nansum(s.err[:, -1] * s.count[:, -1]) / max(1.0, n[-1])), 4)})
     if lone:
@@ -297,6 +301,8 @@ def main():
                     help="timestamped pushes (frames.TimeRule(STEP)) on the feed upsampled UP x (default 1) by linear "
                          "interpolation: the latency and streams cases")
     ap.add_argument("--history", type=int, default=96, help="with --time: samples kept per track")
+    ap.add_argument("--pending", type=int, default=128,
+                    help="with --time and the score case: record rows per stream (predict.TimedScoreSpec)")
     ap.add_argument("--associate", default="1.0,2.0,0", metavar="GATE[,GATE_NEW[,MAX_MISS]]",
                     help="the AssociateSpec of the associate case")
     a = ap.parse_args()
@@ -318,10 +324,12 @@ def main():
         for split, rec in TEST_RECORDINGS:
             print(json.dumps(recording_case(split, rec, a.k, dev, tracks)), flush=True)
     if "score" in cases:
-        from social_stgcnn_amd.predict import ScoreSpec
+        from social_stgcnn_amd.predict import ScoreSpec, TimedScoreSpec
+        # with --time the timed predictors and the records indexed by time
+        spec = ScoreSpec() if timed is None else TimedScoreSpec(pending=a.pending)
         for ns in (int(n) for n in (a.streams if a.streams != "1,8,64,256,600" else "1,64,600").split(",")):
-            off = streams_case(ns, a.k, a.ticks, dev, 0, False, tracks=tracks)
-            on = streams_case(ns, a.k, a.ticks, dev, 0, False, tracks=tracks, score=ScoreSpec())
+            off = streams_case(ns, a.k, a.ticks, dev, 0, False, tracks=tracks, timed=timed)
+            on = streams_case(ns, a.k, a.ticks, dev, 0, False, tracks=tracks, score=spec, timed=timed)
             on.update({"case": "score", "tick_p50_ms_without": off["tick_p50_ms"],
                        "tick_p90_ms_without": off["tick_p90_ms"],
                        "score_cost_p50_ms": round(on["tick_p50_ms"] - off["tick_p50_ms"], 4)})
