@@ -31,9 +31,11 @@ def maxdiff(a, b):
     return float(np.max(np.abs(a - b))) if a.size else 0.0
 
 
-def grad_errors(named_got, ref_of):
+def grad_errors(named_got, ref_of, zero_biases=ZERO_GRAD_BIASES):
     """named_got: iterable of (name, grad tensor / array or None); ref_of(name) -> numpy array or None (dead).
-    Returns {name: relative error} for live parameters; asserts dead ones are None on both sides."""
+    Returns {name: relative error} for live parameters; asserts dead ones are None on both sides.
+    zero_biases: the name endings that get the zero-gradient-bias rule (train mode; () in eval mode, where those
+    biases have ordinary gradients)."""
     named_got = list(named_got)
     refs = {name: ref_of(name) for name, _ in named_got}
     out = {}
@@ -44,13 +46,14 @@ def grad_errors(named_got, ref_of):
             continue
         assert got is not None, name
         scale = max(1e-3, float(np.abs(ref).max()))
-        if name.endswith(ZERO_GRAD_BIASES):
+        zero = bool(zero_biases) and name.endswith(tuple(zero_biases))
+        if zero:
             sib = refs.get(name[:-4] + "weight")
             if sib is not None:
                 scale = max(scale, float(np.abs(sib).max()))
         got = got.detach().cpu().numpy() if torch.is_tensor(got) else got
         err = maxdiff(got, ref) / scale
-        out[name] = err / 10.0 if name.endswith(ZERO_GRAD_BIASES) else err
+        out[name] = err / 10.0 if zero else err
     return out
 
 
@@ -211,16 +214,20 @@ def kink_watch(out):
         F.prelu = orig
 
 
-def oracle_model_step(state, batch, n_stgcnn, n_txpcnn, dtype=torch.float64, training=True, want_dx=False):
+def oracle_model_step(state, batch, n_stgcnn, n_txpcnn, dtype=torch.float64, training=True, want_dx=False,
+                      eval_grads=False):
     """The reference's loop over the scenes of `batch` (oracle.scene_loss, one scene at a time, N = 1) in `dtype`:
     per-scene V_pred (P,c,5) and loss for the unique scenes, the parameter gradients of sum_n w_n loss_n over the whole
     (tiled) batch, dx per unique scene (for weight w_i), and the state after the batch: the running statistics folded
     scene by scene in batch order, zero-pedestrian scenes not counted (`after_once`: after one pass over the unique
-    scenes, carried through the oracle's own BatchNorm calls; `after`: after the whole tiled batch)."""
+    scenes, carried through the oracle's own BatchNorm calls; `after`: after the whole tiled batch).
+    training=False: V_pred and losses from the running statistics; with eval_grads also the parameter gradients (and dx)
+    of the same weighted sum -- the buffers do not move, `after` / `after_once` stay None."""
     from oracle import stgcnn_oracle as O
+    with_grads = training or eval_grads
     st = _cast(state, dtype)
     keys = [k for k in O.state_dict_keys(n_stgcnn, n_txpcnn) if k in st and "running" not in k and "num_batches" not in k]
-    params = {k: st[k].clone().requires_grad_(training) for k in keys}
+    params = {k: st[k].clone().requires_grad_(with_grads) for k in keys}
     stat_keys = [k for k in st if "running" in k]
     work = {k: v.clone() for k, v in st.items()}
     work.update(params)
@@ -236,24 +243,26 @@ def oracle_model_step(state, batch, n_stgcnn, n_txpcnn, dtype=torch.float64, tra
             continue
         xi, lap, t_i = batch.scenes[i]
         before = {k: work[k].clone() for k in stat_keys}
-        x = torch.from_numpy(xi).to(dtype).unsqueeze(0).requires_grad_(want_dx)
+        x = torch.from_numpy(xi).to(dtype).unsqueeze(0).requires_grad_(want_dx and with_grads)
         with kink_watch(kink):
             l, vp = O.scene_loss(work, x, torch.from_numpy(lap).to(dtype), torch.from_numpy(t_i).to(dtype), training,
                                  n_stgcnn=n_stgcnn, n_txpcnn=n_txpcnn)
         res.pred[i], res.loss[i] = vp.detach().numpy(), float(l.detach())
-        if not training:
+        if not with_grads:
             continue
-        # running' = (1 - m) running + m s: the scene's own statistic s (mean / unbiased variance), for the tiled fold
-        stats[i] = {k: (work[k] - keep * before[k]) / O.BN_MOMENTUM for k in stat_keys}
+        if training:
+            # running' = (1 - m) running + m s: the scene's own statistic s (mean / unbiased variance), for the tiled fold
+            stats[i] = {k: (work[k] - keep * before[k]) / O.BN_MOMENTUM for k in stat_keys}
         w_i = float(batch.weights_u[i])
         if want_dx:
             gx, = torch.autograd.grad(l * w_i, x, retain_graph=True)
             res.dx[i] = gx[0].numpy()
         w_i *= int(batch.mult[i])
         total = l * w_i if total is None else total + l * w_i
-    if training:
+    if with_grads:
         total.backward()
         res.grads = {k: (None if params[k].grad is None else params[k].grad.numpy()) for k in keys}
+    if training:
         res.after_once = {k: v.detach().clone() for k, v in work.items() if k not in params}
         after = {k: v.clone() for k, v in res.after_once.items()}
         if batch.n > batch.unique and dtype != torch.float64:
@@ -317,8 +326,10 @@ def oracle_distance(r32, r64):
     loss = max([abs(r32.loss[i] - r64.loss[i]) for i in r64.loss] + [0.0])
     grad = stat = 0.0
     if r64.grads is not None:
-        errs = grad_errors(((k, r32.grads[k]) for k in r64.grads), lambda k: r64.grads[k])
+        errs = grad_errors(((k, r32.grads[k]) for k in r64.grads), lambda k: r64.grads[k],
+                           ZERO_GRAD_BIASES if r64.after_once is not None else ())
         grad = max(errs.values())
+    if r64.after_once is not None:
         stat = max(maxdiff(r32.after_once[k].numpy(), r64.after_once[k].numpy()) for k in r64.after_once
                    if "running" in k)
     return pred, loss, grad, stat
@@ -422,6 +433,15 @@ def trainer_cases():
     return [Case("trainer", b, k, 40, ragged(40, 64), mean_weights=True) for (b, k) in ((1, 3), (1, 8), (2, 5))]
 
 
+def eval_backward_cases():
+    """Full-model backward in eval mode (running statistics, `bn_mode` 0): one ragged batch of 20 scenes per geometry,
+    padded to 57 on the scene path and to 57 and 96 under the stacked layouts."""
+    out = [Case("evalbwd", 1, k, 57, ragged(57, 20)) for k in (3, 5, 8)]
+    for (b, k) in ((2, 5), (4, 8)):
+        out += [Case("evalbwd", b, k, v, ragged(v, 20)) for v in (57, 96)]
+    return out
+
+
 # seeds moved off the PReLU kink: in the float64 oracle of every case no pre-activation lies within KINK_MARGIN of zero,
 # and the float32 oracle sits inside the project bars (test_lib_cpu.py::test_layout_cases_fp32_oracle_inside_project_bars)
 SEED_SHIFT = {
@@ -434,4 +454,6 @@ SEED_SHIFT = {
     "tiled-1x3-V100-N400": 2, "tiled-1x8-V100-N1536": 14, "tiled-1x8-V100-N400": 37, "trainer-1x8-V40-N64": 10,
     "trainer-2x5-V40-N64": 5, "uniform-1x3-V32-N1536": 3, "uniform-1x3-V32-N2048": 3, "uniform-1x8-V32-N1536": 26,
     "uniform-1x8-V32-N2048": 2,
+    # eval-mode backward (test_exact_probes_cpu.py::test_eval_backward_cases_fp32_oracle_inside_project_bars)
+    "evalbwd-1x3-V57-N20": 1, "evalbwd-2x5-V96-N20": 2, "evalbwd-4x8-V96-N20": 1,
 }

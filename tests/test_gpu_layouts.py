@@ -185,6 +185,50 @@ def test_eval_forward_uses_the_running_statistics(dev, layout):
         assert torch.equal(val.cpu(), state[k]), k                            # buffers (and parameters) untouched
 
 
+# ------------------------------------------------------------------------------------------
+# 2b. full-model backward in eval mode
+# ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", LC.eval_backward_cases(), ids=repr)
+def test_eval_backward_against_the_oracle(dev, case):
+    """`.eval()` with requires_grad: stg_model_fwd with a workspace under bn_mode 0, then stg_model_bwd from the loss
+    gradient the nll kernel hands back through autograd.  V_pred, per-scene losses and every parameter gradient of
+    sum_n w_n loss_n against the float64 oracle at training=False; the bars are the file's own.  An eval-mode BatchNorm
+    passes a per-channel shift through, so the conv biases in front of one have ordinary gradients and are compared like
+    every other parameter.  The buffers do not move."""
+    from social_stgcnn_amd.metrics import bivariate_loss
+    model, state, b = case.build()
+    r64 = LC.oracle_model_step(state, b, case.n_stgcnn, case.n_txpcnn, training=False, eval_grads=True)
+    r32 = LC.oracle_model_step(state, b, case.n_stgcnn, case.n_txpcnn, dtype=torch.float32, training=False,
+                               eval_grads=True)
+    own = LC.oracle_distance(r32, r64)
+    bar_p, bar_l, bar_g, _ = LC.bars(own)
+    m = model.to(dev).eval()
+    x, adj, tgt, peds, w = b.device(dev)
+    y, _ = m(x, adj, peds)
+    assert m.last_ws_floats > 0
+    losses = bivariate_loss(y.permute(0, 2, 3, 1), tgt, peds)
+    (losses * w).sum().backward()
+    yc, lc = y.detach().cpu().numpy(), losses.detach().cpu().numpy()
+    e_pred = e_loss = 0.0
+    for i in range(b.unique):
+        c = int(b.counts_u[i])
+        assert np.all(yc[i, :, :, c:] == 0), (case, i, "V_pred padding")
+        if c == 0:
+            assert lc[i] == 0, (case, i)
+            continue
+        e_pred = max(e_pred, LC.maxdiff(yc[i, :, :, :c], np.transpose(r64.pred[i], (2, 0, 1))))
+        e_loss = max(e_loss, abs(float(lc[i]) - r64.loss[i]))
+    errs = LC.grad_errors(((name, p.grad) for name, p in m.named_parameters()), lambda name: r64.grads[name], ())
+    worst = max(errs, key=errs.get)
+    print("\n%-28s V_pred %.1e (fp32 oracle %.1e)  loss %.1e (%.1e)  grad %.1e (%.1e) %s"
+          % (case.id, e_pred, own[0], e_loss, own[1], errs[worst], own[2], worst))
+    assert e_pred < bar_p and e_loss < bar_l, (case, e_pred, e_loss)
+    assert not {k: e for k, e in errs.items() if e > bar_g}, (case, errs)
+    for k, val in m.state_dict().items():
+        if "running" in k or "num_batches" in k:
+            assert torch.equal(val.cpu(), state[k]), k
+
+
 def test_predictor_on_a_non_canonical_model(dev):
     """predict.Predictor with n_txpcnn = 3: V_pred against the oracle at training=False, the mean trajectory equal to
     the cumulative sum of V_pred's means from the last observed position (1e-6 on the device's own V_pred, as
