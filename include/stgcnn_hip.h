@@ -640,6 +640,10 @@ int stg_selftest_mfma(const float *a, const float *b, int K, float *c, void *str
 /* N8 continued: the time-indexed score (inside the extern "C" block above) */
 #include "stgcnn_hip_score_time.h"
 
+/* N10: training windows harvested from the live tracks (added entry points, the ABI version stays),
+ * declared in stgcnn_hip_harvest.h like the timed score above */
+#include "stgcnn_hip_harvest.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -148,6 +148,13 @@ _SIGNATURES_SCORE_TIME = {
                                            c_f, c_f, c_l, c_l, c_l, c_l, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f, c_f, c_i,
                                            c_f, c_f]),
 }
+# ... and those of include/stgcnn_hip_harvest.h, included the same way
+_SIGNATURES_HARVEST = {
+    "stg_window_harvest": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i,
+                                 c_f]),
+    "stg_window_harvest_streams": (c_i, [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_f,
+                                         c_f, c_f, c_i, c_i, c_f]),
+}
 
 _lib = None
 
@@ -173,7 +180,7 @@ def lib():
                 "--offload-arch=gfx950) or `python -c 'import __graft_entry__ as g; g.build()'`. "
                 "There is no CPU or eager-PyTorch fallback for this path." % (LIB_PATH, CSRC))
         h = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in {**_SIGNATURES, **_SIGNATURES_SCORE_TIME}.items():
+        for name, (res, args) in {**_SIGNATURES, **_SIGNATURES_SCORE_TIME, **_SIGNATURES_HARVEST}.items():
             fn = getattr(h, name)
             fn.restype = res
             fn.argtypes = args

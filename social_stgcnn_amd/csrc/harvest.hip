@@ -1,0 +1,312 @@
+// harvest: training windows taken from the live tracks as they mature.  A track detected in each of
+// the last T_all = obs_len + pred_len pushes of its stream is one row of a reference TrajectoryDataset window (utils.py:
+// 130-165, with the window's future now known); the rows of one push, at least min_peds of them in ascending id order,
+// are one window, appended to a log in the layout DeviceWindows / stg_gather_windows read.
+//
+//   stg_window_harvest          one stream: ONE workgroup, behind stg_track_push of the same push.  It reads the track
+//                               state only (slot ids, presence bit 0, the ring row the push has just written), keeps its
+//                               own T_all-deep history, sorts the candidates by id (detections.hpp), places the window
+//                               and writes its rows.
+//   stg_window_harvest_streams  NS streams behind stg_track_push_streams, three launches that never wait for each other:
+//                               update + count (one workgroup per stream, honours pushed[b]); place (ONE workgroup: the
+//                               exclusive scan of the tick's row counts, the capacity test and the header's only
+//                               writer); write (one workgroup per stream).  The log is tick-major, stream-minor.
+//
+// THE LOG IS CLOSED BY ITS FIRST DROP: a window that does not fit (by windows or by rows) is counted in dropped_full and
+// from then on every window is, until the caller clears the header.  What the log holds is therefore always a prefix of
+// what the feed produced, and the capacity test of a tick is monotone in the stream index.
+// Integer work, float64 loads and one float32 conversion per element.  Plain C++ stores; LDS atomics on integer words
+// only.  No host synchronisation: everything is read when the kernels run, so the launches are captured with the push.
+#include "detections.hpp"
+#include "track_rule.hpp"
+
+namespace stg {
+
+constexpr int kHarvestThreads = 256;
+constexpr int kHarvestWaves = kHarvestThreads / kWave;
+
+// a ring row as the state holds it -> [0, n): every ring row is taken modulo its depth
+__device__ __forceinline__ int ring_row(int row, int n) { return (row % n + n) % n; }
+
+// Block-wide exclusive scan of v over the threads (thread order); every thread gets the block total in *total.  Called
+// by all kHarvestThreads threads (two barriers).
+__device__ __forceinline__ int block_scan(int v, int *total, int *wave_tot) {
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    int x = v;
+    for (int o = 1; o < kWave; o <<= 1) {
+        const int y = __shfl_up(x, o, kWave);
+        if (lane >= o) x += y;
+    }
+    if (lane == kWave - 1) wave_tot[wave] = x;
+    __syncthreads();
+    int before = 0, all = 0;
+    for (int w = 0; w < kHarvestWaves; ++w) {
+        const int c = wave_tot[w];
+        before += w < wave ? c : 0;
+        all += c;
+    }
+    __syncthreads();                    // wave_tot is reused by the next call
+    *total = all;
+    return before + x - v;
+}
+
+// One push of one stream's history by one workgroup, behind the track push: age the words, take presence and position
+// from the track state, and leave the candidates -- the slots with all T_all low bits set -- sorted by id in (key,
+// kidx = slot), n2 = det_sort_n(S) entries of LDS.  Returns (in every thread) their number, 0 when below min_peds;
+// `row` is the history's ring row of this push.  Ends on a barrier.
+__device__ __forceinline__ int harvest_update(const TrackView &tr, const HarvestState &hs, const HarvestDims &d,
+                                              int64_t *key, int32_t *kidx, int *wave_cnt, int &row) {
+    const int tid = threadIdx.x, nt = kHarvestThreads, S = d.S, T_all = d.T_all;
+    const uint32_t full = T_all >= 32 ? 0xffffffffu : (1u << T_all) - 1u;
+    const int pushes = hs.head[1];
+    const int trow = ring_row(tr.head_flags[0], d.T_obs);  // the track ring's row of this push
+    row = (ring_row(hs.head[0], T_all) + 1) % T_all;
+    const double *__restrict__ src = tr.ring + (int64_t)trow * S * 2;
+    double *__restrict__ dst = hs.ring + (int64_t)row * S * 2;
+    int c = 0, tot = 0;
+    for (int s0 = 0; s0 < S; s0 += nt) {
+        const int s = s0 + tid;
+        int64_t id = -1;
+        bool cand = false;
+        if (s < S) {
+            id = tr.slot_id[s];
+            uint32_t w = 0;                                  // a free slot has an empty word
+            if (id >= 0) {
+                w = (hs.word[s] << 1) & full;
+                if (tr.mask[s] & 1u) {                       // really detected in this push
+                    w |= 1u;
+                    dst[s * 2] = src[s * 2];
+                    dst[s * 2 + 1] = src[s * 2 + 1];
+                }
+            }
+            hs.word[s] = w;
+            cand = w == full;
+        }
+        const int r = block_rank<kHarvestThreads>(cand, c, &tot, wave_cnt);
+        if (cand) {                                          // (r < S: at most one candidate per slot)
+            key[r] = id;
+            kidx[r] = s;
+        }
+        c += tot;
+    }
+    __syncthreads();                                         // every thread has read head; key / kidx / ring are written
+    if (tid == 0) {
+        hs.head[0] = row;
+        hs.head[1] = pushes + 1;
+    }
+    if (c < d.min_peds) return 0;
+    const int n2 = det_sort_n(c);                            // (<= det_sort_n(S))
+    for (int p = c + tid; p < n2; p += nt) {
+        key[p] = INT64_MAX;
+        kidx[p] = -1;
+    }
+    __syncthreads();
+    det_sort(key, kidx, n2, tid, nt);
+    return c;
+}
+
+// The c rows of one window into the log from row `row0` on: row p is the slot slot_at(p), (2, T_all) float32 with column
+// 0 zero and column t = (float)(pos[t] - pos[t-1]), the subtraction in float64 on the rounded positions, oldest first.
+// Every store is checked against the log's capacity, every slot against S.
+template <class SlotAt>
+__device__ __forceinline__ void harvest_rows(const double *__restrict__ ring, const HarvestDims &d, const HarvestLog &log,
+                                             int64_t row0, int c, int row, SlotAt slot_at) {
+    const int S = d.S, T_all = d.T_all;
+    float *__restrict__ rel = log.rel_all;
+    for (int e = threadIdx.x; e < c * T_all; e += kHarvestThreads) {
+        const int p = e / T_all, t = e % T_all;
+        const int s = slot_at(p);
+        const int64_t r = row0 + p;
+        if (r < 0 || r >= log.cap_rows || s < 0 || s >= S) continue;
+        float dx = 0.0f, dy = 0.0f;
+        if (t > 0) {
+            const int now = (row + 1 + t) % T_all, before = (row + t) % T_all;   // step t is row - (T_all - 1 - t)
+            const double *a = ring + ((int64_t)now * S + s) * 2, *b = ring + ((int64_t)before * S + s) * 2;
+            dx = (float)(a[0] - b[0]);
+            dy = (float)(a[1] - b[1]);
+        }
+        rel[(r * 2) * T_all + t] = dx;
+        rel[(r * 2 + 1) * T_all + t] = dy;
+    }
+}
+
+// does a window of c rows fit behind (nw windows, nr rows)?  Never once a window has been dropped.
+__device__ __forceinline__ bool harvest_fits(const HarvestLog &log, int dropped, int64_t nw, int64_t nr, int c) {
+    return dropped == 0 && nw >= 0 && nr >= 0 && nw < log.cap_windows && nr + c <= log.cap_rows;
+}
+
+// ---- one stream ------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kHarvestThreads) void window_harvest_kernel(TrackView tr, HarvestState hs, HarvestDims d,
+                                                                         HarvestLog log, int stream_index) {
+    extern __shared__ __align__(16) unsigned char lds[];
+    int64_t *key = reinterpret_cast<int64_t *>(lds);
+    int32_t *kidx = reinterpret_cast<int32_t *>(key + det_sort_n(d.S));
+    __shared__ int wave_cnt[kHarvestWaves];
+    // the header as the push found it: read by every thread ahead of the barriers, written by thread 0 behind them
+    const int nw = log.header[0], nr = log.header[1], dropped = log.header[2];
+    const int push = hs.head[1];
+    int row;
+    const int c = harvest_update(tr, hs, d, key, kidx, wave_cnt, row);
+    if (c == 0) return;
+    const bool fits = harvest_fits(log, dropped, nw, nr, c);
+    if (fits) harvest_rows(hs.ring, d, log, nr, c, row, [&](int p) { return kidx[p]; });
+    if (threadIdx.x == 0) {
+        if (fits) {
+            log.win_start[nw + 1] = nr + c;
+            log.win_tag[nw * 2] = stream_index;
+            log.win_tag[nw * 2 + 1] = push;
+            log.header[0] = nw + 1;
+            log.header[1] = nr + c;
+        } else {
+            log.header[2] = dropped + 1;
+        }
+    }
+}
+
+// ---- NS streams: update + count, place, write --------------------------------------------------------------------------
+__global__ __launch_bounds__(kHarvestThreads) void harvest_update_streams_kernel(TrackView tr,
+                                                                                 const int32_t *__restrict__ pushed,
+                                                                                 HarvestState hs, HarvestDims d,
+                                                                                 HarvestWork work) {
+    extern __shared__ __align__(16) unsigned char lds[];
+    int64_t *key = reinterpret_cast<int64_t *>(lds);
+    int32_t *kidx = reinterpret_cast<int32_t *>(key + det_sort_n(d.S));
+    __shared__ int wave_cnt[kHarvestWaves];
+    const int b = blockIdx.x;
+    const HarvestWork mine = work.of_stream(b, d);
+    int c = 0;
+    if (pushed[b] != 0) {                                    // uniform over the block: no barrier is skipped halfway
+        int row;
+        c = harvest_update(tr.of_stream(b, d), hs.of_stream(b, d), d, key, kidx, wave_cnt, row);
+        for (int p = threadIdx.x; p < c; p += kHarvestThreads) mine.cand[p] = kidx[p];
+    }
+    if (threadIdx.x == 0) mine.count[0] = c;
+}
+
+// ONE workgroup: stream b's window (count[b] rows, 0 = none) goes behind the windows of the streams before it.  The
+// exclusive scan counts every window of the tick, placed or not, so the test is monotone: behind the first window that
+// does not fit none does.  The only writer of the header, of win_start and of win_tag.
+__global__ __launch_bounds__(kHarvestThreads) void harvest_place_kernel(const int32_t *__restrict__ head, HarvestDims d,
+                                                                        HarvestWork work, HarvestLog log, int NS) {
+    __shared__ int wave_tot[kHarvestWaves];
+    __shared__ int sums[3];                                  // windows placed, rows placed, windows dropped
+    const int tid = threadIdx.x;
+    const int nw0 = log.header[0], nr0 = log.header[1], dropped0 = log.header[2];
+    if (tid < 3) sums[tid] = 0;
+    __syncthreads();
+    int64_t base_r = 0, base_w = 0;
+    int placed = 0, rows = 0, drops = 0;
+    for (int b0 = 0; b0 < NS; b0 += kHarvestThreads) {
+        const int b = b0 + tid;
+        int c = b < NS ? work.count[b] : 0;
+        c = c < 0 ? 0 : (c > d.S ? d.S : c);
+        const int w = c > 0 ? 1 : 0;
+        int tot_r, tot_w;
+        const int before_r = block_scan(c, &tot_r, wave_tot);
+        const int before_w = block_scan(w, &tot_w, wave_tot);
+        const int64_t r0 = nr0 + base_r + before_r, wi = nw0 + base_w + before_w;
+        const bool fits = w && harvest_fits(log, dropped0, wi, r0, c);
+        if (b < NS) {
+            work.place[2 * b] = fits ? (int32_t)r0 : -1;
+            work.place[2 * b + 1] = fits ? (int32_t)wi : -1;
+        }
+        if (fits) {
+            log.win_start[wi + 1] = (int32_t)(r0 + c);
+            log.win_tag[wi * 2] = b;
+            log.win_tag[wi * 2 + 1] = head[2 * b + 1] - 1;   // (update has counted this push already)
+            placed += 1;
+            rows += c;
+        } else {
+            drops += w;
+        }
+        base_r += tot_r;
+        base_w += tot_w;
+    }
+    if (placed) {
+        atomicAdd(&sums[0], placed);
+        atomicAdd(&sums[1], rows);
+    }
+    if (drops) atomicAdd(&sums[2], drops);
+    __syncthreads();
+    if (tid == 0) {
+        log.header[0] = nw0 + sums[0];
+        log.header[1] = nr0 + sums[1];
+        log.header[2] = dropped0 + sums[2];
+    }
+}
+
+__global__ __launch_bounds__(kHarvestThreads) void harvest_write_streams_kernel(HarvestState hs, HarvestDims d,
+                                                                                HarvestWork work, HarvestLog log) {
+    const int b = blockIdx.x;
+    const HarvestWork mine = work.of_stream(b, d);
+    const int row0 = mine.place[0];
+    if (row0 < 0) return;
+    int c = mine.count[0];
+    c = c < 0 ? 0 : (c > d.S ? d.S : c);
+    const HarvestState st = hs.of_stream(b, d);
+    harvest_rows(st.ring, d, log, row0, c, ring_row(st.head[0], d.T_all), [&](int p) { return mine.cand[p]; });
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------
+static int harvest_args(const char *what, const TrackView &tr, const HarvestState &hs, const HarvestDims &d,
+                        const HarvestLog &log) {
+    STG_REQUIRE(d.S >= 1 && d.S <= STG_TRACK_MAX_SLOTS && d.T_obs >= 1 && d.T_all >= 2 && d.T_all <= STG_HARVEST_MAX_STEPS &&
+                    d.T_all - d.T_obs >= 1 && d.min_peds >= 1,
+                STG_EINVAL, "%s: bad sizes S=%d T_obs=%d T_all=%d min_peds=%d", what, d.S, d.T_obs, d.T_all, d.min_peds);
+    STG_REQUIRE(log.cap_windows >= 1 && log.cap_windows < INT32_MAX && log.cap_rows >= 1, STG_EINVAL,
+                "%s: bad capacities cap_windows=%d cap_rows=%d", what, log.cap_windows, log.cap_rows);
+    STG_REQUIRE(tr.slot_id && tr.mask && tr.ring && tr.head_flags && hs.word && hs.ring && hs.head && log.rel_all &&
+                    log.win_start && log.win_tag && log.header,
+                STG_EINVAL, "%s: null pointer", what);
+    return STG_OK;
+}
+
+static inline size_t harvest_lds(const HarvestDims &d) { return det_sort_lds(det_sort_n(d.S)); }
+
+}  // namespace stg
+
+extern "C" {
+
+int stg_window_harvest(const int64_t *slot_id, const uint32_t *mask, const double *ring, const int32_t *head_flags, int S,
+                       int T_obs, int T_all, int min_peds, int stream_index, uint32_t *h_word, double *h_ring,
+                       int32_t *h_head, float *rel_all, int32_t *win_start, int32_t *win_tag, int32_t *header,
+                       int cap_windows, int cap_rows, void *stream) {
+    const char *what = "stg_window_harvest";
+    const stg::TrackView tr{slot_id, mask, ring, head_flags};
+    const stg::HarvestState hs{h_word, h_ring, h_head};
+    const stg::HarvestDims d{S, T_obs, T_all, min_peds};
+    const stg::HarvestLog log{rel_all, win_start, win_tag, header, cap_windows, cap_rows};
+    const int rc = stg::harvest_args(what, tr, hs, d, log);
+    if (rc != STG_OK) return rc;
+    STG_REQUIRE(stream_index >= 0, STG_EINVAL, "%s: bad stream_index=%d", what, stream_index);
+    return stg::launch({what, dim3(1), dim3(stg::kHarvestThreads), stg::harvest_lds(d), stg::as_stream(stream), 64 * 1024},
+                       stg::window_harvest_kernel, tr, hs, d, log, stream_index);
+}
+
+int stg_window_harvest_streams(const int64_t *slot_id, const uint32_t *mask, const double *ring,
+                               const int32_t *head_flags, const int32_t *pushed, int NS, int S, int T_obs, int T_all,
+                               int min_peds, uint32_t *h_word, double *h_ring, int32_t *h_head, int32_t *work,
+                               float *rel_all, int32_t *win_start, int32_t *win_tag, int32_t *header, int cap_windows,
+                               int cap_rows, void *stream) {
+    const char *what = "stg_window_harvest_streams";
+    const stg::TrackView tr{slot_id, mask, ring, head_flags};
+    const stg::HarvestState hs{h_word, h_ring, h_head};
+    const stg::HarvestDims d{S, T_obs, T_all, min_peds};
+    const stg::HarvestLog log{rel_all, win_start, win_tag, header, cap_windows, cap_rows};
+    STG_REQUIRE(NS >= 1 && NS <= STG_TRACK_MAX_STREAMS, STG_EINVAL, "%s: bad size NS=%d", what, NS);
+    int rc = stg::harvest_args(what, tr, hs, d, log);
+    if (rc != STG_OK) return rc;
+    STG_REQUIRE(pushed && work, STG_EINVAL, "%s: null pointer", what);
+    const stg::HarvestWork wk = stg::HarvestWork::carve(work, NS, S);
+    hipStream_t st = stg::as_stream(stream);
+    rc = stg::launch({what, dim3(NS), dim3(stg::kHarvestThreads), stg::harvest_lds(d), st, 64 * 1024},
+                     stg::harvest_update_streams_kernel, tr, pushed, hs, d, wk);
+    if (rc != STG_OK) return rc;
+    rc = stg::launch({what, dim3(1), dim3(stg::kHarvestThreads), 0, st}, stg::harvest_place_kernel,
+                     (const int32_t *)h_head, d, wk, log, NS);
+    if (rc != STG_OK) return rc;
+    return stg::launch({what, dim3(NS), dim3(stg::kHarvestThreads), 0, st}, stg::harvest_write_streams_kernel, hs, d, wk,
+                       log);
+}
+
+}  // extern "C"

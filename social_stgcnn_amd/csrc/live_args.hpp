@@ -72,6 +72,45 @@ struct SceneOut {
     }
 };
 
+// ---- the window harvest (harvest.hip) ------------------------------------------------------------------
+// The sizes of a harvest: S slots, the push's T_obs, windows of T_all steps, at least min_peds rows each
+struct HarvestDims { int S, T_obs, T_all, min_peds; };
+
+// The push's state as the harvest reads it, behind that push: nothing of it is written
+struct TrackView {
+    const int64_t *slot_id; const uint32_t *mask; const double *ring; const int32_t *head_flags;
+    __device__ __forceinline__ TrackView of_stream(int64_t b, const HarvestDims &d) const {
+        return {slot_id + b * d.S, mask + b * d.S, ring + b * d.T_obs * d.S * 2, head_flags + 2 * b};
+    }
+};
+
+// The harvest's own history: word (S), ring (T_all,S,2), head (2) = {ring row of the last push, pushes since reset}
+struct HarvestState {
+    uint32_t *word; double *ring; int32_t *head;
+    __device__ __forceinline__ HarvestState of_stream(int64_t b, const HarvestDims &d) const {
+        return {word + b * d.S, ring + b * d.T_all * d.S * 2, head + 2 * b};
+    }
+};
+
+// What a tick's launches hand each other, one int32 array: cand (NS,S) the candidates' slots in id order, count (NS)
+// the rows of the stream's window (0: none), place (NS,2) = {first row in the log or -1, window index}
+struct HarvestWork {
+    int32_t *cand, *count, *place;
+    static __host__ __device__ __forceinline__ HarvestWork carve(int32_t *work, int64_t NS, int S) {
+        return {work, work + NS * S, work + NS * S + NS};
+    }
+    __device__ __forceinline__ HarvestWork of_stream(int64_t b, const HarvestDims &d) const {
+        return {cand + b * d.S, count + b, place + 2 * b};
+    }
+};
+
+// The log, one for all streams (no of_stream): rel_all (cap_rows,2,T_all), win_start (cap_windows + 1), win_tag
+// (cap_windows,2), header (3) = {n_windows, n_rows, dropped_full}
+struct HarvestLog {
+    float *rel_all; int32_t *win_start, *win_tag, *header;
+    int cap_windows, cap_rows;
+};
+
 // ---- host side ------------------------------------------------------------------------------------------------------
 // What every _streams entry point checks of its streams, under its own name `what`: NS, M_total and the strides.  The
 // entry points do not all answer alike, and each keeps its answer:

@@ -30,6 +30,40 @@ class DeviceWindows:
         self.rel_all = torch.from_numpy(np.ascontiguousarray(windows.seq_rel, dtype=np.float32)).to(self.device)
         self.win_start = torch.from_numpy(start).to(self.device)
 
+    @classmethod
+    def from_device(cls, rel_all, win_start, num_peds_host, obs_len):
+        """A dataset over windows that are on the device already, without a copy: rel_all float32 (R,2,T_all) and
+        win_start int32 (W+1,), contiguous device tensors (views are fine) in the layout above -- window w holds rows
+        win_start[w] .. win_start[w+1]-1 --, and num_peds_host, the W row counts on the host (they size the batches'
+        padding).  What frames.LiveWindows.snapshot() returns."""
+        if not (torch.is_tensor(rel_all) and rel_all.dtype == torch.float32 and rel_all.dim() == 3
+                and rel_all.shape[1] == 2 and rel_all.is_contiguous()):
+            raise ValueError("from_device: rel_all (R,2,T_all) float32, contiguous, expected")
+        if not (torch.is_tensor(win_start) and win_start.dtype == torch.int32 and win_start.dim() == 1
+                and win_start.is_contiguous()):
+            raise ValueError("from_device: win_start (W+1,) int32, contiguous, expected")
+        peds = np.asarray(num_peds_host)
+        if peds.ndim != 1 or peds.dtype.kind not in "iu" or len(peds) < 1 or len(peds) != win_start.numel() - 1:
+            raise ValueError("from_device: num_peds_host must hold the W >= 1 integer row counts of win_start (W+1,)")
+        if int(peds.min()) < 1 or int(peds.sum()) != rel_all.shape[0]:
+            raise ValueError("from_device: num_peds_host must be >= 1 and sum to the %d rows of rel_all"
+                             % rel_all.shape[0])
+        t_all = int(rel_all.shape[2])
+        if isinstance(obs_len, bool) or int(obs_len) != obs_len or not 1 <= int(obs_len) < t_all:
+            raise ValueError("from_device: obs_len must be an integer in [1, T_all = %d), got %r" % (t_all, obs_len))
+        if rel_all.device != win_start.device:
+            raise ValueError("from_device: rel_all and win_start are on different devices")
+        require_gpu(rel_all)
+        self = cls.__new__(cls)
+        self.device = rel_all.device
+        self.n_windows = len(peds)
+        self.t_all, self.t_obs = t_all, int(obs_len)
+        self.t_pred = t_all - self.t_obs
+        self.num_peds_host = peds.astype(np.int32)
+        self.v_max = int(peds.max())
+        self.rel_all, self.win_start = rel_all, win_start
+        return self
+
     def __len__(self):
         return self.n_windows
 

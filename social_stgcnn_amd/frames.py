@@ -32,6 +32,11 @@ stg_frame_scenes over a recording uploaded once, stg_track_push with the track s
     AssociateSpec      associate=AssociateSpec(gate, gate_new, max_miss) on the two live predictors: pushes carry
                        positions only, push(None, xy); a launch ahead of the push kernel gives every detection its track
                        id on the device (stg_associate); `.det_ids`, `.assoc_flags`
+    HarvestSpec        harvest=HarvestSpec(windows, rows, min_peds, pred_len) on the two live predictors: a launch behind
+                       the push kernel keeps every training window the tracks complete -- a track seen in each of the
+                       last obs_len + pred_len pushes is one row of a reference TrajectoryDataset window -- in a log on
+                       the device (stg_window_harvest); `.harvest` is the LiveWindows, whose snapshot()
+                       is a dataset.DeviceWindows for train.fine_tune
 
 The two live predictors are one core, _LivePredictor: the argument checks, the track state, the eager push and its
 capture (the push kernel ahead of predict.Predictor.capture_chain; the capture recipe itself is graphs.py).  Each class
@@ -171,6 +176,91 @@ class AssociateSpec(collections.namedtuple("AssociateSpec", "gate gate_new max_m
             raise ValueError("AssociateSpec: capacity must be None or an integer in [1, %d], got %r"
                              % (MAX_SLOTS, capacity))
         return super().__new__(cls, gate, gate_new, int(max_miss), None if capacity is None else int(capacity))
+
+
+MAX_WINDOW_STEPS = 32                  # STG_HARVEST_MAX_STEPS: a harvest word is 32 bits
+
+
+class HarvestSpec(collections.namedtuple("HarvestSpec", "windows rows min_peds pred_len")):
+    """Live pushes that also keep the training windows they complete: a track really detected in each
+    of the last obs_len + pred_len pushes is one row of a reference TrajectoryDataset window, and min_peds or more of
+    them (default 2: the reference's len > min_ped with min_ped = 1), in ascending id order, are one window, appended to
+    a log on the device that holds up to `windows` windows and `rows` rows (default windows * max_peds).  pred_len
+    defaults to the model's pred_seq_len.  The first window that does not fit closes the log until clear()."""
+    __slots__ = ()
+
+    def __new__(cls, windows, rows=None, min_peds=2, pred_len=None):
+        if not _is_int(windows, 1, (1 << 31) - 2):
+            raise ValueError("HarvestSpec: windows must be an integer in [1, 2^31 - 2], got %r" % (windows,))
+        if rows is not None and not _is_int(rows, 1, (1 << 31) - 1):
+            raise ValueError("HarvestSpec: rows must be None or an integer in [1, 2^31), got %r" % (rows,))
+        if not _is_int(min_peds, 1, MAX_SLOTS):
+            raise ValueError("HarvestSpec: min_peds must be an integer in [1, %d], got %r" % (MAX_SLOTS, min_peds))
+        if pred_len is not None and not _is_int(pred_len, 1, MAX_WINDOW_STEPS - 1):
+            raise ValueError("HarvestSpec: pred_len must be None or an integer in [1, %d], got %r"
+                             % (MAX_WINDOW_STEPS - 1, pred_len))
+        return super().__new__(cls, int(windows), None if rows is None else int(rows), int(min_peds),
+                               None if pred_len is None else int(pred_len))
+
+    def checked(self, obs_len, max_peds, pred_seq_len):
+        """The spec with rows and pred_len resolved, once it fits a predictor of obs_len observed steps."""
+        pred_len = int(pred_seq_len) if self.pred_len is None else self.pred_len
+        if obs_len < 2:
+            raise ValueError("HarvestSpec: obs_len=%d: the track state frees a slot after obs_len - 1 missed pushes, so "
+                             "with one observed step a slot changes its pedestrian without a gap" % obs_len)
+        if not 1 <= pred_len or obs_len + pred_len > MAX_WINDOW_STEPS:
+            raise ValueError("HarvestSpec: obs_len + pred_len = %d + %d must stay within %d steps"
+                             % (obs_len, pred_len, MAX_WINDOW_STEPS))
+        rows = self.windows * int(max_peds) if self.rows is None else self.rows
+        if rows >= 1 << 31:
+            raise ValueError("HarvestSpec: rows=%d must stay below 2^31" % rows)
+        return HarvestSpec(self.windows, rows, self.min_peds, pred_len)
+
+
+class LiveWindows:
+    """The windows a harvesting predictor has kept, on the device in dataset.DeviceWindows' own layout: rel_all float32
+    (rows,2,T_all), win_start int32 (windows+1,), win_tag int32 (windows,2) = (stream, that stream's push index since
+    its reset) and header int32 (3,) = {n_windows, n_rows, dropped_full}.  Append-only: pushes write behind what is
+    there, the first window that does not fit is counted in dropped_full and closes the log, clear() empties it."""
+
+    def __init__(self, spec, t_obs, device):
+        self.t_obs, self.t_all = int(t_obs), int(t_obs) + spec.pred_len
+        self.cap_windows, self.cap_rows = spec.windows, spec.rows
+        self.rel_all = torch.zeros((spec.rows, 2, self.t_all), device=device, dtype=torch.float32)
+        self.win_start = torch.zeros(spec.windows + 1, device=device, dtype=torch.int32)
+        self.win_tag = torch.zeros((spec.windows, 2), device=device, dtype=torch.int32)
+        self.header = torch.zeros(3, device=device, dtype=torch.int32)
+
+    def _args(self):
+        """the log as the harvest entry points take it"""
+        return (ptr(self.rel_all), ptr(self.win_start), ptr(self.win_tag), ptr(self.header), self.cap_windows,
+                self.cap_rows)
+
+    def counts(self):
+        """(n_windows, n_rows, dropped_full) as of the pushes enqueued so far: one synchronisation."""
+        return tuple(int(x) for x in self.header.cpu().tolist())
+
+    def snapshot(self):
+        """The windows kept so far as a dataset.DeviceWindows that views the log's first n_rows rows and n_windows + 1
+        offsets without copying (one synchronisation: the header and the offsets come back in one copy).  It stays
+        valid until clear(): later pushes only append behind it.  Raises while the log is empty."""
+        from .dataset import DeviceWindows
+        host = torch.cat((self.header, self.win_start)).cpu().numpy()
+        n_w, n_r = int(host[0]), int(host[1])
+        if n_w < 1:
+            raise ValueError("LiveWindows.snapshot: no window has been harvested yet")
+        start = host[3:3 + n_w + 1]
+        return DeviceWindows.from_device(self.rel_all[:n_r], self.win_start[:n_w + 1], np.diff(start), self.t_obs)
+
+    def tags(self):
+        """(n_windows, 2) int32 numpy: (stream, the stream's push index since its reset) of every window kept; one
+        synchronisation."""
+        host = torch.cat((self.header, self.win_tag.reshape(-1))).cpu().numpy()
+        return host[3:3 + 2 * int(host[0])].reshape(-1, 2).copy()
+
+    def clear(self):
+        """Empty the log (the streams' histories go on: the next window is the first of the new log)."""
+        self.header.zero_()
 
 
 def _tick_time(t, what):
@@ -384,15 +474,21 @@ class _LivePredictor:
         _wrap(outs, r, static)   the result tuple of outs and the chain's Prediction r (static: a captured push)
         _still()                 make warm-up pushes harmless; returns the (tensor, saved copy) pairs to put back after
         _associate()             with associate=: launch its association kernel on the staging buffers, ahead of _push
+        _harvest()               with harvest=: launch its window harvest on the track state, behind _push
 
     and `seed_dev`, the (1,) int64 device tensor the sampler reads its seed from."""
     assoc = None                         # the AssociateSpec; None: ids come with the pushes
     _score_pushed = None                 # the (NS,) int32 `pushed` words a timed score launch reads; None: one stream
 
+    harvest = None                       # the LiveWindows of a predictor made with harvest=; None without
+
     def __init__(self, model, k, obs_len, capacity, max_peds, max_detections, decimals, risk=None, keep_samples=True,
-                 tracks=None, score=None, time=None, associate=None):
+                 tracks=None, score=None, time=None, associate=None, harvest=None):
         self.model = model
         self.k = int(k)
+        if harvest is not None and time is not None:
+            raise ValueError("harvest= together with time= is not supported: a timed push is not one frame of a "
+                             "window (DESIGN.md 8)")
         if associate is not None and time is not None:
             raise ValueError("associate= together with time= is not supported: a velocity per tick and a gate that "
                              "grows with the gap are a change of their own (DESIGN.md 8)")
@@ -444,6 +540,12 @@ class _LivePredictor:
             raise ValueError("max_detections must be in [1, %d], got %r" % (MAX_DETECTIONS, max_detections))
         if self.v < 1:
             raise ValueError("max_peds must be >= 1, got %r" % (max_peds,))
+        if harvest is not None:
+            if not isinstance(harvest, HarvestSpec):
+                harvest = HarvestSpec(*harvest) if isinstance(harvest, (tuple, list)) else HarvestSpec(harvest)
+            harvest = harvest.checked(self.t_obs, self.v, model.pred_seq_len)
+        self.harvest_spec = harvest
+        self._harvest_state = None
 
     def _track_state(self, lead=()):
         """Look the model's device up (every argument has been checked by now) and allocate the track state, one set
@@ -493,6 +595,15 @@ class _LivePredictor:
                 self._score_state = ops.score_state(lead[0] if lead else 1, self.model.pred_seq_len, self.v, self.k,
                                                     dev, spec.best_of_k, len(spec.levels))
             self._thr = torch.tensor(spec.thresholds, dtype=torch.float32).to(dev) if spec.levels else None
+        if self.harvest_spec is not None:
+            # the harvest's own history, one per index of `lead` -- presence words, a T_all-deep position ring, {ring row,
+            # pushes since reset} --, the ONE log of the predictor and, for many streams, the launches' scratch
+            self.harvest = LiveWindows(self.harvest_spec, self.t_obs, dev)
+            self.h_word = torch.zeros(lead + (self.s,), device=dev, dtype=torch.int32)
+            self.h_ring = torch.zeros(lead + (self.harvest.t_all, self.s, 2), device=dev, dtype=torch.float64)
+            self.h_head = torch.zeros(lead + (2,), device=dev, dtype=torch.int32)
+            self._harvest_state = (self.h_word, self.h_ring, self.h_head)
+            self._harvest_work = torch.zeros(lead[0] * (self.s + 3), device=dev, dtype=torch.int32) if lead else None
         return dev
 
     @property
@@ -565,11 +676,34 @@ class _LivePredictor:
         writes the ids the push kernel behind it reads."""
         check(getattr(lib(), name)(*det, *map(ptr, self._assoc_state), *self._assoc_args, stream_ptr()), name)
 
+    def _reset_harvest(self, at=None):
+        """Empty the harvest history everywhere, or at the stream indices `at`; the log is left alone.  (A ring row is
+        read only where the word says detected.)"""
+        if self._harvest_state is None:
+            return
+        for x in (self.h_word, self.h_head):
+            if at is None:
+                x.zero_()
+            else:
+                x.index_fill_(0, at, 0)
+
+    def _launch_harvest(self, name, streams, tag, work):
+        """The harvest entry point `name` behind the push: the track state (read only), `streams` (what a _streams
+        entry point is told of its streams), the sizes, `tag` (the lone entry point's stream index), the history, `work`
+        (the _streams entry point's scratch) and the log."""
+        h = self.harvest
+        check(getattr(lib(), name)(*map(ptr, self._state), *streams, self.s, self.t_obs, h.t_all,
+                                   self.harvest_spec.min_peds, *tag, *map(ptr, self._harvest_state), *work, *h._args(),
+                                   stream_ptr()), name)
+
     def _front(self, outs):
-        """The launches that turn the staged detections into the scene: with associate= the association, then the push."""
+        """The launches that turn the staged detections into the scene: with associate= the association, then the push;
+        with harvest= the window harvest behind it, which reads the state the push has left."""
         if self.assoc is not None:
             self._associate()
         self._push(outs)
+        if self.harvest_spec is not None:
+            self._harvest()
 
     def _launch_push(self, name, det, outs, n_out, *tail):
         """The push kernel `name` on the detections `det` (its leading arguments) and the track state, or under a
@@ -626,7 +760,8 @@ class _LivePredictor:
         """Capture ONE linear graph: the push kernel -> observed_inputs -> forward -> stg_sample_trajectories on static
         buffers, the seed read from `seed_dev` (Predictor.capture_chain).  Returns replay(*det, seed=None) -> the
         result on the static outputs, overwritten by the next replay; the detections are staged outside the graph.
-        Warm-up and capture leave the track state as it was, and with it the score records and totals."""
+        Warm-up and capture leave the track state as it was, and with it the score records and totals, the harvest
+        history and the harvested windows."""
         outs = self._outs()
         saved = self._still()
         scored = None
@@ -685,12 +820,16 @@ class FramePredictor(_LivePredictor):
     one launch ahead of the push kernel (inside the captured graph), gives every detection its track id in the staging
     buffer the push and the score read; the returned ids are those track ids, `.det_ids` (M,) the id of every detection
     of the last push in the caller's order, `.assoc_flags` (1,) int32 the association's flags (ASSOC_FULL).  Ids given
-    with associate=, or None without it, are refused.  Not together with time=."""
+    with associate=, or None without it, are refused.  Not together with time=.
+    harvest: a HarvestSpec -- every push also keeps the training window it completes, if any (stg_window_harvest, one
+    launch behind the push kernel, inside the captured graph; it reads the track state only, so it goes with tracks=,
+    associate=, risk= and score=): `.harvest` is the LiveWindows log, its windows tagged (0, push index since reset()).
+    reset() empties the harvest history and leaves the log.  Not together with time=."""
 
     def __init__(self, model, k=20, obs_len=8, capacity=1024, max_peds=128, max_detections=1024, decimals=4,
-                 risk=None, keep_samples=True, tracks=None, score=None, time=None, associate=None):
+                 risk=None, keep_samples=True, tracks=None, score=None, time=None, associate=None, harvest=None):
         super().__init__(model, k, obs_len, capacity, max_peds, max_detections, decimals, risk, keep_samples, tracks,
-                         score, time, associate)
+                         score, time, associate, harvest)
         dev, m = self._track_state(), self.m_max
         self.det_id = torch.zeros(m, device=dev, dtype=torch.int64)
         self.det_xy = torch.zeros((m, 2), device=dev, dtype=torch.float64)
@@ -702,12 +841,13 @@ class FramePredictor(_LivePredictor):
 
     def reset(self):
         """Forget every track (the next obs_len - 1 pushes return empty scenes), and with score= the pending records
-        and the running totals."""
+        and the running totals; with harvest= the harvest history, not the log."""
         self.slot_id.fill_(-1)
         for x in self._forget:
             x.zero_()
         self._reset_assoc()
         self._score_reset()
+        self._reset_harvest()
 
     @property
     def det_ids(self):
@@ -717,6 +857,9 @@ class FramePredictor(_LivePredictor):
 
     def _associate(self):
         self._launch_associate("stg_associate", (ptr(self.det_id), ptr(self.det_xy), ptr(self.det_count), self.m_max))
+
+    def _harvest(self):
+        self._launch_harvest("stg_window_harvest", (), (0,), ())
 
     def _stage(self, ids, xy, seed, t=None):
         """Copy one frame of detections (host arrays or device tensors) into the device buffers the push reads, and
@@ -783,6 +926,10 @@ class FramePredictor(_LivePredictor):
             state += self._assoc_state
         if self._score_state is not None:                    # an empty push is a push: it scores and enqueues
             state += tuple(x for x in self._score_state if x is not None)
+        if self._harvest_state is not None:
+            # an empty push ages the harvest words and moves its ring row; it has no candidates, so of the log only the
+            # header is kept (its rows, offsets and tags are written for a window alone)
+            state += self._harvest_state + (self.harvest.header,)
         saved = [(x, x.clone()) for x in state]
         self.det_count.zero_()
         return saved
@@ -911,13 +1058,16 @@ class StreamsPredictor(_LivePredictor):
     Not together with score=ScoreSpec(...); score=predict.TimedScoreSpec(...) as in FramePredictor
     (stg_score_push_streams_timed, one workgroup per stream, every stream on its own clock): at pending 128, 128
     pedestrians, k = 20 and 12 steps the records hold about 41 MB per stream, 2.6 GB for 64 streams (7.5 MB per stream
-    with best_of_k=False)."""
+    with best_of_k=False).
+    harvest: a HarvestSpec for all streams together, as in FramePredictor (stg_window_harvest_streams: three launches
+    behind the push launch): ONE log, `.harvest`, in which a tick's windows land in stream order, each tagged (stream,
+    that stream's push index since its reset); a stream not pushed keeps its harvest history bit for bit."""
 
     def __init__(self, model, streams, k=20, obs_len=8, capacity=1024, max_peds=128, max_detections=1024, decimals=4,
                  max_total_detections=None, block_threads=0, risk=None, keep_samples=True, tracks=None, score=None,
-                 time=None, associate=None):
+                 time=None, associate=None, harvest=None):
         super().__init__(model, k, obs_len, capacity, max_peds, max_detections, decimals, risk, keep_samples, tracks,
-                         score, time, associate)
+                         score, time, associate, harvest)
         if not _is_int(streams, 1, MAX_STREAMS):
             raise ValueError("streams must be an integer in [1, %d], got %r" % (MAX_STREAMS, streams))
         self.ns = int(streams)
@@ -968,13 +1118,14 @@ class StreamsPredictor(_LivePredictor):
     def reset(self, streams=None):
         """Forget every track of all streams, or of the listed stream indices only (their next obs_len - 1 pushes
         return empty scenes; the other streams go on).  With score= their pending records and running totals are
-        cleared with them."""
+        cleared with them; with harvest= their harvest history, not the log."""
         if streams is None:
             self.slot_id.fill_(-1)
             for x in self._state[1:]:
                 x.zero_()
             self._reset_assoc()
             self._score_reset()
+            self._reset_harvest()
             return
         idx = [int(x) for x in (streams if isinstance(streams, (list, tuple, np.ndarray, range)) else [streams])]
         for x in idx:
@@ -988,6 +1139,7 @@ class StreamsPredictor(_LivePredictor):
             x.index_fill_(0, at, 0)
         self._reset_assoc(at)
         self._score_reset(at)
+        self._reset_harvest(at)
 
     @property
     def det_ids(self):
@@ -998,6 +1150,10 @@ class StreamsPredictor(_LivePredictor):
 
     def _associate(self):
         self._launch_associate("stg_associate_streams", (*self._det.values(), self.ns, self.m_max))
+
+    def _harvest(self):
+        self._launch_harvest("stg_window_harvest_streams", (ptr(self.pushed_dev), self.ns), (),
+                             (ptr(self._harvest_work),))
 
     def _wait_host(self):
         """The pinned buffer is rewritten only after the previous tick's copy has left it."""

@@ -7,6 +7,7 @@ trajectories for every pedestrian tracked over the last obs_seq_len frames.
                                                [--step TICKS [--max_dt D] [--history R] [--max_peds V]
                                                 [--score [--pending N]]]
                                                [--associate GATE[,GATE_NEW[,MAX_MISS]] [--max_peds V]]
+                                               [--harvest WINDOWS [--harvest_out FILE.npz] [--max_peds V]]
                                                --out preds.npz
 
 DIR is a checkpoint directory in the reference's layout (args.pkl and val_best.pth, as social_stgcnn_amd.test reads
@@ -42,6 +43,12 @@ rows in file order, through a captured frames.FramePredictor(associate=frames.As
 detection its track id on the device.  The .npz holds one entry per push with at least --min_peds
 pedestrians, padded to the largest scene (at most --max_peds), its ids the assigned track ids, and assoc_ids (M,) int64:
 the assigned id of every row of the recording, in file order.  Not together with --step or --radius / --zones.
+
+--harvest WINDOWS pushes every distinct frame number through a captured frames.FramePredictor(harvest=
+frames.HarvestSpec(WINDOWS)), which also keeps the training windows the tracks complete (the windows of
+data.load_windows over the same file, in order).  The .npz holds one entry per push with at least --min_peds pedestrians;
+--harvest_out FILE.npz gets the windows: seq_rel (R,2,T) float32, num_peds (W,), tags (W,2) = (0, push index) and
+dropped_full.  Not together with --step, --associate or --radius / --zones.
 """
 import argparse
 import os
@@ -51,7 +58,8 @@ import numpy as np
 import torch
 
 from . import data
-from .frames import AssociateSpec, FramePredictor, TimeRule, TrackRule, predict_recording, score_summary, sorted_rows
+from .frames import (AssociateSpec, FramePredictor, HarvestSpec, TimeRule, TrackRule, predict_recording, score_summary,
+                     sorted_rows)
 from .model import social_stgcnn
 from .predict import RiskSpec, TimedScoreSpec
 from .trainer import load_checkpoint, load_pickle
@@ -87,6 +95,11 @@ def build_parser():
                    help="with --score: record rows kept (at least pushes per step x pred_seq_len)")
     p.add_argument("--associate", default=None, metavar="GATE[,GATE_NEW[,MAX_MISS]]",
                    help="ignore the id column: associate the detections to tracks on the device (assoc_ids array)")
+    p.add_argument("--harvest", type=int, default=None, metavar="WINDOWS",
+                   help="push the recording frame by frame and keep up to this many of the training windows its tracks "
+                        "complete (not with --step, --associate or --radius / --zones)")
+    p.add_argument("--harvest_out", default=None, metavar="FILE.npz",
+                   help="with --harvest: write the harvested windows (seq_rel, num_peds, tags) here")
     p.add_argument("--out", required=True, help="output .npz")
     # a rectangle may begin with a negative coordinate: "-1,-1,1,1" is a value, not an option
     p._negative_number_matcher = re.compile(r"^-[0-9.][0-9.,eE+-]*$")
@@ -198,8 +211,59 @@ def predict_associated(model, rows, associate, k=20, seed=0, min_peds=1, tracks=
     return res
 
 
+def check_harvest_args(a):
+    """The refusals of --harvest / --harvest_out, ahead of anything that needs the device."""
+    if a.harvest is None:
+        if a.harvest_out is not None:
+            raise ValueError("--harvest_out needs --harvest WINDOWS")
+        return
+    if a.step is not None:
+        raise ValueError("--harvest does not go together with --step: a timed push is not one frame of a window")
+    if a.associate is not None or a.radius is not None or a.zones is not None:
+        raise ValueError("--harvest does not go together with --associate or --radius / --zones")
+    if a.harvest < 1:
+        raise ValueError("--harvest: at least one window, got %d" % a.harvest)
+
+
+def predict_harvested(model, rows, harvest, k=20, seed=0, min_peds=1, tracks=None, max_peds=128):
+    """Every distinct frame number of `rows` pushed through ONE captured FramePredictor(harvest=...) -> (a dict of host
+    arrays, one entry per push whose scene holds at least min_peds pedestrians, and the dict of what the run harvested:
+    seq_rel (R,2,T_all) float32, num_peds (W,) int32, tags (W,2) int32 = (0, push index), dropped_full)."""
+    frames, fs, ids, xy = sorted_rows(rows)
+    m_max = max(1, int(np.diff(fs).max()) if len(frames) else 1)
+    fp = FramePredictor(model, k=k, obs_len=model.seq_len, capacity=max(1024, m_max), max_peds=max_peds,
+                        max_detections=m_max, tracks=tracks, harvest=harvest)
+    replay = fp.capture()
+    names = ("frame", "ids", "num_peds", "mean", "samples") + (() if tracks is None else ("seen",))
+    keep = {name: [] for name in names}
+    for f in range(len(frames)):
+        out = replay(ids[fs[f]:fs[f + 1]], xy[fs[f]:fs[f + 1]], seed=seed + f)
+        n = int(out.num_peds.item())
+        if n < min_peds:
+            continue
+        for name, x in zip(names, (frames[f], out.ids, np.int32(n), out.mean, out.samples, fp.seen)):
+            keep[name].append(x.cpu().numpy() if torch.is_tensor(x) else x)
+    v = max(1, max(keep["num_peds"], default=0))
+    p = model.pred_seq_len
+    empty = dict(frame=np.zeros(0), ids=np.zeros((0, v), np.int64), num_peds=np.zeros(0, np.int32),
+                 mean=np.zeros((0, p, v, 2), np.float32), samples=np.zeros((0, fp.k, p, v, 2), np.float32),
+                 seen=np.zeros((0, v), np.int32))
+    res = {name: np.stack(x) if x else empty[name] for name, x in keep.items()}
+    res.update(ids=res["ids"][:, :v], mean=res["mean"][:, :, :v],
+               samples=np.ascontiguousarray(np.moveaxis(res["samples"], 0, 1)[:, :, :, :v]))
+    if tracks is not None:
+        res["seen"] = res["seen"][:, :v]
+    log = fp.harvest
+    n_w, n_r, dropped = log.counts()
+    start = log.win_start[:n_w + 1].cpu().numpy()
+    kept = dict(seq_rel=log.rel_all[:n_r].cpu().numpy(), num_peds=np.diff(start).astype(np.int32), tags=log.tags(),
+                dropped_full=np.int32(dropped))
+    return res, kept
+
+
 def main(argv=None):
     a = build_parser().parse_args(argv)
+    check_harvest_args(a)
     if not torch.cuda.is_available():
         raise RuntimeError("social_stgcnn_amd.predict_frames needs a GPU (MI355X)")
     model = load_model(a.checkpoint, torch.device("cuda", torch.cuda.current_device()))
@@ -211,6 +275,16 @@ def main(argv=None):
     if a.score and (a.step is None or a.associate is not None):
         raise ValueError("--score needs --step (and does not go with --associate): the records it keeps are indexed "
                          "by time")
+    if a.harvest is not None:
+        res, kept = predict_harvested(model, rows, HarvestSpec(a.harvest), a.ksteps, a.seed, a.min_peds, tracks,
+                                      a.max_peds)
+        np.savez(a.out, **res)
+        if a.harvest_out is not None:
+            np.savez(a.harvest_out, **kept)
+        print("%d pushes with a scene, up to %d pedestrians -> %s; %d windows (%d rows) harvested, %d dropped%s"
+              % (len(res["frame"]), res["ids"].shape[1], a.out, len(kept["num_peds"]), len(kept["seq_rel"]),
+                 int(kept["dropped_full"]), "" if a.harvest_out is None else " -> " + a.harvest_out))
+        return
     if a.associate is not None:
         if a.step is not None or a.radius is not None or a.zones is not None:
             raise ValueError("--associate does not go together with --step or --radius / --zones")

@@ -65,6 +65,28 @@ def fit(model, train_ds, val_ds, checkpoint, batch_size=128, num_epochs=250, lr=
     return checkpoint.metrics, checkpoint.constant_metrics
 
 
+def fine_tune(model, ds, epochs, batch_size=128, lr=0.01, clip_grad=None, generator=None, orders=None):
+    """fit's training half alone, for windows that are on the device already (frames.LiveWindows.snapshot(), or any
+    dataset.DeviceWindows): a Trainer and an EpochRunner over `ds`, `epochs` times
+        order = orders(e), or ds.shuffled_order(generator)
+        loss  = runner.train_epoch(order)                 captured group steps (train.py:28-79)
+    with no validation set, no scheduler and no checkpoint files.  Returns the per-epoch train losses, each read back
+    once (the only host synchronisations besides the first epoch's captures).  The model is left in training mode, as
+    fit leaves it; a live predictor switches to eval mode for its own pushes."""
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        raise NotImplementedError("fine_tune() trains on one GPU; drive Trainer / EpochRunner per rank for data "
+                                  "parallelism")
+    if isinstance(epochs, bool) or int(epochs) != epochs or int(epochs) < 0:
+        raise ValueError("fine_tune: epochs must be an integer >= 0, got %r" % (epochs,))
+    trainer = Trainer(model, lr=lr, clip_grad=clip_grad)
+    runner = EpochRunner(trainer, ds, batch_size)
+    losses = []
+    for epoch in range(int(epochs)):
+        order = _device_order(orders(epoch), ds) if orders is not None else ds.shuffled_order(generator)
+        losses.append(float(runner.train_epoch(order)))
+    return losses
+
+
 def build_parser():
     """train.py:125-154's 15 flags (same names, types, defaults) + --datasets, --checkpoints, --seed"""
     p = argparse.ArgumentParser(description="Train Social-STGCNN on one ETH/UCY split (train.py on the device).")

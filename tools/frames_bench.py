@@ -7,6 +7,8 @@
     python tools/frames_bench.py --cases score [--streams 1,64,600] [--ticks 200]
     python tools/frames_bench.py --cases associate [--streams 1,64,600] [--ticks 200] [--associate 1.0,2.0,0]
                                  [--no-lone]
+    python tools/frames_bench.py --cases harvest [--streams 1,64,600] [--ticks 200] [--pushes 2000]
+    python tools/frames_bench.py --harvest ...          the latency and streams cases with harvest=HarvestSpec(...)
     python tools/frames_bench.py --tracks 2,2 ...       every case under frames.TrackRule(2, 2) (the *_rule kernels)
     python tools/frames_bench.py --time 10,10 ...       the latency, streams and score cases on timestamped pushes
                                                         (frames.TimeRule(10, history=--history), stg_track_push_timed):
@@ -40,6 +42,11 @@
              crowds_zara01 and students003, a captured FramePredictor with score=ScoreSpec() fed the recording's own ids
              and one fed none: best-of-K ADE / FDE of both, and the share of wrong links (a detection whose recorded id
              was in the previous push and whose assigned id is not the one that pedestrian had then).
+
+  harvest    the window harvest: the latency case (students001, max_peds 128) and the streams case at
+             NS = 1, 64 and 600 (or --streams), each with and without harvest=HarvestSpec(...) sized so that the log never
+             fills (one window per stream and tick, 32 rows each): p50 / p90 of both, the difference, and what the log
+             holds at the end.  No yardstick.
 
 Kernel times come from a separate run under the profiler (tracing slows the host):
     rocprofv3 --kernel-trace --stats -d OUT -o frames -- python tools/frames_bench.py --cases latency --pushes 500
@@ -110,11 +117,18 @@ def timed_pushes(rows, step, up):
     return out
 
 
-def latency_case(split, rec, max_peds, k, n_push, dev, warmup=50, tracks=None, timed=None):
+def harvest_spec(windows):
+    """A log that `windows` windows of up to 32 rows never fill."""
+    from social_stgcnn_amd import frames
+    return frames.HarvestSpec(windows, rows=32 * windows)
+
+
+def latency_case(split, rec, max_peds, k, n_push, dev, warmup=50, tracks=None, timed=None, harvest=False):
     from social_stgcnn_amd import data, frames
     rows = data.read_file(os.path.join(DATA, rec))
     pushes = pushes_of(rows) if timed is None else timed_pushes(rows, *timed[:2])
-    fp = frames.FramePredictor(model_for(split, dev), k=k, max_peds=max_peds, **tracks_kw(tracks, timed))
+    kw = {"harvest": harvest_spec(warmup + n_push)} if harvest else {}
+    fp = frames.FramePredictor(model_for(split, dev), k=k, max_peds=max_peds, **tracks_kw(tracks, timed), **kw)
     push = fp.capture()
     times, peds = [], []
     for i in range(warmup + n_push):
@@ -134,7 +148,8 @@ def latency_case(split, rec, max_peds, k, n_push, dev, warmup=50, tracks=None, t
             "p50_ms": round(float(np.percentile(ms, 50)), 4), "p90_ms": round(float(np.percentile(ms, 90)), 4),
             "mean_ms": round(float(ms.mean()), 4), "frames_per_s_p50": round(1e3 / float(np.percentile(ms, 50)), 1),
             "mean_peds": round(float(peds.mean()), 2), "max_peds_seen": int(peds.max()),
-            **({} if tracks is None else {"tracks": list(tracks)}), **({} if timed is None else {"time": list(timed)})}
+            **({} if tracks is None else {"tracks": list(tracks)}), **({} if timed is None else {"time": list(timed)}),
+            **({"harvest": list(fp.harvest.counts())} if harvest else {})}
 
 
 def recording_case(split, rec, k, dev, tracks=None):
@@ -170,7 +185,7 @@ def _stream_sequences(ns, n, timed=None):
 
 
 def streams_case(ns, k, n_ticks, dev, block=0, lone=True, max_peds=128, warmup=20, risk="none", tracks=None,
-                 score=None, timed=None, associate=None):
+                 score=None, timed=None, associate=None, harvest=False):
     from social_stgcnn_amd import frames
     model = model_for("univ", dev)
     seq = _stream_sequences(ns, warmup + n_ticks, timed)
@@ -183,6 +198,8 @@ def streams_case(ns, k, n_ticks, dev, block=0, lone=True, max_peds=128, warmup=2
         kw = dict(risk=RiskSpec(0.5, np.array([[-1, -1, 1, 1], [0, 0, 4, 3], [-50, -50, 50, 50]], np.float32)),
                   keep_samples=risk == "samples")
     kw.update(tracks_kw(tracks, timed))
+    if harvest:
+        kw["harvest"] = harvest_spec(ns * (warmup + n_ticks))
     if associate is not None:
         kw["associate"] = associate
         seq = [[(None, xy) for _, xy in q] for q in seq]
@@ -212,6 +229,8 @@ def streams_case(ns, k, n_ticks, dev, block=0, lone=True, max_peds=128, warmup=2
         res["assoc_full"] = int((sp.assoc_flags != 0).sum())
     if tracks is not None:
         res["tracks"] = list(tracks)
+    if harvest:
+        res["harvest"] = list(sp.harvest.counts())               # windows, rows, dropped_full
     if timed is not None:
         res["time"] = list(timed)
         res["state_mb_per_stream"] = round(sum(x[0].numel() * x.element_size() for x in sp._state) / 1e6, 3)
@@ -303,6 +322,8 @@ def main():
     ap.add_argument("--history", type=int, default=96, help="with --time: samples kept per track")
     ap.add_argument("--pending", type=int, default=128,
                     help="with --time and the score case: record rows per stream (predict.TimedScoreSpec)")
+    ap.add_argument("--harvest", action="store_true",
+                    help="the latency and streams cases with harvest=HarvestSpec(...), sized so that the log never fills")
     ap.add_argument("--associate", default="1.0,2.0,0", metavar="GATE[,GATE_NEW[,MAX_MISS]]",
                     help="the AssociateSpec of the associate case")
     a = ap.parse_args()
@@ -318,8 +339,8 @@ def main():
     if "latency" in cases:
         for split, rec, v in (("eth", "eth_test/biwi_eth.txt", 32), ("eth", "eth_test/biwi_eth.txt", 128),
                               ("univ", "univ_test/students001.txt", 128)):
-            print(json.dumps(latency_case(split, rec, v, a.k, a.pushes, dev, tracks=tracks, timed=timed)),
-                  flush=True)
+            print(json.dumps(latency_case(split, rec, v, a.k, a.pushes, dev, tracks=tracks, timed=timed,
+                                          harvest=a.harvest)), flush=True)
     if "recording" in cases:
         for split, rec in TEST_RECORDINGS:
             print(json.dumps(recording_case(split, rec, a.k, dev, tracks)), flush=True)
@@ -333,6 +354,19 @@ def main():
             on.update({"case": "score", "tick_p50_ms_without": off["tick_p50_ms"],
                        "tick_p90_ms_without": off["tick_p90_ms"],
                        "score_cost_p50_ms": round(on["tick_p50_ms"] - off["tick_p50_ms"], 4)})
+            print(json.dumps(on), flush=True)
+    if "harvest" in cases:
+        lat = [latency_case("univ", "univ_test/students001.txt", 128, a.k, a.pushes, dev, tracks=tracks, harvest=h)
+               for h in (False, True)]
+        lat[1].update({"case": "harvest_latency", "p50_ms_without": lat[0]["p50_ms"], "p90_ms_without": lat[0]["p90_ms"],
+                       "harvest_cost_p50_ms": round(lat[1]["p50_ms"] - lat[0]["p50_ms"], 4)})
+        print(json.dumps(lat[1]), flush=True)
+        for ns in (int(n) for n in (a.streams if a.streams != "1,8,64,256,600" else "1,64,600").split(",")):
+            off = streams_case(ns, a.k, a.ticks, dev, 0, False, tracks=tracks)
+            on = streams_case(ns, a.k, a.ticks, dev, 0, False, tracks=tracks, harvest=True)
+            on.update({"case": "harvest", "tick_p50_ms_without": off["tick_p50_ms"],
+                       "tick_p90_ms_without": off["tick_p90_ms"],
+                       "harvest_cost_p50_ms": round(on["tick_p50_ms"] - off["tick_p50_ms"], 4)})
             print(json.dumps(on), flush=True)
     if "associate" in cases:
         from social_stgcnn_amd.frames import AssociateSpec
@@ -353,7 +387,7 @@ def main():
             for ns in (int(n) for n in a.streams.split(",")):
                 for mode in a.risk.split(","):
                     print(json.dumps(streams_case(ns, a.k, a.ticks, dev, block, not a.no_lone, risk=mode,
-                                                  tracks=tracks, timed=timed)),
+                                                  tracks=tracks, timed=timed, harvest=a.harvest)),
                           flush=True)
 
 
