@@ -526,7 +526,7 @@ int stg_sample_risk(const float *pred, int64_t p_sn, int64_t p_sf, int64_t p_sp,
  *     first min(count, M_max) detections of the push, rounded as N6 rounds (scale) and converted to float32 -- taken
  *     from the detections, whatever the track state did with them.  For a matched pedestrian v < num_peds, in float32
  *     as written (no fused multiply-add), dx, dy = mean_h - truth, (cxx, cxy, cyy) = C_h:
- *       err = sqrtf(dx*dx + dy*dy)          det = cxx*cyy - cxy*cxy
+ *       err = sqrtf(dx*dx + dy*dy)          det = fmaxf(cxx*cyy - cxy*cxy, (cxx*cyy) * 2^-15)
  *       d2  = (cyy*(dx*dx) - 2*cxy*dx*dy + cxx*(dy*dy)) / det
  *       nll = 0.5*d2 + 0.5*log(det) + log(2 pi)   (log(det): the correctly rounded float32 logarithm)
  *       best = min_k |samples[k,h] - truth|;   acc[k] += |samples[k,h] - truth|, acc_mean += err, steps += 1

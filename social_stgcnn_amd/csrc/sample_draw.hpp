@@ -14,12 +14,16 @@ struct Chol2 {
     float l00, l10, l11;
 };
 
-// chol([[sx^2, rho sx sy], [rho sx sy, sy^2]]) in the order torch.linalg.cholesky evaluates it
+// chol([[sx^2, rho sx sy], [rho sx sy, sy^2]]) in the order torch.linalg.cholesky evaluates it, with the radicand
+// clamped at zero: where tanhf saturates (|raw| from about 9) the float32 difference sy^2 - l10^2 is rounding noise of
+// either sign, and a negative one would make the draw and every later step of its running sum NaN.  A positive
+// radicand keeps every bit; a clamped one samples on the degenerate line, which is the float64 statement to within
+// the bound of DESIGN.md 2.4
 __device__ __forceinline__ Chol2 draw_chol(float sx, float sy, float rho) {
     const float c01 = rho * sx * sy;
     const float l00 = sqrtf(sx * sx);
     const float l10 = c01 / l00;
-    return {l00, l10, sqrtf(sy * sy - l10 * l10)};
+    return {l00, l10, sqrtf(fmaxf(sy * sy - l10 * l10, 0.f))};
 }
 // q: the element (n, field 0, t, v) of V_pred, p_sf: its field stride
 __device__ __forceinline__ Chol2 draw_chol(const float *q, int64_t p_sf) {

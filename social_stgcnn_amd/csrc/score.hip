@@ -15,7 +15,7 @@
 //            dx, dy = mean_h - truth in float32 and (cxx, cxy, cyy) = C_h, every operation in float32 as written (no
 //            fused multiply-add):
 //              err  = sqrtf(dx*dx + dy*dy)
-//              det  = cxx*cyy - cxy*cxy
+//              det  = fmaxf(cxx*cyy - cxy*cxy, (cxx*cyy) * 2^-15)   (floored where the difference is rounding noise)
 //              d2   = (cyy*(dx*dx) - 2*cxy*dx*dy + cxx*(dy*dy)) / det
 //              nll  = 0.5*d2 + 0.5*log(det) + log(2 pi), log(det) the correctly rounded float32 logarithm (taken in
 //                     float64 and rounded), log(2 pi) the float32 constant

@@ -813,7 +813,8 @@ Score = collections.namedtuple("Score", "rec_ids matched err d2 nll best traj_st
 Score.__doc__ = """One push scored (`stg_score_push`), NS leading.  Row h-1 of the (NS,P,V) fields is the prediction made
 h pushes ago, scored at its step h against this push's detections: rec_ids int64 (the id where matched, else -1),
 matched int32, err (displacement of the mean trajectory), d2 (squared Mahalanobis distance under the predicted
-Gaussian), nll and best (min over the K samples) float32.  The (NS,V) fields are the record that turned P pushes old:
+Gaussian, its determinant floored at 2^-15 cxx cyy so that a saturated correlation gives a large finite value), nll
+and best (min over the K samples) float32.  The (NS,V) fields are the record that turned P pushes old:
 traj_steps int32 (the steps at which its pedestrian was matched), traj_ade / traj_fde (best-of-K; the reference's ADE /
 FDE where traj_steps == P) and traj_ade_mean / traj_fde_mean (the zero-noise trajectory).  Unmatched and padded entries
 are 0.  best, traj_ade and traj_fde are None when samples are not scored."""

@@ -28,11 +28,15 @@ def partner_of(pair):
     return np.where(pair.max(axis=-1) > 0, arg, -1)
 
 
-def risk(samples, num_peds=None, radius=None, zones=None):
+def risk(samples, num_peds=None, radius=None, zones=None, pad=None):
+    """pad (N,V), signed, or None: pedestrian i's own allowance -- a pair hits when its distance is below
+    radius + pad_i + pad_j, and i is inside a rectangle grown by pad_i on every edge."""
     s = np.asarray(samples, np.float64)
     k, n, p, v, _ = s.shape
     vi = clamp_peds(num_peds, n, v)
     out = {}
+    if pad is not None:
+        return _risk_padded(s, vi, radius, zones, np.asarray(pad, np.float64), out)
     if radius is not None:
         r2 = np.float64(radius) * np.float64(radius)
         out.update(conflict=np.zeros((n, p, v), np.int64), conflict_any=np.zeros((n, v), np.int64),
@@ -64,8 +68,47 @@ def risk(samples, num_peds=None, radius=None, zones=None):
     return out
 
 
+def _risk_padded(s, vi, radius, zones, pad, out):
+    """risk() with a per-pedestrian allowance (see there); the same counts over the same sets."""
+    k, n, p, v, _ = s.shape
+    if radius is not None:
+        out.update(conflict=np.zeros((n, p, v), np.int64), conflict_any=np.zeros((n, v), np.int64),
+                   pair=np.zeros((n, v, v), np.int64))
+        for b in range(n):
+            c = int(vi[b])
+            x = s[:, b, :, :c]
+            d = x[:, :, :, None, :] - x[:, :, None, :, :]
+            reach = np.float64(radius) + pad[b, :c, None] + pad[b, None, :c]
+            hit = np.sqrt(d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) < reach
+            hit &= ~np.eye(c, dtype=bool)
+            out["conflict"][b, :, :c] = hit.any(axis=3).sum(axis=0)
+            out["conflict_any"][b, :c] = hit.any(axis=(1, 3)).sum(axis=0)
+            out["pair"][b, :c, :c] = hit.any(axis=1).sum(axis=0)
+        out["partner"] = partner_of(out["pair"])
+    if zones is not None:
+        z = np.asarray(zones, np.float64)
+        z = np.broadcast_to(z, (n,) + z.shape[-2:])
+        nz = z.shape[1]
+        out.update(zone_any=np.zeros((n, p, nz), np.int64), zone_count=np.zeros((n, p, nz), np.int64),
+                   ped_zone=np.zeros((n, v, nz), np.int64))
+        for b in range(n):
+            c = int(vi[b])
+            x, y = s[:, b, :, :c, 0, None], s[:, b, :, :c, 1, None]
+            r, g = z[b], pad[b, :c, None]
+            ins = (r[:, 0] - g <= x) & (x < r[:, 2] + g) & (r[:, 1] - g <= y) & (y < r[:, 3] + g)
+            out["zone_any"][b] = ins.any(axis=2).sum(axis=0)
+            out["zone_count"][b] = ins.sum(axis=(0, 2))
+            out["ped_zone"][b, :c] = ins.any(axis=1).sum(axis=0)
+    return out
+
+
 def bounds(samples, num_peds, radius, zones, delta):
-    """(lower, upper): risk at radius - delta / + delta, the rectangles shrunk / grown by delta on every edge."""
+    """(lower, upper): risk at radius - delta / + delta, the rectangles shrunk / grown by delta on every edge.  delta
+    (N,V): every pedestrian's own bound on how far its positions may lie from `samples` (a pair's distance then moves
+    by at most the sum of the two, an edge test by the pedestrian's own)."""
+    if np.ndim(delta):
+        delta = np.asarray(delta, np.float64)
+        return risk(samples, num_peds, radius, zones, -delta), risk(samples, num_peds, radius, zones, delta)
     grow = np.array([-delta, -delta, delta, delta])
     z = None if zones is None else np.asarray(zones, np.float64)
     lo = risk(samples, num_peds, None if radius is None else radius - delta, None if z is None else z - grow)

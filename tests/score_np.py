@@ -95,7 +95,7 @@ class ScoreModel:
                 dx, dy = f(f(mu[0]) - f(t[0])), f(f(mu[1]) - f(t[1]))
                 err = f(np.sqrt(f(f(dx * dx) + f(dy * dy))))
                 cxx, cxy, cyy = (f(x) for x in rec["cov"][h - 1, v])
-                det = f(f(cxx * cyy) - f(cxy * cxy))
+                det = max(f(f(cxx * cyy) - f(cxy * cxy)), f(f(cxx * cyy) * f(2.0 ** -15)))
                 num = f(f(f(cyy * f(dx * dx)) - f(f(f(f(2) * cxy) * dx) * dy)) + f(cxx * f(dy * dy)))
                 d2 = f(num / det)
                 nll = f(f(f(f(0.5) * d2) + f(f(0.5) * f(np.log(np.float64(det))))) + f(LOG_2PI))
