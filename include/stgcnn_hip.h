@@ -644,6 +644,10 @@ int stg_selftest_mfma(const float *a, const float *b, int K, float *c, void *str
  * declared in stgcnn_hip_harvest.h like the timed score above */
 #include "stgcnn_hip_harvest.h"
 
+/* N11: ... from timestamped pushes, the tracks resampled on the model's step grid (added entry points,
+ * the ABI version stays), declared in stgcnn_hip_harvest_time.h the same way */
+#include "stgcnn_hip_harvest_time.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -155,6 +155,14 @@ _SIGNATURES_HARVEST = {
     "stg_window_harvest_streams": (c_i, [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_f,
                                          c_f, c_f, c_i, c_i, c_f]),
 }
+# ... and those of include/stgcnn_hip_harvest_time.h, included the same way
+c_d = ctypes.c_double
+_SIGNATURES_HARVEST_TIME = {
+    "stg_window_harvest_timed": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_d, c_l, c_l, c_l, c_i,
+                                       c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_f]),
+    "stg_window_harvest_streams_timed": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_d, c_l,
+                                               c_l, c_l, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_f]),
+}
 
 _lib = None
 
@@ -180,7 +188,8 @@ def lib():
                 "--offload-arch=gfx950) or `python -c 'import __graft_entry__ as g; g.build()'`. "
                 "There is no CPU or eager-PyTorch fallback for this path." % (LIB_PATH, CSRC))
         h = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in {**_SIGNATURES, **_SIGNATURES_SCORE_TIME, **_SIGNATURES_HARVEST}.items():
+        for name, (res, args) in {**_SIGNATURES, **_SIGNATURES_SCORE_TIME, **_SIGNATURES_HARVEST,
+                                    **_SIGNATURES_HARVEST_TIME}.items():
             fn = getattr(h, name)
             fn.restype = res
             fn.argtypes = args

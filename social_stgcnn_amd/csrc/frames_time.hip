@@ -16,25 +16,11 @@
 // words, no scratch, no host synchronisation.
 #include "detections.hpp"
 #include "track_rule.hpp"
+#include "time_samples.hpp"
 
 namespace stg {
 
 constexpr int kFlagTimeOrder = STG_TRACK_TIME_ORDER;
-
-// round(pa + (pb - pa) * w): the statement's interpolation, one IEEE operation at a time
-__device__ __forceinline__ double lerp_pos(double pa, double pb, double w, double scale) {
-#pragma clang fp contract(off)
-    const double d = pb - pa;
-    const double p = d * w;
-    return round_pos(pa + p, scale);
-}
-
-// The slot's samples as a push sees them, oldest first: the newest n_old = min(count, R - 1) recorded ones (the one
-// this push overwrites is not among them) and then this push's own.  ring_at: ring index of logical sample i < n_old.
-__device__ __forceinline__ int ring_at(int head, int n_old, int i, int R) {
-    const int x = head + R - n_old + i;                     // < 2 R
-    return x >= R ? x - R : x;
-}
 
 // One timed push of one stream by one workgroup of kThreads threads at the time t_now; the arguments of
 // track_push_body with the timed state and sizes (live_args.hpp) in the place of the plain ones.  Returns the flags.

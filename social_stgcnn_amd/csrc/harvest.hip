@@ -17,38 +17,9 @@
 // what the feed produced, and the capacity test of a tick is monotone in the stream index.
 // Integer work, float64 loads and one float32 conversion per element.  Plain C++ stores; LDS atomics on integer words
 // only.  No host synchronisation: everything is read when the kernels run, so the launches are captured with the push.
-#include "detections.hpp"
-#include "track_rule.hpp"
+#include "harvest_parts.hpp"
 
 namespace stg {
-
-constexpr int kHarvestThreads = 256;
-constexpr int kHarvestWaves = kHarvestThreads / kWave;
-
-// a ring row as the state holds it -> [0, n): every ring row is taken modulo its depth
-__device__ __forceinline__ int ring_row(int row, int n) { return (row % n + n) % n; }
-
-// Block-wide exclusive scan of v over the threads (thread order); every thread gets the block total in *total.  Called
-// by all kHarvestThreads threads (two barriers).
-__device__ __forceinline__ int block_scan(int v, int *total, int *wave_tot) {
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    int x = v;
-    for (int o = 1; o < kWave; o <<= 1) {
-        const int y = __shfl_up(x, o, kWave);
-        if (lane >= o) x += y;
-    }
-    if (lane == kWave - 1) wave_tot[wave] = x;
-    __syncthreads();
-    int before = 0, all = 0;
-    for (int w = 0; w < kHarvestWaves; ++w) {
-        const int c = wave_tot[w];
-        before += w < wave ? c : 0;
-        all += c;
-    }
-    __syncthreads();                    // wave_tot is reused by the next call
-    *total = all;
-    return before + x - v;
-}
 
 // One push of one stream's history by one workgroup, behind the track push: age the words, take presence and position
 // from the track state, and leave the candidates -- the slots with all T_all low bits set -- sorted by id in (key,
@@ -103,36 +74,6 @@ __device__ __forceinline__ int harvest_update(const TrackView &tr, const Harvest
     __syncthreads();
     det_sort(key, kidx, n2, tid, nt);
     return c;
-}
-
-// The c rows of one window into the log from row `row0` on: row p is the slot slot_at(p), (2, T_all) float32 with column
-// 0 zero and column t = (float)(pos[t] - pos[t-1]), the subtraction in float64 on the rounded positions, oldest first.
-// Every store is checked against the log's capacity, every slot against S.
-template <class SlotAt>
-__device__ __forceinline__ void harvest_rows(const double *__restrict__ ring, const HarvestDims &d, const HarvestLog &log,
-                                             int64_t row0, int c, int row, SlotAt slot_at) {
-    const int S = d.S, T_all = d.T_all;
-    float *__restrict__ rel = log.rel_all;
-    for (int e = threadIdx.x; e < c * T_all; e += kHarvestThreads) {
-        const int p = e / T_all, t = e % T_all;
-        const int s = slot_at(p);
-        const int64_t r = row0 + p;
-        if (r < 0 || r >= log.cap_rows || s < 0 || s >= S) continue;
-        float dx = 0.0f, dy = 0.0f;
-        if (t > 0) {
-            const int now = (row + 1 + t) % T_all, before = (row + t) % T_all;   // step t is row - (T_all - 1 - t)
-            const double *a = ring + ((int64_t)now * S + s) * 2, *b = ring + ((int64_t)before * S + s) * 2;
-            dx = (float)(a[0] - b[0]);
-            dy = (float)(a[1] - b[1]);
-        }
-        rel[(r * 2) * T_all + t] = dx;
-        rel[(r * 2 + 1) * T_all + t] = dy;
-    }
-}
-
-// does a window of c rows fit behind (nw windows, nr rows)?  Never once a window has been dropped.
-__device__ __forceinline__ bool harvest_fits(const HarvestLog &log, int dropped, int64_t nw, int64_t nr, int c) {
-    return dropped == 0 && nw >= 0 && nr >= 0 && nw < log.cap_windows && nr + c <= log.cap_rows;
 }
 
 // ---- one stream ------------------------------------------------------------------------------------------------------
@@ -261,7 +202,13 @@ static int harvest_args(const char *what, const TrackView &tr, const HarvestStat
     return STG_OK;
 }
 
-static inline size_t harvest_lds(const HarvestDims &d) { return det_sort_lds(det_sort_n(d.S)); }
+int harvest_place_write(const char *what, const HarvestState &hs, const HarvestDims &d, const HarvestWork &wk,
+                        const HarvestLog &log, int NS, hipStream_t st) {
+    const int rc = launch({what, dim3(1), dim3(kHarvestThreads), 0, st}, harvest_place_kernel, (const int32_t *)hs.head, d,
+                          wk, log, NS);
+    if (rc != STG_OK) return rc;
+    return launch({what, dim3(NS), dim3(kHarvestThreads), 0, st}, harvest_write_streams_kernel, hs, d, wk, log);
+}
 
 }  // namespace stg
 
@@ -302,11 +249,7 @@ int stg_window_harvest_streams(const int64_t *slot_id, const uint32_t *mask, con
     rc = stg::launch({what, dim3(NS), dim3(stg::kHarvestThreads), stg::harvest_lds(d), st, 64 * 1024},
                      stg::harvest_update_streams_kernel, tr, pushed, hs, d, wk);
     if (rc != STG_OK) return rc;
-    rc = stg::launch({what, dim3(1), dim3(stg::kHarvestThreads), 0, st}, stg::harvest_place_kernel,
-                     (const int32_t *)h_head, d, wk, log, NS);
-    if (rc != STG_OK) return rc;
-    return stg::launch({what, dim3(NS), dim3(stg::kHarvestThreads), 0, st}, stg::harvest_write_streams_kernel, hs, d, wk,
-                       log);
+    return stg::harvest_place_write(what, hs, d, wk, log, NS, st);
 }
 
 }  // extern "C"

@@ -111,6 +111,20 @@ struct HarvestLog {
     int cap_windows, cap_rows;
 };
 
+// ---- the timed window harvest (harvest_time.hip) --------------------------------------------------------
+// What the timed harvest adds to HarvestDims: R samples per slot, the push's scale, step, max_dt and settle in ticks
+struct TimedHarvestDims { int R; double scale; int64_t step, max_dt, settle; };
+
+// The timed push's state as the harvest reads it, behind that push: nothing of it is written
+struct TimedView {
+    const int64_t *slot_id, *t_ring; const double *xy_ring; const int32_t *slot_head; const int64_t *clock;
+    const int32_t *head_flags;
+    __device__ __forceinline__ TimedView of_stream(int64_t b, int S, int R) const {
+        return {slot_id + b * S,       t_ring + b * S * R, xy_ring + b * S * R * 2,
+                slot_head + b * S * 2, clock + 2 * b,      head_flags + 2 * b};
+    }
+};
+
 // ---- host side ------------------------------------------------------------------------------------------------------
 // What every _streams entry point checks of its streams, under its own name `what`: NS, M_total and the strides.  The
 // entry points do not all answer alike, and each keeps its answer:

@@ -32,6 +32,9 @@ stg_frame_scenes over a recording uploaded once, stg_track_push with the track s
     AssociateSpec      associate=AssociateSpec(gate, gate_new, max_miss) on the two live predictors: pushes carry
                        positions only, push(None, xy); a launch ahead of the push kernel gives every detection its track
                        id on the device (stg_associate); `.det_ids`, `.assoc_flags`
+    TimedHarvestSpec   harvest=TimedHarvestSpec(windows, rows, min_peds, pred_len, settle) together with time=: the
+                       harvest of HarvestSpec on the timed tracks resampled on the step grid (stg_window_harvest_timed,
+                       DESIGN.md 5.27)
     HarvestSpec        harvest=HarvestSpec(windows, rows, min_peds, pred_len) on the two live predictors: a launch behind
                        the push kernel keeps every training window the tracks complete -- a track seen in each of the
                        last obs_len + pred_len pushes is one row of a reference TrajectoryDataset window -- in a log on
@@ -217,10 +220,46 @@ class HarvestSpec(collections.namedtuple("HarvestSpec", "windows rows min_peds p
         return HarvestSpec(self.windows, rows, self.min_peds, pred_len)
 
 
+class TimedHarvestSpec(collections.namedtuple("TimedHarvestSpec", "windows rows min_peds pred_len settle")):
+    """HarvestSpec for live pushes with time (time=TimeRule(...)): the tracks are resampled on the
+    model's step grid g0 + i * step, g0 the time of the stream's first accepted push, and every resolved grid instant
+    is one frame of a HarvestSpec's harvest -- a track observed at it under the TimeRule's own test (a sample at the
+    instant, or the interpolation of two samples next to it at most max_dt apart), detected in that very push or not.
+    windows, rows, min_peds and pred_len as in HarvestSpec.  settle, 0 <= settle <= max_dt - 1 ticks (default max_dt -
+    1), is how long an instant waits before it is resolved: at max_dt - 1 every bracket the rule allows around it has
+    arrived, so a missed detection costs the track nothing; at 0 an instant is resolved by the first push at or after
+    it.  A push more than a step after the last one skips the instants in between and ends every run of frames.  The
+    TimeRule's history must still hold the sample at or before an instant when it is resolved: the samples of settle +
+    max_dt ticks plus one push interval; a shallower one makes the frame a gap, never a wrong position."""
+    __slots__ = ()
+
+    def __new__(cls, windows, rows=None, min_peds=2, pred_len=None, settle=None):
+        try:
+            base = HarvestSpec(windows, rows, min_peds, pred_len)
+        except ValueError as e:
+            raise ValueError("Timed" + str(e)) from None
+        if settle is not None and not _is_int(settle, 0, (1 << 31) - 2):
+            raise ValueError("TimedHarvestSpec: settle must be None or an integer in [0, max_dt - 1], got %r" % (settle,))
+        return super().__new__(cls, *base, None if settle is None else int(settle))
+
+    def checked(self, obs_len, max_peds, pred_seq_len, max_dt):
+        """The spec with rows, pred_len and settle resolved, once it fits a predictor of obs_len observed steps under a
+        TimeRule with that max_dt."""
+        try:
+            base = HarvestSpec(*self[:4]).checked(obs_len, max_peds, pred_seq_len)
+        except ValueError as e:
+            raise ValueError("Timed" + str(e)) from None
+        settle = max_dt - 1 if self.settle is None else self.settle
+        if settle > max_dt - 1:
+            raise ValueError("TimedHarvestSpec: settle=%d > max_dt - 1 = %d (no bracket is wider than max_dt)"
+                             % (settle, max_dt - 1))
+        return TimedHarvestSpec(*base, settle)
+
+
 class LiveWindows:
     """The windows a harvesting predictor has kept, on the device in dataset.DeviceWindows' own layout: rel_all float32
     (rows,2,T_all), win_start int32 (windows+1,), win_tag int32 (windows,2) = (stream, that stream's push index since
-    its reset) and header int32 (3,) = {n_windows, n_rows, dropped_full}.  Append-only: pushes write behind what is
+    its reset; under a TimedHarvestSpec the grid index of the window's last frame) and header int32 (3,) = {n_windows, n_rows, dropped_full}.  Append-only: pushes write behind what is
     there, the first window that does not fit is counted in dropped_full and closes the log, clear() empties it."""
 
     def __init__(self, spec, t_obs, device):
@@ -481,14 +520,19 @@ class _LivePredictor:
     _score_pushed = None                 # the (NS,) int32 `pushed` words a timed score launch reads; None: one stream
 
     harvest = None                       # the LiveWindows of a predictor made with harvest=; None without
+    h_clock = None                       # with harvest=TimedHarvestSpec: {anchored, g0, instants skipped} per stream
 
     def __init__(self, model, k, obs_len, capacity, max_peds, max_detections, decimals, risk=None, keep_samples=True,
                  tracks=None, score=None, time=None, associate=None, harvest=None):
         self.model = model
         self.k = int(k)
-        if harvest is not None and time is not None:
+        timed_harvest = isinstance(harvest, TimedHarvestSpec)
+        if harvest is not None and time is not None and not timed_harvest:
             raise ValueError("harvest= together with time= is not supported: a timed push is not one frame of a "
                              "window (DESIGN.md 8)")
+        if timed_harvest and time is None:
+            raise ValueError("harvest=TimedHarvestSpec(...) needs time=TimeRule(...): its frames are instants of the "
+                             "step grid (without time= the push-indexed HarvestSpec serves)")
         if associate is not None and time is not None:
             raise ValueError("associate= together with time= is not supported: a velocity per tick and a gate that "
                              "grows with the gap are a change of their own (DESIGN.md 8)")
@@ -540,7 +584,9 @@ class _LivePredictor:
             raise ValueError("max_detections must be in [1, %d], got %r" % (MAX_DETECTIONS, max_detections))
         if self.v < 1:
             raise ValueError("max_peds must be >= 1, got %r" % (max_peds,))
-        if harvest is not None:
+        if timed_harvest:
+            harvest = harvest.checked(self.t_obs, self.v, model.pred_seq_len, self.time.max_dt)
+        elif harvest is not None:
             if not isinstance(harvest, HarvestSpec):
                 harvest = HarvestSpec(*harvest) if isinstance(harvest, (tuple, list)) else HarvestSpec(harvest)
             harvest = harvest.checked(self.t_obs, self.v, model.pred_seq_len)
@@ -603,6 +649,9 @@ class _LivePredictor:
             self.h_ring = torch.zeros(lead + (self.harvest.t_all, self.s, 2), device=dev, dtype=torch.float64)
             self.h_head = torch.zeros(lead + (2,), device=dev, dtype=torch.int32)
             self._harvest_state = (self.h_word, self.h_ring, self.h_head)
+            if self.time is not None:                        # the grid of the timed harvest, behind the history
+                self.h_clock = torch.zeros(lead + (3,), device=dev, dtype=torch.int64)
+                self._harvest_state += (self.h_clock,)
             self._harvest_work = torch.zeros(lead[0] * (self.s + 3), device=dev, dtype=torch.int32) if lead else None
         return dev
 
@@ -676,12 +725,19 @@ class _LivePredictor:
         writes the ids the push kernel behind it reads."""
         check(getattr(lib(), name)(*det, *map(ptr, self._assoc_state), *self._assoc_args, stream_ptr()), name)
 
+    @property
+    def harvest_clock(self):
+        """With harvest=TimedHarvestSpec(...): (NS,3) int64 on the device (NS = 1 for a FramePredictor), per stream
+        {anchored 0/1, g0, grid instants skipped} since its reset -- a window tagged (stream, i) ends at the instant g0 +
+        i * step; reading it is the caller's synchronisation.  None otherwise."""
+        return None if self.h_clock is None else self.h_clock.view(-1, 3)
+
     def _reset_harvest(self, at=None):
         """Empty the harvest history everywhere, or at the stream indices `at`; the log is left alone.  (A ring row is
         read only where the word says detected.)"""
         if self._harvest_state is None:
             return
-        for x in (self.h_word, self.h_head):
+        for x in (self.h_word, self.h_head) + (() if self.h_clock is None else (self.h_clock,)):
             if at is None:
                 x.zero_()
             else:
@@ -692,6 +748,15 @@ class _LivePredictor:
         entry point is told of its streams), the sizes, `tag` (the lone entry point's stream index), the history, `work`
         (the _streams entry point's scratch) and the log."""
         h = self.harvest
+        if self.time is not None:
+            # the timed twin: the sample rings as the state, R behind S, (scale, step, max_dt, settle) behind the sizes,
+            # h_clock behind the history
+            name += "_timed"
+            check(getattr(lib(), name)(*map(ptr, self._state), *streams, self.s, self.time.history, self.t_obs, h.t_all,
+                                       self.harvest_spec.min_peds, ctypes.c_double(self.scale), self.time.step,
+                                       self.time.max_dt, self.harvest_spec.settle, *tag,
+                                       *map(ptr, self._harvest_state), *work, *h._args(), stream_ptr()), name)
+            return
         check(getattr(lib(), name)(*map(ptr, self._state), *streams, self.s, self.t_obs, h.t_all,
                                    self.harvest_spec.min_peds, *tag, *map(ptr, self._harvest_state), *work, *h._args(),
                                    stream_ptr()), name)
@@ -824,7 +889,11 @@ class FramePredictor(_LivePredictor):
     harvest: a HarvestSpec -- every push also keeps the training window it completes, if any (stg_window_harvest, one
     launch behind the push kernel, inside the captured graph; it reads the track state only, so it goes with tracks=,
     associate=, risk= and score=): `.harvest` is the LiveWindows log, its windows tagged (0, push index since reset()).
-    reset() empties the harvest history and leaves the log.  Not together with time=."""
+    reset() empties the harvest history and leaves the log.  Not together with time=: with time= the spec is a
+    TimedHarvestSpec (only together with time=; stg_window_harvest_timed, one launch behind the timed push, inside the
+    captured graph): the frames are the instants of the step grid anchored at the first accepted push, the windows are
+    tagged (0, grid index of their last frame), `.harvest_clock` (1,3) int64 holds {anchored, g0, instants skipped};
+    it goes with tracks=, risk= and score=TimedScoreSpec(...)."""
 
     def __init__(self, model, k=20, obs_len=8, capacity=1024, max_peds=128, max_detections=1024, decimals=4,
                  risk=None, keep_samples=True, tracks=None, score=None, time=None, associate=None, harvest=None):
@@ -1061,7 +1130,9 @@ class StreamsPredictor(_LivePredictor):
     with best_of_k=False).
     harvest: a HarvestSpec for all streams together, as in FramePredictor (stg_window_harvest_streams: three launches
     behind the push launch): ONE log, `.harvest`, in which a tick's windows land in stream order, each tagged (stream,
-    that stream's push index since its reset); a stream not pushed keeps its harvest history bit for bit."""
+    that stream's push index since its reset); a stream not pushed keeps its harvest history bit for bit.  With time= a
+    TimedHarvestSpec, as in FramePredictor (stg_window_harvest_streams_timed): every stream on its own grid,
+    `.harvest_clock` (NS,3)."""
 
     def __init__(self, model, streams, k=20, obs_len=8, capacity=1024, max_peds=128, max_detections=1024, decimals=4,
                  max_total_detections=None, block_threads=0, risk=None, keep_samples=True, tracks=None, score=None,

@@ -5,7 +5,8 @@ trajectories for every pedestrian tracked over the last obs_seq_len frames.
                                                [--min_peds 1] [--delim tab] [--radius R]
                                                [--zones x0,y0,x1,y1 ...] [--min_seen M] [--max_gap G]
                                                [--step TICKS [--max_dt D] [--history R] [--max_peds V]
-                                                [--score [--pending N]]]
+                                                [--score [--pending N]]
+                                                [--harvest_timed WINDOWS [--settle D] [--harvest_out FILE.npz]]]
                                                [--associate GATE[,GATE_NEW[,MAX_MISS]] [--max_peds V]]
                                                [--harvest WINDOWS [--harvest_out FILE.npz] [--max_peds V]]
                                                --out preds.npz
@@ -49,6 +50,12 @@ frames.HarvestSpec(WINDOWS)), which also keeps the training windows the tracks c
 data.load_windows over the same file, in order).  The .npz holds one entry per push with at least --min_peds pedestrians;
 --harvest_out FILE.npz gets the windows: seq_rel (R,2,T) float32, num_peds (W,), tags (W,2) = (0, push index) and
 dropped_full.  Not together with --step, --associate or --radius / --zones.
+
+--step TICKS --harvest_timed WINDOWS is the same on a timed feed (frames.TimedHarvestSpec(WINDOWS, settle=D), DESIGN.md
+5.27): the tracks are resampled on the step grid anchored at the first push's time, an instant resolved --settle D ticks
+after it (default max_dt - 1).  --harvest_out FILE.npz then holds seq_rel, num_peds, tags (W,2) = (0, grid index of the
+window's last frame), g0 (that frame's time is g0 + index * TICKS), skipped (grid instants passed over) and
+dropped_full.  Not together with --harvest or --associate.
 """
 import argparse
 import os
@@ -58,8 +65,8 @@ import numpy as np
 import torch
 
 from . import data
-from .frames import (AssociateSpec, FramePredictor, HarvestSpec, TimeRule, TrackRule, predict_recording, score_summary,
-                     sorted_rows)
+from .frames import (AssociateSpec, FramePredictor, HarvestSpec, TimedHarvestSpec, TimeRule, TrackRule, predict_recording,
+                     score_summary, sorted_rows)
 from .model import social_stgcnn
 from .predict import RiskSpec, TimedScoreSpec
 from .trainer import load_checkpoint, load_pickle
@@ -99,7 +106,13 @@ def build_parser():
                    help="push the recording frame by frame and keep up to this many of the training windows its tracks "
                         "complete (not with --step, --associate or --radius / --zones)")
     p.add_argument("--harvest_out", default=None, metavar="FILE.npz",
-                   help="with --harvest: write the harvested windows (seq_rel, num_peds, tags) here")
+                   help="with --harvest or --harvest_timed: write the harvested windows (seq_rel, num_peds, tags) here")
+    p.add_argument("--harvest_timed", type=int, default=None, metavar="WINDOWS",
+                   help="with --step: keep up to this many of the training windows the timed tracks complete on the "
+                        "step grid (not with --harvest or --associate)")
+    p.add_argument("--settle", type=int, default=None, metavar="D",
+                   help="with --harvest_timed: resolve a grid instant D ticks after it (0 .. max_dt - 1; default "
+                        "max_dt - 1)")
     p.add_argument("--out", required=True, help="output .npz")
     # a rectangle may begin with a negative coordinate: "-1,-1,1,1" is a value, not an option
     p._negative_number_matcher = re.compile(r"^-[0-9.][0-9.,eE+-]*$")
@@ -125,17 +138,19 @@ def load_model(exp_path, device):
     return model.to(device).eval()
 
 
-def predict_timed(model, rows, time, k=20, seed=0, min_peds=1, tracks=None, max_peds=128, score=None):
+def predict_timed(model, rows, time, k=20, seed=0, min_peds=1, tracks=None, max_peds=128, score=None, harvest=None):
     """Every distinct frame number of `rows`, taken as a time in ticks, pushed through ONE captured timed
     FramePredictor -> a dict of host arrays, one entry per push whose scene holds at least min_peds pedestrians.
-    score: a predict.TimedScoreSpec -- the dict also holds the summary of the running totals as score_* arrays."""
+    score: a predict.TimedScoreSpec -- the dict also holds the summary of the running totals as score_* arrays.
+    harvest: a frames.TimedHarvestSpec -- the result is (that dict, the dict of what the run harvested: seq_rel
+    (R,2,T_all) float32, num_peds (W,) int32, tags (W,2) int32 = (0, grid index), g0, skipped, dropped_full)."""
     frames, fs, ids, xy = sorted_rows(rows)
     if np.any(frames != np.round(frames)):
         raise ValueError("--step: the frame column must hold integer ticks")
     ticks = frames.astype(np.int64)
     m_max = max(1, int(np.diff(fs).max()) if len(frames) else 1)
     fp = FramePredictor(model, k=k, obs_len=model.seq_len, max_peds=max_peds, max_detections=m_max, tracks=tracks,
-                        time=time, score=score)
+                        time=time, score=score, harvest=harvest)
     replay = fp.capture()
     keep = {name: [] for name in ("time", "ids", "num_peds", "mean", "samples", "seen")}
     for f, t in enumerate(ticks.tolist()):
@@ -160,6 +175,14 @@ def predict_timed(model, rows, time, k=20, seed=0, min_peds=1, tracks=None, max_
         res.update({"score_" + name: np.asarray(x)[0] for name, x in zip(summary._fields[:-1], summary[:-1])})
         res["score_levels"] = np.asarray(score.levels, np.float64)
         res["score_evictions"] = fp.score_evictions.cpu().numpy()[0]
+    if harvest is not None:
+        log = fp.harvest
+        n_w, n_r, dropped = log.counts()
+        start = log.win_start[:n_w + 1].cpu().numpy()
+        clock = fp.harvest_clock.cpu().numpy()[0]
+        return res, dict(seq_rel=log.rel_all[:n_r].cpu().numpy(), num_peds=np.diff(start).astype(np.int32),
+                         tags=log.tags(), g0=np.int64(clock[1]), skipped=np.int64(clock[2]),
+                         dropped_full=np.int32(dropped))
     return res
 
 
@@ -213,9 +236,26 @@ def predict_associated(model, rows, associate, k=20, seed=0, min_peds=1, tracks=
 
 def check_harvest_args(a):
     """The refusals of --harvest / --harvest_out, ahead of anything that needs the device."""
+    if a.harvest_timed is None:
+        if a.settle is not None:
+            raise ValueError("--settle needs --harvest_timed WINDOWS")
+    else:
+        if a.harvest is not None:
+            raise ValueError("--harvest_timed does not go together with --harvest: one is indexed by time, the other "
+                             "by push")
+        if a.step is None:
+            raise ValueError("--harvest_timed needs --step TICKS: its frames are instants of the step grid")
+        if a.associate is not None:
+            raise ValueError("--harvest_timed does not go together with --associate")
+        if a.harvest_timed < 1:
+            raise ValueError("--harvest_timed: at least one window, got %d" % a.harvest_timed)
+        max_dt = a.step if a.max_dt is None else a.max_dt
+        if a.settle is not None and not 0 <= a.settle <= max_dt - 1:
+            raise ValueError("--settle: %d not in [0, max_dt - 1 = %d]" % (a.settle, max_dt - 1))
+        return
     if a.harvest is None:
         if a.harvest_out is not None:
-            raise ValueError("--harvest_out needs --harvest WINDOWS")
+            raise ValueError("--harvest_out needs --harvest WINDOWS (or --harvest_timed WINDOWS)")
         return
     if a.step is not None:
         raise ValueError("--harvest does not go together with --step: a timed push is not one frame of a window")
@@ -297,10 +337,19 @@ def main(argv=None):
     if a.step is not None:
         if a.radius is not None or a.zones is not None:
             raise ValueError("--step does not go together with --radius / --zones")
+        spec = None if a.harvest_timed is None else TimedHarvestSpec(a.harvest_timed, settle=a.settle)
         res = predict_timed(model, rows, TimeRule(a.step, a.max_dt, a.history), a.ksteps, a.seed, a.min_peds, tracks,
-                            a.max_peds, TimedScoreSpec(pending=a.pending) if a.score else None)
+                            a.max_peds, TimedScoreSpec(pending=a.pending) if a.score else None, spec)
+        if spec is not None:
+            res, kept = res
+            if a.harvest_out is not None:
+                np.savez(a.harvest_out, **kept)
         np.savez(a.out, **res)
         print("%d pushes with a scene, up to %d pedestrians -> %s" % (len(res["time"]), res["ids"].shape[1], a.out))
+        if spec is not None:
+            print("%d windows (%d rows) harvested, %d grid instants skipped, %d dropped%s"
+                  % (len(kept["num_peds"]), len(kept["seq_rel"]), int(kept["skipped"]), int(kept["dropped_full"]),
+                     "" if a.harvest_out is None else " -> " + a.harvest_out))
         if a.score:
             print("scored: %d entries, %d full trajectories, ADE %.4f FDE %.4f, %d records evicted"
                   % (int(res["score_count"].sum()), int(res["score_trajectories"]), float(res["score_ade"]),

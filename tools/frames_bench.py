@@ -10,7 +10,7 @@
     python tools/frames_bench.py --cases harvest [--streams 1,64,600] [--ticks 200] [--pushes 2000]
     python tools/frames_bench.py --harvest ...          the latency and streams cases with harvest=HarvestSpec(...)
     python tools/frames_bench.py --tracks 2,2 ...       every case under frames.TrackRule(2, 2) (the *_rule kernels)
-    python tools/frames_bench.py --time 10,10 ...       the latency, streams and score cases on timestamped pushes
+    python tools/frames_bench.py --time 10,10 ...       the latency, streams, score and harvest cases on timestamped pushes
                                                         (frames.TimeRule(10, history=--history), stg_track_push_timed):
                                                         a model step is 10 ticks and the feed is upsampled 10x by linear
                                                         interpolation, one push per tick (--time STEP: not upsampled)
@@ -46,7 +46,8 @@
   harvest    the window harvest: the latency case (students001, max_peds 128) and the streams case at
              NS = 1, 64 and 600 (or --streams), each with and without harvest=HarvestSpec(...) sized so that the log never
              fills (one window per stream and tick, 32 rows each): p50 / p90 of both, the difference, and what the log
-             holds at the end.  No yardstick.
+             holds at the end.  No yardstick.  With --time STEP[,UP] both sides are the timed predictors and the spec is
+             TimedHarvestSpec (stg_window_harvest_timed, frames on the step grid).
 
 Kernel times come from a separate run under the profiler (tracing slows the host):
     rocprofv3 --kernel-trace --stats -d OUT -o frames -- python tools/frames_bench.py --cases latency --pushes 500
@@ -117,17 +118,17 @@ def timed_pushes(rows, step, up):
     return out
 
 
-def harvest_spec(windows):
-    """A log that `windows` windows of up to 32 rows never fill."""
+def harvest_spec(windows, timed=None):
+    """A log that `windows` windows of up to 32 rows never fill; with --time the timed spec (settle at its default)."""
     from social_stgcnn_amd import frames
-    return frames.HarvestSpec(windows, rows=32 * windows)
+    return (frames.HarvestSpec if timed is None else frames.TimedHarvestSpec)(windows, rows=32 * windows)
 
 
 def latency_case(split, rec, max_peds, k, n_push, dev, warmup=50, tracks=None, timed=None, harvest=False):
     from social_stgcnn_amd import data, frames
     rows = data.read_file(os.path.join(DATA, rec))
     pushes = pushes_of(rows) if timed is None else timed_pushes(rows, *timed[:2])
-    kw = {"harvest": harvest_spec(warmup + n_push)} if harvest else {}
+    kw = {"harvest": harvest_spec(warmup + n_push, timed)} if harvest else {}
     fp = frames.FramePredictor(model_for(split, dev), k=k, max_peds=max_peds, **tracks_kw(tracks, timed), **kw)
     push = fp.capture()
     times, peds = [], []
@@ -199,7 +200,7 @@ def streams_case(ns, k, n_ticks, dev, block=0, lone=True, max_peds=128, warmup=2
                   keep_samples=risk == "samples")
     kw.update(tracks_kw(tracks, timed))
     if harvest:
-        kw["harvest"] = harvest_spec(ns * (warmup + n_ticks))
+        kw["harvest"] = harvest_spec(ns * (warmup + n_ticks), timed)
     if associate is not None:
         kw["associate"] = associate
         seq = [[(None, xy) for _, xy in q] for q in seq]
@@ -323,7 +324,8 @@ def main():
     ap.add_argument("--pending", type=int, default=128,
                     help="with --time and the score case: record rows per stream (predict.TimedScoreSpec)")
     ap.add_argument("--harvest", action="store_true",
-                    help="the latency and streams cases with harvest=HarvestSpec(...), sized so that the log never fills")
+                    help="the latency and streams cases with harvest=HarvestSpec(...) (with --time: TimedHarvestSpec), "
+                         "sized so that the log never fills")
     ap.add_argument("--associate", default="1.0,2.0,0", metavar="GATE[,GATE_NEW[,MAX_MISS]]",
                     help="the AssociateSpec of the associate case")
     a = ap.parse_args()
@@ -356,14 +358,14 @@ def main():
                        "score_cost_p50_ms": round(on["tick_p50_ms"] - off["tick_p50_ms"], 4)})
             print(json.dumps(on), flush=True)
     if "harvest" in cases:
-        lat = [latency_case("univ", "univ_test/students001.txt", 128, a.k, a.pushes, dev, tracks=tracks, harvest=h)
-               for h in (False, True)]
+        lat = [latency_case("univ", "univ_test/students001.txt", 128, a.k, a.pushes, dev, tracks=tracks, timed=timed,
+                            harvest=h) for h in (False, True)]
         lat[1].update({"case": "harvest_latency", "p50_ms_without": lat[0]["p50_ms"], "p90_ms_without": lat[0]["p90_ms"],
                        "harvest_cost_p50_ms": round(lat[1]["p50_ms"] - lat[0]["p50_ms"], 4)})
         print(json.dumps(lat[1]), flush=True)
         for ns in (int(n) for n in (a.streams if a.streams != "1,8,64,256,600" else "1,64,600").split(",")):
-            off = streams_case(ns, a.k, a.ticks, dev, 0, False, tracks=tracks)
-            on = streams_case(ns, a.k, a.ticks, dev, 0, False, tracks=tracks, harvest=True)
+            off = streams_case(ns, a.k, a.ticks, dev, 0, False, tracks=tracks, timed=timed)
+            on = streams_case(ns, a.k, a.ticks, dev, 0, False, tracks=tracks, timed=timed, harvest=True)
             on.update({"case": "harvest", "tick_p50_ms_without": off["tick_p50_ms"],
                        "tick_p90_ms_without": off["tick_p90_ms"],
                        "harvest_cost_p50_ms": round(on["tick_p50_ms"] - off["tick_p50_ms"], 4)})
