@@ -648,6 +648,10 @@ int stg_selftest_mfma(const float *a, const float *b, int K, float *c, void *str
  * the ABI version stays), declared in stgcnn_hip_harvest_time.h the same way */
 #include "stgcnn_hip_harvest_time.h"
 
+/* N12: N9 on timestamped pushes, ahead of the timed push (added entry points, the ABI version stays),
+ * declared in stgcnn_hip_assoc_time.h the same way */
+#include "stgcnn_hip_assoc_time.h"
+
 #ifdef __cplusplus
 }
 #endif

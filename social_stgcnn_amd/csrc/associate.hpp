@@ -1,7 +1,11 @@
-// associate: what the association kernels (associate.hip) share with anything that sizes or reads
-// their launch -- the workgroup sizes, the flag, the LDS image and the two IEEE expressions of the rule.
+// associate: what the association kernels (associate.hip; associate_time.hip) share
+// with each other and with anything that sizes or reads their launch -- the workgroup sizes, the flags, the LDS image,
+// the IEEE expressions of the rule, the state record and the body itself, a template over a MOTION POLICY: how many
+// model steps lie between a slot's last match and this push, and what a match, a miss and a birth do to the word that
+// says so (trk_miss of the untimed rule, trk_t of the timed one).  The matching rounds are the same for both.
 #pragma once
 #include "detections.hpp"
+#include "track_rule.hpp"
 
 namespace stg {
 
@@ -56,6 +60,239 @@ __device__ __forceinline__ double assoc_velocity(double p, double pos, double k)
 #pragma clang fp contract(off)
     const double d = p - pos;
     return d / k;
+}
+
+// The state both rules keep per slot, and per stream; the slot's word of the motion policy is the policy's own
+struct AssocState {
+    int64_t *trk_id;         // (C)    -1 = free
+    double *trk_pos;         // (C,2)  the last matched rounded position
+    double *trk_vel;         // (C,2)  displacement per push (timed: per model step)
+    int32_t *trk_hits;       // (C)    matches so far
+    int64_t *next_id;        // (1)
+    int32_t *assoc_flags;    // (1)    STG_ASSOC_* of the last push
+    __device__ __forceinline__ AssocState of_stream(int64_t b, int C) const {
+        return {trk_id + b * C, trk_pos + b * C * 2, trk_vel + b * C * 2, trk_hits + b * C, next_id + b, assoc_flags + b};
+    }
+};
+
+struct AssocGates {
+    double scale, gate2, gate_new2;
+};
+
+// The untimed motion: every push is one step.  The word is trk_miss, the pushes since the last match.
+struct PushMotion {
+    int32_t *trk_miss;       // (C)
+    int max_miss;
+    using Word = int;
+    __device__ __forceinline__ PushMotion of_stream(int64_t b, int C) const { return {trk_miss + b * C, max_miss}; }
+    __device__ __forceinline__ Word word(int s) const { return trk_miss[s]; }
+    __device__ __forceinline__ double steps(Word miss) const { return (double)(miss + 1); }
+    __device__ __forceinline__ void matched(int s) const { trk_miss[s] = 0; }
+    // a live slot not matched: true = it is freed (the word zeroed with the rest), else it ages
+    __device__ __forceinline__ bool missed(int s, Word miss) const {
+        const bool gone = miss + 1 > max_miss;
+        trk_miss[s] = gone ? 0 : miss + 1;
+        return gone;
+    }
+    __device__ __forceinline__ void born(int s) const { trk_miss[s] = 0; }
+};
+
+// One push of one stream by one workgroup of kThreads threads: the positions of the detections j < min(count, M_max)
+// are read, their ids written.
+template <int kThreads, class Motion>
+__device__ __forceinline__ void associate_body(const DetectionsOut &det, int count, int M_max, const AssocState st,
+                                               const Motion mo, int C, const AssocGates rule) {
+    extern __shared__ __align__(16) unsigned char lds[];
+    double *tq = reinterpret_cast<double *>(lds);               // (C,2) predicted positions
+    double *dp = tq + 2 * (size_t)C;                             // (M_max,2) rounded detections
+    int32_t *tgate = reinterpret_cast<int32_t *>(dp + 2 * (size_t)M_max);     // (C) -1 free slot, 0 gate_new2, 1 gate2
+    int32_t *tstate = tgate + C;                                 // (C) kUnknown, kNone, best detection >= 0, or taken
+    int32_t *list = tstate + C;                                  // (C) live slots in slot order; later the free slots
+    int32_t *dstate = list + C;                                  // (M_max) the same for a detection: best track slot
+    __shared__ int wave_cnt[kThreads / kWave];
+    __shared__ int flags, accepted;
+
+    const int tid = threadIdx.x;
+    const int m = count < 0 ? 0 : (count > M_max ? M_max : count);
+    const int64_t next0 = st.next_id[0];
+    if (tid == 0) {
+        flags = 0;
+        accepted = 0;
+    }
+
+    // 1. predictions and gates of the slots (every load unconditional and no barrier in the loop: the loads of
+    //    successive passes are in flight together), the rounded detections; then the live list from LDS
+#pragma unroll 4
+    for (int s = tid; s < C; s += kThreads) {
+        const int64_t id = st.trk_id[s];
+        const int hits = st.trk_hits[s];
+        const double k = mo.steps(mo.word(s));
+        tq[2 * s] = assoc_predict(st.trk_pos[2 * s], st.trk_vel[2 * s], k);
+        tq[2 * s + 1] = assoc_predict(st.trk_pos[2 * s + 1], st.trk_vel[2 * s + 1], k);
+        tgate[s] = id < 0 ? -1 : (hits >= 2 ? 1 : 0);
+        tstate[s] = kUnknown;
+    }
+    for (int j = tid; j < m; j += kThreads) {
+        dp[2 * j] = round_pos(det.x(j), rule.scale);
+        dp[2 * j + 1] = round_pos(det.y(j), rule.scale);
+        dstate[j] = kUnknown;
+    }
+    __syncthreads();
+    int n_live = 0, tot = 0;
+    for (int s0 = 0; s0 < C; s0 += kThreads) {
+        const int s = s0 + tid;
+        const bool live = s < C && tgate[s] >= 0;
+        const int r = block_rank<kThreads>(live, n_live, &tot, wave_cnt);
+        if (live) list[r] = s;
+        n_live += tot;
+    }
+    __syncthreads();
+
+    // 2. the rounds.  `accepted` only grows; a round that leaves it as it was ends the matching
+    const int bound = n_live < m ? n_live : m;
+    const int sub = tid & (kAssocGroup - 1), grp = tid / kAssocGroup;
+    int done = 0;
+    for (int round = 0; round < bound; ++round) {
+        // a row (a column) is walked by a group of kAssocGroup lanes, partner sub, sub + kAssocGroup, ...; every lane
+        // of the block runs the same passes, so the shuffles of assoc_group_min meet converged
+        for (int i0 = 0; i0 < n_live; i0 += kThreads / kAssocGroup) {
+            const int i = i0 + grp;
+            int s = 0;
+            bool scan = false;
+            if (i < n_live) {
+                s = list[i];
+                const int was = tstate[s];
+                // not: taken / nothing in reach / the remembered detection is still free, so still the best
+                scan = !(assoc_taken(was) || was == kNone || (was >= 0 && !assoc_taken(dstate[was])));
+            }
+            double best = 0.0;
+            int at = kNone;
+            if (scan) {
+                const double qx = tq[2 * s], qy = tq[2 * s + 1], g2 = tgate[s] ? rule.gate2 : rule.gate_new2;
+                for (int j = sub; j < m; j += kAssocGroup) {
+                    if (assoc_taken(dstate[j])) continue;
+                    const double c = assoc_cost(qx, qy, dp[2 * j], dp[2 * j + 1]);
+                    if (c <= g2 && (at < 0 || c < best)) {
+                        best = c;
+                        at = j;
+                    }
+                }
+            }
+            assoc_group_min(best, at);
+            if (scan && sub == 0) tstate[s] = at;
+        }
+        for (int j0 = 0; j0 < m; j0 += kThreads / kAssocGroup) {
+            const int j = j0 + grp;
+            bool scan = false;
+            if (j < m) {
+                const int was = dstate[j];
+                scan = !(assoc_taken(was) || was == kNone || (was >= 0 && !assoc_taken(tstate[was])));
+            }
+            double best = 0.0;
+            int at = kNone;
+            if (scan) {
+                const double px = dp[2 * j], py = dp[2 * j + 1];
+                for (int i = sub; i < n_live; i += kAssocGroup) {         // slot order within a lane
+                    const int s = list[i];
+                    if (assoc_taken(tstate[s])) continue;
+                    const double c = assoc_cost(tq[2 * s], tq[2 * s + 1], px, py);
+                    if (c <= (tgate[s] ? rule.gate2 : rule.gate_new2) && (at < 0 || c < best)) {
+                        best = c;
+                        at = s;
+                    }
+                }
+            }
+            assoc_group_min(best, at);
+            if (scan && sub == 0) dstate[j] = at;
+        }
+        __syncthreads();
+        // a free track whose best detection names it back.  (A taken detection holds a negative word, a free one the
+        // slot of its own best track: neither is s unless the pair is mutual; each word is written by one thread.)
+        for (int i = tid; i < n_live; i += kThreads) {
+            const int s = list[i];
+            const int j = tstate[s];
+            if (j >= 0 && dstate[j] == s) {
+                tstate[s] = assoc_take(j);
+                dstate[j] = assoc_take(s);
+                atomicAdd(&accepted, 1);
+            }
+        }
+        __syncthreads();
+        const int now = accepted;
+        if (now == done) break;
+        done = now;
+    }
+
+    // 3. the tracks: a matched one moves, one not matched ages and is freed past the policy's limit.  Again every load is
+    //    unconditional and the loop holds no barrier; tgate becomes the mark of a free slot (-1) for the list below
+#pragma unroll 4
+    for (int s = tid; s < C; s += kThreads) {
+        const int64_t id = st.trk_id[s];
+        const typename Motion::Word w = mo.word(s);
+        const int hits = st.trk_hits[s];
+        const double ox = st.trk_pos[2 * s], oy = st.trk_pos[2 * s + 1];
+        if (tgate[s] < 0) continue;
+        const int was = tstate[s];
+        if (assoc_taken(was)) {
+            const int j = assoc_partner(was);
+            const double k = mo.steps(w);
+            const double px = dp[2 * j], py = dp[2 * j + 1];
+            st.trk_vel[2 * s] = assoc_velocity(px, ox, k);
+            st.trk_vel[2 * s + 1] = assoc_velocity(py, oy, k);
+            st.trk_pos[2 * s] = px;
+            st.trk_pos[2 * s + 1] = py;
+            mo.matched(s);
+            st.trk_hits[s] = hits + 1;
+            det.id_at(j) = id;
+            tgate[s] = 0;
+        } else if (mo.missed(s, w)) {
+            st.trk_id[s] = -1;
+            st.trk_pos[2 * s] = st.trk_pos[2 * s + 1] = 0.0;
+            st.trk_vel[2 * s] = st.trk_vel[2 * s + 1] = 0.0;
+            st.trk_hits[s] = 0;
+            tgate[s] = -1;
+        } else {
+            tgate[s] = 0;
+        }
+    }
+    __syncthreads();
+    int n_free = 0;                                           // the free slots in slot order, in the place of the live list
+    for (int s0 = 0; s0 < C; s0 += kThreads) {
+        const int s = s0 + tid;
+        const bool fr = s < C && tgate[s] < 0;
+        const int r = block_rank<kThreads>(fr, n_free, &tot, wave_cnt);
+        if (fr) list[r] = s;
+        n_free += tot;
+    }
+    __syncthreads();
+
+    // 4. the detections not matched, in detection order: fresh ids, and the free slots while they last
+    int n_new = 0;
+    for (int j0 = 0; j0 < m; j0 += kThreads) {
+        const int j = j0 + tid;
+        const bool nw = j < m && !assoc_taken(dstate[j]);
+        const int r = block_rank<kThreads>(nw, n_new, &tot, wave_cnt);
+        if (nw) {
+            det.id_at(j) = next0 + r;
+            if (r < n_free) {
+                const int s = list[r];
+                st.trk_id[s] = next0 + r;
+                st.trk_pos[2 * s] = dp[2 * j];
+                st.trk_pos[2 * s + 1] = dp[2 * j + 1];
+                st.trk_vel[2 * s] = st.trk_vel[2 * s + 1] = 0.0;
+                mo.born(s);
+                st.trk_hits[s] = 1;
+            } else {
+                atomicOr(&flags, kFlagAssocFull);
+            }
+        }
+        n_new += tot;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        st.next_id[0] = next0 + n_new;
+        st.assoc_flags[0] = flags;
+    }
 }
 
 }  // namespace stg

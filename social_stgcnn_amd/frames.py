@@ -32,6 +32,9 @@ stg_frame_scenes over a recording uploaded once, stg_track_push with the track s
     AssociateSpec      associate=AssociateSpec(gate, gate_new, max_miss) on the two live predictors: pushes carry
                        positions only, push(None, xy); a launch ahead of the push kernel gives every detection its track
                        id on the device (stg_associate); `.det_ids`, `.assoc_flags`
+    TimedAssociateSpec associate=TimedAssociateSpec(gate, gate_new, max_age) together with time=: the association at the
+                       tracker's own rate, push(None, xy, t=TICKS); a track keeps the time of its last match and its
+                       velocity per model step (stg_associate_timed ahead of the timed push)
     TimedHarvestSpec   harvest=TimedHarvestSpec(windows, rows, min_peds, pred_len, settle) together with time=: the
                        harvest of HarvestSpec on the timed tracks resampled on the step grid (stg_window_harvest_timed,
                        DESIGN.md 5.27)
@@ -146,7 +149,8 @@ class TimeRule(collections.namedtuple("TimeRule", "step max_dt history")):
         return TimeRule(self.step, max_dt, self.history)
 
 
-ASSOC_FULL = 1                         # STG_ASSOC_FULL, the one bit of `.assoc_flags`
+ASSOC_FULL = 1                         # STG_ASSOC_FULL, a bit of `.assoc_flags`
+ASSOC_TIME_ORDER = 2                   # STG_ASSOC_TIME_ORDER (only under a TimedAssociateSpec)
 
 
 class AssociateSpec(collections.namedtuple("AssociateSpec", "gate gate_new max_miss capacity")):
@@ -179,6 +183,30 @@ class AssociateSpec(collections.namedtuple("AssociateSpec", "gate gate_new max_m
             raise ValueError("AssociateSpec: capacity must be None or an integer in [1, %d], got %r"
                              % (MAX_SLOTS, capacity))
         return super().__new__(cls, gate, gate_new, int(max_miss), None if capacity is None else int(capacity))
+
+
+class TimedAssociateSpec(collections.namedtuple("TimedAssociateSpec", "gate gate_new max_age capacity")):
+    """AssociateSpec for live pushes with time (time=TimeRule(...)): positions without ids, timestamped,
+    at the detector's own rate.  The rule is AssociateSpec's with time in the place of the push count: a track keeps the
+    time of its last match and its velocity per model step, and predicts pos + vel * (t - that time) / step; a matched
+    detection gives vel = (p - pos) / the same quotient.  gate and gate_new (default 2 * gate) are the caller's
+    distances whatever the gap, as AssociateSpec's are whatever the misses.  A track not matched is forgotten once its
+    last match is more than max_age ticks old (default 0: by the first push that does not match it; max_miss * step is
+    AssociateSpec's lifetime).  capacity as in AssociateSpec.  A push whose time is not after the stream's last accepted
+    one changes nothing: its ids are -1 and `.assoc_flags` is ASSOC_TIME_ORDER (the timed push behind it refuses it too).
+    Fed one push per step it gives AssociateSpec's ids, positions, velocities and hits bit for bit."""
+    __slots__ = ()
+
+    def __new__(cls, gate, gate_new=None, max_age=None, capacity=None):
+        try:
+            base = AssociateSpec(gate, gate_new, 0, capacity)
+        except ValueError as e:
+            raise ValueError("Timed" + str(e)) from None
+        max_age = 0 if max_age is None else max_age
+        if not _is_number(max_age) or not _is_int(max_age, 0, (1 << 31) - 1):
+            raise ValueError("TimedAssociateSpec: max_age must be an integer number of ticks in [0, 2^31), got %r"
+                             % (max_age,))
+        return super().__new__(cls, base.gate, base.gate_new, int(max_age), base.capacity)
 
 
 MAX_WINDOW_STEPS = 32                  # STG_HARVEST_MAX_STEPS: a harvest word is 32 bits
@@ -313,6 +341,10 @@ FramePrediction.__doc__ = """One push, on the device: ids (V,) int64 (-1 in padd
 obs_abs (1,T_obs,V,2) float64, samples (K,P,V,2), mean (P,V,2), v_pred (5,P,V) float32, flags (1,) int32 (DUPLICATE |
 OVERFLOW | TRUNCATED | TOO_MANY | TIME_ORDER of this push).  From a captured push the tensors are the graph's static
 buffers, overwritten by the next push."""
+
+
+def _is_number(x):
+    return not isinstance(x, bool) and isinstance(x, (int, float, np.integer, np.floating)) and bool(np.isfinite(x))
 
 
 def _is_int(x, lo, hi=None):
@@ -516,7 +548,7 @@ class _LivePredictor:
         _harvest()               with harvest=: launch its window harvest on the track state, behind _push
 
     and `seed_dev`, the (1,) int64 device tensor the sampler reads its seed from."""
-    assoc = None                         # the AssociateSpec; None: ids come with the pushes
+    assoc = None                         # the AssociateSpec or TimedAssociateSpec; None: ids come with the pushes
     _score_pushed = None                 # the (NS,) int32 `pushed` words a timed score launch reads; None: one stream
 
     harvest = None                       # the LiveWindows of a predictor made with harvest=; None without
@@ -533,10 +565,14 @@ class _LivePredictor:
         if timed_harvest and time is None:
             raise ValueError("harvest=TimedHarvestSpec(...) needs time=TimeRule(...): its frames are instants of the "
                              "step grid (without time= the push-indexed HarvestSpec serves)")
-        if associate is not None and time is not None:
+        timed_assoc = isinstance(associate, TimedAssociateSpec)
+        if timed_assoc and time is None:
+            raise ValueError("associate=TimedAssociateSpec(...) needs time=TimeRule(...): its tracks are aged by time "
+                             "(without time= the push-indexed AssociateSpec serves)")
+        if associate is not None and time is not None and not timed_assoc:
             raise ValueError("associate= together with time= is not supported: a velocity per tick and a gate that "
                              "grows with the gap are a change of their own (DESIGN.md 8)")
-        if associate is not None and not isinstance(associate, AssociateSpec):
+        if associate is not None and not isinstance(associate, (AssociateSpec, TimedAssociateSpec)):
             associate = AssociateSpec(*associate) if isinstance(associate, (tuple, list)) else AssociateSpec(associate)
         self.assoc = associate
         self._assoc_state = None
@@ -616,21 +652,27 @@ class _LivePredictor:
             self._state = (self.slot_id, self.t_ring, self.xy_ring, self.slot_head, self.clock, self.head_flags)
             self._forget = (self.slot_head, self.clock, self.head_flags)     # (a ring holds what its count says)
         if self.assoc is not None:
-            # the association state: slot ids, positions, velocities, misses, hits; per stream next_id and the flags
+            # the association state: slot ids, positions, velocities, misses (under a TimedAssociateSpec the times of
+            # the last match in their place), hits; per stream next_id and the flags
             c = self.s if self.assoc.capacity is None else self.assoc.capacity
             one = lead or (1,)
+            timed = isinstance(self.assoc, TimedAssociateSpec)
             self.trk_id = torch.empty(lead + (c,), device=dev, dtype=torch.int64)
             self.trk_pos = torch.zeros(lead + (c, 2), device=dev, dtype=torch.float64)
             self.trk_vel = torch.zeros(lead + (c, 2), device=dev, dtype=torch.float64)
-            self.trk_miss = torch.zeros(lead + (c,), device=dev, dtype=torch.int32)
+            if timed:
+                self.trk_t = torch.zeros(lead + (c,), device=dev, dtype=torch.int64)
+            else:
+                self.trk_miss = torch.zeros(lead + (c,), device=dev, dtype=torch.int32)
             self.trk_hits = torch.zeros(lead + (c,), device=dev, dtype=torch.int32)
             self.next_id = torch.zeros(one, device=dev, dtype=torch.int64)
             self.assoc_flags = torch.zeros(one, device=dev, dtype=torch.int32)
-            self._assoc_state = (self.trk_id, self.trk_pos, self.trk_vel, self.trk_miss, self.trk_hits, self.next_id,
-                                 self.assoc_flags)
-            # (the gates travel squared, in float64)
+            self._assoc_state = (self.trk_id, self.trk_pos, self.trk_vel, self.trk_t if timed else self.trk_miss,
+                                 self.trk_hits, self.next_id, self.assoc_flags)
+            # (the gates travel squared, in float64; the lifetime as max_miss pushes, or as (step, max_age) ticks)
             self._assoc_args = (c, ctypes.c_double(self.scale), ctypes.c_double(self.assoc.gate * self.assoc.gate),
-                                ctypes.c_double(self.assoc.gate_new * self.assoc.gate_new), self.assoc.max_miss)
+                                ctypes.c_double(self.assoc.gate_new * self.assoc.gate_new),
+                                *((self.time.step, self.assoc.max_age) if timed else (self.assoc.max_miss,)))
         self._pred = Predictor(self.model, self.k, *self._risk_args)
         if self.score_spec is not None:
             spec = self.score_spec
@@ -720,10 +762,14 @@ class _LivePredictor:
             else:
                 x.index_fill_(0, at, fill)
 
-    def _launch_associate(self, name, det):
-        """The association kernel `name` on the detections `det` (its leading arguments) and the association state: it
-        writes the ids the push kernel behind it reads."""
-        check(getattr(lib(), name)(*det, *map(ptr, self._assoc_state), *self._assoc_args, stream_ptr()), name)
+    def _launch_associate(self, name, det, when, sizes):
+        """The association kernel `name` on the detections `det` (its leading arguments), the sizes behind them and the
+        association state: it writes the ids the push kernel behind it reads.  Under a TimedAssociateSpec the timed twin:
+        `when`, the time(s) the timed push reads, and that push's clock go between the detections and the sizes."""
+        if isinstance(self.assoc, TimedAssociateSpec):
+            name += "_timed"
+            det += (when, ptr(self.clock))
+        check(getattr(lib(), name)(*det, *sizes, *map(ptr, self._assoc_state), *self._assoc_args, stream_ptr()), name)
 
     @property
     def harvest_clock(self):
@@ -885,7 +931,11 @@ class FramePredictor(_LivePredictor):
     one launch ahead of the push kernel (inside the captured graph), gives every detection its track id in the staging
     buffer the push and the score read; the returned ids are those track ids, `.det_ids` (M,) the id of every detection
     of the last push in the caller's order, `.assoc_flags` (1,) int32 the association's flags (ASSOC_FULL).  Ids given
-    with associate=, or None without it, are refused.  Not together with time=.
+    with associate=, or None without it, are refused.  An AssociateSpec does not go together with time=; with time= the
+    spec is a TimedAssociateSpec (only together with time=; stg_associate_timed, one launch ahead of the timed push,
+    inside the captured graph): push(None, xy, t=TICKS), the tracks aged by time, `.det_ids` and `.assoc_flags` as above
+    (ASSOC_TIME_ORDER, ids -1, for a push the timed push refuses); tracks=, risk=, score=TimedScoreSpec(...) and
+    harvest=TimedHarvestSpec(...) work behind it unchanged.
     harvest: a HarvestSpec -- every push also keeps the training window it completes, if any (stg_window_harvest, one
     launch behind the push kernel, inside the captured graph; it reads the track state only, so it goes with tracks=,
     associate=, risk= and score=): `.harvest` is the LiveWindows log, its windows tagged (0, push index since reset()).
@@ -909,8 +959,9 @@ class FramePredictor(_LivePredictor):
         self.reset()
 
     def reset(self):
-        """Forget every track (the next obs_len - 1 pushes return empty scenes), and with score= the pending records
-        and the running totals; with harvest= the harvest history, not the log."""
+        """Forget every track (the next obs_len - 1 pushes return empty scenes), with associate= the association's
+        tracks and ids with them (under time= together with the clock), and with score= the pending records and the
+        running totals; with harvest= the harvest history, not the log."""
         self.slot_id.fill_(-1)
         for x in self._forget:
             x.zero_()
@@ -925,7 +976,8 @@ class FramePredictor(_LivePredictor):
         return None if self.assoc is None else self.det_id[:self._n_det]
 
     def _associate(self):
-        self._launch_associate("stg_associate", (ptr(self.det_id), ptr(self.det_xy), ptr(self.det_count), self.m_max))
+        self._launch_associate("stg_associate", (ptr(self.det_id), ptr(self.det_xy), ptr(self.det_count)),
+                               ptr(self.det_time), (self.m_max,))
 
     def _harvest(self):
         self._launch_harvest("stg_window_harvest", (), (0,), ())
@@ -1119,7 +1171,9 @@ class StreamsPredictor(_LivePredictor):
     (stg_associate_streams, one workgroup per stream ahead of the push launch): tick entries are (None, xy), a
     DeviceTick is DeviceTick(None, xy, counts); `.det_ids` (M,) holds the ids of the tick's packed detections,
     `.assoc_flags` (NS,) the flags of each stream's last push.  A stream not pushed keeps its association state bit for
-    bit.  Not together with time=.
+    bit.  An AssociateSpec does not go together with time=; with time= a TimedAssociateSpec, as in FramePredictor
+    (stg_associate_streams_timed, every stream on its own clock): tick entries (None, xy) with times=, or
+    DeviceTick(None, xy, counts) with device times.
     time: a TimeRule for every stream, each with its own clock (stg_track_push_streams_timed): push(tick, times=...)
     with times a length-NS sequence or a {stream: t} mapping that covers every pushed stream -- staged in the same ONE
     copy, the staging header extended by NS int64 --, or with a DeviceTick a device int64 (NS) tensor.  The sample
@@ -1220,7 +1274,8 @@ class StreamsPredictor(_LivePredictor):
         return None if self.assoc is None else self._rec_i[:self._n_det, 0]
 
     def _associate(self):
-        self._launch_associate("stg_associate_streams", (*self._det.values(), self.ns, self.m_max))
+        self._launch_associate("stg_associate_streams", tuple(self._det.values()),
+                               ptr(self.times_dev) if self.time is not None else None, (self.ns, self.m_max))
 
     def _harvest(self):
         self._launch_harvest("stg_window_harvest_streams", (ptr(self.pushed_dev), self.ns), (),

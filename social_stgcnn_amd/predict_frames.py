@@ -6,7 +6,8 @@ trajectories for every pedestrian tracked over the last obs_seq_len frames.
                                                [--zones x0,y0,x1,y1 ...] [--min_seen M] [--max_gap G]
                                                [--step TICKS [--max_dt D] [--history R] [--max_peds V]
                                                 [--score [--pending N]]
-                                                [--harvest_timed WINDOWS [--settle D] [--harvest_out FILE.npz]]]
+                                                [--harvest_timed WINDOWS [--settle D] [--harvest_out FILE.npz]]
+                                                [--associate_timed GATE[,GATE_NEW[,MAX_AGE]]]]
                                                [--associate GATE[,GATE_NEW[,MAX_MISS]] [--max_peds V]]
                                                [--harvest WINDOWS [--harvest_out FILE.npz] [--max_peds V]]
                                                --out preds.npz
@@ -56,6 +57,12 @@ dropped_full.  Not together with --step, --associate or --radius / --zones.
 after it (default max_dt - 1).  --harvest_out FILE.npz then holds seq_rel, num_peds, tags (W,2) = (0, grid index of the
 window's last frame), g0 (that frame's time is g0 + index * TICKS), skipped (grid instants passed over) and
 dropped_full.  Not together with --harvest or --associate.
+
+--step TICKS --associate_timed GATE[,GATE_NEW[,MAX_AGE]] ignores the id column on a timed feed: every distinct frame
+number is one timed push of positions only, rows in file order, through a captured frames.FramePredictor(time=...,
+associate=frames.TimedAssociateSpec(...)) (MAX_AGE in ticks, default 0).  The .npz is --step's, its ids
+the assigned track ids, and assoc_ids (M,) int64 as with --associate.  It goes together with --score and
+--harvest_timed; not with --associate.
 """
 import argparse
 import os
@@ -65,8 +72,8 @@ import numpy as np
 import torch
 
 from . import data
-from .frames import (AssociateSpec, FramePredictor, HarvestSpec, TimedHarvestSpec, TimeRule, TrackRule, predict_recording,
-                     score_summary, sorted_rows)
+from .frames import (AssociateSpec, FramePredictor, HarvestSpec, TimedAssociateSpec, TimedHarvestSpec, TimeRule, TrackRule,
+                     predict_recording, score_summary, sorted_rows)
 from .model import social_stgcnn
 from .predict import RiskSpec, TimedScoreSpec
 from .trainer import load_checkpoint, load_pickle
@@ -102,6 +109,9 @@ def build_parser():
                    help="with --score: record rows kept (at least pushes per step x pred_seq_len)")
     p.add_argument("--associate", default=None, metavar="GATE[,GATE_NEW[,MAX_MISS]]",
                    help="ignore the id column: associate the detections to tracks on the device (assoc_ids array)")
+    p.add_argument("--associate_timed", default=None, metavar="GATE[,GATE_NEW[,MAX_AGE]]",
+                   help="with --step: ignore the id column and associate the timed detections to tracks on the device, "
+                        "a track forgotten MAX_AGE ticks after its last match (assoc_ids array; not with --associate)")
     p.add_argument("--harvest", type=int, default=None, metavar="WINDOWS",
                    help="push the recording frame by frame and keep up to this many of the training windows its tracks "
                         "complete (not with --step, --associate or --radius / --zones)")
@@ -138,23 +148,37 @@ def load_model(exp_path, device):
     return model.to(device).eval()
 
 
-def predict_timed(model, rows, time, k=20, seed=0, min_peds=1, tracks=None, max_peds=128, score=None, harvest=None):
+def predict_timed(model, rows, time, k=20, seed=0, min_peds=1, tracks=None, max_peds=128, score=None, harvest=None,
+                  associate=None):
     """Every distinct frame number of `rows`, taken as a time in ticks, pushed through ONE captured timed
     FramePredictor -> a dict of host arrays, one entry per push whose scene holds at least min_peds pedestrians.
+    associate: a frames.TimedAssociateSpec -- the id column is ignored, the rows of a push go in file order, and the dict
+    also holds assoc_ids (M,) int64, the assigned id of every row.
     score: a predict.TimedScoreSpec -- the dict also holds the summary of the running totals as score_* arrays.
     harvest: a frames.TimedHarvestSpec -- the result is (that dict, the dict of what the run harvested: seq_rel
     (R,2,T_all) float32, num_peds (W,) int32, tags (W,2) int32 = (0, grid index), g0, skipped, dropped_full)."""
-    frames, fs, ids, xy = sorted_rows(rows)
+    if associate is None:
+        frames, fs, ids, xy = sorted_rows(rows)
+    else:                                                    # no id is looked at: the rows of a frame in file order
+        rows = np.asarray(rows, dtype=np.float64)
+        frames = np.unique(rows[:, 0])
+        f_idx = np.searchsorted(frames, rows[:, 0])
+        order = np.argsort(f_idx, kind="stable")
+        fs = np.searchsorted(f_idx[order], np.arange(len(frames) + 1))
+        xy = np.ascontiguousarray(rows[order, 2:4])
+        assoc_ids = np.full(len(rows), -1, np.int64)
     if np.any(frames != np.round(frames)):
         raise ValueError("--step: the frame column must hold integer ticks")
     ticks = frames.astype(np.int64)
     m_max = max(1, int(np.diff(fs).max()) if len(frames) else 1)
     fp = FramePredictor(model, k=k, obs_len=model.seq_len, max_peds=max_peds, max_detections=m_max, tracks=tracks,
-                        time=time, score=score, harvest=harvest)
+                        time=time, score=score, harvest=harvest, associate=associate)
     replay = fp.capture()
     keep = {name: [] for name in ("time", "ids", "num_peds", "mean", "samples", "seen")}
     for f, t in enumerate(ticks.tolist()):
-        out = replay(ids[fs[f]:fs[f + 1]], xy[fs[f]:fs[f + 1]], t=t, seed=seed + f)
+        out = replay(None if associate is not None else ids[fs[f]:fs[f + 1]], xy[fs[f]:fs[f + 1]], t=t, seed=seed + f)
+        if associate is not None:
+            assoc_ids[order[fs[f]:fs[f + 1]]] = fp.det_ids.cpu().numpy()
         n = int(out.num_peds.item())
         if n < min_peds:
             continue
@@ -170,6 +194,8 @@ def predict_timed(model, rows, time, k=20, seed=0, min_peds=1, tracks=None, max_
     res.update(ids=res["ids"][:, :v], seen=res["seen"][:, :v], mean=res["mean"][:, :, :v],
                samples=np.ascontiguousarray(np.moveaxis(res["samples"], 0, 1)[:, :, :, :v]))
     res["frame"] = res["time"].astype(np.float64)
+    if associate is not None:
+        res["assoc_ids"] = assoc_ids
     if score is not None:
         summary = score_summary(*fp.score_totals, score.levels)
         res.update({"score_" + name: np.asarray(x)[0] for name, x in zip(summary._fields[:-1], summary[:-1])})
@@ -193,6 +219,28 @@ def parse_associate(spec):
         raise ValueError("--associate: GATE[,GATE_NEW[,MAX_MISS]] expected, got %r" % spec)
     return AssociateSpec(float(parts[0]), float(parts[1]) if len(parts) > 1 else None,
                          int(parts[2]) if len(parts) > 2 else 0)
+
+
+def parse_associate_timed(spec):
+    """'GATE[,GATE_NEW[,MAX_AGE]]' -> frames.TimedAssociateSpec."""
+    parts = spec.split(",")
+    if not 1 <= len(parts) <= 3:
+        raise ValueError("--associate_timed: GATE[,GATE_NEW[,MAX_AGE]] expected, got %r" % spec)
+    return TimedAssociateSpec(float(parts[0]), float(parts[1]) if len(parts) > 1 else None,
+                              int(parts[2]) if len(parts) > 2 else 0)
+
+
+def check_associate_timed_args(a):
+    """The refusals of --associate_timed, ahead of anything that needs the device -> None or the TimedAssociateSpec."""
+    if a.associate_timed is None:
+        return None
+    if a.associate is not None:
+        raise ValueError("--associate_timed does not go together with --associate: one ages its tracks by time, the "
+                         "other by push")
+    if a.step is None:
+        raise ValueError("--associate_timed needs --step TICKS: its tracks are aged by time (without --step, "
+                         "--associate serves)")
+    return parse_associate_timed(a.associate_timed)
 
 
 def predict_associated(model, rows, associate, k=20, seed=0, min_peds=1, tracks=None, max_peds=128):
@@ -304,6 +352,7 @@ def predict_harvested(model, rows, harvest, k=20, seed=0, min_peds=1, tracks=Non
 def main(argv=None):
     a = build_parser().parse_args(argv)
     check_harvest_args(a)
+    assoc_timed = check_associate_timed_args(a)
     if not torch.cuda.is_available():
         raise RuntimeError("social_stgcnn_amd.predict_frames needs a GPU (MI355X)")
     model = load_model(a.checkpoint, torch.device("cuda", torch.cuda.current_device()))
@@ -339,13 +388,15 @@ def main(argv=None):
             raise ValueError("--step does not go together with --radius / --zones")
         spec = None if a.harvest_timed is None else TimedHarvestSpec(a.harvest_timed, settle=a.settle)
         res = predict_timed(model, rows, TimeRule(a.step, a.max_dt, a.history), a.ksteps, a.seed, a.min_peds, tracks,
-                            a.max_peds, TimedScoreSpec(pending=a.pending) if a.score else None, spec)
+                            a.max_peds, TimedScoreSpec(pending=a.pending) if a.score else None, spec, assoc_timed)
         if spec is not None:
             res, kept = res
             if a.harvest_out is not None:
                 np.savez(a.harvest_out, **kept)
         np.savez(a.out, **res)
         print("%d pushes with a scene, up to %d pedestrians -> %s" % (len(res["time"]), res["ids"].shape[1], a.out))
+        if assoc_timed is not None:
+            print("%d track ids" % (int(res["assoc_ids"].max(initial=-1)) + 1))
         if spec is not None:
             print("%d windows (%d rows) harvested, %d grid instants skipped, %d dropped%s"
                   % (len(kept["num_peds"]), len(kept["seq_rel"]), int(kept["skipped"]), int(kept["dropped_full"]),

@@ -7,6 +7,8 @@
     python tools/frames_bench.py --cases score [--streams 1,64,600] [--ticks 200]
     python tools/frames_bench.py --cases associate [--streams 1,64,600] [--ticks 200] [--associate 1.0,2.0,0]
                                  [--no-lone]
+    python tools/frames_bench.py --cases associate_timed [--streams 1,64,600] [--ticks 200] [--time 10,10]
+                                 [--associate_timed 1.0,2.0,0] [--no-lone]
     python tools/frames_bench.py --cases harvest [--streams 1,64,600] [--ticks 200] [--pushes 2000]
     python tools/frames_bench.py --harvest ...          the latency and streams cases with harvest=HarvestSpec(...)
     python tools/frames_bench.py --tracks 2,2 ...       every case under frames.TrackRule(2, 2) (the *_rule kernels)
@@ -42,6 +44,13 @@
              crowds_zara01 and students003, a captured FramePredictor with score=ScoreSpec() fed the recording's own ids
              and one fed none: best-of-K ADE / FDE of both, and the share of wrong links (a detection whose recorded id
              was in the previous push and whose assigned id is not the one that pedestrian had then).
+
+  associate_timed  the associate case on timestamped pushes (--time STEP,UP, default 10,10: ten pushes per
+             model step): the timed streams case with and without associate=TimedAssociateSpec(...)
+             (stg_associate_streams_timed ahead of the timed push launch, inside the graph) at NS = 1, 64 and 600 (or
+             --streams); then, on crowds_zara01 upsampled 4x (step 4), a captured timed FramePredictor with
+             score=TimedScoreSpec() fed the recording's own ids and one fed none: best-of-K ADE / FDE of both and the
+             share of wrong links.
 
   harvest    the window harvest: the latency case (students001, max_peds 128) and the streams case at
              NS = 1, 64 and 600 (or --streams), each with and without harvest=HarvestSpec(...) sized so that the log never
@@ -203,7 +212,7 @@ def streams_case(ns, k, n_ticks, dev, block=0, lone=True, max_peds=128, warmup=2
         kw["harvest"] = harvest_spec(ns * (warmup + n_ticks), timed)
     if associate is not None:
         kw["associate"] = associate
-        seq = [[(None, xy) for _, xy in q] for q in seq]
+        seq = [[(None,) + tuple(p[1:]) for p in q] for q in seq]
     sp = frames.StreamsPredictor(model, ns, k=k, max_peds=max_peds, block_threads=block, **kw)
     replay = sp.capture()
     times, host, peds = [], [], []
@@ -304,6 +313,36 @@ def associate_quality(split, rec, k, dev, spec, max_peds=128):
     return res
 
 
+def associate_timed_quality(split, rec, k, dev, spec, step=4, up=4, max_peds=128):
+    """One recording upsampled `up` x through two captured timed FramePredictors with score=TimedScoreSpec(): one fed the
+    recording's ids, one fed positions only."""
+    from social_stgcnn_amd import data, frames
+    from social_stgcnn_amd.predict import TimedScoreSpec
+    pushes = timed_pushes(data.read_file(os.path.join(DATA, rec)), step, up)
+    model = model_for(split, dev)
+    score = TimedScoreSpec(pending=max(128, 2 * up * CFG["pred_seq_len"]))
+    res = {"case": "associate_timed_quality", "recording": os.path.basename(rec), "k": k, "associate": list(spec[:3]),
+           "time": [step, up], "pushes": len(pushes)}
+    for name, assoc in (("ids", None), ("assoc", spec)):
+        fp = frames.FramePredictor(model, k=k, max_peds=max_peds, score=score, time=frames.TimeRule(step), associate=assoc)
+        replay = fp.capture()
+        prev, wrong, links = {}, 0, 0
+        for n, (ids, xy, t) in enumerate(pushes):
+            replay(None if assoc else ids, xy, t=t, seed=n)
+            if assoc:
+                now = dict(zip(ids.tolist(), fp.det_ids.cpu().tolist()))
+                links += sum(1 for r in now if r in prev)
+                wrong += sum(1 for r, g in now.items() if r in prev and prev[r] != g)
+                prev = now
+        s = frames.score_summary(*fp.score_totals, score.levels)
+        res.update({name + "_trajectories": int(s.trajectories[0]), name + "_ade": round(float(s.ade[0]), 4),
+                    name + "_fde": round(float(s.fde[0]), 4), name + "_scored": int(s.count[0].sum()),
+                    name + "_evictions": int(fp.score_evictions.sum())})
+        if assoc:
+            res.update({"links": links, "wrong_links": wrong, "assoc_flags": int(fp.assoc_flags.item())})
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--pushes", type=int, default=2000)
@@ -328,6 +367,8 @@ def main():
                          "sized so that the log never fills")
     ap.add_argument("--associate", default="1.0,2.0,0", metavar="GATE[,GATE_NEW[,MAX_MISS]]",
                     help="the AssociateSpec of the associate case")
+    ap.add_argument("--associate_timed", default="1.0,2.0,0", metavar="GATE[,GATE_NEW[,MAX_AGE]]",
+                    help="the TimedAssociateSpec of the associate_timed case (MAX_AGE in ticks)")
     a = ap.parse_args()
     tracks = None if a.tracks is None else tuple(int(x) for x in a.tracks.split(","))
     timed = None
@@ -384,6 +425,20 @@ def main():
         for split, rec in (() if a.no_lone else (("zara1", "zara1_test/crowds_zara01.txt"),
                                                  ("univ", "univ_test/students003.txt"))):
             print(json.dumps(associate_quality(split, rec, a.k, dev, spec)), flush=True)
+    if "associate_timed" in cases:
+        from social_stgcnn_amd.frames import TimedAssociateSpec
+        g = a.associate_timed.split(",")
+        spec = TimedAssociateSpec(float(g[0]), float(g[1]) if len(g) > 1 else None, int(g[2]) if len(g) > 2 else 0)
+        t10 = (10, 10, a.history) if timed is None else timed
+        for ns in (int(n) for n in (a.streams if a.streams != "1,8,64,256,600" else "1,64,600").split(",")):
+            off = streams_case(ns, a.k, a.ticks, dev, 0, False, tracks=tracks, timed=t10)
+            on = streams_case(ns, a.k, a.ticks, dev, 0, False, tracks=tracks, timed=t10, associate=spec)
+            on.update({"case": "associate_timed", "tick_p50_ms_without": off["tick_p50_ms"],
+                       "tick_p90_ms_without": off["tick_p90_ms"], "host_p50_ms_without": off["host_p50_ms"],
+                       "associate_cost_p50_ms": round(on["tick_p50_ms"] - off["tick_p50_ms"], 4)})
+            print(json.dumps(on), flush=True)
+        if not a.no_lone:
+            print(json.dumps(associate_timed_quality("zara1", "zara1_test/crowds_zara01.txt", a.k, dev, spec)), flush=True)
     if "streams" in cases:
         for block in (int(b) for b in a.block.split(",")):
             for ns in (int(n) for n in a.streams.split(",")):
