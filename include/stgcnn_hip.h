@@ -652,6 +652,10 @@ int stg_selftest_mfma(const float *a, const float *b, int K, float *c, void *str
  * declared in stgcnn_hip_assoc_time.h the same way */
 #include "stgcnn_hip_assoc_time.h"
 
+/* N13: N12 with a filtered track state and a gate that follows the predicted uncertainty (added entry
+ * points, the ABI version stays), declared in stgcnn_hip_assoc_filter.h the same way */
+#include "stgcnn_hip_assoc_filter.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -170,6 +170,13 @@ _SIGNATURES_ASSOC_TIME = {
     "stg_associate_streams_timed": (c_i, [c_f, c_l, c_f, c_l, c_i, c_f, c_f, c_f, c_f, c_i, c_i, c_f, c_f, c_f, c_f, c_f,
                                           c_f, c_f, c_i, c_d, c_d, c_d, c_l, c_l, c_f]),
 }
+# ... and those of include/stgcnn_hip_assoc_filter.h, included the same way
+_SIGNATURES_ASSOC_FILTER = {
+    "stg_associate_filtered": (c_i, [c_f, c_f, c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_d, c_d,
+                                     c_d, c_d, c_d, c_d, c_l, c_l, c_f]),
+    "stg_associate_streams_filtered": (c_i, [c_f, c_l, c_f, c_l, c_i, c_f, c_f, c_f, c_f, c_i, c_i, c_f, c_f, c_f, c_f,
+                                             c_f, c_f, c_f, c_f, c_i, c_d, c_d, c_d, c_d, c_d, c_d, c_l, c_l, c_f]),
+}
 
 _lib = None
 
@@ -196,7 +203,8 @@ def lib():
                 "There is no CPU or eager-PyTorch fallback for this path." % (LIB_PATH, CSRC))
         h = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in {**_SIGNATURES, **_SIGNATURES_SCORE_TIME, **_SIGNATURES_HARVEST,
-                                    **_SIGNATURES_HARVEST_TIME, **_SIGNATURES_ASSOC_TIME}.items():
+                                    **_SIGNATURES_HARVEST_TIME, **_SIGNATURES_ASSOC_TIME,
+                                    **_SIGNATURES_ASSOC_FILTER}.items():
             fn = getattr(h, name)
             fn.restype = res
             fn.argtypes = args

@@ -1,8 +1,11 @@
-// associate: what the association kernels (associate.hip; associate_time.hip) share
-// with each other and with anything that sizes or reads their launch -- the workgroup sizes, the flags, the LDS image,
-// the IEEE expressions of the rule, the state record and the body itself, a template over a MOTION POLICY: how many
-// model steps lie between a slot's last match and this push, and what a match, a miss and a birth do to the word that
-// says so (trk_miss of the untimed rule, trk_t of the timed one).  The matching rounds are the same for both.
+// associate: what the association kernels (associate.hip; associate_time.hip, DESIGN.md 5.28;
+// associate_filter.hip) share with each other and with anything that sizes or reads their launch -- the
+// workgroup sizes, the flags, the LDS image, the IEEE expressions of the rule, the state record and the body itself, a
+// template over a MOTION POLICY: how many model steps lie between a slot's last match and this push, what a match, a
+// miss and a birth do to the word that says so (trk_miss of the untimed rule, trk_t of the timed ones), what a match
+// does to the slot's position and velocity, and whether the slot's gate is one of the rule's two (chosen by trk_hits)
+// or the policy's own, a float64 per slot in LDS (kSlotGate: the filtered rule).  The matching rounds are the same for
+// all three.
 #pragma once
 #include "detections.hpp"
 #include "track_rule.hpp"
@@ -16,10 +19,13 @@ constexpr int kFlagAssocFull = STG_ASSOC_FULL;
 // LDS image (dynamic): per track slot its predicted position q (2 x float64), its gate (int32: which of the two, -1
 // for a free slot), its state word and one entry of the live list / free list (int32 each): 28 bytes; per detection its
 // rounded position p (2 x float64) and its state word: 20 bytes.  At both limits (2048, 2048) that is 98,304 bytes of
-// the 163,840 a CU holds; at the predictors' defaults (1024, 1024) 49,152, so three workgroups share a CU.
+// the 163,840 a CU holds; at the predictors' defaults (1024, 1024) 49,152, so three workgroups share a CU.  A policy
+// with kSlotGate adds its squared gate per slot (float64): 36 bytes per slot, 114,688 bytes at both limits.
 constexpr size_t kAssocTrackBytes = 2 * sizeof(double) + 3 * sizeof(int32_t);
 constexpr size_t kAssocDetBytes = 2 * sizeof(double) + sizeof(int32_t);
-static inline size_t assoc_lds(int C, int M_max) { return (size_t)C * kAssocTrackBytes + (size_t)M_max * kAssocDetBytes; }
+static inline size_t assoc_lds(int C, int M_max, bool slot_gate = false) {
+    return (size_t)C * (kAssocTrackBytes + (slot_gate ? sizeof(double) : 0)) + (size_t)M_max * kAssocDetBytes;
+}
 
 // A state word of a track (of a detection): kUnknown before its first scan, kNone when no free partner is in reach, the
 // index >= 0 of its best free partner, or, once matched, assoc_take(partner) <= -3.
@@ -79,11 +85,30 @@ struct AssocGates {
     double scale, gate2, gate_new2;
 };
 
+// What a match does under the two-sample rules: vel = (p - pos) / k, pos = p
+__device__ __forceinline__ void assoc_two_sample(const AssocState &st, int s, double k, double px, double py, double ox,
+                                                 double oy) {
+    st.trk_vel[2 * s] = assoc_velocity(px, ox, k);
+    st.trk_vel[2 * s + 1] = assoc_velocity(py, oy, k);
+    st.trk_pos[2 * s] = px;
+    st.trk_pos[2 * s + 1] = py;
+}
+struct AssocNoMore {};       // what a policy loads per slot ahead of the update, beside the shared words: nothing
+
 // The untimed motion: every push is one step.  The word is trk_miss, the pushes since the last match.
 struct PushMotion {
     int32_t *trk_miss;       // (C)
     int max_miss;
     using Word = int;
+    using More = AssocNoMore;
+    static constexpr bool kSlotGate = false;
+    __device__ __forceinline__ More more(const AssocState &, int) const { return {}; }
+    // a matched slot: its prediction (qx, qy), detection (px, py) and old position (ox, oy)
+    __device__ __forceinline__ void update(const AssocState &st, int s, Word miss, const More &, double, double, double px,
+                                           double py, double ox, double oy) const {
+        assoc_two_sample(st, s, steps(miss), px, py, ox, oy);
+        matched(s);
+    }
     __device__ __forceinline__ PushMotion of_stream(int64_t b, int C) const { return {trk_miss + b * C, max_miss}; }
     __device__ __forceinline__ Word word(int s) const { return trk_miss[s]; }
     __device__ __forceinline__ double steps(Word miss) const { return (double)(miss + 1); }
@@ -97,6 +122,20 @@ struct PushMotion {
     __device__ __forceinline__ void born(int s) const { trk_miss[s] = 0; }
 };
 
+// The order test of the timed push (frames_time.hip, step 0) on the same words, for the rules on timestamped pushes.  A
+// refused push: -1 to the ids of its detections, the flag, nothing else.  Returns true when the push was refused;
+// uniform over the block, no barrier.
+constexpr int kFlagAssocTimeOrder = STG_ASSOC_TIME_ORDER;
+template <int kThreads>
+__device__ __forceinline__ bool assoc_refused(const DetectionsOut &det, int count, int M_max, int64_t t_now,
+                                              const int64_t *clock, int32_t *assoc_flags) {
+    if (!(clock[1] > 0 && t_now <= clock[0])) return false;
+    const int m = count < 0 ? 0 : (count > M_max ? M_max : count);
+    for (int j = threadIdx.x; j < m; j += kThreads) det.id_at(j) = -1;
+    if (threadIdx.x == 0) assoc_flags[0] = kFlagAssocTimeOrder;
+    return true;
+}
+
 // One push of one stream by one workgroup of kThreads threads: the positions of the detections j < min(count, M_max)
 // are read, their ids written.
 template <int kThreads, class Motion>
@@ -105,7 +144,9 @@ __device__ __forceinline__ void associate_body(const DetectionsOut &det, int cou
     extern __shared__ __align__(16) unsigned char lds[];
     double *tq = reinterpret_cast<double *>(lds);               // (C,2) predicted positions
     double *dp = tq + 2 * (size_t)C;                             // (M_max,2) rounded detections
-    int32_t *tgate = reinterpret_cast<int32_t *>(dp + 2 * (size_t)M_max);     // (C) -1 free slot, 0 gate_new2, 1 gate2
+    double *tg2 = dp + 2 * (size_t)M_max;                        // (C) the slot's squared gate, under kSlotGate only
+    int32_t *tgate = reinterpret_cast<int32_t *>(tg2 + (Motion::kSlotGate ? (size_t)C : 0));
+                                                                 // (C) -1 free slot, 0 gate_new2, 1 gate2
     int32_t *tstate = tgate + C;                                 // (C) kUnknown, kNone, best detection >= 0, or taken
     int32_t *list = tstate + C;                                  // (C) live slots in slot order; later the free slots
     int32_t *dstate = list + C;                                  // (M_max) the same for a detection: best track slot
@@ -129,6 +170,7 @@ __device__ __forceinline__ void associate_body(const DetectionsOut &det, int cou
         const double k = mo.steps(mo.word(s));
         tq[2 * s] = assoc_predict(st.trk_pos[2 * s], st.trk_vel[2 * s], k);
         tq[2 * s + 1] = assoc_predict(st.trk_pos[2 * s + 1], st.trk_vel[2 * s + 1], k);
+        if constexpr (Motion::kSlotGate) tg2[s] = mo.gate(s, k);
         tgate[s] = id < 0 ? -1 : (hits >= 2 ? 1 : 0);
         tstate[s] = kUnknown;
     }
@@ -151,6 +193,10 @@ __device__ __forceinline__ void associate_body(const DetectionsOut &det, int cou
     // 2. the rounds.  `accepted` only grows; a round that leaves it as it was ends the matching
     const int bound = n_live < m ? n_live : m;
     const int sub = tid & (kAssocGroup - 1), grp = tid / kAssocGroup;
+    const auto gate_of = [&](int s) -> double {
+        if constexpr (Motion::kSlotGate) return tg2[s];
+        else return tgate[s] ? rule.gate2 : rule.gate_new2;
+    };
     int done = 0;
     for (int round = 0; round < bound; ++round) {
         // a row (a column) is walked by a group of kAssocGroup lanes, partner sub, sub + kAssocGroup, ...; every lane
@@ -168,7 +214,7 @@ __device__ __forceinline__ void associate_body(const DetectionsOut &det, int cou
             double best = 0.0;
             int at = kNone;
             if (scan) {
-                const double qx = tq[2 * s], qy = tq[2 * s + 1], g2 = tgate[s] ? rule.gate2 : rule.gate_new2;
+                const double qx = tq[2 * s], qy = tq[2 * s + 1], g2 = gate_of(s);
                 for (int j = sub; j < m; j += kAssocGroup) {
                     if (assoc_taken(dstate[j])) continue;
                     const double c = assoc_cost(qx, qy, dp[2 * j], dp[2 * j + 1]);
@@ -196,7 +242,7 @@ __device__ __forceinline__ void associate_body(const DetectionsOut &det, int cou
                     const int s = list[i];
                     if (assoc_taken(tstate[s])) continue;
                     const double c = assoc_cost(tq[2 * s], tq[2 * s + 1], px, py);
-                    if (c <= (tgate[s] ? rule.gate2 : rule.gate_new2) && (at < 0 || c < best)) {
+                    if (c <= gate_of(s) && (at < 0 || c < best)) {
                         best = c;
                         at = s;
                     }
@@ -231,17 +277,12 @@ __device__ __forceinline__ void associate_body(const DetectionsOut &det, int cou
         const typename Motion::Word w = mo.word(s);
         const int hits = st.trk_hits[s];
         const double ox = st.trk_pos[2 * s], oy = st.trk_pos[2 * s + 1];
+        const typename Motion::More more = mo.more(st, s);
         if (tgate[s] < 0) continue;
         const int was = tstate[s];
         if (assoc_taken(was)) {
             const int j = assoc_partner(was);
-            const double k = mo.steps(w);
-            const double px = dp[2 * j], py = dp[2 * j + 1];
-            st.trk_vel[2 * s] = assoc_velocity(px, ox, k);
-            st.trk_vel[2 * s + 1] = assoc_velocity(py, oy, k);
-            st.trk_pos[2 * s] = px;
-            st.trk_pos[2 * s + 1] = py;
-            mo.matched(s);
+            mo.update(st, s, w, more, tq[2 * s], tq[2 * s + 1], dp[2 * j], dp[2 * j + 1], ox, oy);
             st.trk_hits[s] = hits + 1;
             det.id_at(j) = id;
             tgate[s] = 0;

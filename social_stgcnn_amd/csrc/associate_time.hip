@@ -20,13 +20,19 @@
 
 namespace stg {
 
-constexpr int kFlagAssocTimeOrder = STG_ASSOC_TIME_ORDER;
-
 // The timed motion: the word is trk_t, the time of the slot's last match.  t_now is filled in on the device.
 struct TimedMotion {
     int64_t *trk_t;          // (C)
     int64_t t_now, step, max_age;
     using Word = int64_t;
+    using More = AssocNoMore;
+    static constexpr bool kSlotGate = false;
+    __device__ __forceinline__ More more(const AssocState &, int) const { return {}; }
+    __device__ __forceinline__ void update(const AssocState &st, int s, Word t, const More &, double, double, double px,
+                                           double py, double ox, double oy) const {
+        assoc_two_sample(st, s, steps(t), px, py, ox, oy);
+        matched(s);
+    }
     __device__ __forceinline__ TimedMotion at(int64_t b, int C, int64_t t) const {
         return {trk_t + b * C, t, step, max_age};
     }
@@ -43,18 +49,6 @@ struct TimedMotion {
     }
     __device__ __forceinline__ void born(int s) const { trk_t[s] = t_now; }
 };
-
-// The order test of the timed push (frames_time.hip, step 0) on the same words.  A refused push: -1 to the ids of its
-// detections, the flag, nothing else.  Returns true when the push was refused; uniform over the block, no barrier.
-template <int kThreads>
-__device__ __forceinline__ bool assoc_refused(const DetectionsOut &det, int count, int M_max, int64_t t_now,
-                                              const int64_t *clock, int32_t *assoc_flags) {
-    if (!(clock[1] > 0 && t_now <= clock[0])) return false;
-    const int m = count < 0 ? 0 : (count > M_max ? M_max : count);
-    for (int j = threadIdx.x; j < m; j += kThreads) det.id_at(j) = -1;
-    if (threadIdx.x == 0) assoc_flags[0] = kFlagAssocTimeOrder;
-    return true;
-}
 
 __global__ __launch_bounds__(kAssocThreads) void associate_timed_kernel(
     int64_t *__restrict__ det_id, const double *__restrict__ det_xy, const int32_t *__restrict__ det_count,

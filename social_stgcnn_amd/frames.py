@@ -35,6 +35,9 @@ stg_frame_scenes over a recording uploaded once, stg_track_push with the track s
     TimedAssociateSpec associate=TimedAssociateSpec(gate, gate_new, max_age) together with time=: the association at the
                        tracker's own rate, push(None, xy, t=TICKS); a track keeps the time of its last match and its
                        velocity per model step (stg_associate_timed ahead of the timed push)
+    FilteredAssociateSpec  associate=FilteredAssociateSpec(sigma_det, sigma_acc, ...) together with time=: the timed
+                       association for NOISY detections; a track keeps a constant-velocity Kalman state and its gate
+                       follows the predicted uncertainty (stg_associate_filtered); `.assoc_tracks()`
     TimedHarvestSpec   harvest=TimedHarvestSpec(windows, rows, min_peds, pred_len, settle) together with time=: the
                        harvest of HarvestSpec on the timed tracks resampled on the step grid (stg_window_harvest_timed,
                        DESIGN.md 5.27)
@@ -150,7 +153,7 @@ class TimeRule(collections.namedtuple("TimeRule", "step max_dt history")):
 
 
 ASSOC_FULL = 1                         # STG_ASSOC_FULL, a bit of `.assoc_flags`
-ASSOC_TIME_ORDER = 2                   # STG_ASSOC_TIME_ORDER (only under a TimedAssociateSpec)
+ASSOC_TIME_ORDER = 2                   # STG_ASSOC_TIME_ORDER (only under a TimedAssociateSpec or FilteredAssociateSpec)
 
 
 class AssociateSpec(collections.namedtuple("AssociateSpec", "gate gate_new max_miss capacity")):
@@ -207,6 +210,45 @@ class TimedAssociateSpec(collections.namedtuple("TimedAssociateSpec", "gate gate
             raise ValueError("TimedAssociateSpec: max_age must be an integer number of ticks in [0, 2^31), got %r"
                              % (max_age,))
         return super().__new__(cls, base.gate, base.gate_new, int(max_age), base.capacity)
+
+
+class FilteredAssociateSpec(collections.namedtuple(
+        "FilteredAssociateSpec", "sigma_det sigma_acc sigma_vel0 gate_sigmas gate_max max_age capacity")):
+    """TimedAssociateSpec for NOISY detections (only together with time=TimeRule(...)): a track keeps a
+    constant-velocity Kalman state -- the filtered position, the filtered velocity per model step and their covariance
+    -- in the place of the last detection and a two-sample velocity, which amplifies the detector's noise by the number
+    of pushes per step.  sigma_det: the detector's noise per axis (m); sigma_acc: the walker's random acceleration (m per
+    step^1.5; 0: straight walkers); sigma_vel0: how uncertain a new track's velocity is (m per step).  A track reaches the
+    detections within gate_sigmas standard deviations of its predicted position -- the gate grows with the gap since
+    the last match and with a young track's unknown velocity -- and never further than gate_max (m).  The matching
+    itself, max_age, capacity, the refused push (ids -1, ASSOC_TIME_ORDER) and everything behind the ids are
+    TimedAssociateSpec's; the scene still holds what the detector reported, `.assoc_tracks()` the smoothed state."""
+    __slots__ = ()
+
+    def __new__(cls, sigma_det, sigma_acc, sigma_vel0=1.5, gate_sigmas=5.0, gate_max=2.0, max_age=0, capacity=None):
+        vals = {"sigma_det": sigma_det, "sigma_acc": sigma_acc, "sigma_vel0": sigma_vel0, "gate_sigmas": gate_sigmas,
+                "gate_max": gate_max}
+        for name, x in vals.items():
+            low = name == "sigma_acc"
+            if not _is_number(x) or not (x >= 0 if low else x > 0):
+                raise ValueError("FilteredAssociateSpec: %s must be a finite number %s 0, got %r"
+                                 % (name, ">=" if low else ">", x))
+            sq = float(x) * float(x)
+            if not np.isfinite(sq) or (sq == 0.0 and not low):
+                raise ValueError("FilteredAssociateSpec: the squared %s must be finite and > 0 in float64, got %r"
+                                 % (name, x))
+        max_age = 0 if max_age is None else max_age
+        if not _is_number(max_age) or not _is_int(max_age, 0, (1 << 31) - 1):
+            raise ValueError("FilteredAssociateSpec: max_age must be an integer number of ticks in [0, 2^31), got %r"
+                             % (max_age,))
+        if capacity is not None and (not _is_number(capacity) or not _is_int(capacity, 1, MAX_SLOTS)):
+            raise ValueError("FilteredAssociateSpec: capacity must be None or an integer in [1, %d], got %r"
+                             % (MAX_SLOTS, capacity))
+        return super().__new__(cls, *(float(x) for x in vals.values()), int(max_age),
+                               None if capacity is None else int(capacity))
+
+
+_TIMED_ASSOC = (TimedAssociateSpec, FilteredAssociateSpec)     # the association specs that go with time= only
 
 
 MAX_WINDOW_STEPS = 32                  # STG_HARVEST_MAX_STEPS: a harvest word is 32 bits
@@ -548,7 +590,8 @@ class _LivePredictor:
         _harvest()               with harvest=: launch its window harvest on the track state, behind _push
 
     and `seed_dev`, the (1,) int64 device tensor the sampler reads its seed from."""
-    assoc = None                         # the AssociateSpec or TimedAssociateSpec; None: ids come with the pushes
+    assoc = None                         # the AssociateSpec, TimedAssociateSpec or FilteredAssociateSpec; None: ids come
+                                         # with the pushes
     _score_pushed = None                 # the (NS,) int32 `pushed` words a timed score launch reads; None: one stream
 
     harvest = None                       # the LiveWindows of a predictor made with harvest=; None without
@@ -565,14 +608,14 @@ class _LivePredictor:
         if timed_harvest and time is None:
             raise ValueError("harvest=TimedHarvestSpec(...) needs time=TimeRule(...): its frames are instants of the "
                              "step grid (without time= the push-indexed HarvestSpec serves)")
-        timed_assoc = isinstance(associate, TimedAssociateSpec)
+        timed_assoc = isinstance(associate, _TIMED_ASSOC)
         if timed_assoc and time is None:
-            raise ValueError("associate=TimedAssociateSpec(...) needs time=TimeRule(...): its tracks are aged by time "
-                             "(without time= the push-indexed AssociateSpec serves)")
+            raise ValueError("associate=%s(...) needs time=TimeRule(...): its tracks are aged by time "
+                             "(without time= the push-indexed AssociateSpec serves)" % type(associate).__name__)
         if associate is not None and time is not None and not timed_assoc:
             raise ValueError("associate= together with time= is not supported: a velocity per tick and a gate that "
                              "grows with the gap are a change of their own (DESIGN.md 8)")
-        if associate is not None and not isinstance(associate, (AssociateSpec, TimedAssociateSpec)):
+        if associate is not None and not isinstance(associate, (AssociateSpec,) + _TIMED_ASSOC):
             associate = AssociateSpec(*associate) if isinstance(associate, (tuple, list)) else AssociateSpec(associate)
         self.assoc = associate
         self._assoc_state = None
@@ -653,10 +696,12 @@ class _LivePredictor:
             self._forget = (self.slot_head, self.clock, self.head_flags)     # (a ring holds what its count says)
         if self.assoc is not None:
             # the association state: slot ids, positions, velocities, misses (under a TimedAssociateSpec the times of
-            # the last match in their place), hits; per stream next_id and the flags
+            # the last match in their place, under a FilteredAssociateSpec also the covariances), hits; per stream
+            # next_id and the flags
             c = self.s if self.assoc.capacity is None else self.assoc.capacity
             one = lead or (1,)
-            timed = isinstance(self.assoc, TimedAssociateSpec)
+            timed = isinstance(self.assoc, _TIMED_ASSOC)
+            filtered = isinstance(self.assoc, FilteredAssociateSpec)
             self.trk_id = torch.empty(lead + (c,), device=dev, dtype=torch.int64)
             self.trk_pos = torch.zeros(lead + (c, 2), device=dev, dtype=torch.float64)
             self.trk_vel = torch.zeros(lead + (c, 2), device=dev, dtype=torch.float64)
@@ -667,11 +712,14 @@ class _LivePredictor:
             self.trk_hits = torch.zeros(lead + (c,), device=dev, dtype=torch.int32)
             self.next_id = torch.zeros(one, device=dev, dtype=torch.int64)
             self.assoc_flags = torch.zeros(one, device=dev, dtype=torch.int32)
+            if filtered:
+                self.trk_cov = torch.zeros(lead + (c, 3), device=dev, dtype=torch.float64)
             self._assoc_state = (self.trk_id, self.trk_pos, self.trk_vel, self.trk_t if timed else self.trk_miss,
-                                 self.trk_hits, self.next_id, self.assoc_flags)
-            # (the gates travel squared, in float64; the lifetime as max_miss pushes, or as (step, max_age) ticks)
-            self._assoc_args = (c, ctypes.c_double(self.scale), ctypes.c_double(self.assoc.gate * self.assoc.gate),
-                                ctypes.c_double(self.assoc.gate_new * self.assoc.gate_new),
+                                 *((self.trk_cov,) if filtered else ()), self.trk_hits, self.next_id, self.assoc_flags)
+            # (the gates, or the filter's five parameters, travel squared, in float64; the lifetime as max_miss pushes,
+            # or as (step, max_age) ticks)
+            squared = self.assoc[:5] if filtered else (self.assoc.gate, self.assoc.gate_new)
+            self._assoc_args = (c, ctypes.c_double(self.scale), *(ctypes.c_double(x * x) for x in squared),
                                 *((self.time.step, self.assoc.max_age) if timed else (self.assoc.max_miss,)))
         self._pred = Predictor(self.model, self.k, *self._risk_args)
         if self.score_spec is not None:
@@ -762,12 +810,30 @@ class _LivePredictor:
             else:
                 x.index_fill_(0, at, fill)
 
+    def assoc_tracks(self, host=False):
+        """With associate=: the association's live tracks, (ids (n,) int64, pos (n,2) float64, vel (n,2) float64) in slot
+        order -- under a FilteredAssociateSpec the smoothed positions and the smoothed velocities per model step, under
+        the other two specs the last matched detections and the two-sample velocities (per push, or per model step).
+        A StreamsPredictor returns one such triple per stream.  Device tensors, or with host=True numpy copies; host
+        side only: it waits for the device and is no part of a captured push."""
+        if self._assoc_state is None:
+            raise ValueError("assoc_tracks() needs associate=: without it the ids come with the pushes")
+
+        def one(ids, pos, vel):
+            at = torch.nonzero(ids >= 0).flatten()
+            got = (ids[at], pos[at], vel[at])
+            return tuple(x.cpu().numpy() for x in got) if host else got
+        if self.trk_id.dim() == 1:
+            return one(self.trk_id, self.trk_pos, self.trk_vel)
+        return [one(self.trk_id[b], self.trk_pos[b], self.trk_vel[b]) for b in range(self.trk_id.shape[0])]
+
     def _launch_associate(self, name, det, when, sizes):
         """The association kernel `name` on the detections `det` (its leading arguments), the sizes behind them and the
-        association state: it writes the ids the push kernel behind it reads.  Under a TimedAssociateSpec the timed twin:
-        `when`, the time(s) the timed push reads, and that push's clock go between the detections and the sizes."""
-        if isinstance(self.assoc, TimedAssociateSpec):
-            name += "_timed"
+        association state: it writes the ids the push kernel behind it reads.  Under a TimedAssociateSpec the timed twin,
+        under a FilteredAssociateSpec the filtered one: `when`, the time(s) the timed push reads, and that push's clock
+        go between the detections and the sizes."""
+        if isinstance(self.assoc, _TIMED_ASSOC):
+            name += "_filtered" if isinstance(self.assoc, FilteredAssociateSpec) else "_timed"
             det += (when, ptr(self.clock))
         check(getattr(lib(), name)(*det, *sizes, *map(ptr, self._assoc_state), *self._assoc_args, stream_ptr()), name)
 

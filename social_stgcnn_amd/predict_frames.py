@@ -7,7 +7,9 @@ trajectories for every pedestrian tracked over the last obs_seq_len frames.
                                                [--step TICKS [--max_dt D] [--history R] [--max_peds V]
                                                 [--score [--pending N]]
                                                 [--harvest_timed WINDOWS [--settle D] [--harvest_out FILE.npz]]
-                                                [--associate_timed GATE[,GATE_NEW[,MAX_AGE]]]]
+                                                [--associate_timed GATE[,GATE_NEW[,MAX_AGE]]]
+                                                [--associate_filtered SIGMA_DET,SIGMA_ACC[,SIGMA_VEL0[,GATE_SIGMAS
+                                                                      [,GATE_MAX[,MAX_AGE]]]]]]
                                                [--associate GATE[,GATE_NEW[,MAX_MISS]] [--max_peds V]]
                                                [--harvest WINDOWS [--harvest_out FILE.npz] [--max_peds V]]
                                                --out preds.npz
@@ -63,6 +65,11 @@ number is one timed push of positions only, rows in file order, through a captur
 associate=frames.TimedAssociateSpec(...)) (MAX_AGE in ticks, default 0).  The .npz is --step's, its ids
 the assigned track ids, and assoc_ids (M,) int64 as with --associate.  It goes together with --score and
 --harvest_timed; not with --associate.
+
+--step TICKS --associate_filtered SIGMA_DET,SIGMA_ACC[,SIGMA_VEL0[,GATE_SIGMAS[,GATE_MAX[,MAX_AGE]]]] is the same for a
+noisy detector: associate=frames.FilteredAssociateSpec(...), a constant-velocity Kalman filter per track
+and a gate of GATE_SIGMAS standard deviations of the predicted position, at most GATE_MAX.  The same arrays; the scenes
+hold the detections as reported.  Not with --associate or --associate_timed.
 """
 import argparse
 import os
@@ -72,7 +79,7 @@ import numpy as np
 import torch
 
 from . import data
-from .frames import (AssociateSpec, FramePredictor, HarvestSpec, TimedAssociateSpec, TimedHarvestSpec, TimeRule, TrackRule,
+from .frames import (AssociateSpec, FilteredAssociateSpec, FramePredictor, HarvestSpec, TimedAssociateSpec, TimedHarvestSpec, TimeRule, TrackRule,
                      predict_recording, score_summary, sorted_rows)
 from .model import social_stgcnn
 from .predict import RiskSpec, TimedScoreSpec
@@ -112,6 +119,10 @@ def build_parser():
     p.add_argument("--associate_timed", default=None, metavar="GATE[,GATE_NEW[,MAX_AGE]]",
                    help="with --step: ignore the id column and associate the timed detections to tracks on the device, "
                         "a track forgotten MAX_AGE ticks after its last match (assoc_ids array; not with --associate)")
+    p.add_argument("--associate_filtered", default=None,
+                   metavar="SIGMA_DET,SIGMA_ACC[,SIGMA_VEL0[,GATE_SIGMAS[,GATE_MAX[,MAX_AGE]]]]",
+                   help="with --step: --associate_timed for a noisy detector, a Kalman filter per track and a gate that "
+                        "follows the predicted uncertainty (not with --associate or --associate_timed)")
     p.add_argument("--harvest", type=int, default=None, metavar="WINDOWS",
                    help="push the recording frame by frame and keep up to this many of the training windows its tracks "
                         "complete (not with --step, --associate or --radius / --zones)")
@@ -230,8 +241,25 @@ def parse_associate_timed(spec):
                               int(parts[2]) if len(parts) > 2 else 0)
 
 
+def parse_associate_filtered(spec):
+    """'SIGMA_DET,SIGMA_ACC[,SIGMA_VEL0[,GATE_SIGMAS[,GATE_MAX[,MAX_AGE]]]]' -> frames.FilteredAssociateSpec."""
+    parts = spec.split(",")
+    if not 2 <= len(parts) <= 6:
+        raise ValueError("--associate_filtered: SIGMA_DET,SIGMA_ACC[,SIGMA_VEL0[,GATE_SIGMAS[,GATE_MAX[,MAX_AGE]]]] "
+                         "expected, got %r" % spec)
+    return FilteredAssociateSpec(*(float(x) for x in parts[:5]), **({"max_age": int(parts[5])} if len(parts) > 5 else {}))
+
+
 def check_associate_timed_args(a):
-    """The refusals of --associate_timed, ahead of anything that needs the device -> None or the TimedAssociateSpec."""
+    """The refusals of --associate_timed and --associate_filtered, ahead of anything that needs the device -> None, the
+    TimedAssociateSpec or the FilteredAssociateSpec."""
+    if a.associate_filtered is not None:
+        for other in ("associate", "associate_timed"):
+            if getattr(a, other) is not None:
+                raise ValueError("--associate_filtered does not go together with --%s: a feed is associated by one rule" % other)
+        if a.step is None:
+            raise ValueError("--associate_filtered needs --step TICKS: its tracks are aged by time")
+        return parse_associate_filtered(a.associate_filtered)
     if a.associate_timed is None:
         return None
     if a.associate is not None:

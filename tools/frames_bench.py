@@ -8,7 +8,9 @@
     python tools/frames_bench.py --cases associate [--streams 1,64,600] [--ticks 200] [--associate 1.0,2.0,0]
                                  [--no-lone]
     python tools/frames_bench.py --cases associate_timed [--streams 1,64,600] [--ticks 200] [--time 10,10]
-                                 [--associate_timed 1.0,2.0,0] [--no-lone]
+                                 [--associate_timed 1.0,2.0,0] [--no-lone] [--noise SIGMA]
+    python tools/frames_bench.py --cases associate_filtered [--streams 1,64,600] [--ticks 200] [--time 10,10]
+                                 [--associate_filtered 0.05,1.0] [--no-lone] [--noise SIGMA]
     python tools/frames_bench.py --cases harvest [--streams 1,64,600] [--ticks 200] [--pushes 2000]
     python tools/frames_bench.py --harvest ...          the latency and streams cases with harvest=HarvestSpec(...)
     python tools/frames_bench.py --tracks 2,2 ...       every case under frames.TrackRule(2, 2) (the *_rule kernels)
@@ -51,6 +53,11 @@
              --streams); then, on crowds_zara01 upsampled 4x (step 4), a captured timed FramePredictor with
              score=TimedScoreSpec() fed the recording's own ids and one fed none: best-of-K ADE / FDE of both and the
              share of wrong links.
+
+  associate_filtered  the associate_timed case under associate=FilteredAssociateSpec(...) (DESIGN.md 5.29;
+             stg_associate_streams_filtered).  --noise SIGMA adds seeded Gaussian noise of that many metres to every
+             detection of the feeds of both timed association cases (rounded to 4 decimals, as a recording is), so that
+             both rules can be measured on the same noisy feed.
 
   harvest    the window harvest: the latency case (students001, max_peds 128) and the streams case at
              NS = 1, 64 and 600 (or --streams), each with and without harvest=HarvestSpec(...) sized so that the log never
@@ -127,6 +134,12 @@ def timed_pushes(rows, step, up):
     return out
 
 
+def noisy(pushes, sigma, seed):
+    """Seeded Gaussian detector noise on every detection of [(ids, xy, ...)], rounded to 4 decimals."""
+    gen = np.random.default_rng(seed)
+    return [(p[0], np.around(p[1] + gen.normal(0, sigma, np.shape(p[1])), 4)) + tuple(p[2:]) for p in pushes]
+
+
 def harvest_spec(windows, timed=None):
     """A log that `windows` windows of up to 32 rows never fill; with --time the timed spec (settle at its default)."""
     from social_stgcnn_amd import frames
@@ -195,10 +208,12 @@ def _stream_sequences(ns, n, timed=None):
 
 
 def streams_case(ns, k, n_ticks, dev, block=0, lone=True, max_peds=128, warmup=20, risk="none", tracks=None,
-                 score=None, timed=None, associate=None, harvest=False):
+                 score=None, timed=None, associate=None, harvest=False, noise=0.0):
     from social_stgcnn_amd import frames
     model = model_for("univ", dev)
     seq = _stream_sequences(ns, warmup + n_ticks, timed)
+    if noise > 0:
+        seq = [noisy(q, noise, b) for b, q in enumerate(seq)]
     # a recording that wraps inside the run would push a time that is not after the last: keep the run inside it
     if timed is not None and any(q[t + 1][2] <= q[t][2] for q in seq for t in range(len(q) - 1)):
         raise SystemExit("--time: %d ticks wrap a recording; use fewer --ticks" % (warmup + n_ticks))
@@ -235,7 +250,7 @@ def streams_case(ns, k, n_ticks, dev, block=0, lone=True, max_peds=128, warmup=2
            "frames_per_s_p50": round(ns * 1e3 / p50, 1), "mean_peds": round(float(peds.mean()), 2),
            "max_peds_seen": int(peds.max()), "host_p50_ms": round(float(np.percentile(host, 50)) * 1e3, 4)}
     if associate is not None:
-        res["associate"] = list(associate[:3])
+        res["associate"] = list(associate[:-1])
         res["assoc_full"] = int((sp.assoc_flags != 0).sum())
     if tracks is not None:
         res["tracks"] = list(tracks)
@@ -313,16 +328,19 @@ def associate_quality(split, rec, k, dev, spec, max_peds=128):
     return res
 
 
-def associate_timed_quality(split, rec, k, dev, spec, step=4, up=4, max_peds=128):
-    """One recording upsampled `up` x through two captured timed FramePredictors with score=TimedScoreSpec(): one fed the
-    recording's ids, one fed positions only."""
+def associate_timed_quality(split, rec, k, dev, spec, step=4, up=4, max_peds=128, noise=0.0):
+    """One recording upsampled `up` x (with `noise` metres of seeded Gaussian noise on every detection) through two
+    captured timed FramePredictors with score=TimedScoreSpec(): one fed the recording's ids, one fed positions only."""
     from social_stgcnn_amd import data, frames
     from social_stgcnn_amd.predict import TimedScoreSpec
     pushes = timed_pushes(data.read_file(os.path.join(DATA, rec)), step, up)
+    if noise > 0:
+        pushes = noisy(pushes, noise, 1)
     model = model_for(split, dev)
     score = TimedScoreSpec(pending=max(128, 2 * up * CFG["pred_seq_len"]))
-    res = {"case": "associate_timed_quality", "recording": os.path.basename(rec), "k": k, "associate": list(spec[:3]),
-           "time": [step, up], "pushes": len(pushes)}
+    res = {"case": "associate_filtered_quality" if isinstance(spec, frames.FilteredAssociateSpec)
+           else "associate_timed_quality", "recording": os.path.basename(rec), "k": k, "associate": list(spec[:-1]),
+           "time": [step, up], "pushes": len(pushes), "noise": noise}
     for name, assoc in (("ids", None), ("assoc", spec)):
         fp = frames.FramePredictor(model, k=k, max_peds=max_peds, score=score, time=frames.TimeRule(step), associate=assoc)
         replay = fp.capture()
@@ -369,6 +387,11 @@ def main():
                     help="the AssociateSpec of the associate case")
     ap.add_argument("--associate_timed", default="1.0,2.0,0", metavar="GATE[,GATE_NEW[,MAX_AGE]]",
                     help="the TimedAssociateSpec of the associate_timed case (MAX_AGE in ticks)")
+    ap.add_argument("--associate_filtered", default="0.05,1.0",
+                    metavar="SIGMA_DET,SIGMA_ACC[,SIGMA_VEL0[,GATE_SIGMAS[,GATE_MAX[,MAX_AGE]]]]",
+                    help="the FilteredAssociateSpec of the associate_filtered case (MAX_AGE in ticks)")
+    ap.add_argument("--noise", type=float, default=0.0, metavar="SIGMA",
+                    help="associate_timed and associate_filtered: Gaussian noise of SIGMA metres on every detection")
     a = ap.parse_args()
     tracks = None if a.tracks is None else tuple(int(x) for x in a.tracks.split(","))
     timed = None
@@ -425,20 +448,27 @@ def main():
         for split, rec in (() if a.no_lone else (("zara1", "zara1_test/crowds_zara01.txt"),
                                                  ("univ", "univ_test/students003.txt"))):
             print(json.dumps(associate_quality(split, rec, a.k, dev, spec)), flush=True)
-    if "associate_timed" in cases:
-        from social_stgcnn_amd.frames import TimedAssociateSpec
-        g = a.associate_timed.split(",")
-        spec = TimedAssociateSpec(float(g[0]), float(g[1]) if len(g) > 1 else None, int(g[2]) if len(g) > 2 else 0)
+    for case in ("associate_timed", "associate_filtered"):
+        if case not in cases:
+            continue
+        from social_stgcnn_amd.frames import FilteredAssociateSpec, TimedAssociateSpec
+        if case == "associate_timed":
+            g = a.associate_timed.split(",")
+            spec = TimedAssociateSpec(float(g[0]), float(g[1]) if len(g) > 1 else None, int(g[2]) if len(g) > 2 else 0)
+        else:
+            g = a.associate_filtered.split(",")
+            spec = FilteredAssociateSpec(*(float(x) for x in g[:5]), **({"max_age": int(g[5])} if len(g) > 5 else {}))
         t10 = (10, 10, a.history) if timed is None else timed
         for ns in (int(n) for n in (a.streams if a.streams != "1,8,64,256,600" else "1,64,600").split(",")):
-            off = streams_case(ns, a.k, a.ticks, dev, 0, False, tracks=tracks, timed=t10)
-            on = streams_case(ns, a.k, a.ticks, dev, 0, False, tracks=tracks, timed=t10, associate=spec)
-            on.update({"case": "associate_timed", "tick_p50_ms_without": off["tick_p50_ms"],
+            off = streams_case(ns, a.k, a.ticks, dev, 0, False, tracks=tracks, timed=t10, noise=a.noise)
+            on = streams_case(ns, a.k, a.ticks, dev, 0, False, tracks=tracks, timed=t10, associate=spec, noise=a.noise)
+            on.update({"case": case, "noise": a.noise, "tick_p50_ms_without": off["tick_p50_ms"],
                        "tick_p90_ms_without": off["tick_p90_ms"], "host_p50_ms_without": off["host_p50_ms"],
                        "associate_cost_p50_ms": round(on["tick_p50_ms"] - off["tick_p50_ms"], 4)})
             print(json.dumps(on), flush=True)
         if not a.no_lone:
-            print(json.dumps(associate_timed_quality("zara1", "zara1_test/crowds_zara01.txt", a.k, dev, spec)), flush=True)
+            print(json.dumps(associate_timed_quality("zara1", "zara1_test/crowds_zara01.txt", a.k, dev, spec,
+                                                     noise=a.noise)), flush=True)
     if "streams" in cases:
         for block in (int(b) for b in a.block.split(",")):
             for ns in (int(n) for n in a.streams.split(",")):
