@@ -47,22 +47,17 @@
 //            row m mod P
 // No host synchronisation (the launch is captured into the live predictors' graph), plain C++ stores only, 24 KB of
 // dynamic LDS at the 2,048-detection limit (under the 64 KB the launches name: the kernel's limit is never raised).
+//
+// The arithmetic of `values`, the trajectory values and totals columns, the covariance sum and the column copies of the
+// enqueue and the host's checks of the prediction are score_fn.hpp's, shared with score_time.hip.  This
+// file keeps what is its own: the truth from the sorted detections, a wave per horizon, the launch's outputs.
 #include "detections.hpp"
 #include "score_fn.hpp"
 
 namespace stg {
 
-constexpr int kScoreThreads = 256;
-constexpr int kScoreWaves = kScoreThreads / kWave;
-constexpr int kScoreCols = 5;                      // totals columns ahead of the coverage counts
-
 struct ScoreArgs {
-    // the prediction as the chain leaves it
-    const float *mean, *v_pred;
-    int64_t p_sn, p_sf, p_sp, p_sv;
-    const float *samples;
-    const int64_t *ids;
-    const int32_t *num_peds;
+    ScorePred pred;
     stg_score_state st;
     const float *thr;
     stg_score_out out;
@@ -110,12 +105,13 @@ __device__ __forceinline__ void score_push_body(const ScoreArgs &a, int b, const
     const int head = (int)((uint32_t)hd[0] % (uint32_t)P), filled = hd[1] < 0 ? 0 : (hd[1] > P ? P : hd[1]);
     int64_t *rec_ids = a.st.rec_ids + (int64_t)b * P * V;
     int32_t *rec_peds = a.st.rec_peds + (int64_t)b * P;
-    float *rec_mean = a.st.rec_mean + (int64_t)b * P * P * V * 2;
-    float *rec_cov = a.st.rec_cov + (int64_t)b * P * P * V * 3;
-    float *rec_samples = K > 0 ? a.st.rec_samples + (int64_t)b * P * K * P * V * 2 : nullptr;
-    float *acc = K > 0 ? a.st.acc + (int64_t)b * P * K * V : nullptr;
-    float *acc_mean = a.st.acc_mean + (int64_t)b * P * V;
-    int32_t *steps = a.st.steps + (int64_t)b * P * V;
+    const ScoreRows tab = {a.st.rec_mean + (int64_t)b * P * P * V * 2,
+                            a.st.rec_cov + (int64_t)b * P * P * V * 3,
+                            K > 0 ? a.st.rec_samples + (int64_t)b * P * K * P * V * 2 : nullptr,
+                            K > 0 ? a.st.acc + (int64_t)b * P * K * V : nullptr,
+                            a.st.acc_mean + (int64_t)b * P * V,
+                            a.st.steps + (int64_t)b * P * V,
+                            P, V, K};
     double *totals = a.st.totals + (int64_t)b * P * W;
     double *traj_totals = a.st.traj_totals + (int64_t)b * 5;
     const int64_t ob = (int64_t)b * P * V;
@@ -133,9 +129,9 @@ __device__ __forceinline__ void score_push_body(const ScoreArgs &a, int b, const
         int np = pending ? rec_peds[r] : 0;
         np = np < 0 ? 0 : (np > V ? V : np);
         const bool retire = pending && h == P;
-        double part[kScoreCols + STG_SCORE_MAX_Q], tpart[5];
+        double part[kScoreRow], tpart[5];
 #pragma unroll
-        for (int i = 0; i < kScoreCols + STG_SCORE_MAX_Q; ++i) part[i] = 0.0;
+        for (int i = 0; i < kScoreRow; ++i) part[i] = 0.0;
 #pragma unroll
         for (int i = 0; i < 5; ++i) tpart[i] = 0.0;
         for (int v0 = 0; v0 < V; v0 += kWave) {
@@ -152,45 +148,14 @@ __device__ __forceinline__ void score_push_body(const ScoreArgs &a, int b, const
                     const int j = kidx[at];
                     const float tx = (float)round_pos(det.x(j), a.scale);
                     const float ty = (float)round_pos(det.y(j), a.scale);
-                    const int64_t e = ((int64_t)r * P + (h - 1)) * V + v;
-                    const float2 mu = *reinterpret_cast<const float2 *>(rec_mean + e * 2);
                     mt = 1;
                     oid = id;
-                    err = score_dist(mu.x, mu.y, tx, ty);
-                    score_gauss(mu.x - tx, mu.y - ty, rec_cov[e * 3], rec_cov[e * 3 + 1], rec_cov[e * 3 + 2], d2, nll);
-                    acc_mean[r * V + v] += err;
-                    steps[r * V + v] += 1;
-                    if (K > 0) {
-                        float bmin = INFINITY;
-                        for (int k = 0; k < K; ++k) {
-                            const int64_t se = (((int64_t)r * K + k) * P + (h - 1)) * V + v;
-                            const float2 s = *reinterpret_cast<const float2 *>(rec_samples + se * 2);
-                            const float d = score_dist(s.x, s.y, tx, ty);
-                            bmin = fminf(bmin, d);
-                            acc[((int64_t)r * K + k) * V + v] += d;
-                        }
-                        best = bmin;
-                    }
+                    score_entry(tab, r, h, v, tx, ty, err, d2, nll, best);
                 }
-                if (retire) {
-                    st = steps[r * V + v];
-                    if (st > 0) {
-                        if (K > 0) {
-                            float amin = INFINITY;
-                            for (int k = 0; k < K; ++k) amin = fminf(amin, acc[((int64_t)r * K + k) * V + v]);
-                            t_ade = amin / (float)st;
-                        }
-                        t_adem = acc_mean[r * V + v] / (float)st;
-                    }
+                if (retire) {                                       // from the accumulators just advanced
                     t_fde = best;
                     t_fdem = err;
-                    if (st == P) {
-                        tpart[0] += 1.0;
-                        tpart[1] += (double)t_ade;
-                        tpart[2] += (double)t_fde;
-                        tpart[3] += (double)t_adem;
-                        tpart[4] += (double)t_fdem;
-                    }
+                    st = score_retire(tab, r, v, t_fde, t_fdem, t_ade, t_adem, tpart);
                 }
             }
             const int64_t o = ob + (int64_t)(h - 1) * V + v;
@@ -208,21 +173,12 @@ __device__ __forceinline__ void score_push_body(const ScoreArgs &a, int b, const
                 a.out.traj_ade_mean[x] = t_adem;
                 a.out.traj_fde_mean[x] = t_fdem;
             }
-            if (mt) {
-                part[0] += 1.0;
-                part[1] += (double)err;
-                part[2] += (double)d2;
-                part[3] += (double)nll;
-                part[4] += (double)best;
-#pragma unroll
-                for (int q = 0; q < STG_SCORE_MAX_Q; ++q)
-                    if (q < Q && d2 <= a.thr[q]) part[kScoreCols + q] += 1.0;
-            }
+            if (mt) score_cols<true>(part, err, d2, nll, best, a.thr, Q);
         }
         // 3. the horizon's sums: the whole wave is here (h, pending and retire are uniform over it)
         if (pending) {
 #pragma unroll
-            for (int i = 0; i < kScoreCols + STG_SCORE_MAX_Q; ++i) {
+            for (int i = 0; i < kScoreRow; ++i) {
                 if (i < W) {                                        // (W is uniform)
                     const double s = wave_sum(part[i]);
                     if (lane == 0) totals[(h - 1) * W + i] += s;
@@ -239,51 +195,20 @@ __device__ __forceinline__ void score_push_body(const ScoreArgs &a, int b, const
     }
     __syncthreads();
 
-    // 4. enqueue: this push's record into the retired row, its accumulators zeroed
-    int npn = a.num_peds[b];
+    // 4. enqueue: this push's record into the retired row, its accumulators zeroed.  Every column v < V: those at or
+    //    past num_peds carry id -1 and a zero covariance
+    int npn = a.pred.num_peds[b];
     npn = npn < 0 ? 0 : (npn > V ? V : npn);
     for (int v = tid; v < V; v += kScoreThreads) {
-        rec_ids[head * V + v] = v < npn ? a.ids[(int64_t)b * V + v] : -1;
-        acc_mean[head * V + v] = 0.f;
-        steps[head * V + v] = 0;
-        {
-#pragma clang fp contract(off)
-            float cxx = 0.f, cxy = 0.f, cyy = 0.f;
-            for (int t = 0; t < P; ++t) {
-                float *c = rec_cov + (((int64_t)head * P + t) * V + v) * 3;
-                if (v < npn) {
-                    const float *q = a.v_pred + b * a.p_sn + v * a.p_sv + t * a.p_sp;
-                    const float sx = expf(q[2 * a.p_sf]), sy = expf(q[3 * a.p_sf]), rho = tanhf(q[4 * a.p_sf]);
-                    cxx += sx * sx;
-                    cxy += rho * sx * sy;
-                    cyy += sy * sy;
-                }
-                c[0] = cxx;
-                c[1] = cxy;
-                c[2] = cyy;
-            }
-        }
+        rec_ids[head * V + v] = v < npn ? a.pred.ids[(int64_t)b * V + v] : -1;
+        tab.acc_mean[head * V + v] = 0.f;
+        tab.steps[head * V + v] = 0;
+        score_cov_column(a.pred, b, tab, head, v, v < npn);
     }
-    // mean and samples: the columns of the scene's pedestrians only (nothing reads a slot at or past num_peds, and a
-    // scene of 15 in a padding of 128 would otherwise move eight times the bytes)
-    {
-        const float2 *src = reinterpret_cast<const float2 *>(a.mean + (int64_t)b * P * V * 2);
-        float2 *dst = reinterpret_cast<float2 *>(rec_mean + (int64_t)head * P * V * 2);
-        for (int e = tid; e < P * npn; e += kScoreThreads) {
-            const int t = e / npn, x = t * V + (e - t * npn);
-            dst[x] = src[x];
-        }
-    }
+    score_copy_mean(a.pred, b, tab, head, npn, [](int64_t) {});
     if (K > 0) {
-        const int pv = P * V;
-#pragma unroll 4
-        for (int e = tid; e < K * P * npn; e += kScoreThreads) {
-            const int row = e / npn, v = e - row * npn, k = row / P, x = (row - k * P) * V + v;      // row = k * P + t
-            const float2 *src = reinterpret_cast<const float2 *>(a.samples + ((int64_t)k * a.NS + b) * pv * 2);
-            float2 *dst = reinterpret_cast<float2 *>(rec_samples + ((int64_t)head * K + k) * pv * 2);
-            dst[x] = src[x];
-        }
-        for (int e = tid; e < K * V; e += kScoreThreads) acc[(int64_t)head * K * V + e] = 0.f;
+        score_copy_samples(a.pred, a.NS, b, tab, head, npn);
+        for (int e = tid; e < K * V; e += kScoreThreads) tab.acc[(int64_t)head * K * V + e] = 0.f;
     }
     if (tid == 0) {                                          // (every read of the head and of rec_peds is behind the barrier)
         rec_peds[head] = npn;
@@ -313,37 +238,23 @@ __global__ __launch_bounds__(kScoreThreads) void score_push_streams_kernel(const
 
 // the checks both entry points share, on `a` as the entry point filled it from its arguments; completes it (st, out, M2)
 static int score_args(const char *what, const stg_score_state *st, const stg_score_out *out, ScoreArgs *a) {
-    const int NS = a->NS, M_max = a->M_max, P = a->P, V = a->V, Q = a->Q;
-    int K = a->K;
-    const float *mean = a->mean, *v_pred = a->v_pred, *samples = a->samples, *thr = a->thr;
-    STG_REQUIRE(M_max >= 1 && P >= 1 && V >= 1 && K >= 0 && Q >= 0, STG_EINVAL,
-                "%s: bad sizes M_max=%d P=%d V=%d K=%d Q=%d", what, M_max, P, V, K, Q);
+    const int M_max = a->M_max, P = a->P, V = a->V, Q = a->Q;
+    STG_REQUIRE(M_max >= 1 && P >= 1 && V >= 1 && a->K >= 0 && Q >= 0, STG_EINVAL,
+                "%s: bad sizes M_max=%d P=%d V=%d K=%d Q=%d", what, M_max, P, V, a->K, Q);
     STG_REQUIRE(st && out, STG_EINVAL, "%s: null pointer (state / out)", what);
-    if (!samples) K = 0;
-    STG_REQUIRE(mean && v_pred && a->ids && a->num_peds, STG_EINVAL, "%s: null pointer (mean / v_pred / ids / num_peds)", what);
     STG_REQUIRE(st->rec_ids && st->rec_peds && st->rec_mean && st->rec_cov && st->acc_mean && st->steps && st->head &&
                     st->totals && st->traj_totals,
                 STG_EINVAL, "%s: null pointer in the state", what);
-    STG_REQUIRE(K == 0 || (st->rec_samples && st->acc), STG_EINVAL,
-                "%s: null pointer in the state (rec_samples / acc with K=%d)", what, K);
     STG_REQUIRE(out->rec_ids && out->matched && out->err && out->d2 && out->nll && out->traj_steps &&
                     out->traj_ade_mean && out->traj_fde_mean,
                 STG_EINVAL, "%s: null pointer among the outputs", what);
-    STG_REQUIRE(K == 0 || (out->best && out->traj_ade && out->traj_fde), STG_EINVAL,
-                "%s: null pointer among the outputs (best / traj_ade / traj_fde with K=%d)", what, K);
-    STG_REQUIRE(Q == 0 || thr, STG_EINVAL, "%s: null pointer (thr with Q=%d)", what, Q);
-    STG_REQUIRE(aligned(mean, 8) && aligned(samples, 8) && aligned(st->rec_mean, 8) && aligned(st->rec_samples, 8),
-                STG_EINVAL, "%s: mean / samples and their records must be 8-byte aligned", what);
+    const int rc = score_pred_args(what, &a->pred, a->thr, st->rec_mean, st->rec_samples, st->rec_samples && st->acc,
+                                   "rec_samples / acc", a->NS, P, V, &a->K, Q);
+    if (rc != STG_OK) return rc;
+    STG_REQUIRE(a->K == 0 || (out->best && out->traj_ade && out->traj_fde), STG_EINVAL,
+                "%s: null pointer among the outputs (best / traj_ade / traj_fde with K=%d)", what, a->K);
     STG_REQUIRE(M_max <= STG_TRACK_MAX_DETECTIONS, STG_EUNSUPPORTED, "%s: M_max=%d above STG_TRACK_MAX_DETECTIONS=%d",
                 what, M_max, STG_TRACK_MAX_DETECTIONS);
-    STG_REQUIRE(NS <= STG_TRACK_MAX_STREAMS, STG_EUNSUPPORTED, "%s: NS=%d above STG_TRACK_MAX_STREAMS=%d", what, NS,
-                STG_TRACK_MAX_STREAMS);
-    STG_REQUIRE(V <= STG_SCORE_MAX_V, STG_EUNSUPPORTED, "%s: V=%d above STG_SCORE_MAX_V=%d", what, V, STG_SCORE_MAX_V);
-    STG_REQUIRE(K <= STG_SCORE_MAX_K, STG_EUNSUPPORTED, "%s: K=%d above STG_SCORE_MAX_K=%d", what, K, STG_SCORE_MAX_K);
-    STG_REQUIRE(P <= STG_SCORE_MAX_P, STG_EUNSUPPORTED, "%s: P=%d above STG_SCORE_MAX_P=%d", what, P, STG_SCORE_MAX_P);
-    STG_REQUIRE(Q <= STG_SCORE_MAX_Q, STG_EUNSUPPORTED, "%s: Q=%d above STG_SCORE_MAX_Q=%d", what, Q, STG_SCORE_MAX_Q);
-    a->samples = K > 0 ? samples : nullptr;
-    a->K = K;
     a->st = *st;
     a->out = *out;
     a->M2 = det_sort_n(M_max);
@@ -359,8 +270,8 @@ int stg_score_push(const int64_t *det_id, const double *det_xy, const int32_t *d
                    const float *samples, const int64_t *ids, const int32_t *num_peds, int P, int V, int K,
                    const stg_score_state *state, const float *thr, int Q, const stg_score_out *out, void *stream) {
     stg::ScoreArgs a{};
-    a.mean = mean, a.v_pred = v_pred, a.samples = samples, a.ids = ids, a.num_peds = num_peds, a.thr = thr;
-    a.p_sn = p_sn, a.p_sf = p_sf, a.p_sp = p_sp, a.p_sv = p_sv, a.scale = scale;
+    a.pred = {mean, v_pred, p_sn, p_sf, p_sp, p_sv, samples, ids, num_peds};
+    a.thr = thr, a.scale = scale;
     a.NS = 1, a.P = P, a.V = V, a.K = K, a.Q = Q, a.M_max = M_max;
     const int rc = stg::score_args("stg_score_push", state, out, &a);
     if (rc != STG_OK) return rc;
@@ -379,8 +290,8 @@ int stg_score_push_streams(const int64_t *det_id, int64_t id_stride, const doubl
     int rc = stg::stream_args("stg_score_push_streams", NS, M_total, id_stride, xy_stride, 0, false);    // (see there)
     if (rc != STG_OK || NS == 0) return rc;
     stg::ScoreArgs a{};
-    a.mean = mean, a.v_pred = v_pred, a.samples = samples, a.ids = ids, a.num_peds = num_peds, a.thr = thr;
-    a.p_sn = p_sn, a.p_sf = p_sf, a.p_sp = p_sp, a.p_sv = p_sv, a.scale = scale;
+    a.pred = {mean, v_pred, p_sn, p_sf, p_sp, p_sv, samples, ids, num_peds};
+    a.thr = thr, a.scale = scale;
     a.NS = NS, a.P = P, a.V = V, a.K = K, a.Q = Q, a.M_max = M_max;
     rc = stg::score_args("stg_score_push_streams", state, out, &a);
     if (rc != STG_OK) return rc;

@@ -42,15 +42,16 @@
 //   retire   by the wave that owns the row
 //   enqueue  behind the barrier: the columns v < num_peds only, the tables zeroed for those columns only
 // No host synchronisation, plain C++ stores only, no scratch.
+//
+// The arithmetic of `values`, the trajectory values and totals columns, the covariance sum and the column copies of the
+// enqueue and the host's checks of the prediction are score_fn.hpp's, shared with score.hip.  This file
+// keeps what is its own: the truth interpolated from the track rings, a wave per record row behind the header pass, the
+// record's own tables.
 #include "detections.hpp"
 #include "score_fn.hpp"
 
 namespace stg {
 
-constexpr int kTScoreThreads = 256;
-constexpr int kTScoreWaves = kTScoreThreads / kWave;
-constexpr int kTScoreCols = 5;                          // totals columns ahead of the coverage counts
-constexpr int kTScoreRow = kTScoreCols + STG_SCORE_MAX_Q;
 enum { kRecEmpty = 0, kRecPending = 1, kRecRetired = 2 };
 
 // round(pa + (pb - pa) * w): the interpolation of the timed push (frames_time.hip), one IEEE operation at a time
@@ -81,15 +82,6 @@ struct TimedTracks {
     }
 };
 
-// The prediction as the chain leaves it: mean (NS,P,V,2), v_pred with strides, samples (K,NS,P,V,2), ids (NS,V)
-struct TimedScorePred {
-    const float *mean, *v_pred;
-    int64_t p_sn, p_sf, p_sp, p_sv;
-    const float *samples;
-    const int64_t *ids;
-    const int32_t *num_peds;
-};
-
 // stg_score_timed_state with its slicing rule
 struct TimedScoreState : stg_score_timed_state {
     __device__ __forceinline__ TimedScoreState of_stream(int64_t b, const TimedScoreDims &d) const {
@@ -101,13 +93,16 @@ struct TimedScoreState : stg_score_timed_state {
         s.matched += b * rpv, s.err += b * rpv, s.d2 += b * rpv, s.nll += b * rpv;
         s.traj_steps += b * rv, s.traj_ade_mean += b * rv, s.traj_fde_mean += b * rv;
         if (d.K > 0) s.traj_ade += b * rv, s.traj_fde += b * rv;
-        s.counters += b * 2, s.totals += b * d.P * (kTScoreCols + d.Q), s.traj_totals += b * 5;
+        s.counters += b * 2, s.totals += b * d.P * (kScoreCols + d.Q), s.traj_totals += b * 5;
         return s;
+    }
+    __device__ __forceinline__ ScoreRows tables(const TimedScoreDims &d) const {
+        return {rec_mean, rec_cov, rec_samples, acc, acc_mean, steps, d.P, d.V, d.K};
     }
 };
 
 struct TimedScoreArgs {
-    TimedScorePred pred;
+    ScorePred pred;
     TimedTracks trk;
     TimedScoreState st;
     const float *thr;
@@ -115,26 +110,27 @@ struct TimedScoreArgs {
     TimedScoreDims d;
 };
 
-// One timed push of stream b scored by one workgroup of kTScoreThreads threads; trk and st are the stream's own.
+// One timed push of stream b scored by one workgroup of kScoreThreads threads; trk and st are the stream's own.
 // LDS (dynamic): sort keys (S2 x int64), sort indices (S2 x int32)
 __device__ __forceinline__ void score_timed_body(const TimedScoreArgs &a, int b, const TimedTracks &trk,
                                                  const TimedScoreState &st, bool pushed) {
     extern __shared__ __align__(16) unsigned char lds[];
     int64_t *key = reinterpret_cast<int64_t *>(lds);
     int32_t *kidx = reinterpret_cast<int32_t *>(key + a.d.S2);
-    __shared__ double part[kTScoreWaves][STG_SCORE_MAX_P * kTScoreRow];
-    __shared__ double tpart[kTScoreWaves][5];
+    __shared__ double part[kScoreWaves][STG_SCORE_MAX_P * kScoreRow];
+    __shared__ double tpart[kScoreWaves][5];
     __shared__ int top;                                     // one past the highest slot that takes part
     __shared__ unsigned long long ta_low;                   // the oldest `ta` among them, biased to unsigned order
 
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-    const int P = a.d.P, V = a.d.V, K = a.d.K, Q = a.d.Q, W = kTScoreCols + Q, Rp = a.d.Rp, S = a.d.S, R = a.d.R;
+    const int P = a.d.P, V = a.d.V, K = a.d.K, Q = a.d.Q, W = kScoreCols + Q, Rp = a.d.Rp, S = a.d.S, R = a.d.R;
     const int64_t step = a.d.step, max_dt = a.d.max_dt;
+    const ScoreRows tab = st.tables(a.d);
     double *push_totals = a.out.push_totals + (int64_t)b * P * W, *push_traj = a.out.push_traj + (int64_t)b * 5;
 
     // 0. a stream not pushed, or a push the track kernel refused: nothing moves (uniform over the block)
     if (!pushed || (trk.head_flags[1] & STG_TRACK_TIME_ORDER) != 0) {
-        for (int e = tid; e < P * W; e += kTScoreThreads) push_totals[e] = 0.0;
+        for (int e = tid; e < P * W; e += kScoreThreads) push_totals[e] = 0.0;
         if (tid < 5) push_traj[tid] = 0.0;
         return;
     }
@@ -151,7 +147,7 @@ __device__ __forceinline__ void score_timed_body(const TimedScoreArgs &a, int b,
         ta_low = (unsigned long long)(t_now - 1) ^ kBias;
     }
     __syncthreads();
-    for (int p = tid; p < a.d.S2; p += kTScoreThreads) {
+    for (int p = tid; p < a.d.S2; p += kScoreThreads) {
         int64_t k = INT64_MAX;
         if (p < S) {
             const int h = (int)((uint32_t)trk.slot_head[2 * p] % (uint32_t)R), c = trk.slot_head[2 * p + 1];
@@ -166,19 +162,19 @@ __device__ __forceinline__ void score_timed_body(const TimedScoreArgs &a, int b,
         key[p] = k;
         kidx[p] = p;
     }
-    for (int e = tid; e < kTScoreWaves * STG_SCORE_MAX_P * kTScoreRow; e += kTScoreThreads) (&part[0][0])[e] = 0.0;
-    if (tid < kTScoreWaves * 5) (&tpart[0][0])[tid] = 0.0;
+    for (int e = tid; e < kScoreWaves * STG_SCORE_MAX_P * kScoreRow; e += kScoreThreads) (&part[0][0])[e] = 0.0;
+    if (tid < kScoreWaves * 5) (&tpart[0][0])[tid] = 0.0;
     __syncthreads();
     const int n2 = det_sort_n(top < 1 ? 1 : top);           // (<= S2; the keys from `top` on are padding)
     const int64_t ta_min = (int64_t)(ta_low ^ kBias);
-    det_sort(key, kidx, n2, tid, kTScoreThreads);
+    det_sort(key, kidx, n2, tid, kScoreThreads);
 
     // 2. score and retire: wave -> record, lane -> pedestrian
     //    The headers first, a lane per row of the wave (64 rows at a time): no bracket of this push reaches below
     //    ta_min, so a pending record with no instant in (ta_min, t_now] has no work -- at a steady feed all but the ~P
     //    records whose time is congruent to t_now mod step -- and the wave visits only the rows with work or to retire
-    for (int base = 0; base < Rp; base += kWave * kTScoreWaves) {
-      const int mine = base + lane * kTScoreWaves + wave;
+    for (int base = 0; base < Rp; base += kWave * kScoreWaves) {
+      const int mine = base + lane * kScoreWaves + wave;
       bool visit = false;
       if (mine < Rp && st.rec_status[mine] == kRecPending) {
           const int64_t t_m = st.rec_t[mine];
@@ -186,7 +182,7 @@ __device__ __forceinline__ void score_timed_body(const TimedScoreArgs &a, int b,
           visit = (m_lo < 1 ? 1 : m_lo) <= (m_hi > P ? P : m_hi) || t_now - t_m >= (int64_t)P * step;
       }
       for (unsigned long long rows = __ballot(visit); rows != 0; rows &= rows - 1) {     // uniform over the wave
-        const int r = base + (__ffsll(rows) - 1) * kTScoreWaves + wave;
+        const int r = base + (__ffsll(rows) - 1) * kScoreWaves + wave;
         const int64_t t_r = st.rec_t[r];
         int np = st.rec_peds[r];
         np = np < 0 ? 0 : (np > V ? V : np);
@@ -230,9 +226,9 @@ __device__ __forceinline__ void score_timed_body(const TimedScoreArgs &a, int b,
                 const int64_t tau = t_r + (int64_t)h * step;
                 const bool hit = h >= h_lo && h <= h_hi && (tau == t_now || !wide);
                 if (__ballot(hit) == 0) continue;           // uniform over the wave
-                double pt[kTScoreRow];
+                double pt[kScoreRow];
 #pragma unroll
-                for (int i = 0; i < kTScoreRow; ++i) pt[i] = 0.0;
+                for (int i = 0; i < kScoreRow; ++i) pt[i] = 0.0;
                 if (hit) {
                     double x = bx, y = by;
                     if (tau != t_now) {
@@ -240,42 +236,18 @@ __device__ __forceinline__ void score_timed_body(const TimedScoreArgs &a, int b,
                         x = lerp_pos(ax, bx, w, a.d.scale);
                         y = lerp_pos(ay, by, w, a.d.scale);
                     }
-                    const float tx = (float)x, ty = (float)y;
                     const int64_t e = ((int64_t)r * P + (h - 1)) * V + v;
-                    const float2 mu = *reinterpret_cast<const float2 *>(st.rec_mean + e * 2);
-                    float d2, nll, best = 0.f;
-                    const float err = score_dist(mu.x, mu.y, tx, ty);
-                    score_gauss(mu.x - tx, mu.y - ty, st.rec_cov[e * 3], st.rec_cov[e * 3 + 1], st.rec_cov[e * 3 + 2], d2,
-                                nll);
-                    st.acc_mean[(int64_t)r * V + v] += err;
-                    st.steps[(int64_t)r * V + v] += 1;
-                    if (K > 0) {
-                        float bmin = INFINITY;
-                        for (int k = 0; k < K; ++k) {
-                            const int64_t se = (((int64_t)r * K + k) * P + (h - 1)) * V + v;
-                            const float2 sm = *reinterpret_cast<const float2 *>(st.rec_samples + se * 2);
-                            const float dk = score_dist(sm.x, sm.y, tx, ty);
-                            bmin = fminf(bmin, dk);
-                            st.acc[((int64_t)r * K + k) * V + v] += dk;
-                        }
-                        best = bmin;
-                        st.best[e] = best;
-                    }
+                    float err, d2, nll, best;
+                    score_entry(tab, r, h, v, (float)x, (float)y, err, d2, nll, best);
+                    if (K > 0) st.best[e] = best;
                     st.matched[e] = 1;
                     st.err[e] = err;
                     st.d2[e] = d2;
                     st.nll[e] = nll;
-                    pt[0] = 1.0;
-                    pt[1] = (double)err;
-                    pt[2] = (double)d2;
-                    pt[3] = (double)nll;
-                    pt[4] = (double)best;
-#pragma unroll
-                    for (int q = 0; q < STG_SCORE_MAX_Q; ++q)
-                        if (q < Q && d2 <= a.thr[q]) pt[kTScoreCols + q] = 1.0;
+                    score_cols<false>(pt, err, d2, nll, best, a.thr, Q);
                 }
 #pragma unroll
-                for (int i = 0; i < kTScoreRow; ++i) {
+                for (int i = 0; i < kScoreRow; ++i) {
                     if (i < W) {                            // (W is uniform)
                         const double s = wave_sum(pt[i]);
                         if (lane == 0) part[wave][(h - 1) * W + i] += s;
@@ -285,32 +257,15 @@ __device__ __forceinline__ void score_timed_body(const TimedScoreArgs &a, int b,
             // 3. retire: the trajectory values from the accumulators this lane has just advanced
             if (retire && v < np) {
                 const int64_t x = (int64_t)r * V + v, eP = ((int64_t)r * P + (P - 1)) * V + v;
-                const int sn = st.steps[x];
-                float t_ade = 0.f, t_fde = 0.f, t_adem = 0.f;
-                if (sn > 0) {
-                    if (K > 0) {
-                        float amin = INFINITY;
-                        for (int k = 0; k < K; ++k) amin = fminf(amin, st.acc[((int64_t)r * K + k) * V + v]);
-                        t_ade = amin / (float)sn;
-                    }
-                    t_adem = st.acc_mean[x] / (float)sn;
-                }
-                const float t_fdem = st.err[eP];
+                const float t_fde = K > 0 ? st.best[eP] : 0.f, t_fdem = st.err[eP];     // h = P: from the record's tables
+                float t_ade, t_adem;
+                st.traj_steps[x] = score_retire(tab, r, v, t_fde, t_fdem, t_ade, t_adem, tp);
                 if (K > 0) {
-                    t_fde = st.best[eP];
                     st.traj_ade[x] = t_ade;
                     st.traj_fde[x] = t_fde;
                 }
-                st.traj_steps[x] = sn;
                 st.traj_ade_mean[x] = t_adem;
                 st.traj_fde_mean[x] = t_fdem;
-                if (sn == P) {
-                    tp[0] += 1.0;
-                    tp[1] += (double)t_ade;
-                    tp[2] += (double)t_fde;
-                    tp[3] += (double)t_adem;
-                    tp[4] += (double)t_fdem;
-                }
             }
         }
         if (retire) {                                       // the whole wave is here
@@ -326,7 +281,7 @@ __device__ __forceinline__ void score_timed_body(const TimedScoreArgs &a, int b,
     __syncthreads();
 
     // 4. the totals: the four waves' partials in wave order
-    for (int e = tid; e < P * W; e += kTScoreThreads) {
+    for (int e = tid; e < P * W; e += kScoreThreads) {
         const double s = ((part[0][e] + part[1][e]) + part[2][e]) + part[3][e];
         st.totals[e] += s;
         push_totals[e] = s;
@@ -338,10 +293,10 @@ __device__ __forceinline__ void score_timed_body(const TimedScoreArgs &a, int b,
     }
 
     // 5. enqueue: this push's record into row `head`, the columns of its pedestrians only
-    const TimedScorePred &pr = a.pred;
+    const ScorePred &pr = a.pred;
     int npn = pr.num_peds[b];
     npn = npn < 0 ? 0 : (npn > V ? V : npn);
-    for (int v = tid; v < V; v += kTScoreThreads) {
+    for (int v = tid; v < V; v += kScoreThreads) {
         const int64_t x = (int64_t)head * V + v;
         st.rec_ids[x] = v < npn ? pr.ids[(int64_t)b * V + v] : -1;
         if (v >= npn) continue;
@@ -355,46 +310,16 @@ __device__ __forceinline__ void score_timed_body(const TimedScoreArgs &a, int b,
             st.traj_fde[x] = 0.f;
             for (int k = 0; k < K; ++k) st.acc[((int64_t)head * K + k) * V + v] = 0.f;
         }
-        {
-#pragma clang fp contract(off)
-            float cxx = 0.f, cxy = 0.f, cyy = 0.f;
-            for (int t = 0; t < P; ++t) {
-                float *c = st.rec_cov + (((int64_t)head * P + t) * V + v) * 3;
-                const float *q = pr.v_pred + b * pr.p_sn + v * pr.p_sv + t * pr.p_sp;
-                const float sx = expf(q[2 * pr.p_sf]), sy = expf(q[3 * pr.p_sf]), rho = tanhf(q[4 * pr.p_sf]);
-                cxx += sx * sx;
-                cxy += rho * sx * sy;
-                cyy += sy * sy;
-                c[0] = cxx;
-                c[1] = cxy;
-                c[2] = cyy;
-            }
-        }
+        score_cov_column(pr, b, tab, head, v, true);
     }
-    {
-        const float2 *src = reinterpret_cast<const float2 *>(pr.mean + (int64_t)b * P * V * 2);
-        float2 *dst = reinterpret_cast<float2 *>(st.rec_mean + (int64_t)head * P * V * 2);
-        for (int e = tid; e < P * npn; e += kTScoreThreads) {
-            const int t = e / npn;
-            const int64_t x = (int64_t)t * V + (e - t * npn), y = (int64_t)head * P * V + x;
-            dst[x] = src[x];
-            st.matched[y] = 0;
-            st.err[y] = 0.f;
-            st.d2[y] = 0.f;
-            st.nll[y] = 0.f;
-            if (K > 0) st.best[y] = 0.f;
-        }
-    }
-    if (K > 0) {
-        const int pv = P * V;
-#pragma unroll 4
-        for (int e = tid; e < K * P * npn; e += kTScoreThreads) {
-            const int row = e / npn, v = e - row * npn, k = row / P, x = (row - k * P) * V + v;      // row = k * P + t
-            const float2 *src = reinterpret_cast<const float2 *>(pr.samples + ((int64_t)k * a.d.NS + b) * pv * 2);
-            float2 *dst = reinterpret_cast<float2 *>(st.rec_samples + ((int64_t)head * K + k) * pv * 2);
-            dst[x] = src[x];
-        }
-    }
+    score_copy_mean(pr, b, tab, head, npn, [&](int64_t y) {     // and the record's own tables, the same entries
+        st.matched[y] = 0;
+        st.err[y] = 0.f;
+        st.d2[y] = 0.f;
+        st.nll[y] = 0.f;
+        if (K > 0) st.best[y] = 0.f;
+    });
+    if (K > 0) score_copy_samples(pr, a.d.NS, b, tab, head, npn);
     if (tid == 0) {                                         // (behind the barrier: retirement has been written)
         const bool evicts = st.rec_status[head] == kRecPending;
         st.rec_t[head] = t_now;
@@ -405,12 +330,12 @@ __device__ __forceinline__ void score_timed_body(const TimedScoreArgs &a, int b,
     }
 }
 
-__global__ __launch_bounds__(kTScoreThreads) void score_push_timed_kernel(const TimedScoreArgs a) {
+__global__ __launch_bounds__(kScoreThreads) void score_push_timed_kernel(const TimedScoreArgs a) {
     score_timed_body(a, 0, a.trk, a.st, true);
 }
 
 // One workgroup per stream: stream b scores when pushed[b] != 0, as stg_track_push_streams_timed reads it
-__global__ __launch_bounds__(kTScoreThreads) void score_push_streams_timed_kernel(const TimedScoreArgs a,
+__global__ __launch_bounds__(kScoreThreads) void score_push_streams_timed_kernel(const TimedScoreArgs a,
                                                                                   const int32_t *__restrict__ pushed) {
     const int b = blockIdx.x;
     score_timed_body(a, b, a.trk.of_stream(b, a.d), a.st.of_stream(b, a.d), pushed[b] != 0);
@@ -420,7 +345,6 @@ __global__ __launch_bounds__(kTScoreThreads) void score_push_streams_timed_kerne
 static int score_timed_args(const char *what, const stg_score_timed_state *st, const stg_score_timed_out *out,
                             TimedScoreArgs *a) {
     TimedScoreDims &d = a->d;
-    const TimedScorePred &p = a->pred;
     const TimedTracks &t = a->trk;
     STG_REQUIRE(d.S >= 1 && d.R >= 2 && d.P >= 1 && d.V >= 1 && d.K >= 0 && d.Q >= 0 && d.Rp >= 1, STG_EINVAL,
                 "%s: bad sizes S=%d R=%d P=%d V=%d K=%d Q=%d Rp=%d", what, d.S, d.R, d.P, d.V, d.K, d.Q, d.Rp);
@@ -428,37 +352,25 @@ static int score_timed_args(const char *what, const stg_score_timed_state *st, c
     STG_REQUIRE(d.max_dt >= 1 && d.max_dt < ((int64_t)1 << 31), STG_EINVAL, "%s: max_dt=%lld not in [1, 2^31)", what,
                 (long long)d.max_dt);
     STG_REQUIRE(st && out, STG_EINVAL, "%s: null pointer (state / out)", what);
-    if (!p.samples) d.K = 0;
-    const int K = d.K;
     STG_REQUIRE(t.slot_id && t.t_ring && t.xy_ring && t.slot_head && t.clock && t.head_flags, STG_EINVAL,
                 "%s: null pointer in the track state", what);
-    STG_REQUIRE(p.mean && p.v_pred && p.ids && p.num_peds, STG_EINVAL,
-                "%s: null pointer (mean / v_pred / ids / num_peds)", what);
     STG_REQUIRE(st->rec_t && st->rec_status && st->rec_peds && st->rec_ids && st->rec_mean && st->rec_cov &&
                     st->acc_mean && st->steps && st->matched && st->err && st->d2 && st->nll && st->traj_steps &&
                     st->traj_ade_mean && st->traj_fde_mean && st->counters && st->totals && st->traj_totals,
                 STG_EINVAL, "%s: null pointer in the state", what);
-    STG_REQUIRE(K == 0 || (st->rec_samples && st->acc && st->best && st->traj_ade && st->traj_fde), STG_EINVAL,
-                "%s: null pointer in the state (rec_samples / acc / best / traj_ade / traj_fde with K=%d)", what, K);
     STG_REQUIRE(out->push_totals && out->push_traj, STG_EINVAL, "%s: null pointer among the outputs", what);
-    STG_REQUIRE(d.Q == 0 || a->thr, STG_EINVAL, "%s: null pointer (thr with Q=%d)", what, d.Q);
-    STG_REQUIRE(aligned(p.mean, 8) && aligned(p.samples, 8) && aligned(st->rec_mean, 8) && aligned(st->rec_samples, 8),
-                STG_EINVAL, "%s: mean / samples and their records must be 8-byte aligned", what);
+    const int rc = score_pred_args(what, &a->pred, a->thr, st->rec_mean, st->rec_samples,
+                                   st->rec_samples && st->acc && st->best && st->traj_ade && st->traj_fde,
+                                   "rec_samples / acc / best / traj_ade / traj_fde", d.NS, d.P, d.V, &d.K, d.Q);
+    if (rc != STG_OK) return rc;
     STG_REQUIRE(d.step * d.P < ((int64_t)1 << 31) && d.step < ((int64_t)1 << 31), STG_EUNSUPPORTED,
                 "%s: step=%lld: step * P must stay below 2^31", what, (long long)d.step);
     STG_REQUIRE(d.S <= STG_TRACK_MAX_SLOTS, STG_EUNSUPPORTED, "%s: S=%d above STG_TRACK_MAX_SLOTS=%d", what, d.S,
                 STG_TRACK_MAX_SLOTS);
     STG_REQUIRE(d.R <= STG_TRACK_MAX_HISTORY, STG_EUNSUPPORTED, "%s: R=%d above STG_TRACK_MAX_HISTORY=%d", what, d.R,
                 STG_TRACK_MAX_HISTORY);
-    STG_REQUIRE(d.NS <= STG_TRACK_MAX_STREAMS, STG_EUNSUPPORTED, "%s: NS=%d above STG_TRACK_MAX_STREAMS=%d", what, d.NS,
-                STG_TRACK_MAX_STREAMS);
     STG_REQUIRE(d.Rp <= STG_SCORE_MAX_PENDING, STG_EUNSUPPORTED, "%s: Rp=%d above STG_SCORE_MAX_PENDING=%d", what, d.Rp,
                 STG_SCORE_MAX_PENDING);
-    STG_REQUIRE(d.V <= STG_SCORE_MAX_V, STG_EUNSUPPORTED, "%s: V=%d above STG_SCORE_MAX_V=%d", what, d.V, STG_SCORE_MAX_V);
-    STG_REQUIRE(K <= STG_SCORE_MAX_K, STG_EUNSUPPORTED, "%s: K=%d above STG_SCORE_MAX_K=%d", what, K, STG_SCORE_MAX_K);
-    STG_REQUIRE(d.P <= STG_SCORE_MAX_P, STG_EUNSUPPORTED, "%s: P=%d above STG_SCORE_MAX_P=%d", what, d.P, STG_SCORE_MAX_P);
-    STG_REQUIRE(d.Q <= STG_SCORE_MAX_Q, STG_EUNSUPPORTED, "%s: Q=%d above STG_SCORE_MAX_Q=%d", what, d.Q, STG_SCORE_MAX_Q);
-    if (K == 0) a->pred.samples = nullptr;
     static_cast<stg_score_timed_state &>(a->st) = *st;
     a->out = *out;
     d.S2 = det_sort_n(d.S);
@@ -483,7 +395,7 @@ int stg_score_push_timed(const int64_t *slot_id, const int64_t *t_ring, const do
     a.d = {1, P, V, K, Q, Rp, S, R, 0, step, max_dt, scale};
     const int rc = stg::score_timed_args(what, state, out, &a);
     if (rc != STG_OK) return rc;
-    return stg::launch({what, dim3(1), dim3(stg::kTScoreThreads), stg::det_sort_lds(a.d.S2), stg::as_stream(stream),
+    return stg::launch({what, dim3(1), dim3(stg::kScoreThreads), stg::det_sort_lds(a.d.S2), stg::as_stream(stream),
                         64 * 1024},
                        stg::score_push_timed_kernel, a);
 }
@@ -506,7 +418,7 @@ int stg_score_push_streams_timed(const int64_t *slot_id, const int64_t *t_ring, 
     const int rc = stg::score_timed_args(what, state, out, &a);
     if (rc != STG_OK) return rc;
     STG_REQUIRE(pushed, STG_EINVAL, "%s: null pointer (pushed)", what);
-    return stg::launch({what, dim3((unsigned)NS), dim3(stg::kTScoreThreads), stg::det_sort_lds(a.d.S2),
+    return stg::launch({what, dim3((unsigned)NS), dim3(stg::kScoreThreads), stg::det_sort_lds(a.d.S2),
                         stg::as_stream(stream), 64 * 1024},
                        stg::score_push_streams_timed_kernel, a, pushed);
 }

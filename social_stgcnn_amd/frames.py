@@ -723,14 +723,21 @@ class _LivePredictor:
                                 *((self.time.step, self.assoc.max_age) if timed else (self.assoc.max_miss,)))
         self._pred = Predictor(self.model, self.k, *self._risk_args)
         if self.score_spec is not None:
-            spec = self.score_spec
+            # which of the two score families this predictor holds is decided here, once: its state, the fresh outputs
+            # of a launch (graph capture) and the launch itself, behind the prediction's five tensors
+            spec, ns, p, q = self.score_spec, lead[0] if lead else 1, self.model.pred_seq_len, len(self.score_spec.levels)
+            self._thr = torch.tensor(spec.thresholds, dtype=torch.float32).to(dev) if q else None
             if isinstance(spec, TimedScoreSpec):
-                self._score_state = ops.score_timed_state(lead[0] if lead else 1, self.model.pred_seq_len, self.v,
-                                                          self.k, spec.pending, dev, spec.best_of_k, len(spec.levels))
+                self._score_state = ops.score_timed_state(ns, p, self.v, self.k, spec.pending, dev, spec.best_of_k, q)
+                self._score_buffers = lambda: ops.score_timed_buffers(ns, p, q, dev)
+                self._score_launch = lambda *pred, out: ops.score_timed_push(
+                    self._score_state, self._thr, *pred, self._state, self.time.step, self.time.max_dt, self.scale,
+                    pushed=self._score_pushed, out=out)
             else:
-                self._score_state = ops.score_state(lead[0] if lead else 1, self.model.pred_seq_len, self.v, self.k,
-                                                    dev, spec.best_of_k, len(spec.levels))
-            self._thr = torch.tensor(spec.thresholds, dtype=torch.float32).to(dev) if spec.levels else None
+                self._score_state = ops.score_state(ns, p, self.v, self.k, dev, spec.best_of_k, q)
+                self._score_buffers = lambda: ops.score_buffers(ns, p, self.v, dev, spec.best_of_k)
+                self._score_launch = lambda *pred, out: ops.score_push(
+                    self._score_state, self._thr, *pred, out=out, m_max=self.m_max, scale=self.scale, **self._det)
         if self.harvest_spec is not None:
             # the harvest's own history, one per index of `lead` -- presence words, a T_all-deep position ring, {ring row,
             # pushes since reset} --, the ONE log of the predictor and, for many streams, the launches' scratch
@@ -770,34 +777,18 @@ class _LivePredictor:
         reset() (size `pending` to the feed: predict.TimedScoreSpec).  None otherwise."""
         return self._score_state.counters[:, 1] if self._timed_score else None
 
-    def _score_streams(self):
-        st = self._score_state
-        return (st.counters if self._timed_score else st.head).shape[0]
-
-    def _score_buffers(self):
-        """Fresh outputs of the score launch (graph capture)."""
-        ns, p = self._score_streams(), self.model.pred_seq_len
-        if self._timed_score:
-            return ops.score_timed_buffers(ns, p, len(self.score_spec.levels), self.device)
-        return ops.score_buffers(ns, p, self.v, self.device, self.score_spec.best_of_k)
-
     def _score_reset(self, at=None):
         if self._score_state is not None:
-            (ops.score_timed_reset if self._timed_score else ops.score_reset)(self._score_state, at)
+            ops.score_reset(self._score_state, at)
 
     def _score_push(self, outs, r, out=None):
         """The score launch of one push, behind the sampler (and the risk counts): the pending predictions against this
         push's detections, then this push's prediction into the records (ops.score_push); with a TimedScoreSpec against
         the track samples the timed push has just recorded (ops.score_timed_push)."""
-        ns = self._score_streams()
-        if self._timed_score:
-            return ops.score_timed_push(self._score_state, self._thr, r.mean, r.v_pred,
-                                        r.samples if self.score_spec.best_of_k else None, outs[1].view(ns, self.v),
-                                        outs[2], self._state, self.time.step, self.time.max_dt, self.scale,
-                                        pushed=self._score_pushed, out=out)
-        return ops.score_push(self._score_state, self._thr, r.mean, r.v_pred,
-                              r.samples if self.score_spec.best_of_k else None, outs[1].view(ns, self.v), outs[2],
-                              out=out, m_max=self.m_max, scale=self.scale, **self._det)
+        # (_score_launch and _score_buffers exist only with a score spec: _track_state sets them beside the state)
+        ns = self._score_state.totals.shape[0]
+        return self._score_launch(r.mean, r.v_pred, r.samples if self.score_spec.best_of_k else None,
+                                  outs[1].view(ns, self.v), outs[2], out=out)
 
     def _reset_assoc(self, at=None):
         """Forget the association's tracks and start its ids at 0 again: everywhere, or at the stream indices `at`."""

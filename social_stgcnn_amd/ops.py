@@ -819,6 +819,80 @@ traj_steps int32 (the steps at which its pedestrian was matched), traj_ade / tra
 FDE where traj_steps == P) and traj_ade_mean / traj_fde_mean (the zero-noise trajectory).  Unmatched and padded entries
 are 0.  best, traj_ade and traj_fde are None when samples are not scored."""
 SCORE_MAX_V, SCORE_MAX_K, SCORE_MAX_P, SCORE_MAX_Q = 256, 64, 32, 4          # STG_SCORE_MAX_*
+SCORE_MAX_PENDING = 1024                                                     # STG_SCORE_MAX_PENDING
+_SCORE_SAMPLED = ("rec_samples", "acc")                                      # the fields that are None without samples
+_SCORE_DTYPES = dict(rec_t=torch.int64, rec_ids=torch.int64, counters=torch.int64, totals=torch.float64,
+                     traj_totals=torch.float64)                              # (every other field is float32)
+_SCORE_DTYPES.update({n: torch.int32 for n in ("rec_status", "rec_peds", "steps", "head", "matched", "traj_steps")})
+
+
+# ---- what score_push and score_timed_push share: `what` is the caller's name, `kind` its state's namedtuple and
+# `sampled` the fields of it that are None when samples are not scored
+def _score_shapes(ns, p, v, k, q):
+    return dict(rec_ids=(ns, p, v), rec_peds=(ns, p), rec_mean=(ns, p, p, v, 2), rec_cov=(ns, p, p, v, 3),
+                rec_samples=(ns, p, k, p, v, 2), acc=(ns, p, k, v), acc_mean=(ns, p, v), steps=(ns, p, v), head=(ns, 2),
+                totals=(ns, p, 5 + q), traj_totals=(ns, 5))
+
+
+def _score_limits(what, **sizes):
+    most = dict(v=SCORE_MAX_V, k=SCORE_MAX_K, p=SCORE_MAX_P, q=SCORE_MAX_Q, pending=SCORE_MAX_PENDING)
+    for name, got in sizes.items():
+        if got > most[name.lower()]:
+            raise ValueError("%s: %s=%d above the kernel's limit of %d" % (what, name, got, most[name.lower()]))
+
+
+def _score_cleared(kind, sampled, shapes, k, device):
+    return kind(*[None if (k == 0 and n in sampled) else
+                  torch.full(shapes[n], -1 if n == "rec_ids" else 0, device=device,
+                             dtype=_SCORE_DTYPES.get(n, torch.float32)) for n in kind._fields])
+
+
+def _score_prediction(what, state, mean, v_pred, samples, ids, num_peds):
+    """The prediction as the chain leaves it -> (ns, p, v, k); k = 0 where no samples are scored."""
+    if v_pred.dim() != 4 or v_pred.shape[1] != 5:
+        raise ValueError("%s: v_pred (NS,5,P,V) expected" % what)
+    ns, _, p, v = v_pred.shape
+    _lib.as_f32(v_pred, "v_pred")
+    if tuple(mean.shape) != (ns, p, v, 2) or mean.dtype != torch.float32 or not mean.is_contiguous():
+        raise ValueError("%s: mean must be a contiguous float32 (NS,P,V,2) tensor" % what)
+    k = 0 if samples is None or state.rec_samples is None else samples.shape[0]
+    if k and (tuple(samples.shape) != (k, ns, p, v, 2) or samples.dtype != torch.float32 or not samples.is_contiguous()):
+        raise ValueError("%s: samples must be a contiguous float32 (K,NS,P,V,2) tensor" % what)
+    if ids.numel() != ns * v or ids.dtype != torch.int64 or not ids.is_contiguous():
+        raise ValueError("%s: ids must be a contiguous int64 (NS,V) tensor" % what)
+    if num_peds.numel() != ns or num_peds.dtype != torch.int32:
+        raise ValueError("%s: num_peds must be an int32 (NS,) tensor" % what)
+    return ns, p, v, k
+
+
+def _score_state_fits(what, sampled, state, want, k, thr, q):
+    for name, x in zip(state._fields, state):
+        if k == 0 and name in sampled:
+            continue
+        if x is None or tuple(x.shape) != want[name] or not x.is_contiguous():
+            raise ValueError("%s: state.%s does not fit this call (%s expected)" % (what, name, want[name]))
+    if q and (thr is None or thr.numel() != q or thr.dtype != torch.float32 or not thr.is_cuda):
+        raise ValueError("%s: thr must be a float32 device tensor of %d thresholds" % (what, q))
+
+
+def _score_out_fits(what, out, fresh, device):
+    """`out`, or fresh(device) when there is none; an `out` must look like fresh("meta") field for field."""
+    if out is None:
+        return fresh(device)
+    for name, o, w in zip(out._fields, out, fresh("meta")):
+        if (o is None) != (w is None) or (o is not None and (
+                tuple(o.shape) != tuple(w.shape) or o.dtype != w.dtype or not o.is_contiguous() or not o.is_cuda)):
+            raise ValueError("%s: out.%s does not fit this call" % (what, name))
+    return out
+
+
+def _score_tail(structs, sampled, state, out, thr, mean, v_pred, samples, ids, num_peds, p, v, k, q, *rp):
+    """The arguments every score entry point ends on, from the prediction to the stream (`rp`: the timed pair's Rp)."""
+    st = structs[0](*[None if (x is None or (k == 0 and name in sampled)) else x.data_ptr()
+                      for name, x in zip(state._fields, state)])
+    so = structs[1](*[None if o is None else o.data_ptr() for o in out])
+    return (ptr(mean), ptr(v_pred), *v_pred.stride(), ptr(samples) if k else None, ptr(ids), ptr(num_peds), p, v, k, *rp,
+            ctypes.byref(st), ptr(thr) if q else None, q, ctypes.byref(so), stream_ptr())
 
 
 def score_thresholds(levels):
@@ -839,24 +913,15 @@ def score_state(ns, p, v, k, device, samples=True, q=3):
     Size: with samples P*V*(8 + 20P + 8KP + 4K + 8) bytes per stream -- about 3.5 MB at P 12, V 128, K 20, so 600
     streams hold about 2.1 GB --, about 0.4 MB per stream without samples; the totals add 8P(5+q) + 40 bytes."""
     ns, p, v, k, q = int(ns), int(p), int(v), int(k) if samples else 0, int(q)
-    for what, got, most in (("V", v, SCORE_MAX_V), ("k", k, SCORE_MAX_K), ("P", p, SCORE_MAX_P), ("q", q, SCORE_MAX_Q)):
-        if got > most:
-            raise ValueError("score_state: %s=%d above the kernel's limit of %d" % (what, got, most))
+    _score_limits("score_state", V=v, k=k, P=p, q=q)
     if ns < 1 or p < 1 or v < 1 or k < 0 or q < 0:
         raise ValueError("score_state: bad sizes ns=%d p=%d v=%d k=%d q=%d" % (ns, p, v, k, q))
-
-    def z(dtype, *shape):
-        return torch.zeros(shape, device=device, dtype=dtype)
-    f32, i32 = torch.float32, torch.int32
-    return ScoreState(torch.full((ns, p, v), -1, device=device, dtype=torch.int64), z(i32, ns, p), z(f32, ns, p, p, v, 2),
-                      z(f32, ns, p, p, v, 3), z(f32, ns, p, k, p, v, 2) if k else None, z(f32, ns, p, k, v) if k else None,
-                      z(f32, ns, p, v), z(i32, ns, p, v), z(i32, ns, 2), z(torch.float64, ns, p, 5 + q),
-                      z(torch.float64, ns, 5))
+    return _score_cleared(ScoreState, _SCORE_SAMPLED, _score_shapes(ns, p, v, k, q), k, device)
 
 
 def score_reset(state, streams=None):
     """Clear records and totals of every stream, or of the stream indices in the int64 device tensor `streams`."""
-    for name, x in zip(ScoreState._fields, state):
+    for name, x in zip(state._fields, state):
         if x is None:
             continue
         fill = -1 if name == "rec_ids" else 0
@@ -891,46 +956,13 @@ def score_push(state, thr, mean, v_pred, samples, ids, num_peds, det_id, det_xy,
     det_start (NS+1,) and pushed (NS,) int32 the packed tick of stg_track_push_streams (id_stride, xy_stride, m_total).
     out: an earlier Score to fill (graph capture).  No host synchronisation.  Returns a Score."""
     require_gpu(mean, v_pred, samples, ids, num_peds, *[x for x in state if x is not None])
-    if v_pred.dim() != 4 or v_pred.shape[1] != 5:
-        raise ValueError("score_push: v_pred (NS,5,P,V) expected")
-    ns, _, p, v = v_pred.shape
-    _lib.as_f32(v_pred, "v_pred")
-    if tuple(mean.shape) != (ns, p, v, 2) or mean.dtype != torch.float32 or not mean.is_contiguous():
-        raise ValueError("score_push: mean must be a contiguous float32 (NS,P,V,2) tensor")
-    k = 0 if samples is None or state.rec_samples is None else samples.shape[0]
-    if k and (tuple(samples.shape) != (k, ns, p, v, 2) or samples.dtype != torch.float32 or not samples.is_contiguous()):
-        raise ValueError("score_push: samples must be a contiguous float32 (K,NS,P,V,2) tensor")
-    if ids.numel() != ns * v or ids.dtype != torch.int64 or not ids.is_contiguous():
-        raise ValueError("score_push: ids must be a contiguous int64 (NS,V) tensor")
-    if num_peds.numel() != ns or num_peds.dtype != torch.int32:
-        raise ValueError("score_push: num_peds must be an int32 (NS,) tensor")
+    ns, p, v, k = _score_prediction("score_push", state, mean, v_pred, samples, ids, num_peds)
     q = state.totals.shape[2] - 5
-    want = dict(rec_ids=(ns, p, v), rec_peds=(ns, p), rec_mean=(ns, p, p, v, 2), rec_cov=(ns, p, p, v, 3),
-                rec_samples=(ns, p, k, p, v, 2), acc=(ns, p, k, v), acc_mean=(ns, p, v), steps=(ns, p, v), head=(ns, 2),
-                totals=(ns, p, 5 + q), traj_totals=(ns, 5))
-    for name, x in zip(ScoreState._fields, state):
-        if k == 0 and name in ("rec_samples", "acc"):
-            continue
-        if x is None or tuple(x.shape) != want[name] or not x.is_contiguous():
-            raise ValueError("score_push: state.%s does not fit this call (%s expected)" % (name, want[name]))
-    if q and (thr is None or thr.numel() != q or thr.dtype != torch.float32 or not thr.is_cuda):
-        raise ValueError("score_push: thr must be a float32 device tensor of %d thresholds" % q)
-    for what, got, most in (("V", v, SCORE_MAX_V), ("K", k, SCORE_MAX_K), ("P", p, SCORE_MAX_P), ("Q", q, SCORE_MAX_Q)):
-        if got > most:
-            raise ValueError("score_push: %s=%d above the kernel's limit of %d" % (what, got, most))
-    if out is None:
-        out = score_buffers(ns, p, v, mean.device, k > 0)
-    else:
-        for name, o, w in zip(Score._fields, out, score_buffers(ns, p, v, "meta", k > 0)):
-            if (o is None) != (w is None) or (o is not None and (
-                    tuple(o.shape) != tuple(w.shape) or o.dtype != w.dtype or not o.is_contiguous() or not o.is_cuda)):
-                raise ValueError("score_push: out.%s does not fit this call" % name)
-    st = _lib.ScoreState(*[None if (x is None or (k == 0 and name in ("rec_samples", "acc"))) else x.data_ptr()
-                           for name, x in zip(ScoreState._fields, state)])
-    so = _lib.ScoreOut(*[None if o is None else o.data_ptr() for o in out])
-    sn, sf, sp, sv = v_pred.stride()
-    pred = (ptr(mean), ptr(v_pred), sn, sf, sp, sv, ptr(samples) if k else None, ptr(ids), ptr(num_peds), p, v, k,
-            ctypes.byref(st), ptr(thr) if q else None, q, ctypes.byref(so), stream_ptr())
+    _score_state_fits("score_push", _SCORE_SAMPLED, state, _score_shapes(ns, p, v, k, q), k, thr, q)
+    _score_limits("score_push", V=v, K=k, P=p, Q=q)
+    out = _score_out_fits("score_push", out, lambda dev: score_buffers(ns, p, v, dev, k > 0), mean.device)
+    pred = _score_tail((_lib.ScoreState, _lib.ScoreOut), _SCORE_SAMPLED, state, out, thr, mean, v_pred, samples, ids,
+                       num_peds, p, v, k, q)
     if (det_count is None) == (det_start is None):
         raise ValueError("score_push: pass det_count (one stream) or det_start and pushed (a packed tick)")
     if det_count is not None:
@@ -962,7 +994,6 @@ contract.  rec_samples, acc, best, traj_ade and traj_fde are None when samples a
 ScoreTimed = collections.namedtuple("ScoreTimed", "push_totals push_traj")
 ScoreTimed.__doc__ = """What one timed push added to the running totals (`stg_score_push_timed`), NS leading: push_totals
 (NS,P,5+Q) and push_traj (NS,5) float64, all zero for a stream not pushed or refused."""
-SCORE_MAX_PENDING = 1024                                                     # STG_SCORE_MAX_PENDING
 _SCORE_TIMED_SAMPLED = ("rec_samples", "acc", "best", "traj_ade", "traj_fde")
 
 
@@ -982,32 +1013,13 @@ def score_timed_state(ns, p, v, k, pending, device, samples=True, q=3):
     V 128, K 20, P 12 about 7.5 MB without and 41 MB with the samples (31.5 MB of it the samples themselves), so 64
     streams hold 2.6 GB; the totals add 8P(5+q) + 40 bytes."""
     ns, p, v, k, q, rp = int(ns), int(p), int(v), int(k) if samples else 0, int(q), int(pending)
-    for what, got, most in (("V", v, SCORE_MAX_V), ("k", k, SCORE_MAX_K), ("P", p, SCORE_MAX_P), ("q", q, SCORE_MAX_Q),
-                            ("pending", rp, SCORE_MAX_PENDING)):
-        if got > most:
-            raise ValueError("score_timed_state: %s=%d above the kernel's limit of %d" % (what, got, most))
+    _score_limits("score_timed_state", V=v, k=k, P=p, q=q, pending=rp)
     if ns < 1 or p < 1 or v < 1 or k < 0 or q < 0 or rp < 1:
         raise ValueError("score_timed_state: bad sizes ns=%d p=%d v=%d k=%d q=%d pending=%d" % (ns, p, v, k, q, rp))
-    dtypes = dict(rec_t=torch.int64, rec_ids=torch.int64, counters=torch.int64, totals=torch.float64,
-                  traj_totals=torch.float64)
-    dtypes.update({n: torch.int32 for n in ("rec_status", "rec_peds", "steps", "matched", "traj_steps")})
-    shapes = _score_timed_shapes(ns, p, v, k, q, rp)
-    return ScoreTimedState(*[None if (k == 0 and n in _SCORE_TIMED_SAMPLED) else
-                             torch.full(shapes[n], -1 if n == "rec_ids" else 0, device=device,
-                                        dtype=dtypes.get(n, torch.float32)) for n in ScoreTimedState._fields])
+    return _score_cleared(ScoreTimedState, _SCORE_TIMED_SAMPLED, _score_timed_shapes(ns, p, v, k, q, rp), k, device)
 
 
-def score_timed_reset(state, streams=None):
-    """Clear records, counters and totals of every stream, or of the stream indices in the int64 device tensor
-    `streams`."""
-    for name, x in zip(ScoreTimedState._fields, state):
-        if x is None:
-            continue
-        fill = -1 if name == "rec_ids" else 0
-        if streams is None:
-            x.fill_(fill)
-        else:
-            x.index_fill_(0, streams, fill)
+score_timed_reset = score_reset
 
 
 def score_timed_buffers(ns, p, q, device):
@@ -1027,19 +1039,7 @@ def score_timed_push(state, thr, mean, v_pred, samples, ids, num_peds, tracks, s
     -- None: one stream, always pushed.  out: an earlier ScoreTimed to fill (graph capture).  No host synchronisation.
     Returns a ScoreTimed."""
     require_gpu(mean, v_pred, samples, ids, num_peds, *tracks, *[x for x in state if x is not None])
-    if v_pred.dim() != 4 or v_pred.shape[1] != 5:
-        raise ValueError("score_timed_push: v_pred (NS,5,P,V) expected")
-    ns, _, p, v = v_pred.shape
-    _lib.as_f32(v_pred, "v_pred")
-    if tuple(mean.shape) != (ns, p, v, 2) or mean.dtype != torch.float32 or not mean.is_contiguous():
-        raise ValueError("score_timed_push: mean must be a contiguous float32 (NS,P,V,2) tensor")
-    k = 0 if samples is None or state.rec_samples is None else samples.shape[0]
-    if k and (tuple(samples.shape) != (k, ns, p, v, 2) or samples.dtype != torch.float32 or not samples.is_contiguous()):
-        raise ValueError("score_timed_push: samples must be a contiguous float32 (K,NS,P,V,2) tensor")
-    if ids.numel() != ns * v or ids.dtype != torch.int64 or not ids.is_contiguous():
-        raise ValueError("score_timed_push: ids must be a contiguous int64 (NS,V) tensor")
-    if num_peds.numel() != ns or num_peds.dtype != torch.int32:
-        raise ValueError("score_timed_push: num_peds must be an int32 (NS,) tensor")
+    ns, p, v, k = _score_prediction("score_timed_push", state, mean, v_pred, samples, ids, num_peds)
     slot_id, t_ring, xy_ring, slot_head, clock, head_flags = tracks
     if t_ring.dim() < 2 or slot_id.numel() % ns:
         raise ValueError("score_timed_push: tracks do not fit %d streams" % ns)
@@ -1050,31 +1050,12 @@ def score_timed_push(state, thr, mean, v_pred, samples, ids, num_peds, tracks, s
         if x.numel() != n or x.dtype != dt or not x.is_contiguous():
             raise ValueError("score_timed_push: the track state does not fit this call (S=%d, R=%d)" % (s, r))
     q, rp = state.totals.shape[2] - 5, state.rec_t.shape[1]
-    want = _score_timed_shapes(ns, p, v, k, q, rp)
-    for name, x in zip(ScoreTimedState._fields, state):
-        if k == 0 and name in _SCORE_TIMED_SAMPLED:
-            continue
-        if x is None or tuple(x.shape) != want[name] or not x.is_contiguous():
-            raise ValueError("score_timed_push: state.%s does not fit this call (%s expected)" % (name, want[name]))
-    if q and (thr is None or thr.numel() != q or thr.dtype != torch.float32 or not thr.is_cuda):
-        raise ValueError("score_timed_push: thr must be a float32 device tensor of %d thresholds" % q)
-    for what, got, most in (("V", v, SCORE_MAX_V), ("K", k, SCORE_MAX_K), ("P", p, SCORE_MAX_P), ("Q", q, SCORE_MAX_Q),
-                            ("pending", rp, SCORE_MAX_PENDING)):
-        if got > most:
-            raise ValueError("score_timed_push: %s=%d above the kernel's limit of %d" % (what, got, most))
-    if out is None:
-        out = score_timed_buffers(ns, p, q, mean.device)
-    else:
-        for name, o, w in zip(ScoreTimed._fields, out, score_timed_buffers(ns, p, q, "meta")):
-            if tuple(o.shape) != tuple(w.shape) or o.dtype != w.dtype or not o.is_contiguous() or not o.is_cuda:
-                raise ValueError("score_timed_push: out.%s does not fit this call" % name)
-    st = _lib.ScoreTimedState(*[None if (x is None or (k == 0 and name in _SCORE_TIMED_SAMPLED)) else x.data_ptr()
-                                for name, x in zip(ScoreTimedState._fields, state)])
-    so = _lib.ScoreTimedOut(*[o.data_ptr() for o in out])
-    sn, sf, sp, sv = v_pred.stride()
+    _score_state_fits("score_timed_push", _SCORE_TIMED_SAMPLED, state, _score_timed_shapes(ns, p, v, k, q, rp), k, thr, q)
+    _score_limits("score_timed_push", V=v, K=k, P=p, Q=q, pending=rp)
+    out = _score_out_fits("score_timed_push", out, lambda dev: score_timed_buffers(ns, p, q, dev), mean.device)
     sizes = (s, r, ctypes.c_double(scale), int(step), int(max_dt))
-    pred = (ptr(mean), ptr(v_pred), sn, sf, sp, sv, ptr(samples) if k else None, ptr(ids), ptr(num_peds), p, v, k, rp,
-            ctypes.byref(st), ptr(thr) if q else None, q, ctypes.byref(so), stream_ptr())
+    pred = _score_tail((_lib.ScoreTimedState, _lib.ScoreTimedOut), _SCORE_TIMED_SAMPLED, state, out, thr, mean, v_pred,
+                       samples, ids, num_peds, p, v, k, q, rp)
     if pushed is None:
         if ns != 1:
             raise ValueError("score_timed_push: %d streams need `pushed`" % ns)

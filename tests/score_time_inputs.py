@@ -78,6 +78,26 @@ def script(s, p, v, k, n_push=60):
     return out
 
 
+def edge_script(s, p, v, k, empty_scenes=False, n_push=12):
+    """Stream s, a dozen pushes (13 at the most) for the edge shapes: [(t, ids, xy, prediction)].  Inter-push times 1 to 7
+    at step 4 (no bracket wider than max_dt), at most five ids (no OVERFLOW), id 3 away at pushes 4-5, push 8 empty.  The scene: the
+    push's ids, last detection first; with v > 64 never-detected ids between them so that it fills all v columns and a
+    detected id sits in the last one; with empty_scenes every other prediction holds no pedestrian."""
+    times = (np.cumsum([3, 4, 1, 4, 2, 4, 7, 4, 3, 4, 1, 4, 3][:n_push]) - 20 + s).tolist()
+    base = [1, 2, 3, 4, BIG + 5] if s != 1 else [BIG + 5, 2, 1, 3]
+    out = []
+    for n, t in enumerate(times):
+        ids = [] if n == 8 else [i for i in base if not (i == 3 and n in (4, 5))]
+        scene = list(dict.fromkeys(reversed(ids)))
+        if v > 64:
+            scene = scene[:-1] + [FILLER + j for j in range(v - len(scene))] + scene[-1:]
+        if empty_scenes and n % 2:
+            scene = []
+        out.append((t, np.array(ids, np.int64), np.array([pos(i, t) for i in ids], np.float64).reshape(-1, 2),
+                    exact_prediction(scene, t, p, v, k)))
+    return out
+
+
 class StreamRef:
     """One stream restated: the timed push and the score behind it."""
 

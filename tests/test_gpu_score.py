@@ -190,6 +190,85 @@ def test_scripts_are_bit_exact(dev, k, thr):
         assert 0 < tot[:, :, 5].sum() < tot[:, :, 6].sum() < tot[:, :, 0].sum()      # the thresholds cut the d2 values
 
 
+EDGES = {                      # p, v, k, thr: the shapes at which the helpers of score_fn.hpp take another path
+    "k0": (3, 5, 0, (0.75, 3.0)),                        # no samples: best, traj_ade and traj_fde are absent
+    "q0": (3, 5, 2, ()),
+    "p1": (1, 5, 2, (0.75, 3.0)),                        # one ring row: retired and enqueued on every push
+    "v65": (3, 65, 2, (0.75, 3.0)),                      # a scene of 65: two lane passes, the second with one live lane
+    "peds0": (3, 5, 2, (0.75, 3.0)),                     # every other prediction holds no pedestrian
+}
+FILLER = 1000                                          # ids from here on are never detected
+
+
+def _edge_entry(case, s, m, p, v, k):
+    """The detections of _script_entry; the scene is the detected ids, for v65 with never-detected ids between them so
+    that it fills all 65 columns and a detected id sits in column 64."""
+    ids, xy, _ = _script_entry(s, m, p, 5, 0)
+    scene = sorted(set(ids.tolist()))[:5 - m % 2]
+    if case == "v65":
+        scene = scene[:-1] + [FILLER + j for j in range(v - len(scene))] + scene[-1:]
+    if case == "peds0" and m % 2:
+        scene = []
+    return ids, xy, _exact_prediction(scene, len(scene), m, p, v, k)
+
+
+def _real_covariance(pr, seed):
+    """Seeded log sigma in [-2.5, -0.5] and |v_pred[4]| <= 1.2 (the family of test_real_inputs_...) into a prediction."""
+    g = np.random.default_rng(seed)
+    pr.v_pred[2:4] = g.uniform(-2.5, -0.5, pr.v_pred[2:4].shape)
+    pr.v_pred[4] = g.uniform(-1.2, 1.2, pr.v_pred[4].shape)
+    return pr
+
+
+def _assert_cov(got, pr, what):
+    """A record's rec_cov (P,V,3) against the float64 running sum of the prediction's v_pred, the columns of its
+    pedestrians: cxx and cyy within (5 + P-1) u relative, cxy within (10 + P-1) u of sqrt(cxx cyy) -- the bounds of
+    _d2_bounds (expf within 1 ulp, tanhf within 2, P-1 float32 additions).  A wrong stride or column is off by O(1)."""
+    p, c = pr.v_pred.shape[1], pr.num_peds
+    ref, got = score_np.cumulative_cov(pr.v_pred)[:, :c], got[:, :c].astype(np.float64)
+    assert c > 0 and (np.abs(got[..., [0, 2]] - ref[..., [0, 2]]) <= (5 + p - 1) * U * ref[..., [0, 2]]).all(), what
+    assert (np.abs(got[..., 1] - ref[..., 1]) <= (10 + p - 1) * U * np.sqrt(ref[..., 0] * ref[..., 2])).all(), what
+
+
+@pytest.mark.parametrize("single", (False, True), ids=("streams", "lone"))
+@pytest.mark.parametrize("case", sorted(EDGES))
+def test_edge_shapes_are_bit_exact(dev, case, single):
+    """M_max 7, 12 ticks, through stg_score_push_streams (two streams, stream 1 not pushed at ticks 2 and 6) and through
+    stg_score_push (one stream): every output and the totals equal the restatement evaluated in float32, bit for bit."""
+    p, v, k, thr = EDGES[case]
+    ns = 1 if single else 2
+    h = Harness(dev, ns, p, v, k, thr, 7, single=single)
+    count = [0] * ns
+    matched = np.zeros((p, v), np.int64)
+    full = 0
+    for t in range(12):
+        entries = []
+        for s in range(ns):
+            if s == 1 and t in (2, 6):
+                entries.append(None)
+                continue
+            entries.append(_edge_entry(case, s, count[s], p, v, k))
+            count[s] += 1
+        got, refs = h.tick(entries)
+        h.assert_bit_equal(got, refs, (case, t))
+        assert (got["best"] is None) == (got["traj_ade"] is None) == (got["traj_fde"] is None) == (k == 0)
+        matched += got["matched"].sum(axis=0)
+        full += int((got["traj_steps"] == p).sum())
+    tot, trj = h.totals()
+    assert matched.sum() == tot[:, :, 0].sum() and matched.sum() > 20 * ns
+    assert full == trj[:, 0].sum() and full > 5 * ns
+    assert tot.shape[2] == 5 + len(thr)
+    if case == "v65":
+        assert matched[:, 64].all() and matched[:, :64].any() and not matched[:, 5:64].any()
+    # the covariance sum at this shape on real sigma and rho channels (the scripts hold C_h = h I): one more push of
+    # stream 0, its record against the float64 sum; the columns past num_peds carry zeros
+    ids, xy, pr = _edge_entry(case, 0, count[0], p, v, k)
+    h.tick([(ids, xy, _real_covariance(pr, 5))] + [None] * (ns - 1))
+    cov = h.state.rec_cov[0, (int(h.state.head[0, 0]) - 1) % p].cpu().numpy()
+    _assert_cov(cov, pr, case)
+    assert not cov[:, pr.num_peds:].any()
+
+
 @pytest.mark.parametrize("what", ("m_max_2048", "v_256"))
 def test_limits(dev, what):
     """The largest sort (2,048 detections, ids descending) and the widest scene (256 pedestrians), bit-exact scripts

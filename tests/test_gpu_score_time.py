@@ -17,7 +17,7 @@ from frames_time_np import OVERFLOW, TIME_ORDER, StreamModelTimed
 from live_inputs import _CPush, _model, _pushes
 from score_time_np import TABLES, TRAJ, TimedScoreModel
 from test_gpu_frames_time import _irregular_feed, _upsampled_eth
-from test_gpu_score import U, _d2_bounds
+from test_gpu_score import U, _assert_cov, _d2_bounds, _real_covariance
 
 pytestmark = pytest.mark.gpu
 FLOATS = ("err", "d2", "nll", "best", "traj_ade", "traj_fde", "traj_ade_mean", "traj_fde_mean")
@@ -61,7 +61,7 @@ class Harness:
     score launch for the tick -- stg_score_push_streams_timed, or stg_score_push_timed with single=True and ns = 1 --
     beside one sti.StreamRef per stream.  tick(entries): entries[s] = None (not pushed) or (t, ids, xy, prediction)."""
 
-    def __init__(self, dev, ns, p, v, k, thr, pending, r, single=False):
+    def __init__(self, dev, ns, p, v, k, thr, pending, r, single=False, m_max=sti.M_MAX):
         from social_stgcnn_amd import ops
         self.ops, self.dev, self.ns, self.p, self.v, self.k, self.single = ops, dev, ns, p, v, k, single
         z = lambda shape, dt: torch.zeros(shape, device=dev, dtype=dt)      # noqa: E731
@@ -71,13 +71,13 @@ class Harness:
                        z((ns, 2), torch.int32))
         self.push = []
         for b in range(ns):
-            c = _CPush(dev, (2, 3), v, s, sti.M_MAX, sti.T_OBS, 4, time=(sti.STEP, sti.MAX_DT, r))
+            c = _CPush(dev, (2, 3), v, s, m_max, sti.T_OBS, 4, time=(sti.STEP, sti.MAX_DT, r))
             c.state = tuple(x[b] for x in self.tracks)
             c.slot_id, c.head_flags = c.state[0], c.state[5]
             self.push.append(c)
         self.state = ops.score_timed_state(ns, p, v, k, pending, dev, samples=k > 0, q=len(thr))
         self.thr = torch.tensor(list(thr), dtype=torch.float32).to(dev) if len(thr) else None
-        self.refs = [sti.StreamRef(p, v, k, thr, pending, r) for _ in range(ns)]
+        self.refs = [sti.StreamRef(p, v, k, thr, pending, r, m_max=m_max) for _ in range(ns)]
 
     def snapshot(self):
         return {n: None if x is None else x.cpu().numpy() for n, x in zip(self.state._fields, self.state)}
@@ -184,6 +184,56 @@ def test_scripts_are_bit_exact(dev, case):
         assert not st["counters"][:, 1].any() and st["traj_totals"][:, 0].sum() > 20
     if thr:
         assert 0 < st["totals"][..., 5].sum() < st["totals"][..., 7].sum() < st["totals"][..., 0].sum()
+
+
+EDGES = {                      # p, v, k, thr: the shapes at which the helpers of score_fn.hpp take another path
+    "k0": (3, 5, 0, (0.75, 3.0)),                        # no samples: best, traj_ade and traj_fde are absent
+    "q0": (3, 5, 2, ()),
+    "p1": (1, 5, 2, (0.75, 3.0)),
+    "v65": (3, 65, 2, (0.75, 3.0)),                      # a scene of 65: two lane passes, the second with one live lane
+    "peds0": (3, 5, 2, (0.75, 3.0)),                     # every other prediction holds no pedestrian
+}
+
+
+@pytest.mark.parametrize("single", (False, True), ids=("streams", "lone"))
+@pytest.mark.parametrize("case", sorted(EDGES))
+def test_edge_shapes_are_bit_exact(dev, case, single):
+    """S 8 slots, M_max 8, R 2, pending 4, a dozen pushes a stream (score_time_inputs.edge_script) through
+    stg_score_push_streams_timed (two streams, stream 1 sits out the ticks 2 and 6) and through stg_score_push_timed
+    (one stream): after every tick what the push added, every fourth tick and at the end the whole ring -- tables,
+    retired rows, counters -- equal the restatement evaluated in float32, bit for bit."""
+    p, v, k, thr = EDGES[case]
+    ns = 1 if single else 2
+    h = Harness(dev, ns, p, v, k, thr, 4, 2, single, m_max=8)
+    scripts = [sti.edge_script(s, p, v, k, case == "peds0") for s in range(ns)]
+    last = sti.edge_script(0, p, v, k, case == "peds0", n_push=13)[12]
+    cursor = [0] * ns
+    for n in range(14):
+        entries = []
+        for s in range(ns):
+            if (s == 1 and n in (2, 6)) or cursor[s] >= len(scripts[s]):
+                entries.append(None)
+                continue
+            entries.append(scripts[s][cursor[s]])
+            cursor[s] += 1
+        if all(e is None for e in entries):                     # (the lone entry point has no `pushed`)
+            break
+        assert not any(f for f in h.tick(entries) if f is not None), (case, n)     # (no OVERFLOW, nothing refused)
+        if n % 4 == 3:
+            h.assert_state((case, n))
+    st = h.assert_state(case)
+    assert cursor == [12] * ns and st["counters"][:, 0].tolist() == [12] * ns
+    assert all((st[name] is None) == (k == 0) for name in ("rec_samples", "acc", "best", "traj_ade", "traj_fde"))
+    assert st["totals"].shape[2] == 5 + len(thr) and (st["totals"][:, :, 0].sum(axis=1) > 10).all()
+    assert (st["traj_totals"][:, 0] > 2).all()
+    if case == "v65":
+        assert st["matched"][..., 64].any() and not st["matched"][..., 5:64].any()
+    # the covariance sum at this shape on real sigma and rho channels (the scripts hold C_h = h I): a thirteenth push of
+    # stream 0, its record against the float64 sum
+    h.tick([last[:3] + (_real_covariance(last[3], 5),)] + [None] * (ns - 1))
+    row = (int(h.state.counters[0, 0]) - 1) % 4
+    assert int(h.state.counters[0, 0]) == 13
+    _assert_cov(h.state.rec_cov[0, row].cpu().numpy(), last[3], case)
 
 
 # ---- 2. the anchor on the device ---------------------------------------------------------------------------------

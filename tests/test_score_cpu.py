@@ -158,6 +158,41 @@ def test_entry_points_refuse_before_any_launch(L):
     assert many(ns=0, start=None) == 0                          # no streams: a no-op, nothing is looked at
 
 
+SHARED_REFUSALS = {           # case -> (arguments, status, the message behind the entry point's name)
+    "null mean": (dict(mean=None), -1, ": null pointer (mean / v_pred / ids / num_peds)"),
+    "misaligned samples": (dict(samples=ctypes.c_void_p(68)), -1,
+                           ": mean / samples and their records must be 8-byte aligned"),
+    "null thr with Q": (dict(thr=None), -1, ": null pointer (thr with Q=1)"),
+    "V": (dict(v=257), "EUNSUPPORTED", ": V=257 above STG_SCORE_MAX_V=256"),
+    "K": (dict(k=65), "EUNSUPPORTED", ": K=65 above STG_SCORE_MAX_K=64"),
+    "P": (dict(p=33), "EUNSUPPORTED", ": P=33 above STG_SCORE_MAX_P=32"),
+    "Q": (dict(q=5), "EUNSUPPORTED", ": Q=5 above STG_SCORE_MAX_Q=4"),
+}
+
+
+@pytest.mark.parametrize("entry", ("stg_score_push", "stg_score_push_streams", "stg_score_push_timed",
+                                   "stg_score_push_streams_timed"))
+def test_the_four_entry_points_share_their_refusals(L, entry):
+    """What the push-indexed and the time-indexed pair check in one place (score_fn.hpp) comes back from each of the
+    four with the same status and the same words behind its own name, before any launch: every pointer is 64 or 68."""
+    from social_stgcnn_amd import _lib
+    f = ctypes.c_void_p(64)
+    timed = entry.endswith("_timed")
+    kinds = (_lib.ScoreTimedState, _lib.ScoreTimedOut) if timed else (_lib.ScoreState, _lib.ScoreOut)
+
+    def call(mean=f, samples=f, thr=f, p=3, v=5, k=2, q=1):
+        st, so = (cls(*[64] * len(cls._fields_)) for cls in kinds)
+        tail = (mean, f, 60, 15, 5, 1, samples, f, f, p, v, k) + ((6,) if timed else ()) + \
+            (ctypes.byref(st), thr, q, ctypes.byref(so), None)
+        head = {"stg_score_push": (f, f, f, 8, 1e4), "stg_score_push_streams": (f, 3, f, 3, 16, f, f, 3, 8, 1e4),
+                "stg_score_push_timed": (f, f, f, f, f, f, 8, 4, 1e4, 10, 10),
+                "stg_score_push_streams_timed": (f, f, f, f, f, f, f, 3, 8, 4, 1e4, 10, 10)}[entry]
+        return getattr(L, entry)(*head, *tail)
+    for name, (kw, status, words) in SHARED_REFUSALS.items():
+        assert call(**kw) == (_lib.EUNSUPPORTED if status == "EUNSUPPORTED" else status), name
+        assert L.stg_last_error().decode().endswith(entry + words), (name, L.stg_last_error())
+
+
 def test_score_spec_and_thresholds():
     from social_stgcnn_amd import ops
     from social_stgcnn_amd.predict import ScoreSpec
