@@ -656,6 +656,10 @@ int stg_selftest_mfma(const float *a, const float *b, int K, float *c, void *str
  * points, the ABI version stays), declared in stgcnn_hip_assoc_filter.h the same way */
 #include "stgcnn_hip_assoc_filter.h"
 
+/* N14: distribution metrics of a batch of predictions against the truth, beside stg_bestofk_eval (an
+ * added entry point, the ABI version stays), declared in stgcnn_hip_metrics.h the same way */
+#include "stgcnn_hip_metrics.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -177,6 +177,11 @@ _SIGNATURES_ASSOC_FILTER = {
     "stg_associate_streams_filtered": (c_i, [c_f, c_l, c_f, c_l, c_i, c_f, c_f, c_f, c_f, c_i, c_i, c_f, c_f, c_f, c_f,
                                              c_f, c_f, c_f, c_f, c_i, c_d, c_d, c_d, c_d, c_d, c_d, c_l, c_l, c_f]),
 }
+# ... and the one of include/stgcnn_hip_metrics.h, included the same way
+_SIGNATURES_METRICS = {
+    "stg_dist_metrics": (c_i, [c_f, c_l, c_l, c_l, c_l, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, ctypes.c_float, c_f, c_f,
+                               c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
+}
 
 _lib = None
 
@@ -204,7 +209,7 @@ def lib():
         h = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in {**_SIGNATURES, **_SIGNATURES_SCORE_TIME, **_SIGNATURES_HARVEST,
                                     **_SIGNATURES_HARVEST_TIME, **_SIGNATURES_ASSOC_TIME,
-                                    **_SIGNATURES_ASSOC_FILTER}.items():
+                                    **_SIGNATURES_ASSOC_FILTER, **_SIGNATURES_METRICS}.items():
             fn = getattr(h, name)
             fn.restype = res
             fn.argtypes = args

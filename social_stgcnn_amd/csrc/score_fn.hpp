@@ -117,6 +117,16 @@ __device__ __forceinline__ void score_cols(double (&c)[kScoreRow], float err, fl
 }
 
 // ---- enqueue: the prediction of stream b into record `row` ------------------------------------------------------------
+// One step of the running covariance: (cxx, cxy, cyy) += [sx^2, rho sx sy, sy^2] of the element q = (n, field 0, t, v) of
+// V_pred with field stride p_sf, float32 as written (shared with dist_metrics.hip)
+__device__ __forceinline__ void score_cov_add(const float *q, int64_t p_sf, float &cxx, float &cxy, float &cyy) {
+#pragma clang fp contract(off)
+    const float sx = expf(q[2 * p_sf]), sy = expf(q[3 * p_sf]), rho = tanhf(q[4 * p_sf]);
+    cxx += sx * sx;
+    cxy += rho * sx * sy;
+    cyy += sy * sy;
+}
+
 // The running covariance of column v: C_h = sum_{t<=h} [sx^2, rho sx sy, sy^2]_t, float32, ascending t.  A column that is
 // not live (at or past num_peds) reads nothing and carries zeros
 __device__ __forceinline__ void score_cov_column(const ScorePred &p, int b, const ScoreRows &t, int row, int v, bool live) {
@@ -124,13 +134,7 @@ __device__ __forceinline__ void score_cov_column(const ScorePred &p, int b, cons
     float cxx = 0.f, cxy = 0.f, cyy = 0.f;
     for (int s = 0; s < t.P; ++s) {
         float *c = t.cov + (((int64_t)row * t.P + s) * t.V + v) * 3;
-        if (live) {
-            const float *q = p.v_pred + b * p.p_sn + v * p.p_sv + s * p.p_sp;
-            const float sx = expf(q[2 * p.p_sf]), sy = expf(q[3 * p.p_sf]), rho = tanhf(q[4 * p.p_sf]);
-            cxx += sx * sx;
-            cxy += rho * sx * sy;
-            cyy += sy * sy;
-        }
+        if (live) score_cov_add(p.v_pred + b * p.p_sn + v * p.p_sv + s * p.p_sp, p.p_sf, cxx, cxy, cyy);
         c[0] = cxx;
         c[1] = cxy;
         c[2] = cyy;

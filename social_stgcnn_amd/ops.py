@@ -690,6 +690,79 @@ def best_of_k(y, target_rel, obs_last=None, num_peds=None, k=20, noise=None, see
     return ade, fde
 
 
+DistMetrics = collections.namedtuple("DistMetrics", "d2 nll lam kde_nll ade fde jade jfde jbest")
+DistMetrics.__doc__ = """A batch of predictions judged against the truth (`stg_dist_metrics`, DESIGN.md 5.31), float32 device
+tensors, zeros in padded slots.  (N,P,V): d2 (squared Mahalanobis distance of the truth under N(mean_h, C_h), C_h the
+cumulative covariance of the live score), nll (of that Gaussian), lam (the larger eigenvalue of C_h), kde_nll (minus the
+log density at the truth of the Gaussian KDE of the K samples at that horizon, Scott's bandwidth, clipped from above at
+kde_floor).  (N,V): ade, fde, the best-of-K errors over the given samples.  (N,): jade, jfde -- the minimum over k of
+the scene's mean error, ONE sample for every pedestrian of the scene -- and jbest int32, the k of jade (-1 for an empty
+scene).  The sample-based fields (kde_nll and after) are None without samples."""
+_DIST_SAMPLED = ("kde_nll", "ade", "fde", "jade", "jfde", "jbest")
+
+
+def dist_buffers(n, p, v, device, samples=True, cov=False):
+    """Empty outputs for dist_metrics on n scenes: (DistMetrics, cov (N,P,V,3) or None)."""
+    def f32(*shape):
+        return torch.empty(shape, device=device, dtype=torch.float32)
+    s = bool(samples)
+    m = DistMetrics(f32(n, p, v), f32(n, p, v), f32(n, p, v), f32(n, p, v) if s else None, f32(n, v) if s else None,
+                    f32(n, v) if s else None, f32(n) if s else None, f32(n) if s else None,
+                    torch.empty((n,), device=device, dtype=torch.int32) if s else None)
+    return m, (f32(n, p, v, 3) if cov else None)
+
+
+def dist_metrics(v_pred, mean, samples, truth, num_peds=None, kde_floor=20.0, out=None, cov=None, ref_errors=None):
+    """Distribution metrics of a batch of predictions on the device (`stg_dist_metrics`): v_pred (N,5,P,V) model output
+    (any strides), mean (N,P,V,2) and samples (K,N,P,V,2) as `sample_trajectories` / `Predictor.predict` leave them
+    (samples None: the closed-form fields only; else 3 <= K <= 64), truth (N,P,V,2) absolute positions, num_peds (N,) or
+    None.  kde_floor: kde_nll is clipped from above at this value (the log density from below at -kde_floor).
+    out: an earlier DistMetrics of the same call to fill, cov: a contiguous float32 (N,P,V,3) tensor that receives C_h
+    (graph capture: nothing is allocated then).  ref_errors: a pair of contiguous float64 (N,V) device tensors that
+    receive the best-of-K ADE / FDE in the reference's own arithmetic (float32 differences and squares, float64 root and
+    sum over t: what predict.sample_test computes on the host from the same samples); needs samples.
+    Returns a DistMetrics."""
+    require_gpu(v_pred, mean, samples, truth, cov)
+    if ref_errors is not None:
+        if samples is None or len(ref_errors) != 2:
+            raise ValueError("dist_metrics: ref_errors is a pair (ade, fde) and needs samples")
+        require_gpu(*ref_errors)
+        for x in ref_errors:
+            if tuple(x.shape) != tuple(v_pred.shape[::3]) or x.dtype != torch.float64 or not x.is_contiguous():
+                raise ValueError("dist_metrics: ref_errors must be contiguous float64 (N,V) tensors")
+    if v_pred.dim() != 4 or v_pred.shape[1] != 5:
+        raise ValueError("dist_metrics: v_pred (N,5,P,V) expected")
+    n, _, p, v = v_pred.shape
+    _lib.as_f32(v_pred, "v_pred")
+    k = 0 if samples is None else int(samples.shape[0])
+    for name, x, shape in (("mean", mean, (n, p, v, 2)), ("truth", truth, (n, p, v, 2)),
+                           ("samples", samples, (k, n, p, v, 2)), ("cov", cov, (n, p, v, 3))):
+        if x is not None and (tuple(x.shape) != shape or x.dtype != torch.float32 or not x.is_contiguous()):
+            raise ValueError("dist_metrics: %s must be a contiguous float32 %s tensor" % (name, shape))
+    if samples is not None and not 3 <= k <= SCORE_MAX_K:
+        raise ValueError("dist_metrics: K=%d samples (3 <= K <= %d, or samples=None)" % (k, SCORE_MAX_K))
+    for what, got, most in (("V", v, SCORE_MAX_V), ("P", p, SCORE_MAX_P)):
+        if got > most:
+            raise ValueError("dist_metrics: %s=%d above the kernel's limit of %d" % (what, got, most))
+    if not float(kde_floor) == float(kde_floor):
+        raise ValueError("dist_metrics: kde_floor must be a number")
+    if out is None:
+        out = dist_buffers(n, p, v, v_pred.device, k > 0)[0]
+    else:
+        want = dist_buffers(n, p, v, "meta", k > 0)[0]
+        for name, o, w in zip(DistMetrics._fields, out, want):
+            if (o is None) != (w is None) or (o is not None and (
+                    tuple(o.shape) != tuple(w.shape) or o.dtype != w.dtype or not o.is_contiguous() or not o.is_cuda)):
+                raise ValueError("dist_metrics: out.%s does not fit this call (%s)"
+                                 % (name, "None" if w is None else "contiguous %s %s" % (w.dtype, tuple(w.shape))))
+    peds = peds_arg(num_peds, n, v_pred.device)
+    check(lib().stg_dist_metrics(ptr(v_pred), *v_pred.stride(), ptr(mean), ptr(samples), ptr(truth), ptr(peds), n, p, v,
+                                 k, ctypes.c_float(float(kde_floor)), ptr(cov), *[ptr(o) for o in out],
+                                 *[ptr(x) for x in (ref_errors or (None, None))], stream_ptr()),
+          "stg_dist_metrics")
+    return out
+
+
 def sample_trajectories(y, obs_last=None, num_peds=None, k=20, noise=None, seed=0, seed_dev=None, samples=None,
                         mean=None):
     """The sampled trajectories of test.py:59-91 on the device (`stg_sample_trajectories`): y (N,5,P,V) model output

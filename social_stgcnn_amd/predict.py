@@ -286,3 +286,46 @@ def sample_test(model, windows, k=20, batch_size=64, seed=0, noise_fn=None):
             ades += a.min(axis=0).tolist()
             fdes += f.min(axis=0).tolist()
     return sum(ades) / len(ades), sum(fdes) / len(fdes), raw
+
+
+@torch.no_grad()
+def distribution_test(model, windows, k=20, batch_size=64, seed=0, noise_fn=None, levels=(0.5, 0.9, 0.99),
+                      kde_floor=20.0):
+    """What sample_test cannot say about a test set: whether the predicted Gaussians are calibrated
+    (Mahalanobis distance, NLL, ellipse coverage, the larger eigenvalue), how likely the truth is under the K samples
+    (KDE-NLL) and how well a scene as a whole is predicted (joint ADE / FDE).  The batching and the draws are
+    sample_test's (seed + batch index, or noise_fn) and the truth is its `trgt`; one Predictor.predict and one
+    ops.dist_metrics launch per batch, the sums kept on the device: nothing comes back to the host but the summary and
+    the per-pedestrian errors.  Returns (metrics.DistSummary, ade, fde): the best-of-K errors of every pedestrian,
+    float64 numpy arrays in sample_test's order, in the arithmetic sample_test evaluates on the host (the kernel's
+    ade_ref / fde_ref: float32 differences and squares, float64 root and sum); the summary's .ade / .fde are their means
+    summed as sample_test sums them, so the two functions report the same ADE / FDE at the same seed, to the last bit."""
+    from . import metrics
+    pred = Predictor(model, k)
+    dev = next(model.parameters()).device
+    t_obs = model.seq_len
+    per_h, traj, ades, fdes = None, None, [], []
+    for b, lo in enumerate(range(0, len(windows), batch_size)):
+        idx = np.arange(lo, min(len(windows), lo + batch_size))
+        _, pred_rel, obs_abs, _, counts = data.pad_batch(windows, idx, obs_len=t_obs)
+        n, _, v, _ = obs_abs.shape
+        obs64 = np.zeros(obs_abs.shape)                    # the dataset's float64 positions (see observed_inputs)
+        for j, i in enumerate(idx):
+            s0, e0 = windows.seq_start_end[i]
+            obs64[j, :, :e0 - s0] = np.transpose(windows.seq[s0:e0, :, :t_obs], (2, 0, 1))
+        noise = noise_fn(b, (k, n, pred_rel.shape[1], v, 2)) if noise_fn is not None else None
+        peds = torch.from_numpy(counts).to(dev)
+        r = pred.predict(torch.from_numpy(obs64).to(dev), peds, seed + b, noise)
+        xl = obs_abs[:, -1].astype(np.float64)             # sample_test's trgt
+        trgt = (np.cumsum(pred_rel, axis=1, dtype=np.float32) + xl[:, None]).astype(np.float32)
+        ref = (torch.empty((n, v), device=dev, dtype=torch.float64), torch.empty((n, v), device=dev, dtype=torch.float64))
+        m = ops.dist_metrics(r.v_pred, r.mean, r.samples, torch.from_numpy(trgt).to(dev), peds, kde_floor,
+                             ref_errors=ref)
+        sums = metrics.dist_sums(m, peds, levels)
+        per_h, traj = (sums if per_h is None else (per_h + sums[0], traj + sums[1]))
+        ok = torch.arange(v, device=dev)[None, :] < peds[:, None]
+        ades.append(ref[0][ok])
+        fdes.append(ref[1][ok])
+    ades, fdes = torch.cat(ades).cpu().numpy(), torch.cat(fdes).cpu().numpy()
+    s = metrics.summary_of_sums(per_h, traj, levels)
+    return (s._replace(ade=sum(ades.tolist()) / len(ades), fde=sum(fdes.tolist()) / len(fdes)), ades, fdes)

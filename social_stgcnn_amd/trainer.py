@@ -436,6 +436,30 @@ def evaluate_ade_fde_device(model, batches, k_steps=20, seed=0, noise_fn=None):
     return float(ades.mean()), float(fdes.mean()), ades.tolist(), fdes.tolist()
 
 
+def evaluate_dist_device(model, batches, k_steps=20, seed=0, noise_fn=None, levels=(0.5, 0.9, 0.99), kde_floor=20.0):
+    """The distribution metrics of DESIGN.md 5.31 over the batch tuples `evaluate_ade_fde_device` takes, with its draws
+    (seed + batch index, or noise_fn): per batch the forward, `ops.sample_trajectories` and ONE `ops.dist_metrics`
+    launch, the truth summed on the device from the target displacements; the sums stay on the device until the end, so
+    calibration can be watched during `fit` at the cost of one read-back.  Returns a metrics.DistSummary."""
+    from . import metrics
+    model.eval()
+    per_h, traj = None, None
+    for b, (x, adj, peds, obs_last, tgt_rel) in enumerate(batches):
+        y, _ = model(x, adj, peds)
+        n, _, p, v = y.shape
+        dev = y.device
+        truth = torch.cumsum(torch.as_tensor(tgt_rel).to(device=dev, dtype=torch.float32), dim=1)
+        if obs_last is not None:
+            obs_last = torch.as_tensor(obs_last).to(device=dev, dtype=torch.float32)
+            truth = truth + obs_last[:, None]
+        noise = noise_fn(b, (k_steps, n, p, v, 2)) if noise_fn is not None else None
+        samples, mean = ops.sample_trajectories(y, obs_last, peds, k_steps, noise, seed + b)
+        m = ops.dist_metrics(y, mean, samples, truth.contiguous(), peds, kde_floor)
+        sums = metrics.dist_sums(m, peds, levels)
+        per_h, traj = (sums if per_h is None else (per_h + sums[0], traj + sums[1]))
+    return metrics.summary_of_sums(per_h, traj, levels)
+
+
 # ------------------------------------------------------------------------------------------
 # checkpoint files of train.py:202-246 (what test.py:134-160 reads back)
 # ------------------------------------------------------------------------------------------

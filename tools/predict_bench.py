@@ -2,7 +2,7 @@
 """Device time of the captured Predictor (observed absolute tracks -> K sampled trajectories, ONE graph) and of the
 sampling kernel alone, from device events around graph replays.  One JSON line per case.
 
-    python tools/predict_bench.py [--iters 200] [--cases bench,eth,kernel,risk,bestofk]
+    python tools/predict_bench.py [--iters 200] [--cases bench,eth,kernel,risk,bestofk,metrics]
 
   bench   Predictor replay at N = 2048, V = 32 (every slot a pedestrian), K = 20, eth weights
   eth     Predictor replay on eth/test: its 70 windows as one ragged batch, K = 20
@@ -11,6 +11,8 @@ sampling kernel alone, from device events around graph replays.  One JSON line p
           arguments, both captured: K = 20 at N = 2048 x V = 32 with every slot full, and at N = 600 x V = 128 with the
           ragged scene sizes of the six test recordings (frame scenes taken at a fixed stride)
   bestofk stg_bestofk_eval alone at the kernel case's shape, in-kernel normals, captured
+  metrics stg_dist_metrics alone at the kernel case's shape on the sampler's own samples, captured: with the K = 20
+          samples, and the closed-form fields alone
 
 For the kernel's own time run this under `rocprofv3 --kernel-trace --stats -- python tools/predict_bench.py`.
 With the diagnostic library (STG_USE_DIAG_LIB=1, `make -C social_stgcnn_amd/csrc DIAG=1`) STG_SAMPLE_PEDS=1 forces
@@ -115,6 +117,20 @@ def main():
         ms = time_replays(graphs.warm_capture(run_best, 1)[0].replay, args.iters)
         print(json.dumps(dict({"case": "bestofk", "k": k, "n": n, "v": v, "p": p, "ms_per_replay": round(ms, 5)},
                               **info)), flush=True)
+    if "metrics" in cases:
+        gen = torch.Generator().manual_seed(4)
+        y = (torch.randn((n, p, v, 5), generator=gen) * 0.5).to(dev).permute(0, 3, 1, 2)
+        obs_last = torch.randn((n, v, 2), generator=gen).to(dev)
+        samples, mean = ops.sample_trajectories(y, obs_last, None, k, None, 1)
+        truth = (mean + torch.randn((n, p, v, 2), generator=gen).to(dev)).contiguous()
+        for kk, smp in ((k, samples), (0, None)):
+            out = ops.dist_buffers(n, p, v, dev, kk > 0)[0]
+
+            def run_metrics():
+                ops.dist_metrics(y, mean, smp, truth, None, out=out)
+            ms = time_replays(graphs.warm_capture(run_metrics, 1)[0].replay, args.iters)
+            print(json.dumps(dict({"case": "dist_metrics", "k": kk, "n": n, "v": v, "p": p, "ms_per_replay": round(ms, 5),
+                                   "samples_mb": round(kk * n * p * v * 8 / 1e6, 2)}, **info)), flush=True)
     if "risk" in cases:
         from social_stgcnn_amd import frames
         counts = torch.cat([frames.recording_scenes(data.read_file(os.path.join(ROOT, "tests", "golden", "data", d, f)),
