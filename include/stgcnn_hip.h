@@ -660,6 +660,10 @@ int stg_selftest_mfma(const float *a, const float *b, int K, float *c, void *str
  * added entry point, the ABI version stays), declared in stgcnn_hip_metrics.h the same way */
 #include "stgcnn_hip_metrics.h"
 
+/* N15: calibration of the predicted Gaussians, fit and apply (added entry points, the ABI version
+ * stays), declared in stgcnn_hip_calib.h the same way */
+#include "stgcnn_hip_calib.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -182,6 +182,13 @@ _SIGNATURES_METRICS = {
     "stg_dist_metrics": (c_i, [c_f, c_l, c_l, c_l, c_l, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, ctypes.c_float, c_f, c_f,
                                c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
 }
+# ... and those of include/stgcnn_hip_calib.h, included the same way
+_SIGNATURES_CALIB = {
+    "stg_calib_fit_ws_bytes": (c_l, [c_i, c_i, c_i]),
+    "stg_calib_fit": (c_i, [c_f, c_l, c_l, c_l, c_l, c_f, c_f, c_f, c_i, c_i, c_i, c_i, ctypes.c_float, c_f, c_f, c_f,
+                            c_f, c_f, c_f, c_l, c_f]),
+    "stg_calib_apply": (c_i, [c_f, c_l, c_l, c_l, c_l, c_f, c_i, c_i, c_i, c_f, c_l, c_l, c_l, c_l, c_f]),
+}
 
 _lib = None
 
@@ -209,7 +216,8 @@ def lib():
         h = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in {**_SIGNATURES, **_SIGNATURES_SCORE_TIME, **_SIGNATURES_HARVEST,
                                     **_SIGNATURES_HARVEST_TIME, **_SIGNATURES_ASSOC_TIME,
-                                    **_SIGNATURES_ASSOC_FILTER, **_SIGNATURES_METRICS}.items():
+                                    **_SIGNATURES_ASSOC_FILTER, **_SIGNATURES_METRICS,
+                                    **_SIGNATURES_CALIB}.items():
             fn = getattr(h, name)
             fn.restype = res
             fn.argtypes = args

@@ -117,14 +117,24 @@ __device__ __forceinline__ void score_cols(double (&c)[kScoreRow], float err, fl
 }
 
 // ---- enqueue: the prediction of stream b into record `row` ------------------------------------------------------------
-// One step of the running covariance: (cxx, cxy, cyy) += [sx^2, rho sx sy, sy^2] of the element q = (n, field 0, t, v) of
-// V_pred with field stride p_sf, float32 as written (shared with dist_metrics.hip)
-__device__ __forceinline__ void score_cov_add(const float *q, int64_t p_sf, float &cxx, float &cxy, float &cyy) {
+// The covariance of one step: [sx^2, rho sx sy, sy^2] of the element q = (n, field 0, t, v) of V_pred with field stride
+// p_sf, float32 as written (shared with calibrate.hip, which scales it)
+__device__ __forceinline__ void score_sig(const float *q, int64_t p_sf, float &sxx, float &sxy, float &syy) {
 #pragma clang fp contract(off)
     const float sx = expf(q[2 * p_sf]), sy = expf(q[3 * p_sf]), rho = tanhf(q[4 * p_sf]);
-    cxx += sx * sx;
-    cxy += rho * sx * sy;
-    cyy += sy * sy;
+    sxx = sx * sx;
+    sxy = rho * sx * sy;
+    syy = sy * sy;
+}
+
+// One step of the running covariance: (cxx, cxy, cyy) += score_sig (shared with dist_metrics.hip)
+__device__ __forceinline__ void score_cov_add(const float *q, int64_t p_sf, float &cxx, float &cxy, float &cyy) {
+#pragma clang fp contract(off)
+    float sxx, sxy, syy;
+    score_sig(q, p_sf, sxx, sxy, syy);
+    cxx += sxx;
+    cxy += sxy;
+    cyy += syy;
 }
 
 // The running covariance of column v: C_h = sum_{t<=h} [sx^2, rho sx sy, sy^2]_t, float32, ascending t.  A column that is

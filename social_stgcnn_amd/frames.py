@@ -516,19 +516,20 @@ def fill_tracks(obs_abs, seen, num_peds=None, decimals=4):
 
 @torch.no_grad()
 def predict_recording(model, rows, k=20, seed=0, batch_size=64, noise_fn=None, min_peds=1, decimals=4, v_pad=None,
-                      risk=None, tracks=None):
+                      risk=None, tracks=None, calibration=None):
     """Predictions at every frame scene of a recording (recording_scenes with obs_len = model.seq_len): the Predictor
     over batch_size scenes per launch chain, the draws from the Philox stream keyed by seed + batch index, or from
     noise_fn(batch_index, (k,N,P,V,2)) -> standard normals (as predict.sample_test).  Returns (FrameScenes,
     Prediction) with the per-frame predictions concatenated: samples (K,N,P,V,2), mean (N,P,V,2), v_pred (N,5,P,V).
     risk: a predict.RiskSpec (zones (Z,4), the same for every frame) -- the result is then (FrameScenes, Prediction,
     ops.Risk), the counts of ops.sample_risk over each frame's K samples, concatenated like the predictions.
-    tracks: a TrackRule -- the scenes of recording_scenes(tracks=...), a PartialScenes in the place of FrameScenes."""
+    tracks: a TrackRule -- the scenes of recording_scenes(tracks=...), a PartialScenes in the place of FrameScenes.
+    calibration: a calibrate.Calibration the Predictor applies ahead of the sampler."""
     if int(batch_size) < 1:
         raise ValueError("batch_size must be >= 1")
     dev = next(model.parameters()).device
     scenes = recording_scenes(rows, dev, model.seq_len, min_peds, decimals, v_pad, tracks)
-    pred = Predictor(model, k, risk)
+    pred = Predictor(model, k, risk, calibration=calibration)
     if risk is not None and pred.spec.zones is not None and np.ndim(pred.spec.zones) != 2:
         raise ValueError("predict_recording: risk zones (Z,4) expected")
     n, _, v, _ = scenes.obs_abs.shape
@@ -598,7 +599,7 @@ class _LivePredictor:
     h_clock = None                       # with harvest=TimedHarvestSpec: {anchored, g0, instants skipped} per stream
 
     def __init__(self, model, k, obs_len, capacity, max_peds, max_detections, decimals, risk=None, keep_samples=True,
-                 tracks=None, score=None, time=None, associate=None, harvest=None):
+                 tracks=None, score=None, time=None, associate=None, harvest=None, calibration=None):
         self.model = model
         self.k = int(k)
         timed_harvest = isinstance(harvest, TimedHarvestSpec)
@@ -628,7 +629,7 @@ class _LivePredictor:
         if timed_score and time is None:
             raise ValueError("score=TimedScoreSpec(...) needs time=TimeRule(...): its records are indexed by time "
                              "(without time= the push-indexed ScoreSpec serves)")
-        self._risk_args = (risk, keep_samples)
+        self._risk_args = (risk, keep_samples, calibration)
         if score is not None:
             score = score if isinstance(score, (ScoreSpec, TimedScoreSpec)) else ScoreSpec(*score)
             if score.best_of_k and not keep_samples:
@@ -1000,12 +1001,16 @@ class FramePredictor(_LivePredictor):
     TimedHarvestSpec (only together with time=; stg_window_harvest_timed, one launch behind the timed push, inside the
     captured graph): the frames are the instants of the step grid anchored at the first accepted push, the windows are
     tagged (0, grid index of their last frame), `.harvest_clock` (1,3) int64 holds {anchored, g0, instants skipped};
-    it goes with tracks=, risk= and score=TimedScoreSpec(...)."""
+    it goes with tracks=, risk= and score=TimedScoreSpec(...).
+    calibration: a calibrate.Calibration, as in predict.Predictor -- stg_calib_apply between the model and the sampler,
+    inside the captured graph; the returned v_pred, the samples, the risk counts and the score's records are the
+    calibrated ones."""
 
     def __init__(self, model, k=20, obs_len=8, capacity=1024, max_peds=128, max_detections=1024, decimals=4,
-                 risk=None, keep_samples=True, tracks=None, score=None, time=None, associate=None, harvest=None):
+                 risk=None, keep_samples=True, tracks=None, score=None, time=None, associate=None, harvest=None,
+                 calibration=None):
         super().__init__(model, k, obs_len, capacity, max_peds, max_detections, decimals, risk, keep_samples, tracks,
-                         score, time, associate, harvest)
+                         score, time, associate, harvest, calibration)
         dev, m = self._track_state(), self.m_max
         self.det_id = torch.zeros(m, device=dev, dtype=torch.int64)
         self.det_xy = torch.zeros((m, 2), device=dev, dtype=torch.float64)
@@ -1243,13 +1248,14 @@ class StreamsPredictor(_LivePredictor):
     behind the push launch): ONE log, `.harvest`, in which a tick's windows land in stream order, each tagged (stream,
     that stream's push index since its reset); a stream not pushed keeps its harvest history bit for bit.  With time= a
     TimedHarvestSpec, as in FramePredictor (stg_window_harvest_streams_timed): every stream on its own grid,
-    `.harvest_clock` (NS,3)."""
+    `.harvest_clock` (NS,3).
+    calibration: a calibrate.Calibration for every stream, as in FramePredictor."""
 
     def __init__(self, model, streams, k=20, obs_len=8, capacity=1024, max_peds=128, max_detections=1024, decimals=4,
                  max_total_detections=None, block_threads=0, risk=None, keep_samples=True, tracks=None, score=None,
-                 time=None, associate=None, harvest=None):
+                 time=None, associate=None, harvest=None, calibration=None):
         super().__init__(model, k, obs_len, capacity, max_peds, max_detections, decimals, risk, keep_samples, tracks,
-                         score, time, associate, harvest)
+                         score, time, associate, harvest, calibration)
         if not _is_int(streams, 1, MAX_STREAMS):
             raise ValueError("streams must be an integer in [1, %d], got %r" % (MAX_STREAMS, streams))
         self.ns = int(streams)

@@ -8,6 +8,7 @@ import ctypes
 import dataclasses
 import math
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -761,6 +762,104 @@ def dist_metrics(v_pred, mean, samples, truth, num_peds=None, kde_floor=20.0, ou
                                  *[ptr(x) for x in (ref_errors or (None, None))], stream_ptr()),
           "stg_dist_metrics")
     return out
+
+
+CalibFit = collections.namedtuple("CalibFit", "g bracket flags stats sig")
+CalibFit.__doc__ = """What `stg_calib_fit` leaves on the device (DESIGN.md 5.32): g float32 (P,), the fitted factor on the
+covariance of every predicted step; bracket float32 (P,2), the search's final (lo, hi) with g = hi; flags int32 (P,), 0
+or CALIB_LOW / CALIB_HIGH (the search ran into its clamp 2^-10 / 2^21) / CALIB_EMPTY (no element, g = 1); stats float64
+(P,3) = the number of elements, the sum of d2 at g and the number with d2 <= thr at g; sig float32 (N,P,V,3), the
+per-step covariance terms [sx^2, rho sx sy, sy^2] as the kernel computed them."""
+CALIB_MODES = {"moment": 0, "coverage": 1}                                  # STG_CALIB_MOMENT, STG_CALIB_COVERAGE
+CALIB_LOW, CALIB_HIGH, CALIB_EMPTY = 1, 2, 4                                # STG_CALIB_*
+
+
+def calib_buffers(n, p, v, device):
+    """Empty outputs and the scratch buffer of calib_fit on n scenes: (CalibFit, ws uint8)."""
+    def e(dtype, *shape):
+        return torch.empty(shape, device=device, dtype=dtype)
+    nbytes = lib().stg_calib_fit_ws_bytes(n, p, v) if str(device) != "meta" else 0
+    if nbytes < 0:
+        check(int(nbytes), "stg_calib_fit_ws_bytes")
+    # (float64 storage: the scratch buffer is 8-byte aligned whatever the allocator hands out)
+    ws = torch.empty(((nbytes + 7) // 8,), device=device, dtype=torch.float64)
+    return CalibFit(e(torch.float32, p), e(torch.float32, p, 2), e(torch.int32, p), e(torch.float64, p, 3),
+                    e(torch.float32, n, p, v, 3)), ws
+
+
+def calib_fit(v_pred, mean, truth, num_peds=None, mode="coverage", level=0.9, out=None, ws=None):
+    """Fit one factor per predicted step on a set of predictions against the truth (`stg_calib_fit`): v_pred (N,5,P,V)
+    model output (any strides), mean (N,P,V,2) as the sampler leaves it, truth (N,P,V,2) absolute positions, num_peds
+    (N,) or None.  mode "moment": the smallest searched g_h at which the mean d2 at horizon h is at most 2; "coverage":
+    at which the ellipse of probability `level` (a float32) holds at least that share of the truths.  The fit is
+    sequential over the horizons and needs the whole set in ONE call.  out, ws: calib_buffers(N, P, V, device) of an
+    earlier call (graph capture: nothing is allocated then).  Returns a CalibFit of device tensors; nothing is
+    synchronised."""
+    require_gpu(v_pred, mean, truth)
+    if v_pred.dim() != 4 or v_pred.shape[1] != 5:
+        raise ValueError("calib_fit: v_pred (N,5,P,V) expected")
+    n, _, p, v = v_pred.shape
+    _lib.as_f32(v_pred, "v_pred")
+    for name, x in (("mean", mean), ("truth", truth)):
+        if tuple(x.shape) != (n, p, v, 2) or x.dtype != torch.float32 or not x.is_contiguous():
+            raise ValueError("calib_fit: %s must be a contiguous float32 %s tensor" % (name, (n, p, v, 2)))
+    if mode not in CALIB_MODES:
+        raise ValueError("calib_fit: mode must be one of %s, got %r" % (sorted(CALIB_MODES), mode))
+    level = float(np.float32(level))
+    if not 0.0 < level < 1.0:
+        raise ValueError("calib_fit: level must lie in (0, 1), got %r" % (level,))
+    for what, got, most in (("V", v, SCORE_MAX_V), ("P", p, SCORE_MAX_P)):
+        if got > most:
+            raise ValueError("calib_fit: %s=%d above the kernel's limit of %d" % (what, got, most))
+    if (out is None) != (ws is None):
+        raise ValueError("calib_fit: out and ws go together (calib_buffers)")
+    if out is None:
+        out, ws = calib_buffers(n, p, v, v_pred.device)
+    else:
+        want = calib_buffers(n, p, v, "meta")[0]
+        for name, o, w in zip(CalibFit._fields, out, want):
+            if tuple(o.shape) != tuple(w.shape) or o.dtype != w.dtype or not o.is_contiguous() or not o.is_cuda:
+                raise ValueError("calib_fit: out.%s does not fit this call (contiguous %s %s)"
+                                 % (name, w.dtype, tuple(w.shape)))
+        require_gpu(ws)
+    peds = peds_arg(num_peds, n, v_pred.device)
+    if n == 0:                                              # nothing to launch: the result of a fit without elements
+        out.g.fill_(1.0)
+        out.bracket.fill_(1.0)
+        out.flags.fill_(CALIB_EMPTY)
+        out.stats.zero_()
+        return out
+    check(lib().stg_calib_fit(ptr(v_pred), *v_pred.stride(), ptr(mean), ptr(truth), ptr(peds), n, p, v,
+                              CALIB_MODES[mode], ctypes.c_float(level), *[ptr(o) for o in out], ptr(ws),
+                              ws.numel() * ws.element_size(), stream_ptr()), "stg_calib_fit")
+    return out
+
+
+def calib_shift(g):
+    """The log-sigma shift of the factors g: float32(0.5 log(float64 g)), on the host."""
+    g = np.asarray(g.detach().cpu().numpy() if torch.is_tensor(g) else g, np.float32)
+    if g.ndim != 1 or not (np.isfinite(g).all() and (g > 0).all()):
+        raise ValueError("calib_shift: g must be a vector of positive finite factors")
+    return (0.5 * np.log(g.astype(np.float64))).astype(np.float32)
+
+
+def calib_apply(v_pred, shift, out=None):
+    """v_pred[:, 2:4, t, :] += shift[t] on the device (`stg_calib_apply`), one launch over every V slot: v_pred
+    (N,5,P,V) float32 (any strides), shift (P,) float32 device tensor (calib_shift).  out None: in place; else a float32
+    (N,5,P,V) tensor (any strides) that receives all five fields.  Returns the tensor written."""
+    require_gpu(v_pred, shift, out)
+    if v_pred.dim() != 4 or v_pred.shape[1] != 5:
+        raise ValueError("calib_apply: v_pred (N,5,P,V) expected")
+    n, _, p, v = v_pred.shape
+    _lib.as_f32(v_pred, "v_pred")
+    if tuple(shift.shape) != (p,) or shift.dtype != torch.float32 or not shift.is_contiguous():
+        raise ValueError("calib_apply: shift must be a contiguous float32 (%d,) tensor" % p)
+    if out is not None and (tuple(out.shape) != (n, 5, p, v) or out.dtype != torch.float32):
+        raise ValueError("calib_apply: out must be a float32 %s tensor" % ((n, 5, p, v),))
+    o_strides = out.stride() if out is not None else (0, 0, 0, 0)
+    check(lib().stg_calib_apply(ptr(v_pred), *v_pred.stride(), ptr(shift), n, p, v, ptr(out), *o_strides,
+                                stream_ptr()), "stg_calib_apply")
+    return v_pred if out is None else out
 
 
 def sample_trajectories(y, obs_last=None, num_peds=None, k=20, noise=None, seed=0, seed_dev=None, samples=None,

@@ -128,8 +128,13 @@ def eval_mode(model):
 class Predictor:
     """K sampled trajectories per pedestrian from observed absolute tracks, for a whole batch of scenes."""
 
-    def __init__(self, model, k=20, risk=None, keep_samples=True):
-        """risk: a RiskSpec -- every prediction also reduces its K samples to conflict / zone counts on the device
+    def __init__(self, model, k=20, risk=None, keep_samples=True, calibration=None):
+        """calibration: a calibrate.Calibration (or None) -- one launch of ops.calib_apply between the model and the
+        sampler shifts the two log-sigma channels of the model output by the calibration's per-step shift, so the
+        samples, the risk counts and Prediction.v_pred (what a live score or ops.dist_metrics judge) are the calibrated
+        ones; the mean is untouched.  `self.shift` is the (P,) float32 device tensor the launch reads, one of the static
+        buffers of a captured chain.  With None nothing is launched.
+        risk: a RiskSpec -- every prediction also reduces its K samples to conflict / zone counts on the device
         (ops.sample_risk, same draws), left at `self.risk` (an ops.Risk) by predict() and by every replay; `self.zones`
         is the device tensor of rectangles the reducer reads, which a caller may overwrite between replays.
         keep_samples=False (with risk only): the samples themselves are not written, Prediction.samples is
@@ -146,6 +151,17 @@ class Predictor:
         self.keep_samples = bool(keep_samples)
         self.risk = None
         self.zones = None
+        self.calibration = calibration
+        self.shift = None
+        if calibration is not None and len(calibration.shift) != model.pred_seq_len:
+            raise ValueError("Predictor: the calibration holds %d steps, the model predicts %d"
+                             % (len(calibration.shift), model.pred_seq_len))
+
+    def _shift(self, dev):
+        """The static device tensor of the calibration's shift (None without a calibration)."""
+        if self.shift is None and self.calibration is not None:
+            self.shift = torch.from_numpy(np.ascontiguousarray(self.calibration.shift, dtype=np.float32)).to(dev)
+        return self.shift
 
     def _zones(self, n, dev):
         """The static device tensor of the spec's rectangles, (Z,4) or (n,Z,4)."""
@@ -156,6 +172,8 @@ class Predictor:
     def _forward(self, obs_abs, peds, seed, noise, seed_dev=None, bufs=None, outs=(None, None), risk_out=None):
         x, adj, obs_last = observed_inputs(obs_abs, peds, bufs)
         y, _ = self.model(x, adj, peds)
+        if self.calibration is not None:
+            y = ops.calib_apply(y, self._shift(y.device))
         keep = self.keep_samples
         samples, mean = ops.sample_trajectories(y, obs_last, peds, self.k if keep else 0, noise if keep else None,
                                                 seed, seed_dev, *outs)
@@ -200,6 +218,7 @@ class Predictor:
         freed one would go back to the caching allocator while the graph still writes it."""
         n, _, v, _ = obs.shape
         bufs, outs, risk = self._chain_buffers(n, v, obs.device)
+        self._shift(obs.device)                             # (copied to the device ahead of the capture)
 
         def step():
             if pre is not None:
@@ -210,7 +229,7 @@ class Predictor:
             return r
         with eval_mode(self.model):
             graph, res = graphs.warm_capture(step, warmup)
-        return graph, res, (bufs, outs, risk, self.zones)
+        return graph, res, (bufs, outs, risk, self.zones, self.shift)
 
     def capture(self, n, v, num_peds, dtype=torch.float32, warmup=2):
         """Capture ONE graph on static buffers for batches of n scenes padded to v pedestrians, positions of `dtype`
@@ -250,13 +269,14 @@ def _displacement_errors(pred, trgt):
 
 
 @torch.no_grad()
-def sample_test(model, windows, k=20, batch_size=64, seed=0, noise_fn=None):
+def sample_test(model, windows, k=20, batch_size=64, seed=0, noise_fn=None, calibration=None):
     """test.test() (test.py:18-127) over data.SceneWindows, batch_size windows per launch chain.  Returns (ade, fde,
     raw): raw[step] (1-based, one per window) = {'obs': (T_obs,V_i,2), 'trgt': (P,V_i,2), 'pred': [K x (P,V_i,2)]}
     float32 numpy arrays as test.py:87-105 builds them; ade / fde the best-of-k means over all pedestrians.  The draws
     come from the kernel's Philox stream keyed by seed + batch index, or from noise_fn(batch_index, (k,N,P,V,2)) ->
-    standard normals (as in trainer.evaluate_ade_fde_device)."""
-    pred = Predictor(model, k)
+    standard normals (as in trainer.evaluate_ade_fde_device).  calibration: a calibrate.Calibration the Predictor
+    applies ahead of the sampler (None: nothing is launched)."""
+    pred = Predictor(model, k, calibration=calibration)
     dev = next(model.parameters()).device
     t_obs = model.seq_len
     raw, ades, fdes, step = {}, [], [], 0
@@ -290,7 +310,7 @@ def sample_test(model, windows, k=20, batch_size=64, seed=0, noise_fn=None):
 
 @torch.no_grad()
 def distribution_test(model, windows, k=20, batch_size=64, seed=0, noise_fn=None, levels=(0.5, 0.9, 0.99),
-                      kde_floor=20.0):
+                      kde_floor=20.0, calibration=None):
     """What sample_test cannot say about a test set: whether the predicted Gaussians are calibrated
     (Mahalanobis distance, NLL, ellipse coverage, the larger eigenvalue), how likely the truth is under the K samples
     (KDE-NLL) and how well a scene as a whole is predicted (joint ADE / FDE).  The batching and the draws are
@@ -299,9 +319,11 @@ def distribution_test(model, windows, k=20, batch_size=64, seed=0, noise_fn=None
     the per-pedestrian errors.  Returns (metrics.DistSummary, ade, fde): the best-of-K errors of every pedestrian,
     float64 numpy arrays in sample_test's order, in the arithmetic sample_test evaluates on the host (the kernel's
     ade_ref / fde_ref: float32 differences and squares, float64 root and sum); the summary's .ade / .fde are their means
-    summed as sample_test sums them, so the two functions report the same ADE / FDE at the same seed, to the last bit."""
+    summed as sample_test sums them, so the two functions report the same ADE / FDE at the same seed, to the last bit.
+    calibration: a calibrate.Calibration the Predictor applies ahead of the sampler, so the Gaussians judged are the
+    calibrated ones (None: nothing is launched)."""
     from . import metrics
-    pred = Predictor(model, k)
+    pred = Predictor(model, k, calibration=calibration)
     dev = next(model.parameters()).device
     t_obs = model.seq_len
     per_h, traj, ades, fdes = None, None, [], []

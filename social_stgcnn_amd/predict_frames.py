@@ -12,7 +12,7 @@ trajectories for every pedestrian tracked over the last obs_seq_len frames.
                                                                       [,GATE_MAX[,MAX_AGE]]]]]]
                                                [--associate GATE[,GATE_NEW[,MAX_MISS]] [--max_peds V]]
                                                [--harvest WINDOWS [--harvest_out FILE.npz] [--max_peds V]]
-                                               --out preds.npz
+                                               [--calibration FILE.npz] --out preds.npz
 
 DIR is a checkpoint directory in the reference's layout (args.pkl and val_best.pth, as social_stgcnn_amd.test reads
 it); FILE a recording in the ETH/UCY text format (<frame> <ped> <x> <y>).  The .npz holds, one entry per frame scene:
@@ -70,6 +70,10 @@ the assigned track ids, and assoc_ids (M,) int64 as with --associate.  It goes t
 noisy detector: associate=frames.FilteredAssociateSpec(...), a constant-velocity Kalman filter per track
 and a gate of GATE_SIGMAS standard deviations of the predicted position, at most GATE_MAX.  The same arrays; the scenes
 hold the detections as reported.  Not with --associate or --associate_timed.
+
+--calibration FILE.npz (what `python -m social_stgcnn_amd.test --calibrate ... --save_calibration` writes; DESIGN.md
+5.32) goes with every mode: the predictor shifts the log sigmas of the model output by the file's per-step factors ahead
+of the sampler, so the samples, the risk counts and the score are the calibrated ones; the means do not change.
 """
 import argparse
 import os
@@ -79,6 +83,7 @@ import numpy as np
 import torch
 
 from . import data
+from .calibrate import Calibration
 from .frames import (AssociateSpec, FilteredAssociateSpec, FramePredictor, HarvestSpec, TimedAssociateSpec, TimedHarvestSpec, TimeRule, TrackRule,
                      predict_recording, score_summary, sorted_rows)
 from .model import social_stgcnn
@@ -134,6 +139,9 @@ def build_parser():
     p.add_argument("--settle", type=int, default=None, metavar="D",
                    help="with --harvest_timed: resolve a grid instant D ticks after it (0 .. max_dt - 1; default "
                         "max_dt - 1)")
+    p.add_argument("--calibration", default=None, metavar="FILE.npz",
+                   help="apply the per-step covariance factors of this file (calibrate.Calibration.save) ahead of the "
+                        "sampler")
     p.add_argument("--out", required=True, help="output .npz")
     # a rectangle may begin with a negative coordinate: "-1,-1,1,1" is a value, not an option
     p._negative_number_matcher = re.compile(r"^-[0-9.][0-9.,eE+-]*$")
@@ -160,7 +168,7 @@ def load_model(exp_path, device):
 
 
 def predict_timed(model, rows, time, k=20, seed=0, min_peds=1, tracks=None, max_peds=128, score=None, harvest=None,
-                  associate=None):
+                  associate=None, calibration=None):
     """Every distinct frame number of `rows`, taken as a time in ticks, pushed through ONE captured timed
     FramePredictor -> a dict of host arrays, one entry per push whose scene holds at least min_peds pedestrians.
     associate: a frames.TimedAssociateSpec -- the id column is ignored, the rows of a push go in file order, and the dict
@@ -183,7 +191,7 @@ def predict_timed(model, rows, time, k=20, seed=0, min_peds=1, tracks=None, max_
     ticks = frames.astype(np.int64)
     m_max = max(1, int(np.diff(fs).max()) if len(frames) else 1)
     fp = FramePredictor(model, k=k, obs_len=model.seq_len, max_peds=max_peds, max_detections=m_max, tracks=tracks,
-                        time=time, score=score, harvest=harvest, associate=associate)
+                        time=time, score=score, harvest=harvest, associate=associate, calibration=calibration)
     replay = fp.capture()
     keep = {name: [] for name in ("time", "ids", "num_peds", "mean", "samples", "seen")}
     for f, t in enumerate(ticks.tolist()):
@@ -271,7 +279,7 @@ def check_associate_timed_args(a):
     return parse_associate_timed(a.associate_timed)
 
 
-def predict_associated(model, rows, associate, k=20, seed=0, min_peds=1, tracks=None, max_peds=128):
+def predict_associated(model, rows, associate, k=20, seed=0, min_peds=1, tracks=None, max_peds=128, calibration=None):
     """Every distinct frame number of `rows` pushed without ids, rows in file order, through ONE captured
     FramePredictor(associate=...) -> a dict of host arrays: one entry per push whose scene holds at least min_peds
     pedestrians, and assoc_ids, the assigned id of every row."""
@@ -282,7 +290,7 @@ def predict_associated(model, rows, associate, k=20, seed=0, min_peds=1, tracks=
     fs = np.searchsorted(f_idx[order], np.arange(len(frames) + 1))
     m_max = max(1, int(np.diff(fs).max()) if len(frames) else 1)
     fp = FramePredictor(model, k=k, obs_len=model.seq_len, max_peds=max_peds, max_detections=m_max, tracks=tracks,
-                        associate=associate)
+                        associate=associate, calibration=calibration)
     replay = fp.capture()
     assoc_ids = np.full(len(rows), -1, np.int64)
     names = ("frame", "ids", "num_peds", "mean", "samples") + (() if tracks is None else ("seen",))
@@ -341,14 +349,14 @@ def check_harvest_args(a):
         raise ValueError("--harvest: at least one window, got %d" % a.harvest)
 
 
-def predict_harvested(model, rows, harvest, k=20, seed=0, min_peds=1, tracks=None, max_peds=128):
+def predict_harvested(model, rows, harvest, k=20, seed=0, min_peds=1, tracks=None, max_peds=128, calibration=None):
     """Every distinct frame number of `rows` pushed through ONE captured FramePredictor(harvest=...) -> (a dict of host
     arrays, one entry per push whose scene holds at least min_peds pedestrians, and the dict of what the run harvested:
     seq_rel (R,2,T_all) float32, num_peds (W,) int32, tags (W,2) int32 = (0, push index), dropped_full)."""
     frames, fs, ids, xy = sorted_rows(rows)
     m_max = max(1, int(np.diff(fs).max()) if len(frames) else 1)
     fp = FramePredictor(model, k=k, obs_len=model.seq_len, capacity=max(1024, m_max), max_peds=max_peds,
-                        max_detections=m_max, tracks=tracks, harvest=harvest)
+                        max_detections=m_max, tracks=tracks, harvest=harvest, calibration=calibration)
     replay = fp.capture()
     names = ("frame", "ids", "num_peds", "mean", "samples") + (() if tracks is None else ("seen",))
     keep = {name: [] for name in names}
@@ -385,6 +393,7 @@ def main(argv=None):
         raise RuntimeError("social_stgcnn_amd.predict_frames needs a GPU (MI355X)")
     model = load_model(a.checkpoint, torch.device("cuda", torch.cuda.current_device()))
     rows = data.read_file(a.recording, a.delim)
+    calibration = None if a.calibration is None else Calibration.load(a.calibration)
     extra = {}
     tracks = None
     if a.min_seen is not None or a.max_gap is not None:
@@ -394,7 +403,7 @@ def main(argv=None):
                          "by time")
     if a.harvest is not None:
         res, kept = predict_harvested(model, rows, HarvestSpec(a.harvest), a.ksteps, a.seed, a.min_peds, tracks,
-                                      a.max_peds)
+                                      a.max_peds, calibration)
         np.savez(a.out, **res)
         if a.harvest_out is not None:
             np.savez(a.harvest_out, **kept)
@@ -406,7 +415,7 @@ def main(argv=None):
         if a.step is not None or a.radius is not None or a.zones is not None:
             raise ValueError("--associate does not go together with --step or --radius / --zones")
         res = predict_associated(model, rows, parse_associate(a.associate), a.ksteps, a.seed, a.min_peds, tracks,
-                                 a.max_peds)
+                                 a.max_peds, calibration)
         np.savez(a.out, **res)
         print("%d pushes with a scene, up to %d pedestrians, %d track ids -> %s"
               % (len(res["frame"]), res["ids"].shape[1], int(res["assoc_ids"].max(initial=-1)) + 1, a.out))
@@ -416,7 +425,8 @@ def main(argv=None):
             raise ValueError("--step does not go together with --radius / --zones")
         spec = None if a.harvest_timed is None else TimedHarvestSpec(a.harvest_timed, settle=a.settle)
         res = predict_timed(model, rows, TimeRule(a.step, a.max_dt, a.history), a.ksteps, a.seed, a.min_peds, tracks,
-                            a.max_peds, TimedScoreSpec(pending=a.pending) if a.score else None, spec, assoc_timed)
+                            a.max_peds, TimedScoreSpec(pending=a.pending) if a.score else None, spec, assoc_timed,
+                            calibration)
         if spec is not None:
             res, kept = res
             if a.harvest_out is not None:
@@ -435,11 +445,13 @@ def main(argv=None):
                      float(res["score_fde"]), int(res["score_evictions"])))
         return
     if a.radius is None and a.zones is None:
-        scenes, pred = predict_recording(model, rows, k=a.ksteps, seed=a.seed, min_peds=a.min_peds, tracks=tracks)
+        scenes, pred = predict_recording(model, rows, k=a.ksteps, seed=a.seed, min_peds=a.min_peds, tracks=tracks,
+                                         calibration=calibration)
     else:
         zones = parse_zones(a.zones) if a.zones is not None else None
         scenes, pred, risk = predict_recording(model, rows, k=a.ksteps, seed=a.seed, min_peds=a.min_peds,
-                                               risk=RiskSpec(a.radius, zones, a.radius is not None), tracks=tracks)
+                                               risk=RiskSpec(a.radius, zones, a.radius is not None), tracks=tracks,
+                                               calibration=calibration)
         extra = {"risk_" + f: x.cpu().numpy() for f, x in zip(risk._fields[1:], risk[1:]) if x is not None}
         extra["risk_k"] = np.int32(risk.k)
         if zones is not None:

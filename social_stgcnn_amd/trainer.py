@@ -436,18 +436,25 @@ def evaluate_ade_fde_device(model, batches, k_steps=20, seed=0, noise_fn=None):
     return float(ades.mean()), float(fdes.mean()), ades.tolist(), fdes.tolist()
 
 
-def evaluate_dist_device(model, batches, k_steps=20, seed=0, noise_fn=None, levels=(0.5, 0.9, 0.99), kde_floor=20.0):
+def evaluate_dist_device(model, batches, k_steps=20, seed=0, noise_fn=None, levels=(0.5, 0.9, 0.99), kde_floor=20.0,
+                         calibration=None):
     """The distribution metrics of DESIGN.md 5.31 over the batch tuples `evaluate_ade_fde_device` takes, with its draws
     (seed + batch index, or noise_fn): per batch the forward, `ops.sample_trajectories` and ONE `ops.dist_metrics`
     launch, the truth summed on the device from the target displacements; the sums stay on the device until the end, so
-    calibration can be watched during `fit` at the cost of one read-back.  Returns a metrics.DistSummary."""
+    calibration can be watched during `fit` at the cost of one read-back.  calibration: a calibrate.Calibration --
+    `ops.calib_apply` shifts the model output ahead of the sampler (None: nothing is launched).  Returns a
+    metrics.DistSummary."""
     from . import metrics
     model.eval()
-    per_h, traj = None, None
+    per_h, traj, shift = None, None, None
     for b, (x, adj, peds, obs_last, tgt_rel) in enumerate(batches):
         y, _ = model(x, adj, peds)
         n, _, p, v = y.shape
         dev = y.device
+        if calibration is not None:
+            if shift is None:
+                shift = torch.from_numpy(np.ascontiguousarray(calibration.shift, dtype=np.float32)).to(dev)
+            y = ops.calib_apply(y, shift)
         truth = torch.cumsum(torch.as_tensor(tgt_rel).to(device=dev, dtype=torch.float32), dim=1)
         if obs_last is not None:
             obs_last = torch.as_tensor(obs_last).to(device=dev, dtype=torch.float32)

@@ -208,7 +208,7 @@ def _stream_sequences(ns, n, timed=None):
 
 
 def streams_case(ns, k, n_ticks, dev, block=0, lone=True, max_peds=128, warmup=20, risk="none", tracks=None,
-                 score=None, timed=None, associate=None, harvest=False, noise=0.0):
+                 score=None, timed=None, associate=None, harvest=False, noise=0.0, calibration=None):
     from social_stgcnn_amd import frames
     model = model_for("univ", dev)
     seq = _stream_sequences(ns, warmup + n_ticks, timed)
@@ -225,6 +225,8 @@ def streams_case(ns, k, n_ticks, dev, block=0, lone=True, max_peds=128, warmup=2
     kw.update(tracks_kw(tracks, timed))
     if harvest:
         kw["harvest"] = harvest_spec(ns * (warmup + n_ticks), timed)
+    if calibration is not None:                              # (tools/predict_bench.py --cases calib)
+        kw["calibration"] = calibration
     if associate is not None:
         kw["associate"] = associate
         seq = [[(None,) + tuple(p[1:]) for p in q] for q in seq]

@@ -2,7 +2,7 @@
 """Device time of the captured Predictor (observed absolute tracks -> K sampled trajectories, ONE graph) and of the
 sampling kernel alone, from device events around graph replays.  One JSON line per case.
 
-    python tools/predict_bench.py [--iters 200] [--cases bench,eth,kernel,risk,bestofk,metrics]
+    python tools/predict_bench.py [--iters 200] [--cases bench,eth,kernel,risk,bestofk,metrics,calib]
 
   bench   Predictor replay at N = 2048, V = 32 (every slot a pedestrian), K = 20, eth weights
   eth     Predictor replay on eth/test: its 70 windows as one ragged batch, K = 20
@@ -13,6 +13,9 @@ sampling kernel alone, from device events around graph replays.  One JSON line p
   bestofk stg_bestofk_eval alone at the kernel case's shape, in-kernel normals, captured
   metrics stg_dist_metrics alone at the kernel case's shape on the sampler's own samples, captured: with the K = 20
           samples, and the closed-form fields alone
+  calib   stg_calib_fit (both modes, 2 + 8 P launches) and stg_calib_apply (in place) alone at the kernel case's shape,
+          captured; the Predictor replay of the bench case with calibration=; and a 600-stream tick of
+          frames.StreamsPredictor (frames_bench.py's streams case, 100 ticks) with and without calibration=
 
 For the kernel's own time run this under `rocprofv3 --kernel-trace --stats -- python tools/predict_bench.py`.
 With the diagnostic library (STG_USE_DIAG_LIB=1, `make -C social_stgcnn_amd/csrc DIAG=1`) STG_SAMPLE_PEDS=1 forces
@@ -131,6 +134,42 @@ def main():
             ms = time_replays(graphs.warm_capture(run_metrics, 1)[0].replay, args.iters)
             print(json.dumps(dict({"case": "dist_metrics", "k": kk, "n": n, "v": v, "p": p, "ms_per_replay": round(ms, 5),
                                    "samples_mb": round(kk * n * p * v * 8 / 1e6, 2)}, **info)), flush=True)
+    if "calib" in cases:
+        from social_stgcnn_amd.calibrate import Calibration
+        from social_stgcnn_amd.predict import Predictor
+        gen = torch.Generator().manual_seed(5)
+        y = (torch.randn((n, p, v, 5), generator=gen) * 0.5).to(dev).permute(0, 3, 1, 2)
+        mean = torch.cumsum(torch.randn((n, p, v, 2), generator=gen) * 0.4, 1).to(dev)
+        truth = (mean + torch.randn((n, p, v, 2), generator=gen).to(dev) * 2.0).contiguous()
+        out, ws = ops.calib_buffers(n, p, v, dev)
+        for mode in ("moment", "coverage"):
+            def run_fit():
+                ops.calib_fit(y, mean, truth, None, mode, 0.9, out=out, ws=ws)
+            ms = time_replays(graphs.warm_capture(run_fit, 1)[0].replay, args.iters)
+            print(json.dumps(dict({"case": "calib_fit", "mode": mode, "n": n, "v": v, "p": p, "launches": 2 + 8 * p,
+                                   "ms_per_replay": round(ms, 5), "g": [round(float(x), 4) for x in out.g.cpu()],
+                                   "ws_mb": round(ws.numel() * 8 / 1e6, 3)}, **info)), flush=True)
+        cal = Calibration(out.g, "coverage", 0.9)
+        shift = torch.from_numpy(cal.shift).to(dev)
+
+        def run_apply():
+            ops.calib_apply(y, shift)
+        ms = time_replays(graphs.warm_capture(run_apply, 1)[0].replay, args.iters)
+        print(json.dumps(dict({"case": "calib_apply", "n": n, "v": v, "p": p, "ms_per_replay": round(ms, 5),
+                               "mb_moved": round(2 * n * 2 * p * v * 4 / 1e6, 2)}, **info)), flush=True)
+        start = torch.rand((n, 1, v, 2), generator=gen) * 20 - 10
+        obs = torch.cat([start, start + torch.cumsum(torch.randn((n, 7, v, 2), generator=gen) * 0.3, 1)], 1).to(dev)
+        peds = torch.full((n,), v, dtype=torch.int32, device=dev)
+        for c in (None, cal):
+            pr = Predictor(m, k=k, calibration=c)
+            pr.capture(n, v, peds)(obs, seed=1)
+            ms = time_replays(pr._graph.replay, args.iters)
+            print(json.dumps(dict({"case": "predictor_bench", "calibration": c is not None, "n": n, "v": v, "k": k,
+                                   "ms_per_replay": round(ms, 5)}, **info)), flush=True)
+        import frames_bench                                   # (tools/ is this script's directory)
+        for c in (None, cal):
+            res = frames_bench.streams_case(600, k, 100, dev, lone=False, calibration=c)
+            print(json.dumps(dict(res, calibration=c is not None, **info)), flush=True)
     if "risk" in cases:
         from social_stgcnn_amd import frames
         counts = torch.cat([frames.recording_scenes(data.read_file(os.path.join(ROOT, "tests", "golden", "data", d, f)),
