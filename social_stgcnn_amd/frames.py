@@ -47,14 +47,16 @@ stg_frame_scenes over a recording uploaded once, stg_track_push with the track s
                        the device (stg_window_harvest); `.harvest` is the LiveWindows, whose snapshot()
                        is a dataset.DeviceWindows for train.fine_tune
 
-The two live predictors are one core, _LivePredictor: the argument checks, the track state, the eager push and its
-capture (the push kernel ahead of predict.Predictor.capture_chain; the capture recipe itself is graphs.py).  Each class
-keeps what is its own: how a push is staged, its push kernel, its result tuple, its reset, and how the warm-up is kept
-from moving the tracks.
+The two live predictors are one core, _LivePredictor: the argument checks (which spec goes with time= is one table,
+_OPTIONS), the eager push and its capture (the launches ahead of predict.Predictor.capture_chain and the score behind it;
+the capture recipe itself is graphs.py).  What launches around the model is a _Stage each -- _Association, _Tracks,
+_Harvest, _Score.  Each class keeps what is its own: how a push is staged, what differs between one stream
+and many (its _Feed), its result tuple, which streams its reset names, and how the warm-up is kept from moving the tracks.
 """
 import collections
 import collections.abc
 import ctypes
+import functools
 
 import numpy as np
 import torch
@@ -182,10 +184,7 @@ class AssociateSpec(collections.namedtuple("AssociateSpec", "gate gate_new max_m
             raise ValueError("AssociateSpec: the squared gates must be finite and > 0, got %r, %r" % (gate, gate_new))
         if not _is_int(max_miss, 0, (1 << 31) - 2):
             raise ValueError("AssociateSpec: max_miss must be an integer >= 0, got %r" % (max_miss,))
-        if capacity is not None and not _is_int(capacity, 1, MAX_SLOTS):
-            raise ValueError("AssociateSpec: capacity must be None or an integer in [1, %d], got %r"
-                             % (MAX_SLOTS, capacity))
-        return super().__new__(cls, gate, gate_new, int(max_miss), None if capacity is None else int(capacity))
+        return super().__new__(cls, gate, gate_new, int(max_miss), _capacity(capacity, "AssociateSpec"))
 
 
 class TimedAssociateSpec(collections.namedtuple("TimedAssociateSpec", "gate gate_new max_age capacity")):
@@ -205,11 +204,7 @@ class TimedAssociateSpec(collections.namedtuple("TimedAssociateSpec", "gate gate
             base = AssociateSpec(gate, gate_new, 0, capacity)
         except ValueError as e:
             raise ValueError("Timed" + str(e)) from None
-        max_age = 0 if max_age is None else max_age
-        if not _is_number(max_age) or not _is_int(max_age, 0, (1 << 31) - 1):
-            raise ValueError("TimedAssociateSpec: max_age must be an integer number of ticks in [0, 2^31), got %r"
-                             % (max_age,))
-        return super().__new__(cls, base.gate, base.gate_new, int(max_age), base.capacity)
+        return super().__new__(cls, base.gate, base.gate_new, _max_age(max_age, "TimedAssociateSpec"), base.capacity)
 
 
 class FilteredAssociateSpec(collections.namedtuple(
@@ -237,15 +232,8 @@ class FilteredAssociateSpec(collections.namedtuple(
             if not np.isfinite(sq) or (sq == 0.0 and not low):
                 raise ValueError("FilteredAssociateSpec: the squared %s must be finite and > 0 in float64, got %r"
                                  % (name, x))
-        max_age = 0 if max_age is None else max_age
-        if not _is_number(max_age) or not _is_int(max_age, 0, (1 << 31) - 1):
-            raise ValueError("FilteredAssociateSpec: max_age must be an integer number of ticks in [0, 2^31), got %r"
-                             % (max_age,))
-        if capacity is not None and (not _is_number(capacity) or not _is_int(capacity, 1, MAX_SLOTS)):
-            raise ValueError("FilteredAssociateSpec: capacity must be None or an integer in [1, %d], got %r"
-                             % (MAX_SLOTS, capacity))
-        return super().__new__(cls, *(float(x) for x in vals.values()), int(max_age),
-                               None if capacity is None else int(capacity))
+        return super().__new__(cls, *(float(x) for x in vals.values()), _max_age(max_age, "FilteredAssociateSpec"),
+                               _capacity(capacity, "FilteredAssociateSpec"))
 
 
 _TIMED_ASSOC = (TimedAssociateSpec, FilteredAssociateSpec)     # the association specs that go with time= only
@@ -392,6 +380,26 @@ def _is_number(x):
 def _is_int(x, lo, hi=None):
     """x is an integer (a bool is not) with lo <= x (<= hi)."""
     return not isinstance(x, bool) and int(x) == x and lo <= int(x) and (hi is None or int(x) <= hi)
+
+
+def _max_age(max_age, what):
+    """The max_age of the association specs that age their tracks by time (None: 0)."""
+    max_age = 0 if max_age is None else max_age
+    if not _is_number(max_age) or not _is_int(max_age, 0, (1 << 31) - 1):
+        raise ValueError("%s: max_age must be an integer number of ticks in [0, 2^31), got %r" % (what, max_age))
+    return int(max_age)
+
+
+def _capacity(capacity, what):
+    """The capacity of an association spec: None (the predictor's), or a number of track slots."""
+    if capacity is not None and (not _is_number(capacity) or not _is_int(capacity, 1, MAX_SLOTS)):
+        raise ValueError("%s: capacity must be None or an integer in [1, %d], got %r" % (what, MAX_SLOTS, capacity))
+    return None if capacity is None else int(capacity)
+
+
+def _stream_index(key, streams, what):
+    if isinstance(key, (bool, np.bool_)) or not isinstance(key, (int, np.integer)) or not 0 <= key < streams:
+        raise ValueError("%s: stream index %r not in [0, %d)" % (what, key, streams))
 
 
 def _obs_len(obs_len):
@@ -575,26 +583,219 @@ def host_detections(ids, xy, max_detections):
     return ids_np, np.ascontiguousarray(xy_np)
 
 
+_Option = collections.namedtuple("_Option", "plain timed with_time without_time coerce")
+
+
+def _bare(spec):
+    """A bare tuple or number in the place of the push-indexed `spec` -> that spec."""
+    return lambda x: spec(*x) if isinstance(x, (tuple, list)) else spec(x)
+
+
+# Which spec goes with time=, per option in the order they are checked: the push-indexed spec (what a bare tuple or number
+# is coerced to), the spec(s) that go with time= only, and the refusal of each without its match (%s: the spec's class).
+_OPTIONS = {
+    "harvest": _Option(
+        HarvestSpec, (TimedHarvestSpec,),
+        "harvest= together with time= is not supported: a timed push is not one frame of a window (DESIGN.md 8)",
+        "harvest=%s(...) needs time=TimeRule(...): its frames are instants of the step grid (without time= the "
+        "push-indexed HarvestSpec serves)", _bare(HarvestSpec)),
+    "associate": _Option(
+        AssociateSpec, _TIMED_ASSOC,
+        "associate= together with time= is not supported: a velocity per tick and a gate that grows with the gap are a "
+        "change of their own (DESIGN.md 8)",
+        "associate=%s(...) needs time=TimeRule(...): its tracks are aged by time (without time= the push-indexed "
+        "AssociateSpec serves)", _bare(AssociateSpec)),
+    "score": _Option(
+        ScoreSpec, (TimedScoreSpec,),
+        "time= together with score= is not supported: the score records are indexed by push, and re-indexing them by "
+        "time is a change of its own (DESIGN.md 8); the records indexed by time are score=TimedScoreSpec(...) (DESIGN.md "
+        "5.25)",
+        "score=%s(...) needs time=TimeRule(...): its records are indexed by time (without time= the push-indexed "
+        "ScoreSpec serves)", lambda x: ScoreSpec(*x)),
+}
+
+_Feed = collections.namedtuple("_Feed", "lead det when pushed n_out tail rings")
+_Feed.__doc__ = """What differs between one stream and many, as a predictor hands it to its stages: lead, the leading axis
+of every state tensor (() or (NS,)); det, the staging buffers as pointers by the names ops.score_push takes them, in the
+order the push and association kernels do; when, the pointer to the push time(s) (read under time= only); pushed, the
+(NS,) int32 `pushed` words (None: one stream, always pushed); n_out, how many of _outs() the push kernel writes (`seen`
+apart); tail, the push kernel's arguments behind its outputs; rings, whether reset() clears the position rings too."""
+_I32, _I64, _F64 = torch.int32, torch.int64, torch.float64
+
+
+def _makers(dev, lead):
+    """(zeros, empty): (dtype, *shape) -> a device tensor of lead + shape, one set per stream."""
+    return tuple(lambda dtype, *shape, make=make: make(lead + shape, device=dev, dtype=dtype)
+                 for make in (torch.zeros, torch.empty))
+
+
+class _Stage:
+    """One launch around the model in a live push, built once, behind the predictor's staging buffers.  A stage owns its
+    device tensors (`named`: by the names the predictor shows them under; `state`: the same in the ABI's order), says what
+    a reset fills (`cleared`, (tensor, value) pairs) and what an empty push moves (`moved`), resolves its entry point --
+    the lone or the _streams one, in its push-indexed or its timed form -- with every argument that stays the same from
+    push to push, and has ONE launch, which takes what varies."""
+
+    def _own(self, named, fill, kept=(), also=()):
+        """`named` is the state: a reset fills it with 0, and with fill[name] where that is given, but for the names in
+        `kept`; an empty push moves all of it, and `also`."""
+        self.named, self.state = named, tuple(named.values())
+        self.moved = self.state + also
+        self.cleared = [(x, fill.get(n, 0)) for n, x in named.items() if n not in kept]
+
+    def _bind(self, base, feed, form, *args):
+        """The entry point of the family `base` that serves this feed (many streams: the _streams one) in this form ("",
+        or the suffix of a twin), and its fixed arguments."""
+        self.name = base + ("_streams" if feed.lead else "") + form
+        self.entry, self.args = getattr(lib(), self.name), args
+
+    def launch(self, outs):
+        check(self.entry(*self.args, stream_ptr()), self.name)
+
+
+class _Tracks(_Stage):
+    """The push kernel and the track state: slot ids, presence masks, the position ring and {head, flags}; with time=
+    the sample rings (times, positions), their {write index, count} and the clock in the place of masks and ring."""
+
+    def __init__(self, p, feed):
+        zeros, empty = _makers(p.device, feed.lead)
+        rule = () if p.rule is None else tuple(p.rule)
+        named = dict(slot_id=empty(_I64, p.s))
+        if p.time is None:
+            # the strict kernel, or its *_rule twin with the rule ahead of the outputs and `seen` behind them
+            named.update(mask=empty(_I32, p.s), ring=zeros(_F64, p.t_obs, p.s, 2))
+            form, rings, when = "_rule" if rule else "", ("ring",), ()   # (a ring row is read only where the mask says so)
+            sizes = (p.s, p.t_obs, ctypes.c_double(p.scale), p.v)
+        else:
+            # the timed twin: the time(s) behind the detections, R behind S, (step, max_dt) ahead of the rule
+            r = p.time.history
+            named.update(t_ring=zeros(_I64, p.s, r), xy_ring=zeros(_F64, p.s, r, 2), slot_head=empty(_I32, p.s, 2),
+                         clock=empty(_I64, 2))
+            form, rings, when = "_timed", ("t_ring", "xy_ring"), (feed.when,)    # (a ring holds what its count says)
+            sizes = (p.s, r, p.t_obs, ctypes.c_double(p.scale), p.v, p.time.step, p.time.max_dt)
+        named["head_flags"] = empty(_I32, 2)
+        self._own(named, {"slot_id": -1}, kept=() if feed.rings else rings)
+        self._bind("stg_track_push", feed, form, *feed.det.values(), *when, *feed.lead, p.m_max, *map(ptr, self.state),
+                   *sizes, *rule)
+        # of _outs() the kernel writes the first n_out and, under a rule, `seen`, the last
+        self.feed, self.seen = feed, slice(-1, None) if rule else slice(0, 0)
+
+    def launch(self, outs):
+        """staging buffers + track state -> outs"""
+        n, pushed = self.feed.n_out, self.feed.pushed
+        check(self.entry(*self.args, *map(ptr, outs[:n] + outs[self.seen]), *self.feed.tail, stream_ptr()), self.name)
+        if pushed is not None:                               # many streams: which of them this tick pushed, as a bool
+            torch.ne(pushed, 0, out=outs[n])
+
+
+class _Association(_Stage):
+    """With associate=: the launch ahead of the push kernel that writes the ids it reads, and the association state: slot
+    ids, positions, velocities, misses (under a TimedAssociateSpec the times of the last match in their place, under a
+    FilteredAssociateSpec also the covariances), hits; per stream next_id and the flags."""
+
+    def __init__(self, p, feed, tracks):
+        spec = p.assoc
+        zeros, empty = _makers(p.device, feed.lead)
+        one = feed.lead or (1,)
+        c = p.s if spec.capacity is None else spec.capacity
+        named = dict(trk_id=empty(_I64, c), trk_pos=zeros(_F64, c, 2), trk_vel=zeros(_F64, c, 2))
+        if isinstance(spec, _TIMED_ASSOC):
+            # the timed twin, or the filtered one: the time(s) the timed push reads and that push's clock go between the
+            # detections and the sizes; the lifetime is (step, max_age) ticks
+            filtered = isinstance(spec, FilteredAssociateSpec)
+            named["trk_t"] = zeros(_I64, c)
+            if filtered:
+                named["trk_cov"] = zeros(_F64, c, 3)
+            form, when = "_filtered" if filtered else "_timed", (feed.when, ptr(tracks.named["clock"]))
+            squared, life = spec[:5] if filtered else (spec.gate, spec.gate_new), (p.time.step, spec.max_age)
+        else:
+            named["trk_miss"] = zeros(_I32, c)
+            form, when, squared, life = "", (), (spec.gate, spec.gate_new), (spec.max_miss,)
+        named.update(trk_hits=zeros(_I32, c), next_id=torch.zeros(one, device=p.device, dtype=_I64),
+                     assoc_flags=torch.zeros(one, device=p.device, dtype=_I32))
+        self._own(named, {"trk_id": -1})                     # (an empty push ages the association's tracks too)
+        # (the gates, or the filter's five parameters, travel squared, in float64)
+        self._bind("stg_associate", feed, form, *feed.det.values(), *when, *feed.lead, p.m_max, *map(ptr, self.state), c,
+                   ctypes.c_double(p.scale), *(ctypes.c_double(x * x) for x in squared), *life)
+
+
+class _Harvest(_Stage):
+    """With harvest=: the launch behind the push kernel, which reads the state the push has left, the harvest's own
+    history, one per stream -- presence words, a T_all-deep position ring, {ring row, pushes since reset}; under a
+    TimedHarvestSpec the grid {anchored, g0, instants skipped} behind them --, the ONE log of the predictor and, for many
+    streams, the launches' scratch."""
+
+    def __init__(self, p, feed, tracks):
+        spec = p.harvest_spec
+        zeros, _ = _makers(p.device, feed.lead)
+        log = LiveWindows(spec, p.t_obs, p.device)
+        named = dict(h_word=zeros(_I32, p.s), h_ring=zeros(_F64, log.t_all, p.s, 2), h_head=zeros(_I32, 2))
+        if p.time is None:
+            form, sizes = "", (p.s, p.t_obs, log.t_all, spec.min_peds)
+        else:
+            # the timed twin: R behind S, (scale, step, max_dt, settle) behind the sizes, h_clock behind the history
+            named["h_clock"] = zeros(_I64, 3)
+            form, sizes = "_timed", (p.s, p.time.history, p.t_obs, log.t_all, spec.min_peds, ctypes.c_double(p.scale),
+                                     p.time.step, p.time.max_dt, spec.settle)
+        # A reset leaves the log alone, and the ring: a ring row is read only where the word says detected.  An empty push
+        # ages the words and moves the ring row; it has no candidates, so of the log only the header is kept (its rows,
+        # offsets and tags are written for a window alone).
+        self._own(named, {}, kept=("h_ring",), also=(log.header,))
+        self.named = dict(named, harvest=log)
+        if feed.lead:                                        # a _streams entry point is told of its streams; its scratch
+            self.work = torch.zeros(feed.lead[0] * (p.s + 3), device=p.device, dtype=_I32)
+            streams, tag, work = (ptr(feed.pushed), *feed.lead), (), (ptr(self.work),)
+        else:                                                # the lone one tags its windows with a stream index
+            streams, tag, work = (), (0,), ()
+        self._bind("stg_window_harvest", feed, form, *map(ptr, tracks.state), *streams, *sizes, *tag,
+                   *map(ptr, self.state), *work, *log._args())
+
+
+class _Score:
+    """With score=: the launch behind the sampler (and the risk counts) -- the pending predictions against this push's
+    detections, then this push's prediction into the records (ops.score_push); with a TimedScoreSpec against the track
+    samples the timed push has just recorded (ops.score_timed_push) -- and the records and totals, which it shows as a
+    _Stage shows its tensors.  Its launch also takes the prediction."""
+    named = {}
+
+    def __init__(self, p, feed, tracks):
+        spec, dev = p.score_spec, p.device
+        ns, n_pred, q = (feed.lead or (1,))[0], p.model.pred_seq_len, len(spec.levels)
+        thr = torch.tensor(spec.thresholds, dtype=torch.float32).to(dev) if q else None
+        if isinstance(spec, TimedScoreSpec):
+            self.state = ops.score_timed_state(ns, n_pred, p.v, p.k, spec.pending, dev, spec.best_of_k, q)
+            self.fresh = lambda: ops.score_timed_buffers(ns, n_pred, q, dev)
+            self.push = functools.partial(ops.score_timed_push, self.state, thr, tracks=tracks.state, step=p.time.step,
+                                          max_dt=p.time.max_dt, scale=p.scale, pushed=feed.pushed)
+        else:
+            self.state = ops.score_state(ns, n_pred, p.v, p.k, dev, spec.best_of_k, q)
+            self.fresh = lambda: ops.score_buffers(ns, n_pred, p.v, dev, spec.best_of_k)
+            self.push = functools.partial(ops.score_push, self.state, thr, m_max=p.m_max, scale=p.scale, **feed.det)
+        self.cleared = [(x, -1 if n == "rec_ids" else 0) for n, x in zip(self.state._fields, self.state) if x is not None]
+        self.moved = tuple(x for x, _ in self.cleared)       # an empty push is a push: it scores and enqueues
+        self.ids_shape, self.samples = (ns, p.v), spec.best_of_k
+
+    def launch(self, outs, r, out=None):
+        """Score the chain's Prediction r of the push that wrote outs; `out`: an earlier result to fill (capture)."""
+        return self.push(r.mean, r.v_pred, r.samples if self.samples else None, outs[1].view(self.ids_shape), outs[2],
+                         out=out)
+
+
 class _LivePredictor:
-    """What FramePredictor and StreamsPredictor share: the argument checks, the track state on the device (with the
-    subclass's leading axis), the eager push and its capture as ONE graph.  A subclass supplies
+    """What FramePredictor and StreamsPredictor share: the argument checks, the stages on the device (with the
+    subclass's leading axis), the eager push and its capture as ONE graph.  The core holds the stages in launch order
+    (_build) and shows their tensors under their names; push, capture, reset and the warm-up loop over them.  A subclass
+    builds its staging buffers, hands the stages its _Feed and supplies
 
         _stage(*det, seed)       copy one push's detections (and the seed, unless None) into its device staging buffers;
                                  with time= it takes the push's time(s) by keyword and stages them with the detections
         _outs()                  fresh per-push outputs (obs_abs, ids, num_peds, ...; under a TrackRule `seen` last)
-        _push(outs)              launch its push kernel: staging buffers + track state -> outs
-        _det                     its staging buffers by the names ops.score_push takes them, in the order its push
-                                 kernel does: _push and the score launch read the same ones
         _wrap(outs, r, static)   the result tuple of outs and the chain's Prediction r (static: a captured push)
         _still()                 make warm-up pushes harmless; returns the (tensor, saved copy) pairs to put back after
-        _associate()             with associate=: launch its association kernel on the staging buffers, ahead of _push
-        _harvest()               with harvest=: launch its window harvest on the track state, behind _push
 
     and `seed_dev`, the (1,) int64 device tensor the sampler reads its seed from."""
     assoc = None                         # the AssociateSpec, TimedAssociateSpec or FilteredAssociateSpec; None: ids come
                                          # with the pushes
-    _score_pushed = None                 # the (NS,) int32 `pushed` words a timed score launch reads; None: one stream
-
     harvest = None                       # the LiveWindows of a predictor made with harvest=; None without
     h_clock = None                       # with harvest=TimedHarvestSpec: {anchored, g0, instants skipped} per stream
 
@@ -602,36 +803,23 @@ class _LivePredictor:
                  tracks=None, score=None, time=None, associate=None, harvest=None, calibration=None):
         self.model = model
         self.k = int(k)
-        timed_harvest = isinstance(harvest, TimedHarvestSpec)
-        if harvest is not None and time is not None and not timed_harvest:
-            raise ValueError("harvest= together with time= is not supported: a timed push is not one frame of a "
-                             "window (DESIGN.md 8)")
-        if timed_harvest and time is None:
-            raise ValueError("harvest=TimedHarvestSpec(...) needs time=TimeRule(...): its frames are instants of the "
-                             "step grid (without time= the push-indexed HarvestSpec serves)")
-        timed_assoc = isinstance(associate, _TIMED_ASSOC)
-        if timed_assoc and time is None:
-            raise ValueError("associate=%s(...) needs time=TimeRule(...): its tracks are aged by time "
-                             "(without time= the push-indexed AssociateSpec serves)" % type(associate).__name__)
-        if associate is not None and time is not None and not timed_assoc:
-            raise ValueError("associate= together with time= is not supported: a velocity per tick and a gate that "
-                             "grows with the gap are a change of their own (DESIGN.md 8)")
-        if associate is not None and not isinstance(associate, (AssociateSpec,) + _TIMED_ASSOC):
-            associate = AssociateSpec(*associate) if isinstance(associate, (tuple, list)) else AssociateSpec(associate)
-        self.assoc = associate
-        self._assoc_state = None
+        given = dict(harvest=harvest, associate=associate, score=score)
+        for name, opt in _OPTIONS.items():
+            spec = given[name]
+            if spec is None:
+                continue
+            if isinstance(spec, opt.timed):
+                if time is None:
+                    raise ValueError(opt.without_time % type(spec).__name__)
+            elif time is not None:
+                raise ValueError(opt.with_time)
+            elif not isinstance(spec, opt.plain) and name != "harvest":
+                # (a bare harvest= is coerced below, where it is checked: what it refuses comes behind every other refusal)
+                given[name] = opt.coerce(spec)
+        self.assoc, score = given["associate"], given["score"]
         self._n_det = 0
-        timed_score = isinstance(score, TimedScoreSpec)
-        if time is not None and score is not None and not timed_score:
-            raise ValueError("time= together with score= is not supported: the score records are indexed by push, and "
-                             "re-indexing them by time is a change of its own (DESIGN.md 8); the records indexed by "
-                             "time are score=TimedScoreSpec(...) (DESIGN.md 5.25)")
-        if timed_score and time is None:
-            raise ValueError("score=TimedScoreSpec(...) needs time=TimeRule(...): its records are indexed by time "
-                             "(without time= the push-indexed ScoreSpec serves)")
         self._risk_args = (risk, keep_samples, calibration)
         if score is not None:
-            score = score if isinstance(score, (ScoreSpec, TimedScoreSpec)) else ScoreSpec(*score)
             if score.best_of_k and not keep_samples:
                 raise ValueError("score: ScoreSpec(best_of_k=True) scores the K samples, and keep_samples=False leaves "
                                  "none (pass ScoreSpec(best_of_k=False) or keep the samples)")
@@ -645,7 +833,6 @@ class _LivePredictor:
                                  % (model.pred_seq_len, ops.SCORE_MAX_P))
         self.score_spec = score
         self.score = None
-        self._score_state = None
         self.t_obs = _obs_len(obs_len)
         if self.t_obs != model.seq_len:
             raise ValueError("obs_len=%d but the model observes %d frames" % (self.t_obs, model.seq_len))
@@ -664,94 +851,34 @@ class _LivePredictor:
             raise ValueError("max_detections must be in [1, %d], got %r" % (MAX_DETECTIONS, max_detections))
         if self.v < 1:
             raise ValueError("max_peds must be >= 1, got %r" % (max_peds,))
-        if timed_harvest:
-            harvest = harvest.checked(self.t_obs, self.v, model.pred_seq_len, self.time.max_dt)
-        elif harvest is not None:
-            if not isinstance(harvest, HarvestSpec):
-                harvest = HarvestSpec(*harvest) if isinstance(harvest, (tuple, list)) else HarvestSpec(harvest)
-            harvest = harvest.checked(self.t_obs, self.v, model.pred_seq_len)
+        if harvest is not None:
+            if not isinstance(harvest, (HarvestSpec, TimedHarvestSpec)):
+                harvest = _OPTIONS["harvest"].coerce(harvest)
+            # (the spec that goes with time= also fits its settle to the rule's max_dt)
+            harvest = harvest.checked(self.t_obs, self.v, model.pred_seq_len,
+                                      *(() if self.time is None else (self.time.max_dt,)))
         self.harvest_spec = harvest
-        self._harvest_state = None
 
-    def _track_state(self, lead=()):
-        """Look the model's device up (every argument has been checked by now) and allocate the track state, one set
-        per index of `lead`: slot ids, presence masks, the position ring and {head, flags}; with time= the sample
-        rings (times, positions), their {write index, count} and the clock in the place of masks and ring."""
-        dev = next(self.model.parameters()).device
+    def _device(self):
+        """Look the model's device up: every argument has been checked by now."""
+        self.device = next(self.model.parameters()).device
         require_gpu(next(self.model.parameters()))
-        self.device = dev
-        self.slot_id = torch.empty(lead + (self.s,), device=dev, dtype=torch.int64)
-        self.head_flags = torch.empty(lead + (2,), device=dev, dtype=torch.int32)
-        if self.time is None:
-            self.mask = torch.empty(lead + (self.s,), device=dev, dtype=torch.int32)
-            self.ring = torch.zeros(lead + (self.t_obs, self.s, 2), device=dev, dtype=torch.float64)
-            self._state = (self.slot_id, self.mask, self.ring, self.head_flags)
-            self._forget = (self.mask, self.head_flags)      # (a ring row is read only where the mask says seen)
-        else:
-            r = self.time.history
-            self.t_ring = torch.zeros(lead + (self.s, r), device=dev, dtype=torch.int64)
-            self.xy_ring = torch.zeros(lead + (self.s, r, 2), device=dev, dtype=torch.float64)
-            self.slot_head = torch.empty(lead + (self.s, 2), device=dev, dtype=torch.int32)
-            self.clock = torch.empty(lead + (2,), device=dev, dtype=torch.int64)
-            self._state = (self.slot_id, self.t_ring, self.xy_ring, self.slot_head, self.clock, self.head_flags)
-            self._forget = (self.slot_head, self.clock, self.head_flags)     # (a ring holds what its count says)
-        if self.assoc is not None:
-            # the association state: slot ids, positions, velocities, misses (under a TimedAssociateSpec the times of
-            # the last match in their place, under a FilteredAssociateSpec also the covariances), hits; per stream
-            # next_id and the flags
-            c = self.s if self.assoc.capacity is None else self.assoc.capacity
-            one = lead or (1,)
-            timed = isinstance(self.assoc, _TIMED_ASSOC)
-            filtered = isinstance(self.assoc, FilteredAssociateSpec)
-            self.trk_id = torch.empty(lead + (c,), device=dev, dtype=torch.int64)
-            self.trk_pos = torch.zeros(lead + (c, 2), device=dev, dtype=torch.float64)
-            self.trk_vel = torch.zeros(lead + (c, 2), device=dev, dtype=torch.float64)
-            if timed:
-                self.trk_t = torch.zeros(lead + (c,), device=dev, dtype=torch.int64)
-            else:
-                self.trk_miss = torch.zeros(lead + (c,), device=dev, dtype=torch.int32)
-            self.trk_hits = torch.zeros(lead + (c,), device=dev, dtype=torch.int32)
-            self.next_id = torch.zeros(one, device=dev, dtype=torch.int64)
-            self.assoc_flags = torch.zeros(one, device=dev, dtype=torch.int32)
-            if filtered:
-                self.trk_cov = torch.zeros(lead + (c, 3), device=dev, dtype=torch.float64)
-            self._assoc_state = (self.trk_id, self.trk_pos, self.trk_vel, self.trk_t if timed else self.trk_miss,
-                                 *((self.trk_cov,) if filtered else ()), self.trk_hits, self.next_id, self.assoc_flags)
-            # (the gates, or the filter's five parameters, travel squared, in float64; the lifetime as max_miss pushes,
-            # or as (step, max_age) ticks)
-            squared = self.assoc[:5] if filtered else (self.assoc.gate, self.assoc.gate_new)
-            self._assoc_args = (c, ctypes.c_double(self.scale), *(ctypes.c_double(x * x) for x in squared),
-                                *((self.time.step, self.assoc.max_age) if timed else (self.assoc.max_miss,)))
+        return self.device
+
+    def _build(self, feed):
+        """Build the chain and the stages on the subclass's staging buffers (`feed`); show the stages' tensors by name."""
         self._pred = Predictor(self.model, self.k, *self._risk_args)
-        if self.score_spec is not None:
-            # which of the two score families this predictor holds is decided here, once: its state, the fresh outputs
-            # of a launch (graph capture) and the launch itself, behind the prediction's five tensors
-            spec, ns, p, q = self.score_spec, lead[0] if lead else 1, self.model.pred_seq_len, len(self.score_spec.levels)
-            self._thr = torch.tensor(spec.thresholds, dtype=torch.float32).to(dev) if q else None
-            if isinstance(spec, TimedScoreSpec):
-                self._score_state = ops.score_timed_state(ns, p, self.v, self.k, spec.pending, dev, spec.best_of_k, q)
-                self._score_buffers = lambda: ops.score_timed_buffers(ns, p, q, dev)
-                self._score_launch = lambda *pred, out: ops.score_timed_push(
-                    self._score_state, self._thr, *pred, self._state, self.time.step, self.time.max_dt, self.scale,
-                    pushed=self._score_pushed, out=out)
-            else:
-                self._score_state = ops.score_state(ns, p, self.v, self.k, dev, spec.best_of_k, q)
-                self._score_buffers = lambda: ops.score_buffers(ns, p, self.v, dev, spec.best_of_k)
-                self._score_launch = lambda *pred, out: ops.score_push(
-                    self._score_state, self._thr, *pred, out=out, m_max=self.m_max, scale=self.scale, **self._det)
-        if self.harvest_spec is not None:
-            # the harvest's own history, one per index of `lead` -- presence words, a T_all-deep position ring, {ring row,
-            # pushes since reset} --, the ONE log of the predictor and, for many streams, the launches' scratch
-            self.harvest = LiveWindows(self.harvest_spec, self.t_obs, dev)
-            self.h_word = torch.zeros(lead + (self.s,), device=dev, dtype=torch.int32)
-            self.h_ring = torch.zeros(lead + (self.harvest.t_all, self.s, 2), device=dev, dtype=torch.float64)
-            self.h_head = torch.zeros(lead + (2,), device=dev, dtype=torch.int32)
-            self._harvest_state = (self.h_word, self.h_ring, self.h_head)
-            if self.time is not None:                        # the grid of the timed harvest, behind the history
-                self.h_clock = torch.zeros(lead + (3,), device=dev, dtype=torch.int64)
-                self._harvest_state += (self.h_clock,)
-            self._harvest_work = torch.zeros(lead[0] * (self.s + 3), device=dev, dtype=torch.int32) if lead else None
-        return dev
+        tracks = _Tracks(self, feed)
+        # THE order of the launches of a push: association -> tracks -> harvest, then the chain, then the score
+        ahead = () if self.assoc is None else (_Association(self, feed, tracks),)
+        behind = () if self.harvest_spec is None else (_Harvest(self, feed, tracks),)
+        self._scorer = None if self.score_spec is None else _Score(self, feed, tracks)
+        self._front_stages = ahead + (tracks,) + behind
+        self._stages = self._front_stages + (() if self._scorer is None else (self._scorer,))
+        of = {type(st): st.state for st in self._stages}
+        self._state, self._assoc_state, self._score_state = (of.get(kind) for kind in (_Tracks, _Association, _Score))
+        for st in self._stages:
+            vars(self).update(st.named)
 
     @property
     def score_totals(self):
@@ -762,45 +889,17 @@ class _LivePredictor:
         return None if st is None else (st.totals, st.traj_totals)
 
     @property
-    def _timed_score(self):
-        return isinstance(self.score_spec, TimedScoreSpec)
-
-    @property
     def score_records(self):
         """With score=TimedScoreSpec(...): the record ring on the device, the ops.ScoreTimedState itself (NS = 1 for a
         FramePredictor) -- rec_t, rec_status, rec_peds, rec_ids, the tables matched / err / d2 / nll / best (NS,Rp,P,V)
         and the retired rows traj_* (NS,Rp,V); reading it is the caller's synchronisation.  None otherwise."""
-        return self._score_state if self._timed_score else None
+        return self._score_state if isinstance(self._score_state, ops.ScoreTimedState) else None
 
     @property
     def score_evictions(self):
         """With score=TimedScoreSpec(...): (NS,) int64 on the device, the records overwritten while still pending since
         reset() (size `pending` to the feed: predict.TimedScoreSpec).  None otherwise."""
-        return self._score_state.counters[:, 1] if self._timed_score else None
-
-    def _score_reset(self, at=None):
-        if self._score_state is not None:
-            ops.score_reset(self._score_state, at)
-
-    def _score_push(self, outs, r, out=None):
-        """The score launch of one push, behind the sampler (and the risk counts): the pending predictions against this
-        push's detections, then this push's prediction into the records (ops.score_push); with a TimedScoreSpec against
-        the track samples the timed push has just recorded (ops.score_timed_push)."""
-        # (_score_launch and _score_buffers exist only with a score spec: _track_state sets them beside the state)
-        ns = self._score_state.totals.shape[0]
-        return self._score_launch(r.mean, r.v_pred, r.samples if self.score_spec.best_of_k else None,
-                                  outs[1].view(ns, self.v), outs[2], out=out)
-
-    def _reset_assoc(self, at=None):
-        """Forget the association's tracks and start its ids at 0 again: everywhere, or at the stream indices `at`."""
-        if self._assoc_state is None:
-            return
-        for x in self._assoc_state:
-            fill = -1 if x is self.trk_id else 0
-            if at is None:
-                x.fill_(fill)
-            else:
-                x.index_fill_(0, at, fill)
+        return None if self.score_records is None else self._score_state.counters[:, 1]
 
     def assoc_tracks(self, host=False):
         """With associate=: the association's live tracks, (ids (n,) int64, pos (n,2) float64, vel (n,2) float64) in slot
@@ -819,16 +918,6 @@ class _LivePredictor:
             return one(self.trk_id, self.trk_pos, self.trk_vel)
         return [one(self.trk_id[b], self.trk_pos[b], self.trk_vel[b]) for b in range(self.trk_id.shape[0])]
 
-    def _launch_associate(self, name, det, when, sizes):
-        """The association kernel `name` on the detections `det` (its leading arguments), the sizes behind them and the
-        association state: it writes the ids the push kernel behind it reads.  Under a TimedAssociateSpec the timed twin,
-        under a FilteredAssociateSpec the filtered one: `when`, the time(s) the timed push reads, and that push's clock
-        go between the detections and the sizes."""
-        if isinstance(self.assoc, _TIMED_ASSOC):
-            name += "_filtered" if isinstance(self.assoc, FilteredAssociateSpec) else "_timed"
-            det += (when, ptr(self.clock))
-        check(getattr(lib(), name)(*det, *sizes, *map(ptr, self._assoc_state), *self._assoc_args, stream_ptr()), name)
-
     @property
     def harvest_clock(self):
         """With harvest=TimedHarvestSpec(...): (NS,3) int64 on the device (NS = 1 for a FramePredictor), per stream
@@ -836,60 +925,21 @@ class _LivePredictor:
         i * step; reading it is the caller's synchronisation.  None otherwise."""
         return None if self.h_clock is None else self.h_clock.view(-1, 3)
 
-    def _reset_harvest(self, at=None):
-        """Empty the harvest history everywhere, or at the stream indices `at`; the log is left alone.  (A ring row is
-        read only where the word says detected.)"""
-        if self._harvest_state is None:
-            return
-        for x in (self.h_word, self.h_head) + (() if self.h_clock is None else (self.h_clock,)):
-            if at is None:
-                x.zero_()
-            else:
-                x.index_fill_(0, at, 0)
-
-    def _launch_harvest(self, name, streams, tag, work):
-        """The harvest entry point `name` behind the push: the track state (read only), `streams` (what a _streams
-        entry point is told of its streams), the sizes, `tag` (the lone entry point's stream index), the history, `work`
-        (the _streams entry point's scratch) and the log."""
-        h = self.harvest
-        if self.time is not None:
-            # the timed twin: the sample rings as the state, R behind S, (scale, step, max_dt, settle) behind the sizes,
-            # h_clock behind the history
-            name += "_timed"
-            check(getattr(lib(), name)(*map(ptr, self._state), *streams, self.s, self.time.history, self.t_obs, h.t_all,
-                                       self.harvest_spec.min_peds, ctypes.c_double(self.scale), self.time.step,
-                                       self.time.max_dt, self.harvest_spec.settle, *tag,
-                                       *map(ptr, self._harvest_state), *work, *h._args(), stream_ptr()), name)
-            return
-        check(getattr(lib(), name)(*map(ptr, self._state), *streams, self.s, self.t_obs, h.t_all,
-                                   self.harvest_spec.min_peds, *tag, *map(ptr, self._harvest_state), *work, *h._args(),
-                                   stream_ptr()), name)
-
     def _front(self, outs):
         """The launches that turn the staged detections into the scene: with associate= the association, then the push;
         with harvest= the window harvest behind it, which reads the state the push has left."""
-        if self.assoc is not None:
-            self._associate()
-        self._push(outs)
-        if self.harvest_spec is not None:
-            self._harvest()
+        for st in self._front_stages:
+            st.launch(outs)
 
-    def _launch_push(self, name, det, outs, n_out, *tail):
-        """The push kernel `name` on the detections `det` (its leading arguments) and the track state, or under a
-        TrackRule its *_rule twin: the rule goes ahead of the kernel's n_out outputs, `seen` (the last of outs) behind."""
-        rule, seen = ((), ()) if self.rule is None else (tuple(self.rule), (ptr(outs[-1]),))
-        if self.time is not None:
-            # the timed twin: the time(s) behind the detections, the sample rings as the state, (step, max_dt) ahead
-            # of the rule
-            name += "_timed"
-            check(getattr(lib(), name)(*det, *map(ptr, self._state), self.s, self.time.history, self.t_obs,
-                                       ctypes.c_double(self.scale), self.v, self.time.step, self.time.max_dt, *rule,
-                                       *map(ptr, outs[:n_out]), *seen, *tail, stream_ptr()), name)
-            return
-        name += "_rule" if rule else ""
-        check(getattr(lib(), name)(*det, ptr(self.slot_id), ptr(self.mask), ptr(self.ring), ptr(self.head_flags), self.s,
-                                   self.t_obs, ctypes.c_double(self.scale), self.v, *rule, *map(ptr, outs[:n_out]),
-                                   *seen, *tail, stream_ptr()), name)
+    def _clear(self, at=None):
+        """Fill what every stage says a reset fills -- the tracks forgotten, the association's ids from 0 again, the
+        score's records and totals and the harvest history emptied: everywhere, or at the stream indices `at`."""
+        for st in self._stages:
+            for x, fill in st.cleared:
+                if at is None:
+                    x.fill_(fill)
+                else:
+                    x.index_fill_(0, at, fill)
 
     @property
     def risk(self):
@@ -920,8 +970,8 @@ class _LivePredictor:
             self.seen = outs[-1]
         with eval_mode(self.model):
             r = self._pred._forward(outs[0], outs[2], 0, noise, self.seed_dev)
-        if self.score_spec is not None:
-            self.score = self._score_push(outs, r)
+        if self._scorer is not None:
+            self.score = self._scorer.launch(outs, r)
         return self._wrap(outs, r, False)
 
     @torch.no_grad()
@@ -933,13 +983,11 @@ class _LivePredictor:
         history and the harvested windows."""
         outs = self._outs()
         saved = self._still()
-        scored = None
-        if self.score_spec is not None:
-            scored = self._score_buffers()
+        scored = None if self._scorer is None else self._scorer.fresh()
         try:
             graph, r, chain = self._pred.capture_chain(
                 outs[0], outs[2], self.seed_dev, warmup, pre=lambda: self._front(outs),
-                post=None if scored is None else lambda res: self._score_push(outs, res, scored))
+                post=None if scored is None else lambda res: self._scorer.launch(outs, res, scored))
         finally:
             for x, x0 in saved:
                 x.copy_(x0)
@@ -1011,38 +1059,28 @@ class FramePredictor(_LivePredictor):
                  calibration=None):
         super().__init__(model, k, obs_len, capacity, max_peds, max_detections, decimals, risk, keep_samples, tracks,
                          score, time, associate, harvest, calibration)
-        dev, m = self._track_state(), self.m_max
+        dev, m = self._device(), self.m_max
         self.det_id = torch.zeros(m, device=dev, dtype=torch.int64)
         self.det_xy = torch.zeros((m, 2), device=dev, dtype=torch.float64)
         self.det_count = torch.zeros(1, device=dev, dtype=torch.int32)
         self.det_time = torch.zeros(1, device=dev, dtype=torch.int64)
         self.seed_dev = torch.zeros(1, device=dev, dtype=torch.int64)
-        self._det = dict(det_id=ptr(self.det_id), det_xy=ptr(self.det_xy), det_count=ptr(self.det_count))
+        self._build(_Feed(lead=(), det=dict(det_id=ptr(self.det_id), det_xy=ptr(self.det_xy),
+                                            det_count=ptr(self.det_count)),
+                          when=ptr(self.det_time), pushed=None, n_out=3, tail=(), rings=False))
         self.reset()
 
     def reset(self):
         """Forget every track (the next obs_len - 1 pushes return empty scenes), with associate= the association's
         tracks and ids with them (under time= together with the clock), and with score= the pending records and the
-        running totals; with harvest= the harvest history, not the log."""
-        self.slot_id.fill_(-1)
-        for x in self._forget:
-            x.zero_()
-        self._reset_assoc()
-        self._score_reset()
-        self._reset_harvest()
+        running totals; with harvest= the harvest history, not the log.  The position rings keep what they hold."""
+        self._clear()
 
     @property
     def det_ids(self):
         """With associate=: the track id given to every detection of the last push, (M,) int64 on the device in the
         caller's detection order (a view of the staging buffer, overwritten by the next push)."""
         return None if self.assoc is None else self.det_id[:self._n_det]
-
-    def _associate(self):
-        self._launch_associate("stg_associate", (ptr(self.det_id), ptr(self.det_xy), ptr(self.det_count)),
-                               ptr(self.det_time), (self.m_max,))
-
-    def _harvest(self):
-        self._launch_harvest("stg_window_harvest", (), (0,), ())
 
     def _stage(self, ids, xy, seed, t=None):
         """Copy one frame of detections (host arrays or device tensors) into the device buffers the push reads, and
@@ -1091,10 +1129,6 @@ class FramePredictor(_LivePredictor):
                 torch.empty(v, device=dev, dtype=torch.int64),
                 torch.empty(1, device=dev, dtype=torch.int32)) + self._seen_out(v)
 
-    def _push(self, outs):
-        when = () if self.time is None else (ptr(self.det_time),)
-        self._launch_push("stg_track_push", (*self._det.values(), *when, self.m_max), outs, 3)
-
     def _wrap(self, outs, r, static):
         obs, ids, peds = outs[:3]
         flags = self.head_flags[1:]          # (a captured push returns the state's own flags word)
@@ -1102,18 +1136,9 @@ class FramePredictor(_LivePredictor):
                                flags if static else flags.clone())
 
     def _still(self):
-        """The warm-up pushes frames without detections, which age the tracks (with time=: move the clock): the state
-        goes back after it."""
-        state = self._state + (self.det_count,)
-        if self._assoc_state is not None:                    # an empty push ages the association's tracks too
-            state += self._assoc_state
-        if self._score_state is not None:                    # an empty push is a push: it scores and enqueues
-            state += tuple(x for x in self._score_state if x is not None)
-        if self._harvest_state is not None:
-            # an empty push ages the harvest words and moves its ring row; it has no candidates, so of the log only the
-            # header is kept (its rows, offsets and tags are written for a window alone)
-            state += self._harvest_state + (self.harvest.header,)
-        saved = [(x, x.clone()) for x in state]
+        """The warm-up pushes frames without detections, which age the tracks (with time=: move the clock): what every
+        stage says an empty push moves goes back after it."""
+        saved = [(x, x.clone()) for x in (self.det_count, *(x for st in self._stages for x in st.moved))]
         self.det_count.zero_()
         return saved
 
@@ -1148,8 +1173,7 @@ def pack_tick(tick, streams, max_detections, max_total_detections, associate=Fal
     if isinstance(tick, collections.abc.Mapping):
         entries = []
         for key, det in tick.items():
-            if isinstance(key, (bool, np.bool_)) or not isinstance(key, (int, np.integer)) or not 0 <= key < streams:
-                raise ValueError("tick: stream index %r not in [0, %d)" % (key, streams))
+            _stream_index(key, streams, "tick")
             if det is not None:
                 entries.append((int(key), det))
         entries.sort(key=lambda e: e[0])
@@ -1271,7 +1295,7 @@ class StreamsPredictor(_LivePredictor):
             raise ValueError("block_threads must be 0 (default), 64, 256 or 1024, got %r" % (block_threads,))
         self.block_threads = int(block_threads)
         ns = self.ns
-        dev = self._track_state((ns,))
+        dev = self._device()
         # staging, the same byte layout on the host (pinned) and on the device: det_start (NS+1) int32 | pushed (NS)
         # int32 | seed int64 | cap records (id int64, x, y float64).  A tick copies the header and its M records.
         # With time= the header also holds the streams' push times, (NS) int64 behind the seed.
@@ -1296,9 +1320,10 @@ class StreamsPredictor(_LivePredictor):
         self._rec_i = self._dev[self._hdr:].view(torch.int64).view(self.cap, 3)
         self._rec_f = self._dev[self._hdr:].view(torch.float64).view(self.cap, 3)
         # a record is (id, x, y): ids at stride 3 from its start, positions at stride 3 from 8 bytes in
-        self._det = dict(det_id=ptr(self._rec_i), id_stride=3, det_xy=ctypes.c_void_p(self._rec_f.data_ptr() + 8),
-                         xy_stride=3, m_total=self.cap, det_start=ptr(self.det_start), pushed=ptr(self.pushed_dev))
-        self._score_pushed = self.pushed_dev
+        det = dict(det_id=ptr(self._rec_i), id_stride=3, det_xy=ctypes.c_void_p(self._rec_f.data_ptr() + 8),
+                   xy_stride=3, m_total=self.cap, det_start=ptr(self.det_start), pushed=ptr(self.pushed_dev))
+        self._build(_Feed(lead=(ns,), det=det, when=None if self.time is None else ptr(self.times_dev),
+                          pushed=self.pushed_dev, n_out=4, tail=(self.block_threads,), rings=True))
         self._copied = torch.cuda.Event()
         self._in_flight = False
         self.reset()
@@ -1306,28 +1331,16 @@ class StreamsPredictor(_LivePredictor):
     def reset(self, streams=None):
         """Forget every track of all streams, or of the listed stream indices only (their next obs_len - 1 pushes
         return empty scenes; the other streams go on).  With score= their pending records and running totals are
-        cleared with them; with harvest= their harvest history, not the log."""
+        cleared with them; with harvest= their harvest history, not the log.  The position rings are cleared too."""
         if streams is None:
-            self.slot_id.fill_(-1)
-            for x in self._state[1:]:
-                x.zero_()
-            self._reset_assoc()
-            self._score_reset()
-            self._reset_harvest()
+            self._clear()
             return
         idx = [int(x) for x in (streams if isinstance(streams, (list, tuple, np.ndarray, range)) else [streams])]
         for x in idx:
             if not 0 <= x < self.ns:
                 raise ValueError("reset: stream index %d not in [0, %d)" % (x, self.ns))
-        if not idx:
-            return
-        at = torch.tensor(idx, dtype=torch.int64).to(self.device)
-        self.slot_id.index_fill_(0, at, -1)
-        for x in self._state[1:]:
-            x.index_fill_(0, at, 0)
-        self._reset_assoc(at)
-        self._score_reset(at)
-        self._reset_harvest(at)
+        if idx:
+            self._clear(torch.tensor(idx, dtype=torch.int64).to(self.device))
 
     @property
     def det_ids(self):
@@ -1335,14 +1348,6 @@ class StreamsPredictor(_LivePredictor):
         pushed streams' detections in stream order as the tick listed them (a view of the staging records, overwritten
         by the next tick).  Ids count from 0 in every stream."""
         return None if self.assoc is None else self._rec_i[:self._n_det, 0]
-
-    def _associate(self):
-        self._launch_associate("stg_associate_streams", tuple(self._det.values()),
-                               ptr(self.times_dev) if self.time is not None else None, (self.ns, self.m_max))
-
-    def _harvest(self):
-        self._launch_harvest("stg_window_harvest_streams", (ptr(self.pushed_dev), self.ns), (),
-                             (ptr(self._harvest_work),))
 
     def _wait_host(self):
         """The pinned buffer is rewritten only after the previous tick's copy has left it."""
@@ -1372,8 +1377,7 @@ class StreamsPredictor(_LivePredictor):
             if len(entries) != self.ns:
                 raise ValueError("times: %d entries for %d streams" % (len(entries), self.ns))
         for key, t in entries:
-            if isinstance(key, (bool, np.bool_)) or not isinstance(key, (int, np.integer)) or not 0 <= key < self.ns:
-                raise ValueError("times: stream index %r not in [0, %d)" % (key, self.ns))
+            _stream_index(key, self.ns, "times")
             if t is not None:
                 out[key], have[key] = _tick_time(t, "times: stream %d" % key), True
         missing = np.nonzero((np.asarray(pushed) != 0) & ~have)[0]
@@ -1459,12 +1463,6 @@ class StreamsPredictor(_LivePredictor):
                 torch.empty((ns, v), device=dev, dtype=torch.int64), torch.empty(ns, device=dev, dtype=torch.int32),
                 torch.empty(ns, device=dev, dtype=torch.int32),
                 torch.empty(ns, device=dev, dtype=torch.bool)) + self._seen_out(ns, v)
-
-    def _push(self, outs):
-        when = () if self.time is None else (ptr(self.times_dev),)
-        self._launch_push("stg_track_push_streams", (*self._det.values(), *when, self.ns, self.m_max), outs, 4,
-                          self.block_threads)
-        torch.ne(self.pushed_dev, 0, out=outs[4])
 
     def _wrap(self, outs, r, static):
         obs, ids, peds, flags, pushed = outs[:5]
