@@ -4,14 +4,17 @@ Plumbing only: torch supplies device memory (`tensor.data_ptr()`) and the curren
 every compute call goes to a hand-written HIP kernel.  There is no CPU / eager fallback: if the
 library is missing or a tensor is not on a GPU, the call raises.
 """
+import collections
 import ctypes
 import os
+import re
 import subprocess
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
+INCLUDE = os.path.join(os.path.dirname(_HERE), "include")     # where csrc/Makefile finds the headers: ../../include
 # STG_USE_DIAG_LIB=1 (tools/ only) loads the diagnostic build `make -C csrc DIAG=1` produces; the product
 # library reads no environment variable itself
 DIAG = os.environ.get("STG_USE_DIAG_LIB", "0") not in ("", "0")
@@ -20,11 +23,6 @@ ABI_VERSION = 8
 OPT_WG_PATH, OPT_SPLIT_BF16, OPT_WAVE_PATH, OPT_BF16_STORE, OPT_F32_MFMA, OPT_SEPARATE_FB = 1, 2, 4, 8, 16, 32
 OPT_GENERIC_WGRAD = 64
 EUNSUPPORTED = -2            # STG_EUNSUPPORTED
-
-c_f = ctypes.c_void_p          # device pointers travel as void*
-c_i = ctypes.c_int
-c_l = ctypes.c_int64
-
 
 class ModelDesc(ctypes.Structure):
     """stg_model_desc (include/stgcnn_hip.h)."""
@@ -60,137 +58,116 @@ class ScoreTimedOut(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in ("push_totals", "push_traj")]
 
 
-_SIGNATURES = {
-    "stg_abi_version": (c_i, []),
-    "stg_last_error": (ctypes.c_char_p, []),
-    "stg_adj_build": (c_i, [c_f, c_l, c_l, c_l, c_l, c_f, c_i, c_i, c_i, c_i, c_f, c_f, c_f]),
-    "stg_spatial_agg_fwd": (c_i, [c_f, c_l, c_l, c_l, c_l, c_f, c_l, c_f, c_i, c_i, c_i, c_i, c_f, c_f]),
-    "stg_spatial_agg_bwd": (c_i, [c_f, c_f, c_l, c_f, c_i, c_i, c_i, c_i, c_f, c_f]),
-    "stg_conv_t_fwd": (c_i, [c_f, c_l, c_l, c_l, c_l, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
-    "stg_conv_t_bwd": (c_i, [c_f, c_l, c_l, c_l, c_l, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i,
-                             c_f, c_f, c_f, c_f]),
-    "stg_model_param_count": (c_l, [ctypes.POINTER(ModelDesc)]),
-    "stg_model_buffer_count": (c_l, [ctypes.POINTER(ModelDesc)]),
-    "stg_model_ws_floats": (c_l, [ctypes.POINTER(ModelDesc), c_i]),
-    "stg_model_ws_tail_floats": (c_l, [ctypes.POINTER(ModelDesc), c_i, c_i]),
-    "stg_model_stat_floats": (c_l, [ctypes.POINTER(ModelDesc)]),
-    "stg_model_fwd_scratch_floats": (c_l, [ctypes.POINTER(ModelDesc), c_i, c_i]),
-    "stg_model_bwd_scratch_floats": (c_l, [ctypes.POINTER(ModelDesc), c_i, c_i]),
-    "stg_model_fwd_stamps_offset": (c_l, [ctypes.POINTER(ModelDesc), c_i, c_i]),
-    "stg_model_bwd_stamps_offset": (c_l, [ctypes.POINTER(ModelDesc), c_i, c_i]),
-    "stg_model_fwd": (c_i, [ctypes.POINTER(ModelDesc), c_f, c_f, c_f, c_l, c_l, c_l, c_l, c_f, c_l, c_f, c_i, c_i,
-                            c_f, c_f, c_f, c_f, ctypes.POINTER(ctypes.c_void_p), c_i, c_f]),
-    "stg_model_bwd": (c_i, [ctypes.POINTER(ModelDesc), c_f, c_f, c_f, c_l, c_l, c_l, c_l, c_f, c_l, c_f, c_i, c_i,
-                            c_f, c_f, c_f, c_f, c_f, ctypes.POINTER(ctypes.c_void_p), c_i, c_f]),
-    "stg_model_bwd_nll": (c_i, [ctypes.POINTER(ModelDesc), c_f, c_f, c_f, c_l, c_l, c_l, c_l, c_f, c_l, c_f, c_i, c_i,
-                                c_f, c_f, c_f, c_f, c_f, c_f, c_f, ctypes.POINTER(ctypes.c_void_p), c_i, c_f]),
-    "stg_model_bwd_step": (c_i, [ctypes.POINTER(ModelDesc), c_f, c_f, c_f, c_l, c_l, c_l, c_l, c_f, c_l, c_f, c_i, c_i,
-                                 c_f, c_f, c_f, c_f, c_f, c_f, c_f, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), c_i,
-                                 c_f]),
-    "stg_model_step": (c_i, [ctypes.POINTER(ModelDesc), c_f, c_f, c_f, c_l, c_l, c_l, c_l, c_f, c_l, c_f, c_i, c_i,
-                             c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, ctypes.c_void_p,
-                             ctypes.POINTER(ctypes.c_void_p), c_i, ctypes.POINTER(ctypes.c_void_p), c_i, c_f]),
-    "stg_bn_fold": (c_i, [ctypes.POINTER(ModelDesc), c_f, c_f, c_i, c_f, ctypes.POINTER(ctypes.c_void_p), c_i, c_f]),
-    "stg_nll_fwd": (c_i, [c_f, c_l, c_l, c_l, c_l, c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_f]),
-    "stg_nll_bwd": (c_i, [c_f, c_f, c_i, c_i, c_i, c_f, c_f]),
-    "stg_sgd_step": (c_i, [c_f, c_f, c_l, ctypes.c_float, c_f]),
-    "stg_scene_order": (c_i, [c_f, c_i, c_i, c_f, c_f, c_f]),
-    "stg_optim_step": (c_i, [c_f, c_f, c_l, c_f, ctypes.c_float, ctypes.c_float, c_f, c_f]),
-    "stg_bestofk_eval": (c_i, [c_f, c_l, c_l, c_l, c_l, c_f, c_f, c_f, c_f, ctypes.c_uint64, c_i, c_i, c_i, c_i,
-                               c_f, c_f, c_f]),
-    "stg_sample_trajectories": (c_i, [c_f, c_l, c_l, c_l, c_l, c_f, c_f, c_f, ctypes.c_uint64, c_f, c_i, c_i, c_i, c_i,
-                                      c_f, c_f, c_f]),
-    "stg_sample_risk": (c_i, [c_f, c_l, c_l, c_l, c_l, c_f, c_f, c_f, ctypes.c_uint64, c_f, c_i, c_i, c_i, c_i,
-                              ctypes.c_float, c_f, c_l, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
-    "stg_gather_windows": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f]),
-    "stg_dp_pack": (c_i, [c_f, c_f, c_f, c_f, c_i, ctypes.c_float, c_i, c_i, c_i, c_i, c_f, c_f]),
-    "stg_dp_fold": (c_i, [c_f, c_f, ctypes.c_float, c_i, c_i, c_i, c_i, c_f, ctypes.POINTER(ctypes.c_void_p), c_i, c_f]),
-    "stg_weighted_sum": (c_i, [c_f, c_f, c_i, c_f, c_f]),
-    "stg_train_tail": (c_i, [ctypes.POINTER(ModelDesc), c_f, c_f, c_i, c_f, ctypes.POINTER(ctypes.c_void_p), c_i, c_f, c_f,
-                             c_f, c_f, c_f, c_l, c_f, ctypes.c_float, ctypes.c_float, c_f, c_f]),
-    "stg_frame_scene_counts": (c_i, [c_f, c_f, c_i, c_i, c_f, c_f]),
-    "stg_frame_scenes": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, ctypes.c_double, c_f, c_f, c_f, c_f]),
-    "stg_track_push": (c_i, [c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_i, c_i, ctypes.c_double, c_i, c_f, c_f, c_f,
-                             c_f]),
-    "stg_track_push_streams": (c_i, [c_f, c_l, c_f, c_l, c_i, c_f, c_f, c_i, c_i, c_f, c_f, c_f, c_f, c_i, c_i,
-                                     ctypes.c_double, c_i, c_f, c_f, c_f, c_f, c_i, c_f]),
-    "stg_fill_tracks": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, ctypes.c_double, c_f]),
-    "stg_frame_scene_counts_rule": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_f, c_f]),
-    "stg_frame_scenes_rule": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, ctypes.c_double, c_i, c_i, c_f, c_f, c_f, c_f,
-                                    c_f]),
-    "stg_track_push_rule": (c_i, [c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_i, c_i, ctypes.c_double, c_i, c_i, c_i,
-                                  c_f, c_f, c_f, c_f, c_f]),
-    "stg_track_push_streams_rule": (c_i, [c_f, c_l, c_f, c_l, c_i, c_f, c_f, c_i, c_i, c_f, c_f, c_f, c_f, c_i, c_i,
-                                          ctypes.c_double, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_i, c_f]),
-    "stg_track_push_timed": (c_i, [c_f, c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i,
-                                   ctypes.c_double, c_i, c_l, c_l, c_i, c_i, c_f, c_f, c_f, c_f, c_f]),
-    "stg_track_push_streams_timed": (c_i, [c_f, c_l, c_f, c_l, c_i, c_f, c_f, c_f, c_i, c_i, c_f, c_f, c_f, c_f, c_f,
-                                           c_f, c_i, c_i, c_i, ctypes.c_double, c_i, c_l, c_l, c_i, c_i, c_f, c_f, c_f,
-                                           c_f, c_f, c_i, c_f]),
-    "stg_score_push": (c_i, [c_f, c_f, c_f, c_i, ctypes.c_double, c_f, c_f, c_l, c_l, c_l, c_l, c_f, c_f, c_f, c_i, c_i,
-                             c_i, ctypes.POINTER(ScoreState), c_f, c_i, ctypes.POINTER(ScoreOut), c_f]),
-    "stg_score_push_streams": (c_i, [c_f, c_l, c_f, c_l, c_i, c_f, c_f, c_i, c_i, ctypes.c_double, c_f, c_f, c_l, c_l,
-                                     c_l, c_l, c_f, c_f, c_f, c_i, c_i, c_i, ctypes.POINTER(ScoreState), c_f, c_i,
-                                     ctypes.POINTER(ScoreOut), c_f]),
-    "stg_associate": (c_i, [c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, ctypes.c_double,
-                            ctypes.c_double, ctypes.c_double, c_i, c_f]),
-    "stg_associate_streams": (c_i, [c_f, c_l, c_f, c_l, c_i, c_f, c_f, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f,
-                                    c_i, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_i, c_f]),
-    "stg_selftest_mfma": (c_i, [c_f, c_f, c_i, c_f, c_f]),
-}
-EXPORTS = tuple(_SIGNATURES)
-# the entry points of include/stgcnn_hip_score_time.h (the header stgcnn_hip.h includes at its end), bound with the rest
-_SIGNATURES_SCORE_TIME = {
-    # (state and out: ctypes.byref of a ScoreTimedState / ScoreTimedOut, which a void* parameter takes)
-    "stg_score_push_timed": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, ctypes.c_double, c_l, c_l, c_f, c_f, c_l, c_l,
-                                   c_l, c_l, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f, c_f, c_i, c_f, c_f]),
-    "stg_score_push_streams_timed": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, ctypes.c_double, c_l, c_l,
-                                           c_f, c_f, c_l, c_l, c_l, c_l, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f, c_f, c_i,
-                                           c_f, c_f]),
-}
-# ... and those of include/stgcnn_hip_harvest.h, included the same way
-_SIGNATURES_HARVEST = {
-    "stg_window_harvest": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i,
-                                 c_f]),
-    "stg_window_harvest_streams": (c_i, [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_f,
-                                         c_f, c_f, c_i, c_i, c_f]),
-}
-# ... and those of include/stgcnn_hip_harvest_time.h, included the same way
-c_d = ctypes.c_double
-_SIGNATURES_HARVEST_TIME = {
-    "stg_window_harvest_timed": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_d, c_l, c_l, c_l, c_i,
-                                       c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_f]),
-    "stg_window_harvest_streams_timed": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_d, c_l,
-                                               c_l, c_l, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_f]),
-}
-# ... and those of include/stgcnn_hip_assoc_time.h, included the same way
-_SIGNATURES_ASSOC_TIME = {
-    "stg_associate_timed": (c_i, [c_f, c_f, c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_d, c_d, c_d, c_l,
-                                  c_l, c_f]),
-    "stg_associate_streams_timed": (c_i, [c_f, c_l, c_f, c_l, c_i, c_f, c_f, c_f, c_f, c_i, c_i, c_f, c_f, c_f, c_f, c_f,
-                                          c_f, c_f, c_i, c_d, c_d, c_d, c_l, c_l, c_f]),
-}
-# ... and those of include/stgcnn_hip_assoc_filter.h, included the same way
-_SIGNATURES_ASSOC_FILTER = {
-    "stg_associate_filtered": (c_i, [c_f, c_f, c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_d, c_d,
-                                     c_d, c_d, c_d, c_d, c_l, c_l, c_f]),
-    "stg_associate_streams_filtered": (c_i, [c_f, c_l, c_f, c_l, c_i, c_f, c_f, c_f, c_f, c_i, c_i, c_f, c_f, c_f, c_f,
-                                             c_f, c_f, c_f, c_f, c_i, c_d, c_d, c_d, c_d, c_d, c_d, c_l, c_l, c_f]),
-}
-# ... and the one of include/stgcnn_hip_metrics.h, included the same way
-_SIGNATURES_METRICS = {
-    "stg_dist_metrics": (c_i, [c_f, c_l, c_l, c_l, c_l, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, ctypes.c_float, c_f, c_f,
-                               c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
-}
-# ... and those of include/stgcnn_hip_calib.h, included the same way
-_SIGNATURES_CALIB = {
-    "stg_calib_fit_ws_bytes": (c_l, [c_i, c_i, c_i]),
-    "stg_calib_fit": (c_i, [c_f, c_l, c_l, c_l, c_l, c_f, c_f, c_f, c_i, c_i, c_i, c_i, ctypes.c_float, c_f, c_f, c_f,
-                            c_f, c_f, c_f, c_l, c_f]),
-    "stg_calib_apply": (c_i, [c_f, c_l, c_l, c_l, c_l, c_f, c_i, c_i, c_i, c_f, c_l, c_l, c_l, c_l, c_f]),
-}
+class StepTail(ctypes.Structure):
+    """stg_step_tail (include/stgcnn_hip.h)."""
+    _fields_ = [("params", ctypes.c_void_p), ("lr_dev", ctypes.c_void_p), ("lr", ctypes.c_float),
+                ("stats", ctypes.c_void_p), ("buffers", ctypes.c_void_p), ("nbt", ctypes.POINTER(ctypes.c_void_p)),
+                ("n_bn", ctypes.c_int), ("total", ctypes.c_void_p)]
+
+
+Prototype = collections.namedtuple("Prototype", "name ret params")
+Prototype.__doc__ = """One entry point as a header declares it: its name, the C type it returns and its parameters in
+order, ((parameter name, C type), ...)."""
+_Entry = collections.namedtuple("_Entry", "fn names nameset status")
+
+
+class HeaderError(RuntimeError):
+    """A prototype the binding cannot be derived from; the message names it."""
+
+
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64,
+            "float": ctypes.c_float, "double": ctypes.c_double}
+# the structs Python fills field by field travel typed; every other pointer (device memory, and the structs handed over
+# with ctypes.byref / addressof: stg_step_tail, stg_score_timed_state, stg_score_timed_out) is a void *
+_STRUCTS = {"stg_model_desc": ctypes.POINTER(ModelDesc), "stg_score_state": ctypes.POINTER(ScoreState),
+            "stg_score_out": ctypes.POINTER(ScoreOut)}
+_QUALIFIERS = ("const", "struct")
+
+
+def _words(decl):
+    """A declaration -> (its words without qualifiers, the number of `*`)."""
+    words = decl.replace("*", " * ").split()
+    return [w for w in words if w != "*" and w not in _QUALIFIERS], words.count("*")
+
+
+def parse_header(text):
+    """The prototypes of the entry points (stg_*) that the text of a C header declares, in its order."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    text = "\n".join(l for l in text.split("\n") if not l.lstrip().startswith("#"))
+    protos = []
+    for ret, name, params in re.findall(r"([A-Za-z_][\w\s\*]*?)\b(stg_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
+        pairs = []
+        for decl in ([] if params.strip() == "void" else params.split(",")):
+            words, _ = _words(decl)
+            if len(words) != 2:
+                raise HeaderError("%s: parameter %d, `%s`, is not `<type> <name>`" % (name, len(pairs), decl.strip()))
+            pname = words[1]
+            if any(pname == n for n, _ in pairs):
+                raise HeaderError("%s: two parameters are called `%s`" % (name, pname))
+            pairs.append((pname, " ".join(decl.replace("*", " * ").split()[:-1])))
+        protos.append(Prototype(name, " ".join(ret.split()), tuple(pairs)))
+    return protos
+
+
+def ctype_of(ctype, where):
+    """The ctypes type an argument or a result of the C type `ctype` is bound with; `where` names it in the refusal."""
+    words, stars = _words(ctype)
+    base = words[0] if len(words) == 1 else None
+    if stars == 0 and base in _SCALARS:
+        return _SCALARS[base]
+    if stars == 1 and base in _STRUCTS:
+        return _STRUCTS[base]
+    if stars == 1 and base == "char":
+        return ctypes.c_char_p
+    if stars == 2 and base is not None and base not in _STRUCTS:      # a host array of device pointers
+        return ctypes.POINTER(ctypes.c_void_p)
+    if stars == 1 and base is not None:
+        return ctypes.c_void_p
+    raise HeaderError("%s: no ctypes type for `%s`" % (where, ctype))
+
+
+def collect(texts):
+    """{name: Prototype} over the texts of several headers; a name declared twice is refused."""
+    protos = {}
+    for text in texts:
+        for p in parse_header(text):
+            if p.name in protos:
+                raise HeaderError("%s is declared twice" % p.name)
+            protos[p.name] = p
+    return protos
+
+
+def bind(handle, protos):
+    """Set restype / argtypes of every prototype on the loaded library `handle`; -> {name: _Entry}, what call() needs.
+    An `int` result is a status (check() raises on it) but for the version query."""
+    entries = {}
+    for p in protos.values():
+        res = ctype_of(p.ret, p.name)
+        args = [ctype_of(c, "%s(%s)" % (p.name, n)) for n, c in p.params]
+        fn = getattr(handle, p.name, None)
+        if fn is None:
+            raise HeaderError("%s is declared in the headers but not exported by %s" % (p.name, handle._name))
+        fn.restype, fn.argtypes = res, args
+        names = tuple(n for n, _ in p.params)
+        entries[p.name] = _Entry(fn, names, frozenset(names), res is ctypes.c_int and p.name != "stg_abi_version")
+    return entries
+
+
+def header_texts():
+    """The text of include/stgcnn_hip.h and of the part headers it #includes, in that order."""
+    main = open(os.path.join(INCLUDE, "stgcnn_hip.h")).read()
+    parts = re.findall(r'^\s*#\s*include\s+"([^"]+)"', main, flags=re.M)
+    return [main] + [open(os.path.join(INCLUDE, f)).read() for f in parts]
+
+
+# THE binding: the headers are its only copy.  EXPORTS: the names the main header declares.
+_texts = header_texts()
+PROTOTYPES = collect(_texts)
+EXPORTS = tuple(p.name for p in parse_header(_texts[0]))
 
 _lib = None
+_entries = None
 
 
 def build(verbose=False):
@@ -206,7 +183,7 @@ def build(verbose=False):
 
 def lib():
     """The loaded library (raises if it has not been built: there is no fallback path)."""
-    global _lib
+    global _lib, _entries
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise RuntimeError(
@@ -214,24 +191,71 @@ def lib():
                 "--offload-arch=gfx950) or `python -c 'import __graft_entry__ as g; g.build()'`. "
                 "There is no CPU or eager-PyTorch fallback for this path." % (LIB_PATH, CSRC))
         h = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in {**_SIGNATURES, **_SIGNATURES_SCORE_TIME, **_SIGNATURES_HARVEST,
-                                    **_SIGNATURES_HARVEST_TIME, **_SIGNATURES_ASSOC_TIME,
-                                    **_SIGNATURES_ASSOC_FILTER, **_SIGNATURES_METRICS,
-                                    **_SIGNATURES_CALIB}.items():
-            fn = getattr(h, name)
-            fn.restype = res
-            fn.argtypes = args
+        entries = bind(h, PROTOTYPES)
         if h.stg_abi_version() != ABI_VERSION:
             raise RuntimeError("libstgcnn_hip.so ABI %d != binding ABI %d" % (h.stg_abi_version(), ABI_VERSION))
-        _lib = h
+        _lib, _entries = h, entries
     return _lib
 
 
-class StepTail(ctypes.Structure):
-    """stg_step_tail (include/stgcnn_hip.h)."""
-    _fields_ = [("params", ctypes.c_void_p), ("lr_dev", ctypes.c_void_p), ("lr", ctypes.c_float),
-                ("stats", ctypes.c_void_p), ("buffers", ctypes.c_void_p), ("nbt", ctypes.POINTER(ctypes.c_void_p)),
-                ("n_bn", ctypes.c_int), ("total", ctypes.c_void_p)]
+def _entry(name):
+    lib()
+    return _entries[name]
+
+
+def _refuse(name, names, given):
+    given = list(given)
+    kinds = (("missing", [n for n in names if n not in given]), ("unknown", [n for n in given if n not in names]),
+             ("repeated", sorted({n for n in given if given.count(n) > 1})))
+    raise TypeError("%s: %s" % (name, "; ".join("%s: %s" % (what, ", ".join(ns)) for what, ns in kinds if ns)))
+
+
+def call(name, **kw):
+    """Call the entry point `name` with its arguments by the names its prototype gives them: exactly those, in any
+    order (a missing or an unknown one is a TypeError, and the library is not entered).  `stream` alone has a default,
+    the current torch stream.  A status is checked (RuntimeError with stg_last_error()); a size query returns its value."""
+    fn, names, nameset, status = _entry(name)
+    current = "stream" in nameset and "stream" not in kw
+    if current:
+        kw["stream"] = None
+    if kw.keys() != nameset:
+        _refuse(name, names, kw)
+    if current:
+        kw["stream"] = stream_ptr()
+    res = fn(*[kw[n] for n in names])
+    if status:
+        check(res, name)
+    return res
+
+
+class Bound:
+    """An entry point with the arguments that never change fixed and put in order once, for a caller that launches it
+    over and over: Bound(name, varying, **fixed), then bound(**varying).  `fixed` and the names `varying` must together
+    be exactly the prototype's parameters (`stream` apart, as in call()); that is checked here, when it is built, so a
+    launch orders its few varying arguments and does nothing else."""
+
+    def __init__(self, name, varying, **fixed):
+        self.fn, names, _, self.status = _entry(name)
+        self.name, varying = name, tuple(varying)
+        given = tuple(fixed) + varying
+        self.stream = names.index("stream") if "stream" in names and "stream" not in given else None
+        if sorted(given + ("stream",) * (self.stream is not None)) != sorted(names):
+            _refuse(name, [n for n in names if n != "stream" or self.stream is None], given)
+        self.args = [fixed.get(n) for n in names]
+        self.slots, self.varying = tuple((names.index(n), n) for n in varying), frozenset(varying)
+
+    def __call__(self, **kw):
+        args = list(self.args)
+        if kw.keys() != self.varying:
+            _refuse(self.name, [n for _, n in self.slots], kw)
+        for i, n in self.slots:
+            args[i] = kw[n]
+        if self.stream is not None:
+            args[self.stream] = stream_ptr()
+        res = self.fn(*args)
+        if self.status:
+            check(res, self.name)
+        return res
 
 
 class HipEvents:
@@ -279,10 +303,17 @@ class HipEvents:
             pass
 
 
+class StatusError(RuntimeError):
+    """An entry point returned a status other than 0: `.status` holds it."""
+
+    def __init__(self, what, status, msg):
+        super().__init__("%s failed (status %d): %s" % (what, status, msg))
+        self.status = status
+
+
 def check(rc, what):
     if rc != 0:
-        msg = lib().stg_last_error().decode("utf-8", "replace")
-        raise RuntimeError("%s failed (status %d): %s" % (what, rc, msg))
+        raise StatusError(what, rc, lib().stg_last_error().decode("utf-8", "replace"))
 
 
 def stream_ptr():

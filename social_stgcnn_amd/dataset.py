@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import graphs, ops
-from ._lib import check, lib, ptr, require_gpu, stream_ptr
+from ._lib import call, ptr, require_gpu
 
 
 class DeviceWindows:
@@ -87,9 +87,9 @@ class DeviceWindows:
             n = index.numel()
         obs_rel, target, peds = out if out is not None else self.buffers(n, v_pad)
         v = obs_rel.shape[1]
-        check(lib().stg_gather_windows(ptr(self.rel_all), ptr(self.win_start), ptr(index), self.n_windows, int(n), int(v),
-                                       self.t_obs, self.t_pred, ptr(obs_rel), ptr(target), ptr(peds), stream_ptr()),
-              "stg_gather_windows")
+        call("stg_gather_windows", seq_rel_all=ptr(self.rel_all), win_start=ptr(self.win_start), index=ptr(index),
+             n_windows=self.n_windows, N=int(n), V=int(v), T_obs=self.t_obs, T_pred=self.t_pred, obs_rel=ptr(obs_rel),
+             target=ptr(target), num_peds=ptr(peds))
         return obs_rel, target, peds
 
 

@@ -62,7 +62,7 @@ import numpy as np
 import torch
 
 from . import ops
-from ._lib import check, lib, peds_arg, ptr, require_gpu, seed_i64, stream_ptr
+from ._lib import Bound, call, peds_arg, ptr, require_gpu, seed_i64
 from .predict import Prediction, Predictor, ScoreSpec, TimedScoreSpec, eval_mode
 
 MAX_OBS_LEN = 32                       # presence masks are 32-bit
@@ -330,8 +330,8 @@ class LiveWindows:
 
     def _args(self):
         """the log as the harvest entry points take it"""
-        return (ptr(self.rel_all), ptr(self.win_start), ptr(self.win_tag), ptr(self.header), self.cap_windows,
-                self.cap_rows)
+        return dict(rel_all=ptr(self.rel_all), win_start=ptr(self.win_start), win_tag=ptr(self.win_tag),
+                    header=ptr(self.header), cap_windows=self.cap_windows, cap_rows=self.cap_rows)
 
     def counts(self):
         """(n_windows, n_rows, dropped_full) as of the pushes enqueued so far: one synchronisation."""
@@ -471,10 +471,10 @@ def recording_scenes(rows, device, obs_len=8, min_peds=1, decimals=4, v_pad=None
     ids_d = torch.from_numpy(ids).to(device)
     xy_d = torch.from_numpy(xy).to(device)
     count = torch.zeros(nf, device=device, dtype=torch.int32)
-    # the strict kernels, or their *_rule twins with the rule ahead of the outputs and `seen` behind them
-    name, rule_args = ("%s", ()) if rule is None else ("%s_rule", tuple(rule))
-    check(getattr(lib(), name % "stg_frame_scene_counts")(ptr(fs_d), ptr(ids_d), nf, obs_len, *rule_args, ptr(count),
-                                                          stream_ptr()), name % "stg_frame_scene_counts")
+    # the strict kernels, or their *_rule twins, which also take the rule and write `seen`
+    form, rule_args = ("", {}) if rule is None else ("_rule", rule._asdict())
+    call("stg_frame_scene_counts" + form, frame_start=ptr(fs_d), ids=ptr(ids_d), F=nf, T_obs=obs_len, **rule_args,
+         count=ptr(count))
     cnt = count.cpu().numpy()
     first = obs_len - 1 if rule is None else rule.min_seen - 1
     sel = np.nonzero((cnt >= int(min_peds)) & (np.arange(nf) >= first))[0]
@@ -492,9 +492,9 @@ def recording_scenes(rows, device, obs_len=8, min_peds=1, decimals=4, v_pad=None
     seen = () if rule is None else (torch.empty((n, v), device=device, dtype=torch.int32),)
     if n:
         sel_d = torch.from_numpy(sel.astype(np.int32)).to(device)
-        check(getattr(lib(), name % "stg_frame_scenes")(ptr(fs_d), ptr(ids_d), ptr(xy_d), ptr(sel_d), n, v, obs_len,
-                                                        scale, *rule_args, ptr(obs), ptr(out_ids), ptr(peds),
-                                                        *map(ptr, seen), stream_ptr()), name % "stg_frame_scenes")
+        call("stg_frame_scenes" + form, frame_start=ptr(fs_d), ids=ptr(ids_d), xy=ptr(xy_d), frames=ptr(sel_d), N=n, V=v,
+             T_obs=obs_len, scale=scale, **rule_args, obs_abs=ptr(obs), out_ids=ptr(out_ids), num_peds=ptr(peds),
+             **{"seen": ptr(x) for x in seen})
     return (FrameScenes if rule is None else PartialScenes)(frames[sel], obs, out_ids, peds, *seen)
 
 
@@ -517,8 +517,7 @@ def fill_tracks(obs_abs, seen, num_peds=None, decimals=4):
         raise ValueError("fill_tracks: seen (%d,%d) expected, got %s" % (n, v, tuple(seen.shape)))
     peds = peds_arg(num_peds, n, obs_abs.device)
     if n and v:
-        check(lib().stg_fill_tracks(ptr(obs_abs), ptr(seen), ptr(peds), n, t, v, scale, stream_ptr()),
-              "stg_fill_tracks")
+        call("stg_fill_tracks", obs_abs=ptr(obs_abs), seen=ptr(seen), num_peds=ptr(peds), N=n, T_obs=t, V=v, scale=scale)
     return obs_abs
 
 
@@ -614,13 +613,14 @@ _OPTIONS = {
         "ScoreSpec serves)", lambda x: ScoreSpec(*x)),
 }
 
-_Feed = collections.namedtuple("_Feed", "lead det when pushed n_out tail rings")
+_Feed = collections.namedtuple("_Feed", "lead det when pushed outs tail rings")
 _Feed.__doc__ = """What differs between one stream and many, as a predictor hands it to its stages: lead, the leading axis
-of every state tensor (() or (NS,)); det, the staging buffers as pointers by the names ops.score_push takes them, in the
-order the push and association kernels do; when, the pointer to the push time(s) (read under time= only); pushed, the
-(NS,) int32 `pushed` words (None: one stream, always pushed); n_out, how many of _outs() the push kernel writes (`seen`
-apart); tail, the push kernel's arguments behind its outputs; rings, whether reset() clears the position rings too."""
+of every state tensor (() or (NS,)); det, the staging buffers as pointers by the names the push and association kernels
+take them under; when, the pointer to the push time(s) (read under time= only); pushed, the (NS,) int32 `pushed` words
+(None: one stream, always pushed); outs, the names of those of _outs() that the push kernel writes (`seen` apart); tail,
+what the push kernel takes besides, by name; rings, whether reset() clears the position rings too."""
 _I32, _I64, _F64 = torch.int32, torch.int64, torch.float64
+_PUSH_OUTS = ("obs_abs", "out_ids", "num_peds", "out_flags")        # (out_flags: many streams only)
 
 
 def _makers(dev, lead):
@@ -629,12 +629,16 @@ def _makers(dev, lead):
                  for make in (torch.zeros, torch.empty))
 
 
+def _ptrs(named):
+    return {n: ptr(x) for n, x in named.items()}
+
+
 class _Stage:
     """One launch around the model in a live push, built once, behind the predictor's staging buffers.  A stage owns its
-    device tensors (`named`: by the names the predictor shows them under; `state`: the same in the ABI's order), says what
-    a reset fills (`cleared`, (tensor, value) pairs) and what an empty push moves (`moved`), resolves its entry point --
-    the lone or the _streams one, in its push-indexed or its timed form -- with every argument that stays the same from
-    push to push, and has ONE launch, which takes what varies."""
+    device tensors (`named`: by the names the predictor shows them under, which are the names the entry point takes them
+    under; `state`: the same as a tuple), says what a reset fills (`cleared`, (tensor, value) pairs) and what an empty
+    push moves (`moved`), resolves its entry point -- the lone or the _streams one, in its push-indexed or its timed form
+    -- with every argument that stays the same from push to push, and has ONE launch, which takes what varies."""
 
     def _own(self, named, fill, kept=(), also=()):
         """`named` is the state: a reset fills it with 0, and with fill[name] where that is given, but for the names in
@@ -643,14 +647,15 @@ class _Stage:
         self.moved = self.state + also
         self.cleared = [(x, fill.get(n, 0)) for n, x in named.items() if n not in kept]
 
-    def _bind(self, base, feed, form, *args):
-        """The entry point of the family `base` that serves this feed (many streams: the _streams one) in this form ("",
-        or the suffix of a twin), and its fixed arguments."""
-        self.name = base + ("_streams" if feed.lead else "") + form
-        self.entry, self.args = getattr(lib(), self.name), args
+    def _bind(self, base, feed, form, varying=(), **fixed):
+        """The entry point of the family `base` that serves this feed (many streams: the _streams one, which is told how
+        many) in this form ("", or the suffix of a twin), its `fixed` arguments bound; a launch names the `varying`."""
+        if feed.lead:
+            fixed["NS"] = feed.lead[0]
+        self.entry = Bound(base + ("_streams" if feed.lead else "") + form, varying, **fixed)
 
     def launch(self, outs):
-        check(self.entry(*self.args, stream_ptr()), self.name)
+        self.entry()
 
 
 class _Tracks(_Stage):
@@ -659,31 +664,29 @@ class _Tracks(_Stage):
 
     def __init__(self, p, feed):
         zeros, empty = _makers(p.device, feed.lead)
-        rule = () if p.rule is None else tuple(p.rule)
+        rule = {} if p.rule is None else p.rule._asdict()
         named = dict(slot_id=empty(_I64, p.s))
+        sizes = dict(M_max=p.m_max, S=p.s, T_obs=p.t_obs, scale=p.scale, V=p.v)
         if p.time is None:
-            # the strict kernel, or its *_rule twin with the rule ahead of the outputs and `seen` behind them
+            # the strict kernel, or its *_rule twin, which also takes the rule and writes `seen`
             named.update(mask=empty(_I32, p.s), ring=zeros(_F64, p.t_obs, p.s, 2))
-            form, rings, when = "_rule" if rule else "", ("ring",), ()   # (a ring row is read only where the mask says so)
-            sizes = (p.s, p.t_obs, ctypes.c_double(p.scale), p.v)
+            form, rings = "_rule" if rule else "", ("ring",)         # (a ring row is read only where the mask says so)
         else:
-            # the timed twin: the time(s) behind the detections, R behind S, (step, max_dt) ahead of the rule
-            r = p.time.history
-            named.update(t_ring=zeros(_I64, p.s, r), xy_ring=zeros(_F64, p.s, r, 2), slot_head=empty(_I32, p.s, 2),
-                         clock=empty(_I64, 2))
-            form, rings, when = "_timed", ("t_ring", "xy_ring"), (feed.when,)    # (a ring holds what its count says)
-            sizes = (p.s, r, p.t_obs, ctypes.c_double(p.scale), p.v, p.time.step, p.time.max_dt)
+            named.update(t_ring=zeros(_I64, p.s, p.time.history), xy_ring=zeros(_F64, p.s, p.time.history, 2),
+                         slot_head=empty(_I32, p.s, 2), clock=empty(_I64, 2))
+            form, rings = "_timed", ("t_ring", "xy_ring")            # (a ring holds what its count says)
+            sizes.update(det_time=feed.when, R=p.time.history, step=p.time.step, max_dt=p.time.max_dt)
         named["head_flags"] = empty(_I32, 2)
         self._own(named, {"slot_id": -1}, kept=() if feed.rings else rings)
-        self._bind("stg_track_push", feed, form, *feed.det.values(), *when, *feed.lead, p.m_max, *map(ptr, self.state),
-                   *sizes, *rule)
-        # of _outs() the kernel writes the first n_out and, under a rule, `seen`, the last
+        # of _outs() the kernel writes the first, feed.outs, and, under a rule, `seen`, the last
         self.feed, self.seen = feed, slice(-1, None) if rule else slice(0, 0)
+        self.outs = feed.outs + (("seen",) if rule else ())
+        self._bind("stg_track_push", feed, form, self.outs, **feed.det, **_ptrs(named), **sizes, **rule, **feed.tail)
 
     def launch(self, outs):
         """staging buffers + track state -> outs"""
-        n, pushed = self.feed.n_out, self.feed.pushed
-        check(self.entry(*self.args, *map(ptr, outs[:n] + outs[self.seen]), *self.feed.tail, stream_ptr()), self.name)
+        n, pushed = len(self.feed.outs), self.feed.pushed
+        self.entry(**{name: ptr(x) for name, x in zip(self.outs, outs[:n] + outs[self.seen])})
         if pushed is not None:                               # many streams: which of them this tick pushed, as a bool
             torch.ne(pushed, 0, out=outs[n])
 
@@ -700,23 +703,24 @@ class _Association(_Stage):
         c = p.s if spec.capacity is None else spec.capacity
         named = dict(trk_id=empty(_I64, c), trk_pos=zeros(_F64, c, 2), trk_vel=zeros(_F64, c, 2))
         if isinstance(spec, _TIMED_ASSOC):
-            # the timed twin, or the filtered one: the time(s) the timed push reads and that push's clock go between the
-            # detections and the sizes; the lifetime is (step, max_age) ticks
-            filtered = isinstance(spec, FilteredAssociateSpec)
+            # the timed twin, or the filtered one: it reads the time(s) the timed push reads and that push's clock; the
+            # lifetime is (step, max_age) ticks
             named["trk_t"] = zeros(_I64, c)
-            if filtered:
+            if isinstance(spec, FilteredAssociateSpec):
                 named["trk_cov"] = zeros(_F64, c, 3)
-            form, when = "_filtered" if filtered else "_timed", (feed.when, ptr(tracks.named["clock"]))
-            squared, life = spec[:5] if filtered else (spec.gate, spec.gate_new), (p.time.step, spec.max_age)
+                form, squared = "_filtered", dict(zip(("r", "qa", "v0", "n2", "gmax2"), spec[:5]))
+            else:
+                form, squared = "_timed", dict(gate2=spec.gate, gate_new2=spec.gate_new)
+            rest = dict(det_time=feed.when, clock=ptr(tracks.named["clock"]), step=p.time.step, max_age=spec.max_age)
         else:
             named["trk_miss"] = zeros(_I32, c)
-            form, when, squared, life = "", (), (spec.gate, spec.gate_new), (spec.max_miss,)
+            form, squared, rest = "", dict(gate2=spec.gate, gate_new2=spec.gate_new), dict(max_miss=spec.max_miss)
         named.update(trk_hits=zeros(_I32, c), next_id=torch.zeros(one, device=p.device, dtype=_I64),
                      assoc_flags=torch.zeros(one, device=p.device, dtype=_I32))
         self._own(named, {"trk_id": -1})                     # (an empty push ages the association's tracks too)
         # (the gates, or the filter's five parameters, travel squared, in float64)
-        self._bind("stg_associate", feed, form, *feed.det.values(), *when, *feed.lead, p.m_max, *map(ptr, self.state), c,
-                   ctypes.c_double(p.scale), *(ctypes.c_double(x * x) for x in squared), *life)
+        self._bind("stg_associate", feed, form, **feed.det, M_max=p.m_max, **_ptrs(named), C=c, scale=p.scale,
+                   **{n: x * x for n, x in squared.items()}, **rest)
 
 
 class _Harvest(_Stage):
@@ -730,13 +734,12 @@ class _Harvest(_Stage):
         zeros, _ = _makers(p.device, feed.lead)
         log = LiveWindows(spec, p.t_obs, p.device)
         named = dict(h_word=zeros(_I32, p.s), h_ring=zeros(_F64, log.t_all, p.s, 2), h_head=zeros(_I32, 2))
-        if p.time is None:
-            form, sizes = "", (p.s, p.t_obs, log.t_all, spec.min_peds)
-        else:
-            # the timed twin: R behind S, (scale, step, max_dt, settle) behind the sizes, h_clock behind the history
+        sizes = dict(S=p.s, T_obs=p.t_obs, T_all=log.t_all, min_peds=spec.min_peds)
+        form = ""
+        if p.time is not None:
             named["h_clock"] = zeros(_I64, 3)
-            form, sizes = "_timed", (p.s, p.time.history, p.t_obs, log.t_all, spec.min_peds, ctypes.c_double(p.scale),
-                                     p.time.step, p.time.max_dt, spec.settle)
+            form = "_timed"
+            sizes.update(R=p.time.history, scale=p.scale, step=p.time.step, max_dt=p.time.max_dt, settle=spec.settle)
         # A reset leaves the log alone, and the ring: a ring row is read only where the word says detected.  An empty push
         # ages the words and moves the ring row; it has no candidates, so of the log only the header is kept (its rows,
         # offsets and tags are written for a window alone).
@@ -744,11 +747,11 @@ class _Harvest(_Stage):
         self.named = dict(named, harvest=log)
         if feed.lead:                                        # a _streams entry point is told of its streams; its scratch
             self.work = torch.zeros(feed.lead[0] * (p.s + 3), device=p.device, dtype=_I32)
-            streams, tag, work = (ptr(feed.pushed), *feed.lead), (), (ptr(self.work),)
+            streams = dict(pushed=ptr(feed.pushed), work=ptr(self.work))
         else:                                                # the lone one tags its windows with a stream index
-            streams, tag, work = (), (0,), ()
-        self._bind("stg_window_harvest", feed, form, *map(ptr, tracks.state), *streams, *sizes, *tag,
-                   *map(ptr, self.state), *work, *log._args())
+            streams = dict(stream_index=0)
+        self._bind("stg_window_harvest", feed, form, **_ptrs(tracks.named), **streams, **sizes, **_ptrs(named),
+                   **log._args())
 
 
 class _Score:
@@ -770,7 +773,9 @@ class _Score:
         else:
             self.state = ops.score_state(ns, n_pred, p.v, p.k, dev, spec.best_of_k, q)
             self.fresh = lambda: ops.score_buffers(ns, n_pred, p.v, dev, spec.best_of_k)
-            self.push = functools.partial(ops.score_push, self.state, thr, m_max=p.m_max, scale=p.scale, **feed.det)
+            # (ops.score_push takes the staging buffers by the same names, in lower case)
+            self.push = functools.partial(ops.score_push, self.state, thr, m_max=p.m_max, scale=p.scale,
+                                          **{n.lower(): x for n, x in feed.det.items()})
         self.cleared = [(x, -1 if n == "rec_ids" else 0) for n, x in zip(self.state._fields, self.state) if x is not None]
         self.moved = tuple(x for x, _ in self.cleared)       # an empty push is a push: it scores and enqueues
         self.ids_shape, self.samples = (ns, p.v), spec.best_of_k
@@ -1067,7 +1072,7 @@ class FramePredictor(_LivePredictor):
         self.seed_dev = torch.zeros(1, device=dev, dtype=torch.int64)
         self._build(_Feed(lead=(), det=dict(det_id=ptr(self.det_id), det_xy=ptr(self.det_xy),
                                             det_count=ptr(self.det_count)),
-                          when=ptr(self.det_time), pushed=None, n_out=3, tail=(), rings=False))
+                          when=ptr(self.det_time), pushed=None, outs=_PUSH_OUTS[:3], tail={}, rings=False))
         self.reset()
 
     def reset(self):
@@ -1321,9 +1326,10 @@ class StreamsPredictor(_LivePredictor):
         self._rec_f = self._dev[self._hdr:].view(torch.float64).view(self.cap, 3)
         # a record is (id, x, y): ids at stride 3 from its start, positions at stride 3 from 8 bytes in
         det = dict(det_id=ptr(self._rec_i), id_stride=3, det_xy=ctypes.c_void_p(self._rec_f.data_ptr() + 8),
-                   xy_stride=3, m_total=self.cap, det_start=ptr(self.det_start), pushed=ptr(self.pushed_dev))
+                   xy_stride=3, M_total=self.cap, det_start=ptr(self.det_start), pushed=ptr(self.pushed_dev))
         self._build(_Feed(lead=(ns,), det=det, when=None if self.time is None else ptr(self.times_dev),
-                          pushed=self.pushed_dev, n_out=4, tail=(self.block_threads,), rings=True))
+                          pushed=self.pushed_dev, outs=_PUSH_OUTS, tail=dict(block_threads=self.block_threads),
+                          rings=True))
         self._copied = torch.cuda.Event()
         self._in_flight = False
         self.reset()

@@ -6,13 +6,24 @@ raises if the library or a GPU tensor is missing -- there is no eager fallback.
 import collections
 import ctypes
 import dataclasses
+import functools
 import math
 
 import numpy as np
 import torch
 
 from . import _lib
-from ._lib import ModelDesc, check, lib, peds_arg, ptr, require_gpu, seed_u64, stream_ptr
+from ._lib import ModelDesc, call, check, lib, peds_arg, ptr, require_gpu, seed_u64      # noqa: F401 (lib: for callers)
+
+
+@functools.lru_cache(maxsize=None)
+def _stride_names(prefix, axes):
+    return tuple("%s_s%s" % (prefix, a) for a in axes)
+
+
+def _strides(prefix, x, axes):
+    """The strides of x by the names the C ABI gives them: <prefix>_s<axis> for every letter of `axes`."""
+    return dict(zip(_stride_names(prefix, axes), x.stride()))
 
 
 def _adj_layout(adj, n, t, v):
@@ -51,9 +62,8 @@ def adj_build(seq_rel, num_peds=None, normalize=True, out=None):
     else:
         nodes = torch.empty((n, t, v, 2), device=seq_rel.device, dtype=torch.float32)
         adj = torch.empty((n, t, v, v), device=seq_rel.device, dtype=torch.float32)
-    sn, sv, sc, st = seq_rel.stride()
-    check(lib().stg_adj_build(ptr(seq_rel), sn, sv, sc, st, ptr(peds), n, v, t, 1 if normalize else 0,
-                              ptr(nodes), ptr(adj), stream_ptr()), "stg_adj_build")
+    call("stg_adj_build", rel=ptr(seq_rel), **_strides("rel", seq_rel, "nvct"), num_peds=ptr(peds), N=n, V=v, T=t,
+         normalize=1 if normalize else 0, nodes=ptr(nodes), adj=ptr(adj))
     return nodes, adj
 
 
@@ -70,9 +80,8 @@ class _SpatialAgg(torch.autograd.Function):
         adj_c, a_sn = _adj_layout(adj, n, t, v)
         peds = peds_arg(num_peds, n, x.device)
         y = torch.empty((n, c, t, v), device=x.device, dtype=torch.float32)
-        sn, sc, st, sv = x.stride()
-        check(lib().stg_spatial_agg_fwd(ptr(x), sn, sc, st, sv, ptr(adj_c), a_sn, ptr(peds), n, c, t, v, ptr(y),
-                                        stream_ptr()), "stg_spatial_agg_fwd")
+        call("stg_spatial_agg_fwd", x=ptr(x), **_strides("x", x, "nctv"), adj=ptr(adj_c), a_sn=a_sn, num_peds=ptr(peds),
+             N=n, C=c, T=t, V=v, y=ptr(y))
         ctx.save_for_backward(adj_c, peds if peds is not None else torch.empty(0))
         ctx.a_sn = a_sn
         ctx.has_peds = peds is not None
@@ -84,8 +93,8 @@ class _SpatialAgg(torch.autograd.Function):
         dy = dy.contiguous()
         n, c, t, v = dy.shape
         dx = torch.empty_like(dy)
-        check(lib().stg_spatial_agg_bwd(ptr(dy), ptr(adj_c), ctx.a_sn, ptr(peds) if ctx.has_peds else None, n, c, t,
-                                        v, ptr(dx), stream_ptr()), "stg_spatial_agg_bwd")
+        call("stg_spatial_agg_bwd", dy=ptr(dy), adj=ptr(adj_c), a_sn=ctx.a_sn,
+             num_peds=ptr(peds) if ctx.has_peds else None, N=n, C=c, T=t, V=v, dx=ptr(dx))
         return dx, None, None
 
 
@@ -111,9 +120,8 @@ class _ConvT(torch.autograd.Function):
         w = weight.contiguous()
         b = bias.contiguous() if bias is not None else None
         y = torch.empty((n, cout, to, v), device=x.device, dtype=torch.float32)
-        sn, sc, st, sv = x.stride()
-        check(lib().stg_conv_t_fwd(ptr(x), sn, sc, st, sv, ptr(w), ptr(b), ptr(peds), n, cin, cout, t, v, kt, pad,
-                                   ptr(y), stream_ptr()), "stg_conv_t_fwd")
+        call("stg_conv_t_fwd", x=ptr(x), **_strides("x", x, "nctv"), w=ptr(w), b=ptr(b), num_peds=ptr(peds), N=n,
+             Cin=cin, Cout=cout, T=t, V=v, kt=kt, pad=pad, y=ptr(y))
         ctx.save_for_backward(x, w, peds if peds is not None else torch.empty(0))
         ctx.has_peds = peds is not None
         ctx.has_bias = bias is not None
@@ -129,10 +137,9 @@ class _ConvT(torch.autograd.Function):
         dx = torch.empty((n, cin, t, v), device=x.device, dtype=torch.float32) if ctx.needs_input_grad[0] else None
         dw = torch.zeros_like(w)
         db = torch.zeros(cout, device=x.device, dtype=torch.float32) if ctx.has_bias else None
-        sn, sc, st, sv = x.stride()
-        check(lib().stg_conv_t_bwd(ptr(x), sn, sc, st, sv, ptr(w), ptr(dy), ptr(peds) if ctx.has_peds else None, n,
-                                   cin, cout, t, v, kt, ctx.pad, ptr(dx), ptr(dw), ptr(db), stream_ptr()),
-              "stg_conv_t_bwd")
+        call("stg_conv_t_bwd", x=ptr(x), **_strides("x", x, "nctv"), w=ptr(w), dy=ptr(dy),
+             num_peds=ptr(peds) if ctx.has_peds else None, N=n, Cin=cin, Cout=cout, T=t, V=v, kt=kt, pad=ctx.pad,
+             dx=ptr(dx), dw=ptr(dw), db=ptr(db))
         return dx, dw, db, None, None
 
 
@@ -266,11 +273,12 @@ def _timer_of(holder):
     return getattr(holder, "timer", None) if holder is not None else None
 
 
-def _size(n, what):
+def _size(name, **kw):
     """the value of a size query of the C ABI; a negative one is a status"""
+    n = int(call(name, **kw))
     if n < 0:
-        check(int(n), what)
-    return int(n)
+        check(n, name)
+    return n
 
 
 def _ptr_array(tensors):
@@ -313,20 +321,20 @@ def _check_model_input(x, adj, desc, flat_params, flat_buffers):
 def _fwd_buffers(desc, n, v, dev, save, training, holder):
     """The arrays stg_model_fwd writes, sized by the library: (y, ws, stats, scratch).  ws (the saved activations) only
     when `save`, stats only when `training`, scratch only where the path needs one."""
-    L, d = lib(), ctypes.byref(desc)
+    d = ctypes.byref(desc)
     out_t = desc.t_pred if desc.n_txpcnn > 0 else desc.t_obs
     y = torch.empty((n, desc.c_out, out_t, v), device=dev, dtype=torch.float32)
     ws = None                      # (its size is a diagnostic: last_ws_floats, 0 = inference)
     if save:
-        wsf = _size(L.stg_model_ws_floats(d, v), "stg_model_ws_floats")
-        tail = _size(L.stg_model_ws_tail_floats(d, n, v), "stg_model_ws_tail_floats")
+        wsf = _size("stg_model_ws_floats", d=d, V=v)
+        tail = _size("stg_model_ws_tail_floats", d=d, N=n, V=v)
         ws = torch.empty(n * wsf + tail, device=dev, dtype=torch.float32)
     stats = None
     if training:
-        sf = L.stg_model_stat_floats(d)
+        sf = call("stg_model_stat_floats", d=d)
         stats = torch.empty((n, max(int(sf), 1)), device=dev, dtype=torch.float32)
     scr = None
-    nscr = _size(L.stg_model_fwd_scratch_floats(d, n, v), "stg_model_fwd_scratch_floats")
+    nscr = _size("stg_model_fwd_scratch_floats", d=d, N=n, V=v)
     if nscr > 0:
         scr = torch.empty(nscr, device=dev, dtype=torch.float32)
     if holder is not None:
@@ -337,9 +345,9 @@ def _fwd_buffers(desc, n, v, dev, save, training, holder):
 
 def _bwd_buffers(desc, n, v, dev):
     """The arrays the fused backward writes, sized by the library: (scratch, flat gradient)."""
-    L, d = lib(), ctypes.byref(desc)
-    np_ = int(L.stg_model_param_count(d))
-    n_scratch = _size(L.stg_model_bwd_scratch_floats(d, n, v), "stg_model_bwd_scratch_floats")
+    d = ctypes.byref(desc)
+    np_ = int(call("stg_model_param_count", d=d))
+    n_scratch = _size("stg_model_bwd_scratch_floats", d=d, N=n, V=v)
     slabs = torch.empty(n_scratch, device=dev, dtype=torch.float32)
     grad = torch.empty(np_, device=dev, dtype=torch.float32)
     return slabs, grad
@@ -369,6 +377,23 @@ def _grad_views(grad, shapes, dead, holder):
     return [None if i in dead else grad[off:off + cnt].view(shapes[i]) for i, off, cnt in flat_walk(shapes)]
 
 
+def _model_head(desc, flat_params, flat_buffers, x, adj_c, a_sn, peds):
+    """The arguments every fused model entry point starts with: descriptor, packed tensors, input, adjacency, sizes."""
+    return dict(d=ctypes.byref(desc), params=ptr(flat_params), buffers=ptr(flat_buffers), x=ptr(x),
+                **_strides("x", x, "nctv"), adj=ptr(adj_c), a_sn=a_sn, num_peds=ptr(peds), N=x.shape[0], V=x.shape[3])
+
+
+def _unless_unsupported(name, **kw):
+    """call(); False, in the place of the refusal, where the library has no such form (STG_EUNSUPPORTED)."""
+    try:
+        call(name, **kw)
+    except _lib.StatusError as e:
+        if e.status != _lib.EUNSUPPORTED:
+            raise
+        return False
+    return True
+
+
 class _FusedModel(torch.autograd.Function):
     """x (N,Cin,T,V), adj -> y.  Extra (non-differentiable) arguments carry the packed buffers."""
 
@@ -376,7 +401,6 @@ class _FusedModel(torch.autograd.Function):
     def forward(ctx, x, adj, num_peds, desc, flat_params, flat_buffers, nbt, dead, holder, grad_on, defer_bn_fold,
                 *params):
         n, cin, t, v = _check_model_input(x, adj, desc, flat_params, flat_buffers)
-        L = lib()
         adj_c, a_sn = _adj_layout(adj, n, t, v)
         peds = peds_arg(num_peds, n, x.device)
         training = desc.bn_mode == 1
@@ -389,13 +413,10 @@ class _FusedModel(torch.autograd.Function):
             fields["flags"] |= _lib.OPT_WG_PATH
             desc = ModelDesc(**fields)
         y, ws, stats, scr = _fwd_buffers(desc, n, v, x.device, need_grad, training, holder)
-        sn, sc, st, sv = x.stride()
         timer = _timer_of(holder)
         ev = timer.events("model_fwd") if timer is not None else None
-        check(L.stg_model_fwd(ctypes.byref(desc), ptr(flat_params), ptr(flat_buffers), ptr(x), sn, sc, st, sv,
-                              ptr(adj_c), a_sn, ptr(peds), n, v, ptr(y), ptr(ws), ptr(stats), ptr(scr),
-                              ev.arr if ev else None, ev.n if ev else 0, stream_ptr()),
-              "stg_model_fwd")
+        call("stg_model_fwd", **_model_head(desc, flat_params, flat_buffers, x, adj_c, a_sn, peds), y=ptr(y), ws=ptr(ws),
+             stats=ptr(stats), scratch=ptr(scr), events=ev.arr if ev else None, n_events=ev.n if ev else 0)
         rec = FwdRecord(desc, a_sn, dead, [tuple(p.shape) for p in params], flat_params, flat_buffers, x, adj_c, peds,
                         ws)
         if training and defer_bn_fold:
@@ -404,8 +425,8 @@ class _FusedModel(torch.autograd.Function):
         elif training:
             # nbt[k] counts forwards of BatchNorm k; buffers are interleaved (mean, var) per BatchNorm, the
             # kernel bumps counter i for statistic row i < len(nbt): pass one pointer per BatchNorm.
-            check(L.stg_bn_fold(ctypes.byref(desc), ptr(stats), ptr(peds), n, ptr(flat_buffers), _ptr_array(nbt),
-                                len(nbt), stream_ptr()), "stg_bn_fold")
+            call("stg_bn_fold", d=ctypes.byref(desc), stats=ptr(stats), num_peds=ptr(peds), N=n, buffers=ptr(flat_buffers),
+                 nbt=_ptr_array(nbt), n_bn=len(nbt))
         if holder is not None:
             holder._fwd_state = rec if need_grad else None
         ctx.rec = rec
@@ -427,33 +448,29 @@ def _launch_backward(rec, holder, dy=None, need_dx=False, y=None, target=None, w
     Returns (per-parameter gradient views, None for the dead ones; dx | losses | (losses, total)), with the flat
     gradient left in `holder._flat_grad` -- or None, nothing launched, where the library has no form that starts from
     the target."""
-    L = lib()
     desc, x = rec.desc, rec.x
     n, cin, t, v = x.shape
     slabs, grad = _bwd_buffers(desc, n, v, x.device)
-    sn, sc, st, sv = x.stride()
     timer = _timer_of(holder)
     ev = timer.events("model_bwd") if timer is not None else None
-    head = (ctypes.byref(desc), ptr(rec.flat_params), ptr(rec.flat_buffers), ptr(x), sn, sc, st, sv, ptr(rec.adj_c),
-            rec.a_sn, ptr(rec.peds), n, v)
-    end = (ev.arr if ev else None, ev.n if ev else 0, stream_ptr())
+    common = dict(_model_head(desc, rec.flat_params, rec.flat_buffers, x, rec.adj_c, rec.a_sn, rec.peds), ws=ptr(rec.ws),
+                  scratch=ptr(slabs), grad_params=ptr(grad), events=ev.arr if ev else None, n_events=ev.n if ev else 0)
     if dy is not None:
         out = torch.empty((n, cin, t, v), device=x.device, dtype=torch.float32) if need_dx else None
-        name, rc = "stg_model_bwd", L.stg_model_bwd(*head, ptr(dy), ptr(rec.ws), ptr(slabs), ptr(grad), ptr(out), *end)
+        call("stg_model_bwd", **common, dy=ptr(dy), dx=ptr(out))
     else:
         out = losses = torch.empty(n, device=x.device, dtype=torch.float32)
-        mid = (ptr(y), ptr(target), ptr(weights), ptr(losses), ptr(rec.ws), ptr(slabs), ptr(grad))
+        mid = dict(y=ptr(y), target=ptr(target), weights=ptr(weights), losses=ptr(losses))
         if step is None:
-            name, rc = "stg_model_bwd_nll", L.stg_model_bwd_nll(*head, *mid, *end)
+            done = _unless_unsupported("stg_model_bwd_nll", **common, **mid)
         else:
             tail, total, keep = _step_tail(rec.flat_params, rec.flat_buffers, step, rec.stats, rec.nbt)
-            name, rc = "stg_model_bwd_step", L.stg_model_bwd_step(*head, *mid, ctypes.addressof(tail), *end)
+            done = _unless_unsupported("stg_model_bwd_step", **common, **mid, tail=ctypes.addressof(tail))
             out = (losses, total[0])
-        if rc == _lib.EUNSUPPORTED:
+        if not done:
             if ev is not None:
                 timer.calls["model_bwd"].pop()
             return None
-    check(rc, name)
     return _grad_views(grad, rec.shapes, rec.dead, holder), out
 
 
@@ -511,18 +528,16 @@ def fused_step(x, adj, num_peds, desc, flat_params, flat_buffers, nbt, dead, par
     timer = _timer_of(holder)
     ev_f = timer.events("model_fwd") if timer is not None else None
     ev_b = timer.events("model_bwd") if timer is not None else None
-    sn, sc, st, sv = x.stride()
-    rc = lib().stg_model_step(ctypes.byref(desc), ptr(flat_params), ptr(flat_buffers), ptr(x), sn, sc, st, sv, ptr(adj_c),
-                              a_sn, ptr(peds), n, v, ptr(y), ptr(ws), ptr(stats), ptr(scr), ptr(target), ptr(w),
-                              ptr(losses), ptr(slabs), ptr(grad), ctypes.addressof(tail),
-                              ev_f.arr if ev_f else None, ev_f.n if ev_f else 0,
-                              ev_b.arr if ev_b else None, ev_b.n if ev_b else 0, stream_ptr())
-    if rc == _lib.EUNSUPPORTED:
+    if not _unless_unsupported(
+            "stg_model_step", **_model_head(desc, flat_params, flat_buffers, x, adj_c, a_sn, peds), y=ptr(y), ws=ptr(ws),
+            stats=ptr(stats), fwd_scratch=ptr(scr), target=ptr(target), weights=ptr(w), losses=ptr(losses),
+            bwd_scratch=ptr(slabs), grad_params=ptr(grad), tail=ctypes.addressof(tail),
+            fwd_events=ev_f.arr if ev_f else None, n_fwd_events=ev_f.n if ev_f else 0,
+            bwd_events=ev_b.arr if ev_b else None, n_bwd_events=ev_b.n if ev_b else 0):
         if timer is not None:
             timer.calls["model_fwd"].pop()
             timer.calls["model_bwd"].pop()
         return None
-    check(rc, "stg_model_step")
     return y, losses, total[0], _grad_views(grad, [tuple(p.shape) for p in params], dead, holder)
 
 
@@ -553,9 +568,8 @@ class _BivariateNLL(torch.autograd.Function):
         loss = torch.empty(n, device=pred.device, dtype=torch.float32)
         need = ctx.needs_input_grad[0]
         grad = torch.empty((n, 5, p, v), device=pred.device, dtype=torch.float32) if need else None
-        sn, sp, sv, sf = pred.stride()
-        check(lib().stg_nll_fwd(ptr(pred), sn, sf, sp, sv, ptr(target), ptr(peds), None, n, p, v, ptr(loss), ptr(grad),
-                                stream_ptr()), "stg_nll_fwd")
+        call("stg_nll_fwd", pred=ptr(pred), **_strides("p", pred, "npvf"), target=ptr(target), num_peds=ptr(peds),
+             grad_scale=None, N=n, P=p, V=v, loss=ptr(loss), grad=ptr(grad))
         ctx.grad = grad
         return loss
 
@@ -565,7 +579,7 @@ class _BivariateNLL(torch.autograd.Function):
         n, _, p, v = grad.shape
         gloss = gloss.to(torch.float32).contiguous()
         out = torch.empty_like(grad)
-        check(lib().stg_nll_bwd(ptr(grad), ptr(gloss), n, p, v, ptr(out), stream_ptr()), "stg_nll_bwd")
+        call("stg_nll_bwd", grad=ptr(grad), gloss=ptr(gloss), N=n, P=p, V=v, out=ptr(out))
         # (N,5,P,V) buffer viewed in the caller's (N,P,V,5) index order
         return out.permute(0, 2, 3, 1), None, None
 
@@ -586,17 +600,15 @@ def bivariate_nll_with_grad(y, target, num_peds=None, weights=None):
     loss = torch.empty(n, device=y.device, dtype=torch.float32)
     grad = torch.empty((n, 5, p, v), device=y.device, dtype=torch.float32)
     w = weights.to(torch.float32).contiguous() if weights is not None else None
-    sn, sf, sp, sv = y.stride()
-    check(lib().stg_nll_fwd(ptr(y), sn, sf, sp, sv, ptr(target), ptr(peds), ptr(w), n, p, v, ptr(loss), ptr(grad),
-                            stream_ptr()), "stg_nll_fwd")
+    call("stg_nll_fwd", pred=ptr(y), **_strides("p", y, "nfpv"), target=ptr(target), num_peds=ptr(peds),
+         grad_scale=ptr(w), N=n, P=p, V=v, loss=ptr(loss), grad=ptr(grad))
     return loss, grad
 
 
 def sgd_step(flat_params, flat_grads, lr):
     """p -= lr * g on the flat buffers (train.py:197 SGD without momentum)."""
     require_gpu(flat_params, flat_grads)
-    check(lib().stg_sgd_step(ptr(flat_params), ptr(flat_grads), flat_params.numel(), float(lr), stream_ptr()),
-          "stg_sgd_step")
+    call("stg_sgd_step", params=ptr(flat_params), grads=ptr(flat_grads), count=flat_params.numel(), lr=float(lr))
 
 
 def optim_step(flat_params, flat_grads, lr, max_norm=None, lr_dev=None, grad_norm=None):
@@ -604,9 +616,8 @@ def optim_step(flat_params, flat_grads, lr, max_norm=None, lr_dev=None, grad_nor
     (1-element device tensor) overrides `lr` -- the form a captured hipGraph needs to follow StepLR; `grad_norm`
     (1-element device tensor) receives the unclipped gradient norm.  The gradients are scaled in place."""
     require_gpu(flat_params, flat_grads)
-    check(lib().stg_optim_step(ptr(flat_params), ptr(flat_grads), flat_params.numel(), ptr(lr_dev), float(lr),
-                               float(max_norm) if max_norm is not None else 0.0, ptr(grad_norm), stream_ptr()),
-          "stg_optim_step")
+    call("stg_optim_step", params=ptr(flat_params), grads=ptr(flat_grads), count=flat_params.numel(), lr_dev=ptr(lr_dev),
+         lr=float(lr), max_norm=float(max_norm) if max_norm is not None else 0.0, grad_norm=ptr(grad_norm))
 
 
 def train_tail(rec, losses, weights, flat_params, flat_grads, lr, max_norm=None, lr_dev=None):
@@ -615,10 +626,10 @@ def train_tail(rec, losses, weights, flat_params, flat_grads, lr, max_norm=None,
     require_gpu(losses, flat_params, flat_grads)
     w = weights.to(torch.float32).contiguous() if weights is not None else None
     out = torch.empty(1, device=losses.device, dtype=torch.float32)
-    check(lib().stg_train_tail(ctypes.byref(rec.desc), ptr(rec.stats), ptr(rec.peds), rec.n, ptr(rec.flat_buffers),
-                               _ptr_array(rec.nbt), len(rec.nbt), ptr(losses), ptr(w), ptr(out), ptr(flat_params),
-                               ptr(flat_grads), flat_params.numel(), ptr(lr_dev), float(lr),
-                               float(max_norm) if max_norm is not None else 0.0, None, stream_ptr()), "stg_train_tail")
+    call("stg_train_tail", d=ctypes.byref(rec.desc), stats=ptr(rec.stats), num_peds=ptr(rec.peds), N=rec.n,
+         buffers=ptr(rec.flat_buffers), nbt=_ptr_array(rec.nbt), n_bn=len(rec.nbt), losses=ptr(losses), weights=ptr(w),
+         total=ptr(out), params=ptr(flat_params), grads=ptr(flat_grads), count=flat_params.numel(), lr_dev=ptr(lr_dev),
+         lr=float(lr), max_norm=float(max_norm) if max_norm is not None else 0.0, grad_norm=None)
     return out[0]
 
 
@@ -627,17 +638,18 @@ def dp_pack(flat_grad, bn_before, bn_after, num_peds, n_scenes, momentum, rank, 
     all-reduces (stg_dp_pack).  pack: n_params + world * (n_buffers + 1) floats."""
     require_gpu(flat_grad, bn_before, bn_after, pack)
     peds = peds_arg(num_peds, n_scenes, flat_grad.device)
-    check(lib().stg_dp_pack(ptr(flat_grad), ptr(bn_before), ptr(bn_after), ptr(peds), int(n_scenes), float(momentum),
-                            int(rank), int(world), flat_grad.numel(), bn_before.numel(), ptr(pack), stream_ptr()),
-          "stg_dp_pack")
+    call("stg_dp_pack", grads=ptr(flat_grad), bn_before=ptr(bn_before), bn_after=ptr(bn_after), num_peds=ptr(peds),
+         N=int(n_scenes), momentum=float(momentum), rank=int(rank), world=int(world), n_params=flat_grad.numel(),
+         n_buffers=bn_before.numel(), pack=ptr(pack))
 
 
 def dp_fold(pack, bn_before, momentum, rank, world, n_params, buffers, nbt=()):
     """the exact sequential fold of the running statistics over the ranks from the all-reduced pack (stg_dp_fold);
     `nbt` (the num_batches_tracked tensors) also receive the other ranks' scene counts from the pack."""
     require_gpu(pack, bn_before, buffers)
-    check(lib().stg_dp_fold(ptr(pack), ptr(bn_before), float(momentum), int(rank), int(world), int(n_params),
-                            bn_before.numel(), ptr(buffers), _ptr_array(nbt), len(nbt), stream_ptr()), "stg_dp_fold")
+    call("stg_dp_fold", pack=ptr(pack), bn_before=ptr(bn_before), momentum=float(momentum), rank=int(rank),
+         world=int(world), n_params=int(n_params), n_buffers=bn_before.numel(), buffers=ptr(buffers), nbt=_ptr_array(nbt),
+         n_bn=len(nbt))
 
 
 def weighted_sum(values, weights=None):
@@ -646,7 +658,7 @@ def weighted_sum(values, weights=None):
     values = values.contiguous()
     w = weights.to(torch.float32).contiguous() if weights is not None else None
     out = torch.empty(1, device=values.device, dtype=torch.float32)
-    check(lib().stg_weighted_sum(ptr(values), ptr(w), values.numel(), ptr(out), stream_ptr()), "stg_weighted_sum")
+    call("stg_weighted_sum", values=ptr(values), weights=ptr(w), N=values.numel(), out=ptr(out))
     return out[0]
 
 
@@ -671,6 +683,13 @@ def sample_args(what, y, k, obs_last, noise, seed_dev=None):
     return y, obs_last, noise, n, p, v
 
 
+def _sampler_head(y, obs_last, peds, noise, seed, seed_dev, k):
+    """What stg_sample_trajectories and stg_sample_risk take alike: the model output, the draws and the sizes."""
+    n, _, p, v = y.shape
+    return dict(pred=ptr(y), **_strides("p", y, "nfpv"), obs_last=ptr(obs_last), num_peds=ptr(peds), noise=ptr(noise),
+                seed=seed_u64(seed), seed_dev=ptr(seed_dev), N=n, P=p, V=v, K=k)
+
+
 def best_of_k(y, target_rel, obs_last=None, num_peds=None, k=20, noise=None, seed=0):
     """Evaluation tail of test.py:59-123 on the device: y (N,5,P,V) model output (any strides), target_rel
     (N,P,V,2), obs_last (N,V,2) or None, noise (K,N,P,V,2) standard normals or None (in-kernel Philox stream keyed
@@ -684,10 +703,8 @@ def best_of_k(y, target_rel, obs_last=None, num_peds=None, k=20, noise=None, see
     peds = peds_arg(num_peds, n, y.device)
     ade = torch.empty((n, v), device=y.device, dtype=torch.float32)
     fde = torch.empty((n, v), device=y.device, dtype=torch.float32)
-    sn, sf, sp, sv = y.stride()
-    check(lib().stg_bestofk_eval(ptr(y), sn, sf, sp, sv, ptr(target_rel), ptr(obs_last), ptr(peds), ptr(noise),
-                                 seed_u64(seed), n, p, v, k, ptr(ade), ptr(fde), stream_ptr()),
-          "stg_bestofk_eval")
+    call("stg_bestofk_eval", pred=ptr(y), **_strides("p", y, "nfpv"), target_rel=ptr(target_rel), obs_last=ptr(obs_last),
+         num_peds=ptr(peds), noise=ptr(noise), seed=seed_u64(seed), N=n, P=p, V=v, K=k, ade=ptr(ade), fde=ptr(fde))
     return ade, fde
 
 
@@ -757,10 +774,10 @@ def dist_metrics(v_pred, mean, samples, truth, num_peds=None, kde_floor=20.0, ou
                 raise ValueError("dist_metrics: out.%s does not fit this call (%s)"
                                  % (name, "None" if w is None else "contiguous %s %s" % (w.dtype, tuple(w.shape))))
     peds = peds_arg(num_peds, n, v_pred.device)
-    check(lib().stg_dist_metrics(ptr(v_pred), *v_pred.stride(), ptr(mean), ptr(samples), ptr(truth), ptr(peds), n, p, v,
-                                 k, ctypes.c_float(float(kde_floor)), ptr(cov), *[ptr(o) for o in out],
-                                 *[ptr(x) for x in (ref_errors or (None, None))], stream_ptr()),
-          "stg_dist_metrics")
+    ade_ref, fde_ref = ref_errors or (None, None)
+    call("stg_dist_metrics", v_pred=ptr(v_pred), **_strides("p", v_pred, "nfpv"), mean=ptr(mean), samples=ptr(samples),
+         truth=ptr(truth), num_peds=ptr(peds), N=n, P=p, V=v, K=k, kde_floor=float(kde_floor), cov=ptr(cov),
+         **{name: ptr(o) for name, o in out._asdict().items()}, ade_ref=ptr(ade_ref), fde_ref=ptr(fde_ref))
     return out
 
 
@@ -778,9 +795,7 @@ def calib_buffers(n, p, v, device):
     """Empty outputs and the scratch buffer of calib_fit on n scenes: (CalibFit, ws uint8)."""
     def e(dtype, *shape):
         return torch.empty(shape, device=device, dtype=dtype)
-    nbytes = lib().stg_calib_fit_ws_bytes(n, p, v) if str(device) != "meta" else 0
-    if nbytes < 0:
-        check(int(nbytes), "stg_calib_fit_ws_bytes")
+    nbytes = _size("stg_calib_fit_ws_bytes", N=n, P=p, V=v) if str(device) != "meta" else 0
     # (float64 storage: the scratch buffer is 8-byte aligned whatever the allocator hands out)
     ws = torch.empty(((nbytes + 7) // 8,), device=device, dtype=torch.float64)
     return CalibFit(e(torch.float32, p), e(torch.float32, p, 2), e(torch.int32, p), e(torch.float64, p, 3),
@@ -829,9 +844,9 @@ def calib_fit(v_pred, mean, truth, num_peds=None, mode="coverage", level=0.9, ou
         out.flags.fill_(CALIB_EMPTY)
         out.stats.zero_()
         return out
-    check(lib().stg_calib_fit(ptr(v_pred), *v_pred.stride(), ptr(mean), ptr(truth), ptr(peds), n, p, v,
-                              CALIB_MODES[mode], ctypes.c_float(level), *[ptr(o) for o in out], ptr(ws),
-                              ws.numel() * ws.element_size(), stream_ptr()), "stg_calib_fit")
+    call("stg_calib_fit", v_pred=ptr(v_pred), **_strides("p", v_pred, "nfpv"), mean=ptr(mean), truth=ptr(truth),
+         num_peds=ptr(peds), N=n, P=p, V=v, mode=CALIB_MODES[mode], level=level,
+         **{name: ptr(o) for name, o in out._asdict().items()}, ws=ptr(ws), ws_bytes=ws.numel() * ws.element_size())
     return out
 
 
@@ -856,9 +871,9 @@ def calib_apply(v_pred, shift, out=None):
         raise ValueError("calib_apply: shift must be a contiguous float32 (%d,) tensor" % p)
     if out is not None and (tuple(out.shape) != (n, 5, p, v) or out.dtype != torch.float32):
         raise ValueError("calib_apply: out must be a float32 %s tensor" % ((n, 5, p, v),))
-    o_strides = out.stride() if out is not None else (0, 0, 0, 0)
-    check(lib().stg_calib_apply(ptr(v_pred), *v_pred.stride(), ptr(shift), n, p, v, ptr(out), *o_strides,
-                                stream_ptr()), "stg_calib_apply")
+    o_strides = _strides("o", out, "nfpv") if out is not None else dict(o_sn=0, o_sf=0, o_sp=0, o_sv=0)
+    call("stg_calib_apply", v_pred=ptr(v_pred), **_strides("p", v_pred, "nfpv"), shift=ptr(shift), N=n, P=p, V=v,
+         out=ptr(out), **o_strides)
     return v_pred if out is None else out
 
 
@@ -882,11 +897,8 @@ def sample_trajectories(y, obs_last=None, num_peds=None, k=20, noise=None, seed=
         samples = torch.empty((k, n, p, v, 2), device=y.device, dtype=torch.float32)
     if mean is None:
         mean = torch.empty((n, p, v, 2), device=y.device, dtype=torch.float32)
-    sn, sf, sp, sv = y.stride()
-    check(lib().stg_sample_trajectories(ptr(y), sn, sf, sp, sv, ptr(obs_last), ptr(peds), ptr(noise),
-                                        seed_u64(seed), ptr(seed_dev), n, p, v, k,
-                                        ptr(samples) if k > 0 else None, ptr(mean), stream_ptr()),
-          "stg_sample_trajectories")
+    call("stg_sample_trajectories", **_sampler_head(y, obs_last, peds, noise, seed, seed_dev, k),
+         samples=ptr(samples) if k > 0 else None, mean=ptr(mean))
     return samples, mean
 
 
@@ -962,13 +974,9 @@ def sample_risk(y, obs_last=None, num_peds=None, k=20, radius=None, zones=None, 
                 raise ValueError("sample_risk: out.%s does not fit this call (%s)"
                                  % (name, "None" if w is None else "contiguous int32 %s" % (tuple(w.shape),)))
     peds = peds_arg(num_peds, n, y.device)
-    sn, sf, sp, sv = y.stride()
-    check(lib().stg_sample_risk(ptr(y), sn, sf, sp, sv, ptr(obs_last), ptr(peds), ptr(noise),
-                                seed_u64(seed), ptr(seed_dev), n, p, v, k,
-                                ctypes.c_float(radius if radius is not None else 0.0), ptr(zones), z_sn, z,
-                                ptr(out.conflict), ptr(out.conflict_any), ptr(out.partner), ptr(out.pair),
-                                ptr(out.zone_any), ptr(out.zone_count), ptr(out.ped_zone), stream_ptr()),
-          "stg_sample_risk")
+    call("stg_sample_risk", **_sampler_head(y, obs_last, peds, noise, seed, seed_dev, k),
+         radius=radius if radius is not None else 0.0, zones=ptr(zones), z_sn=z_sn, Z=z,
+         **{name: ptr(o) for name, o in out._asdict().items() if name != "k"})
     return out
 
 
@@ -1058,13 +1066,14 @@ def _score_out_fits(what, out, fresh, device):
     return out
 
 
-def _score_tail(structs, sampled, state, out, thr, mean, v_pred, samples, ids, num_peds, p, v, k, q, *rp):
-    """The arguments every score entry point ends on, from the prediction to the stream (`rp`: the timed pair's Rp)."""
+def _score_tail(structs, sampled, state, out, thr, mean, v_pred, samples, ids, num_peds, p, v, k, q):
+    """The arguments every score entry point takes alike: the prediction, its sizes, the state and the outputs."""
     st = structs[0](*[None if (x is None or (k == 0 and name in sampled)) else x.data_ptr()
                       for name, x in zip(state._fields, state)])
     so = structs[1](*[None if o is None else o.data_ptr() for o in out])
-    return (ptr(mean), ptr(v_pred), *v_pred.stride(), ptr(samples) if k else None, ptr(ids), ptr(num_peds), p, v, k, *rp,
-            ctypes.byref(st), ptr(thr) if q else None, q, ctypes.byref(so), stream_ptr())
+    return dict(mean=ptr(mean), v_pred=ptr(v_pred), **_strides("p", v_pred, "nfpv"), samples=ptr(samples) if k else None,
+                ids=ptr(ids), num_peds=ptr(num_peds), P=p, V=v, K=k, state=ctypes.byref(st), thr=ptr(thr) if q else None,
+                Q=q, out=ctypes.byref(so))
 
 
 def score_thresholds(levels):
@@ -1135,19 +1144,18 @@ def score_push(state, thr, mean, v_pred, samples, ids, num_peds, det_id, det_xy,
     out = _score_out_fits("score_push", out, lambda dev: score_buffers(ns, p, v, dev, k > 0), mean.device)
     pred = _score_tail((_lib.ScoreState, _lib.ScoreOut), _SCORE_SAMPLED, state, out, thr, mean, v_pred, samples, ids,
                        num_peds, p, v, k, q)
+    det = dict(det_id=_dev_ptr(det_id), det_xy=_dev_ptr(det_xy), M_max=int(m_max), scale=scale)
     if (det_count is None) == (det_start is None):
         raise ValueError("score_push: pass det_count (one stream) or det_start and pushed (a packed tick)")
     if det_count is not None:
         if ns != 1:
             raise ValueError("score_push: det_count serves one stream, the prediction holds %d" % ns)
-        check(lib().stg_score_push(_dev_ptr(det_id), _dev_ptr(det_xy), _dev_ptr(det_count), int(m_max),
-                                   ctypes.c_double(scale), *pred), "stg_score_push")
+        call("stg_score_push", **det, det_count=_dev_ptr(det_count), **pred)
     else:
         if pushed is None or m_total is None:
             raise ValueError("score_push: det_start needs pushed and m_total")
-        check(lib().stg_score_push_streams(_dev_ptr(det_id), int(id_stride), _dev_ptr(det_xy), int(xy_stride),
-                                           int(m_total), _dev_ptr(det_start), _dev_ptr(pushed), ns, int(m_max),
-                                           ctypes.c_double(scale), *pred), "stg_score_push_streams")
+        call("stg_score_push_streams", **det, id_stride=int(id_stride), xy_stride=int(xy_stride), M_total=int(m_total),
+             det_start=_dev_ptr(det_start), pushed=_dev_ptr(pushed), NS=ns, **pred)
     return out
 
 
@@ -1225,18 +1233,18 @@ def score_timed_push(state, thr, mean, v_pred, samples, ids, num_peds, tracks, s
     _score_state_fits("score_timed_push", _SCORE_TIMED_SAMPLED, state, _score_timed_shapes(ns, p, v, k, q, rp), k, thr, q)
     _score_limits("score_timed_push", V=v, K=k, P=p, Q=q, pending=rp)
     out = _score_out_fits("score_timed_push", out, lambda dev: score_timed_buffers(ns, p, q, dev), mean.device)
-    sizes = (s, r, ctypes.c_double(scale), int(step), int(max_dt))
+    read = dict(slot_id=ptr(slot_id), t_ring=ptr(t_ring), xy_ring=ptr(xy_ring), slot_head=ptr(slot_head), clock=ptr(clock),
+                head_flags=ptr(head_flags), S=s, R=r, scale=scale, step=int(step), max_dt=int(max_dt), Rp=rp)
     pred = _score_tail((_lib.ScoreTimedState, _lib.ScoreTimedOut), _SCORE_TIMED_SAMPLED, state, out, thr, mean, v_pred,
-                       samples, ids, num_peds, p, v, k, q, rp)
+                       samples, ids, num_peds, p, v, k, q)
     if pushed is None:
         if ns != 1:
             raise ValueError("score_timed_push: %d streams need `pushed`" % ns)
-        check(lib().stg_score_push_timed(*map(ptr, tracks), *sizes, *pred), "stg_score_push_timed")
+        call("stg_score_push_timed", **read, **pred)
     else:
         if pushed.numel() != ns or pushed.dtype != torch.int32 or not pushed.is_cuda:
             raise ValueError("score_timed_push: pushed must be an int32 (NS,) device tensor")
-        check(lib().stg_score_push_streams_timed(*map(ptr, tracks), ptr(pushed), ns, *sizes, *pred),
-              "stg_score_push_streams_timed")
+        call("stg_score_push_streams_timed", **read, pushed=ptr(pushed), NS=ns, **pred)
     return out
 
 
@@ -1255,5 +1263,5 @@ def scene_order(num_peds, v):
         if n == 1:
             key_start[: int(v) - max(0, min(int(v), int(peds[0]))) + 1] = 0
         return order, key_start
-    check(lib().stg_scene_order(ptr(peds), n, int(v), ptr(order), ptr(key_start), stream_ptr()), "stg_scene_order")
+    call("stg_scene_order", num_peds=ptr(peds), N=n, V=int(v), order=ptr(order), key_start=ptr(key_start))
     return order, key_start

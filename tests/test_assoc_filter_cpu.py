@@ -281,41 +281,30 @@ def L():
 
 def test_the_filtered_association_header_its_binding_and_the_exports(L):
     """include/stgcnn_hip_assoc_filter.h -- which stgcnn_hip.h includes inside its extern "C" block, behind the N12
-    header -- against _lib._SIGNATURES_ASSOC_FILTER: the same names, every return and parameter type, the symbols
-    exported, disjoint from the other tables, ABI version 8."""
+    header -- as _lib binds it from that header (tests/test_lib_cpu.py checks the binding of all eight): its two entry
+    points by name, nothing but void *, int, int64_t and double among their parameters, four more of them than their
+    timed twins take, ABI version 8."""
     from social_stgcnn_amd import _lib
     main = open(os.path.join(ROOT, "include", "stgcnn_hip.h")).read()
     inc = '#include "stgcnn_hip_assoc_filter.h"'
     assert re.search("^" + re.escape(inc) + "$", main, re.M)
     assert main.index('extern "C" {') < main.index('#include "stgcnn_hip_assoc_time.h"') < main.index(inc) \
         < main.rindex("#ifdef __cplusplus")
-    hdr = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "stgcnn_hip_assoc_filter.h")).read(), flags=re.S)
-    hdr = "\n".join(line for line in hdr.split("\n") if not line.lstrip().startswith("#"))
-    scalars = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "double": ctypes.c_double}
-
-    def ctype(decl, named):
-        words = decl.replace("*", " * ").split()
-        stars = words.count("*")
-        words = [w for w in words if w not in ("*", "const")]
-        assert len(words) == (2 if named else 1) and stars <= 1, decl
-        return ctypes.c_void_p if stars else scalars[words[0]]
-    protos = re.findall(r"([A-Za-z_][\w\s\*]*?)\b(stg_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", hdr)
-    assert [name for _, name, _ in protos] == ["stg_associate_filtered", "stg_associate_streams_filtered"]
-    assert {name for _, name, _ in protos} == set(_lib._SIGNATURES_ASSOC_FILTER)
-    assert not set(_lib._SIGNATURES_ASSOC_FILTER) & (set(_lib._SIGNATURES) | set(_lib._SIGNATURES_SCORE_TIME) |
-                                                     set(_lib._SIGNATURES_HARVEST) | set(_lib._SIGNATURES_HARVEST_TIME) |
-                                                     set(_lib._SIGNATURES_ASSOC_TIME))
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    for ret, name, params in protos:
-        res, bound = _lib._SIGNATURES_ASSOC_FILTER[name]
-        assert ctype(ret, False) == res, name
-        args = [ctype(q, True) for q in params.split(",")]
-        assert args == list(bound), (name, [i for i, (x, y) in enumerate(zip(args, bound)) if x != y], len(args), len(bound))
-        assert hasattr(raw, name) and getattr(L, name).argtypes == list(bound), name
+    protos = _lib.parse_header(open(os.path.join(ROOT, "include", "stgcnn_hip_assoc_filter.h")).read())
+    assert [p.name for p in protos] == ["stg_associate_filtered", "stg_associate_streams_filtered"]
+    for p in protos:
+        fn = getattr(L, p.name)
+        assert _lib.PROTOTYPES[p.name] == p and len(fn.argtypes) == len(p.params), p.name
+        assert set(fn.argtypes) <= {ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_double}, p.name
+        assert fn.restype == ctypes.c_int, p.name
     # the filtered entry points are the timed ones with trk_cov behind trk_t and five doubles in the place of two
     for name, twin in (("stg_associate_filtered", "stg_associate_timed"),
                        ("stg_associate_streams_filtered", "stg_associate_streams_timed")):
-        assert len(_lib._SIGNATURES_ASSOC_FILTER[name][1]) == len(_lib._SIGNATURES_ASSOC_TIME[twin][1]) + 4
+        mine, theirs = ([n for n, _ in _lib.PROTOTYPES[e].params] for e in (name, twin))
+        assert len(getattr(L, name).argtypes) == len(mine) == len(getattr(L, twin).argtypes) + 4 == len(theirs) + 4
+        at, k = theirs.index("gate2"), theirs.index("trk_t") + 1
+        assert theirs[at:at + 2] == ["gate2", "gate_new2"] and mine[at + 1:at + 6] == ["r", "qa", "v0", "n2", "gmax2"]
+        assert mine[:at + 1] == theirs[:k] + ["trk_cov"] + theirs[k:at] and mine[at + 6:] == theirs[at + 2:]
     assert L.stg_abi_version() == _lib.ABI_VERSION == 8
 
 

@@ -214,8 +214,9 @@ def L():
 
 def test_the_timed_association_header_its_binding_and_the_exports(L):
     """include/stgcnn_hip_assoc_time.h -- which stgcnn_hip.h includes inside its extern "C" block, behind the other
-    part-headers -- against _lib._SIGNATURES_ASSOC_TIME: the same names, every return and parameter type, the symbols
-    exported, disjoint from the other tables, the new flag beside the old one, ABI version 8."""
+    part-headers -- as _lib binds it from that header (tests/test_lib_cpu.py checks the binding of all eight): its two
+    entry points by name, nothing but void *, int, int64_t and double among their parameters, the new flag beside the old
+    one, ABI version 8."""
     from social_stgcnn_amd import _lib
     main = open(os.path.join(ROOT, "include", "stgcnn_hip.h")).read()
     inc = '#include "stgcnn_hip_assoc_time.h"'
@@ -224,28 +225,13 @@ def test_the_timed_association_header_its_binding_and_the_exports(L):
         < main.rindex("#ifdef __cplusplus")
     raw_hdr = open(os.path.join(ROOT, "include", "stgcnn_hip_assoc_time.h")).read()
     assert re.search(r"^#define STG_ASSOC_TIME_ORDER 2\b", raw_hdr, re.M) and re.search(r"^#define STG_ASSOC_FULL 1\b", main, re.M)
-    hdr = re.sub(r"/\*.*?\*/", " ", raw_hdr, flags=re.S)
-    hdr = "\n".join(line for line in hdr.split("\n") if not line.lstrip().startswith("#"))
-    scalars = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "double": ctypes.c_double}
-
-    def ctype(decl, named):
-        words = decl.replace("*", " * ").split()
-        stars = words.count("*")
-        words = [w for w in words if w not in ("*", "const")]
-        assert len(words) == (2 if named else 1) and stars <= 1, decl
-        return ctypes.c_void_p if stars else scalars[words[0]]
-    protos = re.findall(r"([A-Za-z_][\w\s\*]*?)\b(stg_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", hdr)
-    assert [name for _, name, _ in protos] == ["stg_associate_timed", "stg_associate_streams_timed"]
-    assert {name for _, name, _ in protos} == set(_lib._SIGNATURES_ASSOC_TIME)
-    assert not set(_lib._SIGNATURES_ASSOC_TIME) & (set(_lib._SIGNATURES) | set(_lib._SIGNATURES_SCORE_TIME) |
-                                                   set(_lib._SIGNATURES_HARVEST) | set(_lib._SIGNATURES_HARVEST_TIME))
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    for ret, name, params in protos:
-        res, bound = _lib._SIGNATURES_ASSOC_TIME[name]
-        assert ctype(ret, False) == res, name
-        args = [ctype(q, True) for q in params.split(",")]
-        assert args == list(bound), (name, [i for i, (x, y) in enumerate(zip(args, bound)) if x != y], len(args), len(bound))
-        assert hasattr(raw, name) and getattr(L, name).argtypes == list(bound), name
+    protos = _lib.parse_header(raw_hdr)
+    assert [p.name for p in protos] == ["stg_associate_timed", "stg_associate_streams_timed"]
+    for p in protos:
+        fn = getattr(L, p.name)
+        assert _lib.PROTOTYPES[p.name] == p and len(fn.argtypes) == len(p.params), p.name
+        assert set(fn.argtypes) <= {ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_double}, p.name
+        assert fn.restype == ctypes.c_int, p.name
     assert L.stg_abi_version() == _lib.ABI_VERSION == 8
 
 

@@ -26,8 +26,9 @@ def L():
 
 def test_the_calib_header_its_binding_and_the_export(L):
     """include/stgcnn_hip_calib.h -- which stgcnn_hip.h includes behind the metrics header, inside its extern "C" block
-    -- against _lib._SIGNATURES_CALIB, every type mapped to ctypes; the symbols exported; the constants of the header
-    are those of ops and of the restatement; the ABI version 8."""
+    -- as _lib binds it from that header (tests/test_lib_cpu.py checks the binding of all eight): its three entry points
+    by name, nothing but void * and four scalar types among their parameters; the constants of the header are those of
+    ops and of the restatement; the ABI version 8."""
     from social_stgcnn_amd import _lib, ops
     main = open(os.path.join(ROOT, "include", "stgcnn_hip.h")).read()
     assert re.search(r'^#include "stgcnn_hip_calib.h"$', main, re.M)
@@ -40,30 +41,13 @@ def test_the_calib_header_its_binding_and_the_export(L):
         "STG_CALIB_MOMENT": ops.CALIB_MODES["moment"], "STG_CALIB_COVERAGE": ops.CALIB_MODES["coverage"],
         "STG_CALIB_LOW": ops.CALIB_LOW, "STG_CALIB_HIGH": ops.CALIB_HIGH, "STG_CALIB_EMPTY": ops.CALIB_EMPTY}
     assert (cn.MOMENT, cn.COVERAGE, cn.LOW, cn.HIGH, cn.EMPTY) == (0, 1, ops.CALIB_LOW, ops.CALIB_HIGH, ops.CALIB_EMPTY)
-    hdr = re.sub(r"/\*.*?\*/", " ", raw_hdr, flags=re.S)
-    hdr = "\n".join(line for line in hdr.split("\n") if not line.lstrip().startswith("#"))
-    scalars = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": ctypes.c_int64, "double": ctypes.c_double,
-               "float": ctypes.c_float}
-
-    def ctype(decl, named):
-        words = decl.replace("*", " * ").split()
-        stars = words.count("*")
-        words = [w for w in words if w not in ("*", "const", "struct")]
-        assert len(words) == (2 if named else 1) and stars <= 1, decl
-        return ctypes.c_void_p if stars else scalars[words[0]]
-    protos = re.findall(r"([A-Za-z_][\w\s\*]*?)\b(stg_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", hdr)
-    assert [name for _, name, _ in protos] == ["stg_calib_fit_ws_bytes", "stg_calib_fit", "stg_calib_apply"] \
-        == list(_lib._SIGNATURES_CALIB)
-    others = [_lib._SIGNATURES, _lib._SIGNATURES_SCORE_TIME, _lib._SIGNATURES_HARVEST, _lib._SIGNATURES_HARVEST_TIME,
-              _lib._SIGNATURES_ASSOC_TIME, _lib._SIGNATURES_ASSOC_FILTER, _lib._SIGNATURES_METRICS]
-    assert not any(set(_lib._SIGNATURES_CALIB) & set(t) for t in others)
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    for ret, name, params in protos:
-        res, bound = _lib._SIGNATURES_CALIB[name]
-        assert ctype(ret, False) == res, name
-        args = [ctype(q, True) for q in params.split(",")]
-        assert args == list(bound), (name, [i for i, (x, y) in enumerate(zip(args, bound)) if x != y], len(args), len(bound))
-        assert hasattr(raw, name) and getattr(L, name).argtypes == list(bound), name
+    protos = _lib.parse_header(raw_hdr)
+    assert [p.name for p in protos] == ["stg_calib_fit_ws_bytes", "stg_calib_fit", "stg_calib_apply"]
+    for p in protos:
+        fn = getattr(L, p.name)
+        assert _lib.PROTOTYPES[p.name] == p and len(fn.argtypes) == len(p.params), p.name
+        assert set(fn.argtypes) <= {ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_double, ctypes.c_float}, p.name
+        assert fn.restype == (ctypes.c_int64 if p.name == "stg_calib_fit_ws_bytes" else ctypes.c_int), p.name
     assert L.stg_abi_version() == _lib.ABI_VERSION == 8
 
 

@@ -120,35 +120,22 @@ def test_clip_and_collinear_samples():
 
 
 def test_the_metrics_header_its_binding_and_the_export(L):
-    """include/stgcnn_hip_metrics.h -- which stgcnn_hip.h includes -- against _lib._SIGNATURES_METRICS, every type mapped
-    to ctypes as test_score_time_cpu.py maps its header's; the symbol exported; the ABI version 8."""
+    """include/stgcnn_hip_metrics.h -- which stgcnn_hip.h includes -- as _lib binds it from that header
+    (tests/test_lib_cpu.py checks the binding of all eight): its one entry point by name, nothing but void * and four
+    scalar types among its parameters; the ABI version 8."""
     from social_stgcnn_amd import _lib
     main = open(os.path.join(ROOT, "include", "stgcnn_hip.h")).read()
     assert re.search(r'^#include "stgcnn_hip_metrics.h"$', main, re.M)
     assert main.index('#include "stgcnn_hip_metrics.h"') > main.index('extern "C" {')
     assert re.search(r"#define STG_ABI_VERSION 8\b", main)
     raw_hdr = open(os.path.join(ROOT, "include", "stgcnn_hip_metrics.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", " ", raw_hdr, flags=re.S)
-    hdr = "\n".join(line for line in hdr.split("\n") if not line.lstrip().startswith("#"))
-    scalars = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": ctypes.c_int64, "double": ctypes.c_double,
-               "float": ctypes.c_float}
-
-    def ctype(decl, named):
-        words = decl.replace("*", " * ").split()
-        stars = words.count("*")
-        words = [w for w in words if w not in ("*", "const", "struct")]
-        assert len(words) == (2 if named else 1) and stars <= 1, decl
-        return ctypes.c_void_p if stars else scalars[words[0]]
-    protos = re.findall(r"([A-Za-z_][\w\s\*]*?)\b(stg_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", hdr)
-    assert [name for _, name, _ in protos] == ["stg_dist_metrics"] == list(_lib._SIGNATURES_METRICS)
-    assert not set(_lib._SIGNATURES_METRICS) & set(_lib._SIGNATURES)
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    for ret, name, params in protos:
-        res, bound = _lib._SIGNATURES_METRICS[name]
-        assert ctype(ret, False) == res, name
-        args = [ctype(q, True) for q in params.split(",")]
-        assert args == list(bound), (name, [i for i, (x, y) in enumerate(zip(args, bound)) if x != y], len(args), len(bound))
-        assert hasattr(raw, name) and getattr(L, name).argtypes == list(bound), name
+    protos = _lib.parse_header(raw_hdr)
+    assert [p.name for p in protos] == ["stg_dist_metrics"]
+    for p in protos:
+        fn = getattr(L, p.name)
+        assert _lib.PROTOTYPES[p.name] == p and len(fn.argtypes) == len(p.params), p.name
+        assert set(fn.argtypes) <= {ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_double, ctypes.c_float}, p.name
+        assert fn.restype == ctypes.c_int, p.name
     assert L.stg_abi_version() == _lib.ABI_VERSION == 8
 
 

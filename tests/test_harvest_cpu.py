@@ -221,33 +221,20 @@ def test_from_device_argument_checks():
 # ---- 4. the C ABI ---------------------------------------------------------------------------------------------------------
 def test_the_harvest_header_its_binding_and_the_exports(L):
     """include/stgcnn_hip_harvest.h -- which stgcnn_hip.h includes inside its extern "C" block -- against
-    _lib._SIGNATURES_HARVEST: the same names, every return and parameter type, the symbols exported, ABI version 8."""
+    as _lib binds it from that header (tests/test_lib_cpu.py checks the binding of all eight): its two entry points by
+    name, nothing but void * and int among their parameters, ABI version 8, the limit."""
     from social_stgcnn_amd import _lib, frames
     main = open(os.path.join(ROOT, "include", "stgcnn_hip.h")).read()
     assert re.search(r'^#include "stgcnn_hip_harvest.h"$', main, re.M)
     assert main.index('extern "C" {') < main.index('#include "stgcnn_hip_harvest.h"') < main.rindex("#ifdef __cplusplus")
     raw_hdr = open(os.path.join(ROOT, "include", "stgcnn_hip_harvest.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", " ", raw_hdr, flags=re.S)
-    hdr = "\n".join(line for line in hdr.split("\n") if not line.lstrip().startswith("#"))
-    scalars = {"int": ctypes.c_int}
-
-    def ctype(decl, named):
-        words = decl.replace("*", " * ").split()
-        stars = words.count("*")
-        words = [w for w in words if w not in ("*", "const")]
-        assert len(words) == (2 if named else 1) and stars <= 1, decl
-        return ctypes.c_void_p if stars else scalars[words[0]]
-    protos = re.findall(r"([A-Za-z_][\w\s\*]*?)\b(stg_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", hdr)
-    assert [name for _, name, _ in protos] == ["stg_window_harvest", "stg_window_harvest_streams"]
-    assert {name for _, name, _ in protos} == set(_lib._SIGNATURES_HARVEST)
-    assert not set(_lib._SIGNATURES_HARVEST) & (set(_lib._SIGNATURES) | set(_lib._SIGNATURES_SCORE_TIME))
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    for ret, name, params in protos:
-        res, bound = _lib._SIGNATURES_HARVEST[name]
-        assert ctype(ret, False) == res, name
-        args = [ctype(q, True) for q in params.split(",")]
-        assert args == list(bound), (name, [i for i, (x, y) in enumerate(zip(args, bound)) if x != y], len(args), len(bound))
-        assert hasattr(raw, name) and getattr(L, name).argtypes == list(bound), name
+    protos = _lib.parse_header(raw_hdr)
+    assert [p.name for p in protos] == ["stg_window_harvest", "stg_window_harvest_streams"]
+    for p in protos:
+        fn = getattr(L, p.name)
+        assert _lib.PROTOTYPES[p.name] == p and len(fn.argtypes) == len(p.params), p.name
+        assert set(fn.argtypes) <= {ctypes.c_void_p, ctypes.c_int}, p.name
+        assert fn.restype == ctypes.c_int, p.name
     assert L.stg_abi_version() == _lib.ABI_VERSION == 8
     assert re.search(r"#define STG_HARVEST_MAX_STEPS 32\b", raw_hdr) and frames.MAX_WINDOW_STEPS == 32
 

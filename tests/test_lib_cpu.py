@@ -29,50 +29,159 @@ def test_header_symbols_are_exported(L):
     assert L.stg_abi_version() == _lib.ABI_VERSION
 
 
-def test_header_prototypes_match_the_binding():
-    """Every prototype of include/stgcnn_hip.h, its return and parameter types mapped to ctypes, equals the restype /
-    argtypes _lib binds it with: the header and _lib._SIGNATURES are two hand-written copies of the C ABI."""
+def _headers():
+    """(text of include/stgcnn_hip.h, {part header: text} for the part headers it includes, in its order)"""
+    inc = os.path.join(ROOT, "include")
+    main = open(os.path.join(inc, "stgcnn_hip.h")).read()
+    parts = re.findall(r'^#include "(stgcnn_hip_\w+\.h)"$', main, re.M)
+    assert sorted(os.listdir(inc)) == sorted(["stgcnn_hip.h"] + parts) and len(parts) == 7
+    return main, {f: open(os.path.join(inc, f)).read() for f in parts}
+
+
+def test_every_prototype_of_the_headers_is_bound(L):
+    """The eight headers are the only copy of the C ABI: _lib derives restype / argtypes and the parameter names from
+    them.  51 prototypes in include/stgcnn_hip.h and 65 with its seven part headers, every one bound with as many
+    argtypes as it has parameters and exported by the library; ABI version 8."""
     from social_stgcnn_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "stgcnn_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
-    hdr = re.sub(r"//[^\n]*", " ", hdr)
-    hdr = "\n".join(l for l in hdr.split("\n") if not l.lstrip().startswith("#"))
-    structs = {"stg_model_desc": ctypes.POINTER(_lib.ModelDesc), "stg_score_state": ctypes.POINTER(_lib.ScoreState),
-               "stg_score_out": ctypes.POINTER(_lib.ScoreOut), "stg_step_tail": ctypes.c_void_p}
-    scalars = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64,
-               "float": ctypes.c_float, "double": ctypes.c_double}
+    main, parts = _headers()
+    in_main = _lib.parse_header(main)
+    assert len(in_main) == 51 and [p.name for p in in_main] == list(_lib.EXPORTS), \
+        "%d prototypes parsed, 51 pinned: a new entry point changes this count on purpose" % len(in_main)
+    protos = in_main + [p for text in parts.values() for p in _lib.parse_header(text)]
+    assert len(protos) == 65 and len({p.name for p in protos}) == 65, \
+        "%d prototypes parsed, 65 pinned: a new entry point changes this count on purpose" % len(protos)
+    assert {p.name: p for p in protos} == _lib.PROTOTYPES
+    raw = ctypes.CDLL(_lib.LIB_PATH)
+    for p in protos:
+        assert hasattr(raw, p.name), p.name
+        fn = getattr(L, p.name)
+        assert fn.argtypes is not None and len(fn.argtypes) == len(p.params), p.name
+        assert list(fn.argtypes) == [_lib.ctype_of(c, p.name) for _, c in p.params], p.name
+        assert fn.restype == _lib.ctype_of(p.ret, p.name), p.name
+        assert len({n for n, _ in p.params}) == len(p.params), p.name
+    assert L.stg_abi_version() == _lib.ABI_VERSION == 8
 
-    def ctype(decl, named):
-        """`decl`: a C type, followed by the parameter's name when `named`"""
-        words = decl.replace("*", " * ").split()
-        stars = words.count("*")
-        words = [w for w in words if w not in ("*", "const", "struct")]
-        base = words[0]
-        assert len(words) == (2 if named else 1), decl
-        if stars == 0:
-            return scalars[base]
-        if base in structs:
-            assert stars == 1, decl
-            return structs[base]
-        if base == "char":
-            assert stars == 1, decl
-            return ctypes.c_char_p
-        if stars == 2:                     # void **, int64_t *const *: a host array of device pointers
-            assert base not in structs, decl
-            return ctypes.POINTER(ctypes.c_void_p)
-        assert stars == 1, decl
-        return ctypes.c_void_p
 
-    protos = re.findall(r"([A-Za-z_][\w\s\*]*?)\b(stg_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", hdr)
-    assert len(protos) == 51 and len({name for _, name, _ in protos}) == 51, \
-        "%d prototypes parsed, 51 pinned: a new entry point changes this count on purpose" % len(protos)
-    assert {name for _, name, _ in protos} == set(_lib._SIGNATURES)
-    for ret, name, params in protos:
-        args = [] if params.strip() == "void" else [ctype(p, True) for p in params.split(",")]
-        res, bound = _lib._SIGNATURES[name]
-        assert ctype(ret, False) == res, (name, ret, res)
-        assert args == list(bound), (name, [i for i, (a, b) in enumerate(zip(args, bound)) if a != b],
-                                     len(args), len(bound))
+SYNTHETIC = """
+/* a comment that holds a prototype:  int stg_in_a_comment(int n);  */
+#ifndef X_H
+#define STG_SOME_LIMIT 4            /* int stg_behind_a_define(int n); */
+typedef struct stg_model_desc { int32_t n_stgcnn; } stg_model_desc;
+int stg_every_kind(const stg_model_desc *d, int n, int32_t n32, int64_t n64, uint64_t seed,   // int stg_in_a_line(int n);
+                   float lr, double scale, const float *x, void *y, const int64_t *const *rows, void **events,
+                   const stg_score_state *state, const stg_score_out *out, const stg_step_tail *tail,
+                   const struct stg_score_timed_state *timed, stg_score_timed_out *timed_out, const char *text,
+                   void *stream);
+int64_t stg_a_size(void);
+const char *stg_a_text(void);
+#endif
+"""
+
+
+def test_parser_and_type_map_on_a_synthetic_header():
+    """One parameter of every kind the C ABI has -- each scalar, `const T *`, `T *const *`, each struct pointer, `char *`,
+    `void` -- against ctypes written out here; comments and preprocessor lines hold no prototype."""
+    from social_stgcnn_amd import _lib
+    void_p, c = ctypes.c_void_p, ctypes
+    protos = _lib.parse_header(SYNTHETIC)
+    assert [(p.name, p.ret) for p in protos] == [("stg_every_kind", "int"), ("stg_a_size", "int64_t"),
+                                                 ("stg_a_text", "const char *")]
+    assert protos[1].params == () and protos[2].params == ()
+    want = [("d", c.POINTER(_lib.ModelDesc)), ("n", c.c_int), ("n32", c.c_int), ("n64", c.c_int64), ("seed", c.c_uint64),
+            ("lr", c.c_float), ("scale", c.c_double), ("x", void_p), ("y", void_p), ("rows", c.POINTER(void_p)),
+            ("events", c.POINTER(void_p)), ("state", c.POINTER(_lib.ScoreState)), ("out", c.POINTER(_lib.ScoreOut)),
+            ("tail", void_p), ("timed", void_p), ("timed_out", void_p), ("text", c.c_char_p), ("stream", void_p)]
+    assert [n for n, _ in protos[0].params] == [n for n, _ in want]
+    assert [_lib.ctype_of(t, "stg_every_kind") for _, t in protos[0].params] == [t for _, t in want]
+    assert protos[0].params[0][1] == "const stg_model_desc *" and protos[0].params[9][1] == "const int64_t * const *"
+    assert [_lib.ctype_of(p.ret, p.name) for p in protos] == [c.c_int, c.c_int64, c.c_char_p]
+
+
+def test_the_load_refuses_what_it_cannot_bind():
+    """Each refusal names the prototype: a type outside the map, a parameter without a name, a name twice, a declared
+    symbol the library does not export, and a prototype declared in two headers."""
+    from social_stgcnn_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        _lib.build()
+    raw = ctypes.CDLL(_lib.LIB_PATH)
+    load = lambda *texts: _lib.bind(raw, _lib.collect(texts))       # noqa: E731
+    for text in ("int stg_abi_version(unsigned n);", "int stg_abi_version(long n);", "long stg_abi_version(void);",
+                 "int stg_abi_version(float **p, stg_model_desc **d);", "int stg_abi_version(stg_model_desc d);"):
+        with pytest.raises(_lib.HeaderError, match=r"stg_abi_version.*no ctypes type"):
+            load(text)
+    with pytest.raises(_lib.HeaderError, match=r"stg_abi_version: parameter 1, `float \*`"):
+        load("int stg_abi_version(int n, float *, void *stream);")
+    with pytest.raises(_lib.HeaderError, match=r"stg_abi_version: two parameters are called `n`"):
+        load("int stg_abi_version(int n, float *x, const float *n);")
+    with pytest.raises(_lib.HeaderError, match=r"stg_not_in_the_library is declared in the headers but not exported"):
+        load("int stg_abi_version(void);\nint stg_not_in_the_library(int n);")
+    one, two = "int stg_abi_version(void);\nint stg_twice(int n);", "const char *stg_last_error(void);\nint stg_twice(int n);"
+    with pytest.raises(_lib.HeaderError, match=r"stg_twice is declared twice"):
+        load(one, two)
+    assert sorted(load(one.split("\n")[0], two.split("\n")[0])) == ["stg_abi_version", "stg_last_error"]
+
+
+def _ragged_size_rows():
+    import json
+    rows = json.load(open(os.path.join(ROOT, "tests", "size_queries.json")))["rows"]
+    rows = [r for r in rows if r[1] != r[2]]
+    assert {(7, 64), (100, 32)} <= {(r[1], r[2]) for r in rows}
+    return rows
+
+
+def test_calls_go_by_parameter_name(L):
+    """_lib.call orders its keywords by the prototype: stg_model_ws_tail_floats with (V, N, d) in reversed order returns
+    the recorded value wherever N != V, which a call that ignored the names would not.  A missing name, an unknown one
+    and both together are a TypeError that names them, and the library is not entered: stg_last_error() stays."""
+    from social_stgcnn_amd import _lib, ops
+    distinct = 0
+    for f, n, v, tail, _, _ in _ragged_size_rows():
+        d = ops.make_desc(1, 5, 2, 5, 8, 12, 3, 2, False, True)
+        d.flags = f
+        assert _lib.call("stg_model_ws_tail_floats", V=v, N=n, d=ctypes.byref(d)) == tail, (f, n, v)
+        distinct += L.stg_model_ws_tail_floats(ctypes.byref(d), v, n) != tail
+    assert distinct > 100                                  # (the swapped call does give another value)
+    assert L.stg_adj_build(None, 0, 0, 0, 0, None, 1, 4, 8, 1, None, None, None) == -1
+    before = L.stg_last_error()
+    assert b"null" in before
+    r = ctypes.byref(d)
+    for kw, said in ((dict(d=r, N=7), "missing: V"), (dict(d=r, N=7, V=64, n=7), "unknown: n"),
+                     (dict(desc=r, N=7, V=64), "missing: d; unknown: desc"), (dict(), "missing: d, N, V")):
+        with pytest.raises(TypeError, match="^stg_model_ws_tail_floats: %s$" % said):
+            _lib.call("stg_model_ws_tail_floats", **kw)
+        assert L.stg_last_error() == before
+    with pytest.raises(TypeError, match="^stg_adj_build: missing: rel, .*, adj$"):      # (stream alone has a default)
+        _lib.call("stg_adj_build")
+    # a status is checked inside the call, a size query returns its value (a negative one included)
+    with pytest.raises(_lib.StatusError, match="stg_selftest_mfma failed .status -1.") as e:
+        _lib.call("stg_selftest_mfma", a=None, b=None, K=3, c=None, stream=None)
+    assert e.value.status == -1
+    bad = ops.make_desc(1, 5, 2, 5, 6, 12, 3, 2, False, False)
+    assert _lib.call("stg_model_param_count", d=ctypes.byref(bad)) == -2
+
+
+def test_a_prebound_call_is_complete_when_it_is_built(L):
+    """_lib.Bound: the fixed arguments and the names of the varying ones must together be the prototype's parameters
+    when it is built, not at the first launch; a launch names exactly the varying ones, in any order."""
+    from social_stgcnn_amd import _lib, ops
+    d = ops.make_desc(1, 5, 2, 5, 8, 12, 3, 2, False, True)
+    name, r = "stg_model_ws_tail_floats", ctypes.byref(d)
+    for varying, fixed, said in ((("N",), dict(d=r), "missing: V"), (("N", "V"), dict(), "missing: d"),
+                                 (("N", "V"), dict(d=r, T=8), "unknown: T"), (("N", "V"), dict(d=r, V=64), "repeated: V"),
+                                 (("N", "V", "stream"), dict(d=r), "unknown: stream")):
+        with pytest.raises(TypeError, match="^%s: %s$" % (name, said)):
+            _lib.Bound(name, varying, **fixed)
+    with pytest.raises(TypeError, match="^stg_scene_order: missing: key_start$"):         # (stream: the default)
+        _lib.Bound("stg_scene_order", ("order",), num_peds=None, N=2, V=3)
+    bound = _lib.Bound(name, ("N", "V"), d=r)
+    for f, n, v, tail, _, _ in _ragged_size_rows():
+        if f == 0:
+            assert bound(V=v, N=n) == tail, (n, v)
+    before = L.stg_last_error()
+    for kw, said in ((dict(N=7), "missing: V"), (dict(N=7, V=64, d=r), "unknown: d"), (dict(N=7, v=64), "missing: V; unknown: v")):
+        with pytest.raises(TypeError, match="^%s: %s$" % (name, said)):
+            bound(**kw)
+    assert L.stg_last_error() == before
 
 
 def test_layout_queries_match_reference_counts(L):

@@ -14,6 +14,9 @@
     python tools/frames_bench.py --cases harvest [--streams 1,64,600] [--ticks 200] [--pushes 2000]
     python tools/frames_bench.py --harvest ...          the latency and streams cases with harvest=HarvestSpec(...)
     python tools/frames_bench.py --tracks 2,2 ...       every case under frames.TrackRule(2, 2) (the *_rule kernels)
+    python tools/frames_bench.py --eager ...            the latency and streams cases (the yardstick too) through push()
+                                                        in the place of the captured replay: every launch enqueued by
+                                                        the host, so the host's own work per push is in the figure
     python tools/frames_bench.py --time 10,10 ...       the latency, streams, score and harvest cases on timestamped pushes
                                                         (frames.TimeRule(10, history=--history), stg_track_push_timed):
                                                         a model step is 10 ticks and the feed is upsampled 10x by linear
@@ -146,13 +149,13 @@ def harvest_spec(windows, timed=None):
     return (frames.HarvestSpec if timed is None else frames.TimedHarvestSpec)(windows, rows=32 * windows)
 
 
-def latency_case(split, rec, max_peds, k, n_push, dev, warmup=50, tracks=None, timed=None, harvest=False):
+def latency_case(split, rec, max_peds, k, n_push, dev, warmup=50, tracks=None, timed=None, harvest=False, eager=False):
     from social_stgcnn_amd import data, frames
     rows = data.read_file(os.path.join(DATA, rec))
     pushes = pushes_of(rows) if timed is None else timed_pushes(rows, *timed[:2])
     kw = {"harvest": harvest_spec(warmup + n_push, timed)} if harvest else {}
     fp = frames.FramePredictor(model_for(split, dev), k=k, max_peds=max_peds, **tracks_kw(tracks, timed), **kw)
-    push = fp.capture()
+    push = fp.push if eager else fp.capture()
     times, peds = [], []
     for i in range(warmup + n_push):
         ids, xy = pushes[i % len(pushes)][:2]
@@ -172,7 +175,7 @@ def latency_case(split, rec, max_peds, k, n_push, dev, warmup=50, tracks=None, t
             "mean_ms": round(float(ms.mean()), 4), "frames_per_s_p50": round(1e3 / float(np.percentile(ms, 50)), 1),
             "mean_peds": round(float(peds.mean()), 2), "max_peds_seen": int(peds.max()),
             **({} if tracks is None else {"tracks": list(tracks)}), **({} if timed is None else {"time": list(timed)}),
-            **({"harvest": list(fp.harvest.counts())} if harvest else {})}
+            **({"harvest": list(fp.harvest.counts())} if harvest else {}), **({"eager": True} if eager else {})}
 
 
 def recording_case(split, rec, k, dev, tracks=None):
@@ -208,7 +211,7 @@ def _stream_sequences(ns, n, timed=None):
 
 
 def streams_case(ns, k, n_ticks, dev, block=0, lone=True, max_peds=128, warmup=20, risk="none", tracks=None,
-                 score=None, timed=None, associate=None, harvest=False, noise=0.0, calibration=None):
+                 score=None, timed=None, associate=None, harvest=False, noise=0.0, calibration=None, eager=False):
     from social_stgcnn_amd import frames
     model = model_for("univ", dev)
     seq = _stream_sequences(ns, warmup + n_ticks, timed)
@@ -231,7 +234,7 @@ def streams_case(ns, k, n_ticks, dev, block=0, lone=True, max_peds=128, warmup=2
         kw["associate"] = associate
         seq = [[(None,) + tuple(p[1:]) for p in q] for q in seq]
     sp = frames.StreamsPredictor(model, ns, k=k, max_peds=max_peds, block_threads=block, **kw)
-    replay = sp.capture()
+    replay = sp.push if eager else sp.capture()
     times, host, peds = [], [], []
     for t in range(warmup + n_ticks):
         tick = [q[t][:2] for q in seq]
@@ -256,6 +259,8 @@ def streams_case(ns, k, n_ticks, dev, block=0, lone=True, max_peds=128, warmup=2
         res["assoc_full"] = int((sp.assoc_flags != 0).sum())
     if tracks is not None:
         res["tracks"] = list(tracks)
+    if eager:
+        res["eager"] = True
     if harvest:
         res["harvest"] = list(sp.harvest.counts())               # windows, rows, dropped_full
     if timed is not None:
@@ -280,7 +285,7 @@ def streams_case(ns, k, n_ticks, dev, block=0, lone=True, max_peds=128, warmup=2
         # the yardstick: NS lone captured FramePredictors, one after another; fewer ticks at large NS
         n_seq = max(10, min(n_ticks, 4000 // ns))
         fps = [frames.FramePredictor(model, k=k, max_peds=max_peds, **tracks_kw(tracks, timed)) for _ in range(ns)]
-        pushes = [fp.capture() for fp in fps]
+        pushes = [fp.push if eager else fp.capture() for fp in fps]
         times = []
         for t in range(warmup + n_seq):
             tot = 0.0
@@ -392,6 +397,8 @@ def main():
     ap.add_argument("--associate_filtered", default="0.05,1.0",
                     metavar="SIGMA_DET,SIGMA_ACC[,SIGMA_VEL0[,GATE_SIGMAS[,GATE_MAX[,MAX_AGE]]]]",
                     help="the FilteredAssociateSpec of the associate_filtered case (MAX_AGE in ticks)")
+    ap.add_argument("--eager", action="store_true",
+                    help="the latency and streams cases through push() in the place of the captured replay")
     ap.add_argument("--noise", type=float, default=0.0, metavar="SIGMA",
                     help="associate_timed and associate_filtered: Gaussian noise of SIGMA metres on every detection")
     a = ap.parse_args()
@@ -408,7 +415,7 @@ def main():
         for split, rec, v in (("eth", "eth_test/biwi_eth.txt", 32), ("eth", "eth_test/biwi_eth.txt", 128),
                               ("univ", "univ_test/students001.txt", 128)):
             print(json.dumps(latency_case(split, rec, v, a.k, a.pushes, dev, tracks=tracks, timed=timed,
-                                          harvest=a.harvest)), flush=True)
+                                          harvest=a.harvest, eager=a.eager)), flush=True)
     if "recording" in cases:
         for split, rec in TEST_RECORDINGS:
             print(json.dumps(recording_case(split, rec, a.k, dev, tracks)), flush=True)
@@ -476,7 +483,7 @@ def main():
             for ns in (int(n) for n in a.streams.split(",")):
                 for mode in a.risk.split(","):
                     print(json.dumps(streams_case(ns, a.k, a.ticks, dev, block, not a.no_lone, risk=mode,
-                                                  tracks=tracks, timed=timed, harvest=a.harvest)),
+                                                  tracks=tracks, timed=timed, harvest=a.harvest, eager=a.eager)),
                           flush=True)
 
 

@@ -93,9 +93,7 @@ def bind(path):
     """The five entry points, stg_model_ws_floats and stg_last_error of the library at `path`, typed as _lib types them."""
     from social_stgcnn_amd import _lib
     h = ctypes.CDLL(path)
-    for name in list(ARGS) + ["stg_model_ws_floats", "stg_last_error"]:
-        fn = getattr(h, name)
-        fn.restype, fn.argtypes = _lib._SIGNATURES[name]
+    _lib.bind(h, {name: _lib.PROTOTYPES[name] for name in list(ARGS) + ["stg_model_ws_floats", "stg_last_error"]})
     return h
 
 
