@@ -10,7 +10,9 @@
 //   stg_track_push_streams_timed  one workgroup per stream on the (NS, ...) slices, as stg_track_push_streams_rule
 //
 // The sort and the slot assignment (assign_slots), the padding of a scene and the per-stream wrapper are those of every
-// push (track_rule.hpp); a slot is live by its newest sample's age instead of a presence mask.
+// push (track_rule.hpp); a slot is live by its newest sample's age instead of a presence mask.  How a
+// slot's samples are indexed, searched and interpolated is time_samples.hpp's, shared with the score and the harvest
+// behind this push; the push keeps its own virtual last sample: tb = t_now, the position from the input.
 // Everything is read from device memory when the kernel runs -- the time too -- so one captured graph serves every
 // push.  Integer work, float64 arithmetic with IEEE operations as written, plain C++ stores, LDS atomics on integer
 // words, no scratch, no host synchronisation.
@@ -75,7 +77,7 @@ __device__ __forceinline__ int track_push_timed_body(const Detections &det, int 
     const int64_t span = (int64_t)(T_obs - 1) * step;
     for (int s = tid; s < S; s += nt) {
         int h = slot_head[2 * s], c = slot_head[2 * s + 1];
-        if (c > 0 && t_now - t_ring[(int64_t)s * R + (h == 0 ? R - 1 : h - 1)] > span) {
+        if (c > 0 && t_now - t_ring[(int64_t)s * R + ring_before(h, R)] > span) {
             h = c = 0;
             slot_id[s] = -1;
             slot_head[2 * s] = 0;
@@ -110,8 +112,8 @@ __device__ __forceinline__ int track_push_timed_body(const Detections &det, int 
         slot_head[2 * s + 1] = c < R ? c + 1 : R;
     }
 
-    // 6. one thread per (detection with a slot, earlier window step k): binary search of the instant in the slot's
-    //    times (ring order is time order).  Observed: a sample at the instant, or its neighbours at most max_dt apart.
+    // 6. one thread per (detection with a slot, earlier window step k): the search of the instant in the slot's times
+    //    (time_samples.hpp).  Observed: a sample at the instant, or its neighbours at most max_dt apart.
     const int T1 = T_obs - 1;
     for (int e = tid; e < m * T1; e += nt) {
         const int j = e / T1, k = e % T1;
@@ -120,13 +122,7 @@ __device__ __forceinline__ int track_push_timed_body(const Detections &det, int 
         const int c = scnt[s], n_old = c < R - 1 ? c : R - 1, h = shead[s];
         const int64_t tau = t_now - (int64_t)(T1 - k) * step;
         const int64_t *tr = t_ring + (int64_t)s * R;
-        int lo = 0, hi = n_old;                              // the first sample later than tau
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (tr[ring_at(h, n_old, mid, R)] <= tau) lo = mid + 1;
-            else hi = mid;
-        }
-        const int i = lo - 1;
+        const int i = last_at_or_before(tr, h, n_old, R, tau);
         if (i < 0) continue;
         const int64_t ta = tr[ring_at(h, n_old, i, R)];
         const int64_t tb = i + 1 < n_old ? tr[ring_at(h, n_old, i + 1, R)] : t_now;
@@ -182,9 +178,7 @@ __device__ __forceinline__ int track_push_timed_body(const Detections &det, int 
                     bx = xy_ring[b * 2];
                     by = xy_ring[b * 2 + 1];
                 }
-                const double w = (double)(tau - ta) / (double)(tb - ta);
-                x = lerp_pos(x, bx, w, scale);
-                y = lerp_pos(y, by, w, scale);
+                lerp_bracket(ta, x, y, tb, bx, by, tau, scale, x, y);
             }
         }
         obs_abs[((int64_t)k * V + r) * 2] = x;
@@ -233,7 +227,7 @@ __global__ __launch_bounds__(kThreads) void track_push_streams_timed_kernel(
     SceneOut out, int32_t *__restrict__ out_flags) {
     push_stream(det, tick, out, d.T_obs, d.V, out_flags, [&](const Detections &mine, int count, const SceneOut &scene) {
         const int b = blockIdx.x;
-        return track_push_timed_body<kThreads>(mine, count, det_time[b], st.of_stream(b, d), d, rule, scene);
+        return track_push_timed_body<kThreads>(mine, count, det_time[b], st.of_stream(b, d.S, d.R), d, rule, scene);
     });
 }
 
@@ -253,12 +247,8 @@ static int timed_args(const char *what, const TrackRule &rule, const Detections 
     STG_REQUIRE(M_max >= 1 && M_max <= STG_TRACK_MAX_DETECTIONS && S >= 1 && S <= STG_TRACK_MAX_SLOTS && V >= 1,
                 STG_EINVAL, "%s: bad sizes M_max=%d S=%d V=%d", what, M_max, S, V);
     STG_REQUIRE_RULE(what);
-    STG_REQUIRE(R >= 2, STG_EINVAL, "%s: R=%d samples per track (at least 2)", what, R);
-    STG_REQUIRE(R <= STG_TRACK_MAX_HISTORY, STG_EUNSUPPORTED, "%s: R=%d above STG_TRACK_MAX_HISTORY=%d", what, R,
-                STG_TRACK_MAX_HISTORY);
-    STG_REQUIRE(step >= 1, STG_EINVAL, "%s: step=%lld ticks (at least 1)", what, (long long)step);
-    STG_REQUIRE(step < ((int64_t)1 << 31) && step * T_obs < ((int64_t)1 << 31), STG_EUNSUPPORTED,
-                "%s: step=%lld: step * T_obs must stay below 2^31", what, (long long)step);
+    const int rc = timed_size_args(what, R, step, T_obs, "T_obs");
+    if (rc != STG_OK) return rc;
     STG_REQUIRE(max_dt >= 1 && max_dt <= (int64_t)(T_obs - 1) * step, STG_EINVAL,
                 "%s: max_dt=%lld not in [1, (T_obs - 1) * step = %lld]", what, (long long)max_dt,
                 (long long)((int64_t)(T_obs - 1) * step));

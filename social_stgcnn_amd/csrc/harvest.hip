@@ -6,7 +6,8 @@
 //   stg_window_harvest          one stream: ONE workgroup, behind stg_track_push of the same push.  It reads the track
 //                               state only (slot ids, presence bit 0, the ring row the push has just written), keeps its
 //                               own T_all-deep history, sorts the candidates by id (detections.hpp), places the window
-//                               and writes its rows.
+//                               and writes its rows.  The frame, the tail and the streams' body are harvest_parts.hpp's,
+//                               shared with harvest_time.hip: this file says where "seen" comes from.
 //   stg_window_harvest_streams  NS streams behind stg_track_push_streams, three launches that never wait for each other:
 //                               update + count (one workgroup per stream, honours pushed[b]); place (ONE workgroup: the
 //                               exclusive scan of the tick's row counts, the capacity test and the header's only
@@ -21,87 +22,35 @@
 
 namespace stg {
 
-// One push of one stream's history by one workgroup, behind the track push: age the words, take presence and position
-// from the track state, and leave the candidates -- the slots with all T_all low bits set -- sorted by id in (key,
-// kidx = slot), n2 = det_sort_n(S) entries of LDS.  Returns (in every thread) their number, 0 when below min_peds;
-// `row` is the history's ring row of this push.  Ends on a barrier.
-__device__ __forceinline__ int harvest_update(const TrackView &tr, const HarvestState &hs, const HarvestDims &d,
-                                              int64_t *key, int32_t *kidx, int *wave_cnt, int &row) {
-    const int tid = threadIdx.x, nt = kHarvestThreads, S = d.S, T_all = d.T_all;
-    const uint32_t full = T_all >= 32 ? 0xffffffffu : (1u << T_all) - 1u;
-    const int pushes = hs.head[1];
+// One push of one stream's history by one workgroup, behind the track push; `push` = the pushes before it, as
+// hs.head[1] counts them.  harvest_frame (harvest_parts.hpp) with this family's answer to "seen in this frame?": bit 0
+// of the slot's presence mask, and the position the push has just written to the track ring.
+__device__ __forceinline__ int harvest_update(const TrackView &tr, const HarvestState &hs, const HarvestDims &d, int push,
+                                              const HarvestSort &so, int *wave_cnt, int &row) {
     const int trow = ring_row(tr.head_flags[0], d.T_obs);  // the track ring's row of this push
-    row = (ring_row(hs.head[0], T_all) + 1) % T_all;
-    const double *__restrict__ src = tr.ring + (int64_t)trow * S * 2;
-    double *__restrict__ dst = hs.ring + (int64_t)row * S * 2;
-    int c = 0, tot = 0;
-    for (int s0 = 0; s0 < S; s0 += nt) {
-        const int s = s0 + tid;
-        int64_t id = -1;
-        bool cand = false;
-        if (s < S) {
-            id = tr.slot_id[s];
-            uint32_t w = 0;                                  // a free slot has an empty word
-            if (id >= 0) {
-                w = (hs.word[s] << 1) & full;
-                if (tr.mask[s] & 1u) {                       // really detected in this push
-                    w |= 1u;
-                    dst[s * 2] = src[s * 2];
-                    dst[s * 2 + 1] = src[s * 2 + 1];
-                }
-            }
-            hs.word[s] = w;
-            cand = w == full;
-        }
-        const int r = block_rank<kHarvestThreads>(cand, c, &tot, wave_cnt);
-        if (cand) {                                          // (r < S: at most one candidate per slot)
-            key[r] = id;
-            kidx[r] = s;
-        }
-        c += tot;
-    }
-    __syncthreads();                                         // every thread has read head; key / kidx / ring are written
-    if (tid == 0) {
-        hs.head[0] = row;
-        hs.head[1] = pushes + 1;
-    }
-    if (c < d.min_peds) return 0;
-    const int n2 = det_sort_n(c);                            // (<= det_sort_n(S))
-    for (int p = c + tid; p < n2; p += nt) {
-        key[p] = INT64_MAX;
-        kidx[p] = -1;
-    }
-    __syncthreads();
-    det_sort(key, kidx, n2, tid, nt);
-    return c;
+    const double *__restrict__ src = tr.ring + (int64_t)trow * d.S * 2;
+    return harvest_frame(
+        tr.slot_id, hs, d, false, push + 1, so, wave_cnt, row,
+        [&](int s, double &x, double &y) {
+            if ((tr.mask[s] & 1u) == 0) return false;        // not really detected in this push
+            x = src[s * 2];
+            y = src[s * 2 + 1];
+            return true;
+        },
+        [] {});
 }
 
 // ---- one stream ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kHarvestThreads) void window_harvest_kernel(TrackView tr, HarvestState hs, HarvestDims d,
                                                                          HarvestLog log, int stream_index) {
     extern __shared__ __align__(16) unsigned char lds[];
-    int64_t *key = reinterpret_cast<int64_t *>(lds);
-    int32_t *kidx = reinterpret_cast<int32_t *>(key + det_sort_n(d.S));
     __shared__ int wave_cnt[kHarvestWaves];
-    // the header as the push found it: read by every thread ahead of the barriers, written by thread 0 behind them
-    const int nw = log.header[0], nr = log.header[1], dropped = log.header[2];
-    const int push = hs.head[1];
+    const HarvestSort so(lds, d.S);
+    const HarvestHeader at(log);
+    const int push = hs.head[1];                             // the window's tag
     int row;
-    const int c = harvest_update(tr, hs, d, key, kidx, wave_cnt, row);
-    if (c == 0) return;
-    const bool fits = harvest_fits(log, dropped, nw, nr, c);
-    if (fits) harvest_rows(hs.ring, d, log, nr, c, row, [&](int p) { return kidx[p]; });
-    if (threadIdx.x == 0) {
-        if (fits) {
-            log.win_start[nw + 1] = nr + c;
-            log.win_tag[nw * 2] = stream_index;
-            log.win_tag[nw * 2 + 1] = push;
-            log.header[0] = nw + 1;
-            log.header[1] = nr + c;
-        } else {
-            log.header[2] = dropped + 1;
-        }
-    }
+    const int c = harvest_update(tr, hs, d, push, so, wave_cnt, row);
+    harvest_append(hs, d, log, at, c, row, so, stream_index, push);
 }
 
 // ---- NS streams: update + count, place, write --------------------------------------------------------------------------
@@ -109,19 +58,11 @@ __global__ __launch_bounds__(kHarvestThreads) void harvest_update_streams_kernel
                                                                                  const int32_t *__restrict__ pushed,
                                                                                  HarvestState hs, HarvestDims d,
                                                                                  HarvestWork work) {
-    extern __shared__ __align__(16) unsigned char lds[];
-    int64_t *key = reinterpret_cast<int64_t *>(lds);
-    int32_t *kidx = reinterpret_cast<int32_t *>(key + det_sort_n(d.S));
-    __shared__ int wave_cnt[kHarvestWaves];
-    const int b = blockIdx.x;
-    const HarvestWork mine = work.of_stream(b, d);
-    int c = 0;
-    if (pushed[b] != 0) {                                    // uniform over the block: no barrier is skipped halfway
+    harvest_count_stream(pushed, d, work, [&](int b, const HarvestSort &so, int *wave_cnt) {
+        const HarvestState mine = hs.of_stream(b, d);
         int row;
-        c = harvest_update(tr.of_stream(b, d), hs.of_stream(b, d), d, key, kidx, wave_cnt, row);
-        for (int p = threadIdx.x; p < c; p += kHarvestThreads) mine.cand[p] = kidx[p];
-    }
-    if (threadIdx.x == 0) mine.count[0] = c;
+        return harvest_update(tr.of_stream(b, d), mine, d, mine.head[1], so, wave_cnt, row);
+    });
 }
 
 // ONE workgroup: stream b's window (count[b] rows, 0 = none) goes behind the windows of the streams before it.  The
@@ -191,14 +132,10 @@ __global__ __launch_bounds__(kHarvestThreads) void harvest_write_streams_kernel(
 // ---- host side ------------------------------------------------------------------------------------------------------
 static int harvest_args(const char *what, const TrackView &tr, const HarvestState &hs, const HarvestDims &d,
                         const HarvestLog &log) {
-    STG_REQUIRE(d.S >= 1 && d.S <= STG_TRACK_MAX_SLOTS && d.T_obs >= 1 && d.T_all >= 2 && d.T_all <= STG_HARVEST_MAX_STEPS &&
-                    d.T_all - d.T_obs >= 1 && d.min_peds >= 1,
-                STG_EINVAL, "%s: bad sizes S=%d T_obs=%d T_all=%d min_peds=%d", what, d.S, d.T_obs, d.T_all, d.min_peds);
-    STG_REQUIRE(log.cap_windows >= 1 && log.cap_windows < INT32_MAX && log.cap_rows >= 1, STG_EINVAL,
-                "%s: bad capacities cap_windows=%d cap_rows=%d", what, log.cap_windows, log.cap_rows);
-    STG_REQUIRE(tr.slot_id && tr.mask && tr.ring && tr.head_flags && hs.word && hs.ring && hs.head && log.rel_all &&
-                    log.win_start && log.win_tag && log.header,
-                STG_EINVAL, "%s: null pointer", what);
+    const int rc = harvest_size_args(what, d, log);
+    if (rc != STG_OK) return rc;
+    STG_REQUIRE(tr.slot_id && tr.mask && tr.ring && tr.head_flags && harvest_pointers(hs, log), STG_EINVAL,
+                "%s: null pointer", what);
     return STG_OK;
 }
 

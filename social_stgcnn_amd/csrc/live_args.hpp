@@ -1,9 +1,11 @@
-// live_args: the argument records of the live path (frames.hip, frames_time.hip, score.hip, associate.hip; DESIGN.md
-// 5.23): plain structs passed by value as kernel arguments in the place of runs of same-typed pointers.  THE ONE
-// SLICING RULE: a record that lives in (NS, ...) arrays has an of_stream(b, ...) (the detections: from(lo)), the only
-// place its per-stream strides are written; a body only ever sees its own stream's record.  On the host, stream_args
-// is the one check of what the _streams entry points are told about their streams.
+// live_args: the argument records of the live path (frames.hip, frames_time.hip, score.hip, score_time.hip,
+// associate.hip, harvest.hip, harvest_time.hip): plain structs passed by value as kernel arguments
+// in the place of runs of same-typed pointers.  THE ONE SLICING RULE: a record that lives in (NS, ...) arrays has an
+// of_stream(b, ...) (the detections: from(lo)), the only place its per-stream strides are written; a body only ever
+// sees its own stream's record.  On the host, stream_args is the one check of what the _streams entry points are told
+// about their streams, timed_size_args the one check of the track rings' depth and the step.
 #pragma once
+#include <type_traits>
 #include "common.hpp"
 
 namespace stg {
@@ -55,14 +57,20 @@ struct TrackState {
     }
 };
 
-// ... of a timed push: slot_id (S), t_ring (S,R), xy_ring (S,R,2), slot_head (S,2), clock (2), head_flags (2)
-struct TimedState {
-    int64_t *slot_id, *t_ring; double *xy_ring; int32_t *slot_head; int64_t *clock; int32_t *head_flags;
-    __device__ __forceinline__ TimedState of_stream(int64_t b, const TimedDims &d) const {
-        return {slot_id + b * d.S,       t_ring + b * d.S * d.R, xy_ring + b * d.S * d.R * 2,
-                slot_head + b * d.S * 2, clock + 2 * b,          head_flags + 2 * b};
+// ... of a timed push: slot_id (S), t_ring (S,R), xy_ring (S,R,2), slot_head (S,2) = {next write index, count} per slot,
+// clock (2), head_flags (2).  kConst: the same state as the kernels behind the push read it (harvest_time.hip,
+// score_time.hip; time_samples.hpp reads a slot's samples out of it): nothing of it is written.
+template <bool kConst>
+struct TimedStateOf {
+    template <class T> using Ptr = std::conditional_t<kConst, const T, T> *;
+    Ptr<int64_t> slot_id, t_ring; Ptr<double> xy_ring; Ptr<int32_t> slot_head; Ptr<int64_t> clock; Ptr<int32_t> head_flags;
+    __device__ __forceinline__ TimedStateOf of_stream(int64_t b, int S, int R) const {
+        return {slot_id + b * S,       t_ring + b * S * R, xy_ring + b * S * R * 2,
+                slot_head + b * S * 2, clock + 2 * b,      head_flags + 2 * b};
     }
 };
+using TimedState = TimedStateOf<false>;
+using TimedView = TimedStateOf<true>;
 
 // The scene a push leaves: obs_abs (T_obs,V,2), out_ids (V), num_peds (1), seen (V; null in the strict pushes)
 struct SceneOut {
@@ -115,16 +123,6 @@ struct HarvestLog {
 // What the timed harvest adds to HarvestDims: R samples per slot, the push's scale, step, max_dt and settle in ticks
 struct TimedHarvestDims { int R; double scale; int64_t step, max_dt, settle; };
 
-// The timed push's state as the harvest reads it, behind that push: nothing of it is written
-struct TimedView {
-    const int64_t *slot_id, *t_ring; const double *xy_ring; const int32_t *slot_head; const int64_t *clock;
-    const int32_t *head_flags;
-    __device__ __forceinline__ TimedView of_stream(int64_t b, int S, int R) const {
-        return {slot_id + b * S,       t_ring + b * S * R, xy_ring + b * S * R * 2,
-                slot_head + b * S * 2, clock + 2 * b,      head_flags + 2 * b};
-    }
-};
-
 // ---- host side ------------------------------------------------------------------------------------------------------
 // What every _streams entry point checks of its streams, under its own name `what`: NS, M_total and the strides.  The
 // entry points do not all answer alike, and each keeps its answer:
@@ -137,6 +135,22 @@ static inline int stream_args(const char *what, int NS, int M_total, int64_t id_
                     (!limits || (NS <= STG_TRACK_MAX_STREAMS && M_total <= STG_TRACK_MAX_TOTAL_DETECTIONS)),
                 STG_EINVAL, "%s: bad sizes NS=%d M_total=%d strides %lld/%lld", what, NS, M_total, (long long)id_stride,
                 (long long)xy_stride);
+    return STG_OK;
+}
+
+// What the timed push (frames_time.hip), the timed harvest (harvest_time.hip) and the timed score (score_time.hip) are
+// told alike about the track rings and the step, under the entry point's name `what`, in the order of the push:
+// R >= 2; R <= STG_TRACK_MAX_HISTORY (STG_EUNSUPPORTED); step >= 1; step and step * n below 2^31 (STG_EUNSUPPORTED),
+// where n, called n_name in the message, is T_obs for the push and the harvest and P for the score.  The bounds that
+// differ between the families stay with them: max_dt in [1, (T_obs - 1) * step] for the push and the harvest, the
+// harvest's settle, max_dt in [1, 2^31) for the score.
+static inline int timed_size_args(const char *what, int R, int64_t step, int n, const char *n_name) {
+    STG_REQUIRE(R >= 2, STG_EINVAL, "%s: R=%d samples per track (at least 2)", what, R);
+    STG_REQUIRE(R <= STG_TRACK_MAX_HISTORY, STG_EUNSUPPORTED, "%s: R=%d above STG_TRACK_MAX_HISTORY=%d", what, R,
+                STG_TRACK_MAX_HISTORY);
+    STG_REQUIRE(step >= 1, STG_EINVAL, "%s: step=%lld ticks (at least 1)", what, (long long)step);
+    STG_REQUIRE(step < ((int64_t)1 << 31) && step * n < ((int64_t)1 << 31), STG_EUNSUPPORTED,
+                "%s: step=%lld: step * %s must stay below 2^31", what, (long long)step, n_name);
     return STG_OK;
 }
 

@@ -16,7 +16,7 @@
 //                tau == tb                          the truth is pb, no arithmetic is done
 //                ta < tau < tb, tb - ta <= max_dt   per coordinate round(pa + (pb - pa) * ((double)(tau - ta) /
 //                                                   (double)(tb - ta))) in float64, one IEEE operation at a time
-//                                                   (lerp_pos of frames_time.hip)
+//                                                   (lerp_bracket of time_samples.hpp, the push's own)
 //                ta < tau < tb, a wider bracket     that (record, h, v) stays unmatched for good
 //                anything else                      not this push
 //              and the truth is converted to float32.  The brackets of a track are disjoint, so every (record, h, v)
@@ -44,23 +44,18 @@
 // No host synchronisation, plain C++ stores only, no scratch.
 //
 // The arithmetic of `values`, the trajectory values and totals columns, the covariance sum and the column copies of the
-// enqueue and the host's checks of the prediction are score_fn.hpp's, shared with score.hip.  This file
-// keeps what is its own: the truth interpolated from the track rings, a wave per record row behind the header pass, the
-// record's own tables.
+// enqueue and the host's checks of the prediction are score_fn.hpp's, shared with score.hip.  The track
+// state is live_args.hpp's TimedView; the refused push, a slot's head and count, its two newest samples and the
+// interpolation are time_samples.hpp's, shared with the push and the harvest.  This file keeps what is
+// its own: which instants fall into a track's newest bracket, a wave per record row behind the header pass, the record's
+// own tables.
 #include "detections.hpp"
 #include "score_fn.hpp"
+#include "time_samples.hpp"
 
 namespace stg {
 
 enum { kRecEmpty = 0, kRecPending = 1, kRecRetired = 2 };
-
-// round(pa + (pb - pa) * w): the interpolation of the timed push (frames_time.hip), one IEEE operation at a time
-__device__ __forceinline__ double lerp_pos(double pa, double pb, double w, double scale) {
-#pragma clang fp contract(off)
-    const double d = pb - pa;
-    const double p = d * w;
-    return round_pos(pa + p, scale);
-}
 
 // floor(a / b) for b > 0
 __device__ __forceinline__ int64_t floor_div(int64_t a, int64_t b) {
@@ -71,16 +66,6 @@ __device__ __forceinline__ int64_t floor_div(int64_t a, int64_t b) {
 // The sizes of a timed score: S track slots with R samples each (S2 = det_sort_n(S), filled in on the host), Rp record
 // rows of P horizons, V pedestrians, K samples; Q thresholds
 struct TimedScoreDims { int NS, P, V, K, Q, Rp, S, R, S2; int64_t step, max_dt; double scale; };
-
-// The timed track state as the score reads it (TimedState of live_args.hpp, const) and the push's verdict
-struct TimedTracks {
-    const int64_t *slot_id, *t_ring; const double *xy_ring; const int32_t *slot_head; const int64_t *clock;
-    const int32_t *head_flags;
-    __device__ __forceinline__ TimedTracks of_stream(int64_t b, const TimedScoreDims &d) const {
-        return {slot_id + b * d.S,       t_ring + b * d.S * d.R, xy_ring + b * d.S * d.R * 2,
-                slot_head + b * d.S * 2, clock + 2 * b,          head_flags + 2 * b};
-    }
-};
 
 // stg_score_timed_state with its slicing rule
 struct TimedScoreState : stg_score_timed_state {
@@ -103,7 +88,7 @@ struct TimedScoreState : stg_score_timed_state {
 
 struct TimedScoreArgs {
     ScorePred pred;
-    TimedTracks trk;
+    TimedView trk;                                          // the timed track state (live_args.hpp): read only
     TimedScoreState st;
     const float *thr;
     stg_score_timed_out out;
@@ -112,7 +97,7 @@ struct TimedScoreArgs {
 
 // One timed push of stream b scored by one workgroup of kScoreThreads threads; trk and st are the stream's own.
 // LDS (dynamic): sort keys (S2 x int64), sort indices (S2 x int32)
-__device__ __forceinline__ void score_timed_body(const TimedScoreArgs &a, int b, const TimedTracks &trk,
+__device__ __forceinline__ void score_timed_body(const TimedScoreArgs &a, int b, const TimedView &trk,
                                                  const TimedScoreState &st, bool pushed) {
     extern __shared__ __align__(16) unsigned char lds[];
     int64_t *key = reinterpret_cast<int64_t *>(lds);
@@ -129,7 +114,7 @@ __device__ __forceinline__ void score_timed_body(const TimedScoreArgs &a, int b,
     double *push_totals = a.out.push_totals + (int64_t)b * P * W, *push_traj = a.out.push_traj + (int64_t)b * 5;
 
     // 0. a stream not pushed, or a push the track kernel refused: nothing moves (uniform over the block)
-    if (!pushed || (trk.head_flags[1] & STG_TRACK_TIME_ORDER) != 0) {
+    if (!pushed || push_refused(trk.head_flags)) {
         for (int e = tid; e < P * W; e += kScoreThreads) push_totals[e] = 0.0;
         if (tid < 5) push_traj[tid] = 0.0;
         return;
@@ -150,13 +135,13 @@ __device__ __forceinline__ void score_timed_body(const TimedScoreArgs &a, int b,
     for (int p = tid; p < a.d.S2; p += kScoreThreads) {
         int64_t k = INT64_MAX;
         if (p < S) {
-            const int h = (int)((uint32_t)trk.slot_head[2 * p] % (uint32_t)R), c = trk.slot_head[2 * p + 1];
-            const int ib = h == 0 ? R - 1 : h - 1;
+            int h;
+            const int c = slot_samples(trk.slot_head, p, R, &h), ib = ring_before(h, R);
             if (c > 0 && trk.t_ring[(int64_t)p * R + ib] == t_now) {
                 k = trk.slot_id[p];
                 atomicMax(&top, p + 1);
                 if (c >= 2)
-                    atomicMin(&ta_low, (unsigned long long)trk.t_ring[(int64_t)p * R + (ib == 0 ? R - 1 : ib - 1)] ^ kBias);
+                    atomicMin(&ta_low, (unsigned long long)trk.t_ring[(int64_t)p * R + ring_before(ib, R)] ^ kBias);
             }
         }
         key[p] = k;
@@ -204,14 +189,14 @@ __device__ __forceinline__ void score_timed_body(const TimedScoreArgs &a, int b,
                 const int at = id == INT64_MAX ? -1 : det_find(key, n2, id);
                 if (at >= 0) {
                     const int s = kidx[at];
-                    const int hd = (int)((uint32_t)trk.slot_head[2 * s] % (uint32_t)R), c = trk.slot_head[2 * s + 1];
-                    const int ib = hd == 0 ? R - 1 : hd - 1;
+                    int hd;
+                    const int c = slot_samples(trk.slot_head, s, R, &hd), ib = ring_before(hd, R);
                     const int64_t sb = (int64_t)s * R + ib;
                     bx = trk.xy_ring[sb * 2];
                     by = trk.xy_ring[sb * 2 + 1];
                     ta = t_now - 1;                         // no older sample: the bracket holds t_now alone
                     if (c >= 2) {
-                        const int64_t sa = (int64_t)s * R + (ib == 0 ? R - 1 : ib - 1);
+                        const int64_t sa = (int64_t)s * R + ring_before(ib, R);
                         ta = trk.t_ring[sa];
                         ax = trk.xy_ring[sa * 2];
                         ay = trk.xy_ring[sa * 2 + 1];
@@ -231,11 +216,7 @@ __device__ __forceinline__ void score_timed_body(const TimedScoreArgs &a, int b,
                 for (int i = 0; i < kScoreRow; ++i) pt[i] = 0.0;
                 if (hit) {
                     double x = bx, y = by;
-                    if (tau != t_now) {
-                        const double w = (double)(tau - ta) / (double)(t_now - ta);
-                        x = lerp_pos(ax, bx, w, a.d.scale);
-                        y = lerp_pos(ay, by, w, a.d.scale);
-                    }
+                    if (tau != t_now) lerp_bracket(ta, ax, ay, t_now, bx, by, tau, a.d.scale, x, y);
                     const int64_t e = ((int64_t)r * P + (h - 1)) * V + v;
                     float err, d2, nll, best;
                     score_entry(tab, r, h, v, (float)x, (float)y, err, d2, nll, best);
@@ -338,17 +319,18 @@ __global__ __launch_bounds__(kScoreThreads) void score_push_timed_kernel(const T
 __global__ __launch_bounds__(kScoreThreads) void score_push_streams_timed_kernel(const TimedScoreArgs a,
                                                                                   const int32_t *__restrict__ pushed) {
     const int b = blockIdx.x;
-    score_timed_body(a, b, a.trk.of_stream(b, a.d), a.st.of_stream(b, a.d), pushed[b] != 0);
+    score_timed_body(a, b, a.trk.of_stream(b, a.d.S, a.d.R), a.st.of_stream(b, a.d), pushed[b] != 0);
 }
 
 // the checks both entry points share, on `a` as the entry point filled it from its arguments; completes it (st, out, S2)
 static int score_timed_args(const char *what, const stg_score_timed_state *st, const stg_score_timed_out *out,
                             TimedScoreArgs *a) {
     TimedScoreDims &d = a->d;
-    const TimedTracks &t = a->trk;
+    const TimedView &t = a->trk;
     STG_REQUIRE(d.S >= 1 && d.R >= 2 && d.P >= 1 && d.V >= 1 && d.K >= 0 && d.Q >= 0 && d.Rp >= 1, STG_EINVAL,
                 "%s: bad sizes S=%d R=%d P=%d V=%d K=%d Q=%d Rp=%d", what, d.S, d.R, d.P, d.V, d.K, d.Q, d.Rp);
-    STG_REQUIRE(d.step >= 1, STG_EINVAL, "%s: step=%lld ticks (at least 1)", what, (long long)d.step);
+    int rc = timed_size_args(what, d.R, d.step, d.P, "P");
+    if (rc != STG_OK) return rc;
     STG_REQUIRE(d.max_dt >= 1 && d.max_dt < ((int64_t)1 << 31), STG_EINVAL, "%s: max_dt=%lld not in [1, 2^31)", what,
                 (long long)d.max_dt);
     STG_REQUIRE(st && out, STG_EINVAL, "%s: null pointer (state / out)", what);
@@ -359,16 +341,12 @@ static int score_timed_args(const char *what, const stg_score_timed_state *st, c
                     st->traj_ade_mean && st->traj_fde_mean && st->counters && st->totals && st->traj_totals,
                 STG_EINVAL, "%s: null pointer in the state", what);
     STG_REQUIRE(out->push_totals && out->push_traj, STG_EINVAL, "%s: null pointer among the outputs", what);
-    const int rc = score_pred_args(what, &a->pred, a->thr, st->rec_mean, st->rec_samples,
+    rc = score_pred_args(what, &a->pred, a->thr, st->rec_mean, st->rec_samples,
                                    st->rec_samples && st->acc && st->best && st->traj_ade && st->traj_fde,
                                    "rec_samples / acc / best / traj_ade / traj_fde", d.NS, d.P, d.V, &d.K, d.Q);
     if (rc != STG_OK) return rc;
-    STG_REQUIRE(d.step * d.P < ((int64_t)1 << 31) && d.step < ((int64_t)1 << 31), STG_EUNSUPPORTED,
-                "%s: step=%lld: step * P must stay below 2^31", what, (long long)d.step);
     STG_REQUIRE(d.S <= STG_TRACK_MAX_SLOTS, STG_EUNSUPPORTED, "%s: S=%d above STG_TRACK_MAX_SLOTS=%d", what, d.S,
                 STG_TRACK_MAX_SLOTS);
-    STG_REQUIRE(d.R <= STG_TRACK_MAX_HISTORY, STG_EUNSUPPORTED, "%s: R=%d above STG_TRACK_MAX_HISTORY=%d", what, d.R,
-                STG_TRACK_MAX_HISTORY);
     STG_REQUIRE(d.Rp <= STG_SCORE_MAX_PENDING, STG_EUNSUPPORTED, "%s: Rp=%d above STG_SCORE_MAX_PENDING=%d", what, d.Rp,
                 STG_SCORE_MAX_PENDING);
     static_cast<stg_score_timed_state &>(a->st) = *st;

@@ -137,6 +137,52 @@ class Harvester:
             self.hist[b].reset()
 
 
+WIDE_S, WIDE_NS = 272, 2                 # more slots than the 256 threads of a harvest workgroup: a second pass over them
+
+
+def wide_script(ticks=7, seed=7):
+    """The feed of the GPU tests' second-pass case at WIDE_S slots: ticks x WIDE_NS entries (ids, xy) or None (not
+    pushed).  Stream 0 holds 264 ids in every tick, shuffled, a negative one and one above 2^32 among them: they fill the
+    slots 0 .. 263 in the first tick, so candidates sit past slot 255; from tick 2 on one more id per tick, each seen
+    twice, takes the lowest free slot from 264 up (live, never complete) and the last slots stay free.  Stream 1 holds
+    five ids and sits out tick 3."""
+    gen = np.random.default_rng(seed)
+    crowd = list(range(1, 263)) + [-5, (1 << 33) + 7]
+    out = []
+    for t in range(ticks):
+        ids = crowd + [9000 + k for k in (t - 1, t) if k >= 2]
+        ids = np.array(ids, np.int64)[gen.permutation(len(ids))]
+        few = np.array([3, (1 << 33) + 8, 50, 51, 52], np.int64)[gen.permutation(5)]
+        out.append([(ids, gen.uniform(-20, 20, size=(len(ids), 2))),
+                    None if t == 3 else (few, gen.uniform(-20, 20, size=(5, 2)))])
+    return out
+
+
+def wide_ticks(script, t_obs=3, t_all=5, caps=(16, 1024), min_peds=2):
+    """wide_script tick by tick through one TrackModel per stream and a Harvester: yields (the tick's entries, every
+    stream's track state (slot_id, mask, ring, head) behind the tick -- the models' own arrays --, the Harvester behind
+    the tick, the slots of stream 0's window or None)."""
+    tracks = [TrackModel(t_obs, WIDE_S) for _ in range(WIDE_NS)]
+    hv = Harvester(WIDE_NS, WIDE_S, t_all, *caps, min_peds)
+    for tick in script:
+        for b, d in enumerate(tick):
+            if d is not None:
+                assert tracks[b].push(*d) == 0
+        hv.tick({b: tracks[b].state() for b, d in enumerate(tick) if d is not None})
+        cand = np.nonzero(hv.hist[0].word == hv.hist[0].full)[0]
+        yield tick, [tr.state() for tr in tracks], hv, cand if tick[0] is not None and len(cand) >= min_peds else None
+
+
+def wide_conditions(slot_ids, words, full, windows):
+    """What a second-pass feed has to reach, on the statement's own state: slot_ids / words per tick of one stream, full
+    = the word of a complete track, windows = per tick the slots of the window's rows (or None).  At least one window,
+    a row in a slot >= 256, and at some tick a live slot that is no candidate and a free slot, both past slot 255."""
+    rows = [w for w in windows if w is not None]
+    tail = [(np.asarray(i[256:]), np.asarray(w[256:])) for i, w in zip(slot_ids, words)]
+    return (len(rows) >= 1 and any((np.asarray(w) >= 256).any() for w in rows) and
+            any(((i >= 0) & (w != full)).any() and (i == -1).any() for i, w in tail))
+
+
 def pushes_of(rows):
     """rows (M,4) <frame> <ped> <x> <y> -> [(ids int64, xy float64)] per distinct frame number, ascending, ids
     ascending within a frame."""

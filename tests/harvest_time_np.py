@@ -248,6 +248,72 @@ def scripted_feed(t_obs, t_all, pushes, seed, step=10):
     return out
 
 
+WIDE_S, WIDE_NS = 272, 2                 # more slots than the 256 threads of a harvest workgroup: a second pass over them
+
+
+def wide_feed(seed=7, step=10):
+    """The feed of the GPU test's second-pass case at WIDE_S slots, rings of 4, T_obs 3, T_all 5, max_dt = step, settle 0:
+    [WIDE_NS entries (ids, xy, t) or None].  A push every 5 ticks, the grid anchored at the first; stream 0 leaves out
+    the pushes at 20, 40 and 60, so those instants are resolved 5 ticks late from the bracket around them (interpolated)
+    and the instants 10, 30, 50 from a sample (exact).  Stream 0 holds 264 ids in every push, shuffled, a negative one
+    and one above 2^32 among them: the slots 0 .. 263; from the third push on, every third push brings one more id, seen
+    twice, that takes the lowest free slot from 264 up (live, never complete); the last slots stay free.  Stream 1, on
+    its own clock, holds five ids, is pushed every time but once, and only ever sees exact frames."""
+    gen = np.random.default_rng(seed)
+    crowd = list(range(1, 263)) + [-5, (1 << 33) + 7]
+    out = []
+    for n, tt in enumerate(range(0, 70, 5)):
+        ids = crowd + [9000 + k for k in (n - 1, n) if k >= 2 and k % 3 == 2]
+        ids = np.array(ids, np.int64)[gen.permutation(len(ids))]
+        few = np.array([3, (1 << 33) + 8, 50, 51, 52], np.int64)[gen.permutation(5)]
+        tick = []
+        for i, t0, skip in ((ids, 0, tt in (20, 40, 60)), (few, CLOCK0[1], tt == 35)):
+            base = np.stack([(i % 17).astype(np.float64) - 8.0, (i % 5).astype(np.float64)], 1)
+            vel = np.stack([0.01 + (i % 7) * 0.003, -0.02 + (i % 3) * 0.011], 1)
+            tick.append(None if skip else (i, base + vel * tt + gen.normal(0.0, 0.002, size=(len(i), 2)), t0 + tt))
+        out.append(tick)
+    return out
+
+
+def wide_facts(h, slot_of, t_all, window):
+    """Stream 0 behind a tick of wide_feed: h its TimedHistory, slot_of {id: slot} of the tracks the state holds, window:
+    did the tick append a window of it -> (a row of that window past slot 255, such a row with an interpolated frame, a
+    live slot past 255 that is no candidate together with a free one)."""
+    past = {k: s for k, s in slot_of.items() if s >= 256 and k >= 0}
+    cand = [k for k in past if len(h.runs.get(k, [])) == t_all]
+    free = WIDE_S - 256 - sum(s >= 256 for s in slot_of.values())
+    return (window and bool(cand), window and any(any(h.lerped[k]) for k in cand), len(cand) < len(past) and free > 0)
+
+
+def wide_reached(hv, facts):
+    """What the second-pass feed has to reach: a window, and each of wide_facts at some tick."""
+    return int(hv.log.header[0]) >= 1 and int(hv.log.header[2]) == 0 and all(any(f[i] for f in facts) for i in range(3))
+
+
+def wide_run(feed, t_obs=3, t_all=5, r=4, step=10, max_dt=10, settle=0, caps=(16, 1024)):
+    """wide_feed through the timed track statement and the harvest, the slots handed out as the push hands them out
+    (a new id, in detection order, takes the lowest free slot; a forgotten track frees its own) -> (TimedHarvester,
+    wide_facts per tick)."""
+    tracks = [StreamModelTimed(t_obs, step, max_dt, r, max_peds=WIDE_S, capacity=WIDE_S) for _ in range(WIDE_NS)]
+    hv = TimedHarvester(WIDE_NS, t_all, step, max_dt, settle, *caps)
+    slot_of, facts = {}, []
+    for tick in feed:
+        states = {}
+        for b, d in enumerate(tick):
+            if d is not None:
+                assert tracks[b].push(*d)[3] == 0
+                states[b] = (tracks[b].state()[0], d[2], True)
+        if 0 in states:
+            slot_of = {k: s for k, s in slot_of.items() if k in states[0][0]}
+            for k in tick[0][0].tolist():
+                if k not in slot_of:
+                    slot_of[k] = min(set(range(WIDE_S)) - set(slot_of.values()))
+        before = int((hv.log.tags[:, 0] == 0).sum())
+        hv.tick(states)
+        facts.append(wide_facts(hv.hist[0], slot_of, t_all, int((hv.log.tags[:, 0] == 0).sum()) > before))
+    return hv, facts
+
+
 def run_scripted(feed, t_obs, t_all, max_dt, settle, history, caps=(4096, 1 << 16), step=10, capacity=16, min_peds=2):
     """The scripted feed through the timed track statement and the harvest -> (TimedHarvester, the OR of the flags)."""
     tracks = [StreamModelTimed(t_obs, step, max_dt, history, capacity=capacity) for _ in range(NS)]

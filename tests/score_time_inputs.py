@@ -98,6 +98,40 @@ def edge_script(s, p, v, k, empty_scenes=False, n_push=12):
     return out
 
 
+def ring2_script(p, v, k, n_push=26):
+    """One stream for rings of TWO samples: [(t, ids, xy, prediction)] at step 4.  A push is at (cell, phase), t = -20 +
+    4 cell + phase, and moves on by at most one cell: inter-push times 1 to 7, no push passes two grid instants of the
+    harvest (anchored at the first push), and every instant off a push lies in the bracket of the two samples a ring
+    keeps -- behind a gap of 5 or 7 so does an earlier step of the push's own window.  Five ids, id 3 away at pushes
+    4-5.  The scene of a prediction: the push's ids, last detection first."""
+    moves = [(1, 0), (0, 3), (1, 2), (1, 3), (1, 0), (1, 3), (1, 1), (0, 2), (1, 0), (1, 1), (1, 3), (1, 2)]
+    cell, times = 0, [-20]
+    for n in range(n_push - 1):
+        cell += moves[n % len(moves)][0]
+        times.append(-20 + 4 * cell + moves[n % len(moves)][1])
+    assert all(0 < b - a <= MAX_DT for a, b in zip(times, times[1:]))
+    out = []
+    for n, t in enumerate(times):
+        ids = [i for i in (1, 2, 3, 4, BIG + 5) if not (i == 3 and n in (4, 5))]
+        out.append((t, np.array(ids, np.int64), np.array([pos(i, t) for i in ids], np.float64).reshape(-1, 2),
+                    exact_prediction(list(reversed(ids)), t, p, v, k)))
+    return out
+
+
+def interpolated_in_scene(scene, tracks, t, t_obs=T_OBS, step=STEP):
+    """How many observed positions of a push's scene (StreamModelTimed.push's result) are at no sample's instant."""
+    ids, _, seen, _ = scene
+    return sum(1 for i, m in zip(ids.tolist(), seen.tolist()) for j in range(t_obs)
+               if (m >> j) & 1 and not any(tt == t - j * step for tt, _, _ in tracks[i]))
+
+
+def interpolated_in_records(rows, times, step=STEP):
+    """How many matched entries of the records in a TimedScoreModel's ring were scored between two pushes: their instant
+    t_r + h step is no push's time."""
+    return sum(int(rec["matched"][h - 1].sum()) for rec in rows if rec is not None
+               for h in range(1, rec["matched"].shape[0] + 1) if rec["t"] + h * step not in times)
+
+
 class StreamRef:
     """One stream restated: the timed push and the score behind it."""
 
@@ -107,8 +141,9 @@ class StreamRef:
         self.score = TimedScoreModel(p, v, k, step, max_dt, pending, thr, decimals, dtype, truth32)
 
     def push(self, t, ids, xy, pred):
-        """-> (the push's flags, {push_totals, push_traj})."""
-        flags = self.track.push(ids, xy, t)[3]
+        """-> (the push's flags, {push_totals, push_traj}); self.scene: what the push returned."""
+        self.scene = self.track.push(ids, xy, t)
+        flags = self.scene[3]
         return flags, self.score.push(self.track.tracks, t, pred, refused=bool(flags & TIME_ORDER))
 
     def idle(self):

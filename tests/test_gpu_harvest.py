@@ -64,12 +64,13 @@ class _Rig:
     """The track state of NS streams and the harvest's history, log and scratch, all pre-filled: the log with 7s, so a
     store past the fill point shows."""
 
-    def __init__(self, dev, t_obs, t_all, cap_w, cap_r, lead=(NS,)):
+    def __init__(self, dev, t_obs, t_all, cap_w, cap_r, lead=(NS,), S=S):
         z = lambda shape, dt: torch.zeros(shape, device=dev, dtype=dt)      # noqa: E731
         self.track = (torch.full(lead + (S,), -1, device=dev, dtype=torch.int64), z(lead + (S,), torch.int32),
                       z(lead + (t_obs, S, 2), torch.float64), z(lead + (2,), torch.int32))
         self.hist = (z(lead + (S,), torch.int32), z(lead + (t_all, S, 2), torch.float64), z(lead + (2,), torch.int32))
-        self.work = z(NS * (S + 3), torch.int32)
+        self.ns = lead[0]
+        self.work = z(self.ns * (S + 3), torch.int32)
         self.log = (torch.full((cap_r, 2, t_all), 7.0, device=dev), torch.full((cap_w + 1,), -7, device=dev, dtype=torch.int32),
                     torch.full((cap_w, 2), -7, device=dev, dtype=torch.int32), z(3, torch.int32))
         self.log[1][0] = 0
@@ -100,7 +101,7 @@ def _push_streams(rig, tick, dev, t_obs, m_max=32):
 
 def _harvest_streams(rig, track, pushed, min_peds=2):
     from social_stgcnn_amd._lib import check, lib, ptr, stream_ptr
-    check(lib().stg_window_harvest_streams(*map(ptr, track), ptr(pushed), NS, *rig.dims, min_peds, *map(ptr, rig.hist),
+    check(lib().stg_window_harvest_streams(*map(ptr, track), ptr(pushed), rig.ns, *rig.dims, min_peds, *map(ptr, rig.hist),
                                            ptr(rig.work), *map(ptr, rig.log), *rig.caps, stream_ptr()),
           "stg_window_harvest_streams")
 
@@ -151,6 +152,43 @@ def test_both_entry_points_equal_the_restatement(dev, t_obs, t_all, ticks, caps)
         assert dropped > 0 and n_w < caps[0] and n_r <= caps[1]    # full by rows
     # the positions behind the rows: every ring row a word calls detected equals the restatement's
     ring = streams.hist[1].cpu().numpy()
+    for b, h in enumerate(ref.hist):
+        for back in range(t_all):
+            on = ((h.word >> back) & 1) == 1
+            assert np.array_equal(ring[b, (h.row - back) % t_all][on], h.ring[(h.row - back) % t_all][on])
+
+
+def test_a_second_pass_over_the_slots(dev):
+    """272 slots for the 256 threads of the workgroup: the pass over the slots runs twice, the second time ragged, with
+    candidates in it whose rank goes on from the first pass's count.  harvest_np.wide_script through both entry points,
+    the track state written straight into the state tensors from harvest_np.TrackModel (the harvest reads nothing
+    else): words, head, log and header bit for bit after every tick, lone calls against the streams call; the
+    conditions (tests/test_harvest_cpu.py holds them without a GPU) on the statement itself."""
+    t_obs, t_all, caps = 3, 5, (16, 1024)
+    streams, lone = (_Rig(dev, t_obs, t_all, *caps, lead=(H.WIDE_NS,), S=H.WIDE_S) for _ in range(2))
+    ids, words, windows = [], [], []
+    for t, (tick, states, ref, slots) in enumerate(H.wide_ticks(H.wide_script(), t_obs, t_all, caps)):
+        if t == 0:                                                # (the log is empty until tick 4)
+            ref.log.rel_all[:], ref.log.win_start[1:], ref.log.win_tag[:] = 7.0, -7, -7
+        slot_id, mask, pos = (np.stack([s[i] for s in states]) for i in range(3))
+        for x, host in zip(streams.track, (slot_id, mask.astype(np.int32), pos)):
+            x.copy_(torch.from_numpy(host).to(dev))
+        streams.track[3][:, 0] = torch.tensor([s[3] for s in states], dtype=torch.int32).to(dev)
+        pushed = torch.tensor([int(d is not None) for d in tick], dtype=torch.int32).to(dev)
+        _harvest_streams(streams, streams.track, pushed)
+        for b in range(H.WIDE_NS):
+            if tick[b] is not None:
+                _harvest_lone(lone, streams.track, b)
+        for got, want in zip(streams.log, _np_log(ref)):
+            assert got.cpu().numpy().tobytes() == want.tobytes(), t
+        assert np.array_equal(streams.hist[0].cpu().numpy(), np.stack([h.word for h in ref.hist])), t
+        assert np.array_equal(streams.hist[2].cpu().numpy(), np.array([[h.row, h.pushes] for h in ref.hist])), t
+        assert streams.same_log(lone) and all(torch.equal(a, b) for a, b in zip(streams.hist, lone.hist)), t
+        ids.append(states[0][0].copy())
+        words.append(ref.hist[0].word.copy())
+        windows.append(slots)
+    assert H.wide_conditions(ids, words, ref.hist[0].full, windows)
+    ring = streams.hist[1].cpu().numpy()                          # the positions behind the rows, as above
     for b, h in enumerate(ref.hist):
         for back in range(t_all):
             on = ((h.word >> back) & 1) == 1

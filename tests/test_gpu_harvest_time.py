@@ -33,13 +33,14 @@ class _Rig:
     """The timed track state of NS streams and the harvest's history, log and scratch; the log pre-filled with 7s, so a
     store past the fill point shows."""
 
-    def __init__(self, dev, r, t_obs, t_all, max_dt, settle, cap_w, cap_r):
+    def __init__(self, dev, r, t_obs, t_all, max_dt, settle, cap_w, cap_r, NS=NS, S=S):
         z = lambda shape, dt: torch.zeros(shape, device=dev, dtype=dt)      # noqa: E731
         self.track = (torch.full((NS, S), -1, device=dev, dtype=torch.int64), z((NS, S, r), torch.int64),
                       z((NS, S, r, 2), torch.float64), z((NS, S, 2), torch.int32), z((NS, 2), torch.int64),
                       z((NS, 2), torch.int32))
         self.hist = (z((NS, S), torch.int32), z((NS, t_all, S, 2), torch.float64), z((NS, 2), torch.int32),
                      z((NS, 3), torch.int64))
+        self.ns, self.s = NS, S
         self.work = z(NS * (S + 3), torch.int32)
         self.log = (torch.full((cap_r, 2, t_all), 7.0, device=dev), torch.full((cap_w + 1,), -7, device=dev, dtype=torch.int32),
                     torch.full((cap_w, 2), -7, device=dev, dtype=torch.int32), z(3, torch.int32))
@@ -47,12 +48,13 @@ class _Rig:
         self.r, self.t_obs, self.t_all, self.max_dt, self.settle, self.caps = r, t_obs, t_all, max_dt, settle, (cap_w, cap_r)
 
     def sizes(self):
-        return (S, self.r, self.t_obs, self.t_all, 2, ctypes.c_double(1e4), STEP, self.max_dt, self.settle)
+        return (self.s, self.r, self.t_obs, self.t_all, 2, ctypes.c_double(1e4), STEP, self.max_dt, self.settle)
 
 
 def _push_streams(rig, tick, dev, m_max=32):
     """stg_track_push_streams_timed on one tick -> (pushed, the per-stream flags)"""
     from social_stgcnn_amd._lib import check, lib, ptr, stream_ptr
+    NS, S = rig.ns, rig.s
     counts = [0 if d is None else len(d[0]) for d in tick]
     start = torch.tensor(np.concatenate([[0], np.cumsum(counts)]), dtype=torch.int32).to(dev)
     pushed = torch.tensor([int(d is not None) for d in tick], dtype=torch.int32).to(dev)
@@ -73,7 +75,7 @@ def _push_streams(rig, tick, dev, m_max=32):
 
 def _harvest_streams(rig, track, pushed):
     from social_stgcnn_amd._lib import check, lib, ptr, stream_ptr
-    check(lib().stg_window_harvest_streams_timed(*map(ptr, track), ptr(pushed), NS, *rig.sizes(), *map(ptr, rig.hist),
+    check(lib().stg_window_harvest_streams_timed(*map(ptr, track), ptr(pushed), rig.ns, *rig.sizes(), *map(ptr, rig.hist),
                                                  ptr(rig.work), *map(ptr, rig.log), *rig.caps, stream_ptr()),
           "stg_window_harvest_streams_timed")
 
@@ -125,6 +127,40 @@ def test_both_entry_points_equal_the_statement(dev, t_obs, t_all, pushes, r, max
         assert dropped > 0 and n_w == caps[0] and n_r < caps[1]    # full by windows
     elif r == 64:
         assert dropped > 0 and n_w < caps[0] and n_r <= caps[1]    # full by rows
+
+
+def test_a_second_pass_over_the_slots(dev):
+    """272 slots for the 256 threads of the workgroup, rings of 4: the pass over the slots runs twice, the second time
+    ragged, with candidates in it whose rank goes on from the first pass's count and whose frames are searched and
+    interpolated there.  harvest_time_np.wide_feed through the real push (M_max 272) and both entry points, against the
+    statement fed the decoded device state, as above; the conditions (tests/test_harvest_time_cpu.py holds them without
+    a GPU) on the statement, with the slots the device handed out."""
+    t_obs, t_all, r, max_dt, caps = 3, 5, 4, 10, (16, 1024)
+    streams, lone = (_Rig(dev, r, t_obs, t_all, max_dt, 0, *caps, NS=HT.WIDE_NS, S=HT.WIDE_S) for _ in range(2))
+    ref = HT.TimedHarvester(HT.WIDE_NS, t_all, STEP, max_dt, 0, *caps)
+    ref.log.rel_all[:], ref.log.win_start[1:], ref.log.win_tag[:] = 7.0, -7, -7
+    facts = []
+    for n, tick in enumerate(HT.wide_feed()):
+        pushed, flags = _push_streams(streams, tick, dev, m_max=HT.WIDE_S)
+        assert not np.bitwise_or.reduce(flags) & (OVERFLOW | TIME_ORDER), n
+        _harvest_streams(streams, streams.track, pushed)
+        for b in range(HT.WIDE_NS):
+            if tick[b] is not None:
+                _harvest_lone(lone, streams.track, b)
+        host = [x.cpu().numpy() for x in streams.track]
+        before = int((ref.log.tags[:, 0] == 0).sum())
+        ref.tick({b: (HT.decode_tracks(*(x[b] for x in host[:4])), int(host[4][b, 0]), True)
+                  for b in range(HT.WIDE_NS) if tick[b] is not None})
+        for got, want in zip(streams.log, (ref.log.rel_all, ref.log.win_start, ref.log.win_tag, ref.log.header)):
+            assert got.cpu().numpy().tobytes() == want.tobytes(), n
+        word, ring, head, clock = (x.cpu().numpy() for x in streams.hist)
+        for b, h in enumerate(ref.hist):
+            assert head[b].tolist() == h.head and clock[b].tolist() == h.clock, (n, b)
+            assert HT.same_runs(HT.canonical(host[0][b], word[b], ring[b], head[b], t_all), h.runs), (n, b)
+        assert all(torch.equal(a, b) for a, b in zip(streams.log + streams.hist, lone.log + lone.hist)), n
+        slot_of = {int(k): s for s, k in enumerate(host[0][0]) if host[3][0, s, 1] > 0}
+        facts.append(HT.wide_facts(ref.hist[0], slot_of, t_all, int((ref.log.tags[:, 0] == 0).sum()) > before))
+    assert HT.wide_reached(ref, facts) and int(ref.log.header[0]) == 6
 
 
 def test_every_refusal_launches_nothing(dev):

@@ -61,11 +61,10 @@ class Harness:
     score launch for the tick -- stg_score_push_streams_timed, or stg_score_push_timed with single=True and ns = 1 --
     beside one sti.StreamRef per stream.  tick(entries): entries[s] = None (not pushed) or (t, ids, xy, prediction)."""
 
-    def __init__(self, dev, ns, p, v, k, thr, pending, r, single=False, m_max=sti.M_MAX):
+    def __init__(self, dev, ns, p, v, k, thr, pending, r, single=False, m_max=sti.M_MAX, s=sti.SLOTS):
         from social_stgcnn_amd import ops
         self.ops, self.dev, self.ns, self.p, self.v, self.k, self.single = ops, dev, ns, p, v, k, single
         z = lambda shape, dt: torch.zeros(shape, device=dev, dtype=dt)      # noqa: E731
-        s = sti.SLOTS
         self.tracks = (torch.full((ns, s), -1, device=dev, dtype=torch.int64), z((ns, s, r), torch.int64),
                        z((ns, s, r, 2), torch.float64), z((ns, s, 2), torch.int32), z((ns, 2), torch.int64),
                        z((ns, 2), torch.int32))
@@ -77,7 +76,8 @@ class Harness:
             self.push.append(c)
         self.state = ops.score_timed_state(ns, p, v, k, pending, dev, samples=k > 0, q=len(thr))
         self.thr = torch.tensor(list(thr), dtype=torch.float32).to(dev) if len(thr) else None
-        self.refs = [sti.StreamRef(p, v, k, thr, pending, r, m_max=m_max) for _ in range(ns)]
+        self.refs = [sti.StreamRef(p, v, k, thr, pending, r, m_max=m_max, slots=s) for _ in range(ns)]
+        self.scenes = [None] * ns                               # what each stream's last push returned on the device
 
     def snapshot(self):
         return {n: None if x is None else x.cpu().numpy() for n, x in zip(self.state._fields, self.state)}
@@ -96,7 +96,8 @@ class Harness:
                 flags.append(None)
                 continue
             t, d_ids, d_xy, pr = e
-            f = self.push[s].push(d_ids, d_xy, t)[4]
+            self.scenes[s] = self.push[s].push(d_ids, d_xy, t)
+            f = self.scenes[s][4]
             f_ref, added = self.refs[s].push(t, d_ids, d_xy, pr)
             assert f == f_ref, (s, t, f, f_ref)
             flags.append(f)
@@ -234,6 +235,55 @@ def test_edge_shapes_are_bit_exact(dev, case, single):
     row = (int(h.state.counters[0, 0]) - 1) % 4
     assert int(h.state.counters[0, 0]) == 13
     _assert_cov(h.state.rec_cov[0, row].cpu().numpy(), last[3], case)
+
+
+def test_a_ring_of_two_through_the_push_the_harvest_and_the_score(dev):
+    """R = 2, the smallest ring: the search sees at most one old sample, and "the sample before the newest" is the slot
+    the push has just overwritten -- the edge of every helper of time_samples.hpp.  S 16, V 8, P 3, K 2, T_obs 8, step 4,
+    max_dt 8; the harvest with windows of 9 frames, settle 0.  score_time_inputs.ring2_script through
+    stg_track_push_timed, stg_window_harvest_timed and stg_score_push_timed, each against its statement bit for bit
+    after every push: the scene, the decoded rings, the history, clock and log, what the score added and, every fourth
+    push, its whole ring.  The statements hold interpolated scene positions, entries scored between two pushes and
+    harvested windows with interpolated frames."""
+    import ctypes
+    import harvest_time_np as HT
+    from social_stgcnn_amd._lib import check, lib, ptr, stream_ptr
+    p, v, k, thr, s, t_all, caps = 3, 8, 2, (0.75, 3.0), 16, 9, (32, 256)
+    h = Harness(dev, 1, p, v, k, thr, 4, 2, single=True, s=s)
+    ref = h.refs[0]
+    z = lambda shape, dt: torch.zeros(shape, device=dev, dtype=dt)      # noqa: E731
+    hist = (z(s, torch.int32), z((t_all, s, 2), torch.float64), z(2, torch.int32), z(3, torch.int64))
+    log = (torch.full((caps[1], 2, t_all), 7.0, device=dev), torch.full((caps[0] + 1,), -7, device=dev, dtype=torch.int32),
+           torch.full((caps[0], 2), -7, device=dev, dtype=torch.int32), z(3, torch.int32))
+    log[1][0] = 0
+    hv = HT.TimedHarvester(1, t_all, sti.STEP, sti.MAX_DT, 0, *caps)
+    hv.log.rel_all[:], hv.log.win_start[1:], hv.log.win_tag[:] = 7.0, -7, -7
+    script = sti.ring2_script(p, v, k)
+    in_scene = 0
+    for n, (t, ids, xy, pred) in enumerate(script):
+        assert h.tick([(t, ids, xy, pred)]) == [0], n            # the push, then the score: what it added
+        out_ids, peds, obs, seen, _ = h.scenes[0]
+        want = ref.scene
+        assert peds == len(want[0]) and np.array_equal(out_ids[:peds], want[0]) and np.array_equal(seen[:peds], want[2]), n
+        assert obs[:, :peds].tobytes() == want[1].tobytes(), n
+        in_scene += sti.interpolated_in_scene(want, ref.track.tracks, t)
+        check(lib().stg_window_harvest_timed(*(ptr(x[0]) for x in h.tracks), s, 2, sti.T_OBS, t_all, 2, ctypes.c_double(1e4),
+                                             sti.STEP, sti.MAX_DT, 0, 0, *map(ptr, hist), *map(ptr, log), *caps,
+                                             stream_ptr()), "stg_window_harvest_timed")
+        host = [x[0].cpu().numpy() for x in h.tracks]
+        tracks = HT.decode_tracks(*host[:4])
+        assert tracks == ref.track.tracks and all(len(smp) <= 2 for smp in tracks.values()), n
+        hv.tick({0: (tracks, t, True)})
+        for got, wanted in zip(log, (hv.log.rel_all, hv.log.win_start, hv.log.win_tag, hv.log.header)):
+            assert got.cpu().numpy().tobytes() == wanted.tobytes(), n
+        word, ring, head, clock = (x.cpu().numpy() for x in hist)
+        assert head.tolist() == hv.hist[0].head and clock.tolist() == hv.hist[0].clock, n
+        assert HT.same_runs(HT.canonical(host[0], word, ring, head, t_all), hv.hist[0].runs), n
+        if n % 4 == 3:
+            h.assert_state(n)
+    h.assert_state("end")
+    assert in_scene > 0 and sti.interpolated_in_records(ref.score.rows, [e[0] for e in script]) > 0
+    assert int(hv.log.header[0]) >= 1 and int(hv.log.header[2]) == 0 and hv.hist[0].interpolated > 0
 
 
 # ---- 2. the anchor on the device ---------------------------------------------------------------------------------

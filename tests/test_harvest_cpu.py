@@ -156,6 +156,20 @@ def test_slot_reuse_and_overflow_never_join_two_pedestrians():
     assert np.array_equal(second[0], np.array([0, .5, .5, .5, .5], np.float32))
 
 
+def test_the_wide_feed_reaches_what_the_gpu_test_needs():
+    """272 slots, more than a harvest workgroup has threads: windows from tick 4 on with rows past slot 255, a live slot
+    that is no candidate and a free slot past 255, windows of both streams, nothing dropped."""
+    ids, words, windows = [], [], []
+    for _, states, hv, slots in H.wide_ticks(H.wide_script()):
+        ids.append(states[0][0].copy())
+        words.append(hv.hist[0].word.copy())
+        windows.append(slots)
+    assert H.wide_conditions(ids, words, hv.hist[0].full, windows)
+    assert [w is not None for w in windows] == [False] * 4 + [True] * 3 and all(len(w) == 263 for w in windows[4:])
+    assert hv.log.header.tolist() == [5, 3 * 263 + 2 * 5, 0] and hv.log.tags.tolist() == [[0, 4], [0, 5], [1, 4], [0, 6], [1, 5]]
+    assert not H.wide_conditions(ids, words, hv.hist[0].full, [None] * 7)
+
+
 # ---- 3. the spec and the refusals ---------------------------------------------------------------------------------------
 def test_harvest_spec_checks():
     from social_stgcnn_amd.frames import HarvestSpec

@@ -210,6 +210,18 @@ def test_the_scripted_feed_reaches_what_the_gpu_test_needs(t_obs, t_all, pushes,
     assert int(shallow.log.header[0]) < int(runs[max_dt - 1].log.header[0])
 
 
+def test_the_wide_feed_reaches_what_the_gpu_test_needs():
+    """272 slots, more than a harvest workgroup has threads: three windows of 263 rows of stream 0, each with rows past
+    slot 255 that hold interpolated frames, beside a live slot that is no candidate and a free one past 255; three
+    windows of stream 1 without an interpolated frame."""
+    hv, facts = HT.wide_run(HT.wide_feed())
+    assert HT.wide_reached(hv, facts) and not HT.wide_reached(hv, [(False,) * 3] * len(facts))
+    assert hv.log.tags.tolist() == [[1, 4], [0, 4], [0, 5], [1, 5], [1, 6], [0, 6]]
+    assert hv.log.num_peds.tolist() == [5, 263, 263, 5, 5, 263]
+    assert hv.hist[0].interpolated == 263 * (2 + 2 + 3) and hv.hist[1].interpolated == 0
+    assert [h.clock for h in hv.hist] == [[1, 0, 0], [1, HT.CLOCK0[1], 0]]
+
+
 def _frames60(d, f):
     from live_inputs import _pushes, _rows
     return _pushes(_rows(d, f))[:60]

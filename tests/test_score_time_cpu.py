@@ -192,6 +192,24 @@ def _run_script(s, p, v, k, pending, r, thr=(0.75, 3.0, 8.0)):
     return ref, flags
 
 
+def test_the_ring_of_two_script_reaches_what_the_gpu_test_needs():
+    """Rings of two samples through the three statements: scene positions, scored entries and harvested frames that are
+    interpolated from the only bracket such a ring holds, and windows of nine frames in the log."""
+    import harvest_time_np as HT
+    p, v, k = 3, 8, 2
+    ref = sti.StreamRef(p, v, k, (0.75, 3.0), 4, 2, slots=16)
+    hv = HT.TimedHarvester(1, 9, sti.STEP, sti.MAX_DT, 0, 32, 256)
+    script = sti.ring2_script(p, v, k)
+    in_scene = 0
+    for t, ids, xy, pred in script:
+        assert ref.push(t, ids, xy, pred)[0] == 0
+        assert all(len(smp) <= 2 for smp in ref.track.tracks.values())
+        in_scene += sti.interpolated_in_scene(ref.scene, ref.track.tracks, t)
+        hv.tick({0: (ref.track.state()[0], t, True)})
+    assert in_scene == 38 and sti.interpolated_in_records(ref.score.rows, [e[0] for e in script]) == 15
+    assert hv.log.header.tolist() == [14, 64, 0] and hv.hist[0].interpolated > 0 and hv.hist[0].clock == [1, -20, 0]
+
+
 def test_scripts_reach_their_branches():
     """What test_gpu_score_time.py relies on, checked where it is cheap: the exact scripts reach every branch of the
     rule, and their distances are exact in float32 (the float64 restatement gives the same numbers)."""
